@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- RTS hot path on MI355X: Mrays/s and ms/pulse on the BASELINE.json metric config.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value, unit, ms_per_step, ...).  Everything
+else it can measure or check -- the roofline block and the un-timed launches behind it, the CPU baseline, the range-Doppler check
+against torch.fft, the secondary intervals of an N > 1 job -- runs with --full only.  --dump-outputs DIR writes what the timed path
+returned in its last step as float64 .npy files (see dump_outputs); the inputs are seeded, so two builds compare output for output.
 
 Workload (config.workload): BASELINE.json configs[2] -- aircraft-like 100 000-triangle mesh, 1 Tx / 4 Rx, W = 216
 (10 077 696 launch indices per pulse), maxRefl = 6; the configuration the metric ("Mrays/s ... 100k-tri scene") is quoted
@@ -28,13 +33,13 @@ running each rank's plan of a 20-pulse interval in turn (profiles/r05d_as_rank_p
 12-14 ms ray-sharded on configs[2] (11.9 ms on one GPU), 34-45 / 30-68 ms on configs[3] (110 ms): a part of a pulse is a launch of another shape
 whose tile schedule starts from nothing, and an eighth of a configs[2] pulse is 0.08 ms of tracing against a 0.07 ms empty launch.
 Either way the per-(receiver, path) group tables are exchanged once per interval (one all-gather over RCCL) and the complex return
-cube is summed once (one all-reduce), both inside the timed region.  The same job then measures, outside that region and reported
+cube is summed once (one all-reduce), both inside the timed region.  With --full the same job then measures, outside that region and reported
 as secondary blocks: `weak` -- every rank --steps whole pulses (an N x steps interval; per-GPU work as at N = 1, no collective in the
 data path) -- and `n1` -- rank 0 ALONE tracing the strong interval's --steps pulses while the others wait at a barrier --, from
 which `efficiency_vs_n1` = value / (N x n1.value): the line is self-contained.  (--scaling weak makes the weak interval the
 headline, as round 4 did.)
 
-roofline: the trace kernel moves ~150 MB of HBM per launch against >10 GB of cache-served traversal bytes, so HBM is not
+roofline (--full): the trace kernel moves ~150 MB of HBM per launch against >10 GB of cache-served traversal bytes, so HBM is not
 its bound (reported as secondary fields).  What binds is instruction issue: `bound` names the busier of the two per-CU
 pipes measured with rocprofv3 counters on this binary and workload (profiles/<tag>_pmc_<workload>.json, produced by
 tools/pmc_collect.sh + tools/pmc_derive.py): VALU issue and the vector-memory return path.  VALU issue is priced with
@@ -173,6 +178,32 @@ def cpu_baseline(spec, seconds_target=12.0):
                        % (what, seg, dt, threads, cpu_model()))
 
 
+DUMP_RD_BYTES = 48 << 20        # --dump-outputs: the range-Doppler map's share of the 64 MB; a larger map is written as a strided sample
+
+
+def dump_outputs(dirname, resp, cube, dop):
+    """--dump-outputs: what the timed path handed its caller in its last step, as float64 .npy files --
+    responses_<field>.npy: the last pulse's responses (RESPONSE_DTYPE, one file per field, in the order the library returned them);
+    cube_last_pulse.npy: that pulse's row of the return cube, [rx][bin][re, im];
+    range_doppler.npy: the interval's range-Doppler map (the interval's tail runs in the last step), [rx][doppler bin][range bin][re, im],
+    or, above DUMP_RD_BYTES, every s-th complex value of it flattened in that order ([n][re, im], s the smallest stride that fits)"""
+    import torch
+    if not resp:
+        return
+    os.makedirs(dirname, exist_ok=True)
+    last = max(resp)
+    r = resp[last][0]
+    for f in r.dtype.names:
+        np.save(os.path.join(dirname, "responses_%s.npy" % f), r[f].astype(np.float64))
+    np.save(os.path.join(dirname, "cube_last_pulse.npy"), torch.view_as_real(cube[:, last, :]).cpu().numpy().astype(np.float64))
+    if dop is not None:
+        rd = torch.view_as_real(dop).cpu().numpy().astype(np.float64)
+        if rd.nbytes > DUMP_RD_BYTES:
+            stride = (rd.nbytes + DUMP_RD_BYTES - 1) // DUMP_RD_BYTES
+            rd = rd.reshape(-1, 2)[::stride]
+        np.save(os.path.join(dirname, "range_doppler.npy"), rd)
+
+
 def load_pmc(workload):
     p = os.path.join(ROOT, "profiles", "%s_pmc_%s.json" % (PMC_TAG, workload))
     if not os.path.exists(p):
@@ -200,6 +231,8 @@ def main():
     ap.add_argument("--shard", default="auto", choices=["auto", "pulses", "whole", "rays"], help="N > 1, the strong interval: 'whole' = whole pulses only, contiguous runs, some ranks one pulse more; 'pulses' = whole pulses and each left-over pulse split over a group of ranks; 'rays' = every pulse split over all ranks (tiles dealt by cost).  auto: see the top of this file")
     ap.add_argument("--no-secondary", action="store_true", help="N > 1: skip the secondary intervals (weak / strong counterpart and rank 0 alone)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="gloo: rehearsal of the N > 1 path on a box with fewer GPUs than ranks")
+    ap.add_argument("--full", action="store_true", help="after the timed interval also measure and check what the headline does not need: the secondary intervals of an N > 1 job, the serial / counting / dense launches and the roofline, the range-Doppler check against torch.fft, the CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the timed path returned in its last step to DIR/<name>.npy (float64, at most 64 MB in all)")
     args = ap.parse_args()
 
     # stdout carries the JSON line and nothing else: whatever a library prints there (RCCL's version banner under torch.distributed.run
@@ -546,21 +579,25 @@ def main():
     # ---- the line's interval
     acc, resp, dt = timed_interval(n_int, n_warm, cur["shard"], plan_rank, plan_world)
     headline = dict(scaling=args.scaling, shard=cur["shard"], n_int=n_int, deal=dict(dealt) if dealt else None)
-    # range-Doppler map of the interval (slow-time FFT of the summed cube): a check of the dense product, outside the timed
-    # region -- the hot path ends with the per-pulse responses and the (all-reduced) cube
-    # (the transform itself ran inside the timed region, in the interval's tail: rts_cube_doppler; here it is checked against torch.fft)
-    ref_rd = torch.fft.fft(cube, n=n_fft, dim=1) if dop is not None else torch.fft.fft(cube, dim=1)
-    range_doppler_peak = float((dop if dop is not None else ref_rd).abs().max().item()) if args.steps > 0 else 0.0
-    range_doppler_err = float((dop - ref_rd).abs().max().item() / max(float(ref_rd.abs().max().item()), 1e-300)) if dop is not None else None
-    assert range_doppler_err is None or range_doppler_err < 1e-9, "rts_cube_doppler disagrees with torch.fft (%g)" % range_doppler_err
-    cube_desc = "complex128 [%d rx][%d pulses][%d bins], all-reduced once per interval, then %d-point slow-time FFT in the library (rts_cube_doppler, inside the timed region); range-Doppler peak %.6e, max deviation from torch.fft %.1e (relative)" % (cube.shape[0], cube.shape[1], n_bins, n_fft, range_doppler_peak, range_doppler_err or 0.0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, resp, cube, dop)
+    cube_desc = "complex128 [%d rx][%d pulses][%d bins], all-reduced once per interval, then %d-point slow-time FFT in the library (rts_cube_doppler, inside the timed region)" % (cube.shape[0], cube.shape[1], n_bins, n_fft)
+    if args.full:
+        # range-Doppler map of the interval (slow-time FFT of the summed cube): a check of the dense product, outside the timed
+        # region -- the hot path ends with the per-pulse responses and the (all-reduced) cube
+        # (the transform itself ran inside the timed region, in the interval's tail: rts_cube_doppler; here it is checked against torch.fft)
+        ref_rd = torch.fft.fft(cube, n=n_fft, dim=1) if dop is not None else torch.fft.fft(cube, dim=1)
+        range_doppler_peak = float((dop if dop is not None else ref_rd).abs().max().item()) if args.steps > 0 else 0.0
+        range_doppler_err = float((dop - ref_rd).abs().max().item() / max(float(ref_rd.abs().max().item()), 1e-300)) if dop is not None else None
+        assert range_doppler_err is None or range_doppler_err < 1e-9, "rts_cube_doppler disagrees with torch.fft (%g)" % range_doppler_err
+        cube_desc += "; range-Doppler peak %.6e, max deviation from torch.fft %.1e (relative)" % (range_doppler_peak, range_doppler_err or 0.0)
     seg = acc["segments"]; ms_trace = acc["ms_trace"]; ms_scene = acc["ms_scene"]; ms_post = acc["ms_post"]
     shaded = acc["shaded"]; received = acc["received"]; launches = max(acc["launches"], 1)
     seg_all, shaded_all, received_all = job_sums(acc)              # whole-job aggregates (dt is already the slowest rank's)
 
     # ---- secondary intervals of a multi-rank job: the other scaling mode, and rank 0 alone on the strong interval
     secondary = {}
-    if world > 1 and not args.no_secondary and not args.as_rank:
+    if world > 1 and args.full and not args.no_secondary and not args.as_rank:
         other = "weak" if args.scaling == "strong" else "strong"
         o_int = args.steps * (world if other == "weak" else 1); o_warm = min(args.warmup, 2 * len(trs)) * (world if other == "weak" else 1)
         o_shard = "whole" if other == "weak" else resolve_shard(o_int, world)
@@ -576,7 +613,7 @@ def main():
             strong_value = (seg_all / dt / 1e6) if args.scaling == "strong" else secondary["strong"]["value"]
             secondary["efficiency_vs_n1"] = strong_value / (world * n1_value)
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- un-timed measurements behind the roofline block (rank 0, after the timed region)
         # (1) the SERIAL trace kernel: whole pulses one after the other on one handle; HIP events on the kernel's own stream
         ser = []
@@ -692,6 +729,7 @@ def main():
             roof.update(bound="valu_issue", achieved=None, peak=N_SIMD * PEAK_CLOCK_HZ / 1e9, unit="G SIMD issue cycles/s", frac=None, traffic=None, source_hash=lib_hash,
                         note=("the committed counter profile %s was taken on sources %s, this library is %s: not priced -- run tools/pmc_collect.sh + tools/pmc_derive.py again" % (pmc_src, pmc.get("source_hash"), lib_hash)) if pmc_stale
                         else "no committed counter profile for this configuration (profiles/%s_pmc_*.json cover c3 / c5 at W = 216, c2 at W = 100 and c4 -- transmitter 0 -- at W = 465 on one GPU)" % PMC_TAG)
+    if rank == 0:
         out = {
             "metric": "Mrays/s (primary+bounces) & ms/pulse, 100k-tri scene",
             "value": seg_all / dt / 1e6, "unit": "Mrays/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -700,10 +738,7 @@ def main():
             "config": {"workload": "BASELINE.json configs[%d]%s: %s, 1 Tx / %d Rx, W=%d (%d launch indices/pulse), maxRefl=%d, target moves every pulse (re-placed on the device per pulse; static target-space BVH4)"
                                    % ({"c3": 2, "c3ecef": 2, "c3ico": 2, "c4": 3, "c5": 4}.get(args.config, 1), " at Earth-centred coordinates" if args.config == "c3ecef" else (" (both transmitters in turn: pulses [0, %d) from Tx 0, [%d, %d) from Tx 1; a receiver's noise temperature grows by the signal's once per transmitter, ray_tracer.cpp:829 -- host side, the SOARS adapter's)" % (half_of(), half_of(), args.steps) if two_tx else (" -- NOT a BASELINE configuration: the scene of the C++ boundary benchmark (tests/adapter/adapter_bench.cpp)" if args.config == "sphere6" else (" (target re-rotated and translated every pulse, ray_tracer.cpp:993-1014; the transmitter's boresight tracks it)" if args.config == "c5" else ""))), spec["name"], len(spec["rx"]), W, total, spec["max_refl"]),
                        "rays_per_pulse": total, "pulses_in_the_interval": n_int, "segments_per_pulse": seg_all / max(n_int, 1), "received_per_pulse": received_all / max(n_int, 1),
-                       "hit_fraction": hit_fraction, "bounding_sphere_fraction": sphere_fraction, "primary_Mrays_per_s": total * n_int / dt / 1e6,
-                       "walked_segments_per_pulse": walked_per_pulse, "walked_Mrays_per_s": walked_per_pulse * (seg_all / max(seg_serial * n_int, 1)) * n_int / dt / 1e6,
-                       "walked_note": "segments that entered a target's hierarchy (counting build, one pulse); the rest of segments_per_pulse are primaries the conservative pre-filter or the bounding spheres cleared -- counted as rtTrace calls (SURVEY 8d), but bulk culling, not traversal",
-                       "dense_control_Gseg_per_s": (dense or {}).get("Gseg_per_s"),
+                       "primary_Mrays_per_s": total * n_int / dt / 1e6,
                        "return_cube": cube_desc,
                        "as_rank": args.as_rank or None, "deal": (dict(headline["deal"], how="tiles dealt longest-first from the cost records of the warm-up interval (one all-reduce), rts_deal_tiles") if headline["deal"] else "static interleave") if headline["shard"] == "rays" and plan_world > 1 else None,
                        "sharding": ("%d-pulse interval over %d ranks (--scaling %s: %s), --shard %s -> %s: " % (n_int, world, args.scaling, "--steps pulses per rank" if args.scaling == "weak" else "--steps pulses in all", args.shard, headline["shard"])) + ("every pulse split over all ranks, tiles of 4096 launch indices %s" % ("dealt longest-first from the warm-up interval's cost records" if headline["deal"] else "interleaved") if headline["shard"] == "rays" else ("whole pulses only (contiguous runs, some ranks one pulse more)" if headline["shard"] == "whole" else "whole pulses, left-over pulses in interleaved 4096-index tiles")) + "; one group-table all-gather + one cube all-reduce per interval",
@@ -712,13 +747,16 @@ def main():
                        "interval_tail_ms_rank0": acc["tail_ms"],
                        "host_ms_per_pulse_rank0": {k: v / max(acc["launches"], 1) for k, v in acc["host_ms"].items()},
                        "stage_ms_per_launch_rank0": {"scene_placement": ms_scene / launches, "trace": ms_trace / launches, "order+finalise+aggregate": ms_post / launches}},
-            "roofline": roof,
         }
-        out.update(secondary)                                       # N > 1: "weak" (or "strong"), "n1", "efficiency_vs_n1"
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline(spec)
-        else:
-            out["cpu_baseline"] = None
+        if args.full:
+            out["config"].update({
+                "hit_fraction": hit_fraction, "bounding_sphere_fraction": sphere_fraction,
+                "walked_segments_per_pulse": walked_per_pulse, "walked_Mrays_per_s": walked_per_pulse * (seg_all / max(seg_serial * n_int, 1)) * n_int / dt / 1e6,
+                "walked_note": "segments that entered a target's hierarchy (counting build, one pulse); the rest of segments_per_pulse are primaries the conservative pre-filter or the bounding spheres cleared -- counted as rtTrace calls (SURVEY 8d), but bulk culling, not traversal",
+                "dense_control_Gseg_per_s": (dense or {}).get("Gseg_per_s")})
+            out["roofline"] = roof
+            out.update(secondary)                                   # N > 1: "weak" (or "strong"), "n1", "efficiency_vs_n1"
+            out["cpu_baseline"] = cpu_baseline(spec) if not args.no_cpu_baseline and world == 1 else None
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(out) + "\n").encode())     # the ONE line of this process's real stdout (everything else went to stderr, see main)
     if api._PY_LAP:

@@ -4,11 +4,11 @@
 # settings interleaved and the whole round repeated, then -- with BENCH="cfg:steps:warmup ..." -- the pipelined bench line per setting.
 #   tools/ab_env.sh <tag> "<workloads>" "<setting A>" "<setting B>" [...]        a setting: "NAME=value NAME2=value2", or "-" for none
 #   e.g.  BENCH="c3:64:8 c4:24:12" tools/ab_env.sh r05x_batch_ab "c3 c3empty c4" "RTS_DEAD_BATCH=0" "-"
-# Writes gpurun_out/<tag>.log, its first line the command.  (Rounds 2-5 each grew a dozen one-off *_ab.sh of this shape; they are gone, the logs
+# Writes $OUT/<tag>.log, its first line the command.  (Rounds 2-5 each grew a dozen one-off *_ab.sh of this shape; they are gone, the logs
 # they produced under profiles/ carry their command in the first line -- profiles/README.md.)
-cd "${GRAFT_REPO_ROOT:?}"; mkdir -p gpurun_out
+cd "$(dirname "$0")/.."; mkdir -p "${OUT:=out}"      # OUT: where the logs go (default out/)
 T=$1; W=$2; shift 2
-L=gpurun_out/${T}.log
+L=$OUT/${T}.log
 echo "# BENCH=\"${BENCH:-}\" REPS=${REPS:-12} ROUNDS=${ROUNDS:-2} tools/ab_env.sh $T \"$W\" $(printf '"%s" ' "$@")" > $L
 for round in $(seq 1 ${ROUNDS:-2}); do for w in $W; do for s in "$@"; do
   [ "$s" = "-" ] && e="" || e="$s"
@@ -16,8 +16,8 @@ for round in $(seq 1 ${ROUNDS:-2}); do for w in $W; do for s in "$@"; do
 done; done; done
 for c in ${BENCH:-}; do IFS=: read cfg st wu <<< "$c"; for s in "$@"; do
   [ "$s" = "-" ] && e="" || e="$s"
-  env $e python3 bench.py --no-cpu-baseline --config $cfg --steps $st --warmup $wu ${BENCH_ARGS:-} > gpurun_out/${T}_x.json 2>/dev/null
-  echo "[$s] bench --config $cfg --steps $st --warmup $wu ${BENCH_ARGS:-}: $(python3 tools/bench_line.py gpurun_out/${T}_x.json | cut -c1-120)" >> $L
+  env $e python3 bench.py --full --no-cpu-baseline --config $cfg --steps $st --warmup $wu ${BENCH_ARGS:-} > $OUT/${T}_x.json 2>/dev/null
+  echo "[$s] bench --config $cfg --steps $st --warmup $wu ${BENCH_ARGS:-}: $(python3 tools/bench_line.py $OUT/${T}_x.json | cut -c1-120)" >> $L
 done; done
-rm -f gpurun_out/${T}_x.json
+rm -f $OUT/${T}_x.json
 cat $L
