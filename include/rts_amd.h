@@ -291,6 +291,73 @@ int rts_finalise_uniform(RtsHandle h, const double* rcs_per_target, double wavel
 int rts_trace_pulse_end_uniform(RtsHandle h, const double* rcs_per_target, double wavelength, double gt, double gr,
                                 double carrier, double cspeed, int32_t cube_pulse, uint64_t recv_index_base);
 
+/* ---------------------------------------------------------------- tabulated antenna gain and RCS patterns
+ * The per-received-ray update of ray_tracer.cpp:1198-1253 with the simulator's GetRCS / GetGain answered from tables on the
+ * device instead of host callbacks.
+ *
+ * A pattern is a non-negative function of two angles (u, v), of one of three kinds:
+ *   RTS_PATTERN_CONSTANT   scale, exactly (no arithmetic: the bits of the uniform path).
+ *   RTS_PATTERN_SEPARABLE  scale * Lu(u') * Lv(v').  Lu, Lv piecewise-linear over strictly ascending sample abscissae (n >= 1),
+ *                          clamped to the end values outside the sample range.  u' = |u| if RTS_PATTERN_ABS_U is set, else u;
+ *                          likewise v' with RTS_PATTERN_ABS_V.
+ *   RTS_PATTERN_GRID       scale * bilinear(grid, u, v).  grid row-major [n_v][n_u], samples at (u0 + i du, v0 + j dv),
+ *                          du, dv > 0; coordinates clamped to the grid's range; interpolated in u on rows j and j+1, then in v.
+ * A linear segment is y_i + t * (y_{i+1} - y_i), t = (x - s_i) / (s_{i+1} - s_i) (the library builds with -ffp-contract=off).
+ * wrap(x) = x - 2 pi floor((x + pi) / 2 pi), in [-pi, pi).
+ *
+ * Antennas.  transvec / recvvec as ray_tracer.cpp:1204-1211: direct rays (reflDepth == 0 && refrDepth == 0) transvec =
+ * origin - rx_pos, recvvec = rx_pos - origin (the reference's own sign); all others transvec = firstHitPoint - origin, recvvec =
+ * prevHitPoint - rx_pos.  az = atan2(y, x), el = asin(z / |vec|) (0 for a zero vector); u = wrap(az - r_az), v = el - r_el (no
+ * wrap on v).  Reference direction r: the transmitter's is the traced pulse's tx_dir (= GetRotation(time_t)), origin its
+ * ray_origin; receiver k's is (az_k + az_rate_k * delay, el_k + el_rate_k * delay), delay = rayLength / cspeed -- the
+ * GetRotation(delay + time_t) of :1234-1235 for a constant-rate rotation (az_k, el_k at the pulse time, rates in rad/s).
+ * RCS.  At depth d with targ_d >= 0: target targ_d's pattern at u = wrap(x / 2), v = y / 2, (x, y) the ray's rcs_angle at d
+ * (sums of the in- and out-azimuths and -elevations: the half sums are the bistatic bisector).  Another convention is folded
+ * into the tables (e.g. the square root of a separable product is the product of the per-axis square roots).
+ * Finalised ray, in the operand order of :1225-1247: power *= RCS_d in depth order, then power *= (wl*wl*Gt*Gr); Doppler as
+ * rts_finalise_uniform.  With every pattern CONSTANT the result equals rts_finalise_uniform bit for bit.
+ * Tables are for one wavelength: a caller whose carrier changes sets the patterns again. */
+#define RTS_PATTERN_CONSTANT 0u
+#define RTS_PATTERN_SEPARABLE 1u
+#define RTS_PATTERN_GRID 2u
+#define RTS_PATTERN_ABS_U 1u
+#define RTS_PATTERN_ABS_V 2u
+#define RTS_PATTERN_MAX_AXIS 65536u           /* samples per axis (separable n_u, n_v; grid n_u, n_v)   */
+#define RTS_PATTERN_MAX_GRID 4194304u         /* grid n_u * n_v                                         */
+typedef struct RtsPattern {
+    uint32_t kind;               /* RTS_PATTERN_*                                                        */
+    uint32_t flags;              /* RTS_PATTERN_ABS_U | RTS_PATTERN_ABS_V (SEPARABLE only; 0 otherwise)  */
+    uint32_t n_u, n_v;           /* SEPARABLE: samples per axis; GRID: columns, rows; CONSTANT: unused   */
+    double scale;                /* finite, >= 0                                                         */
+    const double* u_samples;     /* SEPARABLE: [n_u] strictly ascending, finite                          */
+    const double* u_values;      /* SEPARABLE: [n_u] finite, >= 0                                        */
+    const double* v_samples;     /* SEPARABLE: [n_v]                                                     */
+    const double* v_values;      /* SEPARABLE: [n_v]                                                     */
+    double u0, du, v0, dv;       /* GRID: first sample and spacing per axis (finite, du, dv > 0)         */
+    const double* grid;          /* GRID: [n_v][n_u] finite, >= 0                                        */
+    uint64_t reserved[2];        /* 0                                                                    */
+} RtsPattern;
+/* Per-pulse parameters of the pattern finalisation. */
+typedef struct RtsPatternPulse {
+    double wavelength, carrier, cspeed;
+    const double* rx_position;   /* [n_rx][3] receiver positions                                         */
+    const double* rx_rotation;   /* [n_rx][4] az, el at the pulse time, az_rate, el_rate (rad/s)          */
+} RtsPatternPulse;
+/* Validates every table (finite values >= 0, ascending samples, size limits, known kind and flags) -- on failure
+ * RTS_ERR_INVALID and the handle keeps its previous tables -- and packs them into one device buffer of the handle (the caller's
+ * arrays are free on return).  Waits for the handle's enqueued work that may still read the previous tables.
+ * tx: the transmitter; rx[n_rx] one per receiver (in rts_set_receivers order); rcs[n_targets] one per target. */
+int rts_set_patterns(RtsHandle h, const RtsPattern* tx, const RtsPattern* rx, uint32_t n_rx, const RtsPattern* rcs,
+                     uint32_t n_targets);
+/* rts_finalise_uniform with the patterns: same place in the call sequence, same implicit end of a begun pulse.
+ * RTS_ERR_INVALID when no patterns are set, when their n_rx / n_targets differ from the handle's receivers / scene, or when the
+ * handle's received set is not a traced pulse's (e.g. after rts_kernel_wrapper_on). */
+int rts_finalise_patterns(RtsHandle h, const RtsPatternPulse* pulse);
+/* rts_trace_pulse_end_uniform with the pattern finalisation (same speculation, same results as the four calls). */
+int rts_trace_pulse_end_patterns(RtsHandle h, const RtsPatternPulse* pulse, int32_t cube_pulse, uint64_t recv_index_base);
+/* Pure host: validates *p and evaluates it at n points (u[i], v[i]) -> out[i].  No device needed. */
+int rts_pattern_eval(const RtsPattern* p, const double* u, const double* v, uint32_t n, double* out);
+
 /* rts_aggregate: myKernel1 + myKernel2 + unique paths (aggregation.cu:32-97,
  * ray_tracer.cpp:1283-1292) on the device-resident received set, as a sort/group-by.
  * recv_index_base offsets the received-list indices (multi-GPU with contiguous ranges: number of received

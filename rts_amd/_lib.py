@@ -73,6 +73,23 @@ class RtsPlanItem(C.Structure):
 RTS_SHARD_PULSES, RTS_SHARD_RAYS, RTS_SHARD_PULSES_WHOLE = 0, 1, 2
 
 
+RTS_PATTERN_CONSTANT, RTS_PATTERN_SEPARABLE, RTS_PATTERN_GRID = 0, 1, 2
+RTS_PATTERN_ABS_U, RTS_PATTERN_ABS_V = 1, 2
+RTS_PATTERN_MAX_AXIS, RTS_PATTERN_MAX_GRID = 65536, 4194304
+
+
+class RtsPattern(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("flags", C.c_uint32), ("n_u", C.c_uint32), ("n_v", C.c_uint32), ("scale", C.c_double),
+                ("u_samples", C.c_void_p), ("u_values", C.c_void_p), ("v_samples", C.c_void_p), ("v_values", C.c_void_p),
+                ("u0", C.c_double), ("du", C.c_double), ("v0", C.c_double), ("dv", C.c_double), ("grid", C.c_void_p),
+                ("reserved", C.c_uint64 * 2)]
+
+
+class RtsPatternPulse(C.Structure):
+    _fields_ = [("wavelength", C.c_double), ("carrier", C.c_double), ("cspeed", C.c_double),
+                ("rx_position", C.c_void_p), ("rx_rotation", C.c_void_p)]
+
+
 class RtsSceneInfo(C.Structure):
     _fields_ = [("n_targets", C.c_uint32), ("n_prims", C.c_uint32), ("n_nodes", C.c_uint32), ("n_leaves", C.c_uint32),
                 ("handles_sharing", C.c_uint32), ("builder", C.c_uint32), ("build_ms", C.c_double),
@@ -155,7 +172,8 @@ EXPORTS = ["rts_create", "rts_destroy", "rts_last_error", "rts_device_count", "r
            "rts_rotation_matrix", "rts_rect_mesh", "rts_sphere_mesh", "rts_file_mesh", "rts_rx_sphere", "rts_get_bvh",
            "rts_build_id", "rts_bind_host_to_device", "rts_get_lane_stats", "rts_get_walk_stats", "rts_self_test_math", "rts_cube_attach", "rts_cube_accumulate", "rts_cube_get", "rts_cube_accumulate_paths", "rts_cube_doppler", "rts_cube_doppler_get", "rts_plan_cpi", "rts_cube_reduce", "rts_kernel_wrapper_on",
            "rts_received_prefetch", "rts_received_view", "rts_finalise_values", "rts_aggregated_view", "rts_build_hierarchy_host",
-           "rts_tile_records_get", "rts_tile_records_set", "rts_deal_tiles", "rts_set_tile_list"]
+           "rts_tile_records_get", "rts_tile_records_set", "rts_deal_tiles", "rts_set_tile_list",
+           "rts_set_patterns", "rts_finalise_patterns", "rts_trace_pulse_end_patterns", "rts_pattern_eval"]
 
 
 def lib():
@@ -216,6 +234,10 @@ def lib():
         "rts_cube_reduce": [vp, u32, C.c_int],
         "rts_tile_records_get": [vp, vp, u32], "rts_tile_records_set": [vp, vp, u32], "rts_deal_tiles": [vp, u32, u64, u32, u32, vp, vp], "rts_set_tile_list": [vp, u32, vp, u32],
         "rts_self_test_math": [vp, vp, vp, vp, vp, vp, vp, vp, u32],
+        "rts_set_patterns": [vp, C.POINTER(RtsPattern), C.POINTER(RtsPattern), u32, C.POINTER(RtsPattern), u32],
+        "rts_finalise_patterns": [vp, C.POINTER(RtsPatternPulse)],
+        "rts_trace_pulse_end_patterns": [vp, C.POINTER(RtsPatternPulse), C.c_int32, u64],
+        "rts_pattern_eval": [C.POINTER(RtsPattern), vp, vp, u32, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name, None)

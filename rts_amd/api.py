@@ -101,6 +101,59 @@ def build_hierarchy_host(verts, tris, split_budget=2.0):
     return nodes[:nn.value], leaf[:nl.value], root.value
 
 
+# ------------------------------------------------------------------------------- tabulated gain / RCS patterns
+class Pattern:
+    """A tabulated antenna gain or RCS pattern over two angles (u, v) -- include/rts_amd.h: RtsPattern for the semantics.
+    Holds its own copies of the tables; desc() is the C descriptor that points into them."""
+
+    def __init__(self, kind, scale=1.0, flags=0, n_u=0, n_v=0, us=None, uy=None, vs=None, vy=None, grid=None, u0=0.0, du=0.0, v0=0.0, dv=0.0):
+        self.kind, self.scale, self.flags, self.n_u, self.n_v = kind, float(scale), flags, n_u, n_v
+        self.us, self.uy, self.vs, self.vy, self.grid_values = us, uy, vs, vy, grid
+        self.u0, self.du, self.v0, self.dv = float(u0), float(du), float(v0), float(dv)
+
+    @classmethod
+    def constant(cls, v):
+        return cls(L.RTS_PATTERN_CONSTANT, scale=v)
+
+    @classmethod
+    def separable(cls, u_samples, u_values, v_samples, v_values, scale=1.0, abs_u=False, abs_v=False):
+        """scale * Lu(u') * Lv(v'): piecewise-linear in each angle, clamped outside the samples; u' = |u| with abs_u (v' likewise)"""
+        a = [np.ascontiguousarray(x, np.float64).ravel() for x in (u_samples, u_values, v_samples, v_values)]
+        if len(a[0]) != len(a[1]) or len(a[2]) != len(a[3]):
+            raise ValueError("Pattern.separable: samples and values differ in length")
+        flags = (L.RTS_PATTERN_ABS_U if abs_u else 0) | (L.RTS_PATTERN_ABS_V if abs_v else 0)
+        return cls(L.RTS_PATTERN_SEPARABLE, scale, flags, len(a[0]), len(a[2]), *a)
+
+    @classmethod
+    def grid(cls, values, u0, du, v0, dv, scale=1.0):
+        """scale * bilinear(values, u, v): values[j][i] at (u0 + i du, v0 + j dv), coordinates clamped to the grid"""
+        g = np.ascontiguousarray(values, np.float64)
+        if g.ndim != 2:
+            raise ValueError("Pattern.grid: values must be [n_v][n_u]")
+        return cls(L.RTS_PATTERN_GRID, scale, 0, g.shape[1], g.shape[0], grid=g, u0=u0, du=du, v0=v0, dv=dv)
+
+    def desc(self):
+        d = L.RtsPattern()
+        d.kind, d.flags, d.n_u, d.n_v, d.scale = self.kind, self.flags, self.n_u, self.n_v, self.scale
+        d.u_samples, d.u_values, d.v_samples, d.v_values, d.grid = [ptr(x) for x in (self.us, self.uy, self.vs, self.vy, self.grid_values)]
+        d.u0, d.du, d.v0, d.dv = self.u0, self.du, self.v0, self.dv
+        return d
+
+
+def _pattern_desc(p):
+    return p if isinstance(p, L.RtsPattern) else p.desc()
+
+
+def pattern_eval(pattern, u, v):
+    """rts_pattern_eval (pure host): the pattern's value at the points (u, v) (broadcast); raises RtsError on a malformed pattern"""
+    u, v = np.broadcast_arrays(np.asarray(u, np.float64), np.asarray(v, np.float64))
+    shape = u.shape
+    u = np.ascontiguousarray(u).ravel(); v = np.ascontiguousarray(v).ravel()
+    out = np.zeros(len(u))
+    check(L.lib().rts_pattern_eval(C.byref(_pattern_desc(pattern)), ptr(u), ptr(v), len(u), ptr(out)))
+    return out.reshape(shape)
+
+
 def device_count():
     n = C.c_int(0)
     rc = L.lib().rts_device_count(C.byref(n))
@@ -321,6 +374,28 @@ class Tracer:
         trace when the handle's previous pulse received few rays; received_count() / stats() / groups() wait"""
         r = np.ascontiguousarray(rcs_per_target, np.float64) if rcs_per_target is not None else None
         check(L.lib().rts_trace_pulse_end_uniform(self.h, ptr(r), wavelength, gt, gr, carrier, cspeed, cube_pulse, recv_index_base))
+
+    def set_patterns(self, tx, rx_list, rcs_list):
+        """rts_set_patterns: the transmitter's, one per receiver and one per target (Pattern or RtsPattern)"""
+        rx = (L.RtsPattern * max(len(rx_list), 1))(*[_pattern_desc(p) for p in rx_list])
+        rcs = (L.RtsPattern * max(len(rcs_list), 1))(*[_pattern_desc(p) for p in rcs_list])
+        check(L.lib().rts_set_patterns(self.h, C.byref(_pattern_desc(tx)), rx, len(rx_list), rcs, len(rcs_list)))
+
+    @staticmethod
+    def _pattern_pulse(rx_positions, rx_rotations, wavelength, carrier, cspeed):
+        pos = np.ascontiguousarray(np.asarray(rx_positions, np.float64).reshape(-1, 3))
+        rot = np.ascontiguousarray(np.asarray(rx_rotations, np.float64).reshape(-1, 4))
+        return L.RtsPatternPulse(wavelength, carrier, cspeed, ptr(pos), ptr(rot)), (pos, rot)
+
+    def finalise_patterns(self, rx_positions, rx_rotations, wavelength, carrier, cspeed):
+        """rts_finalise_patterns: rx_positions [n_rx][3], rx_rotations [n_rx][4] = az, el at the pulse time, az_rate, el_rate (rad/s)"""
+        q, keep = self._pattern_pulse(rx_positions, rx_rotations, wavelength, carrier, cspeed)
+        check(L.lib().rts_finalise_patterns(self.h, C.byref(q)))
+
+    def trace_end_patterns(self, rx_positions, rx_rotations, wavelength, carrier, cspeed, cube_pulse=-1, recv_index_base=0):
+        """trace_end_uniform with the pattern finalisation"""
+        q, keep = self._pattern_pulse(rx_positions, rx_rotations, wavelength, carrier, cspeed)
+        check(L.lib().rts_trace_pulse_end_patterns(self.h, C.byref(q), cube_pulse, recv_index_base))
 
     def aggregate(self, cspeed, carrier, recv_index_base=0, fetch=True):
         """fetch=False: only enqueue (the library reads the group table when it is first asked for: groups())"""

@@ -268,6 +268,9 @@ extern "C" int rts_destroy(RtsHandle c)
     }
     if (c->pulse_open || c->spec_pending) { c->pulse_open = false; c->spec_pending = false; g_open_pulses[c->device & 63]--; }
     rts_comm_cache_forget(c);
+    c->d_pat.release(); c->d_pat_rx.release();
+    if (c->pin_pat) (void)hipHostFree(c->pin_pat);
+    if (c->ev_pat) (void)hipEventDestroy(c->ev_pat);
     if (c->scene && --c->scene->refs == 0) { c->scene->release(); delete c->scene; }
     c->scene = nullptr;
     if (c->hist && --c->hist->refs == 0) { c->hist->d.release(); delete c->hist; }
@@ -743,6 +746,8 @@ extern "C" int rts_trace_pulse_begin(RtsHandle c, const RtsPulse* p)
     hipStream_t st = c->stream;
     c->agg_valid = false; c->agg_pending.valid = false; c->n_recv = 0;
     c->mirror.want = false; c->mirror.recv_valid = false; c->mirror.agg_valid = false; c->v_recv_have = 0;
+    for (int k = 0; k < 3; k++) c->pulse_org[k] = p->ray_origin[k];
+    c->pulse_dir[0] = p->tx_dir[0]; c->pulse_dir[1] = p->tx_dir[1]; c->pulse_traced = true;      // (rts_finalise_patterns: the transmitter's position and boresight)
 
     // ---- scene placement: only when a target actually moved
     RTS_HIP(hipEventRecord(c->ev[0], st));
@@ -1189,7 +1194,7 @@ static int rts_post_chain(RtsContext* c, bool ordered = false)      // ordered: 
     }
     if (q.mode == 1) return RTS_OK;                                     // rts_received_prefetch: the received set goes home, the caller finalises it
     RTS_HIP(hipEventRecord(c->ev[6], st));
-    rc = rts_post_finalise(c, q.rcs.data(), q.wl, q.gt, q.gr, q.carrier, q.cspeed); if (rc != RTS_OK) return rc;
+    rc = q.fin ? rts_post_finalise_patterns(c, q) : rts_post_finalise(c, q.rcs.data(), q.wl, q.gt, q.gr, q.carrier, q.cspeed); if (rc != RTS_OK) return rc;
     c->fin_timed = true; c->agg_valid = false;
     if (q.cube_pulse >= 0) { rc = rts_cube_accumulate_device(c, (uint32_t)q.cube_pulse, q.cspeed, q.carrier); if (rc != RTS_OK) return rc; }
     rc = rts_aggregate_impl(c, q.cspeed, q.carrier, q.base);
@@ -1217,6 +1222,7 @@ static int rts_spec_resolve(RtsContext* c)
     return RTS_OK;
 }
 
+static int rts_trace_pulse_end_chain(RtsContext* c);
 extern "C" int rts_trace_pulse_end_uniform(RtsHandle c, const double* rcs_per_target, double wavelength, double gt, double gr, double carrier, double cspeed,
                                            int32_t cube_pulse, uint64_t recv_index_base)
 {
@@ -1226,7 +1232,13 @@ extern "C" int rts_trace_pulse_end_uniform(RtsHandle c, const double* rcs_per_ta
     RtsSpecParams& q = c->spec;
     const size_t nt = c->scene->meshes.size();
     q.rcs.assign(nt + 1, 1.0); if (rcs_per_target) for (size_t t = 0; t < nt; t++) q.rcs[t] = rcs_per_target[t];
-    q.wl = wavelength; q.gt = gt; q.gr = gr; q.carrier = carrier; q.cspeed = cspeed; q.cube_pulse = cube_pulse; q.base = recv_index_base; q.mode = 0;
+    q.wl = wavelength; q.gt = gt; q.gr = gr; q.carrier = carrier; q.cspeed = cspeed; q.cube_pulse = cube_pulse; q.base = recv_index_base; q.mode = 0; q.fin = 0;
+    return rts_trace_pulse_end_chain(c);
+}
+
+// the rest of rts_trace_pulse_end_uniform / _patterns, once c->spec holds the pulse's post-processing parameters
+static int rts_trace_pulse_end_chain(RtsContext* c)
+{
     const bool keep_all = (c->params.flags & RTS_FLAG_KEEP_ALL_RAYS) != 0;
     bool narrow_key = true;
     {   // capacity of a speculative chain: the smaller of its two one-block sorts (row keys: 32 bits without refraction chains; (receiver, path) keys: D x B + RXB bits)
@@ -1260,6 +1272,148 @@ extern "C" int rts_trace_pulse_end_uniform(RtsHandle c, const double* rcs_per_ta
     c->recv_dev = nullptr; c->n_recv = 0;
     if (rc != RTS_OK) { c->spec_pending = false; g_open_pulses[c->device & 63]--; return rc; }
     return RTS_OK;
+}
+
+// ------------------------------------------------------------------------------------- tabulated antenna gain and RCS patterns
+// (rts_amd.h: RtsPattern; the evaluator is rts_pattern.h, shared by the host export and the finalisation kernels)
+static bool pat_values_ok(const double* a, uint32_t n) { for (uint32_t i = 0; i < n; i++) if (!std::isfinite(a[i]) || a[i] < 0.0) return false; return true; }
+static bool pat_ascending(const double* s, uint32_t n)
+{
+    for (uint32_t i = 0; i < n; i++) if (!std::isfinite(s[i]) || (i && !(s[i] > s[i - 1]))) return false;
+    return true;
+}
+static int rts_pattern_check(const RtsPattern* p, const char* who, uint32_t index)
+{
+    if (!p) { rts_set_error("%s pattern %u: null descriptor", who, index); return RTS_ERR_INVALID; }
+    if (p->reserved[0] || p->reserved[1]) { rts_set_error("%s pattern %u: reserved fields must be 0", who, index); return RTS_ERR_INVALID; }
+    if (!std::isfinite(p->scale) || p->scale < 0.0) { rts_set_error("%s pattern %u: scale must be finite and >= 0", who, index); return RTS_ERR_INVALID; }
+    if (p->kind == RTS_PATTERN_CONSTANT) {
+        if (p->flags) { rts_set_error("%s pattern %u: a constant pattern takes no flags", who, index); return RTS_ERR_INVALID; }
+        return RTS_OK;
+    }
+    if (p->kind != RTS_PATTERN_SEPARABLE && p->kind != RTS_PATTERN_GRID) { rts_set_error("%s pattern %u: unknown kind %u", who, index, p->kind); return RTS_ERR_INVALID; }
+    if (p->n_u < 1 || p->n_v < 1 || p->n_u > RTS_PATTERN_MAX_AXIS || p->n_v > RTS_PATTERN_MAX_AXIS) { rts_set_error("%s pattern %u: %u x %u samples (1 .. %u per axis)", who, index, p->n_u, p->n_v, RTS_PATTERN_MAX_AXIS); return RTS_ERR_INVALID; }
+    if (p->kind == RTS_PATTERN_SEPARABLE) {
+        if (p->flags & ~(RTS_PATTERN_ABS_U | RTS_PATTERN_ABS_V)) { rts_set_error("%s pattern %u: unknown flags 0x%x", who, index, p->flags); return RTS_ERR_INVALID; }
+        if (!p->u_samples || !p->u_values || !p->v_samples || !p->v_values) { rts_set_error("%s pattern %u: null sample or value array", who, index); return RTS_ERR_INVALID; }
+        if (!pat_ascending(p->u_samples, p->n_u) || !pat_ascending(p->v_samples, p->n_v)) { rts_set_error("%s pattern %u: samples must be finite and strictly ascending", who, index); return RTS_ERR_INVALID; }
+        if (!pat_values_ok(p->u_values, p->n_u) || !pat_values_ok(p->v_values, p->n_v)) { rts_set_error("%s pattern %u: values must be finite and >= 0", who, index); return RTS_ERR_INVALID; }
+        return RTS_OK;
+    }
+    if (p->flags) { rts_set_error("%s pattern %u: a grid pattern takes no flags", who, index); return RTS_ERR_INVALID; }
+    if ((uint64_t)p->n_u * p->n_v > RTS_PATTERN_MAX_GRID) { rts_set_error("%s pattern %u: grid of %u x %u samples exceeds %u", who, index, p->n_u, p->n_v, RTS_PATTERN_MAX_GRID); return RTS_ERR_INVALID; }
+    if (!p->grid) { rts_set_error("%s pattern %u: null grid", who, index); return RTS_ERR_INVALID; }
+    if (!std::isfinite(p->u0) || !std::isfinite(p->v0) || !std::isfinite(p->du) || !std::isfinite(p->dv) || !(p->du > 0.0) || !(p->dv > 0.0) ||
+        !std::isfinite(p->u0 + (p->n_u - 1) * p->du) || !std::isfinite(p->v0 + (p->n_v - 1) * p->dv)) { rts_set_error("%s pattern %u: grid origin / spacing must be finite, du and dv > 0", who, index); return RTS_ERR_INVALID; }
+    if (!pat_values_ok(p->grid, p->n_u * p->n_v)) { rts_set_error("%s pattern %u: grid values must be finite and >= 0", who, index); return RTS_ERR_INVALID; }
+    return RTS_OK;
+}
+static RtsPatView pat_view(const RtsPattern& p)
+{
+    RtsPatView v; memset(&v, 0, sizeof(v));
+    v.kind = p.kind; v.flags = p.flags; v.n_u = p.n_u; v.n_v = p.n_v; v.scale = p.scale;
+    v.us = p.u_samples; v.uy = p.u_values; v.vs = p.v_samples; v.vy = p.v_values; v.u0 = p.u0; v.du = p.du; v.v0 = p.v0; v.dv = p.dv; v.grid = p.grid;
+    return v;
+}
+
+extern "C" int rts_pattern_eval(const RtsPattern* p, const double* u, const double* v, uint32_t n, double* out)
+{
+    int rc = rts_pattern_check(p, "rts_pattern_eval:", 0); if (rc != RTS_OK) return rc;
+    if (n && (!u || !v || !out)) { rts_set_error("rts_pattern_eval: null point or output array"); return RTS_ERR_INVALID; }
+    const RtsPatView w = pat_view(*p);
+    for (uint32_t i = 0; i < n; i++) out[i] = rts_pat_eval(w, u[i], v[i]);
+    return RTS_OK;
+}
+
+extern "C" int rts_set_patterns(RtsHandle c, const RtsPattern* tx, const RtsPattern* rx, uint32_t n_rx, const RtsPattern* rcs, uint32_t n_targets)
+{
+    CHECK_HANDLE(c);
+    if ((n_rx && !rx) || (n_targets && !rcs)) { rts_set_error("rts_set_patterns: null receiver or target pattern array"); return RTS_ERR_INVALID; }
+    if (n_rx > (1u << 20) || n_targets > (1u << 20)) { rts_set_error("rts_set_patterns: %u receivers / %u targets", n_rx, n_targets); return RTS_ERR_INVALID; }
+    std::vector<const RtsPattern*> all; all.reserve(1 + (size_t)n_rx + n_targets);
+    all.push_back(tx); for (uint32_t k = 0; k < n_rx; k++) all.push_back(&rx[k]); for (uint32_t t = 0; t < n_targets; t++) all.push_back(&rcs[t]);
+    { int rc = rts_pattern_check(tx, "rts_set_patterns: transmitter", 0); if (rc != RTS_OK) return rc; }
+    for (uint32_t k = 0; k < n_rx; k++) { int rc = rts_pattern_check(&rx[k], "rts_set_patterns: receiver", k); if (rc != RTS_OK) return rc; }
+    for (uint32_t t = 0; t < n_targets; t++) { int rc = rts_pattern_check(&rcs[t], "rts_set_patterns: target", t); if (rc != RTS_OK) return rc; }
+    // ---- pack: [views | the tables' arrays], offsets first, device pointers once the buffer exists
+    const size_t n_pat = all.size(), head = (n_pat * sizeof(RtsPatView) + 15) & ~(size_t)15;
+    size_t n_dbl = 0;
+    for (const RtsPattern* p : all)
+        n_dbl += p->kind == RTS_PATTERN_SEPARABLE ? 2 * ((size_t)p->n_u + p->n_v) : p->kind == RTS_PATTERN_GRID ? (size_t)p->n_u * p->n_v : 0;
+    const size_t bytes = head + n_dbl * sizeof(double);
+    // the handle's enqueued work may still read the previous tables: a speculative chain is resolved (if it has to run again, it runs
+    // with the tables it was enqueued for), then the stream drained
+    if (c->spec_pending) { int rc = rts_spec_resolve(c); if (rc != RTS_OK) return rc; }
+    RTS_HIP(hipStreamSynchronize(c->stream));
+    RTS_HIP(c->d_pat.reserve(bytes));
+    std::vector<char> host(bytes);
+    RtsPatView* views = reinterpret_cast<RtsPatView*>(host.data());
+    double* dst = reinterpret_cast<double*>(host.data() + head);
+    const double* dev = reinterpret_cast<const double*>(c->d_pat.p + head);
+    size_t off = 0;
+    for (size_t k = 0; k < n_pat; k++) {
+        const RtsPattern& p = *all[k];
+        RtsPatView v = pat_view(p);
+        v.us = v.uy = v.vs = v.vy = v.grid = nullptr;
+        if (p.kind == RTS_PATTERN_SEPARABLE) {
+            memcpy(dst + off, p.u_samples, sizeof(double) * p.n_u); v.us = dev + off; off += p.n_u;
+            memcpy(dst + off, p.u_values, sizeof(double) * p.n_u); v.uy = dev + off; off += p.n_u;
+            memcpy(dst + off, p.v_samples, sizeof(double) * p.n_v); v.vs = dev + off; off += p.n_v;
+            memcpy(dst + off, p.v_values, sizeof(double) * p.n_v); v.vy = dev + off; off += p.n_v;
+        } else if (p.kind == RTS_PATTERN_GRID) {
+            memcpy(dst + off, p.grid, sizeof(double) * p.n_u * p.n_v); v.grid = dev + off; off += (size_t)p.n_u * p.n_v;
+        }
+        views[k] = v;
+    }
+    RTS_HIP(hipMemcpy(c->d_pat.p, host.data(), bytes, hipMemcpyHostToDevice));
+    c->pat_n_rx = n_rx; c->pat_n_targets = n_targets; c->pat_set = true;
+    return RTS_OK;
+}
+
+// the pulse's pattern parameters -> q (checks of rts_finalise_patterns / rts_trace_pulse_end_patterns)
+static int rts_pattern_pulse_params(RtsContext* c, const RtsPatternPulse* p, RtsSpecParams& q, const char* who)
+{
+    if (!p) { rts_set_error("%s: null pulse parameters", who); return RTS_ERR_INVALID; }
+    if (!c->pat_set) { rts_set_error("%s: no patterns set (rts_set_patterns)", who); return RTS_ERR_INVALID; }
+    if (c->pat_n_rx != c->n_rx) { rts_set_error("%s: patterns for %u receivers, the handle has %u", who, c->pat_n_rx, c->n_rx); return RTS_ERR_INVALID; }
+    if ((size_t)c->pat_n_targets != c->scene->meshes.size()) { rts_set_error("%s: patterns for %u targets, the scene has %zu", who, c->pat_n_targets, c->scene->meshes.size()); return RTS_ERR_INVALID; }
+    if (!c->pulse_traced) { rts_set_error("%s: the handle's received set is not a traced pulse's", who); return RTS_ERR_INVALID; }
+    if (c->n_rx && (!p->rx_position || !p->rx_rotation)) { rts_set_error("%s: null receiver positions / rotations", who); return RTS_ERR_INVALID; }
+    q.pat_rx.assign((size_t)c->n_rx * 8, 0.0);
+    for (uint32_t k = 0; k < c->n_rx; k++) {
+        for (int j = 0; j < 3; j++) q.pat_rx[(size_t)k * 8 + j] = p->rx_position[(size_t)k * 3 + j];
+        for (int j = 0; j < 4; j++) q.pat_rx[(size_t)k * 8 + 3 + j] = p->rx_rotation[(size_t)k * 4 + j];
+    }
+    for (int j = 0; j < 3; j++) q.pat_org[j] = c->pulse_org[j];
+    q.pat_dir[0] = c->pulse_dir[0]; q.pat_dir[1] = c->pulse_dir[1];
+    q.wl = p->wavelength; q.carrier = p->carrier; q.cspeed = p->cspeed; q.fin = 1;
+    return RTS_OK;
+}
+
+extern "C" int rts_finalise_patterns(RtsHandle c, const RtsPatternPulse* pulse)
+{
+    CHECK_HANDLE(c);
+    CHECK_CLOSED(c);
+    RtsSpecParams q;
+    int rc = rts_pattern_pulse_params(c, pulse, q, "rts_finalise_patterns"); if (rc != RTS_OK) return rc;
+    RTS_HIP(hipEventRecord(c->ev[6], c->stream));
+    rc = rts_post_finalise_patterns(c, q); if (rc != RTS_OK) return rc;
+    RTS_HIP(hipEventRecord(c->ev[7], c->stream));
+    c->fin_timed = true; c->stats_pending = true;
+    c->agg_valid = false;
+    return RTS_OK;
+}
+
+extern "C" int rts_trace_pulse_end_patterns(RtsHandle c, const RtsPatternPulse* pulse, int32_t cube_pulse, uint64_t recv_index_base)
+{
+    CHECK_HANDLE(c);
+    if (!c->pulse_open) { rts_set_error("rts_trace_pulse_end_patterns: no pulse in flight on this handle"); return RTS_ERR_INVALID; }
+    if (cube_pulse >= 0 && (!c->cube_set || (uint32_t)cube_pulse >= c->cube_params.n_pulses)) { rts_set_error("rts_trace_pulse_end_patterns: no cube attached, or pulse %d outside it", cube_pulse); return RTS_ERR_INVALID; }
+    RtsSpecParams& q = c->spec;
+    int rc = rts_pattern_pulse_params(c, pulse, q, "rts_trace_pulse_end_patterns"); if (rc != RTS_OK) return rc;
+    q.rcs.assign(c->scene->meshes.size() + 1, 1.0); q.gt = q.gr = 1.0;
+    q.cube_pulse = cube_pulse; q.base = recv_index_base; q.mode = 0;
+    return rts_trace_pulse_end_chain(c);
 }
 
 // ------------------------------------------------------------------------------------- the received set at home without copy calls
@@ -1861,7 +2015,7 @@ extern "C" int rts_kernel_wrapper_on(RtsHandle h, PerRayData* h_rx_results_arr, 
     if (!h_rx_results_arr || (depthTotal && !h_rx_intersects_arr) || !h_delay_arr || !h_phase_arr || !h_pathMatch) { rts_set_error("rts_kernel_wrapper: null array"); return RTS_ERR_INVALID; }
     RtsContext* c = h;
     if (!c) { int rc = wrapper_context(&c); if (rc != RTS_OK) return rc; }
-    else { CHECK_CLOSED(c); c->agg_valid = false; c->agg_pending.valid = false; c->n_recv = 0; c->mirror.recv_valid = false; c->mirror.agg_valid = false; c->mirror.want = false; }      // the handle's own received set is overwritten
+    else { CHECK_CLOSED(c); c->agg_valid = false; c->agg_pending.valid = false; c->n_recv = 0; c->mirror.recv_valid = false; c->mirror.agg_valid = false; c->mirror.want = false; c->pulse_traced = false; }      // the handle's own received set is overwritten
     RTS_HIP(hipSetDevice(c->device));
     const size_t R = receivedRays, D = depthTotal;
     RTS_HIP(c->d_rx_rays.reserve(R)); RTS_HIP(c->d_rx_paths.reserve(R*D + 1)); RTS_HIP(c->d_delay.reserve(R)); RTS_HIP(c->d_phase.reserve(R)); RTS_HIP(c->d_pathmatch.reserve(R));

@@ -7,6 +7,7 @@
 #include <vector>
 #include "../../include/rts_amd.h"
 #include "rts_device_math.h"
+#include "rts_pattern.h"
 
 // ----------------------------------------------------------------------------- HBM layout
 // BVH4 node, 128 B = one cache line, of the static target-space hierarchy (rts_sah.cpp): half the dependent fetch
@@ -280,7 +281,13 @@ struct RtsTileHist { std::atomic<int> refs{1}; DevBuf<uint32_t> d; uint32_t n = 
 #define RTS_SMALL_CAP32 4096u         // received rays the one-block ordering kernels take with 32-bit sort keys (rts_post.hip) ...
 #define RTS_SMALL_CAP64 2048u         // ... and with 64-bit keys; a speculatively enqueued post-processing chain is sized for the smaller of its two sorts
 struct RtsSpecParams { std::vector<double> rcs; double wl = 0, gt = 0, gr = 0, carrier = 0, cspeed = 0; int32_t cube_pulse = -1; uint64_t base = 0;
-                       int mode = 0; };     // 0: the uniform chain (rts_trace_pulse_end_uniform); 1: order + expand + the received set to the host mirror (rts_received_prefetch)
+                       int mode = 0;        // 0: the uniform chain (rts_trace_pulse_end_uniform); 1: order + expand + the received set to the host mirror (rts_received_prefetch)
+                       int fin = 0;         // mode 0's finaliser: 0 uniform (rcs / gt / gr), 1 the handle's tabulated patterns (rts_trace_pulse_end_patterns) with:
+                       std::vector<double> pat_rx; double pat_org[3] = {0, 0, 0}, pat_dir[2] = {0, 0};      // [n_rx][8] position, az, el, az_rate, el_rate, 0; the pulse's ray_origin and tx_dir
+};
+// Arguments of the pattern finaliser (rts_post.hip: finalise_row_patterns): the handle's packed tables -- views [tx | rx[n_rx] | rcs[n_targets]]
+// followed by their arrays -- and the pulse's receiver rows, uploaded per pulse (rts_pattern_pulse_upload)
+struct RtsPatArgs { const RtsPatView* pats; const double* rx; uint32_t n_rx, n_targets; double ox, oy, oz, tx_az, tx_el, wl, carrier, cspeed; };
 // Host mirror of a pulse's received set and of its aggregation outputs (rts_received_prefetch, the C++ adapter's path): ONE pinned
 // allocation that KERNELS write (k_mirror_rows, k_mirror_agg: only the rows that exist cross the bus, no copy calls) and read
 // (k_set_values: the power / Doppler the simulator's callbacks produced).  cap rows of: PerRayData | path row | RCS-angle row | slot |
@@ -392,6 +399,11 @@ struct RtsContext {
     RtsPinned* pin = nullptr; RtsPinned* pin_dev = nullptr;      // pinned host staging and its address on the device: kernels write the small per-pulse read-backs (counters, group table) straight into it
     bool rcs_uploaded = false; DevBuf<double> d_rcsval; int n_cu = 0; bool stats_pending = false; bool agg_timed = false, fin_timed = false;
     RtsStats stats;
+    // tabulated patterns (rts_set_patterns): one device buffer per handle, and the per-pulse receiver rows behind a pinned staging block
+    // that is rewritten only after the copy of the previous rows has run (ev_pat)
+    DevBuf<char> d_pat; uint32_t pat_n_rx = 0, pat_n_targets = 0; bool pat_set = false;
+    DevBuf<double> d_pat_rx; double* pin_pat = nullptr; size_t pin_pat_cap = 0; hipEvent_t ev_pat = nullptr; bool ev_pat_armed = false;
+    double pulse_org[3] = {0, 0, 0}, pulse_dir[2] = {0, 0}; bool pulse_traced = false;      // the last traced pulse's ray_origin / tx_dir; false after rts_kernel_wrapper_on
     double lap_s[8] = {0, 0, 0, 0, 0, 0, 0, 0}; uint64_t lap_n[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // RTS_LAP=1: host time per section of rts_trace_pulse_begin
     RtsGate* gate = nullptr; bool pulse_open = false;   // gate: never null after rts_create
 };
@@ -416,6 +428,8 @@ int rts_cube_accumulate_device(RtsContext* c, uint32_t pulse_index, double cspee
 int rts_cube_accumulate_paths_device(RtsContext* c, uint32_t pulse_index, int64_t base);
 int rts_cube_doppler_device(RtsContext* c, uint32_t n_fft, double* out);
 int rts_post_finalise(RtsContext* c, const double* rcs_host, double wl, double gt, double gr, double carrier, double cspeed);
+int rts_pattern_pulse_upload(RtsContext* c, const RtsSpecParams& q, RtsPatArgs* out);      // the pulse's receiver rows -> the device, on c->stream
+int rts_post_finalise_patterns(RtsContext* c, const RtsSpecParams& q);                       // k_finalise_patterns on the received set (count from c->recv_dev when set)
 hipError_t rts_stream_wait(RtsContext* c, hipStream_t st);
 int rts_aggregate_fetch(RtsContext* c, std::vector<RtsGroup>* groups);      // second half of rts_aggregate_device when groups == &c->groups: no-op when nothing is pending
 int rts_aggregate_device(RtsContext* c, int32_t max_path, int32_t max_rx, const int32_t* d_paths, uint64_t R, uint32_t D,

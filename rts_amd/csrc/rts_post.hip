@@ -692,6 +692,93 @@ int rts_post_finalise(RtsContext* c, const double* rcs_host, double wl, double g
     return RTS_OK;
 }
 
+// --------------------------------------------------------------------------- pattern finalisation, ray_tracer.cpp:1198-1253 (rts_amd.h: RtsPattern)
+// GetRCS per target on the path, GetGain of the transmitter and of the ray's receiver -- answered from the handle's tables.  Operand order
+// of finalise_row: every CONSTANT table gives the uniform path's bits.
+__device__ __forceinline__ void finalise_row_patterns(PerRayData* __restrict__ rays, const int32_t* __restrict__ paths, const double* __restrict__ angles, const uint32_t i, const uint32_t D,
+                                                      const RtsPatArgs& a)
+{
+    double power = rays[i].power;
+    for (uint32_t k = 0; k < D; k++) {
+        int targ_k = paths[(size_t)i*D + k];
+        if (targ_k >= 0) {                                                   // :1225-1229, GetRCS(rcs_angle.x, rcs_angle.y, Wl) at the bistatic bisector
+            double targRCS = 1.0;
+            if ((uint32_t)targ_k < a.n_targets) {
+                const double* ang = angles + ((size_t)i*D + k) * 2;
+                targRCS = rts_pat_eval(a.pats[1u + a.n_rx + (uint32_t)targ_k], rts_wrap_pi(ang[0] / 2), ang[1] / 2);
+            }
+            power *= targRCS;
+        }
+    }
+    const int32_t rx = rays[i].received;
+    const uint32_t k = ((uint32_t)rx < a.n_rx) ? (uint32_t)rx : 0u;
+    const double* q = a.rx + (size_t)k * 8;
+    const dvec3 org = mk3(a.ox, a.oy, a.oz), pos = mk3(q[0], q[1], q[2]);
+    dvec3 transvec, recvvec;                                                 // :1204-1211
+    if (rays[i].reflDepth == 0 && rays[i].refrDepth == 0) { transvec = sub3(org, pos); recvvec = sub3(pos, org); }
+    else {
+        transvec = sub3(mk3(rays[i].firstHitPoint.x, rays[i].firstHitPoint.y, rays[i].firstHitPoint.z), org);
+        recvvec = sub3(mk3(rays[i].prevHitPoint.x, rays[i].prevHitPoint.y, rays[i].prevHitPoint.z), pos);
+    }
+    const double delay = rays[i].rayLength / a.cspeed;
+    double u, v;
+    rts_pat_angles(transvec, a.tx_az, a.tx_el, u, v);
+    const double Gt = rts_pat_eval(a.pats[0], u, v);                          // :1230-1231, GetRotation(time_t)
+    rts_pat_angles(recvvec, q[3] + q[5] * delay, q[4] + q[6] * delay, u, v);
+    const double Gr = ((uint32_t)rx < a.n_rx) ? rts_pat_eval(a.pats[1u + k], u, v) : 1.0;      // :1234-1235, GetRotation(delay + time_t)
+    const double wl = a.wl;
+    power *= (wl*wl*Gt*Gr);                                                  // :1247
+    double Vr = rays[i].doppler/2;                                           // :1252
+    rays[i].doppler = a.carrier*(((1 + Vr/a.cspeed)/(1 - Vr/a.cspeed)) - 1); // :1253
+    rays[i].power = power;
+}
+__global__ void k_finalise_patterns(PerRayData* __restrict__ rays, const int32_t* __restrict__ paths, const double* __restrict__ angles, uint32_t R, uint32_t D,
+                                    const RtsPatArgs a, const unsigned long long* __restrict__ R_dev)
+{
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (R_dev) { const unsigned long long v_ = *R_dev; if (v_ > (unsigned long long)R) return; R = (uint32_t)v_; }      // (as k_finalise)
+    if (i >= R) return;
+    finalise_row_patterns(rays, paths, angles, i, D, a);
+}
+
+// The pulse's receiver rows [n_rx][8] -> the handle's device buffer, on c->stream (behind whatever of the handle's work still reads the
+// previous rows).  The pinned staging is rewritten only once the previous copy out of it has run: the handle's earlier chains may still be
+// in flight.
+int rts_pattern_pulse_upload(RtsContext* c, const RtsSpecParams& q, RtsPatArgs* out)
+{
+    const size_t n = q.pat_rx.size();
+    if (c->ev_pat_armed) { RTS_HIP(hipEventSynchronize(c->ev_pat)); c->ev_pat_armed = false; }
+    if (c->pin_pat_cap < n + 8) {
+        if (c->pin_pat) { RTS_HIP(hipHostFree(c->pin_pat)); c->pin_pat = nullptr; c->pin_pat_cap = 0; }
+        const size_t cap = std::max<size_t>(n + 8, 512);
+        RTS_HIP(hipHostMalloc((void**)&c->pin_pat, sizeof(double) * cap, hipHostMallocDefault));
+        c->pin_pat_cap = cap;
+    }
+    if (!c->ev_pat) RTS_HIP(hipEventCreateWithFlags(&c->ev_pat, hipEventDisableTiming));
+    RTS_HIP(c->d_pat_rx.reserve(n + 8));
+    if (n) {
+        memcpy(c->pin_pat, q.pat_rx.data(), sizeof(double) * n);
+        RTS_HIP(hipMemcpyAsync(c->d_pat_rx.p, c->pin_pat, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+        RTS_HIP(hipEventRecord(c->ev_pat, c->stream)); c->ev_pat_armed = true;
+    }
+    RtsPatArgs& a = *out;
+    a.pats = reinterpret_cast<const RtsPatView*>(c->d_pat.p); a.rx = c->d_pat_rx.p; a.n_rx = c->pat_n_rx; a.n_targets = c->pat_n_targets;
+    a.ox = q.pat_org[0]; a.oy = q.pat_org[1]; a.oz = q.pat_org[2]; a.tx_az = q.pat_dir[0]; a.tx_el = q.pat_dir[1];
+    a.wl = q.wl; a.carrier = q.carrier; a.cspeed = q.cspeed;
+    return RTS_OK;
+}
+
+int rts_post_finalise_patterns(RtsContext* c, const RtsSpecParams& q)
+{
+    const uint32_t R = (uint32_t)c->n_recv;
+    if (R == 0) return RTS_OK;
+    RtsPatArgs a;
+    int rc = rts_pattern_pulse_upload(c, q, &a); if (rc != RTS_OK) return rc;
+    k_finalise_patterns<<<blocks_for(R, 256), 256, 0, c->stream>>>(c->d_rx_rays.p, c->d_rx_paths.p, c->d_rx_angles.p, R, c->depth, a, c->recv_dev);
+    RTS_HIP(hipGetLastError());
+    return RTS_OK;
+}
+
 // --------------------------------------------------------------------------- complex return cube
 // one lane per received ray, two f64 atomics (global_atomic_add_f64) into cube[rx][pulse][bin]
 __device__ __forceinline__ void cube_row(const PerRayData* __restrict__ rays, const uint32_t i, double* __restrict__ cube, const uint32_t n_rx, const uint32_t n_pulses, const uint32_t n_bins,
@@ -1222,9 +1309,18 @@ struct RtsPostAll {
     const unsigned long long* R_dev; uint32_t prio;
 };
 template <typename K> struct RtsSortMax { enum { ITEMS = sizeof(K) == 4 ? 16 : 8 }; };
+// the finaliser of k_post_all: the uniform one reads its constants from RtsPostAll (the kernel of rts_trace_pulse_end_uniform), the
+// pattern one carries the tables and the pulse's receiver rows (rts_trace_pulse_end_patterns)
+struct RtsFinUniform {
+    __device__ __forceinline__ void operator()(const RtsPostAll& q, const uint32_t j) const { finalise_row(q.rays, q.paths, j, q.D, q.rcs, q.n_targets, q.wl, q.gt, q.gr, q.carrier, q.cspeed); }
+};
+struct RtsFinPatterns {
+    RtsPatArgs a;
+    __device__ __forceinline__ void operator()(const RtsPostAll& q, const uint32_t j) const { finalise_row_patterns(q.rays, q.paths, q.angles, j, q.D, a); }
+};
 #define RTS_POST_ALL_LDS 36864
-template <typename KR, typename KA>
-__global__ void __launch_bounds__(RTS_SMALL_THREADS) k_post_all(const RtsPostAll q)
+template <typename KR, typename KA, typename FIN>
+__global__ void __launch_bounds__(RTS_SMALL_THREADS) k_post_all(const RtsPostAll q, const FIN fin)
 {
     __shared__ __attribute__((aligned(16))) unsigned char s_raw[RTS_POST_ALL_LDS];
     static_assert(sizeof(RtsAggOrderLds<KA, RtsSortMax<KA>::ITEMS>) <= RTS_POST_ALL_LDS && sizeof(typename rocprim::block_radix_sort<KR, RTS_SMALL_THREADS, RtsSortMax<KR>::ITEMS, uint32_t>::storage_type) <= RTS_POST_ALL_LDS &&
@@ -1244,7 +1340,7 @@ __global__ void __launch_bounds__(RTS_SMALL_THREADS) k_post_all(const RtsPostAll
     // ---- the reference's output records, the uniform finalisation, the return cube: row by row
     for (uint32_t j = threadIdx.x; j < R; j += RTS_SMALL_THREADS) {
         expand_row(q.ta, q.rec, q.perm, j, q.D, q.rays, q.paths, q.angles, q.slots);
-        finalise_row(q.rays, q.paths, j, q.D, q.rcs, q.n_targets, q.wl, q.gt, q.gr, q.carrier, q.cspeed);
+        fin(q, j);
         if (q.cube_on) cube_row(q.rays, j, q.cube, q.cube_rx, q.cube_pulses, q.cube_bins, q.cube_pulse, q.cube_t0, q.cube_dt, q.cspeed, q.carrier);
     }
     __syncthreads();
@@ -1271,8 +1367,8 @@ int rts_post_all_small(RtsContext* c, uint32_t cap, const RtsSpecParams& sp, boo
     RTS_HIP(c->d_ri.reserve(cap)); RTS_HIP(c->d_ri_sorted.reserve(cap));
     RTS_HIP(c->d_rx_rays.reserve(cap)); RTS_HIP(c->d_rx_paths.reserve((size_t)cap*D + 1)); RTS_HIP(c->d_rx_angles.reserve((size_t)cap*D*2 + 1)); RTS_HIP(c->d_rx_slots.reserve(cap));
     RTS_HIP(c->d_rcsval.reserve(nt + 1));
-    bool changed = !c->rcs_uploaded;
-    for (uint32_t t = 0; t < nt && t < 256; t++) changed = changed || memcmp(&c->pin->rcs[t], &sp.rcs[t], sizeof(double)) != 0;
+    bool changed = sp.fin == 0 && !c->rcs_uploaded;                     // (the pattern finaliser reads no per-target constants)
+    for (uint32_t t = 0; sp.fin == 0 && t < nt && t < 256; t++) changed = changed || memcmp(&c->pin->rcs[t], &sp.rcs[t], sizeof(double)) != 0;
     if (changed) {
         RTS_HIP(hipStreamSynchronize(st));
         for (uint32_t t = 0; t < nt && t < 256; t++) c->pin->rcs[t] = sp.rcs[t];
@@ -1313,10 +1409,20 @@ int rts_post_all_small(RtsContext* c, uint32_t cap, const RtsSpecParams& sp, boo
                          spec_s, want_groups ? &pd->G : nullptr, pd->gsum, pd->gmin, pd->gkey, pd->grow};
     q.R_dev = c->p_counters; q.prio = c->post_prio;
     const bool kr64 = c->last_args.max_refr != 0, ka64 = key_bits >= 32u;
-    if (!kr64 && !ka64) k_post_all<uint32_t, uint32_t><<<1, RTS_SMALL_THREADS, 0, st>>>(q);
-    else if (!kr64) k_post_all<uint32_t, uint64_t><<<1, RTS_SMALL_THREADS, 0, st>>>(q);
-    else if (!ka64) k_post_all<uint64_t, uint32_t><<<1, RTS_SMALL_THREADS, 0, st>>>(q);
-    else k_post_all<uint64_t, uint64_t><<<1, RTS_SMALL_THREADS, 0, st>>>(q);
+    if (sp.fin == 0) {
+        const RtsFinUniform f{};
+        if (!kr64 && !ka64) k_post_all<uint32_t, uint32_t><<<1, RTS_SMALL_THREADS, 0, st>>>(q, f);
+        else if (!kr64) k_post_all<uint32_t, uint64_t><<<1, RTS_SMALL_THREADS, 0, st>>>(q, f);
+        else if (!ka64) k_post_all<uint64_t, uint32_t><<<1, RTS_SMALL_THREADS, 0, st>>>(q, f);
+        else k_post_all<uint64_t, uint64_t><<<1, RTS_SMALL_THREADS, 0, st>>>(q, f);
+    } else {
+        RtsFinPatterns f;
+        int rc = rts_pattern_pulse_upload(c, sp, &f.a); if (rc != RTS_OK) return rc;
+        if (!kr64 && !ka64) k_post_all<uint32_t, uint32_t><<<1, RTS_SMALL_THREADS, 0, st>>>(q, f);
+        else if (!kr64) k_post_all<uint32_t, uint64_t><<<1, RTS_SMALL_THREADS, 0, st>>>(q, f);
+        else if (!ka64) k_post_all<uint64_t, uint32_t><<<1, RTS_SMALL_THREADS, 0, st>>>(q, f);
+        else k_post_all<uint64_t, uint64_t><<<1, RTS_SMALL_THREADS, 0, st>>>(q, f);
+    }
     RTS_HIP(hipGetLastError());
     c->recv_index_base = sp.base; c->agg_base_local = use_rows ? 0 : (int64_t)sp.base;
     RtsAggPending& ap = c->agg_pending;
