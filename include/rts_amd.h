@@ -409,6 +409,58 @@ int rts_cube_accumulate_paths(RtsHandle h, uint32_t pulse_index);
 int rts_cube_doppler(RtsHandle h, uint32_t n_fft, void* device_out);
 int rts_cube_doppler_get(RtsHandle h, double* host_out, uint64_t capacity_doubles);
 
+/* ---------------------------------------------------------------- received signal: waveform render and range compression
+ * What SOARS does with the responses the reference hands it (ray_tracer.cpp:1311-1320): render them with the pulse's waveform.
+ * A waveform is M complex baseband samples s[0..M-1] at the cube's sample interval dt, and an interpolation length L.  Its
+ * continuous envelope at x (in samples) is
+ *     s(x) = sum_{m=0}^{M-1} s[m] h_L(x - m)
+ *   L = 1       sample-and-hold: h_1(u) = 1 for -1 < u <= 0, else 0 (sample m lands in output sample floor(d) + m: the bin of
+ *               rts_cube_accumulate)
+ *   L even, 2 .. 64   windowed sinc: h_L(u) = sinc(u) w(u) for |u| < L/2, else 0; sinc(u) = sinpi(u) / (pi u), h_L(0) = 1 exactly
+ *               (so an on-grid delay reproduces the samples bit for bit); Blackman w(u) = 0.42 + 0.5 cos(2 pi u / L) + 0.08 cos(4 pi u / L)
+ * Each contribution k -- amplitude a_k = sqrt(P_k) e^{j phi_k}, delay tau_k, Doppler frequency f_k, fractional start
+ * d_k = (tau_k - t0) / dt -- adds to output sample n of the row (rx_k, pulse):
+ *     y[n] += a_k s(n - d_k) e^{j 2 pi f_k (n - d_k) dt}          (f_k = 0 without RTS_RENDER_DOPPLER)
+ * Samples outside [0, n_bins) are dropped.  The contributions are those of the two accumulations above:
+ *   RTS_RENDER_RAYS   every received ray of the last pulse, as rts_cube_accumulate takes it: P its power, tau = rayLength / cspeed,
+ *                     phi = -fmod(2 pi carrier tau, 2 pi), f its Doppler.  (After rts_aggregate -- and after the fused pulse ends,
+ *                     which aggregate -- the rays carry their group's power and Doppler, aggregation.cu:88-93; render before it for
+ *                     the finalised per-ray values.)
+ *   RTS_RENDER_PATHS  the representative of each group of the pulse's rts_aggregate, as rts_cube_accumulate_paths takes it: the
+ *                     group's power, delay, phase and Doppler.  cspeed and carrier are not used.
+ * The render is a gather: per (receiver, tile of output samples) the contributions are summed in the received set's order,
+ * then each sample is added to the cube with one atomic add -- handles that share a cube stay safe, and one handle's render
+ * into a zeroed row is bit-reproducible.  Rendering is linear: rts_cube_reduce (and an all-reduce of caller-owned cubes) sums
+ * rendered cubes as they are.
+ * Range compression (matched filter), in place on the rows of the cube:
+ *     z[n] = sum_{m=0}^{M-1} y[n + m] conj(s[m]),   y[j] = 0 for j >= n_bins
+ * (an on-grid response at n0 peaks at z[n0] = a sum |s[m]|^2).  One workgroup holds a whole row in LDS: n_bins <= 8 192
+ * (128 KiB of complex128 of the 160 KiB a gfx950 workgroup may allocate). */
+#define RTS_RENDER_RAYS 0u
+#define RTS_RENDER_PATHS 1u
+#define RTS_RENDER_DOPPLER 1u
+#define RTS_WAVEFORM_MAX_SAMPLES 4096u     /* the render stages the whole waveform in LDS: 64 KiB of complex128 */
+#define RTS_WAVEFORM_MAX_TAPS 64u
+#define RTS_COMPRESS_MAX_BINS 8192u
+typedef struct RtsWaveform {
+    const double* samples;       /* [n_samples] interleaved re / im, finite                         */
+    uint32_t n_samples;          /* 1 .. RTS_WAVEFORM_MAX_SAMPLES                                   */
+    uint32_t taps;               /* L: 1, or even in [2, RTS_WAVEFORM_MAX_TAPS]                     */
+    uint64_t reserved[2];        /* 0                                                               */
+} RtsWaveform;
+/* Validates *w -- on failure RTS_ERR_INVALID and the handle keeps its previous waveform -- and copies it into a device buffer of
+ * the handle (the caller's array is free on return).  Waits for the handle's enqueued work that may still read the previous one. */
+int rts_cube_set_waveform(RtsHandle h, const RtsWaveform* w);
+/* Renders the last pulse's contributions (source RTS_RENDER_RAYS / RTS_RENDER_PATHS; flags 0 or RTS_RENDER_DOPPLER) into row
+ * pulse_index of every receiver of the attached cube, with the handle's waveform.  Works after every pulse end after which
+ * rts_cube_accumulate works; RTS_RENDER_PATHS needs rts_aggregate of the pulse (or a fused pulse end, which aggregates). */
+int rts_cube_render(RtsHandle h, uint32_t pulse_index, uint32_t source, uint32_t flags, double cspeed, double carrier);
+/* Range-compresses rows first_pulse .. first_pulse + n_pulses - 1 of every receiver in place, with the handle's waveform. */
+int rts_cube_compress(RtsHandle h, uint32_t first_pulse, uint32_t n_pulses);
+/* Pure host: validates *w and evaluates its envelope s(x[i]) -> out[2 i], out[2 i + 1] (re, im); x outside the support or not
+ * finite gives 0.  No device needed. */
+int rts_waveform_eval(const RtsWaveform* w, const double* x, uint32_t n, double* out);
+
 /* ---------------------------------------------------------------- several GPUs (not in the reference: it is single-GPU)
  * Rays are independent (each launch index writes only its own rows, ray_tracer.cu:227-253) and so are pulses
  * (ray_tracer.cpp:843).  rts_plan_cpi deals the n_pulses x total_rays (pulse, launch index) pairs of one coherent

@@ -90,6 +90,15 @@ class RtsPatternPulse(C.Structure):
                 ("rx_position", C.c_void_p), ("rx_rotation", C.c_void_p)]
 
 
+RTS_RENDER_RAYS, RTS_RENDER_PATHS = 0, 1
+RTS_RENDER_DOPPLER = 1
+RTS_WAVEFORM_MAX_SAMPLES, RTS_WAVEFORM_MAX_TAPS, RTS_COMPRESS_MAX_BINS = 4096, 64, 8192
+
+
+class RtsWaveform(C.Structure):
+    _fields_ = [("samples", C.c_void_p), ("n_samples", C.c_uint32), ("taps", C.c_uint32), ("reserved", C.c_uint64 * 2)]
+
+
 class RtsSceneInfo(C.Structure):
     _fields_ = [("n_targets", C.c_uint32), ("n_prims", C.c_uint32), ("n_nodes", C.c_uint32), ("n_leaves", C.c_uint32),
                 ("handles_sharing", C.c_uint32), ("builder", C.c_uint32), ("build_ms", C.c_double),
@@ -173,7 +182,8 @@ EXPORTS = ["rts_create", "rts_destroy", "rts_last_error", "rts_device_count", "r
            "rts_build_id", "rts_bind_host_to_device", "rts_get_lane_stats", "rts_get_walk_stats", "rts_self_test_math", "rts_cube_attach", "rts_cube_accumulate", "rts_cube_get", "rts_cube_accumulate_paths", "rts_cube_doppler", "rts_cube_doppler_get", "rts_plan_cpi", "rts_cube_reduce", "rts_kernel_wrapper_on",
            "rts_received_prefetch", "rts_received_view", "rts_finalise_values", "rts_aggregated_view", "rts_build_hierarchy_host",
            "rts_tile_records_get", "rts_tile_records_set", "rts_deal_tiles", "rts_set_tile_list",
-           "rts_set_patterns", "rts_finalise_patterns", "rts_trace_pulse_end_patterns", "rts_pattern_eval"]
+           "rts_set_patterns", "rts_finalise_patterns", "rts_trace_pulse_end_patterns", "rts_pattern_eval",
+           "rts_cube_set_waveform", "rts_cube_render", "rts_cube_compress", "rts_waveform_eval"]
 
 
 def lib():
@@ -238,6 +248,10 @@ def lib():
         "rts_finalise_patterns": [vp, C.POINTER(RtsPatternPulse)],
         "rts_trace_pulse_end_patterns": [vp, C.POINTER(RtsPatternPulse), C.c_int32, u64],
         "rts_pattern_eval": [C.POINTER(RtsPattern), vp, vp, u32, vp],
+        "rts_cube_set_waveform": [vp, C.POINTER(RtsWaveform)],
+        "rts_cube_render": [vp, u32, u32, u32, C.c_double, C.c_double],
+        "rts_cube_compress": [vp, u32, u32],
+        "rts_waveform_eval": [C.POINTER(RtsWaveform), vp, u32, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name, None)

@@ -154,6 +154,44 @@ def pattern_eval(pattern, u, v):
     return out.reshape(shape)
 
 
+# ------------------------------------------------------------------------------- transmit waveform (render, range compression)
+class Waveform:
+    """A transmit waveform: complex baseband samples at the cube's sample interval and an interpolation length (taps: 1
+    sample-and-hold, or even in [2, 64] windowed sinc) -- include/rts_amd.h: RtsWaveform.  Holds its own copy of the samples."""
+
+    def __init__(self, samples, taps=1):
+        z = np.asarray(samples, np.complex128).ravel()
+        self.samples = z
+        self._iq = np.ascontiguousarray(np.stack([z.real, z.imag], axis=-1))
+        self.taps = int(taps)
+
+    @classmethod
+    def lfm(cls, n, bandwidth_times_dt, taps=16):
+        """linear FM chirp of n samples sweeping bandwidth_times_dt cycles per sample, centred on 0:
+        s[m] = exp(j pi b (m - (n - 1) / 2)^2 / n)"""
+        m = np.arange(n, dtype=np.float64) - (n - 1) / 2.0
+        return cls(np.exp(1j * np.pi * float(bandwidth_times_dt) * m * m / n), taps)
+
+    def desc(self):
+        d = L.RtsWaveform()
+        d.samples, d.n_samples, d.taps = ptr(self._iq), len(self.samples), self.taps
+        return d
+
+
+def _waveform_desc(w):
+    return w if isinstance(w, L.RtsWaveform) else w.desc()
+
+
+def waveform_eval(w, x):
+    """rts_waveform_eval (pure host): the waveform's continuous envelope s(x) at positions x (in samples), complex"""
+    x = np.asarray(x, np.float64)
+    shape = x.shape
+    x = np.ascontiguousarray(x).ravel()
+    out = np.zeros((len(x), 2))
+    check(L.lib().rts_waveform_eval(C.byref(_waveform_desc(w)), ptr(x), len(x), ptr(out)))
+    return (out[:, 0] + 1j * out[:, 1]).reshape(shape)
+
+
 def device_count():
     n = C.c_int(0)
     rc = L.lib().rts_device_count(C.byref(n))
@@ -436,6 +474,25 @@ class Tracer:
         out = np.zeros((self._cube_shape[0], n_fft, self._cube_shape[2], 2), np.float64)
         check(L.lib().rts_cube_doppler_get(self.h, ptr(out), out.size))
         return out[..., 0] + 1j * out[..., 1]
+
+    def cube_set_waveform(self, w):
+        """rts_cube_set_waveform: the waveform (Waveform or RtsWaveform) cube_render and cube_compress use"""
+        check(L.lib().rts_cube_set_waveform(self.h, C.byref(_waveform_desc(w))))
+
+    def cube_render(self, pulse, source="rays", cspeed=None, carrier=None, doppler=True):
+        """rts_cube_render: the last pulse's contributions rendered with the waveform into row `pulse` of every receiver;
+        source "rays" (every received ray: needs cspeed and carrier) or "paths" (one per group of rts_aggregate)"""
+        src = {"rays": L.RTS_RENDER_RAYS, "paths": L.RTS_RENDER_PATHS}.get(source, source)
+        if src == L.RTS_RENDER_RAYS and (cspeed is None or carrier is None):
+            raise ValueError("cube_render(source='rays') needs cspeed and carrier")
+        check(L.lib().rts_cube_render(self.h, pulse, src, L.RTS_RENDER_DOPPLER if doppler else 0,
+                                      0.0 if cspeed is None else cspeed, 0.0 if carrier is None else carrier))
+
+    def cube_compress(self, first=0, count=None):
+        """rts_cube_compress: matched filter of rows first .. first + count - 1 (default: to the last pulse), in place"""
+        if count is None:
+            count = self._cube_shape[1] - first
+        check(L.lib().rts_cube_compress(self.h, first, count))
 
     def cube(self):
         out = np.zeros(self._cube_shape + (2,), np.float64)

@@ -268,7 +268,7 @@ extern "C" int rts_destroy(RtsHandle c)
     }
     if (c->pulse_open || c->spec_pending) { c->pulse_open = false; c->spec_pending = false; g_open_pulses[c->device & 63]--; }
     rts_comm_cache_forget(c);
-    c->d_pat.release(); c->d_pat_rx.release();
+    c->d_pat.release(); c->d_pat_rx.release(); c->d_wave.release();
     if (c->pin_pat) (void)hipHostFree(c->pin_pat);
     if (c->ev_pat) (void)hipEventDestroy(c->ev_pat);
     if (c->scene && --c->scene->refs == 0) { c->scene->release(); delete c->scene; }
@@ -1638,6 +1638,66 @@ extern "C" int rts_cube_get(RtsHandle c, double* host_out, uint64_t capacity_dou
     RTS_HIP(hipStreamSynchronize(c->stream));
     RTS_HIP(hipMemcpy(host_out, c->cube, sizeof(double) * doubles, hipMemcpyDeviceToHost));
     return RTS_OK;
+}
+
+// ------------------------------------------------------------------------------------- received signal: waveform render, range compression
+// (rts_amd.h: RtsWaveform; the interpolator is rts_waveform.h, shared by the host export and the render kernel, rts_render.hip)
+static int rts_waveform_check(const RtsWaveform* w, const char* who)
+{
+    if (!w) { rts_set_error("%s: null waveform", who); return RTS_ERR_INVALID; }
+    if (w->reserved[0] || w->reserved[1]) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
+    if (w->n_samples == 0 || w->n_samples > RTS_WAVEFORM_MAX_SAMPLES) { rts_set_error("%s: %u samples (1 .. %u)", who, w->n_samples, RTS_WAVEFORM_MAX_SAMPLES); return RTS_ERR_INVALID; }
+    if (w->taps != 1u && (w->taps < 2u || w->taps > RTS_WAVEFORM_MAX_TAPS || (w->taps & 1u))) { rts_set_error("%s: taps = %u (1, or even in [2, %u])", who, w->taps, RTS_WAVEFORM_MAX_TAPS); return RTS_ERR_INVALID; }
+    if (!w->samples) { rts_set_error("%s: null sample array", who); return RTS_ERR_INVALID; }
+    for (uint32_t i = 0; i < 2 * w->n_samples; i++) if (!std::isfinite(w->samples[i])) { rts_set_error("%s: sample %u is not finite", who, i / 2); return RTS_ERR_INVALID; }
+    return RTS_OK;
+}
+
+extern "C" int rts_waveform_eval(const RtsWaveform* w, const double* x, uint32_t n, double* out)
+{
+    int rc = rts_waveform_check(w, "rts_waveform_eval"); if (rc != RTS_OK) return rc;
+    if (n && (!x || !out)) { rts_set_error("rts_waveform_eval: null point or output array"); return RTS_ERR_INVALID; }
+    for (uint32_t i = 0; i < n; i++) rts_wave_eval(w->samples, w->n_samples, w->taps, x[i], &out[2 * (size_t)i], &out[2 * (size_t)i + 1]);
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_set_waveform(RtsHandle c, const RtsWaveform* w)
+{
+    CHECK_HANDLE(c);
+    int rc = rts_waveform_check(w, "rts_cube_set_waveform"); if (rc != RTS_OK) return rc;
+    // the handle's enqueued work may still read the previous waveform: a speculative chain is resolved, then the stream drained
+    if (c->spec_pending) { rc = rts_spec_resolve(c); if (rc != RTS_OK) return rc; }
+    RTS_HIP(hipStreamSynchronize(c->stream));
+    RTS_HIP(c->d_wave.reserve(2 * (size_t)w->n_samples));
+    RTS_HIP(hipMemcpy(c->d_wave.p, w->samples, sizeof(double) * 2 * w->n_samples, hipMemcpyHostToDevice));
+    c->wave_M = w->n_samples; c->wave_L = w->taps; c->wave_set = true;
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_render(RtsHandle c, uint32_t pulse_index, uint32_t source, uint32_t flags, double cspeed, double carrier)
+{
+    CHECK_HANDLE(c);
+    if (source != RTS_RENDER_RAYS && source != RTS_RENDER_PATHS) { rts_set_error("rts_cube_render: unknown source %u (RTS_RENDER_RAYS, RTS_RENDER_PATHS)", source); return RTS_ERR_INVALID; }
+    if (flags & ~RTS_RENDER_DOPPLER) { rts_set_error("rts_cube_render: unknown flags 0x%x", flags); return RTS_ERR_INVALID; }
+    CHECK_CLOSED(c);
+    if (!c->cube_set) { rts_set_error("rts_cube_render: call rts_cube_attach first"); return RTS_ERR_INVALID; }
+    if (!c->wave_set) { rts_set_error("rts_cube_render: no waveform (rts_cube_set_waveform)"); return RTS_ERR_INVALID; }
+    if (pulse_index >= c->cube_params.n_pulses) { rts_set_error("rts_cube_render: pulse %u >= %u", pulse_index, c->cube_params.n_pulses); return RTS_ERR_INVALID; }
+    const bool paths = source == RTS_RENDER_PATHS;
+    if (paths && !c->agg_valid) { rts_set_error("rts_cube_render: RTS_RENDER_PATHS needs rts_aggregate of this pulse first (the groups' power, delay and phase are its results)"); return RTS_ERR_INVALID; }
+    return rts_cube_render_device(c, pulse_index, paths, (flags & RTS_RENDER_DOPPLER) != 0, cspeed, carrier, c->agg_base_local);
+}
+
+extern "C" int rts_cube_compress(RtsHandle c, uint32_t first_pulse, uint32_t n_pulses)
+{
+    CHECK_HANDLE(c);
+    CHECK_CLOSED(c);
+    if (!c->cube_set) { rts_set_error("rts_cube_compress: call rts_cube_attach first"); return RTS_ERR_INVALID; }
+    if (!c->wave_set) { rts_set_error("rts_cube_compress: no waveform (rts_cube_set_waveform)"); return RTS_ERR_INVALID; }
+    const RtsCubeParams& q = c->cube_params;
+    if (first_pulse >= q.n_pulses || n_pulses > q.n_pulses - first_pulse) { rts_set_error("rts_cube_compress: pulses %u .. %u + %u outside the cube's %u", first_pulse, first_pulse, n_pulses, q.n_pulses); return RTS_ERR_INVALID; }
+    if (q.n_bins > RTS_COMPRESS_MAX_BINS) { rts_set_error("rts_cube_compress: %u range bins > %u (RTS_COMPRESS_MAX_BINS: one row of complex128 in a workgroup's LDS)", q.n_bins, RTS_COMPRESS_MAX_BINS); return RTS_ERR_INVALID; }
+    return rts_cube_compress_device(c, first_pulse, n_pulses);
 }
 
 // ------------------------------------------------------------------------------------- several GPUs: the plan of an interval
