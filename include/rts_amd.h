@@ -461,6 +461,71 @@ int rts_cube_compress(RtsHandle h, uint32_t first_pulse, uint32_t n_pulses);
  * finite gives 0.  No device needed. */
 int rts_waveform_eval(const RtsWaveform* w, const double* x, uint32_t n, double* out);
 
+/* ---------------------------------------------------------------- receiver noise and CFAR detection on the range-Doppler map
+ * Receiver noise: circular complex Gaussian samples with E|n|^2 = noise_power added to rows first_pulse .. first_pulse + n_pulses - 1
+ * of every receiver of the attached cube.  Sample i -- the cube's flat index i = (rx n_pulses_cube + pulse) n_bins + bin -- is a
+ * pure function of (seed, i), whatever the launch shape and however the rows are split across calls:
+ *     Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85), counter (lo32(i), hi32(i), 0, 0),
+ *     key (lo32(seed), hi32(seed)), output words x0..x3;
+ *     a = (x0 << 32 | x1) >> 11, u1 = (a + 1) 2^-53 in (0, 1];  b = (x2 << 32 | x3) >> 11, u2 = b 2^-53;
+ *     r = sqrt(-2 ln u1);  re += sqrt(noise_power / 2) r cos(2 pi u2),  im += sqrt(noise_power / 2) r sin(2 pi u2).
+ * A plain read-add-write of the rows (no atomics), ordered on the handle's stream.  noise_power finite and >= 0; 0 is a no-op.
+ *   * Add noise after the render and before rts_cube_compress: that is where thermal noise enters a receiver.
+ *   * With several GPUs add it ONCE, on one handle, after rts_cube_reduce or the caller's all-reduce -- otherwise it is summed N times.
+ * rts_noise_eval: pure host, the same generator (rts_noise.h): out[2 j], out[2 j + 1] = the noise sample of flat index index[j]. */
+int rts_cube_add_noise(RtsHandle h, uint32_t first_pulse, uint32_t n_pulses, double noise_power, uint64_t seed);
+int rts_noise_eval(uint64_t seed, const uint64_t* index, uint32_t n, double noise_power, double* out);
+
+/* CFAR detection.  Input z[rx][k][r], complex128 [n_rx][n_doppler][n_bins] (n_rx, n_bins of the attached cube): the handle's last
+ * rts_cube_doppler output (device_map NULL; n_doppler is then its n_fft and the argument is ignored) or a caller device pointer
+ * (n_doppler >= 1 required, any value).  Cell power P = re re + im im.
+ *   Window: the training cells of a cell under test (CUT) are the offsets (dk, dr) with |dk| <= Gd + Td, |dr| <= Gr + Tr, minus the
+ *     guard rectangle |dk| <= Gd, |dr| <= Gr (which holds the CUT).  The Doppler axis is circular (the DFT is periodic) and wraps;
+ *     the range axis is not: training cells outside [0, n_bins) are dropped, so their number N varies near the range edges.
+ *   Noise: CA the mean of the N training cells; GO / SO the larger / smaller of the means of the cells with dr < 0 and with dr > 0
+ *     (dr = 0 belongs to neither; a half that is empty at a range edge yields to the other).  Every estimate is a direct sum of
+ *     the training powers -- never a difference of box sums -- so a cell 10^12 above the noise beside a CUT costs it no accuracy.
+ *   Threshold alpha noise.  With pfa (CA only) each cell uses alpha = N (pfa^(-1/N) - 1), the exact CA threshold for square-law
+ *     detection of complex Gaussian noise: the false-alarm rate is pfa at the range edges too.
+ *   Detection: P > threshold; with RTS_CFAR_LOCAL_MAX also a 3 x 3 local maximum (Doppler wrapped, range truncated): strictly greater
+ *     than each neighbour whose offset (dk, dr) is lexicographically below (0, 0), >= each one above it (one detection per plateau).
+ *   Refinement: per axis a parabola through ln P of the two neighbours, delta = (ln P- - ln P+) / (2 (ln P- - 2 ln P0 + ln P+))
+ *     clamped to [-0.5, 0.5]; 0 when a neighbour is missing (range edge), a power is <= 0 or the denominator is >= 0.
+ *     delay = t0 + (range_bin + range_offset) dt; doppler = w / (n_doppler pri) with w = doppler_bin + doppler_offset wrapped into
+ *     [-n_doppler / 2, n_doppler / 2) (0 when pri is 0).  Sign: with the cube's phase -2 pi fc tau and the transform's e^{-2 pi j k p / n},
+ *     a CLOSING range (tau falling from pulse to pulse) gives a POSITIVE Doppler, fc |d tau / d pulse| / pri.
+ *   Output: the list in ascending flat order (rx, doppler_bin, range_bin), bit-identical from run to run (the order comes from
+ *     counts and a scan, never from atomics).  rts_cube_detect never waits on the host: it writes up to max_detections records and
+ *     the total count to device buffers of the handle, which live until the next rts_cube_detect, rts_cube_attach or rts_destroy.
+ *     rts_cube_detections_get synchronises, sets *n_out to the total and copies min(total, stored, capacity) records; it returns
+ *     RTS_ERR_CAPACITY when that is fewer than the total, RTS_ERR_INVALID after an rts_cube_attach.
+ *   RTS_ERR_INVALID, the message naming the field: no cube or no map; unknown mode or flags; nonzero reserved fields; Tr + Td = 0;
+ *     Gr + Tr or Gd + Td > RTS_CFAR_MAX_HALF; 2 (Gd + Td) + 1 > n_doppler; Gr + Tr >= n_bins; pfa outside (0, 1); both or neither
+ *     of pfa and alpha (alpha > 0 and finite); GO / SO with pfa or with Tr = 0; pri negative or not finite. */
+#define RTS_CFAR_CA 0u          /* cell averaging                                    */
+#define RTS_CFAR_GO 1u          /* greatest-of the two range halves                  */
+#define RTS_CFAR_SO 2u          /* smallest-of                                       */
+#define RTS_CFAR_LOCAL_MAX 1u   /* flag: report only 3x3 local maxima                */
+#define RTS_CFAR_MAX_HALF 16u   /* guard + train per side, per axis                  */
+typedef struct RtsCfarParams {
+    uint32_t guard_range, guard_doppler, train_range, train_doppler;   /* cells on EACH side of the cell under test */
+    uint32_t mode, flags;
+    double pfa;              /* CA only: (0, 1) -> alpha per cell from its own training count; 0: use alpha   */
+    double alpha;            /* > 0 when pfa == 0 (required for GO / SO)                                      */
+    double pri;              /* pulse repetition interval for RtsDetection.doppler; 0: doppler = 0            */
+    uint32_t max_detections; /* device list length; 0: 65 536                                                 */
+    uint32_t reserved0; uint64_t reserved[2];                                         /* 0 */
+} RtsCfarParams;
+typedef struct RtsDetection {
+    uint32_t rx, doppler_bin, range_bin, n_train;
+    double power, noise, threshold;           /* |z|^2 of the cell, the noise estimate, alpha * noise     */
+    double range_offset, doppler_offset;      /* sub-bin refinement, bins, in [-0.5, 0.5]                 */
+    double delay, doppler;                    /* t0 + (range_bin + range_offset) dt;  Hz                  */
+} RtsDetection;                               /* 72 bytes */
+#define RTS_CFAR_DEFAULT_MAX_DETECTIONS 65536u
+int rts_cube_detect(RtsHandle h, const RtsCfarParams* p, const void* device_map, uint32_t n_doppler);
+int rts_cube_detections_get(RtsHandle h, RtsDetection* out, uint32_t capacity, uint32_t* n_out);
+
 /* ---------------------------------------------------------------- several GPUs (not in the reference: it is single-GPU)
  * Rays are independent (each launch index writes only its own rows, ray_tracer.cu:227-253) and so are pulses
  * (ray_tracer.cpp:843).  rts_plan_cpi deals the n_pulses x total_rays (pulse, launch index) pairs of one coherent

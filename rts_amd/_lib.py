@@ -99,6 +99,24 @@ class RtsWaveform(C.Structure):
     _fields_ = [("samples", C.c_void_p), ("n_samples", C.c_uint32), ("taps", C.c_uint32), ("reserved", C.c_uint64 * 2)]
 
 
+RTS_CFAR_CA, RTS_CFAR_GO, RTS_CFAR_SO = 0, 1, 2
+RTS_CFAR_LOCAL_MAX = 1
+RTS_CFAR_MAX_HALF, RTS_CFAR_DEFAULT_MAX_DETECTIONS = 16, 65536
+
+
+class RtsCfarParams(C.Structure):
+    _fields_ = [("guard_range", C.c_uint32), ("guard_doppler", C.c_uint32), ("train_range", C.c_uint32), ("train_doppler", C.c_uint32),
+                ("mode", C.c_uint32), ("flags", C.c_uint32), ("pfa", C.c_double), ("alpha", C.c_double), ("pri", C.c_double),
+                ("max_detections", C.c_uint32), ("reserved0", C.c_uint32), ("reserved", C.c_uint64 * 2)]
+
+
+# RtsDetection (include/rts_amd.h), 72 bytes
+DETECTION_DTYPE = np.dtype([("rx", "<u4"), ("doppler_bin", "<u4"), ("range_bin", "<u4"), ("n_train", "<u4"), ("power", "<f8"),
+                            ("noise", "<f8"), ("threshold", "<f8"), ("range_offset", "<f8"), ("doppler_offset", "<f8"),
+                            ("delay", "<f8"), ("doppler", "<f8")])
+assert DETECTION_DTYPE.itemsize == 72 and C.sizeof(RtsCfarParams) == 72
+
+
 class RtsSceneInfo(C.Structure):
     _fields_ = [("n_targets", C.c_uint32), ("n_prims", C.c_uint32), ("n_nodes", C.c_uint32), ("n_leaves", C.c_uint32),
                 ("handles_sharing", C.c_uint32), ("builder", C.c_uint32), ("build_ms", C.c_double),
@@ -183,7 +201,8 @@ EXPORTS = ["rts_create", "rts_destroy", "rts_last_error", "rts_device_count", "r
            "rts_received_prefetch", "rts_received_view", "rts_finalise_values", "rts_aggregated_view", "rts_build_hierarchy_host",
            "rts_tile_records_get", "rts_tile_records_set", "rts_deal_tiles", "rts_set_tile_list",
            "rts_set_patterns", "rts_finalise_patterns", "rts_trace_pulse_end_patterns", "rts_pattern_eval",
-           "rts_cube_set_waveform", "rts_cube_render", "rts_cube_compress", "rts_waveform_eval"]
+           "rts_cube_set_waveform", "rts_cube_render", "rts_cube_compress", "rts_waveform_eval",
+           "rts_cube_add_noise", "rts_noise_eval", "rts_cube_detect", "rts_cube_detections_get"]
 
 
 def lib():
@@ -252,6 +271,10 @@ def lib():
         "rts_cube_render": [vp, u32, u32, u32, C.c_double, C.c_double],
         "rts_cube_compress": [vp, u32, u32],
         "rts_waveform_eval": [C.POINTER(RtsWaveform), vp, u32, vp],
+        "rts_cube_add_noise": [vp, u32, u32, C.c_double, u64],
+        "rts_noise_eval": [u64, vp, u32, C.c_double, vp],
+        "rts_cube_detect": [vp, C.POINTER(RtsCfarParams), vp, u32],
+        "rts_cube_detections_get": [vp, vp, u32, C.POINTER(u32)],
     }
     for name, args in sig.items():
         fn = getattr(L, name, None)

@@ -192,6 +192,17 @@ def waveform_eval(w, x):
     return (out[:, 0] + 1j * out[:, 1]).reshape(shape)
 
 
+# ------------------------------------------------------------------------------- receiver noise (rts_noise.h)
+def noise_eval(seed, index, noise_power):
+    """rts_noise_eval (pure host): the receiver-noise sample of each flat cube index under seed, complex, E|n|^2 = noise_power"""
+    idx = np.asarray(index, np.uint64)
+    shape = idx.shape
+    idx = np.ascontiguousarray(idx).ravel()
+    out = np.zeros((len(idx), 2))
+    check(L.lib().rts_noise_eval(int(seed), ptr(idx), len(idx), float(noise_power), ptr(out)))
+    return (out[:, 0] + 1j * out[:, 1]).reshape(shape)
+
+
 def device_count():
     n = C.c_int(0)
     rc = L.lib().rts_device_count(C.byref(n))
@@ -493,6 +504,41 @@ class Tracer:
         if count is None:
             count = self._cube_shape[1] - first
         check(L.lib().rts_cube_compress(self.h, first, count))
+
+    def cube_add_noise(self, noise_power, seed, first=0, count=None):
+        """rts_cube_add_noise: complex Gaussian noise of power noise_power (E|n|^2) added to rows first .. first + count - 1 (default:
+        to the last pulse) of every receiver; each sample a function of (seed, flat cube index) alone"""
+        if count is None:
+            count = self._cube_shape[1] - first
+        check(L.lib().rts_cube_add_noise(self.h, first, count, float(noise_power), int(seed)))
+
+    def cube_detect(self, guard=(2, 2), train=(8, 4), mode="ca", pfa=None, alpha=None, local_max=True, pri=0.0, device_ptr=None,
+                    n_doppler=None, max_detections=0, fetch=True):
+        """rts_cube_detect + rts_cube_detections_get: CFAR on the handle's last cube_doppler map (device_ptr None) or on a caller
+        complex128 device map [n_rx][n_doppler][n_bins]; guard and train are (range, Doppler) cells on each side; mode "ca", "go"
+        or "so"; exactly one of pfa (CA) and alpha.  Returns a DETECTION_DTYPE array in flat (rx, doppler_bin, range_bin) order."""
+        p = L.RtsCfarParams()
+        p.guard_range, p.guard_doppler = (int(g) for g in guard)
+        p.train_range, p.train_doppler = (int(t) for t in train)
+        p.mode = {"ca": L.RTS_CFAR_CA, "go": L.RTS_CFAR_GO, "so": L.RTS_CFAR_SO}.get(mode, mode)
+        p.flags = L.RTS_CFAR_LOCAL_MAX if local_max else 0
+        p.pfa = 0.0 if pfa is None else float(pfa)
+        p.alpha = 0.0 if alpha is None else float(alpha)
+        p.pri, p.max_detections = float(pri), int(max_detections)
+        if device_ptr and n_doppler is None:
+            raise ValueError("cube_detect(device_ptr=...) needs n_doppler")
+        check(L.lib().rts_cube_detect(self.h, C.byref(p), C.c_void_p(device_ptr) if device_ptr else None, int(n_doppler or 0)))
+        return self.detections() if fetch else None
+
+    def detections(self):
+        """rts_cube_detections_get: the list of the last cube_detect (every stored record; raises when max_detections cut it)"""
+        n = C.c_uint32(0)
+        rc = L.lib().rts_cube_detections_get(self.h, None, 0, C.byref(n))
+        if rc not in (L.RTS_OK, L.RTS_ERR_CAPACITY):
+            check(rc)
+        out = np.zeros(max(n.value, 1), L.DETECTION_DTYPE)
+        check(L.lib().rts_cube_detections_get(self.h, ptr(out), n.value, C.byref(n)))
+        return out[:n.value].copy()
 
     def cube(self):
         out = np.zeros(self._cube_shape + (2,), np.float64)

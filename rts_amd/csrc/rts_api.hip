@@ -269,6 +269,7 @@ extern "C" int rts_destroy(RtsHandle c)
     if (c->pulse_open || c->spec_pending) { c->pulse_open = false; c->spec_pending = false; g_open_pulses[c->device & 63]--; }
     rts_comm_cache_forget(c);
     c->d_pat.release(); c->d_pat_rx.release(); c->d_wave.release();
+    c->d_det_cnt.release(); c->d_det_off.release(); c->d_det_tmp.release(); c->d_det.release();
     if (c->pin_pat) (void)hipHostFree(c->pin_pat);
     if (c->ev_pat) (void)hipEventDestroy(c->ev_pat);
     if (c->scene && --c->scene->refs == 0) { c->scene->release(); delete c->scene; }
@@ -1580,6 +1581,7 @@ extern "C" int rts_cube_attach(RtsHandle c, const RtsCubeParams* p, void* device
     if (device_ptr) c->cube = (double*)device_ptr;          // caller-owned (and caller-zeroed) device memory
     else { RTS_HIP(c->d_cube_own.reserve(doubles)); c->cube = c->d_cube_own.p; RTS_HIP(hipMemset(c->cube, 0, sizeof(double) * doubles)); }
     c->cube_set = true;
+    c->det_valid = false; c->doppler_fresh = false;         // (a detection list, and a map rts_cube_detect may take, belong to the cube they were made from)
     return RTS_OK;
 }
 
@@ -1612,7 +1614,7 @@ extern "C" int rts_cube_doppler(RtsHandle c, uint32_t n_fft, void* device_out)
     const size_t doubles = 2 * (size_t)c->cube_params.n_rx * n_fft * c->cube_params.n_bins;
     if (device_out) c->doppler = (double*)device_out;
     else { RTS_HIP(c->d_doppler_own.reserve(doubles)); c->doppler = c->d_doppler_own.p; }
-    c->doppler_n = n_fft;
+    c->doppler_n = n_fft; c->doppler_fresh = true;
     return rts_cube_doppler_device(c, n_fft, c->doppler);
 }
 
@@ -1698,6 +1700,82 @@ extern "C" int rts_cube_compress(RtsHandle c, uint32_t first_pulse, uint32_t n_p
     if (first_pulse >= q.n_pulses || n_pulses > q.n_pulses - first_pulse) { rts_set_error("rts_cube_compress: pulses %u .. %u + %u outside the cube's %u", first_pulse, first_pulse, n_pulses, q.n_pulses); return RTS_ERR_INVALID; }
     if (q.n_bins > RTS_COMPRESS_MAX_BINS) { rts_set_error("rts_cube_compress: %u range bins > %u (RTS_COMPRESS_MAX_BINS: one row of complex128 in a workgroup's LDS)", q.n_bins, RTS_COMPRESS_MAX_BINS); return RTS_ERR_INVALID; }
     return rts_cube_compress_device(c, first_pulse, n_pulses);
+}
+
+// ------------------------------------------------------------------------------------- receiver noise, CFAR detection
+// (rts_amd.h; the generator is rts_noise.h, shared by the host export and the noise kernel; the kernels are in rts_detect.hip)
+extern "C" int rts_noise_eval(uint64_t seed, const uint64_t* index, uint32_t n, double noise_power, double* out)
+{
+    if (!std::isfinite(noise_power) || noise_power < 0) { rts_set_error("rts_noise_eval: noise_power = %g (finite, >= 0)", noise_power); return RTS_ERR_INVALID; }
+    if (n && (!index || !out)) { rts_set_error("rts_noise_eval: null index or output array"); return RTS_ERR_INVALID; }
+    const double sigma = sqrt(noise_power / 2.0);
+    for (uint32_t j = 0; j < n; j++) rts_noise_sample(seed, index[j], sigma, &out[2 * (size_t)j], &out[2 * (size_t)j + 1]);
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_add_noise(RtsHandle c, uint32_t first_pulse, uint32_t n_pulses, double noise_power, uint64_t seed)
+{
+    CHECK_HANDLE(c);
+    if (!std::isfinite(noise_power) || noise_power < 0) { rts_set_error("rts_cube_add_noise: noise_power = %g (finite, >= 0)", noise_power); return RTS_ERR_INVALID; }
+    CHECK_CLOSED(c);
+    if (!c->cube_set) { rts_set_error("rts_cube_add_noise: call rts_cube_attach first"); return RTS_ERR_INVALID; }
+    const RtsCubeParams& q = c->cube_params;
+    if (first_pulse >= q.n_pulses || n_pulses > q.n_pulses - first_pulse) { rts_set_error("rts_cube_add_noise: pulses %u .. %u + %u outside the cube's %u", first_pulse, first_pulse, n_pulses, q.n_pulses); return RTS_ERR_INVALID; }
+    if ((uintptr_t)c->cube & 15u) { rts_set_error("rts_cube_add_noise: the cube's device memory is not 16-byte aligned"); return RTS_ERR_INVALID; }
+    return rts_cube_noise_device(c, first_pulse, n_pulses, sqrt(noise_power / 2.0), seed);
+}
+
+extern "C" int rts_cube_detect(RtsHandle c, const RtsCfarParams* p, const void* device_map, uint32_t n_doppler)
+{
+    CHECK_HANDLE(c);
+    if (!p) { rts_set_error("rts_cube_detect: null parameters"); return RTS_ERR_INVALID; }
+    CHECK_CLOSED(c);
+    if (!c->cube_set) { rts_set_error("rts_cube_detect: no cube (call rts_cube_attach first)"); return RTS_ERR_INVALID; }
+    const double* map;
+    if (device_map) {
+        map = (const double*)device_map;
+        if (n_doppler == 0) { rts_set_error("rts_cube_detect: n_doppler = 0 with a caller map"); return RTS_ERR_INVALID; }
+        if ((uintptr_t)map & 15u) { rts_set_error("rts_cube_detect: device_map is not 16-byte aligned"); return RTS_ERR_INVALID; }
+    } else {
+        if (!c->doppler || !c->doppler_fresh) { rts_set_error("rts_cube_detect: no map (call rts_cube_doppler first, or pass device_map)"); return RTS_ERR_INVALID; }
+        map = c->doppler; n_doppler = c->doppler_n;
+    }
+    const uint32_t Gr = p->guard_range, Gd = p->guard_doppler, Tr = p->train_range, Td = p->train_doppler, nb = c->cube_params.n_bins;
+    if (p->mode > RTS_CFAR_SO) { rts_set_error("rts_cube_detect: unknown mode %u (RTS_CFAR_CA, _GO, _SO)", p->mode); return RTS_ERR_INVALID; }
+    if (p->flags & ~RTS_CFAR_LOCAL_MAX) { rts_set_error("rts_cube_detect: unknown flags 0x%x", p->flags); return RTS_ERR_INVALID; }
+    if (p->reserved0 || p->reserved[0] || p->reserved[1]) { rts_set_error("rts_cube_detect: reserved fields must be 0"); return RTS_ERR_INVALID; }
+    if (Tr > RTS_CFAR_MAX_HALF || Td > RTS_CFAR_MAX_HALF || Gr > RTS_CFAR_MAX_HALF || Gd > RTS_CFAR_MAX_HALF) { rts_set_error("rts_cube_detect: guard_range, guard_doppler, train_range, train_doppler are at most %u each", RTS_CFAR_MAX_HALF); return RTS_ERR_INVALID; }
+    if (Tr + Td == 0) { rts_set_error("rts_cube_detect: train_range + train_doppler = 0 (no training cells)"); return RTS_ERR_INVALID; }
+    if (Gr + Tr > RTS_CFAR_MAX_HALF) { rts_set_error("rts_cube_detect: guard_range + train_range = %u > %u", Gr + Tr, RTS_CFAR_MAX_HALF); return RTS_ERR_INVALID; }
+    if (Gd + Td > RTS_CFAR_MAX_HALF) { rts_set_error("rts_cube_detect: guard_doppler + train_doppler = %u > %u", Gd + Td, RTS_CFAR_MAX_HALF); return RTS_ERR_INVALID; }
+    if (2 * (Gd + Td) + 1 > n_doppler) { rts_set_error("rts_cube_detect: guard_doppler + train_doppler = %u: the window (%u rows) exceeds n_doppler = %u", Gd + Td, 2 * (Gd + Td) + 1, n_doppler); return RTS_ERR_INVALID; }
+    if (Gr + Tr >= nb) { rts_set_error("rts_cube_detect: guard_range + train_range = %u >= n_bins = %u", Gr + Tr, nb); return RTS_ERR_INVALID; }
+    const bool has_pfa = p->pfa != 0.0, has_alpha = p->alpha != 0.0;
+    if (has_pfa && !(p->pfa > 0.0 && p->pfa < 1.0)) { rts_set_error("rts_cube_detect: pfa = %g outside (0, 1)", p->pfa); return RTS_ERR_INVALID; }
+    if (has_pfa == has_alpha) { rts_set_error("rts_cube_detect: give exactly one of pfa and alpha"); return RTS_ERR_INVALID; }
+    if (has_alpha && !(p->alpha > 0.0 && std::isfinite(p->alpha))) { rts_set_error("rts_cube_detect: alpha = %g (finite, > 0)", p->alpha); return RTS_ERR_INVALID; }
+    if (p->mode != RTS_CFAR_CA && has_pfa) { rts_set_error("rts_cube_detect: pfa is for mode RTS_CFAR_CA only (GO / SO take alpha)"); return RTS_ERR_INVALID; }
+    if (p->mode != RTS_CFAR_CA && Tr == 0) { rts_set_error("rts_cube_detect: train_range = 0 with GO / SO (the halves are range halves)"); return RTS_ERR_INVALID; }
+    if (!(p->pri >= 0.0) || !std::isfinite(p->pri)) { rts_set_error("rts_cube_detect: pri = %g (finite, >= 0)", p->pri); return RTS_ERR_INVALID; }
+    const uint32_t max_det = p->max_detections ? p->max_detections : RTS_CFAR_DEFAULT_MAX_DETECTIONS;
+    c->det_valid = false;
+    return rts_cube_detect_device(c, *p, map, n_doppler, max_det);
+}
+
+extern "C" int rts_cube_detections_get(RtsHandle c, RtsDetection* out, uint32_t capacity, uint32_t* n_out)
+{
+    CHECK_HANDLE(c);
+    if (!n_out || (capacity && !out)) { rts_set_error("rts_cube_detections_get: null output"); return RTS_ERR_INVALID; }
+    if (!c->det_valid) { rts_set_error("rts_cube_detections_get: no detection list (rts_cube_detect; a list ends at rts_cube_attach)"); return RTS_ERR_INVALID; }
+    RTS_HIP(hipStreamSynchronize(c->stream));
+    uint32_t total = 0;
+    RTS_HIP(hipMemcpy(&total, c->d_det_off.p + c->det_nseg, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    *n_out = total;
+    uint32_t n = total < c->det_max ? total : c->det_max;
+    if (n > capacity) n = capacity;
+    if (n) RTS_HIP(hipMemcpy(out, c->d_det.p, sizeof(RtsDetection) * n, hipMemcpyDeviceToHost));
+    if (n < total) { rts_set_error("rts_cube_detections_get: %u of %u detections copied (max_detections %u, capacity %u)", n, total, c->det_max, capacity); return RTS_ERR_CAPACITY; }
+    return RTS_OK;
 }
 
 // ------------------------------------------------------------------------------------- several GPUs: the plan of an interval

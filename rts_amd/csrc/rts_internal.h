@@ -9,6 +9,7 @@
 #include "rts_device_math.h"
 #include "rts_pattern.h"
 #include "rts_waveform.h"
+#include "rts_noise.h"
 
 // ----------------------------------------------------------------------------- HBM layout
 // BVH4 node, 128 B = one cache line, of the static target-space hierarchy (rts_sah.cpp): half the dependent fetch
@@ -63,6 +64,7 @@ struct __attribute__((aligned(16))) RtsEndRecord {
     uint32_t pad;
 };
 static_assert(sizeof(RtsEndRecord) == 112, "end record size");
+static_assert(sizeof(RtsDetection) == 72 && sizeof(RtsCfarParams) == 72, "CFAR ABI sizes (rts_amd/_lib.py mirrors them)");
 // RtsEndRecord::pad : bits 0-1 chain (output row = chain * n + slot), 2-3 refrDepth, 8-15 (target + 1) of chain 0's
 // refraction (path prefill of rows >= 3), 16-17 children spawned
 
@@ -396,6 +398,10 @@ struct RtsContext {
     RtsCubeParams cube_params; double* cube = nullptr; DevBuf<double> d_cube_own; bool cube_set = false;
     DevBuf<double> d_doppler_own; double* doppler = nullptr; uint32_t doppler_n = 0;       // slow-time transform of the cube (rts_cube_doppler)
     DevBuf<double> d_wave; uint32_t wave_M = 0, wave_L = 0; bool wave_set = false;         // the transmit waveform (rts_cube_set_waveform): M interleaved samples, L taps
+    // CFAR detection (rts_cube_detect, rts_detect.hip): per-segment counts -> exclusive scan (offsets; element n_seg: the total),
+    // the records of the last detection and how many it may hold; det_valid: a list exists for rts_cube_detections_get
+    DevBuf<uint32_t> d_det_cnt, d_det_off; DevBuf<uint8_t> d_det_tmp; DevBuf<RtsDetection> d_det; uint32_t det_nseg = 0, det_max = 0; bool det_valid = false;
+    bool doppler_fresh = false;         // rts_cube_doppler ran on the attached cube (rts_cube_detect without a map takes its output)
     bool agg_delay_in = true;           // rts_aggregate_device: the delay / phase arrays carry initial sums (rs::kernel_wrapper's in-out arguments); false: they start at zero
     int64_t agg_base_local = 0;         // pathMatch value of received ray i after rts_aggregate = agg_base_local + i
     RtsPinned* pin = nullptr; RtsPinned* pin_dev = nullptr;      // pinned host staging and its address on the device: kernels write the small per-pulse read-backs (counters, group table) straight into it
@@ -431,6 +437,8 @@ int rts_cube_accumulate_paths_device(RtsContext* c, uint32_t pulse_index, int64_
 int rts_cube_doppler_device(RtsContext* c, uint32_t n_fft, double* out);
 int rts_cube_render_device(RtsContext* c, uint32_t pulse_index, bool paths, bool doppler, double cspeed, double carrier, int64_t base);      // rts_render.hip
 int rts_cube_compress_device(RtsContext* c, uint32_t first_pulse, uint32_t n_pulses);
+int rts_cube_noise_device(RtsContext* c, uint32_t first_pulse, uint32_t n_pulses, double sigma, uint64_t seed);          // rts_detect.hip
+int rts_cube_detect_device(RtsContext* c, const RtsCfarParams& p, const double* map, uint32_t n_doppler, uint32_t max_det);
 int rts_post_finalise(RtsContext* c, const double* rcs_host, double wl, double gt, double gr, double carrier, double cspeed);
 int rts_pattern_pulse_upload(RtsContext* c, const RtsSpecParams& q, RtsPatArgs* out);      // the pulse's receiver rows -> the device, on c->stream
 int rts_post_finalise_patterns(RtsContext* c, const RtsSpecParams& q);                       // k_finalise_patterns on the received set (count from c->recv_dev when set)
