@@ -184,7 +184,6 @@ extern "C" int rts_create(const RtsParams* p, RtsHandle* out)
     e = hipStreamCreateWithPriority(&c->gate->tstream, hipStreamNonBlocking, prio_low);
     if (e != hipSuccess) { delete c->gate; (void)hipStreamDestroy(c->stream); delete c; rts_set_error("hipStreamCreate: %s", hipGetErrorString(e)); return RTS_ERR_HIP; }
     c->tstream = c->gate->tstream; c->tstream_now = c->tstream;
-    e = hipEventCreateWithFlags(&c->ev_spec, hipEventDisableTiming); if (e != hipSuccess) { delete c; rts_set_error("hipEventCreate: %s", hipGetErrorString(e)); return RTS_ERR_HIP; }
     for (int i = 0; i < 2; i++) { e = hipEventCreateWithFlags(&c->ev_coop[i], hipEventDisableTiming); if (e != hipSuccess) { delete c; rts_set_error("hipEventCreate: %s", hipGetErrorString(e)); return RTS_ERR_HIP; } }
     for (int i = 0; i < 9; i++) { e = hipEventCreate(&c->ev[i]); if (e != hipSuccess) { delete c; rts_set_error("hipEventCreate: %s", hipGetErrorString(e)); return RTS_ERR_HIP; } }
     e = hipHostMalloc((void**)&c->pin, sizeof(RtsPinned), hipHostMallocDefault);
@@ -212,22 +211,12 @@ extern "C" int rts_create(const RtsParams* p, RtsHandle* out)
     { const char* e = getenv("RTS_COOP_VERSIONS"); if (e) c->coop_versions = e[0] != '0'; }
     { const char* e = getenv("RTS_DEAD_BATCH"); if (e) c->batch_dead = strcmp(e, "all") == 0 ? 2 : (e[0] != '0' ? 1 : 0); }      // dead-tile batches of the trace kernel: 0 never, 1 the order's dead part (default), all: every position is screened tile-wise first (tests)
     { const char* e = getenv("RTS_WALK_VERSIONS"); if (e) c->node_versions = e[0] != '0'; }      // (per handle: RTS_NODE_VERSIONS decides whether the scene HAS versions, this whether the handle walks them)
-    { const char* e = getenv("RTS_SUM_IN_KERNEL"); if (e) c->sum_in_kernel = atoi(e) != 0; }
     { const char* e = getenv("RTS_SPIN_WAIT"); if (e) c->spin_wait = atoi(e) != 0; }
-    { const char* e = getenv("RTS_ORDER_FUSED"); if (e) c->order_fused = atoi(e) != 0; }
-    { const char* e = getenv("RTS_PLACE_FUSED"); if (e) c->place_fused = atoi(e) != 0; }
-    { const char* e = getenv("RTS_TILE_SORT"); if (e) c->tile_bucket_order = strcmp(e, "radix") != 0; }
-    { const char* e = getenv("RTS_XCD_AFFINE"); if (e) c->xcd_affine = e[0] == '0' ? 0 : (e[0] == '1' ? 1 : 2); }
     { const char* e = getenv("RTS_TRACE_OWN_STREAM"); if (e) c->trace_own_stream = atoi(e) != 0; }
-    { const char* e = getenv("RTS_SPEC_STREAM"); if (e) c->spec_on_trace_stream = strcmp(e, "trace") == 0; }
     { const char* e = getenv("RTS_SPECULATE"); if (e) c->spec_enabled = atoi(e) != 0; }
     { const char* e = getenv("RTS_POST_SMALL"); if (e) c->post_small = atoi(e) != 0; }
-    { const char* e = getenv("RTS_POST_ONE"); if (e) c->post_one = atoi(e) != 0; }
     { const char* e = getenv("RTS_POST_ONE_MAX"); if (e) c->post_one_max = (uint64_t)strtoull(e, nullptr, 10); }
     { const char* e = getenv("RTS_POST_PRIO"); if (e) c->post_prio = (uint32_t)std::min(3, std::max(0, atoi(e))); }
-    { const char* e = getenv("RTS_ASYNC_IDLE0"); if (e) c->async_idle0 = (uint32_t)std::min(64, std::max(0, atoi(e))); }
-    { const char* e = getenv("RTS_ASYNC_IDLE1"); if (e) c->async_idle1 = (uint32_t)std::min(64, std::max(1, atoi(e))); }
-    { const char* e = getenv("RTS_ASYNC_AGE"); if (e) c->async_age = (uint32_t)std::max(0, atoi(e)); }
     { const char* e = getenv("RTS_COOP_STEPS"); if (e) c->coop_walk_steps = (uint32_t)std::max(0, atoi(e)); }
     { const char* e = getenv("RTS_COOP_STEPS_LO"); if (e) c->coop_walk_steps_lo = (uint32_t)std::max(0, atoi(e)); }
     { const char* e = getenv("RTS_COOP_MID"); if (e) c->coop_mid = std::max(0.0, atof(e)); }
@@ -279,8 +268,8 @@ extern "C" int rts_destroy(RtsHandle c)
     c->d_verts_world.release(); c->d_normals_world.release();
     c->d_params.release();
     c->d_leaves.release(); c->d_sort_tmp.release(); c->d_rx.release(); c->d_recv.release(); c->d_all.release();
-    c->d_block_counters.release(); c->d_timeline.release(); c->d_tile_cost.release(); c->d_tile_key.release(); c->d_tile_key_sorted.release(); c->d_tile_id.release(); c->d_tile_order.release(); c->d_tile_ctr.release(); c->d_dir_hist.release(); c->d_pmask.release(); c->d_child.release(); c->d_rk64.release(); c->d_rk64_sorted.release(); c->d_hit_prim.release(); c->d_hit_t.release(); c->d_stack_ovf.release(); c->d_il_list.release(); c->d_rec_tmp.release();
-    c->d_xcd.release();
+    c->d_block_counters.release(); c->d_timeline.release(); c->d_tile_cost.release(); c->d_tile_key.release(); c->d_tile_order.release(); c->d_tile_ctr.release(); c->d_dir_hist.release(); c->d_pmask.release(); c->d_child.release(); c->d_rk64.release(); c->d_rk64_sorted.release(); c->d_hit_prim.release(); c->d_hit_t.release(); c->d_stack_ovf.release(); c->d_il_list.release(); c->d_rec_tmp.release();
+    c->d_order_sum.release();
     c->d_rk.release(); c->d_rk_sorted.release(); c->d_ri.release(); c->d_ri_sorted.release(); c->d_rx_rays.release(); c->d_rx_paths.release();
     c->d_rx_angles.release(); c->d_rx_slots.release(); c->d_all_rays.release(); c->d_all_paths.release(); c->d_all_angles.release();
     c->d_akeys.release(); c->d_akeys_sorted.release(); c->d_aidx.release(); c->d_aidx_sorted.release(); c->d_ghead.release(); c->d_gid.release();
@@ -292,7 +281,6 @@ extern "C" int rts_destroy(RtsHandle c)
     if (c->pin_rx) (void)hipHostFree(c->pin_rx);
     if (c->mirror.host) (void)hipHostFree(c->mirror.host);
     for (int i = 0; i < 9; i++) (void)hipEventDestroy(c->ev[i]);
-    if (c->ev_spec) (void)hipEventDestroy(c->ev_spec);
     for (int i = 0; i < 2; i++) (void)hipEventDestroy(c->ev_coop[i]);
     if (c->cstream) { (void)hipStreamSynchronize(c->cstream); (void)hipStreamDestroy(c->cstream); }
     (void)hipStreamDestroy(c->stream);
@@ -697,8 +685,7 @@ extern "C" int rts_reserve(RtsHandle c, uint64_t n_rays)
     RTS_HIP(c->d_stack_ovf.reserve((size_t)RTS_STACK_OVF * ((size_t)c->n_cu * 1024 + coop_threads)));
     RTS_HIP(c->d_block_counters.reserve(((size_t)c->n_cu * 64 + c->coop_grid_max) * 8));
     const size_t n_tiles = (size_t)((n + RTS_WTILE - 1) / RTS_WTILE), n_hist = (size_t)((W3 + RTS_WTILE - 1) / RTS_WTILE);
-    RTS_HIP(c->d_tile_ctr.reserve(RTS_ZERO_WORDS + RTS_MASK_WORDS + 64)); c->p_counters = reinterpret_cast<unsigned long long*>(c->d_tile_ctr.p + RTS_OFF_COUNTERS); RTS_HIP(c->d_tile_cost.reserve(n_tiles)); RTS_HIP(c->d_tile_key.reserve(n_tiles)); RTS_HIP(c->d_tile_key_sorted.reserve(n_tiles));
-    RTS_HIP(c->d_tile_id.reserve(n_tiles)); RTS_HIP(c->d_tile_order.reserve(n_tiles));
+    RTS_HIP(c->d_tile_cost.reserve(n_tiles)); RTS_HIP(c->d_tile_key.reserve(n_tiles)); RTS_HIP(c->d_tile_order.reserve(n_tiles));
     if (c->hist->n != (uint32_t)n_hist) {
         std::lock_guard<std::mutex> lk(g_hist_mu);      // (handles that share the history may be driven from different threads)
         RTS_HIP(hipDeviceSynchronize()); RTS_HIP(c->hist->d.reserve(n_hist)); RTS_HIP(hipMemset(c->hist->d.p, 0, sizeof(uint32_t) * n_hist));      // (blocking: the table may be shared with handles on other streams)
@@ -829,7 +816,7 @@ extern "C" int rts_trace_pulse_begin(RtsHandle c, const RtsPulse* p)
     a.lc = c->p_lc;
     // ONE fill per pulse: the draw counters of both kernels, the order's head words and bins, the launch's 16 counters and --
     // behind them, when this pulse has one -- the primary-ray mask
-    RTS_HIP(c->d_tile_ctr.reserve(RTS_ZERO_WORDS + RTS_MASK_WORDS + 64));
+    RTS_HIP(c->d_tile_ctr.reserve(RTS_ZERO_WORDS + RTS_MASK_WORDS + 64)); c->p_counters = reinterpret_cast<unsigned long long*>(c->d_tile_ctr.p + RTS_OFF_COUNTERS);
     RTS_HIP(hipMemsetAsync(c->d_tile_ctr.p, 0, sizeof(uint32_t) * (((RTS_ZERO_WORDS + (lc.mask.n ? (size_t)lc.mask.n * lc.mask.n / 32u + 1u : 0u)) + 63u) & ~(size_t)63u), st));      // (a whole number of 256-byte pieces: the runtime splits an odd-sized fill into two kernels)
     uint32_t* const pmask = c->d_tile_ctr.p + RTS_ZERO_WORDS;
     lt.lap(1);
@@ -843,7 +830,6 @@ extern "C" int rts_trace_pulse_begin(RtsHandle c, const RtsPulse* p)
     const uint32_t chains = a.max_refr ? 3u : 1u;
     if ((uint64_t)n * chains > 0xfffffff0ULL) { rts_set_error("rts_trace_pulse: rays x chains exceeds 2^32"); return RTS_ERR_UNSUPPORTED; }
     a.total_threads = grid * RTS_BLOCK;
-    a.async_idle0 = c->async_idle0; a.async_idle1 = c->async_idle1; a.async_age = c->async_age;
     a.coop_spread = c->coop_spread;
     a.coop_walk_steps_lo = std::min(c->coop_walk_steps_lo, c->coop_walk_steps);
     a.coop_walk_steps = c->coop_walk_steps; a.coop_min_cost = c->coop_walk_steps ? std::min<uint32_t>(c->coop_floor, 1875u) : 0u;      // (nothing shorter than 50 us is looked at; RTS_COOP_STEPS=0: every tile is flagged)
@@ -860,7 +846,7 @@ extern "C" int rts_trace_pulse_begin(RtsHandle c, const RtsPulse* p)
         RTS_HIP(hipMemsetAsync(c->d_hit_t.p, 0, sizeof(float) * (size_t)n * (c->params.max_refl + 1), st));
     }
     a.pmask = lc.mask.n ? pmask : nullptr; a.pre_filter = pre_filter ? 1u : 0u;
-    a.nodes4 = c->scene->d_nodes4.p; a.nodes4v = (c->node_versions && !c->async_idle0) ? c->scene->d_nodes4v.p : nullptr; a.stack_lds = c->stack_lds; a.leaves = c->d_leaves.p; a.tri_nidx = c->scene->d_tri_nidx.p; a.normals = c->d_normals_world.p;
+    a.nodes4 = c->scene->d_nodes4.p; a.nodes4v = c->node_versions ? c->scene->d_nodes4v.p : nullptr; a.stack_lds = c->stack_lds; a.leaves = c->d_leaves.p; a.tri_nidx = c->scene->d_tri_nidx.p; a.normals = c->d_normals_world.p;
     a.targets = c->p_targets; a.rx = c->d_rx.p;
     a.recv_records = c->d_recv.p; a.all_records = c->d_all.p; a.counters = c->p_counters; a.block_counters = c->d_block_counters.p; a.dir_hist = c->d_dir_hist.p;
     a.hit_prim = c->d_hit_prim.p; a.hit_t = c->d_hit_t.p; a.stack_ovf = c->d_stack_ovf.p; a.child = c->d_child.p;
@@ -873,7 +859,6 @@ extern "C" int rts_trace_pulse_begin(RtsHandle c, const RtsPulse* p)
         a.coop_versions = c->coop_versions ? 1u : 0u;
         a.batch_dead = aligned ? (uint32_t)c->batch_dead : 0u;      // (a wave tile must be 64 CONSECUTIVE launch indices for the tile-level screen: rts_tile_maybe)
         const uint32_t n_hist = (uint32_t)((total + RTS_WTILE - 1) / RTS_WTILE);
-        RTS_HIP(c->d_tile_ctr.reserve(RTS_ZERO_WORDS + RTS_MASK_WORDS + 64)); c->p_counters = reinterpret_cast<unsigned long long*>(c->d_tile_ctr.p + RTS_OFF_COUNTERS); a.counters = c->p_counters;
         a.tile_ctr = c->d_tile_ctr.p;
         if (lpt && aligned && n_tiles > grid * (RTS_BLOCK / RTS_WTILE)) {
             if (c->hist->n != n_hist) {
@@ -884,9 +869,8 @@ extern "C" int rts_trace_pulse_begin(RtsHandle c, const RtsPulse* p)
             if (c->tile_cost_pending || c->hist->any) {
                 c->coop_big_now = (il_parts > 1 && !shared_gpu && c->coop_big_part > c->coop_big) ? c->coop_big_part : c->coop_big;
                 int rc = rts_tile_order_build(c, c->tile_cost_sig, c->tile_cost_pending, sig, n_tiles, grid * (RTS_BLOCK / RTS_WTILE)); if (rc != RTS_OK) return rc;
-                a.xcd_seg = c->xcd_affine_now ? c->d_xcd.p : nullptr;
                 a.tile_order = c->d_tile_order.p; a.tile_head = c->coop_frac > 0.0 ? c->d_tile_ctr.p + RTS_OFF_HEAD + 2 : nullptr; a.tile_head_all = a.tile_head; c->hist->any = true;
-                a.tile_live = c->d_tile_ctr.p + RTS_OFF_LIVE;      // (written by the order build when it counts bins; else it stays at the fill's 0 = unknown)
+                a.tile_live = c->d_tile_ctr.p + RTS_OFF_LIVE;      // (written by the order build)
             }
             const bool merged_all = c->tile_cost_pending && (c->tile_cost_sig[0] + RTS_WTILE - 1) / RTS_WTILE >= n_tiles && c->d_tile_cost.cap >= n_tiles;      // k_tile_merge read AND cleared the records
             RTS_HIP(c->d_tile_cost.reserve(n_tiles));
@@ -967,6 +951,16 @@ static void rts_pulse_account(RtsContext* c, const unsigned long long* cnt)
     c->recv_hint = cnt[0]; c->recv_hint_valid = true;
 }
 
+// the counters of a finished launch, once the host has waited for its stream: the launch's own failures, then the received count and
+// the order's head count (sizes the next cooperative grid of the handle and of those that share its history)
+static int rts_counters_home(RtsContext* c, const unsigned long long* cnt)
+{
+    if (cnt[13]) { rts_set_error("rts_trace_pulse: %llu counter rows of the launch were never written by their blocks (counting build)", cnt[13]); return RTS_ERR_HIP; }
+    if (cnt[6]) { rts_set_error("rts_trace_pulse: traversal stack overflow / malformed BVH guard tripped on %llu waves", cnt[6]); return RTS_ERR_HIP; }
+    c->n_recv = cnt[0]; c->n_head_hint = (uint32_t)cnt[7]; c->hist->head_hint = c->n_head_hint; c->hist->head_hint_valid = true;
+    return RTS_OK;
+}
+
 extern "C" int rts_trace_pulse_end(RtsHandle c)
 {
     CHECK_HANDLE(c);
@@ -976,9 +970,7 @@ extern "C" int rts_trace_pulse_end(RtsHandle c)
     const bool keep_all = (c->params.flags & RTS_FLAG_KEEP_ALL_RAYS) != 0;
     unsigned long long* cnt = c->pin->cnt;
     RTS_HIP(rts_stream_wait(c, st));                // the one host sync of the launch: the received count sizes what follows
-    if (cnt[13]) { rts_set_error("rts_trace_pulse: %llu counter rows of the launch were never written by their blocks (counting build)", cnt[13]); return RTS_ERR_HIP; }
-    if (cnt[6]) { rts_set_error("rts_trace_pulse: traversal stack overflow / malformed BVH guard tripped on %llu waves", cnt[6]); return RTS_ERR_HIP; }
-    c->n_recv = cnt[0]; c->n_head_hint = (uint32_t)cnt[7]; c->hist->head_hint = c->n_head_hint; c->hist->head_hint_valid = true;
+    { int rc = rts_counters_home(c, cnt); if (rc != RTS_OK) return rc; }
     if (c->tl_blocks) {      // RTS_TIMELINE_BLOCKS: the launch as a bulk (every block resident) and a tail (rts_get_block_timeline; profiles/r05h_batch_launch.log)
         std::vector<unsigned long long> h((size_t)c->tl_blocks * 2);
         (void)hipMemcpy(h.data(), c->d_timeline.p, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost);
@@ -991,9 +983,9 @@ extern "C" int rts_trace_pulse_end(RtsHandle c)
         if (c->debug_coop) fprintf(stderr, "[rts] blocks of handle %p (us after the first start): start p50 %.1f max %.1f | end min %.1f p10 %.1f p50 %.1f p90 %.1f max %.1f\n", (void*)c,
                                    c->tl_summary[1], c->tl_summary[2], c->tl_summary[3], c->tl_summary[4], c->tl_summary[5], c->tl_summary[6], c->tl_summary[7]);
     }
-    if (c->debug_coop && c->d_xcd.p && c->d_tile_ctr.p) {      // debug: what the head rule of this launch's order build saw (blocking read-backs)
+    if (c->debug_coop && c->d_order_sum.p && c->d_tile_ctr.p) {      // debug: what the head rule of this launch's order build saw (blocking read-backs)
         unsigned long long sums[2] = {0, 0};
-        (void)hipMemcpy(&sums[0], c->d_xcd.p + 32, sizeof(unsigned long long), hipMemcpyDeviceToHost);
+        (void)hipMemcpy(&sums[0], c->d_order_sum.p, sizeof(unsigned long long), hipMemcpyDeviceToHost);
         (void)hipMemcpy(&sums[1], c->d_tile_ctr.p + RTS_OFF_HEAD, sizeof(unsigned long long), hipMemcpyDeviceToHost);
         uint32_t live_w = 0; (void)hipMemcpy(&live_w, c->d_tile_ctr.p + RTS_OFF_LIVE, sizeof(uint32_t), hipMemcpyDeviceToHost);
         fprintf(stderr, "[rts] end: handle %p head count %llu coop grid %u | cost sum persisted %llu, this build's %llu | live word %u of %u tiles\n", (void*)c, cnt[7], c->last_coop_grid, sums[0], sums[1], live_w, (c->n_rays + RTS_WTILE - 1) / RTS_WTILE);
@@ -1177,7 +1169,7 @@ static int rts_post_chain(RtsContext* c, bool ordered = false)      // ordered: 
     // (one block does in 150 us what seven launches -- four of them many blocks wide -- do in 92 us + six launch gaps for BASELINE configs[2]'s
     // ~1 900 received rays; for a few hundred rays it is the other way round: sequential pulses, one kernel against seven, C3 1.025 / 0.980 ms,
     // C2 (400 rays) 0.339 / 0.354, configs[4] (100) 0.955 / 0.978, profiles/r04_post_one_ab.log -- so the choice follows the handle's last count)
-    if (!ordered && q.mode == 0 && c->recv_dev && c->post_one && c->recv_hint_valid && c->recv_hint <= c->post_one_max && c->post_small && !keep_all && !c->mirror.want && c->n_recv <= c->spec_cap) {
+    if (!ordered && q.mode == 0 && c->recv_dev && c->recv_hint_valid && c->recv_hint <= c->post_one_max && c->post_small && !keep_all && !c->mirror.want && c->n_recv <= c->spec_cap) {
         // the speculative chain as ONE kernel (rts_post.hip: k_post_all): sized for the capacity, the count from the device
         RTS_HIP(hipEventRecord(c->ev[4], st)); RTS_HIP(hipEventRecord(c->ev[5], st)); RTS_HIP(hipEventRecord(c->ev[6], st));
         c->agg_pending.valid = false; c->groups.clear();
@@ -1209,9 +1201,7 @@ static int rts_spec_resolve(RtsContext* c)
     RTS_HIP(hipSetDevice(c->device));
     const unsigned long long* cnt = c->pin->cnt;
     RTS_HIP(rts_stream_wait(c, c->stream));
-    if (cnt[13]) { rts_set_error("rts_trace_pulse: %llu counter rows of the launch were never written by their blocks (counting build)", cnt[13]); return RTS_ERR_HIP; }      // (as rts_trace_pulse_end does: ADVICE r4)
-    if (cnt[6]) { rts_set_error("rts_trace_pulse: traversal stack overflow / malformed BVH guard tripped on %llu waves", cnt[6]); return RTS_ERR_HIP; }
-    c->n_recv = cnt[0]; c->n_head_hint = (uint32_t)cnt[7]; c->hist->head_hint = c->n_head_hint; c->hist->head_hint_valid = true;
+    { int rc = rts_counters_home(c, cnt); if (rc != RTS_OK) return rc; }
     c->recv_hint = cnt[0]; c->recv_hint_valid = true;                   // (the next pulse's choices -- speculate at all, one kernel or seven -- follow THIS pulse's count, not the handle's first)
     rts_pulse_account(c, cnt);
     if (c->n_recv > c->spec_cap) {                                      // more rays than the speculative chain was sized for: it did nothing; the ordinary chain now
@@ -1261,15 +1251,7 @@ static int rts_trace_pulse_end_chain(RtsContext* c)
     c->spec_pending = true;
     c->agg_timed = false; c->fin_timed = false;
     c->n_recv = c->spec_cap; c->recv_dev = c->p_counters;              // sizes for the capacity, the count itself from the device
-    // ... on the TRACE stream, behind the trace kernel: enqueued on the handle's other stream -- which waits for the trace through
-    // an event -- every launch call of the chain blocked (0.22 ms per pulse in the submitting thread)
-    int rc;
-    if (c->spec_on_trace_stream && c->tstream_now != c->stream) {
-        hipStream_t own = c->stream; c->stream = c->tstream_now;
-        rc = rts_post_chain(c);
-        RTS_HIP(hipEventRecord(c->ev_spec, c->tstream_now)); c->stream = own;
-        RTS_HIP(hipStreamWaitEvent(c->stream, c->ev_spec, 0));          // (what the handle enqueues next on its own stream comes after the chain)
-    } else rc = rts_post_chain(c);                                      // (the handle's own stream already waits for the trace: rts_trace_pulse_begin)
+    const int rc = rts_post_chain(c);                                   // (the handle's own stream already waits for the trace: rts_trace_pulse_begin)
     c->recv_dev = nullptr; c->n_recv = 0;
     if (rc != RTS_OK) { c->spec_pending = false; g_open_pulses[c->device & 63]--; return rc; }
     return RTS_OK;

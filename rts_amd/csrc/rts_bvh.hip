@@ -168,10 +168,10 @@ int rts_scene_place(RtsContext* c, const RtsLaunchConsts& lc, bool place, uint32
     const bool mask = f.n != 0;
     const RtsScene* sc = c->scene;
     // (the mask buffer -- behind the handle's zero block -- has been cleared with it: rts_trace_pulse_begin)
-    // ONE launch for a pulse that moves a target (RtsContext::place_fused, RTS_PLACE_FUSED=0: k_place + k_leaves): the leaf kernel
-    // places its primitive's vertices itself, its trailing blocks the normals.  (A later pulse that only re-marks the mask -- the
-    // targets stand still, the beam moved -- gathers from the world vertices: kept up to date by k_place in that mode only.)
-    if (place && c->place_fused && sc->n_prims) {
+    // ONE launch for a pulse that moves a target: the leaf kernel places its primitive's vertices itself, its trailing blocks the
+    // normals.  (A later pulse that only re-marks the mask -- the targets stand still, the beam moved -- gathers from the world
+    // vertices, which k_place brings up to date for that pass only.)
+    if (place && sc->n_prims) {
         const unsigned gp = blocks_for(sc->n_prims, 256), gn = blocks_for(sc->n_normals, 256);
         if (mask) k_leaves<true, true, true><<<gp + gn, 256, 0, st>>>(nullptr, sc->d_tri_vidx.p, sc->d_verts_local.p, sc->d_prim_targ.p, c->d_leaves.p, sc->n_prims, lc.ox, lc.oy, lc.oz, f, pmask,
                                                                      c->p_motion, gp, sc->d_normals_local.p, c->d_normals_world.p, sc->d_norm_targ.p, sc->n_normals);
@@ -181,20 +181,16 @@ int rts_scene_place(RtsContext* c, const RtsLaunchConsts& lc, bool place, uint32
         RTS_HIP(hipGetLastError());
         return RTS_OK;
     }
-    if (!place && mask && !c->verts_world_valid && sc->n_verts) {        // the world vertices the mask-only pass gathers from: placed now, once
-        k_place<<<blocks_for((size_t)sc->n_verts, 256), 256, 0, st>>>(sc->d_verts_local.p, c->d_verts_world.p, sc->d_vert_targ.p, sc->n_verts, sc->d_normals_local.p, c->d_normals_world.p, sc->d_norm_targ.p, 0u, c->p_motion);
-        c->verts_world_valid = true;
-    }
-    if (place) c->verts_world_valid = true;
-    if (place) {
+    if (place) {                                                     // a scene without primitives: there is nothing but the placement
         if (sc->n_verts + sc->n_normals) k_place<<<blocks_for((size_t)sc->n_verts + sc->n_normals, 256), 256, 0, st>>>(sc->d_verts_local.p, c->d_verts_world.p, sc->d_vert_targ.p, sc->n_verts,
                                                                                                                          sc->d_normals_local.p, c->d_normals_world.p, sc->d_norm_targ.p, sc->n_normals, c->p_motion);
-    }
-    if (sc->n_prims) {                                               // one leaf record per primitive (rts_api.hip: k_children_to_prims)
-        const unsigned g = blocks_for(sc->n_prims, 256);
-        if (place && mask) k_leaves<true, true><<<g, 256, 0, st>>>(nullptr, sc->d_tri_vidx.p, c->d_verts_world.p, sc->d_prim_targ.p, c->d_leaves.p, sc->n_prims, lc.ox, lc.oy, lc.oz, f, pmask);
-        else if (place) k_leaves<true, false><<<g, 256, 0, st>>>(nullptr, sc->d_tri_vidx.p, c->d_verts_world.p, sc->d_prim_targ.p, c->d_leaves.p, sc->n_prims, lc.ox, lc.oy, lc.oz, f, nullptr);
-        else if (mask) k_leaves<false, true><<<g, 256, 0, st>>>(nullptr, sc->d_tri_vidx.p, c->d_verts_world.p, sc->d_prim_targ.p, nullptr, sc->n_prims, lc.ox, lc.oy, lc.oz, f, pmask);
+        c->verts_world_valid = true;
+    } else if (mask) {                                               // the mask-only pass, one thread per primitive
+        if (!c->verts_world_valid && sc->n_verts) {                  // the world vertices it gathers from: placed now, once
+            k_place<<<blocks_for((size_t)sc->n_verts, 256), 256, 0, st>>>(sc->d_verts_local.p, c->d_verts_world.p, sc->d_vert_targ.p, sc->n_verts, sc->d_normals_local.p, c->d_normals_world.p, sc->d_norm_targ.p, 0u, c->p_motion);
+            c->verts_world_valid = true;
+        }
+        if (sc->n_prims) k_leaves<false, true><<<blocks_for(sc->n_prims, 256), 256, 0, st>>>(nullptr, sc->d_tri_vidx.p, c->d_verts_world.p, sc->d_prim_targ.p, nullptr, sc->n_prims, lc.ox, lc.oy, lc.oz, f, pmask);
     }
     RTS_HIP(hipGetLastError());
     return RTS_OK;

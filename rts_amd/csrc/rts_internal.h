@@ -86,21 +86,19 @@ static_assert(sizeof(RtsChildState) == 128, "child state size");
 #endif
 #define RTS_TILE_BUCKETS 1024       // bins of the tiles' counting order (rts_post.hip: k_tile_bucket_*)
 #define RTS_TILE_CTR_STRIDE 32     // ... one per 128-byte line: same-LINE atomics serialise in L2 (~10 ns each) whatever their address
-// XCD-AFFINE sub-orders (big launches, rts_post.hip: rts_tile_order_build): the order is cut into a head-rest segment + one segment
-// per XCD (a contiguous band of the lattice holding an eighth of the cost last seen), each drawn through 8 counters of its own
+// the cooperative kernel's per-XCD lists of head tiles (rts_trace.hip), each drawn through RTS_SEG_STRIPES counters of its own
 #define RTS_XCD 8
 #define RTS_SEG_STRIPES 8
-#define RTS_TILE_CTRS_LAYOUT ((RTS_XCD + 1) * RTS_SEG_STRIPES + 8)       // counters reserved per kernel in the zero block (>= RTS_TILE_CTRS)
-#define RTS_COARSE_CELLS 1024       // cost of the last launch by 1/1024 of its tile range (the bands' boundaries come from it)
+#define RTS_TILE_CTRS_LAYOUT ((RTS_XCD + 1) * RTS_SEG_STRIPES + 8)       // counters reserved per kernel in the zero block (>= RTS_TILE_CTRS, >= RTS_XCD * RTS_SEG_STRIPES; 80: the layout's size since round 4, kept so that no offset behind it moves)
 // the zero block: ONE fill per launch clears [draw counters of the ordinary kernel | of the cooperative kernel | head words: cost
-// sum lo, hi, head count, ticket | the launch's 16 u64 counters | the order's bins | the coarse cost cells]
+// sum lo, hi, head count, pad | the launch's 16 u64 counters | the order's bins | the bins' reservation counters of the two-launch order build]
 #define RTS_OFF_CTR_COOP (RTS_TILE_CTRS_LAYOUT * RTS_TILE_CTR_STRIDE)
 #define RTS_OFF_HEAD (2 * RTS_TILE_CTRS_LAYOUT * RTS_TILE_CTR_STRIDE)
 #define RTS_OFF_LIVE (RTS_OFF_HEAD + 4)       // 1 + the number of tiles at the front of this launch's order that cost more than a dead tile (0: unknown) -- written by the order build (rts_post.hip)
 #define RTS_OFF_COUNTERS (RTS_OFF_HEAD + 8)
 #define RTS_OFF_BINS (RTS_OFF_COUNTERS + 32)
-#define RTS_OFF_COARSE (RTS_OFF_BINS + RTS_TILE_BUCKETS)
-#define RTS_ZERO_WORDS (RTS_OFF_COARSE + RTS_COARSE_CELLS)
+#define RTS_OFF_TAKEN (RTS_OFF_BINS + RTS_TILE_BUCKETS)
+#define RTS_ZERO_WORDS (RTS_OFF_TAKEN + RTS_TILE_BUCKETS)
 #ifndef RTS_STACK_LDS
 #define RTS_STACK_LDS 24            // traversal stack entries kept in LDS per lane
 #endif
@@ -190,15 +188,12 @@ struct RtsTraceArgs {
     uint32_t* tile_cost;            // [wave tiles] out: duration of the tile (units of 8/3 ticks of the 100 MHz counter = 64 shader clocks at 2.4 GHz, + 1)
     uint32_t* tile_ctr;             // the zero block: draw counters (element s * RTS_TILE_CTR_STRIDE; the cooperative kernel's at RTS_OFF_CTR_COOP), zero at launch
     uint32_t coop_spread;           // 1, 2, 4 or 8: XCD lists a head tile's 64 cooperative units are dealt to (rts_trace.hip)
-    const uint32_t* xcd_seg;        // != null: XCD-affine sub-orders -- [RTS_XCD + 1] first position of each band's segment in tile_order (the last entry: its end)
     const uint32_t* tile_head;      // [1] number of tiles at the head of tile_order that are traced as 64 cooperative units (null: none)
     const uint32_t* tile_head_all;  // the same word whether or not this launch has a cooperative kernel (read back with the counters)
     const uint32_t* tile_live;      // != null: [1 + tiles at the front of tile_order that cost more than a dead tile last time] (0: unknown); the order behind them is drawn 64 tiles at a time, one LANE per tile (k_trace: dead-tile batches)
     uint32_t rx_window_screen;      // 1: the pre-filter also asks whether a crossing of a capture sphere can lie in the receiver's angular window (RTS_RX_WINDOW_SCREEN=0: only whether the sphere is reached)
     uint32_t coop_versions;         // 1: the cooperative kernel walks the octant versions too (product and counting builds of the plain chain; RTS_COOP_VERSIONS=0: the plain records and the sorted children)
     uint32_t batch_dead;            // 0: never batch; 1: batch the order's dead region (needs tile_live); 2: every position goes through the tile-level test first (RTS_DEAD_BATCH=all: tests)
-    uint32_t* done_ctr; uint32_t n_blocks_all; unsigned long long* host_cnt;      // the last block of the launch (ticket from done_ctr, zero at launch) sums the block counters and writes them home
-    uint32_t async_idle0, async_idle1, async_age;   // asynchronous bounces (rts_trace_unit_async): idle-lane limit of a walk phase for young / old tiles (0: lock-step kernel), age in cost units
     uint32_t coop_walk_steps_lo;    // ... bit 30 of the record: >= this many (LONGISH WALKS; the head rule asks more of such a tile's cost, rts_post.hip)
     uint32_t coop_min_cost, coop_walk_steps;   // a tile is flagged LONG WALKS (bit 31 of its cost record) if it took >= coop_min_cost units and >= coop_walk_steps walk iterations per bounce round
     unsigned long long* timeline;   // debug (RTS_TIMELINE, counting build): [grid][2] block start/end ticks, then [tiles] tile durations (100 MHz)
@@ -331,7 +326,7 @@ struct RtsContext {
     // per pulse
     uint64_t ray_first = 0; uint32_t n_rays = 0;
     DevBuf<RtsEndRecord> d_recv, d_all; DevBuf<unsigned long long> d_block_counters, d_timeline; unsigned long long* p_counters = nullptr;      // (the 16 counters live behind the draw counters: one fill zeroes both)
-    DevBuf<uint32_t> d_tile_cost, d_tile_key, d_tile_key_sorted, d_tile_id, d_tile_order, d_tile_ctr;
+    DevBuf<uint32_t> d_tile_cost, d_tile_key, d_tile_order, d_tile_ctr;
     RtsTileHist* hist = nullptr; bool share_history = true;      // never null after rts_create; shared with the handles of the same scene (rts_share_scene) unless RTS_SHARE_HISTORY=0
     uint32_t coop_floor = 7500;         // ... more than this many cost units (shader clocks >> 6; 7 500 = 0.2 ms of one wave) (RTS_COOP_FLOOR)
     uint32_t coop_walk_steps_lo = 400; double coop_mid = 1.5;      // LONGISH WALKS (RTS_COOP_STEPS_LO) go to the head only if the tile cost more than coop_mid x the balanced time (RTS_COOP_MID; 0: never).  3 in round 4;
@@ -346,7 +341,6 @@ struct RtsContext {
     double coop_big = 0.0;              // ... or ANY tile costing more than this multiple of the balanced time, whatever its shape (RTS_COOP_BIG; 0 = off, the default:
                                         // measured on C3 at 0.8 / 1.0 / 1.3 -- the slowest tile of a launch is rarely the slowest of the previous one once the target moves,
                                         // the launch's duration did not change (0.70-0.77 ms, peaks of 1.0 ms as before) and the handle's first such launch takes 10 ms)
-    uint32_t async_idle0 = 0, async_idle1 = 8, async_age = 7500;   // RTS_ASYNC_IDLE0 / _IDLE1 / _AGE (rts_trace_unit_async; idle0 = 0: the lock-step kernel)
     double coop_frac = 0.5;            // a tile costing more than this fraction of the launch's balanced time is traced as cooperative units (RTS_COOP_FRAC; 0: never)
     bool tile_cost_pending = false; uint64_t tile_cost_sig[4] = {0, 0, 0, 0};   // this handle's last launch left cost records that are not merged into the history yet (rts_post.hip)
     // tiles DEALT to this handle (rts_set_tile_list: ray sharding balanced by last-seen cost instead of interleaved parts): ascending tile
@@ -374,19 +368,14 @@ struct RtsContext {
     int batch_dead = 1;                 // dead-tile batches of the trace kernel (RTS_DEAD_BATCH = 0 / 1 / all)
     bool node_versions = true;          // the ordinary trace kernel walks the octant versions of the node records when the scene has them (RTS_NODE_VERSIONS=0: the role fetch + sorting network)
     bool debug_coop = false;            // RTS_DEBUG_COOP: one line per launch on stderr (grids, head hint, thresholds)
-    bool sum_in_kernel = false;         // the launch's last block sums the block counters (RTS_SUM_IN_KERNEL=1) instead of k_sum_counters -- measured SLOWER, off: the ticket's
-                                        // release / acquire fences (one per block) write back and invalidate L2, and the post-processing behind the trace took 0.40 instead of 0.34 ms
     bool spin_wait = true;              // the pulse's two host waits poll the stream instead of blocking (rts_stream_wait; RTS_SPIN_WAIT=0)
-    bool order_fused = true, order_sum_valid = false;        // the tile order in two launches when the previous launch had this launch's shape (RTS_ORDER_FUSED=0: four)
-    bool place_fused = true, verts_world_valid = false;      // the per-pulse scene update in one launch (RTS_PLACE_FUSED=0: k_place + k_leaves); d_verts_world holds the current placement
-    bool tile_bucket_order = true;      // tile order by counting bins instead of a radix sort (RTS_TILE_SORT=radix: the sort)
-    int xcd_affine = 0; bool xcd_affine_now = false; uint32_t xcd_bnd_tiles = 0; DevBuf<uint32_t> d_xcd;      // XCD-affine sub-orders of the ORDINARY kernel (RTS_XCD_AFFINE = 0, the default / 1 / auto; rts_post.hip: rts_tile_order_build) -- measured slower, DESIGN.md section 5
+    bool order_sum_valid = false; DevBuf<unsigned long long> d_order_sum;      // the tile order in two launches when the previous launch had this launch's shape: d_order_sum holds that launch's cost sum (rts_post.hip: rts_tile_order_build)
+    bool verts_world_valid = false;     // d_verts_world holds the current placement (the per-pulse scene update is one launch that writes the leaf records only: rts_scene_place)
     uint32_t post_prio = 3;             // s_setprio of k_post_all's waves (RTS_POST_PRIO = 0 .. 3)
-    uint64_t post_one_max = 1024;       // ... when the handle's previous pulse received at most this many rays (RTS_POST_ONE_MAX); above it the seven launches are faster
-    bool post_one = true;               // rts_trace_pulse_end_uniform: ONE kernel for order + expand + finalise + cube + aggregation of a small received set (RTS_POST_ONE=0: seven)
+    uint64_t post_one_max = 1024;       // rts_trace_pulse_end_uniform: ONE kernel for order + expand + finalise + cube + aggregation when the handle's previous pulse received at most this many rays (RTS_POST_ONE_MAX); above it the seven launches are faster
     bool post_small = true;             // received sets of up to 4096 rays are ordered / finished by single blocks (RTS_POST_SMALL=0: the general chain)
     hipStream_t tstream_now = nullptr; bool trace_own_stream = true;      // the stream this pulse's trace kernel went to (rts_trace_pulse_begin; RTS_TRACE_OWN_STREAM=0: always the trace stream)
-    hipEvent_t ev_spec = nullptr; uint32_t spec_cap = RTS_SMALL_CAP64; bool spec_on_trace_stream = false;      // (RTS_SPEC_STREAM=trace: the speculative chain behind the trace kernel on ITS stream)
+    uint32_t spec_cap = RTS_SMALL_CAP64;
     RtsSpecParams spec; bool spec_pending = false, spec_enabled = true;      // rts_trace_pulse_end_uniform: parameters of the chain; a chain enqueued on the device-side count awaits its resolution (RTS_SPECULATE=0: never)
     const unsigned long long* recv_dev = nullptr;                           // != nullptr while such a chain is being enqueued: its kernels take the received count from here
     uint64_t recv_hint = 0; bool recv_hint_valid = false;                    // received rays of the handle's previous pulse

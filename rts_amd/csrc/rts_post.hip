@@ -184,7 +184,7 @@ __device__ __forceinline__ uint32_t rts_record_to_keep(const uint32_t v, const u
 }
 
 // fold the costs measured by the previous launch into the history
-__global__ void k_tile_merge(uint32_t* __restrict__ cost, RtsTileShape prev, uint32_t* __restrict__ hist, uint32_t n_hist, unsigned long long* __restrict__ head_sum, uint32_t* __restrict__ coarse)
+__global__ void k_tile_merge(uint32_t* __restrict__ cost, RtsTileShape prev, uint32_t* __restrict__ hist, uint32_t n_hist, unsigned long long* __restrict__ head_sum)
 {
     uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
     unsigned long long v64 = 0;
@@ -193,16 +193,6 @@ __global__ void k_tile_merge(uint32_t* __restrict__ cost, RtsTileShape prev, uin
         if (v && g < n_hist) hist[g] = rts_record_to_keep(v, hist[g]);
         v64 = v & 0x3fffffffu;
         cost[j] = 0u;                                                          // (ready for the coming launch: no fill of its own)
-    }
-    if (coarse) {                                                              // (uniform) XCD-affine sub-orders: the launch's cost by 1/1024 of its tile range, in units of 16
-        __shared__ uint32_t s_cc[257];                                         // a block's 256 tiles touch at most 257 cells (one or two when the launch is large)
-        for (uint32_t q = threadIdx.x; q < 257u; q += blockDim.x) s_cc[q] = 0u;
-        __syncthreads();
-        const uint32_t cell0 = (uint32_t)(((unsigned long long)(blockIdx.x * blockDim.x) * RTS_COARSE_CELLS) / prev.n_tiles);
-        if (j < prev.n_tiles && v64) atomicAdd(&s_cc[(uint32_t)(((unsigned long long)j * RTS_COARSE_CELLS) / prev.n_tiles) - cell0], (uint32_t)((v64 + 15u) >> 4));
-        __syncthreads();
-        for (uint32_t q = threadIdx.x; q < 257u; q += blockDim.x) if (s_cc[q] && cell0 + q < RTS_COARSE_CELLS) atomicAdd(&coarse[cell0 + q], s_cc[q]);
-        __syncthreads();
     }
     // one atomic per BLOCK (per wave they were 2 400 on one address for a C3 launch: ~25 us of serialised L2 atomics on the
     // critical chain of every pulse)
@@ -213,12 +203,11 @@ __global__ void k_tile_merge(uint32_t* __restrict__ cost, RtsTileShape prev, uin
     if (threadIdx.x == 0 && head_sum) { const unsigned long long t = s_part[0] + s_part[1] + s_part[2] + s_part[3]; if (t) atomicAdd(head_sum, t); }
 }
 
-// sort key of local tile j of the coming launch: ~(estimated cost record); a tile never traced yet takes the largest record
-// known within 16 global tiles of it (expensive regions are contiguous in launch-index space).  Flagged records sort first
-// (their bit 31), by descending cost: the flagged tiles above the threshold are a prefix of the order.
-__global__ void k_tile_keys(const uint32_t* __restrict__ hist, uint32_t n_hist, RtsTileShape cur, uint32_t* __restrict__ key, uint32_t* __restrict__ id,
-                            const unsigned long long* __restrict__ head_sum, uint32_t* __restrict__ head_count, RtsHeadRule rule, uint32_t* __restrict__ bucket_hist,
-                            int affine, const uint32_t* __restrict__ bnd)
+// key of local tile j of the coming launch: the bin of its estimated cost record in the counting order; a tile never traced yet
+// takes the largest record known within 16 global tiles of it (expensive regions are contiguous in launch-index space).  The
+// tiles the head rule picks take the first half of the bins: they are a prefix of the order.
+__global__ void k_tile_keys(const uint32_t* __restrict__ hist, uint32_t n_hist, RtsTileShape cur, uint32_t* __restrict__ key,
+                            const unsigned long long* __restrict__ head_sum, uint32_t* __restrict__ head_count, RtsHeadRule rule, uint32_t* __restrict__ bucket_hist)
 {
     uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t is_head = 0, bucket = 0;
@@ -232,8 +221,8 @@ __global__ void k_tile_keys(const uint32_t* __restrict__ hist, uint32_t n_hist, 
             }
         }
         // head of the order = the tiles the cooperative kernel traces: LONG WALKS tiles above frac x the balanced time (and, as an
-        // experiment that is OFF by default -- RtsContext::coop_big -- any tile above big x the balanced time).  The key's top bit
-        // is this DECISION (not the record's flag): the head is a prefix of the sorted order.
+        // experiment that is OFF by default -- RtsContext::coop_big -- any tile above big x the balanced time).  The half of the
+        // bins is this DECISION (not the record's flag): the head is a prefix of the order.
         const uint32_t cost = est & 0x3fffffffu;
         if (head_count && rule.frac > 0.0) {
             const double balanced = (double)head_sum[0] / (double)(rule.resident_waves ? rule.resident_waves : 1u);
@@ -241,28 +230,17 @@ __global__ void k_tile_keys(const uint32_t* __restrict__ hist, uint32_t n_hist, 
             double thr_big = rule.big * balanced; if (thr_big < (double)rule.floor_cost) thr_big = (double)rule.floor_cost;
             is_head = rts_head_rule(est, (double)cost, balanced, thr, thr_big, rule) ? 1u : 0u;
         }
-        key[j] = ~((is_head << 31) | cost); id[j] = j;
-        // bucket of the counting order (bucket_hist != nullptr): the head of the order in the first half of the bins, the rest in
+        // bucket of the counting order: the head of the order in the first half of the bins, the rest in
         // the second, each by descending cost in steps of 1/16 octave -- finer than a tile's cost repeats from pulse to pulse
         // (the head is ordered too: its longest cooperative unit has to start first)
         bucket = (is_head ? 0u : RTS_TILE_BUCKETS / 2u) + (RTS_TILE_BUCKETS / 2u - 1u) - (cost <= 1u ? 16u * cost : min((uint32_t)(__log2f((float)cost + 1.0f) * 16.0f), RTS_TILE_BUCKETS / 2u - 1u));      // (cost 1, a dead tile: RTS_DEAD_BIN, said exactly)
-        if (affine) {
-            // XCD-affine sub-orders: [64 head bins, half octaves | RTS_XCD bands x 120 bins, quarter octaves]; band = the contiguous range
-            // of local tile indices (a slab of the lattice) that held an eighth of the cost of the launch before last (bnd: written by
-            // k_tile_bucket_scan of the previous build; none yet: equal counts)
-            uint32_t band = 0;
-            if (bnd) { for (uint32_t r = 1; r < RTS_XCD; r++) if (j >= bnd[r]) band = r; }
-            else band = min((uint32_t)(((unsigned long long)j * RTS_XCD) / cur.n_tiles), (uint32_t)RTS_XCD - 1u);
-            const float lg = __log2f((float)cost + 1.0f);
-            bucket = is_head ? 63u - min((uint32_t)(lg * 2.0f), 63u) : 64u + band * 120u + 119u - min((uint32_t)(lg * 4.0f), 119u);
-        }
-        if (bucket_hist) key[j] = bucket;
+        key[j] = bucket;
     }
     if (head_count) {                                                          // (uniform)
         const unsigned long long m = __ballot(is_head != 0);
         if ((threadIdx.x & 63) == 0 && m) atomicAdd(head_count, (uint32_t)__popcll(m));      // (heads are rare: a handful of waves at most)
     }
-    if (bucket_hist) {                                                         // (uniform) block histogram in LDS, one global atomic per non-empty bin
+    {                                                                          // block histogram in LDS, one global atomic per non-empty bin
         __shared__ uint32_t s_cnt[RTS_TILE_BUCKETS];
         for (uint32_t b = threadIdx.x; b < RTS_TILE_BUCKETS; b += blockDim.x) s_cnt[b] = 0u;
         __syncthreads();
@@ -276,13 +254,10 @@ __global__ void k_tile_keys(const uint32_t* __restrict__ hist, uint32_t n_hist, 
 // every trace launch): histogram in k_tile_keys, exclusive scan of the 1 024 bins by one block, and a scatter in which every
 // block reserves its share of each bin with ONE atomic and ranks its tiles inside it in LDS.  Tiles of a bin come out in no
 // particular order (only the schedule depends on it); the head of the order is the first half of the bins, a prefix as before.
-// xcd != null (XCD-affine sub-orders): xcd[0 .. RTS_XCD] <- first order position of each band's segment (the last entry: the number of
-// tiles), and xcd[16 .. 16 + RTS_XCD] <- the bands of the NEXT build: local tile indices at which the cost cells of the launch just
-// merged (coarse) reach 1/8, 2/8, ... of their sum
 // The bin of a DEAD tile (cost record 1: every launch index cleared by the pre-filter, k_trace): everything in front of it in the order cost more.
 // Its first position + 1 goes to `live` (the trace kernel draws the order behind it 64 tiles at a time, one lane per tile).
 #define RTS_DEAD_BIN (RTS_TILE_BUCKETS / 2u + (RTS_TILE_BUCKETS / 2u - 1u) - 16u)       // (is_head ? 0 : 512) + 511 - min(log2(1 + 1) * 16, 511)
-__global__ void __launch_bounds__(RTS_TILE_BUCKETS) k_tile_bucket_scan(uint32_t* __restrict__ hist, uint32_t* __restrict__ xcd, const uint32_t* __restrict__ coarse, uint32_t n_tiles, uint32_t* __restrict__ live)
+__global__ void __launch_bounds__(RTS_TILE_BUCKETS) k_tile_bucket_scan(uint32_t* __restrict__ hist, uint32_t* __restrict__ live)
 {
     __shared__ uint32_t s[2][RTS_TILE_BUCKETS];
     const uint32_t t = threadIdx.x, v = hist[t];
@@ -290,23 +265,7 @@ __global__ void __launch_bounds__(RTS_TILE_BUCKETS) k_tile_bucket_scan(uint32_t*
     int cur = 0;
     for (uint32_t off = 1; off < RTS_TILE_BUCKETS; off <<= 1) { uint32_t x = s[cur][t]; if (t >= off) x += s[cur][t - off]; s[cur ^ 1][t] = x; cur ^= 1; __syncthreads(); }
     hist[t] = s[cur][t] - v;                                                   // exclusive: first position of the bin
-    if (live && t == RTS_DEAD_BIN) live[0] = s[cur][t] - v + 1u;
-    if (!xcd) return;                                                          // (uniform)
-    if (t >= 64u && (t - 64u) % 120u == 0u && (t - 64u) / 120u < RTS_XCD) xcd[(t - 64u) / 120u] = s[cur][t] - v;
-    if (t == 0) xcd[RTS_XCD] = s[cur][RTS_TILE_BUCKETS - 1];
-    __syncthreads();
-    static_assert(RTS_COARSE_CELLS == RTS_TILE_BUCKETS, "one thread per coarse cell");
-    __shared__ unsigned long long p[2][RTS_COARSE_CELLS];
-    p[0][t] = coarse[t]; __syncthreads();
-    cur = 0;
-    for (uint32_t off = 1; off < RTS_COARSE_CELLS; off <<= 1) { unsigned long long x = p[cur][t]; if (t >= off) x += p[cur][t - off]; p[cur ^ 1][t] = x; cur ^= 1; __syncthreads(); }
-    const unsigned long long total = p[cur][RTS_COARSE_CELLS - 1], mine = p[cur][t], before = t ? p[cur][t - 1] : 0ULL;
-    if (t == 0) { xcd[16] = 0u; xcd[16 + RTS_XCD] = n_tiles; }
-    for (uint32_t r = 1; r < RTS_XCD; r++) {
-        if (total == 0ULL) { if (t == 0) xcd[16 + r] = (uint32_t)(((unsigned long long)n_tiles * r) / RTS_XCD); continue; }
-        const unsigned long long thr = (total * r + RTS_XCD - 1u) / RTS_XCD;      // band r starts behind the cell in which the running sum reaches r/8 of the total
-        if (before < thr && mine >= thr) xcd[16 + r] = (uint32_t)(((unsigned long long)(t + 1u) * n_tiles) / RTS_COARSE_CELLS);
-    }
+    if (t == RTS_DEAD_BIN) live[0] = s[cur][t] - v + 1u;
 }
 __global__ void __launch_bounds__(256) k_tile_bucket_scatter(const uint32_t* __restrict__ bucket_of, uint32_t n, uint32_t* __restrict__ next, uint32_t* __restrict__ order)
 {
@@ -430,7 +389,7 @@ int rts_tile_costs_flush(RtsContext* c)
     if (c->hist->n == 0 || !c->d_tile_cost.p || !c->hist->d.p) return RTS_OK;
     const RtsTileShape p = rts_shape_of(c, c->tile_cost_sig);
     if (p.n_tiles == 0) return RTS_OK;
-    k_tile_merge<<<blocks_for(p.n_tiles, 256), 256, 0, c->stream>>>(c->d_tile_cost.p, p, c->hist->d.p, c->hist->n, nullptr, nullptr);
+    k_tile_merge<<<blocks_for(p.n_tiles, 256), 256, 0, c->stream>>>(c->d_tile_cost.p, p, c->hist->d.p, c->hist->n, nullptr);
     RTS_HIP(hipGetLastError());
     c->hist->any = true;
     return RTS_OK;
@@ -456,51 +415,29 @@ int rts_tile_order_build(RtsContext* c, const uint64_t* prev_sig, bool prev_vali
     auto shape = [c](const uint64_t* sig) { RtsTileShape s; s.first = sig[1]; s.il_tile = (uint32_t)(sig[2] & 0xffffffffu); s.il_parts = (uint32_t)(sig[2] >> 32); s.il_part = (uint32_t)sig[3];
                                            s.n_tiles = (uint32_t)((sig[0] + RTS_WTILE - 1) / RTS_WTILE); s.il_list = s.il_parts == RTS_INTERLEAVE_LIST ? c->d_il_list.p : nullptr; return s; };
     uint32_t* head = c->coop_frac > 0.0 ? c->d_tile_ctr.p + RTS_OFF_HEAD : nullptr;      // [sum lo, sum hi, count, pad]: zeroed with the draw counters
-    uint32_t* bins = c->tile_bucket_order ? c->d_tile_ctr.p + RTS_OFF_BINS : nullptr;      // zeroed with the draw counters
-    // XCD-AFFINE sub-orders (RtsContext::xcd_affine: 0 never -- the default: measured slower, DESIGN.md section 5 --, 1 whenever there is a counting order, 2 for launches of
-    // >= 2^18 wave tiles, i.e. BASELINE configs[3]'s 100 M launch indices, whose scene is a hundred times an XCD's L2)
-    const bool affine = bins != nullptr && (c->xcd_affine == 1 || (c->xcd_affine == 2 && n_tiles_cur >= (1u << 18)));
-    c->xcd_affine_now = affine;
-    if (affine) RTS_HIP(c->d_xcd.reserve(64));
-    uint32_t* coarse = affine ? c->d_tile_ctr.p + RTS_OFF_COARSE : nullptr;
-    if (bins && !affine && c->order_fused && prev_valid && memcmp(prev_sig, cur_sig, 4 * sizeof(uint64_t)) == 0 && c->order_sum_valid) {
-        const RtsTileShape cur2 = shape(cur_sig);
-        const RtsHeadRule rule2 = {c->coop_frac, c->coop_big_now, c->coop_mid, c->coop_floor, resident_waves};
-        RTS_HIP(c->d_tile_key.reserve(n_tiles_cur)); RTS_HIP(c->d_tile_order.reserve(n_tiles_cur)); RTS_HIP(c->d_xcd.reserve(64));
-        unsigned long long* persist = reinterpret_cast<unsigned long long*>(c->d_xcd.p + 32);
-        const uint32_t per = (n_tiles_cur + (256u << 10) - 1u) / (256u << 10), fat = blocks_for(n_tiles_cur, 256u * per);      // at most 1 024 blocks
-        k_tile_merge_keys<<<fat, 256, 0, st>>>(c->d_tile_cost.p, cur2, c->hist->d.p, n_hist, reinterpret_cast<unsigned long long*>(head), persist, head ? head + 2 : nullptr, rule2, c->d_tile_key.p, bins, per);
-        k_tile_scan_scatter<<<fat, 256, 0, st>>>(c->d_tile_key.p, n_tiles_cur, bins, c->d_tile_ctr.p + RTS_OFF_COARSE, c->d_tile_order.p, reinterpret_cast<const unsigned long long*>(head), head ? persist : nullptr, per, c->d_tile_ctr.p + RTS_OFF_LIVE);
-        RTS_HIP(hipGetLastError());
-        return RTS_OK;
-    }
-    bool merged = false;
-    if (!prev_valid && head) { const RtsTileShape cur0 = shape(cur_sig); k_tile_est_sum<<<blocks_for(n_tiles_cur, 256), 256, 0, st>>>(c->hist->d.p, n_hist, cur0, reinterpret_cast<unsigned long long*>(head)); }
-    if (prev_valid) { const RtsTileShape p = shape(prev_sig); if (p.n_tiles) { k_tile_merge<<<blocks_for(p.n_tiles, 256), 256, 0, st>>>(c->d_tile_cost.p, p, c->hist->d.p, n_hist, reinterpret_cast<unsigned long long*>(head), coarse); merged = p.n_tiles == n_tiles_cur; } }
-    RTS_HIP(c->d_tile_key.reserve(n_tiles_cur)); RTS_HIP(c->d_tile_key_sorted.reserve(n_tiles_cur)); RTS_HIP(c->d_tile_id.reserve(n_tiles_cur)); RTS_HIP(c->d_tile_order.reserve(n_tiles_cur));
+    uint32_t* bins = c->d_tile_ctr.p + RTS_OFF_BINS, *taken = c->d_tile_ctr.p + RTS_OFF_TAKEN, *live = c->d_tile_ctr.p + RTS_OFF_LIVE;      // zeroed with the draw counters
     const RtsTileShape cur = shape(cur_sig);
     const RtsHeadRule rule = {c->coop_frac, c->coop_big_now, c->coop_mid, c->coop_floor, resident_waves};
-    // (the bands in force were computed by the previous build's scan from the launch before last; a launch of another shape, or no
-    // build yet: equal counts)
-    const uint32_t* bnd = affine && c->xcd_bnd_tiles == n_tiles_cur ? c->d_xcd.p + 16 : nullptr;
-    k_tile_keys<<<blocks_for(n_tiles_cur, 256), 256, 0, st>>>(c->hist->d.p, n_hist, cur, c->d_tile_key.p, c->d_tile_id.p, reinterpret_cast<const unsigned long long*>(head), head ? head + 2 : nullptr, rule, bins,
-                                                              affine ? 1 : 0, bnd);
-    if (bins) {
-        k_tile_bucket_scan<<<1, RTS_TILE_BUCKETS, 0, st>>>(bins, affine ? c->d_xcd.p : nullptr, coarse, n_tiles_cur, affine ? nullptr : c->d_tile_ctr.p + RTS_OFF_LIVE);      // (the affine keys use other bins)
-        if (affine) c->xcd_bnd_tiles = merged ? n_tiles_cur : 0u;               // (bands from a launch of another shape are not used)
-        k_tile_bucket_scatter<<<blocks_for(n_tiles_cur, 256), 256, 0, st>>>(c->d_tile_key.p, n_tiles_cur, bins, c->d_tile_order.p);
+    RTS_HIP(c->d_tile_key.reserve(n_tiles_cur)); RTS_HIP(c->d_tile_order.reserve(n_tiles_cur)); RTS_HIP(c->d_order_sum.reserve(1));
+    unsigned long long* persist = c->d_order_sum.p;      // the cost sum of the launch before, kept from build to build for the two-launch form
+    if (prev_valid && memcmp(prev_sig, cur_sig, 4 * sizeof(uint64_t)) == 0 && c->order_sum_valid) {
+        const uint32_t per = (n_tiles_cur + (256u << 10) - 1u) / (256u << 10), fat = blocks_for(n_tiles_cur, 256u * per);      // at most 1 024 blocks
+        k_tile_merge_keys<<<fat, 256, 0, st>>>(c->d_tile_cost.p, cur, c->hist->d.p, n_hist, reinterpret_cast<unsigned long long*>(head), persist, head ? head + 2 : nullptr, rule, c->d_tile_key.p, bins, per);
+        k_tile_scan_scatter<<<fat, 256, 0, st>>>(c->d_tile_key.p, n_tiles_cur, bins, taken, c->d_tile_order.p, reinterpret_cast<const unsigned long long*>(head), head ? persist : nullptr, per, live);
         RTS_HIP(hipGetLastError());
-        if (head && c->order_fused && prev_valid) {                     // the launch's cost sum, kept for the two-launch form of the next build
-            RTS_HIP(c->d_xcd.reserve(64));
-            RTS_HIP(hipMemcpyAsync(c->d_xcd.p + 32, head, sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
-            c->order_sum_valid = true;
-        } else if (!head && c->order_fused) { RTS_HIP(c->d_xcd.reserve(64)); RTS_HIP(hipMemsetAsync(c->d_xcd.p + 32, 0, sizeof(unsigned long long), st)); c->order_sum_valid = true; }
         return RTS_OK;
     }
-    size_t tmp = 0;
-    RTS_HIP(rocprim::radix_sort_pairs(nullptr, tmp, c->d_tile_key.p, c->d_tile_key_sorted.p, c->d_tile_id.p, c->d_tile_order.p, n_tiles_cur, 0, 32, st));
-    RTS_HIP(c->d_sort_tmp.reserve(tmp));
-    RTS_HIP(rocprim::radix_sort_pairs(c->d_sort_tmp.p, tmp, c->d_tile_key.p, c->d_tile_key_sorted.p, c->d_tile_id.p, c->d_tile_order.p, n_tiles_cur, 0, 32, st));
+    // a change of launch shape (or the handle's first build): four launches
+    if (!prev_valid && head) k_tile_est_sum<<<blocks_for(n_tiles_cur, 256), 256, 0, st>>>(c->hist->d.p, n_hist, cur, reinterpret_cast<unsigned long long*>(head));
+    if (prev_valid) { const RtsTileShape p = shape(prev_sig); if (p.n_tiles) k_tile_merge<<<blocks_for(p.n_tiles, 256), 256, 0, st>>>(c->d_tile_cost.p, p, c->hist->d.p, n_hist, reinterpret_cast<unsigned long long*>(head)); }
+    k_tile_keys<<<blocks_for(n_tiles_cur, 256), 256, 0, st>>>(c->hist->d.p, n_hist, cur, c->d_tile_key.p, reinterpret_cast<const unsigned long long*>(head), head ? head + 2 : nullptr, rule, bins);
+    k_tile_bucket_scan<<<1, RTS_TILE_BUCKETS, 0, st>>>(bins, live);
+    k_tile_bucket_scatter<<<blocks_for(n_tiles_cur, 256), 256, 0, st>>>(c->d_tile_key.p, n_tiles_cur, bins, c->d_tile_order.p);
+    RTS_HIP(hipGetLastError());
+    if (head && prev_valid) {                     // the launch's cost sum, kept for the two-launch form of the next build
+        RTS_HIP(hipMemcpyAsync(persist, head, sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
+        c->order_sum_valid = true;
+    } else if (!head) { RTS_HIP(hipMemsetAsync(persist, 0, sizeof(unsigned long long), st)); c->order_sum_valid = true; }
     return RTS_OK;
 }
 

@@ -418,8 +418,8 @@ struct RtsRay { dvec3 dir, prev; double rayLength, power, doppler, refx, refy; u
 
 // What happens to a ray after the walk of one segment: miss (receiver capture, Earth) or closest_hit (shading, the refracted
 // child, the reflected direction).  Returns true when the chain goes on with another segment.  ONE body for the three ways a
-// launch index is driven (lanes in lock step per bounce round; lanes advancing on their own, rts_trace_unit_async; one ray per
-// wave, COOP): same expressions, same operand order, bit-identical results.
+// launch index is driven (lanes in lock step per bounce round; one ray per wave, COOP; four rays per wave, COOP with octant
+// versions): same expressions, same operand order, bit-identical results.
 template <bool KEEP_ALL, bool REFR, bool COOP, uint32_t CG = 64u>
 __device__ __forceinline__ bool rts_shade(const RtsTraceArgs& a, const RtsUnitLds& L_, const uint32_t tid, const uint32_t gtid, const uint32_t lane, const uint32_t slot,
                                           const uint32_t chain, const uint32_t D, const uint32_t max_refr, const dvec3& origin, const bool primary, const bool may_rx,
@@ -953,143 +953,6 @@ __device__ __forceinline__ void rts_trace_unit(const RtsTraceArgs& a, const RtsL
 // a duration on the constant-rate counter (100 MHz ticks) in the unit of the tile-cost records: 64 shader clocks at 2.4 GHz = 8/3 ticks (k_trace)
 #define RTS_COST_UNITS(ticks) (((unsigned long long)(ticks) * 3ULL) >> 3)
 
-// ASYNCHRONOUS BOUNCES (the north star's "wave-level ballot / compaction of active rays"): the same launch
-// index per lane, but the lanes of a wave no longer move from segment to segment in lock step.  In rts_trace_unit a wave walks
-// until its SLOWEST lane has finished the segment (counting build, rts_get_lane_stats: 21-28 % of the issued lane-steps belong
-// to lanes that wait for that one, against 2 % to lanes whose ray has ended -- all that re-packing survivors between rounds
-// could recover).  Here a lane is in one of two states -- WALKING (node != sentinel) or ADVANCING (its walk of the current
-// target is over: try the next target's bounding sphere, or shade the segment and open the next one, or end) -- and the wave
-// alternates between an advance phase, run for the lanes that need it, and a walk phase that ends when no lane walks any more
-// OR when `idle_limit` lanes have come out of their walks: those are then advanced and re-join the walkers, whose walk state
-// (node, stack pointer, closest hit, prune bound, target: registers; the stack: LDS) simply stays where it is.
-// idle_limit = 64 is the lock-step schedule.  A low limit costs shading passes with few lanes in them (the shading code is
-// ~30 walk steps' worth of instructions), so the limit is a property of the TILE'S AGE: young tiles -- the 97 % that end within
-// a.async_age -- use a.async_idle0, tiles older than that a.async_idle1 (rts_api.hip: RTS_ASYNC_IDLE0/1, RTS_ASYNC_AGE).
-// No refraction chains here (REFR launches use rts_trace_unit).
-template <bool COUNT, bool KEEP_ALL>
-__device__ __forceinline__ void rts_trace_unit_async(const RtsTraceArgs& a, const RtsLaunchConsts& lc, const RtsUnitLds& L_, const uint32_t tid, const uint32_t gtid, const uint32_t lane,
-                                                     const uint32_t slot_in, const bool pre_on, const bool mask_on, const uint32_t D, const dvec3& origin, const long long tile_t0,
-                                                     uint32_t& n_nodes, uint32_t& n_tris, bool& hard_overflow, unsigned long long (&lane_stats)[5])
-{
-    int32_t* const s_stack = L_.stack; uint32_t* const s_n = L_.n;
-    const int SENTINEL = RTS_STACK_SENTINEL;
-    const int lds_cap = (int)a.stack_lds;
-    // Registers are what this schedule is short of: the walk state of the lanes that are NOT being advanced has to survive the
-    // shading code, on a kernel held to 128 VGPRs.  So between the phases a lane keeps its small payload fields packed in one
-    // word (`st`), the launch index is re-formed from the tile's first index (scalar) and the lane number where it is needed,
-    // and the malformed-tree guard counts the WAVE's walk iterations (scalar).
-    //   st: bits 0-7 reflDepth, 8 end, 9 chain_start, 10 live, 11 may_rx, 16-31 received + 1
-    const uint32_t slot0 = __builtin_amdgcn_readfirstlane(slot_in - lane);
-#define RTS_SLOT() (slot0 + __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)))
-    uint32_t st;
-    dvec3 dir, prev; double rayLength, power, doppler;
-    uint32_t targ;                                              // next target to try; the one being walked is targ - 1
-    {
-        RtsRay S;
-        bool may_target = a.n_prims > 0, may_rx = a.n_rx > 0;
-        rts_primary_setup(a, lc, L_, tid, slot_in, pre_on, mask_on, origin, S, may_target, may_rx);
-        dir = S.dir; prev = S.prev; rayLength = S.rayLength; power = S.power; doppler = S.doppler;
-        st = (1u << 9) | (1u << 10) | (may_rx ? 1u << 11 : 0u);
-        targ = may_target ? 0u : a.n_targets;                   // (a primary ray the pre-filter cleared tries no target)
-    }
-    // the open segment
-    float best_t = RTS_DEFAULT_TMAX, t_prune = RTS_DEFAULT_TMAX;
-    int best_leaf = -1; uint32_t best_prim = 0xffffffffu;
-    int node = SENTINEL, sp = 1;
-    uint32_t wave_steps = 0;
-    atomicAdd(&s_n[tid], RTS_SEG_ONE);
-    for (;;) {
-        // ---------------------------------------------------------------- advance: until the lane walks or its ray has ended
-        while ((st & (1u << 10)) && node == SENTINEL) {
-            if (targ < a.n_targets) {
-                const RtsTargetDev& TG = a.targets[targ++];
-                if (TG.root < 0) continue;
-                const dvec3 q = mk3(TG.cx - prev.x, TG.cy - prev.y, TG.cz - prev.z);          // bounding sphere of the placed target, as in rts_trace_unit
-                const double qq = q.x*q.x + q.y*q.y + q.z*q.z, b = q.x*dir.x + q.y*dir.y + q.z*dir.z;
-                if (qq > TG.r2) {
-                    const double dd = dir.x*dir.x + dir.y*dir.y + dir.z*dir.z;
-                    if (!(b > 0.0) || !(b*b >= (qq - TG.r2) * dd * 0.999999)) continue;
-                }
-                node = TG.root; sp = 1; s_stack[tid] = SENTINEL;
-            } else {
-                RtsRay S;
-                S.dir = dir; S.prev = prev; S.rayLength = rayLength; S.power = power; S.doppler = doppler; S.refx = 1; S.refy = 1;
-                S.reflDepth = st & 0xffu; S.refrDepth = 0; S.received = (int)(st >> 16) - 1; S.end = (st & (1u << 8)) != 0u; S.chain_start = (st & (1u << 9)) != 0u;
-                const bool primary = S.chain_start;
-                const float tmin = primary ? SCENE_EPS : SCENE_EPS_R;
-                uint32_t pending = 0, refr_code0 = 0;
-                const uint32_t slot = RTS_SLOT();
-                const bool go_on = rts_shade<KEEP_ALL, false, false>(a, L_, tid, gtid, lane, slot, 0u, D, 0u, origin, primary, (st & (1u << 11)) != 0u, best_t, best_leaf, best_prim, tmin, S, pending, refr_code0);
-                if (go_on) {
-                    atomicAdd(&s_n[tid], RTS_SEG_ONE);
-                    best_t = RTS_DEFAULT_TMAX; t_prune = RTS_DEFAULT_TMAX; best_leaf = -1; best_prim = 0xffffffffu;
-                    targ = a.n_prims > 0 ? 0u : a.n_targets;
-                } else {
-                    rts_write_back<KEEP_ALL, false, false>(a, L_, tid, lane, slot, 0u, S, pending, refr_code0);
-                }
-                dir = S.dir; prev = S.prev; rayLength = S.rayLength; power = S.power; doppler = S.doppler;
-                st = (S.reflDepth & 0xffu) | (S.end ? 1u << 8 : 0u) | (S.chain_start ? 1u << 9 : 0u) | (go_on ? 1u << 10 : 0u) | (st & (1u << 11)) | ((uint32_t)(S.received + 1) << 16);
-            }
-        }
-        const uint32_t n_live = (uint32_t)__popcll(__ballot((st & (1u << 10)) != 0u));
-        if (n_live == 0u) break;
-        // ---------------------------------------------------------------- the ray in the space of the lane's target (every live lane walks now;
-        // lanes that come back to a walk in progress recompute what they had: nothing of it is carried through the shading code)
-        RtsSlabRay lr;
-        {
-            const RtsTargetDev& TG = a.targets[targ - 1u];
-            const dvec3 q = mk3(prev.x - TG.px, prev.y - TG.py, prev.z - TG.pz);
-            const dvec3 ol = mk3(TG.rinv[0]*q.x + TG.rinv[1]*q.y + TG.rinv[2]*q.z, TG.rinv[3]*q.x + TG.rinv[4]*q.y + TG.rinv[5]*q.z, TG.rinv[6]*q.x + TG.rinv[7]*q.y + TG.rinv[8]*q.z);
-            const dvec3 dl = mk3(TG.rinv[0]*dir.x + TG.rinv[1]*dir.y + TG.rinv[2]*dir.z, TG.rinv[3]*dir.x + TG.rinv[4]*dir.y + TG.rinv[5]*dir.z,
-                                 TG.rinv[6]*dir.x + TG.rinv[7]*dir.y + TG.rinv[8]*dir.z);
-            lr = rts_slab_setup(ol, dl, TG.ew);
-        }
-        const float tmin = (st & (1u << 9)) ? SCENE_EPS : SCENE_EPS_R;
-        const uint32_t age = (uint32_t)RTS_COST_UNITS(wall_clock64() - tile_t0);                 // (s_memrealtime: wave-uniform)
-        const uint32_t idle_limit = age >= a.async_age ? a.async_idle1 : a.async_idle0;
-        // ---------------------------------------------------------------- walk
-        for (;;) {
-            if (node != SENTINEL) {
-                rts_walk_step<COUNT>(a, s_stack, tid, gtid, lds_cap, &s_n[2 * RTS_BLOCK + tid], node, sp, lr, prev, dir, tmin, best_t, best_leaf, best_prim, t_prune,
-                                     n_nodes, n_tris, hard_overflow);
-            }
-            if (++wave_steps > (1u << 26)) { hard_overflow = true; node = SENTINEL; }            // malformed tree guard (per wave and tile): every wave must drain
-            const uint32_t n_walk = (uint32_t)__popcll(__ballot(node != SENTINEL));
-            if (COUNT) { lane_stats[0] += 64u; lane_stats[1] += n_live; lane_stats[2] += n_walk; }     // (after the step: lanes that took it = n_walk + those that just finished; close enough for a ratio)
-            if (n_walk == 0u || n_live - n_walk >= idle_limit) break;
-        }
-    }
-#undef RTS_SLOT
-}
-
-// counters[1..6] = sum over the blocks of a launch (256 threads of ONE block; the launch has at most a few thousand blocks)
-// ... and all of them into the handle's pinned host block (host_cnt: device address of RtsPinned::cnt) -- the host reads them
-// after its wait for the stream, without a copy of their own.  s: 256 u64 of LDS.  Loads at agent scope (see k_trace's epilogue).
-__device__ __forceinline__ void rts_sum_counters_body(const uint32_t t, unsigned long long* s, const unsigned long long* block_counters, unsigned int n_blocks,
-                                                      unsigned long long* counters, const uint32_t* head_count, unsigned long long* host_cnt)
-{
-#define RTS_LD64(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-    if (t == 7) { const unsigned long long h = head_count ? (unsigned long long)__hip_atomic_load(head_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ULL; counters[7] = h; host_cnt[7] = h; }     // the order's head count travels home with the counters (sizes the next cooperative grid)
-    if (t == 0) host_cnt[0] = RTS_LD64(&counters[0]);                          // received rays (appended by the trace kernels)
-    if ((t >= 8 && t <= 12) || t == 14 || t == 15) host_cnt[t] = RTS_LD64(&counters[t]);      // lane statistics and walked segments of the counting build; [12] cost records dropped, [14] tiles (| XCC mask << 56) on which the shader clock ran backwards, [15] never-started lane-steps
-    const unsigned int k = t & 7u, lane = t >> 3;                              // 32 partial sums per counter
-    unsigned long long v = 0;
-    // (counting builds poison the rows before the launch -- rts_trace_launch -- : a row no block wrote is COUNTED, counters[13], instead
-    // of summed; round 3 saw such launches -- a garbage sum in counters[6] -- and could not reproduce them: this names them if they return)
-    unsigned long long poisoned = 0;
-    if (k >= 1 && k <= 6) for (unsigned int b = lane; b < n_blocks; b += 32) { const unsigned long long x = RTS_LD64(&block_counters[(size_t)b * 8 + k]); if (x == ~0ULL) poisoned++; else v += x; }
-    s[t] = v;
-    if (k == 1 && poisoned) { atomicAdd(&counters[13], poisoned); __threadfence(); }      // (the rows' first counter; never in a healthy launch)
-    __syncthreads();
-    if (t >= 1 && t <= 6) {
-        unsigned long long sum = 0;
-        for (unsigned int l = 0; l < 32; l++) sum += s[l * 8 + t];
-        counters[t] = sum; host_cnt[t] = sum;
-    }
-    if (t == 13) host_cnt[13] = RTS_LD64(&counters[13]);                       // rows of block_counters still poisoned (counting builds)
-#undef RTS_LD64
-}
-
 // KEEP_ALL is a template parameter, not a run-time flag: hipcc (ROCm 7.2) lowered the uniform
 // `if (a.keep_all)` to a per-lane v_cmp mask computed under the divergent exec of the bounce loop
 // and re-used it at the write-back under a different exec, so lanes that were inactive at the
@@ -1104,7 +967,7 @@ __device__ __forceinline__ void rts_sum_counters_body(const uint32_t t, unsigned
 // history): it traces the 64 n_head launch indices of the tiles at the head of the cost order, one per wave; the ordinary
 // kernel then starts at position n_head of the order.  A kernel of its own because the shared walk needs ~40 registers more
 // than the 128 the ordinary kernel is held to (four waves per SIMD).
-template <bool COUNT, bool KEEP_ALL, bool REFR, bool COOP, bool ASYNC = false, bool AFFINE = false, bool VERS = false>
+template <bool COUNT, bool KEEP_ALL, bool REFR, bool COOP, bool VERS = false>
 __global__ void __launch_bounds__(RTS_BLOCK, (REFR && COOP) ? 2 : ((REFR || COOP) ? 3 : 4)) k_trace(const RtsTraceArgs a)
 {
     __shared__ __attribute__((aligned(16))) int32_t s_stack[RTS_STACK_LDS * RTS_BLOCK];
@@ -1202,40 +1065,18 @@ __global__ void __launch_bounds__(RTS_BLOCK, (REFR && COOP) ? 2 : ((REFR || COOP
     const uint32_t n_units = COOP ? CG * n_head : n_tiles - n_head;
     __shared__ int32_t s_exch[COOP ? RTS_BLOCK : 1];             // exchange rows of the cooperative walk (one 64-entry row per wave)
     __shared__ uint32_t s_lane_scratch[COUNT ? 2 * (RTS_BLOCK / 64) : 1];      // (counting build: per-wave max / sum of a round's walk steps)
-    __shared__ uint32_t s_walk[ASYNC ? 1 : 2 * (RTS_BLOCK / 64)];           // per wave: walk iterations of the current tile (each walk's slowest lane), walks
+    __shared__ uint32_t s_walk[2 * (RTS_BLOCK / 64)];           // per wave: walk iterations of the current tile (each walk's slowest lane), walks
     const RtsUnitLds ul = {s_stack, s_exch, s_first, s_path, s_n, s_rx, s_rxp, s_lane_scratch, s_walk};
     unsigned long long lane_stats[5] = {0ull, 0ull, 0ull, 0ull, 0ull};
-    // XCD-AFFINE SUB-ORDERS (a.xcd_seg, big launches; ordinary kernel only): the order behind the head is cut into one segment per XCD
-    // -- a band of the lattice that held an eighth of the cost last seen, longest tiles first inside it -- so that the ~500 waves of
-    // an XCD trace neighbouring tiles at the same time and its 4 MB of L2 serves ONE part of a scene that is a hundred times that
-    // size (BASELINE configs[3]: every XCD used to stream the whole scene, 13.5 GB of fabric traffic per launch at an L2 hit rate
-    // of 0.66).  Segment 0 = what is left of the head when no cooperative kernel runs, segments 1 .. 8 = the bands; each has
-    // RTS_SEG_STRIPES draw counters.  A wave starts on segment 0, goes on with ITS XCD's band (HW_REG_XCC_ID) and, when that runs
-    // dry, with the next bands in turn -- every wave visits every segment, so every position is drawn whoever sits where.
-    // (a kernel of its own -- AFFINE -- whose queue state lives in LDS, one row per wave: as five more scalars of the ordinary kernel
-    // they pushed it over its 128 registers, 14 VGPRs into scratch)
-    static_assert(!AFFINE || (!COOP && !ASYNC), "affine sub-orders: ordinary lock-step kernel only");
-    __shared__ uint32_t s_seg[AFFINE ? RTS_XCD + 2 : 1];         // s_seg[i] .. s_seg[i + 1]: order positions of segment i
-    __shared__ uint32_t s_q[AFFINE ? (RTS_BLOCK / 64) * 8 : 1];  // per wave: [0] segment, [1] its first unit, [2] its length, [3] positions per stripe, [4] single draws, [5] segments visited
     // (LDS addresses formed from the scalar wave number AT EACH USE: hoisted out of the tile loop as vector registers they were
     // parked in scratch and reloaded eight times per draw)
 #define RTS_OPAQUE_S(x) ({ uint32_t o_ = (x); asm volatile("" : "+s"(o_)); o_; })
-#define RTS_Q(k) s_q[RTS_OPAQUE_S(wave_u) * 8u + (k)]
-    if (AFFINE) {
-        if (tid <= RTS_XCD) s_seg[tid + 1u] = max(min(a.xcd_seg[tid], n_tiles), n_head);
-        if (tid == 0) s_seg[0] = n_head;
-        __syncthreads();
-        if (lane == 0) {
-            const uint32_t len0 = s_seg[1] - s_seg[0], ps0 = (len0 + RTS_SEG_STRIPES - 1u) / RTS_SEG_STRIPES;
-            RTS_Q(0) = 0u; RTS_Q(1) = s_seg[0] - n_head; RTS_Q(2) = len0; RTS_Q(3) = ps0; RTS_Q(4) = ps0 >= 128u ? ps0 / 4u : ps0; RTS_Q(5) = 0u;
-        }
-    }
     // THE COOPERATIVE KERNEL keeps a head tile's 64 units on ONE XCD: head tile h belongs to the list of XCD h mod 8 (the head is
     // sorted by cost, so dealing it out in turn balances the lists), each list drawn through 8 counters; a wave works through its
     // own XCD's list first and then through the others'.  The 64 rays of a tile are 64 nearly parallel rays along one radial line
     // of the lattice: they walk the same few hundred KB of records, thousands of steps each -- spread over all eight XCDs (the
     // striped queue dealt unit v to stripe v mod 64) every L2 fetched every head tile's records: 5.4 of the 6.4 GB a BASELINE
-    // configs[3] launch moves over the fabric, at an L2 hit rate of 0.64 (profiles/r04_c4_xcd_affine_pmc.log).
+    // configs[3] launch moves over the fabric, at an L2 hit rate of 0.64 (the round-4 counter runs on BASELINE configs[3], profiles/README.md).
     // a.coop_spread = P in {1, 2, 4, 8}: a head tile's 64 units are dealt to P of the eight lists (rays r mod P = c to list
     // (h + (8 / P) c) mod 8); P = 1: the whole tile on one XCD, P = 8: eight rays on each (every L2 sees every tile).
     uint32_t coop_x = 0, coop_sweep = 0, coop_len = 0;           // (COOP) current list, lists visited, head tiles that feed the list
@@ -1246,8 +1087,8 @@ __global__ void __launch_bounds__(RTS_BLOCK, (REFR && COOP) ? 2 : ((REFR || COOP
         coop_x &= (RTS_XCD - 1u);
         coop_len = RTS_COOP_LEN(coop_x);
     }
-    const uint32_t S = (AFFINE || COOP) ? (uint32_t)RTS_SEG_STRIPES : (uint32_t)RTS_TILE_CTRS;      // stripes of a segment
-#define RTS_LSTRIPE (AFFINE ? (RTS_OPAQUE_S(stripe) & (RTS_SEG_STRIPES - 1u)) : (COOP ? (stripe & (RTS_SEG_STRIPES - 1u)) : RTS_OPAQUE_S(stripe)))      // (opaque: the draw counter's ADDRESS is formed at each draw -- hoisted, it is a vector register pair of the tile loop)
+    const uint32_t S = COOP ? (uint32_t)RTS_SEG_STRIPES : (uint32_t)RTS_TILE_CTRS;      // stripes of a list (COOP) / of the order
+#define RTS_LSTRIPE (COOP ? (stripe & (RTS_SEG_STRIPES - 1u)) : RTS_OPAQUE_S(stripe))      // (opaque: the draw counter's ADDRESS is formed at each draw -- hoisted, it is a vector register pair of the tile loop)
     const uint32_t per_stripe_all = (n_units + RTS_TILE_CTRS - 1u) / RTS_TILE_CTRS;
     // DEAD-TILE BATCHES (round 5).  Most wave tiles of a pulse are DEAD -- the pre-filter clears all 64 launch indices: 84 % of BASELINE
     // configs[2]'s tiles -- and the cost order keeps them at its end (cost record 1).  That part of the order is drawn 64 positions at
@@ -1258,7 +1099,7 @@ __global__ void __launch_bounds__(RTS_BLOCK, (REFR && COOP) ? 2 : ((REFR || COOP
     // a.batch_dead == 2 (every position is screened that way first: tests).  Ordinary lock-step kernel of aligned launches only.
     // (the schedule's three numbers and a batch's mask of live positions live in LDS, one row per wave, and are read once per DRAW: as
     // scalars of the kernel they were live through every tile's bounce loops -- 30 more scalar spills, and the pending draw in scratch)
-    constexpr bool BATCHABLE = !COOP && !ASYNC && !AFFINE && !KEEP_ALL;
+    constexpr bool BATCHABLE = !COOP && !KEEP_ALL;
     __shared__ uint32_t s_sched[(RTS_BLOCK / 64) * 8];      // per wave: [0] single draws, [1] draws of four, [2] k_dead, [3] [4] live mask of the batch in hand
 #define RTS_SCHED(k) s_sched[RTS_OPAQUE_S(wave_u) * 8u + (k)]
     const uint32_t single_draws_nobatch = per_stripe_all >= 1024u ? per_stripe_all / 4u : per_stripe_all;      // (short queues: one tile per draw throughout)
@@ -1291,12 +1132,12 @@ __global__ void __launch_bounds__(RTS_BLOCK, (REFR && COOP) ? 2 : ((REFR || COOP
     // unproven.  Product builds reload nothing from scratch (tests/test_host_logic.py checks the ISA).
     __shared__ uint32_t s_draw[RTS_BLOCK / 64];
     uint32_t draw_next = 0;
-#define RTS_DRAW() { const uint32_t dv_ = atomicAdd(&a.tile_ctr[(COOP ? RTS_OFF_CTR_COOP : 0) + ((AFFINE ? RTS_Q(0) * S : (COOP ? coop_x * S : 0u)) + RTS_LSTRIPE) * RTS_TILE_CTR_STRIDE], 1u); if (AFFINE) s_draw[RTS_OPAQUE_S(wave_u)] = dv_; else if (COUNT || KEEP_ALL) s_draw[wave_u] = dv_; else draw_next = dv_; }
+#define RTS_DRAW() { const uint32_t dv_ = atomicAdd(&a.tile_ctr[(COOP ? RTS_OFF_CTR_COOP : 0) + ((COOP ? coop_x * S : 0u) + RTS_LSTRIPE) * RTS_TILE_CTR_STRIDE], 1u); if (COUNT || KEEP_ALL) s_draw[wave_u] = dv_; else draw_next = dv_; }
     if (lane == 0) RTS_DRAW()
     for (;;) {
-      const uint32_t draw = __builtin_amdgcn_readfirstlane(AFFINE ? s_draw[RTS_OPAQUE_S(wave_u)] : ((COUNT || KEEP_ALL) ? s_draw[wave_u] : draw_next));      // (KEEP_ALL builds -- tests -- keep it in LDS too: their refraction instantiation parked it in scratch inside the tile loop)      // (AFFINE: in LDS like the counting builds' -- the kernel has no register for it across the tile loop, see above)
-      const uint32_t per_stripe = AFFINE ? __builtin_amdgcn_readfirstlane(RTS_Q(3)) : (COOP ? (coop_len * (CG / coop_P) + RTS_SEG_STRIPES - 1u) / RTS_SEG_STRIPES : per_stripe_all);
-      const uint32_t single_draws = AFFINE ? __builtin_amdgcn_readfirstlane(RTS_Q(4)) : (COOP ? per_stripe : (BATCHABLE ? __builtin_amdgcn_readfirstlane(RTS_SCHED(0)) : single_draws_all));      // (COOP: one unit per draw -- units are long)
+      const uint32_t draw = __builtin_amdgcn_readfirstlane((COUNT || KEEP_ALL) ? s_draw[wave_u] : draw_next);      // (KEEP_ALL builds -- tests -- keep it in LDS too: their refraction instantiation parked it in scratch inside the tile loop)
+      const uint32_t per_stripe = COOP ? (coop_len * (CG / coop_P) + RTS_SEG_STRIPES - 1u) / RTS_SEG_STRIPES : per_stripe_all;
+      const uint32_t single_draws = COOP ? per_stripe : (BATCHABLE ? __builtin_amdgcn_readfirstlane(RTS_SCHED(0)) : single_draws_all);      // (COOP: one unit per draw -- units are long)
       const uint32_t four_draws = BATCHABLE ? __builtin_amdgcn_readfirstlane(RTS_SCHED(1)) : 0u, k_dead = BATCHABLE ? __builtin_amdgcn_readfirstlane(RTS_SCHED(2)) : 0u;
       const bool batch = BATCHABLE && draw >= single_draws + four_draws;      // (uniform) a batch of 64 positions of the order's dead part
       const uint32_t k0 = draw < single_draws ? draw : (batch ? k_dead + 64u * (draw - single_draws - four_draws) : single_draws + 4u * (draw - single_draws));
@@ -1309,19 +1150,9 @@ __global__ void __launch_bounds__(RTS_BLOCK, (REFR && COOP) ? 2 : ((REFR || COOP
               if (lane == 0) RTS_DRAW()
               continue;
           }
-          if (!AFFINE) break;
-          const uint32_t sweep = __builtin_amdgcn_readfirstlane(RTS_Q(5)) + 1u;
-          if (sweep > RTS_XCD) break;
-          if (lane == 0) {
-              uint32_t xcc; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));      // (read where it is used: a scalar less to carry through the tile loop)
-              const uint32_t si = 1u + ((xcc & (RTS_XCD - 1u)) + sweep - 1u) % RTS_XCD;       // own band first, then the others in turn
-              const uint32_t len = s_seg[si + 1u] - s_seg[si], ps = (len + RTS_SEG_STRIPES - 1u) / RTS_SEG_STRIPES;
-              RTS_Q(0) = si; RTS_Q(1) = s_seg[si] - n_head; RTS_Q(2) = len; RTS_Q(3) = ps; RTS_Q(4) = ps >= 128u ? ps / 4u : ps; RTS_Q(5) = sweep;
-              RTS_DRAW()
-          }
-          continue;
+          break;
       }
-      const uint32_t seg_base = AFFINE ? __builtin_amdgcn_readfirstlane(RTS_Q(1)) : 0u, seg_len = AFFINE ? __builtin_amdgcn_readfirstlane(RTS_Q(2)) : (COOP ? coop_len * (CG / coop_P) : n_units);
+      const uint32_t seg_len = COOP ? coop_len * (CG / coop_P) : n_units;      // positions of the list (COOP) / of the order
       // (only in the cheap part of the order: a draw made before an EXPENSIVE tile would reserve the stripe's next most
       // expensive tile for as long as this one takes -- the launch then ends with that tile, traced alone)
       const bool ahead = draw >= single_draws;
@@ -1355,7 +1186,7 @@ __global__ void __launch_bounds__(RTS_BLOCK, (REFR && COOP) ? 2 : ((REFR || COOP
       if (vloc64 >= seg_len) break;
       // (COOP: unit u of list x: head tile h = x mod G + G (u / (64 / P)), ray c + P (u mod (64 / P)) with c = ((x - h) mod 8) / G;
       // vpos = 64 x head tile + ray, as before)
-      uint32_t vpos = seg_base + (uint32_t)vloc64;
+      uint32_t vpos = (uint32_t)vloc64;
       if (COOP) {
           const uint32_t per = CG / coop_P, j = (uint32_t)vloc64 / per, i = (uint32_t)vloc64 - j * per, h = (coop_x % coop_G) + coop_G * j;      // (CG units per head tile: unit q holds its rays RPU q .. RPU q + RPU - 1)
           vpos = (h << 6) | ((((coop_x - h) & (RTS_XCD - 1u)) / coop_G) + coop_P * i);
@@ -1371,7 +1202,7 @@ __global__ void __launch_bounds__(RTS_BLOCK, (REFR && COOP) ? 2 : ((REFR || COOP
       // (payload initialisation, the bounce loop's tests, clocks, the cost record's arithmetic: half of the ~190 vector and ~90 scalar
       // instructions such a tile cost, 10 % of a BASELINE configs[2] launch's instructions)
       uint32_t pre = 0u;
-      if (!COOP && !ASYNC && !KEEP_ALL && pre_on) {
+      if (!COOP && !KEEP_ALL && pre_on) {
           bool pre_target = a.n_prims > 0, pre_rx = a.n_rx > 0;
           if (slot < a.n_rays) rts_prefilter(lc, slot, mask_on, a.pmask, a.n_rx, s_rxp, pre_target, pre_rx);
           if (!__any(slot < a.n_rays && (pre_target || pre_rx))) {
@@ -1390,11 +1221,10 @@ __global__ void __launch_bounds__(RTS_BLOCK, (REFR && COOP) ? 2 : ((REFR || COOP
       const long long tile_t0 = wall_clock64();
       const long long tile_s0 = COUNT ? clock64() : 0;
       if (!COOP) atomicAnd(&s_n[tid], 0x003fffffu);              // (ds_and_b32: the tile's own segment count starts at zero; a register for it would be the 129th)
-      if (!COOP && !ASYNC && lane == 0) { const uint32_t z_ = RTS_OPAQUE_S(0u); s_walk[2u * wave_u] = z_; s_walk[2u * wave_u + 1u] = z_; }      // (an opaque zero: hoisted out of the tile loop as a register pair the constant was parked in SCRATCH and reloaded per tile)
+      if (!COOP && lane == 0) { const uint32_t z_ = RTS_OPAQUE_S(0u); s_walk[2u * wave_u] = z_; s_walk[2u * wave_u + 1u] = z_; }      // (an opaque zero: hoisted out of the tile loop as a register pair the constant was parked in SCRATCH and reloaded per tile)
       const unsigned long long tl_tile = (COUNT && a.timeline && lane == 0) ? wall_clock64() : 0ULL;
       if (slot < a.n_rays) {
-          if (ASYNC) rts_trace_unit_async<COUNT, KEEP_ALL>(a, lc, ul, tid, gtid, lane, slot, pre_on, mask_on, D, origin, tile_t0, n_nodes, n_tris, hard_overflow, lane_stats);
-          else rts_trace_unit<COUNT, KEEP_ALL, REFR, COOP, VERS>(a, lc, ul, tid, gtid, lane, slot, pre_on, mask_on, D, max_refr, origin, n_nodes, n_tris, hard_overflow, lane_stats, pre);
+          rts_trace_unit<COUNT, KEEP_ALL, REFR, COOP, VERS>(a, lc, ul, tid, gtid, lane, slot, pre_on, mask_on, D, max_refr, origin, n_nodes, n_tris, hard_overflow, lane_stats, pre);
       }   // slot < n_rays
       // (the segment count of the tile is only formed for tiles long enough to matter: an all-miss tile is ~100 instructions)
       const unsigned long long dt = RTS_COST_UNITS(wall_clock64() - tile_t0);                     // (s_memrealtime: wave-uniform)
@@ -1403,7 +1233,7 @@ __global__ void __launch_bounds__(RTS_BLOCK, (REFR && COOP) ? 2 : ((REFR || COOP
           atomicAdd(&a.counters[14], 1ULL); atomicOr(&a.counters[14], 1ULL << (56u + (xcc & 7u)));      // (count in the low bits, the XCCs' mask in bits 56-63)
       }
       bool long_walks = false, longish_walks = false;
-      if (!COOP && !ASYNC && a.tile_cost && dt >= a.coop_min_cost) {      // (the asynchronous-bounce experiment keeps no walk statistics: it flags nothing)
+      if (!COOP && a.tile_cost && dt >= a.coop_min_cost) {
           // LONG WALKS: the tile's bounce rounds took a.coop_walk_steps walk iterations of the wave on average -- rays that graze along a surface
           // through thousands of boxes (BASELINE configs[3]: ~4 000 per segment; an ordinary tile's walks: 20-150).  Counted, not
           // timed: a duration per segment (rounds 2-3) had to be judged against the launch's mean, and a launch that consists of its
@@ -1468,60 +1298,53 @@ __global__ void __launch_bounds__(RTS_BLOCK, (REFR && COOP) ? 2 : ((REFR || COOP
         else v = any_overflow ? 1ULL : 0ULL;
         a.block_counters[((size_t)(COOP ? a.total_threads / RTS_BLOCK : 0u) + blockIdx.x) * 8 + tid_e] = v;
     }
-    // The LAST block of the launch -- of either kernel -- to get here adds the blocks' rows up and writes the launch's counters
-    // into the handle's pinned host block: no kernel of its own between the end of the trace and the host's wake-up (it ran
-    // 20-35 us among the neighbouring pulses' blocks).  Release / acquire around the ticket: every thread fences after its
-    // stores, the last block fences before its loads, which bypass the non-coherent caches (the head count a few words away
-    // was read by every block when it started).
-    if (a.done_ctr) {
-        __threadfence();
-        __syncthreads();
-        uint32_t* s_ticket = reinterpret_cast<uint32_t*>(s_stack) + 1024;                 // (beyond the [waves][8] sums above)
-        if (tid_e == 0) *s_ticket = atomicAdd(a.done_ctr, 1u);
-        __syncthreads();
-        if (*s_ticket == a.n_blocks_all - 1u) {
-            __threadfence();
-            rts_sum_counters_body(tid_e, reinterpret_cast<unsigned long long*>(s_stack) + 1024, a.block_counters, a.n_blocks_all, a.counters, a.tile_head_all, a.host_cnt);
-        }
-    }
 }
 
-// k_sum_counters for a launch without launch indices (an interleaved part that is empty): zeros go home
+// counters[1..6] = sum over the blocks of a launch (256 threads of ONE block; the launch has at most a few thousand blocks)
+// ... and all of them into the handle's pinned host block (host_cnt: device address of RtsPinned::cnt) -- the host reads them
+// after its wait for the stream, without a copy of their own.  Loads at agent scope: they bypass the non-coherent caches.
+// (n_blocks = 0: a launch without launch indices -- an interleaved part that is empty -- : zeros go home)
 __global__ void k_sum_counters(const unsigned long long* __restrict__ block_counters, unsigned int n_blocks, unsigned long long* __restrict__ counters, const uint32_t* __restrict__ head_count,
                                unsigned long long* __restrict__ host_cnt)
 {
     __shared__ unsigned long long s[256];
-    rts_sum_counters_body(threadIdx.x, s, block_counters, n_blocks, counters, head_count, host_cnt);
+    const uint32_t t = threadIdx.x;
+#define RTS_LD64(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+    if (t == 7) { const unsigned long long h = head_count ? (unsigned long long)__hip_atomic_load(head_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ULL; counters[7] = h; host_cnt[7] = h; }     // the order's head count travels home with the counters (sizes the next cooperative grid)
+    if (t == 0) host_cnt[0] = RTS_LD64(&counters[0]);                          // received rays (appended by the trace kernels)
+    if ((t >= 8 && t <= 12) || t == 14 || t == 15) host_cnt[t] = RTS_LD64(&counters[t]);      // lane statistics and walked segments of the counting build; [12] cost records dropped, [14] tiles (| XCC mask << 56) on which the shader clock ran backwards, [15] never-started lane-steps
+    const unsigned int k = t & 7u, lane = t >> 3;                              // 32 partial sums per counter
+    unsigned long long v = 0;
+    // (counting builds poison the rows before the launch -- rts_trace_launch -- : a row no block wrote is COUNTED, counters[13], instead
+    // of summed; round 3 saw such launches -- a garbage sum in counters[6] -- and could not reproduce them: this names them if they return)
+    unsigned long long poisoned = 0;
+    if (k >= 1 && k <= 6) for (unsigned int b = lane; b < n_blocks; b += 32) { const unsigned long long x = RTS_LD64(&block_counters[(size_t)b * 8 + k]); if (x == ~0ULL) poisoned++; else v += x; }
+    s[t] = v;
+    if (k == 1 && poisoned) { atomicAdd(&counters[13], poisoned); __threadfence(); }      // (the rows' first counter; never in a healthy launch)
+    __syncthreads();
+    if (t >= 1 && t <= 6) {
+        unsigned long long sum = 0;
+        for (unsigned int l = 0; l < 32; l++) sum += s[l * 8 + t];
+        counters[t] = sum; host_cnt[t] = sum;
+    }
+    if (t == 13) host_cnt[13] = RTS_LD64(&counters[13]);                       // rows of block_counters still poisoned (counting builds)
+#undef RTS_LD64
 }
 
 template <bool COOP>
 static void rts_trace_dispatch(const RtsTraceArgs& a, bool count_traversal, unsigned grid, hipStream_t st)
 {
     const int sel = (a.max_refr ? 4 : 0) | (a.keep_all ? 2 : 0) | (count_traversal ? 1 : 0);
-    if (!COOP && a.xcd_seg && a.tile_order && !a.async_idle0 && sel < 2) {      // XCD-affine sub-orders: product and counting build of the plain reflection chain (every other
-        if (sel == 0) k_trace<false, false, false, false, false, true><<<grid, RTS_BLOCK, 0, st>>>(a);      // build traces the same order without the segments)
-        else k_trace<true, false, false, false, false, true><<<grid, RTS_BLOCK, 0, st>>>(a);
-        return;
-    }
-    if (!COOP && a.async_idle0 && sel < 4) {                      // asynchronous bounces (rts_trace_unit_async): ordinary kernel, no refraction chains
+    if (!COOP && a.nodes4v) {                                    // octant versions of the node records (ordinary lock-step kernel)
         switch (sel) {
             case 0: k_trace<false, false, false, false, true><<<grid, RTS_BLOCK, 0, st>>>(a); break;
             case 1: k_trace<true, false, false, false, true><<<grid, RTS_BLOCK, 0, st>>>(a); break;
             case 2: k_trace<false, true, false, false, true><<<grid, RTS_BLOCK, 0, st>>>(a); break;
-            default: k_trace<true, true, false, false, true><<<grid, RTS_BLOCK, 0, st>>>(a); break;
-        }
-        return;
-    }
-    if (!COOP && a.nodes4v) {                                    // octant versions of the node records (ordinary lock-step kernel)
-        switch (sel) {
-            case 0: k_trace<false, false, false, false, false, false, true><<<grid, RTS_BLOCK, 0, st>>>(a); break;
-            case 1: k_trace<true, false, false, false, false, false, true><<<grid, RTS_BLOCK, 0, st>>>(a); break;
-            case 2: k_trace<false, true, false, false, false, false, true><<<grid, RTS_BLOCK, 0, st>>>(a); break;
-            case 3: k_trace<true, true, false, false, false, false, true><<<grid, RTS_BLOCK, 0, st>>>(a); break;
-            case 4: k_trace<false, false, true, false, false, false, true><<<grid, RTS_BLOCK, 0, st>>>(a); break;
-            case 5: k_trace<true, false, true, false, false, false, true><<<grid, RTS_BLOCK, 0, st>>>(a); break;
-            case 6: k_trace<false, true, true, false, false, false, true><<<grid, RTS_BLOCK, 0, st>>>(a); break;
-            default: k_trace<true, true, true, false, false, false, true><<<grid, RTS_BLOCK, 0, st>>>(a); break;
+            case 3: k_trace<true, true, false, false, true><<<grid, RTS_BLOCK, 0, st>>>(a); break;
+            case 4: k_trace<false, false, true, false, true><<<grid, RTS_BLOCK, 0, st>>>(a); break;
+            case 5: k_trace<true, false, true, false, true><<<grid, RTS_BLOCK, 0, st>>>(a); break;
+            case 6: k_trace<false, true, true, false, true><<<grid, RTS_BLOCK, 0, st>>>(a); break;
+            default: k_trace<true, true, true, false, true><<<grid, RTS_BLOCK, 0, st>>>(a); break;
         }
         return;
     }
@@ -1529,8 +1352,8 @@ static void rts_trace_dispatch(const RtsTraceArgs& a, bool count_traversal, unsi
     // low / high selects like the ordinary kernel's did, and all 64 lanes of a unit walk ONE ray, one octant: BASELINE configs[3] lone launch 4.72 -> 4.52 ms, pipelined 5.21 -> 5.10,
     // an eighth of the pulse 1.18 -> 1.14 ms (profiles/r05p_coop_versions.log).  RTS_COOP_VERSIONS=0: the plain records.
     if (COOP && a.nodes4v && a.coop_versions && sel < 2) {
-        if (sel == 0) k_trace<false, false, false, true, false, false, true><<<grid, RTS_BLOCK, 0, st>>>(a);
-        else k_trace<true, false, false, true, false, false, true><<<grid, RTS_BLOCK, 0, st>>>(a);
+        if (sel == 0) k_trace<false, false, false, true, true><<<grid, RTS_BLOCK, 0, st>>>(a);
+        else k_trace<true, false, false, true, true><<<grid, RTS_BLOCK, 0, st>>>(a);
         return;
     }
     switch (sel) {
@@ -1551,11 +1374,8 @@ static void rts_trace_dispatch(const RtsTraceArgs& a, bool count_traversal, unsi
 // C4 9.4 instead of 8.7 ms).  The stream is created by the first launch that needs it: HIP maps streams onto a handful of
 // hardware queues, and one more stream per handle made unrelated handles of a three-pulse pipeline share a queue --
 // 0.69 -> 0.93 ms per pulse on C3, where there is no cooperative work at all.
-int rts_trace_launch(RtsContext* c, const RtsTraceArgs& a_in, bool count_traversal, unsigned coop_grid)
+int rts_trace_launch(RtsContext* c, const RtsTraceArgs& a, bool count_traversal, unsigned coop_grid)
 {
-    RtsTraceArgs a = a_in;
-    a.done_ctr = c->sum_in_kernel ? a.tile_ctr + RTS_OFF_HEAD + 3 : nullptr;      // (the pad word behind the head words: zeroed with them)
-    a.n_blocks_all = a.total_threads / RTS_BLOCK + coop_grid; a.host_cnt = c->pin_dev->cnt;
     if (a.n_rays == 0) {                                            // nothing to trace (an interleaved part without launch indices): the counters still go home, as zeros
         k_sum_counters<<<1, 256, 0, c->tstream_now>>>(a.block_counters, 0u, a.counters, nullptr, c->pin_dev->cnt);
         RTS_HIP(hipGetLastError());
@@ -1573,7 +1393,7 @@ int rts_trace_launch(RtsContext* c, const RtsTraceArgs& a_in, bool count_travers
     }
     rts_trace_dispatch<false>(a, count_traversal, grid, st);
     if (coop_grid) RTS_HIP(hipStreamWaitEvent(st, c->ev_coop[1], 0));
-    if (!c->sum_in_kernel) k_sum_counters<<<1, 256, 0, st>>>(a.block_counters, grid + coop_grid, a.counters, a.tile_head_all, c->pin_dev->cnt);
+    k_sum_counters<<<1, 256, 0, st>>>(a.block_counters, grid + coop_grid, a.counters, a.tile_head_all, c->pin_dev->cnt);
     RTS_HIP(hipGetLastError());
     return RTS_OK;
 }

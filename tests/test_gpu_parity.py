@@ -1501,47 +1501,6 @@ def test_pulse_end_uniform_equals_the_four_calls(rts, scenes, monkeypatch):
         np.testing.assert_allclose(cube, cube_ref, rtol=0, atol=1e-18 + 1e-12 * np.abs(cube_ref).max())      # (atomic adds: order varies)
 
 
-def test_xcd_affine_sub_orders_are_invisible(rts, oracle, scenes, monkeypatch):
-    """RTS_XCD_AFFINE=1 forces the XCD-affine sub-orders (rts_post.hip: the cost order cut into a head-rest segment and one band of
-    the lattice per XCD, each drawn through eight counters of its own; k_trace<.., AFFINE>: a wave sweeps every segment, its own
-    XCD's band first) onto launches far smaller than the 2^18 tiles they are meant for: another SCHEDULE, the same results --
-    every launch index traced exactly once (segment accounting), the received set field by field, pulse after pulse on one handle
-    (bands from the launch before last, equal counts before that), whole pulses and an interleaved part, product and counting
-    build; and the pulse's received records against the oracle's brute force"""
-    c3 = scenes.config3(W=80, detail=0.3, rx_radius=300.0)
-    tx = c3["tx"]; n_all = c3["W"] ** 3
-    out = {}
-    monkeypatch.setenv("RTS_WALK_VERSIONS", "0")      # (the experiment exists for the sorted walk only; the counts below are compared step for step)
-    for mode in ("0", "1"):
-        monkeypatch.setenv("RTS_XCD_AFFINE", mode)
-        for count in (False, True):
-            tr = rts.Tracer(c3["W"], c3["max_refl"], 0, c3["smooth"], count_traversal=count)
-            tr.set_scene(c3["meshes"]); tr.set_receivers(c3["rx"])
-            res = []
-            for k in range(5):
-                mo = [dict(m, position=tuple(np.add(m["position"], (0.3 * k, 0.05 * k, 0.0)))) for m in c3["motion"]]
-                il = (4096, 2, 1) if k == 3 else None
-                st = tr.trace(tx["origin"], tx["span"], tx["dir"], mo, ray_first=0, ray_count=n_all, interleave=il)
-                res.append((st, tr.received()))
-            out[(mode, count)] = res
-            tr.close()
-    for count in (False, True):
-        for k, ((sa, ra), (sb, rb)) in enumerate(zip(out[("0", count)], out[("1", count)])):
-            for f in ("rays", "segments", "shaded", "received") + (("node_visits", "tri_tests", "walked_segments") if count else ()):
-                assert sa[f] == sb[f], (count, k, f, sa[f], sb[f])
-            H.assert_prd_equal(ra["results"], rb["results"], "affine vs global order, pulse %d" % k)
-            assert np.array_equal(ra["slots"], rb["slots"]) and np.array_equal(ra["path"], rb["path"]) and ra["rcs_angle"].tobytes() == rb["rcs_angle"].tobytes()
-    st, rec = out[("1", False)][4]
-    assert st["rays"] == n_all and st["received"] > 500
-    mo = [dict(m, position=tuple(np.add(m["position"], (0.3 * 4, 0.05 * 4, 0.0)))) for m in c3["motion"]]
-    idx = rec["slots"][:: max(len(rec["slots"]) // 400, 1)].astype(np.int64)
-    sc = H.oracle_scene(oracle, c3, mo)
-    for i in idx[:400]:
-        o = sc.trace(tx["origin"], tx["span"], tx["dir"], c3["W"], c3["max_refl"], 0, c3["smooth"], ray_first=int(i), ray_stride=1, n_rays=1, use_bvh=False)
-        j = int(np.searchsorted(rec["slots"], i))
-        H.assert_prd_equal(o["results"][:1], rec["results"][j:j + 1], "launch index %d against the brute-force oracle" % i)
-
-
 def test_host_mirror_equals_the_copy_calls(rts, scenes, monkeypatch):
     """rts_received_prefetch / rts_received_view / rts_finalise_values / rts_aggregate / rts_aggregated_view -- the C++ adapter's
     per-pulse path: the received set stored into pinned host memory by a kernel behind the trace (on the device-side count from
@@ -1649,49 +1608,6 @@ def test_pulse_end_uniform_with_wide_keys(rts, scenes, monkeypatch):
             assert ra["results"].tobytes() == rb["results"].tobytes() and np.array_equal(ra["path"], rb["path"]), (mode, k)
             for f in ("results", "delay", "phase", "pathMatch"):
                 assert aa[f].tobytes() == ab[f].tobytes(), (mode, k, f)
-
-
-def test_asynchronous_bounces_are_invisible(rts, scenes, monkeypatch):
-    """RTS_ASYNC_IDLE0 > 0 selects the kernel whose lanes advance from segment to segment on their own
-    (rts_trace_unit_async: a walk phase ends as soon as `idle` lanes have come out of their walks; they are shaded and
-    re-join the lanes still walking, whose walk state stays in registers / LDS).  Which lanes are advanced together depends on
-    the limit and on timings (the limit switches with the tile's age), the results must not: lock step (the default kernel)
-    against limits 64, 8 and 1, in KEEP_ALL + counting builds and in the product build, several targets (a lane may be at
-    another target than its neighbour), a 3-entry LDS stack, Earth-centred coordinates, the miss-branch scene"""
-    import math
-    monkeypatch.setenv("RTS_GRID_MULT", "1"); monkeypatch.setenv("RTS_COOP_FRAC", "0")       # (no cooperative units: the node visits are compared)
-    c3 = scenes.config3(W=56, detail=0.3, rx_radius=300.0)
-    multi = scenes.config_multi(W=44)
-    cases = [("c3", c3, {}), ("c3 ecef", scenes.translate(c3, scenes.ecef_offset(lat=math.pi / 2)), {}), ("multi", multi, {}),
-             ("c3 short stack", c3, {"RTS_STACK_LDS_DEBUG": "3"}), ("miss branches", scenes.config_miss_branches(W=44), {})]
-    for name, spec, env in cases:
-        n = spec["W"] ** 3
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
-        out = {}
-        monkeypatch.setenv("RTS_WALK_VERSIONS", "0")      # (the asynchronous schedule exists for the sorted walk only; its counts are compared step for step with the lock-step kernel's)
-        for mode in ("0", "64", "8", "1"):
-            monkeypatch.setenv("RTS_ASYNC_IDLE0", mode); monkeypatch.setenv("RTS_ASYNC_IDLE1", "1" if mode == "64" else mode if mode != "0" else "1"); monkeypatch.setenv("RTS_ASYNC_AGE", "40")
-            tr = H.gpu_tracer(rts, spec, keep_all=True, count_traversal=True)
-            tp = H.gpu_tracer(rts, spec)                                        # the product build
-            for rep in range(2):
-                _, st = H.gpu_trace(rts, spec, tr=tr); _, sp = H.gpu_trace(rts, spec, tr=tp)
-            out[mode] = (tr.all_rays(n), tr.received(), st, tp.received(), sp)
-            tr.close(); tp.close()
-        for k in env:
-            monkeypatch.delenv(k)
-        a, ra, sa, pa, spa = out["0"]
-        for mode in ("64", "8", "1"):
-            b, rb, sb, pb, spb = out[mode]
-            _all_equal(a, b, "%s, idle limit %s" % (name, mode))
-            for x, y, what in ((ra, rb, "counting build"), (pa, pb, "product build"), (ra, pb, "product vs counting")):
-                assert np.array_equal(x["slots"], y["slots"]) and np.array_equal(x["path"], y["path"]), (name, mode, what)
-                H.assert_prd_equal(x["results"], y["results"], "%s (received, %s, idle limit %s)" % (name, what, mode))
-                np.testing.assert_allclose(x["rcs_angle"], y["rcs_angle"], rtol=0, atol=1e-12)
-            # the same walks, step for step: only their interleaving differs
-            assert (sa["segments"], sa["shaded"], sa["received"], sa["node_visits"], sa["tri_tests"]) == (sb["segments"], sb["shaded"], sb["received"], sb["node_visits"], sb["tri_tests"]), (name, mode)
-            assert (spb["segments"], spb["shaded"], spb["received"]) == (sa["segments"], sa["shaded"], sa["received"]), (name, mode)
-        assert sa["received"] > 0 and sa["tri_tests"] >= sa["shaded"] > 0, name
 
 
 def test_primary_prefilter_switches_off_when_most_rays_hit(rts, scenes):

@@ -461,10 +461,7 @@ def test_product_trace_kernels_use_no_scratch():
     allocator has no register for them across the tile loop) and reloaded in the epilogue or -- loop invariants -- per draw / per tile, never deeper.
     Also checked here: the record fetch of a traversal step -- its global_load_dwordx4 group and the
     s_waitcnt vmcnt(0) that covers it -- is ONE inline-asm block, so no compiler-placed instruction can touch the destination
-    registers while the loads are in flight.
-    The asynchronous-bounce instantiations (k_trace<.., ASYNC = true>, an experiment that is off by default: RTS_ASYNC_IDLE0)
-    carry their walk state through the shading code and do spill -- per tile or per advance phase (loop depth <= 3), never per walk
-    step, which is what is checked for them."""
+    registers while the loads are in flight."""
     import re, shutil, subprocess, tempfile
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
@@ -484,13 +481,9 @@ def test_product_trace_kernels_use_no_scratch():
         seen += 1
         scratch = int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", b).group(1)); vspill = int(re.search(r"VGPRs Spill: (\d+)", b).group(1))
         lds = int(re.search(r"LDS Size \[bytes/block\]: (\d+)", b).group(1)); occ = int(re.search(r"Occupancy \[waves/SIMD\]: (\d+)", b).group(1))
-        flags = [q == "1" for q in re.findall(r"Lb([01])", name.split("EEv")[0])]      # k_trace<COUNT, KEEP_ALL, REFR, COOP, ASYNC, AFFINE, VERS>
-        assert len(flags) == 7, name
-        async_k = flags[4]
-        if async_k:
-            assert scratch <= 64 and vspill <= 16, (name, scratch, vspill)
-        else:
-            assert scratch <= 16 and vspill <= 3, (name, scratch, vspill)
+        flags = [q == "1" for q in re.findall(r"Lb([01])", name.split("EEv")[0])]      # k_trace<COUNT, KEEP_ALL, REFR, COOP, VERS>
+        assert len(flags) == 5, name
+        assert scratch <= 16 and vspill <= 3, (name, scratch, vspill)
         coop = flags[3]; refr = flags[2]
         if coop:
             assert lds * 3 <= 160 * 1024 and occ >= (2 if refr else 3), (name, lds, occ)      # the cooperative kernel: three blocks per CU -- and three waves per SIMD: at 169 registers (one above
@@ -514,14 +507,11 @@ def test_product_trace_kernels_use_no_scratch():
                     asm_loads += 1
                 if t.startswith("s_waitcnt vmcnt(0)") and asm_loads:
                     assert asm_loads == 7, (name, asm_loads); fetch_blocks += 1; asm_loads = 0
-            if async_k:                                            # (an experiment, off by default) no STORE to scratch below the tile level; r04: the base of the stack's spill
-                assert "scratch_" not in t or depth <= 3 or t.startswith("scratch_load"), (name, depth, t)      # slab is reloaded in the (rare) deep-stack branch of its walk step; r05: a store per advance phase (depth 3) since the pre-filter grew -- never in the walk loop (depth 4)
-                continue
             if "scratch_" in t:                                   # a value the tile loop has no register for, parked in scratch in the prologue: STORES only outside every loop (once per persistent
                 assert not in_loop or (t.startswith("scratch_load") and depth <= 2), (name, depth, t)      # wave); RELOADS of such a loop-invariant value per draw or per tile (depth <= 2), never per segment or walk step (r05:
                                                                                                             # the dead-tile batches' screen took the last register the draw counter's address had)
         assert fetch_blocks >= 1 and asm_loads == 0, (name, fetch_blocks, asm_loads)     # every asm load group ends in its own wait
-    assert seen == 16      # 4 ordinary (role fetch) + 4 ordinary (octant versions) + 4 cooperative + 1 cooperative (octant versions) + 2 asynchronous + 1 XCD-affine product instantiations
+    assert seen == 13      # 4 ordinary (role fetch) + 4 ordinary (octant versions) + 4 cooperative + 1 cooperative (octant versions) product instantiations
 
 
 def test_fuzz_generator_versions_are_frozen(rts):

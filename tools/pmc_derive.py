@@ -31,7 +31,7 @@ def kernel_rows(path):
         name = r["Kernel_Name"]
         if "k_trace" not in name:
             continue
-        targs = [x.strip() for x in name.split("(")[0].split("<", 1)[-1].rstrip("> ").split(",")]      # k_trace<COUNT, KEEP_ALL, REFR, COOP[, ASYNC]>
+        targs = [x.strip() for x in name.split("(")[0].split("<", 1)[-1].rstrip("> ").split(",")]      # k_trace<COUNT, KEEP_ALL, REFR, COOP[, VERS]>
         coop = len(targs) >= 4 and targs[3] == "true"
         d = rows[coop].setdefault(int(r["Dispatch_Id"]), {})
         d[r["Counter_Name"]] = d.get(r["Counter_Name"], 0.0) + float(r["Counter_Value"])
