@@ -489,6 +489,10 @@ int rts_noise_eval(uint64_t seed, const uint64_t* index, uint32_t n, double nois
  *     detection of complex Gaussian noise: the false-alarm rate is pfa at the range edges too.
  *   Detection: P > threshold; with RTS_CFAR_LOCAL_MAX also a 3 x 3 local maximum (Doppler wrapped, range truncated): strictly greater
  *     than each neighbour whose offset (dk, dr) is lexicographically below (0, 0), >= each one above it (one detection per plateau).
+ *     The wrap is applied as it stands, also on a map too short for it: with n_doppler = 2 both Doppler offsets name the same row,
+ *     and with n_doppler = 1 they name the cell's OWN row -- the neighbour (-1, 0) is then the cell itself, "strictly greater" never
+ *     holds, and NO cell is reported.  That is the rule's consequence and it is kept (a one-row map has no Doppler axis to be a
+ *     maximum along): detect on a single-row map without RTS_CFAR_LOCAL_MAX.
  *   Refinement: per axis a parabola through ln P of the two neighbours, delta = (ln P- - ln P+) / (2 (ln P- - 2 ln P0 + ln P+))
  *     clamped to [-0.5, 0.5]; 0 when a neighbour is missing (range edge), a power is <= 0 or the denominator is >= 0.
  *     delay = t0 + (range_bin + range_offset) dt; doppler = w / (n_doppler pri) with w = doppler_bin + doppler_offset wrapped into
