@@ -666,34 +666,54 @@ static int fill_target_placement(const RtsContext* c, uint32_t t, RtsTargetDev& 
     return RTS_OK;
 }
 
+// The shared tile-cost history holds n_hist records: left alone when it already does, else (re)allocated, zeroed and forgotten.
+static int rts_hist_ensure(RtsContext* c, uint32_t n_hist)
+{
+    if (c->hist->n == n_hist) return RTS_OK;
+    std::lock_guard<std::mutex> lk(g_hist_mu);      // (handles that share the history may be driven from different threads)
+    RTS_HIP(hipDeviceSynchronize()); RTS_HIP(c->hist->d.reserve(n_hist)); RTS_HIP(hipMemset(c->hist->d.p, 0, sizeof(uint32_t) * n_hist));      // (blocking, once: the table may be shared with handles on other streams)
+    c->hist->n = n_hist; c->hist->any = false; c->tile_cost_pending = false;
+    return RTS_OK;
+}
+
+// The zero block and, behind it, room for the primary-ray mask; p_counters points at the block's 16 counters.
+static int rts_zero_block_reserve(RtsContext* c)
+{
+    RTS_HIP(c->d_tile_ctr.reserve(RTS_ZERO_WORDS + RTS_MASK_WORDS + 64));
+    c->p_counters = reinterpret_cast<unsigned long long*>(c->d_tile_ctr.p + RTS_OFF_COUNTERS);
+    return RTS_OK;
+}
+
+// The eight per-pulse buffers hold at least the given element counts (rts_launch_plan.h: rts_launch_sizes).
+static int rts_launch_buffers_reserve(RtsContext* c, const RtsLaunchSizes& s)
+{
+    RTS_HIP(c->d_recv.reserve(s.recv)); RTS_HIP(c->d_dir_hist.reserve(s.dir_hist)); RTS_HIP(c->d_child.reserve(s.child));
+    RTS_HIP(c->d_stack_ovf.reserve(s.stack_ovf)); RTS_HIP(c->d_block_counters.reserve(s.block_counters));
+    RTS_HIP(c->d_all.reserve(s.all)); RTS_HIP(c->d_hit_prim.reserve(s.hit_prim)); RTS_HIP(c->d_hit_t.reserve(s.hit_t));
+    return RTS_OK;
+}
+
+// the cooperative kernel's rows of the per-thread slabs
+static uint32_t rts_coop_threads(const RtsContext* c) { return c->coop_frac > 0.0 ? c->coop_grid_max * RTS_BLOCK : 0u; }
+
 // Device buffers of a launch of up to n launch indices (grown, never shrunk).  Also the first touch of the big slabs:
 // doing it before the first pulse keeps multi-GB hipMalloc calls out of a caller's timed or latency-critical region.
 extern "C" int rts_reserve(RtsHandle c, uint64_t n_rays)
 {
     CHECK_HANDLE(c);
-    const uint64_t W3 = (uint64_t)c->params.width * c->params.width * c->params.width;
+    const uint64_t W3 = rts_lattice_size(c->params.width);
     const uint64_t n = std::min<uint64_t>(n_rays ? n_rays : W3, W3);
-    const uint32_t chains = c->params.max_refr ? 3u : 1u;
-    if (n * chains > 0xfffffff0ULL) { rts_set_error("rts_reserve: rays x chains exceeds 2^32"); return RTS_ERR_UNSUPPORTED; }
-    const size_t threads = (size_t)c->n_cu * 64 * RTS_BLOCK;             // upper bound of any launch's grid
-    const uint32_t H = c->params.max_refl + 1;
-    RTS_HIP(c->d_recv.reserve((size_t)n * chains + 1));
-    RTS_HIP(c->d_tile_ctr.reserve(RTS_ZERO_WORDS + RTS_MASK_WORDS + 64)); c->p_counters = reinterpret_cast<unsigned long long*>(c->d_tile_ctr.p + RTS_OFF_COUNTERS);
-    RTS_HIP(c->d_dir_hist.reserve((size_t)(c->params.max_refr ? 3 * H : std::max<uint32_t>(c->params.max_refl, 1)) * 3 * n + 4));
-    const size_t coop_threads = c->coop_frac > 0.0 ? (size_t)c->coop_grid_max * RTS_BLOCK : 0;
-    if (c->params.max_refr) RTS_HIP(c->d_child.reserve(2 * (threads + coop_threads)));
-    RTS_HIP(c->d_stack_ovf.reserve((size_t)RTS_STACK_OVF * ((size_t)c->n_cu * 1024 + coop_threads)));
-    RTS_HIP(c->d_block_counters.reserve(((size_t)c->n_cu * 64 + c->coop_grid_max) * 8));
-    const size_t n_tiles = (size_t)((n + RTS_WTILE - 1) / RTS_WTILE), n_hist = (size_t)((W3 + RTS_WTILE - 1) / RTS_WTILE);
+    if (n * rts_chains(c->params.max_refr) > 0xfffffff0ULL) { rts_set_error("rts_reserve: rays x chains exceeds 2^32"); return RTS_ERR_UNSUPPORTED; }
+    // upper bounds of any launch's grid: threads of the child slab, threads of the overflow stack, blocks of both kernels
+    const RtsLaunchSizes sz = rts_launch_sizes(n, (uint64_t)c->n_cu * 64 * RTS_BLOCK, (uint64_t)c->n_cu * 1024, rts_coop_threads(c), (uint64_t)c->n_cu * 64 + c->coop_grid_max,
+                                               c->params.max_refl, c->params.max_refr, (c->params.flags & RTS_FLAG_KEEP_ALL_RAYS) != 0);
+    { int rc = rts_launch_buffers_reserve(c, sz); if (rc != RTS_OK) return rc; }
+    { int rc = rts_zero_block_reserve(c); if (rc != RTS_OK) return rc; }
+    const size_t n_tiles = (size_t)rts_wave_tiles(n);
     RTS_HIP(c->d_tile_cost.reserve(n_tiles)); RTS_HIP(c->d_tile_key.reserve(n_tiles)); RTS_HIP(c->d_tile_order.reserve(n_tiles));
-    if (c->hist->n != (uint32_t)n_hist) {
-        std::lock_guard<std::mutex> lk(g_hist_mu);      // (handles that share the history may be driven from different threads)
-        RTS_HIP(hipDeviceSynchronize()); RTS_HIP(c->hist->d.reserve(n_hist)); RTS_HIP(hipMemset(c->hist->d.p, 0, sizeof(uint32_t) * n_hist));      // (blocking: the table may be shared with handles on other streams)
-        c->hist->n = (uint32_t)n_hist; c->hist->any = false; c->tile_cost_pending = false;
-    }
-    if (c->params.flags & RTS_FLAG_KEEP_ALL_RAYS) { RTS_HIP(c->d_all.reserve((size_t)n * chains + 1)); RTS_HIP(c->d_hit_prim.reserve((size_t)n * H + 1)); RTS_HIP(c->d_hit_t.reserve((size_t)n * H + 1)); }
+    { int rc = rts_hist_ensure(c, (uint32_t)rts_wave_tiles(W3)); if (rc != RTS_OK) return rc; }
     // touch the two slabs the trace kernel writes sparsely, so that their pages exist before the first launch
-    RTS_HIP(hipMemsetAsync(c->d_recv.p, 0, sizeof(RtsEndRecord) * ((size_t)n * chains + 1), c->stream));
+    RTS_HIP(hipMemsetAsync(c->d_recv.p, 0, sizeof(RtsEndRecord) * sz.recv, c->stream));
     RTS_HIP(hipMemsetAsync(c->d_dir_hist.p, 0, sizeof(float) * c->d_dir_hist.cap, c->stream));
     RTS_HIP(hipStreamSynchronize(c->stream));
     return RTS_OK;
@@ -706,39 +726,49 @@ extern "C" int rts_trace_pulse(RtsHandle c, const RtsPulse* p)
     return rc != RTS_OK ? rc : rts_trace_pulse_end(c);
 }
 
-// Everything of a pulse up to and including the trace kernel, left in flight on the handle's stream.
-extern "C" int rts_trace_pulse_begin(RtsHandle c, const RtsPulse* p)
+// What the steps of rts_trace_pulse_begin hand on to each other: the resolved range, the ordinary kernel's grid and arguments.
+struct RtsPulseLaunch {
+    RtsRayRange r; uint32_t n = 0, grid = 0;
+    bool moved = false, shared_gpu = false, keep_all = false, count_trav = false, pre_filter = false;
+    RtsTraceArgs a;
+    const char* tl_path = nullptr; size_t cnt_tl = 0;      // debug (RTS_TIMELINE): where this launch's timeline goes and its length
+};
+
+// The pulse's range arguments against the lattice and the handle's dealt list (rts_launch_plan.h: rts_ray_range); writes nothing.
+static RtsRayRange pulse_ray_range(const RtsContext* c, const RtsPulse* p)
 {
-    if (!c) { rts_set_error("null handle"); return RTS_ERR_INVALID; }
-    RtsLapTimer lt(c);
-    CHECK_HANDLE(c);
-    lt.lap(5);
-    if (!p) { rts_set_error("rts_trace_pulse: null pulse"); return RTS_ERR_INVALID; }
-    if (c->pulse_open) { rts_set_error("rts_trace_pulse_begin: the previous pulse of this handle was begun but not ended"); return RTS_ERR_INVALID; }
-    if (c->spec_pending) { int rc_ = rts_spec_resolve(c); if (rc_ != RTS_OK) return rc_; }
-    lt.lap(6);
-    const uint32_t W = c->params.width;
-    const uint64_t total = (uint64_t)W * W * W;
-    uint64_t first = p->ray_first, count = p->ray_count ? p->ray_count : (total > first ? total - first : 0);
-    uint32_t il_tile = 0, il_parts = 0, il_part = 0;
-    const bool il_list = p->interleave_parts == RTS_INTERLEAVE_LIST;      // the tiles dealt to this handle (rts_set_tile_list)
-    if (il_list) {
-        if (c->il_list_tile == 0 || p->interleave_tile != c->il_list_tile) { rts_set_error("rts_trace_pulse: RTS_INTERLEAVE_LIST with tile %u, but the handle's tile list has %u tiles of %u launch indices (rts_set_tile_list)", p->interleave_tile, c->il_list_n, c->il_list_tile); return RTS_ERR_INVALID; }
-        il_tile = c->il_list_tile; il_parts = RTS_INTERLEAVE_LIST; il_part = c->il_list_gen;
-    } else if (p->interleave_parts > 1) {
-        il_tile = p->interleave_tile; il_parts = p->interleave_parts; il_part = p->interleave_part;
-        if (il_tile == 0 || il_part >= il_parts) { rts_set_error("rts_trace_pulse: bad interleave (tile %u, part %u of %u)", il_tile, il_part, il_parts); return RTS_ERR_INVALID; }
+    const RtsRangeArgs q = {p->ray_first, p->ray_count, rts_lattice_size(c->params.width), p->interleave_tile, p->interleave_parts, p->interleave_part, RTS_INTERLEAVE_LIST,
+                            c->il_list_tile, c->il_list_n, c->il_list_last, c->il_list_gen};
+    return rts_ray_range(q);
+}
+
+// The failed check of a range as the caller reads it.
+static int pulse_range_error(const RtsContext* c, const RtsPulse* p, const RtsRayRange& r)
+{
+    switch (r.err) {
+    case RTS_RANGE_OK: return RTS_OK;
+    case RTS_RANGE_LIST_TILE: rts_set_error("rts_trace_pulse: RTS_INTERLEAVE_LIST with tile %u, but the handle's tile list has %u tiles of %u launch indices (rts_set_tile_list)", p->interleave_tile, c->il_list_n, c->il_list_tile); break;
+    case RTS_RANGE_BAD_INTERLEAVE: rts_set_error("rts_trace_pulse: bad interleave (tile %u, part %u of %u)", r.il_tile, r.il_part, r.il_parts); break;
+    case RTS_RANGE_OUTSIDE: rts_set_error("rts_trace_pulse: ray range [%llu, +%llu) outside W^3 = %llu", (unsigned long long)r.first, (unsigned long long)r.span, (unsigned long long)rts_lattice_size(c->params.width)); break;
+    case RTS_RANGE_LIST_BEYOND: rts_set_error("rts_trace_pulse: the handle's tile list names tile %u, the range has %llu tiles of %u launch indices", c->il_list_last, (unsigned long long)r.range_tiles, r.il_tile); break;
     }
-    if (first > total || count > total - first) { rts_set_error("rts_trace_pulse: ray range [%llu, +%llu) outside W^3 = %llu", (unsigned long long)first, (unsigned long long)count, (unsigned long long)total); return RTS_ERR_INVALID; }
-    const uint32_t n_targets = (uint32_t)c->scene->meshes.size();
-    hipStream_t st = c->stream;
+    return RTS_ERR_INVALID;
+}
+
+// Forgets the previous pulse's results and notes the transmitter of this one (rts_finalise_patterns: its position and boresight).
+static void pulse_reset_results(RtsContext* c, const RtsPulse* p)
+{
     c->agg_valid = false; c->agg_pending.valid = false; c->n_recv = 0;
     c->mirror.want = false; c->mirror.recv_valid = false; c->mirror.agg_valid = false; c->v_recv_have = 0;
     for (int k = 0; k < 3; k++) c->pulse_org[k] = p->ray_origin[k];
-    c->pulse_dir[0] = p->tx_dir[0]; c->pulse_dir[1] = p->tx_dir[1]; c->pulse_traced = true;      // (rts_finalise_patterns: the transmitter's position and boresight)
+    c->pulse_dir[0] = p->tx_dir[0]; c->pulse_dir[1] = p->tx_dir[1]; c->pulse_traced = true;
+}
 
-    // ---- scene placement: only when a target actually moved
-    RTS_HIP(hipEventRecord(c->ev[0], st));
+// Leaves the pulse's motion on the handle and says whether a target moved; if one did, the placements are in the pinned staging
+// and bvh_valid is false until pulse_scene_place has enqueued them.
+static int pulse_stage_motion(RtsContext* c, const RtsPulse* p, bool* moved_out)
+{
+    const uint32_t n_targets = (uint32_t)c->scene->meshes.size();
     bool moved = !c->bvh_valid;
     if (p->motion) {
         if (!c->motion_valid || memcmp(c->motion.data(), p->motion, sizeof(RtsTargetMotion)*n_targets) != 0) moved = true;
@@ -749,152 +779,144 @@ extern "C" int rts_trace_pulse_begin(RtsHandle c, const RtsPulse* p)
         c->motion_valid = true; moved = true;
     }
     c->stats.bvh_rebuilt = 0;
-    if (moved) {
-        for (uint32_t t = 0; t < n_targets; t++) for (int k = 0; k < 3; k++)
-            if (!std::isfinite(c->motion[t].position[k]) || !std::isfinite(c->motion[t].velocity[k])) { rts_set_error("rts_trace_pulse: target %u has a non-finite position/velocity", t); return RTS_ERR_INVALID; }
-        if (n_targets > 256) { rts_set_error("rts_trace_pulse: more than 256 targets"); return RTS_ERR_UNSUPPORTED; }
-        // pinned staging is safe to rewrite: every earlier upload precedes the previous launch's trace kernel, whose
-        // completion the host already waited for (received-count readback)
-        RtsTargetDev* td = c->pin->td;
-        for (uint32_t t = 0; t < n_targets; t++) {
-            td[t].reflCoeff = c->scene->meshes[t].refl_coeff; td[t].vx = c->motion[t].velocity[0]; td[t].vy = c->motion[t].velocity[1]; td[t].vz = c->motion[t].velocity[2];
-            td[t].tri_base = c->scene->meshes[t].tri_base; td[t].perface_normals = c->scene->meshes[t].perface ? 1u : 0u; td[t].refrIndex = c->scene->meshes[t].refr_index;
-            int rc = fill_target_placement(c, t, td[t]); if (rc != RTS_OK) { c->bvh_valid = false; c->motion_valid = false; return rc; }
-            c->pin->motion[t] = c->motion[t];
-        }
-        c->bvh_valid = false;                                     // (until the upload and the placement kernels below have been enqueued: an early return in between must not leave the device with the old placement)
-        // (uploaded below, together with the launch constants: one copy; the placement kernels follow it)
+    *moved_out = moved;
+    if (!moved) return RTS_OK;
+    for (uint32_t t = 0; t < n_targets; t++) for (int k = 0; k < 3; k++)
+        if (!std::isfinite(c->motion[t].position[k]) || !std::isfinite(c->motion[t].velocity[k])) { rts_set_error("rts_trace_pulse: target %u has a non-finite position/velocity", t); return RTS_ERR_INVALID; }
+    if (n_targets > 256) { rts_set_error("rts_trace_pulse: more than 256 targets"); return RTS_ERR_UNSUPPORTED; }
+    // pinned staging is safe to rewrite: every earlier upload precedes the previous launch's trace kernel, whose
+    // completion the host already waited for (received-count readback)
+    RtsTargetDev* td = c->pin->td;
+    for (uint32_t t = 0; t < n_targets; t++) {
+        td[t].reflCoeff = c->scene->meshes[t].refl_coeff; td[t].vx = c->motion[t].velocity[0]; td[t].vy = c->motion[t].velocity[1]; td[t].vz = c->motion[t].velocity[2];
+        td[t].tri_base = c->scene->meshes[t].tri_base; td[t].perface_normals = c->scene->meshes[t].perface ? 1u : 0u; td[t].refrIndex = c->scene->meshes[t].refr_index;
+        int rc = fill_target_placement(c, t, td[t]); if (rc != RTS_OK) { c->bvh_valid = false; c->motion_valid = false; return rc; }
+        c->pin->motion[t] = c->motion[t];
     }
+    c->bvh_valid = false;                                     // (until the upload and the placement kernels have been enqueued: an early return in between must not leave the device with the old placement)
+    return RTS_OK;
+}
 
-    // ---- per-pulse buffers
-    if (il_list) {           // every listed tile is whole, except the last tile of the range when it is listed (the list is ascending: it is the last entry)
-        const uint64_t range_tiles = (count + il_tile - 1) / il_tile;
-        if (c->il_list_n == 0) count = 0;
-        else if (c->il_list_last >= range_tiles) { rts_set_error("rts_trace_pulse: the handle's tile list names tile %u, the range has %llu tiles of %u launch indices", c->il_list_last, (unsigned long long)range_tiles, il_tile); return RTS_ERR_INVALID; }
-        else {
-            uint64_t cnt = (uint64_t)c->il_list_n * il_tile;
-            if (c->il_list_last == range_tiles - 1) cnt -= range_tiles * il_tile - count;
-            count = cnt;
-        }
-    } else if (il_parts > 1) {      // number of launch indices of the range that fall into this part's tiles
-        const uint64_t stride = (uint64_t)il_tile * il_parts, full = count / stride, rem = count % stride;
-        const uint64_t lo = (uint64_t)il_part * il_tile;
-        count = full * il_tile + (rem > lo ? std::min<uint64_t>(rem - lo, il_tile) : 0);
-    }
-    const uint32_t n = (uint32_t)count;
-    c->ray_first = first; c->n_rays = n;
-    const bool keep_all = (c->params.flags & RTS_FLAG_KEEP_ALL_RAYS) != 0;
-    const bool count_trav = (c->params.flags & RTS_FLAG_COUNT_TRAVERSAL) != 0;
-    const bool shared_gpu = c->grid_spare_forced || g_open_pulses[c->device & 63].load() > 0;
-    const int grid_mult = c->grid_mult, grid_spare = shared_gpu ? c->grid_spare : 0;   // blocks per CU: 4 = exactly the resident set (waves draw tiles from a queue); block slots left free
-    // the trace kernel's blocks are persistent and four of them fill a CU's register file: leave a few block slots free so
-    // that the short kernels of the neighbouring pulses (other streams) are not locked out for the whole launch
-    uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)n + RTS_BLOCK - 1) / RTS_BLOCK, (uint64_t)std::max<int>((c->n_cu * grid_mult - grid_spare * c->n_cu / 256) * (256 / RTS_BLOCK), c->n_cu));   // (grid_spare: block slots per 256 CUs; 160 measured best with three pulses in flight: 0.709 vs 0.735 ms/pulse at 64)
-    if (grid == 0) grid = 1;
-    RtsTraceArgs a; memset(&a, 0, sizeof(a));
+// Leaves the pulse's launch constants in c->last_lc: ray generation, range and interleave, the division by W, the mask frame and
+// the f32 constants of the pre-filter.
+static void pulse_fill_constants(RtsContext* c, const RtsPulse& p, const RtsRayRange& r, bool pre_filter)
+{
+    const uint32_t W = c->params.width;
     RtsLaunchConsts& lc = c->last_lc; memset(&lc, 0, sizeof(lc));
-    fill_launch_constants(lc, *p, W);
-    lc.ray_first = first; lc.W = W; lc.il_tile = il_tile; lc.il_parts = il_parts; lc.il_part = il_part; lc.il_list = il_list ? c->d_il_list.p : nullptr;
-    if (W >= 2) {                                                     // branch-free magic number of the division by W (libdivide's u32 scheme)
-        const uint32_t fl = 31u - (uint32_t)__builtin_clz(W);
-        if ((W & (W - 1)) == 0) { lc.w_magic = 0; lc.w_more = fl - 1; }
-        else {
-            const uint64_t k2 = 1ULL << (32 + fl); uint64_t pm = k2 / W; const uint64_t rem = k2 - pm * W;
-            pm += pm; const uint64_t tr = rem + rem;
-            if (tr >= W || tr < rem) pm += 1;
-            lc.w_magic = (uint32_t)(1 + pm); lc.w_more = fl;
-        }
-    }
-    const bool pre_filter = c->use_pmask && !c->pre_dense;           // (a launch where most rays hit pays for the filter and skips nothing)
+    fill_launch_constants(lc, p, W);
+    lc.ray_first = r.first; lc.W = W; lc.il_tile = r.il_tile; lc.il_parts = r.il_parts; lc.il_part = r.il_part; lc.il_list = r.il_list ? c->d_il_list.p : nullptr;
+    const RtsDivMagic d = rts_div_magic(W); lc.w_magic = d.magic; lc.w_more = d.more;
     fill_mask_frame(lc, pre_filter && c->scene->n_prims > 0);
     for (int k = 0; k < 3; k++) { lc.f_bs[k] = (float)(&lc.bsx)[k]; lc.f_st[k] = (float)(&lc.stx)[k]; }
     for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) lc.f_m[3 * i + j] = (float)(lc.rot1[3 * i] * lc.rot[j] + lc.rot1[3 * i + 1] * lc.rot[3 + j] + lc.rot1[3 * i + 2] * lc.rot[6 + j]);
-    lt.lap(0);
-    // ---- the pulse's parameters in ONE upload: launch constants, and -- when a target moved -- the placements behind them
-    c->pin->lc = lc;
-    RTS_HIP(hipMemcpyAsync(c->d_params.p, &c->pin->lc, moved && n_targets ? offsetof(RtsPinned, td) + sizeof(RtsTargetDev) * n_targets : sizeof(RtsLaunchConsts), hipMemcpyHostToDevice, st));
-    a.lc = c->p_lc;
-    // ONE fill per pulse: the draw counters of both kernels, the order's head words and bins, the launch's 16 counters and --
-    // behind them, when this pulse has one -- the primary-ray mask
-    RTS_HIP(c->d_tile_ctr.reserve(RTS_ZERO_WORDS + RTS_MASK_WORDS + 64)); c->p_counters = reinterpret_cast<unsigned long long*>(c->d_tile_ctr.p + RTS_OFF_COUNTERS);
-    RTS_HIP(hipMemsetAsync(c->d_tile_ctr.p, 0, sizeof(uint32_t) * (((RTS_ZERO_WORDS + (lc.mask.n ? (size_t)lc.mask.n * lc.mask.n / 32u + 1u : 0u)) + 63u) & ~(size_t)63u), st));      // (a whole number of 256-byte pieces: the runtime splits an odd-sized fill into two kernels)
-    uint32_t* const pmask = c->d_tile_ctr.p + RTS_ZERO_WORDS;
-    lt.lap(1);
-    { int rc = rts_scene_place(c, lc, moved, pmask); if (rc != RTS_OK) return rc; }      // placement (a target moved) + the primary-ray mask: one pass over the leaves for both
+}
+
+static uint32_t* pulse_mask_words(const RtsContext* c) { return c->d_tile_ctr.p + RTS_ZERO_WORDS; }      // the primary-ray mask, behind the zero block
+
+// Leaves enqueued: the pulse's parameters in ONE upload -- launch constants, and when a target moved the placements behind them --
+// and ONE fill: the draw counters of both kernels, the order's head words and bins, the launch's 16 counters and, behind them,
+// when this pulse has one, the primary-ray mask.
+static int pulse_upload_and_fill(RtsContext* c, bool moved)
+{
+    const uint32_t n_targets = (uint32_t)c->scene->meshes.size(); const RtsMaskFrame& mask = c->last_lc.mask;
+    c->pin->lc = c->last_lc;
+    RTS_HIP(hipMemcpyAsync(c->d_params.p, &c->pin->lc, moved && n_targets ? offsetof(RtsPinned, td) + sizeof(RtsTargetDev) * n_targets : sizeof(RtsLaunchConsts), hipMemcpyHostToDevice, c->stream));
+    { int rc = rts_zero_block_reserve(c); if (rc != RTS_OK) return rc; }
+    RTS_HIP(hipMemsetAsync(c->d_tile_ctr.p, 0, sizeof(uint32_t) * (((RTS_ZERO_WORDS + (mask.n ? (size_t)mask.n * mask.n / 32u + 1u : 0u)) + 63u) & ~(size_t)63u), c->stream));      // (a whole number of 256-byte pieces: the runtime splits an odd-sized fill into two kernels)
+    return RTS_OK;
+}
+
+// Leaves the placement (a target moved) and the primary-ray mask enqueued -- one pass over the leaves for both -- and bvh_valid true.
+static int pulse_scene_place(RtsContext* c, bool moved)
+{
+    { int rc = rts_scene_place(c, c->last_lc, moved, pulse_mask_words(c)); if (rc != RTS_OK) return rc; }
     if (moved) { RTS_STAGE(c, "scene_place"); c->bvh_valid = true; c->stats.bvh_rebuilt = 1; }
-    RTS_HIP(hipEventRecord(c->ev[1], st));
-    lt.lap(2);
-    a.ray_first = first; a.n_rays = n; a.W = W; a.max_refl = c->params.max_refl; a.smooth = c->params.interpolate_smooth ? 1u : 0u;
-    a.n_prims = c->scene->n_prims; a.n_targets = n_targets; a.n_rx = c->n_rx; a.keep_all = keep_all ? 1u : 0u;
-    a.max_refr = c->params.max_refr; a.rows = a.max_refr ? c->params.max_refl + 3 : 1;
-    const uint32_t chains = a.max_refr ? 3u : 1u;
-    if ((uint64_t)n * chains > 0xfffffff0ULL) { rts_set_error("rts_trace_pulse: rays x chains exceeds 2^32"); return RTS_ERR_UNSUPPORTED; }
-    a.total_threads = grid * RTS_BLOCK;
+    RTS_HIP(hipEventRecord(c->ev[1], c->stream));
+    return RTS_OK;
+}
+
+// Leaves L.a filled from the handle (all but the tile order and the timeline) and the per-pulse buffers reserved; the keep-all hit
+// records are cleared.
+static int pulse_args_and_buffers(RtsContext* c, RtsPulseLaunch& L)
+{
+    RtsTraceArgs& a = L.a; memset(&a, 0, sizeof(a));
+    const uint32_t n = L.n; const RtsLaunchConsts& lc = c->last_lc; hipStream_t st = c->stream;
+    a.lc = c->p_lc;
+    a.ray_first = L.r.first; a.n_rays = n; a.W = c->params.width; a.max_refl = c->params.max_refl; a.smooth = c->params.interpolate_smooth ? 1u : 0u;
+    a.n_prims = c->scene->n_prims; a.n_targets = (uint32_t)c->scene->meshes.size(); a.n_rx = c->n_rx; a.keep_all = L.keep_all ? 1u : 0u;
+    a.max_refr = c->params.max_refr; a.rows = a.max_refr ? c->params.max_refl + 3 : 1;      // (output rows per launch index: not rts_hit_rows)
+    if ((uint64_t)n * rts_chains(a.max_refr) > 0xfffffff0ULL) { rts_set_error("rts_trace_pulse: rays x chains exceeds 2^32"); return RTS_ERR_UNSUPPORTED; }
+    a.total_threads = L.grid * RTS_BLOCK;
     a.coop_spread = c->coop_spread;
     a.coop_walk_steps_lo = std::min(c->coop_walk_steps_lo, c->coop_walk_steps);
     a.coop_walk_steps = c->coop_walk_steps; a.coop_min_cost = c->coop_walk_steps ? std::min<uint32_t>(c->coop_floor, 1875u) : 0u;      // (nothing shorter than 50 us is looked at; RTS_COOP_STEPS=0: every tile is flagged)
-    const uint32_t coop_threads = c->coop_frac > 0.0 ? c->coop_grid_max * RTS_BLOCK : 0u;      // the cooperative kernel's rows of the per-thread slabs
-    a.slab_threads = a.total_threads + coop_threads;
-    RTS_HIP(c->d_recv.reserve((size_t)n * chains + 1));
-    RTS_HIP(c->d_dir_hist.reserve((size_t)(a.max_refr ? 3 * (c->params.max_refl + 1) : std::max<uint32_t>(c->params.max_refl, 1)) * 3 * n + 4));
-    if (a.max_refr) RTS_HIP(c->d_child.reserve((size_t)2 * a.slab_threads));
-    RTS_HIP(c->d_stack_ovf.reserve((size_t)RTS_STACK_OVF * a.slab_threads));
-    RTS_HIP(c->d_block_counters.reserve(((size_t)grid + c->coop_grid_max) * 8));
-    if (keep_all) {
-        RTS_HIP(c->d_all.reserve((size_t)n * chains + 1)); RTS_HIP(c->d_hit_prim.reserve((size_t)n * (c->params.max_refl + 1) + 1)); RTS_HIP(c->d_hit_t.reserve((size_t)n * (c->params.max_refl + 1) + 1));
-        rts_fill_i32(st, c->d_hit_prim.p, -2, (size_t)n * (c->params.max_refl + 1));
-        RTS_HIP(hipMemsetAsync(c->d_hit_t.p, 0, sizeof(float) * (size_t)n * (c->params.max_refl + 1), st));
+    a.slab_threads = a.total_threads + rts_coop_threads(c);
+    const RtsLaunchSizes sz = rts_launch_sizes(n, a.total_threads, a.total_threads, rts_coop_threads(c), (uint64_t)L.grid + c->coop_grid_max, a.max_refl, a.max_refr, L.keep_all);
+    { int rc = rts_launch_buffers_reserve(c, sz); if (rc != RTS_OK) return rc; }
+    if (L.keep_all) {      // (the buffers' last element is spare)
+        rts_fill_i32(st, c->d_hit_prim.p, -2, sz.hit_prim - 1);
+        RTS_HIP(hipMemsetAsync(c->d_hit_t.p, 0, sizeof(float) * (sz.hit_t - 1), st));
     }
-    a.pmask = lc.mask.n ? pmask : nullptr; a.pre_filter = pre_filter ? 1u : 0u;
+    a.pmask = lc.mask.n ? pulse_mask_words(c) : nullptr; a.pre_filter = L.pre_filter ? 1u : 0u;
     a.nodes4 = c->scene->d_nodes4.p; a.nodes4v = c->node_versions ? c->scene->d_nodes4v.p : nullptr; a.stack_lds = c->stack_lds; a.leaves = c->d_leaves.p; a.tri_nidx = c->scene->d_tri_nidx.p; a.normals = c->d_normals_world.p;
     a.targets = c->p_targets; a.rx = c->d_rx.p;
     a.recv_records = c->d_recv.p; a.all_records = c->d_all.p; a.counters = c->p_counters; a.block_counters = c->d_block_counters.p; a.dir_hist = c->d_dir_hist.p;
     a.hit_prim = c->d_hit_prim.p; a.hit_t = c->d_hit_t.p; a.stack_ovf = c->d_stack_ovf.p; a.child = c->d_child.p;
-    {   // longest-tile-first order from what this handle's earlier launches measured per global tile (rts_post.hip)
-        const int lpt = c->tile_lpt ? 1 : 0;
-        const uint32_t n_tiles = (n + RTS_WTILE - 1) / RTS_WTILE;
-        const uint64_t sig[4] = {n, first, ((uint64_t)il_parts << 32) | il_tile, il_part};
-        const bool aligned = first % RTS_WTILE == 0 && (il_parts <= 1 || il_tile % RTS_WTILE == 0);
-        a.rx_window_screen = c->rx_window_screen ? 1u : 0u;
-        a.coop_versions = c->coop_versions ? 1u : 0u;
-        a.batch_dead = aligned ? (uint32_t)c->batch_dead : 0u;      // (a wave tile must be 64 CONSECUTIVE launch indices for the tile-level screen: rts_tile_maybe)
-        const uint32_t n_hist = (uint32_t)((total + RTS_WTILE - 1) / RTS_WTILE);
-        a.tile_ctr = c->d_tile_ctr.p;
-        if (lpt && aligned && n_tiles > grid * (RTS_BLOCK / RTS_WTILE)) {
-            if (c->hist->n != n_hist) {
-                std::lock_guard<std::mutex> lk(g_hist_mu);
-                RTS_HIP(hipDeviceSynchronize()); RTS_HIP(c->hist->d.reserve(n_hist)); RTS_HIP(hipMemset(c->hist->d.p, 0, sizeof(uint32_t) * n_hist));      // (blocking, once: the table may be shared with handles on other streams)
-                c->hist->n = n_hist; c->hist->any = false; c->tile_cost_pending = false;
-            }
-            if (c->tile_cost_pending || c->hist->any) {
-                c->coop_big_now = (il_parts > 1 && !shared_gpu && c->coop_big_part > c->coop_big) ? c->coop_big_part : c->coop_big;
-                int rc = rts_tile_order_build(c, c->tile_cost_sig, c->tile_cost_pending, sig, n_tiles, grid * (RTS_BLOCK / RTS_WTILE)); if (rc != RTS_OK) return rc;
-                a.tile_order = c->d_tile_order.p; a.tile_head = c->coop_frac > 0.0 ? c->d_tile_ctr.p + RTS_OFF_HEAD + 2 : nullptr; a.tile_head_all = a.tile_head; c->hist->any = true;
-                a.tile_live = c->d_tile_ctr.p + RTS_OFF_LIVE;      // (written by the order build)
-            }
-            const bool merged_all = c->tile_cost_pending && (c->tile_cost_sig[0] + RTS_WTILE - 1) / RTS_WTILE >= n_tiles && c->d_tile_cost.cap >= n_tiles;      // k_tile_merge read AND cleared the records
-            RTS_HIP(c->d_tile_cost.reserve(n_tiles));
-            if (!merged_all) RTS_HIP(hipMemsetAsync(c->d_tile_cost.p, 0, sizeof(uint32_t) * n_tiles, st));
-            a.tile_cost = c->d_tile_cost.p;
-            c->tile_cost_pending = true; memcpy(c->tile_cost_sig, sig, sizeof(sig)); memcpy(c->tile_last_sig, sig, sizeof(sig)); c->tile_last_valid = true;
-        } else { c->tile_cost_pending = false; c->tile_last_valid = false; }      // (costs of an unaligned or single-sweep launch are not recorded)
-    }
-    const char* tl_path = count_trav ? getenv("RTS_TIMELINE") : nullptr;      // debug: dump the block/tile timeline of this launch
-    const size_t cnt_tl = (size_t)grid * 2 + 2 * (size_t)((n + RTS_WTILE - 1) / RTS_WTILE);          // [grid][2] block ticks, [tiles] durations, [tiles] start ticks
-    if (tl_path) { RTS_HIP(c->d_timeline.reserve(cnt_tl + 1)); RTS_HIP(hipMemsetAsync(c->d_timeline.p, 0, sizeof(unsigned long long) * (cnt_tl + 1), st)); a.timeline = c->d_timeline.p; }
-    c->tl_blocks = 0;
-    if (!tl_path && !count_trav && c->timeline_blocks) {      // debug, product builds: when every block of this launch started and ended (printed by rts_trace_pulse_end)
-        RTS_HIP(c->d_timeline.reserve((size_t)grid * 2 + 1)); RTS_HIP(hipMemsetAsync(c->d_timeline.p, 0, sizeof(unsigned long long) * ((size_t)grid * 2 + 1), st)); a.timeline = c->d_timeline.p; c->tl_blocks = grid;
-    }
-    c->last_args = a;
+    a.rx_window_screen = c->rx_window_screen ? 1u : 0u;
+    a.coop_versions = c->coop_versions ? 1u : 0u;
+    a.tile_ctr = c->d_tile_ctr.p;
+    return RTS_OK;
+}
 
-    lt.lap(3);
-    // ---- trace
+// Leaves the longest-tile-first order built from what this handle's earlier launches measured per global tile (rts_post.hip) and
+// this launch's cost records cleared -- or, for a launch whose costs are not recorded (unaligned, or a single sweep), neither.
+static int pulse_tile_order(RtsContext* c, RtsPulseLaunch& L)
+{
+    RtsTraceArgs& a = L.a;
+    const RtsLaunchShape s = rts_launch_shape(L.n, L.r.first, L.r.il_tile, L.r.il_parts, L.r.il_part, rts_lattice_size(c->params.width));
+    const uint32_t n_tiles = s.n_tiles, resident_waves = L.grid * (RTS_BLOCK / RTS_WTILE);
+    a.batch_dead = s.aligned ? (uint32_t)c->batch_dead : 0u;      // (a wave tile must be 64 CONSECUTIVE launch indices for the tile-level screen: rts_tile_maybe)
+    if (!(c->tile_lpt && s.aligned && n_tiles > resident_waves)) { c->tile_cost_pending = false; c->tile_last_valid = false; return RTS_OK; }
+    { int rc = rts_hist_ensure(c, s.n_hist); if (rc != RTS_OK) return rc; }
+    if (c->tile_cost_pending || c->hist->any) {
+        c->coop_big_now = (L.r.il_parts > 1 && !L.shared_gpu && c->coop_big_part > c->coop_big) ? c->coop_big_part : c->coop_big;
+        int rc = rts_tile_order_build(c, c->tile_cost_sig, c->tile_cost_pending, s.sig, n_tiles, resident_waves); if (rc != RTS_OK) return rc;
+        a.tile_order = c->d_tile_order.p; a.tile_head = c->coop_frac > 0.0 ? c->d_tile_ctr.p + RTS_OFF_HEAD + 2 : nullptr; a.tile_head_all = a.tile_head; c->hist->any = true;
+        a.tile_live = c->d_tile_ctr.p + RTS_OFF_LIVE;      // (written by the order build)
+    }
+    const bool merged_all = c->tile_cost_pending && rts_wave_tiles(c->tile_cost_sig[0]) >= n_tiles && c->d_tile_cost.cap >= n_tiles;      // k_tile_merge read AND cleared the records
+    RTS_HIP(c->d_tile_cost.reserve(n_tiles));
+    if (!merged_all) RTS_HIP(hipMemsetAsync(c->d_tile_cost.p, 0, sizeof(uint32_t) * n_tiles, c->stream));
+    a.tile_cost = c->d_tile_cost.p;
+    c->tile_cost_pending = true; memcpy(c->tile_cost_sig, s.sig, sizeof(s.sig)); memcpy(c->tile_last_sig, s.sig, sizeof(s.sig)); c->tile_last_valid = true;
+    return RTS_OK;
+}
+
+// Leaves the debug timeline of this launch zeroed and named in L.a: RTS_TIMELINE (counting build: blocks and tiles, dumped by
+// pulse_timeline_dump) or RTS_TIMELINE_BLOCKS (product build: when every block started and ended, printed by rts_trace_pulse_end).
+static int pulse_timelines(RtsContext* c, RtsPulseLaunch& L)
+{
+    const size_t blocks2 = (size_t)L.grid * 2;
+    L.tl_path = L.count_trav ? getenv("RTS_TIMELINE") : nullptr;
+    L.cnt_tl = blocks2 + 2 * (size_t)rts_wave_tiles(L.n);          // [grid][2] block ticks, [tiles] durations, [tiles] start ticks
+    c->tl_blocks = 0;
+    const size_t words = L.tl_path ? L.cnt_tl + 1 : (!L.count_trav && c->timeline_blocks) ? blocks2 + 1 : 0;
+    if (!words) return RTS_OK;
+    RTS_HIP(c->d_timeline.reserve(words)); RTS_HIP(hipMemsetAsync(c->d_timeline.p, 0, sizeof(unsigned long long) * words, c->stream)); L.a.timeline = c->d_timeline.p;
+    if (!L.tl_path) c->tl_blocks = L.grid;
+    return RTS_OK;
+}
+
+// Leaves both trace kernels enqueued on the stream chosen for this pulse (c->tstream_now), bracketed by ev[2] / ev[3], and the
+// handle's own stream waiting for them.
+static int pulse_launch(RtsContext* c, RtsPulseLaunch& L)
+{
+    RtsTraceArgs& a = L.a; hipStream_t st = c->stream;
     RTS_STAGE(c, "pre-trace");
     // The trace kernel's stream: the handle's low-priority trace stream when other pulses share the GPU (their short kernels then get
     // in beside it), the handle's OWN stream when none does -- a pulse on its own is one dependent chain, and every hop between two
     // streams costs it 17-25 us of event hand-over (profiles/r04_inflight1_pulse_timeline.log: two hops per pulse)
-    c->tstream_now = (c->trace_own_stream && !shared_gpu && c->gate->refs.load() == 1) ? st : c->tstream;
+    c->tstream_now = (c->trace_own_stream && !L.shared_gpu && c->gate->refs.load() == 1) ? st : c->tstream;
     if (c->tstream_now != st) {
         RTS_HIP(hipEventRecord(c->ev[8], st));                   // scene + per-pulse buffers of this handle are ready
         RTS_HIP(hipStreamWaitEvent(c->tstream_now, c->ev[8], 0));
@@ -908,30 +930,78 @@ extern "C" int rts_trace_pulse_begin(RtsHandle c, const RtsPulse* p)
     unsigned coop_grid = 0;
     if (a.tile_head) {
         if (c->hist->head_hint_valid) c->n_head_hint = c->hist->head_hint;      // (the latest head count of ANY handle that shares the history)
-        const bool grouped = a.nodes4v && a.coop_versions && !keep_all && !a.max_refr;      // (rts_trace_dispatch: the cooperative kernel that walks the octant versions holds 64 / RTS_COOP_GROUP rays per unit)
-        const uint64_t units = (grouped ? (uint64_t)RTS_COOP_GROUP : 64ULL) * c->n_head_hint;
-        if (units == 0) a.tile_head = nullptr;
-        else coop_grid = (unsigned)std::min<uint64_t>(c->coop_grid_max, std::max<uint64_t>(16, (units + 3) / 4));
+        const bool grouped = a.nodes4v && a.coop_versions && !L.keep_all && !a.max_refr;      // (rts_trace_dispatch: the cooperative kernel that walks the octant versions holds 64 / RTS_COOP_GROUP rays per unit)
+        coop_grid = rts_coop_grid(c->n_head_hint, grouped, c->coop_grid_max);
+        if (coop_grid == 0) a.tile_head = nullptr;
         c->last_args = a;
     }
-    if (c->debug_coop) fprintf(stderr, "[rts] launch: n_rays %u grid %u head hint %u coop grid %u walk-steps threshold %u min cost %u order %d\n", n, grid, c->n_head_hint, coop_grid, a.coop_walk_steps, a.coop_min_cost, a.tile_order ? 1 : 0);
+    if (c->debug_coop) fprintf(stderr, "[rts] launch: n_rays %u grid %u head hint %u coop grid %u walk-steps threshold %u min cost %u order %d\n", L.n, L.grid, c->n_head_hint, coop_grid, a.coop_walk_steps, a.coop_min_cost, a.tile_order ? 1 : 0);
     c->last_coop_grid = coop_grid;
-    int rc = rts_trace_launch(c, a, count_trav, coop_grid);
+    int rc = rts_trace_launch(c, a, L.count_trav, coop_grid);
     if (rc != RTS_OK) return rc;
     RTS_STAGE(c, "k_trace");
     RTS_HIP(hipEventRecord(c->ev[3], c->tstream_now));
     if (c->tstream_now != st) RTS_HIP(hipStreamWaitEvent(st, c->ev[3], 0));      // everything later on this handle's stream follows its trace
+    return RTS_OK;
+}
+
+// debug (RTS_TIMELINE): waits for the launch and writes its block / tile timeline to the named file
+static int pulse_timeline_dump(RtsContext* c, const RtsPulseLaunch& L)
+{
+    RTS_HIP(hipStreamSynchronize(c->stream));
+    std::vector<unsigned long long> h(L.cnt_tl + 2);
+    h[0] = L.grid; h[1] = rts_wave_tiles(L.n);
+    RTS_HIP(hipMemcpy(h.data() + 2, c->d_timeline.p, sizeof(unsigned long long) * L.cnt_tl, hipMemcpyDeviceToHost));
+    if (FILE* f = fopen(L.tl_path, "wb")) { fwrite(h.data(), sizeof(unsigned long long), h.size(), f); fclose(f); }
+    return RTS_OK;
+}
+
+// Everything of a pulse up to and including the trace kernel, left in flight on the handle's stream.
+// (the RtsLapTimer sections: rts_destroy's names[])
+extern "C" int rts_trace_pulse_begin(RtsHandle c, const RtsPulse* p)
+{
+    if (!c) { rts_set_error("null handle"); return RTS_ERR_INVALID; }
+    RtsLapTimer lt(c);
+    CHECK_HANDLE(c);
+    lt.lap(5);
+    if (!p) { rts_set_error("rts_trace_pulse: null pulse"); return RTS_ERR_INVALID; }
+    if (c->pulse_open) { rts_set_error("rts_trace_pulse_begin: the previous pulse of this handle was begun but not ended"); return RTS_ERR_INVALID; }
+    if (c->spec_pending) { int rc_ = rts_spec_resolve(c); if (rc_ != RTS_OK) return rc_; }
+    lt.lap(6);
+    RtsPulseLaunch L;
+    L.r = pulse_ray_range(c, p);
+    // (a dealt list that names a tile beyond the range is reported AFTER the motion is staged: a bad motion is the error of a call
+    // that has both wrong, and the failed call leaves motion_valid and bvh_valid as staged)
+    if (L.r.err != RTS_RANGE_OK && L.r.err != RTS_RANGE_LIST_BEYOND) return pulse_range_error(c, p, L.r);
+    pulse_reset_results(c, p);
+    RTS_HIP(hipEventRecord(c->ev[0], c->stream));
+    { int rc = pulse_stage_motion(c, p, &L.moved); if (rc != RTS_OK) return rc; }
+    if (L.r.err != RTS_RANGE_OK) return pulse_range_error(c, p, L.r);
+    L.n = (uint32_t)L.r.count;
+    c->ray_first = L.r.first; c->n_rays = L.n;
+    L.keep_all = (c->params.flags & RTS_FLAG_KEEP_ALL_RAYS) != 0;
+    L.count_trav = (c->params.flags & RTS_FLAG_COUNT_TRAVERSAL) != 0;
+    // the trace kernel's blocks are persistent and four of them fill a CU's register file: a launch that shares the GPU leaves a few
+    // block slots free so that the short kernels of the neighbouring pulses (other streams) are not locked out for the whole launch
+    L.shared_gpu = c->grid_spare_forced || g_open_pulses[c->device & 63].load() > 0;
+    L.grid = rts_trace_grid(L.n, c->n_cu, c->grid_mult, L.shared_gpu ? c->grid_spare : 0);
+    L.pre_filter = c->use_pmask && !c->pre_dense;           // (a launch where most rays hit pays for the filter and skips nothing)
+    pulse_fill_constants(c, *p, L.r, L.pre_filter);
+    lt.lap(0);
+    { int rc = pulse_upload_and_fill(c, L.moved); if (rc != RTS_OK) return rc; }
+    lt.lap(1);
+    { int rc = pulse_scene_place(c, L.moved); if (rc != RTS_OK) return rc; }
+    lt.lap(2);
+    { int rc = pulse_args_and_buffers(c, L); if (rc != RTS_OK) return rc; }
+    { int rc = pulse_tile_order(c, L); if (rc != RTS_OK) return rc; }
+    { int rc = pulse_timelines(c, L); if (rc != RTS_OK) return rc; }
+    c->last_args = L.a;
+    lt.lap(3);
+    { int rc = pulse_launch(c, L); if (rc != RTS_OK) return rc; }
     lt.lap(4);
     // (the eight counters were written into the pinned block by k_sum_counters itself: no copy)
     c->pulse_open = true; g_open_pulses[c->device & 63]++;
-    if (tl_path) {
-        RTS_HIP(hipStreamSynchronize(st));
-        std::vector<unsigned long long> h(cnt_tl + 2);
-        h[0] = grid; h[1] = (n + RTS_WTILE - 1) / RTS_WTILE;
-        RTS_HIP(hipMemcpy(h.data() + 2, c->d_timeline.p, sizeof(unsigned long long) * cnt_tl, hipMemcpyDeviceToHost));
-        if (FILE* f = fopen(tl_path, "wb")) { fwrite(h.data(), sizeof(unsigned long long), h.size(), f); fclose(f); }
-    }
-    return RTS_OK;
+    return L.tl_path ? pulse_timeline_dump(c, L) : RTS_OK;
 }
 
 // Waits for the pulse begun on this handle, then orders + expands its received rays (left in flight).
@@ -944,7 +1014,7 @@ static void rts_pulse_account(RtsContext* c, const unsigned long long* cnt)
     s.n_prims = c->scene->n_prims; s.n_nodes = c->scene->n_nodes;
     s.walked_segments = cnt[11]; s.cost_records_dropped = (uint32_t)cnt[12];
     if (c->debug_coop && (cnt[12] || cnt[14])) fprintf(stderr, "[rts] clocks: %llu cost records dropped; shader clock ran backwards on %llu tiles (XCC mask 0x%llx)\n", cnt[12], cnt[14] & 0x00ffffffffffffffULL, cnt[14] >> 56);
-    s.coop_tiles = c->last_coop_grid ? (uint32_t)std::min<unsigned long long>(std::min<unsigned long long>(cnt[7], (n + RTS_WTILE - 1) / RTS_WTILE), 16384ull) : 0u;      // (the bounds k_trace applies to the order's head count)
+    s.coop_tiles = c->last_coop_grid ? (uint32_t)std::min<unsigned long long>(std::min<unsigned long long>(cnt[7], rts_wave_tiles(n)), 16384ull) : 0u;      // (the bounds k_trace applies to the order's head count)
     c->pre_dense = 2 * s.shaded > (uint64_t)n;                      // next launch of this handle: pre-filter only if most launch indices hit nothing
     s.ms_scene = s.ms_trace = s.ms_compact = s.ms_aggregate = 0;
     c->stats_pending = true;
@@ -988,9 +1058,9 @@ extern "C" int rts_trace_pulse_end(RtsHandle c)
         (void)hipMemcpy(&sums[0], c->d_order_sum.p, sizeof(unsigned long long), hipMemcpyDeviceToHost);
         (void)hipMemcpy(&sums[1], c->d_tile_ctr.p + RTS_OFF_HEAD, sizeof(unsigned long long), hipMemcpyDeviceToHost);
         uint32_t live_w = 0; (void)hipMemcpy(&live_w, c->d_tile_ctr.p + RTS_OFF_LIVE, sizeof(uint32_t), hipMemcpyDeviceToHost);
-        fprintf(stderr, "[rts] end: handle %p head count %llu coop grid %u | cost sum persisted %llu, this build's %llu | live word %u of %u tiles\n", (void*)c, cnt[7], c->last_coop_grid, sums[0], sums[1], live_w, (c->n_rays + RTS_WTILE - 1) / RTS_WTILE);
+        fprintf(stderr, "[rts] end: handle %p head count %llu coop grid %u | cost sum persisted %llu, this build's %llu | live word %u of %u tiles\n", (void*)c, cnt[7], c->last_coop_grid, sums[0], sums[1], live_w, (uint32_t)rts_wave_tiles(c->n_rays));
         if (c->tile_cost_pending && c->d_tile_cost.p) {          // the cost records this launch wrote (merged by the next order build)
-            const uint32_t nt = (uint32_t)((c->tile_cost_sig[0] + RTS_WTILE - 1) / RTS_WTILE);
+            const uint32_t nt = (uint32_t)rts_wave_tiles(c->tile_cost_sig[0]);
             std::vector<uint32_t> h(nt);
             (void)hipMemcpy(h.data(), c->d_tile_cost.p, sizeof(uint32_t) * nt, hipMemcpyDeviceToHost);
             unsigned long long sum = 0, big = 0, flagged = 0; uint32_t mx = 0, shown = 0;
@@ -1093,7 +1163,7 @@ extern "C" int rts_get_all_rays(RtsHandle c, PerRayData* results, int32_t* targ_
     CHECK_HANDLE(c);
     CHECK_CLOSED(c);
     if (!(c->params.flags & RTS_FLAG_KEEP_ALL_RAYS)) { rts_set_error("rts_get_all_rays: handle was not created with RTS_FLAG_KEEP_ALL_RAYS"); return RTS_ERR_INVALID; }
-    const uint64_t n1 = c->n_rays, n = n1 * c->last_args.rows; const uint32_t D = c->depth, H = c->params.max_refl + 1;
+    const uint64_t n1 = c->n_rays, n = n1 * c->last_args.rows; const uint32_t D = c->depth, H = rts_hit_rows(c->params.max_refl);
     if (capacity < n) { rts_set_error("rts_get_all_rays: capacity too small (%llu rows)", (unsigned long long)n); return RTS_ERR_CAPACITY; }
     if (n == 0) return RTS_OK;
     RTS_HIP(hipStreamSynchronize(c->stream));
@@ -1774,7 +1844,7 @@ extern "C" int rts_set_tile_list(RtsHandle c, uint32_t tile, const uint32_t* til
     if ((n_ids && !tile_ids) || tile % RTS_WTILE != 0) { rts_set_error("rts_set_tile_list: tile must be a positive multiple of %d launch indices (got %u)", RTS_WTILE, tile); return RTS_ERR_INVALID; }
     if (n_ids == 0) { c->il_list_n = 0; c->il_list_tile = tile; c->il_list_last = 0; c->il_list_gen++; c->tile_last_valid = false; return RTS_OK; }      // an EMPTY list: this worker was dealt nothing, its launches trace no launch index
     for (uint32_t k = 1; k < n_ids; k++) if (tile_ids[k] <= tile_ids[k - 1]) { rts_set_error("rts_set_tile_list: tile ids must be ascending and unique (entry %u: %u after %u)", k, tile_ids[k], tile_ids[k - 1]); return RTS_ERR_INVALID; }
-    const uint64_t total = (uint64_t)c->params.width * c->params.width * c->params.width;
+    const uint64_t total = rts_lattice_size(c->params.width);
     if ((uint64_t)tile_ids[n_ids - 1] * tile >= total) { rts_set_error("rts_set_tile_list: tile %u of %u launch indices lies beyond W^3 = %llu", tile_ids[n_ids - 1], tile, (unsigned long long)total); return RTS_ERR_INVALID; }
     if ((uint64_t)n_ids * tile > 0xffffffffull) { rts_set_error("rts_set_tile_list: more than 2^32 launch indices"); return RTS_ERR_INVALID; }
     RTS_HIP(hipStreamSynchronize(c->stream));                      // (kernels still reading the old list through their launch constants: k_expand of the last pulse)
@@ -1789,8 +1859,8 @@ extern "C" int rts_tile_records_get(RtsHandle c, uint32_t* records, uint32_t n)
 {
     CHECK_HANDLE(c);
     if (c->pulse_open) { rts_set_error("rts_tile_records_get: a pulse of this handle is in flight"); return RTS_ERR_INVALID; }
-    const uint64_t total = (uint64_t)c->params.width * c->params.width * c->params.width;
-    if (!records || n != (uint32_t)((total + RTS_WTILE - 1) / RTS_WTILE)) { rts_set_error("rts_tile_records_get: n must be ceil(W^3 / %d) = %llu", RTS_WTILE, (unsigned long long)((total + RTS_WTILE - 1) / RTS_WTILE)); return RTS_ERR_INVALID; }
+    const uint64_t total = rts_lattice_size(c->params.width);
+    if (!records || n != (uint32_t)rts_wave_tiles(total)) { rts_set_error("rts_tile_records_get: n must be ceil(W^3 / %d) = %llu", RTS_WTILE, (unsigned long long)rts_wave_tiles(total)); return RTS_ERR_INVALID; }
     { int rc = rts_tile_costs_flush(c); if (rc != RTS_OK) return rc; }
     RTS_HIP(c->d_rec_tmp.reserve(n));
     { int rc = rts_tile_records_masked(c, c->d_rec_tmp.p, n); if (rc != RTS_OK) return rc; }
@@ -1803,8 +1873,8 @@ extern "C" int rts_tile_records_set(RtsHandle c, const uint32_t* records, uint32
 {
     CHECK_HANDLE(c);
     if (c->pulse_open) { rts_set_error("rts_tile_records_set: a pulse of this handle is in flight"); return RTS_ERR_INVALID; }
-    const uint64_t total = (uint64_t)c->params.width * c->params.width * c->params.width;
-    if (!records || n != (uint32_t)((total + RTS_WTILE - 1) / RTS_WTILE)) { rts_set_error("rts_tile_records_set: n must be ceil(W^3 / %d) = %llu", RTS_WTILE, (unsigned long long)((total + RTS_WTILE - 1) / RTS_WTILE)); return RTS_ERR_INVALID; }
+    const uint64_t total = rts_lattice_size(c->params.width);
+    if (!records || n != (uint32_t)rts_wave_tiles(total)) { rts_set_error("rts_tile_records_set: n must be ceil(W^3 / %d) = %llu", RTS_WTILE, (unsigned long long)rts_wave_tiles(total)); return RTS_ERR_INVALID; }
     RTS_HIP(hipStreamSynchronize(c->stream));
     RTS_HIP(c->hist->d.reserve(n));
     RTS_HIP(hipMemcpy(c->hist->d.p, records, sizeof(uint32_t) * n, hipMemcpyHostToDevice));
@@ -1816,7 +1886,7 @@ extern "C" int rts_tile_records_set(RtsHandle c, const uint32_t* records, uint32
 extern "C" int rts_deal_tiles(const uint32_t* records, uint32_t n_records, uint64_t total_rays, uint32_t tile, uint32_t parts, uint32_t* part_of_tile, uint64_t* cost_of_part)
 {
     if (!records || !part_of_tile || parts == 0 || tile == 0 || tile % RTS_WTILE != 0 || total_rays == 0) { rts_set_error("rts_deal_tiles: bad arguments (tile must be a positive multiple of %d, parts >= 1)", RTS_WTILE); return RTS_ERR_INVALID; }
-    if ((uint64_t)n_records != (total_rays + RTS_WTILE - 1) / RTS_WTILE) { rts_set_error("rts_deal_tiles: n_records must be ceil(total_rays / %d)", RTS_WTILE); return RTS_ERR_INVALID; }
+    if ((uint64_t)n_records != rts_wave_tiles(total_rays)) { rts_set_error("rts_deal_tiles: n_records must be ceil(total_rays / %d)", RTS_WTILE); return RTS_ERR_INVALID; }
     const uint64_t n_plan64 = (total_rays + tile - 1) / tile;
     if (n_plan64 > 0xffffffffull) { rts_set_error("rts_deal_tiles: too many tiles"); return RTS_ERR_INVALID; }
     const uint32_t n_plan = (uint32_t)n_plan64, per = tile / RTS_WTILE;
@@ -1868,13 +1938,6 @@ extern "C" int rts_deal_tiles(const uint32_t* records, uint32_t n_records, uint6
     return RTS_OK;
 }
 
-static uint64_t plan_part_count(uint64_t total, uint32_t tile, uint32_t parts, uint32_t part)
-{
-    if (parts <= 1) return total;
-    const uint64_t stride = (uint64_t)tile * parts, full = total / stride, rem = total % stride, lo = (uint64_t)part * tile;
-    return full * tile + (rem > lo ? std::min<uint64_t>(rem - lo, tile) : 0);
-}
-
 extern "C" int rts_plan_cpi(uint64_t total_rays, uint32_t n_pulses, uint32_t rank, uint32_t world, uint32_t mode, uint32_t min_items,
                             uint32_t tile, RtsPlanItem* out, uint32_t capacity, uint32_t* n_out)
 {
@@ -1906,7 +1969,7 @@ extern "C" int rts_plan_cpi(uint64_t total_rays, uint32_t n_pulses, uint32_t ran
     while (!plan.empty() && plan.size() < min_items) {
         const RtsPlanItem it = plan.front();
         const uint32_t parts = it.interleave_parts > 1 ? it.interleave_parts : 1u, part = it.interleave_parts > 1 ? it.interleave_part : 0u;
-        if (parts > 0x3fffffffu || plan_part_count(it.ray_count, tile, 2 * parts, part + parts) == 0) break;      // nothing left to split off
+        if (parts > 0x3fffffffu || rts_part_count(it.ray_count, tile, 2 * parts, part + parts) == 0) break;      // nothing left to split off
         plan.erase(plan.begin());
         plan.push_back(item(it.pulse, 2 * parts, part)); plan.push_back(item(it.pulse, 2 * parts, part + parts));
     }

@@ -10,6 +10,7 @@
 #include "rts_pattern.h"
 #include "rts_waveform.h"
 #include "rts_noise.h"
+#include "rts_launch_plan.h"      // RTS_BLOCK, RTS_WTILE, RTS_COOP_GROUP, RTS_STACK_OVF and the host arithmetic of a launch
 
 // ----------------------------------------------------------------------------- HBM layout
 // BVH4 node, 128 B = one cache line, of the static target-space hierarchy (rts_sah.cpp): half the dependent fetch
@@ -77,10 +78,6 @@ struct __attribute__((aligned(16))) RtsChildState {
 };
 static_assert(sizeof(RtsChildState) == 128, "child state size");
 
-#ifndef RTS_BLOCK
-#define RTS_BLOCK 256
-#endif
-#define RTS_WTILE 64               // work unit of the trace kernel: launch indices per wave tile
 #ifndef RTS_TILE_CTRS
 #define RTS_TILE_CTRS 64           // striped draw counters of the tile queue
 #endif
@@ -105,7 +102,6 @@ static_assert(sizeof(RtsChildState) == 128, "child state size");
 #ifndef RTS_RX_LDS
 #define RTS_RX_LDS 16               // receivers whose capture spheres the trace kernel keeps in LDS (the rest are read from memory)
 #endif
-#define RTS_STACK_OVF 128           // further entries spilled to global memory (rare); a BVH4 node pushes up to 3 entries
 
 // Launch constants of ray_generation (hoisted trig, ray_tracer.cu:155-203).  Device resident and
 // read through a pointer: keeping these 30 doubles as by-value kernel arguments pinned ~60
@@ -143,7 +139,7 @@ struct RtsLaunchConsts {
     double w1x, w1y, w1z;           // direction for W == 1
     uint64_t ray_first;
     uint32_t W, pad;
-    uint32_t w_magic, w_more;       // division by W (>= 2) without a divide: q = mulhi(magic, g); ((g - q) >> 1) + q >> more  (fill_launch_constants)
+    uint32_t w_magic, w_more;       // division by W (>= 2) without a divide: q = mulhi(magic, g); ((g - q) >> 1) + q >> more  (rts_launch_plan.h: rts_div_magic)
     uint32_t il_tile, il_parts, il_part, pad2;     // interleaved tiles (il_parts <= 1: contiguous)
     const uint32_t* il_list;        // != nullptr: local tile j of il_tile launch indices is tile il_list[j] of the range (rts_set_tile_list: tiles DEALT to this launch, ascending) instead of j * il_parts + il_part
     RtsMaskFrame mask;              // primary-ray mask frame (n = 0: no mask this launch)
@@ -153,10 +149,6 @@ struct RtsLaunchConsts {
 };
 static_assert(sizeof(RtsLaunchConsts) % 8 == 0, "launch constants are copied to LDS dword by dword");
 
-// lanes that share a ray in a unit of the cooperative kernel that walks the octant versions (rts_trace.hip: rts_walk_coop): 32 = two rays per wave (measured best: profiles/r05v_coop_group.log), 16 = four, 64 = one
-#ifndef RTS_COOP_GROUP
-#define RTS_COOP_GROUP 32
-#endif
 struct RtsTraceArgs {
     const RtsLaunchConsts* lc;      // device copy of the launch constants
     uint64_t ray_first;

@@ -360,7 +360,7 @@ __global__ void __launch_bounds__(256) k_tile_scan_scatter(const uint32_t* __res
 static RtsTileShape rts_shape_of(const RtsContext* c, const uint64_t* sig)
 {
     RtsTileShape s; s.first = sig[1]; s.il_tile = (uint32_t)(sig[2] & 0xffffffffu); s.il_parts = (uint32_t)(sig[2] >> 32); s.il_part = (uint32_t)sig[3];
-    s.n_tiles = (uint32_t)((sig[0] + RTS_WTILE - 1) / RTS_WTILE); s.il_list = s.il_parts == RTS_INTERLEAVE_LIST ? c->d_il_list.p : nullptr; return s;
+    s.n_tiles = (uint32_t)rts_wave_tiles(sig[0]); s.il_list = s.il_parts == RTS_INTERLEAVE_LIST ? c->d_il_list.p : nullptr; return s;
 }
 __global__ void k_tile_records_masked(const uint32_t* __restrict__ hist, uint32_t n_hist, RtsTileShape last, uint32_t* __restrict__ out)
 {
@@ -413,7 +413,7 @@ int rts_tile_order_build(RtsContext* c, const uint64_t* prev_sig, bool prev_vali
     // (a launch over a dealt tile list has il_parts = RTS_INTERLEAVE_LIST and the list's generation in il_part; the list on the device is
     // the one BOTH shapes mean: rts_set_tile_list merges pending cost records before it replaces the list)
     auto shape = [c](const uint64_t* sig) { RtsTileShape s; s.first = sig[1]; s.il_tile = (uint32_t)(sig[2] & 0xffffffffu); s.il_parts = (uint32_t)(sig[2] >> 32); s.il_part = (uint32_t)sig[3];
-                                           s.n_tiles = (uint32_t)((sig[0] + RTS_WTILE - 1) / RTS_WTILE); s.il_list = s.il_parts == RTS_INTERLEAVE_LIST ? c->d_il_list.p : nullptr; return s; };
+                                           s.n_tiles = (uint32_t)rts_wave_tiles(sig[0]); s.il_list = s.il_parts == RTS_INTERLEAVE_LIST ? c->d_il_list.p : nullptr; return s; };
     uint32_t* head = c->coop_frac > 0.0 ? c->d_tile_ctr.p + RTS_OFF_HEAD : nullptr;      // [sum lo, sum hi, count, pad]: zeroed with the draw counters
     uint32_t* bins = c->d_tile_ctr.p + RTS_OFF_BINS, *taken = c->d_tile_ctr.p + RTS_OFF_TAKEN, *live = c->d_tile_ctr.p + RTS_OFF_LIVE;      // zeroed with the draw counters
     const RtsTileShape cur = shape(cur_sig);
@@ -452,7 +452,7 @@ int rts_post_order_and_expand(RtsContext* c)
     if (c->post_small && R <= rts_small_cap_recv(c)) {
         // items per thread by the size of the set (a speculative chain -- count on the device -- is sized for the capacity); sort bits by the largest row
         const uint32_t cap = c->recv_dev ? rts_small_cap_recv(c) : R;
-        const uint64_t rows = (uint64_t)c->n_rays * (c->last_args.max_refr != 0 ? 3u : 1u);
+        const uint64_t rows = (uint64_t)c->n_rays * rts_chains(c->last_args.max_refr);
         uint32_t bits = 1; while (bits < 40 && ((uint64_t)1 << bits) <= rows) bits++;       // (the padding key, 2^bits - 1, stays above every row)
         if (c->last_args.max_refr == 0) {
             if (cap <= 4u * RTS_SMALL_THREADS) k_recv_order_small<uint32_t, 4><<<1, RTS_SMALL_THREADS, 0, st>>>(c->d_recv.p, R, c->n_rays, 0, bits, c->d_ri_sorted.p, c->recv_dev);
@@ -1333,7 +1333,7 @@ int rts_post_all_small(RtsContext* c, uint32_t cap, const RtsSpecParams& sp, boo
     const uint64_t base = use_rows ? 0 : sp.base;
     RtsPostAll q; memset(&q, 0, sizeof(q));
     q.ta = c->last_args; q.rec = c->d_recv.p; q.cap = cap; q.n_rays = c->n_rays; q.with_chain = c->last_args.max_refr != 0 ? 1 : 0;
-    { const uint64_t rows = (uint64_t)c->n_rays * (c->last_args.max_refr != 0 ? 3u : 1u); uint32_t bits = 1; while (bits < 40 && ((uint64_t)1 << bits) <= rows) bits++; q.bits = bits; }
+    { const uint64_t rows = (uint64_t)c->n_rays * rts_chains(c->last_args.max_refr); uint32_t bits = 1; while (bits < 40 && ((uint64_t)1 << bits) <= rows) bits++; q.bits = bits; }
     q.perm = c->d_ri_sorted.p; q.D = D; q.rays = c->d_rx_rays.p; q.paths = c->d_rx_paths.p; q.angles = c->d_rx_angles.p; q.slots = c->d_rx_slots.p;
     q.rcs = c->d_rcsval.p; q.n_targets = nt; q.wl = sp.wl; q.gt = sp.gt; q.gr = sp.gr; q.carrier = sp.carrier; q.cspeed = sp.cspeed;
     q.cube_on = sp.cube_pulse >= 0 ? 1 : 0;

@@ -747,6 +747,63 @@ def test_interleaved_parts_equal_whole(rts, oracle, scenes):
     tr.close()
 
 
+@pytest.mark.parametrize("W", [3, 5, 8])
+def test_ranges_and_parts_at_small_widths(rts, scenes, W):
+    """ranges that do not start at 0 and interleaved parts on lattices of 27, 125 and 512 launch indices (an odd width, a power
+    of two; a range whose last tile is partial): a sub-launch traces as many launch indices as enumeration says; its keep-all
+    rows (PerRayData, path, hit records: one per launch index, in slot order) are the whole launch's rows at the global indices
+    it owns, bit for bit, and its received set is the whole launch's restricted to those indices; a bad range or interleave is
+    refused and leaves the handle able to trace the whole pulse again.  The scene shades rays at every width (3, 25 and 139 of
+    them by the CPU oracle) but receives none at W = 8, so the rows of every launch index carry the comparison there."""
+    from rts_amd import _lib
+    spec = scenes.config_multi(W=W)
+    n = W ** 3
+    tr = H.gpu_tracer(rts, spec, keep_all=True)
+    _, st = H.gpu_trace(rts, spec, tr=tr)
+    assert st["rays"] == n
+    whole, whole_all = tr.received(), tr.all_rays(n)
+    shaded = whole_all["results"]["reflDepth"] > 0
+    assert np.count_nonzero(shaded) >= 3 and (W == 8 or len(whole["slots"]) > 0)
+
+    def same_rows(got, want, what):
+        H.assert_prd_equal(got["results"], want["results"], what)
+        for f in ("path", "hit_prim", "hit_t"):
+            assert got[f].shape == want[f].shape and got[f].tobytes() == want[f].tobytes(), (what, f)
+
+    subs = [dict(ray_first=1, ray_count=0), dict(ray_first=n - 1), dict(ray_first=7, ray_count={3: 17, 5: 100, 8: 200}[W])]      # (ends in the middle of a tile, behind rays that hit)
+    subs += [dict(ray_first=0, interleave=(64, 3, part)) for part in range(3)]
+    if W == 8:
+        subs += [dict(ray_first=64, interleave=(64, 2, part)) for part in range(2)]      # 448 launch indices: 7 tiles
+    for kw in subs:
+        first = kw["ray_first"]; span = kw.get("ray_count") or n - first
+        local = np.arange(span, dtype=np.int64)
+        if "interleave" in kw:
+            tile, parts, part = kw["interleave"]
+            local = local[(local // tile) % parts == part]
+        own = first + local                                   # the global launch indices of this sub-launch, in slot order
+        if W == 8 and first in (0, 64, 7):
+            assert np.count_nonzero(shaded[own]) > 0, kw      # (the power of two and the partial last tile are compared on rays that hit)
+        _, st = H.gpu_trace(rts, spec, tr=tr, **kw)
+        assert st["rays"] == len(own), kw
+        got = tr.received()
+        keep = np.isin(whole["slots"].astype(np.int64), own)
+        assert np.array_equal(got["slots"], whole["slots"][keep]), kw
+        H.assert_prd_equal(got["results"], whole["results"][keep], "sub-launch %r" % (kw,))
+        assert np.array_equal(got["path"], whole["path"][keep]), kw
+        if len(own):
+            same_rows(tr.all_rays(len(own)), {f: whole_all[f][own] for f in ("results", "path", "hit_prim", "hit_t")}, "rows of sub-launch %r" % (kw,))
+    for bad in (dict(ray_first=n + 1), dict(interleave=(64, 3, 3))):
+        with pytest.raises(_lib.RtsError) as e:
+            H.gpu_trace(rts, spec, tr=tr, **bad)
+        assert e.value.code == _lib.RTS_ERR_INVALID, bad
+    _, st = H.gpu_trace(rts, spec, tr=tr)
+    again = tr.received()
+    assert st["rays"] == n and np.array_equal(again["slots"], whole["slots"]) and np.array_equal(again["path"], whole["path"])
+    H.assert_prd_equal(again["results"], whole["results"], "the whole pulse after two refused ones")
+    same_rows(tr.all_rays(n), whole_all, "rows of the whole pulse after two refused ones")
+    tr.close()
+
+
 def test_dealt_tile_lists_equal_whole(rts, scenes):
     """ray sharding dealt by last-seen cost (rts_tile_records_get / _set, rts_deal_tiles, rts_set_tile_list): for ARBITRARY tile ->
     worker maps -- random ones, and the longest-first deal from the cost records of a whole pulse -- the parts' received sets,
