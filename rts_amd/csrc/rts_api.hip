@@ -13,6 +13,7 @@
 #include <algorithm>
 #include <chrono>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <stdexcept>
 #include <string>
@@ -157,6 +158,28 @@ extern "C" int rts_device_count(int* n)
     *n = k; return RTS_OK;
 }
 
+void rts_scene_unref(RtsScene* s) { if (s && --s->refs == 0) delete s; }
+void rts_hist_unref(RtsTileHist* h) { if (h && --h->refs == 0) delete h; }
+void rts_gate_unref(RtsGate* g) { if (g && --g->refs == 0) { if (g->tstream) (void)hipStreamDestroy(g->tstream); delete g; } }
+
+// The teardown of a handle, once.  After this body the members destroy themselves in reverse order of declaration: every DevBuf
+// (hipFree) and the pinned blocks pin, pin_rx, pin_pat and the mirror's (hipHostFree).  That is safe because no work can read
+// them any more: `stream` and `cstream` have been drained, the trace stream has been drained (it may live on with the other
+// handles of the link group, but carries no work of this handle), and nothing is enqueued on a handle's behalf anywhere else.
+RtsContext::~RtsContext()
+{
+    if (stream) (void)hipStreamSynchronize(stream);
+    rts_scene_unref(scene); scene = nullptr;
+    rts_hist_unref(hist); hist = nullptr;
+    if (tstream) (void)hipStreamSynchronize(tstream);
+    rts_gate_unref(gate); gate = nullptr;
+    if (ev_pat) (void)hipEventDestroy(ev_pat);
+    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : ev_coop) if (e) (void)hipEventDestroy(e);
+    if (cstream) { (void)hipStreamSynchronize(cstream); (void)hipStreamDestroy(cstream); }
+    if (stream) (void)hipStreamDestroy(stream);
+}
+
 extern "C" int rts_create(const RtsParams* p, RtsHandle* out)
 {
     if (!p || !out) { rts_set_error("rts_create: null argument"); return RTS_ERR_INVALID; }
@@ -178,18 +201,18 @@ extern "C" int rts_create(const RtsParams* p, RtsHandle* out)
     // short build/ordering/aggregation kernels on the high one so that they slot in while a trace kernel is running
     int prio_low = 0, prio_high = 0;
     (void)hipDeviceGetStreamPriorityRange(&prio_low, &prio_high);
+    // every failure below: delete c (the destructor undoes whatever exists by then), set the error, return
     hipError_t e = hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, prio_high);
     if (e != hipSuccess) { delete c; rts_set_error("hipStreamCreate: %s", hipGetErrorString(e)); return RTS_ERR_HIP; }
     c->gate = new RtsGate(); c->gate->refs = 1; c->gate->device = p->device;
     e = hipStreamCreateWithPriority(&c->gate->tstream, hipStreamNonBlocking, prio_low);
-    if (e != hipSuccess) { delete c->gate; (void)hipStreamDestroy(c->stream); delete c; rts_set_error("hipStreamCreate: %s", hipGetErrorString(e)); return RTS_ERR_HIP; }
+    if (e != hipSuccess) { delete c; rts_set_error("hipStreamCreate: %s", hipGetErrorString(e)); return RTS_ERR_HIP; }
     c->tstream = c->gate->tstream; c->tstream_now = c->tstream;
     for (int i = 0; i < 2; i++) { e = hipEventCreateWithFlags(&c->ev_coop[i], hipEventDisableTiming); if (e != hipSuccess) { delete c; rts_set_error("hipEventCreate: %s", hipGetErrorString(e)); return RTS_ERR_HIP; } }
     for (int i = 0; i < 9; i++) { e = hipEventCreate(&c->ev[i]); if (e != hipSuccess) { delete c; rts_set_error("hipEventCreate: %s", hipGetErrorString(e)); return RTS_ERR_HIP; } }
-    e = hipHostMalloc((void**)&c->pin, sizeof(RtsPinned), hipHostMallocDefault);
-    if (e != hipSuccess) { delete c; rts_set_error("hipHostMalloc: %s", hipGetErrorString(e)); return RTS_ERR_HIP; }
-    memset(c->pin, 0, sizeof(RtsPinned));
-    { void* dp = nullptr; e = hipHostGetDevicePointer(&dp, c->pin, 0); if (e != hipSuccess) { delete c; rts_set_error("hipHostGetDevicePointer: %s", hipGetErrorString(e)); return RTS_ERR_HIP; } c->pin_dev = (RtsPinned*)dp; }
+    e = c->pin.reserve(1, true);
+    if (e != hipSuccess) { delete c; rts_set_error("hipHostMalloc / hipHostGetDevicePointer: %s", hipGetErrorString(e)); return RTS_ERR_HIP; }
+    memset(c->pin.p, 0, sizeof(RtsPinned));
     hipDeviceProp_t prop; e = hipGetDeviceProperties(&prop, p->device);
     if (e != hipSuccess) { delete c; rts_set_error("hipGetDeviceProperties: %s", hipGetErrorString(e)); return RTS_ERR_HIP; }
     c->n_cu = prop.multiProcessorCount;
@@ -257,33 +280,6 @@ extern "C" int rts_destroy(RtsHandle c)
     }
     if (c->pulse_open || c->spec_pending) { c->pulse_open = false; c->spec_pending = false; g_open_pulses[c->device & 63]--; }
     rts_comm_cache_forget(c);
-    c->d_pat.release(); c->d_pat_rx.release(); c->d_wave.release();
-    c->d_det_cnt.release(); c->d_det_off.release(); c->d_det_tmp.release(); c->d_det.release();
-    if (c->pin_pat) (void)hipHostFree(c->pin_pat);
-    if (c->ev_pat) (void)hipEventDestroy(c->ev_pat);
-    if (c->scene && --c->scene->refs == 0) { c->scene->release(); delete c->scene; }
-    c->scene = nullptr;
-    if (c->hist && --c->hist->refs == 0) { c->hist->d.release(); delete c->hist; }
-    c->hist = nullptr;
-    c->d_verts_world.release(); c->d_normals_world.release();
-    c->d_params.release();
-    c->d_leaves.release(); c->d_sort_tmp.release(); c->d_rx.release(); c->d_recv.release(); c->d_all.release();
-    c->d_block_counters.release(); c->d_timeline.release(); c->d_tile_cost.release(); c->d_tile_key.release(); c->d_tile_order.release(); c->d_tile_ctr.release(); c->d_dir_hist.release(); c->d_pmask.release(); c->d_child.release(); c->d_rk64.release(); c->d_rk64_sorted.release(); c->d_hit_prim.release(); c->d_hit_t.release(); c->d_stack_ovf.release(); c->d_il_list.release(); c->d_rec_tmp.release();
-    c->d_order_sum.release();
-    c->d_rk.release(); c->d_rk_sorted.release(); c->d_ri.release(); c->d_ri_sorted.release(); c->d_rx_rays.release(); c->d_rx_paths.release();
-    c->d_rx_angles.release(); c->d_rx_slots.release(); c->d_all_rays.release(); c->d_all_paths.release(); c->d_all_angles.release();
-    c->d_akeys.release(); c->d_akeys_sorted.release(); c->d_aidx.release(); c->d_aidx_sorted.release(); c->d_ghead.release(); c->d_gid.release();
-    c->d_gsum.release(); c->d_gmin.release(); c->d_gkey.release(); c->d_gpath.release(); c->d_grow.release(); c->d_gcount.release(); c->d_delay.release(); c->d_phase.release();
-    c->d_pathmatch.release(); c->d_rcs.release(); c->d_rcsval.release(); c->d_cube_own.release(); c->d_doppler_own.release();
-    (void)hipStreamSynchronize(c->tstream);
-    if (--c->gate->refs == 0) { (void)hipStreamDestroy(c->gate->tstream); delete c->gate; }
-    if (c->pin) (void)hipHostFree(c->pin);
-    if (c->pin_rx) (void)hipHostFree(c->pin_rx);
-    if (c->mirror.host) (void)hipHostFree(c->mirror.host);
-    for (int i = 0; i < 9; i++) (void)hipEventDestroy(c->ev[i]);
-    for (int i = 0; i < 2; i++) (void)hipEventDestroy(c->ev_coop[i]);
-    if (c->cstream) { (void)hipStreamSynchronize(c->cstream); (void)hipStreamDestroy(c->cstream); }
-    (void)hipStreamDestroy(c->stream);
     delete c;
     return RTS_OK;
 }
@@ -305,7 +301,7 @@ extern "C" int rts_link_handles(RtsHandle a, RtsHandle b)
     RtsContext* host = joiner == b ? a : b;
     RTS_HIP(hipSetDevice(a->device));
     RTS_HIP(hipStreamSynchronize(joiner->tstream));
-    (void)hipStreamDestroy(joiner->gate->tstream); delete joiner->gate;
+    rts_gate_unref(joiner->gate);      // (its only reference)
     joiner->gate = host->gate; joiner->gate->refs++; joiner->tstream = joiner->gate->tstream; joiner->tstream_now = joiner->tstream;
     return RTS_OK;
 }
@@ -368,8 +364,8 @@ extern "C" int rts_set_scene(RtsHandle c, const RtsMesh* meshes, uint32_t n_targ
         for (uint32_t i = 0; i < m.n_normals; i++) { ntarg[(size_t)h.normal_base + i] = t; for (int k = 0; k < 3; k++) normals[3*((size_t)h.normal_base + i) + k] = m.normals[3*(size_t)i + k]; }
     }
     // ---- the new scene object (swapped in at the end; every failure path below leaves the handle's old scene alone)
-    struct SceneGuard { RtsScene* s; ~SceneGuard() { if (s) { s->release(); delete s; } } } guard{new RtsScene()};
-    RtsScene* ns = guard.s; ns->device = c->device;
+    std::unique_ptr<RtsScene> guard(new RtsScene());
+    RtsScene* ns = guard.get(); ns->device = c->device;
     RTS_HIP(hipStreamSynchronize(c->stream));
     RTS_HIP(ns->d_tri_vidx.reserve(3*nt + 1)); RTS_HIP(ns->d_tri_nidx.reserve(3*nt + 1)); RTS_HIP(ns->d_vert_targ.reserve(nv + 1)); RTS_HIP(ns->d_norm_targ.reserve(nn + 1));
     RTS_HIP(ns->d_prim_targ.reserve(nt + 1)); RTS_HIP(ns->d_verts_local.reserve(3*nv + 1)); RTS_HIP(ns->d_normals_local.reserve(3*nn + 1));
@@ -456,8 +452,8 @@ extern "C" int rts_set_scene(RtsHandle c, const RtsMesh* meshes, uint32_t n_targ
     ns->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_build0).count();
 
     // ---- swap it in
-    if (--c->scene->refs == 0) { c->scene->release(); delete c->scene; }
-    c->scene = ns; guard.s = nullptr;
+    rts_scene_unref(c->scene);
+    c->scene = guard.release();
     return rts_attach_scene(c);
 }
 
@@ -476,7 +472,7 @@ static int rts_attach_scene(RtsContext* c)
         c->rcs_uploaded = false;
     }
     c->verts_world_valid = false; c->order_sum_valid = false;
-    if (c->hist->refs.load() > 1) { c->hist->refs--; c->hist = new RtsTileHist(); }      // (a handle that leaves a shared scene leaves the shared history)
+    if (c->hist->refs.load() > 1) { rts_hist_unref(c->hist); c->hist = new RtsTileHist(); }      // (a handle that leaves a shared scene leaves the shared history)
     c->motion.assign(n_targets, RtsTargetMotion{}); c->motion_valid = false; c->bvh_valid = false; c->hist->n = 0; c->hist->any = false; c->hist->head_hint_valid = false; c->tile_cost_pending = false; c->tile_last_valid = false;
     return RTS_OK;
 }
@@ -495,11 +491,11 @@ extern "C" int rts_share_scene(RtsHandle dst, RtsHandle src)
     CHECK_CLOSED(c);
     RTS_HIP(hipStreamSynchronize(c->stream));
     if (dst->scene == src->scene) return RTS_OK;
-    if (--dst->scene->refs == 0) { dst->scene->release(); delete dst->scene; }
+    rts_scene_unref(dst->scene);
     dst->scene = src->scene; dst->scene->refs++;
     { int rc = rts_attach_scene(dst); if (rc != RTS_OK) return rc; }
     if (dst->share_history && src->share_history && dst->params.width == src->params.width) {      // ... and the tile-cost history of the scene's handles (RtsTileHist)
-        if (--dst->hist->refs == 0) { dst->hist->d.release(); delete dst->hist; }
+        rts_hist_unref(dst->hist);
         dst->hist = src->hist; dst->hist->refs++;
     }
     return RTS_OK;
@@ -539,13 +535,12 @@ extern "C" int rts_set_receivers(RtsHandle c, const RtsReceiverSphere* rx, uint3
     // previous upload from the staging has long completed: its pulse was waited for).
     if (c->n_rx == n_rx && c->rx_host.size() == n_rx && (n_rx == 0 || memcmp(c->rx_host.data(), h.data(), sizeof(RtsRxDev) * n_rx) == 0)) return RTS_OK;
     if (n_rx <= 1024) {
-        if (c->pin_rx_cap < n_rx) {
-            if (c->pin_rx) { RTS_HIP(hipStreamSynchronize(c->stream)); (void)hipHostFree(c->pin_rx); c->pin_rx = nullptr; c->pin_rx_cap = 0; }
-            const uint32_t cap = std::max<uint32_t>(64u, n_rx);
-            RTS_HIP(hipHostMalloc((void**)&c->pin_rx, sizeof(RtsRxDev) * cap, hipHostMallocDefault)); c->pin_rx_cap = cap;
+        if (c->pin_rx.cap < n_rx) {
+            if (c->pin_rx.p) RTS_HIP(hipStreamSynchronize(c->stream));
+            RTS_HIP(c->pin_rx.reserve(std::max<uint32_t>(64u, n_rx), false));
         }
         if (c->d_rx.cap < (size_t)n_rx + 1) { RTS_HIP(hipStreamSynchronize(c->stream)); RTS_HIP(c->d_rx.reserve(n_rx + 1)); }
-        if (n_rx) { memcpy(c->pin_rx, h.data(), sizeof(RtsRxDev) * n_rx); RTS_HIP(hipMemcpyAsync(c->d_rx.p, c->pin_rx, sizeof(RtsRxDev) * n_rx, hipMemcpyHostToDevice, c->stream)); }
+        if (n_rx) { memcpy(c->pin_rx.p, h.data(), sizeof(RtsRxDev) * n_rx); RTS_HIP(hipMemcpyAsync(c->d_rx.p, c->pin_rx.p, sizeof(RtsRxDev) * n_rx, hipMemcpyHostToDevice, c->stream)); }
     } else {
         RTS_HIP(hipStreamSynchronize(c->stream));
         RTS_HIP(c->d_rx.reserve(n_rx + 1));
@@ -786,12 +781,12 @@ static int pulse_stage_motion(RtsContext* c, const RtsPulse* p, bool* moved_out)
     if (n_targets > 256) { rts_set_error("rts_trace_pulse: more than 256 targets"); return RTS_ERR_UNSUPPORTED; }
     // pinned staging is safe to rewrite: every earlier upload precedes the previous launch's trace kernel, whose
     // completion the host already waited for (received-count readback)
-    RtsTargetDev* td = c->pin->td;
+    RtsTargetDev* td = c->pin.p->td;
     for (uint32_t t = 0; t < n_targets; t++) {
         td[t].reflCoeff = c->scene->meshes[t].refl_coeff; td[t].vx = c->motion[t].velocity[0]; td[t].vy = c->motion[t].velocity[1]; td[t].vz = c->motion[t].velocity[2];
         td[t].tri_base = c->scene->meshes[t].tri_base; td[t].perface_normals = c->scene->meshes[t].perface ? 1u : 0u; td[t].refrIndex = c->scene->meshes[t].refr_index;
         int rc = fill_target_placement(c, t, td[t]); if (rc != RTS_OK) { c->bvh_valid = false; c->motion_valid = false; return rc; }
-        c->pin->motion[t] = c->motion[t];
+        c->pin.p->motion[t] = c->motion[t];
     }
     c->bvh_valid = false;                                     // (until the upload and the placement kernels have been enqueued: an early return in between must not leave the device with the old placement)
     return RTS_OK;
@@ -819,8 +814,8 @@ static uint32_t* pulse_mask_words(const RtsContext* c) { return c->d_tile_ctr.p 
 static int pulse_upload_and_fill(RtsContext* c, bool moved)
 {
     const uint32_t n_targets = (uint32_t)c->scene->meshes.size(); const RtsMaskFrame& mask = c->last_lc.mask;
-    c->pin->lc = c->last_lc;
-    RTS_HIP(hipMemcpyAsync(c->d_params.p, &c->pin->lc, moved && n_targets ? offsetof(RtsPinned, td) + sizeof(RtsTargetDev) * n_targets : sizeof(RtsLaunchConsts), hipMemcpyHostToDevice, c->stream));
+    c->pin.p->lc = c->last_lc;
+    RTS_HIP(hipMemcpyAsync(c->d_params.p, &c->pin.p->lc, moved && n_targets ? offsetof(RtsPinned, td) + sizeof(RtsTargetDev) * n_targets : sizeof(RtsLaunchConsts), hipMemcpyHostToDevice, c->stream));
     { int rc = rts_zero_block_reserve(c); if (rc != RTS_OK) return rc; }
     RTS_HIP(hipMemsetAsync(c->d_tile_ctr.p, 0, sizeof(uint32_t) * (((RTS_ZERO_WORDS + (mask.n ? (size_t)mask.n * mask.n / 32u + 1u : 0u)) + 63u) & ~(size_t)63u), c->stream));      // (a whole number of 256-byte pieces: the runtime splits an odd-sized fill into two kernels)
     return RTS_OK;
@@ -1038,7 +1033,7 @@ extern "C" int rts_trace_pulse_end(RtsHandle c)
     c->pulse_open = false; g_open_pulses[c->device & 63]--;
     hipStream_t st = c->stream;
     const bool keep_all = (c->params.flags & RTS_FLAG_KEEP_ALL_RAYS) != 0;
-    unsigned long long* cnt = c->pin->cnt;
+    unsigned long long* cnt = c->pin.p->cnt;
     RTS_HIP(rts_stream_wait(c, st));                // the one host sync of the launch: the received count sizes what follows
     { int rc = rts_counters_home(c, cnt); if (rc != RTS_OK) return rc; }
     if (c->tl_blocks) {      // RTS_TIMELINE_BLOCKS: the launch as a bulk (every block resident) and a tail (rts_get_block_timeline; profiles/r05h_batch_launch.log)
@@ -1119,7 +1114,7 @@ extern "C" int rts_get_lane_stats(RtsHandle c, uint64_t* out3)
 {
     if (!c || !out3) { rts_set_error("rts_get_lane_stats: null argument"); return RTS_ERR_INVALID; }
     CHECK_CLOSED(c);
-    for (int k = 0; k < 3; k++) out3[k] = c->pin->cnt[8 + k];
+    for (int k = 0; k < 3; k++) out3[k] = c->pin.p->cnt[8 + k];
     return RTS_OK;
 }
 
@@ -1132,7 +1127,7 @@ extern "C" int rts_get_walk_stats(RtsHandle c, uint64_t* out, uint32_t n)
     if (!c || !out) { rts_set_error("rts_get_walk_stats: null argument"); return RTS_ERR_INVALID; }
     CHECK_CLOSED(c);
     const int src[5] = {8, 9, 10, 11, 15};
-    for (uint32_t k = 0; k < n && k < 5u; k++) out[k] = c->pin->cnt[src[k]];
+    for (uint32_t k = 0; k < n && k < 5u; k++) out[k] = c->pin.p->cnt[src[k]];
     return RTS_OK;
 }
 
@@ -1269,7 +1264,7 @@ static int rts_spec_resolve(RtsContext* c)
     if (!c->spec_pending) return RTS_OK;
     c->spec_pending = false; g_open_pulses[c->device & 63]--;
     RTS_HIP(hipSetDevice(c->device));
-    const unsigned long long* cnt = c->pin->cnt;
+    const unsigned long long* cnt = c->pin.p->cnt;
     RTS_HIP(rts_stream_wait(c, c->stream));
     { int rc = rts_counters_home(c, cnt); if (rc != RTS_OK) return rc; }
     c->recv_hint = cnt[0]; c->recv_hint_valid = true;                   // (the next pulse's choices -- speculate at all, one kernel or seven -- follow THIS pulse's count, not the handle's first)
@@ -1508,8 +1503,8 @@ extern "C" int rts_received_view(RtsHandle c, const PerRayData** rays, const int
     RTS_HIP(rts_stream_wait(c, c->stream));
     const RtsHostMirror& m = c->mirror;
     if (m.recv_valid && R <= m.cap) {
-        if (rays) *rays = (const PerRayData*)(m.host + m.o_rays); if (paths) *paths = (const int32_t*)(m.host + m.o_paths);
-        if (rcs_angles) *rcs_angles = (const double*)(m.host + m.o_angles); if (slots) *slots = (const uint64_t*)(m.host + m.o_slots);
+        if (rays) *rays = (const PerRayData*)(m.buf.p + m.o_rays); if (paths) *paths = (const int32_t*)(m.buf.p + m.o_paths);
+        if (rcs_angles) *rcs_angles = (const double*)(m.buf.p + m.o_angles); if (slots) *slots = (const uint64_t*)(m.buf.p + m.o_slots);
         return RTS_OK;
     }
     // no mirror of this set (not asked for, or larger than the mirror): copies into storage the handle keeps.  Each array is read from the
@@ -1536,11 +1531,11 @@ extern "C" int rts_finalise_values(RtsHandle c, const double* power, const doubl
     if (!power || !doppler) { rts_set_error("rts_finalise_values: null array"); return RTS_ERR_INVALID; }
     RTS_HIP(hipEventRecord(c->ev[6], c->stream));
     RtsHostMirror& m = c->mirror;
-    if (!m.host) { int rc = rts_mirror_reserve(c, RTS_SMALL_CAP32); if (rc != RTS_OK) return rc; }
+    if (!m.buf.p) { int rc = rts_mirror_reserve(c, RTS_SMALL_CAP32); if (rc != RTS_OK) return rc; }
     if (count <= m.cap) {
         // (the staging is free: what read it last -- this handle's previous pulse -- was waited for before this pulse was begun)
-        memcpy(m.host + m.o_vpower, power, sizeof(double) * count); memcpy(m.host + m.o_vdoppler, doppler, sizeof(double) * count);
-        int rc = rts_post_set_values(c, (const double*)(m.dev + m.o_vpower), (const double*)(m.dev + m.o_vdoppler)); if (rc != RTS_OK) return rc;
+        memcpy(m.buf.p + m.o_vpower, power, sizeof(double) * count); memcpy(m.buf.p + m.o_vdoppler, doppler, sizeof(double) * count);
+        int rc = rts_post_set_values(c, (const double*)(m.buf.dev + m.o_vpower), (const double*)(m.buf.dev + m.o_vdoppler)); if (rc != RTS_OK) return rc;
     } else {                                                            // a set beyond the mirror: blocking uploads into scratch the aggregation overwrites later
         RTS_HIP(c->d_delay.reserve(count)); RTS_HIP(c->d_phase.reserve(count));
         RTS_HIP(hipMemcpyAsync(c->d_delay.p, power, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
@@ -1570,8 +1565,8 @@ extern "C" int rts_aggregated_view(RtsHandle c, const double** power, const doub
     RTS_HIP(rts_stream_wait(c, c->stream));
     const RtsHostMirror& m = c->mirror;
     if (m.agg_valid && R <= m.cap) {
-        if (power) *power = (const double*)(m.host + m.o_apower); if (doppler) *doppler = (const double*)(m.host + m.o_adoppler);
-        if (delay) *delay = (const double*)(m.host + m.o_adelay); if (phase) *phase = (const double*)(m.host + m.o_aphase); if (path_match) *path_match = (const int32_t*)(m.host + m.o_apm);
+        if (power) *power = (const double*)(m.buf.p + m.o_apower); if (doppler) *doppler = (const double*)(m.buf.p + m.o_adoppler);
+        if (delay) *delay = (const double*)(m.buf.p + m.o_adelay); if (phase) *phase = (const double*)(m.buf.p + m.o_aphase); if (path_match) *path_match = (const int32_t*)(m.buf.p + m.o_apm);
         return RTS_OK;
     }
     if (power || doppler) {
@@ -2090,7 +2085,6 @@ extern "C" int rts_cube_reduce(RtsHandle* hs, uint32_t n, int transport)
     RtsContext* c0 = hs[0];
     RTS_HIP(hipSetDevice(c0->device));
     DevBuf<double> tmp; RTS_HIP(tmp.reserve(doubles));
-    struct FreeTmp { DevBuf<double>& t; ~FreeTmp() { t.release(); } } ft{tmp};
     for (uint32_t i = 1; i < n; i++) {
         RTS_HIP(hipMemcpyPeerAsync(tmp.p, c0->device, hs[i]->cube, hs[i]->device, sizeof(double) * doubles, c0->stream));
         k_add_f64<<<(unsigned)((doubles + 255) / 256), 256, 0, c0->stream>>>(c0->cube, tmp.p, doubles);
@@ -2282,14 +2276,13 @@ extern "C" int rts_self_test_math(RtsHandle c, const float* y, const float* x, f
 {
     CHECK_HANDLE(c);
     if (n == 0) return RTS_OK;
-    float *dy, *dx, *dat; double *da, *db, *ddv, *dsq;
-    RTS_HIP(hipMalloc((void**)&dy, 4*n)); RTS_HIP(hipMalloc((void**)&dx, 4*n)); RTS_HIP(hipMalloc((void**)&dat, 4*n));
-    RTS_HIP(hipMalloc((void**)&da, 8*n)); RTS_HIP(hipMalloc((void**)&db, 8*n)); RTS_HIP(hipMalloc((void**)&ddv, 8*n)); RTS_HIP(hipMalloc((void**)&dsq, 8*n));
-    RTS_HIP(hipMemcpy(dy, y, 4*n, hipMemcpyHostToDevice)); RTS_HIP(hipMemcpy(dx, x, 4*n, hipMemcpyHostToDevice));
-    RTS_HIP(hipMemcpy(da, a, 8*n, hipMemcpyHostToDevice)); RTS_HIP(hipMemcpy(db, b, 8*n, hipMemcpyHostToDevice));
-    k_self_test_math<<<(n + 255)/256, 256, 0, c->stream>>>(dy, dx, dat, da, db, ddv, dsq, n);
+    DevBuf<float> dy, dx, dat; DevBuf<double> da, db, ddv, dsq;
+    RTS_HIP(dy.reserve(n)); RTS_HIP(dx.reserve(n)); RTS_HIP(dat.reserve(n));
+    RTS_HIP(da.reserve(n)); RTS_HIP(db.reserve(n)); RTS_HIP(ddv.reserve(n)); RTS_HIP(dsq.reserve(n));
+    RTS_HIP(hipMemcpy(dy.p, y, 4*n, hipMemcpyHostToDevice)); RTS_HIP(hipMemcpy(dx.p, x, 4*n, hipMemcpyHostToDevice));
+    RTS_HIP(hipMemcpy(da.p, a, 8*n, hipMemcpyHostToDevice)); RTS_HIP(hipMemcpy(db.p, b, 8*n, hipMemcpyHostToDevice));
+    k_self_test_math<<<(n + 255)/256, 256, 0, c->stream>>>(dy.p, dx.p, dat.p, da.p, db.p, ddv.p, dsq.p, n);
     RTS_HIP(hipGetLastError()); RTS_HIP(hipStreamSynchronize(c->stream));
-    RTS_HIP(hipMemcpy(atan2f_out, dat, 4*n, hipMemcpyDeviceToHost)); RTS_HIP(hipMemcpy(div_out, ddv, 8*n, hipMemcpyDeviceToHost)); RTS_HIP(hipMemcpy(sqrt_out, dsq, 8*n, hipMemcpyDeviceToHost));
-    (void)hipFree(dy); (void)hipFree(dx); (void)hipFree(dat); (void)hipFree(da); (void)hipFree(db); (void)hipFree(ddv); (void)hipFree(dsq);
+    RTS_HIP(hipMemcpy(atan2f_out, dat.p, 4*n, hipMemcpyDeviceToHost)); RTS_HIP(hipMemcpy(div_out, ddv.p, 8*n, hipMemcpyDeviceToHost)); RTS_HIP(hipMemcpy(sqrt_out, dsq.p, 8*n, hipMemcpyDeviceToHost));
     return RTS_OK;
 }

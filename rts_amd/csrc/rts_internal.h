@@ -10,6 +10,7 @@
 #include "rts_pattern.h"
 #include "rts_waveform.h"
 #include "rts_noise.h"
+#include "rts_owned.h"            // DevBuf, PinBuf: device and pinned host memory that frees itself
 #include "rts_launch_plan.h"      // RTS_BLOCK, RTS_WTILE, RTS_COOP_GROUP, RTS_STACK_OVF and the host arithmetic of a launch
 
 // ----------------------------------------------------------------------------- HBM layout
@@ -217,23 +218,6 @@ struct RtsPinned {
     double gsum[5 * RTS_PIN_GROUPS]; uint64_t gkey[RTS_PIN_GROUPS]; uint64_t grow[RTS_PIN_GROUPS]; uint32_t gmin[RTS_PIN_GROUPS];
 };
 
-template <typename T> struct DevBuf {
-    T* p = nullptr; size_t cap = 0;
-    hipError_t reserve(size_t n) {
-        if (n <= cap) return hipSuccess;
-        // hipFree is a device-wide synchronisation (it stalls the other handles' launches): grow geometrically, and give
-        // the many small buffers sized by a pulse's received-ray count room to begin with
-        size_t want = n + n / 8 + 16;
-        if (want < 2 * cap) want = 2 * cap;
-        if (sizeof(T) <= 144 && want < 65536) want = 65536;
-        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-        hipError_t e = hipMalloc((void**)&p, want * sizeof(T));
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
-
 // Handles joined by rts_link_handles share one trace stream: their trace kernels execute one after the other, in the
 // order the pulses were begun; the rest of each pulse (scene placement before, ordering / finalise /
 // aggregation after) runs on the handle's own (high-priority) stream and overlaps with the other handles' trace kernels.
@@ -256,8 +240,6 @@ struct RtsScene {
         return d_tri_vidx.cap * 4 + d_tri_nidx.cap * 4 + d_vert_targ.cap * 4 + d_norm_targ.cap * 4 + d_prim_targ.cap * 4 + d_verts_local.cap * 8 +
                d_normals_local.cap * 8 + (d_nodes4.cap + d_nodes4v.cap) * sizeof(RtsNode4) + d_leaf_prim.cap * 4;
     }
-    void release() { d_tri_vidx.release(); d_tri_nidx.release(); d_vert_targ.release(); d_norm_targ.release(); d_prim_targ.release();
-                     d_verts_local.release(); d_normals_local.release(); d_nodes4.release(); d_nodes4v.release(); d_leaf_prim.release(); }
 };
 
 // The tile-cost HISTORY (what every wave tile of the W^3 lattice cost the launch that traced it last: the cost order, the cooperative kernel's
@@ -283,7 +265,7 @@ struct RtsPatArgs { const RtsPatView* pats; const double* rx; uint32_t n_rx, n_t
 // (k_set_values: the power / Doppler the simulator's callbacks produced).  cap rows of: PerRayData | path row | RCS-angle row | slot |
 // aggregated power, doppler, delay, phase, pathMatch | values in: power, doppler.
 struct RtsHostMirror {
-    char* host = nullptr; char* dev = nullptr; size_t bytes = 0; uint32_t cap = 0, D = 0;
+    PinBuf<char> buf; uint32_t cap = 0, D = 0;       // buf.p / buf.dev: the block as the host / the kernels address it; cap: rows
     size_t o_rays = 0, o_paths = 0, o_angles = 0, o_slots = 0, o_apower = 0, o_adoppler = 0, o_adelay = 0, o_aphase = 0, o_apm = 0, o_vpower = 0, o_vdoppler = 0;
     bool recv_valid = false, agg_valid = false;      // the mirror holds the last pulse's received set / aggregation outputs (once the stream has drained)
     bool want = false;                               // this pulse's post-processing feeds the mirror (set by rts_received_prefetch, cleared by the next rts_trace_pulse_begin)
@@ -293,16 +275,16 @@ struct RtsAggPending { bool valid = false, wide = false, rows = false; uint32_t 
 
 struct RtsContext {
     RtsParams params;
-    uint32_t depth;                 // D = max_refr + max_refl
-    int device;
+    uint32_t depth = 0;             // D = max_refr + max_refl
+    int device = 0;
     hipStream_t stream = nullptr;       // scene placement, ordering, finalise, aggregation (high priority: short kernels)
     hipStream_t tstream = nullptr;      // trace kernels (the link group's, see RtsGate)
-    hipStream_t cstream = nullptr; hipEvent_t ev_coop[2];      // the cooperative trace kernel of a launch runs beside the ordinary one; stream created on first use (rts_trace.hip)
+    hipStream_t cstream = nullptr; hipEvent_t ev_coop[2] = {nullptr, nullptr};      // the cooperative trace kernel of a launch runs beside the ordinary one; stream created on first use (rts_trace.hip)
     uint32_t coop_grid_max = 1024;      // most blocks of the cooperative kernel (RTS_COOP_GRID)
     uint32_t coop_spread = 1;           // XCD lists a head tile's units are dealt to (RTS_COOP_SPREAD = 1 / 2 / 4 / 8)
     uint32_t n_head_hint = 0;           // head count of the handle's previous order build (came home with that launch's counters)
     uint32_t last_coop_grid = 0;        // blocks of the cooperative kernel in the handle's last launch (0: none was launched)
-    hipEvent_t ev[9];
+    hipEvent_t ev[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     // scene: the shared static part, and this handle's placement of it
     RtsScene* scene = nullptr;          // never null after rts_create
     DevBuf<double> d_verts_world, d_normals_world;
@@ -375,7 +357,7 @@ struct RtsContext {
     RtsHostMirror mirror;               // rts_received_prefetch / rts_received_view / rts_finalise_values / rts_aggregated_view
     std::vector<PerRayData> v_rays; std::vector<int32_t> v_paths; std::vector<double> v_angles, v_apower, v_adoppler, v_adelay, v_aphase; std::vector<uint64_t> v_slots; std::vector<int32_t> v_apm;      // the views' fallback storage (sets beyond the mirror's capacity)
     std::vector<PerRayData> v_agg_rays; unsigned v_recv_have = 0;      // rts_aggregated_view's own scratch (never the received view's storage); bits: which of v_rays / v_paths / v_angles / v_slots hold THIS pulse's set already
-    RtsRxDev* pin_rx = nullptr; uint32_t pin_rx_cap = 0; std::vector<RtsRxDev> rx_host;      // receivers: last values set (an unchanged set is not uploaded again) and the pinned staging of the asynchronous upload
+    PinBuf<RtsRxDev> pin_rx; std::vector<RtsRxDev> rx_host;      // receivers: last values set (an unchanged set is not uploaded again) and the pinned staging of the asynchronous upload
     RtsCubeParams cube_params; double* cube = nullptr; DevBuf<double> d_cube_own; bool cube_set = false;
     DevBuf<double> d_doppler_own; double* doppler = nullptr; uint32_t doppler_n = 0;       // slow-time transform of the cube (rts_cube_doppler)
     DevBuf<double> d_wave; uint32_t wave_M = 0, wave_L = 0; bool wave_set = false;         // the transmit waveform (rts_cube_set_waveform): M interleaved samples, L taps
@@ -385,17 +367,24 @@ struct RtsContext {
     bool doppler_fresh = false;         // rts_cube_doppler ran on the attached cube (rts_cube_detect without a map takes its output)
     bool agg_delay_in = true;           // rts_aggregate_device: the delay / phase arrays carry initial sums (rs::kernel_wrapper's in-out arguments); false: they start at zero
     int64_t agg_base_local = 0;         // pathMatch value of received ray i after rts_aggregate = agg_base_local + i
-    RtsPinned* pin = nullptr; RtsPinned* pin_dev = nullptr;      // pinned host staging and its address on the device: kernels write the small per-pulse read-backs (counters, group table) straight into it
+    PinBuf<RtsPinned> pin;      // pinned host staging (one RtsPinned) and its address on the device (pin.dev): kernels write the small per-pulse read-backs (counters, group table) straight into it
     bool rcs_uploaded = false; DevBuf<double> d_rcsval; int n_cu = 0; bool stats_pending = false; bool agg_timed = false, fin_timed = false;
     RtsStats stats;
     // tabulated patterns (rts_set_patterns): one device buffer per handle, and the per-pulse receiver rows behind a pinned staging block
     // that is rewritten only after the copy of the previous rows has run (ev_pat)
     DevBuf<char> d_pat; uint32_t pat_n_rx = 0, pat_n_targets = 0; bool pat_set = false;
-    DevBuf<double> d_pat_rx; double* pin_pat = nullptr; size_t pin_pat_cap = 0; hipEvent_t ev_pat = nullptr; bool ev_pat_armed = false;
+    DevBuf<double> d_pat_rx; PinBuf<double> pin_pat; hipEvent_t ev_pat = nullptr; bool ev_pat_armed = false;
     double pulse_org[3] = {0, 0, 0}, pulse_dir[2] = {0, 0}; bool pulse_traced = false;      // the last traced pulse's ray_origin / tx_dir; false after rts_kernel_wrapper_on
     double lap_s[8] = {0, 0, 0, 0, 0, 0, 0, 0}; uint64_t lap_n[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // RTS_LAP=1: host time per section of rts_trace_pulse_begin
     RtsGate* gate = nullptr; bool pulse_open = false;   // gate: never null after rts_create
+    // Every raw handle above starts null and the destructor skips what is null: `delete c` is right for a handle that rts_create
+    // left half built.  The body (rts_api.hip) drains the streams, drops the shared objects and destroys the events and streams; the
+    // DevBuf / PinBuf members free themselves after it.  The caller makes the handle's device current first.
+    ~RtsContext();
 };
+void rts_scene_unref(RtsScene* s);          // drop one reference; the last one deletes the object (and with it its buffers)
+void rts_hist_unref(RtsTileHist* h);
+void rts_gate_unref(RtsGate* g);            // ... and destroys the group's trace stream
 
 // implemented in the .hip units
 int rts_sah_build(const double* verts, const uint32_t* tris, uint32_t n_tris, double split_budget, std::vector<RtsNode4>& nodes, std::vector<uint32_t>& leaf_prim, RtsBlasInfo& out);

@@ -673,12 +673,9 @@ int rts_lbvh_build_device(RtsContext* c, RtsScene* ns, const std::vector<uint32_
     ns->n_nodes = 0; ns->n_leaves = 0;
     if (n_max == 0) { RTS_HIP(ns->d_nodes4.reserve(1)); RTS_HIP(ns->d_leaf_prim.reserve(1)); return RTS_OK; }
 
-    // ---- temporaries of both passes (grown on demand)
+    // ---- temporaries of both passes (grown on demand; every temporary of this function frees itself on return)
     DevBuf<float> d_prim_box; DevBuf<uint64_t> d_keys, d_keys_sorted; DevBuf<uint32_t> d_vals, d_vals_sorted, d_bounds, d_flags, d_ref_tri; DevBuf<int32_t> d_parent, d_leaf_parent;
     DevBuf<Node2> d_nodes2; DevBuf<int2> d_range; DevBuf<char> d_tmp;
-    struct Free { DevBuf<float>& a; DevBuf<uint64_t>& b; DevBuf<uint64_t>& b2; DevBuf<uint32_t>& c1; DevBuf<uint32_t>& c2; DevBuf<uint32_t>& c3; DevBuf<uint32_t>& c4; DevBuf<uint32_t>& c5; DevBuf<int32_t>& d1; DevBuf<int32_t>& d2; DevBuf<Node2>& e; DevBuf<int2>& f; DevBuf<char>& g;
-                  ~Free() { a.release(); b.release(); b2.release(); c1.release(); c2.release(); c3.release(); c4.release(); c5.release(); d1.release(); d2.release(); e.release(); f.release(); g.release(); } }
-        free_all{d_prim_box, d_keys, d_keys_sorted, d_vals, d_vals_sorted, d_bounds, d_flags, d_ref_tri, d_parent, d_leaf_parent, d_nodes2, d_range, d_tmp};
     size_t tmp = 0;
     auto ensure_tmp = [&](uint32_t r) -> int {
         RTS_HIP(d_prim_box.reserve(6 * (size_t)r)); RTS_HIP(d_keys.reserve(r)); RTS_HIP(d_keys_sorted.reserve(r)); RTS_HIP(d_vals.reserve(r)); RTS_HIP(d_vals_sorted.reserve(r)); RTS_HIP(d_ref_tri.reserve(r));
@@ -695,9 +692,6 @@ int rts_lbvh_build_device(RtsContext* c, RtsScene* ns, const std::vector<uint32_
     int crowd_rounds = 0; { const char* e = getenv("RTS_CROWD_ROUNDS"); if (e) crowd_rounds = std::max(0, std::min(3, atoi(e))); }
     DevBuf<uint32_t> d_sah_bins, d_sah_cb, d_sah_fill, d_boost; DevBuf<SahSplit> d_sah_split; DevBuf<SahWork> d_sah_work_a, d_sah_work_b;
     DevBuf<RtsNode4> d_nodes4_tmp; DevBuf<uint32_t> d_reach, d_newid, d_rflag;
-    struct FreeC { DevBuf<RtsNode4>& a; DevBuf<uint32_t>& b; DevBuf<uint32_t>& c1; DevBuf<uint32_t>& d; ~FreeC() { a.release(); b.release(); c1.release(); d.release(); } } free_c{d_nodes4_tmp, d_reach, d_newid, d_rflag};
-    struct FreeSah { DevBuf<uint32_t>& a; DevBuf<uint32_t>& b; DevBuf<uint32_t>& c1; DevBuf<uint32_t>& c2; DevBuf<SahSplit>& d; DevBuf<SahWork>& e; DevBuf<SahWork>& f; ~FreeSah() { a.release(); b.release(); c1.release(); c2.release(); d.release(); e.release(); f.release(); } }
-        free_sah{d_sah_bins, d_sah_cb, d_sah_fill, d_boost, d_sah_split, d_sah_work_a, d_sah_work_b};
     RTS_HIP(d_boost.reserve((size_t)ns->n_prims + 2)); RTS_HIP(hipMemsetAsync(d_boost.p, 0, sizeof(uint32_t) * ((size_t)ns->n_prims + 2), st));       // per triangle: 1 = twice the slabs (k_crowd); last word: a counter
 
     // the level loop of the binned-SAH builder over the nv valid references of the current mesh (boxes in d_prim_box):
@@ -740,7 +734,6 @@ int rts_lbvh_build_device(RtsContext* c, RtsScene* ns, const std::vector<uint32_
 
     // ---- pass A: the split threshold of every mesh and its number of references (valid ones first after the sort)
     DevBuf<double> d_acc; DevBuf<uint32_t> d_cnt, d_off, d_nvr; DevBuf<char> d_scan_tmp;
-    struct FreeA { DevBuf<double>& a; DevBuf<uint32_t>& b; DevBuf<uint32_t>& c1; DevBuf<uint32_t>& d; DevBuf<char>& e; ~FreeA() { a.release(); b.release(); c1.release(); d.release(); e.release(); } } free_a{d_acc, d_cnt, d_off, d_nvr, d_scan_tmp};
     RTS_HIP(d_acc.reserve(2)); RTS_HIP(d_cnt.reserve(n_max)); RTS_HIP(d_off.reserve(n_max)); RTS_HIP(d_nvr.reserve(1));
     size_t scan_tmp = 0;
     RTS_HIP(rocprim::exclusive_scan(nullptr, scan_tmp, d_cnt.p, d_off.p, 0u, n_max, rocprim::plus<uint32_t>(), st));

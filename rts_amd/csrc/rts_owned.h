@@ -1,0 +1,65 @@
+// rts_owned.h -- the two owning buffer types of librts_amd.so: device memory (DevBuf) and pinned host memory (PinBuf).
+//
+// Both free what they hold in their destructor and are move-only, so a struct that holds them (RtsContext, RtsScene,
+// RtsTileHist, a function's temporaries) needs no release list of its own: `delete` or leaving the scope frees the buffers,
+// members in reverse order of declaration.  hipFree waits for the device, so a buffer an enqueued kernel still reads is not
+// freed under it; hipHostFree does not say so: the owner of a PinBuf synchronises the stream that reads it first.
+//
+// NO OBJECT OF THESE TYPES MAY HAVE STATIC STORAGE DURATION (nor a struct that holds one): its destructor would call HIP after
+// the runtime has shut down.  The library has none; process-lifetime contexts are held by pointer and never deleted.
+//
+// Host code only, HIP's API header and the standard library only (tests/owned/owned_main.cpp builds it without the runtime).
+#pragma once
+#include <hip/hip_runtime_api.h>
+#include <stddef.h>
+
+template <typename T> struct DevBuf {
+    T* p = nullptr; size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; } return *this; }
+    ~DevBuf() { release(); }
+    hipError_t reserve(size_t n) {
+        if (n <= cap) return hipSuccess;
+        // hipFree is a device-wide synchronisation (it stalls the other handles' launches): grow geometrically, and give
+        // the many small buffers sized by a pulse's received-ray count room to begin with
+        size_t want = n + n / 8 + 16;
+        if (want < 2 * cap) want = 2 * cap;
+        if (sizeof(T) <= 144 && want < 65536) want = 65536;
+        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
+        hipError_t e = hipMalloc((void**)&p, want * sizeof(T));
+        if (e == hipSuccess) cap = want;
+        return e;
+    }
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+};
+
+// Pinned host staging (hipHostMalloc).  cap elements at p; dev: the same block as kernels address it, fetched only for the
+// buffers that kernels write or read in place (want_dev, the same at every call for one buffer).  The caller chooses the size
+// (no growth rule here: each staging block has its own) and, before a regrow, synchronises whatever stream may still read
+// the old block.
+template <typename T> struct PinBuf {
+    T* p = nullptr; T* dev = nullptr; size_t cap = 0;
+    PinBuf() = default;
+    PinBuf(const PinBuf&) = delete;
+    PinBuf& operator=(const PinBuf&) = delete;
+    PinBuf(PinBuf&& o) noexcept : p(o.p), dev(o.dev), cap(o.cap) { o.p = nullptr; o.dev = nullptr; o.cap = 0; }
+    PinBuf& operator=(PinBuf&& o) noexcept { if (this != &o) { release(); p = o.p; dev = o.dev; cap = o.cap; o.p = nullptr; o.dev = nullptr; o.cap = 0; } return *this; }
+    ~PinBuf() { release(); }
+    hipError_t reserve(size_t n, bool want_dev) {
+        if (n <= cap) return hipSuccess;
+        release();
+        hipError_t e = hipHostMalloc((void**)&p, n * sizeof(T), hipHostMallocDefault);
+        if (e != hipSuccess) { p = nullptr; return e; }
+        if (want_dev) {
+            void* dp = nullptr; e = hipHostGetDevicePointer(&dp, p, 0);
+            if (e != hipSuccess) { release(); return e; }
+            dev = static_cast<T*>(dp);
+        }
+        cap = n;
+        return hipSuccess;
+    }
+    void release() { if (p) (void)hipHostFree(p); p = nullptr; dev = nullptr; cap = 0; }
+};

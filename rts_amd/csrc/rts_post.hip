@@ -520,16 +520,15 @@ int rts_mirror_reserve(RtsContext* c, uint32_t rows)
 {
     RtsHostMirror& m = c->mirror;
     const uint32_t D = c->depth;
-    if (m.host && m.cap >= rows && m.D == D) return RTS_OK;
-    if (m.host) { RTS_HIP(hipStreamSynchronize(c->stream)); (void)hipHostFree(m.host); m.host = nullptr; m.dev = nullptr; m.cap = 0; }
+    if (m.buf.p && m.cap >= rows && m.D == D) return RTS_OK;
+    if (m.buf.p) { RTS_HIP(hipStreamSynchronize(c->stream)); m.buf.release(); m.cap = 0; }
     uint32_t cap = std::max<uint32_t>(rows, RTS_SMALL_CAP32); cap = (cap + 63u) & ~63u;
     size_t o = 0;
     auto take = [&](size_t bytes_per_row) { const size_t at = o; o += ((size_t)cap * bytes_per_row + 255) & ~(size_t)255; return at; };
     m.o_rays = take(sizeof(PerRayData)); m.o_paths = take(4 * (size_t)std::max(D, 1u)); m.o_angles = take(16 * (size_t)std::max(D, 1u)); m.o_slots = take(8);
     m.o_apower = take(8); m.o_adoppler = take(8); m.o_adelay = take(8); m.o_aphase = take(8); m.o_apm = take(4); m.o_vpower = take(8); m.o_vdoppler = take(8);
-    RTS_HIP(hipHostMalloc((void**)&m.host, o, hipHostMallocDefault));
-    void* dp = nullptr; RTS_HIP(hipHostGetDevicePointer(&dp, m.host, 0));
-    m.dev = (char*)dp; m.bytes = o; m.cap = cap; m.D = D; m.recv_valid = false; m.agg_valid = false;
+    RTS_HIP(m.buf.reserve(o, true));
+    m.cap = cap; m.D = D; m.recv_valid = false; m.agg_valid = false;
     return RTS_OK;
 }
 
@@ -541,10 +540,10 @@ int rts_post_mirror_received(RtsContext* c)
     if (R == 0) { m.recv_valid = true; return RTS_OK; }
     if (R > m.cap) return RTS_OK;                                  // (a set beyond the mirror: the views fall back to copies)
     RtsMirrorSegs g;
-    g.dst[0] = (uint32_t*)(m.dev + m.o_rays); g.src[0] = (const uint32_t*)c->d_rx_rays.p; g.row_words[0] = sizeof(PerRayData) / 4;
-    g.dst[1] = (uint32_t*)(m.dev + m.o_paths); g.src[1] = (const uint32_t*)c->d_rx_paths.p; g.row_words[1] = D;
-    g.dst[2] = (uint32_t*)(m.dev + m.o_angles); g.src[2] = (const uint32_t*)c->d_rx_angles.p; g.row_words[2] = 4 * D;
-    g.dst[3] = (uint32_t*)(m.dev + m.o_slots); g.src[3] = (const uint32_t*)c->d_rx_slots.p; g.row_words[3] = 2;
+    g.dst[0] = (uint32_t*)(m.buf.dev + m.o_rays); g.src[0] = (const uint32_t*)c->d_rx_rays.p; g.row_words[0] = sizeof(PerRayData) / 4;
+    g.dst[1] = (uint32_t*)(m.buf.dev + m.o_paths); g.src[1] = (const uint32_t*)c->d_rx_paths.p; g.row_words[1] = D;
+    g.dst[2] = (uint32_t*)(m.buf.dev + m.o_angles); g.src[2] = (const uint32_t*)c->d_rx_angles.p; g.row_words[2] = 4 * D;
+    g.dst[3] = (uint32_t*)(m.buf.dev + m.o_slots); g.src[3] = (const uint32_t*)c->d_rx_slots.p; g.row_words[3] = 2;
     const uint32_t bx = std::min<uint32_t>(blocks_for((size_t)R * (sizeof(PerRayData) / 4), 256), 64u);
     k_mirror_rows<<<dim3(bx, 4), 256, 0, c->stream>>>(g, R, c->recv_dev);
     RTS_HIP(hipGetLastError());
@@ -558,9 +557,9 @@ int rts_post_mirror_aggregated(RtsContext* c)
     const uint32_t R = (uint32_t)c->n_recv;
     m.agg_valid = false;
     if (R == 0) { m.agg_valid = true; return RTS_OK; }
-    if (!m.host || R > m.cap) return RTS_OK;
-    k_mirror_agg<<<blocks_for(R, 256), 256, 0, c->stream>>>(c->d_rx_rays.p, c->d_delay.p, c->d_phase.p, c->d_pathmatch.p, R, (double*)(m.dev + m.o_apower), (double*)(m.dev + m.o_adoppler),
-                                                           (double*)(m.dev + m.o_adelay), (double*)(m.dev + m.o_aphase), (int32_t*)(m.dev + m.o_apm), c->recv_dev);
+    if (!m.buf.p || R > m.cap) return RTS_OK;
+    k_mirror_agg<<<blocks_for(R, 256), 256, 0, c->stream>>>(c->d_rx_rays.p, c->d_delay.p, c->d_phase.p, c->d_pathmatch.p, R, (double*)(m.buf.dev + m.o_apower), (double*)(m.buf.dev + m.o_adoppler),
+                                                           (double*)(m.buf.dev + m.o_adelay), (double*)(m.buf.dev + m.o_aphase), (int32_t*)(m.buf.dev + m.o_apm), c->recv_dev);
     RTS_HIP(hipGetLastError());
     m.agg_valid = true;
     return RTS_OK;
@@ -617,11 +616,11 @@ int rts_post_finalise(RtsContext* c, const double* rcs_host, double wl, double g
     const uint32_t nt = (uint32_t)c->scene->meshes.size();
     RTS_HIP(c->d_rcsval.reserve(nt + 1));
     bool changed = !c->rcs_uploaded;
-    for (uint32_t t = 0; t < nt && t < 256; t++) changed = changed || memcmp(&c->pin->rcs[t], &rcs_host[t], sizeof(double)) != 0;
+    for (uint32_t t = 0; t < nt && t < 256; t++) changed = changed || memcmp(&c->pin.p->rcs[t], &rcs_host[t], sizeof(double)) != 0;
     if (changed) {                                                            // (the same values pulse after pulse: uploaded once)
         RTS_HIP(hipStreamSynchronize(c->stream));                            // an upload of the previous values may still read the staging
-        for (uint32_t t = 0; t < nt && t < 256; t++) c->pin->rcs[t] = rcs_host[t];
-        if (nt) RTS_HIP(hipMemcpyAsync(c->d_rcsval.p, c->pin->rcs, sizeof(double)*nt, hipMemcpyHostToDevice, c->stream));
+        for (uint32_t t = 0; t < nt && t < 256; t++) c->pin.p->rcs[t] = rcs_host[t];
+        if (nt) RTS_HIP(hipMemcpyAsync(c->d_rcsval.p, c->pin.p->rcs, sizeof(double)*nt, hipMemcpyHostToDevice, c->stream));
         c->rcs_uploaded = true;
     }
     k_finalise<<<blocks_for(R, 256), 256, 0, c->stream>>>(c->d_rx_rays.p, c->d_rx_paths.p, R, c->depth, c->d_rcsval.p, nt, wl, gt, gr, carrier, cspeed, c->recv_dev);
@@ -685,17 +684,12 @@ int rts_pattern_pulse_upload(RtsContext* c, const RtsSpecParams& q, RtsPatArgs* 
 {
     const size_t n = q.pat_rx.size();
     if (c->ev_pat_armed) { RTS_HIP(hipEventSynchronize(c->ev_pat)); c->ev_pat_armed = false; }
-    if (c->pin_pat_cap < n + 8) {
-        if (c->pin_pat) { RTS_HIP(hipHostFree(c->pin_pat)); c->pin_pat = nullptr; c->pin_pat_cap = 0; }
-        const size_t cap = std::max<size_t>(n + 8, 512);
-        RTS_HIP(hipHostMalloc((void**)&c->pin_pat, sizeof(double) * cap, hipHostMallocDefault));
-        c->pin_pat_cap = cap;
-    }
+    if (c->pin_pat.cap < n + 8) RTS_HIP(c->pin_pat.reserve(std::max<size_t>(n + 8, 512), false));
     if (!c->ev_pat) RTS_HIP(hipEventCreateWithFlags(&c->ev_pat, hipEventDisableTiming));
     RTS_HIP(c->d_pat_rx.reserve(n + 8));
     if (n) {
-        memcpy(c->pin_pat, q.pat_rx.data(), sizeof(double) * n);
-        RTS_HIP(hipMemcpyAsync(c->d_pat_rx.p, c->pin_pat, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+        memcpy(c->pin_pat.p, q.pat_rx.data(), sizeof(double) * n);
+        RTS_HIP(hipMemcpyAsync(c->d_pat_rx.p, c->pin_pat.p, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
         RTS_HIP(hipEventRecord(c->ev_pat, c->stream)); c->ev_pat_armed = true;
     }
     RtsPatArgs& a = *out;
@@ -1305,11 +1299,11 @@ int rts_post_all_small(RtsContext* c, uint32_t cap, const RtsSpecParams& sp, boo
     RTS_HIP(c->d_rx_rays.reserve(cap)); RTS_HIP(c->d_rx_paths.reserve((size_t)cap*D + 1)); RTS_HIP(c->d_rx_angles.reserve((size_t)cap*D*2 + 1)); RTS_HIP(c->d_rx_slots.reserve(cap));
     RTS_HIP(c->d_rcsval.reserve(nt + 1));
     bool changed = sp.fin == 0 && !c->rcs_uploaded;                     // (the pattern finaliser reads no per-target constants)
-    for (uint32_t t = 0; sp.fin == 0 && t < nt && t < 256; t++) changed = changed || memcmp(&c->pin->rcs[t], &sp.rcs[t], sizeof(double)) != 0;
+    for (uint32_t t = 0; sp.fin == 0 && t < nt && t < 256; t++) changed = changed || memcmp(&c->pin.p->rcs[t], &sp.rcs[t], sizeof(double)) != 0;
     if (changed) {
         RTS_HIP(hipStreamSynchronize(st));
-        for (uint32_t t = 0; t < nt && t < 256; t++) c->pin->rcs[t] = sp.rcs[t];
-        if (nt) RTS_HIP(hipMemcpyAsync(c->d_rcsval.p, c->pin->rcs, sizeof(double)*nt, hipMemcpyHostToDevice, st));
+        for (uint32_t t = 0; t < nt && t < 256; t++) c->pin.p->rcs[t] = sp.rcs[t];
+        if (nt) RTS_HIP(hipMemcpyAsync(c->d_rcsval.p, c->pin.p->rcs, sizeof(double)*nt, hipMemcpyHostToDevice, st));
         c->rcs_uploaded = true;
     }
     const int32_t max_path = (int32_t)nt - 1, max_rx = c->n_rx ? (int32_t)c->n_rx - 1 : 0;
@@ -1329,7 +1323,7 @@ int rts_post_all_small(RtsContext* c, uint32_t cap, const RtsSpecParams& sp, boo
     uint32_t* gstart = c->d_gcount.p; uint32_t* d_G = c->d_gcount.p + R + 2;
     double* gsum = c->d_gsum.p; double* tile_first = gsum + 5*R; double* tile_last = tile_first + 5*(size_t)ntiles;
     double* d_rxtot = c->d_rcs.p; uint32_t* d_rxmin = (uint32_t*)(c->d_rcs.p + 5*(size_t)n_rx_tab);
-    RtsPinned* pd = c->pin_dev;
+    RtsPinned* pd = c->pin.dev;
     const uint64_t base = use_rows ? 0 : sp.base;
     RtsPostAll q; memset(&q, 0, sizeof(q));
     q.ta = c->last_args; q.rec = c->d_recv.p; q.cap = cap; q.n_rays = c->n_rays; q.with_chain = c->last_args.max_refr != 0 ? 1 : 0;
@@ -1440,7 +1434,7 @@ int rts_aggregate_device(RtsContext* c, int32_t max_path, int32_t max_rx, const 
     }
     k_agg_tiles<<<ntiles, AGG_TILE, 0, st>>>(d_rays, c->d_aidx_sorted.p, c->d_gid.p, gstart, R, cspeed, carrier, gsum, tile_first, tile_last, c->recv_dev);
     if (small) {
-        RtsPinned* pd = c->pin_dev;
+        RtsPinned* pd = c->pin.dev;
         const uint32_t spec_s = std::min<uint32_t>(R, RTS_PIN_GROUPS);
         const RtsAggFinish fq = {d_rays, c->d_aidx_sorted.p, c->d_akeys_sorted.p, c->d_gid.p, gstart, tile_first, tile_last, gsum, c->d_gmin.p, c->d_gkey.p, d_G,
                                  d_rows, d_rows ? c->d_grow.p : nullptr, shift, n_rx_tab, d_rxtot, d_rxmin, (int64_t)base, d_npath, d_power_sum, d_doppler_sum, d_delay, d_phase, d_pm,
@@ -1469,7 +1463,7 @@ int rts_aggregate_device(RtsContext* c, int32_t max_path, int32_t max_rx, const 
     // group table to the host: count + the first AGG_SPEC groups speculatively in one batch (pinned), rest on demand
     const uint32_t spec = std::min<uint32_t>(R, RTS_PIN_GROUPS);
     // (written by ONE kernel straight into the pinned block -- five small device-to-host copies per pulse before)
-    k_agg_export<<<blocks_for(spec, 256), 256, 0, st>>>(d_G, gsum, c->d_gmin.p, c->d_gkey.p, d_rows ? c->d_grow.p : nullptr, spec, &c->pin_dev->G, c->pin_dev->gsum, c->pin_dev->gmin, c->pin_dev->gkey, c->pin_dev->grow);
+    k_agg_export<<<blocks_for(spec, 256), 256, 0, st>>>(d_G, gsum, c->d_gmin.p, c->d_gkey.p, d_rows ? c->d_grow.p : nullptr, spec, &c->pin.dev->G, c->pin.dev->gsum, c->pin.dev->gmin, c->pin.dev->gkey, c->pin.dev->grow);
     RTS_HIP(hipGetLastError());
     // The table is READ when somebody asks for it (rts_aggregate_fetch): a caller that keeps several pulses in flight enqueues the
     // next pulse while this one's ~16 small kernels wait their turn among the trace kernels' blocks -- the submitting thread used
@@ -1487,7 +1481,7 @@ int rts_aggregate_fetch(RtsContext* c, std::vector<RtsGroup>* groups)
     if (!ap.valid) return RTS_OK;
     ap.valid = false;
     hipStream_t st = c->stream;
-    RtsPinned* pin = c->pin;
+    RtsPinned* pin = c->pin.p;
     const uint32_t R = ap.R, D = ap.D, B = ap.B, shift = ap.shift, spec = ap.spec; const bool wide = ap.wide; const uint64_t base = ap.base;
     const bool d_rows = ap.rows; double* gsum = ap.gsum; (void)R;
     RTS_HIP(rts_stream_wait(c, st));

@@ -1377,7 +1377,7 @@ static void rts_trace_dispatch(const RtsTraceArgs& a, bool count_traversal, unsi
 int rts_trace_launch(RtsContext* c, const RtsTraceArgs& a, bool count_traversal, unsigned coop_grid)
 {
     if (a.n_rays == 0) {                                            // nothing to trace (an interleaved part without launch indices): the counters still go home, as zeros
-        k_sum_counters<<<1, 256, 0, c->tstream_now>>>(a.block_counters, 0u, a.counters, nullptr, c->pin_dev->cnt);
+        k_sum_counters<<<1, 256, 0, c->tstream_now>>>(a.block_counters, 0u, a.counters, nullptr, c->pin.dev->cnt);
         RTS_HIP(hipGetLastError());
         return RTS_OK;
     }
@@ -1393,7 +1393,7 @@ int rts_trace_launch(RtsContext* c, const RtsTraceArgs& a, bool count_traversal,
     }
     rts_trace_dispatch<false>(a, count_traversal, grid, st);
     if (coop_grid) RTS_HIP(hipStreamWaitEvent(st, c->ev_coop[1], 0));
-    k_sum_counters<<<1, 256, 0, st>>>(a.block_counters, grid + coop_grid, a.counters, a.tile_head_all, c->pin_dev->cnt);
+    k_sum_counters<<<1, 256, 0, st>>>(a.block_counters, grid + coop_grid, a.counters, a.tile_head_all, c->pin.dev->cnt);
     RTS_HIP(hipGetLastError());
     return RTS_OK;
 }
