@@ -311,12 +311,10 @@ extern "C" int rts_link_handles(RtsHandle a, RtsHandle b)
 // beyond 256 bits would be refused HERE, when the scene or the receivers are set, not in the middle of a pulse loop.
 static int check_key_width(uint32_t depth, uint32_t n_targets, uint32_t n_rx, const char* who)
 {
-    uint32_t B = 1; while (((uint64_t)1 << B) < (uint64_t)n_targets + 1) B++;
-    uint32_t RXB = 1; while (((uint64_t)1 << RXB) < (uint64_t)std::max<uint32_t>(n_rx, 1)) RXB++;
-    if (depth == 0) B = 0;
-    if ((uint64_t)depth * B + RXB > 256) {            // (cannot happen within the other limits: 16 x 8 + 16 = 144 bits)
+    const RtsKeyPlan k = rts_key_plan_for(depth, n_targets, n_rx);
+    if (!k.supported) {                               // (cannot happen within the other limits: 16 x 8 + 16 = 144 bits)
         rts_set_error("%s: %u targets x depth %u (max_refl + max_refr) with %u receivers needs a %u-bit (receiver, path) aggregation key; the limit is 256 bits",
-                      who, n_targets, depth, n_rx, depth * B + RXB);
+                      who, n_targets, depth, n_rx, k.key_bits);
         return RTS_ERR_UNSUPPORTED;
     }
     return RTS_OK;
@@ -1274,7 +1272,7 @@ static int rts_spec_resolve(RtsContext* c)
         return rts_post_chain(c);
     }
     if (c->n_recv == 0) { c->agg_pending.valid = false; c->groups.clear(); c->agg_valid = true; return RTS_OK; }
-    c->agg_pending.R = (uint32_t)c->n_recv; c->agg_pending.spec = std::min<uint32_t>((uint32_t)c->n_recv, RTS_PIN_GROUPS);
+    c->agg_pending.R = (uint32_t)c->n_recv; c->agg_pending.spec = rts_agg_spec((uint32_t)c->n_recv);
     return RTS_OK;
 }
 
@@ -1292,34 +1290,37 @@ extern "C" int rts_trace_pulse_end_uniform(RtsHandle c, const double* rcs_per_ta
     return rts_trace_pulse_end_chain(c);
 }
 
+// Is the open pulse's chain (c->spec), of capacity `cap` rays (0: it has none), enqueued behind the trace at once, on the device-side
+// count?  When the handle's previous pulse received no more than 3/4 of the capacity.
+static bool rts_speculates(const RtsContext* c, uint32_t cap)
+{
+    const bool keep_all = (c->params.flags & RTS_FLAG_KEEP_ALL_RAYS) != 0;
+    return c->post_small && c->spec_enabled && cap > 0 && !keep_all && c->n_rays > 0 && c->recv_hint_valid && c->recv_hint <= ((uint64_t)cap * 3ull) / 4ull;
+}
+// ... and its enqueueing: the pulse is closed and awaits its resolution (rts_spec_resolve), the chain runs sized for the capacity
+// with the count itself from the device (the handle's own stream already waits for the trace: rts_trace_pulse_begin)
+static int rts_chain_on_device_count(RtsContext* c, uint32_t cap)
+{
+    c->spec_cap = cap;
+    c->pulse_open = false; c->spec_pending = true;                      // (the pulse stays counted as open on its device until it is resolved)
+    c->agg_timed = false; c->fin_timed = false;
+    c->n_recv = cap; c->recv_dev = c->p_counters;
+    const int rc = rts_post_chain(c);
+    c->recv_dev = nullptr; c->n_recv = 0;
+    if (rc != RTS_OK) { c->spec_pending = false; g_open_pulses[c->device & 63]--; }
+    return rc;
+}
+
 // the rest of rts_trace_pulse_end_uniform / _patterns, once c->spec holds the pulse's post-processing parameters
 static int rts_trace_pulse_end_chain(RtsContext* c)
 {
-    const bool keep_all = (c->params.flags & RTS_FLAG_KEEP_ALL_RAYS) != 0;
-    bool narrow_key = true;
-    {   // capacity of a speculative chain: the smaller of its two one-block sorts (row keys: 32 bits without refraction chains; (receiver, path) keys: D x B + RXB bits)
-        uint32_t B = 1; while (((uint64_t)1 << B) < (uint64_t)(c->scene->meshes.size() + 1)) B++;
-        uint32_t RXB = 1; while (((uint64_t)1 << RXB) < (uint64_t)std::max<uint32_t>(c->n_rx, 1u)) RXB++;
-        const uint32_t key_bits = (c->depth ? c->depth * B : 0u) + RXB;
-        c->spec_cap = (c->last_args.max_refr == 0 && key_bits < 32u) ? RTS_SMALL_CAP32 : RTS_SMALL_CAP64;
-        // a key beyond 64 bits (e.g. 16 bounces among >= 8 targets) is sorted as two or three words by the GENERAL chain, whose
-        // kernels take the received count from the host (rts_post.hip: only the one-block path reads it on the device): such a
-        // handle never speculates
-        narrow_key = key_bits <= 64u;
-    }
-    const bool speculate = c->post_small && c->spec_enabled && narrow_key && !keep_all && c->n_rays > 0 && c->recv_hint_valid && c->recv_hint <= ((uint64_t)c->spec_cap * 3ull) / 4ull;
-    if (!speculate) {
-        int rc = rts_trace_pulse_end(c); if (rc != RTS_OK) return rc;
-        return rts_post_chain(c, true);
-    }
-    c->pulse_open = false;                                              // (the pulse stays counted as open on its device until it is resolved)
-    c->spec_pending = true;
-    c->agg_timed = false; c->fin_timed = false;
-    c->n_recv = c->spec_cap; c->recv_dev = c->p_counters;              // sizes for the capacity, the count itself from the device
-    const int rc = rts_post_chain(c);                                   // (the handle's own stream already waits for the trace: rts_trace_pulse_begin)
-    c->recv_dev = nullptr; c->n_recv = 0;
-    if (rc != RTS_OK) { c->spec_pending = false; g_open_pulses[c->device & 63]--; return rc; }
-    return RTS_OK;
+    // the capacity of the chain: the smaller of its two one-block sorts -- none with a key beyond 64 bits (e.g. 16 bounces among >= 8
+    // targets), sorted as two or three words by the GENERAL chain, whose kernels take the received count from the host (rts_post.hip:
+    // only the one-block path reads it on the device): such a handle never speculates
+    const uint32_t cap = rts_spec_cap(c->last_args.max_refr, rts_handle_key_plan(c));
+    if (rts_speculates(c, cap)) return rts_chain_on_device_count(c, cap);
+    int rc = rts_trace_pulse_end(c); if (rc != RTS_OK) return rc;
+    return rts_post_chain(c, true);
 }
 
 // ------------------------------------------------------------------------------------- tabulated antenna gain and RCS patterns
@@ -1475,20 +1476,12 @@ extern "C" int rts_received_prefetch(RtsHandle c)
 {
     CHECK_HANDLE(c);
     if (!c->pulse_open) { rts_set_error("rts_received_prefetch: no pulse in flight on this handle"); return RTS_ERR_INVALID; }
-    const bool keep_all = (c->params.flags & RTS_FLAG_KEEP_ALL_RAYS) != 0;
-    const uint32_t cap = c->last_args.max_refr == 0 ? RTS_SMALL_CAP32 : RTS_SMALL_CAP64;
+    const uint32_t cap = rts_small_cap(rts_recv_key64(c->last_args.max_refr));      // (the chain's only sort: the received rows')
     { int rc = rts_mirror_reserve(c, cap); if (rc != RTS_OK) return rc; }
     c->mirror.want = true;
-    const bool speculate = c->post_small && c->spec_enabled && !keep_all && c->n_rays > 0 && c->recv_hint_valid && c->recv_hint <= ((uint64_t)cap * 3ull) / 4ull;
-    if (!speculate) return RTS_OK;
-    c->spec.mode = 1; c->spec_cap = cap;
-    c->pulse_open = false; c->spec_pending = true;                     // (the pulse stays counted as open on its device until it is resolved)
-    c->agg_timed = false; c->fin_timed = false;
-    c->n_recv = cap; c->recv_dev = c->p_counters;
-    const int rc = rts_post_chain(c);
-    c->recv_dev = nullptr; c->n_recv = 0;
-    if (rc != RTS_OK) { c->spec_pending = false; g_open_pulses[c->device & 63]--; return rc; }
-    return RTS_OK;
+    if (!rts_speculates(c, cap)) return RTS_OK;
+    c->spec.mode = 1;
+    return rts_chain_on_device_count(c, cap);
 }
 
 extern "C" int rts_received_view(RtsHandle c, const PerRayData** rays, const int32_t** paths, const double** rcs_angles, const uint64_t** slots, uint64_t* count)

@@ -12,6 +12,7 @@
 #include "rts_noise.h"
 #include "rts_owned.h"            // DevBuf, PinBuf: device and pinned host memory that frees itself
 #include "rts_launch_plan.h"      // RTS_BLOCK, RTS_WTILE, RTS_COOP_GROUP, RTS_STACK_OVF and the host arithmetic of a launch
+#include "rts_post_plan.h"        // RTS_SMALL_CAP32 / 64, RTS_AGG_TILE and the host arithmetic of the post-processing
 
 // ----------------------------------------------------------------------------- HBM layout
 // BVH4 node, 128 B = one cache line, of the static target-space hierarchy (rts_sah.cpp): half the dependent fetch
@@ -206,6 +207,7 @@ struct RtsMeshHost {
 // Pinned host staging (hipHostMalloc): every small per-pulse upload/readback goes through it, so the
 // stream never has to be drained just to recycle a pageable temporary.
 #define RTS_PIN_GROUPS 4096
+static inline uint32_t rts_agg_spec(uint32_t R) { return R < RTS_PIN_GROUPS ? R : RTS_PIN_GROUPS; }      // groups of the table of R rays that come home in the pinned block (the rest on demand: rts_aggregate_fetch)
 struct RtsPinned {
     // [lc | motion | td]: the per-pulse parameters, uploaded with ONE copy into RtsContext::d_params (same layout): the launch
     // constants alone when no target moved, else up to the last target's placement
@@ -250,8 +252,6 @@ struct RtsScene {
 // (RTS_SHARE_HISTORY=0: every handle its own.)
 struct RtsTileHist { std::atomic<int> refs{1}; DevBuf<uint32_t> d; uint32_t n = 0; bool any = false; uint32_t head_hint = 0; bool head_hint_valid = false; };
 
-#define RTS_SMALL_CAP32 4096u         // received rays the one-block ordering kernels take with 32-bit sort keys (rts_post.hip) ...
-#define RTS_SMALL_CAP64 2048u         // ... and with 64-bit keys; a speculatively enqueued post-processing chain is sized for the smaller of its two sorts
 struct RtsSpecParams { std::vector<double> rcs; double wl = 0, gt = 0, gr = 0, carrier = 0, cspeed = 0; int32_t cube_pulse = -1; uint64_t base = 0;
                        int mode = 0;        // 0: the uniform chain (rts_trace_pulse_end_uniform); 1: order + expand + the received set to the host mirror (rts_received_prefetch)
                        int fin = 0;         // mode 0's finaliser: 0 uniform (rcs / gt / gr), 1 the handle's tabulated patterns (rts_trace_pulse_end_patterns) with:
@@ -271,7 +271,7 @@ struct RtsHostMirror {
     bool want = false;                               // this pulse's post-processing feeds the mirror (set by rts_received_prefetch, cleared by the next rts_trace_pulse_begin)
 };
 // rts_aggregate enqueues; the table is read (stream wait + pinned block -> RtsGroup records) by the first call that needs it
-struct RtsAggPending { bool valid = false, wide = false, rows = false; uint32_t R = 0, D = 0, B = 0, shift = 0, spec = 0; uint64_t base = 0; double* gsum = nullptr; };
+struct RtsAggPending { bool valid = false, rows = false; uint32_t R = 0, D = 0, spec = 0; RtsKeyPlan key = {}; uint64_t base = 0; double* gsum = nullptr; };
 
 struct RtsContext {
     RtsParams params;
@@ -382,6 +382,9 @@ struct RtsContext {
     // DevBuf / PinBuf members free themselves after it.  The caller makes the handle's device current first.
     ~RtsContext();
 };
+// the (receiver, path) aggregation key of depth D among n_targets targets and n_rx receivers, and of the handle's own received sets
+static inline RtsKeyPlan rts_key_plan_for(uint32_t D, uint32_t n_targets, uint32_t n_rx) { return rts_key_plan(D, (int64_t)n_targets - 1, (int64_t)(n_rx ? n_rx : 1u) - 1); }
+static inline RtsKeyPlan rts_handle_key_plan(const RtsContext* c) { return rts_key_plan_for(c->depth, (uint32_t)c->scene->meshes.size(), c->n_rx); }
 void rts_scene_unref(RtsScene* s);          // drop one reference; the last one deletes the object (and with it its buffers)
 void rts_hist_unref(RtsTileHist* h);
 void rts_gate_unref(RtsGate* g);            // ... and destroys the group's trace stream

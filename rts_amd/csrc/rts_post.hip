@@ -11,11 +11,10 @@
 #include "rts_raygen.h"
 
 static inline unsigned blocks_for(size_t n, unsigned bs) { return (unsigned)((n + bs - 1) / bs); }
-static inline uint32_t rts_small_cap_recv(const RtsContext* c) { return c->last_args.max_refr == 0 ? RTS_SMALL_CAP32 : RTS_SMALL_CAP64; }
 // received sets up to this size: single-block ordering / finishing kernels (see k_agg_order_small) -- 4 096 rays when the sort
-// keys fit 32 bits (no refraction chains in the row key; a (receiver, path) key of <= 31 bits), 2 048 with 64-bit keys: the
-// block's sort storage has to stay below the 40 KB of a free block slot
-#define RTS_SMALL_THREADS 256
+// keys fit 32 bits (no refraction chains in the row key; a (receiver, path) key of <= 31 bits), 2 048 with 64-bit keys
+// (rts_post_plan.h: rts_small_cap, rts_small_items)
+static inline uint32_t rts_small_cap_recv(const RtsContext* c) { return rts_small_cap(rts_recv_key64(c->last_args.max_refr)); }
 static_assert(RTS_SMALL_CAP32 == 16 * RTS_SMALL_THREADS && RTS_SMALL_CAP64 == 8 * RTS_SMALL_THREADS, "items per thread of the one-block sorts");
 template <typename K, int ITEMS> __global__ void k_recv_order_small(const RtsEndRecord* __restrict__ rec, uint32_t n, uint32_t n_rays, int with_chain, uint32_t bits, uint32_t* __restrict__ perm, const unsigned long long* __restrict__ R_dev);
 
@@ -441,27 +440,28 @@ int rts_tile_order_build(RtsContext* c, const uint64_t* prev_sig, bool prev_vali
     return RTS_OK;
 }
 
+// the ordered, expanded received set of R rays: what rts_post_order_and_expand and k_post_all write
+static int rts_recv_reserve(RtsContext* c, uint32_t R)
+{
+    const uint32_t D = c->depth;
+    RTS_HIP(c->d_ri.reserve(R)); RTS_HIP(c->d_ri_sorted.reserve(R));
+    RTS_HIP(c->d_rx_rays.reserve(R)); RTS_HIP(c->d_rx_paths.reserve((size_t)R*D + 1)); RTS_HIP(c->d_rx_angles.reserve((size_t)R*D*2 + 1)); RTS_HIP(c->d_rx_slots.reserve(R));
+    return RTS_OK;
+}
+
 int rts_post_order_and_expand(RtsContext* c)
 {
     const uint32_t R = (uint32_t)c->n_recv, D = c->depth;
     if (R == 0) return RTS_OK;
     hipStream_t st = c->stream;
-    RTS_HIP(c->d_ri.reserve(R)); RTS_HIP(c->d_ri_sorted.reserve(R));
-    RTS_HIP(c->d_rx_rays.reserve(R)); RTS_HIP(c->d_rx_paths.reserve((size_t)R*D + 1)); RTS_HIP(c->d_rx_angles.reserve((size_t)R*D*2 + 1)); RTS_HIP(c->d_rx_slots.reserve(R));
+    { int rc = rts_recv_reserve(c, R); if (rc != RTS_OK) return rc; }
     size_t tmp = 0;
     if (c->post_small && R <= rts_small_cap_recv(c)) {
-        // items per thread by the size of the set (a speculative chain -- count on the device -- is sized for the capacity); sort bits by the largest row
-        const uint32_t cap = c->recv_dev ? rts_small_cap_recv(c) : R;
-        const uint64_t rows = (uint64_t)c->n_rays * rts_chains(c->last_args.max_refr);
-        uint32_t bits = 1; while (bits < 40 && ((uint64_t)1 << bits) <= rows) bits++;       // (the padding key, 2^bits - 1, stays above every row)
-        if (c->last_args.max_refr == 0) {
-            if (cap <= 4u * RTS_SMALL_THREADS) k_recv_order_small<uint32_t, 4><<<1, RTS_SMALL_THREADS, 0, st>>>(c->d_recv.p, R, c->n_rays, 0, bits, c->d_ri_sorted.p, c->recv_dev);
-            else if (cap <= 8u * RTS_SMALL_THREADS) k_recv_order_small<uint32_t, 8><<<1, RTS_SMALL_THREADS, 0, st>>>(c->d_recv.p, R, c->n_rays, 0, bits, c->d_ri_sorted.p, c->recv_dev);
-            else k_recv_order_small<uint32_t, 16><<<1, RTS_SMALL_THREADS, 0, st>>>(c->d_recv.p, R, c->n_rays, 0, bits, c->d_ri_sorted.p, c->recv_dev);
-        } else {
-            if (cap <= 4u * RTS_SMALL_THREADS) k_recv_order_small<uint64_t, 4><<<1, RTS_SMALL_THREADS, 0, st>>>(c->d_recv.p, R, c->n_rays, 1, bits, c->d_ri_sorted.p, c->recv_dev);
-            else k_recv_order_small<uint64_t, 8><<<1, RTS_SMALL_THREADS, 0, st>>>(c->d_recv.p, R, c->n_rays, 1, bits, c->d_ri_sorted.p, c->recv_dev);
-        }
+        // items per thread by the size of the set (a speculative chain -- count on the device -- is sized for the capacity)
+        const uint32_t cap = c->recv_dev ? rts_small_cap_recv(c) : R, items = rts_small_items(cap), bits = rts_recv_sort_bits(c->n_rays, c->last_args.max_refr);
+        auto order = [&](auto kernel, int with_chain) { kernel<<<1, RTS_SMALL_THREADS, 0, st>>>(c->d_recv.p, R, c->n_rays, with_chain, bits, c->d_ri_sorted.p, c->recv_dev); };
+        if (!rts_recv_key64(c->last_args.max_refr)) { if (items == 4) order(k_recv_order_small<uint32_t, 4>, 0); else if (items == 8) order(k_recv_order_small<uint32_t, 8>, 0); else order(k_recv_order_small<uint32_t, 16>, 0); }
+        else { if (items == 4) order(k_recv_order_small<uint64_t, 4>, 1); else order(k_recv_order_small<uint64_t, 8>, 1); }
         RTS_STAGE(c, "recv order (one block)");
     } else if (c->last_args.max_refr == 0) {
         RTS_HIP(c->d_rk.reserve(R)); RTS_HIP(c->d_rk_sorted.reserve(R));
@@ -609,12 +609,12 @@ __global__ void k_finalise(PerRayData* __restrict__ rays, const int32_t* __restr
     finalise_row(rays, paths, i, D, rcs, n_targets, wl, gt, gr, carrier, cspeed);
 }
 
-int rts_post_finalise(RtsContext* c, const double* rcs_host, double wl, double gt, double gr, double carrier, double cspeed)
+// the per-target RCS values of the uniform finaliser on the device: uploaded if they changed (rcs_host == nullptr: the buffer alone)
+static int rts_rcs_upload(RtsContext* c, const double* rcs_host)
 {
-    const uint32_t R = (uint32_t)c->n_recv;
-    if (R == 0) return RTS_OK;
     const uint32_t nt = (uint32_t)c->scene->meshes.size();
     RTS_HIP(c->d_rcsval.reserve(nt + 1));
+    if (!rcs_host) return RTS_OK;
     bool changed = !c->rcs_uploaded;
     for (uint32_t t = 0; t < nt && t < 256; t++) changed = changed || memcmp(&c->pin.p->rcs[t], &rcs_host[t], sizeof(double)) != 0;
     if (changed) {                                                            // (the same values pulse after pulse: uploaded once)
@@ -623,6 +623,15 @@ int rts_post_finalise(RtsContext* c, const double* rcs_host, double wl, double g
         if (nt) RTS_HIP(hipMemcpyAsync(c->d_rcsval.p, c->pin.p->rcs, sizeof(double)*nt, hipMemcpyHostToDevice, c->stream));
         c->rcs_uploaded = true;
     }
+    return RTS_OK;
+}
+
+int rts_post_finalise(RtsContext* c, const double* rcs_host, double wl, double gt, double gr, double carrier, double cspeed)
+{
+    const uint32_t R = (uint32_t)c->n_recv;
+    if (R == 0) return RTS_OK;
+    const uint32_t nt = (uint32_t)c->scene->meshes.size();
+    { int rc = rts_rcs_upload(c, rcs_host); if (rc != RTS_OK) return rc; }
     k_finalise<<<blocks_for(R, 256), 256, 0, c->stream>>>(c->d_rx_rays.p, c->d_rx_paths.p, R, c->depth, c->d_rcsval.p, nt, wl, gt, gr, carrier, cspeed, c->recv_dev);
     RTS_HIP(hipGetLastError());
     return RTS_OK;
@@ -899,7 +908,7 @@ __global__ void k_agg_starts(const uint32_t* __restrict__ head, const uint32_t* 
     if (i == R - 1) gstart[gid_incl[i]] = R;
 }
 
-#define AGG_TILE 256
+#define AGG_TILE RTS_AGG_TILE
 // Per-ray contributions (aggregation.cu:59-65) summed per group with a FIXED reduction shape
 // (segmented Hillis-Steele scan inside 256-element tiles, then tile partials in tile order), so
 // the f64 sums are reproducible run to run.  vals: 5 doubles {n, sqrt(power), delay, phase, doppler}.
@@ -1288,6 +1297,55 @@ __global__ void __launch_bounds__(RTS_SMALL_THREADS) k_post_all(const RtsPostAll
     agg_finish_block(q.fin, R, ntiles, min(q.fin.spec, R));
 }
 
+// ---- the host side of the aggregation, shared by k_post_all's launch and rts_aggregate_device (its arithmetic: rts_post_plan.h)
+// The aggregation's scratch for R rays, reserved and sliced as rts_agg_layout says (the wide path's d_gpath and the sorts' d_sort_tmp
+// stay with their users).  use_rows: the groups' global buffer rows are wanted too.
+struct RtsAggScratch { uint32_t ntiles; uint32_t* gstart; uint32_t* d_G; double* gsum; double* tile_first; double* tile_last; double* rxtot; uint32_t* rxmin; };
+static int rts_agg_scratch(RtsContext* c, const RtsKeyPlan& k, uint32_t R, bool use_rows, RtsAggScratch* s)
+{
+    const RtsAggLayout l = rts_agg_layout(R, k.n_rx_tab);
+    RTS_HIP(c->d_akeys.reserve(l.per_ray)); RTS_HIP(c->d_akeys_sorted.reserve(l.per_ray)); RTS_HIP(c->d_aidx.reserve(l.per_ray)); RTS_HIP(c->d_aidx_sorted.reserve(l.per_ray));
+    RTS_HIP(c->d_ghead.reserve(l.per_ray)); RTS_HIP(c->d_gid.reserve(l.per_ray));
+    RTS_HIP(c->d_gcount.reserve(l.gcount)); RTS_HIP(c->d_gsum.reserve(l.gsum));
+    RTS_HIP(c->d_gmin.reserve(l.per_ray)); RTS_HIP(c->d_gkey.reserve(l.per_ray)); if (use_rows) RTS_HIP(c->d_grow.reserve(l.per_ray));
+    RTS_HIP(c->d_rcs.reserve(l.rcs));
+    s->ntiles = l.ntiles;
+    s->gstart = c->d_gcount.p; s->d_G = c->d_gcount.p + l.o_G;
+    s->gsum = c->d_gsum.p; s->tile_first = c->d_gsum.p + l.o_tile_first; s->tile_last = c->d_gsum.p + l.o_tile_last;
+    s->rxtot = c->d_rcs.p; s->rxmin = (uint32_t*)(c->d_rcs.p + l.o_rxmin);
+    return RTS_OK;
+}
+// What agg_finish_block reads and writes for R rays `rays` (rows: their global buffer rows, or null): the handle's sorted order,
+// scratch and group table; pathMatch counted from `base`; the first groups exported to the pinned block, with their count if
+// want_groups.  As built, the rays' sums start at zero and the outputs are the handle's delay / phase / pathMatch arrays
+// (rts_aggregate_device puts its caller's in-out arrays in their place).
+static RtsAggFinish rts_agg_finish_args(RtsContext* c, const RtsKeyPlan& k, const RtsAggScratch& s, uint32_t R, PerRayData* rays, const uint64_t* rows, uint64_t base, bool want_groups)
+{
+    RtsPinned* pd = c->pin.dev;
+    RtsAggFinish q = {};
+    q.rays = rays; q.idx_sorted = c->d_aidx_sorted.p; q.keys_sorted = c->d_akeys_sorted.p; q.gid_incl = c->d_gid.p;
+    q.gstart = s.gstart; q.tile_first = s.tile_first; q.tile_last = s.tile_last; q.gsum = s.gsum; q.d_G = s.d_G; q.rxtot = s.rxtot; q.rxmin = s.rxmin;
+    q.gmin = c->d_gmin.p; q.gkey = c->d_gkey.p;
+    q.rows = rows; q.grow = rows ? c->d_grow.p : nullptr;
+    q.shift = k.shift; q.n_rx_tab = k.n_rx_tab; q.base = (int64_t)base;
+    q.delay = c->d_delay.p; q.phase = c->d_phase.p; q.pm = c->d_pathmatch.p; q.pm_init_const = INT32_MAX; q.use_pm_in = 0; q.dly_in = 0;
+    q.spec = rts_agg_spec(R); q.h_G = want_groups ? &pd->G : nullptr; q.h_gsum = pd->gsum; q.h_gmin = pd->gmin; q.h_gkey = pd->gkey; q.h_grow = pd->grow;
+    return q;
+}
+// the group table of R rays is on its way to the pinned block: rts_aggregate_fetch reads it
+static void rts_agg_pending_set(RtsContext* c, const RtsKeyPlan& k, uint32_t R, uint32_t D, uint64_t base, bool rows, double* gsum)
+{
+    RtsAggPending& ap = c->agg_pending; ap.valid = true; ap.R = R; ap.D = D; ap.key = k; ap.base = base; ap.rows = rows; ap.spec = rts_agg_spec(R); ap.gsum = gsum;
+}
+// k_post_all for the sorts' key types, with finaliser f
+template <typename FIN> static void rts_post_all_launch(hipStream_t st, const RtsPostAll& q, bool kr64, bool ka64, const FIN& f)
+{
+    if (!kr64 && !ka64) k_post_all<uint32_t, uint32_t><<<1, RTS_SMALL_THREADS, 0, st>>>(q, f);
+    else if (!kr64) k_post_all<uint32_t, uint64_t><<<1, RTS_SMALL_THREADS, 0, st>>>(q, f);
+    else if (!ka64) k_post_all<uint64_t, uint32_t><<<1, RTS_SMALL_THREADS, 0, st>>>(q, f);
+    else k_post_all<uint64_t, uint64_t><<<1, RTS_SMALL_THREADS, 0, st>>>(q, f);
+}
+
 // Enqueues k_post_all for the pulse whose trace is in flight or over: buffers sized for `cap` rays, the count from the device.
 // The caller has checked: no KEEP_ALL, a (receiver, path) key of <= 64 bits, cap within the one-block sorts.
 int rts_post_all_small(RtsContext* c, uint32_t cap, const RtsSpecParams& sp, bool want_groups)
@@ -1295,69 +1353,34 @@ int rts_post_all_small(RtsContext* c, uint32_t cap, const RtsSpecParams& sp, boo
     const uint32_t D = c->depth; hipStream_t st = c->stream;
     const uint32_t nt = (uint32_t)c->scene->meshes.size();
     // ---- what rts_post_order_and_expand, rts_post_finalise and rts_aggregate_device reserve, for cap rays
-    RTS_HIP(c->d_ri.reserve(cap)); RTS_HIP(c->d_ri_sorted.reserve(cap));
-    RTS_HIP(c->d_rx_rays.reserve(cap)); RTS_HIP(c->d_rx_paths.reserve((size_t)cap*D + 1)); RTS_HIP(c->d_rx_angles.reserve((size_t)cap*D*2 + 1)); RTS_HIP(c->d_rx_slots.reserve(cap));
-    RTS_HIP(c->d_rcsval.reserve(nt + 1));
-    bool changed = sp.fin == 0 && !c->rcs_uploaded;                     // (the pattern finaliser reads no per-target constants)
-    for (uint32_t t = 0; sp.fin == 0 && t < nt && t < 256; t++) changed = changed || memcmp(&c->pin.p->rcs[t], &sp.rcs[t], sizeof(double)) != 0;
-    if (changed) {
-        RTS_HIP(hipStreamSynchronize(st));
-        for (uint32_t t = 0; t < nt && t < 256; t++) c->pin.p->rcs[t] = sp.rcs[t];
-        if (nt) RTS_HIP(hipMemcpyAsync(c->d_rcsval.p, c->pin.p->rcs, sizeof(double)*nt, hipMemcpyHostToDevice, st));
-        c->rcs_uploaded = true;
-    }
-    const int32_t max_path = (int32_t)nt - 1, max_rx = c->n_rx ? (int32_t)c->n_rx - 1 : 0;
-    uint32_t B = 1; while (((uint64_t)1 << B) < (uint64_t)(max_path + 2)) B++;
-    uint32_t RXB = 1; while (((uint64_t)1 << RXB) < (uint64_t)(max_rx + 1)) RXB++;
-    if (D == 0) B = 0;
-    const uint32_t key_bits = D * B + RXB, shift = D * B, n_rx_tab = (uint32_t)max_rx + 1, ntiles = blocks_for(cap, AGG_TILE);
-    const size_t R = cap;
-    RTS_HIP(c->d_delay.reserve(R)); RTS_HIP(c->d_phase.reserve(R)); RTS_HIP(c->d_pathmatch.reserve(R));
-    RTS_HIP(c->d_akeys.reserve(R)); RTS_HIP(c->d_akeys_sorted.reserve(R)); RTS_HIP(c->d_aidx.reserve(R)); RTS_HIP(c->d_aidx_sorted.reserve(R));
-    RTS_HIP(c->d_ghead.reserve(R)); RTS_HIP(c->d_gid.reserve(R));
-    RTS_HIP(c->d_gcount.reserve(R + 4)); RTS_HIP(c->d_gsum.reserve(5*(R + 2*(size_t)ntiles) + 16));
-    RTS_HIP(c->d_gmin.reserve(R)); RTS_HIP(c->d_gkey.reserve(R));
+    int rc = rts_recv_reserve(c, cap); if (rc != RTS_OK) return rc;
+    rc = rts_rcs_upload(c, sp.fin == 0 ? sp.rcs.data() : nullptr); if (rc != RTS_OK) return rc;      // (the pattern finaliser reads no per-target constants)
+    const RtsKeyPlan k = rts_handle_key_plan(c);
+    RTS_HIP(c->d_delay.reserve(cap)); RTS_HIP(c->d_phase.reserve(cap)); RTS_HIP(c->d_pathmatch.reserve(cap));
     const bool use_rows = sp.base == RTS_BASE_USE_ROWS;
-    if (use_rows) RTS_HIP(c->d_grow.reserve(R));
-    RTS_HIP(c->d_rcs.reserve(5*(size_t)n_rx_tab + n_rx_tab + 8));
-    uint32_t* gstart = c->d_gcount.p; uint32_t* d_G = c->d_gcount.p + R + 2;
-    double* gsum = c->d_gsum.p; double* tile_first = gsum + 5*R; double* tile_last = tile_first + 5*(size_t)ntiles;
-    double* d_rxtot = c->d_rcs.p; uint32_t* d_rxmin = (uint32_t*)(c->d_rcs.p + 5*(size_t)n_rx_tab);
-    RtsPinned* pd = c->pin.dev;
+    RtsAggScratch s;
+    rc = rts_agg_scratch(c, k, cap, use_rows, &s); if (rc != RTS_OK) return rc;
     const uint64_t base = use_rows ? 0 : sp.base;
     RtsPostAll q; memset(&q, 0, sizeof(q));
     q.ta = c->last_args; q.rec = c->d_recv.p; q.cap = cap; q.n_rays = c->n_rays; q.with_chain = c->last_args.max_refr != 0 ? 1 : 0;
-    { const uint64_t rows = (uint64_t)c->n_rays * rts_chains(c->last_args.max_refr); uint32_t bits = 1; while (bits < 40 && ((uint64_t)1 << bits) <= rows) bits++; q.bits = bits; }
+    q.bits = rts_recv_sort_bits(c->n_rays, c->last_args.max_refr);
     q.perm = c->d_ri_sorted.p; q.D = D; q.rays = c->d_rx_rays.p; q.paths = c->d_rx_paths.p; q.angles = c->d_rx_angles.p; q.slots = c->d_rx_slots.p;
     q.rcs = c->d_rcsval.p; q.n_targets = nt; q.wl = sp.wl; q.gt = sp.gt; q.gr = sp.gr; q.carrier = sp.carrier; q.cspeed = sp.cspeed;
     q.cube_on = sp.cube_pulse >= 0 ? 1 : 0;
     if (q.cube_on) { const RtsCubeParams& cp = c->cube_params; q.cube = c->cube; q.cube_rx = cp.n_rx; q.cube_pulses = cp.n_pulses; q.cube_bins = cp.n_bins; q.cube_pulse = (uint32_t)sp.cube_pulse; q.cube_t0 = cp.t0; q.cube_dt = cp.dt; }
-    q.B = B; q.key_bits = key_bits; q.ahead = c->d_ghead.p;
-    const uint32_t spec_s = std::min<uint32_t>(cap, RTS_PIN_GROUPS);
-    q.fin = RtsAggFinish{c->d_rx_rays.p, c->d_aidx_sorted.p, c->d_akeys_sorted.p, c->d_gid.p, gstart, tile_first, tile_last, gsum, c->d_gmin.p, c->d_gkey.p, d_G,
-                         use_rows ? c->d_rx_slots.p : nullptr, use_rows ? c->d_grow.p : nullptr, shift, n_rx_tab, d_rxtot, d_rxmin, (int64_t)base, nullptr, nullptr, nullptr,
-                         c->d_delay.p, c->d_phase.p, c->d_pathmatch.p, INT32_MAX, 0, 0,
-                         spec_s, want_groups ? &pd->G : nullptr, pd->gsum, pd->gmin, pd->gkey, pd->grow};
+    q.B = k.B; q.key_bits = k.key_bits; q.ahead = c->d_ghead.p;
+    q.fin = rts_agg_finish_args(c, k, s, cap, c->d_rx_rays.p, use_rows ? c->d_rx_slots.p : nullptr, base, want_groups);
     q.R_dev = c->p_counters; q.prio = c->post_prio;
-    const bool kr64 = c->last_args.max_refr != 0, ka64 = key_bits >= 32u;
-    if (sp.fin == 0) {
-        const RtsFinUniform f{};
-        if (!kr64 && !ka64) k_post_all<uint32_t, uint32_t><<<1, RTS_SMALL_THREADS, 0, st>>>(q, f);
-        else if (!kr64) k_post_all<uint32_t, uint64_t><<<1, RTS_SMALL_THREADS, 0, st>>>(q, f);
-        else if (!ka64) k_post_all<uint64_t, uint32_t><<<1, RTS_SMALL_THREADS, 0, st>>>(q, f);
-        else k_post_all<uint64_t, uint64_t><<<1, RTS_SMALL_THREADS, 0, st>>>(q, f);
-    } else {
+    const bool kr64 = rts_recv_key64(c->last_args.max_refr), ka64 = rts_agg_key64(k);
+    if (sp.fin == 0) rts_post_all_launch(st, q, kr64, ka64, RtsFinUniform{});
+    else {
         RtsFinPatterns f;
-        int rc = rts_pattern_pulse_upload(c, sp, &f.a); if (rc != RTS_OK) return rc;
-        if (!kr64 && !ka64) k_post_all<uint32_t, uint32_t><<<1, RTS_SMALL_THREADS, 0, st>>>(q, f);
-        else if (!kr64) k_post_all<uint32_t, uint64_t><<<1, RTS_SMALL_THREADS, 0, st>>>(q, f);
-        else if (!ka64) k_post_all<uint64_t, uint32_t><<<1, RTS_SMALL_THREADS, 0, st>>>(q, f);
-        else k_post_all<uint64_t, uint64_t><<<1, RTS_SMALL_THREADS, 0, st>>>(q, f);
+        rc = rts_pattern_pulse_upload(c, sp, &f.a); if (rc != RTS_OK) return rc;
+        rts_post_all_launch(st, q, kr64, ka64, f);
     }
     RTS_HIP(hipGetLastError());
     c->recv_index_base = sp.base; c->agg_base_local = use_rows ? 0 : (int64_t)sp.base;
-    RtsAggPending& ap = c->agg_pending;
-    ap.valid = true; ap.R = cap; ap.D = D; ap.B = B; ap.shift = shift; ap.wide = false; ap.base = base; ap.rows = use_rows; ap.spec = spec_s; ap.gsum = gsum;
+    rts_agg_pending_set(c, k, cap, D, base, use_rows, s.gsum);
     return RTS_OK;
 }
 
@@ -1376,53 +1399,39 @@ int rts_aggregate_device(RtsContext* c, int32_t max_path, int32_t max_rx, const 
     if (R64 > 0x7fffffffULL) { rts_set_error("aggregate: more than 2^31 received rays"); return RTS_ERR_UNSUPPORTED; }
     const uint32_t R = (uint32_t)R64;
     hipStream_t st = c->stream;
-    uint32_t B = 1; while (((uint64_t)1 << B) < (uint64_t)(max_path + 2)) B++;
-    uint32_t RXB = 1; while (((uint64_t)1 << RXB) < (uint64_t)(max_rx + 1)) RXB++;
-    if (D == 0) B = 0;
-    if (D > RTS_MAX_DEPTH || (uint64_t)D * B + RXB > 256) {
-        rts_set_error("aggregate: depth %u > %d or a (receiver, path) key of %u x %u + %u bits > 256", D, RTS_MAX_DEPTH, D, B, RXB);
+    const RtsKeyPlan k = rts_key_plan(D, max_path, max_rx);
+    if (!k.supported) {
+        rts_set_error("aggregate: depth %u > %d or a (receiver, path) key of %u x %u + %u bits > 256", D, RTS_MAX_DEPTH, D, k.B, k.RXB);
         return RTS_ERR_UNSUPPORTED;
     }
-    const uint32_t key_bits = D * B + RXB;
-    const bool wide = key_bits > 64;                  // multi-word key: least-significant-word-first passes of the stable sort
-    const uint32_t shift = wide ? 32u : D * B;        // where the receiver sits in the 64-bit (surrogate) key of the sorted order
-    const uint32_t n_rx_tab = (uint32_t)max_rx + 1;
-    const uint32_t ntiles = blocks_for(R, AGG_TILE);
-    RTS_HIP(c->d_akeys.reserve(R)); RTS_HIP(c->d_akeys_sorted.reserve(R)); RTS_HIP(c->d_aidx.reserve(R)); RTS_HIP(c->d_aidx_sorted.reserve(R));
-    RTS_HIP(c->d_ghead.reserve(R)); RTS_HIP(c->d_gid.reserve(R));
-    RTS_HIP(c->d_gcount.reserve((size_t)R + 4)); RTS_HIP(c->d_gsum.reserve(5*((size_t)R + 2*(size_t)ntiles) + 16));
-    RTS_HIP(c->d_gmin.reserve(R)); RTS_HIP(c->d_gkey.reserve(R)); if (d_rows) RTS_HIP(c->d_grow.reserve(R));
-    RTS_HIP(c->d_rcs.reserve(5*(size_t)n_rx_tab + n_rx_tab + 8));
-    uint32_t* gstart = c->d_gcount.p;                 // [<= R + 1]
-    uint32_t* d_G = c->d_gcount.p + (size_t)R + 2;    // group count, device resident
-    double* gsum = c->d_gsum.p; double* tile_first = gsum + 5*(size_t)R; double* tile_last = tile_first + 5*(size_t)ntiles;
-    double* d_rxtot = c->d_rcs.p; uint32_t* d_rxmin = (uint32_t*)(c->d_rcs.p + 5*(size_t)n_rx_tab);
+    RtsAggScratch s;
+    { int rc = rts_agg_scratch(c, k, R, d_rows != nullptr, &s); if (rc != RTS_OK) return rc; }
     size_t tmp = 0;
-    const bool small = c->post_small && !wide && R <= (key_bits < 32u ? RTS_SMALL_CAP32 : RTS_SMALL_CAP64);       // one block orders, one block finishes (see k_agg_order_small)
+    const uint32_t small_cap = rts_small_cap(rts_agg_key64(k));
+    const bool small = c->post_small && !k.wide && R <= small_cap;       // one block orders, one block finishes (see k_agg_order_small)
     if (small) {
-        const uint32_t cap = c->recv_dev ? (key_bits < 32u ? RTS_SMALL_CAP32 : RTS_SMALL_CAP64) : R;
-#define RTS_AGG_ORDER(K, I) k_agg_order_small<K, I><<<1, RTS_SMALL_THREADS, 0, st>>>(d_rays, d_paths, R, D, B, key_bits, c->d_akeys_sorted.p, c->d_aidx_sorted.p, c->d_ghead.p, c->d_gid.p, gstart, c->recv_dev)
-        if (key_bits < 32u) { if (cap <= 4u * RTS_SMALL_THREADS) RTS_AGG_ORDER(uint32_t, 4); else if (cap <= 8u * RTS_SMALL_THREADS) RTS_AGG_ORDER(uint32_t, 8); else RTS_AGG_ORDER(uint32_t, 16); }
-        else { if (cap <= 4u * RTS_SMALL_THREADS) RTS_AGG_ORDER(uint64_t, 4); else RTS_AGG_ORDER(uint64_t, 8); }
-#undef RTS_AGG_ORDER
-    } else if (!wide) {
-        k_agg_keys<<<blocks_for(R, 256), 256, 0, st>>>(d_rays, d_paths, R, D, B, c->d_akeys.p, c->d_aidx.p);
-        RTS_HIP(rocprim::radix_sort_pairs(nullptr, tmp, c->d_akeys.p, c->d_akeys_sorted.p, c->d_aidx.p, c->d_aidx_sorted.p, R, 0, key_bits, st));
+        const uint32_t cap = c->recv_dev ? small_cap : R;             // (a chain enqueued on the device-side count is sized for the capacity)
+        auto order = [&](auto kernel) { kernel<<<1, RTS_SMALL_THREADS, 0, st>>>(d_rays, d_paths, R, D, k.B, k.key_bits, c->d_akeys_sorted.p, c->d_aidx_sorted.p, c->d_ghead.p, c->d_gid.p, s.gstart, c->recv_dev); };
+        const uint32_t items = rts_small_items(cap);
+        if (!rts_agg_key64(k)) { if (items == 4) order(k_agg_order_small<uint32_t, 4>); else if (items == 8) order(k_agg_order_small<uint32_t, 8>); else order(k_agg_order_small<uint32_t, 16>); }
+        else { if (items == 4) order(k_agg_order_small<uint64_t, 4>); else order(k_agg_order_small<uint64_t, 8>); }
+    } else if (!k.wide) {
+        k_agg_keys<<<blocks_for(R, 256), 256, 0, st>>>(d_rays, d_paths, R, D, k.B, c->d_akeys.p, c->d_aidx.p);
+        RTS_HIP(rocprim::radix_sort_pairs(nullptr, tmp, c->d_akeys.p, c->d_akeys_sorted.p, c->d_aidx.p, c->d_aidx_sorted.p, R, 0, k.key_bits, st));
         RTS_HIP(c->d_sort_tmp.reserve(tmp));
-        RTS_HIP(rocprim::radix_sort_pairs(c->d_sort_tmp.p, tmp, c->d_akeys.p, c->d_akeys_sorted.p, c->d_aidx.p, c->d_aidx_sorted.p, R, 0, key_bits, st));
+        RTS_HIP(rocprim::radix_sort_pairs(c->d_sort_tmp.p, tmp, c->d_akeys.p, c->d_akeys_sorted.p, c->d_aidx.p, c->d_aidx_sorted.p, R, 0, k.key_bits, st));
         k_agg_heads<<<blocks_for(R, 256), 256, 0, st>>>(c->d_akeys_sorted.p, c->d_ghead.p, R);
     } else {
-        const uint32_t n_words = (key_bits + 63u) / 64u;
         RTS_HIP(rocprim::radix_sort_pairs(nullptr, tmp, c->d_akeys.p, c->d_akeys_sorted.p, c->d_aidx.p, c->d_aidx_sorted.p, R, 0, 64, st));
         RTS_HIP(c->d_sort_tmp.reserve(tmp));
         RTS_HIP(c->d_gid.reserve(R));                  // (free until the scan: the order handed from one pass to the next)
-        for (uint32_t w = 0; w < n_words; w++) {
+        for (uint32_t w = 0; w < k.n_words; w++) {
             // keys of word w in the order left by the passes so far (pass 0: ray order), then a stable sort by that word
-            k_agg_keys_wide<<<blocks_for(R, 256), 256, 0, st>>>(d_rays, d_paths, w == 0 ? nullptr : c->d_gid.p, R, D, B, w, c->d_akeys.p, c->d_aidx.p);
-            const uint32_t bits = std::min(64u, key_bits - 64u * w);
+            k_agg_keys_wide<<<blocks_for(R, 256), 256, 0, st>>>(d_rays, d_paths, w == 0 ? nullptr : c->d_gid.p, R, D, k.B, w, c->d_akeys.p, c->d_aidx.p);
+            const uint32_t bits = std::min(64u, k.key_bits - 64u * w);
             size_t t2 = tmp;
             RTS_HIP(rocprim::radix_sort_pairs(c->d_sort_tmp.p, t2, c->d_akeys.p, c->d_akeys_sorted.p, c->d_aidx.p, c->d_aidx_sorted.p, R, 0, bits, st));
-            if (w + 1 < n_words) RTS_HIP(hipMemcpyAsync(c->d_gid.p, c->d_aidx_sorted.p, sizeof(uint32_t) * R, hipMemcpyDeviceToDevice, st));
+            if (w + 1 < k.n_words) RTS_HIP(hipMemcpyAsync(c->d_gid.p, c->d_aidx_sorted.p, sizeof(uint32_t) * R, hipMemcpyDeviceToDevice, st));
         }
         k_agg_heads_wide<<<blocks_for(R, 256), 256, 0, st>>>(d_rays, d_paths, c->d_aidx_sorted.p, R, D, c->d_ghead.p, c->d_akeys_sorted.p);
     }
@@ -1430,46 +1439,41 @@ int rts_aggregate_device(RtsContext* c, int32_t max_path, int32_t max_rx, const 
         RTS_HIP(rocprim::inclusive_scan(nullptr, tmp, c->d_ghead.p, c->d_gid.p, R, rocprim::plus<uint32_t>(), st));
         RTS_HIP(c->d_sort_tmp.reserve(tmp));
         RTS_HIP(rocprim::inclusive_scan(c->d_sort_tmp.p, tmp, c->d_ghead.p, c->d_gid.p, R, rocprim::plus<uint32_t>(), st));
-        k_agg_starts<<<blocks_for(R, 256), 256, 0, st>>>(c->d_ghead.p, c->d_gid.p, gstart, R);
+        k_agg_starts<<<blocks_for(R, 256), 256, 0, st>>>(c->d_ghead.p, c->d_gid.p, s.gstart, R);
     }
-    k_agg_tiles<<<ntiles, AGG_TILE, 0, st>>>(d_rays, c->d_aidx_sorted.p, c->d_gid.p, gstart, R, cspeed, carrier, gsum, tile_first, tile_last, c->recv_dev);
+    k_agg_tiles<<<s.ntiles, AGG_TILE, 0, st>>>(d_rays, c->d_aidx_sorted.p, c->d_gid.p, s.gstart, R, cspeed, carrier, s.gsum, s.tile_first, s.tile_last, c->recv_dev);
     if (small) {
-        RtsPinned* pd = c->pin.dev;
-        const uint32_t spec_s = std::min<uint32_t>(R, RTS_PIN_GROUPS);
-        const RtsAggFinish fq = {d_rays, c->d_aidx_sorted.p, c->d_akeys_sorted.p, c->d_gid.p, gstart, tile_first, tile_last, gsum, c->d_gmin.p, c->d_gkey.p, d_G,
-                                 d_rows, d_rows ? c->d_grow.p : nullptr, shift, n_rx_tab, d_rxtot, d_rxmin, (int64_t)base, d_npath, d_power_sum, d_doppler_sum, d_delay, d_phase, d_pm,
-                                 pm_init, pm_init == INT32_MIN ? 1 : 0, c->agg_delay_in ? 1 : 0,
-                                 spec_s, groups ? &pd->G : nullptr, pd->gsum, pd->gmin, pd->gkey, pd->grow};
-        k_agg_finish_small<<<1, 256, 0, st>>>(fq, R, ntiles, c->recv_dev);
+        RtsAggFinish fq = rts_agg_finish_args(c, k, s, R, d_rays, d_rows, base, groups != nullptr);
+        fq.npath0 = d_npath; fq.power0 = d_power_sum; fq.doppler0 = d_doppler_sum; fq.delay = d_delay; fq.phase = d_phase; fq.pm = d_pm;      // the caller's in-out arrays
+        fq.pm_init_const = pm_init; fq.use_pm_in = pm_init == INT32_MIN ? 1 : 0; fq.dly_in = c->agg_delay_in ? 1 : 0;
+        k_agg_finish_small<<<1, 256, 0, st>>>(fq, R, s.ntiles, c->recv_dev);
         RTS_HIP(hipGetLastError());
         if (!groups) { RTS_HIP(hipStreamSynchronize(st)); return RTS_OK; }
-        RtsAggPending& ap = c->agg_pending;
-        ap.valid = true; ap.R = R; ap.D = D; ap.B = B; ap.shift = shift; ap.wide = false; ap.base = base; ap.rows = d_rows != nullptr; ap.spec = spec_s; ap.gsum = gsum;
+        rts_agg_pending_set(c, k, R, D, base, d_rows != nullptr, s.gsum);
         if (groups != &c->groups) return rts_aggregate_fetch(c, groups);
         return RTS_OK;
     }
-    k_agg_span<<<ntiles, 64, 0, st>>>(gstart, c->d_gid.p, R, tile_first, tile_last, gsum);
-    k_agg_groupinfo<<<blocks_for(R, 256), 256, 0, st>>>(gstart, c->d_aidx_sorted.p, c->d_akeys_sorted.p, c->d_gid.p, R, c->d_gmin.p, c->d_gkey.p, d_G, d_rows, d_rows ? c->d_grow.p : nullptr);
-    k_agg_rxtot<<<n_rx_tab, 64, 0, st>>>(c->d_gkey.p, gsum, c->d_gmin.p, d_G, shift, d_rxtot, d_rxmin);
-    k_agg_scatter<<<blocks_for(R, 256), 256, 0, st>>>(d_rays, c->d_aidx_sorted.p, c->d_gid.p, gsum, c->d_gmin.p, d_rxtot, d_rxmin, n_rx_tab, R,
+    k_agg_span<<<s.ntiles, 64, 0, st>>>(s.gstart, c->d_gid.p, R, s.tile_first, s.tile_last, s.gsum);
+    k_agg_groupinfo<<<blocks_for(R, 256), 256, 0, st>>>(s.gstart, c->d_aidx_sorted.p, c->d_akeys_sorted.p, c->d_gid.p, R, c->d_gmin.p, c->d_gkey.p, s.d_G, d_rows, d_rows ? c->d_grow.p : nullptr);
+    k_agg_rxtot<<<k.n_rx_tab, 64, 0, st>>>(c->d_gkey.p, s.gsum, c->d_gmin.p, s.d_G, k.shift, s.rxtot, s.rxmin);
+    k_agg_scatter<<<blocks_for(R, 256), 256, 0, st>>>(d_rays, c->d_aidx_sorted.p, c->d_gid.p, s.gsum, c->d_gmin.p, s.rxtot, s.rxmin, k.n_rx_tab, R,
                                                        (int64_t)base, d_npath, d_power_sum, d_doppler_sum, d_delay, d_phase, d_pm, pm_init, pm_init == INT32_MIN ? 1 : 0, c->agg_delay_in ? 1 : 0);
     RTS_HIP(hipGetLastError());
     if (!groups) { RTS_HIP(hipStreamSynchronize(st)); return RTS_OK; }
-    if (wide) {                                        // the groups' path rows, for the host copy of the table
+    if (k.wide) {                                        // the groups' path rows, for the host copy of the table
         RTS_HIP(c->d_gpath.reserve((size_t)R * D + 1));
-        k_agg_gather_paths<<<blocks_for(R, 256), 256, 0, st>>>(d_paths, c->d_gmin.p, d_G, D, c->d_gpath.p);
+        k_agg_gather_paths<<<blocks_for(R, 256), 256, 0, st>>>(d_paths, c->d_gmin.p, s.d_G, D, c->d_gpath.p);
         RTS_HIP(hipGetLastError());
     }
     // group table to the host: count + the first AGG_SPEC groups speculatively in one batch (pinned), rest on demand
-    const uint32_t spec = std::min<uint32_t>(R, RTS_PIN_GROUPS);
+    const uint32_t spec = rts_agg_spec(R);
     // (written by ONE kernel straight into the pinned block -- five small device-to-host copies per pulse before)
-    k_agg_export<<<blocks_for(spec, 256), 256, 0, st>>>(d_G, gsum, c->d_gmin.p, c->d_gkey.p, d_rows ? c->d_grow.p : nullptr, spec, &c->pin.dev->G, c->pin.dev->gsum, c->pin.dev->gmin, c->pin.dev->gkey, c->pin.dev->grow);
+    k_agg_export<<<blocks_for(spec, 256), 256, 0, st>>>(s.d_G, s.gsum, c->d_gmin.p, c->d_gkey.p, d_rows ? c->d_grow.p : nullptr, spec, &c->pin.dev->G, c->pin.dev->gsum, c->pin.dev->gmin, c->pin.dev->gkey, c->pin.dev->grow);
     RTS_HIP(hipGetLastError());
     // The table is READ when somebody asks for it (rts_aggregate_fetch): a caller that keeps several pulses in flight enqueues the
     // next pulse while this one's ~16 small kernels wait their turn among the trace kernels' blocks -- the submitting thread used
     // to sit out that chain here, 0.4 of the 0.63 ms of a pipelined BASELINE configs[2] pulse.
-    RtsAggPending& ap = c->agg_pending;
-    ap.valid = true; ap.R = R; ap.D = D; ap.B = B; ap.shift = shift; ap.wide = wide; ap.base = base; ap.rows = d_rows != nullptr; ap.spec = spec; ap.gsum = gsum;
+    rts_agg_pending_set(c, k, R, D, base, d_rows != nullptr, s.gsum);
     if (groups != &c->groups) return rts_aggregate_fetch(c, groups);          // (a caller's own vector: now)
     return RTS_OK;
 }
@@ -1482,8 +1486,8 @@ int rts_aggregate_fetch(RtsContext* c, std::vector<RtsGroup>* groups)
     ap.valid = false;
     hipStream_t st = c->stream;
     RtsPinned* pin = c->pin.p;
-    const uint32_t R = ap.R, D = ap.D, B = ap.B, shift = ap.shift, spec = ap.spec; const bool wide = ap.wide; const uint64_t base = ap.base;
-    const bool d_rows = ap.rows; double* gsum = ap.gsum; (void)R;
+    const uint32_t D = ap.D, spec = ap.spec; const RtsKeyPlan key = ap.key; const bool wide = key.wide; const uint64_t base = ap.base;
+    const bool d_rows = ap.rows; double* gsum = ap.gsum;
     RTS_HIP(rts_stream_wait(c, st));
     const uint32_t G = pin->G;
     const double* h_gsum = pin->gsum; const uint32_t* h_gmin = pin->gmin; const uint64_t* h_gkey = pin->gkey;
@@ -1497,17 +1501,16 @@ int rts_aggregate_fetch(RtsContext* c, std::vector<RtsGroup>* groups)
         RTS_HIP(hipMemcpy(v_gkey.data(), c->d_gkey.p, sizeof(uint64_t)*G, hipMemcpyDeviceToHost));
         h_gsum = v_gsum.data(); h_gmin = v_gmin.data(); h_gkey = v_gkey.data();
     }
-    const uint64_t pmask = (shift >= 64) ? ~0ULL : (((uint64_t)1 << shift) - 1);
     std::vector<int32_t> v_gpath;
     if (wide && G) { v_gpath.resize((size_t)G * D); RTS_HIP(hipMemcpy(v_gpath.data(), c->d_gpath.p, sizeof(int32_t) * (size_t)G * D, hipMemcpyDeviceToHost)); }
     groups->resize(G);
     for (uint32_t g = 0; g < G; g++) {
         RtsGroup& gr = (*groups)[g]; memset(&gr, 0, sizeof(gr));
-        gr.rx = (int32_t)((shift >= 64) ? 0u : (uint32_t)(h_gkey[g] >> shift));
+        gr.rx = (int32_t)rts_key_rx(key, h_gkey[g]);
         bool all_neg = true;
         for (uint32_t k = 0; k < RTS_MAX_DEPTH; k++) {
             int v = -1;
-            if (k < D) v = wide ? v_gpath[(size_t)g * D + k] : (int)(((h_gkey[g] & pmask) >> (k*B)) & (((uint64_t)1 << B) - 1)) - 1;
+            if (k < D) v = wide ? v_gpath[(size_t)g * D + k] : rts_key_path(key, h_gkey[g], k);      // (the host cannot decode the path from a wide key's surrogate)
             gr.path[k] = v; if (v >= 0) all_neg = false;
         }
         gr.direct = all_neg ? 1u : 0u;

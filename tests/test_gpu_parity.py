@@ -334,12 +334,21 @@ def test_shared_scene_between_handles(rts, scenes):
 
 
 @pytest.mark.parametrize("seed,R,D,n_rx,n_targ", [(1, 50, 3, 2, 2), (2, 3000, 4, 4, 3), (3, 700, 1, 1, 1), (4, 5000, 6, 3, 1), (5, 1, 2, 1, 1),
-                                                   (6, 2500, 16, 5, 100), (7, 1500, 16, 300, 250), (8, 900, 9, 2, 200)])
+                                                   (6, 2500, 16, 5, 100), (7, 1500, 16, 300, 250), (8, 900, 9, 2, 200),
+                                                   (9, 4096, 10, 2, 7), (10, 4097, 10, 2, 7),
+                                                   (11, 1024, 10, 4, 7), (12, 1025, 10, 4, 7), (13, 2048, 10, 4, 7), (14, 2049, 10, 4, 7),
+                                                   (15, 2048, 15, 16, 15), (16, 2048, 15, 17, 15)])
 def test_kernel_wrapper_equals_literal(rts, oracle, seed, R, D, n_rx, n_targ):
     """rs::kernel_wrapper drop-in (aggregation.cuh:19-22): same in/out arrays as the O(R^2) myKernel1/2.  Seeds 6-8 need a
-    (receiver, path) key of 115 / 137 / 73 bits: the multi-word (wide key) path of the group-by"""
+    (receiver, path) key of 115 / 137 / 73 bits: the multi-word (wide key) path of the group-by.  Seeds 9-16 sit on the
+    boundaries of the key plan (rts_post_plan.h): a key of 31 bits, the last that is sorted as 32 bits, with 4 096 rays (one
+    block, 16 items per thread) and 4 097 (the general chain); 32 bits, the first 64-bit sort, with 1 024 / 1 025 rays (4 and 8
+    items per thread) and 2 048 / 2 049 (one block, the general chain); 64 bits, the key fills the word and the receiver sits at
+    bit 60; 65 bits, the first wide key.  The wrapper sizes the key from the largest entries it is given: the last receiver and
+    the last target occur in every set."""
     rng = np.random.default_rng(seed)
     a, paths = random_received_set(oracle, rng, R, D, n_rx, n_targ)
+    assert a["received"].max() == n_rx - 1 and paths.max() == (n_targ - 1 if (a["reflDepth"] > 0).any() else -1)
     fc = 10e9
     lit = oracle.aggregate_literal(a, paths, C0, fc, 10 ** 6)
     got = rts.kernel_wrapper(a, paths, C0, fc, 10 ** 6)
