@@ -530,6 +530,68 @@ typedef struct RtsDetection {
 int rts_cube_detect(RtsHandle h, const RtsCfarParams* p, const void* device_map, uint32_t n_doppler);
 int rts_cube_detections_get(RtsHandle h, RtsDetection* out, uint32_t capacity, uint32_t* n_out);
 
+/* ---------------------------------------------------------------- backprojection imaging (SAR / ISAR) of the return cube
+ * A derived product like the cube itself: time-domain backprojection of a coherent interval onto a planar
+ * pixel grid -- exact for any track, any bistatic geometry and any target motion, where the slow-time DFT focuses only while a
+ * scatterer stays in its range bin.  Input: the attached cube y[rx][pulse][bin] -- range-compressed rows, or the impulse cube of
+ * rts_cube_accumulate; t0, dt, n_bins, n_rx are the cube's.  The arithmetic below is rts_amd/csrc/rts_image.h, shared by the kernel
+ * and the host evaluator (the library builds with -ffp-contract=off: the tree is the contract).
+ *   Pixel (ix, iy) lies at x[c] = origin[c] + (double)ix * step_x[c] + (double)iy * step_y[c], evaluated left to right.
+ *   For geometry index j in [0, n_pulses), cube row first_pulse + j and receiver r:
+ *     dT  = sqrt(ax*ax + ay*ay + az*az),  a = x - tx_position[j]
+ *     dR  = sqrt(bx*bx + by*by + bz*bz),  b = x - rx_position[r][j]
+ *     tau = (dT + dR) / cspeed
+ *     d   = (tau - t0) / dt
+ *     v   = the row interpolated at d:
+ *             taps even (2 .. RTS_WAVEFORM_MAX_TAPS): sum_m row[m] h_L(d - m), L = taps, the render's own h_L (RtsWaveform above), 0
+ *               outside the row.  With i = floor(d), phi = d - i the L taps are m = i - L/2 + 1 + k, k = 0 .. L-1, summed in ascending
+ *               m over those inside [0, n_bins); tap k sits at u = phi + (double)(L/2 - 1 - k), its sinc is (-1)^q sinpi(phi) / (pi u)
+ *               (q = L/2 - 1 - k: ONE sinpi per sample) and its window 0.42 + 0.5 C + 0.08 (2 C C - 1) with C = cos(2 pi u / L) taken
+ *               directly at the first tap summed and advanced from tap to tap by the rotation (C, S) <- (C cd + S sd, S cd - C sd),
+ *               cd = cos(2 pi / L), sd = sin(2 pi / L).  phi = 0 gives row[i] bit for bit (0 outside the row).
+ *             taps == 1: row[n], n = floor(d + 0.5); 0 if n is outside [0, n_bins)
+ *             a d that is not finite gives 0.
+ *     c   = carrier * tau;  f = c - floor(c);  (sn, cs) = sincospi(2 f)     -- undoes the cube's phase -fmod(2 pi fc tau, 2 pi)
+ *     term = (w[j] * v) * (cs + j sn), re = a cs - b sn, im = a sn + b cs with (a, b) = (w re v, w im v);  w = pulse_weight, 1 when NULL
+ *   image[r][iy][ix] = sum_j term, in ONE order whatever the launch shape: ascending j from 0 inside chunks of RTS_IMAGE_PULSE_CHUNK
+ *   pulses, then the chunk sums added in ascending chunk order (the first chunk's sum is the start value) -- bit-identical from
+ *   run to run, and a small image of many pulses still fills the GPU (one chunk per workgroup, a second kernel adds them; no atomics).
+ *   With RTS_IMAGE_ACCUMULATE the finished sum is added to what the output holds (pulse-sharded GPUs: images are linear in the cube).
+ * Geometry: stop-and-go, which is what a traced pulse records (rayLength / c at the pulse time).  All positions are given in the
+ * image's frame: for SAR the world frame; for ISAR the caller moves the radar into the target's frame, p' = R_j^T (p - position_j)
+ * with RtsTargetMotion's rotation and position of pulse j.
+ * A COHERENT image needs a cube accumulated or rendered from rays (rts_cube_accumulate, RTS_RENDER_RAYS): the path products carry
+ * the reference's mean of wrapped phases, which is not the phase of any delay.
+ * rts_cube_backproject is ordered on the handle's stream and never waits for the device's earlier work (it waits only for the
+ * copy of the PREVIOUS call's geometry out of the handle's pinned staging block); the caller's arrays are free on return.
+ * device_out: caller-owned device memory of 2 n_rx n_y n_x doubles (16-byte aligned), or NULL: library-owned, alive until the next
+ * backprojection of another size, rts_cube_attach or rts_destroy (the rule of the Doppler map).  rts_cube_image_get synchronises and
+ * copies the library-owned image; RTS_ERR_INVALID after an rts_cube_attach.  RTS_IMAGE_ACCUMULATE with device_out NULL needs an
+ * existing library-owned image of the same shape.
+ * RTS_ERR_INVALID, the message naming the field: no cube attached; n_x or n_y zero or n_x n_y > RTS_IMAGE_MAX_PIXELS; taps not 1 and
+ * not even in [2, RTS_WAVEFORM_MAX_TAPS]; unknown flags; nonzero reserved fields; n_pulses zero or first_pulse + n_pulses beyond the
+ * cube's rows; cspeed not finite or <= 0; carrier not finite or negative; a non-finite position, origin, step or weight; a NULL
+ * tx_position or rx_position; more than 65 535 receivers or chunks (the launch grid).
+ * rts_backproject_eval: pure host, no device.  The same validation (q in place of the attached cube) and the same rts_image.h
+ * functions on a host cube [n_rx][q->n_pulses][n_bins] (interleaved re / im) -> out [n_rx][n_y][n_x] (interleaved), added to
+ * with RTS_IMAGE_ACCUMULATE.  A refused call leaves out untouched. */
+#define RTS_IMAGE_ACCUMULATE 1u          /* add to the output instead of overwriting it */
+#define RTS_IMAGE_PULSE_CHUNK 64u
+#define RTS_IMAGE_MAX_PIXELS 16777216u   /* n_x * n_y */
+typedef struct RtsImageParams {
+    uint32_t n_x, n_y, taps, flags;
+    uint32_t first_pulse, n_pulses;      /* cube rows first_pulse .. first_pulse + n_pulses - 1 */
+    double origin[3], step_x[3], step_y[3];
+    double cspeed, carrier;
+    const double* tx_position;           /* [n_pulses][3]           host */
+    const double* rx_position;           /* [n_rx][n_pulses][3]     host */
+    const double* pulse_weight;          /* [n_pulses] or NULL      host */
+    uint64_t reserved[2];                /* 0 */
+} RtsImageParams;
+int rts_cube_backproject(RtsHandle h, const RtsImageParams* p, void* device_out);   /* complex128 [n_rx][n_y][n_x]; NULL: library-owned */
+int rts_cube_image_get(RtsHandle h, double* host_out, uint64_t capacity_doubles);
+int rts_backproject_eval(const RtsCubeParams* q, const double* cube, const RtsImageParams* p, double* out);  /* pure host, no device */
+
 /* ---------------------------------------------------------------- several GPUs (not in the reference: it is single-GPU)
  * Rays are independent (each launch index writes only its own rows, ray_tracer.cu:227-253) and so are pulses
  * (ray_tracer.cpp:843).  rts_plan_cpi deals the n_pulses x total_rays (pulse, launch index) pairs of one coherent

@@ -117,6 +117,21 @@ DETECTION_DTYPE = np.dtype([("rx", "<u4"), ("doppler_bin", "<u4"), ("range_bin",
 assert DETECTION_DTYPE.itemsize == 72 and C.sizeof(RtsCfarParams) == 72
 
 
+RTS_IMAGE_ACCUMULATE, RTS_IMAGE_PULSE_CHUNK, RTS_IMAGE_MAX_PIXELS = 1, 64, 16777216
+
+
+class RtsImageParams(C.Structure):
+    _fields_ = [("n_x", C.c_uint32), ("n_y", C.c_uint32), ("taps", C.c_uint32), ("flags", C.c_uint32),
+                ("first_pulse", C.c_uint32), ("n_pulses", C.c_uint32),
+                ("origin", C.c_double * 3), ("step_x", C.c_double * 3), ("step_y", C.c_double * 3),
+                ("cspeed", C.c_double), ("carrier", C.c_double),
+                ("tx_position", C.c_void_p), ("rx_position", C.c_void_p), ("pulse_weight", C.c_void_p),
+                ("reserved", C.c_uint64 * 2)]
+
+
+assert C.sizeof(RtsImageParams) == 152
+
+
 class RtsSceneInfo(C.Structure):
     _fields_ = [("n_targets", C.c_uint32), ("n_prims", C.c_uint32), ("n_nodes", C.c_uint32), ("n_leaves", C.c_uint32),
                 ("handles_sharing", C.c_uint32), ("builder", C.c_uint32), ("build_ms", C.c_double),
@@ -202,7 +217,8 @@ EXPORTS = ["rts_create", "rts_destroy", "rts_last_error", "rts_device_count", "r
            "rts_tile_records_get", "rts_tile_records_set", "rts_deal_tiles", "rts_set_tile_list",
            "rts_set_patterns", "rts_finalise_patterns", "rts_trace_pulse_end_patterns", "rts_pattern_eval",
            "rts_cube_set_waveform", "rts_cube_render", "rts_cube_compress", "rts_waveform_eval",
-           "rts_cube_add_noise", "rts_noise_eval", "rts_cube_detect", "rts_cube_detections_get"]
+           "rts_cube_add_noise", "rts_noise_eval", "rts_cube_detect", "rts_cube_detections_get",
+           "rts_cube_backproject", "rts_cube_image_get", "rts_backproject_eval"]
 
 
 def lib():
@@ -275,6 +291,9 @@ def lib():
         "rts_noise_eval": [u64, vp, u32, C.c_double, vp],
         "rts_cube_detect": [vp, C.POINTER(RtsCfarParams), vp, u32],
         "rts_cube_detections_get": [vp, vp, u32, C.POINTER(u32)],
+        "rts_cube_backproject": [vp, C.POINTER(RtsImageParams), vp],
+        "rts_cube_image_get": [vp, vp, u64],
+        "rts_backproject_eval": [C.POINTER(RtsCubeParams), vp, C.POINTER(RtsImageParams), vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name, None)

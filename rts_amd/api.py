@@ -203,6 +203,61 @@ def noise_eval(seed, index, noise_power):
     return (out[:, 0] + 1j * out[:, 1]).reshape(shape)
 
 
+# ------------------------------------------------------------------------------- backprojection imaging (rts_image.h)
+def _image_params(origin, step_x, step_y, n_x, n_y, tx_positions, rx_positions, cspeed, carrier, taps, first, count, weights, accumulate, n_rx):
+    """RtsImageParams and the arrays it points to (keep them alive for the call).  tx_positions [P][3]; rx_positions [n_rx][P][3]
+    ([P][3] for one receiver); count None: every position given"""
+    tx = np.ascontiguousarray(np.asarray(tx_positions, np.float64).reshape(-1, 3))
+    P = len(tx) if count is None else int(count)
+    rx = np.ascontiguousarray(np.asarray(rx_positions, np.float64).reshape(-1, 3))
+    if len(tx) != P or len(rx) != n_rx * P:
+        raise ValueError("backprojection: %d transmitter and %d receiver positions for %d pulses and %d receivers" % (len(tx), len(rx), P, n_rx))
+    w = None if weights is None else np.ascontiguousarray(np.asarray(weights, np.float64).ravel())
+    if w is not None and len(w) != P:
+        raise ValueError("backprojection: %d weights for %d pulses" % (len(w), P))
+    p = L.RtsImageParams()
+    p.n_x, p.n_y, p.taps, p.flags = int(n_x), int(n_y), int(taps), L.RTS_IMAGE_ACCUMULATE if accumulate else 0
+    p.first_pulse, p.n_pulses = int(first), P
+    for k in range(3):
+        p.origin[k], p.step_x[k], p.step_y[k] = float(origin[k]), float(step_x[k]), float(step_y[k])
+    p.cspeed, p.carrier = float(cspeed), float(carrier)
+    p.tx_position, p.rx_position, p.pulse_weight = ptr(tx), ptr(rx), ptr(w)
+    return p, (tx, rx, w)
+
+
+def backproject_eval(cube, t0, dt, origin, step_x, step_y, n_x, n_y, tx_positions, rx_positions, cspeed, carrier, taps=8, first=0, count=None,
+                     weights=None, out=None):
+    """rts_backproject_eval (pure host): the backprojected image of a host cube [n_rx][n_pulses][n_bins] (complex), complex
+    [n_rx][n_y][n_x]; out: an image to ADD to (RTS_IMAGE_ACCUMULATE), returned updated"""
+    cube = np.ascontiguousarray(np.asarray(cube, np.complex128))
+    n_rx, n_p, n_bins = cube.shape
+    q = L.RtsCubeParams(n_rx, n_p, n_bins, 0, float(t0), float(dt))
+    p, keep = _image_params(origin, step_x, step_y, n_x, n_y, tx_positions, rx_positions, cspeed, carrier, taps, first, count, weights, out is not None, n_rx)
+    img = np.zeros((n_rx, int(n_y), int(n_x)), np.complex128) if out is None else np.ascontiguousarray(np.array(out, np.complex128))
+    if img.shape != (n_rx, int(n_y), int(n_x)):
+        raise ValueError("backproject_eval: out has shape %s" % (img.shape,))
+    check(L.lib().rts_backproject_eval(C.byref(q), ptr(cube.view(np.float64)), C.byref(p), ptr(img.view(np.float64))))
+    return img
+
+
+def image_frame(positions, motions):
+    """ISAR change of frame: radar positions [..., P, 3] (world) -> the target's frame, p' = R_j^T (p - position_j) per pulse j.
+    motions: per pulse a dict(position=, rotation= 9 values row-major or None) or an RtsTargetMotion"""
+    p = np.asarray(positions, np.float64)
+    out = np.empty_like(p)
+    if p.shape[-2] != len(motions):
+        raise ValueError("image_frame: %d pulses of positions, %d motions" % (p.shape[-2], len(motions)))
+    for j, m in enumerate(motions):
+        if isinstance(m, L.RtsTargetMotion):
+            pos = np.array(m.position[:]); rot = np.array(m.rotation[:]).reshape(3, 3) if m.has_rotation else None
+        else:
+            pos = np.asarray(m["position"], np.float64); rot = m.get("rotation")
+            rot = None if rot is None else np.asarray(rot, np.float64).reshape(3, 3)
+        d = p[..., j, :] - pos
+        out[..., j, :] = d if rot is None else d @ rot              # (R^T d)_i = sum_k R[k][i] d_k
+    return out
+
+
 def device_count():
     n = C.c_int(0)
     rc = L.lib().rts_device_count(C.byref(n))
@@ -539,6 +594,27 @@ class Tracer:
         out = np.zeros(max(n.value, 1), L.DETECTION_DTYPE)
         check(L.lib().rts_cube_detections_get(self.h, ptr(out), n.value, C.byref(n)))
         return out[:n.value].copy()
+
+    def cube_backproject(self, origin, step_x, step_y, n_x, n_y, tx_positions, rx_positions, cspeed, carrier, taps=8, first=0, count=None,
+                         weights=None, accumulate=False, device_ptr=None, fetch=True):
+        """rts_cube_backproject: the attached cube's rows first .. first + count - 1 backprojected onto the pixel grid origin + ix step_x +
+        iy step_y; tx_positions [count][3], rx_positions [n_rx][count][3] in the image's frame (image_frame for ISAR).  Into a caller
+        complex128 device tensor [n_rx][n_y][n_x] (device_ptr; nothing is fetched) or the library's image, returned complex
+        [n_rx][n_y][n_x] when fetch"""
+        p, keep = _image_params(origin, step_x, step_y, n_x, n_y, tx_positions, rx_positions, cspeed, carrier, taps, first, count, weights, accumulate,
+                                self._cube_shape[0])
+        check(L.lib().rts_cube_backproject(self.h, C.byref(p), C.c_void_p(device_ptr) if device_ptr else None))
+        if device_ptr:
+            return None
+        self._image_shape = (self._cube_shape[0], int(n_y), int(n_x))
+        return self.image() if fetch else None
+
+    def image(self):
+        """rts_cube_image_get: the library-owned image of the last cube_backproject"""
+        shape = getattr(self, "_image_shape", None) or (1, 1, 1)
+        out = np.zeros(shape + (2,), np.float64)
+        check(L.lib().rts_cube_image_get(self.h, ptr(out), out.size))
+        return out[..., 0] + 1j * out[..., 1]
 
     def cube(self):
         out = np.zeros(self._cube_shape + (2,), np.float64)

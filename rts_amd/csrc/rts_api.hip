@@ -163,7 +163,7 @@ void rts_hist_unref(RtsTileHist* h) { if (h && --h->refs == 0) delete h; }
 void rts_gate_unref(RtsGate* g) { if (g && --g->refs == 0) { if (g->tstream) (void)hipStreamDestroy(g->tstream); delete g; } }
 
 // The teardown of a handle, once.  After this body the members destroy themselves in reverse order of declaration: every DevBuf
-// (hipFree) and the pinned blocks pin, pin_rx, pin_pat and the mirror's (hipHostFree).  That is safe because no work can read
+// (hipFree) and the pinned blocks pin, pin_rx, pin_pat, pin_img and the mirror's (hipHostFree).  That is safe because no work can read
 // them any more: `stream` and `cstream` have been drained, the trace stream has been drained (it may live on with the other
 // handles of the link group, but carries no work of this handle), and nothing is enqueued on a handle's behalf anywhere else.
 RtsContext::~RtsContext()
@@ -174,6 +174,7 @@ RtsContext::~RtsContext()
     if (tstream) (void)hipStreamSynchronize(tstream);
     rts_gate_unref(gate); gate = nullptr;
     if (ev_pat) (void)hipEventDestroy(ev_pat);
+    if (ev_img) (void)hipEventDestroy(ev_img);
     for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ev_coop) if (e) (void)hipEventDestroy(e);
     if (cstream) { (void)hipStreamSynchronize(cstream); (void)hipStreamDestroy(cstream); }
@@ -239,6 +240,7 @@ extern "C" int rts_create(const RtsParams* p, RtsHandle* out)
     { const char* e = getenv("RTS_SPECULATE"); if (e) c->spec_enabled = atoi(e) != 0; }
     { const char* e = getenv("RTS_POST_SMALL"); if (e) c->post_small = atoi(e) != 0; }
     { const char* e = getenv("RTS_POST_ONE_MAX"); if (e) c->post_one_max = (uint64_t)strtoull(e, nullptr, 10); }
+    { const char* e = getenv("RTS_IMAGE_SPLIT_BELOW"); if (e) c->img_split_below = (uint32_t)std::min(65536, std::max(0, atoi(e))); }
     { const char* e = getenv("RTS_POST_PRIO"); if (e) c->post_prio = (uint32_t)std::min(3, std::max(0, atoi(e))); }
     { const char* e = getenv("RTS_COOP_STEPS"); if (e) c->coop_walk_steps = (uint32_t)std::max(0, atoi(e)); }
     { const char* e = getenv("RTS_COOP_STEPS_LO"); if (e) c->coop_walk_steps_lo = (uint32_t)std::max(0, atoi(e)); }
@@ -1622,6 +1624,7 @@ extern "C" int rts_cube_attach(RtsHandle c, const RtsCubeParams* p, void* device
     else { RTS_HIP(c->d_cube_own.reserve(doubles)); c->cube = c->d_cube_own.p; RTS_HIP(hipMemset(c->cube, 0, sizeof(double) * doubles)); }
     c->cube_set = true;
     c->det_valid = false; c->doppler_fresh = false;         // (a detection list, and a map rts_cube_detect may take, belong to the cube they were made from)
+    c->img_valid = false;                                   // (... and so does an image)
     return RTS_OK;
 }
 
@@ -1815,6 +1818,83 @@ extern "C" int rts_cube_detections_get(RtsHandle c, RtsDetection* out, uint32_t 
     if (n > capacity) n = capacity;
     if (n) RTS_HIP(hipMemcpy(out, c->d_det.p, sizeof(RtsDetection) * n, hipMemcpyDeviceToHost));
     if (n < total) { rts_set_error("rts_cube_detections_get: %u of %u detections copied (max_detections %u, capacity %u)", n, total, c->det_max, capacity); return RTS_ERR_CAPACITY; }
+    return RTS_OK;
+}
+
+// ------------------------------------------------------------------------------------- backprojection imaging
+// (rts_amd.h: RtsImageParams; the arithmetic and the launch plan are rts_image.h, shared by the host export and the kernel, rts_image.hip)
+static int rts_image_check(const RtsImageParams* p, const RtsCubeParams& q, const char* who)
+{
+    if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
+    if (p->n_x == 0 || p->n_y == 0 || (uint64_t)p->n_x * p->n_y > RTS_IMAGE_MAX_PIXELS) { rts_set_error("%s: n_x = %u, n_y = %u (each >= 1, n_x * n_y <= %u)", who, p->n_x, p->n_y, RTS_IMAGE_MAX_PIXELS); return RTS_ERR_INVALID; }
+    if (p->taps != 1u && (p->taps < 2u || p->taps > RTS_WAVEFORM_MAX_TAPS || (p->taps & 1u))) { rts_set_error("%s: taps = %u (1, or even in [2, %u])", who, p->taps, RTS_WAVEFORM_MAX_TAPS); return RTS_ERR_INVALID; }
+    if (p->flags & ~RTS_IMAGE_ACCUMULATE) { rts_set_error("%s: unknown flags 0x%x", who, p->flags); return RTS_ERR_INVALID; }
+    if (p->reserved[0] || p->reserved[1]) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
+    if (p->n_pulses == 0 || p->first_pulse >= q.n_pulses || p->n_pulses > q.n_pulses - p->first_pulse) { rts_set_error("%s: first_pulse = %u, n_pulses = %u: at least one pulse, inside the cube's %u rows", who, p->first_pulse, p->n_pulses, q.n_pulses); return RTS_ERR_INVALID; }
+    if (!std::isfinite(p->cspeed) || !(p->cspeed > 0.0)) { rts_set_error("%s: cspeed = %g (finite, > 0)", who, p->cspeed); return RTS_ERR_INVALID; }
+    if (!std::isfinite(p->carrier) || p->carrier < 0.0) { rts_set_error("%s: carrier = %g (finite, >= 0)", who, p->carrier); return RTS_ERR_INVALID; }
+    for (int k = 0; k < 3; k++) {
+        if (!std::isfinite(p->origin[k])) { rts_set_error("%s: origin[%d] is not finite", who, k); return RTS_ERR_INVALID; }
+        if (!std::isfinite(p->step_x[k])) { rts_set_error("%s: step_x[%d] is not finite", who, k); return RTS_ERR_INVALID; }
+        if (!std::isfinite(p->step_y[k])) { rts_set_error("%s: step_y[%d] is not finite", who, k); return RTS_ERR_INVALID; }
+    }
+    if (!p->tx_position) { rts_set_error("%s: null tx_position", who); return RTS_ERR_INVALID; }
+    if (!p->rx_position) { rts_set_error("%s: null rx_position", who); return RTS_ERR_INVALID; }
+    for (size_t i = 0; i < 3 * (size_t)p->n_pulses; i++) if (!std::isfinite(p->tx_position[i])) { rts_set_error("%s: tx_position of pulse %zu is not finite", who, i / 3); return RTS_ERR_INVALID; }
+    for (size_t i = 0; i < 3 * (size_t)q.n_rx * p->n_pulses; i++) if (!std::isfinite(p->rx_position[i])) { rts_set_error("%s: rx_position of receiver %zu, pulse %zu is not finite", who, i / 3 / p->n_pulses, i / 3 % p->n_pulses); return RTS_ERR_INVALID; }
+    if (p->pulse_weight) for (uint32_t j = 0; j < p->n_pulses; j++) if (!std::isfinite(p->pulse_weight[j])) { rts_set_error("%s: pulse_weight[%u] is not finite", who, j); return RTS_ERR_INVALID; }
+    if (!rts_image_plan(p->n_x, p->n_y, q.n_rx, p->n_pulses, 0u).supported) { rts_set_error("%s: n_rx = %u receivers / n_pulses = %u: more than %u receivers or chunks of %u pulses", who, q.n_rx, p->n_pulses, RTS_IMAGE_GRID_MAX, RTS_IMAGE_PULSE_CHUNK); return RTS_ERR_INVALID; }
+    return RTS_OK;
+}
+
+extern "C" int rts_backproject_eval(const RtsCubeParams* q, const double* cube, const RtsImageParams* p, double* out)
+{
+    if (!q || q->n_rx == 0 || q->n_pulses == 0 || q->n_bins == 0 || !(q->dt > 0) || !std::isfinite(q->dt) || !std::isfinite(q->t0)) { rts_set_error("rts_backproject_eval: bad cube parameters"); return RTS_ERR_INVALID; }
+    int rc = rts_image_check(p, *q, "rts_backproject_eval"); if (rc != RTS_OK) return rc;
+    if (!cube || !out) { rts_set_error("rts_backproject_eval: null cube or output array"); return RTS_ERR_INVALID; }
+    rts_image_eval_host(q, cube, p, out);
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_backproject(RtsHandle c, const RtsImageParams* p, void* device_out)
+{
+    CHECK_HANDLE(c);
+    if (!c->cube_set) { rts_set_error("rts_cube_backproject: no cube (call rts_cube_attach first)"); return RTS_ERR_INVALID; }
+    const RtsCubeParams& q = c->cube_params;
+    int rc = rts_image_check(p, q, "rts_cube_backproject"); if (rc != RTS_OK) return rc;
+    if ((uintptr_t)device_out & 15u) { rts_set_error("rts_cube_backproject: device_out is not 16-byte aligned"); return RTS_ERR_INVALID; }
+    const bool acc = (p->flags & RTS_IMAGE_ACCUMULATE) != 0;
+    if (acc && !device_out && !(c->img_valid && c->img_nx == p->n_x && c->img_ny == p->n_y)) {
+        rts_set_error("rts_cube_backproject: RTS_IMAGE_ACCUMULATE without device_out needs a library-owned image of the same n_x, n_y"); return RTS_ERR_INVALID; }
+    CHECK_CLOSED(c);
+    const RtsImagePlan plan = rts_image_plan(p->n_x, p->n_y, q.n_rx, p->n_pulses, c->img_split_below);
+    const size_t doubles = 2 * (size_t)q.n_rx * p->n_y * p->n_x;
+    double* out = (double*)device_out;
+    if (!out) { RTS_HIP(c->d_image_own.reserve(doubles)); out = c->d_image_own.p; }       // (accumulate: the shape is the same, so the buffer stays)
+    // the geometry [tx | rx | w] -> pinned staging -> the device, on the stream
+    const size_t P = p->n_pulses, n_geo = 3 * P + 3 * (size_t)q.n_rx * P + P;
+    if (c->ev_img_armed) { RTS_HIP(hipEventSynchronize(c->ev_img)); c->ev_img_armed = false; }
+    if (c->pin_img.cap < n_geo) RTS_HIP(c->pin_img.reserve(std::max<size_t>(n_geo + n_geo / 2, 4096), false));
+    if (!c->ev_img) RTS_HIP(hipEventCreateWithFlags(&c->ev_img, hipEventDisableTiming));
+    RTS_HIP(c->d_img_geo.reserve(n_geo));
+    double* g = c->pin_img.p;
+    memcpy(g, p->tx_position, sizeof(double) * 3 * P);
+    memcpy(g + 3 * P, p->rx_position, sizeof(double) * 3 * q.n_rx * P);
+    for (size_t j = 0; j < P; j++) g[3 * P + 3 * (size_t)q.n_rx * P + j] = p->pulse_weight ? p->pulse_weight[j] : 1.0;
+    RTS_HIP(hipMemcpyAsync(c->d_img_geo.p, g, sizeof(double) * n_geo, hipMemcpyHostToDevice, c->stream));
+    RTS_HIP(hipEventRecord(c->ev_img, c->stream)); c->ev_img_armed = true;
+    if (!device_out) { c->img_nx = p->n_x; c->img_ny = p->n_y; c->img_valid = true; }
+    return rts_cube_backproject_device(c, *p, plan, c->d_img_geo.p, out);
+}
+
+extern "C" int rts_cube_image_get(RtsHandle c, double* host_out, uint64_t capacity_doubles)
+{
+    CHECK_HANDLE(c);
+    if (!c->cube_set || !c->img_valid || !host_out) { rts_set_error("rts_cube_image_get: no library-owned image (rts_cube_backproject with device_out NULL; an image ends at rts_cube_attach) / null output"); return RTS_ERR_INVALID; }
+    const size_t doubles = 2 * (size_t)c->cube_params.n_rx * c->img_ny * c->img_nx;
+    if (capacity_doubles < doubles) { rts_set_error("rts_cube_image_get: capacity too small"); return RTS_ERR_CAPACITY; }
+    RTS_HIP(hipStreamSynchronize(c->stream));
+    RTS_HIP(hipMemcpy(host_out, c->d_image_own.p, sizeof(double) * doubles, hipMemcpyDeviceToHost));
     return RTS_OK;
 }
 

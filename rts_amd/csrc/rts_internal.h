@@ -10,6 +10,7 @@
 #include "rts_pattern.h"
 #include "rts_waveform.h"
 #include "rts_noise.h"
+#include "rts_image.h"            // the arithmetic of a backprojected pixel and the host-only plan of its launch
 #include "rts_owned.h"            // DevBuf, PinBuf: device and pinned host memory that frees itself
 #include "rts_launch_plan.h"      // RTS_BLOCK, RTS_WTILE, RTS_COOP_GROUP, RTS_STACK_OVF and the host arithmetic of a launch
 #include "rts_post_plan.h"        // RTS_SMALL_CAP32 / 64, RTS_AGG_TILE and the host arithmetic of the post-processing
@@ -364,6 +365,12 @@ struct RtsContext {
     // CFAR detection (rts_cube_detect, rts_detect.hip): per-segment counts -> exclusive scan (offsets; element n_seg: the total),
     // the records of the last detection and how many it may hold; det_valid: a list exists for rts_cube_detections_get
     DevBuf<uint32_t> d_det_cnt, d_det_off; DevBuf<uint8_t> d_det_tmp; DevBuf<RtsDetection> d_det; uint32_t det_nseg = 0, det_max = 0; bool det_valid = false;
+    // backprojection (rts_cube_backproject, rts_image.hip): the library-owned image and its shape; img_valid: it holds an image of the
+    // attached cube, for rts_cube_image_get / RTS_IMAGE_ACCUMULATE (a caller-owned output leaves it alone); the call's geometry [tx | rx | w] goes through a pinned staging
+    // block that is rewritten only after the copy of the previous call's has run (ev_img); the chunk sums of a split launch
+    DevBuf<double> d_image_own, d_img_geo, d_img_scratch; uint32_t img_nx = 0, img_ny = 0; bool img_valid = false;
+    PinBuf<double> pin_img; hipEvent_t ev_img = nullptr; bool ev_img_armed = false;
+    uint32_t img_split_below = RTS_IMAGE_SPLIT_BELOW;      // RTS_IMAGE_SPLIT_BELOW: workgroups below which the pulse chunks go on the grid (tests: 0 = never, 65536 = whenever there are two chunks)
     bool doppler_fresh = false;         // rts_cube_doppler ran on the attached cube (rts_cube_detect without a map takes its output)
     bool agg_delay_in = true;           // rts_aggregate_device: the delay / phase arrays carry initial sums (rs::kernel_wrapper's in-out arguments); false: they start at zero
     int64_t agg_base_local = 0;         // pathMatch value of received ray i after rts_aggregate = agg_base_local + i
@@ -412,6 +419,7 @@ int rts_cube_render_device(RtsContext* c, uint32_t pulse_index, bool paths, bool
 int rts_cube_compress_device(RtsContext* c, uint32_t first_pulse, uint32_t n_pulses);
 int rts_cube_noise_device(RtsContext* c, uint32_t first_pulse, uint32_t n_pulses, double sigma, uint64_t seed);          // rts_detect.hip
 int rts_cube_detect_device(RtsContext* c, const RtsCfarParams& p, const double* map, uint32_t n_doppler, uint32_t max_det);
+int rts_cube_backproject_device(RtsContext* c, const RtsImageParams& p, const RtsImagePlan& plan, const double* geo, double* out);      // rts_image.hip
 int rts_post_finalise(RtsContext* c, const double* rcs_host, double wl, double gt, double gr, double carrier, double cspeed);
 int rts_pattern_pulse_upload(RtsContext* c, const RtsSpecParams& q, RtsPatArgs* out);      // the pulse's receiver rows -> the device, on c->stream
 int rts_post_finalise_patterns(RtsContext* c, const RtsSpecParams& q);                       // k_finalise_patterns on the received set (count from c->recv_dev when set)
