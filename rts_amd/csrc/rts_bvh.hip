@@ -10,6 +10,7 @@
 #include <cstring>
 #include <hip/hip_runtime.h>
 #include "rts_internal.h"
+#include "rts_ray_ops.h"            // tri_terms: the ray-free terms of the f64 triangle test, written into the leaf records
 
 // --------------------------------------------------------------------------- placement
 // verts_rot[v][i] = sum_k R[i][k] * vert[v][k], accumulated from 0 in k order
@@ -102,7 +103,8 @@ __device__ __forceinline__ void rts_mask_mark(RtsMaskLds& S, const bool have, co
 }
 
 // Leaf record i = primitive leaf_prim[i] with its world-space vertices pre-gathered (the reference gathers through
-// dbuf_triangles -> dbuf_triVertices per test, triangle_mesh.cu:147-154).  LEAVES && MASK: one pass over the placed triangles
+// dbuf_triangles -> dbuf_triVertices per test, triangle_mesh.cu:147-154) and, of the second and third, only what the test makes
+// of them whatever the ray: the two edges and the normal (RtsLeafTri).  LEAVES && MASK: one pass over the placed triangles
 // for both (a pulse that moves a target needs both; the vertices are gathered once).  MASK alone: the targets stand still,
 // the beam moved.
 // PLACE (r04): the kernel places what it gathers -- the three vertices of its primitive from the LOCAL arrays through the pulse's
@@ -148,9 +150,13 @@ __global__ void __launch_bounds__(256) k_leaves(const uint32_t* __restrict__ lea
         p[6] = verts[3*(size_t)c]; p[7] = verts[3*(size_t)c+1]; p[8] = verts[3*(size_t)c+2];
         }
         if (LEAVES) {
+            // the ray-free terms of the f64 test, from the placed vertices (tri_terms, rts_ray_ops.h: triangle_mesh.cu:127-129)
+            dvec3 e0, e1, nn;
+            tri_terms(mk3(p[0], p[1], p[2]), mk3(p[3], p[4], p[5]), mk3(p[6], p[7], p[8]), e0, e1, nn);
             RtsLeafTri L;
-            L.p0x = p[0]; L.p0y = p[1]; L.p0z = p[2]; L.p1x = p[3]; L.p1y = p[4]; L.p1z = p[5]; L.p2x = p[6]; L.p2y = p[7]; L.p2z = p[8];
-            L.prim = g; L.targ = prim_targ[g];
+            L.p0x = p[0]; L.p0y = p[1]; L.p0z = p[2]; L.e0x = e0.x; L.e0y = e0.y; L.e0z = e0.z; L.e1x = e1.x; L.e1y = e1.y; L.e1z = e1.z;
+            L.nx = nn.x; L.ny = nn.y; L.nz = nn.z;
+            L.prim = g; L.targ = prim_targ[g]; L.pad[0] = 0u; L.pad[1] = 0u;
             leaves[i] = L;
         }
     }

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stddef.h>
 #include <atomic>
 #include <string>
 #include <vector>
@@ -26,15 +27,25 @@ struct __attribute__((aligned(128))) RtsNode4 {
 };
 static_assert(sizeof(RtsNode4) == 128, "node4 size");
 
-// Leaf record, 80 B, in the hierarchy's (depth-first) leaf order, refreshed every pulse: the three f64 WORLD-space
-// vertices the f64 intersection test needs, pre-gathered (the reference gathers through dbuf_triangles ->
-// dbuf_triVertices per test, triangle_mesh.cu:147-154), plus the global primitive id.
+// Leaf record, 112 B (the bytes a lane at a node reads of its record: the same seven dwordx4 loads serve both), in the
+// hierarchy's (depth-first) leaf order, refreshed every pulse: what the f64 intersection test needs of the triangle and
+// what does not depend on the ray -- the first WORLD-space vertex, pre-gathered (the reference gathers through
+// dbuf_triangles -> dbuf_triVertices per test, triangle_mesh.cu:147-154), and the test's ray-free terms e0 = p1 - p0,
+// e1 = p0 - p2, n = e1 x e0 (triangle_mesh.cu:127-129), formed once per pulse by the placement kernel (k_leaves,
+// rts_bvh.hip) with the helpers and in the order the test formed them per lane and per step: the same bits.  Plus the
+// global primitive id and the target.
 struct __attribute__((aligned(16))) RtsLeafTri {
-    double p0x, p0y, p0z, p1x, p1y, p1z, p2x, p2y, p2z;
+    double p0x, p0y, p0z, e0x, e0y, e0z, e1x, e1y, e1z, nx, ny, nz;
     uint32_t prim;                  // global primitive id (targets concatenated in order)
     uint32_t targ;                  // target index
+    uint32_t pad[2];
 };
-static_assert(sizeof(RtsLeafTri) == 80, "leaf size");
+static_assert(sizeof(RtsLeafTri) == 112, "leaf size");
+// the walk step decodes the record from the fetch's seven dwordx4 registers (rts_walk_step, rts_trace.hip): q0 = (p0x, p0y), q1 = (p0z, e0x),
+// q2 = (e0y, e0z), q3 = (e1x, e1y), q4 = (e1z, nx), q5 = (ny, nz), q6 = (prim, targ, pad, pad)
+static_assert(offsetof(RtsLeafTri, p0x) == 0 && offsetof(RtsLeafTri, p0z) == 16 && offsetof(RtsLeafTri, e0y) == 32 && offsetof(RtsLeafTri, e1x) == 48 &&
+              offsetof(RtsLeafTri, e1z) == 64 && offsetof(RtsLeafTri, ny) == 80 && offsetof(RtsLeafTri, prim) == 96 && offsetof(RtsLeafTri, targ) == 100,
+              "leaf record offsets of the walk step's decode");
 
 struct RtsTargetDev {               // per target, per pulse
     double reflCoeff;               // d_targReflCoeff

@@ -5,14 +5,25 @@
 
 struct TriHit { double t, beta, gamma; dvec3 n; bool ok; };
 
-// intersect_triangle_doubles, triangle_mesh.cu:121-137 (tmin/tmax are the f32 ray constants)
+// The ray-free terms of the test (triangle_mesh.cu:127-129: e0 = p1 - p0, e1 = p0 - p2, n = cross(e1, e0)), formed ONCE per
+// pulse where the placed vertices are in registers (k_leaves, rts_bvh.hip) and carried by the leaf record: same operands, same
+// operations in the same order, contraction off -- the bits the test formed for itself at every step of every lane.
+__device__ __forceinline__ void tri_terms(dvec3 p0, dvec3 p1, dvec3 p2, dvec3& e0, dvec3& e1, dvec3& n)
+{
+    e0 = sub3(p1, p0);
+    e1 = sub3(p0, p2);
+    n = cross3(e1, e0);
+}
+
+// intersect_triangle_doubles, triangle_mesh.cu:121-137 (tmin/tmax are the f32 ray constants).  Lines 127-129 -- the edges and
+// the normal -- moved to the placement kernel (tri_terms above); the test starts at line 130, 1 / dot(n, d).
 __device__ __forceinline__ TriHit tri_test(const RtsLeafTri& L, dvec3 o, dvec3 d, float tmin, float tmax)
 {
-    const dvec3 p0 = mk3(L.p0x, L.p0y, L.p0z), p1 = mk3(L.p1x, L.p1y, L.p1z), p2 = mk3(L.p2x, L.p2y, L.p2z);
-    const dvec3 e0 = sub3(p1, p0);
-    const dvec3 e1 = sub3(p0, p2);
+    const dvec3 p0 = mk3(L.p0x, L.p0y, L.p0z);
+    const dvec3 e0 = mk3(L.e0x, L.e0y, L.e0z);
+    const dvec3 e1 = mk3(L.e1x, L.e1y, L.e1z);
     TriHit h;
-    h.n = cross3(e1, e0);
+    h.n = mk3(L.nx, L.ny, L.nz);
     const dvec3 e2 = scale3(1 / dot3(h.n, d), sub3(p0, o));
     const dvec3 i = cross3(d, e2);
     h.beta = dot3(i, e1);

@@ -72,9 +72,9 @@ __device__ __forceinline__ RtsSlabRay rts_slab_setup(const dvec3& o, const dvec3
 
 // The record fetch of a traversal step as explicit instructions.  Written as plain loads ahead of the node / leaf branches
 // the compiler sinks them into the branches again -- narrowed to the dwords each branch uses (17 global_load_dword) and, being
-// in an if / else, issued one branch after the other: two dependent memory round trips per step.  Here: five dwordx4 loads
-// from one per-lane base for every lane, two more for the lanes at nodes (lanes at leaves need 80 bytes, lanes at nodes 112;
-// EXEC is narrowed to the latter inside the block), then the wait -- ONE asm statement:
+// in an if / else, issued one branch after the other: two dependent memory round trips per step.  Here: seven dwordx4 loads
+// from one per-lane base, issued for every lane (a lane at a node needs 112 bytes of its record, a lane at a leaf its
+// 112-byte record), then the wait -- ONE asm statement:
 // the backend does not track vector-memory loads issued from inline asm and the hardware has no interlock on a VGPR with a
 // load in flight, so nothing the compiler might place (a copy, a spill of q0..q6) may come between the loads and the wait.
 typedef unsigned int rts_u32x4 __attribute__((ext_vector_type(4)));
@@ -82,54 +82,52 @@ typedef unsigned int rts_u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) int32_t rts_lds_i32;
 __device__ __forceinline__ uint32_t rts_lds_addr(int32_t* p) { return (uint32_t)(uintptr_t)(rts_lds_i32*)p; }
 // Loads: q0..q2 <- N planes x, y, z (record + 0 / 16 / 32 + offset), q3..q5 <- F planes (record + 0 / 16 / 32 + 48 - offset),
-// q6 <- the child ids (record + 96); q5, q6 for the lanes at nodes only.  A lane at a leaf reads its record straight through
+// q6 <- the child ids (record + 96), all seven for every lane: a lane at a leaf reads its 112-byte record straight through
 // (offsets 0: nm = 0).
-__device__ __forceinline__ void rts_fetch_record(const void* p, int node, uint32_t nm, float iNx, float iNy, float iNz, rts_u32x4& q0, rts_u32x4& q1, rts_u32x4& q2, rts_u32x4& q3,
+static_assert(offsetof(RtsNode4, loy) == 16 && offsetof(RtsNode4, loz) == 32 && offsetof(RtsNode4, hix) == 48 && offsetof(RtsNode4, child) == 96,
+              "node record offsets hard-coded in the record fetch");
+__device__ __forceinline__ void rts_fetch_record(const void* p, uint32_t nm, float iNx, float iNy, float iNz, rts_u32x4& q0, rts_u32x4& q1, rts_u32x4& q2, rts_u32x4& q3,
                                                  rts_u32x4& q4, rts_u32x4& q5, rts_u32x4& q6)
 {
     // nm = 48 for a lane at a node, 0 at a leaf.  Per axis: off = (sign of iN ? 48 : 0) & nm; N-plane address = record + off,
     // F-plane address = record + (off ^ 48) -- formed INSIDE the block, one axis after the other, in one 64-bit temporary (a
     // load's address registers are read when it issues; its successor may overwrite them): as six 64-bit operands the
     // addresses cost the kernel twelve registers at its tightest point, and spills in the loops around the walk.
-    // (the lanes at nodes -- node >= 0 -- are found and EXEC is parked in VCC, which the allocator never hands out as a
-    // general pair: the kernel has no scalar register to spare; the carry-out of the address additions goes to VCC as well,
-    // before that)
+    // (the carry-out of the address additions goes to VCC, which the allocator never hands out as a general pair: the kernel
+    // has no scalar register to spare)
     unsigned long long t; uint32_t o;
-    asm volatile("v_ashrrev_i32 %8, 31, %12\n\t"
-                 "v_and_b32 %8, %8, %11\n\t"
+    asm volatile("v_ashrrev_i32 %8, 31, %11\n\t"
+                 "v_and_b32 %8, %8, %10\n\t"
                  "v_mad_u64_u32 %7, vcc, %8, 1, %9\n\t"
                  "global_load_dwordx4 %0, %7, off\n\t"
                  "v_xor_b32 %8, 48, %8\n\t"
                  "v_mad_u64_u32 %7, vcc, %8, 1, %9\n\t"
                  "global_load_dwordx4 %3, %7, off\n\t"
-                 "v_ashrrev_i32 %8, 31, %13\n\t"
-                 "v_and_b32 %8, %8, %11\n\t"
+                 "v_ashrrev_i32 %8, 31, %12\n\t"
+                 "v_and_b32 %8, %8, %10\n\t"
                  "v_mad_u64_u32 %7, vcc, %8, 1, %9\n\t"
                  "global_load_dwordx4 %1, %7, off offset:16\n\t"
                  "v_xor_b32 %8, 48, %8\n\t"
                  "v_mad_u64_u32 %7, vcc, %8, 1, %9\n\t"
                  "global_load_dwordx4 %4, %7, off offset:16\n\t"
-                 "v_ashrrev_i32 %8, 31, %14\n\t"
-                 "v_and_b32 %8, %8, %11\n\t"
+                 "v_ashrrev_i32 %8, 31, %13\n\t"
+                 "v_and_b32 %8, %8, %10\n\t"
                  "v_mad_u64_u32 %7, vcc, %8, 1, %9\n\t"
                  "global_load_dwordx4 %2, %7, off offset:32\n\t"
                  "v_xor_b32 %8, 48, %8\n\t"
                  "v_mad_u64_u32 %7, vcc, %8, 1, %9\n\t"
-                 "v_cmp_lt_i32 vcc, -1, %10\n\t"
-                 "s_and_saveexec_b64 vcc, vcc\n\t"
                  "global_load_dwordx4 %5, %7, off offset:32\n\t"
                  "global_load_dwordx4 %6, %9, off offset:96\n\t"
-                 "s_mov_b64 exec, vcc\n\t"
                  "s_waitcnt vmcnt(0)"
-                 : "=&v"(q0), "=&v"(q1), "=&v"(q2), "=&v"(q3), "=&v"(q4), "=&v"(q5), "=&v"(q6), "=&v"(t), "=&v"(o)     // (q5, q6: written for the lanes at nodes only, read by them only)
-                 : "v"(p), "v"(node), "v"(nm), "v"(iNx), "v"(iNy), "v"(iNz) : "memory", "scc", "vcc");
+                 : "=&v"(q0), "=&v"(q1), "=&v"(q2), "=&v"(q3), "=&v"(q4), "=&v"(q5), "=&v"(q6), "=&v"(t), "=&v"(o)
+                 : "v"(p), "v"(nm), "v"(iNx), "v"(iNy), "v"(iNz) : "memory", "vcc");
 }
 
 // The record read straight through (offsets 0 .. 96): the cooperative kernel's fetch.  Its waves are few and wait for memory,
 // not for issue slots; the address arithmetic between the loads of the fetch above spreads them over ~15 instructions, and on
 // BASELINE configs[3] -- 440 MB of records streaming through the L1 -- lines were evicted between the first and the last load
 // of a record: +15 % L2 requests, the cooperative kernel 2.5 -> 2.95 ms (profiles/r03c_c4_ab.log).
-__device__ __forceinline__ void rts_fetch_record_plain(const void* p, int node, rts_u32x4& q0, rts_u32x4& q1, rts_u32x4& q2, rts_u32x4& q3,
+__device__ __forceinline__ void rts_fetch_record_plain(const void* p, rts_u32x4& q0, rts_u32x4& q1, rts_u32x4& q2, rts_u32x4& q3,
                                                        rts_u32x4& q4, rts_u32x4& q5, rts_u32x4& q6)
 {
     asm volatile("global_load_dwordx4 %0, %7, off\n\t"
@@ -137,14 +135,11 @@ __device__ __forceinline__ void rts_fetch_record_plain(const void* p, int node, 
                  "global_load_dwordx4 %2, %7, off offset:32\n\t"
                  "global_load_dwordx4 %3, %7, off offset:48\n\t"
                  "global_load_dwordx4 %4, %7, off offset:64\n\t"
-                 "v_cmp_lt_i32 vcc, -1, %8\n\t"
-                 "s_and_saveexec_b64 vcc, vcc\n\t"
                  "global_load_dwordx4 %5, %7, off offset:80\n\t"
                  "global_load_dwordx4 %6, %7, off offset:96\n\t"
-                 "s_mov_b64 exec, vcc\n\t"
                  "s_waitcnt vmcnt(0)"
                  : "=&v"(q0), "=&v"(q1), "=&v"(q2), "=&v"(q3), "=&v"(q4), "=&v"(q5), "=&v"(q6)
-                 : "v"(p), "v"(node) : "memory", "scc", "vcc");
+                 : "v"(p) : "memory");
 }
 // the constants of a ray by PLANE for that fetch: N* <- the low plane's pair, F* <- the high plane's
 __device__ __forceinline__ RtsSlabRay rts_slab_by_plane(const RtsSlabRay& r)
@@ -190,16 +185,16 @@ __device__ __forceinline__ void rts_walk_step(const RtsTraceArgs& a, int32_t* s_
     const bool deep = __any(sp + 4 > lds_cap);                  // wave-uniform: some lane is about to leave the LDS part
     int below = s_stack[min(sp - 1, lds_cap - 1) * RTS_BLOCK + tid];      // (always an LDS read: a second, global source here made the compiler fold both into one FLAT load)
     if (deep) below = rts_stack_below_spilled(below, sp, lds_cap, a.stack_ovf, a.slab_threads, gtid);
-    // One fetch for both kinds of step: a lane at a node needs its 112-byte record (six planes + child ids),
-    // a lane at a leaf its 80-byte record -- the same five (seven) dwordx4 loads from a per-lane base,
+    // One fetch for both kinds of step: a lane at a node needs 112 bytes of its record (six planes + child ids),
+    // a lane at a leaf its 112-byte record -- the same seven dwordx4 loads from a per-lane base,
     // issued together at the top of the step, so a wave whose lanes are at nodes AND at leaves waits for
     // ONE memory round trip (as if / else bodies the leaf loads could only be issued after the node body).
     const bool at_node = node >= 0;
     // (VERS: a node id IS the index of its record in a.nodes4v -- 8 node + octant; the children a version names carry that version's octant)
     const void* rp = at_node ? static_cast<const void*>(VERS ? a.nodes4v + node : a.nodes4 + node) : static_cast<const void*>(a.leaves + ~node);
     rts_u32x4 q0, q1, q2, q3, q4, q5, q6;
-    if (MODE == RTS_WALK_ROLES) rts_fetch_record(rp, node, at_node ? 48u : 0u, lr.iNx, lr.iNy, lr.iNz, q0, q1, q2, q3, q4, q5, q6);
-    else rts_fetch_record_plain(rp, node, q0, q1, q2, q3, q4, q5, q6);
+    if (MODE == RTS_WALK_ROLES) rts_fetch_record(rp, at_node ? 48u : 0u, lr.iNx, lr.iNy, lr.iNz, q0, q1, q2, q3, q4, q5, q6);
+    else rts_fetch_record_plain(rp, q0, q1, q2, q3, q4, q5, q6);
     if (at_node) {
         // BVH4 node: six dwordx4 planes (lo/hi x,y,z of the four children) + the four child ids
         // (by value through __uint_as_float: __builtin_bit_cast applied to an ext-vector ELEMENT reads element 0)
@@ -228,6 +223,7 @@ __device__ __forceinline__ void rts_walk_step(const RtsTraceArgs& a, int32_t* s_
                 // first: eight more scalar registers live through the step, and 0 / 1 selects + adds for the stack pointer).  Child 0:
                 // node = open ? child 0 : top;  sp += open - 1 (closed: the top of the stack -- the entry just pushed, or `below`).
                 // (the LDS stores of one wave complete in order: the next step's read of `below` sees them)
+                static_assert(RTS_BLOCK * sizeof(int32_t) == 1u << 10, "the push sequence shifts the stack pointer by 10: one stack level is RTS_BLOCK words");
                 uint32_t ad_; int top_, nd_;
                 asm volatile("v_lshl_add_u32 %[ad], %[sp], 10, %[base]\n\t"
                              "ds_write_b32 %[ad], %[c3]\n\t"
@@ -298,9 +294,10 @@ __device__ __forceinline__ void rts_walk_step(const RtsTraceArgs& a, int32_t* s_
         const int leaf = ~node;
         RtsLeafTri L;
 #define RTS_F64(lo, hi) __hiloint2double((int)(hi), (int)(lo))
-        L.p0x = RTS_F64(q0.x, q0.y); L.p0y = RTS_F64(q0.z, q0.w); L.p0z = RTS_F64(q1.x, q1.y); L.p1x = RTS_F64(q1.z, q1.w);
-        L.p1y = RTS_F64(q2.x, q2.y); L.p1z = RTS_F64(q2.z, q2.w); L.p2x = RTS_F64(q3.x, q3.y); L.p2y = RTS_F64(q3.z, q3.w);
-        L.p2z = RTS_F64(q4.x, q4.y); L.prim = q4.z; L.targ = q4.w;
+        L.p0x = RTS_F64(q0.x, q0.y); L.p0y = RTS_F64(q0.z, q0.w); L.p0z = RTS_F64(q1.x, q1.y); L.e0x = RTS_F64(q1.z, q1.w);
+        L.e0y = RTS_F64(q2.x, q2.y); L.e0z = RTS_F64(q2.z, q2.w); L.e1x = RTS_F64(q3.x, q3.y); L.e1y = RTS_F64(q3.z, q3.w);
+        L.e1z = RTS_F64(q4.x, q4.y); L.nx = RTS_F64(q4.z, q4.w); L.ny = RTS_F64(q5.x, q5.y); L.nz = RTS_F64(q5.z, q5.w);
+        L.prim = q6.x; L.targ = q6.y;
 #undef RTS_F64
         if (COUNT) n_tris++;
         const TriHit h = tri_test(L, prev, dir, tmin, RTS_DEFAULT_TMAX);
