@@ -530,6 +530,78 @@ typedef struct RtsDetection {
 int rts_cube_detect(RtsHandle h, const RtsCfarParams* p, const void* device_map, uint32_t n_doppler);
 int rts_cube_detections_get(RtsHandle h, RtsDetection* out, uint32_t capacity, uint32_t* n_out);
 
+/* ---------------------------------------------------------------- tapered slow-time spectrogram (STFT) of the return cube
+ * The short-time Fourier transform over the pulse axis, per range gate bin or summed over a gate: how Doppler changes INSIDE the
+ * interval (rotor and blade flashes, tumbling bodies), where rts_cube_doppler's single rectangular DFT smears it into a band.  A
+ * single frame whose window spans the interval is the TAPERED range-Doppler map: with all bins and complex output it has the layout
+ * rts_cube_detect takes as device_map (n_doppler = n_fft), and with a NULL window, first_pulse 0 and window_len = n_pulses = the
+ * cube's rows it equals rts_cube_doppler's output bit for bit.  Input: the attached cube y[rx][pulse][bin].  The arithmetic is
+ * rts_amd/csrc/rts_stft.h, shared by the kernel (rts_stft.hip) and the host evaluator (the library builds with -ffp-contract=off:
+ * the tree is the contract).
+ *   Frames: only whole frames are formed, n_frames = 1 + (n_pulses - window_len) / hop (integer division); pulses left over at the
+ *     end of the span are not read.  hop > window_len (gaps) and hop < window_len (overlap) are both legal.
+ *   Frame input, for frame f, receiver r and gate bin g (cube bin first_bin + g; n_gate = n_bins, or the cube's n_bins - first_bin
+ *     when n_bins == 0):
+ *       x[i] = w[i] * y[r][first_pulse + f hop + i][first_bin + g]  for i < window_len, computed as (w re, w im);
+ *       x[i] = 0                                                     for window_len <= i < n_fft;
+ *     with window == NULL the samples are taken as they are, with no multiply at all.
+ *   Transform: X[k] = sum_i x[i] e^{-2 pi j k i / n_fft}, by the one fixed tree of rts_cube_doppler's kernel: the samples stored at
+ *     their bit-reversed index, then log2 n_fft radix-2 decimation-in-time stages; stage s = 1 .. log2 n_fft has half = 2^(s-1) and
+ *     for every j < n_fft / 2, with k = j mod half, i0 = (j div half) 2^s + k, i1 = i0 + half, the butterfly
+ *       (u, v) = (x[i0], x[i1]) -> (u + t, u - t),  t = tw v evaluated as (wr xr - wi xi, wr xi + wi xr),
+ *       tw = tw_table[k (n_fft >> s)],  tw_table[m] = (cos, sin)(pi (-2 m / n_fft)) from one sincospi(-2.0 * m / n_fft), m < n_fft / 2.
+ *   Output (row-major): complex128 [n_rx][n_frames][n_fft][n_gate];  with RTS_STFT_POWER f64 re re + im im of the same shape;  with
+ *     RTS_STFT_POWER | RTS_STFT_SUM_BINS f64 [n_rx][n_frames][n_fft], the powers summed over the gate in ONE order whatever the launch
+ *     shape: the gate is cut into tiles of RTS_STFT_BIN_TILE consecutive gate bins starting at gate bin 0; inside a tile the powers
+ *     are added in ascending bin order, the first one the start value; then the tile sums are added in ascending tile order, the
+ *     first again the start value.  No atomics: bit-identical from run to run.
+ *   Axes: frame f is centred on pulse first_pulse + f hop + (window_len - 1) / 2.0.  Row k is Doppler k' / (n_fft pri), k' = k wrapped
+ *     into [-n_fft / 2, n_fft / 2).  Sign as rts_cube_detect's: with the cube's phase -2 pi fc tau a CLOSING range (tau falling from
+ *     pulse to pulse) gives a POSITIVE Doppler.
+ * rts_cube_spectrogram is enqueued on the handle's stream and never waits for the device's earlier work (it waits only for the copy
+ * of the PREVIOUS call's window out of the handle's pinned staging block); the caller's window array is free on return.  *n_frames_out
+ * (may be NULL) is set on success.  device_out: caller-owned device memory of the output's size, 16-byte aligned, or NULL:
+ * library-owned, alive until the next spectrogram of another size, rts_cube_attach or rts_destroy.  rts_cube_spectrogram_get
+ * synchronises and copies the library-owned output (2 doubles per complex element); RTS_ERR_INVALID after an rts_cube_attach or with
+ * no library-owned spectrogram, RTS_ERR_CAPACITY when capacity_doubles is too small.
+ * Memory: the complex output is 16 n_rx n_frames n_fft n_gate bytes (the power form half of it); RTS_STFT_SUM_BINS writes
+ * 8 n_rx n_frames n_fft bytes and, with more than one tile, keeps ceil(n_gate / 8) times that in a scratch buffer of the handle.
+ * RTS_ERR_INVALID, the message naming the field: no cube attached; NULL p; nonzero reserved fields; unknown flags; RTS_STFT_SUM_BINS
+ * without RTS_STFT_POWER; n_fft not a power of two in [2, RTS_STFT_MAX_FFT]; window_len 0, > n_fft or > n_pulses; hop 0; n_pulses 0
+ * or first_pulse + n_pulses beyond the cube's rows; first_bin >= the cube's n_bins, or first_bin + n_bins beyond it; a non-finite
+ * window value; a shape the launch grid cannot take: more than RTS_STFT_MAX_RX receivers (n_rx), or n_frames times the number of
+ * workgroups per frame (ceil(n_gate / BT), BT = 8 up to n_fft 1024, 4 at 2048, 2 at 4096; ceil(n_gate / 8) with RTS_STFT_SUM_BINS)
+ * above RTS_STFT_MAX_GRID_X.
+ * rts_stft_eval: pure host, no device.  The same validation (q in place of the attached cube) and the same rts_stft.h functions on a
+ * host cube [n_rx][q->n_pulses][q->n_bins] (interleaved re / im) -> out in the layout above.  A refused call leaves out untouched.
+ * rts_window_make: pure host.  The symmetric windows w[i] = a0 - a1 cos(2 pi i / (n - 1)) + a2 cos(4 pi i / (n - 1)), i < n, with
+ * (a0, a1, a2) = (1, 0, 0) RECT, (0.5, 0.5, 0) HANN, (0.54, 0.46, 0) HAMMING, (0.42, 0.5, 0.08) BLACKMAN; n == 1 gives 1.  The second
+ * half mirrors the first (w[n - 1 - i] = w[i] exactly).  RTS_ERR_INVALID for n == 0, an unknown kind or a NULL out.  A window always
+ * reaches the device as a host array copied by the call, so kernel and evaluator multiply by the same bits. */
+#define RTS_STFT_POWER     1u   /* output re*re + im*im (real f64) instead of complex128            */
+#define RTS_STFT_SUM_BINS  2u   /* needs RTS_STFT_POWER: one value per (rx, frame, k), summed over the gate */
+#define RTS_STFT_MAX_FFT   4096u
+#define RTS_STFT_BIN_TILE  8u   /* the summation order of RTS_STFT_SUM_BINS, see above             */
+#define RTS_STFT_MAX_RX    65535u        /* the launch grid: receivers                               */
+#define RTS_STFT_MAX_GRID_X 2147483647u  /* the launch grid: frames x workgroups per frame           */
+typedef struct RtsStftParams {
+    uint32_t first_pulse, n_pulses;   /* cube rows first_pulse .. first_pulse + n_pulses - 1                 */
+    uint32_t window_len, hop;         /* pulses per frame (1 .. n_fft, <= n_pulses); pulses between frame starts (>= 1) */
+    uint32_t n_fft;                   /* power of two in [2, RTS_STFT_MAX_FFT], >= window_len                */
+    uint32_t first_bin, n_bins;       /* range gate; n_bins == 0: all bins from first_bin to the cube's last */
+    uint32_t flags;
+    const double* window;             /* [window_len] host, finite; NULL: rectangular (no multiply at all)   */
+    uint64_t reserved[2];             /* 0 */
+} RtsStftParams;
+int rts_cube_spectrogram(RtsHandle h, const RtsStftParams* p, void* device_out, uint32_t* n_frames_out);
+int rts_cube_spectrogram_get(RtsHandle h, double* host_out, uint64_t capacity_doubles);
+int rts_stft_eval(const RtsCubeParams* q, const double* cube, const RtsStftParams* p, double* out, uint32_t* n_frames_out); /* pure host */
+#define RTS_WINDOW_RECT 0u
+#define RTS_WINDOW_HANN 1u
+#define RTS_WINDOW_HAMMING 2u
+#define RTS_WINDOW_BLACKMAN 3u
+int rts_window_make(uint32_t kind, uint32_t n, double* out);   /* pure host */
+
 /* ---------------------------------------------------------------- backprojection imaging (SAR / ISAR) of the return cube
  * A derived product like the cube itself: time-domain backprojection of a coherent interval onto a planar
  * pixel grid -- exact for any track, any bistatic geometry and any target motion, where the slow-time DFT focuses only while a

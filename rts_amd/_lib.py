@@ -132,6 +132,20 @@ class RtsImageParams(C.Structure):
 assert C.sizeof(RtsImageParams) == 152
 
 
+RTS_STFT_POWER, RTS_STFT_SUM_BINS = 1, 2
+RTS_STFT_MAX_FFT, RTS_STFT_BIN_TILE, RTS_STFT_MAX_RX, RTS_STFT_MAX_GRID_X = 4096, 8, 65535, 2147483647
+RTS_WINDOW_RECT, RTS_WINDOW_HANN, RTS_WINDOW_HAMMING, RTS_WINDOW_BLACKMAN = 0, 1, 2, 3
+
+
+class RtsStftParams(C.Structure):
+    _fields_ = [("first_pulse", C.c_uint32), ("n_pulses", C.c_uint32), ("window_len", C.c_uint32), ("hop", C.c_uint32),
+                ("n_fft", C.c_uint32), ("first_bin", C.c_uint32), ("n_bins", C.c_uint32), ("flags", C.c_uint32),
+                ("window", C.c_void_p), ("reserved", C.c_uint64 * 2)]
+
+
+assert C.sizeof(RtsStftParams) == 56
+
+
 class RtsSceneInfo(C.Structure):
     _fields_ = [("n_targets", C.c_uint32), ("n_prims", C.c_uint32), ("n_nodes", C.c_uint32), ("n_leaves", C.c_uint32),
                 ("handles_sharing", C.c_uint32), ("builder", C.c_uint32), ("build_ms", C.c_double),
@@ -218,7 +232,8 @@ EXPORTS = ["rts_create", "rts_destroy", "rts_last_error", "rts_device_count", "r
            "rts_set_patterns", "rts_finalise_patterns", "rts_trace_pulse_end_patterns", "rts_pattern_eval",
            "rts_cube_set_waveform", "rts_cube_render", "rts_cube_compress", "rts_waveform_eval",
            "rts_cube_add_noise", "rts_noise_eval", "rts_cube_detect", "rts_cube_detections_get",
-           "rts_cube_backproject", "rts_cube_image_get", "rts_backproject_eval"]
+           "rts_cube_backproject", "rts_cube_image_get", "rts_backproject_eval",
+           "rts_cube_spectrogram", "rts_cube_spectrogram_get", "rts_stft_eval", "rts_window_make"]
 
 
 def lib():
@@ -294,6 +309,10 @@ def lib():
         "rts_cube_backproject": [vp, C.POINTER(RtsImageParams), vp],
         "rts_cube_image_get": [vp, vp, u64],
         "rts_backproject_eval": [C.POINTER(RtsCubeParams), vp, C.POINTER(RtsImageParams), vp],
+        "rts_cube_spectrogram": [vp, C.POINTER(RtsStftParams), vp, C.POINTER(u32)],
+        "rts_cube_spectrogram_get": [vp, vp, u64],
+        "rts_stft_eval": [C.POINTER(RtsCubeParams), vp, C.POINTER(RtsStftParams), vp, C.POINTER(u32)],
+        "rts_window_make": [u32, u32, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name, None)

@@ -258,6 +258,70 @@ def image_frame(positions, motions):
     return out
 
 
+# ------------------------------------------------------------------------------- slow-time spectrogram (rts_stft.h)
+_WINDOW_KINDS = {"rect": L.RTS_WINDOW_RECT, "hann": L.RTS_WINDOW_HANN, "hamming": L.RTS_WINDOW_HAMMING, "blackman": L.RTS_WINDOW_BLACKMAN}
+
+
+def window(kind, n):
+    """rts_window_make (pure host): the symmetric window "rect", "hann", "hamming" or "blackman" (or an RTS_WINDOW_* value) of n points"""
+    out = np.zeros(max(int(n), 1))
+    check(L.lib().rts_window_make(_WINDOW_KINDS.get(kind, kind), int(n), ptr(out)))
+    return out
+
+
+def _stft_params(window_len, hop, n_fft, window, first, count, first_bin, n_bins, power, sum_bins, n_pulses_cube):
+    """RtsStftParams and the window array it points to (keep it alive for the call); count None: to the cube's last row"""
+    w = None if window is None else np.ascontiguousarray(np.asarray(window, np.float64).ravel())
+    if w is not None and len(w) != int(window_len):
+        raise ValueError("spectrogram: a window of %d values for window_len = %d" % (len(w), window_len))
+    p = L.RtsStftParams()
+    p.first_pulse, p.n_pulses = int(first), int(n_pulses_cube - first if count is None else count)
+    p.window_len, p.hop, p.n_fft, p.first_bin, p.n_bins = int(window_len), int(hop), int(n_fft), int(first_bin), int(n_bins)
+    p.flags = (L.RTS_STFT_POWER if power else 0) | (L.RTS_STFT_SUM_BINS if sum_bins else 0)
+    p.window = ptr(w)
+    return p, w
+
+
+def _stft_shape(n_rx, n_frames, n_fft, n_gate, power, sum_bins):
+    """(shape, dtype) of a spectrogram in the layout of include/rts_amd.h"""
+    if sum_bins:
+        return (n_rx, n_frames, n_fft), np.float64
+    return (n_rx, n_frames, n_fft, n_gate), np.float64 if power else np.complex128
+
+
+def stft_frames(n_pulses, window_len, hop):
+    """the number of whole frames of a span of n_pulses pulses"""
+    return 1 + (int(n_pulses) - int(window_len)) // int(hop)
+
+
+def stft_eval(cube, window_len, hop, n_fft, window=None, first=0, count=None, first_bin=0, n_bins=0, power=False, sum_bins=False):
+    """rts_stft_eval (pure host): the spectrogram of a host cube [n_rx][n_pulses][n_bins] (complex): complex
+    [n_rx][n_frames][n_fft][n_gate], float64 of that shape with power, float64 [n_rx][n_frames][n_fft] with power and sum_bins"""
+    cube = np.ascontiguousarray(np.asarray(cube, np.complex128))
+    n_rx, n_p, nb = cube.shape
+    q = L.RtsCubeParams(n_rx, n_p, nb, 0, 0.0, 1.0)
+    p, keep = _stft_params(window_len, hop, n_fft, window, first, count, first_bin, n_bins, power, sum_bins, n_p)
+    n_gate = p.n_bins if p.n_bins else max(nb - p.first_bin, 0)
+    n_frames = max(stft_frames(p.n_pulses, p.window_len, max(p.hop, 1)), 0)
+    shape, dtype = _stft_shape(n_rx, n_frames, p.n_fft, n_gate, power, sum_bins)
+    out = np.zeros(shape, dtype)
+    nf = C.c_uint32(0)
+    check(L.lib().rts_stft_eval(C.byref(q), ptr(cube.view(np.float64)), C.byref(p), ptr(out), C.byref(nf)))
+    assert nf.value == n_frames
+    return out
+
+
+def spectrogram_axes(window_len, hop, n_fft, n_pulses, pri, first=0):
+    """the axes of a spectrogram of pulses first .. first + n_pulses - 1: (the pulse index each frame is centred on, float64
+    [n_frames]; the Doppler of each row in Hz, float64 [n_fft], row k at k' / (n_fft pri) with k' = k wrapped into
+    [-n_fft / 2, n_fft / 2): a closing range is a positive Doppler)"""
+    f = np.arange(stft_frames(n_pulses, window_len, hop), dtype=np.float64)
+    centres = first + f * hop + (window_len - 1) / 2.0
+    k = np.arange(n_fft)
+    k = np.where(k >= n_fft // 2, k - n_fft, k).astype(np.float64)
+    return centres, k / (n_fft * float(pri))
+
+
 def device_count():
     n = C.c_int(0)
     rc = L.lib().rts_device_count(C.byref(n))
@@ -615,6 +679,29 @@ class Tracer:
         out = np.zeros(shape + (2,), np.float64)
         check(L.lib().rts_cube_image_get(self.h, ptr(out), out.size))
         return out[..., 0] + 1j * out[..., 1]
+
+    def cube_spectrogram(self, window_len, hop, n_fft, window=None, first=0, count=None, first_bin=0, n_bins=0, power=False, sum_bins=False,
+                         device_ptr=None, fetch=True):
+        """rts_cube_spectrogram: the short-time Fourier transform over the pulse axis of the attached cube's rows first .. first + count - 1
+        (default: to the last), frames of window_len pulses every hop pulses, tapered by window (an array of window_len values, or
+        None), zero-padded to n_fft, for the gate first_bin .. first_bin + n_bins - 1 (n_bins 0: to the last bin).  Into a caller
+        device tensor (device_ptr; nothing is fetched) or the library's output, returned when fetch: complex
+        [n_rx][n_frames][n_fft][n_gate], float64 of that shape with power, float64 [n_rx][n_frames][n_fft] with power and sum_bins"""
+        n_rx, n_p, nb = self._cube_shape
+        p, keep = _stft_params(window_len, hop, n_fft, window, first, count, first_bin, n_bins, power, sum_bins, n_p)
+        nf = C.c_uint32(0)
+        check(L.lib().rts_cube_spectrogram(self.h, C.byref(p), C.c_void_p(device_ptr) if device_ptr else None, C.byref(nf)))
+        if device_ptr:
+            return None
+        self._stft_shape = _stft_shape(n_rx, nf.value, p.n_fft, p.n_bins if p.n_bins else nb - p.first_bin, power, sum_bins)
+        return self.spectrogram() if fetch else None
+
+    def spectrogram(self):
+        """rts_cube_spectrogram_get: the library-owned output of the last cube_spectrogram"""
+        shape, dtype = getattr(self, "_stft_shape", None) or ((1, 1, 2), np.float64)
+        out = np.zeros(shape, dtype)
+        check(L.lib().rts_cube_spectrogram_get(self.h, ptr(out), out.size * (2 if dtype is np.complex128 else 1)))
+        return out
 
     def cube(self):
         out = np.zeros(self._cube_shape + (2,), np.float64)

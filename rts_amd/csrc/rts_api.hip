@@ -163,7 +163,7 @@ void rts_hist_unref(RtsTileHist* h) { if (h && --h->refs == 0) delete h; }
 void rts_gate_unref(RtsGate* g) { if (g && --g->refs == 0) { if (g->tstream) (void)hipStreamDestroy(g->tstream); delete g; } }
 
 // The teardown of a handle, once.  After this body the members destroy themselves in reverse order of declaration: every DevBuf
-// (hipFree) and the pinned blocks pin, pin_rx, pin_pat, pin_img and the mirror's (hipHostFree).  That is safe because no work can read
+// (hipFree) and the pinned blocks pin, pin_rx, pin_pat, pin_img, pin_stft and the mirror's (hipHostFree).  That is safe because no work can read
 // them any more: `stream` and `cstream` have been drained, the trace stream has been drained (it may live on with the other
 // handles of the link group, but carries no work of this handle), and nothing is enqueued on a handle's behalf anywhere else.
 RtsContext::~RtsContext()
@@ -175,6 +175,7 @@ RtsContext::~RtsContext()
     rts_gate_unref(gate); gate = nullptr;
     if (ev_pat) (void)hipEventDestroy(ev_pat);
     if (ev_img) (void)hipEventDestroy(ev_img);
+    if (ev_stft) (void)hipEventDestroy(ev_stft);
     for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ev_coop) if (e) (void)hipEventDestroy(e);
     if (cstream) { (void)hipStreamSynchronize(cstream); (void)hipStreamDestroy(cstream); }
@@ -1625,6 +1626,7 @@ extern "C" int rts_cube_attach(RtsHandle c, const RtsCubeParams* p, void* device
     c->cube_set = true;
     c->det_valid = false; c->doppler_fresh = false;         // (a detection list, and a map rts_cube_detect may take, belong to the cube they were made from)
     c->img_valid = false;                                   // (... and so does an image)
+    c->stft_valid = false;                                  // (... and a spectrogram)
     return RTS_OK;
 }
 
@@ -1818,6 +1820,90 @@ extern "C" int rts_cube_detections_get(RtsHandle c, RtsDetection* out, uint32_t 
     if (n > capacity) n = capacity;
     if (n) RTS_HIP(hipMemcpy(out, c->d_det.p, sizeof(RtsDetection) * n, hipMemcpyDeviceToHost));
     if (n < total) { rts_set_error("rts_cube_detections_get: %u of %u detections copied (max_detections %u, capacity %u)", n, total, c->det_max, capacity); return RTS_ERR_CAPACITY; }
+    return RTS_OK;
+}
+
+// ------------------------------------------------------------------------------------- tapered slow-time spectrogram
+// (rts_amd.h: RtsStftParams; the tree and the launch plan are rts_stft.h, shared by the host export and the kernel, rts_stft.hip)
+static int rts_stft_check(const RtsStftParams* p, const RtsCubeParams& q, const char* who, RtsStftPlan* plan)
+{
+    if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
+    if (p->reserved[0] || p->reserved[1]) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
+    if (p->flags & ~(RTS_STFT_POWER | RTS_STFT_SUM_BINS)) { rts_set_error("%s: unknown flags 0x%x", who, p->flags); return RTS_ERR_INVALID; }
+    if ((p->flags & RTS_STFT_SUM_BINS) && !(p->flags & RTS_STFT_POWER)) { rts_set_error("%s: flags: RTS_STFT_SUM_BINS needs RTS_STFT_POWER", who); return RTS_ERR_INVALID; }
+    if (p->n_fft < 2u || p->n_fft > RTS_STFT_MAX_FFT || (p->n_fft & (p->n_fft - 1u)) != 0u) { rts_set_error("%s: n_fft = %u must be a power of two in [2, %u]", who, p->n_fft, RTS_STFT_MAX_FFT); return RTS_ERR_INVALID; }
+    if (p->n_pulses == 0 || p->first_pulse >= q.n_pulses || p->n_pulses > q.n_pulses - p->first_pulse) { rts_set_error("%s: first_pulse = %u, n_pulses = %u: at least one pulse, inside the cube's %u rows", who, p->first_pulse, p->n_pulses, q.n_pulses); return RTS_ERR_INVALID; }
+    if (p->window_len == 0 || p->window_len > p->n_fft || p->window_len > p->n_pulses) { rts_set_error("%s: window_len = %u (1 .. n_fft = %u, <= n_pulses = %u)", who, p->window_len, p->n_fft, p->n_pulses); return RTS_ERR_INVALID; }
+    if (p->hop == 0) { rts_set_error("%s: hop = 0 (>= 1)", who); return RTS_ERR_INVALID; }
+    if (p->first_bin >= q.n_bins || p->n_bins > q.n_bins - p->first_bin) { rts_set_error("%s: first_bin = %u, n_bins = %u: inside the cube's %u bins", who, p->first_bin, p->n_bins, q.n_bins); return RTS_ERR_INVALID; }
+    if (p->window) for (uint32_t i = 0; i < p->window_len; i++) if (!std::isfinite(p->window[i])) { rts_set_error("%s: window[%u] is not finite", who, i); return RTS_ERR_INVALID; }
+    const uint32_t n_gate = p->n_bins ? p->n_bins : q.n_bins - p->first_bin;
+    *plan = rts_stft_plan(q.n_rx, p->n_pulses, p->window_len, p->hop, p->n_fft, n_gate, p->flags);
+    if (!plan->supported) {
+        if (q.n_rx > RTS_STFT_MAX_RX) rts_set_error("%s: n_rx = %u receivers: more than %u (the launch grid)", who, q.n_rx, RTS_STFT_MAX_RX);
+        else rts_set_error("%s: n_frames = %u frames x %u workgroups per frame (hop, n_bins): more than %u (the launch grid)", who, plan->n_frames, plan->tiles, RTS_STFT_MAX_GRID_X);
+        return RTS_ERR_INVALID;
+    }
+    return RTS_OK;
+}
+
+extern "C" int rts_window_make(uint32_t kind, uint32_t n, double* out)
+{
+    if (n == 0) { rts_set_error("rts_window_make: n = 0"); return RTS_ERR_INVALID; }
+    if (kind > RTS_WINDOW_BLACKMAN) { rts_set_error("rts_window_make: unknown kind %u", kind); return RTS_ERR_INVALID; }
+    if (!out) { rts_set_error("rts_window_make: null output array"); return RTS_ERR_INVALID; }
+    rts_stft_window_host(kind, n, out);
+    return RTS_OK;
+}
+
+extern "C" int rts_stft_eval(const RtsCubeParams* q, const double* cube, const RtsStftParams* p, double* out, uint32_t* n_frames_out)
+{
+    if (!q || q->n_rx == 0 || q->n_pulses == 0 || q->n_bins == 0) { rts_set_error("rts_stft_eval: bad cube parameters"); return RTS_ERR_INVALID; }
+    RtsStftPlan plan;
+    int rc = rts_stft_check(p, *q, "rts_stft_eval", &plan); if (rc != RTS_OK) return rc;
+    if (!cube || !out) { rts_set_error("rts_stft_eval: null cube or output array"); return RTS_ERR_INVALID; }
+    std::vector<double> work(4 * (size_t)p->n_fft);
+    rts_stft_eval_host(q, cube, p, plan, out, work.data());
+    if (n_frames_out) *n_frames_out = plan.n_frames;
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_spectrogram(RtsHandle c, const RtsStftParams* p, void* device_out, uint32_t* n_frames_out)
+{
+    CHECK_HANDLE(c);
+    if (!c->cube_set) { rts_set_error("rts_cube_spectrogram: no cube (call rts_cube_attach first)"); return RTS_ERR_INVALID; }
+    const RtsCubeParams& q = c->cube_params;
+    RtsStftPlan plan;
+    int rc = rts_stft_check(p, q, "rts_cube_spectrogram", &plan); if (rc != RTS_OK) return rc;
+    if ((uintptr_t)device_out & 15u) { rts_set_error("rts_cube_spectrogram: device_out is not 16-byte aligned"); return RTS_ERR_INVALID; }
+    CHECK_CLOSED(c);
+    double* out = (double*)device_out;
+    if (!out) { RTS_HIP(c->d_stft_own.reserve(plan.out_doubles)); out = c->d_stft_own.p; }
+    // the window -> pinned staging -> the device, on the stream
+    const double* win = nullptr;
+    if (p->window) {
+        const size_t n = p->window_len;
+        if (c->ev_stft_armed) { RTS_HIP(hipEventSynchronize(c->ev_stft)); c->ev_stft_armed = false; }
+        if (c->pin_stft.cap < n) RTS_HIP(c->pin_stft.reserve(RTS_STFT_MAX_FFT, false));
+        if (!c->ev_stft) RTS_HIP(hipEventCreateWithFlags(&c->ev_stft, hipEventDisableTiming));
+        RTS_HIP(c->d_stft_win.reserve(RTS_STFT_MAX_FFT));
+        memcpy(c->pin_stft.p, p->window, sizeof(double) * n);
+        RTS_HIP(hipMemcpyAsync(c->d_stft_win.p, c->pin_stft.p, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+        RTS_HIP(hipEventRecord(c->ev_stft, c->stream)); c->ev_stft_armed = true;
+        win = c->d_stft_win.p;
+    }
+    if (!device_out) { c->stft_doubles = plan.out_doubles; c->stft_valid = true; }
+    if (n_frames_out) *n_frames_out = plan.n_frames;
+    return rts_cube_stft_device(c, *p, plan, win, out);
+}
+
+extern "C" int rts_cube_spectrogram_get(RtsHandle c, double* host_out, uint64_t capacity_doubles)
+{
+    CHECK_HANDLE(c);
+    if (!c->cube_set || !c->stft_valid || !host_out) { rts_set_error("rts_cube_spectrogram_get: no library-owned spectrogram (rts_cube_spectrogram with device_out NULL; a spectrogram ends at rts_cube_attach) / null output"); return RTS_ERR_INVALID; }
+    if (capacity_doubles < c->stft_doubles) { rts_set_error("rts_cube_spectrogram_get: capacity too small"); return RTS_ERR_CAPACITY; }
+    RTS_HIP(hipStreamSynchronize(c->stream));
+    RTS_HIP(hipMemcpy(host_out, c->d_stft_own.p, sizeof(double) * c->stft_doubles, hipMemcpyDeviceToHost));
     return RTS_OK;
 }
 

@@ -12,6 +12,7 @@
 #include "rts_waveform.h"
 #include "rts_noise.h"
 #include "rts_image.h"            // the arithmetic of a backprojected pixel and the host-only plan of its launch
+#include "rts_stft.h"             // the tree of the slow-time spectrogram and the host-only plan of its launch
 #include "rts_owned.h"            // DevBuf, PinBuf: device and pinned host memory that frees itself
 #include "rts_launch_plan.h"      // RTS_BLOCK, RTS_WTILE, RTS_COOP_GROUP, RTS_STACK_OVF and the host arithmetic of a launch
 #include "rts_post_plan.h"        // RTS_SMALL_CAP32 / 64, RTS_AGG_TILE and the host arithmetic of the post-processing
@@ -382,6 +383,11 @@ struct RtsContext {
     DevBuf<double> d_image_own, d_img_geo, d_img_scratch; uint32_t img_nx = 0, img_ny = 0; bool img_valid = false;
     PinBuf<double> pin_img; hipEvent_t ev_img = nullptr; bool ev_img_armed = false;
     uint32_t img_split_below = RTS_IMAGE_SPLIT_BELOW;      // RTS_IMAGE_SPLIT_BELOW: workgroups below which the pulse chunks go on the grid (tests: 0 = never, 65536 = whenever there are two chunks)
+    // spectrogram (rts_cube_spectrogram, rts_stft.hip): the library-owned output and its size in doubles; stft_valid: it holds a spectrogram
+    // of the attached cube, for rts_cube_spectrogram_get (a caller-owned output leaves it alone); the call's window goes through a pinned
+    // staging block that is rewritten only after the copy of the previous call's has run (ev_stft); the tile sums of RTS_STFT_SUM_BINS
+    DevBuf<double> d_stft_own, d_stft_win, d_stft_part; size_t stft_doubles = 0; bool stft_valid = false;
+    PinBuf<double> pin_stft; hipEvent_t ev_stft = nullptr; bool ev_stft_armed = false;
     bool doppler_fresh = false;         // rts_cube_doppler ran on the attached cube (rts_cube_detect without a map takes its output)
     bool agg_delay_in = true;           // rts_aggregate_device: the delay / phase arrays carry initial sums (rs::kernel_wrapper's in-out arguments); false: they start at zero
     int64_t agg_base_local = 0;         // pathMatch value of received ray i after rts_aggregate = agg_base_local + i
@@ -430,6 +436,7 @@ int rts_cube_render_device(RtsContext* c, uint32_t pulse_index, bool paths, bool
 int rts_cube_compress_device(RtsContext* c, uint32_t first_pulse, uint32_t n_pulses);
 int rts_cube_noise_device(RtsContext* c, uint32_t first_pulse, uint32_t n_pulses, double sigma, uint64_t seed);          // rts_detect.hip
 int rts_cube_detect_device(RtsContext* c, const RtsCfarParams& p, const double* map, uint32_t n_doppler, uint32_t max_det);
+int rts_cube_stft_device(RtsContext* c, const RtsStftParams& p, const RtsStftPlan& plan, const double* window, double* out);      // rts_stft.hip
 int rts_cube_backproject_device(RtsContext* c, const RtsImageParams& p, const RtsImagePlan& plan, const double* geo, double* out);      // rts_image.hip
 int rts_post_finalise(RtsContext* c, const double* rcs_host, double wl, double gt, double gr, double carrier, double cspeed);
 int rts_pattern_pulse_upload(RtsContext* c, const RtsSpecParams& q, RtsPatArgs* out);      // the pulse's receiver rows -> the device, on c->stream
