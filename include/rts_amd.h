@@ -405,7 +405,9 @@ int rts_cube_accumulate_paths(RtsHandle h, uint32_t pulse_index);
 /* Slow-time (Doppler) transform: for every receiver and range bin the n_fft-point DFT over the pulse axis, n_fft a power
  * of two with n_pulses <= n_fft <= 4096 (pulses beyond n_pulses count as zeros):
  *     out[rx][k][bin] = sum_p cube[rx][p][bin] e^{-2 pi j k p / n_fft}          (complex128, [n_rx][n_fft][n_bins])
- * device_out: caller-owned device memory of 2 n_rx n_fft n_bins doubles, or NULL: library-owned (rts_cube_doppler_get). */
+ * device_out: caller-owned device memory of 2 n_rx n_fft n_bins doubles, or NULL: library-owned (rts_cube_doppler_get).
+ * The map lives until the next rts_cube_doppler, rts_cube_attach or rts_destroy: after rts_cube_attach, rts_cube_doppler_get
+ * returns RTS_ERR_INVALID and rts_cube_detect without a map of its own has none. */
 int rts_cube_doppler(RtsHandle h, uint32_t n_fft, void* device_out);
 int rts_cube_doppler_get(RtsHandle h, double* host_out, uint64_t capacity_doubles);
 

@@ -1,4 +1,4 @@
-// rts_api.hip -- host side of librts_amd.so: the C-ABI of include/rts_amd.h.
+// rts_api.hip -- host side of librts_amd.so: the C-ABI of include/rts_amd.h but for the cube (rts_cube_api.hip; rts_cube_reduce is here).
 //
 // Mirrors the host driver rs::RTS of the reference (ray_tracer.cpp:507-1364) from the point
 // where it owns device state: context set-up, per-pulse scene placement, launch, read-back,
@@ -163,7 +163,8 @@ void rts_hist_unref(RtsTileHist* h) { if (h && --h->refs == 0) delete h; }
 void rts_gate_unref(RtsGate* g) { if (g && --g->refs == 0) { if (g->tstream) (void)hipStreamDestroy(g->tstream); delete g; } }
 
 // The teardown of a handle, once.  After this body the members destroy themselves in reverse order of declaration: every DevBuf
-// (hipFree) and the pinned blocks pin, pin_rx, pin_pat, pin_img, pin_stft and the mirror's (hipHostFree).  That is safe because no work can read
+// (hipFree), the pinned blocks pin, pin_rx and the mirror's (hipHostFree) and the three staged uploads (pat_rx, cube.img_geo, cube.stft_win:
+// their event, then their blocks).  That is safe because no work can read
 // them any more: `stream` and `cstream` have been drained, the trace stream has been drained (it may live on with the other
 // handles of the link group, but carries no work of this handle), and nothing is enqueued on a handle's behalf anywhere else.
 RtsContext::~RtsContext()
@@ -173,9 +174,6 @@ RtsContext::~RtsContext()
     rts_hist_unref(hist); hist = nullptr;
     if (tstream) (void)hipStreamSynchronize(tstream);
     rts_gate_unref(gate); gate = nullptr;
-    if (ev_pat) (void)hipEventDestroy(ev_pat);
-    if (ev_img) (void)hipEventDestroy(ev_img);
-    if (ev_stft) (void)hipEventDestroy(ev_stft);
     for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ev_coop) if (e) (void)hipEventDestroy(e);
     if (cstream) { (void)hipStreamSynchronize(cstream); (void)hipStreamDestroy(cstream); }
@@ -241,7 +239,7 @@ extern "C" int rts_create(const RtsParams* p, RtsHandle* out)
     { const char* e = getenv("RTS_SPECULATE"); if (e) c->spec_enabled = atoi(e) != 0; }
     { const char* e = getenv("RTS_POST_SMALL"); if (e) c->post_small = atoi(e) != 0; }
     { const char* e = getenv("RTS_POST_ONE_MAX"); if (e) c->post_one_max = (uint64_t)strtoull(e, nullptr, 10); }
-    { const char* e = getenv("RTS_IMAGE_SPLIT_BELOW"); if (e) c->img_split_below = (uint32_t)std::min(65536, std::max(0, atoi(e))); }
+    { const char* e = getenv("RTS_IMAGE_SPLIT_BELOW"); if (e) c->cube.img_split_below = (uint32_t)std::min(65536, std::max(0, atoi(e))); }
     { const char* e = getenv("RTS_POST_PRIO"); if (e) c->post_prio = (uint32_t)std::min(3, std::max(0, atoi(e))); }
     { const char* e = getenv("RTS_COOP_STEPS"); if (e) c->coop_walk_steps = (uint32_t)std::max(0, atoi(e)); }
     { const char* e = getenv("RTS_COOP_STEPS_LO"); if (e) c->coop_walk_steps_lo = (uint32_t)std::max(0, atoi(e)); }
@@ -286,12 +284,6 @@ extern "C" int rts_destroy(RtsHandle c)
     delete c;
     return RTS_OK;
 }
-
-#define CHECK_HANDLE(c) do { if (!(c)) { rts_set_error("null handle"); return RTS_ERR_INVALID; } RTS_HIP(hipSetDevice((c)->device)); } while (0)
-// entry points that consume a pulse's results complete a pulse that was begun but not yet ended
-static int rts_spec_resolve(RtsContext* c);
-#define CHECK_CLOSED(c) do { if ((c)->pulse_open) { int rc_ = rts_trace_pulse_end(c); if (rc_ != RTS_OK) return rc_; } \
-                             if ((c)->spec_pending) { int rc_ = rts_spec_resolve(c); if (rc_ != RTS_OK) return rc_; } } while (0)
 
 extern "C" int rts_link_handles(RtsHandle a, RtsHandle b)
 {
@@ -1260,7 +1252,7 @@ static int rts_post_chain(RtsContext* c, bool ordered = false)      // ordered: 
     return rc;
 }
 
-static int rts_spec_resolve(RtsContext* c)
+int rts_spec_resolve(RtsContext* c)
 {
     if (!c->spec_pending) return RTS_OK;
     c->spec_pending = false; g_open_pulses[c->device & 63]--;
@@ -1285,7 +1277,7 @@ extern "C" int rts_trace_pulse_end_uniform(RtsHandle c, const double* rcs_per_ta
 {
     CHECK_HANDLE(c);
     if (!c->pulse_open) { rts_set_error("rts_trace_pulse_end_uniform: no pulse in flight on this handle"); return RTS_ERR_INVALID; }
-    if (cube_pulse >= 0 && (!c->cube_set || (uint32_t)cube_pulse >= c->cube_params.n_pulses)) { rts_set_error("rts_trace_pulse_end_uniform: no cube attached, or pulse %d outside it", cube_pulse); return RTS_ERR_INVALID; }
+    if (cube_pulse >= 0 && (!c->cube.set || (uint32_t)cube_pulse >= c->cube.params.n_pulses)) { rts_set_error("rts_trace_pulse_end_uniform: no cube attached, or pulse %d outside it", cube_pulse); return RTS_ERR_INVALID; }
     RtsSpecParams& q = c->spec;
     const size_t nt = c->scene->meshes.size();
     q.rcs.assign(nt + 1, 1.0); if (rcs_per_target) for (size_t t = 0; t < nt; t++) q.rcs[t] = rcs_per_target[t];
@@ -1460,7 +1452,7 @@ extern "C" int rts_trace_pulse_end_patterns(RtsHandle c, const RtsPatternPulse* 
 {
     CHECK_HANDLE(c);
     if (!c->pulse_open) { rts_set_error("rts_trace_pulse_end_patterns: no pulse in flight on this handle"); return RTS_ERR_INVALID; }
-    if (cube_pulse >= 0 && (!c->cube_set || (uint32_t)cube_pulse >= c->cube_params.n_pulses)) { rts_set_error("rts_trace_pulse_end_patterns: no cube attached, or pulse %d outside it", cube_pulse); return RTS_ERR_INVALID; }
+    if (cube_pulse >= 0 && (!c->cube.set || (uint32_t)cube_pulse >= c->cube.params.n_pulses)) { rts_set_error("rts_trace_pulse_end_patterns: no cube attached, or pulse %d outside it", cube_pulse); return RTS_ERR_INVALID; }
     RtsSpecParams& q = c->spec;
     int rc = rts_pattern_pulse_params(c, pulse, q, "rts_trace_pulse_end_patterns"); if (rc != RTS_OK) return rc;
     q.rcs.assign(c->scene->meshes.size() + 1, 1.0); q.gt = q.gr = 1.0;
@@ -1610,377 +1602,6 @@ extern "C" int rts_get_aggregated(RtsHandle c, PerRayData* rays, double* delay, 
     if (delay) RTS_HIP(hipMemcpy(delay, c->d_delay.p, sizeof(double)*R, hipMemcpyDeviceToHost));
     if (phase) RTS_HIP(hipMemcpy(phase, c->d_phase.p, sizeof(double)*R, hipMemcpyDeviceToHost));
     if (path_match) RTS_HIP(hipMemcpy(path_match, c->d_pathmatch.p, sizeof(int32_t)*R, hipMemcpyDeviceToHost));
-    return RTS_OK;
-}
-
-// ------------------------------------------------------------------------------------- complex return cube
-extern "C" int rts_cube_attach(RtsHandle c, const RtsCubeParams* p, void* device_ptr)
-{
-    CHECK_HANDLE(c);
-    if (!p || p->n_rx == 0 || p->n_pulses == 0 || p->n_bins == 0 || !(p->dt > 0) || !std::isfinite(p->t0)) { rts_set_error("rts_cube_attach: bad parameters"); return RTS_ERR_INVALID; }
-    const size_t doubles = 2 * (size_t)p->n_rx * p->n_pulses * p->n_bins;
-    RTS_HIP(hipStreamSynchronize(c->stream));
-    c->cube_params = *p;
-    if (device_ptr) c->cube = (double*)device_ptr;          // caller-owned (and caller-zeroed) device memory
-    else { RTS_HIP(c->d_cube_own.reserve(doubles)); c->cube = c->d_cube_own.p; RTS_HIP(hipMemset(c->cube, 0, sizeof(double) * doubles)); }
-    c->cube_set = true;
-    c->det_valid = false; c->doppler_fresh = false;         // (a detection list, and a map rts_cube_detect may take, belong to the cube they were made from)
-    c->img_valid = false;                                   // (... and so does an image)
-    c->stft_valid = false;                                  // (... and a spectrogram)
-    return RTS_OK;
-}
-
-extern "C" int rts_cube_accumulate(RtsHandle c, uint32_t pulse_index, double cspeed, double carrier)
-{
-    CHECK_HANDLE(c);
-    CHECK_CLOSED(c);
-    if (!c->cube_set) { rts_set_error("rts_cube_accumulate: call rts_cube_attach first"); return RTS_ERR_INVALID; }
-    if (pulse_index >= c->cube_params.n_pulses) { rts_set_error("rts_cube_accumulate: pulse %u >= %u", pulse_index, c->cube_params.n_pulses); return RTS_ERR_INVALID; }
-    return rts_cube_accumulate_device(c, pulse_index, cspeed, carrier);
-}
-
-extern "C" int rts_cube_accumulate_paths(RtsHandle c, uint32_t pulse_index)
-{
-    CHECK_HANDLE(c);
-    CHECK_CLOSED(c);
-    if (!c->cube_set) { rts_set_error("rts_cube_accumulate_paths: call rts_cube_attach first"); return RTS_ERR_INVALID; }
-    if (!c->agg_valid) { rts_set_error("rts_cube_accumulate_paths: call rts_aggregate for this pulse first (the groups' power, delay and phase are its results)"); return RTS_ERR_INVALID; }
-    if (pulse_index >= c->cube_params.n_pulses) { rts_set_error("rts_cube_accumulate_paths: pulse %u >= %u", pulse_index, c->cube_params.n_pulses); return RTS_ERR_INVALID; }
-    return rts_cube_accumulate_paths_device(c, pulse_index, c->agg_base_local);
-}
-
-extern "C" int rts_cube_doppler(RtsHandle c, uint32_t n_fft, void* device_out)
-{
-    CHECK_HANDLE(c);
-    CHECK_CLOSED(c);
-    if (!c->cube_set) { rts_set_error("rts_cube_doppler: call rts_cube_attach first"); return RTS_ERR_INVALID; }
-    if (n_fft < 2 || n_fft > 4096 || (n_fft & (n_fft - 1)) != 0 || n_fft < c->cube_params.n_pulses) {
-        rts_set_error("rts_cube_doppler: n_fft = %u must be a power of two in [max(2, n_pulses = %u), 4096]", n_fft, c->cube_params.n_pulses); return RTS_ERR_INVALID; }
-    const size_t doubles = 2 * (size_t)c->cube_params.n_rx * n_fft * c->cube_params.n_bins;
-    if (device_out) c->doppler = (double*)device_out;
-    else { RTS_HIP(c->d_doppler_own.reserve(doubles)); c->doppler = c->d_doppler_own.p; }
-    c->doppler_n = n_fft; c->doppler_fresh = true;
-    return rts_cube_doppler_device(c, n_fft, c->doppler);
-}
-
-extern "C" int rts_cube_doppler_get(RtsHandle c, double* host_out, uint64_t capacity_doubles)
-{
-    CHECK_HANDLE(c);
-    CHECK_CLOSED(c);
-    if (!c->cube_set || !c->doppler || !host_out) { rts_set_error("rts_cube_doppler_get: no transform (rts_cube_doppler) / null output"); return RTS_ERR_INVALID; }
-    const size_t doubles = 2 * (size_t)c->cube_params.n_rx * c->doppler_n * c->cube_params.n_bins;
-    if (capacity_doubles < doubles) { rts_set_error("rts_cube_doppler_get: capacity too small"); return RTS_ERR_CAPACITY; }
-    RTS_HIP(hipStreamSynchronize(c->stream));
-    RTS_HIP(hipMemcpy(host_out, c->doppler, sizeof(double) * doubles, hipMemcpyDeviceToHost));
-    return RTS_OK;
-}
-
-extern "C" int rts_cube_get(RtsHandle c, double* host_out, uint64_t capacity_doubles)
-{
-    CHECK_HANDLE(c);
-    CHECK_CLOSED(c);
-    if (!c->cube_set || !host_out) { rts_set_error("rts_cube_get: no cube / null output"); return RTS_ERR_INVALID; }
-    const size_t doubles = 2 * (size_t)c->cube_params.n_rx * c->cube_params.n_pulses * c->cube_params.n_bins;
-    if (capacity_doubles < doubles) { rts_set_error("rts_cube_get: capacity too small"); return RTS_ERR_CAPACITY; }
-    RTS_HIP(hipStreamSynchronize(c->stream));
-    RTS_HIP(hipMemcpy(host_out, c->cube, sizeof(double) * doubles, hipMemcpyDeviceToHost));
-    return RTS_OK;
-}
-
-// ------------------------------------------------------------------------------------- received signal: waveform render, range compression
-// (rts_amd.h: RtsWaveform; the interpolator is rts_waveform.h, shared by the host export and the render kernel, rts_render.hip)
-static int rts_waveform_check(const RtsWaveform* w, const char* who)
-{
-    if (!w) { rts_set_error("%s: null waveform", who); return RTS_ERR_INVALID; }
-    if (w->reserved[0] || w->reserved[1]) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
-    if (w->n_samples == 0 || w->n_samples > RTS_WAVEFORM_MAX_SAMPLES) { rts_set_error("%s: %u samples (1 .. %u)", who, w->n_samples, RTS_WAVEFORM_MAX_SAMPLES); return RTS_ERR_INVALID; }
-    if (w->taps != 1u && (w->taps < 2u || w->taps > RTS_WAVEFORM_MAX_TAPS || (w->taps & 1u))) { rts_set_error("%s: taps = %u (1, or even in [2, %u])", who, w->taps, RTS_WAVEFORM_MAX_TAPS); return RTS_ERR_INVALID; }
-    if (!w->samples) { rts_set_error("%s: null sample array", who); return RTS_ERR_INVALID; }
-    for (uint32_t i = 0; i < 2 * w->n_samples; i++) if (!std::isfinite(w->samples[i])) { rts_set_error("%s: sample %u is not finite", who, i / 2); return RTS_ERR_INVALID; }
-    return RTS_OK;
-}
-
-extern "C" int rts_waveform_eval(const RtsWaveform* w, const double* x, uint32_t n, double* out)
-{
-    int rc = rts_waveform_check(w, "rts_waveform_eval"); if (rc != RTS_OK) return rc;
-    if (n && (!x || !out)) { rts_set_error("rts_waveform_eval: null point or output array"); return RTS_ERR_INVALID; }
-    for (uint32_t i = 0; i < n; i++) rts_wave_eval(w->samples, w->n_samples, w->taps, x[i], &out[2 * (size_t)i], &out[2 * (size_t)i + 1]);
-    return RTS_OK;
-}
-
-extern "C" int rts_cube_set_waveform(RtsHandle c, const RtsWaveform* w)
-{
-    CHECK_HANDLE(c);
-    int rc = rts_waveform_check(w, "rts_cube_set_waveform"); if (rc != RTS_OK) return rc;
-    // the handle's enqueued work may still read the previous waveform: a speculative chain is resolved, then the stream drained
-    if (c->spec_pending) { rc = rts_spec_resolve(c); if (rc != RTS_OK) return rc; }
-    RTS_HIP(hipStreamSynchronize(c->stream));
-    RTS_HIP(c->d_wave.reserve(2 * (size_t)w->n_samples));
-    RTS_HIP(hipMemcpy(c->d_wave.p, w->samples, sizeof(double) * 2 * w->n_samples, hipMemcpyHostToDevice));
-    c->wave_M = w->n_samples; c->wave_L = w->taps; c->wave_set = true;
-    return RTS_OK;
-}
-
-extern "C" int rts_cube_render(RtsHandle c, uint32_t pulse_index, uint32_t source, uint32_t flags, double cspeed, double carrier)
-{
-    CHECK_HANDLE(c);
-    if (source != RTS_RENDER_RAYS && source != RTS_RENDER_PATHS) { rts_set_error("rts_cube_render: unknown source %u (RTS_RENDER_RAYS, RTS_RENDER_PATHS)", source); return RTS_ERR_INVALID; }
-    if (flags & ~RTS_RENDER_DOPPLER) { rts_set_error("rts_cube_render: unknown flags 0x%x", flags); return RTS_ERR_INVALID; }
-    CHECK_CLOSED(c);
-    if (!c->cube_set) { rts_set_error("rts_cube_render: call rts_cube_attach first"); return RTS_ERR_INVALID; }
-    if (!c->wave_set) { rts_set_error("rts_cube_render: no waveform (rts_cube_set_waveform)"); return RTS_ERR_INVALID; }
-    if (pulse_index >= c->cube_params.n_pulses) { rts_set_error("rts_cube_render: pulse %u >= %u", pulse_index, c->cube_params.n_pulses); return RTS_ERR_INVALID; }
-    const bool paths = source == RTS_RENDER_PATHS;
-    if (paths && !c->agg_valid) { rts_set_error("rts_cube_render: RTS_RENDER_PATHS needs rts_aggregate of this pulse first (the groups' power, delay and phase are its results)"); return RTS_ERR_INVALID; }
-    return rts_cube_render_device(c, pulse_index, paths, (flags & RTS_RENDER_DOPPLER) != 0, cspeed, carrier, c->agg_base_local);
-}
-
-extern "C" int rts_cube_compress(RtsHandle c, uint32_t first_pulse, uint32_t n_pulses)
-{
-    CHECK_HANDLE(c);
-    CHECK_CLOSED(c);
-    if (!c->cube_set) { rts_set_error("rts_cube_compress: call rts_cube_attach first"); return RTS_ERR_INVALID; }
-    if (!c->wave_set) { rts_set_error("rts_cube_compress: no waveform (rts_cube_set_waveform)"); return RTS_ERR_INVALID; }
-    const RtsCubeParams& q = c->cube_params;
-    if (first_pulse >= q.n_pulses || n_pulses > q.n_pulses - first_pulse) { rts_set_error("rts_cube_compress: pulses %u .. %u + %u outside the cube's %u", first_pulse, first_pulse, n_pulses, q.n_pulses); return RTS_ERR_INVALID; }
-    if (q.n_bins > RTS_COMPRESS_MAX_BINS) { rts_set_error("rts_cube_compress: %u range bins > %u (RTS_COMPRESS_MAX_BINS: one row of complex128 in a workgroup's LDS)", q.n_bins, RTS_COMPRESS_MAX_BINS); return RTS_ERR_INVALID; }
-    return rts_cube_compress_device(c, first_pulse, n_pulses);
-}
-
-// ------------------------------------------------------------------------------------- receiver noise, CFAR detection
-// (rts_amd.h; the generator is rts_noise.h, shared by the host export and the noise kernel; the kernels are in rts_detect.hip)
-extern "C" int rts_noise_eval(uint64_t seed, const uint64_t* index, uint32_t n, double noise_power, double* out)
-{
-    if (!std::isfinite(noise_power) || noise_power < 0) { rts_set_error("rts_noise_eval: noise_power = %g (finite, >= 0)", noise_power); return RTS_ERR_INVALID; }
-    if (n && (!index || !out)) { rts_set_error("rts_noise_eval: null index or output array"); return RTS_ERR_INVALID; }
-    const double sigma = sqrt(noise_power / 2.0);
-    for (uint32_t j = 0; j < n; j++) rts_noise_sample(seed, index[j], sigma, &out[2 * (size_t)j], &out[2 * (size_t)j + 1]);
-    return RTS_OK;
-}
-
-extern "C" int rts_cube_add_noise(RtsHandle c, uint32_t first_pulse, uint32_t n_pulses, double noise_power, uint64_t seed)
-{
-    CHECK_HANDLE(c);
-    if (!std::isfinite(noise_power) || noise_power < 0) { rts_set_error("rts_cube_add_noise: noise_power = %g (finite, >= 0)", noise_power); return RTS_ERR_INVALID; }
-    CHECK_CLOSED(c);
-    if (!c->cube_set) { rts_set_error("rts_cube_add_noise: call rts_cube_attach first"); return RTS_ERR_INVALID; }
-    const RtsCubeParams& q = c->cube_params;
-    if (first_pulse >= q.n_pulses || n_pulses > q.n_pulses - first_pulse) { rts_set_error("rts_cube_add_noise: pulses %u .. %u + %u outside the cube's %u", first_pulse, first_pulse, n_pulses, q.n_pulses); return RTS_ERR_INVALID; }
-    if ((uintptr_t)c->cube & 15u) { rts_set_error("rts_cube_add_noise: the cube's device memory is not 16-byte aligned"); return RTS_ERR_INVALID; }
-    return rts_cube_noise_device(c, first_pulse, n_pulses, sqrt(noise_power / 2.0), seed);
-}
-
-extern "C" int rts_cube_detect(RtsHandle c, const RtsCfarParams* p, const void* device_map, uint32_t n_doppler)
-{
-    CHECK_HANDLE(c);
-    if (!p) { rts_set_error("rts_cube_detect: null parameters"); return RTS_ERR_INVALID; }
-    CHECK_CLOSED(c);
-    if (!c->cube_set) { rts_set_error("rts_cube_detect: no cube (call rts_cube_attach first)"); return RTS_ERR_INVALID; }
-    const double* map;
-    if (device_map) {
-        map = (const double*)device_map;
-        if (n_doppler == 0) { rts_set_error("rts_cube_detect: n_doppler = 0 with a caller map"); return RTS_ERR_INVALID; }
-        if ((uintptr_t)map & 15u) { rts_set_error("rts_cube_detect: device_map is not 16-byte aligned"); return RTS_ERR_INVALID; }
-    } else {
-        if (!c->doppler || !c->doppler_fresh) { rts_set_error("rts_cube_detect: no map (call rts_cube_doppler first, or pass device_map)"); return RTS_ERR_INVALID; }
-        map = c->doppler; n_doppler = c->doppler_n;
-    }
-    const uint32_t Gr = p->guard_range, Gd = p->guard_doppler, Tr = p->train_range, Td = p->train_doppler, nb = c->cube_params.n_bins;
-    if (p->mode > RTS_CFAR_SO) { rts_set_error("rts_cube_detect: unknown mode %u (RTS_CFAR_CA, _GO, _SO)", p->mode); return RTS_ERR_INVALID; }
-    if (p->flags & ~RTS_CFAR_LOCAL_MAX) { rts_set_error("rts_cube_detect: unknown flags 0x%x", p->flags); return RTS_ERR_INVALID; }
-    if (p->reserved0 || p->reserved[0] || p->reserved[1]) { rts_set_error("rts_cube_detect: reserved fields must be 0"); return RTS_ERR_INVALID; }
-    if (Tr > RTS_CFAR_MAX_HALF || Td > RTS_CFAR_MAX_HALF || Gr > RTS_CFAR_MAX_HALF || Gd > RTS_CFAR_MAX_HALF) { rts_set_error("rts_cube_detect: guard_range, guard_doppler, train_range, train_doppler are at most %u each", RTS_CFAR_MAX_HALF); return RTS_ERR_INVALID; }
-    if (Tr + Td == 0) { rts_set_error("rts_cube_detect: train_range + train_doppler = 0 (no training cells)"); return RTS_ERR_INVALID; }
-    if (Gr + Tr > RTS_CFAR_MAX_HALF) { rts_set_error("rts_cube_detect: guard_range + train_range = %u > %u", Gr + Tr, RTS_CFAR_MAX_HALF); return RTS_ERR_INVALID; }
-    if (Gd + Td > RTS_CFAR_MAX_HALF) { rts_set_error("rts_cube_detect: guard_doppler + train_doppler = %u > %u", Gd + Td, RTS_CFAR_MAX_HALF); return RTS_ERR_INVALID; }
-    if (2 * (Gd + Td) + 1 > n_doppler) { rts_set_error("rts_cube_detect: guard_doppler + train_doppler = %u: the window (%u rows) exceeds n_doppler = %u", Gd + Td, 2 * (Gd + Td) + 1, n_doppler); return RTS_ERR_INVALID; }
-    if (Gr + Tr >= nb) { rts_set_error("rts_cube_detect: guard_range + train_range = %u >= n_bins = %u", Gr + Tr, nb); return RTS_ERR_INVALID; }
-    const bool has_pfa = p->pfa != 0.0, has_alpha = p->alpha != 0.0;
-    if (has_pfa && !(p->pfa > 0.0 && p->pfa < 1.0)) { rts_set_error("rts_cube_detect: pfa = %g outside (0, 1)", p->pfa); return RTS_ERR_INVALID; }
-    if (has_pfa == has_alpha) { rts_set_error("rts_cube_detect: give exactly one of pfa and alpha"); return RTS_ERR_INVALID; }
-    if (has_alpha && !(p->alpha > 0.0 && std::isfinite(p->alpha))) { rts_set_error("rts_cube_detect: alpha = %g (finite, > 0)", p->alpha); return RTS_ERR_INVALID; }
-    if (p->mode != RTS_CFAR_CA && has_pfa) { rts_set_error("rts_cube_detect: pfa is for mode RTS_CFAR_CA only (GO / SO take alpha)"); return RTS_ERR_INVALID; }
-    if (p->mode != RTS_CFAR_CA && Tr == 0) { rts_set_error("rts_cube_detect: train_range = 0 with GO / SO (the halves are range halves)"); return RTS_ERR_INVALID; }
-    if (!(p->pri >= 0.0) || !std::isfinite(p->pri)) { rts_set_error("rts_cube_detect: pri = %g (finite, >= 0)", p->pri); return RTS_ERR_INVALID; }
-    const uint32_t max_det = p->max_detections ? p->max_detections : RTS_CFAR_DEFAULT_MAX_DETECTIONS;
-    c->det_valid = false;
-    return rts_cube_detect_device(c, *p, map, n_doppler, max_det);
-}
-
-extern "C" int rts_cube_detections_get(RtsHandle c, RtsDetection* out, uint32_t capacity, uint32_t* n_out)
-{
-    CHECK_HANDLE(c);
-    if (!n_out || (capacity && !out)) { rts_set_error("rts_cube_detections_get: null output"); return RTS_ERR_INVALID; }
-    if (!c->det_valid) { rts_set_error("rts_cube_detections_get: no detection list (rts_cube_detect; a list ends at rts_cube_attach)"); return RTS_ERR_INVALID; }
-    RTS_HIP(hipStreamSynchronize(c->stream));
-    uint32_t total = 0;
-    RTS_HIP(hipMemcpy(&total, c->d_det_off.p + c->det_nseg, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    *n_out = total;
-    uint32_t n = total < c->det_max ? total : c->det_max;
-    if (n > capacity) n = capacity;
-    if (n) RTS_HIP(hipMemcpy(out, c->d_det.p, sizeof(RtsDetection) * n, hipMemcpyDeviceToHost));
-    if (n < total) { rts_set_error("rts_cube_detections_get: %u of %u detections copied (max_detections %u, capacity %u)", n, total, c->det_max, capacity); return RTS_ERR_CAPACITY; }
-    return RTS_OK;
-}
-
-// ------------------------------------------------------------------------------------- tapered slow-time spectrogram
-// (rts_amd.h: RtsStftParams; the tree and the launch plan are rts_stft.h, shared by the host export and the kernel, rts_stft.hip)
-static int rts_stft_check(const RtsStftParams* p, const RtsCubeParams& q, const char* who, RtsStftPlan* plan)
-{
-    if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
-    if (p->reserved[0] || p->reserved[1]) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
-    if (p->flags & ~(RTS_STFT_POWER | RTS_STFT_SUM_BINS)) { rts_set_error("%s: unknown flags 0x%x", who, p->flags); return RTS_ERR_INVALID; }
-    if ((p->flags & RTS_STFT_SUM_BINS) && !(p->flags & RTS_STFT_POWER)) { rts_set_error("%s: flags: RTS_STFT_SUM_BINS needs RTS_STFT_POWER", who); return RTS_ERR_INVALID; }
-    if (p->n_fft < 2u || p->n_fft > RTS_STFT_MAX_FFT || (p->n_fft & (p->n_fft - 1u)) != 0u) { rts_set_error("%s: n_fft = %u must be a power of two in [2, %u]", who, p->n_fft, RTS_STFT_MAX_FFT); return RTS_ERR_INVALID; }
-    if (p->n_pulses == 0 || p->first_pulse >= q.n_pulses || p->n_pulses > q.n_pulses - p->first_pulse) { rts_set_error("%s: first_pulse = %u, n_pulses = %u: at least one pulse, inside the cube's %u rows", who, p->first_pulse, p->n_pulses, q.n_pulses); return RTS_ERR_INVALID; }
-    if (p->window_len == 0 || p->window_len > p->n_fft || p->window_len > p->n_pulses) { rts_set_error("%s: window_len = %u (1 .. n_fft = %u, <= n_pulses = %u)", who, p->window_len, p->n_fft, p->n_pulses); return RTS_ERR_INVALID; }
-    if (p->hop == 0) { rts_set_error("%s: hop = 0 (>= 1)", who); return RTS_ERR_INVALID; }
-    if (p->first_bin >= q.n_bins || p->n_bins > q.n_bins - p->first_bin) { rts_set_error("%s: first_bin = %u, n_bins = %u: inside the cube's %u bins", who, p->first_bin, p->n_bins, q.n_bins); return RTS_ERR_INVALID; }
-    if (p->window) for (uint32_t i = 0; i < p->window_len; i++) if (!std::isfinite(p->window[i])) { rts_set_error("%s: window[%u] is not finite", who, i); return RTS_ERR_INVALID; }
-    const uint32_t n_gate = p->n_bins ? p->n_bins : q.n_bins - p->first_bin;
-    *plan = rts_stft_plan(q.n_rx, p->n_pulses, p->window_len, p->hop, p->n_fft, n_gate, p->flags);
-    if (!plan->supported) {
-        if (q.n_rx > RTS_STFT_MAX_RX) rts_set_error("%s: n_rx = %u receivers: more than %u (the launch grid)", who, q.n_rx, RTS_STFT_MAX_RX);
-        else rts_set_error("%s: n_frames = %u frames x %u workgroups per frame (hop, n_bins): more than %u (the launch grid)", who, plan->n_frames, plan->tiles, RTS_STFT_MAX_GRID_X);
-        return RTS_ERR_INVALID;
-    }
-    return RTS_OK;
-}
-
-extern "C" int rts_window_make(uint32_t kind, uint32_t n, double* out)
-{
-    if (n == 0) { rts_set_error("rts_window_make: n = 0"); return RTS_ERR_INVALID; }
-    if (kind > RTS_WINDOW_BLACKMAN) { rts_set_error("rts_window_make: unknown kind %u", kind); return RTS_ERR_INVALID; }
-    if (!out) { rts_set_error("rts_window_make: null output array"); return RTS_ERR_INVALID; }
-    rts_stft_window_host(kind, n, out);
-    return RTS_OK;
-}
-
-extern "C" int rts_stft_eval(const RtsCubeParams* q, const double* cube, const RtsStftParams* p, double* out, uint32_t* n_frames_out)
-{
-    if (!q || q->n_rx == 0 || q->n_pulses == 0 || q->n_bins == 0) { rts_set_error("rts_stft_eval: bad cube parameters"); return RTS_ERR_INVALID; }
-    RtsStftPlan plan;
-    int rc = rts_stft_check(p, *q, "rts_stft_eval", &plan); if (rc != RTS_OK) return rc;
-    if (!cube || !out) { rts_set_error("rts_stft_eval: null cube or output array"); return RTS_ERR_INVALID; }
-    std::vector<double> work(4 * (size_t)p->n_fft);
-    rts_stft_eval_host(q, cube, p, plan, out, work.data());
-    if (n_frames_out) *n_frames_out = plan.n_frames;
-    return RTS_OK;
-}
-
-extern "C" int rts_cube_spectrogram(RtsHandle c, const RtsStftParams* p, void* device_out, uint32_t* n_frames_out)
-{
-    CHECK_HANDLE(c);
-    if (!c->cube_set) { rts_set_error("rts_cube_spectrogram: no cube (call rts_cube_attach first)"); return RTS_ERR_INVALID; }
-    const RtsCubeParams& q = c->cube_params;
-    RtsStftPlan plan;
-    int rc = rts_stft_check(p, q, "rts_cube_spectrogram", &plan); if (rc != RTS_OK) return rc;
-    if ((uintptr_t)device_out & 15u) { rts_set_error("rts_cube_spectrogram: device_out is not 16-byte aligned"); return RTS_ERR_INVALID; }
-    CHECK_CLOSED(c);
-    double* out = (double*)device_out;
-    if (!out) { RTS_HIP(c->d_stft_own.reserve(plan.out_doubles)); out = c->d_stft_own.p; }
-    // the window -> pinned staging -> the device, on the stream
-    const double* win = nullptr;
-    if (p->window) {
-        const size_t n = p->window_len;
-        if (c->ev_stft_armed) { RTS_HIP(hipEventSynchronize(c->ev_stft)); c->ev_stft_armed = false; }
-        if (c->pin_stft.cap < n) RTS_HIP(c->pin_stft.reserve(RTS_STFT_MAX_FFT, false));
-        if (!c->ev_stft) RTS_HIP(hipEventCreateWithFlags(&c->ev_stft, hipEventDisableTiming));
-        RTS_HIP(c->d_stft_win.reserve(RTS_STFT_MAX_FFT));
-        memcpy(c->pin_stft.p, p->window, sizeof(double) * n);
-        RTS_HIP(hipMemcpyAsync(c->d_stft_win.p, c->pin_stft.p, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
-        RTS_HIP(hipEventRecord(c->ev_stft, c->stream)); c->ev_stft_armed = true;
-        win = c->d_stft_win.p;
-    }
-    if (!device_out) { c->stft_doubles = plan.out_doubles; c->stft_valid = true; }
-    if (n_frames_out) *n_frames_out = plan.n_frames;
-    return rts_cube_stft_device(c, *p, plan, win, out);
-}
-
-extern "C" int rts_cube_spectrogram_get(RtsHandle c, double* host_out, uint64_t capacity_doubles)
-{
-    CHECK_HANDLE(c);
-    if (!c->cube_set || !c->stft_valid || !host_out) { rts_set_error("rts_cube_spectrogram_get: no library-owned spectrogram (rts_cube_spectrogram with device_out NULL; a spectrogram ends at rts_cube_attach) / null output"); return RTS_ERR_INVALID; }
-    if (capacity_doubles < c->stft_doubles) { rts_set_error("rts_cube_spectrogram_get: capacity too small"); return RTS_ERR_CAPACITY; }
-    RTS_HIP(hipStreamSynchronize(c->stream));
-    RTS_HIP(hipMemcpy(host_out, c->d_stft_own.p, sizeof(double) * c->stft_doubles, hipMemcpyDeviceToHost));
-    return RTS_OK;
-}
-
-// ------------------------------------------------------------------------------------- backprojection imaging
-// (rts_amd.h: RtsImageParams; the arithmetic and the launch plan are rts_image.h, shared by the host export and the kernel, rts_image.hip)
-static int rts_image_check(const RtsImageParams* p, const RtsCubeParams& q, const char* who)
-{
-    if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
-    if (p->n_x == 0 || p->n_y == 0 || (uint64_t)p->n_x * p->n_y > RTS_IMAGE_MAX_PIXELS) { rts_set_error("%s: n_x = %u, n_y = %u (each >= 1, n_x * n_y <= %u)", who, p->n_x, p->n_y, RTS_IMAGE_MAX_PIXELS); return RTS_ERR_INVALID; }
-    if (p->taps != 1u && (p->taps < 2u || p->taps > RTS_WAVEFORM_MAX_TAPS || (p->taps & 1u))) { rts_set_error("%s: taps = %u (1, or even in [2, %u])", who, p->taps, RTS_WAVEFORM_MAX_TAPS); return RTS_ERR_INVALID; }
-    if (p->flags & ~RTS_IMAGE_ACCUMULATE) { rts_set_error("%s: unknown flags 0x%x", who, p->flags); return RTS_ERR_INVALID; }
-    if (p->reserved[0] || p->reserved[1]) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
-    if (p->n_pulses == 0 || p->first_pulse >= q.n_pulses || p->n_pulses > q.n_pulses - p->first_pulse) { rts_set_error("%s: first_pulse = %u, n_pulses = %u: at least one pulse, inside the cube's %u rows", who, p->first_pulse, p->n_pulses, q.n_pulses); return RTS_ERR_INVALID; }
-    if (!std::isfinite(p->cspeed) || !(p->cspeed > 0.0)) { rts_set_error("%s: cspeed = %g (finite, > 0)", who, p->cspeed); return RTS_ERR_INVALID; }
-    if (!std::isfinite(p->carrier) || p->carrier < 0.0) { rts_set_error("%s: carrier = %g (finite, >= 0)", who, p->carrier); return RTS_ERR_INVALID; }
-    for (int k = 0; k < 3; k++) {
-        if (!std::isfinite(p->origin[k])) { rts_set_error("%s: origin[%d] is not finite", who, k); return RTS_ERR_INVALID; }
-        if (!std::isfinite(p->step_x[k])) { rts_set_error("%s: step_x[%d] is not finite", who, k); return RTS_ERR_INVALID; }
-        if (!std::isfinite(p->step_y[k])) { rts_set_error("%s: step_y[%d] is not finite", who, k); return RTS_ERR_INVALID; }
-    }
-    if (!p->tx_position) { rts_set_error("%s: null tx_position", who); return RTS_ERR_INVALID; }
-    if (!p->rx_position) { rts_set_error("%s: null rx_position", who); return RTS_ERR_INVALID; }
-    for (size_t i = 0; i < 3 * (size_t)p->n_pulses; i++) if (!std::isfinite(p->tx_position[i])) { rts_set_error("%s: tx_position of pulse %zu is not finite", who, i / 3); return RTS_ERR_INVALID; }
-    for (size_t i = 0; i < 3 * (size_t)q.n_rx * p->n_pulses; i++) if (!std::isfinite(p->rx_position[i])) { rts_set_error("%s: rx_position of receiver %zu, pulse %zu is not finite", who, i / 3 / p->n_pulses, i / 3 % p->n_pulses); return RTS_ERR_INVALID; }
-    if (p->pulse_weight) for (uint32_t j = 0; j < p->n_pulses; j++) if (!std::isfinite(p->pulse_weight[j])) { rts_set_error("%s: pulse_weight[%u] is not finite", who, j); return RTS_ERR_INVALID; }
-    if (!rts_image_plan(p->n_x, p->n_y, q.n_rx, p->n_pulses, 0u).supported) { rts_set_error("%s: n_rx = %u receivers / n_pulses = %u: more than %u receivers or chunks of %u pulses", who, q.n_rx, p->n_pulses, RTS_IMAGE_GRID_MAX, RTS_IMAGE_PULSE_CHUNK); return RTS_ERR_INVALID; }
-    return RTS_OK;
-}
-
-extern "C" int rts_backproject_eval(const RtsCubeParams* q, const double* cube, const RtsImageParams* p, double* out)
-{
-    if (!q || q->n_rx == 0 || q->n_pulses == 0 || q->n_bins == 0 || !(q->dt > 0) || !std::isfinite(q->dt) || !std::isfinite(q->t0)) { rts_set_error("rts_backproject_eval: bad cube parameters"); return RTS_ERR_INVALID; }
-    int rc = rts_image_check(p, *q, "rts_backproject_eval"); if (rc != RTS_OK) return rc;
-    if (!cube || !out) { rts_set_error("rts_backproject_eval: null cube or output array"); return RTS_ERR_INVALID; }
-    rts_image_eval_host(q, cube, p, out);
-    return RTS_OK;
-}
-
-extern "C" int rts_cube_backproject(RtsHandle c, const RtsImageParams* p, void* device_out)
-{
-    CHECK_HANDLE(c);
-    if (!c->cube_set) { rts_set_error("rts_cube_backproject: no cube (call rts_cube_attach first)"); return RTS_ERR_INVALID; }
-    const RtsCubeParams& q = c->cube_params;
-    int rc = rts_image_check(p, q, "rts_cube_backproject"); if (rc != RTS_OK) return rc;
-    if ((uintptr_t)device_out & 15u) { rts_set_error("rts_cube_backproject: device_out is not 16-byte aligned"); return RTS_ERR_INVALID; }
-    const bool acc = (p->flags & RTS_IMAGE_ACCUMULATE) != 0;
-    if (acc && !device_out && !(c->img_valid && c->img_nx == p->n_x && c->img_ny == p->n_y)) {
-        rts_set_error("rts_cube_backproject: RTS_IMAGE_ACCUMULATE without device_out needs a library-owned image of the same n_x, n_y"); return RTS_ERR_INVALID; }
-    CHECK_CLOSED(c);
-    const RtsImagePlan plan = rts_image_plan(p->n_x, p->n_y, q.n_rx, p->n_pulses, c->img_split_below);
-    const size_t doubles = 2 * (size_t)q.n_rx * p->n_y * p->n_x;
-    double* out = (double*)device_out;
-    if (!out) { RTS_HIP(c->d_image_own.reserve(doubles)); out = c->d_image_own.p; }       // (accumulate: the shape is the same, so the buffer stays)
-    // the geometry [tx | rx | w] -> pinned staging -> the device, on the stream
-    const size_t P = p->n_pulses, n_geo = 3 * P + 3 * (size_t)q.n_rx * P + P;
-    if (c->ev_img_armed) { RTS_HIP(hipEventSynchronize(c->ev_img)); c->ev_img_armed = false; }
-    if (c->pin_img.cap < n_geo) RTS_HIP(c->pin_img.reserve(std::max<size_t>(n_geo + n_geo / 2, 4096), false));
-    if (!c->ev_img) RTS_HIP(hipEventCreateWithFlags(&c->ev_img, hipEventDisableTiming));
-    RTS_HIP(c->d_img_geo.reserve(n_geo));
-    double* g = c->pin_img.p;
-    memcpy(g, p->tx_position, sizeof(double) * 3 * P);
-    memcpy(g + 3 * P, p->rx_position, sizeof(double) * 3 * q.n_rx * P);
-    for (size_t j = 0; j < P; j++) g[3 * P + 3 * (size_t)q.n_rx * P + j] = p->pulse_weight ? p->pulse_weight[j] : 1.0;
-    RTS_HIP(hipMemcpyAsync(c->d_img_geo.p, g, sizeof(double) * n_geo, hipMemcpyHostToDevice, c->stream));
-    RTS_HIP(hipEventRecord(c->ev_img, c->stream)); c->ev_img_armed = true;
-    if (!device_out) { c->img_nx = p->n_x; c->img_ny = p->n_y; c->img_valid = true; }
-    return rts_cube_backproject_device(c, *p, plan, c->d_img_geo.p, out);
-}
-
-extern "C" int rts_cube_image_get(RtsHandle c, double* host_out, uint64_t capacity_doubles)
-{
-    CHECK_HANDLE(c);
-    if (!c->cube_set || !c->img_valid || !host_out) { rts_set_error("rts_cube_image_get: no library-owned image (rts_cube_backproject with device_out NULL; an image ends at rts_cube_attach) / null output"); return RTS_ERR_INVALID; }
-    const size_t doubles = 2 * (size_t)c->cube_params.n_rx * c->img_ny * c->img_nx;
-    if (capacity_doubles < doubles) { rts_set_error("rts_cube_image_get: capacity too small"); return RTS_ERR_CAPACITY; }
-    RTS_HIP(hipStreamSynchronize(c->stream));
-    RTS_HIP(hipMemcpy(host_out, c->d_image_own.p, sizeof(double) * doubles, hipMemcpyDeviceToHost));
     return RTS_OK;
 }
 
@@ -2211,12 +1832,12 @@ extern "C" int rts_cube_reduce(RtsHandle* hs, uint32_t n, int transport)
 {
     if (!hs || n == 0) { rts_set_error("rts_cube_reduce: no handles"); return RTS_ERR_INVALID; }
     for (uint32_t i = 0; i < n; i++) {
-        if (!hs[i] || !hs[i]->cube_set) { rts_set_error("rts_cube_reduce: handle %u has no cube (rts_cube_attach)", i); return RTS_ERR_INVALID; }
-        const RtsCubeParams &a = hs[0]->cube_params, &b = hs[i]->cube_params;
+        if (!hs[i] || !hs[i]->cube.set) { rts_set_error("rts_cube_reduce: handle %u has no cube (rts_cube_attach)", i); return RTS_ERR_INVALID; }
+        const RtsCubeParams &a = hs[0]->cube.params, &b = hs[i]->cube.params;
         if (a.n_rx != b.n_rx || a.n_pulses != b.n_pulses || a.n_bins != b.n_bins) { rts_set_error("rts_cube_reduce: handle %u has a cube of another shape", i); return RTS_ERR_INVALID; }
-        for (uint32_t j = 0; j < i; j++) if (hs[j]->cube == hs[i]->cube) { rts_set_error("rts_cube_reduce: handles %u and %u share one cube buffer (nothing to add)", j, i); return RTS_ERR_INVALID; }
+        for (uint32_t j = 0; j < i; j++) if (hs[j]->cube.p == hs[i]->cube.p) { rts_set_error("rts_cube_reduce: handles %u and %u share one cube buffer (nothing to add)", j, i); return RTS_ERR_INVALID; }
     }
-    const size_t doubles = 2 * (size_t)hs[0]->cube_params.n_rx * hs[0]->cube_params.n_pulses * hs[0]->cube_params.n_bins;
+    const size_t doubles = 2 * (size_t)hs[0]->cube.params.n_rx * hs[0]->cube.params.n_pulses * hs[0]->cube.params.n_bins;
     for (uint32_t i = 0; i < n; i++) { RtsContext* c = hs[i]; CHECK_CLOSED(c); RTS_HIP(hipSetDevice(c->device)); RTS_HIP(hipStreamSynchronize(c->stream)); }
     if (n == 1 && transport != 1) return RTS_OK;
     bool distinct = true;
@@ -2229,7 +1850,7 @@ extern "C" int rts_cube_reduce(RtsHandle* hs, uint32_t n, int transport)
             // From here on there is no falling back: the all-reduce is in place, and after a failure part-way some cubes may
             // already hold partial sums -- adding them again over peer copies would count them twice.
             rc = g_rccl.GroupStart();
-            for (uint32_t i = 0; i < n && rc == 0; i++) { (void)hipSetDevice(hs[i]->device); rc = g_rccl.AllReduce(hs[i]->cube, hs[i]->cube, doubles, 8 /* ncclFloat64 */, 0 /* ncclSum */, (*comms)[i], hs[i]->stream); }
+            for (uint32_t i = 0; i < n && rc == 0; i++) { (void)hipSetDevice(hs[i]->device); rc = g_rccl.AllReduce(hs[i]->cube.p, hs[i]->cube.p, doubles, 8 /* ncclFloat64 */, 0 /* ncclSum */, (*comms)[i], hs[i]->stream); }
             const int rc2 = g_rccl.GroupEnd(); if (rc == 0) rc = rc2;
             for (uint32_t i = 0; i < n; i++) { (void)hipSetDevice(hs[i]->device); (void)hipStreamSynchronize(hs[i]->stream); }
             if (rc == 0) return RTS_OK;
@@ -2245,12 +1866,12 @@ extern "C" int rts_cube_reduce(RtsHandle* hs, uint32_t n, int transport)
     RTS_HIP(hipSetDevice(c0->device));
     DevBuf<double> tmp; RTS_HIP(tmp.reserve(doubles));
     for (uint32_t i = 1; i < n; i++) {
-        RTS_HIP(hipMemcpyPeerAsync(tmp.p, c0->device, hs[i]->cube, hs[i]->device, sizeof(double) * doubles, c0->stream));
-        k_add_f64<<<(unsigned)((doubles + 255) / 256), 256, 0, c0->stream>>>(c0->cube, tmp.p, doubles);
+        RTS_HIP(hipMemcpyPeerAsync(tmp.p, c0->device, hs[i]->cube.p, hs[i]->device, sizeof(double) * doubles, c0->stream));
+        k_add_f64<<<(unsigned)((doubles + 255) / 256), 256, 0, c0->stream>>>(c0->cube.p, tmp.p, doubles);
         RTS_HIP(hipGetLastError());
     }
     RTS_HIP(hipStreamSynchronize(c0->stream));
-    for (uint32_t i = 1; i < n; i++) RTS_HIP(hipMemcpyPeer(hs[i]->cube, hs[i]->device, c0->cube, c0->device, sizeof(double) * doubles));
+    for (uint32_t i = 1; i < n; i++) RTS_HIP(hipMemcpyPeer(hs[i]->cube.p, hs[i]->device, c0->cube.p, c0->device, sizeof(double) * doubles));
     return RTS_OK;
 }
 

@@ -1,0 +1,369 @@
+// rts_cube_api.hip -- the cube part of the C-ABI of include/rts_amd.h (rts_cube_reduce apart: rts_api.hip) and the pure-host evaluators that go with it.
+// Host code only, no kernels: argument checks, the handle's cube state (RtsCubeState, rts_internal.h), the calls of the launchers in the kernels' units.
+#include <cmath>
+#include <cstring>
+#include <algorithm>
+#include "rts_internal.h"
+
+// ------------------------------------------------------------------------------------- shared argument checks (each forms the message of the entry point `who`), the copy-out
+#define NEED_CUBE(c, who, wording) do { if (!(c)->cube.set) { rts_set_error("%s: %s", (who), (wording)); return RTS_ERR_INVALID; } } while (0)
+
+static int rts_pulses_check(const char* who, uint32_t first, uint32_t n, uint32_t rows, bool at_least_one)      // pulses first .. first + n inside the cube's rows; a product needs at least one
+{
+    if ((!at_least_one || n != 0) && first < rows && n <= rows - first) return RTS_OK;
+    if (at_least_one) rts_set_error("%s: first_pulse = %u, n_pulses = %u: at least one pulse, inside the cube's %u rows", who, first, n, rows);
+    else rts_set_error("%s: pulses %u .. %u + %u outside the cube's %u", who, first, first, n, rows);
+    return RTS_ERR_INVALID;
+}
+
+static int rts_taps_check(const char* who, uint32_t taps)      // the interpolator's support (rts_waveform.h): the nearest sample, or an even number of taps
+{
+    if (taps != 1u && (taps < 2u || taps > RTS_WAVEFORM_MAX_TAPS || (taps & 1u))) { rts_set_error("%s: taps = %u (1, or even in [2, %u])", who, taps, RTS_WAVEFORM_MAX_TAPS); return RTS_ERR_INVALID; }
+    return RTS_OK;
+}
+
+// `doubles` doubles at src -> the host, once the stream has produced them; have: they exist (the cube, or a valid product: its RECORDED place and size); none: the message when not
+static int rts_cube_copy_out(RtsContext* c, const char* who, const char* none, bool have, const double* src, size_t doubles, double* host_out, uint64_t capacity_doubles)
+{
+    if (!c->cube.set || !have || !host_out) { rts_set_error("%s: %s", who, none); return RTS_ERR_INVALID; }
+    if (capacity_doubles < doubles) { rts_set_error("%s: capacity too small", who); return RTS_ERR_CAPACITY; }
+    RTS_HIP(hipStreamSynchronize(c->stream));
+    RTS_HIP(hipMemcpy(host_out, src, sizeof(double) * doubles, hipMemcpyDeviceToHost));
+    return RTS_OK;
+}
+
+// ------------------------------------------------------------------------------------- complex return cube
+extern "C" int rts_cube_attach(RtsHandle c, const RtsCubeParams* p, void* device_ptr)
+{
+    CHECK_HANDLE(c);
+    if (!p || p->n_rx == 0 || p->n_pulses == 0 || p->n_bins == 0 || !(p->dt > 0) || !std::isfinite(p->t0)) { rts_set_error("rts_cube_attach: bad parameters"); return RTS_ERR_INVALID; }
+    const size_t doubles = 2 * (size_t)p->n_rx * p->n_pulses * p->n_bins;
+    RTS_HIP(hipStreamSynchronize(c->stream));
+    c->cube.params = *p;
+    if (device_ptr) c->cube.p = (double*)device_ptr;        // caller-owned (and caller-zeroed) device memory
+    else { RTS_HIP(c->cube.own.reserve(doubles)); c->cube.p = c->cube.own.p; RTS_HIP(hipMemset(c->cube.p, 0, sizeof(double) * doubles)); }
+    c->cube.set = true;
+    c->cube.end_products();
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_accumulate(RtsHandle c, uint32_t pulse_index, double cspeed, double carrier)
+{
+    CHECK_HANDLE(c);
+    CHECK_CLOSED(c);
+    NEED_CUBE(c, "rts_cube_accumulate", "call rts_cube_attach first");
+    if (pulse_index >= c->cube.params.n_pulses) { rts_set_error("rts_cube_accumulate: pulse %u >= %u", pulse_index, c->cube.params.n_pulses); return RTS_ERR_INVALID; }
+    return rts_cube_accumulate_device(c, pulse_index, cspeed, carrier);
+}
+
+extern "C" int rts_cube_accumulate_paths(RtsHandle c, uint32_t pulse_index)
+{
+    CHECK_HANDLE(c);
+    CHECK_CLOSED(c);
+    NEED_CUBE(c, "rts_cube_accumulate_paths", "call rts_cube_attach first");
+    if (!c->agg_valid) { rts_set_error("rts_cube_accumulate_paths: call rts_aggregate for this pulse first (the groups' power, delay and phase are its results)"); return RTS_ERR_INVALID; }
+    if (pulse_index >= c->cube.params.n_pulses) { rts_set_error("rts_cube_accumulate_paths: pulse %u >= %u", pulse_index, c->cube.params.n_pulses); return RTS_ERR_INVALID; }
+    return rts_cube_accumulate_paths_device(c, pulse_index, c->agg_base_local);
+}
+
+extern "C" int rts_cube_doppler(RtsHandle c, uint32_t n_fft, void* device_out)
+{
+    CHECK_HANDLE(c);
+    CHECK_CLOSED(c);
+    NEED_CUBE(c, "rts_cube_doppler", "call rts_cube_attach first");
+    if (n_fft < 2 || n_fft > 4096 || (n_fft & (n_fft - 1)) != 0 || n_fft < c->cube.params.n_pulses) {
+        rts_set_error("rts_cube_doppler: n_fft = %u must be a power of two in [max(2, n_pulses = %u), 4096]", n_fft, c->cube.params.n_pulses); return RTS_ERR_INVALID; }
+    const size_t doubles = 2 * (size_t)c->cube.params.n_rx * n_fft * c->cube.params.n_bins;
+    double* out; RTS_HIP(c->cube.doppler.place(device_out, doubles, &out));
+    c->cube.doppler.record(out, doubles); c->cube.doppler_n = n_fft;       // (also when caller-owned: rts_cube_detect without a map takes it)
+    return rts_cube_doppler_device(c, n_fft, out);
+}
+
+extern "C" int rts_cube_doppler_get(RtsHandle c, double* host_out, uint64_t capacity_doubles)
+{
+    CHECK_HANDLE(c);
+    CHECK_CLOSED(c);
+    return rts_cube_copy_out(c, "rts_cube_doppler_get", "no transform (rts_cube_doppler) / null output", c->cube.doppler.valid, c->cube.doppler.p, c->cube.doppler.doubles, host_out, capacity_doubles);
+}
+
+extern "C" int rts_cube_get(RtsHandle c, double* host_out, uint64_t capacity_doubles)
+{
+    CHECK_HANDLE(c);
+    CHECK_CLOSED(c);
+    return rts_cube_copy_out(c, "rts_cube_get", "no cube / null output", true, c->cube.p, 2 * (size_t)c->cube.params.n_rx * c->cube.params.n_pulses * c->cube.params.n_bins, host_out, capacity_doubles);
+}
+
+// ------------------------------------------------------------------------------------- received signal: waveform render, range compression
+// (rts_amd.h: RtsWaveform; the interpolator is rts_waveform.h, shared by the host export and the render kernel, rts_render.hip)
+static int rts_waveform_check(const RtsWaveform* w, const char* who)
+{
+    if (!w) { rts_set_error("%s: null waveform", who); return RTS_ERR_INVALID; }
+    if (w->reserved[0] || w->reserved[1]) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
+    if (w->n_samples == 0 || w->n_samples > RTS_WAVEFORM_MAX_SAMPLES) { rts_set_error("%s: %u samples (1 .. %u)", who, w->n_samples, RTS_WAVEFORM_MAX_SAMPLES); return RTS_ERR_INVALID; }
+    { int rc = rts_taps_check(who, w->taps); if (rc != RTS_OK) return rc; }
+    if (!w->samples) { rts_set_error("%s: null sample array", who); return RTS_ERR_INVALID; }
+    for (uint32_t i = 0; i < 2 * w->n_samples; i++) if (!std::isfinite(w->samples[i])) { rts_set_error("%s: sample %u is not finite", who, i / 2); return RTS_ERR_INVALID; }
+    return RTS_OK;
+}
+
+extern "C" int rts_waveform_eval(const RtsWaveform* w, const double* x, uint32_t n, double* out)
+{
+    int rc = rts_waveform_check(w, "rts_waveform_eval"); if (rc != RTS_OK) return rc;
+    if (n && (!x || !out)) { rts_set_error("rts_waveform_eval: null point or output array"); return RTS_ERR_INVALID; }
+    for (uint32_t i = 0; i < n; i++) rts_wave_eval(w->samples, w->n_samples, w->taps, x[i], &out[2 * (size_t)i], &out[2 * (size_t)i + 1]);
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_set_waveform(RtsHandle c, const RtsWaveform* w)
+{
+    CHECK_HANDLE(c);
+    int rc = rts_waveform_check(w, "rts_cube_set_waveform"); if (rc != RTS_OK) return rc;
+    // the handle's enqueued work may still read the previous waveform: a speculative chain is resolved, then the stream drained
+    if (c->spec_pending) { rc = rts_spec_resolve(c); if (rc != RTS_OK) return rc; }
+    RTS_HIP(hipStreamSynchronize(c->stream));
+    RTS_HIP(c->cube.d_wave.reserve(2 * (size_t)w->n_samples));
+    RTS_HIP(hipMemcpy(c->cube.d_wave.p, w->samples, sizeof(double) * 2 * w->n_samples, hipMemcpyHostToDevice));
+    c->cube.wave_M = w->n_samples; c->cube.wave_L = w->taps; c->cube.wave_set = true;
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_render(RtsHandle c, uint32_t pulse_index, uint32_t source, uint32_t flags, double cspeed, double carrier)
+{
+    CHECK_HANDLE(c);
+    if (source != RTS_RENDER_RAYS && source != RTS_RENDER_PATHS) { rts_set_error("rts_cube_render: unknown source %u (RTS_RENDER_RAYS, RTS_RENDER_PATHS)", source); return RTS_ERR_INVALID; }
+    if (flags & ~RTS_RENDER_DOPPLER) { rts_set_error("rts_cube_render: unknown flags 0x%x", flags); return RTS_ERR_INVALID; }
+    CHECK_CLOSED(c);
+    NEED_CUBE(c, "rts_cube_render", "call rts_cube_attach first");
+    if (!c->cube.wave_set) { rts_set_error("rts_cube_render: no waveform (rts_cube_set_waveform)"); return RTS_ERR_INVALID; }
+    if (pulse_index >= c->cube.params.n_pulses) { rts_set_error("rts_cube_render: pulse %u >= %u", pulse_index, c->cube.params.n_pulses); return RTS_ERR_INVALID; }
+    const bool paths = source == RTS_RENDER_PATHS;
+    if (paths && !c->agg_valid) { rts_set_error("rts_cube_render: RTS_RENDER_PATHS needs rts_aggregate of this pulse first (the groups' power, delay and phase are its results)"); return RTS_ERR_INVALID; }
+    return rts_cube_render_device(c, pulse_index, paths, (flags & RTS_RENDER_DOPPLER) != 0, cspeed, carrier, c->agg_base_local);
+}
+
+extern "C" int rts_cube_compress(RtsHandle c, uint32_t first_pulse, uint32_t n_pulses)
+{
+    CHECK_HANDLE(c);
+    CHECK_CLOSED(c);
+    NEED_CUBE(c, "rts_cube_compress", "call rts_cube_attach first");
+    if (!c->cube.wave_set) { rts_set_error("rts_cube_compress: no waveform (rts_cube_set_waveform)"); return RTS_ERR_INVALID; }
+    const RtsCubeParams& q = c->cube.params;
+    { int rc = rts_pulses_check("rts_cube_compress", first_pulse, n_pulses, q.n_pulses, false); if (rc != RTS_OK) return rc; }
+    if (q.n_bins > RTS_COMPRESS_MAX_BINS) { rts_set_error("rts_cube_compress: %u range bins > %u (RTS_COMPRESS_MAX_BINS: one row of complex128 in a workgroup's LDS)", q.n_bins, RTS_COMPRESS_MAX_BINS); return RTS_ERR_INVALID; }
+    return rts_cube_compress_device(c, first_pulse, n_pulses);
+}
+
+// ------------------------------------------------------------------------------------- receiver noise, CFAR detection
+// (rts_amd.h; the generator is rts_noise.h, shared by the host export and the noise kernel; the kernels are in rts_detect.hip)
+extern "C" int rts_noise_eval(uint64_t seed, const uint64_t* index, uint32_t n, double noise_power, double* out)
+{
+    if (!std::isfinite(noise_power) || noise_power < 0) { rts_set_error("rts_noise_eval: noise_power = %g (finite, >= 0)", noise_power); return RTS_ERR_INVALID; }
+    if (n && (!index || !out)) { rts_set_error("rts_noise_eval: null index or output array"); return RTS_ERR_INVALID; }
+    const double sigma = sqrt(noise_power / 2.0);
+    for (uint32_t j = 0; j < n; j++) rts_noise_sample(seed, index[j], sigma, &out[2 * (size_t)j], &out[2 * (size_t)j + 1]);
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_add_noise(RtsHandle c, uint32_t first_pulse, uint32_t n_pulses, double noise_power, uint64_t seed)
+{
+    CHECK_HANDLE(c);
+    if (!std::isfinite(noise_power) || noise_power < 0) { rts_set_error("rts_cube_add_noise: noise_power = %g (finite, >= 0)", noise_power); return RTS_ERR_INVALID; }
+    CHECK_CLOSED(c);
+    NEED_CUBE(c, "rts_cube_add_noise", "call rts_cube_attach first");
+    const RtsCubeParams& q = c->cube.params;
+    { int rc = rts_pulses_check("rts_cube_add_noise", first_pulse, n_pulses, q.n_pulses, false); if (rc != RTS_OK) return rc; }
+    if ((uintptr_t)c->cube.p & 15u) { rts_set_error("rts_cube_add_noise: the cube's device memory is not 16-byte aligned"); return RTS_ERR_INVALID; }
+    return rts_cube_noise_device(c, first_pulse, n_pulses, sqrt(noise_power / 2.0), seed);
+}
+
+extern "C" int rts_cube_detect(RtsHandle c, const RtsCfarParams* p, const void* device_map, uint32_t n_doppler)
+{
+    CHECK_HANDLE(c);
+    if (!p) { rts_set_error("rts_cube_detect: null parameters"); return RTS_ERR_INVALID; }
+    CHECK_CLOSED(c);
+    NEED_CUBE(c, "rts_cube_detect", "no cube (call rts_cube_attach first)");
+    const double* map = (const double*)device_map;
+    if (map) {
+        if (n_doppler == 0) { rts_set_error("rts_cube_detect: n_doppler = 0 with a caller map"); return RTS_ERR_INVALID; }
+        if ((uintptr_t)map & 15u) { rts_set_error("rts_cube_detect: device_map is not 16-byte aligned"); return RTS_ERR_INVALID; }
+    } else {
+        if (!c->cube.doppler.valid) { rts_set_error("rts_cube_detect: no map (call rts_cube_doppler first, or pass device_map)"); return RTS_ERR_INVALID; }
+        map = c->cube.doppler.p; n_doppler = c->cube.doppler_n;
+    }
+    const uint32_t Gr = p->guard_range, Gd = p->guard_doppler, Tr = p->train_range, Td = p->train_doppler, nb = c->cube.params.n_bins;
+    if (p->mode > RTS_CFAR_SO) { rts_set_error("rts_cube_detect: unknown mode %u (RTS_CFAR_CA, _GO, _SO)", p->mode); return RTS_ERR_INVALID; }
+    if (p->flags & ~RTS_CFAR_LOCAL_MAX) { rts_set_error("rts_cube_detect: unknown flags 0x%x", p->flags); return RTS_ERR_INVALID; }
+    if (p->reserved0 || p->reserved[0] || p->reserved[1]) { rts_set_error("rts_cube_detect: reserved fields must be 0"); return RTS_ERR_INVALID; }
+    if (Tr > RTS_CFAR_MAX_HALF || Td > RTS_CFAR_MAX_HALF || Gr > RTS_CFAR_MAX_HALF || Gd > RTS_CFAR_MAX_HALF) { rts_set_error("rts_cube_detect: guard_range, guard_doppler, train_range, train_doppler are at most %u each", RTS_CFAR_MAX_HALF); return RTS_ERR_INVALID; }
+    if (Tr + Td == 0) { rts_set_error("rts_cube_detect: train_range + train_doppler = 0 (no training cells)"); return RTS_ERR_INVALID; }
+    if (Gr + Tr > RTS_CFAR_MAX_HALF) { rts_set_error("rts_cube_detect: guard_range + train_range = %u > %u", Gr + Tr, RTS_CFAR_MAX_HALF); return RTS_ERR_INVALID; }
+    if (Gd + Td > RTS_CFAR_MAX_HALF) { rts_set_error("rts_cube_detect: guard_doppler + train_doppler = %u > %u", Gd + Td, RTS_CFAR_MAX_HALF); return RTS_ERR_INVALID; }
+    if (2 * (Gd + Td) + 1 > n_doppler) { rts_set_error("rts_cube_detect: guard_doppler + train_doppler = %u: the window (%u rows) exceeds n_doppler = %u", Gd + Td, 2 * (Gd + Td) + 1, n_doppler); return RTS_ERR_INVALID; }
+    if (Gr + Tr >= nb) { rts_set_error("rts_cube_detect: guard_range + train_range = %u >= n_bins = %u", Gr + Tr, nb); return RTS_ERR_INVALID; }
+    const bool has_pfa = p->pfa != 0.0, has_alpha = p->alpha != 0.0;
+    if (has_pfa && !(p->pfa > 0.0 && p->pfa < 1.0)) { rts_set_error("rts_cube_detect: pfa = %g outside (0, 1)", p->pfa); return RTS_ERR_INVALID; }
+    if (has_pfa == has_alpha) { rts_set_error("rts_cube_detect: give exactly one of pfa and alpha"); return RTS_ERR_INVALID; }
+    if (has_alpha && !(p->alpha > 0.0 && std::isfinite(p->alpha))) { rts_set_error("rts_cube_detect: alpha = %g (finite, > 0)", p->alpha); return RTS_ERR_INVALID; }
+    if (p->mode != RTS_CFAR_CA && has_pfa) { rts_set_error("rts_cube_detect: pfa is for mode RTS_CFAR_CA only (GO / SO take alpha)"); return RTS_ERR_INVALID; }
+    if (p->mode != RTS_CFAR_CA && Tr == 0) { rts_set_error("rts_cube_detect: train_range = 0 with GO / SO (the halves are range halves)"); return RTS_ERR_INVALID; }
+    if (!(p->pri >= 0.0) || !std::isfinite(p->pri)) { rts_set_error("rts_cube_detect: pri = %g (finite, >= 0)", p->pri); return RTS_ERR_INVALID; }
+    c->cube.det_valid = false;
+    return rts_cube_detect_device(c, *p, map, n_doppler, p->max_detections ? p->max_detections : RTS_CFAR_DEFAULT_MAX_DETECTIONS);
+}
+
+extern "C" int rts_cube_detections_get(RtsHandle c, RtsDetection* out, uint32_t capacity, uint32_t* n_out)
+{
+    CHECK_HANDLE(c);
+    if (!n_out || (capacity && !out)) { rts_set_error("rts_cube_detections_get: null output"); return RTS_ERR_INVALID; }
+    if (!c->cube.det_valid) { rts_set_error("rts_cube_detections_get: no detection list (rts_cube_detect; a list ends at rts_cube_attach)"); return RTS_ERR_INVALID; }
+    RTS_HIP(hipStreamSynchronize(c->stream));
+    uint32_t total = 0;
+    RTS_HIP(hipMemcpy(&total, c->cube.d_det_off.p + c->cube.det_nseg, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    *n_out = total;
+    uint32_t n = total < c->cube.det_max ? total : c->cube.det_max;
+    if (n > capacity) n = capacity;
+    if (n) RTS_HIP(hipMemcpy(out, c->cube.d_det.p, sizeof(RtsDetection) * n, hipMemcpyDeviceToHost));
+    if (n < total) { rts_set_error("rts_cube_detections_get: %u of %u detections copied (max_detections %u, capacity %u)", n, total, c->cube.det_max, capacity); return RTS_ERR_CAPACITY; }
+    return RTS_OK;
+}
+
+// ------------------------------------------------------------------------------------- tapered slow-time spectrogram
+// (rts_amd.h: RtsStftParams; the tree and the launch plan are rts_stft.h, shared by the host export and the kernel, rts_stft.hip)
+static int rts_stft_check(const RtsStftParams* p, const RtsCubeParams& q, const char* who, RtsStftPlan* plan)
+{
+    if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
+    if (p->reserved[0] || p->reserved[1]) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
+    if (p->flags & ~(RTS_STFT_POWER | RTS_STFT_SUM_BINS)) { rts_set_error("%s: unknown flags 0x%x", who, p->flags); return RTS_ERR_INVALID; }
+    if ((p->flags & RTS_STFT_SUM_BINS) && !(p->flags & RTS_STFT_POWER)) { rts_set_error("%s: flags: RTS_STFT_SUM_BINS needs RTS_STFT_POWER", who); return RTS_ERR_INVALID; }
+    if (p->n_fft < 2u || p->n_fft > RTS_STFT_MAX_FFT || (p->n_fft & (p->n_fft - 1u)) != 0u) { rts_set_error("%s: n_fft = %u must be a power of two in [2, %u]", who, p->n_fft, RTS_STFT_MAX_FFT); return RTS_ERR_INVALID; }
+    { int rc = rts_pulses_check(who, p->first_pulse, p->n_pulses, q.n_pulses, true); if (rc != RTS_OK) return rc; }
+    if (p->window_len == 0 || p->window_len > p->n_fft || p->window_len > p->n_pulses) { rts_set_error("%s: window_len = %u (1 .. n_fft = %u, <= n_pulses = %u)", who, p->window_len, p->n_fft, p->n_pulses); return RTS_ERR_INVALID; }
+    if (p->hop == 0) { rts_set_error("%s: hop = 0 (>= 1)", who); return RTS_ERR_INVALID; }
+    if (p->first_bin >= q.n_bins || p->n_bins > q.n_bins - p->first_bin) { rts_set_error("%s: first_bin = %u, n_bins = %u: inside the cube's %u bins", who, p->first_bin, p->n_bins, q.n_bins); return RTS_ERR_INVALID; }
+    if (p->window) for (uint32_t i = 0; i < p->window_len; i++) if (!std::isfinite(p->window[i])) { rts_set_error("%s: window[%u] is not finite", who, i); return RTS_ERR_INVALID; }
+    const uint32_t n_gate = p->n_bins ? p->n_bins : q.n_bins - p->first_bin;
+    *plan = rts_stft_plan(q.n_rx, p->n_pulses, p->window_len, p->hop, p->n_fft, n_gate, p->flags);
+    if (!plan->supported) {
+        if (q.n_rx > RTS_STFT_MAX_RX) rts_set_error("%s: n_rx = %u receivers: more than %u (the launch grid)", who, q.n_rx, RTS_STFT_MAX_RX);
+        else rts_set_error("%s: n_frames = %u frames x %u workgroups per frame (hop, n_bins): more than %u (the launch grid)", who, plan->n_frames, plan->tiles, RTS_STFT_MAX_GRID_X);
+        return RTS_ERR_INVALID;
+    }
+    return RTS_OK;
+}
+
+extern "C" int rts_window_make(uint32_t kind, uint32_t n, double* out)
+{
+    if (n == 0) { rts_set_error("rts_window_make: n = 0"); return RTS_ERR_INVALID; }
+    if (kind > RTS_WINDOW_BLACKMAN) { rts_set_error("rts_window_make: unknown kind %u", kind); return RTS_ERR_INVALID; }
+    if (!out) { rts_set_error("rts_window_make: null output array"); return RTS_ERR_INVALID; }
+    rts_stft_window_host(kind, n, out);
+    return RTS_OK;
+}
+
+extern "C" int rts_stft_eval(const RtsCubeParams* q, const double* cube, const RtsStftParams* p, double* out, uint32_t* n_frames_out)
+{
+    if (!q || q->n_rx == 0 || q->n_pulses == 0 || q->n_bins == 0) { rts_set_error("rts_stft_eval: bad cube parameters"); return RTS_ERR_INVALID; }
+    RtsStftPlan plan;
+    int rc = rts_stft_check(p, *q, "rts_stft_eval", &plan); if (rc != RTS_OK) return rc;
+    if (!cube || !out) { rts_set_error("rts_stft_eval: null cube or output array"); return RTS_ERR_INVALID; }
+    std::vector<double> work(4 * (size_t)p->n_fft);
+    rts_stft_eval_host(q, cube, p, plan, out, work.data());
+    if (n_frames_out) *n_frames_out = plan.n_frames;
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_spectrogram(RtsHandle c, const RtsStftParams* p, void* device_out, uint32_t* n_frames_out)
+{
+    CHECK_HANDLE(c);
+    NEED_CUBE(c, "rts_cube_spectrogram", "no cube (call rts_cube_attach first)");
+    const RtsCubeParams& q = c->cube.params;
+    RtsStftPlan plan;
+    int rc = rts_stft_check(p, q, "rts_cube_spectrogram", &plan); if (rc != RTS_OK) return rc;
+    if ((uintptr_t)device_out & 15u) { rts_set_error("rts_cube_spectrogram: device_out is not 16-byte aligned"); return RTS_ERR_INVALID; }
+    CHECK_CLOSED(c);
+    double* out; RTS_HIP(c->cube.stft.place(device_out, plan.out_doubles, &out));
+    // the window -> pinned staging -> the device, on the stream (window_len <= RTS_STFT_MAX_FFT: one size for every call)
+    const double* win = nullptr;
+    if (p->window) {
+        double* w = nullptr;
+        RTS_HIP(c->cube.stft_win.begin(RTS_STFT_MAX_FFT, RTS_STFT_MAX_FFT, RTS_STFT_MAX_FFT, &w));
+        memcpy(w, p->window, sizeof(double) * p->window_len);
+        RTS_HIP(c->cube.stft_win.send(p->window_len, c->stream));
+        win = c->cube.stft_win.dev.p;
+    }
+    if (!device_out) c->cube.stft.record(out, plan.out_doubles);
+    if (n_frames_out) *n_frames_out = plan.n_frames;
+    return rts_cube_stft_device(c, *p, plan, win, out);
+}
+
+extern "C" int rts_cube_spectrogram_get(RtsHandle c, double* host_out, uint64_t capacity_doubles)
+{
+    CHECK_HANDLE(c);
+    return rts_cube_copy_out(c, "rts_cube_spectrogram_get", "no library-owned spectrogram (rts_cube_spectrogram with device_out NULL; a spectrogram ends at rts_cube_attach) / null output", c->cube.stft.valid, c->cube.stft.p, c->cube.stft.doubles, host_out, capacity_doubles);
+}
+
+// ------------------------------------------------------------------------------------- backprojection imaging
+// (rts_amd.h: RtsImageParams; the arithmetic and the launch plan are rts_image.h, shared by the host export and the kernel, rts_image.hip)
+static int rts_image_check(const RtsImageParams* p, const RtsCubeParams& q, const char* who)
+{
+    if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
+    if (p->n_x == 0 || p->n_y == 0 || (uint64_t)p->n_x * p->n_y > RTS_IMAGE_MAX_PIXELS) { rts_set_error("%s: n_x = %u, n_y = %u (each >= 1, n_x * n_y <= %u)", who, p->n_x, p->n_y, RTS_IMAGE_MAX_PIXELS); return RTS_ERR_INVALID; }
+    { int rc = rts_taps_check(who, p->taps); if (rc != RTS_OK) return rc; }
+    if (p->flags & ~RTS_IMAGE_ACCUMULATE) { rts_set_error("%s: unknown flags 0x%x", who, p->flags); return RTS_ERR_INVALID; }
+    if (p->reserved[0] || p->reserved[1]) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
+    { int rc = rts_pulses_check(who, p->first_pulse, p->n_pulses, q.n_pulses, true); if (rc != RTS_OK) return rc; }
+    if (!std::isfinite(p->cspeed) || !(p->cspeed > 0.0)) { rts_set_error("%s: cspeed = %g (finite, > 0)", who, p->cspeed); return RTS_ERR_INVALID; }
+    if (!std::isfinite(p->carrier) || p->carrier < 0.0) { rts_set_error("%s: carrier = %g (finite, >= 0)", who, p->carrier); return RTS_ERR_INVALID; }
+    for (int k = 0; k < 3; k++) {
+        if (!std::isfinite(p->origin[k])) { rts_set_error("%s: origin[%d] is not finite", who, k); return RTS_ERR_INVALID; }
+        if (!std::isfinite(p->step_x[k])) { rts_set_error("%s: step_x[%d] is not finite", who, k); return RTS_ERR_INVALID; }
+        if (!std::isfinite(p->step_y[k])) { rts_set_error("%s: step_y[%d] is not finite", who, k); return RTS_ERR_INVALID; }
+    }
+    if (!p->tx_position) { rts_set_error("%s: null tx_position", who); return RTS_ERR_INVALID; }
+    if (!p->rx_position) { rts_set_error("%s: null rx_position", who); return RTS_ERR_INVALID; }
+    for (size_t i = 0; i < 3 * (size_t)p->n_pulses; i++) if (!std::isfinite(p->tx_position[i])) { rts_set_error("%s: tx_position of pulse %zu is not finite", who, i / 3); return RTS_ERR_INVALID; }
+    for (size_t i = 0; i < 3 * (size_t)q.n_rx * p->n_pulses; i++) if (!std::isfinite(p->rx_position[i])) { rts_set_error("%s: rx_position of receiver %zu, pulse %zu is not finite", who, i / 3 / p->n_pulses, i / 3 % p->n_pulses); return RTS_ERR_INVALID; }
+    if (p->pulse_weight) for (uint32_t j = 0; j < p->n_pulses; j++) if (!std::isfinite(p->pulse_weight[j])) { rts_set_error("%s: pulse_weight[%u] is not finite", who, j); return RTS_ERR_INVALID; }
+    if (!rts_image_plan(p->n_x, p->n_y, q.n_rx, p->n_pulses, 0u).supported) { rts_set_error("%s: n_rx = %u receivers / n_pulses = %u: more than %u receivers or chunks of %u pulses", who, q.n_rx, p->n_pulses, RTS_IMAGE_GRID_MAX, RTS_IMAGE_PULSE_CHUNK); return RTS_ERR_INVALID; }
+    return RTS_OK;
+}
+
+extern "C" int rts_backproject_eval(const RtsCubeParams* q, const double* cube, const RtsImageParams* p, double* out)
+{
+    if (!q || q->n_rx == 0 || q->n_pulses == 0 || q->n_bins == 0 || !(q->dt > 0) || !std::isfinite(q->dt) || !std::isfinite(q->t0)) { rts_set_error("rts_backproject_eval: bad cube parameters"); return RTS_ERR_INVALID; }
+    int rc = rts_image_check(p, *q, "rts_backproject_eval"); if (rc != RTS_OK) return rc;
+    if (!cube || !out) { rts_set_error("rts_backproject_eval: null cube or output array"); return RTS_ERR_INVALID; }
+    rts_image_eval_host(q, cube, p, out);
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_backproject(RtsHandle c, const RtsImageParams* p, void* device_out)
+{
+    CHECK_HANDLE(c);
+    NEED_CUBE(c, "rts_cube_backproject", "no cube (call rts_cube_attach first)");
+    const RtsCubeParams& q = c->cube.params;
+    int rc = rts_image_check(p, q, "rts_cube_backproject"); if (rc != RTS_OK) return rc;
+    if ((uintptr_t)device_out & 15u) { rts_set_error("rts_cube_backproject: device_out is not 16-byte aligned"); return RTS_ERR_INVALID; }
+    if ((p->flags & RTS_IMAGE_ACCUMULATE) && !device_out && !(c->cube.image.valid && c->cube.img_nx == p->n_x && c->cube.img_ny == p->n_y)) {
+        rts_set_error("rts_cube_backproject: RTS_IMAGE_ACCUMULATE without device_out needs a library-owned image of the same n_x, n_y"); return RTS_ERR_INVALID; }
+    CHECK_CLOSED(c);
+    const RtsImagePlan plan = rts_image_plan(p->n_x, p->n_y, q.n_rx, p->n_pulses, c->cube.img_split_below);
+    const size_t doubles = 2 * (size_t)q.n_rx * p->n_y * p->n_x;
+    double* out; RTS_HIP(c->cube.image.place(device_out, doubles, &out));       // (accumulate: the shape is the same, so the buffer stays)
+    // the geometry [tx | rx | w] -> pinned staging -> the device, on the stream
+    const size_t P = p->n_pulses, n_geo = 3 * P + 3 * (size_t)q.n_rx * P + P;
+    double* g = nullptr;
+    RTS_HIP(c->cube.img_geo.begin(n_geo, std::max<size_t>(n_geo + n_geo / 2, 4096), n_geo, &g));
+    memcpy(g, p->tx_position, sizeof(double) * 3 * P);
+    memcpy(g + 3 * P, p->rx_position, sizeof(double) * 3 * q.n_rx * P);
+    for (size_t j = 0; j < P; j++) g[3 * P + 3 * (size_t)q.n_rx * P + j] = p->pulse_weight ? p->pulse_weight[j] : 1.0;
+    RTS_HIP(c->cube.img_geo.send(n_geo, c->stream));
+    if (!device_out) { c->cube.image.record(out, doubles); c->cube.img_nx = p->n_x; c->cube.img_ny = p->n_y; }
+    return rts_cube_backproject_device(c, *p, plan, c->cube.img_geo.dev.p, out);
+}
+
+extern "C" int rts_cube_image_get(RtsHandle c, double* host_out, uint64_t capacity_doubles)
+{
+    CHECK_HANDLE(c);
+    return rts_cube_copy_out(c, "rts_cube_image_get", "no library-owned image (rts_cube_backproject with device_out NULL; an image ends at rts_cube_attach) / null output", c->cube.image.valid, c->cube.image.p, c->cube.image.doubles, host_out, capacity_doubles);
+}

@@ -24,11 +24,11 @@ __global__ void __launch_bounds__(RTS_NOISE_THREADS) k_cube_noise(double2* __res
 
 int rts_cube_noise_device(RtsContext* c, uint32_t first_pulse, uint32_t n_pulses, double sigma, uint64_t seed)
 {
-    const RtsCubeParams& q = c->cube_params;
+    const RtsCubeParams& q = c->cube.params;
     const uint64_t per_rx = (uint64_t)n_pulses * q.n_bins;
     if (per_rx == 0 || sigma == 0.0) return RTS_OK;
     dim3 grid((unsigned)((per_rx + RTS_NOISE_THREADS - 1) / RTS_NOISE_THREADS), q.n_rx);
-    k_cube_noise<<<grid, RTS_NOISE_THREADS, 0, c->stream>>>((double2*)c->cube, q.n_pulses, q.n_bins, first_pulse, per_rx, sigma, seed);
+    k_cube_noise<<<grid, RTS_NOISE_THREADS, 0, c->stream>>>((double2*)c->cube.p, q.n_pulses, q.n_bins, first_pulse, per_rx, sigma, seed);
     RTS_HIP(hipGetLastError());
     return RTS_OK;
 }
@@ -168,7 +168,7 @@ __global__ void __launch_bounds__(RTS_CFAR_THREADS) k_cfar(const RtsCfarArgs a)
 
 int rts_cube_detect_device(RtsContext* c, const RtsCfarParams& p, const double* map, uint32_t n_doppler, uint32_t max_det)
 {
-    const RtsCubeParams& q = c->cube_params;
+    const RtsCubeParams& q = c->cube.params;
     RtsCfarArgs a;
     a.map = (const double2*)map; a.nd = n_doppler; a.nb = q.n_bins; a.n_rt = (q.n_bins + RTS_CFAR_TR - 1) / RTS_CFAR_TR;
     a.gr = (int)p.guard_range; a.gd = (int)p.guard_doppler; a.tr = (int)p.train_range; a.td = (int)p.train_doppler;
@@ -178,18 +178,18 @@ int rts_cube_detect_device(RtsContext* c, const RtsCfarParams& p, const double* 
     const size_t n_seg = (size_t)q.n_rx * n_doppler * a.n_rt;
     if (n_seg + 1 > 0xffffffffull) { rts_set_error("rts_cube_detect: %zu segments: the map is too large", n_seg); return RTS_ERR_INVALID; }
     a.n_seg = (uint32_t)n_seg; a.max_det = max_det;
-    RTS_HIP(c->d_det_cnt.reserve(n_seg + 1)); RTS_HIP(c->d_det_off.reserve(n_seg + 1)); RTS_HIP(c->d_det.reserve(max_det));
+    RTS_HIP(c->cube.d_det_cnt.reserve(n_seg + 1)); RTS_HIP(c->cube.d_det_off.reserve(n_seg + 1)); RTS_HIP(c->cube.d_det.reserve(max_det));
     size_t tmp = 0;
-    RTS_HIP(rocprim::exclusive_scan(nullptr, tmp, c->d_det_cnt.p, c->d_det_off.p, 0u, n_seg + 1, rocprim::plus<uint32_t>(), c->stream));
-    RTS_HIP(c->d_det_tmp.reserve(tmp + 1));
-    a.cnt = c->d_det_cnt.p; a.off = c->d_det_off.p; a.out = c->d_det.p;
+    RTS_HIP(rocprim::exclusive_scan(nullptr, tmp, c->cube.d_det_cnt.p, c->cube.d_det_off.p, 0u, n_seg + 1, rocprim::plus<uint32_t>(), c->stream));
+    RTS_HIP(c->cube.d_det_tmp.reserve(tmp + 1));
+    a.cnt = c->cube.d_det_cnt.p; a.off = c->cube.d_det_off.p; a.out = c->cube.d_det.p;
     const size_t lds = sizeof(double) * ((size_t)(RTS_CFAR_TD + 2 * a.hd) * (RTS_CFAR_TR + 2 * a.hr) + 2 * (size_t)RTS_CFAR_TD * (RTS_CFAR_TR + 2 * a.hr));      // <= 60 KiB
     dim3 grid(a.n_rt, (n_doppler + RTS_CFAR_TD - 1) / RTS_CFAR_TD, q.n_rx);
     k_cfar<false><<<grid, RTS_CFAR_THREADS, lds, c->stream>>>(a);
     RTS_HIP(hipGetLastError());
-    RTS_HIP(rocprim::exclusive_scan(c->d_det_tmp.p, tmp, c->d_det_cnt.p, c->d_det_off.p, 0u, n_seg + 1, rocprim::plus<uint32_t>(), c->stream));
+    RTS_HIP(rocprim::exclusive_scan(c->cube.d_det_tmp.p, tmp, c->cube.d_det_cnt.p, c->cube.d_det_off.p, 0u, n_seg + 1, rocprim::plus<uint32_t>(), c->stream));
     k_cfar<true><<<grid, RTS_CFAR_THREADS, lds, c->stream>>>(a);
     RTS_HIP(hipGetLastError());
-    c->det_nseg = (uint32_t)n_seg; c->det_max = max_det; c->det_valid = true;
+    c->cube.det_nseg = (uint32_t)n_seg; c->cube.det_max = max_det; c->cube.det_valid = true;
     return RTS_OK;
 }

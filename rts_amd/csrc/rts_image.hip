@@ -67,12 +67,12 @@ __global__ void __launch_bounds__(256) k_backproject_sum(const double2* __restri
     out[i] = s;
 }
 
-// geo: the call's [tx | rx | w] block on the device (rts_api.hip uploads it on the stream before this)
+// geo: the call's [tx | rx | w] block on the device (rts_cube_api.hip uploads it on the stream before this: RtsCubeState::img_geo)
 int rts_cube_backproject_device(RtsContext* c, const RtsImageParams& p, const RtsImagePlan& plan, const double* geo, double* out)
 {
-    const RtsCubeParams& q = c->cube_params;
+    const RtsCubeParams& q = c->cube.params;
     RtsImageArgs a;
-    a.cube = c->cube; a.n_pulses_cube = q.n_pulses; a.n_bins = q.n_bins; a.n_rx = q.n_rx; a.t0 = q.t0; a.dt = q.dt;
+    a.cube = c->cube.p; a.n_pulses_cube = q.n_pulses; a.n_bins = q.n_bins; a.n_rx = q.n_rx; a.t0 = q.t0; a.dt = q.dt;
     a.n_x = p.n_x; a.n_y = p.n_y; a.taps = p.taps; a.accumulate = (p.flags & RTS_IMAGE_ACCUMULATE) ? 1u : 0u;
     a.first_pulse = p.first_pulse; a.n_pulses = p.n_pulses; a.n_chunks = plan.n_chunks; a.split = plan.split ? 1u : 0u;
     a.tiles_x = plan.tiles_x; a.tw_log2 = plan.tw_log2;
@@ -80,7 +80,7 @@ int rts_cube_backproject_device(RtsContext* c, const RtsImageParams& p, const Rt
     a.cspeed = p.cspeed; a.carrier = p.carrier;
     a.tx = geo; a.rx = geo + 3 * (size_t)p.n_pulses; a.w = a.rx + 3 * (size_t)q.n_rx * p.n_pulses;
     a.out = (double2*)out; a.scratch = nullptr;
-    if (plan.split) { RTS_HIP(c->d_img_scratch.reserve(2 * plan.scratch)); a.scratch = (double2*)c->d_img_scratch.p; }
+    if (plan.split) { RTS_HIP(c->cube.d_img_scratch.reserve(2 * plan.scratch)); a.scratch = (double2*)c->cube.d_img_scratch.p; }
     dim3 grid(plan.tiles_x * plan.tiles_y, plan.split ? plan.n_chunks : 1u, q.n_rx);
     k_backproject<<<grid, RTS_IMAGE_TILE, 0, c->stream>>>(a);
     RTS_HIP(hipGetLastError());

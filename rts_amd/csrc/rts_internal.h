@@ -13,7 +13,7 @@
 #include "rts_noise.h"
 #include "rts_image.h"            // the arithmetic of a backprojected pixel and the host-only plan of its launch
 #include "rts_stft.h"             // the tree of the slow-time spectrogram and the host-only plan of its launch
-#include "rts_owned.h"            // DevBuf, PinBuf: device and pinned host memory that frees itself
+#include "rts_owned.h"            // DevBuf, PinBuf, StagedUpload: device and pinned host memory that frees itself
 #include "rts_launch_plan.h"      // RTS_BLOCK, RTS_WTILE, RTS_COOP_GROUP, RTS_STACK_OVF and the host arithmetic of a launch
 #include "rts_post_plan.h"        // RTS_SMALL_CAP32 / 64, RTS_AGG_TILE and the host arithmetic of the post-processing
 
@@ -286,6 +286,46 @@ struct RtsHostMirror {
 // rts_aggregate enqueues; the table is read (stream wait + pinned block -> RtsGroup records) by the first call that needs it
 struct RtsAggPending { bool valid = false, rows = false; uint32_t R = 0, D = 0, spec = 0; RtsKeyPlan key = {}; uint64_t base = 0; double* gsum = nullptr; };
 
+// A derived output of the attached cube (Doppler map, image, spectrogram): `own` when the library allocates it, p / doubles: where the
+// last one went and its size; valid: it is a product of the ATTACHED cube, for its rts_cube_*_get -- every product ends at rts_cube_attach
+// (RtsCubeState::end_products).  The image and the spectrogram are recorded only when library-owned (a caller-owned
+// output leaves the record alone), the Doppler map also when caller-owned (rts_cube_detect without a map takes it).
+struct RtsCubeProduct {
+    DevBuf<double> own; double* p = nullptr; size_t doubles = 0; bool valid = false;
+    // where a call's n doubles go: the caller's memory, or `own` made large enough.  A regrow frees the block a record may name: the record
+    // ends BEFORE it, so a call that fails after this (the reserve itself, a staged upload) leaves no getter a freed address
+    hipError_t place(void* device_out, size_t n, double** out)
+    {
+        *out = (double*)device_out; if (*out) return hipSuccess;
+        if (n > own.cap) { p = nullptr; doubles = 0; valid = false; }
+        const hipError_t e = own.reserve(n); *out = own.p; return e;
+    }
+    void record(double* out, size_t n) { p = out; doubles = n; valid = true; }
+};
+
+// The cube part of a handle: it shares nothing with the pulse path but the handle (rts_cube_api.hip; the launchers of rts_post.hip,
+// rts_render.hip, rts_detect.hip, rts_image.hip, rts_stft.hip).
+struct RtsCubeState {
+    RtsCubeParams params = {}; double* p = nullptr; DevBuf<double> own; bool set = false;      // p: the attached cube, own when the library allocated it
+    DevBuf<double> d_wave; uint32_t wave_M = 0, wave_L = 0; bool wave_set = false;         // the transmit waveform (rts_cube_set_waveform): M interleaved samples, L taps
+    RtsCubeProduct doppler; uint32_t doppler_n = 0;       // slow-time transform of the cube (rts_cube_doppler) and its n_fft
+    // CFAR detection (rts_cube_detect, rts_detect.hip): per-segment counts -> exclusive scan (offsets; element n_seg: the total),
+    // the records of the last detection and how many it may hold; det_valid: a list exists for rts_cube_detections_get
+    DevBuf<uint32_t> d_det_cnt, d_det_off; DevBuf<uint8_t> d_det_tmp; DevBuf<RtsDetection> d_det; uint32_t det_nseg = 0, det_max = 0; bool det_valid = false;
+    // backprojection (rts_cube_backproject, rts_image.hip): the image and its shape, for rts_cube_image_get / RTS_IMAGE_ACCUMULATE; the
+    // call's geometry [tx | rx | w] goes through a staged upload; the chunk sums of a split launch
+    RtsCubeProduct image; uint32_t img_nx = 0, img_ny = 0;
+    StagedUpload<double> img_geo; DevBuf<double> d_img_scratch;
+    uint32_t img_split_below = RTS_IMAGE_SPLIT_BELOW;      // RTS_IMAGE_SPLIT_BELOW: workgroups below which the pulse chunks go on the grid (tests: 0 = never, 65536 = whenever there are two chunks)
+    // spectrogram (rts_cube_spectrogram, rts_stft.hip): the output, for rts_cube_spectrogram_get; the call's window goes through a
+    // staged upload; the tile sums of RTS_STFT_SUM_BINS
+    RtsCubeProduct stft;
+    StagedUpload<double> stft_win; DevBuf<double> d_stft_part;
+    // every product belongs to the cube it was made from: the Doppler map (which rts_cube_detect may take), the detection list, the image
+    // and the spectrogram end when another cube is attached
+    void end_products() { doppler.valid = false; det_valid = false; image.valid = false; stft.valid = false; }
+};
+
 struct RtsContext {
     RtsParams params;
     uint32_t depth = 0;             // D = max_refr + max_refl
@@ -371,39 +411,21 @@ struct RtsContext {
     std::vector<PerRayData> v_rays; std::vector<int32_t> v_paths; std::vector<double> v_angles, v_apower, v_adoppler, v_adelay, v_aphase; std::vector<uint64_t> v_slots; std::vector<int32_t> v_apm;      // the views' fallback storage (sets beyond the mirror's capacity)
     std::vector<PerRayData> v_agg_rays; unsigned v_recv_have = 0;      // rts_aggregated_view's own scratch (never the received view's storage); bits: which of v_rays / v_paths / v_angles / v_slots hold THIS pulse's set already
     PinBuf<RtsRxDev> pin_rx; std::vector<RtsRxDev> rx_host;      // receivers: last values set (an unchanged set is not uploaded again) and the pinned staging of the asynchronous upload
-    RtsCubeParams cube_params; double* cube = nullptr; DevBuf<double> d_cube_own; bool cube_set = false;
-    DevBuf<double> d_doppler_own; double* doppler = nullptr; uint32_t doppler_n = 0;       // slow-time transform of the cube (rts_cube_doppler)
-    DevBuf<double> d_wave; uint32_t wave_M = 0, wave_L = 0; bool wave_set = false;         // the transmit waveform (rts_cube_set_waveform): M interleaved samples, L taps
-    // CFAR detection (rts_cube_detect, rts_detect.hip): per-segment counts -> exclusive scan (offsets; element n_seg: the total),
-    // the records of the last detection and how many it may hold; det_valid: a list exists for rts_cube_detections_get
-    DevBuf<uint32_t> d_det_cnt, d_det_off; DevBuf<uint8_t> d_det_tmp; DevBuf<RtsDetection> d_det; uint32_t det_nseg = 0, det_max = 0; bool det_valid = false;
-    // backprojection (rts_cube_backproject, rts_image.hip): the library-owned image and its shape; img_valid: it holds an image of the
-    // attached cube, for rts_cube_image_get / RTS_IMAGE_ACCUMULATE (a caller-owned output leaves it alone); the call's geometry [tx | rx | w] goes through a pinned staging
-    // block that is rewritten only after the copy of the previous call's has run (ev_img); the chunk sums of a split launch
-    DevBuf<double> d_image_own, d_img_geo, d_img_scratch; uint32_t img_nx = 0, img_ny = 0; bool img_valid = false;
-    PinBuf<double> pin_img; hipEvent_t ev_img = nullptr; bool ev_img_armed = false;
-    uint32_t img_split_below = RTS_IMAGE_SPLIT_BELOW;      // RTS_IMAGE_SPLIT_BELOW: workgroups below which the pulse chunks go on the grid (tests: 0 = never, 65536 = whenever there are two chunks)
-    // spectrogram (rts_cube_spectrogram, rts_stft.hip): the library-owned output and its size in doubles; stft_valid: it holds a spectrogram
-    // of the attached cube, for rts_cube_spectrogram_get (a caller-owned output leaves it alone); the call's window goes through a pinned
-    // staging block that is rewritten only after the copy of the previous call's has run (ev_stft); the tile sums of RTS_STFT_SUM_BINS
-    DevBuf<double> d_stft_own, d_stft_win, d_stft_part; size_t stft_doubles = 0; bool stft_valid = false;
-    PinBuf<double> pin_stft; hipEvent_t ev_stft = nullptr; bool ev_stft_armed = false;
-    bool doppler_fresh = false;         // rts_cube_doppler ran on the attached cube (rts_cube_detect without a map takes its output)
+    RtsCubeState cube;                  // the complex return cube and what is derived from it (rts_cube_api.hip)
     bool agg_delay_in = true;           // rts_aggregate_device: the delay / phase arrays carry initial sums (rs::kernel_wrapper's in-out arguments); false: they start at zero
     int64_t agg_base_local = 0;         // pathMatch value of received ray i after rts_aggregate = agg_base_local + i
     PinBuf<RtsPinned> pin;      // pinned host staging (one RtsPinned) and its address on the device (pin.dev): kernels write the small per-pulse read-backs (counters, group table) straight into it
     bool rcs_uploaded = false; DevBuf<double> d_rcsval; int n_cu = 0; bool stats_pending = false; bool agg_timed = false, fin_timed = false;
     RtsStats stats;
-    // tabulated patterns (rts_set_patterns): one device buffer per handle, and the per-pulse receiver rows behind a pinned staging block
-    // that is rewritten only after the copy of the previous rows has run (ev_pat)
+    // tabulated patterns (rts_set_patterns): one device buffer per handle, and the per-pulse receiver rows behind a staged upload
     DevBuf<char> d_pat; uint32_t pat_n_rx = 0, pat_n_targets = 0; bool pat_set = false;
-    DevBuf<double> d_pat_rx; PinBuf<double> pin_pat; hipEvent_t ev_pat = nullptr; bool ev_pat_armed = false;
+    StagedUpload<double> pat_rx;
     double pulse_org[3] = {0, 0, 0}, pulse_dir[2] = {0, 0}; bool pulse_traced = false;      // the last traced pulse's ray_origin / tx_dir; false after rts_kernel_wrapper_on
     double lap_s[8] = {0, 0, 0, 0, 0, 0, 0, 0}; uint64_t lap_n[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // RTS_LAP=1: host time per section of rts_trace_pulse_begin
     RtsGate* gate = nullptr; bool pulse_open = false;   // gate: never null after rts_create
     // Every raw handle above starts null and the destructor skips what is null: `delete c` is right for a handle that rts_create
     // left half built.  The body (rts_api.hip) drains the streams, drops the shared objects and destroys the events and streams; the
-    // DevBuf / PinBuf members free themselves after it.  The caller makes the handle's device current first.
+    // DevBuf / PinBuf / StagedUpload members free themselves after it.  The caller makes the handle's device current first.
     ~RtsContext();
 };
 // the (receiver, path) aggregation key of depth D among n_targets targets and n_rx receivers, and of the handle's own received sets
@@ -455,3 +477,10 @@ int rts_debug_stage(RtsContext* c, const char* name);
 
 #define RTS_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
     rts_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return RTS_ERR_HIP; } } while (0)
+
+// every entry point that takes a handle (rts_api.hip, rts_cube_api.hip) makes its device current ...
+#define CHECK_HANDLE(c) do { if (!(c)) { rts_set_error("null handle"); return RTS_ERR_INVALID; } RTS_HIP(hipSetDevice((c)->device)); } while (0)
+// ... and those that consume a pulse's results complete a pulse that was begun but not yet ended
+int rts_spec_resolve(RtsContext* c);        // rts_api.hip: the outcome of a chain that was enqueued on the device-side count
+#define CHECK_CLOSED(c) do { if ((c)->pulse_open) { int rc_ = rts_trace_pulse_end(c); if (rc_ != RTS_OK) return rc_; } \
+                             if ((c)->spec_pending) { int rc_ = rts_spec_resolve(c); if (rc_ != RTS_OK) return rc_; } } while (0)

@@ -1,6 +1,7 @@
-// rts_owned.h -- the two owning buffer types of librts_amd.so: device memory (DevBuf) and pinned host memory (PinBuf).
+// rts_owned.h -- the owning types of librts_amd.so: device memory (DevBuf), pinned host memory (PinBuf), and the pair of them
+// behind an event that a small asynchronous upload goes through (StagedUpload).
 //
-// Both free what they hold in their destructor and are move-only, so a struct that holds them (RtsContext, RtsScene,
+// All free what they hold in their destructor and are move-only, so a struct that holds them (RtsContext, RtsScene,
 // RtsTileHist, a function's temporaries) needs no release list of its own: `delete` or leaving the scope frees the buffers,
 // members in reverse order of declaration.  hipFree waits for the device, so a buffer an enqueued kernel still reads is not
 // freed under it; hipHostFree does not say so: the owner of a PinBuf synchronises the stream that reads it first.
@@ -12,6 +13,7 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stddef.h>
+#include <utility>
 
 template <typename T> struct DevBuf {
     T* p = nullptr; size_t cap = 0;
@@ -62,4 +64,44 @@ template <typename T> struct PinBuf {
         return hipSuccess;
     }
     void release() { if (p) (void)hipHostFree(p); p = nullptr; dev = nullptr; cap = 0; }
+};
+
+// A small per-call upload that must not drain the stream: the caller's values -> a pinned staging block -> a device buffer, by an
+// asynchronous copy on the stream whose later kernels read them.  The staging is rewritten only once the previous copy out of it
+// has run (the event): the handle's earlier calls may still be in flight.
+//   T* h; begin(need, grow_to, dev_need, &h);  fill h[0 .. n);  send(n, stream);  kernels on `stream` read dev.p
+// begin waits for the previous send, makes room -- the pinned block is replaced by one of grow_to elements when it holds fewer than
+// `need` (each site brings its own sizes, as with PinBuf), the device buffer holds dev_need -- and creates the event on first use.
+// A begin without a send is allowed (nothing to upload this time).  The destructor destroys the event, then the members free
+// themselves; like a PinBuf's owner, whoever destroys or move-assigns over a StagedUpload drains the stream it was sent on first.
+template <typename T> struct StagedUpload {
+    PinBuf<T> pin; DevBuf<T> dev; hipEvent_t ev = nullptr; bool armed = false;
+    StagedUpload() = default;
+    StagedUpload(const StagedUpload&) = delete;
+    StagedUpload& operator=(const StagedUpload&) = delete;
+    StagedUpload(StagedUpload&& o) noexcept : pin(std::move(o.pin)), dev(std::move(o.dev)), ev(o.ev), armed(o.armed) { o.ev = nullptr; o.armed = false; }
+    StagedUpload& operator=(StagedUpload&& o) noexcept
+    {
+        if (this != &o) { drop_event(); pin = std::move(o.pin); dev = std::move(o.dev); ev = o.ev; armed = o.armed; o.ev = nullptr; o.armed = false; }
+        return *this;
+    }
+    ~StagedUpload() { drop_event(); }
+    hipError_t begin(size_t need, size_t grow_to, size_t dev_need, T** host)
+    {
+        hipError_t e;
+        if (armed) { e = hipEventSynchronize(ev); if (e != hipSuccess) return e; armed = false; }
+        if (pin.cap < need) { e = pin.reserve(grow_to, false); if (e != hipSuccess) return e; }
+        if (!ev) { e = hipEventCreateWithFlags(&ev, hipEventDisableTiming); if (e != hipSuccess) { ev = nullptr; return e; } }
+        e = dev.reserve(dev_need); if (e != hipSuccess) return e;
+        *host = pin.p;
+        return hipSuccess;
+    }
+    hipError_t send(size_t n, hipStream_t s)
+    {
+        hipError_t e = hipMemcpyAsync(dev.p, pin.p, n * sizeof(T), hipMemcpyHostToDevice, s); if (e != hipSuccess) return e;
+        e = hipEventRecord(ev, s); if (e != hipSuccess) return e;
+        armed = true;
+        return hipSuccess;
+    }
+    void drop_event() { if (ev) (void)hipEventDestroy(ev); ev = nullptr; armed = false; }
 };

@@ -692,17 +692,11 @@ __global__ void k_finalise_patterns(PerRayData* __restrict__ rays, const int32_t
 int rts_pattern_pulse_upload(RtsContext* c, const RtsSpecParams& q, RtsPatArgs* out)
 {
     const size_t n = q.pat_rx.size();
-    if (c->ev_pat_armed) { RTS_HIP(hipEventSynchronize(c->ev_pat)); c->ev_pat_armed = false; }
-    if (c->pin_pat.cap < n + 8) RTS_HIP(c->pin_pat.reserve(std::max<size_t>(n + 8, 512), false));
-    if (!c->ev_pat) RTS_HIP(hipEventCreateWithFlags(&c->ev_pat, hipEventDisableTiming));
-    RTS_HIP(c->d_pat_rx.reserve(n + 8));
-    if (n) {
-        memcpy(c->pin_pat.p, q.pat_rx.data(), sizeof(double) * n);
-        RTS_HIP(hipMemcpyAsync(c->d_pat_rx.p, c->pin_pat.p, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
-        RTS_HIP(hipEventRecord(c->ev_pat, c->stream)); c->ev_pat_armed = true;
-    }
+    double* rows = nullptr;
+    RTS_HIP(c->pat_rx.begin(n + 8, std::max<size_t>(n + 8, 512), n + 8, &rows));
+    if (n) { memcpy(rows, q.pat_rx.data(), sizeof(double) * n); RTS_HIP(c->pat_rx.send(n, c->stream)); }
     RtsPatArgs& a = *out;
-    a.pats = reinterpret_cast<const RtsPatView*>(c->d_pat.p); a.rx = c->d_pat_rx.p; a.n_rx = c->pat_n_rx; a.n_targets = c->pat_n_targets;
+    a.pats = reinterpret_cast<const RtsPatView*>(c->d_pat.p); a.rx = c->pat_rx.dev.p; a.n_rx = c->pat_n_rx; a.n_targets = c->pat_n_targets;
     a.ox = q.pat_org[0]; a.oy = q.pat_org[1]; a.oz = q.pat_org[2]; a.tx_az = q.pat_dir[0]; a.tx_el = q.pat_dir[1];
     a.wl = q.wl; a.carrier = q.carrier; a.cspeed = q.cspeed;
     return RTS_OK;
@@ -748,8 +742,8 @@ int rts_cube_accumulate_device(RtsContext* c, uint32_t pulse_index, double cspee
 {
     const uint32_t R = (uint32_t)c->n_recv;
     if (R == 0) return RTS_OK;
-    const RtsCubeParams& q = c->cube_params;
-    k_cube_accumulate<<<blocks_for(R, 256), 256, 0, c->stream>>>(c->d_rx_rays.p, R, c->cube, q.n_rx, q.n_pulses, q.n_bins, pulse_index, q.t0, q.dt, cspeed, carrier, c->recv_dev);
+    const RtsCubeParams& q = c->cube.params;
+    k_cube_accumulate<<<blocks_for(R, 256), 256, 0, c->stream>>>(c->d_rx_rays.p, R, c->cube.p, q.n_rx, q.n_pulses, q.n_bins, pulse_index, q.t0, q.dt, cspeed, carrier, c->recv_dev);
     RTS_HIP(hipGetLastError());
     return RTS_OK;
 }
@@ -777,8 +771,8 @@ int rts_cube_accumulate_paths_device(RtsContext* c, uint32_t pulse_index, int64_
 {
     const uint32_t R = (uint32_t)c->n_recv;
     if (R == 0) return RTS_OK;
-    const RtsCubeParams& q = c->cube_params;
-    k_cube_accumulate_paths<<<blocks_for(R, 256), 256, 0, c->stream>>>(c->d_rx_rays.p, c->d_delay.p, c->d_phase.p, c->d_pathmatch.p, R, base, c->cube, q.n_rx, q.n_pulses, q.n_bins,
+    const RtsCubeParams& q = c->cube.params;
+    k_cube_accumulate_paths<<<blocks_for(R, 256), 256, 0, c->stream>>>(c->d_rx_rays.p, c->d_delay.p, c->d_phase.p, c->d_pathmatch.p, R, base, c->cube.p, q.n_rx, q.n_pulses, q.n_bins,
                                                                         pulse_index, q.t0, q.dt);
     RTS_HIP(hipGetLastError());
     return RTS_OK;
@@ -823,13 +817,13 @@ __global__ void __launch_bounds__(256) k_cube_doppler(const double* __restrict__
 
 int rts_cube_doppler_device(RtsContext* c, uint32_t n_fft, double* out)
 {
-    const RtsCubeParams& q = c->cube_params;
+    const RtsCubeParams& q = c->cube.params;
     uint32_t logN = 0; while ((1u << logN) < n_fft) logN++;
     uint32_t BT = 8; while (BT > 1 && (size_t)n_fft * BT * 16 > 65536) BT >>= 1;
     const size_t lds = (size_t)n_fft * BT * 16 + (size_t)n_fft * 8;
     RTS_HIP(hipFuncSetAttribute((const void*)k_cube_doppler, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     dim3 grid((q.n_bins + BT - 1) / BT, q.n_rx);
-    k_cube_doppler<<<grid, 256, lds, c->stream>>>(c->cube, out, q.n_pulses, q.n_bins, n_fft, logN, BT);
+    k_cube_doppler<<<grid, 256, lds, c->stream>>>(c->cube.p, out, q.n_pulses, q.n_bins, n_fft, logN, BT);
     RTS_HIP(hipGetLastError());
     return RTS_OK;
 }
@@ -1367,7 +1361,7 @@ int rts_post_all_small(RtsContext* c, uint32_t cap, const RtsSpecParams& sp, boo
     q.perm = c->d_ri_sorted.p; q.D = D; q.rays = c->d_rx_rays.p; q.paths = c->d_rx_paths.p; q.angles = c->d_rx_angles.p; q.slots = c->d_rx_slots.p;
     q.rcs = c->d_rcsval.p; q.n_targets = nt; q.wl = sp.wl; q.gt = sp.gt; q.gr = sp.gr; q.carrier = sp.carrier; q.cspeed = sp.cspeed;
     q.cube_on = sp.cube_pulse >= 0 ? 1 : 0;
-    if (q.cube_on) { const RtsCubeParams& cp = c->cube_params; q.cube = c->cube; q.cube_rx = cp.n_rx; q.cube_pulses = cp.n_pulses; q.cube_bins = cp.n_bins; q.cube_pulse = (uint32_t)sp.cube_pulse; q.cube_t0 = cp.t0; q.cube_dt = cp.dt; }
+    if (q.cube_on) { const RtsCubeParams& cp = c->cube.params; q.cube = c->cube.p; q.cube_rx = cp.n_rx; q.cube_pulses = cp.n_pulses; q.cube_bins = cp.n_bins; q.cube_pulse = (uint32_t)sp.cube_pulse; q.cube_t0 = cp.t0; q.cube_dt = cp.dt; }
     q.B = k.B; q.key_bits = k.key_bits; q.ahead = c->d_ghead.p;
     q.fin = rts_agg_finish_args(c, k, s, cap, c->d_rx_rays.p, use_rows ? c->d_rx_slots.p : nullptr, base, want_groups);
     q.R_dev = c->p_counters; q.prio = c->post_prio;

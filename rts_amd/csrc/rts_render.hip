@@ -105,12 +105,12 @@ int rts_cube_render_device(RtsContext* c, uint32_t pulse_index, bool paths, bool
 {
     const uint32_t R = (uint32_t)c->n_recv;
     if (R == 0) return RTS_OK;
-    const RtsCubeParams& q = c->cube_params;
+    const RtsCubeParams& q = c->cube.params;
     RtsRenderArgs a;
     a.rays = c->d_rx_rays.p; a.delay = c->d_delay.p; a.phase = c->d_phase.p; a.pm = c->d_pathmatch.p; a.base = base;
     a.R = R; a.paths = paths ? 1 : 0; a.doppler = doppler ? 1 : 0;
-    a.cube = c->cube; a.n_rx = q.n_rx; a.n_pulses = q.n_pulses; a.n_bins = q.n_bins; a.pulse = pulse_index; a.t0 = q.t0; a.dt = q.dt;
-    a.cspeed = cspeed; a.carrier = carrier; a.wave = c->d_wave.p; a.M = c->wave_M; a.L = c->wave_L;
+    a.cube = c->cube.p; a.n_rx = q.n_rx; a.n_pulses = q.n_pulses; a.n_bins = q.n_bins; a.pulse = pulse_index; a.t0 = q.t0; a.dt = q.dt;
+    a.cspeed = cspeed; a.carrier = carrier; a.wave = c->cube.d_wave.p; a.M = c->cube.wave_M; a.L = c->cube.wave_L;
     const size_t lds = sizeof(double) * (2 * (size_t)a.M + (size_t)RTS_RENDER_SUB * a.L);      // <= 64 KiB + 16 KiB
     RTS_HIP(hipFuncSetAttribute((const void*)k_cube_render, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     dim3 grid((q.n_bins + RTS_RENDER_TILE - 1) / RTS_RENDER_TILE, q.n_rx);
@@ -154,12 +154,12 @@ __global__ void __launch_bounds__(RTS_COMPRESS_THREADS) k_cube_compress(double* 
 
 int rts_cube_compress_device(RtsContext* c, uint32_t first_pulse, uint32_t n_pulses)
 {
-    const RtsCubeParams& q = c->cube_params;
+    const RtsCubeParams& q = c->cube.params;
     if (n_pulses == 0) return RTS_OK;
     const size_t lds = 16 * (size_t)q.n_bins;                                   // <= 128 KiB (RTS_COMPRESS_MAX_BINS)
     RTS_HIP(hipFuncSetAttribute((const void*)k_cube_compress, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     dim3 grid(n_pulses, q.n_rx);
-    k_cube_compress<<<grid, RTS_COMPRESS_THREADS, lds, c->stream>>>(c->cube, c->d_wave.p, c->wave_M, q.n_pulses, first_pulse, q.n_bins);
+    k_cube_compress<<<grid, RTS_COMPRESS_THREADS, lds, c->stream>>>(c->cube.p, c->cube.d_wave.p, c->cube.wave_M, q.n_pulses, first_pulse, q.n_bins);
     RTS_HIP(hipGetLastError());
     return RTS_OK;
 }

@@ -1,6 +1,6 @@
 """Lifetime of a handle's device and pinned memory (-m gpu): what handles take they give back when they are destroyed, in either
 order of destruction, and a shared scene lives exactly as long as its last user.  The buffers free themselves (rts_owned.h:
-DevBuf, PinBuf -- tests/test_owned_host.py has their rules without a GPU); this file checks the handle built from them."""
+DevBuf, PinBuf, StagedUpload -- tests/test_owned_host.py has their rules without a GPU); this file checks the handle built from them."""
 import math
 
 import numpy as np
@@ -33,7 +33,7 @@ def _cycle(rts, s, owner_first):
     """three handles, two pulses each, every feature that owns memory; then all three destroyed"""
     tx = s["tx"]; wl = CS / FC; P = rts.Pattern.constant
     # plain handle: device-built scene, patterns, the host mirror, a receiver set that grows (the pinned receiver staging regrows),
-    # a cube of its own, a waveform, render / compress / Doppler / detect
+    # a cube of its own, a waveform, render / compress / Doppler / detect / spectrogram / backprojection
     a = H.gpu_tracer(rts, s)
     # host-build handle: builds a scene of its own, drops it for a's, joins a's link group
     h = H.gpu_tracer(rts, s, device_build=False)
@@ -54,6 +54,9 @@ def _cycle(rts, s, owner_first):
     a.cube_attach(70, 2, NB, T0, DT); a.cube_set_waveform(rts.Waveform.lfm(32, 0.5, 8))
     a.cube_render(0, "rays", CS, FC); a.cube_render(1, "paths")
     a.cube_compress(); a.cube_doppler(4, fetch=False); a.cube_detect(guard=(1, 0), train=(2, 1), pfa=1e-3)
+    # ... and the two products behind a staged upload (library-owned outputs): with the pattern rows above, all three are armed at the end
+    a.cube_spectrogram(2, 1, 2, window=[1.0, 0.5], fetch=False)
+    a.cube_backproject((0.0, 0.0, 0.0), (1.0, 0.0, 0.0), (0.0, 1.0, 0.0), 2, 2, np.tile(tx["origin"], (2, 1)), np.repeat(pos[:, None, :], 2, axis=1), CS, FC, fetch=False)
     for _ in range(2):
         _trace(h, s); h.finalise_uniform(None, wl, 1.0, 1.0, FC, CS); h.aggregate(CS, FC)
         _trace(k, s); k.all_rays(s["W"] ** 3); k.received()

@@ -1,6 +1,7 @@
-"""The owning buffer types (rts_amd/csrc/rts_owned.h: DevBuf, PinBuf) without a GPU and without the HIP runtime:
+"""The owning types (rts_amd/csrc/rts_owned.h: DevBuf, PinBuf, StagedUpload) without a GPU and without the HIP runtime:
 tests/owned/owned_main.cpp includes the header alone, supplies its own hipMalloc / hipFree / hipHostMalloc / hipHostFree /
-hipHostGetDevicePointer -- which log every call, know which blocks are live and can be told to fail -- and is built with g++ under
+hipHostGetDevicePointer, the four event calls and hipMemcpyAsync (which copies the bytes) -- which log every call, know which
+blocks and events are live and can be told to fail -- and is built with g++ under
 AddressSanitizer + UndefinedBehaviorSanitizer (without them where g++ has no libasan).  One case per line; the driver answers with
 the log of allocator calls and the buffers' states (the token format is described at the top of the driver).  Every expectation
 here is written out or formed by the growth rule as restated below, never read back from the header."""
@@ -172,3 +173,61 @@ def test_a_struct_of_owners_moves_as_a_whole(owned):
     assert got[:i] == ["M:1:%d" % (65536 * 4), "M:2:%d" % (65536 * 4), "M:3:%d" % (65536 * 8), "HM:4:100", "GP:4"]
     assert got[i + 1:i + 6] == ["S:0:0:0", "S:0:0:0", "S:1:65536:0", "S:0:0:0", "S:4:100:1"]
     assert sorted(got[i + 6:-1]) == ["F:1", "F:2", "F:3", "HF:4"] and got[-1] == "LIVE:0"
+
+
+# ---- StagedUpload<double>: a step is begin(need, grow_to, dev_need) and, when n != 0, a fill of n elements and send(n).  Blocks and
+# events are numbered apart, each from 1; the device buffer of a few doubles is DevBuf's floor of 65 536 elements (524 288 bytes).
+# U:<pinned block>:<cap>:<device block>:<cap>:<event>:<armed>
+FIRST = ["HM:1:128", "EC:1", "M:2:524288", "E:0", "U:1:16:2:65536:1:0", "W:1", "CP:2:1:80", "ER:1", "E:0", "EQ:1", "U:1:16:2:65536:1:1"]      # the step (10, 16, 10, 10) on a new object
+EMPTY = "U:0:0:0:0:0:0"
+
+
+def test_staged_first_use_creates_one_event_and_the_scope_end_destroys_it_once(owned):
+    """room on both sides (the pinned block of the size to grow to, not of the need), ONE event, the copy of n elements from the
+    pinned block to the device block, the record; the device bytes are the staged ones; the scope end destroys the event first and
+    exactly once, then frees the two blocks"""
+    got = owned([("steps", "staged", 0, 0, 10, 16, 10, 10)])[0]
+    assert got == FIRST + ["|", "ED:1", "F:2", "HF:1", "LIVE:0"]
+
+
+def test_staged_second_begin_waits_before_the_staging_is_touched_or_regrown(owned):
+    got = owned([("steps", "staged", 0, 0, 10, 16, 10, 10, 12, 16, 12, 12), ("steps", "staged", 0, 0, 10, 16, 10, 10, 20, 30, 20, 20)])
+    # room enough: the wait, then the fill, no allocator call, no second event
+    assert got[0] == FIRST + ["ES:1", "E:0", "U:1:16:2:65536:1:0", "W:1", "CP:2:1:96", "ER:1", "E:0", "EQ:1", "U:1:16:2:65536:1:1", "|", "ED:1", "F:2", "HF:1", "LIVE:0"]
+    # too small: the wait comes BEFORE the old pinned block is freed (once) and replaced by one of grow_to = 30 elements
+    assert got[1] == FIRST + ["ES:1", "HF:1", "HM:3:240", "E:0", "U:3:30:2:65536:1:0", "W:3", "CP:2:3:160", "ER:1", "E:0", "EQ:1", "U:3:30:2:65536:1:1",
+                              "|", "ED:1", "F:2", "HF:3", "LIVE:0"]
+    for g in got:
+        assert g.count("EC:1") == 1 and not [t for t in g if t.startswith("EC:") and t != "EC:1"]
+        assert g.count("HF:1") == 1 and g.count("ED:1") == 1
+
+
+def test_staged_begin_without_a_send_arms_nothing(owned):
+    """nothing to upload (the pattern rows of a pulse without receivers): the next begin does not wait, a regrow needs no wait either"""
+    got = owned([("steps", "staged", 0, 0, 10, 16, 10, 0, 20, 30, 20, 0, 5, 5, 5, 5)])[0]
+    assert got == ["HM:1:128", "EC:1", "M:2:524288", "E:0", "U:1:16:2:65536:1:0", "HF:1", "HM:3:240", "E:0", "U:3:30:2:65536:1:0",
+                   "E:0", "U:3:30:2:65536:1:0", "W:3", "CP:2:3:40", "ER:1", "E:0", "EQ:1", "U:3:30:2:65536:1:1", "|", "ED:1", "F:2", "HF:3", "LIVE:0"]
+    assert not [t for t in got if t.startswith("ES:")]
+
+
+def test_staged_failures_leave_the_object_destructible_and_usable(owned):
+    got = owned([("steps", "staged", 1, 0, 10, 16, 10, 10, 10, 16, 10, 10), ("steps", "staged", 0, 1, 10, 16, 10, 10, 10, 16, 10, 10),
+                 ("steps", "staged", 2, 0, 10, 16, 10, 10, 10, 16, 10, 10), ("steps", "staged", 0, 1, 10, 16, 10, 10)])
+    tail = ["|", "ED:1", "F:2", "HF:1", "LIVE:0"]
+    assert got[0] == ["X:HM", "E:1", EMPTY] + FIRST + tail                                       # the pinned block: nothing exists, no event yet
+    assert got[1] == ["HM:1:128", "X:EC", "E:1", "U:1:16:0:0:0:0", "EC:1", "M:2:524288"] + FIRST[3:] + tail        # the event: no handle kept
+    assert got[2] == ["HM:1:128", "EC:1", "X:M", "E:1", "U:1:16:0:0:1:0", "M:2:524288"] + FIRST[3:] + tail         # the device buffer
+    assert got[3] == ["HM:1:128", "X:EC", "E:1", "U:1:16:0:0:0:0", "|", "HF:1", "LIVE:0"]        # destroyed as the failure left it: no event to destroy
+
+
+def test_staged_moves(owned):
+    """move construction and move assignment leave the source empty (and usable) and carry the armed event along: the new owner's
+    next begin waits for it; the assignment target gives up its own event and blocks once; nothing is destroyed twice"""
+    again = ["ES:1", "E:0", "U:1:16:2:65536:1:0", "W:1", "CP:2:1:80", "ER:1", "E:0", "EQ:1", "U:1:16:2:65536:1:1"]
+    got = owned([("movector", "staged", 10, 16, 10, 10), ("moveassign", "staged", 10, 16, 10, 10, 5, 8, 5, 5), ("selfmove", "staged", 10, 16, 10, 10)])
+    assert got[0] == FIRST + ["|", EMPTY, "U:1:16:2:65536:1:1"] + again + ["|", "ED:1", "F:2", "HF:1", "LIVE:0"]
+    second = ["HM:3:64", "EC:2", "M:4:524288", "E:0", "U:3:8:4:65536:2:0", "W:3", "CP:4:3:40", "ER:2", "E:0", "EQ:1", "U:3:8:4:65536:2:1"]
+    third = ["HM:5:128", "EC:3", "M:6:524288", "E:0", "U:5:16:6:65536:3:0", "W:5", "CP:6:5:80", "ER:3", "E:0", "EQ:1", "U:5:16:6:65536:3:1"]
+    assert got[1] == FIRST + second + ["|", "ED:2", "HF:3", "F:4", EMPTY, "U:1:16:2:65536:1:1"] + third + \
+        ["|", "ED:1", "F:2", "HF:1", "ED:3", "F:6", "HF:5", "LIVE:0"]                         # (b before a: reverse order of declaration)
+    assert got[2] == FIRST + ["|", "U:1:16:2:65536:1:1", "|", "ED:1", "F:2", "HF:1", "LIVE:0"]
