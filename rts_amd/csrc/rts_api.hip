@@ -1,4 +1,4 @@
-// rts_api.hip -- host side of librts_amd.so: the C-ABI of include/rts_amd.h but for the cube (rts_cube_api.hip; rts_cube_reduce is here).
+// rts_api.hip -- host side of librts_amd.so: the C-ABI of include/rts_amd.h but for the cube (rts_cube_api.hip; rts_cube_reduce is here) and the accessors of a pulse's results (rts_results_api.hip).
 //
 // Mirrors the host driver rs::RTS of the reference (ray_tracer.cpp:507-1364) from the point
 // where it owns device state: context set-up, per-pulse scene placement, launch, read-back,
@@ -263,9 +263,9 @@ struct RtsLapTimer {
     void lap(int k) { if (!on) return; const auto t1 = std::chrono::steady_clock::now(); c->lap_s[k] += std::chrono::duration<double>(t1 - t0).count(); c->lap_n[k]++; t0 = t1; }
 };
 
-// pulses begun and not yet ended, per device: a trace launch that will share the GPU with another pulse's kernels leaves block
-// slots free for them (RtsContext::grid_spare), a lone pulse takes the whole chip
-static std::atomic<int> g_open_pulses[64];
+// pulses begun and not yet ended or resolved, per device: a trace launch that will share the GPU with another pulse's kernels leaves block
+// slots free for them (RtsContext::grid_spare), a lone pulse takes the whole chip.  Moved by the transitions of RtsPulseState alone (rts_pulse_state.h).
+static std::atomic<int> g_open_pulses[RTS_PULSE_SLOTS];
 static std::mutex g_hist_mu;      // (re)allocation of a shared tile-cost history (RtsTileHist)
 
 extern "C" int rts_destroy(RtsHandle c)
@@ -279,7 +279,7 @@ extern "C" int rts_destroy(RtsHandle c)
         for (int k = 0; k < 7; k++) fprintf(stderr, " %s %.1f |", names[k], c->lap_s[k] / (double)c->lap_n[0] * 1e6);
         fprintf(stderr, "\n");
     }
-    if (c->pulse_open || c->spec_pending) { c->pulse_open = false; c->spec_pending = false; g_open_pulses[c->device & 63]--; }
+    c->pulse.abandon();
     rts_comm_cache_forget(c);
     delete c;
     return RTS_OK;
@@ -291,7 +291,7 @@ extern "C" int rts_link_handles(RtsHandle a, RtsHandle b)
     if (a->device != b->device) { rts_set_error("rts_link_handles: handles live on different devices (%d, %d)", a->device, b->device); return RTS_ERR_INVALID; }
     if (a->gate == b->gate) return RTS_OK;
     if (a->gate->refs > 1 && b->gate->refs > 1) { rts_set_error("rts_link_handles: both handles already belong to (different) groups"); return RTS_ERR_INVALID; }
-    if (a->pulse_open || b->pulse_open) { rts_set_error("rts_link_handles: a pulse is in flight"); return RTS_ERR_INVALID; }
+    if (a->pulse.open() || b->pulse.open()) { rts_set_error("rts_link_handles: a pulse is in flight"); return RTS_ERR_INVALID; }
     RtsContext* joiner = b->gate->refs == 1 ? b : a;     // the handle that is still alone adopts the other's trace stream
     RtsContext* host = joiner == b ? a : b;
     RTS_HIP(hipSetDevice(a->device));
@@ -746,8 +746,7 @@ static int pulse_range_error(const RtsContext* c, const RtsPulse* p, const RtsRa
 // Forgets the previous pulse's results and notes the transmitter of this one (rts_finalise_patterns: its position and boresight).
 static void pulse_reset_results(RtsContext* c, const RtsPulse* p)
 {
-    c->agg_valid = false; c->agg_pending.valid = false; c->n_recv = 0;
-    c->mirror.want = false; c->mirror.recv_valid = false; c->mirror.agg_valid = false; c->v_recv_have = 0;
+    c->res.forget();
     for (int k = 0; k < 3; k++) c->pulse_org[k] = p->ray_origin[k];
     c->pulse_dir[0] = p->tx_dir[0]; c->pulse_dir[1] = p->tx_dir[1]; c->pulse_traced = true;
 }
@@ -953,8 +952,8 @@ extern "C" int rts_trace_pulse_begin(RtsHandle c, const RtsPulse* p)
     CHECK_HANDLE(c);
     lt.lap(5);
     if (!p) { rts_set_error("rts_trace_pulse: null pulse"); return RTS_ERR_INVALID; }
-    if (c->pulse_open) { rts_set_error("rts_trace_pulse_begin: the previous pulse of this handle was begun but not ended"); return RTS_ERR_INVALID; }
-    if (c->spec_pending) { int rc_ = rts_spec_resolve(c); if (rc_ != RTS_OK) return rc_; }
+    if (c->pulse.open()) { rts_set_error("rts_trace_pulse_begin: the previous pulse of this handle was begun but not ended"); return RTS_ERR_INVALID; }
+    CHECK_CLOSED(c);
     lt.lap(6);
     RtsPulseLaunch L;
     L.r = pulse_ray_range(c, p);
@@ -971,7 +970,8 @@ extern "C" int rts_trace_pulse_begin(RtsHandle c, const RtsPulse* p)
     L.count_trav = (c->params.flags & RTS_FLAG_COUNT_TRAVERSAL) != 0;
     // the trace kernel's blocks are persistent and four of them fill a CU's register file: a launch that shares the GPU leaves a few
     // block slots free so that the short kernels of the neighbouring pulses (other streams) are not locked out for the whole launch
-    L.shared_gpu = c->grid_spare_forced || g_open_pulses[c->device & 63].load() > 0;
+    std::atomic<int>& open_here = rts_pulse_slot(g_open_pulses, c->device);
+    L.shared_gpu = c->grid_spare_forced || open_here.load() > 0;
     L.grid = rts_trace_grid(L.n, c->n_cu, c->grid_mult, L.shared_gpu ? c->grid_spare : 0);
     L.pre_filter = c->use_pmask && !c->pre_dense;           // (a launch where most rays hit pays for the filter and skips nothing)
     pulse_fill_constants(c, *p, L.r, L.pre_filter);
@@ -988,11 +988,10 @@ extern "C" int rts_trace_pulse_begin(RtsHandle c, const RtsPulse* p)
     { int rc = pulse_launch(c, L); if (rc != RTS_OK) return rc; }
     lt.lap(4);
     // (the eight counters were written into the pinned block by k_sum_counters itself: no copy)
-    c->pulse_open = true; g_open_pulses[c->device & 63]++;
+    c->pulse.begin(open_here);
     return L.tl_path ? pulse_timeline_dump(c, L) : RTS_OK;
 }
 
-// Waits for the pulse begun on this handle, then orders + expands its received rays (left in flight).
 // counters of a finished launch -> the handle's statistics and the hints its next launch uses
 static void rts_pulse_account(RtsContext* c, const unsigned long long* cnt)
 {
@@ -1006,7 +1005,7 @@ static void rts_pulse_account(RtsContext* c, const unsigned long long* cnt)
     c->pre_dense = 2 * s.shaded > (uint64_t)n;                      // next launch of this handle: pre-filter only if most launch indices hit nothing
     s.ms_scene = s.ms_trace = s.ms_compact = s.ms_aggregate = 0;
     c->stats_pending = true;
-    c->recv_hint = cnt[0]; c->recv_hint_valid = true;
+    c->recv_hint = cnt[0]; c->recv_hint_valid = true;      // (the next pulse's choices -- speculate at all, one kernel or seven -- follow THIS pulse's count, not the handle's first)
 }
 
 // the counters of a finished launch, once the host has waited for its stream: the launch's own failures, then the received count and
@@ -1015,152 +1014,75 @@ static int rts_counters_home(RtsContext* c, const unsigned long long* cnt)
 {
     if (cnt[13]) { rts_set_error("rts_trace_pulse: %llu counter rows of the launch were never written by their blocks (counting build)", cnt[13]); return RTS_ERR_HIP; }
     if (cnt[6]) { rts_set_error("rts_trace_pulse: traversal stack overflow / malformed BVH guard tripped on %llu waves", cnt[6]); return RTS_ERR_HIP; }
-    c->n_recv = cnt[0]; c->n_head_hint = (uint32_t)cnt[7]; c->hist->head_hint = c->n_head_hint; c->hist->head_hint_valid = true;
+    c->res.n_recv = cnt[0]; c->n_head_hint = (uint32_t)cnt[7]; c->hist->head_hint = c->n_head_hint; c->hist->head_hint_valid = true;
     return RTS_OK;
 }
 
-extern "C" int rts_trace_pulse_end(RtsHandle c)
+// RTS_TIMELINE_BLOCKS: the launch as a bulk (every block resident) and a tail (rts_get_block_timeline; profiles/r05h_batch_launch.log)
+static void pulse_timeline_summary(RtsContext* c)
 {
-    CHECK_HANDLE(c);
-    if (!c->pulse_open) { rts_set_error("rts_trace_pulse_end: no pulse in flight on this handle"); return RTS_ERR_INVALID; }
-    c->pulse_open = false; g_open_pulses[c->device & 63]--;
-    hipStream_t st = c->stream;
-    const bool keep_all = (c->params.flags & RTS_FLAG_KEEP_ALL_RAYS) != 0;
-    unsigned long long* cnt = c->pin.p->cnt;
-    RTS_HIP(rts_stream_wait(c, st));                // the one host sync of the launch: the received count sizes what follows
+    std::vector<unsigned long long> h((size_t)c->tl_blocks * 2);
+    (void)hipMemcpy(h.data(), c->d_timeline.p, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost);
+    std::vector<unsigned long long> s0, s1; for (uint32_t i = 0; i < c->tl_blocks; i++) { s0.push_back(h[2 * i]); s1.push_back(h[2 * i + 1]); }
+    std::sort(s0.begin(), s0.end()); std::sort(s1.begin(), s1.end());
+    const size_t m = s0.size(); const unsigned long long t0 = s0[0];
+    const size_t q[8] = {0, m / 2, m - 1, 0, m / 10, m / 2, m * 9 / 10, m - 1};
+    for (int k = 0; k < 8; k++) c->tl_summary[k] = (double)((k < 3 ? s0[q[k]] : s1[q[k]]) - t0) / 100.0;      // us after the first block's start (100 MHz counter)
+    c->tl_summary[8] = (double)m;
+    if (c->debug_coop) fprintf(stderr, "[rts] blocks of handle %p (us after the first start): start p50 %.1f max %.1f | end min %.1f p10 %.1f p50 %.1f p90 %.1f max %.1f\n", (void*)c,
+                               c->tl_summary[1], c->tl_summary[2], c->tl_summary[3], c->tl_summary[4], c->tl_summary[5], c->tl_summary[6], c->tl_summary[7]);
+}
+
+// debug (RTS_DEBUG_COOP): what the head rule of this launch's order build saw (blocking read-backs)
+static void pulse_debug_dump(RtsContext* c, const unsigned long long* cnt)
+{
+    unsigned long long sums[2] = {0, 0};
+    (void)hipMemcpy(&sums[0], c->d_order_sum.p, sizeof(unsigned long long), hipMemcpyDeviceToHost);
+    (void)hipMemcpy(&sums[1], c->d_tile_ctr.p + RTS_OFF_HEAD, sizeof(unsigned long long), hipMemcpyDeviceToHost);
+    uint32_t live_w = 0; (void)hipMemcpy(&live_w, c->d_tile_ctr.p + RTS_OFF_LIVE, sizeof(uint32_t), hipMemcpyDeviceToHost);
+    fprintf(stderr, "[rts] end: handle %p head count %llu coop grid %u | cost sum persisted %llu, this build's %llu | live word %u of %u tiles\n", (void*)c, cnt[7], c->last_coop_grid, sums[0], sums[1], live_w, (uint32_t)rts_wave_tiles(c->n_rays));
+    if (c->tile_cost_pending && c->d_tile_cost.p) {          // the cost records this launch wrote (merged by the next order build)
+        const uint32_t nt = (uint32_t)rts_wave_tiles(c->tile_cost_sig[0]);
+        std::vector<uint32_t> h(nt);
+        (void)hipMemcpy(h.data(), c->d_tile_cost.p, sizeof(uint32_t) * nt, hipMemcpyDeviceToHost);
+        unsigned long long sum = 0, big = 0, flagged = 0; uint32_t mx = 0, shown = 0;
+        for (uint32_t j = 0; j < nt; j++) { const uint32_t v = h[j] & 0x3fffffffu; sum += v; if (v > mx) mx = v; if (h[j] >> 31) flagged++; if (v > (1u << 26)) { big++; if (shown++ < 6) fprintf(stderr, "[rts]    tile %u record 0x%08x\n", j, h[j]); } }
+        fprintf(stderr, "[rts]    records of this launch: sum %llu max %u, %llu above 2^26, %llu flagged LONG WALKS\n", sum, mx, big, flagged);
+    }
+}
+
+// What every way of ending a pulse does once the host has waited for its stream: the launch's counters (its failures, the received count,
+// the head count), the block timeline's summary, the statistics and the hints of the handle's next launch.
+static int rts_pulse_home(RtsContext* c)
+{
+    const unsigned long long* cnt = c->pin.p->cnt;
     { int rc = rts_counters_home(c, cnt); if (rc != RTS_OK) return rc; }
-    if (c->tl_blocks) {      // RTS_TIMELINE_BLOCKS: the launch as a bulk (every block resident) and a tail (rts_get_block_timeline; profiles/r05h_batch_launch.log)
-        std::vector<unsigned long long> h((size_t)c->tl_blocks * 2);
-        (void)hipMemcpy(h.data(), c->d_timeline.p, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost);
-        std::vector<unsigned long long> s0, s1; for (uint32_t i = 0; i < c->tl_blocks; i++) { s0.push_back(h[2 * i]); s1.push_back(h[2 * i + 1]); }
-        std::sort(s0.begin(), s0.end()); std::sort(s1.begin(), s1.end());
-        const size_t m = s0.size(); const unsigned long long t0 = s0[0];
-        const size_t q[8] = {0, m / 2, m - 1, 0, m / 10, m / 2, m * 9 / 10, m - 1};
-        for (int k = 0; k < 8; k++) c->tl_summary[k] = (double)((k < 3 ? s0[q[k]] : s1[q[k]]) - t0) / 100.0;      // us after the first block's start (100 MHz counter)
-        c->tl_summary[8] = (double)m;
-        if (c->debug_coop) fprintf(stderr, "[rts] blocks of handle %p (us after the first start): start p50 %.1f max %.1f | end min %.1f p10 %.1f p50 %.1f p90 %.1f max %.1f\n", (void*)c,
-                                   c->tl_summary[1], c->tl_summary[2], c->tl_summary[3], c->tl_summary[4], c->tl_summary[5], c->tl_summary[6], c->tl_summary[7]);
-    }
-    if (c->debug_coop && c->d_order_sum.p && c->d_tile_ctr.p) {      // debug: what the head rule of this launch's order build saw (blocking read-backs)
-        unsigned long long sums[2] = {0, 0};
-        (void)hipMemcpy(&sums[0], c->d_order_sum.p, sizeof(unsigned long long), hipMemcpyDeviceToHost);
-        (void)hipMemcpy(&sums[1], c->d_tile_ctr.p + RTS_OFF_HEAD, sizeof(unsigned long long), hipMemcpyDeviceToHost);
-        uint32_t live_w = 0; (void)hipMemcpy(&live_w, c->d_tile_ctr.p + RTS_OFF_LIVE, sizeof(uint32_t), hipMemcpyDeviceToHost);
-        fprintf(stderr, "[rts] end: handle %p head count %llu coop grid %u | cost sum persisted %llu, this build's %llu | live word %u of %u tiles\n", (void*)c, cnt[7], c->last_coop_grid, sums[0], sums[1], live_w, (uint32_t)rts_wave_tiles(c->n_rays));
-        if (c->tile_cost_pending && c->d_tile_cost.p) {          // the cost records this launch wrote (merged by the next order build)
-            const uint32_t nt = (uint32_t)rts_wave_tiles(c->tile_cost_sig[0]);
-            std::vector<uint32_t> h(nt);
-            (void)hipMemcpy(h.data(), c->d_tile_cost.p, sizeof(uint32_t) * nt, hipMemcpyDeviceToHost);
-            unsigned long long sum = 0, big = 0, flagged = 0; uint32_t mx = 0, shown = 0;
-            for (uint32_t j = 0; j < nt; j++) { const uint32_t v = h[j] & 0x3fffffffu; sum += v; if (v > mx) mx = v; if (h[j] >> 31) flagged++; if (v > (1u << 26)) { big++; if (shown++ < 6) fprintf(stderr, "[rts]    tile %u record 0x%08x\n", j, h[j]); } }
-            fprintf(stderr, "[rts]    records of this launch: sum %llu max %u, %llu above 2^26, %llu flagged LONG WALKS\n", sum, mx, big, flagged);
-        }
-    }
-
-    // ---- order + expand the received rays (and the keep-all buffers); left in flight on the stream
-    RTS_HIP(hipEventRecord(c->ev[4], st));
-    int rc = rts_post_order_and_expand(c); if (rc != RTS_OK) return rc;
-    if (keep_all) { rc = rts_post_expand_all(c); if (rc != RTS_OK) return rc; }
-    if (c->mirror.want) { rc = rts_post_mirror_received(c); if (rc != RTS_OK) return rc; }
-    RTS_HIP(hipEventRecord(c->ev[5], st));
-
-    c->agg_timed = false; c->fin_timed = false;
+    if (c->tl_blocks) pulse_timeline_summary(c);
     rts_pulse_account(c, cnt);
     return RTS_OK;
 }
 
-extern "C" int rts_get_stats(RtsHandle c, RtsStats* out)
+// ev[4] ... order + expand the received rays (and the keep-all buffers, and the host mirror when the pulse feeds it) ... ev[5]; left in flight on the stream
+static int rts_post_received(RtsContext* c)
 {
-    if (!c || !out) { rts_set_error("rts_get_stats: null argument"); return RTS_ERR_INVALID; }
-    CHECK_CLOSED(c);
-    if (c->stats_pending) {                          // stage timers are resolved lazily: reading them drains the stream
-        RTS_HIP(hipSetDevice(c->device));
-        RTS_HIP(hipStreamSynchronize(c->stream));
-        RtsStats& s = c->stats; float ms = 0;
-        RTS_HIP(hipEventElapsedTime(&s.ms_scene, c->ev[0], c->ev[1]));
-        RTS_HIP(hipEventElapsedTime(&s.ms_trace, c->ev[2], c->ev[3]));
-        RTS_HIP(hipEventElapsedTime(&s.ms_compact, c->ev[4], c->ev[5]));
-        s.ms_aggregate = 0;
-        if (c->fin_timed || c->agg_timed) { RTS_HIP(hipEventElapsedTime(&ms, c->ev[6], c->ev[7])); s.ms_aggregate = ms; }
-        c->stats_pending = false;
-    }
-    *out = c->stats; return RTS_OK;
-}
-
-// Lane statistics of the last launch's walk (RTS_FLAG_COUNT_TRAVERSAL builds; zeros otherwise): out[0] lane-steps ISSUED (64 x the
-// longest walk of every bounce round of every tile), out[1] of them issued to lanes that were in the round at all, out[2]
-// walk steps actually taken.  1 - out[1]/out[0]: what lanes that left their tile early cost (re-packing rays between rounds could
-// recover at most this); (out[1] - out[2])/out[0]: what waiting for the round's slowest lane costs.
-// When the persistent blocks of the handle's last launch started and ended (a handle created with RTS_TIMELINE_BLOCKS=1; product builds): out[0..2] first / median / last
-// block START, out[3..7] first / 10th percentile / median / 90th percentile / last block END, all in microseconds after the first start (the 100 MHz counter), out[8] the blocks.
-// A launch is a BULK -- every block resident; the median end -- and a tail of the few tiles that are one ray's long chain of dependent steps.
-extern "C" int rts_get_block_timeline(RtsHandle c, double* out, uint32_t n)
-{
-    if (!c || !out) { rts_set_error("rts_get_block_timeline: null argument"); return RTS_ERR_INVALID; }
-    CHECK_CLOSED(c);
-    if (!c->timeline_blocks || c->tl_summary[8] == 0.0) { rts_set_error("rts_get_block_timeline: the handle records no block timeline (create it with RTS_TIMELINE_BLOCKS=1, product build) or has not traced yet"); return RTS_ERR_INVALID; }
-    for (uint32_t k = 0; k < n && k < 9; k++) out[k] = c->tl_summary[k];
+    RTS_HIP(hipEventRecord(c->ev[4], c->stream));
+    int rc = rts_post_order_and_expand(c); if (rc != RTS_OK) return rc;
+    if (c->params.flags & RTS_FLAG_KEEP_ALL_RAYS) { rc = rts_post_expand_all(c); if (rc != RTS_OK) return rc; }
+    if (c->res.mirror.want) { rc = rts_post_mirror_received(c); if (rc != RTS_OK) return rc; }
+    RTS_HIP(hipEventRecord(c->ev[5], c->stream));
     return RTS_OK;
 }
 
-extern "C" int rts_get_lane_stats(RtsHandle c, uint64_t* out3)
-{
-    if (!c || !out3) { rts_set_error("rts_get_lane_stats: null argument"); return RTS_ERR_INVALID; }
-    CHECK_CLOSED(c);
-    for (int k = 0; k < 3; k++) out3[k] = c->pin.p->cnt[8 + k];
-    return RTS_OK;
-}
-
-// ... and the split VERDICT r4 #3 asked for: out[0..2] as rts_get_lane_stats, out[3] segments that walked at all, out[4] lane-steps issued to
-// lanes that are in their tile's bounce round but never started a walk in it (a primary the pre-filter or every bounding sphere cleared, in a
-// tile other lanes of which walk): out[4] / out[0] is what packing live launch indices of several tiles into dense waves could recover at most;
-// (out[1] - out[2] - out[4]) / out[0] what waiting for the round's slowest WALKING lane costs.  n: capacity of out (<= 5 values are written).
-extern "C" int rts_get_walk_stats(RtsHandle c, uint64_t* out, uint32_t n)
-{
-    if (!c || !out) { rts_set_error("rts_get_walk_stats: null argument"); return RTS_ERR_INVALID; }
-    CHECK_CLOSED(c);
-    const int src[5] = {8, 9, 10, 11, 15};
-    for (uint32_t k = 0; k < n && k < 5u; k++) out[k] = c->pin.p->cnt[src[k]];
-    return RTS_OK;
-}
-
-extern "C" int rts_received_count(RtsHandle c, uint64_t* count)
-{
-    if (!c || !count) { rts_set_error("rts_received_count: null argument"); return RTS_ERR_INVALID; }
-    CHECK_CLOSED(c);
-    *count = c->n_recv; return RTS_OK;
-}
-
-extern "C" int rts_get_received(RtsHandle c, PerRayData* rays, int32_t* paths, double* rcs_angles, uint64_t* slots, uint64_t capacity)
+// Waits for the pulse begun on this handle, then orders + expands its received rays (left in flight).
+extern "C" int rts_trace_pulse_end(RtsHandle c)
 {
     CHECK_HANDLE(c);
-    CHECK_CLOSED(c);
-    const uint64_t R = c->n_recv; const uint32_t D = c->depth;
-    if (capacity < R) { rts_set_error("rts_get_received: capacity %llu < %llu received rays", (unsigned long long)capacity, (unsigned long long)R); return RTS_ERR_CAPACITY; }
-    if (R == 0) return RTS_OK;
-    RTS_HIP(hipStreamSynchronize(c->stream));
-    if (rays) RTS_HIP(hipMemcpy(rays, c->d_rx_rays.p, sizeof(PerRayData)*R, hipMemcpyDeviceToHost));
-    if (paths && D) RTS_HIP(hipMemcpy(paths, c->d_rx_paths.p, sizeof(int32_t)*R*D, hipMemcpyDeviceToHost));
-    if (rcs_angles && D) RTS_HIP(hipMemcpy(rcs_angles, c->d_rx_angles.p, sizeof(double)*2*R*D, hipMemcpyDeviceToHost));
-    if (slots) RTS_HIP(hipMemcpy(slots, c->d_rx_slots.p, sizeof(uint64_t)*R, hipMemcpyDeviceToHost));
-    return RTS_OK;
-}
-
-extern "C" int rts_get_all_rays(RtsHandle c, PerRayData* results, int32_t* targ_intersect, double* rcs_angle, int32_t* hit_prim, float* hit_t, uint64_t capacity)
-{
-    CHECK_HANDLE(c);
-    CHECK_CLOSED(c);
-    if (!(c->params.flags & RTS_FLAG_KEEP_ALL_RAYS)) { rts_set_error("rts_get_all_rays: handle was not created with RTS_FLAG_KEEP_ALL_RAYS"); return RTS_ERR_INVALID; }
-    const uint64_t n1 = c->n_rays, n = n1 * c->last_args.rows; const uint32_t D = c->depth, H = rts_hit_rows(c->params.max_refl);
-    if (capacity < n) { rts_set_error("rts_get_all_rays: capacity too small (%llu rows)", (unsigned long long)n); return RTS_ERR_CAPACITY; }
-    if (n == 0) return RTS_OK;
-    RTS_HIP(hipStreamSynchronize(c->stream));
-    if (results) RTS_HIP(hipMemcpy(results, c->d_all_rays.p, sizeof(PerRayData)*n, hipMemcpyDeviceToHost));
-    if (targ_intersect && D) RTS_HIP(hipMemcpy(targ_intersect, c->d_all_paths.p, sizeof(int32_t)*n*D, hipMemcpyDeviceToHost));
-    if (rcs_angle && D) RTS_HIP(hipMemcpy(rcs_angle, c->d_all_angles.p, sizeof(double)*2*n*D, hipMemcpyDeviceToHost));
-    if (hit_prim) RTS_HIP(hipMemcpy(hit_prim, c->d_hit_prim.p, sizeof(int32_t)*n1*H, hipMemcpyDeviceToHost));
-    if (hit_t) RTS_HIP(hipMemcpy(hit_t, c->d_hit_t.p, sizeof(float)*n1*H, hipMemcpyDeviceToHost));
-    return RTS_OK;
+    if (!c->pulse.end()) { rts_set_error("rts_trace_pulse_end: no pulse in flight on this handle"); return RTS_ERR_INVALID; }
+    RTS_HIP(rts_stream_wait(c, c->stream));         // the one host sync of the launch: the received count sizes what follows
+    { int rc = rts_pulse_home(c); if (rc != RTS_OK) return rc; }
+    if (c->debug_coop && c->d_order_sum.p && c->d_tile_ctr.p) pulse_debug_dump(c, c->pin.p->cnt);
+    c->res.agg_timed = false; c->res.fin_timed = false;
+    return rts_post_received(c);
 }
 
 // ------------------------------------------------------------------------------------- finalise + aggregate
@@ -1170,35 +1092,30 @@ extern "C" int rts_finalise_uniform(RtsHandle c, const double* rcs_per_target, d
     CHECK_CLOSED(c);
     std::vector<double> ones;
     if (!rcs_per_target) { ones.assign(c->scene->meshes.size() + 1, 1.0); rcs_per_target = ones.data(); }
-    RTS_HIP(hipEventRecord(c->ev[6], c->stream));
-    int rc = rts_post_finalise(c, rcs_per_target, wavelength, gt, gr, carrier, cspeed); if (rc != RTS_OK) return rc;
-    RTS_HIP(hipEventRecord(c->ev[7], c->stream));
-    c->fin_timed = true; c->stats_pending = true;
-    c->agg_valid = false;      // (the mirror keeps the set AS RECEIVED for the rest of the pulse: rts_received_view)
-    return RTS_OK;
+    return rts_finalise_bracket(c, [&] { return rts_post_finalise(c, rcs_per_target, wavelength, gt, gr, carrier, cspeed); });
 }
 
 static int rts_aggregate_impl(RtsContext* c, double cspeed, double carrier, uint64_t recv_index_base)
 {
-    const uint64_t R = c->n_recv;
-    c->agg_pending.valid = false;                                       // (an unread table of an earlier call is dropped)
-    c->groups.clear(); c->recv_index_base = recv_index_base;
-    if (R == 0) { c->agg_valid = true; return RTS_OK; }
+    const uint64_t R = c->res.n_recv;
+    c->res.agg_pending.valid = false;                                       // (an unread table of an earlier call is dropped)
+    c->res.groups.clear(); c->res.recv_index_base = recv_index_base;
+    if (R == 0) { c->res.agg_valid = true; return RTS_OK; }
     RTS_HIP(c->d_delay.reserve(R)); RTS_HIP(c->d_phase.reserve(R)); RTS_HIP(c->d_pathmatch.reserve(R));
-    if (!c->fin_timed) RTS_HIP(hipEventRecord(c->ev[6], c->stream));
-    c->agg_delay_in = false;                                            // (delay / phase sums start at zero: no fills)
+    if (!c->res.fin_timed) RTS_HIP(hipEventRecord(c->ev[6], c->stream));
+    c->res.agg_delay_in = false;                                            // (delay / phase sums start at zero: no fills)
     const int32_t max_path = (int32_t)c->scene->meshes.size() - 1, max_rx = c->n_rx ? (int32_t)c->n_rx - 1 : 0;
     const bool use_rows = recv_index_base == RTS_BASE_USE_ROWS;
-    c->agg_base_local = use_rows ? 0 : (int64_t)recv_index_base;
+    c->res.agg_base_local = use_rows ? 0 : (int64_t)recv_index_base;
     int rc = rts_aggregate_device(c, max_path, max_rx, c->d_rx_paths.p, R, c->depth, cspeed, carrier, use_rows ? 0 : recv_index_base, c->d_rx_rays.p,
-                                  c->d_delay.p, c->d_phase.p, c->d_pathmatch.p, &c->groups, nullptr, nullptr, nullptr, INT32_MAX, use_rows ? c->d_rx_slots.p : nullptr);
-    c->agg_delay_in = true;
+                                  c->d_delay.p, c->d_phase.p, c->d_pathmatch.p, &c->res.groups, nullptr, nullptr, nullptr, INT32_MAX, use_rows ? c->d_rx_slots.p : nullptr);
+    c->res.agg_delay_in = true;
     if (rc != RTS_OK) return rc;
     // (the rays' power / Doppler on the device are the group values now; the mirror still holds the set as it was received, and rts_received_view keeps serving it)
-    if (c->mirror.want) { rc = rts_post_mirror_aggregated(c); if (rc != RTS_OK) return rc; }
+    if (c->res.mirror.want) { rc = rts_post_mirror_aggregated(c); if (rc != RTS_OK) return rc; }
     RTS_HIP(hipEventRecord(c->ev[7], c->stream));
-    c->agg_timed = true; c->stats_pending = true;
-    c->agg_valid = true;
+    c->res.agg_timed = true; c->stats_pending = true;
+    c->res.agg_valid = true;
     return RTS_OK;
 }
 
@@ -1227,56 +1144,49 @@ static int rts_post_chain(RtsContext* c, bool ordered = false)      // ordered: 
     // (one block does in 150 us what seven launches -- four of them many blocks wide -- do in 92 us + six launch gaps for BASELINE configs[2]'s
     // ~1 900 received rays; for a few hundred rays it is the other way round: sequential pulses, one kernel against seven, C3 1.025 / 0.980 ms,
     // C2 (400 rays) 0.339 / 0.354, configs[4] (100) 0.955 / 0.978, profiles/r04_post_one_ab.log -- so the choice follows the handle's last count)
-    if (!ordered && q.mode == 0 && c->recv_dev && c->recv_hint_valid && c->recv_hint <= c->post_one_max && c->post_small && !keep_all && !c->mirror.want && c->n_recv <= c->spec_cap) {
+    if (!ordered && q.mode == 0 && c->res.recv_dev && c->recv_hint_valid && c->recv_hint <= c->post_one_max && c->post_small && !keep_all && !c->res.mirror.want && c->res.n_recv <= c->spec_cap) {
         // the speculative chain as ONE kernel (rts_post.hip: k_post_all): sized for the capacity, the count from the device
         RTS_HIP(hipEventRecord(c->ev[4], st)); RTS_HIP(hipEventRecord(c->ev[5], st)); RTS_HIP(hipEventRecord(c->ev[6], st));
-        c->agg_pending.valid = false; c->groups.clear();
-        rc = rts_post_all_small(c, (uint32_t)c->n_recv, q, true); if (rc != RTS_OK) return rc;
+        c->res.agg_pending.valid = false; c->res.groups.clear();
+        rc = rts_post_all_small(c, (uint32_t)c->res.n_recv, q, true); if (rc != RTS_OK) return rc;
         RTS_HIP(hipEventRecord(c->ev[7], st));
-        c->fin_timed = true; c->agg_timed = true; c->stats_pending = true; c->agg_valid = true;
+        c->res.fin_timed = true; c->res.agg_timed = true; c->stats_pending = true; c->res.agg_valid = true;
         return RTS_OK;
     }
-    if (!ordered) {
-        RTS_HIP(hipEventRecord(c->ev[4], st));
-        rc = rts_post_order_and_expand(c); if (rc != RTS_OK) return rc;
-        if (keep_all) { rc = rts_post_expand_all(c); if (rc != RTS_OK) return rc; }
-        if (c->mirror.want) { rc = rts_post_mirror_received(c); if (rc != RTS_OK) return rc; }
-        RTS_HIP(hipEventRecord(c->ev[5], st));
-    }
+    if (!ordered) { rc = rts_post_received(c); if (rc != RTS_OK) return rc; }
     if (q.mode == 1) return RTS_OK;                                     // rts_received_prefetch: the received set goes home, the caller finalises it
     RTS_HIP(hipEventRecord(c->ev[6], st));
     rc = q.fin ? rts_post_finalise_patterns(c, q) : rts_post_finalise(c, q.rcs.data(), q.wl, q.gt, q.gr, q.carrier, q.cspeed); if (rc != RTS_OK) return rc;
-    c->fin_timed = true; c->agg_valid = false;
+    c->res.fin_timed = true; c->res.agg_valid = false;
     if (q.cube_pulse >= 0) { rc = rts_cube_accumulate_device(c, (uint32_t)q.cube_pulse, q.cspeed, q.carrier); if (rc != RTS_OK) return rc; }
     rc = rts_aggregate_impl(c, q.cspeed, q.carrier, q.base);
     return rc;
 }
 
-int rts_spec_resolve(RtsContext* c)
+static int rts_spec_resolve(RtsContext* c)      // the outcome of a chain that was enqueued on the device-side count (agg_timed / fin_timed stay as the chain set them)
 {
-    if (!c->spec_pending) return RTS_OK;
-    c->spec_pending = false; g_open_pulses[c->device & 63]--;
+    if (!c->pulse.resolve()) return RTS_OK;
     RTS_HIP(hipSetDevice(c->device));
-    const unsigned long long* cnt = c->pin.p->cnt;
     RTS_HIP(rts_stream_wait(c, c->stream));
-    { int rc = rts_counters_home(c, cnt); if (rc != RTS_OK) return rc; }
-    c->recv_hint = cnt[0]; c->recv_hint_valid = true;                   // (the next pulse's choices -- speculate at all, one kernel or seven -- follow THIS pulse's count, not the handle's first)
-    rts_pulse_account(c, cnt);
-    if (c->n_recv > c->spec_cap) {                                      // more rays than the speculative chain was sized for: it did nothing; the ordinary chain now
-        c->agg_pending.valid = false;
+    { int rc = rts_pulse_home(c); if (rc != RTS_OK) return rc; }
+    if (c->res.n_recv > c->spec_cap) {                                      // more rays than the speculative chain was sized for: it did nothing; the ordinary chain now
+        c->res.agg_pending.valid = false;
         return rts_post_chain(c);
     }
-    if (c->n_recv == 0) { c->agg_pending.valid = false; c->groups.clear(); c->agg_valid = true; return RTS_OK; }
-    c->agg_pending.R = (uint32_t)c->n_recv; c->agg_pending.spec = rts_agg_spec((uint32_t)c->n_recv);
+    if (c->res.n_recv == 0) { c->res.agg_pending.valid = false; c->res.groups.clear(); c->res.agg_valid = true; return RTS_OK; }
+    c->res.agg_pending.R = (uint32_t)c->res.n_recv; c->res.agg_pending.spec = rts_agg_spec((uint32_t)c->res.n_recv);
     return RTS_OK;
 }
+
+// CHECK_CLOSED: OPEN -> ended, CHAINED -> resolved, IDLE -> nothing to do
+int rts_pulse_settle(RtsContext* c) { return c->pulse.open() ? rts_trace_pulse_end(c) : c->pulse.chained() ? rts_spec_resolve(c) : RTS_OK; }
 
 static int rts_trace_pulse_end_chain(RtsContext* c);
 extern "C" int rts_trace_pulse_end_uniform(RtsHandle c, const double* rcs_per_target, double wavelength, double gt, double gr, double carrier, double cspeed,
                                            int32_t cube_pulse, uint64_t recv_index_base)
 {
     CHECK_HANDLE(c);
-    if (!c->pulse_open) { rts_set_error("rts_trace_pulse_end_uniform: no pulse in flight on this handle"); return RTS_ERR_INVALID; }
+    if (!c->pulse.open()) { rts_set_error("rts_trace_pulse_end_uniform: no pulse in flight on this handle"); return RTS_ERR_INVALID; }
     if (cube_pulse >= 0 && (!c->cube.set || (uint32_t)cube_pulse >= c->cube.params.n_pulses)) { rts_set_error("rts_trace_pulse_end_uniform: no cube attached, or pulse %d outside it", cube_pulse); return RTS_ERR_INVALID; }
     RtsSpecParams& q = c->spec;
     const size_t nt = c->scene->meshes.size();
@@ -1297,12 +1207,12 @@ static bool rts_speculates(const RtsContext* c, uint32_t cap)
 static int rts_chain_on_device_count(RtsContext* c, uint32_t cap)
 {
     c->spec_cap = cap;
-    c->pulse_open = false; c->spec_pending = true;                      // (the pulse stays counted as open on its device until it is resolved)
-    c->agg_timed = false; c->fin_timed = false;
-    c->n_recv = cap; c->recv_dev = c->p_counters;
+    c->pulse.chain();                                                   // (the pulse stays counted on its device until it is resolved)
+    c->res.agg_timed = false; c->res.fin_timed = false;
+    c->res.n_recv = cap; c->res.recv_dev = c->p_counters;
     const int rc = rts_post_chain(c);
-    c->recv_dev = nullptr; c->n_recv = 0;
-    if (rc != RTS_OK) { c->spec_pending = false; g_open_pulses[c->device & 63]--; }
+    c->res.recv_dev = nullptr; c->res.n_recv = 0;
+    if (rc != RTS_OK) c->pulse.abandon();
     return rc;
 }
 
@@ -1387,7 +1297,7 @@ extern "C" int rts_set_patterns(RtsHandle c, const RtsPattern* tx, const RtsPatt
     const size_t bytes = head + n_dbl * sizeof(double);
     // the handle's enqueued work may still read the previous tables: a speculative chain is resolved (if it has to run again, it runs
     // with the tables it was enqueued for), then the stream drained
-    if (c->spec_pending) { int rc = rts_spec_resolve(c); if (rc != RTS_OK) return rc; }
+    if (c->pulse.chained()) CHECK_CLOSED(c);      // (an OPEN pulse stays in flight: it is finalised with the new tables)
     RTS_HIP(hipStreamSynchronize(c->stream));
     RTS_HIP(c->d_pat.reserve(bytes));
     std::vector<char> host(bytes);
@@ -1440,18 +1350,13 @@ extern "C" int rts_finalise_patterns(RtsHandle c, const RtsPatternPulse* pulse)
     CHECK_CLOSED(c);
     RtsSpecParams q;
     int rc = rts_pattern_pulse_params(c, pulse, q, "rts_finalise_patterns"); if (rc != RTS_OK) return rc;
-    RTS_HIP(hipEventRecord(c->ev[6], c->stream));
-    rc = rts_post_finalise_patterns(c, q); if (rc != RTS_OK) return rc;
-    RTS_HIP(hipEventRecord(c->ev[7], c->stream));
-    c->fin_timed = true; c->stats_pending = true;
-    c->agg_valid = false;
-    return RTS_OK;
+    return rts_finalise_bracket(c, [&] { return rts_post_finalise_patterns(c, q); });
 }
 
 extern "C" int rts_trace_pulse_end_patterns(RtsHandle c, const RtsPatternPulse* pulse, int32_t cube_pulse, uint64_t recv_index_base)
 {
     CHECK_HANDLE(c);
-    if (!c->pulse_open) { rts_set_error("rts_trace_pulse_end_patterns: no pulse in flight on this handle"); return RTS_ERR_INVALID; }
+    if (!c->pulse.open()) { rts_set_error("rts_trace_pulse_end_patterns: no pulse in flight on this handle"); return RTS_ERR_INVALID; }
     if (cube_pulse >= 0 && (!c->cube.set || (uint32_t)cube_pulse >= c->cube.params.n_pulses)) { rts_set_error("rts_trace_pulse_end_patterns: no cube attached, or pulse %d outside it", cube_pulse); return RTS_ERR_INVALID; }
     RtsSpecParams& q = c->spec;
     int rc = rts_pattern_pulse_params(c, pulse, q, "rts_trace_pulse_end_patterns"); if (rc != RTS_OK) return rc;
@@ -1470,139 +1375,13 @@ extern "C" int rts_trace_pulse_end_patterns(RtsHandle c, const RtsPatternPulse* 
 extern "C" int rts_received_prefetch(RtsHandle c)
 {
     CHECK_HANDLE(c);
-    if (!c->pulse_open) { rts_set_error("rts_received_prefetch: no pulse in flight on this handle"); return RTS_ERR_INVALID; }
+    if (!c->pulse.open()) { rts_set_error("rts_received_prefetch: no pulse in flight on this handle"); return RTS_ERR_INVALID; }
     const uint32_t cap = rts_small_cap(rts_recv_key64(c->last_args.max_refr));      // (the chain's only sort: the received rows')
     { int rc = rts_mirror_reserve(c, cap); if (rc != RTS_OK) return rc; }
-    c->mirror.want = true;
+    c->res.mirror.want = true;
     if (!rts_speculates(c, cap)) return RTS_OK;
     c->spec.mode = 1;
     return rts_chain_on_device_count(c, cap);
-}
-
-extern "C" int rts_received_view(RtsHandle c, const PerRayData** rays, const int32_t** paths, const double** rcs_angles, const uint64_t** slots, uint64_t* count)
-{
-    CHECK_HANDLE(c);
-    if (!count) { rts_set_error("rts_received_view: null count"); return RTS_ERR_INVALID; }
-    CHECK_CLOSED(c);
-    const uint64_t R = c->n_recv; const uint32_t D = c->depth;
-    *count = R;
-    if (rays) *rays = nullptr; if (paths) *paths = nullptr; if (rcs_angles) *rcs_angles = nullptr; if (slots) *slots = nullptr;
-    if (R == 0) return RTS_OK;
-    RTS_HIP(rts_stream_wait(c, c->stream));
-    const RtsHostMirror& m = c->mirror;
-    if (m.recv_valid && R <= m.cap) {
-        if (rays) *rays = (const PerRayData*)(m.buf.p + m.o_rays); if (paths) *paths = (const int32_t*)(m.buf.p + m.o_paths);
-        if (rcs_angles) *rcs_angles = (const double*)(m.buf.p + m.o_angles); if (slots) *slots = (const uint64_t*)(m.buf.p + m.o_slots);
-        return RTS_OK;
-    }
-    // no mirror of this set (not asked for, or larger than the mirror): copies into storage the handle keeps.  Each array is read from the
-    // device ONCE per pulse (v_recv_have): pointers handed out earlier stay valid and keep their content -- the records as they were at the
-    // pulse's first call, i.e. AS RECEIVED when that call came before rts_finalise_values (a second call used to re-read records
-    // the finalisation had changed, and rts_aggregated_view's fallback overwrote them with group values)
-    if (rays) { if (!(c->v_recv_have & 1u)) { c->v_rays.resize(R); RTS_HIP(hipMemcpy(c->v_rays.data(), c->d_rx_rays.p, sizeof(PerRayData) * R, hipMemcpyDeviceToHost)); c->v_recv_have |= 1u; } *rays = c->v_rays.data(); }
-    if (paths && D) { if (!(c->v_recv_have & 2u)) { c->v_paths.resize(R * D); RTS_HIP(hipMemcpy(c->v_paths.data(), c->d_rx_paths.p, sizeof(int32_t) * R * D, hipMemcpyDeviceToHost)); c->v_recv_have |= 2u; } *paths = c->v_paths.data(); }
-    if (rcs_angles && D) { if (!(c->v_recv_have & 4u)) { c->v_angles.resize(2 * R * D); RTS_HIP(hipMemcpy(c->v_angles.data(), c->d_rx_angles.p, sizeof(double) * 2 * R * D, hipMemcpyDeviceToHost)); c->v_recv_have |= 4u; } *rcs_angles = c->v_angles.data(); }
-    if (slots) { if (!(c->v_recv_have & 8u)) { c->v_slots.resize(R); RTS_HIP(hipMemcpy(c->v_slots.data(), c->d_rx_slots.p, sizeof(uint64_t) * R, hipMemcpyDeviceToHost)); c->v_recv_have |= 8u; } *slots = c->v_slots.data(); }
-    return RTS_OK;
-}
-
-// The per-received-ray update of ray_tracer.cpp:1219-1253 when the factors come from the simulator's callbacks: the caller has
-// formed every received ray's final power and Doppler shift on the host (from rts_received_view's records); they replace the
-// traced values on the device, in received order.  Enqueued (the values are copied out of the caller's arrays before the call
-// returns); rts_aggregate follows.
-extern "C" int rts_finalise_values(RtsHandle c, const double* power, const double* doppler, uint64_t count)
-{
-    CHECK_HANDLE(c);
-    CHECK_CLOSED(c);
-    if (count != c->n_recv) { rts_set_error("rts_finalise_values: %llu values for %llu received rays", (unsigned long long)count, (unsigned long long)c->n_recv); return RTS_ERR_INVALID; }
-    if (count == 0) return RTS_OK;
-    if (!power || !doppler) { rts_set_error("rts_finalise_values: null array"); return RTS_ERR_INVALID; }
-    RTS_HIP(hipEventRecord(c->ev[6], c->stream));
-    RtsHostMirror& m = c->mirror;
-    if (!m.buf.p) { int rc = rts_mirror_reserve(c, RTS_SMALL_CAP32); if (rc != RTS_OK) return rc; }
-    if (count <= m.cap) {
-        // (the staging is free: what read it last -- this handle's previous pulse -- was waited for before this pulse was begun)
-        memcpy(m.buf.p + m.o_vpower, power, sizeof(double) * count); memcpy(m.buf.p + m.o_vdoppler, doppler, sizeof(double) * count);
-        int rc = rts_post_set_values(c, (const double*)(m.buf.dev + m.o_vpower), (const double*)(m.buf.dev + m.o_vdoppler)); if (rc != RTS_OK) return rc;
-    } else {                                                            // a set beyond the mirror: blocking uploads into scratch the aggregation overwrites later
-        RTS_HIP(c->d_delay.reserve(count)); RTS_HIP(c->d_phase.reserve(count));
-        RTS_HIP(hipMemcpyAsync(c->d_delay.p, power, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
-        RTS_HIP(hipMemcpyAsync(c->d_phase.p, doppler, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
-        int rc = rts_post_set_values(c, c->d_delay.p, c->d_phase.p); if (rc != RTS_OK) return rc;
-        RTS_HIP(hipStreamSynchronize(c->stream));
-    }
-    RTS_HIP(hipEventRecord(c->ev[7], c->stream));
-    c->fin_timed = true; c->stats_pending = true;
-    c->agg_valid = false;      // (the mirror keeps the set AS RECEIVED for the rest of the pulse: rts_received_view)
-    return RTS_OK;
-}
-
-// Per-ray outputs of the last rts_aggregate (what rs::kernel_wrapper leaves in h_rx_results_arr[].power / .doppler, h_delay_arr,
-// h_phase_arr, h_pathMatch): pointers into the host mirror when the pulse was prefetched (the call waits for the handle's stream
-// once), copies otherwise.  Valid until the handle's next rts_trace_pulse_begin.
-extern "C" int rts_aggregated_view(RtsHandle c, const double** power, const double** doppler, const double** delay, const double** phase, const int32_t** path_match, uint64_t* count)
-{
-    CHECK_HANDLE(c);
-    if (!count) { rts_set_error("rts_aggregated_view: null count"); return RTS_ERR_INVALID; }
-    CHECK_CLOSED(c);
-    if (!c->agg_valid) { rts_set_error("rts_aggregated_view: call rts_aggregate first"); return RTS_ERR_INVALID; }
-    const uint64_t R = c->n_recv;
-    *count = R;
-    if (power) *power = nullptr; if (doppler) *doppler = nullptr; if (delay) *delay = nullptr; if (phase) *phase = nullptr; if (path_match) *path_match = nullptr;
-    if (R == 0) return RTS_OK;
-    RTS_HIP(rts_stream_wait(c, c->stream));
-    const RtsHostMirror& m = c->mirror;
-    if (m.agg_valid && R <= m.cap) {
-        if (power) *power = (const double*)(m.buf.p + m.o_apower); if (doppler) *doppler = (const double*)(m.buf.p + m.o_adoppler);
-        if (delay) *delay = (const double*)(m.buf.p + m.o_adelay); if (phase) *phase = (const double*)(m.buf.p + m.o_aphase); if (path_match) *path_match = (const int32_t*)(m.buf.p + m.o_apm);
-        return RTS_OK;
-    }
-    if (power || doppler) {
-        c->v_agg_rays.resize(R); RTS_HIP(hipMemcpy(c->v_agg_rays.data(), c->d_rx_rays.p, sizeof(PerRayData) * R, hipMemcpyDeviceToHost));      // (scratch of its own: rts_received_view's records stay as they were)
-        c->v_apower.resize(R); c->v_adoppler.resize(R);
-        for (uint64_t i = 0; i < R; i++) { c->v_apower[i] = c->v_agg_rays[i].power; c->v_adoppler[i] = c->v_agg_rays[i].doppler; }
-        if (power) *power = c->v_apower.data(); if (doppler) *doppler = c->v_adoppler.data();
-    }
-    if (delay) { c->v_adelay.resize(R); RTS_HIP(hipMemcpy(c->v_adelay.data(), c->d_delay.p, sizeof(double) * R, hipMemcpyDeviceToHost)); *delay = c->v_adelay.data(); }
-    if (phase) { c->v_aphase.resize(R); RTS_HIP(hipMemcpy(c->v_aphase.data(), c->d_phase.p, sizeof(double) * R, hipMemcpyDeviceToHost)); *phase = c->v_aphase.data(); }
-    if (path_match) { c->v_apm.resize(R); RTS_HIP(hipMemcpy(c->v_apm.data(), c->d_pathmatch.p, sizeof(int32_t) * R, hipMemcpyDeviceToHost)); *path_match = c->v_apm.data(); }
-    return RTS_OK;
-}
-
-extern "C" int rts_group_count(RtsHandle c, uint32_t* count)
-{
-    if (!c || !count) { rts_set_error("rts_group_count: null argument"); return RTS_ERR_INVALID; }
-    CHECK_CLOSED(c);
-    if (!c->agg_valid) { rts_set_error("rts_group_count: call rts_aggregate first"); return RTS_ERR_INVALID; }
-    { int rc = rts_aggregate_fetch(c, &c->groups); if (rc != RTS_OK) return rc; }
-    *count = (uint32_t)c->groups.size(); return RTS_OK;
-}
-
-extern "C" int rts_get_groups(RtsHandle c, RtsGroup* groups, uint32_t capacity)
-{
-    if (!c || (!groups && capacity)) { rts_set_error("rts_get_groups: null argument"); return RTS_ERR_INVALID; }
-    CHECK_CLOSED(c);
-    if (!c->agg_valid) { rts_set_error("rts_get_groups: call rts_aggregate first"); return RTS_ERR_INVALID; }
-    { int rc = rts_aggregate_fetch(c, &c->groups); if (rc != RTS_OK) return rc; }
-    if (capacity < c->groups.size()) { rts_set_error("rts_get_groups: capacity too small"); return RTS_ERR_CAPACITY; }
-    if (!c->groups.empty()) memcpy(groups, c->groups.data(), sizeof(RtsGroup)*c->groups.size());
-    return RTS_OK;
-}
-
-extern "C" int rts_get_aggregated(RtsHandle c, PerRayData* rays, double* delay, double* phase, int32_t* path_match, uint64_t capacity)
-{
-    CHECK_HANDLE(c);
-    CHECK_CLOSED(c);
-    if (!c->agg_valid) { rts_set_error("rts_get_aggregated: call rts_aggregate first"); return RTS_ERR_INVALID; }
-    const uint64_t R = c->n_recv;
-    if (capacity < R) { rts_set_error("rts_get_aggregated: capacity too small"); return RTS_ERR_CAPACITY; }
-    if (R == 0) return RTS_OK;
-    RTS_HIP(hipStreamSynchronize(c->stream));
-    if (rays) RTS_HIP(hipMemcpy(rays, c->d_rx_rays.p, sizeof(PerRayData)*R, hipMemcpyDeviceToHost));
-    if (delay) RTS_HIP(hipMemcpy(delay, c->d_delay.p, sizeof(double)*R, hipMemcpyDeviceToHost));
-    if (phase) RTS_HIP(hipMemcpy(phase, c->d_phase.p, sizeof(double)*R, hipMemcpyDeviceToHost));
-    if (path_match) RTS_HIP(hipMemcpy(path_match, c->d_pathmatch.p, sizeof(int32_t)*R, hipMemcpyDeviceToHost));
-    return RTS_OK;
 }
 
 // ------------------------------------------------------------------------------------- several GPUs: the plan of an interval
@@ -1611,8 +1390,8 @@ extern "C" int rts_get_aggregated(RtsHandle c, PerRayData* rays, double* delay, 
 extern "C" int rts_set_tile_list(RtsHandle c, uint32_t tile, const uint32_t* tile_ids, uint32_t n_ids)
 {
     CHECK_HANDLE(c);
-    if (c->pulse_open) { rts_set_error("rts_set_tile_list: a pulse of this handle is in flight"); return RTS_ERR_INVALID; }
-    if (c->spec_pending) { int rc_ = rts_spec_resolve(c); if (rc_ != RTS_OK) return rc_; }
+    if (c->pulse.open()) { rts_set_error("rts_set_tile_list: a pulse of this handle is in flight"); return RTS_ERR_INVALID; }
+    CHECK_CLOSED(c);
     // the cost records of the last launch are indexed through the list in force: into the history before it goes
     { int rc = rts_tile_costs_flush(c); if (rc != RTS_OK) return rc; }
     if (tile == 0) { c->il_list_n = 0; c->il_list_tile = 0; c->il_list_gen++; c->tile_last_valid = false; return RTS_OK; }      // no list any more
@@ -1633,7 +1412,7 @@ extern "C" int rts_set_tile_list(RtsHandle c, uint32_t tile, const uint32_t* til
 extern "C" int rts_tile_records_get(RtsHandle c, uint32_t* records, uint32_t n)
 {
     CHECK_HANDLE(c);
-    if (c->pulse_open) { rts_set_error("rts_tile_records_get: a pulse of this handle is in flight"); return RTS_ERR_INVALID; }
+    if (c->pulse.open()) { rts_set_error("rts_tile_records_get: a pulse of this handle is in flight"); return RTS_ERR_INVALID; }
     const uint64_t total = rts_lattice_size(c->params.width);
     if (!records || n != (uint32_t)rts_wave_tiles(total)) { rts_set_error("rts_tile_records_get: n must be ceil(W^3 / %d) = %llu", RTS_WTILE, (unsigned long long)rts_wave_tiles(total)); return RTS_ERR_INVALID; }
     { int rc = rts_tile_costs_flush(c); if (rc != RTS_OK) return rc; }
@@ -1647,7 +1426,7 @@ extern "C" int rts_tile_records_get(RtsHandle c, uint32_t* records, uint32_t n)
 extern "C" int rts_tile_records_set(RtsHandle c, const uint32_t* records, uint32_t n)
 {
     CHECK_HANDLE(c);
-    if (c->pulse_open) { rts_set_error("rts_tile_records_set: a pulse of this handle is in flight"); return RTS_ERR_INVALID; }
+    if (c->pulse.open()) { rts_set_error("rts_tile_records_set: a pulse of this handle is in flight"); return RTS_ERR_INVALID; }
     const uint64_t total = rts_lattice_size(c->params.width);
     if (!records || n != (uint32_t)rts_wave_tiles(total)) { rts_set_error("rts_tile_records_set: n must be ceil(W^3 / %d) = %llu", RTS_WTILE, (unsigned long long)rts_wave_tiles(total)); return RTS_ERR_INVALID; }
     RTS_HIP(hipStreamSynchronize(c->stream));
@@ -1972,7 +1751,7 @@ extern "C" int rts_kernel_wrapper_on(RtsHandle h, PerRayData* h_rx_results_arr, 
     if (!h_rx_results_arr || (depthTotal && !h_rx_intersects_arr) || !h_delay_arr || !h_phase_arr || !h_pathMatch) { rts_set_error("rts_kernel_wrapper: null array"); return RTS_ERR_INVALID; }
     RtsContext* c = h;
     if (!c) { int rc = wrapper_context(&c); if (rc != RTS_OK) return rc; }
-    else { CHECK_CLOSED(c); c->agg_valid = false; c->agg_pending.valid = false; c->n_recv = 0; c->mirror.recv_valid = false; c->mirror.agg_valid = false; c->mirror.want = false; c->pulse_traced = false; }      // the handle's own received set is overwritten
+    else { CHECK_CLOSED(c); c->res.forget(); c->pulse_traced = false; }      // the handle's own received set is overwritten
     RTS_HIP(hipSetDevice(c->device));
     const size_t R = receivedRays, D = depthTotal;
     RTS_HIP(c->d_rx_rays.reserve(R)); RTS_HIP(c->d_rx_paths.reserve(R*D + 1)); RTS_HIP(c->d_delay.reserve(R)); RTS_HIP(c->d_phase.reserve(R)); RTS_HIP(c->d_pathmatch.reserve(R));

@@ -61,9 +61,9 @@ extern "C" int rts_cube_accumulate_paths(RtsHandle c, uint32_t pulse_index)
     CHECK_HANDLE(c);
     CHECK_CLOSED(c);
     NEED_CUBE(c, "rts_cube_accumulate_paths", "call rts_cube_attach first");
-    if (!c->agg_valid) { rts_set_error("rts_cube_accumulate_paths: call rts_aggregate for this pulse first (the groups' power, delay and phase are its results)"); return RTS_ERR_INVALID; }
+    if (!c->res.agg_valid) { rts_set_error("rts_cube_accumulate_paths: call rts_aggregate for this pulse first (the groups' power, delay and phase are its results)"); return RTS_ERR_INVALID; }
     if (pulse_index >= c->cube.params.n_pulses) { rts_set_error("rts_cube_accumulate_paths: pulse %u >= %u", pulse_index, c->cube.params.n_pulses); return RTS_ERR_INVALID; }
-    return rts_cube_accumulate_paths_device(c, pulse_index, c->agg_base_local);
+    return rts_cube_accumulate_paths_device(c, pulse_index, c->res.agg_base_local);
 }
 
 extern "C" int rts_cube_doppler(RtsHandle c, uint32_t n_fft, void* device_out)
@@ -119,7 +119,7 @@ extern "C" int rts_cube_set_waveform(RtsHandle c, const RtsWaveform* w)
     CHECK_HANDLE(c);
     int rc = rts_waveform_check(w, "rts_cube_set_waveform"); if (rc != RTS_OK) return rc;
     // the handle's enqueued work may still read the previous waveform: a speculative chain is resolved, then the stream drained
-    if (c->spec_pending) { rc = rts_spec_resolve(c); if (rc != RTS_OK) return rc; }
+    if (c->pulse.chained()) CHECK_CLOSED(c);      // (an OPEN pulse stays in flight: its render comes after the stream is drained below)
     RTS_HIP(hipStreamSynchronize(c->stream));
     RTS_HIP(c->cube.d_wave.reserve(2 * (size_t)w->n_samples));
     RTS_HIP(hipMemcpy(c->cube.d_wave.p, w->samples, sizeof(double) * 2 * w->n_samples, hipMemcpyHostToDevice));
@@ -137,8 +137,8 @@ extern "C" int rts_cube_render(RtsHandle c, uint32_t pulse_index, uint32_t sourc
     if (!c->cube.wave_set) { rts_set_error("rts_cube_render: no waveform (rts_cube_set_waveform)"); return RTS_ERR_INVALID; }
     if (pulse_index >= c->cube.params.n_pulses) { rts_set_error("rts_cube_render: pulse %u >= %u", pulse_index, c->cube.params.n_pulses); return RTS_ERR_INVALID; }
     const bool paths = source == RTS_RENDER_PATHS;
-    if (paths && !c->agg_valid) { rts_set_error("rts_cube_render: RTS_RENDER_PATHS needs rts_aggregate of this pulse first (the groups' power, delay and phase are its results)"); return RTS_ERR_INVALID; }
-    return rts_cube_render_device(c, pulse_index, paths, (flags & RTS_RENDER_DOPPLER) != 0, cspeed, carrier, c->agg_base_local);
+    if (paths && !c->res.agg_valid) { rts_set_error("rts_cube_render: RTS_RENDER_PATHS needs rts_aggregate of this pulse first (the groups' power, delay and phase are its results)"); return RTS_ERR_INVALID; }
+    return rts_cube_render_device(c, pulse_index, paths, (flags & RTS_RENDER_DOPPLER) != 0, cspeed, carrier, c->res.agg_base_local);
 }
 
 extern "C" int rts_cube_compress(RtsHandle c, uint32_t first_pulse, uint32_t n_pulses)

@@ -16,6 +16,7 @@
 #include "rts_owned.h"            // DevBuf, PinBuf, StagedUpload: device and pinned host memory that frees itself
 #include "rts_launch_plan.h"      // RTS_BLOCK, RTS_WTILE, RTS_COOP_GROUP, RTS_STACK_OVF and the host arithmetic of a launch
 #include "rts_post_plan.h"        // RTS_SMALL_CAP32 / 64, RTS_AGG_TILE and the host arithmetic of the post-processing
+#include "rts_pulse_state.h"      // RtsPulseState: IDLE / OPEN / CHAINED, and the only code that moves the per-device count of open pulses
 
 // ----------------------------------------------------------------------------- HBM layout
 // BVH4 node, 128 B = one cache line, of the static target-space hierarchy (rts_sah.cpp): half the dependent fetch
@@ -326,6 +327,23 @@ struct RtsCubeState {
     void end_products() { doppler.valid = false; det_valid = false; image.valid = false; stft.valid = false; }
 };
 
+// What a pulse leaves for its accessors (rts_results_api.hip; the finalisers, the aggregation and the end-of-pulse chains of rts_api.hip; the
+// launchers of rts_post.hip / rts_render.hip read n_recv / recv_dev).  The device buffers the results live in stay on the handle.
+struct RtsPulseResults {
+    uint64_t n_recv = 0;                // received rays (ordered, expanded: RtsContext::d_rx_*)
+    const unsigned long long* recv_dev = nullptr;      // != nullptr while a chain is being enqueued on the device-side count: its kernels take the received count from here
+    std::vector<RtsGroup> groups; bool agg_valid = false; uint64_t recv_index_base = 0;
+    RtsAggPending agg_pending;          // the group table of the last rts_aggregate is still on its way (rts_aggregate_fetch reads it)
+    bool agg_delay_in = true;           // rts_aggregate_device: the delay / phase arrays carry initial sums (rs::kernel_wrapper's in-out arguments); false: they start at zero
+    int64_t agg_base_local = 0;         // pathMatch value of received ray i after rts_aggregate = agg_base_local + i
+    RtsHostMirror mirror;               // rts_received_prefetch / rts_received_view / rts_finalise_values / rts_aggregated_view
+    std::vector<PerRayData> v_rays; std::vector<int32_t> v_paths; std::vector<double> v_angles, v_apower, v_adoppler, v_adelay, v_aphase; std::vector<uint64_t> v_slots; std::vector<int32_t> v_apm;      // the views' fallback storage (sets beyond the mirror's capacity)
+    std::vector<PerRayData> v_agg_rays; unsigned v_recv_have = 0;      // rts_aggregated_view's own scratch (never the received view's storage); bits: which of v_rays / v_paths / v_angles / v_slots hold THIS pulse's set already
+    bool agg_timed = false, fin_timed = false;      // ev[6] / ev[7] bracket this pulse's finalisation / aggregation (rts_get_stats)
+    // the previous results are gone: a new pulse begins (rts_trace_pulse_begin), or rts_kernel_wrapper_on overwrites the received set
+    void forget() { agg_valid = false; agg_pending.valid = false; n_recv = 0; mirror.want = false; mirror.recv_valid = false; mirror.agg_valid = false; v_recv_have = 0; }
+};
+
 struct RtsContext {
     RtsParams params;
     uint32_t depth = 0;             // D = max_refr + max_refl
@@ -378,8 +396,7 @@ struct RtsContext {
     DevBuf<int32_t> d_hit_prim; DevBuf<float> d_hit_t; DevBuf<int32_t> d_stack_ovf; DevBuf<RtsChildState> d_child;
     DevBuf<uint64_t> d_rk64, d_rk64_sorted;
     RtsTraceArgs last_args; RtsLaunchConsts last_lc;
-    // received set (ordered, expanded)
-    uint64_t n_recv = 0;
+    // received set (ordered, expanded; its count: res.n_recv)
     DevBuf<uint32_t> d_rk, d_rk_sorted, d_ri, d_ri_sorted;
     DevBuf<PerRayData> d_rx_rays; DevBuf<int32_t> d_rx_paths; DevBuf<double> d_rx_angles; DevBuf<uint64_t> d_rx_slots;
     DevBuf<PerRayData> d_all_rays; DevBuf<int32_t> d_all_paths; DevBuf<double> d_all_angles;
@@ -387,7 +404,6 @@ struct RtsContext {
     DevBuf<uint64_t> d_akeys, d_akeys_sorted; DevBuf<uint32_t> d_aidx, d_aidx_sorted; DevBuf<uint32_t> d_ghead, d_gid;
     DevBuf<double> d_gsum; DevBuf<uint32_t> d_gmin; DevBuf<uint64_t> d_gkey; DevBuf<uint32_t> d_gcount; DevBuf<uint64_t> d_grow; DevBuf<int32_t> d_gpath;
     DevBuf<double> d_delay, d_phase; DevBuf<int32_t> d_pathmatch; DevBuf<double> d_rcs;
-    std::vector<RtsGroup> groups; bool agg_valid = false; uint64_t recv_index_base = 0;
     bool rx_window_screen = true;       // RTS_RX_WINDOW_SCREEN
     bool timeline_blocks = false; double tl_summary[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};      // RTS_TIMELINE_BLOCKS (rts_get_block_timeline)
     uint32_t tl_blocks = 0;             // debug (RTS_TIMELINE_BLOCKS): blocks whose start / end ticks this launch recorded
@@ -403,26 +419,21 @@ struct RtsContext {
     bool post_small = true;             // received sets of up to 4096 rays are ordered / finished by single blocks (RTS_POST_SMALL=0: the general chain)
     hipStream_t tstream_now = nullptr; bool trace_own_stream = true;      // the stream this pulse's trace kernel went to (rts_trace_pulse_begin; RTS_TRACE_OWN_STREAM=0: always the trace stream)
     uint32_t spec_cap = RTS_SMALL_CAP64;
-    RtsSpecParams spec; bool spec_pending = false, spec_enabled = true;      // rts_trace_pulse_end_uniform: parameters of the chain; a chain enqueued on the device-side count awaits its resolution (RTS_SPECULATE=0: never)
-    const unsigned long long* recv_dev = nullptr;                           // != nullptr while such a chain is being enqueued: its kernels take the received count from here
+    RtsSpecParams spec; bool spec_enabled = true;      // rts_trace_pulse_end_uniform: parameters of the chain, which may be enqueued on the device-side count (pulse.chained(); RTS_SPECULATE=0: never)
     uint64_t recv_hint = 0; bool recv_hint_valid = false;                    // received rays of the handle's previous pulse
-    RtsAggPending agg_pending;          // the group table of the last rts_aggregate is still on its way (rts_aggregate_fetch reads it)
-    RtsHostMirror mirror;               // rts_received_prefetch / rts_received_view / rts_finalise_values / rts_aggregated_view
-    std::vector<PerRayData> v_rays; std::vector<int32_t> v_paths; std::vector<double> v_angles, v_apower, v_adoppler, v_adelay, v_aphase; std::vector<uint64_t> v_slots; std::vector<int32_t> v_apm;      // the views' fallback storage (sets beyond the mirror's capacity)
-    std::vector<PerRayData> v_agg_rays; unsigned v_recv_have = 0;      // rts_aggregated_view's own scratch (never the received view's storage); bits: which of v_rays / v_paths / v_angles / v_slots hold THIS pulse's set already
+    RtsPulseResults res;                // what the last pulse left for its accessors (rts_results_api.hip)
     PinBuf<RtsRxDev> pin_rx; std::vector<RtsRxDev> rx_host;      // receivers: last values set (an unchanged set is not uploaded again) and the pinned staging of the asynchronous upload
     RtsCubeState cube;                  // the complex return cube and what is derived from it (rts_cube_api.hip)
-    bool agg_delay_in = true;           // rts_aggregate_device: the delay / phase arrays carry initial sums (rs::kernel_wrapper's in-out arguments); false: they start at zero
-    int64_t agg_base_local = 0;         // pathMatch value of received ray i after rts_aggregate = agg_base_local + i
     PinBuf<RtsPinned> pin;      // pinned host staging (one RtsPinned) and its address on the device (pin.dev): kernels write the small per-pulse read-backs (counters, group table) straight into it
-    bool rcs_uploaded = false; DevBuf<double> d_rcsval; int n_cu = 0; bool stats_pending = false; bool agg_timed = false, fin_timed = false;
+    bool rcs_uploaded = false; DevBuf<double> d_rcsval; int n_cu = 0; bool stats_pending = false;
     RtsStats stats;
     // tabulated patterns (rts_set_patterns): one device buffer per handle, and the per-pulse receiver rows behind a staged upload
     DevBuf<char> d_pat; uint32_t pat_n_rx = 0, pat_n_targets = 0; bool pat_set = false;
     StagedUpload<double> pat_rx;
     double pulse_org[3] = {0, 0, 0}, pulse_dir[2] = {0, 0}; bool pulse_traced = false;      // the last traced pulse's ray_origin / tx_dir; false after rts_kernel_wrapper_on
     double lap_s[8] = {0, 0, 0, 0, 0, 0, 0, 0}; uint64_t lap_n[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // RTS_LAP=1: host time per section of rts_trace_pulse_begin
-    RtsGate* gate = nullptr; bool pulse_open = false;   // gate: never null after rts_create
+    RtsGate* gate = nullptr;            // never null after rts_create
+    RtsPulseState pulse;                // IDLE, OPEN (begun, the trace in flight) or CHAINED (its chain enqueued on the device-side count, awaiting rts_spec_resolve); counted on its device while not IDLE
     // Every raw handle above starts null and the destructor skips what is null: `delete c` is right for a handle that rts_create
     // left half built.  The body (rts_api.hip) drains the streams, drops the shared objects and destroys the events and streams; the
     // DevBuf / PinBuf / StagedUpload members free themselves after it.  The caller makes the handle's device current first.
@@ -446,7 +457,7 @@ int rts_trace_launch(RtsContext* c, const RtsTraceArgs& a, bool count_traversal,
 void rts_trace_preload();
 int rts_post_order_and_expand(RtsContext* c);
 int rts_mirror_reserve(RtsContext* c, uint32_t rows);
-int rts_post_mirror_received(RtsContext* c);       // the ordered, expanded received set -> the host mirror (kernel stores, count from c->recv_dev when set)
+int rts_post_mirror_received(RtsContext* c);       // the ordered, expanded received set -> the host mirror (kernel stores, count from c->res.recv_dev when set)
 int rts_post_mirror_aggregated(RtsContext* c);     // per-ray aggregation outputs -> the host mirror
 int rts_post_set_values(RtsContext* c, const double* power, const double* doppler);      // power / Doppler of the received rays <- device-readable arrays (the mirror's values-in area)
 int rts_post_expand_all(RtsContext* c);
@@ -462,9 +473,9 @@ int rts_cube_stft_device(RtsContext* c, const RtsStftParams& p, const RtsStftPla
 int rts_cube_backproject_device(RtsContext* c, const RtsImageParams& p, const RtsImagePlan& plan, const double* geo, double* out);      // rts_image.hip
 int rts_post_finalise(RtsContext* c, const double* rcs_host, double wl, double gt, double gr, double carrier, double cspeed);
 int rts_pattern_pulse_upload(RtsContext* c, const RtsSpecParams& q, RtsPatArgs* out);      // the pulse's receiver rows -> the device, on c->stream
-int rts_post_finalise_patterns(RtsContext* c, const RtsSpecParams& q);                       // k_finalise_patterns on the received set (count from c->recv_dev when set)
+int rts_post_finalise_patterns(RtsContext* c, const RtsSpecParams& q);                       // k_finalise_patterns on the received set (count from c->res.recv_dev when set)
 hipError_t rts_stream_wait(RtsContext* c, hipStream_t st);
-int rts_aggregate_fetch(RtsContext* c, std::vector<RtsGroup>* groups);      // second half of rts_aggregate_device when groups == &c->groups: no-op when nothing is pending
+int rts_aggregate_fetch(RtsContext* c, std::vector<RtsGroup>* groups);      // second half of rts_aggregate_device when groups == &c->res.groups: no-op when nothing is pending
 int rts_aggregate_device(RtsContext* c, int32_t max_path, int32_t max_rx, const int32_t* d_paths, uint64_t R, uint32_t D,
                          double cspeed, double carrier, uint64_t base, PerRayData* d_rays, double* d_delay,
                          double* d_phase, int32_t* d_pm, std::vector<RtsGroup>* groups, double* d_npath,
@@ -480,7 +491,18 @@ int rts_debug_stage(RtsContext* c, const char* name);
 
 // every entry point that takes a handle (rts_api.hip, rts_cube_api.hip) makes its device current ...
 #define CHECK_HANDLE(c) do { if (!(c)) { rts_set_error("null handle"); return RTS_ERR_INVALID; } RTS_HIP(hipSetDevice((c)->device)); } while (0)
-// ... and those that consume a pulse's results complete a pulse that was begun but not yet ended
-int rts_spec_resolve(RtsContext* c);        // rts_api.hip: the outcome of a chain that was enqueued on the device-side count
-#define CHECK_CLOSED(c) do { if ((c)->pulse_open) { int rc_ = rts_trace_pulse_end(c); if (rc_ != RTS_OK) return rc_; } \
-                             if ((c)->spec_pending) { int rc_ = rts_spec_resolve(c); if (rc_ != RTS_OK) return rc_; } } while (0)
+// ... and those that consume a pulse's results, or replace what its enqueued work reads, settle the handle's pulse first: an OPEN one is
+// ended (rts_trace_pulse_end), a CHAINED one resolved (rts_api.hip)
+int rts_pulse_settle(RtsContext* c);
+#define CHECK_CLOSED(c) do { int rc_ = rts_pulse_settle(c); if (rc_ != RTS_OK) return rc_; } while (0)
+
+// What every finaliser of a received set does around its work: ev[6] / ev[7] bracket it for rts_get_stats, and the aggregation of the
+// set as it was is no longer valid (the mirror keeps the set AS RECEIVED for the rest of the pulse: rts_received_view).
+template <class Work> static inline int rts_finalise_bracket(RtsContext* c, Work work)
+{
+    RTS_HIP(hipEventRecord(c->ev[6], c->stream));
+    { const int rc = work(); if (rc != RTS_OK) return rc; }
+    RTS_HIP(hipEventRecord(c->ev[7], c->stream));
+    c->res.fin_timed = true; c->stats_pending = true; c->res.agg_valid = false;
+    return RTS_OK;
+}

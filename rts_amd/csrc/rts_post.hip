@@ -451,15 +451,15 @@ static int rts_recv_reserve(RtsContext* c, uint32_t R)
 
 int rts_post_order_and_expand(RtsContext* c)
 {
-    const uint32_t R = (uint32_t)c->n_recv, D = c->depth;
+    const uint32_t R = (uint32_t)c->res.n_recv, D = c->depth;
     if (R == 0) return RTS_OK;
     hipStream_t st = c->stream;
     { int rc = rts_recv_reserve(c, R); if (rc != RTS_OK) return rc; }
     size_t tmp = 0;
     if (c->post_small && R <= rts_small_cap_recv(c)) {
         // items per thread by the size of the set (a speculative chain -- count on the device -- is sized for the capacity)
-        const uint32_t cap = c->recv_dev ? rts_small_cap_recv(c) : R, items = rts_small_items(cap), bits = rts_recv_sort_bits(c->n_rays, c->last_args.max_refr);
-        auto order = [&](auto kernel, int with_chain) { kernel<<<1, RTS_SMALL_THREADS, 0, st>>>(c->d_recv.p, R, c->n_rays, with_chain, bits, c->d_ri_sorted.p, c->recv_dev); };
+        const uint32_t cap = c->res.recv_dev ? rts_small_cap_recv(c) : R, items = rts_small_items(cap), bits = rts_recv_sort_bits(c->n_rays, c->last_args.max_refr);
+        auto order = [&](auto kernel, int with_chain) { kernel<<<1, RTS_SMALL_THREADS, 0, st>>>(c->d_recv.p, R, c->n_rays, with_chain, bits, c->d_ri_sorted.p, c->res.recv_dev); };
         if (!rts_recv_key64(c->last_args.max_refr)) { if (items == 4) order(k_recv_order_small<uint32_t, 4>, 0); else if (items == 8) order(k_recv_order_small<uint32_t, 8>, 0); else order(k_recv_order_small<uint32_t, 16>, 0); }
         else { if (items == 4) order(k_recv_order_small<uint64_t, 4>, 1); else order(k_recv_order_small<uint64_t, 8>, 1); }
         RTS_STAGE(c, "recv order (one block)");
@@ -478,7 +478,7 @@ int rts_post_order_and_expand(RtsContext* c)
         RTS_HIP(rocprim::radix_sort_pairs(c->d_sort_tmp.p, tmp, c->d_rk64.p, c->d_rk64_sorted.p, c->d_ri.p, c->d_ri_sorted.p, R, 0, 34, st));
     }
     RTS_STAGE(c, "recv sort");
-    k_expand<<<blocks_for(R, 256), 256, 0, st>>>(c->last_args, c->d_recv.p, c->d_ri_sorted.p, R, D, c->d_rx_rays.p, c->d_rx_paths.p, c->d_rx_angles.p, c->d_rx_slots.p, c->recv_dev);
+    k_expand<<<blocks_for(R, 256), 256, 0, st>>>(c->last_args, c->d_recv.p, c->d_ri_sorted.p, R, D, c->d_rx_rays.p, c->d_rx_paths.p, c->d_rx_angles.p, c->d_rx_slots.p, c->res.recv_dev);
     RTS_STAGE(c, "k_expand");
     RTS_HIP(hipGetLastError());
     return RTS_OK;
@@ -518,7 +518,7 @@ __global__ void k_set_values(PerRayData* __restrict__ rays, const double* __rest
 
 int rts_mirror_reserve(RtsContext* c, uint32_t rows)
 {
-    RtsHostMirror& m = c->mirror;
+    RtsHostMirror& m = c->res.mirror;
     const uint32_t D = c->depth;
     if (m.buf.p && m.cap >= rows && m.D == D) return RTS_OK;
     if (m.buf.p) { RTS_HIP(hipStreamSynchronize(c->stream)); m.buf.release(); m.cap = 0; }
@@ -534,8 +534,8 @@ int rts_mirror_reserve(RtsContext* c, uint32_t rows)
 
 int rts_post_mirror_received(RtsContext* c)
 {
-    RtsHostMirror& m = c->mirror;
-    const uint32_t R = (uint32_t)c->n_recv, D = c->depth;
+    RtsHostMirror& m = c->res.mirror;
+    const uint32_t R = (uint32_t)c->res.n_recv, D = c->depth;
     m.recv_valid = false; m.agg_valid = false;
     if (R == 0) { m.recv_valid = true; return RTS_OK; }
     if (R > m.cap) return RTS_OK;                                  // (a set beyond the mirror: the views fall back to copies)
@@ -545,7 +545,7 @@ int rts_post_mirror_received(RtsContext* c)
     g.dst[2] = (uint32_t*)(m.buf.dev + m.o_angles); g.src[2] = (const uint32_t*)c->d_rx_angles.p; g.row_words[2] = 4 * D;
     g.dst[3] = (uint32_t*)(m.buf.dev + m.o_slots); g.src[3] = (const uint32_t*)c->d_rx_slots.p; g.row_words[3] = 2;
     const uint32_t bx = std::min<uint32_t>(blocks_for((size_t)R * (sizeof(PerRayData) / 4), 256), 64u);
-    k_mirror_rows<<<dim3(bx, 4), 256, 0, c->stream>>>(g, R, c->recv_dev);
+    k_mirror_rows<<<dim3(bx, 4), 256, 0, c->stream>>>(g, R, c->res.recv_dev);
     RTS_HIP(hipGetLastError());
     m.recv_valid = true;
     return RTS_OK;
@@ -553,13 +553,13 @@ int rts_post_mirror_received(RtsContext* c)
 
 int rts_post_mirror_aggregated(RtsContext* c)
 {
-    RtsHostMirror& m = c->mirror;
-    const uint32_t R = (uint32_t)c->n_recv;
+    RtsHostMirror& m = c->res.mirror;
+    const uint32_t R = (uint32_t)c->res.n_recv;
     m.agg_valid = false;
     if (R == 0) { m.agg_valid = true; return RTS_OK; }
     if (!m.buf.p || R > m.cap) return RTS_OK;
     k_mirror_agg<<<blocks_for(R, 256), 256, 0, c->stream>>>(c->d_rx_rays.p, c->d_delay.p, c->d_phase.p, c->d_pathmatch.p, R, (double*)(m.buf.dev + m.o_apower), (double*)(m.buf.dev + m.o_adoppler),
-                                                           (double*)(m.buf.dev + m.o_adelay), (double*)(m.buf.dev + m.o_aphase), (int32_t*)(m.buf.dev + m.o_apm), c->recv_dev);
+                                                           (double*)(m.buf.dev + m.o_adelay), (double*)(m.buf.dev + m.o_aphase), (int32_t*)(m.buf.dev + m.o_apm), c->res.recv_dev);
     RTS_HIP(hipGetLastError());
     m.agg_valid = true;
     return RTS_OK;
@@ -567,7 +567,7 @@ int rts_post_mirror_aggregated(RtsContext* c)
 
 int rts_post_set_values(RtsContext* c, const double* power, const double* doppler)
 {
-    const uint32_t R = (uint32_t)c->n_recv;
+    const uint32_t R = (uint32_t)c->res.n_recv;
     if (R == 0) return RTS_OK;
     k_set_values<<<blocks_for(R, 256), 256, 0, c->stream>>>(c->d_rx_rays.p, power, doppler, R);
     RTS_HIP(hipGetLastError());
@@ -628,11 +628,11 @@ static int rts_rcs_upload(RtsContext* c, const double* rcs_host)
 
 int rts_post_finalise(RtsContext* c, const double* rcs_host, double wl, double gt, double gr, double carrier, double cspeed)
 {
-    const uint32_t R = (uint32_t)c->n_recv;
+    const uint32_t R = (uint32_t)c->res.n_recv;
     if (R == 0) return RTS_OK;
     const uint32_t nt = (uint32_t)c->scene->meshes.size();
     { int rc = rts_rcs_upload(c, rcs_host); if (rc != RTS_OK) return rc; }
-    k_finalise<<<blocks_for(R, 256), 256, 0, c->stream>>>(c->d_rx_rays.p, c->d_rx_paths.p, R, c->depth, c->d_rcsval.p, nt, wl, gt, gr, carrier, cspeed, c->recv_dev);
+    k_finalise<<<blocks_for(R, 256), 256, 0, c->stream>>>(c->d_rx_rays.p, c->d_rx_paths.p, R, c->depth, c->d_rcsval.p, nt, wl, gt, gr, carrier, cspeed, c->res.recv_dev);
     RTS_HIP(hipGetLastError());
     return RTS_OK;
 }
@@ -704,11 +704,11 @@ int rts_pattern_pulse_upload(RtsContext* c, const RtsSpecParams& q, RtsPatArgs* 
 
 int rts_post_finalise_patterns(RtsContext* c, const RtsSpecParams& q)
 {
-    const uint32_t R = (uint32_t)c->n_recv;
+    const uint32_t R = (uint32_t)c->res.n_recv;
     if (R == 0) return RTS_OK;
     RtsPatArgs a;
     int rc = rts_pattern_pulse_upload(c, q, &a); if (rc != RTS_OK) return rc;
-    k_finalise_patterns<<<blocks_for(R, 256), 256, 0, c->stream>>>(c->d_rx_rays.p, c->d_rx_paths.p, c->d_rx_angles.p, R, c->depth, a, c->recv_dev);
+    k_finalise_patterns<<<blocks_for(R, 256), 256, 0, c->stream>>>(c->d_rx_rays.p, c->d_rx_paths.p, c->d_rx_angles.p, R, c->depth, a, c->res.recv_dev);
     RTS_HIP(hipGetLastError());
     return RTS_OK;
 }
@@ -740,10 +740,10 @@ __global__ void k_cube_accumulate(const PerRayData* __restrict__ rays, uint32_t 
 
 int rts_cube_accumulate_device(RtsContext* c, uint32_t pulse_index, double cspeed, double carrier)
 {
-    const uint32_t R = (uint32_t)c->n_recv;
+    const uint32_t R = (uint32_t)c->res.n_recv;
     if (R == 0) return RTS_OK;
     const RtsCubeParams& q = c->cube.params;
-    k_cube_accumulate<<<blocks_for(R, 256), 256, 0, c->stream>>>(c->d_rx_rays.p, R, c->cube.p, q.n_rx, q.n_pulses, q.n_bins, pulse_index, q.t0, q.dt, cspeed, carrier, c->recv_dev);
+    k_cube_accumulate<<<blocks_for(R, 256), 256, 0, c->stream>>>(c->d_rx_rays.p, R, c->cube.p, q.n_rx, q.n_pulses, q.n_bins, pulse_index, q.t0, q.dt, cspeed, carrier, c->res.recv_dev);
     RTS_HIP(hipGetLastError());
     return RTS_OK;
 }
@@ -769,7 +769,7 @@ __global__ void k_cube_accumulate_paths(const PerRayData* __restrict__ rays, con
 
 int rts_cube_accumulate_paths_device(RtsContext* c, uint32_t pulse_index, int64_t base)
 {
-    const uint32_t R = (uint32_t)c->n_recv;
+    const uint32_t R = (uint32_t)c->res.n_recv;
     if (R == 0) return RTS_OK;
     const RtsCubeParams& q = c->cube.params;
     k_cube_accumulate_paths<<<blocks_for(R, 256), 256, 0, c->stream>>>(c->d_rx_rays.p, c->d_delay.p, c->d_phase.p, c->d_pathmatch.p, R, base, c->cube.p, q.n_rx, q.n_pulses, q.n_bins,
@@ -1329,7 +1329,7 @@ static RtsAggFinish rts_agg_finish_args(RtsContext* c, const RtsKeyPlan& k, cons
 // the group table of R rays is on its way to the pinned block: rts_aggregate_fetch reads it
 static void rts_agg_pending_set(RtsContext* c, const RtsKeyPlan& k, uint32_t R, uint32_t D, uint64_t base, bool rows, double* gsum)
 {
-    RtsAggPending& ap = c->agg_pending; ap.valid = true; ap.R = R; ap.D = D; ap.key = k; ap.base = base; ap.rows = rows; ap.spec = rts_agg_spec(R); ap.gsum = gsum;
+    RtsAggPending& ap = c->res.agg_pending; ap.valid = true; ap.R = R; ap.D = D; ap.key = k; ap.base = base; ap.rows = rows; ap.spec = rts_agg_spec(R); ap.gsum = gsum;
 }
 // k_post_all for the sorts' key types, with finaliser f
 template <typename FIN> static void rts_post_all_launch(hipStream_t st, const RtsPostAll& q, bool kr64, bool ka64, const FIN& f)
@@ -1373,7 +1373,7 @@ int rts_post_all_small(RtsContext* c, uint32_t cap, const RtsSpecParams& sp, boo
         rts_post_all_launch(st, q, kr64, ka64, f);
     }
     RTS_HIP(hipGetLastError());
-    c->recv_index_base = sp.base; c->agg_base_local = use_rows ? 0 : (int64_t)sp.base;
+    c->res.recv_index_base = sp.base; c->res.agg_base_local = use_rows ? 0 : (int64_t)sp.base;
     rts_agg_pending_set(c, k, cap, D, base, use_rows, s.gsum);
     return RTS_OK;
 }
@@ -1404,8 +1404,8 @@ int rts_aggregate_device(RtsContext* c, int32_t max_path, int32_t max_rx, const 
     const uint32_t small_cap = rts_small_cap(rts_agg_key64(k));
     const bool small = c->post_small && !k.wide && R <= small_cap;       // one block orders, one block finishes (see k_agg_order_small)
     if (small) {
-        const uint32_t cap = c->recv_dev ? small_cap : R;             // (a chain enqueued on the device-side count is sized for the capacity)
-        auto order = [&](auto kernel) { kernel<<<1, RTS_SMALL_THREADS, 0, st>>>(d_rays, d_paths, R, D, k.B, k.key_bits, c->d_akeys_sorted.p, c->d_aidx_sorted.p, c->d_ghead.p, c->d_gid.p, s.gstart, c->recv_dev); };
+        const uint32_t cap = c->res.recv_dev ? small_cap : R;             // (a chain enqueued on the device-side count is sized for the capacity)
+        auto order = [&](auto kernel) { kernel<<<1, RTS_SMALL_THREADS, 0, st>>>(d_rays, d_paths, R, D, k.B, k.key_bits, c->d_akeys_sorted.p, c->d_aidx_sorted.p, c->d_ghead.p, c->d_gid.p, s.gstart, c->res.recv_dev); };
         const uint32_t items = rts_small_items(cap);
         if (!rts_agg_key64(k)) { if (items == 4) order(k_agg_order_small<uint32_t, 4>); else if (items == 8) order(k_agg_order_small<uint32_t, 8>); else order(k_agg_order_small<uint32_t, 16>); }
         else { if (items == 4) order(k_agg_order_small<uint64_t, 4>); else order(k_agg_order_small<uint64_t, 8>); }
@@ -1435,23 +1435,23 @@ int rts_aggregate_device(RtsContext* c, int32_t max_path, int32_t max_rx, const 
         RTS_HIP(rocprim::inclusive_scan(c->d_sort_tmp.p, tmp, c->d_ghead.p, c->d_gid.p, R, rocprim::plus<uint32_t>(), st));
         k_agg_starts<<<blocks_for(R, 256), 256, 0, st>>>(c->d_ghead.p, c->d_gid.p, s.gstart, R);
     }
-    k_agg_tiles<<<s.ntiles, AGG_TILE, 0, st>>>(d_rays, c->d_aidx_sorted.p, c->d_gid.p, s.gstart, R, cspeed, carrier, s.gsum, s.tile_first, s.tile_last, c->recv_dev);
+    k_agg_tiles<<<s.ntiles, AGG_TILE, 0, st>>>(d_rays, c->d_aidx_sorted.p, c->d_gid.p, s.gstart, R, cspeed, carrier, s.gsum, s.tile_first, s.tile_last, c->res.recv_dev);
     if (small) {
         RtsAggFinish fq = rts_agg_finish_args(c, k, s, R, d_rays, d_rows, base, groups != nullptr);
         fq.npath0 = d_npath; fq.power0 = d_power_sum; fq.doppler0 = d_doppler_sum; fq.delay = d_delay; fq.phase = d_phase; fq.pm = d_pm;      // the caller's in-out arrays
-        fq.pm_init_const = pm_init; fq.use_pm_in = pm_init == INT32_MIN ? 1 : 0; fq.dly_in = c->agg_delay_in ? 1 : 0;
-        k_agg_finish_small<<<1, 256, 0, st>>>(fq, R, s.ntiles, c->recv_dev);
+        fq.pm_init_const = pm_init; fq.use_pm_in = pm_init == INT32_MIN ? 1 : 0; fq.dly_in = c->res.agg_delay_in ? 1 : 0;
+        k_agg_finish_small<<<1, 256, 0, st>>>(fq, R, s.ntiles, c->res.recv_dev);
         RTS_HIP(hipGetLastError());
         if (!groups) { RTS_HIP(hipStreamSynchronize(st)); return RTS_OK; }
         rts_agg_pending_set(c, k, R, D, base, d_rows != nullptr, s.gsum);
-        if (groups != &c->groups) return rts_aggregate_fetch(c, groups);
+        if (groups != &c->res.groups) return rts_aggregate_fetch(c, groups);
         return RTS_OK;
     }
     k_agg_span<<<s.ntiles, 64, 0, st>>>(s.gstart, c->d_gid.p, R, s.tile_first, s.tile_last, s.gsum);
     k_agg_groupinfo<<<blocks_for(R, 256), 256, 0, st>>>(s.gstart, c->d_aidx_sorted.p, c->d_akeys_sorted.p, c->d_gid.p, R, c->d_gmin.p, c->d_gkey.p, s.d_G, d_rows, d_rows ? c->d_grow.p : nullptr);
     k_agg_rxtot<<<k.n_rx_tab, 64, 0, st>>>(c->d_gkey.p, s.gsum, c->d_gmin.p, s.d_G, k.shift, s.rxtot, s.rxmin);
     k_agg_scatter<<<blocks_for(R, 256), 256, 0, st>>>(d_rays, c->d_aidx_sorted.p, c->d_gid.p, s.gsum, c->d_gmin.p, s.rxtot, s.rxmin, k.n_rx_tab, R,
-                                                       (int64_t)base, d_npath, d_power_sum, d_doppler_sum, d_delay, d_phase, d_pm, pm_init, pm_init == INT32_MIN ? 1 : 0, c->agg_delay_in ? 1 : 0);
+                                                       (int64_t)base, d_npath, d_power_sum, d_doppler_sum, d_delay, d_phase, d_pm, pm_init, pm_init == INT32_MIN ? 1 : 0, c->res.agg_delay_in ? 1 : 0);
     RTS_HIP(hipGetLastError());
     if (!groups) { RTS_HIP(hipStreamSynchronize(st)); return RTS_OK; }
     if (k.wide) {                                        // the groups' path rows, for the host copy of the table
@@ -1468,14 +1468,14 @@ int rts_aggregate_device(RtsContext* c, int32_t max_path, int32_t max_rx, const 
     // next pulse while this one's ~16 small kernels wait their turn among the trace kernels' blocks -- the submitting thread used
     // to sit out that chain here, 0.4 of the 0.63 ms of a pipelined BASELINE configs[2] pulse.
     rts_agg_pending_set(c, k, R, D, base, d_rows != nullptr, s.gsum);
-    if (groups != &c->groups) return rts_aggregate_fetch(c, groups);          // (a caller's own vector: now)
+    if (groups != &c->res.groups) return rts_aggregate_fetch(c, groups);          // (a caller's own vector: now)
     return RTS_OK;
 }
 
 // Second half of rts_aggregate_device: wait for the handle's stream and turn the exported table into RtsGroup records.
 int rts_aggregate_fetch(RtsContext* c, std::vector<RtsGroup>* groups)
 {
-    RtsAggPending& ap = c->agg_pending;
+    RtsAggPending& ap = c->res.agg_pending;
     if (!ap.valid) return RTS_OK;
     ap.valid = false;
     hipStream_t st = c->stream;

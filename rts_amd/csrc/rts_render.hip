@@ -103,7 +103,7 @@ __global__ void __launch_bounds__(RTS_RENDER_TILE) k_cube_render(const RtsRender
 
 int rts_cube_render_device(RtsContext* c, uint32_t pulse_index, bool paths, bool doppler, double cspeed, double carrier, int64_t base)
 {
-    const uint32_t R = (uint32_t)c->n_recv;
+    const uint32_t R = (uint32_t)c->res.n_recv;
     if (R == 0) return RTS_OK;
     const RtsCubeParams& q = c->cube.params;
     RtsRenderArgs a;
@@ -114,7 +114,7 @@ int rts_cube_render_device(RtsContext* c, uint32_t pulse_index, bool paths, bool
     const size_t lds = sizeof(double) * (2 * (size_t)a.M + (size_t)RTS_RENDER_SUB * a.L);      // <= 64 KiB + 16 KiB
     RTS_HIP(hipFuncSetAttribute((const void*)k_cube_render, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     dim3 grid((q.n_bins + RTS_RENDER_TILE - 1) / RTS_RENDER_TILE, q.n_rx);
-    k_cube_render<<<grid, RTS_RENDER_TILE, lds, c->stream>>>(a, c->recv_dev);
+    k_cube_render<<<grid, RTS_RENDER_TILE, lds, c->stream>>>(a, c->res.recv_dev);
     RTS_HIP(hipGetLastError());
     return RTS_OK;
 }
