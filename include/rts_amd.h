@@ -532,6 +532,61 @@ typedef struct RtsDetection {
 int rts_cube_detect(RtsHandle h, const RtsCfarParams* p, const void* device_map, uint32_t n_doppler);
 int rts_cube_detections_get(RtsHandle h, RtsDetection* out, uint32_t capacity, uint32_t* n_out);
 
+/* ---------------------------------------------------------------- ordered-statistic (OS) CFAR detection on the range-Doppler map
+ * The detector above with the noise estimated by a RANK of the training powers instead of their mean: the estimate stays put until
+ * k of a cell's N training cells are contaminated, so a strong return (another target, a multi-bounce path a few bins away, a
+ * blade flash along Doppler) in a neighbour's window does not lift that neighbour's threshold by P / N and hide it.  Its own entry
+ * point and parameter record: rts_cube_detect keeps refusing modes above RTS_CFAR_SO.  The arithmetic is rts_amd/csrc/rts_cfar_os.h,
+ * shared by the kernel (rts_detect.hip) and the host evaluator.
+ *   Taken unchanged from rts_cube_detect: the input map (the handle's last rts_cube_doppler output, or a caller device pointer, 16-byte
+ *     aligned, with n_doppler >= 1); the window (the training annulus |dk| <= Gd + Td, |dr| <= Gr + Tr minus the guard rectangle,
+ *     Doppler wrapped, range truncated, so N varies near the range edges); RTS_CFAR_LOCAL_MAX, including its behaviour on one-row and
+ *     two-row maps; the refinement, the delay and doppler fields and the Doppler sign; the output order, flat (rx, doppler_bin,
+ *     range_bin), from counts and a scan, never from atomics; RtsDetection, max_detections, RTS_CFAR_DEFAULT_MAX_DETECTIONS.
+ *     rts_cube_detect_os never waits on the host.  Its list shares the handle's detection buffers and is read with
+ *     rts_cube_detections_get; a later rts_cube_detect, rts_cube_detect_os, rts_cube_attach or rts_destroy ends it.
+ *   Window size and rank: a full window holds N0 = (2 (Gr + Tr) + 1) (2 (Gd + Td) + 1) - (2 Gr + 1) (2 Gd + 1) training cells
+ *     (at most RTS_CFAR_OS_MAX_TRAIN) and `rank` = k0 in [1, N0] is the rank in a full window.  A cell with N training cells uses the
+ *     rank k = (rank N + N0 - 1) / N0 in integer arithmetic, the ceiling of rank N / N0; it is at least 1 because N >= 1 under the
+ *     validation rules.
+ *   Noise, threshold, detection: noise is the k-th smallest (1-based) of the N training powers P = re re + im im; threshold =
+ *     alpha noise, one multiply; a cell is detected when P > threshold (and, with RTS_CFAR_LOCAL_MAX, is a local maximum).
+ *     RtsDetection.noise is that order statistic -- one of the map's own powers, bit for bit -- and n_train is N.  Powers are assumed
+ *     finite or +inf; with a NaN in the map which cells are reported is unspecified, but nothing is read out of bounds.
+ *   pfa: each cell uses alpha(N, k), the root of prod_{i=0}^{k-1} (N - i) / (N - i + alpha) = pfa, the exact OS false-alarm law for
+ *     square-law detected complex Gaussian noise: the rate is pfa at the range edges too.  rts_cfar_os_alpha (pure host; n_train = N,
+ *     rank = k) returns that root such that the product, re-evaluated at the returned alpha, is within 1e-11 relative of pfa
+ *     (rounding alpha moves ln of the product by at most k 2^-53, about 1.2e-13; a checker evaluating k <= 1 088 factors adds about
+ *     3 k 2^-53, about 3.6e-13; 1e-11 leaves a factor of 20 over the sum).  The device path and rts_cfar_os_eval take their alphas
+ *     from this one function -- rts_cube_detect_os computes them on the host for the values of N that occur and passes them as a
+ *     table -- so their thresholds are equal bit for bit.
+ *   rts_cfar_os_eval: pure host, the same detector on a host map [n_rx][n_doppler][n_bins] (complex128, interleaved) with q (n_rx,
+ *     n_bins, t0, dt; n_pulses is not used) in place of the attached cube: up to `capacity` records to out in the same order, the
+ *     total to *n_out.  Integer fields, power, noise and threshold equal the device's bit for bit; the refinement fields to the
+ *     rounding of log.
+ *   RTS_ERR_INVALID, the message naming the field: everything rts_cube_detect refuses on the shared fields (no cube or no map;
+ *     unknown flags; nonzero reserved fields; Tr + Td = 0; Gr + Tr or Gd + Td > RTS_CFAR_MAX_HALF; 2 (Gd + Td) + 1 > n_doppler;
+ *     Gr + Tr >= n_bins; pfa outside (0, 1); both or neither of pfa and alpha (alpha > 0 and finite); pri negative or not finite);
+ *     rank = 0 or rank > N0.  rts_cfar_os_alpha refuses n_train = 0, rank = 0, rank > n_train, pfa outside (0, 1) and a NULL output.
+ *     rts_cfar_os_eval applies the same validation and also refuses NULL arguments (out may be NULL when capacity is 0); a refused
+ *     call leaves out untouched.  It returns RTS_ERR_CAPACITY, with *n_out the total and the first `capacity` records written, when
+ *     capacity is too small. */
+#define RTS_CFAR_OS_MAX_TRAIN 1088u        /* (2*16+1)^2 - 1 */
+typedef struct RtsCfarOsParams {
+    uint32_t guard_range, guard_doppler, train_range, train_doppler;   /* cells on EACH side of the cell under test */
+    uint32_t rank;           /* k0 in [1, N0]: the rank in a FULL window of N0 training cells                  */
+    uint32_t flags;          /* RTS_CFAR_LOCAL_MAX                                                            */
+    double pfa;              /* (0, 1) -> alpha per cell from its own training count and rank; 0: use alpha   */
+    double alpha;            /* > 0 when pfa == 0                                                             */
+    double pri;              /* pulse repetition interval for RtsDetection.doppler; 0: doppler = 0            */
+    uint32_t max_detections; /* device list length; 0: 65 536                                                 */
+    uint32_t reserved0; uint64_t reserved[2];                                         /* 0 */
+} RtsCfarOsParams;                            /* 72 bytes */
+int rts_cube_detect_os(RtsHandle h, const RtsCfarOsParams* p, const void* device_map, uint32_t n_doppler);
+int rts_cfar_os_alpha(uint32_t n_train, uint32_t rank, double pfa, double* alpha);
+int rts_cfar_os_eval(const RtsCubeParams* q, const double* map, uint32_t n_doppler, const RtsCfarOsParams* p,
+                     RtsDetection* out, uint32_t capacity, uint32_t* n_out);
+
 /* ---------------------------------------------------------------- tapered slow-time spectrogram (STFT) of the return cube
  * The short-time Fourier transform over the pulse axis, per range gate bin or summed over a gate: how Doppler changes INSIDE the
  * interval (rotor and blade flashes, tumbling bodies), where rts_cube_doppler's single rectangular DFT smears it into a band.  A

@@ -116,6 +116,17 @@ DETECTION_DTYPE = np.dtype([("rx", "<u4"), ("doppler_bin", "<u4"), ("range_bin",
                             ("delay", "<f8"), ("doppler", "<f8")])
 assert DETECTION_DTYPE.itemsize == 72 and C.sizeof(RtsCfarParams) == 72
 
+RTS_CFAR_OS_MAX_TRAIN = 1088
+
+
+class RtsCfarOsParams(C.Structure):
+    _fields_ = [("guard_range", C.c_uint32), ("guard_doppler", C.c_uint32), ("train_range", C.c_uint32), ("train_doppler", C.c_uint32),
+                ("rank", C.c_uint32), ("flags", C.c_uint32), ("pfa", C.c_double), ("alpha", C.c_double), ("pri", C.c_double),
+                ("max_detections", C.c_uint32), ("reserved0", C.c_uint32), ("reserved", C.c_uint64 * 2)]
+
+
+assert C.sizeof(RtsCfarOsParams) == 72
+
 
 RTS_IMAGE_ACCUMULATE, RTS_IMAGE_PULSE_CHUNK, RTS_IMAGE_MAX_PIXELS = 1, 64, 16777216
 
@@ -232,6 +243,7 @@ EXPORTS = ["rts_create", "rts_destroy", "rts_last_error", "rts_device_count", "r
            "rts_set_patterns", "rts_finalise_patterns", "rts_trace_pulse_end_patterns", "rts_pattern_eval",
            "rts_cube_set_waveform", "rts_cube_render", "rts_cube_compress", "rts_waveform_eval",
            "rts_cube_add_noise", "rts_noise_eval", "rts_cube_detect", "rts_cube_detections_get",
+           "rts_cube_detect_os", "rts_cfar_os_alpha", "rts_cfar_os_eval",
            "rts_cube_backproject", "rts_cube_image_get", "rts_backproject_eval",
            "rts_cube_spectrogram", "rts_cube_spectrogram_get", "rts_stft_eval", "rts_window_make"]
 
@@ -306,6 +318,9 @@ def lib():
         "rts_noise_eval": [u64, vp, u32, C.c_double, vp],
         "rts_cube_detect": [vp, C.POINTER(RtsCfarParams), vp, u32],
         "rts_cube_detections_get": [vp, vp, u32, C.POINTER(u32)],
+        "rts_cube_detect_os": [vp, C.POINTER(RtsCfarOsParams), vp, u32],
+        "rts_cfar_os_alpha": [u32, u32, C.c_double, C.POINTER(C.c_double)],
+        "rts_cfar_os_eval": [C.POINTER(RtsCubeParams), vp, u32, C.POINTER(RtsCfarOsParams), vp, u32, C.POINTER(u32)],
         "rts_cube_backproject": [vp, C.POINTER(RtsImageParams), vp],
         "rts_cube_image_get": [vp, vp, u64],
         "rts_backproject_eval": [C.POINTER(RtsCubeParams), vp, C.POINTER(RtsImageParams), vp],

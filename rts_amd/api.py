@@ -203,6 +203,50 @@ def noise_eval(seed, index, noise_power):
     return (out[:, 0] + 1j * out[:, 1]).reshape(shape)
 
 
+# ------------------------------------------------------------------------------- ordered-statistic CFAR (rts_cfar_os.h)
+def cfar_os_n0(guard, train):
+    """training cells of a full window: guard and train are (range, Doppler) cells on each side"""
+    (gr, gd), (tr, td) = (int(g) for g in guard), (int(t) for t in train)
+    return (2 * (gr + tr) + 1) * (2 * (gd + td) + 1) - (2 * gr + 1) * (2 * gd + 1)
+
+
+def cfar_os_alpha(n, k, pfa):
+    """rts_cfar_os_alpha (pure host): the threshold factor of the k-th smallest of n training cells at false-alarm rate pfa"""
+    a = C.c_double(0.0)
+    check(L.lib().rts_cfar_os_alpha(int(n), int(k), float(pfa), C.byref(a)))
+    return a.value
+
+
+def _cfar_os_params(guard, train, rank, pfa, alpha, local_max, pri, max_detections):
+    """RtsCfarOsParams; rank None: three quarters of a full window, (3 N0) // 4"""
+    p = L.RtsCfarOsParams()
+    p.guard_range, p.guard_doppler = (int(g) for g in guard)
+    p.train_range, p.train_doppler = (int(t) for t in train)
+    p.rank = (3 * cfar_os_n0(guard, train)) // 4 if rank is None else int(rank)
+    p.flags = L.RTS_CFAR_LOCAL_MAX if local_max else 0
+    p.pfa = 0.0 if pfa is None else float(pfa)
+    p.alpha = 0.0 if alpha is None else float(alpha)
+    p.pri, p.max_detections = float(pri), int(max_detections)
+    return p
+
+
+def cfar_os_eval(map, guard=(2, 2), train=(8, 4), rank=None, pfa=None, alpha=None, local_max=True, pri=0.0, t0=0.0, dt=1.0):
+    """rts_cfar_os_eval (pure host): OS-CFAR on a host map [n_rx][n_doppler][n_bins] (complex); a DETECTION_DTYPE array in flat
+    (rx, doppler_bin, range_bin) order"""
+    m = np.ascontiguousarray(np.asarray(map, np.complex128))
+    n_rx, nd, nb = m.shape
+    q = L.RtsCubeParams(n_rx, 1, nb, 0, float(t0), float(dt))
+    p = _cfar_os_params(guard, train, rank, pfa, alpha, local_max, pri, 0)
+    n = C.c_uint32(0)
+    out = np.zeros(min(m.size, 65536), L.DETECTION_DTYPE)
+    rc = L.lib().rts_cfar_os_eval(C.byref(q), ptr(m.view(np.float64)), nd, C.byref(p), ptr(out), len(out), C.byref(n))
+    if rc == L.RTS_ERR_CAPACITY:
+        out = np.zeros(n.value, L.DETECTION_DTYPE)
+        rc = L.lib().rts_cfar_os_eval(C.byref(q), ptr(m.view(np.float64)), nd, C.byref(p), ptr(out), len(out), C.byref(n))
+    check(rc)
+    return out[:n.value].copy()
+
+
 # ------------------------------------------------------------------------------- backprojection imaging (rts_image.h)
 def _image_params(origin, step_x, step_y, n_x, n_y, tx_positions, rx_positions, cspeed, carrier, taps, first, count, weights, accumulate, n_rx):
     """RtsImageParams and the arrays it points to (keep them alive for the call).  tx_positions [P][3]; rx_positions [n_rx][P][3]
@@ -649,8 +693,20 @@ class Tracer:
         check(L.lib().rts_cube_detect(self.h, C.byref(p), C.c_void_p(device_ptr) if device_ptr else None, int(n_doppler or 0)))
         return self.detections() if fetch else None
 
+    def cube_detect_os(self, guard=(2, 2), train=(8, 4), rank=None, pfa=None, alpha=None, local_max=True, pri=0.0, device_ptr=None,
+                       n_doppler=None, max_detections=0, fetch=True):
+        """rts_cube_detect_os + rts_cube_detections_get: ordered-statistic CFAR on the handle's last cube_doppler map (device_ptr None)
+        or on a caller complex128 device map [n_rx][n_doppler][n_bins]; guard and train are (range, Doppler) cells on each side; rank
+        is the rank in a full window of N0 training cells (None: (3 N0) // 4); exactly one of pfa and alpha.  Returns a
+        DETECTION_DTYPE array in flat (rx, doppler_bin, range_bin) order."""
+        p = _cfar_os_params(guard, train, rank, pfa, alpha, local_max, pri, max_detections)
+        if device_ptr and n_doppler is None:
+            raise ValueError("cube_detect_os(device_ptr=...) needs n_doppler")
+        check(L.lib().rts_cube_detect_os(self.h, C.byref(p), C.c_void_p(device_ptr) if device_ptr else None, int(n_doppler or 0)))
+        return self.detections() if fetch else None
+
     def detections(self):
-        """rts_cube_detections_get: the list of the last cube_detect (every stored record; raises when max_detections cut it)"""
+        """rts_cube_detections_get: the list of the last cube_detect or cube_detect_os (every stored record; raises when max_detections cut it)"""
         n = C.c_uint32(0)
         rc = L.lib().rts_cube_detections_get(self.h, None, 0, C.byref(n))
         if rc not in (L.RTS_OK, L.RTS_ERR_CAPACITY):

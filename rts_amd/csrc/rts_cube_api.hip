@@ -215,7 +215,7 @@ extern "C" int rts_cube_detections_get(RtsHandle c, RtsDetection* out, uint32_t 
 {
     CHECK_HANDLE(c);
     if (!n_out || (capacity && !out)) { rts_set_error("rts_cube_detections_get: null output"); return RTS_ERR_INVALID; }
-    if (!c->cube.det_valid) { rts_set_error("rts_cube_detections_get: no detection list (rts_cube_detect; a list ends at rts_cube_attach)"); return RTS_ERR_INVALID; }
+    if (!c->cube.det_valid) { rts_set_error("rts_cube_detections_get: no detection list (rts_cube_detect, rts_cube_detect_os; a list ends at rts_cube_attach)"); return RTS_ERR_INVALID; }
     RTS_HIP(hipStreamSynchronize(c->stream));
     uint32_t total = 0;
     RTS_HIP(hipMemcpy(&total, c->cube.d_det_off.p + c->cube.det_nseg, sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -225,6 +225,95 @@ extern "C" int rts_cube_detections_get(RtsHandle c, RtsDetection* out, uint32_t 
     if (n) RTS_HIP(hipMemcpy(out, c->cube.d_det.p, sizeof(RtsDetection) * n, hipMemcpyDeviceToHost));
     if (n < total) { rts_set_error("rts_cube_detections_get: %u of %u detections copied (max_detections %u, capacity %u)", n, total, c->cube.det_max, capacity); return RTS_ERR_CAPACITY; }
     return RTS_OK;
+}
+
+// ------------------------------------------------------------------------------------- ordered-statistic CFAR
+// (rts_amd.h: RtsCfarOsParams; the arithmetic is rts_cfar_os.h, shared by the host exports and the kernel, rts_detect.hip)
+static int rts_cfar_os_check(const RtsCfarOsParams* p, uint32_t nb, uint32_t n_doppler, const char* who)
+{
+    const uint32_t Gr = p->guard_range, Gd = p->guard_doppler, Tr = p->train_range, Td = p->train_doppler;
+    if (p->flags & ~RTS_CFAR_LOCAL_MAX) { rts_set_error("%s: unknown flags 0x%x", who, p->flags); return RTS_ERR_INVALID; }
+    if (p->reserved0 || p->reserved[0] || p->reserved[1]) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
+    if (Tr > RTS_CFAR_MAX_HALF || Td > RTS_CFAR_MAX_HALF || Gr > RTS_CFAR_MAX_HALF || Gd > RTS_CFAR_MAX_HALF) { rts_set_error("%s: guard_range, guard_doppler, train_range, train_doppler are at most %u each", who, RTS_CFAR_MAX_HALF); return RTS_ERR_INVALID; }
+    if (Tr + Td == 0) { rts_set_error("%s: train_range + train_doppler = 0 (no training cells)", who); return RTS_ERR_INVALID; }
+    if (Gr + Tr > RTS_CFAR_MAX_HALF) { rts_set_error("%s: guard_range + train_range = %u > %u", who, Gr + Tr, RTS_CFAR_MAX_HALF); return RTS_ERR_INVALID; }
+    if (Gd + Td > RTS_CFAR_MAX_HALF) { rts_set_error("%s: guard_doppler + train_doppler = %u > %u", who, Gd + Td, RTS_CFAR_MAX_HALF); return RTS_ERR_INVALID; }
+    if (2 * (Gd + Td) + 1 > n_doppler) { rts_set_error("%s: guard_doppler + train_doppler = %u: the window (%u rows) exceeds n_doppler = %u", who, Gd + Td, 2 * (Gd + Td) + 1, n_doppler); return RTS_ERR_INVALID; }
+    if (Gr + Tr >= nb) { rts_set_error("%s: guard_range + train_range = %u >= n_bins = %u", who, Gr + Tr, nb); return RTS_ERR_INVALID; }
+    const uint32_t N0 = rts_cfar_os_n0(Gr, Gd, Tr, Td);
+    if (p->rank == 0 || p->rank > N0) { rts_set_error("%s: rank = %u outside [1, N0 = %u] (the training cells of a full window)", who, p->rank, N0); return RTS_ERR_INVALID; }
+    const bool has_pfa = p->pfa != 0.0, has_alpha = p->alpha != 0.0;
+    if (has_pfa && !(p->pfa > 0.0 && p->pfa < 1.0)) { rts_set_error("%s: pfa = %g outside (0, 1)", who, p->pfa); return RTS_ERR_INVALID; }
+    if (has_pfa == has_alpha) { rts_set_error("%s: give exactly one of pfa and alpha", who); return RTS_ERR_INVALID; }
+    if (has_alpha && !(p->alpha > 0.0 && std::isfinite(p->alpha))) { rts_set_error("%s: alpha = %g (finite, > 0)", who, p->alpha); return RTS_ERR_INVALID; }
+    if (!(p->pri >= 0.0) || !std::isfinite(p->pri)) { rts_set_error("%s: pri = %g (finite, >= 0)", who, p->pri); return RTS_ERR_INVALID; }
+    return RTS_OK;
+}
+
+extern "C" int rts_cfar_os_alpha(uint32_t n_train, uint32_t rank, double pfa, double* alpha)
+{
+    if (n_train == 0) { rts_set_error("rts_cfar_os_alpha: n_train = 0"); return RTS_ERR_INVALID; }
+    if (rank == 0 || rank > n_train) { rts_set_error("rts_cfar_os_alpha: rank = %u outside [1, n_train = %u]", rank, n_train); return RTS_ERR_INVALID; }
+    if (!(pfa > 0.0 && pfa < 1.0)) { rts_set_error("rts_cfar_os_alpha: pfa = %g outside (0, 1)", pfa); return RTS_ERR_INVALID; }
+    if (!alpha) { rts_set_error("rts_cfar_os_alpha: null output"); return RTS_ERR_INVALID; }
+    *alpha = rts_cfar_os_alpha_solve(n_train, rank, pfa);
+    return RTS_OK;
+}
+
+extern "C" int rts_cfar_os_eval(const RtsCubeParams* q, const double* map, uint32_t n_doppler, const RtsCfarOsParams* p, RtsDetection* out, uint32_t capacity, uint32_t* n_out)
+{
+    if (!q || q->n_rx == 0 || q->n_bins == 0 || !(q->dt > 0) || !std::isfinite(q->dt) || !std::isfinite(q->t0)) { rts_set_error("rts_cfar_os_eval: bad cube parameters"); return RTS_ERR_INVALID; }
+    if (!p) { rts_set_error("rts_cfar_os_eval: null parameters"); return RTS_ERR_INVALID; }
+    if (n_doppler == 0) { rts_set_error("rts_cfar_os_eval: n_doppler = 0"); return RTS_ERR_INVALID; }
+    int rc = rts_cfar_os_check(p, q->n_bins, n_doppler, "rts_cfar_os_eval"); if (rc != RTS_OK) return rc;
+    if (!map || !n_out || (capacity && !out)) { rts_set_error("rts_cfar_os_eval: null map or output"); return RTS_ERR_INVALID; }
+    const uint32_t N0 = rts_cfar_os_n0(p->guard_range, p->guard_doppler, p->train_range, p->train_doppler);
+    std::vector<double> tab; std::vector<uint64_t> keys(N0);
+    if (p->pfa != 0.0) { tab.assign((size_t)N0 + 1, 0.0); rts_cfar_os_alpha_table(p->guard_range, p->guard_doppler, p->train_range, p->train_doppler, p->rank, p->pfa, q->n_bins, tab.data()); }
+    const uint32_t total = rts_cfar_os_eval_host(q, map, n_doppler, p, tab.empty() ? nullptr : tab.data(), keys.data(), out, capacity);
+    *n_out = total;
+    if (total > capacity) { rts_set_error("rts_cfar_os_eval: %u of %u detections written (capacity %u)", capacity, total, capacity); return RTS_ERR_CAPACITY; }
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_detect_os(RtsHandle c, const RtsCfarOsParams* p, const void* device_map, uint32_t n_doppler)
+{
+    CHECK_HANDLE(c);
+    if (!p) { rts_set_error("rts_cube_detect_os: null parameters"); return RTS_ERR_INVALID; }
+    CHECK_CLOSED(c);
+    NEED_CUBE(c, "rts_cube_detect_os", "no cube (call rts_cube_attach first)");
+    const double* map = (const double*)device_map;
+    if (map) {
+        if (n_doppler == 0) { rts_set_error("rts_cube_detect_os: n_doppler = 0 with a caller map"); return RTS_ERR_INVALID; }
+        if ((uintptr_t)map & 15u) { rts_set_error("rts_cube_detect_os: device_map is not 16-byte aligned"); return RTS_ERR_INVALID; }
+    } else {
+        if (!c->cube.doppler.valid) { rts_set_error("rts_cube_detect_os: no map (call rts_cube_doppler first, or pass device_map)"); return RTS_ERR_INVALID; }
+        map = c->cube.doppler.p; n_doppler = c->cube.doppler_n;
+    }
+    const uint32_t nb = c->cube.params.n_bins;
+    { int rc = rts_cfar_os_check(p, nb, n_doppler, "rts_cube_detect_os"); if (rc != RTS_OK) return rc; }
+    c->cube.det_valid = false;
+    // the alphas by training count -> pinned staging -> the device, on the stream (N0 + 1 <= RTS_CFAR_OS_MAX_TRAIN + 1: one size for every call);
+    // a call that needs nothing the device table of the previous one lacks sends nothing
+    const double* tab_dev = nullptr;
+    if (p->pfa != 0.0) {
+        RtsCubeState& s = c->cube;
+        const uint32_t N0 = rts_cfar_os_n0(p->guard_range, p->guard_doppler, p->train_range, p->train_doppler);
+        const uint32_t key[5] = {p->guard_range, p->guard_doppler, p->train_range, p->train_doppler, p->rank};
+        if (s.os_tab.size() != (size_t)N0 + 1 || memcmp(key, s.os_tab_key, sizeof(key)) != 0 || s.os_tab_pfa != p->pfa) {
+            s.os_tab.assign((size_t)N0 + 1, 0.0); memcpy(s.os_tab_key, key, sizeof(key)); s.os_tab_pfa = p->pfa; s.os_tab_sent = false;
+        }
+        if (rts_cfar_os_alpha_table(p->guard_range, p->guard_doppler, p->train_range, p->train_doppler, p->rank, p->pfa, nb, s.os_tab.data()) != 0) s.os_tab_sent = false;
+        if (!s.os_tab_sent) {
+            double* h = nullptr;
+            RTS_HIP(s.os_alpha.begin(RTS_CFAR_OS_MAX_TRAIN + 1u, RTS_CFAR_OS_MAX_TRAIN + 1u, RTS_CFAR_OS_MAX_TRAIN + 1u, &h));
+            memcpy(h, s.os_tab.data(), sizeof(double) * ((size_t)N0 + 1));
+            RTS_HIP(s.os_alpha.send((size_t)N0 + 1, c->stream));
+            s.os_tab_sent = true;
+        }
+        tab_dev = s.os_alpha.dev.p;
+    }
+    return rts_cube_detect_os_device(c, *p, tab_dev, map, n_doppler, p->max_detections ? p->max_detections : RTS_CFAR_DEFAULT_MAX_DETECTIONS);
 }
 
 // ------------------------------------------------------------------------------------- tapered slow-time spectrogram

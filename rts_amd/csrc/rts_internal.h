@@ -13,6 +13,7 @@
 #include "rts_noise.h"
 #include "rts_image.h"            // the arithmetic of a backprojected pixel and the host-only plan of its launch
 #include "rts_stft.h"             // the tree of the slow-time spectrogram and the host-only plan of its launch
+#include "rts_cfar_os.h"          // ordered-statistic CFAR: window size, training count, rank rule, alphas, the host evaluator
 #include "rts_owned.h"            // DevBuf, PinBuf, StagedUpload: device and pinned host memory that frees itself
 #include "rts_launch_plan.h"      // RTS_BLOCK, RTS_WTILE, RTS_COOP_GROUP, RTS_STACK_OVF and the host arithmetic of a launch
 #include "rts_post_plan.h"        // RTS_SMALL_CAP32 / 64, RTS_AGG_TILE and the host arithmetic of the post-processing
@@ -81,7 +82,7 @@ struct __attribute__((aligned(16))) RtsEndRecord {
     uint32_t pad;
 };
 static_assert(sizeof(RtsEndRecord) == 112, "end record size");
-static_assert(sizeof(RtsDetection) == 72 && sizeof(RtsCfarParams) == 72, "CFAR ABI sizes (rts_amd/_lib.py mirrors them)");
+static_assert(sizeof(RtsDetection) == 72 && sizeof(RtsCfarParams) == 72 && sizeof(RtsCfarOsParams) == 72, "CFAR ABI sizes (rts_amd/_lib.py mirrors them)");
 // RtsEndRecord::pad : bits 0-1 chain (output row = chain * n + slot), 2-3 refrDepth, 8-15 (target + 1) of chain 0's
 // refraction (path prefill of rows >= 3), 16-17 children spawned
 
@@ -313,6 +314,10 @@ struct RtsCubeState {
     // CFAR detection (rts_cube_detect, rts_detect.hip): per-segment counts -> exclusive scan (offsets; element n_seg: the total),
     // the records of the last detection and how many it may hold; det_valid: a list exists for rts_cube_detections_get
     DevBuf<uint32_t> d_det_cnt, d_det_off; DevBuf<uint8_t> d_det_tmp; DevBuf<RtsDetection> d_det; uint32_t det_nseg = 0, det_max = 0; bool det_valid = false;
+    // OS-CFAR (rts_cube_detect_os): the alphas by training count go through a staged upload; os_tab keeps them on the host for the next
+    // call with the same window, rank and pfa (os_tab_key), so that only training counts not seen yet are solved for; os_tab_sent: the
+    // device holds os_tab as it stands
+    StagedUpload<double> os_alpha; std::vector<double> os_tab; uint32_t os_tab_key[5] = {0, 0, 0, 0, 0}; double os_tab_pfa = 0.0; bool os_tab_sent = false;
     // backprojection (rts_cube_backproject, rts_image.hip): the image and its shape, for rts_cube_image_get / RTS_IMAGE_ACCUMULATE; the
     // call's geometry [tx | rx | w] goes through a staged upload; the chunk sums of a split launch
     RtsCubeProduct image; uint32_t img_nx = 0, img_ny = 0;
@@ -469,6 +474,7 @@ int rts_cube_render_device(RtsContext* c, uint32_t pulse_index, bool paths, bool
 int rts_cube_compress_device(RtsContext* c, uint32_t first_pulse, uint32_t n_pulses);
 int rts_cube_noise_device(RtsContext* c, uint32_t first_pulse, uint32_t n_pulses, double sigma, uint64_t seed);          // rts_detect.hip
 int rts_cube_detect_device(RtsContext* c, const RtsCfarParams& p, const double* map, uint32_t n_doppler, uint32_t max_det);
+int rts_cube_detect_os_device(RtsContext* c, const RtsCfarOsParams& p, const double* alpha_tab, const double* map, uint32_t n_doppler, uint32_t max_det);      // alpha_tab: device, by training count (pfa), or null (p.alpha)
 int rts_cube_stft_device(RtsContext* c, const RtsStftParams& p, const RtsStftPlan& plan, const double* window, double* out);      // rts_stft.hip
 int rts_cube_backproject_device(RtsContext* c, const RtsImageParams& p, const RtsImagePlan& plan, const double* geo, double* out);      // rts_image.hip
 int rts_post_finalise(RtsContext* c, const double* rcs_host, double wl, double gt, double gr, double carrier, double cspeed);
