@@ -659,6 +659,100 @@ int rts_stft_eval(const RtsCubeParams* q, const double* cube, const RtsStftParam
 #define RTS_WINDOW_BLACKMAN 3u
 int rts_window_make(uint32_t kind, uint32_t n, double* out);   /* pure host */
 
+/* ---------------------------------------------------------------- FMCW / stretch processing: dechirped beat render, fast-time range transform
+ * The second class of radar: FMCW sets (automotive, altimeters, short-range surveillance) and pulsed LFM sets with stretch processing
+ * never see the waveform at baseband.  They mix the echo with the running transmit chirp, sample the low-bandwidth BEAT signal and
+ * take range from a fast-time FFT.  rts_cube_render_beat writes that beat signal into a row of the cube, rts_cube_range_transform
+ * transforms rows along the range axis; everything downstream (noise, rts_cube_doppler, the CFARs, the spectrogram) then works
+ * unchanged on the transformed cube.  The arithmetic is rts_amd/csrc/rts_beat.h (the transform's: rts_stft.h), shared by the kernels
+ * (rts_beat.hip) and the host evaluators (the library builds with -ffp-contract=off: the tree is the contract).
+ *
+ * Beat render.  The contributions are exactly those of rts_cube_render for the chosen source: receiver rx_k, amplitude
+ * a_k = sqrt(P_k) e^{j phi_k} (RTS_RENDER_RAYS: phi = -fmod(2 pi carrier tau, 2 pi); RTS_RENDER_PATHS: the group's phase), delay
+ * tau_k, Doppler f_k (0 without RTS_RENDER_DOPPLER).  The call has rts_cube_render's place in the call sequence and its
+ * preconditions, except that no waveform is needed.  With t_n = t0 + n dt (the cube's t0, dt; t = 0 is the start of the chirp) the
+ * transmit baseband chirp is e^{j 2 pi S t^2 / 2}; the mixer forms rx conj(tx), so the cube's phase convention -2 pi fc tau and the
+ * Doppler sign of rts_cube_doppler / rts_cube_detect carry over:
+ *     y[rx_k][pulse][n] += a_k e^{j 2 pi psi_k(n)},   psi_k(n) = (f_k - S tau_k) t_n + S tau_k^2 / 2 - f_k tau_k     (turns)
+ *         for the samples with tau_k <= t_n and 0 <= t_n < T;  nothing for a non-finite tau_k.
+ * The beat frequency is f_k - S tau_k.  The caller keeps |S tau| dt < 1/2; aliasing is physics and is not refused.
+ *   The tree: the row is cut into strips of RTS_BEAT_STRIP samples starting at multiples of it.  Per contribution, once:
+ *       st = S tau;  fb = f - st;  ph0 = (st tau) 0.5 - f tau;  delta = fb dt;  (sd, cd) = sincospi(2 (delta - floor(delta))).
+ *     Per contribution and strip whose last sample in the row has tau <= t (a later strip is skipped whole), with n0 its first sample:
+ *       psi = fb t_n0 + ph0;  (s, c) = sincospi(2 (psi - floor(psi)));
+ *       for i = 0 .. RTS_BEAT_STRIP - 1:  term = (are c - aim s, are s + aim c), added to the sample's sum only if sample n0 + i is in
+ *       the row and passes the gate (tau <= t, t >= 0, t < T, t = t0 + (double)(n0 + i) dt);  then (c, s) <- (c cd - s sd, s cd + c sd).
+ *     One sincospi per 16 samples instead of one per sample; the rotation's drift over 16 steps is a few ulp.
+ *   Summation: a sample's sum starts at zero and takes the contributions in the received set's order; a sum that is not zero
+ *     reaches the cube with ONE atomic add per component, so handles sharing a cube stay safe.  A large received set is cut into
+ *     P <= RTS_BEAT_MAX_PARTS parts of consecutive records, each summed by workgroups of its own into a scratch buffer of the handle
+ *     (16 P n_rx n_bins bytes at most); a second kernel adds the parts in ascending order, the first the start value, and does the
+ *     atomic add.  P comes from a pure-host plan (rts_beat.h: rts_beat_plan) of the set's size and the cube's shape only, so a render
+ *     into a zeroed row is bit-identical from run to run.  P is not part of the ABI; renders that differ in P differ in the last bits.
+ *     (RTS_BEAT_PARTS = n in the environment of rts_create forces P = n as far as the set has records: the tests' switch.)
+ *   The call is enqueued on the handle's stream and never waits on the host.
+ *   RTS_ERR_INVALID, the message naming the field: no cube attached; NULL p; slope 0 or not finite; duration <= 0 or not finite; an
+ *   unknown source or flags; nonzero reserved fields; pulse_index beyond the cube's rows; RTS_RENDER_RAYS with a cspeed that is not
+ *   finite and > 0 or a carrier that is not finite and >= 0; RTS_RENDER_PATHS without rts_aggregate of the pulse; more than 65 535
+ *   receivers (the launch grid).
+ * rts_beat_eval: pure host, no device.  The same rts_beat.h functions on n contributions given as records (rx outside [0, n_rx) or
+ * a non-finite delay: skipped), summed in order from zero and added to row pulse_index of a host cube
+ * [n_rx][q->n_pulses][q->n_bins] (interleaved re / im) -- the kernel's order with P = 1.  The same validation of q and p (source is
+ * checked and otherwise unused); a refused call leaves the cube untouched.
+ *
+ * Range transform.  Per row (rx, first_pulse + j), j < n_pulses, of the attached cube:
+ *     x[i] = w[i] * y[first_bin + i]  for i < n_samples, computed as (w re, w im);   x[i] = 0  for n_samples <= i < n_fft;
+ *     with window == NULL the samples are taken as they are, with no multiply at all;
+ *     X = the transform of rts_stft.h as it stands (RtsStftParams above: bit-reversed load, radix-2 decimation-in-time stages,
+ *     twiddles from one sincospi(-2 m / n_fft) each), X[k] = sum_i x[i] e^{-2 pi j k i / n_fft};
+ *     out[rx][j][k] = X[k], or X[(n_fft - k) mod n_fft] with RTS_RANGE_REVERSE (the e^{+2 pi j k i / n_fft} transform), for k < n_out.
+ *   Axis: an up-chirp (S > 0) has beat frequency -S tau and is transformed with RTS_RANGE_REVERSE, a down-chirp without it; bin k is
+ *     then delay k / (|S| n_fft dt).  A caller attaches the output as a cube (rts_cube_attach with device_ptr, t0 = 0,
+ *     dt = 1 / (|S| n_fft dt), n_bins = n_out) and runs rts_cube_doppler / rts_cube_detect* / rts_cube_spectrogram on it unchanged.
+ *     Range-Doppler coupling: a Doppler f moves the apparent delay by -f / S.  It is inherent to the waveform and is not corrected.
+ *   Output: complex128 [n_rx][n_pulses][n_out].  device_out: caller-owned device memory of that size, 16-byte aligned, or NULL:
+ *     library-owned, alive until the next range transform of another size, rts_cube_attach or rts_destroy.  rts_cube_range_get
+ *     synchronises and copies the library-owned output; RTS_ERR_INVALID after an rts_cube_attach or with no library-owned output,
+ *     RTS_ERR_CAPACITY when capacity_doubles is too small.  The call is enqueued on the handle's stream and never waits for the
+ *     device's earlier work (only for the copy of the PREVIOUS call's window out of the handle's pinned staging block); the
+ *     caller's window array is free on return.
+ *   RTS_ERR_INVALID, the message naming the field: no cube attached; NULL p; nonzero reserved fields; unknown flags; n_fft not a power
+ *   of two in [2, RTS_RANGE_MAX_FFT]; first_bin >= the cube's n_bins or first_bin + n_samples beyond it; n_samples (after the default)
+ *   > n_fft; n_out > n_fft; n_pulses 0 or first_pulse + n_pulses beyond the cube's rows; a non-finite window value; a device_out that
+ *   is not 16-byte aligned; more than 2^31 - 1 workgroups (ceil(n_rx n_pulses / RT) with RT = min(16, 4096 / n_fft) rows each).
+ * rts_range_eval: pure host, no device.  The same validation (q in place of the attached cube) and the same rts_stft.h functions on
+ * a host cube [n_rx][q->n_pulses][q->n_bins] (interleaved re / im) -> out [n_rx][n_pulses][n_out].  A refused call leaves out untouched. */
+#define RTS_BEAT_STRIP     16u     /* samples advanced by rotation from one sincospi (the summation tree, above) */
+#define RTS_BEAT_MAX_PARTS 64u     /* most parts the received set is cut into (bounds the scratch)               */
+typedef struct RtsBeatParams {
+    double slope;            /* S, Hz/s: finite, != 0 (sign = up / down chirp)                      */
+    double duration;         /* T, s: the local oscillator runs on 0 <= t < T; finite, > 0         */
+    uint32_t source;         /* RTS_RENDER_RAYS / RTS_RENDER_PATHS (the contributions of rts_cube_render) */
+    uint32_t flags;          /* 0 or RTS_RENDER_DOPPLER                                             */
+    uint64_t reserved[2];    /* 0 */
+} RtsBeatParams;
+int rts_cube_render_beat(RtsHandle h, uint32_t pulse_index, const RtsBeatParams* p, double cspeed, double carrier);
+
+typedef struct RtsBeatContribution { int32_t rx, reserved; double re, im, delay, doppler; } RtsBeatContribution;
+/* pure host: adds the contributions into row pulse_index of a host cube [n_rx][q->n_pulses][q->n_bins] */
+int rts_beat_eval(const RtsCubeParams* q, const RtsBeatParams* p, const RtsBeatContribution* c, uint32_t n,
+                  uint32_t pulse_index, double* cube);
+
+#define RTS_RANGE_REVERSE  1u      /* out[k] = X[(n_fft - k) mod n_fft]: the e^{+2 pi j k n / N} transform */
+#define RTS_RANGE_MAX_FFT  4096u
+typedef struct RtsRangeParams {
+    uint32_t first_pulse, n_pulses;   /* cube rows first_pulse .. first_pulse + n_pulses - 1          */
+    uint32_t first_bin, n_samples;    /* fast-time samples first_bin .. first_bin + n_samples - 1; n_samples 0: to the row's end */
+    uint32_t n_fft;                   /* power of two in [2, RTS_RANGE_MAX_FFT], >= n_samples         */
+    uint32_t n_out;                   /* bins kept, 1 .. n_fft; 0: n_fft                              */
+    uint32_t flags, reserved0;
+    const double* window;             /* [n_samples] host, finite; NULL: no multiply at all          */
+    uint64_t reserved[2];
+} RtsRangeParams;
+int rts_cube_range_transform(RtsHandle h, const RtsRangeParams* p, void* device_out);  /* complex128 [n_rx][n_pulses][n_out] */
+int rts_cube_range_get(RtsHandle h, double* host_out, uint64_t capacity_doubles);
+int rts_range_eval(const RtsCubeParams* q, const double* cube, const RtsRangeParams* p, double* out);  /* pure host */
+
 /* ---------------------------------------------------------------- backprojection imaging (SAR / ISAR) of the return cube
  * A derived product like the cube itself: time-domain backprojection of a coherent interval onto a planar
  * pixel grid -- exact for any track, any bistatic geometry and any target motion, where the slow-time DFT focuses only while a

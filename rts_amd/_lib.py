@@ -157,6 +157,27 @@ class RtsStftParams(C.Structure):
 assert C.sizeof(RtsStftParams) == 56
 
 
+RTS_BEAT_STRIP, RTS_BEAT_MAX_PARTS = 16, 64
+RTS_RANGE_REVERSE, RTS_RANGE_MAX_FFT = 1, 4096
+
+
+class RtsBeatParams(C.Structure):
+    _fields_ = [("slope", C.c_double), ("duration", C.c_double), ("source", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint64 * 2)]
+
+
+# RtsBeatContribution (include/rts_amd.h), 40 bytes
+BEAT_CONTRIBUTION_DTYPE = np.dtype([("rx", "<i4"), ("reserved", "<i4"), ("re", "<f8"), ("im", "<f8"), ("delay", "<f8"), ("doppler", "<f8")])
+
+
+class RtsRangeParams(C.Structure):
+    _fields_ = [("first_pulse", C.c_uint32), ("n_pulses", C.c_uint32), ("first_bin", C.c_uint32), ("n_samples", C.c_uint32),
+                ("n_fft", C.c_uint32), ("n_out", C.c_uint32), ("flags", C.c_uint32), ("reserved0", C.c_uint32),
+                ("window", C.c_void_p), ("reserved", C.c_uint64 * 2)]
+
+
+assert C.sizeof(RtsBeatParams) == 40 and BEAT_CONTRIBUTION_DTYPE.itemsize == 40 and C.sizeof(RtsRangeParams) == 56
+
+
 class RtsSceneInfo(C.Structure):
     _fields_ = [("n_targets", C.c_uint32), ("n_prims", C.c_uint32), ("n_nodes", C.c_uint32), ("n_leaves", C.c_uint32),
                 ("handles_sharing", C.c_uint32), ("builder", C.c_uint32), ("build_ms", C.c_double),
@@ -245,7 +266,8 @@ EXPORTS = ["rts_create", "rts_destroy", "rts_last_error", "rts_device_count", "r
            "rts_cube_add_noise", "rts_noise_eval", "rts_cube_detect", "rts_cube_detections_get",
            "rts_cube_detect_os", "rts_cfar_os_alpha", "rts_cfar_os_eval",
            "rts_cube_backproject", "rts_cube_image_get", "rts_backproject_eval",
-           "rts_cube_spectrogram", "rts_cube_spectrogram_get", "rts_stft_eval", "rts_window_make"]
+           "rts_cube_spectrogram", "rts_cube_spectrogram_get", "rts_stft_eval", "rts_window_make",
+           "rts_cube_render_beat", "rts_beat_eval", "rts_cube_range_transform", "rts_cube_range_get", "rts_range_eval"]
 
 
 def lib():
@@ -328,6 +350,11 @@ def lib():
         "rts_cube_spectrogram_get": [vp, vp, u64],
         "rts_stft_eval": [C.POINTER(RtsCubeParams), vp, C.POINTER(RtsStftParams), vp, C.POINTER(u32)],
         "rts_window_make": [u32, u32, vp],
+        "rts_cube_render_beat": [vp, u32, C.POINTER(RtsBeatParams), C.c_double, C.c_double],
+        "rts_beat_eval": [C.POINTER(RtsCubeParams), C.POINTER(RtsBeatParams), vp, u32, u32, vp],
+        "rts_cube_range_transform": [vp, C.POINTER(RtsRangeParams), vp],
+        "rts_cube_range_get": [vp, vp, u64],
+        "rts_range_eval": [C.POINTER(RtsCubeParams), vp, C.POINTER(RtsRangeParams), vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name, None)

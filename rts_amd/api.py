@@ -366,6 +366,69 @@ def spectrogram_axes(window_len, hop, n_fft, n_pulses, pri, first=0):
     return centres, k / (n_fft * float(pri))
 
 
+# ------------------------------------------------------------------------------- FMCW: beat render, range transform (rts_beat.h)
+_RENDER_SOURCES = {"rays": L.RTS_RENDER_RAYS, "paths": L.RTS_RENDER_PATHS}
+
+
+def _beat_params(slope, duration, source, doppler):
+    p = L.RtsBeatParams()
+    p.slope, p.duration = float(slope), float(duration)
+    p.source, p.flags = _RENDER_SOURCES.get(source, source), L.RTS_RENDER_DOPPLER if doppler else 0
+    return p
+
+
+def beat_eval(cube, pulse, contributions, slope, duration, t0, dt, source="rays", doppler=True):
+    """rts_beat_eval (pure host): the dechirped beat signal of the contributions -- (rx, complex amplitude, delay, Doppler) tuples, or a
+    BEAT_CONTRIBUTION_DTYPE array -- added into row `pulse` of the host cube [n_rx][n_pulses][n_bins] (complex128, in place when it
+    is a contiguous complex128 array); returns the cube"""
+    cube = np.ascontiguousarray(np.asarray(cube, np.complex128))
+    n_rx, n_p, nb = cube.shape
+    if isinstance(contributions, np.ndarray) and contributions.dtype == L.BEAT_CONTRIBUTION_DTYPE:
+        c = np.ascontiguousarray(contributions)
+    else:
+        c = np.zeros(len(contributions), L.BEAT_CONTRIBUTION_DTYPE)
+        for k, (rx, a, tau, f) in enumerate(contributions):
+            c[k] = (rx, 0, complex(a).real, complex(a).imag, tau, f)
+    q = L.RtsCubeParams(n_rx, n_p, nb, 0, float(t0), float(dt))
+    p = _beat_params(slope, duration, source, doppler)
+    check(L.lib().rts_beat_eval(C.byref(q), C.byref(p), ptr(c) if len(c) else None, len(c), int(pulse), ptr(cube.view(np.float64))))
+    return cube
+
+
+def _range_params(n_fft, window, first, count, first_bin, n_samples, n_out, reverse, n_pulses_cube, n_bins_cube):
+    """RtsRangeParams and the window array it points to (keep it alive for the call); count None: to the cube's last row"""
+    w = None if window is None else np.ascontiguousarray(np.asarray(window, np.float64).ravel())
+    want = int(n_samples) if n_samples else max(n_bins_cube - int(first_bin), 0)
+    if w is not None and len(w) != want:
+        raise ValueError("range transform: a window of %d values for %d samples" % (len(w), want))
+    p = L.RtsRangeParams()
+    p.first_pulse, p.n_pulses = int(first), int(n_pulses_cube - first if count is None else count)
+    p.first_bin, p.n_samples, p.n_fft, p.n_out = int(first_bin), int(n_samples), int(n_fft), int(n_out)
+    p.flags = L.RTS_RANGE_REVERSE if reverse else 0
+    p.window = ptr(w)
+    return p, w
+
+
+def range_eval(cube, n_fft, window=None, first=0, count=None, first_bin=0, n_samples=0, n_out=0, reverse=False):
+    """rts_range_eval (pure host): the fast-time transform of rows first .. first + count - 1 of a host cube
+    [n_rx][n_pulses][n_bins] (complex): complex [n_rx][count][n_out or n_fft]"""
+    cube = np.ascontiguousarray(np.asarray(cube, np.complex128))
+    n_rx, n_p, nb = cube.shape
+    q = L.RtsCubeParams(n_rx, n_p, nb, 0, 0.0, 1.0)
+    p, keep = _range_params(n_fft, window, first, count, first_bin, n_samples, n_out, reverse, n_p, nb)
+    out = np.zeros((n_rx, max(p.n_pulses, 0), p.n_out if p.n_out else p.n_fft), np.complex128)
+    check(L.lib().rts_range_eval(C.byref(q), ptr(cube.view(np.float64)), C.byref(p), ptr(out.view(np.float64))))
+    return out
+
+
+def beat_axis(slope, n_fft, dt, n_out=0):
+    """the range axis of a transformed beat cube: (delay of each kept bin in s, float64 [n_out or n_fft], bin k at
+    k / (|slope| n_fft dt); the `reverse` flag the transform needs: True for an up-chirp, whose beat frequency -S tau is negative).
+    The step delays[1] is the dt to attach the output with (t0 = 0)."""
+    n = int(n_out) if n_out else int(n_fft)
+    return np.arange(n, dtype=np.float64) / (abs(float(slope)) * int(n_fft) * float(dt)), slope > 0
+
+
 def device_count():
     n = C.c_int(0)
     rc = L.lib().rts_device_count(C.byref(n))
@@ -661,6 +724,36 @@ class Tracer:
             raise ValueError("cube_render(source='rays') needs cspeed and carrier")
         check(L.lib().rts_cube_render(self.h, pulse, src, L.RTS_RENDER_DOPPLER if doppler else 0,
                                       0.0 if cspeed is None else cspeed, 0.0 if carrier is None else carrier))
+
+    def cube_render_beat(self, pulse, slope, duration, source="rays", cspeed=None, carrier=None, doppler=True):
+        """rts_cube_render_beat: the last pulse's contributions as the dechirped beat signal of a chirp of `slope` Hz/s running for
+        `duration` s, added into row `pulse` of every receiver; source "rays" (needs cspeed and carrier) or "paths" (one per group of
+        rts_aggregate).  No waveform is needed."""
+        p = _beat_params(slope, duration, source, doppler)
+        if p.source == L.RTS_RENDER_RAYS and (cspeed is None or carrier is None):
+            raise ValueError("cube_render_beat(source='rays') needs cspeed and carrier")
+        check(L.lib().rts_cube_render_beat(self.h, pulse, C.byref(p), 0.0 if cspeed is None else cspeed, 0.0 if carrier is None else carrier))
+
+    def cube_range_transform(self, n_fft, window=None, first=0, count=None, first_bin=0, n_samples=0, n_out=0, reverse=False, device_ptr=None,
+                             fetch=True):
+        """rts_cube_range_transform: the n_fft-point transform along the range axis of the attached cube's rows first .. first + count - 1
+        (default: to the last), of the samples first_bin .. first_bin + n_samples - 1 (n_samples 0: to the row's end) tapered by window
+        (an array of that many values, or None) and zero-padded; n_out bins kept (0: all), index-reversed with reverse (an up-chirp:
+        beat_axis).  Into a caller complex128 device tensor [n_rx][count][n_out] (device_ptr; nothing is fetched) or the library's
+        output, returned when fetch"""
+        n_rx, n_p, nb = self._cube_shape
+        p, keep = _range_params(n_fft, window, first, count, first_bin, n_samples, n_out, reverse, n_p, nb)
+        check(L.lib().rts_cube_range_transform(self.h, C.byref(p), C.c_void_p(device_ptr) if device_ptr else None))
+        if device_ptr:
+            return None
+        self._range_shape = (n_rx, p.n_pulses, p.n_out if p.n_out else p.n_fft)
+        return self.range_map() if fetch else None
+
+    def range_map(self):
+        """rts_cube_range_get: the library-owned output of the last cube_range_transform, complex [n_rx][count][n_out]"""
+        out = np.zeros(getattr(self, "_range_shape", None) or (1, 1, 1), np.complex128)
+        check(L.lib().rts_cube_range_get(self.h, ptr(out.view(np.float64)), 2 * out.size))
+        return out
 
     def cube_compress(self, first=0, count=None):
         """rts_cube_compress: matched filter of rows first .. first + count - 1 (default: to the last pulse), in place"""

@@ -240,6 +240,7 @@ extern "C" int rts_create(const RtsParams* p, RtsHandle* out)
     { const char* e = getenv("RTS_POST_SMALL"); if (e) c->post_small = atoi(e) != 0; }
     { const char* e = getenv("RTS_POST_ONE_MAX"); if (e) c->post_one_max = (uint64_t)strtoull(e, nullptr, 10); }
     { const char* e = getenv("RTS_IMAGE_SPLIT_BELOW"); if (e) c->cube.img_split_below = (uint32_t)std::min(65536, std::max(0, atoi(e))); }
+    { const char* e = getenv("RTS_BEAT_PARTS"); if (e) c->cube.beat_force_parts = (uint32_t)std::min((int)RTS_BEAT_MAX_PARTS, std::max(0, atoi(e))); }      // tests: the parts of a beat render (0: the plan's own)
     { const char* e = getenv("RTS_POST_PRIO"); if (e) c->post_prio = (uint32_t)std::min(3, std::max(0, atoi(e))); }
     { const char* e = getenv("RTS_COOP_STEPS"); if (e) c->coop_walk_steps = (uint32_t)std::max(0, atoi(e)); }
     { const char* e = getenv("RTS_COOP_STEPS_LO"); if (e) c->coop_walk_steps_lo = (uint32_t)std::max(0, atoi(e)); }

@@ -391,6 +391,104 @@ extern "C" int rts_cube_spectrogram_get(RtsHandle c, double* host_out, uint64_t 
     return rts_cube_copy_out(c, "rts_cube_spectrogram_get", "no library-owned spectrogram (rts_cube_spectrogram with device_out NULL; a spectrogram ends at rts_cube_attach) / null output", c->cube.stft.valid, c->cube.stft.p, c->cube.stft.doubles, host_out, capacity_doubles);
 }
 
+// ------------------------------------------------------------------------------------- FMCW: dechirped beat render, fast-time range transform
+// (rts_amd.h: RtsBeatParams, RtsRangeParams; the trees and the launch plans are rts_beat.h / rts_stft.h, shared by the host exports and the kernels, rts_beat.hip)
+static int rts_beat_check(const RtsBeatParams* p, const RtsCubeParams& q, uint32_t pulse_index, const char* who)
+{
+    if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
+    if (!std::isfinite(p->slope) || p->slope == 0.0) { rts_set_error("%s: slope = %g (finite, != 0)", who, p->slope); return RTS_ERR_INVALID; }
+    if (!std::isfinite(p->duration) || !(p->duration > 0.0)) { rts_set_error("%s: duration = %g (finite, > 0)", who, p->duration); return RTS_ERR_INVALID; }
+    if (p->source != RTS_RENDER_RAYS && p->source != RTS_RENDER_PATHS) { rts_set_error("%s: unknown source %u (RTS_RENDER_RAYS, RTS_RENDER_PATHS)", who, p->source); return RTS_ERR_INVALID; }
+    if (p->flags & ~RTS_RENDER_DOPPLER) { rts_set_error("%s: unknown flags 0x%x", who, p->flags); return RTS_ERR_INVALID; }
+    if (p->reserved[0] || p->reserved[1]) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
+    if (pulse_index >= q.n_pulses) { rts_set_error("%s: pulse_index = %u >= the cube's %u rows", who, pulse_index, q.n_pulses); return RTS_ERR_INVALID; }
+    if (q.n_rx > RTS_BEAT_MAX_RX) { rts_set_error("%s: n_rx = %u receivers: more than %u (the launch grid)", who, q.n_rx, RTS_BEAT_MAX_RX); return RTS_ERR_INVALID; }
+    return RTS_OK;
+}
+
+extern "C" int rts_beat_eval(const RtsCubeParams* q, const RtsBeatParams* p, const RtsBeatContribution* c, uint32_t n, uint32_t pulse_index, double* cube)
+{
+    if (!q || q->n_rx == 0 || q->n_pulses == 0 || q->n_bins == 0 || !(q->dt > 0) || !std::isfinite(q->dt) || !std::isfinite(q->t0)) { rts_set_error("rts_beat_eval: bad cube parameters"); return RTS_ERR_INVALID; }
+    int rc = rts_beat_check(p, *q, pulse_index, "rts_beat_eval"); if (rc != RTS_OK) return rc;
+    if ((n && !c) || !cube) { rts_set_error("rts_beat_eval: null contribution array or cube"); return RTS_ERR_INVALID; }
+    std::vector<double> work(2 * (size_t)q->n_rx * q->n_bins);
+    rts_beat_eval_host(q, p, c, n, pulse_index, cube, work.data());
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_render_beat(RtsHandle c, uint32_t pulse_index, const RtsBeatParams* p, double cspeed, double carrier)
+{
+    CHECK_HANDLE(c);
+    NEED_CUBE(c, "rts_cube_render_beat", "call rts_cube_attach first");
+    { int rc = rts_beat_check(p, c->cube.params, pulse_index, "rts_cube_render_beat"); if (rc != RTS_OK) return rc; }
+    const bool paths = p->source == RTS_RENDER_PATHS;
+    if (!paths && (!std::isfinite(cspeed) || !(cspeed > 0.0))) { rts_set_error("rts_cube_render_beat: cspeed = %g (finite, > 0, with RTS_RENDER_RAYS)", cspeed); return RTS_ERR_INVALID; }
+    if (!paths && (!std::isfinite(carrier) || carrier < 0.0)) { rts_set_error("rts_cube_render_beat: carrier = %g (finite, >= 0, with RTS_RENDER_RAYS)", carrier); return RTS_ERR_INVALID; }
+    CHECK_CLOSED(c);
+    if (paths && !c->res.agg_valid) { rts_set_error("rts_cube_render_beat: RTS_RENDER_PATHS needs rts_aggregate of this pulse first (the groups' power, delay and phase are its results)"); return RTS_ERR_INVALID; }
+    const RtsBeatPlan plan = rts_beat_plan(c->res.n_recv, c->cube.params.n_rx, c->cube.params.n_bins, c->cube.beat_force_parts);
+    if (!plan.supported) { rts_set_error("rts_cube_render_beat: %llu received rays: more than the launch takes", (unsigned long long)c->res.n_recv); return RTS_ERR_INVALID; }
+    return rts_cube_beat_device(c, pulse_index, *p, plan, cspeed, carrier, c->res.agg_base_local);
+}
+
+static int rts_range_check(const RtsRangeParams* p, const RtsCubeParams& q, const char* who, RtsRangePlan* plan)
+{
+    if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
+    if (p->reserved0 || p->reserved[0] || p->reserved[1]) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
+    if (p->flags & ~RTS_RANGE_REVERSE) { rts_set_error("%s: unknown flags 0x%x", who, p->flags); return RTS_ERR_INVALID; }
+    if (p->n_fft < 2u || p->n_fft > RTS_RANGE_MAX_FFT || (p->n_fft & (p->n_fft - 1u)) != 0u) { rts_set_error("%s: n_fft = %u must be a power of two in [2, %u]", who, p->n_fft, RTS_RANGE_MAX_FFT); return RTS_ERR_INVALID; }
+    { int rc = rts_pulses_check(who, p->first_pulse, p->n_pulses, q.n_pulses, true); if (rc != RTS_OK) return rc; }
+    if (p->first_bin >= q.n_bins || p->n_samples > q.n_bins - p->first_bin) { rts_set_error("%s: first_bin = %u, n_samples = %u: inside the row's %u bins", who, p->first_bin, p->n_samples, q.n_bins); return RTS_ERR_INVALID; }
+    const uint32_t n_samples = p->n_samples ? p->n_samples : q.n_bins - p->first_bin;
+    if (n_samples > p->n_fft) { rts_set_error("%s: n_samples = %u > n_fft = %u", who, n_samples, p->n_fft); return RTS_ERR_INVALID; }
+    if (p->n_out > p->n_fft) { rts_set_error("%s: n_out = %u > n_fft = %u", who, p->n_out, p->n_fft); return RTS_ERR_INVALID; }
+    if (p->window) for (uint32_t i = 0; i < n_samples; i++) if (!std::isfinite(p->window[i])) { rts_set_error("%s: window[%u] is not finite", who, i); return RTS_ERR_INVALID; }
+    *plan = rts_range_plan(q.n_rx, p->n_pulses, n_samples, p->n_fft, p->n_out);
+    if (!plan->supported) { rts_set_error("%s: n_rx = %u receivers x n_pulses = %u rows, %u per workgroup: more than %u workgroups (the launch grid)", who, q.n_rx, p->n_pulses, plan->RT, RTS_RANGE_MAX_GRID_X); return RTS_ERR_INVALID; }
+    return RTS_OK;
+}
+
+extern "C" int rts_range_eval(const RtsCubeParams* q, const double* cube, const RtsRangeParams* p, double* out)
+{
+    if (!q || q->n_rx == 0 || q->n_pulses == 0 || q->n_bins == 0) { rts_set_error("rts_range_eval: bad cube parameters"); return RTS_ERR_INVALID; }
+    RtsRangePlan plan;
+    int rc = rts_range_check(p, *q, "rts_range_eval", &plan); if (rc != RTS_OK) return rc;
+    if (!cube || !out) { rts_set_error("rts_range_eval: null cube or output array"); return RTS_ERR_INVALID; }
+    std::vector<double> work(3 * (size_t)p->n_fft);
+    rts_range_eval_host(q, cube, p, plan, out, work.data());
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_range_transform(RtsHandle c, const RtsRangeParams* p, void* device_out)
+{
+    CHECK_HANDLE(c);
+    NEED_CUBE(c, "rts_cube_range_transform", "no cube (call rts_cube_attach first)");
+    const RtsCubeParams& q = c->cube.params;
+    RtsRangePlan plan;
+    int rc = rts_range_check(p, q, "rts_cube_range_transform", &plan); if (rc != RTS_OK) return rc;
+    if ((uintptr_t)device_out & 15u) { rts_set_error("rts_cube_range_transform: device_out is not 16-byte aligned"); return RTS_ERR_INVALID; }
+    if ((uintptr_t)c->cube.p & 15u) { rts_set_error("rts_cube_range_transform: the cube's device memory is not 16-byte aligned"); return RTS_ERR_INVALID; }
+    CHECK_CLOSED(c);
+    double* out; RTS_HIP(c->cube.range.place(device_out, plan.out_doubles, &out));
+    // the window -> pinned staging -> the device, on the stream (n_samples <= RTS_RANGE_MAX_FFT: one size for every call)
+    const double* win = nullptr;
+    if (p->window) {
+        double* w = nullptr;
+        RTS_HIP(c->cube.range_win.begin(RTS_RANGE_MAX_FFT, RTS_RANGE_MAX_FFT, RTS_RANGE_MAX_FFT, &w));
+        memcpy(w, p->window, sizeof(double) * plan.n_samples);
+        RTS_HIP(c->cube.range_win.send(plan.n_samples, c->stream));
+        win = c->cube.range_win.dev.p;
+    }
+    if (!device_out) c->cube.range.record(out, plan.out_doubles);
+    return rts_cube_range_device(c, *p, plan, win, out);
+}
+
+extern "C" int rts_cube_range_get(RtsHandle c, double* host_out, uint64_t capacity_doubles)
+{
+    CHECK_HANDLE(c);
+    return rts_cube_copy_out(c, "rts_cube_range_get", "no library-owned range map (rts_cube_range_transform with device_out NULL; a range map ends at rts_cube_attach) / null output", c->cube.range.valid, c->cube.range.p, c->cube.range.doubles, host_out, capacity_doubles);
+}
+
 // ------------------------------------------------------------------------------------- backprojection imaging
 // (rts_amd.h: RtsImageParams; the arithmetic and the launch plan are rts_image.h, shared by the host export and the kernel, rts_image.hip)
 static int rts_image_check(const RtsImageParams* p, const RtsCubeParams& q, const char* who)

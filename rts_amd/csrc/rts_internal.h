@@ -13,6 +13,7 @@
 #include "rts_noise.h"
 #include "rts_image.h"            // the arithmetic of a backprojected pixel and the host-only plan of its launch
 #include "rts_stft.h"             // the tree of the slow-time spectrogram and the host-only plan of its launch
+#include "rts_beat.h"             // the tree of the dechirped beat render, the range transform's evaluator and the host-only plans of their launches
 #include "rts_cfar_os.h"          // ordered-statistic CFAR: window size, training count, rank rule, alphas, the host evaluator
 #include "rts_owned.h"            // DevBuf, PinBuf, StagedUpload: device and pinned host memory that frees itself
 #include "rts_launch_plan.h"      // RTS_BLOCK, RTS_WTILE, RTS_COOP_GROUP, RTS_STACK_OVF and the host arithmetic of a launch
@@ -306,7 +307,7 @@ struct RtsCubeProduct {
 };
 
 // The cube part of a handle: it shares nothing with the pulse path but the handle (rts_cube_api.hip; the launchers of rts_post.hip,
-// rts_render.hip, rts_detect.hip, rts_image.hip, rts_stft.hip).
+// rts_render.hip, rts_detect.hip, rts_image.hip, rts_stft.hip, rts_beat.hip).
 struct RtsCubeState {
     RtsCubeParams params = {}; double* p = nullptr; DevBuf<double> own; bool set = false;      // p: the attached cube, own when the library allocated it
     DevBuf<double> d_wave; uint32_t wave_M = 0, wave_L = 0; bool wave_set = false;         // the transmit waveform (rts_cube_set_waveform): M interleaved samples, L taps
@@ -327,9 +328,14 @@ struct RtsCubeState {
     // staged upload; the tile sums of RTS_STFT_SUM_BINS
     RtsCubeProduct stft;
     StagedUpload<double> stft_win; DevBuf<double> d_stft_part;
+    // FMCW (rts_beat.hip): the part sums of a beat render (rts_cube_render_beat) and the parts forced on its plan (RTS_BEAT_PARTS, the
+    // tests: 0 = the plan's own); the range transform's output (rts_cube_range_transform), for rts_cube_range_get, and its staged window
+    DevBuf<double> d_beat_part; uint32_t beat_force_parts = 0;
+    RtsCubeProduct range;
+    StagedUpload<double> range_win;
     // every product belongs to the cube it was made from: the Doppler map (which rts_cube_detect may take), the detection list, the image
-    // and the spectrogram end when another cube is attached
-    void end_products() { doppler.valid = false; det_valid = false; image.valid = false; stft.valid = false; }
+    // the spectrogram and the range transform end when another cube is attached
+    void end_products() { doppler.valid = false; det_valid = false; image.valid = false; stft.valid = false; range.valid = false; }
 };
 
 // What a pulse leaves for its accessors (rts_results_api.hip; the finalisers, the aggregation and the end-of-pulse chains of rts_api.hip; the
@@ -476,6 +482,8 @@ int rts_cube_noise_device(RtsContext* c, uint32_t first_pulse, uint32_t n_pulses
 int rts_cube_detect_device(RtsContext* c, const RtsCfarParams& p, const double* map, uint32_t n_doppler, uint32_t max_det);
 int rts_cube_detect_os_device(RtsContext* c, const RtsCfarOsParams& p, const double* alpha_tab, const double* map, uint32_t n_doppler, uint32_t max_det);      // alpha_tab: device, by training count (pfa), or null (p.alpha)
 int rts_cube_stft_device(RtsContext* c, const RtsStftParams& p, const RtsStftPlan& plan, const double* window, double* out);      // rts_stft.hip
+int rts_cube_beat_device(RtsContext* c, uint32_t pulse_index, const RtsBeatParams& p, const RtsBeatPlan& plan, double cspeed, double carrier, int64_t base);      // rts_beat.hip
+int rts_cube_range_device(RtsContext* c, const RtsRangeParams& p, const RtsRangePlan& plan, const double* window, double* out);
 int rts_cube_backproject_device(RtsContext* c, const RtsImageParams& p, const RtsImagePlan& plan, const double* geo, double* out);      // rts_image.hip
 int rts_post_finalise(RtsContext* c, const double* rcs_host, double wl, double gt, double gr, double carrier, double cspeed);
 int rts_pattern_pulse_upload(RtsContext* c, const RtsSpecParams& q, RtsPatArgs* out);      // the pulse's receiver rows -> the device, on c->stream
