@@ -537,7 +537,7 @@ int rts_cube_detections_get(RtsHandle h, RtsDetection* out, uint32_t capacity, u
  * k of a cell's N training cells are contaminated, so a strong return (another target, a multi-bounce path a few bins away, a
  * blade flash along Doppler) in a neighbour's window does not lift that neighbour's threshold by P / N and hide it.  Its own entry
  * point and parameter record: rts_cube_detect keeps refusing modes above RTS_CFAR_SO.  The arithmetic is rts_amd/csrc/rts_cfar_os.h,
- * shared by the kernel (rts_detect.hip) and the host evaluator.
+ * shared by the kernel (rts_detect.hip) and the host evaluator; what it takes unchanged from rts_cube_detect is rts_amd/csrc/rts_cfar.h.
  *   Taken unchanged from rts_cube_detect: the input map (the handle's last rts_cube_doppler output, or a caller device pointer, 16-byte
  *     aligned, with n_doppler >= 1); the window (the training annulus |dk| <= Gd + Td, |dr| <= Gr + Tr minus the guard rectangle,
  *     Doppler wrapped, range truncated, so N varies near the range edges); RTS_CFAR_LOCAL_MAX, including its behaviour on one-row and

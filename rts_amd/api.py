@@ -217,16 +217,21 @@ def cfar_os_alpha(n, k, pfa):
     return a.value
 
 
-def _cfar_os_params(guard, train, rank, pfa, alpha, local_max, pri, max_detections):
-    """RtsCfarOsParams; rank None: three quarters of a full window, (3 N0) // 4"""
-    p = L.RtsCfarOsParams()
+def _cfar_params(p, guard, train, pfa, alpha, local_max, pri, max_detections):
+    """the fields RtsCfarParams and RtsCfarOsParams share, into p"""
     p.guard_range, p.guard_doppler = (int(g) for g in guard)
     p.train_range, p.train_doppler = (int(t) for t in train)
-    p.rank = (3 * cfar_os_n0(guard, train)) // 4 if rank is None else int(rank)
     p.flags = L.RTS_CFAR_LOCAL_MAX if local_max else 0
     p.pfa = 0.0 if pfa is None else float(pfa)
     p.alpha = 0.0 if alpha is None else float(alpha)
     p.pri, p.max_detections = float(pri), int(max_detections)
+    return p
+
+
+def _cfar_os_params(guard, train, rank, pfa, alpha, local_max, pri, max_detections):
+    """RtsCfarOsParams; rank None: three quarters of a full window, (3 N0) // 4"""
+    p = _cfar_params(L.RtsCfarOsParams(), guard, train, pfa, alpha, local_max, pri, max_detections)
+    p.rank = (3 * cfar_os_n0(guard, train)) // 4 if rank is None else int(rank)
     return p
 
 
@@ -773,18 +778,9 @@ class Tracer:
         """rts_cube_detect + rts_cube_detections_get: CFAR on the handle's last cube_doppler map (device_ptr None) or on a caller
         complex128 device map [n_rx][n_doppler][n_bins]; guard and train are (range, Doppler) cells on each side; mode "ca", "go"
         or "so"; exactly one of pfa (CA) and alpha.  Returns a DETECTION_DTYPE array in flat (rx, doppler_bin, range_bin) order."""
-        p = L.RtsCfarParams()
-        p.guard_range, p.guard_doppler = (int(g) for g in guard)
-        p.train_range, p.train_doppler = (int(t) for t in train)
+        p = _cfar_params(L.RtsCfarParams(), guard, train, pfa, alpha, local_max, pri, max_detections)
         p.mode = {"ca": L.RTS_CFAR_CA, "go": L.RTS_CFAR_GO, "so": L.RTS_CFAR_SO}.get(mode, mode)
-        p.flags = L.RTS_CFAR_LOCAL_MAX if local_max else 0
-        p.pfa = 0.0 if pfa is None else float(pfa)
-        p.alpha = 0.0 if alpha is None else float(alpha)
-        p.pri, p.max_detections = float(pri), int(max_detections)
-        if device_ptr and n_doppler is None:
-            raise ValueError("cube_detect(device_ptr=...) needs n_doppler")
-        check(L.lib().rts_cube_detect(self.h, C.byref(p), C.c_void_p(device_ptr) if device_ptr else None, int(n_doppler or 0)))
-        return self.detections() if fetch else None
+        return self._detect(L.lib().rts_cube_detect, "cube_detect", p, device_ptr, n_doppler, fetch)
 
     def cube_detect_os(self, guard=(2, 2), train=(8, 4), rank=None, pfa=None, alpha=None, local_max=True, pri=0.0, device_ptr=None,
                        n_doppler=None, max_detections=0, fetch=True):
@@ -793,9 +789,13 @@ class Tracer:
         is the rank in a full window of N0 training cells (None: (3 N0) // 4); exactly one of pfa and alpha.  Returns a
         DETECTION_DTYPE array in flat (rx, doppler_bin, range_bin) order."""
         p = _cfar_os_params(guard, train, rank, pfa, alpha, local_max, pri, max_detections)
+        return self._detect(L.lib().rts_cube_detect_os, "cube_detect_os", p, device_ptr, n_doppler, fetch)
+
+    def _detect(self, call, who, p, device_ptr, n_doppler, fetch):
+        """either detector on the handle's map (device_ptr None) or the caller's, which needs n_doppler; the list when fetch"""
         if device_ptr and n_doppler is None:
-            raise ValueError("cube_detect_os(device_ptr=...) needs n_doppler")
-        check(L.lib().rts_cube_detect_os(self.h, C.byref(p), C.c_void_p(device_ptr) if device_ptr else None, int(n_doppler or 0)))
+            raise ValueError("%s(device_ptr=...) needs n_doppler" % who)
+        check(call(self.h, C.byref(p), C.c_void_p(device_ptr) if device_ptr else None, int(n_doppler or 0)))
         return self.detections() if fetch else None
 
     def detections(self):

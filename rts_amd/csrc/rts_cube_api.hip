@@ -176,37 +176,66 @@ extern "C" int rts_cube_add_noise(RtsHandle c, uint32_t first_pulse, uint32_t n_
     return rts_cube_noise_device(c, first_pulse, n_pulses, sqrt(noise_power / 2.0), seed);
 }
 
+// The checks rts_cube_detect, rts_cube_detect_os and rts_cfar_os_eval share, in the order each of them applies them.
+// The map of a device detector: the caller's (n_doppler rows, 16-byte aligned) or the handle's last Doppler map.
+static int rts_cfar_map(RtsContext* c, const char* who, const void* device_map, const double** map, uint32_t* n_doppler)
+{
+    *map = (const double*)device_map;
+    if (*map) {
+        if (*n_doppler == 0) { rts_set_error("%s: n_doppler = 0 with a caller map", who); return RTS_ERR_INVALID; }
+        if ((uintptr_t)*map & 15u) { rts_set_error("%s: device_map is not 16-byte aligned", who); return RTS_ERR_INVALID; }
+    } else {
+        if (!c->cube.doppler.valid) { rts_set_error("%s: no map (call rts_cube_doppler first, or pass device_map)", who); return RTS_ERR_INVALID; }
+        *map = c->cube.doppler.p; *n_doppler = c->cube.doppler_n;
+    }
+    return RTS_OK;
+}
+
+// flags, reserved fields and the window of either parameter record on a map of n_doppler x nb cells
+template <class Params> static int rts_cfar_window_check(const char* who, const Params* p, uint32_t nb, uint32_t n_doppler)
+{
+    const uint32_t Gr = p->guard_range, Gd = p->guard_doppler, Tr = p->train_range, Td = p->train_doppler;
+    if (p->flags & ~RTS_CFAR_LOCAL_MAX) { rts_set_error("%s: unknown flags 0x%x", who, p->flags); return RTS_ERR_INVALID; }
+    if (p->reserved0 || p->reserved[0] || p->reserved[1]) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
+    if (Tr > RTS_CFAR_MAX_HALF || Td > RTS_CFAR_MAX_HALF || Gr > RTS_CFAR_MAX_HALF || Gd > RTS_CFAR_MAX_HALF) { rts_set_error("%s: guard_range, guard_doppler, train_range, train_doppler are at most %u each", who, RTS_CFAR_MAX_HALF); return RTS_ERR_INVALID; }
+    if (Tr + Td == 0) { rts_set_error("%s: train_range + train_doppler = 0 (no training cells)", who); return RTS_ERR_INVALID; }
+    if (Gr + Tr > RTS_CFAR_MAX_HALF) { rts_set_error("%s: guard_range + train_range = %u > %u", who, Gr + Tr, RTS_CFAR_MAX_HALF); return RTS_ERR_INVALID; }
+    if (Gd + Td > RTS_CFAR_MAX_HALF) { rts_set_error("%s: guard_doppler + train_doppler = %u > %u", who, Gd + Td, RTS_CFAR_MAX_HALF); return RTS_ERR_INVALID; }
+    if (2 * (Gd + Td) + 1 > n_doppler) { rts_set_error("%s: guard_doppler + train_doppler = %u: the window (%u rows) exceeds n_doppler = %u", who, Gd + Td, 2 * (Gd + Td) + 1, n_doppler); return RTS_ERR_INVALID; }
+    if (Gr + Tr >= nb) { rts_set_error("%s: guard_range + train_range = %u >= n_bins = %u", who, Gr + Tr, nb); return RTS_ERR_INVALID; }
+    return RTS_OK;
+}
+
+// exactly one of pfa and alpha, each in its range; pri.  Two checks, because rts_cube_detect has always reported its GO / SO rules
+// between them, and a record with several wrong fields keeps reporting the one it reported
+static int rts_cfar_level_check(const char* who, double pfa, double alpha)
+{
+    const bool has_pfa = pfa != 0.0, has_alpha = alpha != 0.0;
+    if (has_pfa && !(pfa > 0.0 && pfa < 1.0)) { rts_set_error("%s: pfa = %g outside (0, 1)", who, pfa); return RTS_ERR_INVALID; }
+    if (has_pfa == has_alpha) { rts_set_error("%s: give exactly one of pfa and alpha", who); return RTS_ERR_INVALID; }
+    if (has_alpha && !(alpha > 0.0 && std::isfinite(alpha))) { rts_set_error("%s: alpha = %g (finite, > 0)", who, alpha); return RTS_ERR_INVALID; }
+    return RTS_OK;
+}
+static int rts_cfar_pri_check(const char* who, double pri)
+{
+    if (!(pri >= 0.0) || !std::isfinite(pri)) { rts_set_error("%s: pri = %g (finite, >= 0)", who, pri); return RTS_ERR_INVALID; }
+    return RTS_OK;
+}
+
 extern "C" int rts_cube_detect(RtsHandle c, const RtsCfarParams* p, const void* device_map, uint32_t n_doppler)
 {
     CHECK_HANDLE(c);
     if (!p) { rts_set_error("rts_cube_detect: null parameters"); return RTS_ERR_INVALID; }
     CHECK_CLOSED(c);
     NEED_CUBE(c, "rts_cube_detect", "no cube (call rts_cube_attach first)");
-    const double* map = (const double*)device_map;
-    if (map) {
-        if (n_doppler == 0) { rts_set_error("rts_cube_detect: n_doppler = 0 with a caller map"); return RTS_ERR_INVALID; }
-        if ((uintptr_t)map & 15u) { rts_set_error("rts_cube_detect: device_map is not 16-byte aligned"); return RTS_ERR_INVALID; }
-    } else {
-        if (!c->cube.doppler.valid) { rts_set_error("rts_cube_detect: no map (call rts_cube_doppler first, or pass device_map)"); return RTS_ERR_INVALID; }
-        map = c->cube.doppler.p; n_doppler = c->cube.doppler_n;
-    }
-    const uint32_t Gr = p->guard_range, Gd = p->guard_doppler, Tr = p->train_range, Td = p->train_doppler, nb = c->cube.params.n_bins;
+    const double* map;
+    { int rc = rts_cfar_map(c, "rts_cube_detect", device_map, &map, &n_doppler); if (rc != RTS_OK) return rc; }
     if (p->mode > RTS_CFAR_SO) { rts_set_error("rts_cube_detect: unknown mode %u (RTS_CFAR_CA, _GO, _SO)", p->mode); return RTS_ERR_INVALID; }
-    if (p->flags & ~RTS_CFAR_LOCAL_MAX) { rts_set_error("rts_cube_detect: unknown flags 0x%x", p->flags); return RTS_ERR_INVALID; }
-    if (p->reserved0 || p->reserved[0] || p->reserved[1]) { rts_set_error("rts_cube_detect: reserved fields must be 0"); return RTS_ERR_INVALID; }
-    if (Tr > RTS_CFAR_MAX_HALF || Td > RTS_CFAR_MAX_HALF || Gr > RTS_CFAR_MAX_HALF || Gd > RTS_CFAR_MAX_HALF) { rts_set_error("rts_cube_detect: guard_range, guard_doppler, train_range, train_doppler are at most %u each", RTS_CFAR_MAX_HALF); return RTS_ERR_INVALID; }
-    if (Tr + Td == 0) { rts_set_error("rts_cube_detect: train_range + train_doppler = 0 (no training cells)"); return RTS_ERR_INVALID; }
-    if (Gr + Tr > RTS_CFAR_MAX_HALF) { rts_set_error("rts_cube_detect: guard_range + train_range = %u > %u", Gr + Tr, RTS_CFAR_MAX_HALF); return RTS_ERR_INVALID; }
-    if (Gd + Td > RTS_CFAR_MAX_HALF) { rts_set_error("rts_cube_detect: guard_doppler + train_doppler = %u > %u", Gd + Td, RTS_CFAR_MAX_HALF); return RTS_ERR_INVALID; }
-    if (2 * (Gd + Td) + 1 > n_doppler) { rts_set_error("rts_cube_detect: guard_doppler + train_doppler = %u: the window (%u rows) exceeds n_doppler = %u", Gd + Td, 2 * (Gd + Td) + 1, n_doppler); return RTS_ERR_INVALID; }
-    if (Gr + Tr >= nb) { rts_set_error("rts_cube_detect: guard_range + train_range = %u >= n_bins = %u", Gr + Tr, nb); return RTS_ERR_INVALID; }
-    const bool has_pfa = p->pfa != 0.0, has_alpha = p->alpha != 0.0;
-    if (has_pfa && !(p->pfa > 0.0 && p->pfa < 1.0)) { rts_set_error("rts_cube_detect: pfa = %g outside (0, 1)", p->pfa); return RTS_ERR_INVALID; }
-    if (has_pfa == has_alpha) { rts_set_error("rts_cube_detect: give exactly one of pfa and alpha"); return RTS_ERR_INVALID; }
-    if (has_alpha && !(p->alpha > 0.0 && std::isfinite(p->alpha))) { rts_set_error("rts_cube_detect: alpha = %g (finite, > 0)", p->alpha); return RTS_ERR_INVALID; }
-    if (p->mode != RTS_CFAR_CA && has_pfa) { rts_set_error("rts_cube_detect: pfa is for mode RTS_CFAR_CA only (GO / SO take alpha)"); return RTS_ERR_INVALID; }
-    if (p->mode != RTS_CFAR_CA && Tr == 0) { rts_set_error("rts_cube_detect: train_range = 0 with GO / SO (the halves are range halves)"); return RTS_ERR_INVALID; }
-    if (!(p->pri >= 0.0) || !std::isfinite(p->pri)) { rts_set_error("rts_cube_detect: pri = %g (finite, >= 0)", p->pri); return RTS_ERR_INVALID; }
+    { int rc = rts_cfar_window_check("rts_cube_detect", p, c->cube.params.n_bins, n_doppler); if (rc != RTS_OK) return rc; }
+    { int rc = rts_cfar_level_check("rts_cube_detect", p->pfa, p->alpha); if (rc != RTS_OK) return rc; }
+    if (p->mode != RTS_CFAR_CA && p->pfa != 0.0) { rts_set_error("rts_cube_detect: pfa is for mode RTS_CFAR_CA only (GO / SO take alpha)"); return RTS_ERR_INVALID; }
+    if (p->mode != RTS_CFAR_CA && p->train_range == 0) { rts_set_error("rts_cube_detect: train_range = 0 with GO / SO (the halves are range halves)"); return RTS_ERR_INVALID; }
+    { int rc = rts_cfar_pri_check("rts_cube_detect", p->pri); if (rc != RTS_OK) return rc; }
     c->cube.det_valid = false;
     return rts_cube_detect_device(c, *p, map, n_doppler, p->max_detections ? p->max_detections : RTS_CFAR_DEFAULT_MAX_DETECTIONS);
 }
@@ -228,26 +257,15 @@ extern "C" int rts_cube_detections_get(RtsHandle c, RtsDetection* out, uint32_t 
 }
 
 // ------------------------------------------------------------------------------------- ordered-statistic CFAR
-// (rts_amd.h: RtsCfarOsParams; the arithmetic is rts_cfar_os.h, shared by the host exports and the kernel, rts_detect.hip)
+// (rts_amd.h: RtsCfarOsParams; the arithmetic is rts_cfar_os.h, shared by the host exports and the kernel, rts_detect.hip; the checks of the
+// fields it shares with RtsCfarParams are rts_cube_detect's, above)
 static int rts_cfar_os_check(const RtsCfarOsParams* p, uint32_t nb, uint32_t n_doppler, const char* who)
 {
-    const uint32_t Gr = p->guard_range, Gd = p->guard_doppler, Tr = p->train_range, Td = p->train_doppler;
-    if (p->flags & ~RTS_CFAR_LOCAL_MAX) { rts_set_error("%s: unknown flags 0x%x", who, p->flags); return RTS_ERR_INVALID; }
-    if (p->reserved0 || p->reserved[0] || p->reserved[1]) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
-    if (Tr > RTS_CFAR_MAX_HALF || Td > RTS_CFAR_MAX_HALF || Gr > RTS_CFAR_MAX_HALF || Gd > RTS_CFAR_MAX_HALF) { rts_set_error("%s: guard_range, guard_doppler, train_range, train_doppler are at most %u each", who, RTS_CFAR_MAX_HALF); return RTS_ERR_INVALID; }
-    if (Tr + Td == 0) { rts_set_error("%s: train_range + train_doppler = 0 (no training cells)", who); return RTS_ERR_INVALID; }
-    if (Gr + Tr > RTS_CFAR_MAX_HALF) { rts_set_error("%s: guard_range + train_range = %u > %u", who, Gr + Tr, RTS_CFAR_MAX_HALF); return RTS_ERR_INVALID; }
-    if (Gd + Td > RTS_CFAR_MAX_HALF) { rts_set_error("%s: guard_doppler + train_doppler = %u > %u", who, Gd + Td, RTS_CFAR_MAX_HALF); return RTS_ERR_INVALID; }
-    if (2 * (Gd + Td) + 1 > n_doppler) { rts_set_error("%s: guard_doppler + train_doppler = %u: the window (%u rows) exceeds n_doppler = %u", who, Gd + Td, 2 * (Gd + Td) + 1, n_doppler); return RTS_ERR_INVALID; }
-    if (Gr + Tr >= nb) { rts_set_error("%s: guard_range + train_range = %u >= n_bins = %u", who, Gr + Tr, nb); return RTS_ERR_INVALID; }
-    const uint32_t N0 = rts_cfar_os_n0(Gr, Gd, Tr, Td);
+    { int rc = rts_cfar_window_check(who, p, nb, n_doppler); if (rc != RTS_OK) return rc; }
+    const uint32_t N0 = rts_cfar_n0(p->guard_range, p->guard_doppler, p->train_range, p->train_doppler);
     if (p->rank == 0 || p->rank > N0) { rts_set_error("%s: rank = %u outside [1, N0 = %u] (the training cells of a full window)", who, p->rank, N0); return RTS_ERR_INVALID; }
-    const bool has_pfa = p->pfa != 0.0, has_alpha = p->alpha != 0.0;
-    if (has_pfa && !(p->pfa > 0.0 && p->pfa < 1.0)) { rts_set_error("%s: pfa = %g outside (0, 1)", who, p->pfa); return RTS_ERR_INVALID; }
-    if (has_pfa == has_alpha) { rts_set_error("%s: give exactly one of pfa and alpha", who); return RTS_ERR_INVALID; }
-    if (has_alpha && !(p->alpha > 0.0 && std::isfinite(p->alpha))) { rts_set_error("%s: alpha = %g (finite, > 0)", who, p->alpha); return RTS_ERR_INVALID; }
-    if (!(p->pri >= 0.0) || !std::isfinite(p->pri)) { rts_set_error("%s: pri = %g (finite, >= 0)", who, p->pri); return RTS_ERR_INVALID; }
-    return RTS_OK;
+    { int rc = rts_cfar_level_check(who, p->pfa, p->alpha); if (rc != RTS_OK) return rc; }
+    return rts_cfar_pri_check(who, p->pri);
 }
 
 extern "C" int rts_cfar_os_alpha(uint32_t n_train, uint32_t rank, double pfa, double* alpha)
@@ -267,7 +285,7 @@ extern "C" int rts_cfar_os_eval(const RtsCubeParams* q, const double* map, uint3
     if (n_doppler == 0) { rts_set_error("rts_cfar_os_eval: n_doppler = 0"); return RTS_ERR_INVALID; }
     int rc = rts_cfar_os_check(p, q->n_bins, n_doppler, "rts_cfar_os_eval"); if (rc != RTS_OK) return rc;
     if (!map || !n_out || (capacity && !out)) { rts_set_error("rts_cfar_os_eval: null map or output"); return RTS_ERR_INVALID; }
-    const uint32_t N0 = rts_cfar_os_n0(p->guard_range, p->guard_doppler, p->train_range, p->train_doppler);
+    const uint32_t N0 = rts_cfar_n0(p->guard_range, p->guard_doppler, p->train_range, p->train_doppler);
     std::vector<double> tab; std::vector<uint64_t> keys(N0);
     if (p->pfa != 0.0) { tab.assign((size_t)N0 + 1, 0.0); rts_cfar_os_alpha_table(p->guard_range, p->guard_doppler, p->train_range, p->train_doppler, p->rank, p->pfa, q->n_bins, tab.data()); }
     const uint32_t total = rts_cfar_os_eval_host(q, map, n_doppler, p, tab.empty() ? nullptr : tab.data(), keys.data(), out, capacity);
@@ -282,14 +300,8 @@ extern "C" int rts_cube_detect_os(RtsHandle c, const RtsCfarOsParams* p, const v
     if (!p) { rts_set_error("rts_cube_detect_os: null parameters"); return RTS_ERR_INVALID; }
     CHECK_CLOSED(c);
     NEED_CUBE(c, "rts_cube_detect_os", "no cube (call rts_cube_attach first)");
-    const double* map = (const double*)device_map;
-    if (map) {
-        if (n_doppler == 0) { rts_set_error("rts_cube_detect_os: n_doppler = 0 with a caller map"); return RTS_ERR_INVALID; }
-        if ((uintptr_t)map & 15u) { rts_set_error("rts_cube_detect_os: device_map is not 16-byte aligned"); return RTS_ERR_INVALID; }
-    } else {
-        if (!c->cube.doppler.valid) { rts_set_error("rts_cube_detect_os: no map (call rts_cube_doppler first, or pass device_map)"); return RTS_ERR_INVALID; }
-        map = c->cube.doppler.p; n_doppler = c->cube.doppler_n;
-    }
+    const double* map;
+    { int rc = rts_cfar_map(c, "rts_cube_detect_os", device_map, &map, &n_doppler); if (rc != RTS_OK) return rc; }
     const uint32_t nb = c->cube.params.n_bins;
     { int rc = rts_cfar_os_check(p, nb, n_doppler, "rts_cube_detect_os"); if (rc != RTS_OK) return rc; }
     c->cube.det_valid = false;
@@ -298,7 +310,7 @@ extern "C" int rts_cube_detect_os(RtsHandle c, const RtsCfarOsParams* p, const v
     const double* tab_dev = nullptr;
     if (p->pfa != 0.0) {
         RtsCubeState& s = c->cube;
-        const uint32_t N0 = rts_cfar_os_n0(p->guard_range, p->guard_doppler, p->train_range, p->train_doppler);
+        const uint32_t N0 = rts_cfar_n0(p->guard_range, p->guard_doppler, p->train_range, p->train_doppler);
         const uint32_t key[5] = {p->guard_range, p->guard_doppler, p->train_range, p->train_doppler, p->rank};
         if (s.os_tab.size() != (size_t)N0 + 1 || memcmp(key, s.os_tab_key, sizeof(key)) != 0 || s.os_tab_pfa != p->pfa) {
             s.os_tab.assign((size_t)N0 + 1, 0.0); memcpy(s.os_tab_key, key, sizeof(key)); s.os_tab_pfa = p->pfa; s.os_tab_sent = false;

@@ -14,7 +14,7 @@
 #include "rts_image.h"            // the arithmetic of a backprojected pixel and the host-only plan of its launch
 #include "rts_stft.h"             // the tree of the slow-time spectrogram and the host-only plan of its launch
 #include "rts_beat.h"             // the tree of the dechirped beat render, the range transform's evaluator and the host-only plans of their launches
-#include "rts_cfar_os.h"          // ordered-statistic CFAR: window size, training count, rank rule, alphas, the host evaluator
+#include "rts_cfar_os.h"          // CFAR: what every detector shares (rts_cfar.h: window, training count, local maximum, refinement, record); OS: rank rule, alphas, the host evaluator
 #include "rts_owned.h"            // DevBuf, PinBuf, StagedUpload: device and pinned host memory that frees itself
 #include "rts_launch_plan.h"      // RTS_BLOCK, RTS_WTILE, RTS_COOP_GROUP, RTS_STACK_OVF and the host arithmetic of a launch
 #include "rts_post_plan.h"        // RTS_SMALL_CAP32 / 64, RTS_AGG_TILE and the host arithmetic of the post-processing

@@ -1,7 +1,7 @@
 """Ordered-statistic CFAR on the host (no GPU): rts_cfar_os_alpha against the false-alarm law it inverts, rts_cfar_os_eval against an
 independent numpy restatement of include/rts_amd.h (RtsCfarOsParams; tests/cfar_os_ref.py) on the shapes of the GPU test, the
 masking that cell averaging suffers and OS does not, the false-alarm rate on Gaussian noise, the validation of malformed records,
-and rts_amd/csrc/rts_cfar_os.h alone under AddressSanitizer + UndefinedBehaviorSanitizer (tests/cfar_os/cfar_os_main.cpp).
+and rts_amd/csrc/rts_cfar_os.h (with the rts_cfar.h every detector shares) alone under AddressSanitizer + UndefinedBehaviorSanitizer (tests/cfar_os/cfar_os_main.cpp).
 
 An order statistic has no summation order: integer fields, power and noise are compared exactly, the threshold exactly when alpha
 is given and to 1e-11 relative with pfa (the bound rts_cfar_os_alpha documents for the law at its alpha; the restatement's alpha is
@@ -210,6 +210,26 @@ def test_header_alone_window_and_rank(os_main):
         got = os_main([("ranks", rank, n0)], int)[0]
         assert got == [-(-rank * N // n0) for N in range(1, n0 + 1)]
         assert min(got) >= 1 and all(k <= N for k, N in zip(got, range(1, n0 + 1))) and got[-1] == rank
+
+
+def test_header_alone_halves(os_main):
+    """the training count's left and right halves (the mean-level kernel's GO / SO means divide by them) against a count one offset at
+    a time, and, for every window of up to 16 cells per field and every pair of edge distances, the integers of the two texts the
+    shared count replaced"""
+    for (g, t) in WINDOWS:
+        Or, Od = g[0] + t[0], g[1] + t[1]
+        for nb in (Or + 1, Or + 2, 2 * Or + 1, 70):
+            got = np.array(os_main([("halves", g[0], g[1], t[0], t[1], nb)], int)[0]).reshape(nb, 2)
+            r = np.arange(nb)
+            want = np.zeros((nb, 2), np.int64)
+            for dk in range(-Od, Od + 1):
+                for dr in range(-Or, Or + 1):
+                    if dr != 0 and not (abs(dk) <= g[1] and abs(dr) <= g[0]):
+                        want[:, 0 if dr < 0 else 1] += (r + dr >= 0) & (r + dr < nb)
+            assert np.array_equal(got, want), (g, t, nb)
+            assert (got.sum(axis=1) + 2 * t[1]).tolist() == counts_ref(g[0], g[1], t[0], t[1], nb).tolist()
+    checked, bad = os_main([("halves", 16)], int)[0]
+    assert checked == 17 * 17 * sum((gr + tr + 2) ** 2 for gr in range(17) for tr in range(17)) and bad == 0
 
 
 def test_header_alone_alpha_and_table(os_main):

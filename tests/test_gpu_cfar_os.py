@@ -1,6 +1,6 @@
 """Ordered-statistic CFAR on the device (rts_cube_detect_os, k_cfar_os): against the numpy restatement of include/rts_amd.h
 (tests/cfar_os_ref.py) and, bit for bit, against the host evaluator rts_cfar_os_eval on eight shapes that cover the kernel's paths;
-the masking that hides a target from cell averaging; the false-alarm rate and a moving target end to end; determinism, the two map
+the masking that hides a target from cell averaging; both detectors' lists byte for byte on a map where their estimates coincide; the false-alarm rate and a moving target end to end; determinism, the two map
 sources, the shared detection list; and the error / lifetime rules.
 
 Integer fields, power and noise are compared exactly with the restatement (an order statistic has no summation order), the
@@ -132,6 +132,50 @@ def test_moving_target_end_to_end(rts):
         assert sa["power"] == sb["power"] and sb["doppler"] > 0          # (closing: positive Doppler)
         checked += 1
     assert checked >= 1
+
+
+# ----------------------------------------------------------------------------- both detectors, one list
+def flat_noise_map():
+    """2 x 20 x 130, one tile and a bit on each axis: background 1, in receiver rx peaks of amplitude 10 + rx with sloped neighbours
+    (3.0 at r - 1, 2.25 at r + 1, 2.5 at k - 1, 1.5 at k + 1; Doppler wrapped, range neighbours outside the map omitted)"""
+    n_rx, nd, nb = 2, 20, 130
+    peaks = [(0, 0), (3, 63), (8, 64), (15, 100), (16, 129), (19, 30)]
+    z = np.ones((n_rx, nd, nb), np.complex128)
+    for rx in range(n_rx):
+        for k, r in peaks:
+            z[rx, k, r] = 10.0 + rx
+            for dk, dr, amp in ((0, -1, 3.0), (0, 1, 2.25), (-1, 0, 2.5), (1, 0, 1.5)):
+                if 0 <= r + dr < nb:
+                    z[rx, (k + dk) % nd, r + dr] = amp
+    return z, peaks
+
+
+def test_both_detectors_one_list(rts):
+    """Every training cell of every peak of flat_noise_map is exactly 1.0 under guard (1, 1), train (2, 2): the mean (a sum of at most
+    40 ones, exact) and every order statistic are 1.0 and the threshold is 4.0 in both detectors, and with the local-maximum rule
+    neither reports another cell.  So cell averaging and OS at ranks 1, 20 and 36 of N0 = 40 write the same 12 records byte for
+    byte: frame, refinement, delay and Doppler included.  Without the rule the neighbours are reported too, 44 records from each,
+    and the noise estimates differ: the comparison is not vacuous."""
+    z, peaks = flat_noise_map()
+    n_rx, nd, nb = z.shape
+    m = dev(z)
+    tr = handle(rts, n_rx, 1, nb, T0, DT)
+    kw = dict(guard=(1, 1), train=(2, 2), alpha=4.0, pri=PRI, device_ptr=m.data_ptr(), n_doppler=nd)
+    assert R.n0_of((1, 1), (2, 2)) == 40
+    ca = tr.cube_detect(mode="ca", local_max=True, **kw)
+    lists = [tr.cube_detect_os(rank=rank, local_max=True, **kw) for rank in (1, 20, 36)]
+    ca_all = tr.cube_detect(mode="ca", local_max=False, **kw)
+    os_all = tr.cube_detect_os(rank=20, local_max=False, **kw)
+    tr.close()
+    for got in [ca] + lists:
+        assert len(got) == 12
+        assert list(zip(got["rx"].tolist(), got["doppler_bin"].tolist(), got["range_bin"].tolist())) == [(rx, k, r) for rx in range(n_rx) for k, r in peaks]
+        assert got["n_train"].tolist() == [22 if r in (0, nb - 1) else 40 for rx in range(n_rx) for k, r in peaks]
+        assert np.all(got["noise"] == 1.0) and np.all(got["threshold"] == 4.0)
+        assert got.tobytes() == ca.tobytes()
+    print("records: %d and %d with the rule, %d and %d without" % (len(ca), len(lists[0]), len(ca_all), len(os_all)))
+    assert len(ca_all) == 44 and len(os_all) == 44
+    assert np.any(ca_all["noise"] != os_all["noise"])
 
 
 # ----------------------------------------------------------------------------- determinism, map sources, the shared list
