@@ -1,6 +1,6 @@
 // rts_beat.h -- FMCW / stretch processing (include/rts_amd.h: RtsBeatParams, RtsRangeParams): the dechirped beat render's tree, shared
 // by the kernel (rts_beat.hip: k_cube_beat) and the host evaluator (rts_beat_eval), the fast-time range transform's host evaluator
-// (the tree itself is rts_stft.h's, used as it stands) and the host-only plans of the three launches.  Fixed trees of IEEE basic
+// (on the one transform tree, rts_stft.h) and the host-only plans of the three launches.  Fixed trees of IEEE basic
 // operations plus sincospi, compiled with -ffp-contract=off.  Includes nothing of HIP: it compiles with any host compiler and is
 // tested without a GPU (tests/test_beat_host.py, tests/beat/beat_main.cpp).
 #pragma once
@@ -160,7 +160,7 @@ static inline size_t rts_range_lds_bytes(uint32_t n_fft, uint32_t RT) { return (
 static inline RtsRangePlan rts_range_plan(uint32_t n_rx, uint32_t n_pulses, uint32_t n_samples, uint32_t n_fft, uint32_t n_out)
 {
     RtsRangePlan p;
-    p.logN = 0; while (p.logN < 31u && (1u << p.logN) < n_fft) p.logN++;
+    p.logN = rts_stft_log2(n_fft);
     p.RT = RTS_RANGE_ROW_TILE; while (p.RT > 1u && (uint64_t)p.RT * n_fft > RTS_RANGE_TILE_ELEMS) p.RT >>= 1;
     p.lds = rts_range_lds_bytes(n_fft, p.RT);
     p.n_samples = n_samples; p.n_out = n_out ? n_out : n_fft;

@@ -1,7 +1,8 @@
 // rts_beat.hip -- FMCW / stretch processing on the device (include/rts_amd.h: rts_cube_render_beat, rts_cube_range_transform):
 //   * the dechirped beat render of a pulse's contributions into a row of the return cube (k_cube_beat, k_cube_beat_sum)
 //   * the fast-time (range-axis) transform of the cube's rows (k_cube_range)
-// The arithmetic and the plans of the launches are rts_beat.h (the transform's tree: rts_stft.h), shared with the host evaluators.
+// The arithmetic and the plans of the launches are rts_beat.h (the transform's tree: rts_stft.h), shared with the host evaluators;
+// what a received record contributes, the cell and the add are rts_cube_source.h, shared with the other writers (rts_render.hip).
 #include <hip/hip_runtime.h>
 #include "rts_internal.h"
 #include "rts_beat.h"
@@ -19,9 +20,8 @@
 // 16 lanes) so that the workgroup's global accesses are coalesced: 64 consecutive samples per instruction, whether they are the
 // atomic adds of a one-part render or the stores of a part's sums to scratch[part][rx][n].
 struct RtsBeatArgs {
-    const PerRayData* rays; const double* delay; const double* phase; const int32_t* pm; int64_t base;
-    uint32_t R, part_len; int paths, doppler;
-    double* cube; uint32_t n_pulses, n_bins, pulse; double t0, dt, cspeed, carrier, S, T;
+    RtsCubeSource src; uint32_t part_len; int doppler;
+    double* cube; uint32_t n_pulses, n_bins, pulse; double t0, dt, S, T;
     double2* scratch;                 // more than one part: [parts][n_rx][n_bins]; else null: the sums are added to the cube
 };
 #define RTS_BEAT_PAD (RTS_BEAT_STRIP + 1u)
@@ -31,8 +31,8 @@ __global__ void __launch_bounds__(RTS_BEAT_THREADS) k_cube_beat(const RtsBeatArg
     __shared__ __attribute__((aligned(16))) RtsBeatItem s_item[RTS_BEAT_THREADS];
     __shared__ __attribute__((aligned(16))) double2 s_out[RTS_BEAT_THREADS * RTS_BEAT_PAD];
     const uint32_t lane = threadIdx.x, rx = blockIdx.y, part = blockIdx.z, n_rx = gridDim.y;
-    uint32_t R = a.R;
-    if (R_dev) { const unsigned long long v_ = *R_dev; R = v_ > (unsigned long long)R ? 0u : (uint32_t)v_; }      // (as k_cube_render: a count beyond the host's bound renders nothing)
+    uint32_t R = a.src.R;
+    RTS_DEV_COUNT(R_dev, R, R = 0u);        // (renders nothing, but reaches the barriers and writes its part's zeros to scratch)
     const uint32_t tile0 = blockIdx.x * RTS_BEAT_TILE, n0 = tile0 + lane * RTS_BEAT_STRIP;
     const uint32_t tile_end = a.n_bins - tile0 < RTS_BEAT_TILE ? a.n_bins : tile0 + RTS_BEAT_TILE;      // (tile0 < n_bins: the grid's tiles)
     const double t_tile = rts_beat_time(a.t0, a.dt, tile_end - 1u);
@@ -50,15 +50,12 @@ __global__ void __launch_bounds__(RTS_BEAT_THREADS) k_cube_beat(const RtsBeatArg
         const uint32_t i = c0 + lane;            // (c0 < end <= R < 2^32, lane < 64: wraps only past R, where the test below fails)
         bool keep = false; RtsBeatItem it;
         if (i >= c0 && i < end) {
-            const PerRayData& r = a.rays[i];
-            if (r.received == (int32_t)rx && (!a.paths || (int64_t)a.pm[i] == a.base + (int64_t)i)) {
-                double delay, phase;
-                if (a.paths) { delay = a.delay[i]; phase = a.phase[i]; }
-                else { delay = (r.rayLength)/a.cspeed; phase = -fmod(delay*2*RTS_PI*a.carrier, 2*RTS_PI); }      // aggregation.cu:59-60, as k_cube_render
+            if (rts_cube_counts_for(a.src, a.src.paths != 0, i, (int32_t)rx)) {
+                double delay, phase; rts_cube_timing(a.src, a.src.paths != 0, i, &delay, &phase);
                 if (rts_beat_finite(delay) && delay <= t_tile) {
-                    const double amp = sqrt(r.power);
-                    double sn, cs; sincos(phase, &sn, &cs);
-                    it = rts_beat_item(amp * cs, amp * sn, delay, a.doppler ? r.doppler : 0.0, a.S, a.dt);
+                    const PerRayData& r = a.src.rays[i];
+                    double are, aim; rts_cube_amplitude(r.power, phase, &are, &aim);
+                    it = rts_beat_item(are, aim, delay, a.doppler ? r.doppler : 0.0, a.S, a.dt);
                     keep = true;
                 }
             }
@@ -79,10 +76,7 @@ __global__ void __launch_bounds__(RTS_BEAT_THREADS) k_cube_beat(const RtsBeatArg
         if (n >= a.n_bins) break;
         const double2 v = s_out[(m / RTS_BEAT_STRIP) * RTS_BEAT_PAD + (m % RTS_BEAT_STRIP)];
         if (a.scratch) a.scratch[((size_t)part * n_rx + rx) * a.n_bins + n] = v;
-        else if (v.x != 0.0 || v.y != 0.0) {
-            double* cell = a.cube + 2 * (((size_t)rx * a.n_pulses + a.pulse) * a.n_bins + (size_t)n);
-            atomicAdd(cell, v.x); atomicAdd(cell + 1, v.y);
-        }
+        else if (v.x != 0.0 || v.y != 0.0) rts_cube_add(rts_cube_cell(a.cube, a.n_pulses, a.n_bins, rx, a.pulse, n), v.x, v.y);
     }
 }
 
@@ -96,21 +90,19 @@ __global__ void __launch_bounds__(256) k_cube_beat_sum(const double2* __restrict
     for (uint32_t p = 1; p < parts; p++) { const double2 v = scratch[(size_t)p * cells + i]; s.x += v.x; s.y += v.y; }
     if (s.x != 0.0 || s.y != 0.0) {
         const size_t rx = i / n_bins, n = i - rx * n_bins;
-        double* cell = cube + 2 * ((rx * n_pulses + pulse) * n_bins + n);
-        atomicAdd(cell, s.x); atomicAdd(cell + 1, s.y);
+        rts_cube_add(rts_cube_cell(cube, n_pulses, n_bins, rx, pulse, n), s.x, s.y);
     }
 }
 
 int rts_cube_beat_device(RtsContext* c, uint32_t pulse_index, const RtsBeatParams& p, const RtsBeatPlan& plan, double cspeed, double carrier, int64_t base)
 {
-    const uint32_t R = (uint32_t)c->res.n_recv;
-    if (R == 0) return RTS_OK;
-    const RtsCubeParams& q = c->cube.params;
     RtsBeatArgs a;
-    a.rays = c->d_rx_rays.p; a.delay = c->d_delay.p; a.phase = c->d_phase.p; a.pm = c->d_pathmatch.p; a.base = base;
-    a.R = R; a.part_len = plan.part_len; a.paths = p.source == RTS_RENDER_PATHS ? 1 : 0; a.doppler = (p.flags & RTS_RENDER_DOPPLER) ? 1 : 0;
+    a.src = rts_cube_source(c, p.source == RTS_RENDER_PATHS, cspeed, carrier, base);
+    if (a.src.R == 0) return RTS_OK;
+    const RtsCubeParams& q = c->cube.params;
+    a.part_len = plan.part_len; a.doppler = (p.flags & RTS_RENDER_DOPPLER) ? 1 : 0;
     a.cube = c->cube.p; a.n_pulses = q.n_pulses; a.n_bins = q.n_bins; a.pulse = pulse_index; a.t0 = q.t0; a.dt = q.dt;
-    a.cspeed = cspeed; a.carrier = carrier; a.S = p.slope; a.T = p.duration; a.scratch = nullptr;
+    a.S = p.slope; a.T = p.duration; a.scratch = nullptr;
     if (plan.scratch_doubles) { RTS_HIP(c->cube.d_beat_part.reserve(plan.scratch_doubles)); a.scratch = (double2*)c->cube.d_beat_part.p; }
     dim3 grid(plan.tiles, q.n_rx, plan.P);
     k_cube_beat<<<grid, RTS_BEAT_THREADS, 0, c->stream>>>(a, c->res.recv_dev);

@@ -22,6 +22,25 @@ static int rts_taps_check(const char* who, uint32_t taps)      // the interpolat
     return RTS_OK;
 }
 
+static int rts_pulse_index_check(const char* who, uint32_t pulse_index, uint32_t rows)      // the row an impulse writer or the waveform render adds to
+{
+    if (pulse_index >= rows) { rts_set_error("%s: pulse %u >= %u", who, pulse_index, rows); return RTS_ERR_INVALID; }
+    return RTS_OK;
+}
+
+// what a render reads and how (rts_cube_render's arguments, RtsBeatParams' fields); RTS_RENDER_PATHS reads the aggregation's results
+static int rts_render_source_check(const char* who, uint32_t source, uint32_t flags)
+{
+    if (source != RTS_RENDER_RAYS && source != RTS_RENDER_PATHS) { rts_set_error("%s: unknown source %u (RTS_RENDER_RAYS, RTS_RENDER_PATHS)", who, source); return RTS_ERR_INVALID; }
+    if (flags & ~RTS_RENDER_DOPPLER) { rts_set_error("%s: unknown flags 0x%x", who, flags); return RTS_ERR_INVALID; }
+    return RTS_OK;
+}
+static int rts_render_paths_check(const RtsContext* c, const char* who)
+{
+    if (!c->res.agg_valid) { rts_set_error("%s: RTS_RENDER_PATHS needs rts_aggregate of this pulse first (the groups' power, delay and phase are its results)", who); return RTS_ERR_INVALID; }
+    return RTS_OK;
+}
+
 // `doubles` doubles at src -> the host, once the stream has produced them; have: they exist (the cube, or a valid product: its RECORDED place and size); none: the message when not
 static int rts_cube_copy_out(RtsContext* c, const char* who, const char* none, bool have, const double* src, size_t doubles, double* host_out, uint64_t capacity_doubles)
 {
@@ -52,7 +71,7 @@ extern "C" int rts_cube_accumulate(RtsHandle c, uint32_t pulse_index, double csp
     CHECK_HANDLE(c);
     CHECK_CLOSED(c);
     NEED_CUBE(c, "rts_cube_accumulate", "call rts_cube_attach first");
-    if (pulse_index >= c->cube.params.n_pulses) { rts_set_error("rts_cube_accumulate: pulse %u >= %u", pulse_index, c->cube.params.n_pulses); return RTS_ERR_INVALID; }
+    { int rc = rts_pulse_index_check("rts_cube_accumulate", pulse_index, c->cube.params.n_pulses); if (rc != RTS_OK) return rc; }
     return rts_cube_accumulate_device(c, pulse_index, cspeed, carrier);
 }
 
@@ -62,7 +81,7 @@ extern "C" int rts_cube_accumulate_paths(RtsHandle c, uint32_t pulse_index)
     CHECK_CLOSED(c);
     NEED_CUBE(c, "rts_cube_accumulate_paths", "call rts_cube_attach first");
     if (!c->res.agg_valid) { rts_set_error("rts_cube_accumulate_paths: call rts_aggregate for this pulse first (the groups' power, delay and phase are its results)"); return RTS_ERR_INVALID; }
-    if (pulse_index >= c->cube.params.n_pulses) { rts_set_error("rts_cube_accumulate_paths: pulse %u >= %u", pulse_index, c->cube.params.n_pulses); return RTS_ERR_INVALID; }
+    { int rc = rts_pulse_index_check("rts_cube_accumulate_paths", pulse_index, c->cube.params.n_pulses); if (rc != RTS_OK) return rc; }
     return rts_cube_accumulate_paths_device(c, pulse_index, c->res.agg_base_local);
 }
 
@@ -130,14 +149,13 @@ extern "C" int rts_cube_set_waveform(RtsHandle c, const RtsWaveform* w)
 extern "C" int rts_cube_render(RtsHandle c, uint32_t pulse_index, uint32_t source, uint32_t flags, double cspeed, double carrier)
 {
     CHECK_HANDLE(c);
-    if (source != RTS_RENDER_RAYS && source != RTS_RENDER_PATHS) { rts_set_error("rts_cube_render: unknown source %u (RTS_RENDER_RAYS, RTS_RENDER_PATHS)", source); return RTS_ERR_INVALID; }
-    if (flags & ~RTS_RENDER_DOPPLER) { rts_set_error("rts_cube_render: unknown flags 0x%x", flags); return RTS_ERR_INVALID; }
+    { int rc = rts_render_source_check("rts_cube_render", source, flags); if (rc != RTS_OK) return rc; }
     CHECK_CLOSED(c);
     NEED_CUBE(c, "rts_cube_render", "call rts_cube_attach first");
     if (!c->cube.wave_set) { rts_set_error("rts_cube_render: no waveform (rts_cube_set_waveform)"); return RTS_ERR_INVALID; }
-    if (pulse_index >= c->cube.params.n_pulses) { rts_set_error("rts_cube_render: pulse %u >= %u", pulse_index, c->cube.params.n_pulses); return RTS_ERR_INVALID; }
+    { int rc = rts_pulse_index_check("rts_cube_render", pulse_index, c->cube.params.n_pulses); if (rc != RTS_OK) return rc; }
     const bool paths = source == RTS_RENDER_PATHS;
-    if (paths && !c->res.agg_valid) { rts_set_error("rts_cube_render: RTS_RENDER_PATHS needs rts_aggregate of this pulse first (the groups' power, delay and phase are its results)"); return RTS_ERR_INVALID; }
+    if (paths) { int rc = rts_render_paths_check(c, "rts_cube_render"); if (rc != RTS_OK) return rc; }
     return rts_cube_render_device(c, pulse_index, paths, (flags & RTS_RENDER_DOPPLER) != 0, cspeed, carrier, c->res.agg_base_local);
 }
 
@@ -410,8 +428,7 @@ static int rts_beat_check(const RtsBeatParams* p, const RtsCubeParams& q, uint32
     if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
     if (!std::isfinite(p->slope) || p->slope == 0.0) { rts_set_error("%s: slope = %g (finite, != 0)", who, p->slope); return RTS_ERR_INVALID; }
     if (!std::isfinite(p->duration) || !(p->duration > 0.0)) { rts_set_error("%s: duration = %g (finite, > 0)", who, p->duration); return RTS_ERR_INVALID; }
-    if (p->source != RTS_RENDER_RAYS && p->source != RTS_RENDER_PATHS) { rts_set_error("%s: unknown source %u (RTS_RENDER_RAYS, RTS_RENDER_PATHS)", who, p->source); return RTS_ERR_INVALID; }
-    if (p->flags & ~RTS_RENDER_DOPPLER) { rts_set_error("%s: unknown flags 0x%x", who, p->flags); return RTS_ERR_INVALID; }
+    { int rc = rts_render_source_check(who, p->source, p->flags); if (rc != RTS_OK) return rc; }
     if (p->reserved[0] || p->reserved[1]) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
     if (pulse_index >= q.n_pulses) { rts_set_error("%s: pulse_index = %u >= the cube's %u rows", who, pulse_index, q.n_pulses); return RTS_ERR_INVALID; }
     if (q.n_rx > RTS_BEAT_MAX_RX) { rts_set_error("%s: n_rx = %u receivers: more than %u (the launch grid)", who, q.n_rx, RTS_BEAT_MAX_RX); return RTS_ERR_INVALID; }
@@ -437,7 +454,7 @@ extern "C" int rts_cube_render_beat(RtsHandle c, uint32_t pulse_index, const Rts
     if (!paths && (!std::isfinite(cspeed) || !(cspeed > 0.0))) { rts_set_error("rts_cube_render_beat: cspeed = %g (finite, > 0, with RTS_RENDER_RAYS)", cspeed); return RTS_ERR_INVALID; }
     if (!paths && (!std::isfinite(carrier) || carrier < 0.0)) { rts_set_error("rts_cube_render_beat: carrier = %g (finite, >= 0, with RTS_RENDER_RAYS)", carrier); return RTS_ERR_INVALID; }
     CHECK_CLOSED(c);
-    if (paths && !c->res.agg_valid) { rts_set_error("rts_cube_render_beat: RTS_RENDER_PATHS needs rts_aggregate of this pulse first (the groups' power, delay and phase are its results)"); return RTS_ERR_INVALID; }
+    if (paths) { int rc = rts_render_paths_check(c, "rts_cube_render_beat"); if (rc != RTS_OK) return rc; }
     const RtsBeatPlan plan = rts_beat_plan(c->res.n_recv, c->cube.params.n_rx, c->cube.params.n_bins, c->cube.beat_force_parts);
     if (!plan.supported) { rts_set_error("rts_cube_render_beat: %llu received rays: more than the launch takes", (unsigned long long)c->res.n_recv); return RTS_ERR_INVALID; }
     return rts_cube_beat_device(c, pulse_index, *p, plan, cspeed, carrier, c->res.agg_base_local);

@@ -12,7 +12,8 @@
 #include "rts_waveform.h"
 #include "rts_noise.h"
 #include "rts_image.h"            // the arithmetic of a backprojected pixel and the host-only plan of its launch
-#include "rts_stft.h"             // the tree of the slow-time spectrogram and the host-only plan of its launch
+#include "rts_cube_source.h"      // what a received record brings to the cube: which counts, its delay, phase and amplitude, the cell and the add
+#include "rts_stft.h"             // the radix-2 tree of the slow-time and fast-time transforms and the host-only plans of the Doppler map's and the spectrogram's launches
 #include "rts_beat.h"             // the tree of the dechirped beat render, the range transform's evaluator and the host-only plans of their launches
 #include "rts_cfar_os.h"          // CFAR: what every detector shares (rts_cfar.h: window, training count, local maximum, refinement, record); OS: rank rule, alphas, the host evaluator
 #include "rts_owned.h"            // DevBuf, PinBuf, StagedUpload: device and pinned host memory that frees itself
@@ -306,8 +307,8 @@ struct RtsCubeProduct {
     void record(double* out, size_t n) { p = out; doubles = n; valid = true; }
 };
 
-// The cube part of a handle: it shares nothing with the pulse path but the handle (rts_cube_api.hip; the launchers of rts_post.hip,
-// rts_render.hip, rts_detect.hip, rts_image.hip, rts_stft.hip, rts_beat.hip).
+// The cube part of a handle: it shares nothing with the pulse path but the handle (rts_cube_api.hip; the launchers of rts_render.hip,
+// rts_stft.hip, rts_beat.hip, rts_detect.hip, rts_image.hip).
 struct RtsCubeState {
     RtsCubeParams params = {}; double* p = nullptr; DevBuf<double> own; bool set = false;      // p: the attached cube, own when the library allocated it
     DevBuf<double> d_wave; uint32_t wave_M = 0, wave_L = 0; bool wave_set = false;         // the transmit waveform (rts_cube_set_waveform): M interleaved samples, L taps
@@ -354,6 +355,12 @@ struct RtsPulseResults {
     // the previous results are gone: a new pulse begins (rts_trace_pulse_begin), or rts_kernel_wrapper_on overwrites the received set
     void forget() { agg_valid = false; agg_pending.valid = false; n_recv = 0; mirror.want = false; mirror.recv_valid = false; mirror.agg_valid = false; v_recv_have = 0; }
 };
+// What every kernel that takes recv_dev does first (R: the host's bound on the received count, which becomes the count).  Speculative
+// post-processing: the count is the trace kernel's, on the device.  More than the caller's capacity: nothing is to be done, and
+// `beyond` says how the kernel does nothing -- return, or what its barriers need.  A macro and not an inline function that returns
+// a flag: the compiler folds such a flag into the bounds test that follows, and the kernels behind the trace keep their
+// instructions (profiles/cube_source_refactor.txt).
+#define RTS_DEV_COUNT(R_dev, R, beyond) do { if (R_dev) { const unsigned long long v_ = *(R_dev); if (v_ > (unsigned long long)(R)) { beyond; } else (R) = (uint32_t)v_; } } while (0)
 
 struct RtsContext {
     RtsParams params;
@@ -453,6 +460,14 @@ struct RtsContext {
 // the (receiver, path) aggregation key of depth D among n_targets targets and n_rx receivers, and of the handle's own received sets
 static inline RtsKeyPlan rts_key_plan_for(uint32_t D, uint32_t n_targets, uint32_t n_rx) { return rts_key_plan(D, (int64_t)n_targets - 1, (int64_t)(n_rx ? n_rx : 1u) - 1); }
 static inline RtsKeyPlan rts_handle_key_plan(const RtsContext* c) { return rts_key_plan_for(c->depth, (uint32_t)c->scene->meshes.size(), c->n_rx); }
+// the received set of the handle's pulse as a cube writer reads it (rts_cube_source.h; base: RtsPulseResults::agg_base_local)
+static inline RtsCubeSource rts_cube_source(const RtsContext* c, bool paths, double cspeed, double carrier, int64_t base)
+{
+    RtsCubeSource s;
+    s.rays = c->d_rx_rays.p; s.delay = c->d_delay.p; s.phase = c->d_phase.p; s.pm = c->d_pathmatch.p; s.base = base;
+    s.R = (uint32_t)c->res.n_recv; s.paths = paths ? 1 : 0; s.cspeed = cspeed; s.carrier = carrier;
+    return s;
+}
 void rts_scene_unref(RtsScene* s);          // drop one reference; the last one deletes the object (and with it its buffers)
 void rts_hist_unref(RtsTileHist* h);
 void rts_gate_unref(RtsGate* g);            // ... and destroys the group's trace stream
@@ -473,15 +488,15 @@ int rts_post_mirror_aggregated(RtsContext* c);     // per-ray aggregation output
 int rts_post_set_values(RtsContext* c, const double* power, const double* doppler);      // power / Doppler of the received rays <- device-readable arrays (the mirror's values-in area)
 int rts_post_expand_all(RtsContext* c);
 int rts_post_all_small(RtsContext* c, uint32_t cap, const RtsSpecParams& sp, bool want_groups);      // the whole uniform post-processing of a small received set in ONE one-block kernel (count from the device)
-int rts_cube_accumulate_device(RtsContext* c, uint32_t pulse_index, double cspeed, double carrier);
+int rts_cube_accumulate_device(RtsContext* c, uint32_t pulse_index, double cspeed, double carrier);      // rts_render.hip: the writers of the cube, range compression
 int rts_cube_accumulate_paths_device(RtsContext* c, uint32_t pulse_index, int64_t base);
-int rts_cube_doppler_device(RtsContext* c, uint32_t n_fft, double* out);
-int rts_cube_render_device(RtsContext* c, uint32_t pulse_index, bool paths, bool doppler, double cspeed, double carrier, int64_t base);      // rts_render.hip
+int rts_cube_render_device(RtsContext* c, uint32_t pulse_index, bool paths, bool doppler, double cspeed, double carrier, int64_t base);
 int rts_cube_compress_device(RtsContext* c, uint32_t first_pulse, uint32_t n_pulses);
 int rts_cube_noise_device(RtsContext* c, uint32_t first_pulse, uint32_t n_pulses, double sigma, uint64_t seed);          // rts_detect.hip
 int rts_cube_detect_device(RtsContext* c, const RtsCfarParams& p, const double* map, uint32_t n_doppler, uint32_t max_det);
 int rts_cube_detect_os_device(RtsContext* c, const RtsCfarOsParams& p, const double* alpha_tab, const double* map, uint32_t n_doppler, uint32_t max_det);      // alpha_tab: device, by training count (pfa), or null (p.alpha)
-int rts_cube_stft_device(RtsContext* c, const RtsStftParams& p, const RtsStftPlan& plan, const double* window, double* out);      // rts_stft.hip
+int rts_cube_doppler_device(RtsContext* c, uint32_t n_fft, double* out);      // rts_stft.hip: the slow-time transforms
+int rts_cube_stft_device(RtsContext* c, const RtsStftParams& p, const RtsStftPlan& plan, const double* window, double* out);
 int rts_cube_beat_device(RtsContext* c, uint32_t pulse_index, const RtsBeatParams& p, const RtsBeatPlan& plan, double cspeed, double carrier, int64_t base);      // rts_beat.hip
 int rts_cube_range_device(RtsContext* c, const RtsRangeParams& p, const RtsRangePlan& plan, const double* window, double* out);
 int rts_cube_backproject_device(RtsContext* c, const RtsImageParams& p, const RtsImagePlan& plan, const double* geo, double* out);      // rts_image.hip

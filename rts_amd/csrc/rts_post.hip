@@ -125,7 +125,7 @@ __global__ void k_expand(const RtsTraceArgs a, const RtsEndRecord* __restrict__ 
                          PerRayData* __restrict__ rays, int32_t* __restrict__ paths, double* __restrict__ angles, uint64_t* __restrict__ slots, const unsigned long long* __restrict__ R_dev)
 {
     uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    { uint32_t R = n_out; if (R_dev) { const unsigned long long v_ = *R_dev; if (v_ > (unsigned long long)R) return; R = (uint32_t)v_; } n_out = R; }
+    RTS_DEV_COUNT(R_dev, n_out, return);
     if (j >= n_out) return;
     expand_row(a, rec, perm, j, D, rays, paths, angles, slots);
 }
@@ -493,7 +493,7 @@ int rts_post_order_and_expand(RtsContext* c)
 struct RtsMirrorSegs { uint32_t* dst[4]; const uint32_t* src[4]; uint32_t row_words[4]; };
 __global__ void __launch_bounds__(256) k_mirror_rows(const RtsMirrorSegs g, uint32_t R, const unsigned long long* __restrict__ R_dev)
 {
-    if (R_dev) { const unsigned long long v_ = *R_dev; if (v_ > (unsigned long long)R) return; R = (uint32_t)v_; }
+    RTS_DEV_COUNT(R_dev, R, return);
     const uint32_t k = blockIdx.y;
     const size_t n = (size_t)R * g.row_words[k];
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) g.dst[k][i] = g.src[k][i];
@@ -502,7 +502,7 @@ __global__ void k_mirror_agg(const PerRayData* __restrict__ rays, const double* 
                              double* __restrict__ h_power, double* __restrict__ h_doppler, double* __restrict__ h_delay, double* __restrict__ h_phase, int32_t* __restrict__ h_pm,
                              const unsigned long long* __restrict__ R_dev)
 {
-    if (R_dev) { const unsigned long long v_ = *R_dev; if (v_ > (unsigned long long)R) return; R = (uint32_t)v_; }
+    RTS_DEV_COUNT(R_dev, R, return);
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= R) return;
     h_power[i] = rays[i].power; h_doppler[i] = rays[i].doppler; h_delay[i] = delay[i]; h_phase[i] = phase[i]; h_pm[i] = pm[i];
@@ -604,7 +604,7 @@ __global__ void k_finalise(PerRayData* __restrict__ rays, const int32_t* __restr
                            const double* __restrict__ rcs, uint32_t n_targets, double wl, double gt, double gr, double carrier, double cspeed, const unsigned long long* __restrict__ R_dev)
 {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (R_dev) { const unsigned long long v_ = *R_dev; if (v_ > (unsigned long long)R) return; R = (uint32_t)v_; }      // (speculative post-processing: the count is the trace kernel's, on the device; more than the caller's capacity: nothing is done here)
+    RTS_DEV_COUNT(R_dev, R, return);
     if (i >= R) return;
     finalise_row(rays, paths, i, D, rcs, n_targets, wl, gt, gr, carrier, cspeed);
 }
@@ -681,7 +681,7 @@ __global__ void k_finalise_patterns(PerRayData* __restrict__ rays, const int32_t
                                     const RtsPatArgs a, const unsigned long long* __restrict__ R_dev)
 {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (R_dev) { const unsigned long long v_ = *R_dev; if (v_ > (unsigned long long)R) return; R = (uint32_t)v_; }      // (as k_finalise)
+    RTS_DEV_COUNT(R_dev, R, return);
     if (i >= R) return;
     finalise_row_patterns(rays, paths, angles, i, D, a);
 }
@@ -709,121 +709,6 @@ int rts_post_finalise_patterns(RtsContext* c, const RtsSpecParams& q)
     RtsPatArgs a;
     int rc = rts_pattern_pulse_upload(c, q, &a); if (rc != RTS_OK) return rc;
     k_finalise_patterns<<<blocks_for(R, 256), 256, 0, c->stream>>>(c->d_rx_rays.p, c->d_rx_paths.p, c->d_rx_angles.p, R, c->depth, a, c->res.recv_dev);
-    RTS_HIP(hipGetLastError());
-    return RTS_OK;
-}
-
-// --------------------------------------------------------------------------- complex return cube
-// one lane per received ray, two f64 atomics (global_atomic_add_f64) into cube[rx][pulse][bin]
-__device__ __forceinline__ void cube_row(const PerRayData* __restrict__ rays, const uint32_t i, double* __restrict__ cube, const uint32_t n_rx, const uint32_t n_pulses, const uint32_t n_bins,
-                                         const uint32_t pulse, const double t0, const double dt, const double cspeed, const double carrier)
-{
-    const PerRayData r = rays[i];
-    if (r.received < 0 || (uint32_t)r.received >= n_rx) return;
-    const double delay = (r.rayLength)/cspeed;                               // aggregation.cu:59
-    const double phase = -fmod(delay*2*RTS_PI*carrier, 2*RTS_PI);            // aggregation.cu:60
-    const double b = floor((delay - t0) / dt);
-    if (!(b >= 0.0) || !(b < (double)n_bins)) return;
-    const double amp = sqrt(r.power);
-    double sn, cs; sincos(phase, &sn, &cs);
-    double* cell = cube + 2 * (((size_t)r.received * n_pulses + pulse) * n_bins + (size_t)b);
-    atomicAdd(cell, amp * cs); atomicAdd(cell + 1, amp * sn);
-}
-__global__ void k_cube_accumulate(const PerRayData* __restrict__ rays, uint32_t R, double* __restrict__ cube, uint32_t n_rx, uint32_t n_pulses,
-                                  uint32_t n_bins, uint32_t pulse, double t0, double dt, double cspeed, double carrier, const unsigned long long* __restrict__ R_dev)
-{
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (R_dev) { const unsigned long long v_ = *R_dev; if (v_ > (unsigned long long)R) return; R = (uint32_t)v_; }      // (speculative post-processing: the count is the trace kernel's, on the device; more than the caller's capacity: nothing is done here)
-    if (i >= R) return;
-    cube_row(rays, i, cube, n_rx, n_pulses, n_bins, pulse, t0, dt, cspeed, carrier);
-}
-
-int rts_cube_accumulate_device(RtsContext* c, uint32_t pulse_index, double cspeed, double carrier)
-{
-    const uint32_t R = (uint32_t)c->res.n_recv;
-    if (R == 0) return RTS_OK;
-    const RtsCubeParams& q = c->cube.params;
-    k_cube_accumulate<<<blocks_for(R, 256), 256, 0, c->stream>>>(c->d_rx_rays.p, R, c->cube.p, q.n_rx, q.n_pulses, q.n_bins, pulse_index, q.t0, q.dt, cspeed, carrier, c->res.recv_dev);
-    RTS_HIP(hipGetLastError());
-    return RTS_OK;
-}
-
-// The same product PER UNIQUE PATH: one contribution per response the reference would emit for the pulse
-// (ray_tracer.cpp:1290-1321) -- the representative ray of every (receiver, path) group (pathMatch[i] == i) with the GROUP's
-// power ((sum sqrt p / n)^2), mean delay and mean phase (aggregation.cu:88-93).  Needs the aggregation of the pulse.
-__global__ void k_cube_accumulate_paths(const PerRayData* __restrict__ rays, const double* __restrict__ delay, const double* __restrict__ phase, const int32_t* __restrict__ pm,
-                                        uint32_t R, int64_t base, double* __restrict__ cube, uint32_t n_rx, uint32_t n_pulses, uint32_t n_bins, uint32_t pulse, double t0, double dt)
-{
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= R) return;
-    if ((int64_t)pm[i] != base + (int64_t)i) return;                          // not the representative of its group
-    const PerRayData r = rays[i];
-    if (r.received < 0 || (uint32_t)r.received >= n_rx) return;
-    const double b = floor((delay[i] - t0) / dt);
-    if (!(b >= 0.0) || !(b < (double)n_bins)) return;
-    const double amp = sqrt(r.power);
-    double sn, cs; sincos(phase[i], &sn, &cs);
-    double* cell = cube + 2 * (((size_t)r.received * n_pulses + pulse) * n_bins + (size_t)b);
-    atomicAdd(cell, amp * cs); atomicAdd(cell + 1, amp * sn);
-}
-
-int rts_cube_accumulate_paths_device(RtsContext* c, uint32_t pulse_index, int64_t base)
-{
-    const uint32_t R = (uint32_t)c->res.n_recv;
-    if (R == 0) return RTS_OK;
-    const RtsCubeParams& q = c->cube.params;
-    k_cube_accumulate_paths<<<blocks_for(R, 256), 256, 0, c->stream>>>(c->d_rx_rays.p, c->d_delay.p, c->d_phase.p, c->d_pathmatch.p, R, base, c->cube.p, q.n_rx, q.n_pulses, q.n_bins,
-                                                                        pulse_index, q.t0, q.dt);
-    RTS_HIP(hipGetLastError());
-    return RTS_OK;
-}
-
-// --------------------------------------------------------------------------- slow-time (Doppler) transform of the cube
-// out[rx][k][bin] = sum_{p < n_pulses} cube[rx][p][bin] e^{-2 pi j k p / N}, N a power of two >= n_pulses (zero padded).
-// One block per (receiver, tile of BT consecutive range bins): the tile's N x BT complex128 column set lives in LDS
-// (bit-reversed on the way in), log2 N radix-2 stages with a twiddle table in LDS, every stage's N/2 x BT butterflies dealt to
-// the block's threads; rows of BT x 16 bytes are contiguous in the cube, so loads and stores are BT-bin segments.  No MFMA: a
-// 1024-point f64 transform per (receiver, bin) is 5 120 butterflies; the whole C3 interval (4 x 1024 columns) is ~20 Mflop.
-__global__ void __launch_bounds__(256) k_cube_doppler(const double* __restrict__ cube, double* __restrict__ out, uint32_t n_pulses, uint32_t n_bins, uint32_t N, uint32_t logN, uint32_t BT)
-{
-    extern __shared__ __attribute__((aligned(16))) double s_fft[];               // [N][BT] complex, then [N/2] complex twiddles
-    double* x = s_fft; double* tw = s_fft + 2 * (size_t)N * BT;
-    const uint32_t rx = blockIdx.y, bin0 = blockIdx.x * BT, t = threadIdx.x;
-    for (uint32_t k = t; k < N / 2; k += blockDim.x) { double sn, cs; sincospi(-2.0 * (double)k / (double)N, &sn, &cs); tw[2 * k] = cs; tw[2 * k + 1] = sn; }
-    for (uint32_t idx = t; idx < N * BT; idx += blockDim.x) {
-        const uint32_t p = idx / BT, b = idx - p * BT, bin = bin0 + b;
-        double re = 0.0, im = 0.0;
-        if (p < n_pulses && bin < n_bins) { const double* src = cube + 2 * (((size_t)rx * n_pulses + p) * n_bins + bin); re = src[0]; im = src[1]; }
-        const uint32_t pr = __brev(p) >> (32u - logN);
-        x[2 * ((size_t)pr * BT + b)] = re; x[2 * ((size_t)pr * BT + b) + 1] = im;
-    }
-    __syncthreads();
-    for (uint32_t s = 1; s <= logN; s++) {
-        const uint32_t half = 1u << (s - 1), tstep = N >> s;
-        for (uint32_t idx = t; idx < (N / 2) * BT; idx += blockDim.x) {
-            const uint32_t j = idx / BT, b = idx - j * BT, k = j & (half - 1u), i0 = ((j >> (s - 1)) << s) + k, i1 = i0 + half;
-            const double wr = tw[2 * (k * tstep)], wi = tw[2 * (k * tstep) + 1];
-            double* a0 = x + 2 * ((size_t)i0 * BT + b); double* a1 = x + 2 * ((size_t)i1 * BT + b);
-            const double xr = a1[0], xi = a1[1], tr = wr * xr - wi * xi, ti = wr * xi + wi * xr, ur = a0[0], ui = a0[1];
-            a0[0] = ur + tr; a0[1] = ui + ti; a1[0] = ur - tr; a1[1] = ui - ti;
-        }
-        __syncthreads();
-    }
-    for (uint32_t idx = t; idx < N * BT; idx += blockDim.x) {
-        const uint32_t k = idx / BT, b = idx - k * BT, bin = bin0 + b;
-        if (bin < n_bins) { double* dst = out + 2 * (((size_t)rx * N + k) * n_bins + bin); dst[0] = x[2 * ((size_t)k * BT + b)]; dst[1] = x[2 * ((size_t)k * BT + b) + 1]; }
-    }
-}
-
-int rts_cube_doppler_device(RtsContext* c, uint32_t n_fft, double* out)
-{
-    const RtsCubeParams& q = c->cube.params;
-    uint32_t logN = 0; while ((1u << logN) < n_fft) logN++;
-    uint32_t BT = 8; while (BT > 1 && (size_t)n_fft * BT * 16 > 65536) BT >>= 1;
-    const size_t lds = (size_t)n_fft * BT * 16 + (size_t)n_fft * 8;
-    RTS_HIP(hipFuncSetAttribute((const void*)k_cube_doppler, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    dim3 grid((q.n_bins + BT - 1) / BT, q.n_rx);
-    k_cube_doppler<<<grid, 256, lds, c->stream>>>(c->cube.p, out, q.n_pulses, q.n_bins, n_fft, logN, BT);
     RTS_HIP(hipGetLastError());
     return RTS_OK;
 }
@@ -955,7 +840,7 @@ __global__ void __launch_bounds__(AGG_TILE) k_agg_tiles(const PerRayData* __rest
         const uint32_t* __restrict__ gid_incl, const uint32_t* __restrict__ gstart, uint32_t R, double cspeed, double carrier,
         double* __restrict__ gsum, double* __restrict__ tile_first, double* __restrict__ tile_last, const unsigned long long* __restrict__ R_dev)
 {
-    if (R_dev) { const unsigned long long v_ = *R_dev; if (v_ > (unsigned long long)R) return; R = (uint32_t)v_; }      // (speculative post-processing: the count is the trace kernel's, on the device; more than the caller's capacity: nothing is done here)
+    RTS_DEV_COUNT(R_dev, R, return);
     __shared__ __attribute__((aligned(16))) unsigned char s_raw[RTS_AGG_TILE_LDS];
     agg_tile_block(s_raw, blockIdx.x, rays, idx_sorted, gid_incl, gstart, R, cspeed, carrier, gsum, tile_first, tile_last);
 }
@@ -1121,7 +1006,7 @@ template <typename K, int ITEMS>
 __global__ void __launch_bounds__(RTS_SMALL_THREADS) k_recv_order_small(const RtsEndRecord* __restrict__ rec, uint32_t n, uint32_t n_rays, int with_chain, uint32_t bits, uint32_t* __restrict__ perm, const unsigned long long* __restrict__ R_dev)
 {
     typedef rocprim::block_radix_sort<K, RTS_SMALL_THREADS, ITEMS, uint32_t> Sort;
-    { uint32_t R = n; bool skip = false; if (R_dev) { const unsigned long long v_ = *R_dev; if (v_ > (unsigned long long)R) skip = true; else R = (uint32_t)v_; } if (skip) return; n = R; }
+    { uint32_t R = n; bool skip = false; RTS_DEV_COUNT(R_dev, R, skip = true); if (skip) return; n = R; }
     __shared__ __attribute__((aligned(16))) unsigned char s_raw[sizeof(typename Sort::storage_type)];
     recv_order_block<K, ITEMS>(s_raw, rec, n, n_rays, with_chain, bits, perm);
 }
@@ -1186,7 +1071,7 @@ __global__ void __launch_bounds__(RTS_SMALL_THREADS) k_agg_order_small(const Per
                                                                        uint64_t* __restrict__ keys_sorted, uint32_t* __restrict__ idx_sorted, uint32_t* __restrict__ head,
                                                                        uint32_t* __restrict__ gid_incl, uint32_t* __restrict__ gstart, const unsigned long long* __restrict__ R_dev)
 {
-    if (R_dev) { const unsigned long long v_ = *R_dev; if (v_ > (unsigned long long)R) return; R = (uint32_t)v_; }      // (speculative post-processing: the count is the trace kernel's, on the device; more than the caller's capacity: nothing is done here)
+    RTS_DEV_COUNT(R_dev, R, return);
     __shared__ __attribute__((aligned(16))) unsigned char s_raw[sizeof(RtsAggOrderLds<K, ITEMS>)];
     agg_order_block<K, ITEMS>(s_raw, rays, paths, R, D, B, key_bits, keys_sorted, idx_sorted, head, gid_incl, gstart);
 }
@@ -1216,10 +1101,9 @@ __device__ __forceinline__ void agg_finish_block(const RtsAggFinish& q, const ui
 __global__ void __launch_bounds__(256) k_agg_finish_small(const RtsAggFinish q, uint32_t R, uint32_t ntiles, const unsigned long long* __restrict__ R_dev)
 {
     uint32_t spec = q.spec;
-    if (R_dev) {
-        const unsigned long long v_ = *R_dev;
-        if (v_ > (unsigned long long)R) return;
-        R = (uint32_t)v_; ntiles = (R + AGG_TILE - 1) / AGG_TILE; spec = min(spec, R);
+    if (R_dev) {                                 // (and what the host derived from its bound, from the count)
+        RTS_DEV_COUNT(R_dev, R, return);
+        ntiles = (R + AGG_TILE - 1) / AGG_TILE; spec = min(spec, R);
         if (R == 0u) { if (q.h_G && threadIdx.x == 0) *q.h_G = 0u; return; }
     }
     agg_finish_block(q, R, ntiles, spec);
@@ -1272,10 +1156,11 @@ __global__ void __launch_bounds__(RTS_SMALL_THREADS) k_post_all(const RtsPostAll
     else recv_order_block<KR, RtsSortMax<KR>::ITEMS>(s_raw, q.rec, R, q.n_rays, q.with_chain, q.bits, q.perm);
     __syncthreads();
     // ---- the reference's output records, the uniform finalisation, the return cube: row by row
+    const RtsCubeSource src = {q.rays, nullptr, nullptr, nullptr, 0, R, 0, q.cspeed, q.carrier};      // the set as k_cube_accumulate reads it (rts_render.hip)
     for (uint32_t j = threadIdx.x; j < R; j += RTS_SMALL_THREADS) {
         expand_row(q.ta, q.rec, q.perm, j, q.D, q.rays, q.paths, q.angles, q.slots);
         fin(q, j);
-        if (q.cube_on) cube_row(q.rays, j, q.cube, q.cube_rx, q.cube_pulses, q.cube_bins, q.cube_pulse, q.cube_t0, q.cube_dt, q.cspeed, q.carrier);
+        if (q.cube_on) rts_cube_impulse_row<false>(src, j, q.cube, q.cube_rx, q.cube_pulses, q.cube_bins, q.cube_pulse, q.cube_t0, q.cube_dt);
     }
     __syncthreads();
     // ---- aggregation: order, tile sums, finish

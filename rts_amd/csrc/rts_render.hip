@@ -1,8 +1,35 @@
-// rts_render.hip -- the received signal on the device (include/rts_amd.h: RtsWaveform):
-//   * the render of a pulse's contributions with the handle's transmit waveform into the return cube (k_cube_render)
+// rts_render.hip -- the writers of the cube: impulse, waveform render; range compression (include/rts_amd.h: RtsCubeParams, RtsWaveform):
+//   * a pulse's contributions as impulses into the return cube, per received ray or per unique path (k_cube_accumulate)
+//   * their render with the handle's transmit waveform (k_cube_render)
 //   * range compression (matched filter) of the cube's rows in place (k_cube_compress)
+// What a received record contributes, the cell and the add are rts_cube_source.h, shared with the beat render (rts_beat.hip).
 #include <hip/hip_runtime.h>
 #include "rts_internal.h"
+
+// --------------------------------------------------------------------------- impulse cube
+// one lane per received record, two f64 atomics into cube[rx][pulse][bin].  PATHS: per unique path, which needs the aggregation of
+// the pulse (RtsCubeSource).  The fused end-of-pulse kernel (rts_post.hip: k_post_all) runs the same row.
+template <bool PATHS>
+__global__ void k_cube_accumulate(const RtsCubeSource s, double* __restrict__ cube, uint32_t n_rx, uint32_t n_pulses, uint32_t n_bins, uint32_t pulse, double t0, double dt,
+                                  const unsigned long long* __restrict__ R_dev)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t R = s.R;
+    RTS_DEV_COUNT(R_dev, R, return);
+    if (i >= R) return;
+    rts_cube_impulse_row<PATHS>(s, i, cube, n_rx, n_pulses, n_bins, pulse, t0, dt);
+}
+
+template <bool PATHS> static int rts_cube_accumulate_launch(RtsContext* c, const RtsCubeSource& s, uint32_t pulse_index)
+{
+    if (s.R == 0) return RTS_OK;
+    const RtsCubeParams& q = c->cube.params;
+    k_cube_accumulate<PATHS><<<(unsigned)(((size_t)s.R + 255) / 256), 256, 0, c->stream>>>(s, c->cube.p, q.n_rx, q.n_pulses, q.n_bins, pulse_index, q.t0, q.dt, c->res.recv_dev);
+    RTS_HIP(hipGetLastError());
+    return RTS_OK;
+}
+int rts_cube_accumulate_device(RtsContext* c, uint32_t pulse_index, double cspeed, double carrier) { return rts_cube_accumulate_launch<false>(c, rts_cube_source(c, false, cspeed, carrier, 0), pulse_index); }
+int rts_cube_accumulate_paths_device(RtsContext* c, uint32_t pulse_index, int64_t base) { return rts_cube_accumulate_launch<true>(c, rts_cube_source(c, true, 0.0, 0.0, base), pulse_index); }
 
 // --------------------------------------------------------------------------- render (a gather)
 // One block per (receiver, tile of RTS_RENDER_TILE output samples); thread t owns output sample n = tile start + t.  The waveform
@@ -14,9 +41,8 @@
 #define RTS_RENDER_TILE 128
 #define RTS_RENDER_SUB 32
 struct RtsRenderArgs {
-    const PerRayData* rays; const double* delay; const double* phase; const int32_t* pm; int64_t base;
-    uint32_t R; int paths, doppler;
-    double* cube; uint32_t n_rx, n_pulses, n_bins, pulse; double t0, dt, cspeed, carrier;
+    RtsCubeSource src; int doppler;
+    double* cube; uint32_t n_rx, n_pulses, n_bins, pulse; double t0, dt;
     const double* wave; uint32_t M, L;
 };
 struct RtsRenderItem { double are, aim, phi, d, f; int D; int pad; };
@@ -34,8 +60,8 @@ __global__ void __launch_bounds__(RTS_RENDER_TILE) k_cube_render(const RtsRender
     const double n0 = (double)(blockIdx.x * RTS_RENDER_TILE);
     const double n1 = fmin(n0 + (double)(RTS_RENDER_TILE - 1), (double)a.n_bins - 1.0);       // last sample of the tile
     const double reach = (double)q0 + (double)(L - 1u) + (double)(M - 1u);                        // support of a start D: [D + q0, D + reach]
-    uint32_t R = a.R;
-    if (R_dev) { const unsigned long long v_ = *R_dev; if (v_ > (unsigned long long)R) return; R = (uint32_t)v_; }      // (as k_cube_accumulate)
+    uint32_t R = a.src.R;
+    RTS_DEV_COUNT(R_dev, R, return);
     for (uint32_t i = t; i < 2 * M; i += RTS_RENDER_TILE) sw[i] = a.wave[i];
     double acc_r = 0.0, acc_i = 0.0;
     for (uint32_t c0 = 0; c0 < R; c0 += RTS_RENDER_TILE) {
@@ -43,18 +69,14 @@ __global__ void __launch_bounds__(RTS_RENDER_TILE) k_cube_render(const RtsRender
         const uint32_t i = c0 + t;
         bool keep = false; RtsRenderItem it;
         if (i < R) {
-            const PerRayData& r = a.rays[i];
-            const int32_t rcv = r.received;
-            if (rcv == (int32_t)rx && (!a.paths || (int64_t)a.pm[i] == a.base + (int64_t)i)) {
-                double delay, phase;
-                if (a.paths) { delay = a.delay[i]; phase = a.phase[i]; }
-                else { delay = (r.rayLength)/a.cspeed; phase = -fmod(delay*2*RTS_PI*a.carrier, 2*RTS_PI); }      // aggregation.cu:59-60, as cube_row
+            if (rts_cube_counts_for(a.src, a.src.paths != 0, i, (int32_t)rx)) {
+                double delay, phase; rts_cube_timing(a.src, a.src.paths != 0, i, &delay, &phase);
                 const double d = (delay - a.t0) / a.dt;
                 const double Df = floor(d);
                 if (Df + (double)q0 <= n1 && Df + reach >= n0) {          // (false for a non-finite start)
-                    const double amp = sqrt(r.power);
-                    double sn, cs; sincos(phase, &sn, &cs);
-                    it.are = amp * cs; it.aim = amp * sn; it.phi = d - Df; it.d = d; it.f = r.doppler; it.D = (int)Df; it.pad = 0;
+                    const PerRayData& r = a.src.rays[i];
+                    rts_cube_amplitude(r.power, phase, &it.are, &it.aim);
+                    it.phi = d - Df; it.d = d; it.f = r.doppler; it.D = (int)Df; it.pad = 0;
                     keep = true;
                 }
             }
@@ -95,22 +117,17 @@ __global__ void __launch_bounds__(RTS_RENDER_TILE) k_cube_render(const RtsRender
             __syncthreads();
         }
     }
-    if ((uint32_t)n < a.n_bins && (acc_r != 0.0 || acc_i != 0.0)) {
-        double* cell = a.cube + 2 * (((size_t)rx * a.n_pulses + a.pulse) * a.n_bins + (size_t)n);
-        atomicAdd(cell, acc_r); atomicAdd(cell + 1, acc_i);
-    }
+    if ((uint32_t)n < a.n_bins && (acc_r != 0.0 || acc_i != 0.0)) rts_cube_add(rts_cube_cell(a.cube, a.n_pulses, a.n_bins, rx, a.pulse, n), acc_r, acc_i);
 }
 
 int rts_cube_render_device(RtsContext* c, uint32_t pulse_index, bool paths, bool doppler, double cspeed, double carrier, int64_t base)
 {
-    const uint32_t R = (uint32_t)c->res.n_recv;
-    if (R == 0) return RTS_OK;
-    const RtsCubeParams& q = c->cube.params;
     RtsRenderArgs a;
-    a.rays = c->d_rx_rays.p; a.delay = c->d_delay.p; a.phase = c->d_phase.p; a.pm = c->d_pathmatch.p; a.base = base;
-    a.R = R; a.paths = paths ? 1 : 0; a.doppler = doppler ? 1 : 0;
+    a.src = rts_cube_source(c, paths, cspeed, carrier, base); a.doppler = doppler ? 1 : 0;
+    if (a.src.R == 0) return RTS_OK;
+    const RtsCubeParams& q = c->cube.params;
     a.cube = c->cube.p; a.n_rx = q.n_rx; a.n_pulses = q.n_pulses; a.n_bins = q.n_bins; a.pulse = pulse_index; a.t0 = q.t0; a.dt = q.dt;
-    a.cspeed = cspeed; a.carrier = carrier; a.wave = c->cube.d_wave.p; a.M = c->cube.wave_M; a.L = c->cube.wave_L;
+    a.wave = c->cube.d_wave.p; a.M = c->cube.wave_M; a.L = c->cube.wave_L;
     const size_t lds = sizeof(double) * (2 * (size_t)a.M + (size_t)RTS_RENDER_SUB * a.L);      // <= 64 KiB + 16 KiB
     RTS_HIP(hipFuncSetAttribute((const void*)k_cube_render, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     dim3 grid((q.n_bins + RTS_RENDER_TILE - 1) / RTS_RENDER_TILE, q.n_rx);

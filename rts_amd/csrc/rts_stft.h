@@ -1,8 +1,9 @@
-// rts_stft.h -- the tapered slow-time spectrogram of the return cube (include/rts_amd.h: RtsStftParams): the transform's tree, shared
-// by the kernel (rts_stft.hip: k_cube_stft) and the host evaluator (rts_stft_eval), the host-only plan of the launch and the windows.
-// The tree is k_cube_doppler's (rts_post.hip): bit-reversed load, log2 N radix-2 decimation-in-time stages, twiddles from one
-// sincospi(-2 k / N) each.  Fixed trees of IEEE basic operations, compiled with -ffp-contract=off.  Includes nothing of HIP: it
-// compiles with any host compiler and is tested without a GPU (tests/test_stft_host.py, tests/stft/stft_main.cpp).
+// rts_stft.h -- the slow-time transforms of the return cube: the radix-2 tree every transform of the library runs -- bit-reversed
+// load, log2 N decimation-in-time stages, twiddles from one sincospi(-2 k / N) each -- shared by the kernels (rts_stft.hip:
+// k_cube_doppler, k_cube_stft; rts_beat.hip: k_cube_range) and the host evaluators (rts_stft_eval, rts_range_eval); the host-only
+// plans of the Doppler map's and the spectrogram's launches (include/rts_amd.h: rts_cube_doppler, RtsStftParams) and the windows.
+// Fixed trees of IEEE basic operations, compiled with -ffp-contract=off.  Includes nothing of HIP: it compiles with any host
+// compiler and is tested without a GPU (tests/test_stft_host.py, tests/stft/stft_main.cpp; tests/test_cube_source_host.py).
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -62,18 +63,35 @@ RTS_HD void rts_stft_taper(double w, double* re, double* im) { *re = w * *re; *i
 
 RTS_HD double rts_stft_power(double re, double im) { return re * re + im * im; }
 
-// ---- the plan of a launch (host only).  One workgroup per (receiver, frame, tile of gate bins); its LDS holds the tile's N x BT
+// ---- the plans of the launches (host only).  log2 of a transform's size: the least logN <= 31 with 2^logN >= n_fft
+static inline uint32_t rts_stft_log2(uint32_t n_fft) { uint32_t logN = 0; while (logN < 31u && (1u << logN) < n_fft) logN++; return logN; }
+static inline size_t rts_stft_lds_bytes(uint32_t n_fft, uint32_t BT) { return (size_t)n_fft * BT * 16u + (size_t)n_fft * 8u; }
+
+// The Doppler map (rts_cube_doppler: every pulse of the cube, no frames, gate or taper).  One workgroup per (receiver, tile of BT
+// consecutive range bins); BT: the most columns, a power of two up to RTS_DOPPLER_BIN_TILE, whose N x BT complex128 fit 64 KiB.
+#define RTS_DOPPLER_BIN_TILE 8u
+#define RTS_DOPPLER_TILE_BYTES 65536u
+struct RtsDopplerPlan { uint32_t logN, BT; size_t lds; };
+static inline RtsDopplerPlan rts_doppler_plan(uint32_t n_fft)
+{
+    RtsDopplerPlan p;
+    p.logN = rts_stft_log2(n_fft);
+    p.BT = RTS_DOPPLER_BIN_TILE; while (p.BT > 1u && (size_t)n_fft * p.BT * 16u > RTS_DOPPLER_TILE_BYTES) p.BT >>= 1;
+    p.lds = rts_stft_lds_bytes(n_fft, p.BT);
+    return p;
+}
+
+// The spectrogram.  One workgroup per (receiver, frame, tile of gate bins); its LDS holds the tile's N x BT
 // complex128 columns and the N / 2 complex twiddles.  BT: the most columns, a power of two up to RTS_STFT_BIN_TILE, that fit the
 // 160 KiB a workgroup may allocate.  A workgroup takes BT gate bins; with RTS_STFT_SUM_BINS it takes a whole summation tile of
 // RTS_STFT_BIN_TILE bins in RTS_STFT_BIN_TILE / BT passes.  The grid is (n_frames * tiles, n_rx).
 #define RTS_STFT_LDS_MAX 163840u
 #define RTS_STFT_THREADS 256u
 struct RtsStftPlan { uint32_t logN, BT, passes, tiles, n_frames, n_gate; size_t lds, out_doubles, partial_doubles; bool supported; };
-static inline size_t rts_stft_lds_bytes(uint32_t n_fft, uint32_t BT) { return (size_t)n_fft * BT * 16u + (size_t)n_fft * 8u; }
 static inline RtsStftPlan rts_stft_plan(uint32_t n_rx, uint32_t n_pulses, uint32_t window_len, uint32_t hop, uint32_t n_fft, uint32_t n_gate, uint32_t flags)
 {
     RtsStftPlan p;
-    p.logN = 0; while (p.logN < 31u && (1u << p.logN) < n_fft) p.logN++;
+    p.logN = rts_stft_log2(n_fft);
     p.BT = RTS_STFT_BIN_TILE; while (p.BT > 1u && rts_stft_lds_bytes(n_fft, p.BT) > RTS_STFT_LDS_MAX) p.BT >>= 1;
     p.lds = rts_stft_lds_bytes(n_fft, p.BT);
     const bool sum = (flags & RTS_STFT_SUM_BINS) != 0;

@@ -1,18 +1,66 @@
-// rts_stft.hip -- the tapered slow-time spectrogram of the return cube on the device (include/rts_amd.h: rts_cube_spectrogram).
-// f64 butterflies in LDS, no MFMA: one workgroup per (receiver, frame, tile of gate bins) holds the tile's N x BT complex128
-// columns and the twiddle table in LDS (rts_stft.h: rts_stft_plan chooses BT from the 160 KiB a workgroup may allocate); the tree
-// is rts_stft.h, shared with the host evaluator and bit-identical to k_cube_doppler's (rts_post.hip).
+// rts_stft.hip -- the slow-time transforms of the return cube on the device (include/rts_amd.h: rts_cube_doppler, rts_cube_spectrogram):
+//   * the Doppler map: every pulse of a range bin, zero padded (k_cube_doppler)
+//   * the tapered spectrogram: frames of a gate of bins (k_cube_stft, k_stft_sum_tiles)
+// f64 butterflies in LDS, no MFMA: a workgroup holds a tile's N x BT complex128 columns and the twiddle table in LDS; the tree and
+// the plans of the launches are rts_stft.h, shared with the host evaluators, so the two kernels' bins agree bit for bit.
 //
-// LDS layout: column set x[row][b], 16-byte elements, row stride BT (no padding: at n_fft 4096 the two columns and the table fill
-// the 160 KiB exactly).  A thread owns element idx = row * BT + b with b fastest, so the load, every stage with 2^(s-1) * BT >= 16
-// and the store touch runs of at least 16 consecutive 16-byte elements per 16 lanes: conflict-free for the 128-bit LDS accesses,
-// whose 16-lane groups cover 256 contiguous bytes.  Stage 1 at BT = 8 (and the first 4 - log2 BT stages below that) alternates
-// BT-element runs of rows i0 and skips those of i1, which lands two runs of a lane group on the same banks (2-way); that is one
-// stage of log2 N.
+// LDS layout: column set x[row][b], 16-byte elements, row stride BT (no padding: at n_fft 4096 the spectrogram's two columns and the
+// table fill the 160 KiB exactly).  A thread owns element idx = row * BT + b with b fastest, so the load, every stage with
+// 2^(s-1) * BT >= 16 and the store touch runs of at least 16 consecutive 16-byte elements per 16 lanes: conflict-free for the 128-bit
+// LDS accesses, whose 16-lane groups cover 256 contiguous bytes.  Stage 1 at BT = 8 (and the first 4 - log2 BT stages below that)
+// alternates BT-element runs of rows i0 and skips those of i1, which lands two runs of a lane group on the same banks (2-way); that
+// is one stage of log2 N.
 #include <hip/hip_runtime.h>
 #include "rts_internal.h"
 #include "rts_stft.h"
 
+// --------------------------------------------------------------------------- the Doppler map
+// out[rx][k][bin] = sum_{p < n_pulses} cube[rx][p][bin] e^{-2 pi j k p / N}, N a power of two >= n_pulses (zero padded).
+// One block per (receiver, tile of BT consecutive range bins; rts_stft.h: rts_doppler_plan): every stage's N/2 x BT butterflies are
+// dealt to the block's threads; rows of BT x 16 bytes are contiguous in the cube, so loads and stores are BT-bin segments.  A
+// 1024-point f64 transform per (receiver, bin) is 5 120 butterflies; the whole C3 interval (4 x 1024 columns) is ~20 Mflop.
+__global__ void __launch_bounds__(256) k_cube_doppler(const double* __restrict__ cube, double* __restrict__ out, uint32_t n_pulses, uint32_t n_bins, uint32_t N, uint32_t logN, uint32_t BT)
+{
+    extern __shared__ __attribute__((aligned(16))) double s_fft[];               // [N][BT] complex, then [N/2] complex twiddles
+    double* x = s_fft; double* tw = s_fft + 2 * (size_t)N * BT;
+    const uint32_t rx = blockIdx.y, bin0 = blockIdx.x * BT, t = threadIdx.x;
+    for (uint32_t k = t; k < N / 2; k += blockDim.x) rts_stft_twiddle(k, N, &tw[2 * k], &tw[2 * k + 1]);
+    for (uint32_t idx = t; idx < N * BT; idx += blockDim.x) {
+        const uint32_t p = idx / BT, b = idx - p * BT, bin = bin0 + b;
+        double re = 0.0, im = 0.0;
+        if (p < n_pulses && bin < n_bins) { const double* src = cube + 2 * (((size_t)rx * n_pulses + p) * n_bins + bin); re = src[0]; im = src[1]; }
+        const uint32_t pr = rts_stft_bitrev(p, logN);
+        x[2 * ((size_t)pr * BT + b)] = re; x[2 * ((size_t)pr * BT + b) + 1] = im;
+    }
+    __syncthreads();
+    for (uint32_t s = 1; s <= logN; s++) {
+        for (uint32_t idx = t; idx < (N / 2) * BT; idx += blockDim.x) {
+            const uint32_t j = idx / BT, b = idx - j * BT;
+            __builtin_assume(j < 0x80000000u);       // (j < N / 2.  Said because the compiler bounds rts_stft_pair's j by its callers in this unit, and k_cube_stft's j has this bound)
+            uint32_t i0, i1, k; rts_stft_pair(j, s, N, &i0, &i1, &k);
+            double* a0 = x + 2 * ((size_t)i0 * BT + b); double* a1 = x + 2 * ((size_t)i1 * BT + b);
+            rts_stft_butterfly(tw[2 * k], tw[2 * k + 1], &a0[0], &a0[1], &a1[0], &a1[1]);
+        }
+        __syncthreads();
+    }
+    for (uint32_t idx = t; idx < N * BT; idx += blockDim.x) {
+        const uint32_t k = idx / BT, b = idx - k * BT, bin = bin0 + b;
+        if (bin < n_bins) { double* dst = out + 2 * (((size_t)rx * N + k) * n_bins + bin); dst[0] = x[2 * ((size_t)k * BT + b)]; dst[1] = x[2 * ((size_t)k * BT + b) + 1]; }
+    }
+}
+
+int rts_cube_doppler_device(RtsContext* c, uint32_t n_fft, double* out)
+{
+    const RtsCubeParams& q = c->cube.params;
+    const RtsDopplerPlan plan = rts_doppler_plan(n_fft);
+    RTS_HIP(hipFuncSetAttribute((const void*)k_cube_doppler, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
+    dim3 grid((q.n_bins + plan.BT - 1) / plan.BT, q.n_rx);
+    k_cube_doppler<<<grid, 256, plan.lds, c->stream>>>(c->cube.p, out, q.n_pulses, q.n_bins, n_fft, plan.logN, plan.BT);
+    RTS_HIP(hipGetLastError());
+    return RTS_OK;
+}
+
+// --------------------------------------------------------------------------- the spectrogram
 // a workgroup's N x BT elements dealt to its threads: at most 8192 / 256 each (rts_stft_plan: 1024 x 8, 2048 x 4, 4096 x 2) --
 // N x BT is a power of two and its 16-byte elements fit the LDS beside the table, so it is below twice this many per thread
 #define RTS_STFT_SUM_ITERS 32u
