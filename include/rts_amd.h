@@ -753,6 +753,82 @@ int rts_cube_range_transform(RtsHandle h, const RtsRangeParams* p, void* device_
 int rts_cube_range_get(RtsHandle h, double* host_out, uint64_t capacity_doubles);
 int rts_range_eval(const RtsCubeParams* q, const double* cube, const RtsRangeParams* p, double* out);  /* pure host */
 
+/* ---------------------------------------------------------------- receive-array beamforming across the cube's receivers
+ * The third axis of the cube.  Every other product treats the receiver index as a loop index; this one combines the receivers of a
+ * coherent cube into beams: the angle of a detection, and the array gain that makes a weak target detectable at all.  The arithmetic
+ * is rts_amd/csrc/rts_beam.h, shared by the kernel (rts_beam.hip) and the host evaluator (the library builds with
+ * -ffp-contract=off: the tree is the contract).  It holds no transcendental, so device and evaluator agree BIT FOR BIT.
+ *   Input z[rx][row][bin], complex128; n_rx and n_bins are the attached cube's (a cube must be attached for every source):
+ *     RTS_BEAM_FROM_CUBE     the attached cube, n_pulses rows;
+ *     RTS_BEAM_FROM_MAP      the handle's last library-owned rts_cube_doppler map, n_fft rows;
+ *     RTS_BEAM_FROM_POINTER  device_in, caller-owned device memory [n_rx][n_rows_in][n_bins], 16-byte aligned.
+ *   Rows first_row .. first_row + n_rows - 1 of every receiver are read (n_rows 0: from first_row to the source's last row).
+ *   Weights w[beam][rx], complex128 (interleaved re / im), on the host; the call copies them, kernel and evaluator multiply by the
+ *   same bits.
+ *     term(b, rx)    = conj(w[b][rx]) z[rx][row][bin] = (wr zr + wi zi, wr zi - wi zr)     four multiplies, one add, one subtract
+ *     y[b][row][bin] = the sum of term(b, rx) over ascending rx; the rx = 0 term is the start value.
+ *   Output, row-major:
+ *     default          complex128 [n_beams][n_rows][n_bins]: the layout of a cube with n_rx = n_beams, which another handle attaches
+ *                      (rts_cube_attach with device_ptr) to run rts_cube_doppler / rts_cube_detect* / rts_cube_spectrogram on beams;
+ *     RTS_BEAM_POWER   f64 re re + im im, the same shape;
+ *     RTS_BEAM_PEAK    f64 [n_rows][n_bins][2] = (P*, coordinate) and no per-beam output (it excludes RTS_BEAM_POWER): P* the
+ *                      largest beam power of the cell, b* the LOWEST beam index that attains it,
+ *                      coordinate = (double)b* + the log-parabola offset of the detection records (RtsDetection's range_offset rule)
+ *                      through P[b* - 1], P[b*], P[b* + 1]; the offset is 0 when b* is the first or the last beam (the beam axis
+ *                      does not wrap).  With a NaN among a cell's powers the reported beam is unspecified; nothing is read out of
+ *                      bounds.
+ *   No atomics: every output element is one plain store, bit-identical from run to run.
+ *   device_out: caller-owned device memory of the output's size, 16-byte aligned, or NULL: library-owned, alive until the next
+ *     beamform of another size, rts_cube_attach or rts_destroy.  rts_cube_beam_get synchronises and copies the library-owned
+ *     output; RTS_ERR_INVALID after an rts_cube_attach or with no library-owned output, RTS_ERR_CAPACITY when capacity_doubles is
+ *     too small.  The call is enqueued on the handle's stream and never waits for the device's earlier work (only for the copy of
+ *     the PREVIOUS call's weights out of the handle's pinned staging block); the caller's weight array is free on return.
+ *   RTS_ERR_INVALID, the message naming the field: no cube attached; NULL p or NULL weights; nonzero reserved fields; an unknown
+ *   source or flags; RTS_BEAM_PEAK together with RTS_BEAM_POWER; n_beams 0 or above RTS_BEAM_MAX_BEAMS; n_rx above RTS_BEAM_MAX_RX;
+ *   n_beams * n_rx above RTS_BEAM_MAX_WEIGHTS (64 KiB of complex128: the whole table sits in a workgroup's LDS); a non-finite
+ *   weight; RTS_BEAM_FROM_MAP without a library-owned map; RTS_BEAM_FROM_POINTER with a NULL or misaligned device_in or with
+ *   n_rows_in 0; n_rows_in or device_in set with another source; first_row or first_row + n_rows beyond the source's rows; a
+ *   misaligned device_out; a caller-owned device_out whose bytes overlap the bytes of the input the call reads (the transform is not
+ *   in place); a shape the launch grid cannot take (more than 2^31 - 1 workgroups of 256 cells).  A refused call leaves the
+ *   handle's previous output and weights as they were.
+ * rts_beamform_eval: pure host, no device.  The same rts_beam.h functions on a host array `in` [n_rx][n_rows_in][n_bins] (interleaved
+ *   re / im), which stands for the source p names; q in place of the attached cube (n_rx, n_bins).  The same validation as far as it
+ *   concerns no device memory: with RTS_BEAM_FROM_POINTER p->n_rows_in must equal the n_rows_in argument and p->device_in is not
+ *   looked at.  NULL q, in or out, n_rx, n_bins or n_rows_in 0 are refused too.  A refused call leaves out untouched.
+ * rts_steering_make: pure host.  Far-field steering weights in the cube's phase convention.  Direction b is (az, el) in radians,
+ *   directions[2 b], directions[2 b + 1]; positions[3 rx ..] the element centres in metres:
+ *     u = (cos el cos az, cos el sin az, sin el);  x = ((ux px + uy py) + uz pz) / wavelength;  f = x - floor(x);
+ *     w[b][rx] = taper[rx] (cos 2 pi f + j sin 2 pi f), the cosine and sine by exact reflection into the first octants, then libm
+ *     (the host side of the transforms' twiddles); a NULL taper means 1 and no multiply at all.
+ *   The sign: the cube's phase is -2 pi fc tau; a plane wave from direction u reaches the element at p earlier by (u . p) / c, so its
+ *   phase there is +2 pi (u . p) / lambda ahead, and y = sum conj(w) z peaks in the beam steered at u.
+ *   RTS_ERR_INVALID for a NULL pointer (taper apart), n_rx or n_beams 0, a wavelength not finite and > 0, a non-finite position,
+ *   direction or taper.
+ * NOTE on geometry: the tracer ends a ray's length on the receiver's capture SPHERE, not at its centre.  Receivers of equal radius in
+ *   the far field share that offset, so their relative phases are those of their centres.  Unequal radii or near-field geometry are
+ *   the caller's to model; the beamformer itself is plain linear algebra on whatever cube it is given. */
+#define RTS_BEAM_FROM_CUBE    0u   /* rows of the attached cube                                                     */
+#define RTS_BEAM_FROM_MAP     1u   /* the handle's last library-owned rts_cube_doppler map; rows = its n_fft       */
+#define RTS_BEAM_FROM_POINTER 2u   /* device_in: complex128 [n_rx][n_rows_in][n_bins], 16-byte aligned              */
+#define RTS_BEAM_POWER        1u   /* f64 re re + im im per beam                                                    */
+#define RTS_BEAM_PEAK         2u   /* f64 (P*, coordinate) per cell, no per-beam output; excludes RTS_BEAM_POWER    */
+#define RTS_BEAM_MAX_RX       64u
+#define RTS_BEAM_MAX_BEAMS    1024u
+#define RTS_BEAM_MAX_WEIGHTS  4096u  /* bounds n_beams * n_rx: 64 KiB of complex128                                 */
+typedef struct RtsBeamParams {
+    uint32_t n_beams, source;
+    uint32_t first_row, n_rows;      /* n_rows 0: from first_row to the last row of the source                      */
+    uint32_t n_rows_in, flags;       /* n_rows_in: POINTER only (0 otherwise); flags: RTS_BEAM_POWER | RTS_BEAM_PEAK */
+    const double* weights;           /* host [n_beams][n_rx], interleaved re / im, finite                           */
+    const void* device_in;           /* POINTER only                                                                */
+    uint64_t reserved[2];            /* 0 */
+} RtsBeamParams;
+int rts_cube_beamform(RtsHandle h, const RtsBeamParams* p, void* device_out);
+int rts_cube_beam_get(RtsHandle h, double* host_out, uint64_t capacity_doubles);
+int rts_beamform_eval(const RtsCubeParams* q, const double* in, uint32_t n_rows_in, const RtsBeamParams* p, double* out); /* pure host */
+int rts_steering_make(const double* positions, uint32_t n_rx, const double* directions, uint32_t n_beams,
+                      double wavelength, const double* taper, double* weights_out);                                      /* pure host */
+
 /* ---------------------------------------------------------------- backprojection imaging (SAR / ISAR) of the return cube
  * A derived product like the cube itself: time-domain backprojection of a coherent interval onto a planar
  * pixel grid -- exact for any track, any bistatic geometry and any target motion, where the slow-time DFT focuses only while a

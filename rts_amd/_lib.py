@@ -178,6 +178,20 @@ class RtsRangeParams(C.Structure):
 assert C.sizeof(RtsBeatParams) == 40 and BEAT_CONTRIBUTION_DTYPE.itemsize == 40 and C.sizeof(RtsRangeParams) == 56
 
 
+RTS_BEAM_FROM_CUBE, RTS_BEAM_FROM_MAP, RTS_BEAM_FROM_POINTER = 0, 1, 2
+RTS_BEAM_POWER, RTS_BEAM_PEAK = 1, 2
+RTS_BEAM_MAX_RX, RTS_BEAM_MAX_BEAMS, RTS_BEAM_MAX_WEIGHTS = 64, 1024, 4096
+
+
+class RtsBeamParams(C.Structure):
+    _fields_ = [("n_beams", C.c_uint32), ("source", C.c_uint32), ("first_row", C.c_uint32), ("n_rows", C.c_uint32),
+                ("n_rows_in", C.c_uint32), ("flags", C.c_uint32), ("weights", C.c_void_p), ("device_in", C.c_void_p),
+                ("reserved", C.c_uint64 * 2)]
+
+
+assert C.sizeof(RtsBeamParams) == 56
+
+
 class RtsSceneInfo(C.Structure):
     _fields_ = [("n_targets", C.c_uint32), ("n_prims", C.c_uint32), ("n_nodes", C.c_uint32), ("n_leaves", C.c_uint32),
                 ("handles_sharing", C.c_uint32), ("builder", C.c_uint32), ("build_ms", C.c_double),
@@ -267,7 +281,8 @@ EXPORTS = ["rts_create", "rts_destroy", "rts_last_error", "rts_device_count", "r
            "rts_cube_detect_os", "rts_cfar_os_alpha", "rts_cfar_os_eval",
            "rts_cube_backproject", "rts_cube_image_get", "rts_backproject_eval",
            "rts_cube_spectrogram", "rts_cube_spectrogram_get", "rts_stft_eval", "rts_window_make",
-           "rts_cube_render_beat", "rts_beat_eval", "rts_cube_range_transform", "rts_cube_range_get", "rts_range_eval"]
+           "rts_cube_render_beat", "rts_beat_eval", "rts_cube_range_transform", "rts_cube_range_get", "rts_range_eval",
+           "rts_cube_beamform", "rts_cube_beam_get", "rts_beamform_eval", "rts_steering_make"]
 
 
 def lib():
@@ -355,6 +370,10 @@ def lib():
         "rts_cube_range_transform": [vp, C.POINTER(RtsRangeParams), vp],
         "rts_cube_range_get": [vp, vp, u64],
         "rts_range_eval": [C.POINTER(RtsCubeParams), vp, C.POINTER(RtsRangeParams), vp],
+        "rts_cube_beamform": [vp, C.POINTER(RtsBeamParams), vp],
+        "rts_cube_beam_get": [vp, vp, u64],
+        "rts_beamform_eval": [C.POINTER(RtsCubeParams), vp, u32, C.POINTER(RtsBeamParams), vp],
+        "rts_steering_make": [vp, u32, vp, u32, C.c_double, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name, None)

@@ -434,6 +434,69 @@ def beat_axis(slope, n_fft, dt, n_out=0):
     return np.arange(n, dtype=np.float64) / (abs(float(slope)) * int(n_fft) * float(dt)), slope > 0
 
 
+_BEAM_SOURCES = {"cube": L.RTS_BEAM_FROM_CUBE, "map": L.RTS_BEAM_FROM_MAP, "pointer": L.RTS_BEAM_FROM_POINTER}
+
+
+def steering(positions, directions, wavelength, taper=None):
+    """rts_steering_make (pure host): far-field steering weights complex [n_beams][n_rx] in the cube's phase convention, for element
+    centres positions [n_rx][3] (m), beam directions [n_beams][2] = (az, el) in radians and an optional real taper [n_rx];
+    y = sum conj(w) z peaks in the beam steered at a plane wave's direction of arrival"""
+    pos = np.ascontiguousarray(np.asarray(positions, np.float64).reshape(-1, 3))
+    d = np.ascontiguousarray(np.asarray(directions, np.float64).reshape(-1, 2))
+    t = None if taper is None else np.ascontiguousarray(np.asarray(taper, np.float64).ravel())
+    if t is not None and len(t) != len(pos):
+        raise ValueError("steering: a taper of %d values for %d receivers" % (len(t), len(pos)))
+    w = np.zeros((len(d), len(pos)), np.complex128)
+    check(L.lib().rts_steering_make(ptr(pos), len(pos), ptr(d), len(d), float(wavelength), ptr(t), ptr(w.view(np.float64))))
+    return w
+
+
+def _beam_params(weights, n_rx, source, first, count, power, peak, device_in, n_rows_in):
+    """RtsBeamParams and the weight array it points to (keep it alive for the call); count None: to the source's last row"""
+    w = np.ascontiguousarray(np.asarray(weights, np.complex128))
+    if w.ndim != 2 or w.shape[1] != n_rx:
+        raise ValueError("beamform: weights of shape %s for %d receivers ([n_beams][n_rx])" % (w.shape, n_rx))
+    p = L.RtsBeamParams()
+    p.n_beams, p.source = w.shape[0], _BEAM_SOURCES.get(source, source)
+    p.first_row, p.n_rows, p.n_rows_in = int(first), int(count or 0), int(n_rows_in)
+    p.flags = (L.RTS_BEAM_POWER if power else 0) | (L.RTS_BEAM_PEAK if peak else 0)
+    p.weights = ptr(w.view(np.float64))
+    p.device_in = device_in if device_in else None
+    return p, w
+
+
+def _beam_out(n_beams, n_rows, n_bins, power, peak):
+    """the host array of a beamformer's output: (P*, coordinate) per cell, power or complex per beam"""
+    n_rows = max(n_rows, 0)
+    if peak:
+        return np.zeros((n_rows, n_bins, 2), np.float64)
+    return np.zeros((n_beams, n_rows, n_bins), np.float64 if power else np.complex128)
+
+
+def beamform_eval(inp, weights, first=0, count=None, power=False, peak=False):
+    """rts_beamform_eval (pure host): beams y[b] = sum_rx conj(w[b][rx]) z[rx] of rows first .. first + count - 1 (default: to the last)
+    of a host array [n_rx][n_rows][n_bins] (complex): complex [n_beams][count][n_bins], its power (float64, same shape) with power,
+    or float64 [count][n_bins][2] = (largest beam power, refined beam coordinate) with peak"""
+    inp = np.ascontiguousarray(np.asarray(inp, np.complex128))
+    n_rx, rows, nb = inp.shape
+    q = L.RtsCubeParams(n_rx, rows, nb, 0, 0.0, 1.0)
+    p, keep = _beam_params(weights, n_rx, "cube", first, count, power, peak, None, 0)
+    out = _beam_out(p.n_beams, p.n_rows if p.n_rows else rows - p.first_row, nb, power, peak)
+    check(L.lib().rts_beamform_eval(C.byref(q), ptr(inp.view(np.float64)), rows, C.byref(p), ptr(out.view(np.float64))))
+    return out
+
+
+def beam_angles(coordinate, directions):
+    """the caller's beam directions ([n_beams] or [n_beams][k], e.g. (az, el)) interpolated linearly at the beam coordinate of a
+    RTS_BEAM_PEAK output (beam index + offset): an array of coordinate's shape (with a trailing axis of k)"""
+    d = np.asarray(directions, np.float64)
+    c = np.asarray(coordinate, np.float64)
+    idx = np.arange(len(d), dtype=np.float64)
+    if d.ndim == 1:
+        return np.interp(c, idx, d)
+    return np.stack([np.interp(c, idx, d[:, k]) for k in range(d.shape[1])], axis=-1)
+
+
 def device_count():
     n = C.c_int(0)
     rc = L.lib().rts_device_count(C.byref(n))
@@ -711,6 +774,7 @@ class Tracer:
     def cube_doppler(self, n_fft, device_ptr=None, fetch=True):
         """slow-time DFT over the pulse axis (n_fft: power of two >= n_pulses): complex [n_rx][n_fft][n_bins]"""
         check(L.lib().rts_cube_doppler(self.h, n_fft, C.c_void_p(device_ptr) if device_ptr else None))
+        self._doppler_n = n_fft
         if not fetch:
             return None
         out = np.zeros((self._cube_shape[0], n_fft, self._cube_shape[2], 2), np.float64)
@@ -758,6 +822,29 @@ class Tracer:
         """rts_cube_range_get: the library-owned output of the last cube_range_transform, complex [n_rx][count][n_out]"""
         out = np.zeros(getattr(self, "_range_shape", None) or (1, 1, 1), np.complex128)
         check(L.lib().rts_cube_range_get(self.h, ptr(out.view(np.float64)), 2 * out.size))
+        return out
+
+    def cube_beamform(self, weights, source="cube", first=0, count=None, power=False, peak=False, device_in=None, n_rows_in=0, device_ptr=None,
+                      fetch=True):
+        """rts_cube_beamform: beams y[b] = sum_rx conj(w[b][rx]) z[rx] over the receivers, weights complex [n_beams][n_rx] (steering), of
+        rows first .. first + count - 1 (default: to the last) of the source: "cube" (the attached cube), "map" (the library-owned
+        map of the last cube_doppler) or "pointer" (device_in = data_ptr() of a complex128 device tensor [n_rx][n_rows_in][n_bins]).
+        Complex [n_beams][count][n_bins] -- the layout of a cube of n_beams receivers --, its power with power, or float64
+        [count][n_bins][2] = (largest beam power, refined beam coordinate: beam_angles) with peak.  Into a caller device tensor
+        (device_ptr; nothing is fetched) or the library's output, returned when fetch"""
+        n_rx, n_p, nb = self._cube_shape
+        p, keep = _beam_params(weights, n_rx, source, first, count, power, peak, device_in, n_rows_in)
+        check(L.lib().rts_cube_beamform(self.h, C.byref(p), C.c_void_p(device_ptr) if device_ptr else None))
+        if device_ptr:
+            return None
+        rows = {L.RTS_BEAM_FROM_CUBE: n_p, L.RTS_BEAM_FROM_MAP: getattr(self, "_doppler_n", 0)}.get(p.source, p.n_rows_in)
+        self._beam_shape = (p.n_beams, p.n_rows if p.n_rows else rows - p.first_row, nb, bool(power), bool(peak))
+        return self.beam_map() if fetch else None
+
+    def beam_map(self):
+        """rts_cube_beam_get: the library-owned output of the last cube_beamform, in its form"""
+        out = _beam_out(*(getattr(self, "_beam_shape", None) or (1, 1, 1, False, False)))
+        check(L.lib().rts_cube_beam_get(self.h, ptr(out.view(np.float64)), out.view(np.float64).size))
         return out
 
     def cube_compress(self, first=0, count=None):

@@ -518,6 +518,116 @@ extern "C" int rts_cube_range_get(RtsHandle c, double* host_out, uint64_t capaci
     return rts_cube_copy_out(c, "rts_cube_range_get", "no library-owned range map (rts_cube_range_transform with device_out NULL; a range map ends at rts_cube_attach) / null output", c->cube.range.valid, c->cube.range.p, c->cube.range.doubles, host_out, capacity_doubles);
 }
 
+// ------------------------------------------------------------------------------------- receive-array beamforming
+// (rts_amd.h: RtsBeamParams; the arithmetic and the launch plan are rts_beam.h, shared by the host export and the kernel, rts_beam.hip)
+// the record, the limits and the weight table: what needs no source
+static int rts_beam_check(const RtsBeamParams* p, uint32_t n_rx, const char* who)
+{
+    if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
+    if (p->reserved[0] || p->reserved[1]) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
+    if (p->source > RTS_BEAM_FROM_POINTER) { rts_set_error("%s: unknown source %u (RTS_BEAM_FROM_CUBE, _MAP, _POINTER)", who, p->source); return RTS_ERR_INVALID; }
+    if (p->flags & ~(RTS_BEAM_POWER | RTS_BEAM_PEAK)) { rts_set_error("%s: unknown flags 0x%x", who, p->flags); return RTS_ERR_INVALID; }
+    if ((p->flags & RTS_BEAM_PEAK) && (p->flags & RTS_BEAM_POWER)) { rts_set_error("%s: flags: RTS_BEAM_PEAK excludes RTS_BEAM_POWER", who); return RTS_ERR_INVALID; }
+    if (p->n_beams == 0 || p->n_beams > RTS_BEAM_MAX_BEAMS) { rts_set_error("%s: n_beams = %u (1 .. %u)", who, p->n_beams, RTS_BEAM_MAX_BEAMS); return RTS_ERR_INVALID; }
+    if (n_rx > RTS_BEAM_MAX_RX) { rts_set_error("%s: n_rx = %u receivers: more than %u", who, n_rx, RTS_BEAM_MAX_RX); return RTS_ERR_INVALID; }
+    if ((uint64_t)p->n_beams * n_rx > RTS_BEAM_MAX_WEIGHTS) { rts_set_error("%s: n_beams * n_rx = %u * %u weights: more than %u (the table sits in a workgroup's LDS)", who, p->n_beams, n_rx, RTS_BEAM_MAX_WEIGHTS); return RTS_ERR_INVALID; }
+    if (!p->weights) { rts_set_error("%s: null weights", who); return RTS_ERR_INVALID; }
+    for (uint32_t i = 0; i < 2 * p->n_beams * n_rx; i++) if (!std::isfinite(p->weights[i])) { rts_set_error("%s: weights[%u][%u] is not finite", who, i / 2 / n_rx, i / 2 % n_rx); return RTS_ERR_INVALID; }
+    if (p->source != RTS_BEAM_FROM_POINTER && p->n_rows_in != 0) { rts_set_error("%s: n_rows_in = %u without RTS_BEAM_FROM_POINTER", who, p->n_rows_in); return RTS_ERR_INVALID; }
+    if (p->source != RTS_BEAM_FROM_POINTER && p->device_in) { rts_set_error("%s: device_in without RTS_BEAM_FROM_POINTER", who); return RTS_ERR_INVALID; }
+    if (p->source == RTS_BEAM_FROM_POINTER && p->n_rows_in == 0) { rts_set_error("%s: n_rows_in = 0 with RTS_BEAM_FROM_POINTER", who); return RTS_ERR_INVALID; }
+    return RTS_OK;
+}
+// the span inside the source's rows, and the plan of its launch
+static int rts_beam_rows_check(const RtsBeamParams* p, uint32_t rows, uint32_t n_rx, uint32_t n_bins, const char* who, RtsBeamPlan* plan)
+{
+    if (p->first_row >= rows || p->n_rows > rows - p->first_row) { rts_set_error("%s: first_row = %u, n_rows = %u: inside the source's %u rows", who, p->first_row, p->n_rows, rows); return RTS_ERR_INVALID; }
+    *plan = rts_beam_plan(n_rx, p->n_beams, p->n_rows ? p->n_rows : rows - p->first_row, n_bins, p->flags);
+    if (!plan->supported) { rts_set_error("%s: %llu cells (n_rows * n_bins), %u per workgroup: more than %u workgroups (the launch grid)", who, (unsigned long long)plan->cells, RTS_BEAM_THREADS, RTS_BEAM_MAX_GRID_X); return RTS_ERR_INVALID; }
+    return RTS_OK;
+}
+
+extern "C" int rts_beamform_eval(const RtsCubeParams* q, const double* in, uint32_t n_rows_in, const RtsBeamParams* p, double* out)
+{
+    if (!q || q->n_rx == 0 || q->n_bins == 0) { rts_set_error("rts_beamform_eval: bad cube parameters"); return RTS_ERR_INVALID; }
+    if (n_rows_in == 0) { rts_set_error("rts_beamform_eval: n_rows_in = 0"); return RTS_ERR_INVALID; }
+    int rc = rts_beam_check(p, q->n_rx, "rts_beamform_eval"); if (rc != RTS_OK) return rc;
+    if (p->source == RTS_BEAM_FROM_POINTER && p->n_rows_in != n_rows_in) { rts_set_error("rts_beamform_eval: the parameters' n_rows_in = %u, the array's %u", p->n_rows_in, n_rows_in); return RTS_ERR_INVALID; }
+    RtsBeamPlan plan;
+    rc = rts_beam_rows_check(p, n_rows_in, q->n_rx, q->n_bins, "rts_beamform_eval", &plan); if (rc != RTS_OK) return rc;
+    if (!in || !out) { rts_set_error("rts_beamform_eval: null input or output array"); return RTS_ERR_INVALID; }
+    rts_beam_eval_host(q->n_rx, q->n_bins, in, n_rows_in, p->first_row, (uint32_t)(plan.cells / q->n_bins), p->n_beams, p->weights, p->flags, out);
+    return RTS_OK;
+}
+
+extern "C" int rts_steering_make(const double* positions, uint32_t n_rx, const double* directions, uint32_t n_beams, double wavelength, const double* taper, double* weights_out)
+{
+    if (!positions || !directions || !weights_out) { rts_set_error("rts_steering_make: null positions, directions or output array"); return RTS_ERR_INVALID; }
+    if (n_rx == 0 || n_beams == 0) { rts_set_error("rts_steering_make: n_rx = %u, n_beams = %u (each >= 1)", n_rx, n_beams); return RTS_ERR_INVALID; }
+    if (!std::isfinite(wavelength) || !(wavelength > 0.0)) { rts_set_error("rts_steering_make: wavelength = %g (finite, > 0)", wavelength); return RTS_ERR_INVALID; }
+    for (size_t i = 0; i < 3 * (size_t)n_rx; i++) if (!std::isfinite(positions[i])) { rts_set_error("rts_steering_make: position of receiver %zu is not finite", i / 3); return RTS_ERR_INVALID; }
+    for (size_t i = 0; i < 2 * (size_t)n_beams; i++) if (!std::isfinite(directions[i])) { rts_set_error("rts_steering_make: direction of beam %zu is not finite", i / 2); return RTS_ERR_INVALID; }
+    if (taper) for (uint32_t r = 0; r < n_rx; r++) if (!std::isfinite(taper[r])) { rts_set_error("rts_steering_make: taper[%u] is not finite", r); return RTS_ERR_INVALID; }
+    for (uint32_t b = 0; b < n_beams; b++) {
+        const double az = directions[2 * (size_t)b], el = directions[2 * (size_t)b + 1];
+        const double ce = cos(el), ux = ce * cos(az), uy = ce * sin(az), uz = sin(el);
+        for (uint32_t r = 0; r < n_rx; r++) {
+            const double* pos = positions + 3 * (size_t)r;
+            const double x = ((ux * pos[0] + uy * pos[1]) + uz * pos[2]) / wavelength;
+            double s, cs; rts_beat_sincos_turns(x, &s, &cs);      // f = x - floor(x), the exact reflections, then libm: the host side of the transforms' twiddles
+            double* w = weights_out + 2 * ((size_t)b * n_rx + r);
+            if (taper) { w[0] = taper[r] * cs; w[1] = taper[r] * s; } else { w[0] = cs; w[1] = s; }
+        }
+    }
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_beamform(RtsHandle c, const RtsBeamParams* p, void* device_out)
+{
+    CHECK_HANDLE(c);
+    NEED_CUBE(c, "rts_cube_beamform", "no cube (call rts_cube_attach first)");
+    const RtsCubeParams& q = c->cube.params;
+    int rc = rts_beam_check(p, q.n_rx, "rts_cube_beamform"); if (rc != RTS_OK) return rc;
+    const double* src = c->cube.p; uint32_t rows = q.n_pulses;
+    if (p->source == RTS_BEAM_FROM_MAP) {
+        const RtsCubeProduct& m = c->cube.doppler;
+        if (!m.valid || !m.own.p || m.p != m.own.p) { rts_set_error("rts_cube_beamform: RTS_BEAM_FROM_MAP: no library-owned map (rts_cube_doppler with device_out NULL)"); return RTS_ERR_INVALID; }
+        src = m.p; rows = c->cube.doppler_n;
+    } else if (p->source == RTS_BEAM_FROM_POINTER) {
+        if (!p->device_in) { rts_set_error("rts_cube_beamform: null device_in with RTS_BEAM_FROM_POINTER"); return RTS_ERR_INVALID; }
+        src = (const double*)p->device_in; rows = p->n_rows_in;
+    }
+    if ((uintptr_t)src & 15u) { rts_set_error("rts_cube_beamform: %s is not 16-byte aligned", p->source == RTS_BEAM_FROM_POINTER ? "device_in" : "the source's device memory"); return RTS_ERR_INVALID; }
+    RtsBeamPlan plan;
+    rc = rts_beam_rows_check(p, rows, q.n_rx, q.n_bins, "rts_cube_beamform", &plan); if (rc != RTS_OK) return rc;
+    if ((uintptr_t)device_out & 15u) { rts_set_error("rts_cube_beamform: device_out is not 16-byte aligned"); return RTS_ERR_INVALID; }
+    const uint64_t rx_stride = (uint64_t)rows * q.n_bins;
+    const double* in = src + 2 * (size_t)p->first_row * q.n_bins;
+    if (device_out) {       // the transform is not in place: the output's bytes against each receiver's span of the input
+        const uintptr_t o0 = (uintptr_t)device_out, o1 = o0 + sizeof(double) * plan.out_doubles;
+        for (uint32_t r = 0; r < q.n_rx; r++) {
+            const uintptr_t i0 = (uintptr_t)(in + 2 * (size_t)r * rx_stride), i1 = i0 + 16u * (uintptr_t)plan.cells;
+            if (o0 < i1 && i0 < o1) { rts_set_error("rts_cube_beamform: device_out overlaps the input the call reads (receiver %u): the transform is not in place", r); return RTS_ERR_INVALID; }
+        }
+    }
+    CHECK_CLOSED(c);
+    double* out; RTS_HIP(c->cube.beam.place(device_out, plan.out_doubles, &out));
+    // the weights -> pinned staging -> the device, on the stream (n_beams n_rx <= RTS_BEAM_MAX_WEIGHTS: one size for every call)
+    const size_t nw = 2 * (size_t)p->n_beams * q.n_rx;
+    double* w = nullptr;
+    RTS_HIP(c->cube.beam_w.begin(2u * RTS_BEAM_MAX_WEIGHTS, 2u * RTS_BEAM_MAX_WEIGHTS, 2u * RTS_BEAM_MAX_WEIGHTS, &w));
+    memcpy(w, p->weights, sizeof(double) * nw);
+    RTS_HIP(c->cube.beam_w.send(nw, c->stream));
+    if (!device_out) c->cube.beam.record(out, plan.out_doubles);
+    return rts_cube_beam_device(c, *p, plan, in, rx_stride, c->cube.beam_w.dev.p, out);
+}
+
+extern "C" int rts_cube_beam_get(RtsHandle c, double* host_out, uint64_t capacity_doubles)
+{
+    CHECK_HANDLE(c);
+    return rts_cube_copy_out(c, "rts_cube_beam_get", "no library-owned beams (rts_cube_beamform with device_out NULL; the beams end at rts_cube_attach) / null output", c->cube.beam.valid, c->cube.beam.p, c->cube.beam.doubles, host_out, capacity_doubles);
+}
+
 // ------------------------------------------------------------------------------------- backprojection imaging
 // (rts_amd.h: RtsImageParams; the arithmetic and the launch plan are rts_image.h, shared by the host export and the kernel, rts_image.hip)
 static int rts_image_check(const RtsImageParams* p, const RtsCubeParams& q, const char* who)
