@@ -124,10 +124,10 @@ __global__ void k_node_versions(const RtsNode4* __restrict__ nodes, uint32_t n, 
 // The two waits of a pulse (its trace, its post-processing): a thread blocked in hipStreamSynchronize lets its core fall
 // asleep, and every wake-up -- two per pulse, each in front of work the GPU is waiting for -- costs tens of microseconds on
 // the hosts of this pool (the C++ adapter's loop ran 0.44 ms per pulse right after a second of host-side hierarchy build had
-// kept the core awake, 0.72 ms otherwise).  RtsContext::spin_wait (default on; RTS_SPIN_WAIT=0): poll the stream instead.
+// kept the core awake, 0.72 ms otherwise).  RtsTuning::spin_wait (default on; RTS_SPIN_WAIT=0): poll the stream instead.
 hipError_t rts_stream_wait(RtsContext* c, hipStream_t st)
 {
-    if (!c->spin_wait) return hipStreamSynchronize(st);
+    if (!c->tune.spin_wait) return hipStreamSynchronize(st);
     for (;;) {
         const hipError_t e = hipStreamQuery(st);
         if (e != hipErrorNotReady) return e;
@@ -137,11 +137,14 @@ hipError_t rts_stream_wait(RtsContext* c, hipStream_t st)
 static int rts_attach_scene(RtsContext* c);
 void rts_comm_cache_forget(RtsContext* c);
 
+// The environment, as the readers of rts_tuning.h take it: the library looks at it nowhere else.
+static const char* rts_env(const char* name) { return getenv(name); }
+// RTS_LAP, RTS_DEBUG_SYNC: read once per process, by whichever of the two is asked for first
+static const RtsProcessTuning& rts_process_tuning() { static const RtsProcessTuning t = [] { RtsProcessTuning r; rts_tuning_read(&r, rts_env); return r; }(); return t; }
+
 int rts_debug_stage(RtsContext* c, const char* name)
 {
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("RTS_DEBUG_SYNC"); on = (e && e[0] == '1') ? 1 : 0; }
-    if (!on) return RTS_OK;
+    if (!rts_process_tuning().debug_sync) return RTS_OK;
     fprintf(stderr, "[rts] stage %s ... ", name); fflush(stderr);
     hipError_t e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->tstream);
@@ -163,8 +166,8 @@ void rts_hist_unref(RtsTileHist* h) { if (h && --h->refs == 0) delete h; }
 void rts_gate_unref(RtsGate* g) { if (g && --g->refs == 0) { if (g->tstream) (void)hipStreamDestroy(g->tstream); delete g; } }
 
 // The teardown of a handle, once.  After this body the members destroy themselves in reverse order of declaration: every DevBuf
-// (hipFree), the pinned blocks pin, pin_rx and the mirror's (hipHostFree) and the three staged uploads (pat_rx, cube.img_geo, cube.stft_win:
-// their event, then their blocks).  That is safe because no work can read
+// (hipFree), the pinned blocks pin, pin_rx and the mirror's (hipHostFree) and the staged uploads (pat_rx and the cube's: cube.os_alpha, img_geo,
+// stft_win, range_win, beam_w: their event, then their blocks).  That is safe because no work can read
 // them any more: `stream` and `cstream` have been drained, the trace stream has been drained (it may live on with the other
 // handles of the link group, but carries no work of this handle), and nothing is enqueued on a handle's behalf anywhere else.
 RtsContext::~RtsContext()
@@ -217,55 +220,24 @@ extern "C" int rts_create(const RtsParams* p, RtsHandle* out)
     if (e != hipSuccess) { delete c; rts_set_error("hipGetDeviceProperties: %s", hipGetErrorString(e)); return RTS_ERR_HIP; }
     c->n_cu = prop.multiProcessorCount;
     rts_trace_preload();
-    { const char* e = getenv("RTS_PRIMARY_MASK"); if (e && e[0] == '0') c->use_pmask = false; }            // experiments / tests: no primary-ray pre-filter
-    if (p->flags & RTS_FLAG_NO_PREFILTER) c->use_pmask = false;
-    // experiment / test knobs, read ONCE PER HANDLE at creation (never per process: two handles of one process may differ)
-    { const char* e = getenv("RTS_GRID_MULT"); if (e) c->grid_mult = std::max(1, atoi(e)); }
-    { const char* e = getenv("RTS_GRID_SPARE"); if (e) { c->grid_spare = std::max(0, atoi(e)); c->grid_spare_forced = true; } }
-    { const char* e = getenv("RTS_TILE_LPT"); if (e && e[0] == '0') c->tile_lpt = false; }
-    { const char* e = getenv("RTS_COOP_BIG_PART"); if (e) { const double v = atof(e); if (v >= 0) c->coop_big_part = v; } }
-    { const char* e = getenv("RTS_COOP_FRAC"); if (e) { const double v = atof(e); if (v >= 0) c->coop_frac = v; } }                  // 0: no cooperative units; tests: tiny values put every tile at the head
-    { const char* e = getenv("RTS_COOP_FLOOR"); if (e) c->coop_floor = (uint32_t)std::max(0, atoi(e)); }
-    c->debug_coop = getenv("RTS_DEBUG_COOP") != nullptr;
+    // experiment / test knobs, read ONCE PER HANDLE at creation (never per process: two handles of one process may differ): rts_tuning.h
+    rts_tuning_read(&c->tune, rts_env);
+    if (p->flags & RTS_FLAG_NO_PREFILTER) c->tune.use_pmask = false;
     c->hist = new RtsTileHist();
-    { const char* e = getenv("RTS_SHARE_HISTORY"); if (e) c->share_history = e[0] != '0'; }
-    { const char* e = getenv("RTS_RX_WINDOW_SCREEN"); if (e) c->rx_window_screen = e[0] != '0'; }
-    { const char* e = getenv("RTS_TIMELINE_BLOCKS"); if (e) c->timeline_blocks = e[0] != '0'; }
-    { const char* e = getenv("RTS_COOP_VERSIONS"); if (e) c->coop_versions = e[0] != '0'; }
-    { const char* e = getenv("RTS_DEAD_BATCH"); if (e) c->batch_dead = strcmp(e, "all") == 0 ? 2 : (e[0] != '0' ? 1 : 0); }      // dead-tile batches of the trace kernel: 0 never, 1 the order's dead part (default), all: every position is screened tile-wise first (tests)
-    { const char* e = getenv("RTS_WALK_VERSIONS"); if (e) c->node_versions = e[0] != '0'; }      // (per handle: RTS_NODE_VERSIONS decides whether the scene HAS versions, this whether the handle walks them)
-    { const char* e = getenv("RTS_SPIN_WAIT"); if (e) c->spin_wait = atoi(e) != 0; }
-    { const char* e = getenv("RTS_TRACE_OWN_STREAM"); if (e) c->trace_own_stream = atoi(e) != 0; }
-    { const char* e = getenv("RTS_SPECULATE"); if (e) c->spec_enabled = atoi(e) != 0; }
-    { const char* e = getenv("RTS_POST_SMALL"); if (e) c->post_small = atoi(e) != 0; }
-    { const char* e = getenv("RTS_POST_ONE_MAX"); if (e) c->post_one_max = (uint64_t)strtoull(e, nullptr, 10); }
-    { const char* e = getenv("RTS_IMAGE_SPLIT_BELOW"); if (e) c->cube.img_split_below = (uint32_t)std::min(65536, std::max(0, atoi(e))); }
-    { const char* e = getenv("RTS_BEAT_PARTS"); if (e) c->cube.beat_force_parts = (uint32_t)std::min((int)RTS_BEAT_MAX_PARTS, std::max(0, atoi(e))); }      // tests: the parts of a beat render (0: the plan's own)
-    { const char* e = getenv("RTS_POST_PRIO"); if (e) c->post_prio = (uint32_t)std::min(3, std::max(0, atoi(e))); }
-    { const char* e = getenv("RTS_COOP_STEPS"); if (e) c->coop_walk_steps = (uint32_t)std::max(0, atoi(e)); }
-    { const char* e = getenv("RTS_COOP_STEPS_LO"); if (e) c->coop_walk_steps_lo = (uint32_t)std::max(0, atoi(e)); }
-    { const char* e = getenv("RTS_COOP_MID"); if (e) c->coop_mid = std::max(0.0, atof(e)); }
-    { const char* e = getenv("RTS_COOP_SEG"); if (e && atoi(e) == 0) c->coop_walk_steps = 0; }      // (the tests' old switch: every tile above the floor is flagged)
-    { const char* e = getenv("RTS_COOP_BIG"); if (e) c->coop_big = std::max(0.0, atof(e)); }
-    { const char* e = getenv("RTS_COOP_SPREAD"); if (e) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4 || v == 8) c->coop_spread = (uint32_t)v; } }
-    { const char* e = getenv("RTS_COOP_GRID"); if (e) c->coop_grid_max = (uint32_t)std::min(4096, std::max(1, atoi(e))); }
-    { const char* e = getenv("RTS_EW_REL"); if (e) { const double v = atof(e); if (v > 0) c->ew_rel = v; } }
-    { const char* e = getenv("RTS_STACK_LDS_DEBUG"); if (e) { int v = atoi(e); if (v >= 1 && v <= RTS_STACK_LDS) c->stack_lds = (uint32_t)v; } }   // tests: force the spill path
     *out = c;
     return RTS_OK;
 }
 
 // RTS_LAP=1: where the host side of rts_trace_pulse_begin spends its time, per section, summed per handle and printed by
 // rts_destroy (stderr) -- the tool behind DESIGN.md's "what a slow run is"
-static int rts_lap_on() { static int on = -1; if (on < 0) { const char* e = getenv("RTS_LAP"); on = (e && e[0] == '1') ? 1 : 0; } return on; }
 struct RtsLapTimer {
     RtsContext* c; std::chrono::steady_clock::time_point t0; bool on;
-    explicit RtsLapTimer(RtsContext* c_) : c(c_), on(rts_lap_on() != 0) { if (on) t0 = std::chrono::steady_clock::now(); }
+    explicit RtsLapTimer(RtsContext* c_) : c(c_), on(rts_process_tuning().lap) { if (on) t0 = std::chrono::steady_clock::now(); }
     void lap(int k) { if (!on) return; const auto t1 = std::chrono::steady_clock::now(); c->lap_s[k] += std::chrono::duration<double>(t1 - t0).count(); c->lap_n[k]++; t0 = t1; }
 };
 
 // pulses begun and not yet ended or resolved, per device: a trace launch that will share the GPU with another pulse's kernels leaves block
-// slots free for them (RtsContext::grid_spare), a lone pulse takes the whole chip.  Moved by the transitions of RtsPulseState alone (rts_pulse_state.h).
+// slots free for them (RtsTuning::grid_spare), a lone pulse takes the whole chip.  Moved by the transitions of RtsPulseState alone (rts_pulse_state.h).
 static std::atomic<int> g_open_pulses[RTS_PULSE_SLOTS];
 static std::mutex g_hist_mu;      // (re)allocation of a shared tile-cost history (RtsTileHist)
 
@@ -274,7 +246,7 @@ extern "C" int rts_destroy(RtsHandle c)
     if (!c) return RTS_OK;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    if (rts_lap_on() && c->lap_n[0]) {
+    if (rts_process_tuning().lap && c->lap_n[0]) {
         static const char* names[8] = {"host prep", "upload + fill", "scene place", "buffers + tile order", "events + trace launch", "hipSetDevice", "resolve previous", ""};
         fprintf(stderr, "[rts lap] handle %p, %llu pulses begun, us per pulse:", (void*)c, (unsigned long long)c->lap_n[0]);
         for (int k = 0; k < 7; k++) fprintf(stderr, " %s %.1f |", names[k], c->lap_s[k] / (double)c->lap_n[0] * 1e6);
@@ -377,21 +349,20 @@ extern "C" int rts_set_scene(RtsHandle c, const RtsMesh* meshes, uint32_t n_targ
     //          tile runs through the pole fans of the synthetic airframe), the pipelined benchmark, the dense control, spheres
     //          and C4 within 1-4 %
     const auto t_build0 = std::chrono::steady_clock::now();
-    bool device_build = (c->params.flags & RTS_FLAG_HOST_BUILD) == 0;
-    { const char* e = getenv("RTS_BUILDER"); if (e) device_build = (strcmp(e, "host") != 0); }
+    RtsSceneTuning st; st.device_build = (c->params.flags & RTS_FLAG_HOST_BUILD) == 0;
+    rts_tuning_read(&st, rts_env);
+    bool device_build = st.device_build;
     // extra references for triangles whose boxes are mostly empty (rts_sah.cpp, rts_lbvh.hip): an average triangle gets about
     // 1 + budget references where cutting pays (2 measured best for both builders)
-    double split_budget = 2.0;
-    { const char* e = getenv("RTS_SPLIT_BUDGET"); if (e) { const double v = atof(e); if (v >= 0 && v <= 8) split_budget = v; } }
+    const double split_budget = st.split_budget;
     if (device_build) {
         // The device builder sizes its bins by the references of a level and closes within 256 levels or gives up: out of memory, or
         // a mesh it does not close on, must not fail the scene -- the host builder takes over (RTS_DEVICE_BUILD_FALLBACK=0:
         // the error is returned, for tests of the builder itself).
-        int rc = rts_lbvh_build_device(c, ns, vidx, mh, split_budget);
-        if (rc == RTS_OK && getenv("RTS_DEBUG_FAIL_DEVICE_BUILD")) { rts_set_error("rts_set_scene: device builder failure injected (RTS_DEBUG_FAIL_DEVICE_BUILD)"); rc = RTS_ERR_HIP; }      // tests: the fall-back below, with the builder's state to clean up
+        int rc = rts_lbvh_build_device(c, ns, vidx, mh, st);
+        if (rc == RTS_OK && st.fail_device_build) { rts_set_error("rts_set_scene: device builder failure injected (RTS_DEBUG_FAIL_DEVICE_BUILD)"); rc = RTS_ERR_HIP; }      // tests: the fall-back below, with the builder's state to clean up
         if (rc != RTS_OK) {
-            const char* e = getenv("RTS_DEVICE_BUILD_FALLBACK");
-            if (rc == RTS_ERR_INVALID || (e && e[0] == '0')) return rc;
+            if (rc == RTS_ERR_INVALID || !st.build_fallback) return rc;
             (void)hipGetLastError();                                     // (a failed allocation leaves a sticky error code behind)
             fprintf(stderr, "[rts] device hierarchy build failed (%s): falling back to the host builder\n", rts_last_error());
             ns->d_nodes4.release(); ns->d_leaf_prim.release(); ns->blas.clear(); ns->n_nodes = 0; ns->n_leaves = 0;
@@ -432,8 +403,8 @@ extern "C" int rts_set_scene(RtsHandle c, const RtsMesh* meshes, uint32_t n_targ
     if (ns->n_nodes) { k_children_to_prims<<<(ns->n_nodes + 255) / 256, 256, 0, c->stream>>>(ns->d_nodes4.p, ns->n_nodes, ns->d_leaf_prim.p); RTS_HIP(hipGetLastError()); RTS_HIP(hipStreamSynchronize(c->stream)); }
     {   // the octant versions of the node records (k_node_versions): RTS_NODE_VERSIONS=0: none; they need 1 KB per node -- a scene whose
         // versions would not fit a quarter of the device's free memory goes without (the kernel then walks d_nodes4 as before)
-        const char* e = getenv("RTS_NODE_VERSIONS"); const bool want = !(e && e[0] == '0');
-        const char* km = getenv("RTS_VERSION_KEY"); const int key_mode = (km && strcmp(km, "corner") == 0) ? 0 : 1;      // (measured, profiles/r05a_versions_ab.log: by centre the dense control visits 5.9 % more nodes than the sorted walk, by entry corner 9.6 %)
+        const bool want = st.node_versions;
+        const int key_mode = st.version_key_centre ? 1 : 0;      // (measured, profiles/r05a_versions_ab.log: by centre the dense control visits 5.9 % more nodes than the sorted walk, by entry corner 9.6 %)
         size_t free_b = 0, total_b = 0; (void)hipMemGetInfo(&free_b, &total_b);
         const size_t need = (size_t)ns->n_nodes * 8 * sizeof(RtsNode4);
         if (want && ns->n_nodes && ns->n_nodes < (1u << 28) && need < free_b / 4) {
@@ -488,7 +459,7 @@ extern "C" int rts_share_scene(RtsHandle dst, RtsHandle src)
     rts_scene_unref(dst->scene);
     dst->scene = src->scene; dst->scene->refs++;
     { int rc = rts_attach_scene(dst); if (rc != RTS_OK) return rc; }
-    if (dst->share_history && src->share_history && dst->params.width == src->params.width) {      // ... and the tile-cost history of the scene's handles (RtsTileHist)
+    if (dst->tune.share_history && src->tune.share_history && dst->params.width == src->params.width) {      // ... and the tile-cost history of the scene's handles (RtsTileHist)
         rts_hist_unref(dst->hist);
         dst->hist = src->hist; dst->hist->refs++;
     }
@@ -650,7 +621,7 @@ static int fill_target_placement(const RtsContext* c, uint32_t t, RtsTargetDev& 
     // itself (Sterbenz-exact or correctly rounded), the f32 narrowing of the mapped origin -- is relative to |o - p| and
     // is inside the 3e-7 |o'| of rts_slab_setup.  2^-49 wmax is that bound times 9.  (Round 1 used 4e-9 wmax: harmless
     // near the origin, but 2.6 cm on every slab plane of a mesh of 10-30 cm triangles at 6.4e6 m.)
-    td.ew = (float)(wmax * c->ew_rel) + 1.0e-30f;
+    td.ew = (float)(wmax * c->tune.ew_rel) + 1.0e-30f;
     if (b.root < 0 || !std::isfinite(td.cx + td.cy + td.cz + td.r2)) td.root = -1;
     return RTS_OK;
 }
@@ -683,7 +654,7 @@ static int rts_launch_buffers_reserve(RtsContext* c, const RtsLaunchSizes& s)
 }
 
 // the cooperative kernel's rows of the per-thread slabs
-static uint32_t rts_coop_threads(const RtsContext* c) { return c->coop_frac > 0.0 ? c->coop_grid_max * RTS_BLOCK : 0u; }
+static uint32_t rts_coop_threads(const RtsContext* c) { return c->tune.coop_frac > 0.0 ? c->tune.coop_grid_max * RTS_BLOCK : 0u; }
 
 // Device buffers of a launch of up to n launch indices (grown, never shrunk).  Also the first touch of the big slabs:
 // doing it before the first pulse keeps multi-GB hipMalloc calls out of a caller's timed or latency-critical region.
@@ -694,7 +665,7 @@ extern "C" int rts_reserve(RtsHandle c, uint64_t n_rays)
     const uint64_t n = std::min<uint64_t>(n_rays ? n_rays : W3, W3);
     if (n * rts_chains(c->params.max_refr) > 0xfffffff0ULL) { rts_set_error("rts_reserve: rays x chains exceeds 2^32"); return RTS_ERR_UNSUPPORTED; }
     // upper bounds of any launch's grid: threads of the child slab, threads of the overflow stack, blocks of both kernels
-    const RtsLaunchSizes sz = rts_launch_sizes(n, (uint64_t)c->n_cu * 64 * RTS_BLOCK, (uint64_t)c->n_cu * 1024, rts_coop_threads(c), (uint64_t)c->n_cu * 64 + c->coop_grid_max,
+    const RtsLaunchSizes sz = rts_launch_sizes(n, (uint64_t)c->n_cu * 64 * RTS_BLOCK, (uint64_t)c->n_cu * 1024, rts_coop_threads(c), (uint64_t)c->n_cu * 64 + c->tune.coop_grid_max,
                                                c->params.max_refl, c->params.max_refr, (c->params.flags & RTS_FLAG_KEEP_ALL_RAYS) != 0);
     { int rc = rts_launch_buffers_reserve(c, sz); if (rc != RTS_OK) return rc; }
     { int rc = rts_zero_block_reserve(c); if (rc != RTS_OK) return rc; }
@@ -835,23 +806,23 @@ static int pulse_args_and_buffers(RtsContext* c, RtsPulseLaunch& L)
     a.max_refr = c->params.max_refr; a.rows = a.max_refr ? c->params.max_refl + 3 : 1;      // (output rows per launch index: not rts_hit_rows)
     if ((uint64_t)n * rts_chains(a.max_refr) > 0xfffffff0ULL) { rts_set_error("rts_trace_pulse: rays x chains exceeds 2^32"); return RTS_ERR_UNSUPPORTED; }
     a.total_threads = L.grid * RTS_BLOCK;
-    a.coop_spread = c->coop_spread;
-    a.coop_walk_steps_lo = std::min(c->coop_walk_steps_lo, c->coop_walk_steps);
-    a.coop_walk_steps = c->coop_walk_steps; a.coop_min_cost = c->coop_walk_steps ? std::min<uint32_t>(c->coop_floor, 1875u) : 0u;      // (nothing shorter than 50 us is looked at; RTS_COOP_STEPS=0: every tile is flagged)
+    a.coop_spread = c->tune.coop_spread;
+    a.coop_walk_steps_lo = std::min(c->tune.coop_walk_steps_lo, c->tune.coop_walk_steps);
+    a.coop_walk_steps = c->tune.coop_walk_steps; a.coop_min_cost = c->tune.coop_walk_steps ? std::min<uint32_t>(c->tune.coop_floor, 1875u) : 0u;      // (nothing shorter than 50 us is looked at; RTS_COOP_STEPS=0: every tile is flagged)
     a.slab_threads = a.total_threads + rts_coop_threads(c);
-    const RtsLaunchSizes sz = rts_launch_sizes(n, a.total_threads, a.total_threads, rts_coop_threads(c), (uint64_t)L.grid + c->coop_grid_max, a.max_refl, a.max_refr, L.keep_all);
+    const RtsLaunchSizes sz = rts_launch_sizes(n, a.total_threads, a.total_threads, rts_coop_threads(c), (uint64_t)L.grid + c->tune.coop_grid_max, a.max_refl, a.max_refr, L.keep_all);
     { int rc = rts_launch_buffers_reserve(c, sz); if (rc != RTS_OK) return rc; }
     if (L.keep_all) {      // (the buffers' last element is spare)
         rts_fill_i32(st, c->d_hit_prim.p, -2, sz.hit_prim - 1);
         RTS_HIP(hipMemsetAsync(c->d_hit_t.p, 0, sizeof(float) * (sz.hit_t - 1), st));
     }
     a.pmask = lc.mask.n ? pulse_mask_words(c) : nullptr; a.pre_filter = L.pre_filter ? 1u : 0u;
-    a.nodes4 = c->scene->d_nodes4.p; a.nodes4v = c->node_versions ? c->scene->d_nodes4v.p : nullptr; a.stack_lds = c->stack_lds; a.leaves = c->d_leaves.p; a.tri_nidx = c->scene->d_tri_nidx.p; a.normals = c->d_normals_world.p;
+    a.nodes4 = c->scene->d_nodes4.p; a.nodes4v = c->tune.node_versions ? c->scene->d_nodes4v.p : nullptr; a.stack_lds = c->tune.stack_lds; a.leaves = c->d_leaves.p; a.tri_nidx = c->scene->d_tri_nidx.p; a.normals = c->d_normals_world.p;
     a.targets = c->p_targets; a.rx = c->d_rx.p;
     a.recv_records = c->d_recv.p; a.all_records = c->d_all.p; a.counters = c->p_counters; a.block_counters = c->d_block_counters.p; a.dir_hist = c->d_dir_hist.p;
     a.hit_prim = c->d_hit_prim.p; a.hit_t = c->d_hit_t.p; a.stack_ovf = c->d_stack_ovf.p; a.child = c->d_child.p;
-    a.rx_window_screen = c->rx_window_screen ? 1u : 0u;
-    a.coop_versions = c->coop_versions ? 1u : 0u;
+    a.rx_window_screen = c->tune.rx_window_screen ? 1u : 0u;
+    a.coop_versions = c->tune.coop_versions ? 1u : 0u;
     a.tile_ctr = c->d_tile_ctr.p;
     return RTS_OK;
 }
@@ -863,13 +834,13 @@ static int pulse_tile_order(RtsContext* c, RtsPulseLaunch& L)
     RtsTraceArgs& a = L.a;
     const RtsLaunchShape s = rts_launch_shape(L.n, L.r.first, L.r.il_tile, L.r.il_parts, L.r.il_part, rts_lattice_size(c->params.width));
     const uint32_t n_tiles = s.n_tiles, resident_waves = L.grid * (RTS_BLOCK / RTS_WTILE);
-    a.batch_dead = s.aligned ? (uint32_t)c->batch_dead : 0u;      // (a wave tile must be 64 CONSECUTIVE launch indices for the tile-level screen: rts_tile_maybe)
-    if (!(c->tile_lpt && s.aligned && n_tiles > resident_waves)) { c->tile_cost_pending = false; c->tile_last_valid = false; return RTS_OK; }
+    a.batch_dead = s.aligned ? (uint32_t)c->tune.batch_dead : 0u;      // (a wave tile must be 64 CONSECUTIVE launch indices for the tile-level screen: rts_tile_maybe)
+    if (!(c->tune.tile_lpt && s.aligned && n_tiles > resident_waves)) { c->tile_cost_pending = false; c->tile_last_valid = false; return RTS_OK; }
     { int rc = rts_hist_ensure(c, s.n_hist); if (rc != RTS_OK) return rc; }
     if (c->tile_cost_pending || c->hist->any) {
-        c->coop_big_now = (L.r.il_parts > 1 && !L.shared_gpu && c->coop_big_part > c->coop_big) ? c->coop_big_part : c->coop_big;
+        c->coop_big_now = (L.r.il_parts > 1 && !L.shared_gpu && c->tune.coop_big_part > c->tune.coop_big) ? c->tune.coop_big_part : c->tune.coop_big;
         int rc = rts_tile_order_build(c, c->tile_cost_sig, c->tile_cost_pending, s.sig, n_tiles, resident_waves); if (rc != RTS_OK) return rc;
-        a.tile_order = c->d_tile_order.p; a.tile_head = c->coop_frac > 0.0 ? c->d_tile_ctr.p + RTS_OFF_HEAD + 2 : nullptr; a.tile_head_all = a.tile_head; c->hist->any = true;
+        a.tile_order = c->d_tile_order.p; a.tile_head = c->tune.coop_frac > 0.0 ? c->d_tile_ctr.p + RTS_OFF_HEAD + 2 : nullptr; a.tile_head_all = a.tile_head; c->hist->any = true;
         a.tile_live = c->d_tile_ctr.p + RTS_OFF_LIVE;      // (written by the order build)
     }
     const bool merged_all = c->tile_cost_pending && rts_wave_tiles(c->tile_cost_sig[0]) >= n_tiles && c->d_tile_cost.cap >= n_tiles;      // k_tile_merge read AND cleared the records
@@ -885,10 +856,11 @@ static int pulse_tile_order(RtsContext* c, RtsPulseLaunch& L)
 static int pulse_timelines(RtsContext* c, RtsPulseLaunch& L)
 {
     const size_t blocks2 = (size_t)L.grid * 2;
-    L.tl_path = L.count_trav ? getenv("RTS_TIMELINE") : nullptr;
+    RtsLaunchTuning lt; if (L.count_trav) rts_tuning_read(&lt, rts_env);
+    L.tl_path = lt.timeline;
     L.cnt_tl = blocks2 + 2 * (size_t)rts_wave_tiles(L.n);          // [grid][2] block ticks, [tiles] durations, [tiles] start ticks
     c->tl_blocks = 0;
-    const size_t words = L.tl_path ? L.cnt_tl + 1 : (!L.count_trav && c->timeline_blocks) ? blocks2 + 1 : 0;
+    const size_t words = L.tl_path ? L.cnt_tl + 1 : (!L.count_trav && c->tune.timeline_blocks) ? blocks2 + 1 : 0;
     if (!words) return RTS_OK;
     RTS_HIP(c->d_timeline.reserve(words)); RTS_HIP(hipMemsetAsync(c->d_timeline.p, 0, sizeof(unsigned long long) * words, c->stream)); L.a.timeline = c->d_timeline.p;
     if (!L.tl_path) c->tl_blocks = L.grid;
@@ -904,7 +876,7 @@ static int pulse_launch(RtsContext* c, RtsPulseLaunch& L)
     // The trace kernel's stream: the handle's low-priority trace stream when other pulses share the GPU (their short kernels then get
     // in beside it), the handle's OWN stream when none does -- a pulse on its own is one dependent chain, and every hop between two
     // streams costs it 17-25 us of event hand-over (profiles/r04_inflight1_pulse_timeline.log: two hops per pulse)
-    c->tstream_now = (c->trace_own_stream && !L.shared_gpu && c->gate->refs.load() == 1) ? st : c->tstream;
+    c->tstream_now = (c->tune.trace_own_stream && !L.shared_gpu && c->gate->refs.load() == 1) ? st : c->tstream;
     if (c->tstream_now != st) {
         RTS_HIP(hipEventRecord(c->ev[8], st));                   // scene + per-pulse buffers of this handle are ready
         RTS_HIP(hipStreamWaitEvent(c->tstream_now, c->ev[8], 0));
@@ -919,11 +891,11 @@ static int pulse_launch(RtsContext* c, RtsPulseLaunch& L)
     if (a.tile_head) {
         if (c->hist->head_hint_valid) c->n_head_hint = c->hist->head_hint;      // (the latest head count of ANY handle that shares the history)
         const bool grouped = a.nodes4v && a.coop_versions && !L.keep_all && !a.max_refr;      // (rts_trace_dispatch: the cooperative kernel that walks the octant versions holds 64 / RTS_COOP_GROUP rays per unit)
-        coop_grid = rts_coop_grid(c->n_head_hint, grouped, c->coop_grid_max);
+        coop_grid = rts_coop_grid(c->n_head_hint, grouped, c->tune.coop_grid_max);
         if (coop_grid == 0) a.tile_head = nullptr;
         c->last_args = a;
     }
-    if (c->debug_coop) fprintf(stderr, "[rts] launch: n_rays %u grid %u head hint %u coop grid %u walk-steps threshold %u min cost %u order %d\n", L.n, L.grid, c->n_head_hint, coop_grid, a.coop_walk_steps, a.coop_min_cost, a.tile_order ? 1 : 0);
+    if (c->tune.debug_coop) fprintf(stderr, "[rts] launch: n_rays %u grid %u head hint %u coop grid %u walk-steps threshold %u min cost %u order %d\n", L.n, L.grid, c->n_head_hint, coop_grid, a.coop_walk_steps, a.coop_min_cost, a.tile_order ? 1 : 0);
     c->last_coop_grid = coop_grid;
     int rc = rts_trace_launch(c, a, L.count_trav, coop_grid);
     if (rc != RTS_OK) return rc;
@@ -972,9 +944,9 @@ extern "C" int rts_trace_pulse_begin(RtsHandle c, const RtsPulse* p)
     // the trace kernel's blocks are persistent and four of them fill a CU's register file: a launch that shares the GPU leaves a few
     // block slots free so that the short kernels of the neighbouring pulses (other streams) are not locked out for the whole launch
     std::atomic<int>& open_here = rts_pulse_slot(g_open_pulses, c->device);
-    L.shared_gpu = c->grid_spare_forced || open_here.load() > 0;
-    L.grid = rts_trace_grid(L.n, c->n_cu, c->grid_mult, L.shared_gpu ? c->grid_spare : 0);
-    L.pre_filter = c->use_pmask && !c->pre_dense;           // (a launch where most rays hit pays for the filter and skips nothing)
+    L.shared_gpu = c->tune.grid_spare_forced || open_here.load() > 0;
+    L.grid = rts_trace_grid(L.n, c->n_cu, c->tune.grid_mult, L.shared_gpu ? c->tune.grid_spare : 0);
+    L.pre_filter = c->tune.use_pmask && !c->pre_dense;           // (a launch where most rays hit pays for the filter and skips nothing)
     pulse_fill_constants(c, *p, L.r, L.pre_filter);
     lt.lap(0);
     { int rc = pulse_upload_and_fill(c, L.moved); if (rc != RTS_OK) return rc; }
@@ -1001,7 +973,7 @@ static void rts_pulse_account(RtsContext* c, const unsigned long long* cnt)
     s.rays = n; s.segments = cnt[1]; s.shaded = cnt[2]; s.received = cnt[0]; s.node_visits = cnt[3]; s.tri_tests = cnt[4]; s.stack_overflows = (uint32_t)cnt[5];
     s.n_prims = c->scene->n_prims; s.n_nodes = c->scene->n_nodes;
     s.walked_segments = cnt[11]; s.cost_records_dropped = (uint32_t)cnt[12];
-    if (c->debug_coop && (cnt[12] || cnt[14])) fprintf(stderr, "[rts] clocks: %llu cost records dropped; shader clock ran backwards on %llu tiles (XCC mask 0x%llx)\n", cnt[12], cnt[14] & 0x00ffffffffffffffULL, cnt[14] >> 56);
+    if (c->tune.debug_coop && (cnt[12] || cnt[14])) fprintf(stderr, "[rts] clocks: %llu cost records dropped; shader clock ran backwards on %llu tiles (XCC mask 0x%llx)\n", cnt[12], cnt[14] & 0x00ffffffffffffffULL, cnt[14] >> 56);
     s.coop_tiles = c->last_coop_grid ? (uint32_t)std::min<unsigned long long>(std::min<unsigned long long>(cnt[7], rts_wave_tiles(n)), 16384ull) : 0u;      // (the bounds k_trace applies to the order's head count)
     c->pre_dense = 2 * s.shaded > (uint64_t)n;                      // next launch of this handle: pre-filter only if most launch indices hit nothing
     s.ms_scene = s.ms_trace = s.ms_compact = s.ms_aggregate = 0;
@@ -1030,7 +1002,7 @@ static void pulse_timeline_summary(RtsContext* c)
     const size_t q[8] = {0, m / 2, m - 1, 0, m / 10, m / 2, m * 9 / 10, m - 1};
     for (int k = 0; k < 8; k++) c->tl_summary[k] = (double)((k < 3 ? s0[q[k]] : s1[q[k]]) - t0) / 100.0;      // us after the first block's start (100 MHz counter)
     c->tl_summary[8] = (double)m;
-    if (c->debug_coop) fprintf(stderr, "[rts] blocks of handle %p (us after the first start): start p50 %.1f max %.1f | end min %.1f p10 %.1f p50 %.1f p90 %.1f max %.1f\n", (void*)c,
+    if (c->tune.debug_coop) fprintf(stderr, "[rts] blocks of handle %p (us after the first start): start p50 %.1f max %.1f | end min %.1f p10 %.1f p50 %.1f p90 %.1f max %.1f\n", (void*)c,
                                c->tl_summary[1], c->tl_summary[2], c->tl_summary[3], c->tl_summary[4], c->tl_summary[5], c->tl_summary[6], c->tl_summary[7]);
 }
 
@@ -1081,7 +1053,7 @@ extern "C" int rts_trace_pulse_end(RtsHandle c)
     if (!c->pulse.end()) { rts_set_error("rts_trace_pulse_end: no pulse in flight on this handle"); return RTS_ERR_INVALID; }
     RTS_HIP(rts_stream_wait(c, c->stream));         // the one host sync of the launch: the received count sizes what follows
     { int rc = rts_pulse_home(c); if (rc != RTS_OK) return rc; }
-    if (c->debug_coop && c->d_order_sum.p && c->d_tile_ctr.p) pulse_debug_dump(c, c->pin.p->cnt);
+    if (c->tune.debug_coop && c->d_order_sum.p && c->d_tile_ctr.p) pulse_debug_dump(c, c->pin.p->cnt);
     c->res.agg_timed = false; c->res.fin_timed = false;
     return rts_post_received(c);
 }
@@ -1145,7 +1117,7 @@ static int rts_post_chain(RtsContext* c, bool ordered = false)      // ordered: 
     // (one block does in 150 us what seven launches -- four of them many blocks wide -- do in 92 us + six launch gaps for BASELINE configs[2]'s
     // ~1 900 received rays; for a few hundred rays it is the other way round: sequential pulses, one kernel against seven, C3 1.025 / 0.980 ms,
     // C2 (400 rays) 0.339 / 0.354, configs[4] (100) 0.955 / 0.978, profiles/r04_post_one_ab.log -- so the choice follows the handle's last count)
-    if (!ordered && q.mode == 0 && c->res.recv_dev && c->recv_hint_valid && c->recv_hint <= c->post_one_max && c->post_small && !keep_all && !c->res.mirror.want && c->res.n_recv <= c->spec_cap) {
+    if (!ordered && q.mode == 0 && c->res.recv_dev && c->recv_hint_valid && c->recv_hint <= c->tune.post_one_max && c->tune.post_small && !keep_all && !c->res.mirror.want && c->res.n_recv <= c->spec_cap) {
         // the speculative chain as ONE kernel (rts_post.hip: k_post_all): sized for the capacity, the count from the device
         RTS_HIP(hipEventRecord(c->ev[4], st)); RTS_HIP(hipEventRecord(c->ev[5], st)); RTS_HIP(hipEventRecord(c->ev[6], st));
         c->res.agg_pending.valid = false; c->res.groups.clear();
@@ -1201,7 +1173,7 @@ extern "C" int rts_trace_pulse_end_uniform(RtsHandle c, const double* rcs_per_ta
 static bool rts_speculates(const RtsContext* c, uint32_t cap)
 {
     const bool keep_all = (c->params.flags & RTS_FLAG_KEEP_ALL_RAYS) != 0;
-    return c->post_small && c->spec_enabled && cap > 0 && !keep_all && c->n_rays > 0 && c->recv_hint_valid && c->recv_hint <= ((uint64_t)cap * 3ull) / 4ull;
+    return c->tune.post_small && c->tune.spec_enabled && cap > 0 && !keep_all && c->n_rays > 0 && c->recv_hint_valid && c->recv_hint <= ((uint64_t)cap * 3ull) / 4ull;
 }
 // ... and its enqueueing: the pulse is closed and awaits its resolution (rts_spec_resolve), the chain runs sized for the capacity
 // with the count itself from the device (the handle's own stream already waits for the trace: rts_trace_pulse_begin)

@@ -455,7 +455,7 @@ extern "C" int rts_cube_render_beat(RtsHandle c, uint32_t pulse_index, const Rts
     if (!paths && (!std::isfinite(carrier) || carrier < 0.0)) { rts_set_error("rts_cube_render_beat: carrier = %g (finite, >= 0, with RTS_RENDER_RAYS)", carrier); return RTS_ERR_INVALID; }
     CHECK_CLOSED(c);
     if (paths) { int rc = rts_render_paths_check(c, "rts_cube_render_beat"); if (rc != RTS_OK) return rc; }
-    const RtsBeatPlan plan = rts_beat_plan(c->res.n_recv, c->cube.params.n_rx, c->cube.params.n_bins, c->cube.beat_force_parts);
+    const RtsBeatPlan plan = rts_beat_plan(c->res.n_recv, c->cube.params.n_rx, c->cube.params.n_bins, c->tune.beat_force_parts);
     if (!plan.supported) { rts_set_error("rts_cube_render_beat: %llu received rays: more than the launch takes", (unsigned long long)c->res.n_recv); return RTS_ERR_INVALID; }
     return rts_cube_beat_device(c, pulse_index, *p, plan, cspeed, carrier, c->res.agg_base_local);
 }
@@ -673,7 +673,7 @@ extern "C" int rts_cube_backproject(RtsHandle c, const RtsImageParams* p, void* 
     if ((p->flags & RTS_IMAGE_ACCUMULATE) && !device_out && !(c->cube.image.valid && c->cube.img_nx == p->n_x && c->cube.img_ny == p->n_y)) {
         rts_set_error("rts_cube_backproject: RTS_IMAGE_ACCUMULATE without device_out needs a library-owned image of the same n_x, n_y"); return RTS_ERR_INVALID; }
     CHECK_CLOSED(c);
-    const RtsImagePlan plan = rts_image_plan(p->n_x, p->n_y, q.n_rx, p->n_pulses, c->cube.img_split_below);
+    const RtsImagePlan plan = rts_image_plan(p->n_x, p->n_y, q.n_rx, p->n_pulses, c->tune.img_split_below);
     const size_t doubles = 2 * (size_t)q.n_rx * p->n_y * p->n_x;
     double* out; RTS_HIP(c->cube.image.place(device_out, doubles, &out));       // (accumulate: the shape is the same, so the buffer stays)
     // the geometry [tx | rx | w] -> pinned staging -> the device, on the stream

@@ -21,6 +21,8 @@
 #include "rts_launch_plan.h"      // RTS_BLOCK, RTS_WTILE, RTS_COOP_GROUP, RTS_STACK_OVF and the host arithmetic of a launch
 #include "rts_post_plan.h"        // RTS_SMALL_CAP32 / 64, RTS_AGG_TILE and the host arithmetic of the post-processing
 #include "rts_pulse_state.h"      // RtsPulseState: IDLE / OPEN / CHAINED, and the only code that moves the per-device count of open pulses
+#include "rts_tuning.h"           // RTS_STACK_LDS; RtsTuning, RtsSceneTuning: what the RTS_* environment switches fill, their table and its reader
+static_assert(RtsTuning().img_split_below == RTS_IMAGE_SPLIT_BELOW, "the default of RTS_IMAGE_SPLIT_BELOW is rts_image.h's");
 
 // ----------------------------------------------------------------------------- HBM layout
 // BVH4 node, 128 B = one cache line, of the static target-space hierarchy (rts_sah.cpp): half the dependent fetch
@@ -116,9 +118,6 @@ static_assert(sizeof(RtsChildState) == 128, "child state size");
 #define RTS_OFF_BINS (RTS_OFF_COUNTERS + 32)
 #define RTS_OFF_TAKEN (RTS_OFF_BINS + RTS_TILE_BUCKETS)
 #define RTS_ZERO_WORDS (RTS_OFF_TAKEN + RTS_TILE_BUCKETS)
-#ifndef RTS_STACK_LDS
-#define RTS_STACK_LDS 24            // traversal stack entries kept in LDS per lane
-#endif
 #ifndef RTS_RX_LDS
 #define RTS_RX_LDS 16               // receivers whose capture spheres the trace kernel keeps in LDS (the rest are read from memory)
 #endif
@@ -325,14 +324,13 @@ struct RtsCubeState {
     // call's geometry [tx | rx | w] goes through a staged upload; the chunk sums of a split launch
     RtsCubeProduct image; uint32_t img_nx = 0, img_ny = 0;
     StagedUpload<double> img_geo; DevBuf<double> d_img_scratch;
-    uint32_t img_split_below = RTS_IMAGE_SPLIT_BELOW;      // RTS_IMAGE_SPLIT_BELOW: workgroups below which the pulse chunks go on the grid (tests: 0 = never, 65536 = whenever there are two chunks)
     // spectrogram (rts_cube_spectrogram, rts_stft.hip): the output, for rts_cube_spectrogram_get; the call's window goes through a
     // staged upload; the tile sums of RTS_STFT_SUM_BINS
     RtsCubeProduct stft;
     StagedUpload<double> stft_win; DevBuf<double> d_stft_part;
-    // FMCW (rts_beat.hip): the part sums of a beat render (rts_cube_render_beat) and the parts forced on its plan (RTS_BEAT_PARTS, the
-    // tests: 0 = the plan's own); the range transform's output (rts_cube_range_transform), for rts_cube_range_get, and its staged window
-    DevBuf<double> d_beat_part; uint32_t beat_force_parts = 0;
+    // FMCW (rts_beat.hip): the part sums of a beat render (rts_cube_render_beat); the range transform's output
+    // (rts_cube_range_transform), for rts_cube_range_get, and its staged window
+    DevBuf<double> d_beat_part;
     RtsCubeProduct range;
     StagedUpload<double> range_win;
     // beamforming (rts_cube_beamform, rts_beam.hip): the output, for rts_cube_beam_get; the call's weight table goes through a staged upload
@@ -368,13 +366,12 @@ struct RtsPulseResults {
 
 struct RtsContext {
     RtsParams params;
+    RtsTuning tune;                 // what the handle's RTS_* switches said at rts_create (rts_tuning.h); everything below is resources and state
     uint32_t depth = 0;             // D = max_refr + max_refl
     int device = 0;
     hipStream_t stream = nullptr;       // scene placement, ordering, finalise, aggregation (high priority: short kernels)
     hipStream_t tstream = nullptr;      // trace kernels (the link group's, see RtsGate)
     hipStream_t cstream = nullptr; hipEvent_t ev_coop[2] = {nullptr, nullptr};      // the cooperative trace kernel of a launch runs beside the ordinary one; stream created on first use (rts_trace.hip)
-    uint32_t coop_grid_max = 1024;      // most blocks of the cooperative kernel (RTS_COOP_GRID)
-    uint32_t coop_spread = 1;           // XCD lists a head tile's units are dealt to (RTS_COOP_SPREAD = 1 / 2 / 4 / 8)
     uint32_t n_head_hint = 0;           // head count of the handle's previous order build (came home with that launch's counters)
     uint32_t last_coop_grid = 0;        // blocks of the cooperative kernel in the handle's last launch (0: none was launched)
     hipEvent_t ev[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -385,8 +382,6 @@ struct RtsContext {
     DevBuf<char> d_params;              // device image of RtsPinned's [lc | motion | td]
     RtsLaunchConsts* p_lc = nullptr; RtsTargetMotion* p_motion = nullptr; RtsTargetDev* p_targets = nullptr;     // ... and its parts
     // hierarchy: static nodes + leaf order (set_scene), leaf records refreshed per pulse
-    uint32_t stack_lds = RTS_STACK_LDS;
-    int grid_mult = 4, grid_spare = 160; bool grid_spare_forced = false; bool tile_lpt = true; double ew_rel = 1.7763568394002505e-15;   // per-handle knobs (rts_create reads RTS_GRID_MULT / RTS_GRID_SPARE / RTS_TILE_LPT / RTS_EW_REL)
     DevBuf<RtsLeafTri> d_leaves; DevBuf<char> d_sort_tmp;
     // receivers
     DevBuf<RtsRxDev> d_rx; uint32_t n_rx = 0;
@@ -394,27 +389,14 @@ struct RtsContext {
     uint64_t ray_first = 0; uint32_t n_rays = 0;
     DevBuf<RtsEndRecord> d_recv, d_all; DevBuf<unsigned long long> d_block_counters, d_timeline; unsigned long long* p_counters = nullptr;      // (the 16 counters live behind the draw counters: one fill zeroes both)
     DevBuf<uint32_t> d_tile_cost, d_tile_key, d_tile_order, d_tile_ctr;
-    RtsTileHist* hist = nullptr; bool share_history = true;      // never null after rts_create; shared with the handles of the same scene (rts_share_scene) unless RTS_SHARE_HISTORY=0
-    uint32_t coop_floor = 7500;         // ... more than this many cost units (shader clocks >> 6; 7 500 = 0.2 ms of one wave) (RTS_COOP_FLOOR)
-    uint32_t coop_walk_steps_lo = 400; double coop_mid = 1.5;      // LONGISH WALKS (RTS_COOP_STEPS_LO) go to the head only if the tile cost more than coop_mid x the balanced time (RTS_COOP_MID; 0: never).  3 in round 4;
-                                        // re-scanned in round 5, when the dead work had left the balanced time and the cooperative records had stopped flip-flopping (rts_record_to_keep): 1.5 takes a lone
-                                        // BASELINE configs[3] launch from 7.4 to 4.75 ms and the pipelined pulse from 5.23 to 5.06, configs[2] / [4] / [1] do not move (profiles/r05c_coop_mid_scan.log)
-    uint32_t coop_walk_steps = 1000;     // ... and whose bounce rounds took at least this many walk iterations each, on average (RTS_COOP_STEPS; 0: every tile above the floor is flagged) --
-                                        // counted by the kernel, so neither other pulses sharing the GPU nor a launch that is all tail move it
-    double coop_big_part = 1.5, coop_big_now = 0.0;      // coop_big for a launch that is a PART of a pulse (interleaved or dealt tiles) on a GPU no other pulse shares (RTS_COOP_BIG_PART; 0: off) -- one
-                                        // pulse split over N GPUs for latency: such a launch is all tail, 1-2 ms tiles of moderately long walks bound it, and the ~5 x work of
-                                        // cooperative units is free on an idle chip: one GPU's eighth of a BASELINE configs[3] pulse 1.1-2.3 -> 1.1-1.5 ms (profiles/r04_c4_deal*.log).  Whole pulses:
-                                        // off (configs[4] one pulse at a time loses 3-5 % with it, the others do not move, profiles/r04_coop_big_inflight1.log); coop_big_now: the launch's value
-    double coop_big = 0.0;              // ... or ANY tile costing more than this multiple of the balanced time, whatever its shape (RTS_COOP_BIG; 0 = off, the default:
-                                        // measured on C3 at 0.8 / 1.0 / 1.3 -- the slowest tile of a launch is rarely the slowest of the previous one once the target moves,
-                                        // the launch's duration did not change (0.70-0.77 ms, peaks of 1.0 ms as before) and the handle's first such launch takes 10 ms)
-    double coop_frac = 0.5;            // a tile costing more than this fraction of the launch's balanced time is traced as cooperative units (RTS_COOP_FRAC; 0: never)
+    RtsTileHist* hist = nullptr;        // never null after rts_create; shared with the handles of the same scene (rts_share_scene) unless tune.share_history is off
+    double coop_big_now = 0.0;          // this launch's tune.coop_big: tune.coop_big_part when the launch is a part of a pulse on a GPU no other pulse shares
     bool tile_cost_pending = false; uint64_t tile_cost_sig[4] = {0, 0, 0, 0};   // this handle's last launch left cost records that are not merged into the history yet (rts_post.hip)
     // tiles DEALT to this handle (rts_set_tile_list: ray sharding balanced by last-seen cost instead of interleaved parts): ascending tile
     // numbers in units of il_list_tile launch indices; a pulse with interleave_parts == RTS_INTERLEAVE_LIST traces them
     DevBuf<uint32_t> d_il_list; uint32_t il_list_n = 0, il_list_tile = 0, il_list_gen = 0; uint32_t il_list_last = 0;
     uint64_t tile_last_sig[4] = {0, 0, 0, 0}; bool tile_last_valid = false; DevBuf<uint32_t> d_rec_tmp;      // shape of the last launch that recorded costs (rts_tile_records_get)
-    DevBuf<float> d_dir_hist; DevBuf<uint32_t> d_pmask; bool use_pmask = true, pre_dense = false;
+    DevBuf<float> d_dir_hist; DevBuf<uint32_t> d_pmask; bool pre_dense = false;
     DevBuf<int32_t> d_hit_prim; DevBuf<float> d_hit_t; DevBuf<int32_t> d_stack_ovf; DevBuf<RtsChildState> d_child;
     DevBuf<uint64_t> d_rk64, d_rk64_sorted;
     RtsTraceArgs last_args; RtsLaunchConsts last_lc;
@@ -426,22 +408,13 @@ struct RtsContext {
     DevBuf<uint64_t> d_akeys, d_akeys_sorted; DevBuf<uint32_t> d_aidx, d_aidx_sorted; DevBuf<uint32_t> d_ghead, d_gid;
     DevBuf<double> d_gsum; DevBuf<uint32_t> d_gmin; DevBuf<uint64_t> d_gkey; DevBuf<uint32_t> d_gcount; DevBuf<uint64_t> d_grow; DevBuf<int32_t> d_gpath;
     DevBuf<double> d_delay, d_phase; DevBuf<int32_t> d_pathmatch; DevBuf<double> d_rcs;
-    bool rx_window_screen = true;       // RTS_RX_WINDOW_SCREEN
-    bool timeline_blocks = false; double tl_summary[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};      // RTS_TIMELINE_BLOCKS (rts_get_block_timeline)
-    uint32_t tl_blocks = 0;             // debug (RTS_TIMELINE_BLOCKS): blocks whose start / end ticks this launch recorded
-    bool coop_versions = true;          // RTS_COOP_VERSIONS
-    int batch_dead = 1;                 // dead-tile batches of the trace kernel (RTS_DEAD_BATCH = 0 / 1 / all)
-    bool node_versions = true;          // the ordinary trace kernel walks the octant versions of the node records when the scene has them (RTS_NODE_VERSIONS=0: the role fetch + sorting network)
-    bool debug_coop = false;            // RTS_DEBUG_COOP: one line per launch on stderr (grids, head hint, thresholds)
-    bool spin_wait = true;              // the pulse's two host waits poll the stream instead of blocking (rts_stream_wait; RTS_SPIN_WAIT=0)
+    double tl_summary[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};      // tune.timeline_blocks: the last launch's percentiles (rts_get_block_timeline)
+    uint32_t tl_blocks = 0;             // ... and the blocks whose start / end ticks this launch recorded
     bool order_sum_valid = false; DevBuf<unsigned long long> d_order_sum;      // the tile order in two launches when the previous launch had this launch's shape: d_order_sum holds that launch's cost sum (rts_post.hip: rts_tile_order_build)
     bool verts_world_valid = false;     // d_verts_world holds the current placement (the per-pulse scene update is one launch that writes the leaf records only: rts_scene_place)
-    uint32_t post_prio = 3;             // s_setprio of k_post_all's waves (RTS_POST_PRIO = 0 .. 3)
-    uint64_t post_one_max = 1024;       // rts_trace_pulse_end_uniform: ONE kernel for order + expand + finalise + cube + aggregation when the handle's previous pulse received at most this many rays (RTS_POST_ONE_MAX); above it the seven launches are faster
-    bool post_small = true;             // received sets of up to 4096 rays are ordered / finished by single blocks (RTS_POST_SMALL=0: the general chain)
-    hipStream_t tstream_now = nullptr; bool trace_own_stream = true;      // the stream this pulse's trace kernel went to (rts_trace_pulse_begin; RTS_TRACE_OWN_STREAM=0: always the trace stream)
+    hipStream_t tstream_now = nullptr;  // the stream this pulse's trace kernel went to (rts_trace_pulse_begin; tune.trace_own_stream off: always the trace stream)
     uint32_t spec_cap = RTS_SMALL_CAP64;
-    RtsSpecParams spec; bool spec_enabled = true;      // rts_trace_pulse_end_uniform: parameters of the chain, which may be enqueued on the device-side count (pulse.chained(); RTS_SPECULATE=0: never)
+    RtsSpecParams spec;                 // rts_trace_pulse_end_uniform: parameters of the chain, which may be enqueued on the device-side count (pulse.chained(); tune.spec_enabled off: never)
     uint64_t recv_hint = 0; bool recv_hint_valid = false;                    // received rays of the handle's previous pulse
     RtsPulseResults res;                // what the last pulse left for its accessors (rts_results_api.hip)
     PinBuf<RtsRxDev> pin_rx; std::vector<RtsRxDev> rx_host;      // receivers: last values set (an unchanged set is not uploaded again) and the pinned staging of the asynchronous upload
@@ -478,7 +451,7 @@ void rts_gate_unref(RtsGate* g);            // ... and destroys the group's trac
 
 // implemented in the .hip units
 int rts_sah_build(const double* verts, const uint32_t* tris, uint32_t n_tris, double split_budget, std::vector<RtsNode4>& nodes, std::vector<uint32_t>& leaf_prim, RtsBlasInfo& out);
-int rts_lbvh_build_device(RtsContext* c, RtsScene* ns, const std::vector<uint32_t>& vidx, const std::vector<RtsMeshHost>& mh, double split_budget);
+int rts_lbvh_build_device(RtsContext* c, RtsScene* ns, const std::vector<uint32_t>& vidx, const std::vector<RtsMeshHost>& mh, const RtsSceneTuning& tune);
 int rts_scene_place(RtsContext* c, const RtsLaunchConsts& lc, bool place, uint32_t* pmask);      // placement kernels (place) + the primary-ray mask (lc.mask.n != 0)
 int rts_tile_costs_flush(RtsContext* c);      // merge the cost records of the last launch into the history now (before its launch shape goes away)
 int rts_tile_records_masked(RtsContext* c, uint32_t* d_out, uint32_t n);      // the history's records of the tiles the last launch traced, 0 elsewhere

@@ -647,7 +647,7 @@ __global__ void k_valid_key(const float* __restrict__ ref_box, uint64_t* __restr
 // ns->d_leaf_prim, ns->blas, ns->n_nodes, ns->n_leaves.  Uses the handle's stream; temporaries are freed before returning.
 // split_budget: aimed-at extra references per triangle (0: one reference per triangle); the threshold of ref_count is the
 // mesh's mean box area / (1 + budget)^2, i.e. an average triangle gets about 1 + budget references.
-int rts_lbvh_build_device(RtsContext* c, RtsScene* ns, const std::vector<uint32_t>& vidx, const std::vector<RtsMeshHost>& mh, double split_budget)
+int rts_lbvh_build_device(RtsContext* c, RtsScene* ns, const std::vector<uint32_t>& vidx, const std::vector<RtsMeshHost>& mh, const RtsSceneTuning& tune)
 {
     hipStream_t st = c->stream;
     const uint32_t n_targets = (uint32_t)mh.size();
@@ -685,11 +685,11 @@ int rts_lbvh_build_device(RtsContext* c, RtsScene* ns, const std::vector<uint32_
         RTS_HIP(d_tmp.reserve(need)); tmp = std::max(tmp, need);
         return RTS_OK;
     };
-    bool sah_tree = true;                                          // top-down binned SAH (default) or the Morton / Karras tree
-    { const char* e = getenv("RTS_DEVICE_TREE"); if (e) sah_tree = strcmp(e, "lbvh") != 0; }
+    const double split_budget = tune.split_budget;
+    const bool sah_tree = tune.sah_tree;                           // top-down binned SAH (default) or the Morton / Karras tree
     // (crowding rounds -- a provisional tree, twice the slabs for triangles in crowded spots, the host builder's second stage: built,
     // measured on C3 at 0 / 1 / 2 rounds: 0.812 / 0.810 / 0.830 ms, and they double the build time: off unless RTS_CROWD_ROUNDS asks)
-    int crowd_rounds = 0; { const char* e = getenv("RTS_CROWD_ROUNDS"); if (e) crowd_rounds = std::max(0, std::min(3, atoi(e))); }
+    const int crowd_rounds = tune.crowd_rounds;
     DevBuf<uint32_t> d_sah_bins, d_sah_cb, d_sah_fill, d_boost; DevBuf<SahSplit> d_sah_split; DevBuf<SahWork> d_sah_work_a, d_sah_work_b;
     DevBuf<RtsNode4> d_nodes4_tmp; DevBuf<uint32_t> d_reach, d_newid, d_rflag;
     RTS_HIP(d_boost.reserve((size_t)ns->n_prims + 2)); RTS_HIP(hipMemsetAsync(d_boost.p, 0, sizeof(uint32_t) * ((size_t)ns->n_prims + 2), st));       // per triangle: 1 = twice the slabs (k_crowd); last word: a counter
@@ -739,7 +739,7 @@ int rts_lbvh_build_device(RtsContext* c, RtsScene* ns, const std::vector<uint32_
     RTS_HIP(rocprim::exclusive_scan(nullptr, scan_tmp, d_cnt.p, d_off.p, 0u, n_max, rocprim::plus<uint32_t>(), st));
     RTS_HIP(d_scan_tmp.reserve(scan_tmp + 16));
     std::vector<double> a_thr(n_targets, 0.0); std::vector<uint32_t> n_refs(n_targets, 0), n_valid(n_targets, 0);
-    int gain_rule = 1; { const char* e = getenv("RTS_REF_GAIN_RULE"); if (e) gain_rule = atoi(e) != 0; }
+    const int gain_rule = tune.ref_gain_rule;
     auto count_refs = [&](uint32_t t) -> int {                       // cnt / off of mesh t (deterministic: pass B repeats it)
         const uint32_t n = mh[t].n_tris;
         const uint32_t* tv = ns->d_tri_vidx.p + 3 * (size_t)mh[t].tri_base;
@@ -782,7 +782,7 @@ int rts_lbvh_build_device(RtsContext* c, RtsScene* ns, const std::vector<uint32_
             RTS_HIP(hipMemcpyAsync(&before, n_boosted, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
             k_crowd<<<blocks_for(n_valid[t], 256), 256, 0, st>>>(d_nodes2.p, d_prim_box.p, d_vals_sorted.p, d_ref_tri.p, tv, ns->d_verts_local.p, n_valid[t], d_boost.p + mh[t].tri_base, n_boosted);
             RTS_HIP(hipMemcpyAsync(&after, n_boosted, sizeof(uint32_t), hipMemcpyDeviceToHost, st)); RTS_HIP(hipStreamSynchronize(st));
-            if (getenv("RTS_DEBUG_BUILD")) fprintf(stderr, "[rts build] mesh %u round %d: %u triangles, %u references (%u valid), %u triangles boosted\n", t, round, n, n_refs[t], n_valid[t], after - before);
+            if (tune.debug_build) fprintf(stderr, "[rts build] mesh %u round %d: %u triangles, %u references (%u valid), %u triangles boosted\n", t, round, n, n_refs[t], n_valid[t], after - before);
             if (after == before) break;
             { int rc = count_refs(t); if (rc != RTS_OK) return rc; }
             { int rc = read_counts(t); if (rc != RTS_OK) return rc; }

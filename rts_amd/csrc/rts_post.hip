@@ -161,7 +161,7 @@ struct RtsHeadRule { double frac, big, mid; uint32_t floor_cost, resident_waves;
 //   launch -- a launch that consists of its tail, e.g. one GPU's eighth of a BASELINE configs[3] pulse, where the ~5 x more work of
 //   64 units with short walks is free because the chip is idle; in a launch that is busy throughout the same tile stays where it is:
 //   BASELINE configs[4] lost 9 % when such tiles were made cooperative, profiles/r04_coop_steps_scan.log); or
-//   the experiment RtsContext::coop_big.
+//   the experiment RtsTuning::coop_big.
 __device__ __forceinline__ bool rts_head_rule(const uint32_t est, const double cost, const double balanced, const double thr, const double thr_big, const RtsHeadRule& rule)
 {
     const double thr_mid = fmax(rule.mid * balanced, (double)rule.floor_cost);
@@ -220,7 +220,7 @@ __global__ void k_tile_keys(const uint32_t* __restrict__ hist, uint32_t n_hist, 
             }
         }
         // head of the order = the tiles the cooperative kernel traces: LONG WALKS tiles above frac x the balanced time (and, as an
-        // experiment that is OFF by default -- RtsContext::coop_big -- any tile above big x the balanced time).  The half of the
+        // experiment that is OFF by default -- RtsTuning::coop_big -- any tile above big x the balanced time).  The half of the
         // bins is this DECISION (not the record's flag): the head is a prefix of the order.
         const uint32_t cost = est & 0x3fffffffu;
         if (head_count && rule.frac > 0.0) {
@@ -413,10 +413,10 @@ int rts_tile_order_build(RtsContext* c, const uint64_t* prev_sig, bool prev_vali
     // the one BOTH shapes mean: rts_set_tile_list merges pending cost records before it replaces the list)
     auto shape = [c](const uint64_t* sig) { RtsTileShape s; s.first = sig[1]; s.il_tile = (uint32_t)(sig[2] & 0xffffffffu); s.il_parts = (uint32_t)(sig[2] >> 32); s.il_part = (uint32_t)sig[3];
                                            s.n_tiles = (uint32_t)rts_wave_tiles(sig[0]); s.il_list = s.il_parts == RTS_INTERLEAVE_LIST ? c->d_il_list.p : nullptr; return s; };
-    uint32_t* head = c->coop_frac > 0.0 ? c->d_tile_ctr.p + RTS_OFF_HEAD : nullptr;      // [sum lo, sum hi, count, pad]: zeroed with the draw counters
+    uint32_t* head = c->tune.coop_frac > 0.0 ? c->d_tile_ctr.p + RTS_OFF_HEAD : nullptr;      // [sum lo, sum hi, count, pad]: zeroed with the draw counters
     uint32_t* bins = c->d_tile_ctr.p + RTS_OFF_BINS, *taken = c->d_tile_ctr.p + RTS_OFF_TAKEN, *live = c->d_tile_ctr.p + RTS_OFF_LIVE;      // zeroed with the draw counters
     const RtsTileShape cur = shape(cur_sig);
-    const RtsHeadRule rule = {c->coop_frac, c->coop_big_now, c->coop_mid, c->coop_floor, resident_waves};
+    const RtsHeadRule rule = {c->tune.coop_frac, c->coop_big_now, c->tune.coop_mid, c->tune.coop_floor, resident_waves};
     RTS_HIP(c->d_tile_key.reserve(n_tiles_cur)); RTS_HIP(c->d_tile_order.reserve(n_tiles_cur)); RTS_HIP(c->d_order_sum.reserve(1));
     unsigned long long* persist = c->d_order_sum.p;      // the cost sum of the launch before, kept from build to build for the two-launch form
     if (prev_valid && memcmp(prev_sig, cur_sig, 4 * sizeof(uint64_t)) == 0 && c->order_sum_valid) {
@@ -456,7 +456,7 @@ int rts_post_order_and_expand(RtsContext* c)
     hipStream_t st = c->stream;
     { int rc = rts_recv_reserve(c, R); if (rc != RTS_OK) return rc; }
     size_t tmp = 0;
-    if (c->post_small && R <= rts_small_cap_recv(c)) {
+    if (c->tune.post_small && R <= rts_small_cap_recv(c)) {
         // items per thread by the size of the set (a speculative chain -- count on the device -- is sized for the capacity)
         const uint32_t cap = c->res.recv_dev ? rts_small_cap_recv(c) : R, items = rts_small_items(cap), bits = rts_recv_sort_bits(c->n_rays, c->last_args.max_refr);
         auto order = [&](auto kernel, int with_chain) { kernel<<<1, RTS_SMALL_THREADS, 0, st>>>(c->d_recv.p, R, c->n_rays, with_chain, bits, c->d_ri_sorted.p, c->res.recv_dev); };
@@ -1249,7 +1249,7 @@ int rts_post_all_small(RtsContext* c, uint32_t cap, const RtsSpecParams& sp, boo
     if (q.cube_on) { const RtsCubeParams& cp = c->cube.params; q.cube = c->cube.p; q.cube_rx = cp.n_rx; q.cube_pulses = cp.n_pulses; q.cube_bins = cp.n_bins; q.cube_pulse = (uint32_t)sp.cube_pulse; q.cube_t0 = cp.t0; q.cube_dt = cp.dt; }
     q.B = k.B; q.key_bits = k.key_bits; q.ahead = c->d_ghead.p;
     q.fin = rts_agg_finish_args(c, k, s, cap, c->d_rx_rays.p, use_rows ? c->d_rx_slots.p : nullptr, base, want_groups);
-    q.R_dev = c->p_counters; q.prio = c->post_prio;
+    q.R_dev = c->p_counters; q.prio = c->tune.post_prio;
     const bool kr64 = rts_recv_key64(c->last_args.max_refr), ka64 = rts_agg_key64(k);
     if (sp.fin == 0) rts_post_all_launch(st, q, kr64, ka64, RtsFinUniform{});
     else {
@@ -1287,7 +1287,7 @@ int rts_aggregate_device(RtsContext* c, int32_t max_path, int32_t max_rx, const 
     { int rc = rts_agg_scratch(c, k, R, d_rows != nullptr, &s); if (rc != RTS_OK) return rc; }
     size_t tmp = 0;
     const uint32_t small_cap = rts_small_cap(rts_agg_key64(k));
-    const bool small = c->post_small && !k.wide && R <= small_cap;       // one block orders, one block finishes (see k_agg_order_small)
+    const bool small = c->tune.post_small && !k.wide && R <= small_cap;       // one block orders, one block finishes (see k_agg_order_small)
     if (small) {
         const uint32_t cap = c->res.recv_dev ? small_cap : R;             // (a chain enqueued on the device-side count is sized for the capacity)
         auto order = [&](auto kernel) { kernel<<<1, RTS_SMALL_THREADS, 0, st>>>(d_rays, d_paths, R, D, k.B, k.key_bits, c->d_akeys_sorted.p, c->d_aidx_sorted.p, c->d_ghead.p, c->d_gid.p, s.gstart, c->res.recv_dev); };

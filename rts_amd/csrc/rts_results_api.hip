@@ -43,7 +43,7 @@ extern "C" int rts_get_block_timeline(RtsHandle c, double* out, uint32_t n)
 {
     if (!c || !out) { rts_set_error("rts_get_block_timeline: null argument"); return RTS_ERR_INVALID; }
     CHECK_CLOSED(c);
-    if (!c->timeline_blocks || c->tl_summary[8] == 0.0) { rts_set_error("rts_get_block_timeline: the handle records no block timeline (create it with RTS_TIMELINE_BLOCKS=1, product build) or has not traced yet"); return RTS_ERR_INVALID; }
+    if (!c->tune.timeline_blocks || c->tl_summary[8] == 0.0) { rts_set_error("rts_get_block_timeline: the handle records no block timeline (create it with RTS_TIMELINE_BLOCKS=1, product build) or has not traced yet"); return RTS_ERR_INVALID; }
     for (uint32_t k = 0; k < n && k < 9; k++) out[k] = c->tl_summary[k];
     return RTS_OK;
 }
