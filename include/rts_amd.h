@@ -829,6 +829,90 @@ int rts_beamform_eval(const RtsCubeParams* q, const double* in, uint32_t n_rows_
 int rts_steering_make(const double* positions, uint32_t n_rx, const double* directions, uint32_t n_beams,
                       double wavelength, const double* taper, double* weights_out);                                      /* pure host */
 
+/* ---------------------------------------------------------------- adaptive (MVDR) beamforming: sample covariance and weight solve
+ * Weights computed FROM THE DATA for rts_cube_beamform: the sample covariance R of the receivers over a set of training cells, and
+ * the sample-matrix-inversion MVDR weights w = R^-1 s / (s^H R^-1 s) of steering rows s (rts_steering_make's layout).  Against a
+ * strong directional interferer a conventional beam is limited by its sidelobes; these weights place a null on it.  The arithmetic
+ * is rts_amd/csrc/rts_adapt.h, shared by the kernels (rts_adapt.hip) and the host evaluators (the library builds with
+ * -ffp-contract=off: the trees are the contract).  They hold + - * / and sqrt only, so device and evaluators agree BIT FOR BIT.
+ *
+ * rts_cube_covariance.  Input z[rx][row][bin], complex128, from the beamformer's three sources under the beamformer's rules
+ *   (RTS_BEAM_FROM_CUBE, _MAP, _POINTER; n_rows_in and device_in with _POINTER only; n_rx and n_bins are the attached cube's).
+ *   Training cells: rows first_row .. first_row + n_rows - 1 (n_rows 0: to the source's last row), bins first_bin .. first_bin +
+ *   n_bins - 1 (n_bins 0: to the last bin) WITHOUT the bins skip_first_bin .. skip_first_bin + skip_n_bins - 1 (the cells under test
+ *   and their guard, so that a target does not null itself; skip_n_bins 0: none, and skip_first_bin must be 0 then).  The skipped
+ *   interval lies inside the bin span and leaves at least one bin.  The cells are numbered row-major over the included bins,
+ *   c = 0 .. K - 1.
+ *     term(i, j, c) = z_i conj(z_j) = (ar br + ai bi, ai br - ar bi), a = z_i, b = z_j: four multiplies, one add, one subtract; j <= i.
+ *     The cells are cut into tiles = ceil(K / RTS_ADAPT_TILE) tiles of consecutive cells and parts = min(RTS_ADAPT_MAX_PARTS, tiles)
+ *     parts; part p owns the tiles floor(p tiles / parts) .. floor((p + 1) tiles / parts) - 1.  A part's sum runs over its cells in
+ *     ascending c, the first term the start value; the parts are summed in ascending p, part 0 the start value; each component is
+ *     then divided once by (double)K.  R[j][i] (j < i) is the exact conjugate (re, -im) of R[i][j]; the imaginary part of the
+ *     diagonal is stored as +0.0.  The partition is a function of the shape alone, never of the device.
+ *   Output complex128 [n_rx][n_rx], row-major, interleaved re / im.  No atomics: identical bits from run to run.
+ * rts_cube_mvdr.  cov: device_cov (caller-owned device memory [n_rx][n_rx] complex128, 16-byte aligned, n_rx the record's) or, with
+ *   device_cov NULL, the handle's last library-owned covariance (the record's n_rx is then 0 or that covariance's).  Only the lower
+ *   triangle is read, and of the diagonal only the real part.  steering: host, complex128 [n_beams][n_rx], finite; copied by the call.
+ *     1. A = R + loading I: one add per diagonal real part; loading >= 0 in the cube's power units (e.g. rts_cube_add_noise's
+ *        noise_power).
+ *     2. Column Cholesky A = L L^H, columns j ascending:
+ *          d = A_jj, then d = d - (L_jk.re L_jk.re + L_jk.im L_jk.im) for k = 0 .. j - 1 ascending;  L_jj = sqrt(d);
+ *          for i > j: x = A_ij, then x = x - L_ik conj(L_jk) (term's tree: a = L_ik, b = L_jk; re and im each one subtraction) for
+ *          k = 0 .. j - 1 ascending;  L_ij = (x.re / L_jj, x.im / L_jj).
+ *     3. Per beam b, s = steering[b]:
+ *          forward, rows i ascending:  x = s_i, then x = x - L_ik u_k = x - (lr ur - li ui, lr ui + li ur) for k = 0 .. i - 1 ascending;
+ *                                      u_i = (x.re / L_ii, x.im / L_ii);
+ *          den = the sum of (u_k.re u_k.re + u_k.im u_k.im) over ascending k, the k = 0 term the start value;
+ *          back, rows i descending:    x = u_i, then x = x - conj(L_ki) v_k = x - (lr vr + li vi, lr vi - li vr) for k = i + 1 .. n_rx - 1
+ *                                      ascending;  v_i = (x.re / L_ii, x.im / L_ii);
+ *          w[b][i] = (v_i.re / den, v_i.im / den).
+ *     With the beamformer's y = sum conj(w) z the beam is distortionless: w^H s = 1.
+ *     A pivot d that is not finite or not > 0 fails the solve at column j: EVERY weight of the output is NaN and a status word of the
+ *     handle on the device records j; rts_cube_mvdr_get then returns RTS_ERR_INVALID naming the pivot (the handle stays usable).
+ *   Output complex128 [n_beams][n_rx]: a weight table of rts_cube_beamform (n_rx <= RTS_BEAM_MAX_RX, n_beams <= RTS_BEAM_MAX_BEAMS,
+ *   n_beams * n_rx <= RTS_BEAM_MAX_WEIGHTS), which the caller moves with rts_cube_mvdr_get -> RtsBeamParams.weights.
+ * device_out of either call: caller-owned device memory of the output's size, 16-byte aligned, or NULL: library-owned, alive until
+ *   the next call of another size, rts_cube_attach or rts_destroy; rts_cube_covariance_get / rts_cube_mvdr_get synchronise and copy
+ *   the library-owned output (RTS_ERR_INVALID after an rts_cube_attach or with none, RTS_ERR_CAPACITY when capacity_doubles is too
+ *   small).  A caller-owned output is not recorded.  The calls are enqueued on the handle's stream and never wait for the device's
+ *   earlier work (rts_cube_mvdr: only for the copy of the PREVIOUS call's steering out of the handle's pinned staging block).
+ * RTS_ERR_INVALID, the message naming the field: no cube attached; NULL p; nonzero reserved fields; an unknown source;
+ *   RTS_BEAM_FROM_MAP without a library-owned map; RTS_BEAM_FROM_POINTER with a NULL or misaligned device_in or n_rows_in 0; n_rows_in
+ *   or device_in with another source; rows or bins outside the source; a skipped interval outside the bin span, leaving no bin, or
+ *   skip_first_bin set with skip_n_bins 0; n_rx above RTS_BEAM_MAX_RX; more than 2^32 - 1 tiles; a misaligned device_out; a
+ *   device_out that overlaps the bytes the call reads; n_beams 0 or beyond the limits above; NULL or non-finite steering; a loading
+ *   that is negative or not finite; neither device_cov nor a library-owned covariance; a misaligned device_cov; an n_rx that is 0
+ *   with device_cov or differs from the library-owned covariance's.  A refused call leaves the handle's previous products as they
+ *   were.
+ * rts_covariance_eval / rts_mvdr_eval: pure host, no device: the same rts_adapt.h functions.  `in` [n_rx][n_rows_in][n_bins] stands for
+ *   the source p names, q for the attached cube (n_rx, n_bins); as rts_beamform_eval, with RTS_BEAM_FROM_POINTER p->n_rows_in must
+ *   equal the argument and device_in is not looked at.  rts_mvdr_eval reads cov [n_rx][n_rx] as the kernel does (device_cov is not
+ *   looked at, p->n_rx must equal the argument); a failed solve returns RTS_ERR_INVALID naming the pivot.  A refused or failed call
+ *   leaves out untouched. */
+#define RTS_ADAPT_TILE       64u    /* training cells per tile of the covariance's tree                                 */
+#define RTS_ADAPT_MAX_PARTS  512u   /* parts of the covariance's tree: the scratch is parts * n_rx^2 * 16 bytes (<= 32 MiB) */
+typedef struct RtsCovParams {
+    uint32_t source, n_rows_in;      /* RTS_BEAM_FROM_*; n_rows_in: POINTER only (0 otherwise)                       */
+    uint32_t first_row, n_rows;      /* n_rows 0: from first_row to the last row of the source                      */
+    uint32_t first_bin, n_bins;      /* n_bins 0: from first_bin to the last bin                                    */
+    uint32_t skip_first_bin, skip_n_bins;  /* bins left out of the training set; skip_n_bins 0: none                */
+    const void* device_in;           /* POINTER only                                                                */
+    uint64_t reserved[2];            /* 0 */
+} RtsCovParams;
+typedef struct RtsMvdrParams {
+    uint32_t n_beams, n_rx;          /* n_rx: with device_cov and in the evaluator; 0 or the covariance's otherwise  */
+    double loading;                  /* >= 0, finite: added to the diagonal                                         */
+    const double* steering;          /* host [n_beams][n_rx], interleaved re / im, finite                           */
+    const void* device_cov;          /* complex128 [n_rx][n_rx], 16-byte aligned; NULL: the last library-owned covariance */
+    uint64_t reserved[2];            /* 0 */
+} RtsMvdrParams;
+int rts_cube_covariance(RtsHandle h, const RtsCovParams* p, void* device_out);         /* complex128 [n_rx][n_rx] */
+int rts_cube_covariance_get(RtsHandle h, double* host_out, uint64_t capacity_doubles);
+int rts_covariance_eval(const RtsCubeParams* q, const double* in, uint32_t n_rows_in, const RtsCovParams* p, double* out);  /* pure host */
+int rts_cube_mvdr(RtsHandle h, const RtsMvdrParams* p, void* device_out);              /* complex128 [n_beams][n_rx] */
+int rts_cube_mvdr_get(RtsHandle h, double* host_out, uint64_t capacity_doubles);
+int rts_mvdr_eval(const double* cov, uint32_t n_rx, const RtsMvdrParams* p, double* out);                                     /* pure host */
+
 /* ---------------------------------------------------------------- backprojection imaging (SAR / ISAR) of the return cube
  * A derived product like the cube itself: time-domain backprojection of a coherent interval onto a planar
  * pixel grid -- exact for any track, any bistatic geometry and any target motion, where the slow-time DFT focuses only while a

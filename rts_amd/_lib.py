@@ -192,6 +192,23 @@ class RtsBeamParams(C.Structure):
 assert C.sizeof(RtsBeamParams) == 56
 
 
+RTS_ADAPT_TILE, RTS_ADAPT_MAX_PARTS = 64, 512
+
+
+class RtsCovParams(C.Structure):
+    _fields_ = [("source", C.c_uint32), ("n_rows_in", C.c_uint32), ("first_row", C.c_uint32), ("n_rows", C.c_uint32),
+                ("first_bin", C.c_uint32), ("n_bins", C.c_uint32), ("skip_first_bin", C.c_uint32), ("skip_n_bins", C.c_uint32),
+                ("device_in", C.c_void_p), ("reserved", C.c_uint64 * 2)]
+
+
+class RtsMvdrParams(C.Structure):
+    _fields_ = [("n_beams", C.c_uint32), ("n_rx", C.c_uint32), ("loading", C.c_double), ("steering", C.c_void_p),
+                ("device_cov", C.c_void_p), ("reserved", C.c_uint64 * 2)]
+
+
+assert C.sizeof(RtsCovParams) == 56 and C.sizeof(RtsMvdrParams) == 48
+
+
 class RtsSceneInfo(C.Structure):
     _fields_ = [("n_targets", C.c_uint32), ("n_prims", C.c_uint32), ("n_nodes", C.c_uint32), ("n_leaves", C.c_uint32),
                 ("handles_sharing", C.c_uint32), ("builder", C.c_uint32), ("build_ms", C.c_double),
@@ -282,7 +299,8 @@ EXPORTS = ["rts_create", "rts_destroy", "rts_last_error", "rts_device_count", "r
            "rts_cube_backproject", "rts_cube_image_get", "rts_backproject_eval",
            "rts_cube_spectrogram", "rts_cube_spectrogram_get", "rts_stft_eval", "rts_window_make",
            "rts_cube_render_beat", "rts_beat_eval", "rts_cube_range_transform", "rts_cube_range_get", "rts_range_eval",
-           "rts_cube_beamform", "rts_cube_beam_get", "rts_beamform_eval", "rts_steering_make"]
+           "rts_cube_beamform", "rts_cube_beam_get", "rts_beamform_eval", "rts_steering_make",
+           "rts_cube_covariance", "rts_cube_covariance_get", "rts_covariance_eval", "rts_cube_mvdr", "rts_cube_mvdr_get", "rts_mvdr_eval"]
 
 
 def lib():
@@ -374,6 +392,12 @@ def lib():
         "rts_cube_beam_get": [vp, vp, u64],
         "rts_beamform_eval": [C.POINTER(RtsCubeParams), vp, u32, C.POINTER(RtsBeamParams), vp],
         "rts_steering_make": [vp, u32, vp, u32, C.c_double, vp, vp],
+        "rts_cube_covariance": [vp, C.POINTER(RtsCovParams), vp],
+        "rts_cube_covariance_get": [vp, vp, u64],
+        "rts_covariance_eval": [C.POINTER(RtsCubeParams), vp, u32, C.POINTER(RtsCovParams), vp],
+        "rts_cube_mvdr": [vp, C.POINTER(RtsMvdrParams), vp],
+        "rts_cube_mvdr_get": [vp, vp, u64],
+        "rts_mvdr_eval": [vp, u32, C.POINTER(RtsMvdrParams), vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name, None)

@@ -497,6 +497,54 @@ def beam_angles(coordinate, directions):
     return np.stack([np.interp(c, idx, d[:, k]) for k in range(d.shape[1])], axis=-1)
 
 
+def _cov_params(source, first, count, first_bin, n_bins, skip, device_in, n_rows_in):
+    """RtsCovParams: rows first .. first + count - 1 (count None: to the last), bins first_bin .. first_bin + n_bins - 1 (n_bins None: to
+    the last) without skip = (first skipped bin, how many) or None"""
+    p = L.RtsCovParams()
+    p.source, p.n_rows_in = _BEAM_SOURCES.get(source, source), int(n_rows_in)
+    p.first_row, p.n_rows, p.first_bin, p.n_bins = int(first), int(count or 0), int(first_bin), int(n_bins or 0)
+    p.skip_first_bin, p.skip_n_bins = (int(skip[0]), int(skip[1])) if skip is not None else (0, 0)
+    p.device_in = device_in if device_in else None
+    return p
+
+
+def covariance_eval(inp, first=0, count=None, first_bin=0, n_bins=None, skip=None):
+    """rts_covariance_eval (pure host): the sample covariance R[i][j] = mean over the training cells of z_i conj(z_j) of a host array
+    [n_rx][n_rows][n_bins] (complex) -- rows first .. first + count - 1, bins first_bin .. first_bin + n_bins - 1 without the skip
+    interval (first skipped bin, how many): complex [n_rx][n_rx]"""
+    inp = np.ascontiguousarray(np.asarray(inp, np.complex128))
+    n_rx, rows, nb = inp.shape
+    q = L.RtsCubeParams(n_rx, rows, nb, 0, 0.0, 1.0)
+    p = _cov_params("cube", first, count, first_bin, n_bins, skip, None, 0)
+    out = np.zeros((n_rx, n_rx), np.complex128)
+    check(L.lib().rts_covariance_eval(C.byref(q), ptr(inp.view(np.float64)), rows, C.byref(p), ptr(out.view(np.float64))))
+    return out
+
+
+def _mvdr_params(steering, n_rx, loading, device_cov):
+    """RtsMvdrParams and the steering array it points to (keep it alive for the call)"""
+    s = np.ascontiguousarray(np.asarray(steering, np.complex128))
+    if s.ndim != 2 or (n_rx and s.shape[1] != n_rx):
+        raise ValueError("mvdr: steering of shape %s for %d receivers ([n_beams][n_rx])" % (s.shape, n_rx))
+    p = L.RtsMvdrParams()
+    p.n_beams, p.n_rx, p.loading = s.shape[0], s.shape[1], float(loading)
+    p.steering = ptr(s.view(np.float64))
+    p.device_cov = device_cov if device_cov else None
+    return p, s
+
+
+def mvdr_eval(cov, steering, loading=0.0):
+    """rts_mvdr_eval (pure host): the MVDR weights w[b] = A^-1 s_b / (s_b^H A^-1 s_b), A = cov + loading I, of steering rows complex
+    [n_beams][n_rx] (steering) by Cholesky: complex [n_beams][n_rx], a weight table of beamform_eval / cube_beamform"""
+    cov = np.ascontiguousarray(np.asarray(cov, np.complex128))
+    if cov.ndim != 2 or cov.shape[0] != cov.shape[1]:
+        raise ValueError("mvdr_eval: a covariance of shape %s ([n_rx][n_rx])" % (cov.shape,))
+    p, keep = _mvdr_params(steering, cov.shape[0], loading, None)
+    out = np.zeros((p.n_beams, cov.shape[0]), np.complex128)
+    check(L.lib().rts_mvdr_eval(ptr(cov.view(np.float64)), cov.shape[0], C.byref(p), ptr(out.view(np.float64))))
+    return out
+
+
 def device_count():
     n = C.c_int(0)
     rc = L.lib().rts_device_count(C.byref(n))
@@ -846,6 +894,52 @@ class Tracer:
         out = _beam_out(*(getattr(self, "_beam_shape", None) or (1, 1, 1, False, False)))
         check(L.lib().rts_cube_beam_get(self.h, ptr(out.view(np.float64)), out.view(np.float64).size))
         return out
+
+    def cube_covariance(self, source="cube", first=0, count=None, first_bin=0, n_bins=None, skip=None, device_in=None, n_rows_in=0,
+                        device_ptr=None, fetch=True):
+        """rts_cube_covariance: the sample covariance of the receivers over the training cells -- rows first .. first + count - 1 and bins
+        first_bin .. first_bin + n_bins - 1 (defaults: to the last) of the source ("cube", "map" or "pointer", as cube_beamform)
+        without the bins skip = (first skipped bin, how many): the cells under test and their guard.  Complex [n_rx][n_rx] into a
+        caller device tensor (device_ptr; nothing is fetched) or the library's output, returned when fetch"""
+        p = _cov_params(source, first, count, first_bin, n_bins, skip, device_in, n_rows_in)
+        check(L.lib().rts_cube_covariance(self.h, C.byref(p), C.c_void_p(device_ptr) if device_ptr else None))
+        if device_ptr:
+            return None
+        self._cov_n = self._cube_shape[0]
+        return self.covariance() if fetch else None
+
+    def covariance(self):
+        """rts_cube_covariance_get: the library-owned output of the last cube_covariance, complex [n_rx][n_rx]"""
+        n = getattr(self, "_cov_n", None) or 1
+        out = np.zeros((n, n), np.complex128)
+        check(L.lib().rts_cube_covariance_get(self.h, ptr(out.view(np.float64)), 2 * out.size))
+        return out
+
+    def cube_mvdr(self, steering, loading=0.0, device_cov=None, device_ptr=None, fetch=True):
+        """rts_cube_mvdr: the MVDR weights of steering rows complex [n_beams][n_rx] (steering) from the library-owned covariance of the
+        last cube_covariance, or from device_cov = data_ptr() of a complex128 device tensor [n_rx][n_rx]; loading is added to the
+        covariance's diagonal (the cube's power units, e.g. cube_add_noise's noise_power).  Complex [n_beams][n_rx] into a caller
+        device tensor (device_ptr; nothing is fetched) or the library's output, returned when fetch; a failed solve raises there"""
+        p, keep = _mvdr_params(steering, 0 if device_cov else getattr(self, "_cov_n", 0), loading, device_cov)
+        check(L.lib().rts_cube_mvdr(self.h, C.byref(p), C.c_void_p(device_ptr) if device_ptr else None))
+        if device_ptr:
+            return None
+        self._mvdr_shape = (p.n_beams, p.n_rx)
+        return self.mvdr_weights() if fetch else None
+
+    def mvdr_weights(self):
+        """rts_cube_mvdr_get: the library-owned output of the last cube_mvdr, complex [n_beams][n_rx]: cube_beamform's weights"""
+        out = np.zeros(getattr(self, "_mvdr_shape", None) or (1, 1), np.complex128)
+        check(L.lib().rts_cube_mvdr_get(self.h, ptr(out.view(np.float64)), 2 * out.size))
+        return out
+
+    def cube_adaptive_beamform(self, steering, train=None, loading=0.0, **beamform_kwargs):
+        """cube_covariance(**train) -> cube_mvdr(steering, loading) -> cube_beamform(the weights, **beamform_kwargs): beams whose
+        weights are computed from the training cells `train` names (cube_covariance's keywords; default: every cell of the cube).
+        The cube stays on the device; the weights (at most 64 KiB) pass through the host.  Returns cube_beamform's result."""
+        self.cube_covariance(fetch=False, **(train or {}))
+        w = self.cube_mvdr(steering, loading)
+        return self.cube_beamform(w, **beamform_kwargs)
 
     def cube_compress(self, first=0, count=None):
         """rts_cube_compress: matched filter of rows first .. first + count - 1 (default: to the last pulse), in place"""

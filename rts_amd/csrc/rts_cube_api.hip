@@ -628,6 +628,166 @@ extern "C" int rts_cube_beam_get(RtsHandle c, double* host_out, uint64_t capacit
     return rts_cube_copy_out(c, "rts_cube_beam_get", "no library-owned beams (rts_cube_beamform with device_out NULL; the beams end at rts_cube_attach) / null output", c->cube.beam.valid, c->cube.beam.p, c->cube.beam.doubles, host_out, capacity_doubles);
 }
 
+// ------------------------------------------------------------------------------------- adaptive (MVDR) beamforming
+// (rts_amd.h: RtsCovParams, RtsMvdrParams; the trees and the launch plans are rts_adapt.h, shared by the host exports and the kernels, rts_adapt.hip)
+// the record: what needs no source
+static int rts_cov_check(const RtsCovParams* p, uint32_t n_rx, const char* who)
+{
+    if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
+    if (p->reserved[0] || p->reserved[1]) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
+    if (p->source > RTS_BEAM_FROM_POINTER) { rts_set_error("%s: unknown source %u (RTS_BEAM_FROM_CUBE, _MAP, _POINTER)", who, p->source); return RTS_ERR_INVALID; }
+    if (n_rx > RTS_BEAM_MAX_RX) { rts_set_error("%s: n_rx = %u receivers: more than %u", who, n_rx, RTS_BEAM_MAX_RX); return RTS_ERR_INVALID; }
+    if (p->source != RTS_BEAM_FROM_POINTER && p->n_rows_in != 0) { rts_set_error("%s: n_rows_in = %u without RTS_BEAM_FROM_POINTER", who, p->n_rows_in); return RTS_ERR_INVALID; }
+    if (p->source != RTS_BEAM_FROM_POINTER && p->device_in) { rts_set_error("%s: device_in without RTS_BEAM_FROM_POINTER", who); return RTS_ERR_INVALID; }
+    if (p->source == RTS_BEAM_FROM_POINTER && p->n_rows_in == 0) { rts_set_error("%s: n_rows_in = 0 with RTS_BEAM_FROM_POINTER", who); return RTS_ERR_INVALID; }
+    return RTS_OK;
+}
+// the training set inside the source's rows and bins, and the plan of its launches
+static int rts_cov_set_check(const RtsCovParams* p, uint32_t rows, uint32_t n_rx, uint32_t nb, const char* who, RtsCovSet* set, RtsCovPlan* plan)
+{
+    if (p->first_row >= rows || p->n_rows > rows - p->first_row) { rts_set_error("%s: first_row = %u, n_rows = %u: inside the source's %u rows", who, p->first_row, p->n_rows, rows); return RTS_ERR_INVALID; }
+    if (p->first_bin >= nb || p->n_bins > nb - p->first_bin) { rts_set_error("%s: first_bin = %u, n_bins = %u: inside the source's %u bins", who, p->first_bin, p->n_bins, nb); return RTS_ERR_INVALID; }
+    const uint32_t span = p->n_bins ? p->n_bins : nb - p->first_bin;
+    if (p->skip_n_bins == 0 && p->skip_first_bin != 0) { rts_set_error("%s: skip_first_bin = %u with skip_n_bins = 0", who, p->skip_first_bin); return RTS_ERR_INVALID; }
+    if (p->skip_n_bins != 0 && (p->skip_first_bin < p->first_bin || p->skip_first_bin - p->first_bin >= span || p->skip_n_bins > span - (p->skip_first_bin - p->first_bin))) {
+        rts_set_error("%s: skip_first_bin = %u, skip_n_bins = %u: inside the bins %u .. %u + %u", who, p->skip_first_bin, p->skip_n_bins, p->first_bin, p->first_bin, span); return RTS_ERR_INVALID; }
+    if (p->skip_n_bins == span) { rts_set_error("%s: skip_n_bins = %u leaves no bin of the span's %u", who, p->skip_n_bins, span); return RTS_ERR_INVALID; }
+    set->first_row = p->first_row; set->n_rows = p->n_rows ? p->n_rows : rows - p->first_row; set->first_bin = p->first_bin;
+    set->kept = span - p->skip_n_bins; set->skip_n = p->skip_n_bins; set->skip_at = p->skip_n_bins ? p->skip_first_bin - p->first_bin : set->kept;
+    *plan = rts_cov_plan(n_rx, set->n_rows, set->kept);
+    if (!plan->supported) { rts_set_error("%s: %llu training cells (n_rows * kept bins) in tiles of %u: more than %llu tiles", who, (unsigned long long)plan->K, RTS_ADAPT_TILE, RTS_ADAPT_MAX_TILES); return RTS_ERR_INVALID; }
+    return RTS_OK;
+}
+
+extern "C" int rts_covariance_eval(const RtsCubeParams* q, const double* in, uint32_t n_rows_in, const RtsCovParams* p, double* out)
+{
+    if (!q || q->n_rx == 0 || q->n_bins == 0) { rts_set_error("rts_covariance_eval: bad cube parameters"); return RTS_ERR_INVALID; }
+    if (n_rows_in == 0) { rts_set_error("rts_covariance_eval: n_rows_in = 0"); return RTS_ERR_INVALID; }
+    int rc = rts_cov_check(p, q->n_rx, "rts_covariance_eval"); if (rc != RTS_OK) return rc;
+    if (p->source == RTS_BEAM_FROM_POINTER && p->n_rows_in != n_rows_in) { rts_set_error("rts_covariance_eval: the parameters' n_rows_in = %u, the array's %u", p->n_rows_in, n_rows_in); return RTS_ERR_INVALID; }
+    RtsCovSet set; RtsCovPlan plan;
+    rc = rts_cov_set_check(p, n_rows_in, q->n_rx, q->n_bins, "rts_covariance_eval", &set, &plan); if (rc != RTS_OK) return rc;
+    if (!in || !out) { rts_set_error("rts_covariance_eval: null input or output array"); return RTS_ERR_INVALID; }
+    rts_cov_eval_host(q->n_rx, q->n_bins, in, n_rows_in, set, plan, out);
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_covariance(RtsHandle c, const RtsCovParams* p, void* device_out)
+{
+    CHECK_HANDLE(c);
+    NEED_CUBE(c, "rts_cube_covariance", "no cube (call rts_cube_attach first)");
+    const RtsCubeParams& q = c->cube.params;
+    int rc = rts_cov_check(p, q.n_rx, "rts_cube_covariance"); if (rc != RTS_OK) return rc;
+    const double* src = c->cube.p; uint32_t rows = q.n_pulses;
+    if (p->source == RTS_BEAM_FROM_MAP) {
+        const RtsCubeProduct& m = c->cube.doppler;
+        if (!m.valid || !m.own.p || m.p != m.own.p) { rts_set_error("rts_cube_covariance: RTS_BEAM_FROM_MAP: no library-owned map (rts_cube_doppler with device_out NULL)"); return RTS_ERR_INVALID; }
+        src = m.p; rows = c->cube.doppler_n;
+    } else if (p->source == RTS_BEAM_FROM_POINTER) {
+        if (!p->device_in) { rts_set_error("rts_cube_covariance: null device_in with RTS_BEAM_FROM_POINTER"); return RTS_ERR_INVALID; }
+        src = (const double*)p->device_in; rows = p->n_rows_in;
+    }
+    if ((uintptr_t)src & 15u) { rts_set_error("rts_cube_covariance: %s is not 16-byte aligned", p->source == RTS_BEAM_FROM_POINTER ? "device_in" : "the source's device memory"); return RTS_ERR_INVALID; }
+    RtsCovSet set; RtsCovPlan plan;
+    rc = rts_cov_set_check(p, rows, q.n_rx, q.n_bins, "rts_cube_covariance", &set, &plan); if (rc != RTS_OK) return rc;
+    if ((uintptr_t)device_out & 15u) { rts_set_error("rts_cube_covariance: device_out is not 16-byte aligned"); return RTS_ERR_INVALID; }
+    const uint64_t rx_stride = (uint64_t)rows * q.n_bins;
+    if (device_out) {       // the output's bytes against each receiver's span of the input: its first training cell .. its last
+        const uintptr_t o0 = (uintptr_t)device_out, o1 = o0 + sizeof(double) * plan.out_doubles;
+        const uint64_t e0 = rts_cov_cell_index(set, q.n_bins, 0), e1 = rts_cov_cell_index(set, q.n_bins, plan.K - 1u) + 1u;
+        for (uint32_t r = 0; r < q.n_rx; r++) {
+            const uintptr_t i0 = (uintptr_t)(src + 2 * ((size_t)r * rx_stride + e0)), i1 = (uintptr_t)(src + 2 * ((size_t)r * rx_stride + e1));
+            if (o0 < i1 && i0 < o1) { rts_set_error("rts_cube_covariance: device_out overlaps the input the call reads (receiver %u)", r); return RTS_ERR_INVALID; }
+        }
+    }
+    CHECK_CLOSED(c);
+    double* out; RTS_HIP(c->cube.cov.place(device_out, plan.out_doubles, &out));
+    RTS_HIP(c->cube.d_cov_part.reserve(plan.scratch_bytes / sizeof(double)));
+    if (!device_out) { c->cube.cov.record(out, plan.out_doubles); c->cube.cov_n = q.n_rx; }
+    return rts_cube_cov_device(c, set, plan, src, rx_stride, c->cube.d_cov_part.p, out);
+}
+
+extern "C" int rts_cube_covariance_get(RtsHandle c, double* host_out, uint64_t capacity_doubles)
+{
+    CHECK_HANDLE(c);
+    return rts_cube_copy_out(c, "rts_cube_covariance_get", "no library-owned covariance (rts_cube_covariance with device_out NULL; a covariance ends at rts_cube_attach) / null output", c->cube.cov.valid, c->cube.cov.p, c->cube.cov.doubles, host_out, capacity_doubles);
+}
+
+// the record, the limits and the steering rows of a solve over n_rx receivers
+static int rts_mvdr_check(const RtsMvdrParams* p, uint32_t n_rx, const char* who, RtsMvdrPlan* plan)
+{
+    if (p->reserved[0] || p->reserved[1]) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
+    if (n_rx == 0 || n_rx > RTS_BEAM_MAX_RX) { rts_set_error("%s: n_rx = %u receivers (1 .. %u)", who, n_rx, RTS_BEAM_MAX_RX); return RTS_ERR_INVALID; }
+    if (p->n_beams == 0 || p->n_beams > RTS_BEAM_MAX_BEAMS) { rts_set_error("%s: n_beams = %u (1 .. %u)", who, p->n_beams, RTS_BEAM_MAX_BEAMS); return RTS_ERR_INVALID; }
+    if ((uint64_t)p->n_beams * n_rx > RTS_BEAM_MAX_WEIGHTS) { rts_set_error("%s: n_beams * n_rx = %u * %u weights: more than %u (a weight table of rts_cube_beamform)", who, p->n_beams, n_rx, RTS_BEAM_MAX_WEIGHTS); return RTS_ERR_INVALID; }
+    if (!std::isfinite(p->loading) || p->loading < 0) { rts_set_error("%s: loading = %g (finite, >= 0)", who, p->loading); return RTS_ERR_INVALID; }
+    if (!p->steering) { rts_set_error("%s: null steering", who); return RTS_ERR_INVALID; }
+    for (uint32_t i = 0; i < 2 * p->n_beams * n_rx; i++) if (!std::isfinite(p->steering[i])) { rts_set_error("%s: steering[%u][%u] is not finite", who, i / 2 / n_rx, i / 2 % n_rx); return RTS_ERR_INVALID; }
+    *plan = rts_mvdr_plan(n_rx, p->n_beams);
+    if (!plan->supported) { rts_set_error("%s: n_rx = %u, n_beams = %u: beyond the solve's plan", who, n_rx, p->n_beams); return RTS_ERR_INVALID; }
+    return RTS_OK;
+}
+
+extern "C" int rts_mvdr_eval(const double* cov, uint32_t n_rx, const RtsMvdrParams* p, double* out)
+{
+    if (!p) { rts_set_error("rts_mvdr_eval: null parameters"); return RTS_ERR_INVALID; }
+    if (p->n_rx != n_rx) { rts_set_error("rts_mvdr_eval: the parameters' n_rx = %u, the array's %u", p->n_rx, n_rx); return RTS_ERR_INVALID; }
+    RtsMvdrPlan plan;
+    int rc = rts_mvdr_check(p, n_rx, "rts_mvdr_eval", &plan); if (rc != RTS_OK) return rc;
+    if (!cov || !out) { rts_set_error("rts_mvdr_eval: null covariance or output array"); return RTS_ERR_INVALID; }
+    std::vector<double> L(2 * (size_t)n_rx * n_rx), x(2 * (size_t)n_rx), w(plan.out_doubles);
+    const int pivot = rts_mvdr_eval_host(cov, n_rx, p->n_beams, p->steering, p->loading, L.data(), x.data(), w.data());
+    if (pivot >= 0) { rts_set_error("rts_mvdr_eval: the solve failed at pivot %d (not finite or not > 0: the covariance plus loading is not positive definite)", pivot); return RTS_ERR_INVALID; }
+    memcpy(out, w.data(), sizeof(double) * plan.out_doubles);
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_mvdr(RtsHandle c, const RtsMvdrParams* p, void* device_out)
+{
+    CHECK_HANDLE(c);
+    NEED_CUBE(c, "rts_cube_mvdr", "no cube (call rts_cube_attach first)");
+    if (!p) { rts_set_error("rts_cube_mvdr: null parameters"); return RTS_ERR_INVALID; }
+    const double* cov = (const double*)p->device_cov; uint32_t n_rx = p->n_rx;
+    if (cov) {
+        if ((uintptr_t)cov & 15u) { rts_set_error("rts_cube_mvdr: device_cov is not 16-byte aligned"); return RTS_ERR_INVALID; }
+    } else {
+        if (!c->cube.cov.valid) { rts_set_error("rts_cube_mvdr: no covariance (rts_cube_covariance with device_out NULL first, or pass device_cov)"); return RTS_ERR_INVALID; }
+        if (n_rx != 0 && n_rx != c->cube.cov_n) { rts_set_error("rts_cube_mvdr: n_rx = %u, the library-owned covariance's %u (or 0)", n_rx, c->cube.cov_n); return RTS_ERR_INVALID; }
+        cov = c->cube.cov.p; n_rx = c->cube.cov_n;
+    }
+    RtsMvdrPlan plan;
+    int rc = rts_mvdr_check(p, n_rx, "rts_cube_mvdr", &plan); if (rc != RTS_OK) return rc;
+    if ((uintptr_t)device_out & 15u) { rts_set_error("rts_cube_mvdr: device_out is not 16-byte aligned"); return RTS_ERR_INVALID; }
+    if (device_out) {
+        const uintptr_t o0 = (uintptr_t)device_out, o1 = o0 + sizeof(double) * plan.out_doubles, i0 = (uintptr_t)cov, i1 = i0 + 16u * (uintptr_t)n_rx * n_rx;
+        if (o0 < i1 && i0 < o1) { rts_set_error("rts_cube_mvdr: device_out overlaps the covariance the call reads"); return RTS_ERR_INVALID; }
+    }
+    CHECK_CLOSED(c);
+    double* out; RTS_HIP(c->cube.mvdr.place(device_out, plan.out_doubles, &out));
+    RTS_HIP(c->cube.d_mvdr_status.reserve(2));
+    // the steering rows -> pinned staging -> the device, on the stream (n_beams n_rx <= RTS_BEAM_MAX_WEIGHTS: one size for every call)
+    double* s = nullptr;
+    RTS_HIP(c->cube.mvdr_s.begin(2u * RTS_BEAM_MAX_WEIGHTS, 2u * RTS_BEAM_MAX_WEIGHTS, 2u * RTS_BEAM_MAX_WEIGHTS, &s));
+    memcpy(s, p->steering, sizeof(double) * plan.out_doubles);
+    RTS_HIP(c->cube.mvdr_s.send(plan.out_doubles, c->stream));
+    if (!device_out) c->cube.mvdr.record(out, plan.out_doubles);
+    return rts_cube_mvdr_device(c, plan, n_rx, p->n_beams, p->loading, cov, c->cube.mvdr_s.dev.p, c->cube.d_mvdr_status.p + (device_out ? 1 : 0), out);
+}
+
+extern "C" int rts_cube_mvdr_get(RtsHandle c, double* host_out, uint64_t capacity_doubles)
+{
+    CHECK_HANDLE(c);
+    const RtsCubeProduct& m = c->cube.mvdr;
+    if (!c->cube.set || !m.valid || !host_out) { rts_set_error("rts_cube_mvdr_get: no library-owned weights (rts_cube_mvdr with device_out NULL; the weights end at rts_cube_attach) / null output"); return RTS_ERR_INVALID; }
+    if (capacity_doubles < m.doubles) { rts_set_error("rts_cube_mvdr_get: capacity too small"); return RTS_ERR_CAPACITY; }
+    RTS_HIP(hipStreamSynchronize(c->stream));
+    uint32_t status = 0;
+    RTS_HIP(hipMemcpy(&status, c->cube.d_mvdr_status.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (status) { rts_set_error("rts_cube_mvdr_get: the solve failed at pivot %u (not finite or not > 0: the covariance plus loading is not positive definite); every weight is NaN", status - 1u); return RTS_ERR_INVALID; }
+    RTS_HIP(hipMemcpy(host_out, m.p, sizeof(double) * m.doubles, hipMemcpyDeviceToHost));
+    return RTS_OK;
+}
+
 // ------------------------------------------------------------------------------------- backprojection imaging
 // (rts_amd.h: RtsImageParams; the arithmetic and the launch plan are rts_image.h, shared by the host export and the kernel, rts_image.hip)
 static int rts_image_check(const RtsImageParams* p, const RtsCubeParams& q, const char* who)

@@ -16,6 +16,7 @@
 #include "rts_stft.h"             // the radix-2 tree of the slow-time and fast-time transforms and the host-only plans of the Doppler map's and the spectrogram's launches
 #include "rts_beat.h"             // the tree of the dechirped beat render, the range transform's evaluator and the host-only plans of their launches
 #include "rts_beam.h"             // the beamformer's term, sum and streaming peak, its evaluator and the host-only plan of its launch
+#include "rts_adapt.h"            // adaptive beamforming: the covariance's term and partition, the weight solve, their evaluators and the host-only plans of their launches
 #include "rts_cfar_os.h"          // CFAR: what every detector shares (rts_cfar.h: window, training count, local maximum, refinement, record); OS: rank rule, alphas, the host evaluator
 #include "rts_owned.h"            // DevBuf, PinBuf, StagedUpload: device and pinned host memory that frees itself
 #include "rts_launch_plan.h"      // RTS_BLOCK, RTS_WTILE, RTS_COOP_GROUP, RTS_STACK_OVF and the host arithmetic of a launch
@@ -336,9 +337,15 @@ struct RtsCubeState {
     // beamforming (rts_cube_beamform, rts_beam.hip): the output, for rts_cube_beam_get; the call's weight table goes through a staged upload
     RtsCubeProduct beam;
     StagedUpload<double> beam_w;
+    // adaptive beamforming (rts_cube_covariance, rts_cube_mvdr, rts_adapt.hip): the covariance and its n_rx, for rts_cube_covariance_get
+    // and rts_cube_mvdr without device_cov, and the parts' partial sums; the weights, for rts_cube_mvdr_get; the call's steering rows go
+    // through a staged upload; the solves' status words (0: library-owned output, 1: caller-owned)
+    RtsCubeProduct cov; uint32_t cov_n = 0; DevBuf<double> d_cov_part;
+    RtsCubeProduct mvdr;
+    StagedUpload<double> mvdr_s; DevBuf<uint32_t> d_mvdr_status;
     // every product belongs to the cube it was made from: the Doppler map (which rts_cube_detect may take), the detection list, the image
-    // the spectrogram, the range transform and the beams end when another cube is attached
-    void end_products() { doppler.valid = false; det_valid = false; image.valid = false; stft.valid = false; range.valid = false; beam.valid = false; }
+    // the spectrogram, the range transform, the beams, the covariance and the adaptive weights end when another cube is attached
+    void end_products() { doppler.valid = false; det_valid = false; image.valid = false; stft.valid = false; range.valid = false; beam.valid = false; cov.valid = false; mvdr.valid = false; }
 };
 
 // What a pulse leaves for its accessors (rts_results_api.hip; the finalisers, the aggregation and the end-of-pulse chains of rts_api.hip; the
@@ -477,6 +484,8 @@ int rts_cube_stft_device(RtsContext* c, const RtsStftParams& p, const RtsStftPla
 int rts_cube_beat_device(RtsContext* c, uint32_t pulse_index, const RtsBeatParams& p, const RtsBeatPlan& plan, double cspeed, double carrier, int64_t base);      // rts_beat.hip
 int rts_cube_range_device(RtsContext* c, const RtsRangeParams& p, const RtsRangePlan& plan, const double* window, double* out);
 int rts_cube_beam_device(RtsContext* c, const RtsBeamParams& p, const RtsBeamPlan& plan, const double* in, uint64_t rx_stride, const double* weights, void* out);      // rts_beam.hip
+int rts_cube_cov_device(RtsContext* c, const RtsCovSet& set, const RtsCovPlan& plan, const double* in, uint64_t rx_stride, double* part, double* out);      // rts_adapt.hip
+int rts_cube_mvdr_device(RtsContext* c, const RtsMvdrPlan& plan, uint32_t n_rx, uint32_t n_beams, double loading, const double* cov, const double* steering, uint32_t* status, double* out);
 int rts_cube_backproject_device(RtsContext* c, const RtsImageParams& p, const RtsImagePlan& plan, const double* geo, double* out);      // rts_image.hip
 int rts_post_finalise(RtsContext* c, const double* rcs_host, double wl, double gt, double gr, double carrier, double cspeed);
 int rts_pattern_pulse_upload(RtsContext* c, const RtsSpecParams& q, RtsPatArgs* out);      // the pulse's receiver rows -> the device, on c->stream
