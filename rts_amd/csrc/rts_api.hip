@@ -20,6 +20,7 @@
 #include <thread>
 #include "rts_internal.h"
 #include "rts_raygen.h"
+#include "rts_prim_order.h"
 #include <atomic>
 
 static thread_local char g_err[1024] = "";
@@ -401,6 +402,17 @@ extern "C" int rts_set_scene(RtsHandle c, const RtsMesh* meshes, uint32_t n_targ
     // the record's unused words for rts_get_bvh.  A third of the per-pulse leaf refresh and of the leaf bytes on C3 (300 k slots
     // for 100 k triangles), and of the 240 MB per handle on BASELINE configs[3].
     if (ns->n_nodes) { k_children_to_prims<<<(ns->n_nodes + 255) / 256, 256, 0, c->stream>>>(ns->d_nodes4.p, ns->n_nodes, ns->d_leaf_prim.p); RTS_HIP(hipGetLastError()); RTS_HIP(hipStreamSynchronize(c->stream)); }
+    // The order in which the per-pulse scene update visits the primitives (k_leaves, rts_bvh.hip): by first appearance in the leaf
+    // slots, so that a block's 256 triangles are neighbours in space whatever the mesh's own numbering (rts_prim_order.h).  Once
+    // per scene, whichever builder ran: one read-back of the slots, the de-duplication on the host.
+    if (ns->n_prims) {
+        std::vector<uint32_t> slots(ns->n_leaves);
+        RTS_HIP(hipStreamSynchronize(c->stream));
+        if (ns->n_leaves) RTS_HIP(hipMemcpy(slots.data(), ns->d_leaf_prim.p, sizeof(uint32_t) * ns->n_leaves, hipMemcpyDeviceToHost));
+        const std::vector<uint32_t> order = rts_prim_order(slots.data(), slots.size(), ns->n_prims);
+        RTS_HIP(ns->d_prim_order.reserve(order.size() + 1));
+        RTS_HIP(hipMemcpy(ns->d_prim_order.p, order.data(), sizeof(uint32_t) * order.size(), hipMemcpyHostToDevice));
+    }
     {   // the octant versions of the node records (k_node_versions): RTS_NODE_VERSIONS=0: none; they need 1 KB per node -- a scene whose
         // versions would not fit a quarter of the device's free memory goes without (the kernel then walks d_nodes4 as before)
         const bool want = st.node_versions;

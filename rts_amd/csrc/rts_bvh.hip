@@ -3,7 +3,7 @@
 // The hierarchy itself is static (rts_sah.cpp: one target-space BVH4 per mesh, built when the scene is set); what a
 // pulse changes is the placement  world = R * local + position  of every target (ray_tracer.cpp:993-1014).  Per pulse:
 //   place  : world vertices/normals = R * local (+ position), the reference's arithmetic          (ray_tracer.cpp:120-137)
-//   leaves : gather the three f64 world vertices of each primitive into the static leaf order
+//   leaves : gather the three f64 world vertices of each primitive into its leaf record
 // The reference instead refills its vertex buffers and has OptiX rebuild the "Bvh" acceleration each pulse
 // (ray_tracer.cpp:1126-1130); the per-target inverse placement and world bounds the traversal needs are launch
 // constants computed on the host (rts_api.hip: fill_target_placement).
@@ -41,12 +41,17 @@ __global__ void k_place(const double* __restrict__ v_local, double* __restrict__
 }
 
 // --------------------------------------------------------------------------- primary-ray mask (see RtsMaskFrame)
-// One thread per LEAF, in leaf order: neighbouring leaves are neighbours in space, so the 256 triangles of a block cover a
-// compact patch of the bitmap.  The block rasterises into an LDS tile over the bounding rectangle of its triangles' rectangles
-// and then ORs the tile's non-zero words into the mask -- a few dozen global atomics per block instead of a few per triangle
-// (100 k triangles marking the same ~5 k words: same-line atomics serialise in L2, the per-triangle version took 80-130 us).
-// A block whose patch does not fit the tile falls back to per-triangle atomics.
+// One thread per PRIMITIVE, the primitives taken in the order of the hierarchy's leaf slots (RtsScene::d_prim_order: thread i
+// holds primitive order[i], not primitive i -- the mesh's own numbering says nothing about where a triangle lies): neighbours
+// in that order are neighbours in space, so the 256 triangles of a block cover a compact patch of the bitmap.  The block
+// rasterises into an LDS tile over the bounding rectangle of its triangles' rectangles and then ORs the tile's non-zero words
+// into the mask -- a few dozen global atomics per block instead of a few per triangle (100 k triangles marking the same ~5 k
+// words: same-line atomics serialise in L2, the per-triangle version took 80-130 us).
+// A patch that does not fit the tile is cut into bands of whole rows (a row of the mask is at most RTS_MASK_N / 32 words, so a
+// band holds at least 64 of them) and the block goes through zero / mark / flush once per band: whatever the order of the
+// primitives, a triangle's marks are LDS atomics and only the tile's non-zero words reach memory.
 #define RTS_MASK_TILE_WORDS 2048
+static_assert(RTS_MASK_N / 32u <= RTS_MASK_TILE_WORDS, "a band of the mask tile holds at least one whole row");
 struct RtsMaskLds { uint32_t tile[RTS_MASK_TILE_WORDS]; int box[4]; };          // box: min iu0, min iv0, max iu1, max iv1 of the block
 // (called by every thread of the block: `have` = the thread holds a triangle, p[k] = its world-space vertices)
 __device__ __forceinline__ void rts_mask_mark(RtsMaskLds& S, const bool have, const double (&p)[9], const double ox, const double oy, const double oz, const RtsMaskFrame& f, uint32_t* __restrict__ mask)
@@ -78,31 +83,42 @@ __device__ __forceinline__ void rts_mask_mark(RtsMaskLds& S, const bool have, co
         }
     }
     const bool any = iu1 >= iu0 && iv1 >= iv0;
-    if (any) { atomicMin(&S.box[0], iu0); atomicMin(&S.box[1], iv0); atomicMax(&S.box[2], iu1); atomicMax(&S.box[3], iv1); }
+    {   // the block's box: reduced within the wave first, then four LDS atomics per WAVE (four per thread -- 1 024 atomics on the same
+        // four words, which the LDS takes one at a time -- were 7 of the 21 us of this kernel in a lone C3 pulse: profiles/mask_order_ab.txt)
+        int b0 = any ? iu0 : 0x7fffffff, b1 = any ? iv0 : 0x7fffffff, b2 = any ? iu1 : -1, b3 = any ? iv1 : -1;
+        for (int d = warpSize / 2; d > 0; d >>= 1) {                // (every lane of the block is here: rts_mask_mark is called by all threads)
+            b0 = min(b0, __shfl_xor(b0, d)); b1 = min(b1, __shfl_xor(b1, d)); b2 = max(b2, __shfl_xor(b2, d)); b3 = max(b3, __shfl_xor(b3, d));
+        }
+        if ((threadIdx.x & (warpSize - 1)) == 0 && b2 >= 0) { atomicMin(&S.box[0], b0); atomicMin(&S.box[1], b1); atomicMax(&S.box[2], b2); atomicMax(&S.box[3], b3); }
+    }
     __syncthreads();
     if (S.box[2] < 0) return;                                       // (uniform) nothing to mark in this block
     const int W0 = S.box[0] >> 5, V0 = S.box[1], TW = (S.box[2] >> 5) - W0 + 1, TH = S.box[3] - V0 + 1;
-    const bool tiled = (long long)TW * TH <= RTS_MASK_TILE_WORDS;   // (uniform)
-    if (tiled) { for (int w = threadIdx.x; w < TW * TH; w += blockDim.x) S.tile[w] = 0u; __syncthreads(); }
-    if (any) {
-        for (int iv = iv0; iv <= iv1; iv++) {
-            for (int w0 = iu0 >> 5; w0 <= (iu1 >> 5); w0++) {       // one atomic per touched word of the row
-                const int lo = max(iu0, w0 << 5) & 31, hi = min(iu1, (w0 << 5) + 31) & 31;
-                const uint32_t bits = (hi == 31 ? 0xffffffffu : ((1u << (hi + 1)) - 1u)) & ~((1u << lo) - 1u);
-                if (tiled) atomicOr(&S.tile[(iv - V0) * TW + (w0 - W0)], bits);
-                else atomicOr(&mask[((size_t)iv * f.n >> 5) + (size_t)w0], bits);
+    const int band = RTS_MASK_TILE_WORDS / TW;                      // rows of the patch the tile holds at a time (TW <= 32: >= 64)
+    for (int b0 = 0; b0 < TH; b0 += band) {                         // (uniform: every thread takes every barrier; one band unless the patch exceeds the tile)
+        const int B0 = V0 + b0, bh = min(band, TH - b0), nw = TW * bh;
+        if (b0) __syncthreads();                                    // the last band's flush has read the tile
+        for (int w = threadIdx.x; w < nw; w += blockDim.x) S.tile[w] = 0u;
+        __syncthreads();
+        if (any) {
+            for (int iv = max(iv0, B0); iv <= min(iv1, B0 + bh - 1); iv++) {      // the rows of the rectangle that fall in this band
+                for (int w0 = iu0 >> 5; w0 <= (iu1 >> 5); w0++) {   // one atomic per touched word of the row
+                    const int lo = max(iu0, w0 << 5) & 31, hi = min(iu1, (w0 << 5) + 31) & 31;
+                    const uint32_t bits = (hi == 31 ? 0xffffffffu : ((1u << (hi + 1)) - 1u)) & ~((1u << lo) - 1u);
+                    atomicOr(&S.tile[(iv - B0) * TW + (w0 - W0)], bits);
+                }
             }
         }
-    }
-    if (!tiled) return;
-    __syncthreads();
-    for (int w = threadIdx.x; w < TW * TH; w += blockDim.x) {
-        const uint32_t bits = S.tile[w];
-        if (bits) atomicOr(&mask[((size_t)(V0 + w / TW) * f.n >> 5) + (size_t)(W0 + w % TW)], bits);
+        __syncthreads();
+        for (int w = threadIdx.x; w < nw; w += blockDim.x) {
+            const uint32_t bits = S.tile[w];
+            if (bits) atomicOr(&mask[((size_t)(B0 + w / TW) * f.n >> 5) + (size_t)(W0 + w % TW)], bits);
+        }
     }
 }
 
-// Leaf record i = primitive leaf_prim[i] with its world-space vertices pre-gathered (the reference gathers through
+// Leaf record g = primitive g (thread i handles g = order[i], RtsScene::d_prim_order, and writes its own record: the index stays
+// the primitive id) with its world-space vertices pre-gathered (the reference gathers through
 // dbuf_triangles -> dbuf_triVertices per test, triangle_mesh.cu:147-154) and, of the second and third, only what the test makes
 // of them whatever the ray: the two edges and the normal (RtsLeafTri).  LEAVES && MASK: one pass over the placed triangles
 // for both (a pulse that moves a target needs both; the vertices are gathered once).  MASK alone: the targets stand still,
@@ -124,7 +140,7 @@ __device__ __forceinline__ void place_vertex(const double* __restrict__ local, c
     out3[0] = x; out3[1] = y; out3[2] = z;
 }
 template <bool LEAVES, bool MASK, bool PLACE = false>
-__global__ void __launch_bounds__(256) k_leaves(const uint32_t* __restrict__ leaf_prim, const uint32_t* __restrict__ tri_vidx, const double* __restrict__ verts,
+__global__ void __launch_bounds__(256) k_leaves(const uint32_t* __restrict__ order, const uint32_t* __restrict__ tri_vidx, const double* __restrict__ verts,
                                                 const uint32_t* __restrict__ prim_targ, RtsLeafTri* __restrict__ leaves, uint32_t n,
                                                 double ox, double oy, double oz, RtsMaskFrame f, uint32_t* __restrict__ mask,
                                                 const RtsTargetMotion* __restrict__ motion = nullptr, uint32_t prim_blocks = 0, const double* __restrict__ n_local = nullptr,
@@ -139,7 +155,7 @@ __global__ void __launch_bounds__(256) k_leaves(const uint32_t* __restrict__ lea
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     double p[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     if (i < n) {
-        const uint32_t g = leaf_prim ? leaf_prim[i] : i;                 // (one record per primitive: leaf_prim == nullptr)
+        const uint32_t g = order[i];                                     // (a permutation of the primitives: every record is written once)
         const uint32_t a = tri_vidx[3*(size_t)g], b = tri_vidx[3*(size_t)g+1], c = tri_vidx[3*(size_t)g+2];
         if (PLACE) {                                                     // verts = the LOCAL vertices
             const RtsTargetMotion m = motion[prim_targ[g]];
@@ -157,7 +173,7 @@ __global__ void __launch_bounds__(256) k_leaves(const uint32_t* __restrict__ lea
             L.p0x = p[0]; L.p0y = p[1]; L.p0z = p[2]; L.e0x = e0.x; L.e0y = e0.y; L.e0z = e0.z; L.e1x = e1.x; L.e1y = e1.y; L.e1z = e1.z;
             L.nx = nn.x; L.ny = nn.y; L.nz = nn.z;
             L.prim = g; L.targ = prim_targ[g]; L.pad[0] = 0u; L.pad[1] = 0u;
-            leaves[i] = L;
+            leaves[g] = L;
         }
     }
     if (MASK) rts_mask_mark(*reinterpret_cast<RtsMaskLds*>(s_raw), i < n, p, ox, oy, oz, f, mask);
@@ -179,9 +195,9 @@ int rts_scene_place(RtsContext* c, const RtsLaunchConsts& lc, bool place, uint32
     // vertices, which k_place brings up to date for that pass only.)
     if (place && sc->n_prims) {
         const unsigned gp = blocks_for(sc->n_prims, 256), gn = blocks_for(sc->n_normals, 256);
-        if (mask) k_leaves<true, true, true><<<gp + gn, 256, 0, st>>>(nullptr, sc->d_tri_vidx.p, sc->d_verts_local.p, sc->d_prim_targ.p, c->d_leaves.p, sc->n_prims, lc.ox, lc.oy, lc.oz, f, pmask,
+        if (mask) k_leaves<true, true, true><<<gp + gn, 256, 0, st>>>(sc->d_prim_order.p, sc->d_tri_vidx.p, sc->d_verts_local.p, sc->d_prim_targ.p, c->d_leaves.p, sc->n_prims, lc.ox, lc.oy, lc.oz, f, pmask,
                                                                      c->p_motion, gp, sc->d_normals_local.p, c->d_normals_world.p, sc->d_norm_targ.p, sc->n_normals);
-        else k_leaves<true, false, true><<<gp + gn, 256, 0, st>>>(nullptr, sc->d_tri_vidx.p, sc->d_verts_local.p, sc->d_prim_targ.p, c->d_leaves.p, sc->n_prims, lc.ox, lc.oy, lc.oz, f, nullptr,
+        else k_leaves<true, false, true><<<gp + gn, 256, 0, st>>>(sc->d_prim_order.p, sc->d_tri_vidx.p, sc->d_verts_local.p, sc->d_prim_targ.p, c->d_leaves.p, sc->n_prims, lc.ox, lc.oy, lc.oz, f, nullptr,
                                                                   c->p_motion, gp, sc->d_normals_local.p, c->d_normals_world.p, sc->d_norm_targ.p, sc->n_normals);
         c->verts_world_valid = false;
         RTS_HIP(hipGetLastError());
@@ -196,7 +212,7 @@ int rts_scene_place(RtsContext* c, const RtsLaunchConsts& lc, bool place, uint32
             k_place<<<blocks_for((size_t)sc->n_verts, 256), 256, 0, st>>>(sc->d_verts_local.p, c->d_verts_world.p, sc->d_vert_targ.p, sc->n_verts, sc->d_normals_local.p, c->d_normals_world.p, sc->d_norm_targ.p, 0u, c->p_motion);
             c->verts_world_valid = true;
         }
-        if (sc->n_prims) k_leaves<false, true><<<blocks_for(sc->n_prims, 256), 256, 0, st>>>(nullptr, sc->d_tri_vidx.p, c->d_verts_world.p, sc->d_prim_targ.p, nullptr, sc->n_prims, lc.ox, lc.oy, lc.oz, f, pmask);
+        if (sc->n_prims) k_leaves<false, true><<<blocks_for(sc->n_prims, 256), 256, 0, st>>>(sc->d_prim_order.p, sc->d_tri_vidx.p, c->d_verts_world.p, sc->d_prim_targ.p, nullptr, sc->n_prims, lc.ox, lc.oy, lc.oz, f, pmask);
     }
     RTS_HIP(hipGetLastError());
     return RTS_OK;

@@ -36,8 +36,10 @@ struct __attribute__((aligned(128))) RtsNode4 {
 };
 static_assert(sizeof(RtsNode4) == 128, "node4 size");
 
-// Leaf record, 112 B (the bytes a lane at a node reads of its record: the same seven dwordx4 loads serve both), in the
-// hierarchy's (depth-first) leaf order, refreshed every pulse: what the f64 intersection test needs of the triangle and
+// Leaf record, 112 B (the bytes a lane at a node reads of its record: the same seven dwordx4 loads serve both), ONE PER
+// PRIMITIVE and indexed by the global primitive id (the nodes' leaf children name primitives: k_children_to_prims, rts_api.hip;
+// only the ORDER in which k_leaves visits them follows the hierarchy's leaf slots, RtsScene::d_prim_order), refreshed every
+// pulse: what the f64 intersection test needs of the triangle and
 // what does not depend on the ray -- the first WORLD-space vertex, pre-gathered (the reference gathers through
 // dbuf_triangles -> dbuf_triVertices per test, triangle_mesh.cu:147-154), and the test's ray-free terms e0 = p1 - p0,
 // e1 = p0 - p2, n = e1 x e0 (triangle_mesh.cu:127-129), formed once per pulse by the placement kernel (k_leaves,
@@ -254,11 +256,12 @@ struct RtsScene {
     DevBuf<double> d_verts_local, d_normals_local;
     std::vector<RtsBlasInfo> blas; uint32_t n_nodes = 0, n_leaves = 0;
     DevBuf<RtsNode4> d_nodes4; DevBuf<uint32_t> d_leaf_prim;
+    DevBuf<uint32_t> d_prim_order;  // [n_prims] the primitives by first appearance in d_leaf_prim (rts_prim_order.h): thread i of k_leaves handles primitive d_prim_order[i]
     DevBuf<RtsNode4> d_nodes4v;     // [n_nodes][8] octant versions of d_nodes4 (empty: none -- RTS_NODE_VERSIONS=0, or the scene too large for them)
     double build_ms = 0; uint32_t builder = 0;     // how long the hierarchy build took, and where it ran (0 host SAH, 1 device LBVH)
     size_t device_bytes() const {
         return d_tri_vidx.cap * 4 + d_tri_nidx.cap * 4 + d_vert_targ.cap * 4 + d_norm_targ.cap * 4 + d_prim_targ.cap * 4 + d_verts_local.cap * 8 +
-               d_normals_local.cap * 8 + (d_nodes4.cap + d_nodes4v.cap) * sizeof(RtsNode4) + d_leaf_prim.cap * 4;
+               d_normals_local.cap * 8 + (d_nodes4.cap + d_nodes4v.cap) * sizeof(RtsNode4) + d_leaf_prim.cap * 4 + d_prim_order.cap * 4;
     }
 };
 
