@@ -1,4 +1,4 @@
-// rts_api.hip -- host side of librts_amd.so: the C-ABI of include/rts_amd.h but for the cube (rts_cube_api.hip; rts_cube_reduce is here) and the accessors of a pulse's results (rts_results_api.hip).
+// rts_api.hip -- host side of librts_amd.so: the C-ABI of include/rts_amd.h but for the scene (rts_scene.hip), the cube (rts_cube_api.hip; rts_cube_reduce is here) and the accessors of a pulse's results (rts_results_api.hip).
 //
 // Mirrors the host driver rs::RTS of the reference (ray_tracer.cpp:507-1364) from the point
 // where it owns device state: context set-up, per-pulse scene placement, launch, read-back,
@@ -13,14 +13,11 @@
 #include <algorithm>
 #include <chrono>
 #include <map>
-#include <memory>
 #include <mutex>
 #include <stdexcept>
 #include <string>
-#include <thread>
 #include "rts_internal.h"
 #include "rts_raygen.h"
-#include "rts_prim_order.h"
 #include <atomic>
 
 static thread_local char g_err[1024] = "";
@@ -75,53 +72,6 @@ extern "C" int rts_bind_host_to_device(int device, int* numa_node)
 
 extern int rts_fill_i32(hipStream_t st, int32_t* p, int32_t v, size_t n);
 
-__global__ void k_children_to_prims(RtsNode4* __restrict__ nodes, uint32_t n, const uint32_t* __restrict__ leaf_prim)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    for (int k = 0; k < 4; k++) { const int32_t ch = nodes[i].child[k]; nodes[i].pad[k] = ch; if (ch < 0) nodes[i].child[k] = ~(int32_t)leaf_prim[~ch]; }
-}
-
-// OCTANT VERSIONS of the node records (round 5; RtsScene::d_nodes4v, [node][octant]).  A ray's octant in a target's frame -- the
-// signs of its direction there -- is fixed for a whole walk, and two things the node step used to work out per visit depend on
-// nothing else: which plane of a child's slab the ray enters through (low when it runs towards +axis, high towards -axis: the
-// role fetch formed six per-lane addresses for that) and a good front-to-back order of the four children (the step sorted the
-// four entry distances: 5 compares + 20 selects).  Both are baked here, once per scene: version o of a node holds, per child
-// slot, [entry planes x y z | exit planes x y z | child: ~primitive, or 8 x node + o = the child's record of the same octant], the slots in ascending order of the children's position along the
-// octant's diagonal (key_mode 1, the default: the box's centre; 0: its entry corner), unused slots (degenerate box, never entered) last.
-// The trace kernel reads the record of (node, octant) straight through and visits the open children in slot order.
-// Eight times the node bytes (BASELINE configs[2]: 18 -> 145 MB, configs[3]: 185 MB -> 1.5 GB of 288 GB), of which a walk
-// touches one version only.
-__global__ void k_node_versions(const RtsNode4* __restrict__ nodes, uint32_t n, RtsNode4* __restrict__ out, int key_mode)
-{
-    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;      // one thread per (node, octant)
-    if (g >= n * 8u) return;
-    const uint32_t i = g >> 3, o = g & 7u;
-    const RtsNode4 nd = nodes[i];
-    const bool mx = (o & 1u) != 0u, my = (o & 2u) != 0u, mz = (o & 4u) != 0u;      // the ray runs towards -x / -y / -z
-    float key[4]; int ord[4];
-    for (int k = 0; k < 4; k++) {
-        const float ex = mx ? -nd.hix[k] : nd.lox[k], ey = my ? -nd.hiy[k] : nd.loy[k], ez = mz ? -nd.hiz[k] : nd.loz[k];      // entry corner, along the diagonal
-        const float cx = 0.5f * (nd.lox[k] + nd.hix[k]), cy = 0.5f * (nd.loy[k] + nd.hiy[k]), cz = 0.5f * (nd.loz[k] + nd.hiz[k]);
-        const float kc = key_mode == 1 ? ((mx ? -cx : cx) + (my ? -cy : cy) + (mz ? -cz : cz)) : (ex + ey + ez);
-        key[k] = nd.child[k] == 0x7fffffff ? __builtin_inff() : kc;
-        ord[k] = k;
-    }
-    for (int a = 1; a < 4; a++)                                     // stable insertion sort of four
-        for (int b = a; b > 0 && key[ord[b]] < key[ord[b - 1]]; b--) { const int t = ord[b]; ord[b] = ord[b - 1]; ord[b - 1] = t; }
-    RtsNode4 v;
-    for (int j = 0; j < 4; j++) {
-        const int k = ord[j];
-        v.lox[j] = mx ? nd.hix[k] : nd.lox[k]; v.hix[j] = mx ? nd.lox[k] : nd.hix[k];      // lo* <- entry planes, hi* <- exit planes
-        v.loy[j] = my ? nd.hiy[k] : nd.loy[k]; v.hiy[j] = my ? nd.loy[k] : nd.hiy[k];
-        v.loz[j] = mz ? nd.hiz[k] : nd.loz[k]; v.hiz[j] = mz ? nd.loz[k] : nd.hiz[k];
-        const int32_t ch = nd.child[k];
-        v.child[j] = (ch >= 0 && ch != 0x7fffffff) ? (int32_t)(((uint32_t)ch << 3) | o) : ch;      // a node child: the index of ITS record of this octant (a walk never changes octant)
-        v.pad[j] = nd.pad[k];
-    }
-    out[g] = v;
-}
-
 // The two waits of a pulse (its trace, its post-processing): a thread blocked in hipStreamSynchronize lets its core fall
 // asleep, and every wake-up -- two per pulse, each in front of work the GPU is waiting for -- costs tens of microseconds on
 // the hosts of this pool (the C++ adapter's loop ran 0.44 ms per pulse right after a second of host-side hierarchy build had
@@ -135,11 +85,10 @@ hipError_t rts_stream_wait(RtsContext* c, hipStream_t st)
         __builtin_ia32_pause();
     }
 }
-static int rts_attach_scene(RtsContext* c);
 void rts_comm_cache_forget(RtsContext* c);
 
 // The environment, as the readers of rts_tuning.h take it: the library looks at it nowhere else.
-static const char* rts_env(const char* name) { return getenv(name); }
+const char* rts_env(const char* name) { return getenv(name); }
 // RTS_LAP, RTS_DEBUG_SYNC: read once per process, by whichever of the two is asked for first
 static const RtsProcessTuning& rts_process_tuning() { static const RtsProcessTuning t = [] { RtsProcessTuning r; rts_tuning_read(&r, rts_env); return r; }(); return t; }
 
@@ -162,7 +111,6 @@ extern "C" int rts_device_count(int* n)
     *n = k; return RTS_OK;
 }
 
-void rts_scene_unref(RtsScene* s) { if (s && --s->refs == 0) delete s; }
 void rts_hist_unref(RtsTileHist* h) { if (h && --h->refs == 0) delete h; }
 void rts_gate_unref(RtsGate* g) { if (g && --g->refs == 0) { if (g->tstream) (void)hipStreamDestroy(g->tstream); delete g; } }
 
@@ -278,7 +226,7 @@ extern "C" int rts_link_handles(RtsHandle a, RtsHandle b)
 // The aggregation groups received rays by a packed (receiver, path) key of D x ceil(log2(targets + 1)) + ceil(log2(receivers))
 // bits: one 64-bit sort when it fits, two or three stable passes when it does not (rts_post.hip: wide keys).  A configuration
 // beyond 256 bits would be refused HERE, when the scene or the receivers are set, not in the middle of a pulse loop.
-static int check_key_width(uint32_t depth, uint32_t n_targets, uint32_t n_rx, const char* who)
+int check_key_width(uint32_t depth, uint32_t n_targets, uint32_t n_rx, const char* who)
 {
     const RtsKeyPlan k = rts_key_plan_for(depth, n_targets, n_rx);
     if (!k.supported) {                               // (cannot happen within the other limits: 16 x 8 + 16 = 144 bits)
@@ -289,207 +237,7 @@ static int check_key_width(uint32_t depth, uint32_t n_targets, uint32_t n_rx, co
     return RTS_OK;
 }
 
-// ------------------------------------------------------------------------------------- scene
-extern "C" int rts_set_scene(RtsHandle c, const RtsMesh* meshes, uint32_t n_targets)
-{
-    CHECK_HANDLE(c);
-    CHECK_CLOSED(c);
-    { int rc = check_key_width(c->depth, n_targets, c->n_rx, "rts_set_scene"); if (rc != RTS_OK) return rc; }
-    if (n_targets && !meshes) { rts_set_error("rts_set_scene: null meshes"); return RTS_ERR_INVALID; }
-    if (n_targets > 254) { rts_set_error("rts_set_scene: more than 254 targets"); return RTS_ERR_UNSUPPORTED; }
-    std::vector<RtsMeshHost> mh(n_targets);
-    uint64_t nt = 0, nv = 0, nn = 0;
-    for (uint32_t t = 0; t < n_targets; t++) {
-        const RtsMesh& m = meshes[t];
-        if ((m.n_triangles && !m.triangles) || (m.n_vertices && !m.vertices) || (m.n_normals && !m.normals)) { rts_set_error("rts_set_scene: target %u has null arrays", t); return RTS_ERR_INVALID; }
-        mh[t].n_tris = m.n_triangles; mh[t].n_verts = m.n_vertices; mh[t].n_normals = m.n_normals;
-        mh[t].tri_base = (uint32_t)nt; mh[t].vert_base = (uint32_t)nv; mh[t].normal_base = (uint32_t)nn;
-        mh[t].refl_coeff = m.refl_coeff; mh[t].refr_index = m.refr_index;
-        mh[t].perface = m.n_normals > m.n_vertices;                              // triangle_mesh.cu:178
-        nt += m.n_triangles; nv += m.n_vertices; nn += m.n_normals;
-        if (nt > 0x7ffffff0ULL || nv > 0x7ffffff0ULL || nn > 0x7ffffff0ULL) { rts_set_error("rts_set_scene: scene too large"); return RTS_ERR_UNSUPPORTED; }
-    }
-    std::vector<uint32_t> vidx(3*nt), nidx(3*nt), vtarg(nv), ntarg(nn), ptarg(nt);
-    std::vector<double> verts(3*nv), normals(3*nn);
-    for (uint32_t t = 0; t < n_targets; t++) {
-        const RtsMesh& m = meshes[t]; const RtsMeshHost& h = mh[t];
-        for (uint32_t i = 0; i < m.n_triangles; i++) {
-            for (int k = 0; k < 3; k++) {
-                uint32_t v = m.triangles[3*(size_t)i + k];
-                if (v >= m.n_vertices) { rts_set_error("rts_set_scene: target %u triangle %u references vertex %u >= %u", t, i, v, m.n_vertices); return RTS_ERR_INVALID; }
-                vidx[3*((size_t)h.tri_base + i) + k] = h.vert_base + v;
-                // dbuf_normals is indexed by the vertex index (triangle_mesh.cu:170-172), or by the
-                // primitive index for per-face ("rect") normals (:178-180)
-                uint32_t ni = h.perface ? i : v;
-                if (m.n_normals == 0) ni = 0; else if (ni >= m.n_normals) { rts_set_error("rts_set_scene: target %u normal index %u >= %u", t, ni, m.n_normals); return RTS_ERR_INVALID; }
-                nidx[3*((size_t)h.tri_base + i) + k] = h.normal_base + ni;
-            }
-            ptarg[(size_t)h.tri_base + i] = t;
-        }
-        if (m.n_triangles && m.n_normals == 0 && c->params.interpolate_smooth) { rts_set_error("rts_set_scene: target %u has no normals but interpolate_smooth is set", t); return RTS_ERR_INVALID; }
-        for (uint32_t i = 0; i < m.n_vertices; i++) { vtarg[(size_t)h.vert_base + i] = t; for (int k = 0; k < 3; k++) verts[3*((size_t)h.vert_base + i) + k] = m.vertices[3*(size_t)i + k]; }
-        for (uint32_t i = 0; i < m.n_normals; i++) { ntarg[(size_t)h.normal_base + i] = t; for (int k = 0; k < 3; k++) normals[3*((size_t)h.normal_base + i) + k] = m.normals[3*(size_t)i + k]; }
-    }
-    // ---- the new scene object (swapped in at the end; every failure path below leaves the handle's old scene alone)
-    std::unique_ptr<RtsScene> guard(new RtsScene());
-    RtsScene* ns = guard.get(); ns->device = c->device;
-    RTS_HIP(hipStreamSynchronize(c->stream));
-    RTS_HIP(ns->d_tri_vidx.reserve(3*nt + 1)); RTS_HIP(ns->d_tri_nidx.reserve(3*nt + 1)); RTS_HIP(ns->d_vert_targ.reserve(nv + 1)); RTS_HIP(ns->d_norm_targ.reserve(nn + 1));
-    RTS_HIP(ns->d_prim_targ.reserve(nt + 1)); RTS_HIP(ns->d_verts_local.reserve(3*nv + 1)); RTS_HIP(ns->d_normals_local.reserve(3*nn + 1));
-    if (nt) { RTS_HIP(hipMemcpy(ns->d_tri_vidx.p, vidx.data(), sizeof(uint32_t)*3*nt, hipMemcpyHostToDevice)); RTS_HIP(hipMemcpy(ns->d_tri_nidx.p, nidx.data(), sizeof(uint32_t)*3*nt, hipMemcpyHostToDevice));
-              RTS_HIP(hipMemcpy(ns->d_prim_targ.p, ptarg.data(), sizeof(uint32_t)*nt, hipMemcpyHostToDevice)); }
-    if (nv) { RTS_HIP(hipMemcpy(ns->d_vert_targ.p, vtarg.data(), sizeof(uint32_t)*nv, hipMemcpyHostToDevice)); RTS_HIP(hipMemcpy(ns->d_verts_local.p, verts.data(), sizeof(double)*3*nv, hipMemcpyHostToDevice)); }
-    if (nn) { RTS_HIP(hipMemcpy(ns->d_norm_targ.p, ntarg.data(), sizeof(uint32_t)*nn, hipMemcpyHostToDevice)); RTS_HIP(hipMemcpy(ns->d_normals_local.p, normals.data(), sizeof(double)*3*nn, hipMemcpyHostToDevice)); }
-    ns->meshes = mh; ns->n_prims = (uint32_t)nt; ns->n_verts = (uint32_t)nv; ns->n_normals = (uint32_t)nn;
-
-    // ---- static target-space hierarchy, one per mesh; leaf slots name GLOBAL primitive ids.  Two builders, same node format:
-    //   device (default) top-down binned SAH over split references, built on the GPU level by level (rts_lbvh.hip): milliseconds;
-    //          RTS_DEVICE_TREE=lbvh: the Morton / Karras tree of round 2 instead
-    //   host   RTS_BUILDER=host / RtsParams.flags & RTS_FLAG_HOST_BUILD: the same algorithm with a greedier reference splitter on
-    //          one host thread per mesh (rts_sah.cpp): ~1 s per 100 k triangles; traces a lone C3 pulse 7 % faster (its slowest
-    //          tile runs through the pole fans of the synthetic airframe), the pipelined benchmark, the dense control, spheres
-    //          and C4 within 1-4 %
-    const auto t_build0 = std::chrono::steady_clock::now();
-    RtsSceneTuning st; st.device_build = (c->params.flags & RTS_FLAG_HOST_BUILD) == 0;
-    rts_tuning_read(&st, rts_env);
-    bool device_build = st.device_build;
-    // extra references for triangles whose boxes are mostly empty (rts_sah.cpp, rts_lbvh.hip): an average triangle gets about
-    // 1 + budget references where cutting pays (2 measured best for both builders)
-    const double split_budget = st.split_budget;
-    if (device_build) {
-        // The device builder sizes its bins by the references of a level and closes within 256 levels or gives up: out of memory, or
-        // a mesh it does not close on, must not fail the scene -- the host builder takes over (RTS_DEVICE_BUILD_FALLBACK=0:
-        // the error is returned, for tests of the builder itself).
-        int rc = rts_lbvh_build_device(c, ns, vidx, mh, st);
-        if (rc == RTS_OK && st.fail_device_build) { rts_set_error("rts_set_scene: device builder failure injected (RTS_DEBUG_FAIL_DEVICE_BUILD)"); rc = RTS_ERR_HIP; }      // tests: the fall-back below, with the builder's state to clean up
-        if (rc != RTS_OK) {
-            if (rc == RTS_ERR_INVALID || !st.build_fallback) return rc;
-            (void)hipGetLastError();                                     // (a failed allocation leaves a sticky error code behind)
-            fprintf(stderr, "[rts] device hierarchy build failed (%s): falling back to the host builder\n", rts_last_error());
-            ns->d_nodes4.release(); ns->d_leaf_prim.release(); ns->blas.clear(); ns->n_nodes = 0; ns->n_leaves = 0;
-            device_build = false;
-        } else ns->builder = 1;
-    }
-    if (!device_build) {
-        std::vector<RtsNode4> nodes4; std::vector<uint32_t> leaf_prim; std::vector<RtsBlasInfo> blas(n_targets);
-        {   // the meshes are independent: one host thread each (at most 16 at a time), results concatenated in target order
-            std::vector<std::vector<RtsNode4>> pn(n_targets); std::vector<std::vector<uint32_t>> pl(n_targets); std::vector<int> prc(n_targets, RTS_OK);
-            for (uint32_t t0 = 0; t0 < n_targets; t0 += 16) {
-                std::vector<std::thread> pool;
-                for (uint32_t t = t0; t < std::min(n_targets, t0 + 16); t++)
-                    pool.emplace_back([&, t]() { prc[t] = rts_sah_build(meshes[t].vertices, meshes[t].triangles, meshes[t].n_triangles, split_budget, pn[t], pl[t], blas[t]); });
-                for (auto& th : pool) th.join();
-            }
-            for (uint32_t t = 0; t < n_targets; t++) {
-                if (prc[t] != RTS_OK) return prc[t];
-                const int32_t node_base = (int32_t)nodes4.size(), leaf_base = (int32_t)leaf_prim.size();
-                for (RtsNode4 nd : pn[t]) {
-                    for (int k = 0; k < 4; k++) { int32_t& ch = nd.child[k]; if (ch == 0x7fffffff) continue; if (ch >= 0) ch += node_base; else ch = ~(~ch + leaf_base); }
-                    nodes4.push_back(nd);
-                }
-                for (uint32_t lp : pl[t]) leaf_prim.push_back(lp + mh[t].tri_base);
-                if (blas[t].root >= 0) blas[t].root += node_base;
-            }
-        }
-        RTS_HIP(ns->d_nodes4.reserve(nodes4.size() + 1)); RTS_HIP(ns->d_leaf_prim.reserve(leaf_prim.size() + 1));
-        if (!nodes4.empty()) RTS_HIP(hipMemcpy(ns->d_nodes4.p, nodes4.data(), sizeof(RtsNode4)*nodes4.size(), hipMemcpyHostToDevice));
-        if (!leaf_prim.empty()) RTS_HIP(hipMemcpy(ns->d_leaf_prim.p, leaf_prim.data(), sizeof(uint32_t)*leaf_prim.size(), hipMemcpyHostToDevice));
-        ns->blas = blas; ns->n_nodes = (uint32_t)nodes4.size(); ns->n_leaves = (uint32_t)leaf_prim.size();
-        ns->builder = 0;
-    }
-    // Leaf records are kept per PRIMITIVE, not per leaf slot (a triangle cut into several references has several slots): the
-    // nodes' leaf children are rewritten from ~slot to ~primitive here, once, whichever builder ran; the slot form is parked in
-    // the record's unused words for rts_get_bvh.  A third of the per-pulse leaf refresh and of the leaf bytes on C3 (300 k slots
-    // for 100 k triangles), and of the 240 MB per handle on BASELINE configs[3].
-    if (ns->n_nodes) { k_children_to_prims<<<(ns->n_nodes + 255) / 256, 256, 0, c->stream>>>(ns->d_nodes4.p, ns->n_nodes, ns->d_leaf_prim.p); RTS_HIP(hipGetLastError()); RTS_HIP(hipStreamSynchronize(c->stream)); }
-    // The order in which the per-pulse scene update visits the primitives (k_leaves, rts_bvh.hip): by first appearance in the leaf
-    // slots, so that a block's 256 triangles are neighbours in space whatever the mesh's own numbering (rts_prim_order.h).  Once
-    // per scene, whichever builder ran: one read-back of the slots, the de-duplication on the host.
-    if (ns->n_prims) {
-        std::vector<uint32_t> slots(ns->n_leaves);
-        RTS_HIP(hipStreamSynchronize(c->stream));
-        if (ns->n_leaves) RTS_HIP(hipMemcpy(slots.data(), ns->d_leaf_prim.p, sizeof(uint32_t) * ns->n_leaves, hipMemcpyDeviceToHost));
-        const std::vector<uint32_t> order = rts_prim_order(slots.data(), slots.size(), ns->n_prims);
-        RTS_HIP(ns->d_prim_order.reserve(order.size() + 1));
-        RTS_HIP(hipMemcpy(ns->d_prim_order.p, order.data(), sizeof(uint32_t) * order.size(), hipMemcpyHostToDevice));
-    }
-    {   // the octant versions of the node records (k_node_versions): RTS_NODE_VERSIONS=0: none; they need 1 KB per node -- a scene whose
-        // versions would not fit a quarter of the device's free memory goes without (the kernel then walks d_nodes4 as before)
-        const bool want = st.node_versions;
-        const int key_mode = st.version_key_centre ? 1 : 0;      // (measured, profiles/r05a_versions_ab.log: by centre the dense control visits 5.9 % more nodes than the sorted walk, by entry corner 9.6 %)
-        size_t free_b = 0, total_b = 0; (void)hipMemGetInfo(&free_b, &total_b);
-        const size_t need = (size_t)ns->n_nodes * 8 * sizeof(RtsNode4);
-        if (want && ns->n_nodes && ns->n_nodes < (1u << 28) && need < free_b / 4) {
-            if (ns->d_nodes4v.reserve((size_t)ns->n_nodes * 8) == hipSuccess) {
-                k_node_versions<<<(ns->n_nodes * 8u + 255u) / 256u, 256, 0, c->stream>>>(ns->d_nodes4.p, ns->n_nodes, ns->d_nodes4v.p, key_mode);
-                RTS_HIP(hipGetLastError()); RTS_HIP(hipStreamSynchronize(c->stream));
-            } else (void)hipGetLastError();
-        }
-    }
-    ns->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_build0).count();
-
-    // ---- swap it in
-    rts_scene_unref(c->scene);
-    c->scene = guard.release();
-    return rts_attach_scene(c);
-}
-
-// Per-handle buffers sized by the scene the handle now points at; placement and tile history start afresh.
-static int rts_attach_scene(RtsContext* c)
-{
-    const RtsScene* sc = c->scene; const uint32_t n_targets = (uint32_t)sc->meshes.size();
-    RTS_HIP(c->d_leaves.reserve((size_t)sc->n_prims + 1));      // one record per primitive (k_children_to_prims)
-    RTS_HIP(c->d_verts_world.reserve(3*(size_t)sc->n_verts + 1)); RTS_HIP(c->d_normals_world.reserve(3*(size_t)sc->n_normals + 1));
-    {   // device image of the pinned block's [lc | motion | td]
-        const size_t span = offsetof(RtsPinned, cnt);
-        RTS_HIP(c->d_params.reserve(span));
-        c->p_lc = reinterpret_cast<RtsLaunchConsts*>(c->d_params.p + offsetof(RtsPinned, lc));
-        c->p_motion = reinterpret_cast<RtsTargetMotion*>(c->d_params.p + offsetof(RtsPinned, motion));
-        c->p_targets = reinterpret_cast<RtsTargetDev*>(c->d_params.p + offsetof(RtsPinned, td));
-        c->rcs_uploaded = false;
-    }
-    c->verts_world_valid = false; c->order_sum_valid = false;
-    if (c->hist->refs.load() > 1) { rts_hist_unref(c->hist); c->hist = new RtsTileHist(); }      // (a handle that leaves a shared scene leaves the shared history)
-    c->motion.assign(n_targets, RtsTargetMotion{}); c->motion_valid = false; c->bvh_valid = false; c->hist->n = 0; c->hist->any = false; c->hist->head_hint_valid = false; c->tile_cost_pending = false; c->tile_last_valid = false;
-    return RTS_OK;
-}
-
-// rts_share_scene: dst drops its own scene and uses src's (same device): the meshes, the hierarchy and its leaf order then
-// exist once however many handles keep pulses in flight, and the hierarchy is built once.
-extern "C" int rts_share_scene(RtsHandle dst, RtsHandle src)
-{
-    if (!dst || !src || dst == src) { rts_set_error("rts_share_scene: needs two distinct handles"); return RTS_ERR_INVALID; }
-    if (dst->device != src->device) { rts_set_error("rts_share_scene: handles live on different devices (%d, %d)", dst->device, src->device); return RTS_ERR_INVALID; }
-    if (dst->params.interpolate_smooth && !src->params.interpolate_smooth) {
-        for (const RtsMeshHost& m : src->scene->meshes) if (m.n_tris && m.n_normals == 0) { rts_set_error("rts_share_scene: the scene has a mesh without normals but the receiving handle interpolates normals"); return RTS_ERR_INVALID; }
-    }
-    RtsContext* c = dst;
-    CHECK_HANDLE(c);
-    CHECK_CLOSED(c);
-    RTS_HIP(hipStreamSynchronize(c->stream));
-    if (dst->scene == src->scene) return RTS_OK;
-    rts_scene_unref(dst->scene);
-    dst->scene = src->scene; dst->scene->refs++;
-    { int rc = rts_attach_scene(dst); if (rc != RTS_OK) return rc; }
-    if (dst->tune.share_history && src->tune.share_history && dst->params.width == src->params.width) {      // ... and the tile-cost history of the scene's handles (RtsTileHist)
-        rts_hist_unref(dst->hist);
-        dst->hist = src->hist; dst->hist->refs++;
-    }
-    return RTS_OK;
-}
-
-extern "C" int rts_scene_info(RtsHandle c, RtsSceneInfo* out)
-{
-    if (!c || !out) { rts_set_error("rts_scene_info: null argument"); return RTS_ERR_INVALID; }
-    const RtsScene* sc = c->scene;
-    memset(out, 0, sizeof(*out));
-    out->n_targets = (uint32_t)sc->meshes.size(); out->n_prims = sc->n_prims; out->n_nodes = sc->n_nodes; out->n_leaves = sc->n_leaves;
-    out->handles_sharing = (uint32_t)sc->refs.load(); out->builder = sc->builder; out->build_ms = sc->build_ms;
-    out->shared_device_bytes = sc->device_bytes(); out->version_bytes = sc->d_nodes4v.cap * sizeof(RtsNode4);
-    out->handle_device_bytes = c->d_leaves.cap * sizeof(RtsLeafTri) + c->d_verts_world.cap * 8 + c->d_normals_world.cap * 8 + c->d_params.cap;
-    return RTS_OK;
-}
-
+// ------------------------------------------------------------------------------------- receivers (the scene: rts_scene.hip)
 extern "C" int rts_set_receivers(RtsHandle c, const RtsReceiverSphere* rx, uint32_t n_rx)
 {
     CHECK_HANDLE(c);
@@ -1789,23 +1537,7 @@ void kernel_wrapper(PerRayData* h_rx_results_arr, int* h_rx_intersects_arr, unsi
 }
 }
 
-// ------------------------------------------------------------------------------------- introspection
-extern "C" int rts_get_bvh(RtsHandle c, void* nodes128, uint32_t* leaf_prim, int32_t* roots, uint32_t node_capacity, uint32_t leaf_capacity, uint32_t* n_leaves)
-{
-    CHECK_HANDLE(c);
-    if (n_leaves) *n_leaves = c->scene->n_leaves;
-    if ((nodes128 && node_capacity < c->scene->n_nodes) || (leaf_prim && leaf_capacity < c->scene->n_leaves)) { rts_set_error("rts_get_bvh: capacity too small (%u nodes, %u leaves)", c->scene->n_nodes, c->scene->n_leaves); return RTS_ERR_CAPACITY; }
-    RTS_HIP(hipStreamSynchronize(c->stream));
-    if (nodes128 && c->scene->n_nodes) {
-        RTS_HIP(hipMemcpy(nodes128, c->scene->d_nodes4.p, sizeof(RtsNode4)*c->scene->n_nodes, hipMemcpyDeviceToHost));
-        RtsNode4* nd = static_cast<RtsNode4*>(nodes128);              // (the builders' form: leaf children as ~slot, see k_children_to_prims)
-        for (uint32_t i = 0; i < c->scene->n_nodes; i++) for (int k = 0; k < 4; k++) { nd[i].child[k] = nd[i].pad[k]; nd[i].pad[k] = 0; }
-    }
-    if (leaf_prim && c->scene->n_leaves) RTS_HIP(hipMemcpy(leaf_prim, c->scene->d_leaf_prim.p, sizeof(uint32_t)*c->scene->n_leaves, hipMemcpyDeviceToHost));
-    if (roots) for (size_t t = 0; t < c->scene->blas.size(); t++) roots[t] = c->scene->blas[t].root;
-    return RTS_OK;
-}
-
+// ------------------------------------------------------------------------------------- self test
 __global__ void k_self_test_math(const float* y, const float* x, float* at, const double* a, const double* b, double* dv, double* sq, uint32_t n)
 {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -22,22 +22,15 @@
 #include "rts_launch_plan.h"      // RTS_BLOCK, RTS_WTILE, RTS_COOP_GROUP, RTS_STACK_OVF and the host arithmetic of a launch
 #include "rts_post_plan.h"        // RTS_SMALL_CAP32 / 64, RTS_AGG_TILE and the host arithmetic of the post-processing
 #include "rts_pulse_state.h"      // RtsPulseState: IDLE / OPEN / CHAINED, and the only code that moves the per-device count of open pulses
+#include "rts_scene_host.h"       // RtsNode4, RtsBlasInfo, RtsMeshHost; the flattening of the caller's meshes, the host trees' concatenation, a mesh's bounds
 #include "rts_tuning.h"           // RTS_STACK_LDS; RtsTuning, RtsSceneTuning: what the RTS_* environment switches fill, their table and its reader
 static_assert(RtsTuning().img_split_below == RTS_IMAGE_SPLIT_BELOW, "the default of RTS_IMAGE_SPLIT_BELOW is rts_image.h's");
 
 // ----------------------------------------------------------------------------- HBM layout
-// BVH4 node, 128 B = one cache line, of the static target-space hierarchy (rts_sah.cpp): half the dependent fetch
-// round-trips of a binary tree per ray.  SoA over the four children so that one dwordx4 load brings the same plane of
-// all four (padded, f32, TARGET-SPACE) boxes.  Unused slots: empty box (never hit).
-struct __attribute__((aligned(128))) RtsNode4 {
-    float lox[4], loy[4], loz[4], hix[4], hiy[4], hiz[4];
-    int32_t child[4];               // >= 0 -> node index, < 0 -> ~leaf slot, 0x7fffffff -> unused
-    int32_t pad[4];
-};
-static_assert(sizeof(RtsNode4) == 128, "node4 size");
+// (the BVH4 node of the static hierarchy, RtsNode4: rts_scene_host.h)
 
 // Leaf record, 112 B (the bytes a lane at a node reads of its record: the same seven dwordx4 loads serve both), ONE PER
-// PRIMITIVE and indexed by the global primitive id (the nodes' leaf children name primitives: k_children_to_prims, rts_api.hip;
+// PRIMITIVE and indexed by the global primitive id (the nodes' leaf children name primitives: k_children_to_prims, rts_scene.hip;
 // only the ORDER in which k_leaves visits them follows the hierarchy's leaf slots, RtsScene::d_prim_order), refreshed every
 // pulse: what the f64 intersection test needs of the triangle and
 // what does not depend on the ray -- the first WORLD-space vertex, pre-gathered (the reference gathers through
@@ -72,9 +65,6 @@ struct RtsTargetDev {               // per target, per pulse
                                     // vertices, of the exact test and of the world -> target mapping (~1e-12 of the world scale)
     int32_t root;                   // root node of the target's hierarchy, < 0: no (finite) geometry
 };
-
-// One mesh's slice of the static hierarchy (host side).
-struct RtsBlasInfo { int32_t root; uint32_t n_nodes, n_leaves, depth; double lo[3], hi[3], max_abs; };
 
 struct RtsRxDev { double cx, cy, cz, radius, minTheta, maxTheta, minPhi, maxPhi; };
 
@@ -181,7 +171,7 @@ struct RtsTraceArgs {
     RtsChildState* child;           // [2][grid threads] (refraction only)
     // scene
     const RtsNode4* nodes4;
-    const RtsNode4* nodes4v;        // != null: the eight OCTANT VERSIONS of every node record, [node][octant] (k_node_versions, rts_api.hip): the ordinary kernel walks these
+    const RtsNode4* nodes4v;        // != null: the eight OCTANT VERSIONS of every node record, [node][octant] (k_node_versions, rts_scene.hip): the ordinary kernel walks these
     const RtsLeafTri* leaves;
     const uint32_t* tri_nidx;       // [n_prims][3] indices into normals
     const double* normals;          // world-space normals [.][3]
@@ -217,13 +207,6 @@ struct RtsTraceArgs {
 };
 
 // ----------------------------------------------------------------------------- host context
-struct RtsMeshHost {
-    uint32_t n_tris, n_verts, n_normals;
-    uint32_t tri_base, vert_base, normal_base;
-    double refl_coeff, refr_index;
-    bool perface;
-};
-
 // Pinned host staging (hipHostMalloc): every small per-pulse upload/readback goes through it, so the
 // stream never has to be drained just to recycle a pageable temporary.
 #define RTS_PIN_GROUPS 4096
@@ -461,7 +444,7 @@ void rts_gate_unref(RtsGate* g);            // ... and destroys the group's trac
 
 // implemented in the .hip units
 int rts_sah_build(const double* verts, const uint32_t* tris, uint32_t n_tris, double split_budget, std::vector<RtsNode4>& nodes, std::vector<uint32_t>& leaf_prim, RtsBlasInfo& out);
-int rts_lbvh_build_device(RtsContext* c, RtsScene* ns, const std::vector<uint32_t>& vidx, const std::vector<RtsMeshHost>& mh, const RtsSceneTuning& tune);
+int rts_lbvh_build_device(RtsContext* c, RtsScene* ns, const RtsSceneFlat& flat, const RtsSceneTuning& tune);
 int rts_scene_place(RtsContext* c, const RtsLaunchConsts& lc, bool place, uint32_t* pmask);      // placement kernels (place) + the primary-ray mask (lc.mask.n != 0)
 int rts_tile_costs_flush(RtsContext* c);      // merge the cost records of the last launch into the history now (before its launch shape goes away)
 int rts_tile_records_masked(RtsContext* c, uint32_t* d_out, uint32_t n);      // the history's records of the tiles the last launch traced, 0 elsewhere
@@ -499,7 +482,9 @@ int rts_aggregate_device(RtsContext* c, int32_t max_path, int32_t max_rx, const 
                          double cspeed, double carrier, uint64_t base, PerRayData* d_rays, double* d_delay,
                          double* d_phase, int32_t* d_pm, std::vector<RtsGroup>* groups, double* d_npath,
                          double* d_power_sum, double* d_doppler_sum, int32_t pm_init, const uint64_t* d_rows);
-void rts_set_error(const char* fmt, ...);
+const char* rts_env(const char* name);      // the environment, for the readers of rts_tuning.h (rts_api.hip: the library looks at it nowhere else)
+int check_key_width(uint32_t depth, uint32_t n_targets, uint32_t n_rx, const char* who);      // rts_api.hip: the aggregation key of a scene and a receiver set fits
+int rts_attach_scene(RtsContext* c);        // rts_scene.hip: per-handle buffers sized by the scene the handle now points at
 // RTS_DEBUG_SYNC=1: synchronise after every stage and name it on stderr, so that a device
 // fault is attributed to the kernel that caused it
 int rts_debug_stage(RtsContext* c, const char* name);

@@ -643,31 +643,20 @@ __global__ void k_valid_key(const float* __restrict__ ref_box, uint64_t* __restr
 
 }  // namespace
 
-// vidx: [n_prims][3] GLOBAL vertex indices (host copy of ns->d_tri_vidx); mh: per-mesh slices.  Fills ns->d_nodes4,
+// flat: the scene as rts_set_scene uploaded it (ns->d_tri_vidx and ns->d_verts_local hold flat.vidx and flat.verts).  Fills ns->d_nodes4,
 // ns->d_leaf_prim, ns->blas, ns->n_nodes, ns->n_leaves.  Uses the handle's stream; temporaries are freed before returning.
 // split_budget: aimed-at extra references per triangle (0: one reference per triangle); the threshold of ref_count is the
 // mesh's mean box area / (1 + budget)^2, i.e. an average triangle gets about 1 + budget references.
-int rts_lbvh_build_device(RtsContext* c, RtsScene* ns, const std::vector<uint32_t>& vidx, const std::vector<RtsMeshHost>& mh, const RtsSceneTuning& tune)
+int rts_lbvh_build_device(RtsContext* c, RtsScene* ns, const RtsSceneFlat& flat, const RtsSceneTuning& tune)
 {
     hipStream_t st = c->stream;
+    const std::vector<RtsMeshHost>& mh = flat.meshes;
     const uint32_t n_targets = (uint32_t)mh.size();
     ns->blas.assign(n_targets, RtsBlasInfo{});
-    // host pass: the f64 bounds of every mesh over its finite triangles (for the per-pulse placement constants)
-    std::vector<double> hv(3 * (size_t)ns->n_verts);
-    if (ns->n_verts) RTS_HIP(hipMemcpy(hv.data(), ns->d_verts_local.p, sizeof(double) * hv.size(), hipMemcpyDeviceToHost));
     uint32_t n_max = 0;
     for (uint32_t t = 0; t < n_targets; t++) {
         RtsBlasInfo& b = ns->blas[t]; b.root = -1; b.depth = 64;
-        double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        uint32_t nv = 0;
-        for (uint32_t i = 0; i < mh[t].n_tris; i++) {
-            bool finite = true;
-            for (int k = 0; k < 3; k++) { const double* p = &hv[3 * (size_t)vidx[3 * ((size_t)mh[t].tri_base + i) + k]]; finite = finite && std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]); }
-            if (!finite) continue;
-            nv++;
-            for (int k = 0; k < 3; k++) { const double* p = &hv[3 * (size_t)vidx[3 * ((size_t)mh[t].tri_base + i) + k]]; for (int a = 0; a < 3; a++) { lo[a] = std::min(lo[a], p[a]); hi[a] = std::max(hi[a], p[a]); } }
-        }
-        for (int a = 0; a < 3; a++) { b.lo[a] = nv ? lo[a] : 0; b.hi[a] = nv ? hi[a] : 0; b.max_abs = std::max(b.max_abs, std::max(std::fabs(b.lo[a]), std::fabs(b.hi[a]))); }
+        rts_mesh_bounds(flat, t, &b);
         n_max = std::max(n_max, mh[t].n_tris);
     }
     ns->n_nodes = 0; ns->n_leaves = 0;

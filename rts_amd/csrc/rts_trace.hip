@@ -166,7 +166,7 @@ __device__ __attribute__((noinline)) int rts_stack_below_spilled(int from_lds, i
 //   RTS_WALK_ROLES     the role fetch above (entry / exit planes by per-axis address offsets), children sorted by entry distance;
 //   RTS_WALK_PLANES    the record read straight through (low / high planes; lr by plane, rts_slab_by_plane), children sorted -- the cooperative kernel's;
 //   RTS_WALK_VERSIONS  the record of the ray's OCTANT (a.nodes4v: eight versions per node, written once per scene by k_node_versions,
-//                      rts_api.hip) read straight through: its planes are already entry / exit planes for every ray of that octant and its
+//                      rts_scene.hip) read straight through: its planes are already entry / exit planes for every ray of that octant and its
 //                      children are already in front-to-back order along the octant's diagonal -- no address arithmetic per axis, no
 //                      sorting network (5 compares + 20 selects of the node step), no +inf selects.  The ORDER only decides what gets
 //                      pruned, never the result: every child whose slab interval is open is visited in either scheme, and the closest hit

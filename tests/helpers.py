@@ -1,8 +1,37 @@
 """Shared drivers for the parity tests: run the same scene spec through the oracle (checker)
 and through the product (librts_amd.so via ctypes) and compare."""
+import os
+import shutil
+import subprocess
+
 import numpy as np
+import pytest
 
 from rts_amd import scenes
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def host_driver(tmp_path_factory, source):
+    """The stand-alone driver tests/<source> of a host-only header of rts_amd/csrc: built with g++ (under AddressSanitizer +
+    UndefinedBehaviorSanitizer where g++ has the runtime) and run as a child process.  Returns run(text) -> its stdout for the
+    cases `text` on stdin; a sanitizer report, or any other non-zero exit, fails the test."""
+    gxx = shutil.which("g++")
+    if not gxx:
+        pytest.skip("needs g++")
+    rt = subprocess.run([gxx, "-print-file-name=libasan.so"], capture_output=True, text=True).stdout.strip()
+    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if os.path.isabs(rt) and os.path.exists(rt) else []
+    name = os.path.splitext(os.path.basename(source))[0]
+    exe = str(tmp_path_factory.mktemp(name) / name)
+    subprocess.check_call([gxx, "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror"] + san +
+                          ["-I", os.path.join(ROOT, "rts_amd", "csrc"), os.path.join(ROOT, "tests", source), "-o", exe])
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+
+    def run(text):
+        r = subprocess.run([exe], input=text, capture_output=True, text=True, env=env, timeout=120)
+        assert r.returncode == 0, r.stderr[-3000:]
+        return r.stdout
+    return run
 
 
 def oracle_scene(O, spec, motion=None):

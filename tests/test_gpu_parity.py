@@ -1283,7 +1283,7 @@ def test_cooperative_units_are_invisible(rts, oracle, scenes, monkeypatch):
 
 
 def test_octant_versions_are_invisible(rts, oracle, scenes, monkeypatch):
-    """round 5: the ordinary trace kernel walks the OCTANT VERSIONS of the node records (k_node_versions, rts_api.hip: per node eight
+    """round 5: the ordinary trace kernel walks the OCTANT VERSIONS of the node records (k_node_versions, rts_scene.hip: per node eight
     records whose planes are entry / exit planes for a ray of that octant and whose children sit in front-to-back order along the
     octant's diagonal -- no sorting network, no per-axis fetch addresses; k_trace<.., VERS>).  The visiting ORDER only decides what
     is pruned: every output buffer must be the same bits with the versions walked (the default) and with the role fetch + sorted

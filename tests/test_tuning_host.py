@@ -217,8 +217,9 @@ def test_the_environment_is_read_in_one_place():
                         hits.append((fn, line.strip()))
                     if fn != "rts_tuning.h":
                         reads += [(fn, m) for m in re.findall(r"\brts_tuning_read\(([^)]*)\)", line)]
-    assert hits == [("rts_api.hip", "static const char* rts_env(const char* name) { return getenv(name); }")]
-    assert len(reads) == 4 and all(fn == "rts_api.hip" and args.endswith(", rts_env") for fn, args in reads), reads
+    assert hits == [("rts_api.hip", "const char* rts_env(const char* name) { return getenv(name); }")]
+    assert len(reads) == 4 and all(args.endswith(", rts_env") for fn, args in reads), reads
+    assert sorted(fn for fn, _ in reads) == ["rts_api.hip"] * 3 + ["rts_scene.hip"]                 # (the scene's switches: rts_set_scene)
 
 
 def test_integration_md_lists_exactly_these_switches():
