@@ -7,10 +7,11 @@
 // It exists so that tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg can
 // CHECK the HIP product path.  Nothing under rts_amd/ may include, link or call it.
 //
-// PARITY STATUS: *parity unpinned*.  The reference ships no tests, golden vectors or
-// fixtures and cannot be compiled here (needs NVIDIA OptiX <= 6.x, nvcc and the SOARS
-// rs*.cuh headers).  The oracle is pinned only by (1) the closed-form known-answer tests
-// derivable from the cited formulas (tests/test_oracle_kat.py) and (2) the source text.
+// PARITY STATUS: the device programs (triangle_mesh.cu, normal_shader.cu, ray_tracer.cu) and the two aggregation
+// kernels are PINNED on the CPU: oracle/refshim compiles the reference's own sources, unmodified, against stand-in
+// headers, and tests/test_reference_pin.py compares this file with them bit for bit (no difference found).  The OptiX
+// traversal, CUDA's atan2f bits and the reference's host program (needs the OptiX <= 6.x host API, nvcc and the SOARS
+// rs*.cuh headers) remain restated: held by the closed-form known-answer tests (tests/test_oracle_kat.py) and the text.
 //
 // Third-party arithmetic that is NOT under /root/reference (NVIDIA OptiX SDK, legacy rt*
 // API, version unpinned by the reference) is restated from its published semantics:
@@ -831,6 +832,45 @@ int orc_trace(void* s, const OPulse* p, uint64_t ray_first, uint64_t ray_stride,
 int orc_bound(const double* v0, const double* v1, const double* v2, float* out6)
 {
     return prim_bound(to_double3(v0[0],v0[1],v0[2]), to_double3(v1[0],v1[1],v1[2]), to_double3(v2[0],v2[1],v2[2]), out6) ? 1 : 0;
+}
+
+void orc_bound_n(uint64_t n, const double* v /* [n][3][3] */, float* out /* [n][6] */, int* valid)
+{
+    for (uint64_t i = 0; i < n; i++) valid[i] = orc_bound(v + 9*i, v + 9*i + 3, v + 9*i + 6, out + 6*i);
+}
+
+// ---------------------------------------------------------------- triangle_mesh.cu:142-200 on one ray and one triangle
+// test_prim() -- the function every segment of orc_trace goes through -- on a one-triangle mesh.  origin / dir: the payload's
+// f64 prevHitPoint / rayDirection; tmin / tmax: the ray's.  normals [nnormals][3], nnormals >= 3; nnormals > 3 is the
+// "more normals than vertices" rule (:178).  Returns 1 on an accepted hit, with its f32 t and the attribute normal.
+int orc_intersect(const double* origin, const double* dir, float tmin, float tmax, const double* verts9, const double* normals,
+                  uint32_t nnormals, int smooth, float* t_out, double* normal_out)
+{
+    OScene sc; OMesh m;
+    m.tris = {0, 1, 2};
+    for (int k = 0; k < 3; k++) m.verts.push_back(to_double3(verts9[3*k], verts9[3*k+1], verts9[3*k+2]));
+    for (uint32_t k = 0; k < nnormals; k++) m.normals.push_back(to_double3(normals[3*k], normals[3*k+1], normals[3*k+2]));
+    m.reflCoeff = 1; m.refrIndex = 1; m.vel = to_double3(0, 0, 0);
+    sc.meshes.push_back(std::move(m));
+    OPulse p; memset(&p, 0, sizeof(p)); p.interpolate_smooth = smooth ? 1 : 0;
+    OTraceCtx cx; cx.sc = &sc; cx.p = &p; cx.triTests = 0;
+    PerRayData prd; memset(&prd, 0, sizeof(prd));
+    prd.prevHitPoint = to_double3(origin[0], origin[1], origin[2]); prd.rayDirection = to_double3(dir[0], dir[1], dir[2]);
+    Ray ray; ray.origin = make_float3((float)origin[0], (float)origin[1], (float)origin[2]);
+    ray.direction = make_float3((float)dir[0], (float)dir[1], (float)dir[2]); ray.tmin = tmin; ray.tmax = tmax;
+    Hit h; h.found = false; h.t = 0; h.targ = h.prim = 0; h.normal = to_double3(0, 0, 0);
+    float cur_tmax = ray.tmax;
+    test_prim(cx, ray, prd, 0, 0, cur_tmax, h);
+    *t_out = h.found ? h.t : 0.0f;
+    normal_out[0] = h.found ? h.normal.x : 0.0; normal_out[1] = h.found ? h.normal.y : 0.0; normal_out[2] = h.found ? h.normal.z : 0.0;
+    return h.found ? 1 : 0;
+}
+void orc_intersect_n(uint64_t n, const double* origin, const double* dir, const float* tmin, const float* tmax, const double* verts9,
+                     const double* normals /* [n][nnormals][3] */, uint32_t nnormals, int smooth, int* hit, float* t_out, double* normal_out)
+{
+    for (uint64_t i = 0; i < n; i++)
+        hit[i] = orc_intersect(origin + 3*i, dir + 3*i, tmin[i], tmax[i], verts9 + 9*i, normals + 3*(size_t)nnormals*i, nnormals, smooth,
+                               t_out + i, normal_out + 3*i);
 }
 
 float orc_atan2f(float y, float x) { return orc_atan2f_cr(y, x); }

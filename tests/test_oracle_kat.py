@@ -1,8 +1,8 @@
 """Known-answer tests that pin the CPU oracle to the reference's formulas.
 
 The reference ships no tests or golden vectors; these closed-form cases are derived from the
-cited source lines and are what "pins" the oracle (parity status: unpinned by reference
-fixtures, pinned by KATs).  All run on the CPU.
+cited source lines and pin the oracle by formula; tests/test_reference_pin.py pins it to the
+reference's own device programs, bit for bit.  All run on the CPU.
 """
 import math
 
