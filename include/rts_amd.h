@@ -913,6 +913,71 @@ int rts_cube_mvdr(RtsHandle h, const RtsMvdrParams* p, void* device_out);       
 int rts_cube_mvdr_get(RtsHandle h, double* host_out, uint64_t capacity_doubles);
 int rts_mvdr_eval(const double* cov, uint32_t n_rx, const RtsMvdrParams* p, double* out);                                     /* pure host */
 
+/* ---------------------------------------------------------------- space-time adaptive processing (STAP): stacked covariance, tap filter
+ * The adaptive blocks above see ONE axis: the receivers of one cell.  On a moving platform the ground clutter is a ridge in the
+ * angle-Doppler plane; a spatial null or a Doppler filter alone removes the target with it or leaves its sidelobes.  STAP applies the
+ * same sample-matrix inversion to snapshots stacked over the receivers AND over n_taps consecutive rows (pulses).  The arithmetic is
+ * rts_amd/csrc/rts_stap.h, shared by the kernels (rts_adapt.hip: the covariance; rts_stap.hip: the filter) and the host evaluators.
+ * The trees hold + - * / only: device and evaluators agree BIT FOR BIT (the library builds with -ffp-contract=off).
+ *   Input z[rx][row][bin], complex128, from the beamformer's three sources under the beamformer's rules.  N = the cube's n_rx,
+ *   M = n_taps (1 .. RTS_ST_MAX_TAPS), D = M N <= RTS_BEAM_MAX_RX.  The snapshot at (row p, bin b) is
+ *     x[d] = z[d % N][p + d / N][b],  d = m N + rx      tap-major: a steering vector is temporal (x) spatial.
+ *   A span of n_rows rows (n_rows 0: from first_row to the source's last row) holds n_rows - M + 1 snapshot rows; n_rows < M is refused.
+ * rts_cube_st_covariance.  Output complex128 [D][D].  Training snapshots: the start rows first_row .. first_row + n_rows - M, of each
+ *   the bins rts_cube_covariance selects (span and skipped interval), numbered row-major c = 0 .. K - 1, K = (n_rows - M + 1) kept.
+ *   The tree is rts_cube_covariance's with x in place of z: term(i, j <= i, c) = x_i conj(x_j), tiles of RTS_ADAPT_TILE cells,
+ *   min(RTS_ADAPT_MAX_PARTS, tiles) parts, ascending sums, one division by (double)K, the exact conjugate in the upper triangle, +0.0
+ *   on the diagonal's imaginary part, no atomics.  With n_taps = 1 the output is rts_cube_covariance's, bit for bit.
+ *   A library-owned result (device_out NULL) becomes THE HANDLE'S LAST LIBRARY-OWNED COVARIANCE, of order D: rts_cube_mvdr with
+ *   device_cov NULL solves it (steering rows of D entries, the record's n_rx 0 or D) and rts_cube_covariance_get copies it (2 D D
+ *   doubles), through the code paths they have for rts_cube_covariance's.
+ * rts_cube_st_apply.  Weights w[f][d], complex128 on the host [n_filters][D], copied by the call (n_filters <= RTS_BEAM_MAX_BEAMS,
+ *   n_filters D <= RTS_BEAM_MAX_WEIGHTS).
+ *     y[f][p][b] = the sum of conj(w[f][d]) x[d] (rts_cube_beamform's term) over ascending d; the d = 0 term is the start value.
+ *   Output complex128 [n_filters][n_rows - M + 1][n_bins]: the layout of a cube with n_rx = n_filters and n_rows - M + 1 pulses, which
+ *   another handle attaches (rts_cube_attach with device_ptr) for rts_cube_doppler / rts_cube_detect*; with the flag RTS_BEAM_POWER
+ *   f64 re re + im im of the same shape.  No PEAK form.  Plain stores only: identical bits from run to run.  With n_taps = 1 the
+ *   output is rts_cube_beamform's, bit for bit.  rts_cube_st_get copies a library-owned output, under rts_cube_beam_get's rules.
+ * device_out, the stream and the staging of the weights: as rts_cube_covariance / rts_cube_beamform.
+ * rts_st_steering_make: pure host.  spatial [n_beams][n_rx] (rts_steering_make's rows), doppler [n_doppler] in cycles per pulse,
+ *   tap_taper [n_taps] real or NULL (1, and no multiply at all):
+ *     x = f (double)m;  fr = x - floor(x);  t_m = tap_taper[m] (cos 2 pi fr + j sin 2 pi fr), cosine and sine as in rts_steering_make;
+ *     out[beam n_doppler + k][m n_rx + rx] = t_m spatial[beam][rx] = (tr ar - ti ai, tr ai + ti ar).
+ *   The sign: rts_cube_doppler is sum_p cube[p] e^(-2 pi j k p / n_fft); a scatterer at f cycles per pulse advances by e^(+2 pi j f)
+ *   per pulse, and y = sum conj(w) x peaks in the filter steered at f.
+ * rts_st_covariance_eval / rts_st_apply_eval: pure host, no device: the same rts_stap.h functions on `in` [n_rx][n_rows_in][n_bins],
+ *   under rts_covariance_eval's / rts_beamform_eval's rules.  A refused call leaves out untouched.
+ * RTS_ERR_INVALID, the message naming the field: everything rts_cube_covariance / rts_cube_beamform refuse for the fields they share
+ *   (n_filters in n_beams' place), and: n_taps 0 or above RTS_ST_MAX_TAPS; n_taps * n_rx above RTS_BEAM_MAX_RX; n_rows (after the
+ *   default) below n_taps; flags other than RTS_BEAM_POWER; nonzero reserved fields; a caller-owned output that overlaps the input the
+ *   call reads; a shape the launch grid cannot take.  A refused call leaves the handle's previous products as they were. */
+#define RTS_ST_MAX_TAPS      16u
+typedef struct RtsStCovParams {
+    uint32_t source, n_rows_in;      /* as RtsCovParams                                                              */
+    uint32_t first_row, n_rows;      /* the span of rows the snapshots lie in; n_rows 0: to the source's last row    */
+    uint32_t first_bin, n_bins;
+    uint32_t skip_first_bin, skip_n_bins;
+    uint32_t n_taps, reserved0;      /* 1 .. RTS_ST_MAX_TAPS; 0                                                      */
+    const void* device_in;           /* POINTER only                                                                */
+    uint64_t reserved[2];            /* 0 */
+} RtsStCovParams;
+typedef struct RtsStApplyParams {
+    uint32_t n_filters, source;
+    uint32_t first_row, n_rows;      /* n_rows 0: from first_row to the last row of the source                      */
+    uint32_t n_rows_in, flags;       /* n_rows_in: POINTER only (0 otherwise); flags: RTS_BEAM_POWER                 */
+    uint32_t n_taps, reserved0;      /* 1 .. RTS_ST_MAX_TAPS; 0                                                      */
+    const double* weights;           /* host [n_filters][n_taps n_rx], interleaved re / im, finite                  */
+    const void* device_in;           /* POINTER only                                                                */
+    uint64_t reserved[2];            /* 0 */
+} RtsStApplyParams;
+int rts_cube_st_covariance(RtsHandle h, const RtsStCovParams* p, void* device_out);    /* complex128 [D][D], D = n_taps n_rx */
+int rts_st_covariance_eval(const RtsCubeParams* q, const double* in, uint32_t n_rows_in, const RtsStCovParams* p, double* out);  /* pure host */
+int rts_cube_st_apply(RtsHandle h, const RtsStApplyParams* p, void* device_out);       /* complex128 [n_filters][n_rows - n_taps + 1][n_bins] */
+int rts_cube_st_get(RtsHandle h, double* host_out, uint64_t capacity_doubles);
+int rts_st_apply_eval(const RtsCubeParams* q, const double* in, uint32_t n_rows_in, const RtsStApplyParams* p, double* out);     /* pure host */
+int rts_st_steering_make(const double* spatial, uint32_t n_rx, uint32_t n_beams, const double* doppler, uint32_t n_doppler,
+                         uint32_t n_taps, const double* tap_taper, double* out);                                                  /* pure host */
+
 /* ---------------------------------------------------------------- backprojection imaging (SAR / ISAR) of the return cube
  * A derived product like the cube itself: time-domain backprojection of a coherent interval onto a planar
  * pixel grid -- exact for any track, any bistatic geometry and any target motion, where the slow-time DFT focuses only while a

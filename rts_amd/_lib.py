@@ -209,6 +209,24 @@ class RtsMvdrParams(C.Structure):
 assert C.sizeof(RtsCovParams) == 56 and C.sizeof(RtsMvdrParams) == 48
 
 
+RTS_ST_MAX_TAPS = 16
+
+
+class RtsStCovParams(C.Structure):
+    _fields_ = [("source", C.c_uint32), ("n_rows_in", C.c_uint32), ("first_row", C.c_uint32), ("n_rows", C.c_uint32),
+                ("first_bin", C.c_uint32), ("n_bins", C.c_uint32), ("skip_first_bin", C.c_uint32), ("skip_n_bins", C.c_uint32),
+                ("n_taps", C.c_uint32), ("reserved0", C.c_uint32), ("device_in", C.c_void_p), ("reserved", C.c_uint64 * 2)]
+
+
+class RtsStApplyParams(C.Structure):
+    _fields_ = [("n_filters", C.c_uint32), ("source", C.c_uint32), ("first_row", C.c_uint32), ("n_rows", C.c_uint32),
+                ("n_rows_in", C.c_uint32), ("flags", C.c_uint32), ("n_taps", C.c_uint32), ("reserved0", C.c_uint32),
+                ("weights", C.c_void_p), ("device_in", C.c_void_p), ("reserved", C.c_uint64 * 2)]
+
+
+assert C.sizeof(RtsStCovParams) == 64 and C.sizeof(RtsStApplyParams) == 64
+
+
 class RtsSceneInfo(C.Structure):
     _fields_ = [("n_targets", C.c_uint32), ("n_prims", C.c_uint32), ("n_nodes", C.c_uint32), ("n_leaves", C.c_uint32),
                 ("handles_sharing", C.c_uint32), ("builder", C.c_uint32), ("build_ms", C.c_double),
@@ -300,7 +318,8 @@ EXPORTS = ["rts_create", "rts_destroy", "rts_last_error", "rts_device_count", "r
            "rts_cube_spectrogram", "rts_cube_spectrogram_get", "rts_stft_eval", "rts_window_make",
            "rts_cube_render_beat", "rts_beat_eval", "rts_cube_range_transform", "rts_cube_range_get", "rts_range_eval",
            "rts_cube_beamform", "rts_cube_beam_get", "rts_beamform_eval", "rts_steering_make",
-           "rts_cube_covariance", "rts_cube_covariance_get", "rts_covariance_eval", "rts_cube_mvdr", "rts_cube_mvdr_get", "rts_mvdr_eval"]
+           "rts_cube_covariance", "rts_cube_covariance_get", "rts_covariance_eval", "rts_cube_mvdr", "rts_cube_mvdr_get", "rts_mvdr_eval",
+           "rts_cube_st_covariance", "rts_st_covariance_eval", "rts_cube_st_apply", "rts_cube_st_get", "rts_st_apply_eval", "rts_st_steering_make"]
 
 
 def lib():
@@ -398,6 +417,12 @@ def lib():
         "rts_cube_mvdr": [vp, C.POINTER(RtsMvdrParams), vp],
         "rts_cube_mvdr_get": [vp, vp, u64],
         "rts_mvdr_eval": [vp, u32, C.POINTER(RtsMvdrParams), vp],
+        "rts_cube_st_covariance": [vp, C.POINTER(RtsStCovParams), vp],
+        "rts_st_covariance_eval": [C.POINTER(RtsCubeParams), vp, u32, C.POINTER(RtsStCovParams), vp],
+        "rts_cube_st_apply": [vp, C.POINTER(RtsStApplyParams), vp],
+        "rts_cube_st_get": [vp, vp, u64],
+        "rts_st_apply_eval": [C.POINTER(RtsCubeParams), vp, u32, C.POINTER(RtsStApplyParams), vp],
+        "rts_st_steering_make": [vp, u32, u32, vp, u32, u32, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name, None)

@@ -545,6 +545,71 @@ def mvdr_eval(cov, steering, loading=0.0):
     return out
 
 
+def _st_cov_params(taps, source, first, count, first_bin, n_bins, skip, device_in, n_rows_in):
+    """RtsStCovParams: _cov_params' fields (the rows are the span the snapshots lie in) and the taps"""
+    c = _cov_params(source, first, count, first_bin, n_bins, skip, device_in, n_rows_in)
+    p = L.RtsStCovParams()
+    for name in ("source", "n_rows_in", "first_row", "n_rows", "first_bin", "n_bins", "skip_first_bin", "skip_n_bins", "device_in"):
+        setattr(p, name, getattr(c, name))
+    p.n_taps = int(taps)
+    return p
+
+
+def st_covariance_eval(inp, taps, first=0, count=None, first_bin=0, n_bins=None, skip=None):
+    """rts_st_covariance_eval (pure host): the sample covariance of the snapshots stacked over the receivers and `taps` consecutive
+    rows, x[m n_rx + rx] = z[rx][p + m][b], of a host array [n_rx][n_rows][n_bins] (complex) -- start rows first .. first + count - taps
+    of the span of count rows (default: to the last), bins as covariance_eval: complex [taps n_rx][taps n_rx]"""
+    inp = np.ascontiguousarray(np.asarray(inp, np.complex128))
+    n_rx, rows, nb = inp.shape
+    q = L.RtsCubeParams(n_rx, rows, nb, 0, 0.0, 1.0)
+    p = _st_cov_params(taps, "cube", first, count, first_bin, n_bins, skip, None, 0)
+    D = n_rx * max(int(taps), 0)
+    out = np.zeros((D, D), np.complex128)
+    check(L.lib().rts_st_covariance_eval(C.byref(q), ptr(inp.view(np.float64)), rows, C.byref(p), ptr(out.view(np.float64))))
+    return out
+
+
+def _st_apply_params(weights, taps, n_rx, source, first, count, power, device_in, n_rows_in):
+    """RtsStApplyParams and the weight array it points to (keep it alive for the call); count None: to the source's last row"""
+    w = np.ascontiguousarray(np.asarray(weights, np.complex128))
+    if w.ndim != 2 or w.shape[1] != int(taps) * n_rx:
+        raise ValueError("st_apply: weights of shape %s for %d taps of %d receivers ([n_filters][taps n_rx])" % (w.shape, taps, n_rx))
+    p = L.RtsStApplyParams()
+    p.n_filters, p.source, p.n_taps = w.shape[0], _BEAM_SOURCES.get(source, source), int(taps)
+    p.first_row, p.n_rows, p.n_rows_in = int(first), int(count or 0), int(n_rows_in)
+    p.flags = L.RTS_BEAM_POWER if power else 0
+    p.weights = ptr(w.view(np.float64))
+    p.device_in = device_in if device_in else None
+    return p, w
+
+
+def st_apply_eval(inp, weights, taps, first=0, count=None, power=False):
+    """rts_st_apply_eval (pure host): y[f][p] = sum_d conj(w[f][d]) x[d] over the stacked snapshots (st_covariance_eval) of rows
+    first .. first + count - 1 (default: to the last) of a host array [n_rx][n_rows][n_bins] (complex), weights complex
+    [n_filters][taps n_rx]: complex [n_filters][count - taps + 1][n_bins], or its power (float64, same shape) with power"""
+    inp = np.ascontiguousarray(np.asarray(inp, np.complex128))
+    n_rx, rows, nb = inp.shape
+    q = L.RtsCubeParams(n_rx, rows, nb, 0, 0.0, 1.0)
+    p, keep = _st_apply_params(weights, taps, n_rx, "cube", first, count, power, None, 0)
+    out = _beam_out(p.n_filters, (p.n_rows if p.n_rows else rows - p.first_row) - p.n_taps + 1, nb, power, False)
+    check(L.lib().rts_st_apply_eval(C.byref(q), ptr(inp.view(np.float64)), rows, C.byref(p), ptr(out.view(np.float64))))
+    return out
+
+
+def st_steering(spatial, dopplers, taps, tap_taper=None):
+    """rts_st_steering_make (pure host): space-time steering rows temporal (x) spatial for spatial steering rows complex [n_beams][n_rx]
+    (steering), Doppler frequencies [n_doppler] in cycles per pulse and an optional real taper over the taps: complex
+    [n_beams n_doppler][taps n_rx], row beam n_doppler + k; y = sum conj(w) x peaks at a scatterer of that direction and frequency"""
+    a = np.ascontiguousarray(np.atleast_2d(np.asarray(spatial, np.complex128)))
+    f = np.ascontiguousarray(np.asarray(dopplers, np.float64).ravel())
+    t = None if tap_taper is None else np.ascontiguousarray(np.asarray(tap_taper, np.float64).ravel())
+    if t is not None and len(t) != int(taps):
+        raise ValueError("st_steering: a taper of %d values for %d taps" % (len(t), taps))
+    out = np.zeros((a.shape[0] * len(f), max(int(taps), 0) * a.shape[1]), np.complex128)
+    check(L.lib().rts_st_steering_make(ptr(a.view(np.float64)), a.shape[1], a.shape[0], ptr(f), len(f), int(taps), ptr(t), ptr(out.view(np.float64))))
+    return out
+
+
 def device_count():
     n = C.c_int(0)
     rc = L.lib().rts_device_count(C.byref(n))
@@ -940,6 +1005,49 @@ class Tracer:
         self.cube_covariance(fetch=False, **(train or {}))
         w = self.cube_mvdr(steering, loading)
         return self.cube_beamform(w, **beamform_kwargs)
+
+    def cube_st_covariance(self, taps, source="cube", first=0, count=None, first_bin=0, n_bins=None, skip=None, device_in=None, n_rows_in=0,
+                           device_ptr=None, fetch=True):
+        """rts_cube_st_covariance: the sample covariance of the snapshots stacked over the receivers and `taps` consecutive rows of the
+        source (st_covariance_eval; sources and training cells as cube_covariance, the rows being the span the snapshots lie in).
+        Complex [taps n_rx][taps n_rx] into a caller device tensor (device_ptr; nothing is fetched) or the library's output, which
+        is then the handle's covariance: covariance() returns it and cube_mvdr solves it"""
+        p = _st_cov_params(taps, source, first, count, first_bin, n_bins, skip, device_in, n_rows_in)
+        check(L.lib().rts_cube_st_covariance(self.h, C.byref(p), C.c_void_p(device_ptr) if device_ptr else None))
+        if device_ptr:
+            return None
+        self._cov_n = self._cube_shape[0] * p.n_taps
+        return self.covariance() if fetch else None
+
+    def cube_st_apply(self, weights, taps, source="cube", first=0, count=None, power=False, device_in=None, n_rows_in=0, device_ptr=None, fetch=True):
+        """rts_cube_st_apply: the space-time filters y[f][p] = sum_d conj(w[f][d]) x[d], weights complex [n_filters][taps n_rx], over
+        the stacked snapshots of rows first .. first + count - 1 (default: to the last) of the source (as cube_beamform).  Complex
+        [n_filters][count - taps + 1][n_bins] -- the layout of a cube of n_filters receivers and count - taps + 1 pulses --, or its
+        power with power.  Into a caller device tensor (device_ptr; nothing is fetched) or the library's output, returned when fetch"""
+        n_rx, n_p, nb = self._cube_shape
+        p, keep = _st_apply_params(weights, taps, n_rx, source, first, count, power, device_in, n_rows_in)
+        check(L.lib().rts_cube_st_apply(self.h, C.byref(p), C.c_void_p(device_ptr) if device_ptr else None))
+        if device_ptr:
+            return None
+        rows = {L.RTS_BEAM_FROM_CUBE: n_p, L.RTS_BEAM_FROM_MAP: getattr(self, "_doppler_n", 0)}.get(p.source, p.n_rows_in)
+        self._st_shape = (p.n_filters, (p.n_rows if p.n_rows else rows - p.first_row) - p.n_taps + 1, nb, bool(power), False)
+        return self.st_map() if fetch else None
+
+    def st_map(self):
+        """rts_cube_st_get: the library-owned output of the last cube_st_apply, in its form"""
+        out = _beam_out(*(getattr(self, "_st_shape", None) or (1, 1, 1, False, False)))
+        check(L.lib().rts_cube_st_get(self.h, ptr(out.view(np.float64)), out.view(np.float64).size))
+        return out
+
+    def cube_stap(self, spatial_steering, dopplers, taps, train=None, loading=0.0, **apply_kwargs):
+        """cube_st_covariance(taps, **train) -> cube_mvdr(st_steering(spatial_steering, dopplers, taps), loading) on the library-owned
+        covariance -> cube_st_apply(the weights, taps, **apply_kwargs): space-time filters, one per (beam, Doppler) pair in
+        st_steering's order, whose weights are computed from the training snapshots `train` names (cube_st_covariance's keywords;
+        default: every snapshot of the cube).  The cube stays on the device; the weights (at most 64 KiB) pass through the host.
+        Returns cube_st_apply's result."""
+        self.cube_st_covariance(taps, fetch=False, **(train or {}))
+        w = self.cube_mvdr(st_steering(spatial_steering, dopplers, taps), loading)
+        return self.cube_st_apply(w, taps, **apply_kwargs)
 
     def cube_compress(self, first=0, count=None):
         """rts_cube_compress: matched filter of rows first .. first + count - 1 (default: to the last pulse), in place"""

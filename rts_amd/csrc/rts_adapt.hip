@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include "rts_internal.h"
 #include "rts_adapt.h"
+#include "rts_stap.h"
 
 // The sample covariance is a rank-K update of the lower triangle of an n_rx x n_rx Hermitian matrix: per training cell
 // n_rx (n_rx + 1) / 2 terms of four multiplies, an add and a subtract plus the two adds of the running sum, all f64 and uncontracted
@@ -18,7 +19,8 @@ struct RtsCovArgs {
     const double2* in;                // receiver 0, row 0, bin 0 of the source
     uint64_t rx_stride, K, tiles;     // elements between two receivers of the source; training cells; tiles
     RtsCovSet set;
-    uint32_t row_bins, parts, n_rx, blocks;
+    uint32_t row_bins, parts, n_rx, blocks;       // n_rx: the matrix's order (the stacked form: n_taps n_sp)
+    uint32_t n_sp;                    // the stacked form (rts_stap.h): the source's receivers; row d of the matrix is receiver d % n_sp, d / n_sp rows on
     double2* part;                    // [parts][n_rx][n_rx]
     double2* out;                     // [n_rx][n_rx]
 };
@@ -36,7 +38,7 @@ __device__ __forceinline__ void rts_cov_cell(bool first, const double2* __restri
 
 // the staging of a tile, in two halves: the thread's cell of its receivers r_first, r_first + r_step, ... (at most RTS_ADAPT_STAGE:
 // rts_adapt.h's plan) from memory into registers, and from the registers into the receivers' LDS rows
-__device__ __forceinline__ void rts_cov_fetch(double2* pre, const RtsCovArgs& a, bool any, uint64_t tile, uint32_t cc, uint32_t r_first, uint32_t r_step)
+template <bool ST> __device__ __forceinline__ void rts_cov_fetch(double2* pre, const RtsCovArgs& a, bool any, uint64_t tile, uint32_t cc, uint32_t r_first, uint32_t r_step)
 {
     const uint64_t c = tile * RTS_ADAPT_TILE + cc;
     const bool live = any && c < a.K;
@@ -45,7 +47,7 @@ __device__ __forceinline__ void rts_cov_fetch(double2* pre, const RtsCovArgs& a,
     for (uint32_t k = 0; k < RTS_ADAPT_STAGE; k++) {       // (every register gets a value: the array stays in registers)
         const uint32_t r = r_first + k * r_step;
         double2 v = make_double2(0.0, 0.0);
-        if (live && r < a.n_rx) v = src[(uint64_t)r * a.rx_stride];
+        if (live && r < a.n_rx) v = src[ST ? rts_st_offset(r, a.n_sp, a.rx_stride, a.row_bins) : (uint64_t)r * a.rx_stride];
         pre[k] = v;
     }
 }
@@ -57,7 +59,8 @@ __device__ __forceinline__ void rts_cov_stage(const double2* pre, double2* s_z, 
 }
 
 // (five waves per SIMD: two workgroups of nine waves on a CU, one summing while the other stages)
-__global__ void __launch_bounds__(RTS_ADAPT_MAX_THREADS) __attribute__((amdgpu_waves_per_eu(5, 8))) k_cube_cov(const RtsCovArgs a)
+// ST: the stacked snapshots of rts_stap.h in place of the receivers -- only the staging's addresses differ
+template <bool ST> __global__ void __launch_bounds__(RTS_ADAPT_MAX_THREADS) __attribute__((amdgpu_waves_per_eu(5, 8))) k_cube_cov(const RtsCovArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) double2 s_cov_z[];            // [n_rx][RTS_ADAPT_TILE + 1], the rows in rts_cov_lds_row's order
     const uint32_t t = threadIdx.x, p = blockIdx.x, ld = RTS_ADAPT_TILE + 1u;
@@ -77,12 +80,12 @@ __global__ void __launch_bounds__(RTS_ADAPT_MAX_THREADS) __attribute__((amdgpu_w
     for (uint32_t k = 0; k < RTS_ADAPT_BLOCK * RTS_ADAPT_BLOCK; k++) acc[k / RTS_ADAPT_BLOCK][k % RTS_ADAPT_BLOCK] = make_double2(0.0, 0.0);
     const uint32_t cc = t % RTS_ADAPT_TILE, r_first = (uint32_t)__builtin_amdgcn_readfirstlane((int)(t / RTS_ADAPT_TILE)), r_step = blockDim.x / RTS_ADAPT_TILE;
     double2 pre[RTS_ADAPT_STAGE];                                                 // (r_first is the wave's: its receivers' addresses are scalar)
-    rts_cov_fetch(pre, a, true, tile0, cc, r_first, r_step);
+    rts_cov_fetch<ST>(pre, a, true, tile0, cc, r_first, r_step);
     for (uint64_t tile = tile0; tile < tile1; tile++) {
         __syncthreads();                                                          // (the previous tile's reads are done)
         rts_cov_stage(pre, s_cov_z, a, tile, cc, r_first, r_step);
         __syncthreads();
-        rts_cov_fetch(pre, a, tile + 1u < tile1, tile + 1u, cc, r_first, r_step);                  // the next tile: in flight while this one is summed
+        rts_cov_fetch<ST>(pre, a, tile + 1u < tile1, tile + 1u, cc, r_first, r_step);                  // the next tile: in flight while this one is summed
         const uint64_t left = a.K - tile * RTS_ADAPT_TILE;
         const uint32_t ncell = left < RTS_ADAPT_TILE ? (uint32_t)left : RTS_ADAPT_TILE;
         if (active) {
@@ -125,15 +128,17 @@ __global__ void __launch_bounds__(RTS_ADAPT_REDUCE_THREADS) k_cube_cov_reduce(co
     else { a.out[e] = s; a.out[(size_t)j * a.n_rx + i] = make_double2(s.x, -s.y); }
 }
 
-// in: the source's receiver 0, row 0 (device); rx_stride: its n_rows_in n_bins; part: plan.scratch_bytes of scratch
-int rts_cube_cov_device(RtsContext* c, const RtsCovSet& set, const RtsCovPlan& plan, const double* in, uint64_t rx_stride, double* part, double* out)
+// in: the source's receiver 0, row 0 (device); rx_stride: its n_rows_in n_bins; part: plan.scratch_bytes of scratch; n_taps 1: the
+// receivers' covariance, set and plan over the cube's n_rx; more: the stacked one, set over the snapshots' start rows, plan over n_taps n_rx
+int rts_cube_cov_device(RtsContext* c, const RtsCovSet& set, const RtsCovPlan& plan, uint32_t n_taps, const double* in, uint64_t rx_stride, double* part, double* out)
 {
     RtsCovArgs a;
     a.in = (const double2*)in; a.rx_stride = rx_stride; a.K = plan.K; a.tiles = plan.tiles; a.set = set;
-    a.row_bins = c->cube.params.n_bins; a.parts = plan.parts; a.n_rx = c->cube.params.n_rx; a.blocks = plan.blocks;
+    a.row_bins = c->cube.params.n_bins; a.parts = plan.parts; a.n_sp = c->cube.params.n_rx; a.n_rx = a.n_sp * n_taps; a.blocks = plan.blocks;
     a.part = (double2*)part; a.out = (double2*)out;
-    RTS_HIP(hipFuncSetAttribute((const void*)k_cube_cov, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
-    k_cube_cov<<<plan.parts, plan.threads, plan.lds, c->stream>>>(a);
+    void (*k)(const RtsCovArgs) = n_taps > 1u ? k_cube_cov<true> : k_cube_cov<false>;
+    RTS_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
+    k<<<plan.parts, plan.threads, plan.lds, c->stream>>>(a);
     RTS_HIP(hipGetLastError());
     k_cube_cov_reduce<<<plan.reduce_groups, RTS_ADAPT_REDUCE_THREADS, 0, c->stream>>>(a);
     RTS_HIP(hipGetLastError());

@@ -642,8 +642,9 @@ static int rts_cov_check(const RtsCovParams* p, uint32_t n_rx, const char* who)
     if (p->source == RTS_BEAM_FROM_POINTER && p->n_rows_in == 0) { rts_set_error("%s: n_rows_in = 0 with RTS_BEAM_FROM_POINTER", who); return RTS_ERR_INVALID; }
     return RTS_OK;
 }
-// the training set inside the source's rows and bins, and the plan of its launches
-static int rts_cov_set_check(const RtsCovParams* p, uint32_t rows, uint32_t n_rx, uint32_t nb, const char* who, RtsCovSet* set, RtsCovPlan* plan)
+// the training set inside the source's rows and bins, and the plan of its launches.  n_taps 1: the receivers' covariance; more: the
+// stacked one (rts_stap.h) -- the span holds n_taps - 1 fewer start rows than rows, the matrix is of order n_taps n_rx
+static int rts_cov_set_check(const RtsCovParams* p, uint32_t rows, uint32_t n_rx, uint32_t nb, const char* who, RtsCovSet* set, RtsCovPlan* plan, uint32_t n_taps = 1u)
 {
     if (p->first_row >= rows || p->n_rows > rows - p->first_row) { rts_set_error("%s: first_row = %u, n_rows = %u: inside the source's %u rows", who, p->first_row, p->n_rows, rows); return RTS_ERR_INVALID; }
     if (p->first_bin >= nb || p->n_bins > nb - p->first_bin) { rts_set_error("%s: first_bin = %u, n_bins = %u: inside the source's %u bins", who, p->first_bin, p->n_bins, nb); return RTS_ERR_INVALID; }
@@ -654,7 +655,9 @@ static int rts_cov_set_check(const RtsCovParams* p, uint32_t rows, uint32_t n_rx
     if (p->skip_n_bins == span) { rts_set_error("%s: skip_n_bins = %u leaves no bin of the span's %u", who, p->skip_n_bins, span); return RTS_ERR_INVALID; }
     set->first_row = p->first_row; set->n_rows = p->n_rows ? p->n_rows : rows - p->first_row; set->first_bin = p->first_bin;
     set->kept = span - p->skip_n_bins; set->skip_n = p->skip_n_bins; set->skip_at = p->skip_n_bins ? p->skip_first_bin - p->first_bin : set->kept;
-    *plan = rts_cov_plan(n_rx, set->n_rows, set->kept);
+    if (set->n_rows < n_taps) { rts_set_error("%s: n_rows = %u rows hold no snapshot of n_taps = %u", who, set->n_rows, n_taps); return RTS_ERR_INVALID; }
+    set->n_rows -= n_taps - 1u;
+    *plan = rts_cov_plan(n_rx * n_taps, set->n_rows, set->kept);
     if (!plan->supported) { rts_set_error("%s: %llu training cells (n_rows * kept bins) in tiles of %u: more than %llu tiles", who, (unsigned long long)plan->K, RTS_ADAPT_TILE, RTS_ADAPT_MAX_TILES); return RTS_ERR_INVALID; }
     return RTS_OK;
 }
@@ -704,7 +707,7 @@ extern "C" int rts_cube_covariance(RtsHandle c, const RtsCovParams* p, void* dev
     double* out; RTS_HIP(c->cube.cov.place(device_out, plan.out_doubles, &out));
     RTS_HIP(c->cube.d_cov_part.reserve(plan.scratch_bytes / sizeof(double)));
     if (!device_out) { c->cube.cov.record(out, plan.out_doubles); c->cube.cov_n = q.n_rx; }
-    return rts_cube_cov_device(c, set, plan, src, rx_stride, c->cube.d_cov_part.p, out);
+    return rts_cube_cov_device(c, set, plan, 1u, src, rx_stride, c->cube.d_cov_part.p, out);
 }
 
 extern "C" int rts_cube_covariance_get(RtsHandle c, double* host_out, uint64_t capacity_doubles)
@@ -786,6 +789,193 @@ extern "C" int rts_cube_mvdr_get(RtsHandle c, double* host_out, uint64_t capacit
     if (status) { rts_set_error("rts_cube_mvdr_get: the solve failed at pivot %u (not finite or not > 0: the covariance plus loading is not positive definite); every weight is NaN", status - 1u); return RTS_ERR_INVALID; }
     RTS_HIP(hipMemcpy(host_out, m.p, sizeof(double) * m.doubles, hipMemcpyDeviceToHost));
     return RTS_OK;
+}
+
+// ------------------------------------------------------------------------------------- space-time adaptive processing
+// (rts_amd.h: RtsStCovParams, RtsStApplyParams; the snapshot, the evaluators and the filter's launch plan are rts_stap.h; the covariance's checks, tree,
+// plan and kernels are the adaptive beamformer's, above, with n_taps; its library-owned result is the handle's `cov`, of order n_taps n_rx)
+static int rts_st_taps_check(const char* who, uint32_t n_taps, uint32_t reserved0, uint32_t n_rx)
+{
+    if (reserved0) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
+    if (n_taps == 0 || n_taps > RTS_ST_MAX_TAPS) { rts_set_error("%s: n_taps = %u (1 .. %u)", who, n_taps, RTS_ST_MAX_TAPS); return RTS_ERR_INVALID; }
+    if ((uint64_t)n_taps * n_rx > RTS_BEAM_MAX_RX) { rts_set_error("%s: n_taps * n_rx = %u * %u: a snapshot of more than %u entries", who, n_taps, n_rx, RTS_BEAM_MAX_RX); return RTS_ERR_INVALID; }
+    return RTS_OK;
+}
+// the record's shared fields as the covariance's record
+static RtsCovParams rts_st_cov_fields(const RtsStCovParams* p)
+{
+    RtsCovParams s = {};
+    s.source = p->source; s.n_rows_in = p->n_rows_in; s.first_row = p->first_row; s.n_rows = p->n_rows; s.first_bin = p->first_bin; s.n_bins = p->n_bins;
+    s.skip_first_bin = p->skip_first_bin; s.skip_n_bins = p->skip_n_bins; s.device_in = p->device_in; s.reserved[0] = p->reserved[0]; s.reserved[1] = p->reserved[1];
+    return s;
+}
+// the device source of a call (the beamformer's three) and its rows
+static int rts_st_source(RtsContext* c, const char* who, uint32_t source, const void* device_in, uint32_t n_rows_in, const double** src, uint32_t* rows)
+{
+    *src = c->cube.p; *rows = c->cube.params.n_pulses;
+    if (source == RTS_BEAM_FROM_MAP) {
+        const RtsCubeProduct& m = c->cube.doppler;
+        if (!m.valid || !m.own.p || m.p != m.own.p) { rts_set_error("%s: RTS_BEAM_FROM_MAP: no library-owned map (rts_cube_doppler with device_out NULL)", who); return RTS_ERR_INVALID; }
+        *src = m.p; *rows = c->cube.doppler_n;
+    } else if (source == RTS_BEAM_FROM_POINTER) {
+        if (!device_in) { rts_set_error("%s: null device_in with RTS_BEAM_FROM_POINTER", who); return RTS_ERR_INVALID; }
+        *src = (const double*)device_in; *rows = n_rows_in;
+    }
+    if ((uintptr_t)*src & 15u) { rts_set_error("%s: %s is not 16-byte aligned", who, source == RTS_BEAM_FROM_POINTER ? "device_in" : "the source's device memory"); return RTS_ERR_INVALID; }
+    return RTS_OK;
+}
+
+extern "C" int rts_st_covariance_eval(const RtsCubeParams* q, const double* in, uint32_t n_rows_in, const RtsStCovParams* p, double* out)
+{
+    const char* who = "rts_st_covariance_eval";
+    if (!q || q->n_rx == 0 || q->n_bins == 0) { rts_set_error("%s: bad cube parameters", who); return RTS_ERR_INVALID; }
+    if (n_rows_in == 0) { rts_set_error("%s: n_rows_in = 0", who); return RTS_ERR_INVALID; }
+    if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
+    const RtsCovParams s = rts_st_cov_fields(p);
+    int rc = rts_cov_check(&s, q->n_rx, who); if (rc != RTS_OK) return rc;
+    rc = rts_st_taps_check(who, p->n_taps, p->reserved0, q->n_rx); if (rc != RTS_OK) return rc;
+    if (p->source == RTS_BEAM_FROM_POINTER && p->n_rows_in != n_rows_in) { rts_set_error("%s: the parameters' n_rows_in = %u, the array's %u", who, p->n_rows_in, n_rows_in); return RTS_ERR_INVALID; }
+    RtsCovSet set; RtsCovPlan plan;
+    rc = rts_cov_set_check(&s, n_rows_in, q->n_rx, q->n_bins, who, &set, &plan, p->n_taps); if (rc != RTS_OK) return rc;
+    if (!in || !out) { rts_set_error("%s: null input or output array", who); return RTS_ERR_INVALID; }
+    rts_st_cov_eval_host(q->n_rx, p->n_taps, q->n_bins, in, n_rows_in, set, plan, out);
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_st_covariance(RtsHandle c, const RtsStCovParams* p, void* device_out)
+{
+    const char* who = "rts_cube_st_covariance";
+    CHECK_HANDLE(c);
+    NEED_CUBE(c, who, "no cube (call rts_cube_attach first)");
+    if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
+    const RtsCubeParams& q = c->cube.params;
+    const RtsCovParams s = rts_st_cov_fields(p);
+    int rc = rts_cov_check(&s, q.n_rx, who); if (rc != RTS_OK) return rc;
+    rc = rts_st_taps_check(who, p->n_taps, p->reserved0, q.n_rx); if (rc != RTS_OK) return rc;
+    const double* src; uint32_t rows;
+    rc = rts_st_source(c, who, p->source, p->device_in, p->n_rows_in, &src, &rows); if (rc != RTS_OK) return rc;
+    RtsCovSet set; RtsCovPlan plan;
+    rc = rts_cov_set_check(&s, rows, q.n_rx, q.n_bins, who, &set, &plan, p->n_taps); if (rc != RTS_OK) return rc;
+    if ((uintptr_t)device_out & 15u) { rts_set_error("%s: device_out is not 16-byte aligned", who); return RTS_ERR_INVALID; }
+    const uint64_t rx_stride = (uint64_t)rows * q.n_bins;
+    if (device_out) {       // the output's bytes against each receiver's span of the input: the first snapshot's first cell .. the last one's last tap
+        const uintptr_t o0 = (uintptr_t)device_out, o1 = o0 + sizeof(double) * plan.out_doubles;
+        const uint64_t e0 = rts_cov_cell_index(set, q.n_bins, 0), e1 = rts_cov_cell_index(set, q.n_bins, plan.K - 1u) + (uint64_t)(p->n_taps - 1u) * q.n_bins + 1u;
+        for (uint32_t r = 0; r < q.n_rx; r++) {
+            const uintptr_t i0 = (uintptr_t)(src + 2 * ((size_t)r * rx_stride + e0)), i1 = (uintptr_t)(src + 2 * ((size_t)r * rx_stride + e1));
+            if (o0 < i1 && i0 < o1) { rts_set_error("%s: device_out overlaps the input the call reads (receiver %u)", who, r); return RTS_ERR_INVALID; }
+        }
+    }
+    CHECK_CLOSED(c);
+    double* out; RTS_HIP(c->cube.cov.place(device_out, plan.out_doubles, &out));
+    RTS_HIP(c->cube.d_cov_part.reserve(plan.scratch_bytes / sizeof(double)));
+    if (!device_out) { c->cube.cov.record(out, plan.out_doubles); c->cube.cov_n = q.n_rx * p->n_taps; }
+    return rts_cube_cov_device(c, set, plan, p->n_taps, src, rx_stride, c->cube.d_cov_part.p, out);
+}
+
+// the filter's record, limits and weight table: what needs no source
+static int rts_st_apply_check(const RtsStApplyParams* p, uint32_t n_rx, const char* who)
+{
+    if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
+    if (p->reserved[0] || p->reserved[1]) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
+    if (p->source > RTS_BEAM_FROM_POINTER) { rts_set_error("%s: unknown source %u (RTS_BEAM_FROM_CUBE, _MAP, _POINTER)", who, p->source); return RTS_ERR_INVALID; }
+    if (p->flags & ~RTS_BEAM_POWER) { rts_set_error("%s: unknown flags 0x%x (RTS_BEAM_POWER)", who, p->flags); return RTS_ERR_INVALID; }
+    { int rc = rts_st_taps_check(who, p->n_taps, p->reserved0, n_rx); if (rc != RTS_OK) return rc; }
+    const uint32_t D = p->n_taps * n_rx;
+    if (p->n_filters == 0 || p->n_filters > RTS_BEAM_MAX_BEAMS) { rts_set_error("%s: n_filters = %u (1 .. %u)", who, p->n_filters, RTS_BEAM_MAX_BEAMS); return RTS_ERR_INVALID; }
+    if ((uint64_t)p->n_filters * D > RTS_BEAM_MAX_WEIGHTS) { rts_set_error("%s: n_filters * n_taps * n_rx = %u * %u weights: more than %u (a weight table of rts_cube_beamform)", who, p->n_filters, D, RTS_BEAM_MAX_WEIGHTS); return RTS_ERR_INVALID; }
+    if (!p->weights) { rts_set_error("%s: null weights", who); return RTS_ERR_INVALID; }
+    for (uint32_t i = 0; i < 2 * p->n_filters * D; i++) if (!std::isfinite(p->weights[i])) { rts_set_error("%s: weights[%u][%u] is not finite", who, i / 2 / D, i / 2 % D); return RTS_ERR_INVALID; }
+    if (p->source != RTS_BEAM_FROM_POINTER && p->n_rows_in != 0) { rts_set_error("%s: n_rows_in = %u without RTS_BEAM_FROM_POINTER", who, p->n_rows_in); return RTS_ERR_INVALID; }
+    if (p->source != RTS_BEAM_FROM_POINTER && p->device_in) { rts_set_error("%s: device_in without RTS_BEAM_FROM_POINTER", who); return RTS_ERR_INVALID; }
+    if (p->source == RTS_BEAM_FROM_POINTER && p->n_rows_in == 0) { rts_set_error("%s: n_rows_in = 0 with RTS_BEAM_FROM_POINTER", who); return RTS_ERR_INVALID; }
+    return RTS_OK;
+}
+// the span inside the source's rows, and the plan of its launch
+static int rts_st_apply_rows_check(const RtsStApplyParams* p, uint32_t rows, uint32_t n_rx, uint32_t n_bins, const char* who, RtsStApplyPlan* plan)
+{
+    if (p->first_row >= rows || p->n_rows > rows - p->first_row) { rts_set_error("%s: first_row = %u, n_rows = %u: inside the source's %u rows", who, p->first_row, p->n_rows, rows); return RTS_ERR_INVALID; }
+    const uint32_t n_rows = p->n_rows ? p->n_rows : rows - p->first_row;
+    if (n_rows < p->n_taps) { rts_set_error("%s: n_rows = %u rows hold no snapshot of n_taps = %u", who, n_rows, p->n_taps); return RTS_ERR_INVALID; }
+    *plan = rts_st_apply_plan(n_rx, p->n_taps, p->n_filters, n_rows, n_bins, p->flags);
+    if (!plan->supported) { rts_set_error("%s: n_rows = %u, n_bins = %u, n_filters = %u: more than %u workgroups (the launch grid)", who, n_rows, n_bins, p->n_filters, RTS_ST_MAX_GRID_X); return RTS_ERR_INVALID; }
+    return RTS_OK;
+}
+
+extern "C" int rts_st_apply_eval(const RtsCubeParams* q, const double* in, uint32_t n_rows_in, const RtsStApplyParams* p, double* out)
+{
+    const char* who = "rts_st_apply_eval";
+    if (!q || q->n_rx == 0 || q->n_bins == 0) { rts_set_error("%s: bad cube parameters", who); return RTS_ERR_INVALID; }
+    if (n_rows_in == 0) { rts_set_error("%s: n_rows_in = 0", who); return RTS_ERR_INVALID; }
+    int rc = rts_st_apply_check(p, q->n_rx, who); if (rc != RTS_OK) return rc;
+    if (p->source == RTS_BEAM_FROM_POINTER && p->n_rows_in != n_rows_in) { rts_set_error("%s: the parameters' n_rows_in = %u, the array's %u", who, p->n_rows_in, n_rows_in); return RTS_ERR_INVALID; }
+    RtsStApplyPlan plan;
+    rc = rts_st_apply_rows_check(p, n_rows_in, q->n_rx, q->n_bins, who, &plan); if (rc != RTS_OK) return rc;
+    if (!in || !out) { rts_set_error("%s: null input or output array", who); return RTS_ERR_INVALID; }
+    rts_st_apply_eval_host(q->n_rx, p->n_taps, q->n_bins, in, n_rows_in, p->first_row, plan.out_rows + p->n_taps - 1u, p->n_filters, p->weights, p->flags, out);
+    return RTS_OK;
+}
+
+extern "C" int rts_st_steering_make(const double* spatial, uint32_t n_rx, uint32_t n_beams, const double* doppler, uint32_t n_doppler, uint32_t n_taps, const double* tap_taper, double* out)
+{
+    const char* who = "rts_st_steering_make";
+    if (!spatial || !doppler || !out) { rts_set_error("%s: null spatial, doppler or output array", who); return RTS_ERR_INVALID; }
+    if (n_rx == 0 || n_beams == 0 || n_doppler == 0) { rts_set_error("%s: n_rx = %u, n_beams = %u, n_doppler = %u (each >= 1)", who, n_rx, n_beams, n_doppler); return RTS_ERR_INVALID; }
+    { int rc = rts_st_taps_check(who, n_taps, 0u, n_rx); if (rc != RTS_OK) return rc; }
+    for (size_t i = 0; i < 2 * (size_t)n_beams * n_rx; i++) if (!std::isfinite(spatial[i])) { rts_set_error("%s: spatial[%zu][%zu] is not finite", who, i / 2 / n_rx, i / 2 % n_rx); return RTS_ERR_INVALID; }
+    for (uint32_t k = 0; k < n_doppler; k++) if (!std::isfinite(doppler[k])) { rts_set_error("%s: doppler[%u] is not finite", who, k); return RTS_ERR_INVALID; }
+    if (tap_taper) for (uint32_t m = 0; m < n_taps; m++) if (!std::isfinite(tap_taper[m])) { rts_set_error("%s: tap_taper[%u] is not finite", who, m); return RTS_ERR_INVALID; }
+    const uint32_t D = n_taps * n_rx;
+    for (uint32_t b = 0; b < n_beams; b++) for (uint32_t k = 0; k < n_doppler; k++) for (uint32_t m = 0; m < n_taps; m++) {
+        double s, cs; rts_beat_sincos_turns(doppler[k] * (double)m, &s, &cs);      // (rts_steering_make's cosine and sine)
+        const double tr = tap_taper ? tap_taper[m] * cs : cs, ti = tap_taper ? tap_taper[m] * s : s;
+        for (uint32_t r = 0; r < n_rx; r++) {
+            const double* a = spatial + 2 * ((size_t)b * n_rx + r);
+            double* o = out + 2 * (((size_t)b * n_doppler + k) * D + (size_t)m * n_rx + r);
+            rts_st_steer_mul(tr, ti, a[0], a[1], &o[0], &o[1]);
+        }
+    }
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_st_apply(RtsHandle c, const RtsStApplyParams* p, void* device_out)
+{
+    const char* who = "rts_cube_st_apply";
+    CHECK_HANDLE(c);
+    NEED_CUBE(c, who, "no cube (call rts_cube_attach first)");
+    const RtsCubeParams& q = c->cube.params;
+    int rc = rts_st_apply_check(p, q.n_rx, who); if (rc != RTS_OK) return rc;
+    const double* src; uint32_t rows;
+    rc = rts_st_source(c, who, p->source, p->device_in, p->n_rows_in, &src, &rows); if (rc != RTS_OK) return rc;
+    RtsStApplyPlan plan;
+    rc = rts_st_apply_rows_check(p, rows, q.n_rx, q.n_bins, who, &plan); if (rc != RTS_OK) return rc;
+    if ((uintptr_t)device_out & 15u) { rts_set_error("%s: device_out is not 16-byte aligned", who); return RTS_ERR_INVALID; }
+    const uint64_t rx_stride = (uint64_t)rows * q.n_bins;
+    const double* in = src + 2 * (size_t)p->first_row * q.n_bins;
+    if (device_out) {       // the filter is not in place: the output's bytes against each receiver's span of the input
+        const uintptr_t o0 = (uintptr_t)device_out, o1 = o0 + sizeof(double) * plan.out_doubles;
+        const uint64_t span = (uint64_t)(plan.out_rows + p->n_taps - 1u) * q.n_bins;
+        for (uint32_t r = 0; r < q.n_rx; r++) {
+            const uintptr_t i0 = (uintptr_t)(in + 2 * (size_t)r * rx_stride), i1 = i0 + 16u * (uintptr_t)span;
+            if (o0 < i1 && i0 < o1) { rts_set_error("%s: device_out overlaps the input the call reads (receiver %u): the filter is not in place", who, r); return RTS_ERR_INVALID; }
+        }
+    }
+    CHECK_CLOSED(c);
+    double* out; RTS_HIP(c->cube.st.place(device_out, plan.out_doubles, &out));
+    // the weights -> pinned staging -> the device, on the stream (n_filters D <= RTS_BEAM_MAX_WEIGHTS: one size for every call)
+    const size_t nw = 2 * (size_t)p->n_filters * plan.D;
+    double* w = nullptr;
+    RTS_HIP(c->cube.st_w.begin(2u * RTS_BEAM_MAX_WEIGHTS, 2u * RTS_BEAM_MAX_WEIGHTS, 2u * RTS_BEAM_MAX_WEIGHTS, &w));
+    memcpy(w, p->weights, sizeof(double) * nw);
+    RTS_HIP(c->cube.st_w.send(nw, c->stream));
+    if (!device_out) c->cube.st.record(out, plan.out_doubles);
+    return rts_cube_st_apply_device(c, *p, plan, in, rx_stride, c->cube.st_w.dev.p, out);
+}
+
+extern "C" int rts_cube_st_get(RtsHandle c, double* host_out, uint64_t capacity_doubles)
+{
+    CHECK_HANDLE(c);
+    return rts_cube_copy_out(c, "rts_cube_st_get", "no library-owned filter output (rts_cube_st_apply with device_out NULL; the output ends at rts_cube_attach) / null output", c->cube.st.valid, c->cube.st.p, c->cube.st.doubles, host_out, capacity_doubles);
 }
 
 // ------------------------------------------------------------------------------------- backprojection imaging

@@ -17,6 +17,7 @@
 #include "rts_beat.h"             // the tree of the dechirped beat render, the range transform's evaluator and the host-only plans of their launches
 #include "rts_beam.h"             // the beamformer's term, sum and streaming peak, its evaluator and the host-only plan of its launch
 #include "rts_adapt.h"            // adaptive beamforming: the covariance's term and partition, the weight solve, their evaluators and the host-only plans of their launches
+#include "rts_stap.h"             // space-time adaptive processing: the stacked snapshot, its covariance's and filter's evaluators, the host-only plan of the filter's launch
 #include "rts_cfar_os.h"          // CFAR: what every detector shares (rts_cfar.h: window, training count, local maximum, refinement, record); OS: rank rule, alphas, the host evaluator
 #include "rts_owned.h"            // DevBuf, PinBuf, StagedUpload: device and pinned host memory that frees itself
 #include "rts_launch_plan.h"      // RTS_BLOCK, RTS_WTILE, RTS_COOP_GROUP, RTS_STACK_OVF and the host arithmetic of a launch
@@ -329,9 +330,13 @@ struct RtsCubeState {
     RtsCubeProduct cov; uint32_t cov_n = 0; DevBuf<double> d_cov_part;
     RtsCubeProduct mvdr;
     StagedUpload<double> mvdr_s; DevBuf<uint32_t> d_mvdr_status;
+    // space-time adaptive processing (rts_cube_st_covariance: `cov` above, of order n_taps n_rx; rts_cube_st_apply, rts_stap.hip): the
+    // filter's output, for rts_cube_st_get; the call's weight table goes through a staged upload
+    RtsCubeProduct st;
+    StagedUpload<double> st_w;
     // every product belongs to the cube it was made from: the Doppler map (which rts_cube_detect may take), the detection list, the image
-    // the spectrogram, the range transform, the beams, the covariance and the adaptive weights end when another cube is attached
-    void end_products() { doppler.valid = false; det_valid = false; image.valid = false; stft.valid = false; range.valid = false; beam.valid = false; cov.valid = false; mvdr.valid = false; }
+    // the spectrogram, the range transform, the beams, the covariance, the adaptive weights and the space-time filter's output end when another cube is attached
+    void end_products() { doppler.valid = false; det_valid = false; image.valid = false; stft.valid = false; range.valid = false; beam.valid = false; cov.valid = false; mvdr.valid = false; st.valid = false; }
 };
 
 // What a pulse leaves for its accessors (rts_results_api.hip; the finalisers, the aggregation and the end-of-pulse chains of rts_api.hip; the
@@ -470,8 +475,9 @@ int rts_cube_stft_device(RtsContext* c, const RtsStftParams& p, const RtsStftPla
 int rts_cube_beat_device(RtsContext* c, uint32_t pulse_index, const RtsBeatParams& p, const RtsBeatPlan& plan, double cspeed, double carrier, int64_t base);      // rts_beat.hip
 int rts_cube_range_device(RtsContext* c, const RtsRangeParams& p, const RtsRangePlan& plan, const double* window, double* out);
 int rts_cube_beam_device(RtsContext* c, const RtsBeamParams& p, const RtsBeamPlan& plan, const double* in, uint64_t rx_stride, const double* weights, void* out);      // rts_beam.hip
-int rts_cube_cov_device(RtsContext* c, const RtsCovSet& set, const RtsCovPlan& plan, const double* in, uint64_t rx_stride, double* part, double* out);      // rts_adapt.hip
+int rts_cube_cov_device(RtsContext* c, const RtsCovSet& set, const RtsCovPlan& plan, uint32_t n_taps, const double* in, uint64_t rx_stride, double* part, double* out);      // rts_adapt.hip
 int rts_cube_mvdr_device(RtsContext* c, const RtsMvdrPlan& plan, uint32_t n_rx, uint32_t n_beams, double loading, const double* cov, const double* steering, uint32_t* status, double* out);
+int rts_cube_st_apply_device(RtsContext* c, const RtsStApplyParams& p, const RtsStApplyPlan& plan, const double* in, uint64_t rx_stride, const double* weights, void* out);      // rts_stap.hip
 int rts_cube_backproject_device(RtsContext* c, const RtsImageParams& p, const RtsImagePlan& plan, const double* geo, double* out);      // rts_image.hip
 int rts_post_finalise(RtsContext* c, const double* rcs_host, double wl, double gt, double gr, double carrier, double cspeed);
 int rts_pattern_pulse_upload(RtsContext* c, const RtsSpecParams& q, RtsPatArgs* out);      // the pulse's receiver rows -> the device, on c->stream
