@@ -978,6 +978,112 @@ int rts_st_apply_eval(const RtsCubeParams* q, const double* in, uint32_t n_rows_
 int rts_st_steering_make(const double* spatial, uint32_t n_rx, uint32_t n_beams, const double* doppler, uint32_t n_doppler,
                          uint32_t n_taps, const double* tap_taper, double* out);                                                  /* pure host */
 
+/* ---------------------------------------------------------------- direction finding: Hermitian eigensolver, angular spectrum scan
+ * The beamformers above answer "what arrives from the directions I steer at"; the eigendecomposition of the covariance answers "how
+ * many sources are there and where": MUSIC, Capon's and Bartlett's spectra, the source count (AIC / MDL), and whatever else stands
+ * on eigenpairs (eigencanceler weights, principal components).  The arithmetic is rts_amd/csrc/rts_doa.h, shared by the kernels
+ * (rts_doa.hip) and the host evaluators; + - * /, sqrt and comparisons only (the library builds with -ffp-contract=off): device and
+ * evaluators agree BIT FOR BIT.  No atomics, plain stores only.
+ *
+ * rts_cube_eig.  cov: device_cov (caller-owned device memory [n][n] complex128, 16-byte aligned, n the record's) or, with device_cov
+ *   NULL, the handle's last library-owned covariance -- rts_cube_covariance's of order n_rx or rts_cube_st_covariance's of order D
+ *   (the record's n is then 0 or that order).  n <= RTS_BEAM_MAX_RX.  Only the lower triangle is read, and of the diagonal only the
+ *   real part.  One-sided (Hestenes) Jacobi on X = A, V = I, both [n][n]:
+ *     X[i][j] = A[i][j] (i > j), X[i][i] = (re A[i][i], +0.0), X[j][i] = (re, -im) of A[i][j].
+ *     A sweep: m2 = the largest of norm2(col) = sum over ascending i of (re re + im im) of X[i][col] (the i = 0 term the start value),
+ *     by `if (v > m2) m2 = v` over ascending col from norm2(0); floor2 = 2^-104 m2.  Then the rounds r = 0 .. M - 2 (M = n rounded up to
+ *     even) of M / 2 disjoint column pairs: slot 0 pairs M - 1 with r, slot k > 0 pairs (r + k) % (M - 1) with
+ *     (r + M - 1 - k) % (M - 1); p the smaller, q the larger; q >= n is the bye of an odd n.  A function of n alone.  Per pair:
+ *       alpha = norm2(p);  beta = norm2(q);  gamma = sum over ascending i of conj(x_ip) x_iq = (pr qr + pi qi, pr qi - pi qr), the
+ *       i = 0 term the start value;  g2 = gr gr + gi gi.
+ *       No rotation when g2 <= 2^-100 (alpha beta), or alpha <= floor2, or beta <= floor2 (a column of a null space holds only
+ *       rounding noise: it would pass the relative test for ever).  Otherwise
+ *       g = sqrt(g2);  e = (gr / g, gi / g);  zeta = (beta - alpha) / (2.0 g);  d = |zeta| + sqrt(1.0 + zeta zeta);
+ *       t = 1.0 / d, or -1.0 / d when zeta < 0;  c = 1.0 / sqrt(1.0 + t t);  s = c t;  sr = s e.re;  si = s e.im;  and every row i of X,
+ *       then of V, with a = [i][p], b = [i][q]:
+ *         a' = (c ar - (sr br + si bi), c ai - (sr bi - si br));   b' = ((sr ar - si ai) + c br, (sr ai + si ar) + c bi).
+ *     The solver runs sweeps until one rotates nothing (status 0); after RTS_EIG_MAX_SWEEPS sweeps that each rotated it gives up
+ *     (status 1).  An entry of the lower triangle outside [-DBL_MAX, DBL_MAX] (NaN included), checked before anything: status 2.
+ *     lambda(col) = sum over ascending i of (vr xr + vi xi), v = V[i][col], x = X[i][col], the i = 0 term the start value.
+ *     Order: descending lambda, ties by ascending column (rank(col) = the count of j with lambda(j) > lambda(col), or equal and
+ *     j < col): fixed, never an unstable sort.  No phase normalisation.
+ *   Output: device_values f64 [n] and device_vectors complex128 [n][n], ROW k = eigenvector k: a weight row of rts_cube_beamform.
+ *     Both caller-owned (8- and 16-byte aligned) or both NULL: library-owned, THE HANDLE'S LAST LIBRARY-OWNED EIGENPAIRS.  With a
+ *     status other than 0 EVERY output is NaN and a status word of the handle on the device records it; rts_cube_eig_get then returns
+ *     RTS_ERR_INVALID naming the cause (the handle stays usable).  rts_cube_eig_get copies whichever of values_out (n doubles) and
+ *     vectors_out (2 n n doubles) is not NULL.
+ *   A is meant positive semidefinite (a covariance): V diagonalises A^2, so eigenvalues of equal magnitude and opposite sign would
+ *   share a subspace.
+ * rts_cube_doa_scan.  The angular spectrum of n_dirs directions through m vectors v_k [n] and weights g_k:
+ *     y_k = sum over ascending rx of conj(v_k[rx]) a[rx] (rts_cube_beamform's term and sum: rx = 0 the start value);
+ *     p_k = y.re y.re + y.im y.im;  q = g_0 p_0, then q = q + g_k p_k for ascending k;  out = q, or with RTS_DOA_INVERSE 1.0 / q: the
+ *     IEEE quotient with no clamp, so q = 0 gives +inf.
+ *   device_steering: caller-owned device memory, complex128 ELEMENT-MAJOR [n][n_dirs] (the cube's layout with the directions in the
+ *   bins' place; rts_steering_make's rows transposed), 16-byte aligned.  The vectors are rows first_vector .. first_vector + m - 1 of
+ *   device_vectors (complex128 [n][n], 16-byte aligned, n the record's) or, with device_vectors NULL, of the handle's last
+ *   library-owned eigenvectors (n 0 or their order): MUSIC's noise subspace is a row range of the sorted table, nothing is copied.
+ *   g: host [m], finite, copied by the call.  Output f64 [n_dirs], 8-byte aligned or NULL: library-owned, for rts_cube_doa_get.
+ *   With m = 1 and g = 1 the output is rts_cube_beamform's RTS_BEAM_POWER of the table as a one-row cube, bit for bit.
+ * rts_doa_weights: pure host.  (first, m, g[m], flags) of the scan for a spectrum, from the eigenvalues in the solver's order:
+ *     RTS_DOA_BARTLETT  first 0, m n, g_k = lambda_k,                 flags 0                  a^H R a
+ *     RTS_DOA_CAPON     first 0, m n, g_k = 1.0 / (lambda_k + loading), RTS_DOA_INVERSE        1 / (a^H (R + loading I)^-1 a)
+ *     RTS_DOA_MUSIC     first n_sources, m n - n_sources, g_k = 1.0,  RTS_DOA_INVERSE          1 / |noise subspace^H a|^2
+ *   g has room for n values.  Refused: NULL pointers; n 0 or above RTS_BEAM_MAX_RX; an unknown method; a loading that is negative or
+ *   not finite; a non-finite eigenvalue; MUSIC with n_sources >= n; Capon with a lambda_k + loading not > 0.  n_sources is looked
+ *   at by MUSIC only, loading is used by Capon only.
+ * rts_source_count: pure host, libm's log, no device twin and no bit contract.  Eigenvalues in descending order, K snapshots; with
+ *   the n - k smallest eigenvalues L(k) = K (n - k) (log(their arithmetic mean) - the mean of their logs),
+ *     RTS_DOA_AIC: 2 L(k) + 2 k (2 n - k);  RTS_DOA_MDL: L(k) + 0.5 k (2 n - k) log K;  the first k in 0 .. n - 1 of the smallest value.
+ *   Refused: NULL pointers; n 0 or above RTS_BEAM_MAX_RX; K 0; an unknown criterion; an eigenvalue that is not finite, not > 0
+ *   (every one enters a logarithm: a rank-deficient covariance has no estimate) or larger than the one before it.
+ * device outputs, the stream: as rts_cube_mvdr.  The calls are enqueued on the handle's stream and never wait for the device's
+ *   earlier work (rts_cube_doa_scan: only for the copy of the PREVIOUS call's g out of the handle's pinned staging block).  The
+ *   library-owned eigenpairs and spectrum end at rts_cube_attach; the getters synchronise and copy (RTS_ERR_INVALID with none,
+ *   RTS_ERR_CAPACITY when a capacity is too small).  A caller-owned output is not recorded.
+ * RTS_ERR_INVALID, the message naming the field: no cube attached; NULL p; nonzero reserved fields; neither device_cov nor a
+ *   library-owned covariance; a misaligned device_cov; an n that is 0 or above RTS_BEAM_MAX_RX with device_cov, or differs from the
+ *   library-owned covariance's; one of device_values / device_vectors NULL and the other not; a misaligned output; outputs that overlap
+ *   each other or the bytes the call reads.  rts_cube_doa_scan: NULL or misaligned device_steering; n_dirs 0 or more than 2^31 - 1
+ *   workgroups of 256 directions; m 0; first_vector + m above n; unknown flags; NULL g or a non-finite g_k; neither device_vectors nor
+ *   library-owned eigenvectors; a misaligned device_vectors; an n that is 0 or above RTS_BEAM_MAX_RX with device_vectors, or differs
+ *   from the library-owned eigenvectors'; a misaligned device_out; a device_out that overlaps the steering table or the vectors.  A
+ *   refused call leaves the handle's previous products as they were.
+ * rts_eig_eval / rts_doa_scan_eval: pure host, no device: the same rts_doa.h functions.  rts_eig_eval reads cov [n][n] as the kernel
+ *   does; sweeps_out (or NULL): the sweeps that rotated (the identity: 0).  Status 1 or 2 returns RTS_ERR_INVALID naming the status.
+ *   rts_doa_scan_eval: vectors [m][n] (the rows the scan uses), g [m], steering element-major [n][n_dirs].  A refused or failed
+ *   call leaves the outputs untouched. */
+#define RTS_EIG_MAX_SWEEPS   30u    /* sweeps that rotate before rts_cube_eig gives up (status 1)                       */
+#define RTS_DOA_INVERSE      1u     /* out = 1.0 / q                                                                    */
+#define RTS_DOA_BARTLETT     0u
+#define RTS_DOA_CAPON        1u
+#define RTS_DOA_MUSIC        2u
+#define RTS_DOA_AIC          0u
+#define RTS_DOA_MDL          1u
+typedef struct RtsEigParams {
+    uint32_t n, reserved0;           /* n: with device_cov; 0 or the covariance's order otherwise; reserved0: 0         */
+    const void* device_cov;          /* complex128 [n][n], 16-byte aligned; NULL: the last library-owned covariance    */
+    uint64_t reserved[2];            /* 0 */
+} RtsEigParams;
+typedef struct RtsDoaScanParams {
+    uint32_t n, first_vector;        /* n: with device_vectors; 0 or the eigenvectors' order otherwise                 */
+    uint32_t m, flags;               /* rows first_vector .. first_vector + m - 1; RTS_DOA_INVERSE                     */
+    uint64_t n_dirs;
+    const double* g;                 /* host [m], finite                                                            */
+    const void* device_steering;     /* complex128 [n][n_dirs], 16-byte aligned                                     */
+    const void* device_vectors;      /* complex128 [n][n], 16-byte aligned; NULL: the last library-owned eigenvectors */
+    uint64_t reserved[2];            /* 0 */
+} RtsDoaScanParams;
+int rts_cube_eig(RtsHandle h, const RtsEigParams* p, void* device_values, void* device_vectors);     /* f64 [n], complex128 [n][n] */
+int rts_cube_eig_get(RtsHandle h, double* values_out, double* vectors_out, uint64_t capacity_values, uint64_t capacity_vector_doubles);
+int rts_eig_eval(const double* cov, uint32_t n, double* values_out, double* vectors_out, uint32_t* sweeps_out);              /* pure host */
+int rts_cube_doa_scan(RtsHandle h, const RtsDoaScanParams* p, void* device_out);                      /* f64 [n_dirs] */
+int rts_cube_doa_get(RtsHandle h, double* host_out, uint64_t capacity_doubles);
+int rts_doa_scan_eval(const double* vectors, const double* g, uint32_t n, uint32_t m, const double* steering, uint64_t n_dirs,
+                      uint32_t flags, double* out);                                                                            /* pure host */
+int rts_doa_weights(uint32_t method, const double* values, uint32_t n, uint32_t n_sources, double loading,
+                    uint32_t* first, uint32_t* m, double* g, uint32_t* flags);                                                 /* pure host */
+int rts_source_count(const double* values, uint32_t n, uint64_t K, uint32_t criterion, uint32_t* n_sources);                  /* pure host */
+
 /* ---------------------------------------------------------------- backprojection imaging (SAR / ISAR) of the return cube
  * A derived product like the cube itself: time-domain backprojection of a coherent interval onto a planar
  * pixel grid -- exact for any track, any bistatic geometry and any target motion, where the slow-time DFT focuses only while a

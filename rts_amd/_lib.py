@@ -227,6 +227,24 @@ class RtsStApplyParams(C.Structure):
 assert C.sizeof(RtsStCovParams) == 64 and C.sizeof(RtsStApplyParams) == 64
 
 
+RTS_EIG_MAX_SWEEPS = 30
+RTS_DOA_INVERSE = 1
+RTS_DOA_BARTLETT, RTS_DOA_CAPON, RTS_DOA_MUSIC = 0, 1, 2
+RTS_DOA_AIC, RTS_DOA_MDL = 0, 1
+
+
+class RtsEigParams(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("reserved0", C.c_uint32), ("device_cov", C.c_void_p), ("reserved", C.c_uint64 * 2)]
+
+
+class RtsDoaScanParams(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("first_vector", C.c_uint32), ("m", C.c_uint32), ("flags", C.c_uint32), ("n_dirs", C.c_uint64),
+                ("g", C.c_void_p), ("device_steering", C.c_void_p), ("device_vectors", C.c_void_p), ("reserved", C.c_uint64 * 2)]
+
+
+assert C.sizeof(RtsEigParams) == 32 and C.sizeof(RtsDoaScanParams) == 64
+
+
 class RtsSceneInfo(C.Structure):
     _fields_ = [("n_targets", C.c_uint32), ("n_prims", C.c_uint32), ("n_nodes", C.c_uint32), ("n_leaves", C.c_uint32),
                 ("handles_sharing", C.c_uint32), ("builder", C.c_uint32), ("build_ms", C.c_double),
@@ -319,7 +337,8 @@ EXPORTS = ["rts_create", "rts_destroy", "rts_last_error", "rts_device_count", "r
            "rts_cube_render_beat", "rts_beat_eval", "rts_cube_range_transform", "rts_cube_range_get", "rts_range_eval",
            "rts_cube_beamform", "rts_cube_beam_get", "rts_beamform_eval", "rts_steering_make",
            "rts_cube_covariance", "rts_cube_covariance_get", "rts_covariance_eval", "rts_cube_mvdr", "rts_cube_mvdr_get", "rts_mvdr_eval",
-           "rts_cube_st_covariance", "rts_st_covariance_eval", "rts_cube_st_apply", "rts_cube_st_get", "rts_st_apply_eval", "rts_st_steering_make"]
+           "rts_cube_st_covariance", "rts_st_covariance_eval", "rts_cube_st_apply", "rts_cube_st_get", "rts_st_apply_eval", "rts_st_steering_make",
+           "rts_cube_eig", "rts_cube_eig_get", "rts_eig_eval", "rts_cube_doa_scan", "rts_cube_doa_get", "rts_doa_scan_eval", "rts_doa_weights", "rts_source_count"]
 
 
 def lib():
@@ -423,6 +442,14 @@ def lib():
         "rts_cube_st_get": [vp, vp, u64],
         "rts_st_apply_eval": [C.POINTER(RtsCubeParams), vp, u32, C.POINTER(RtsStApplyParams), vp],
         "rts_st_steering_make": [vp, u32, u32, vp, u32, u32, vp, vp],
+        "rts_cube_eig": [vp, C.POINTER(RtsEigParams), vp, vp],
+        "rts_cube_eig_get": [vp, vp, vp, u64, u64],
+        "rts_eig_eval": [vp, u32, vp, vp, C.POINTER(u32)],
+        "rts_cube_doa_scan": [vp, C.POINTER(RtsDoaScanParams), vp],
+        "rts_cube_doa_get": [vp, vp, u64],
+        "rts_doa_scan_eval": [vp, vp, u32, u32, vp, u64, u32, vp],
+        "rts_doa_weights": [u32, vp, u32, u32, C.c_double, C.POINTER(u32), C.POINTER(u32), vp, C.POINTER(u32)],
+        "rts_source_count": [vp, u32, u64, u32, C.POINTER(u32)],
     }
     for name, args in sig.items():
         fn = getattr(L, name, None)

@@ -545,6 +545,63 @@ def mvdr_eval(cov, steering, loading=0.0):
     return out
 
 
+def eig_eval(cov, sweeps=False):
+    """rts_eig_eval (pure host): the eigenpairs of a Hermitian matrix complex [n][n] (its lower triangle and the real part of its
+    diagonal are read) by one-sided Jacobi: (eigenvalues float64 [n] in descending order, eigenvectors complex [n][n], ROW k the
+    eigenvector of value k: a weight row of beamform_eval); with sweeps also the number of sweeps that rotated"""
+    cov = np.ascontiguousarray(np.asarray(cov, np.complex128))
+    if cov.ndim != 2 or cov.shape[0] != cov.shape[1]:
+        raise ValueError("eig_eval: a matrix of shape %s ([n][n])" % (cov.shape,))
+    n = cov.shape[0]
+    values = np.zeros(n, np.float64); vectors = np.zeros((n, n), np.complex128); ns = C.c_uint32(0)
+    check(L.lib().rts_eig_eval(ptr(cov.view(np.float64)), n, ptr(values), ptr(vectors.view(np.float64)), C.byref(ns)))
+    return (values, vectors, ns.value) if sweeps else (values, vectors)
+
+
+def _steering_table(steering):
+    """a host steering table [n_dirs][n] (steering()'s rows) as the scan reads it: element-major complex [n][n_dirs]"""
+    a = np.asarray(steering, np.complex128)
+    if a.ndim != 2:
+        raise ValueError("doa: a steering table of shape %s ([n_dirs][n])" % (a.shape,))
+    return np.ascontiguousarray(a.T)
+
+
+def doa_scan_eval(vectors, g, steering, inverse=False):
+    """rts_doa_scan_eval (pure host): q[dir] = sum_k g[k] |sum_rx conj(v_k[rx]) a_dir[rx]|^2 of the vectors complex [m][n], the weights
+    g [m] and the host steering table complex [n_dirs][n] (steering()'s rows); 1 / q with inverse (q = 0 gives +inf): float64 [n_dirs]"""
+    v = np.ascontiguousarray(np.asarray(vectors, np.complex128)); g = np.ascontiguousarray(np.asarray(g, np.float64).ravel())
+    a = _steering_table(steering)
+    if v.ndim != 2 or v.shape[1] != a.shape[0] or len(g) != v.shape[0]:
+        raise ValueError("doa_scan_eval: vectors of shape %s, %d weights, a table of %d elements" % (v.shape, len(g), a.shape[0]))
+    out = np.zeros(a.shape[1], np.float64)
+    check(L.lib().rts_doa_scan_eval(ptr(v.view(np.float64)), ptr(g), v.shape[1], v.shape[0], ptr(a.view(np.float64)), a.shape[1],
+                                    L.RTS_DOA_INVERSE if inverse else 0, ptr(out)))
+    return out
+
+
+_DOA_METHODS = {"bartlett": L.RTS_DOA_BARTLETT, "capon": L.RTS_DOA_CAPON, "music": L.RTS_DOA_MUSIC}
+
+
+def doa_weights(method, values, n_sources=0, loading=0.0):
+    """rts_doa_weights (pure host): a spectrum ("bartlett", "capon", "music") as the scan's (first vector, g [m], inverse) from the
+    eigenvalues in eig_eval's order: Bartlett g = lambda over all vectors, Capon g = 1 / (lambda + loading) over all and inverse,
+    MUSIC g = 1 over the vectors from n_sources on and inverse"""
+    values = np.ascontiguousarray(np.asarray(values, np.float64).ravel())
+    first, m, flags = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0); g = np.zeros(max(len(values), 1), np.float64)
+    check(L.lib().rts_doa_weights(_DOA_METHODS.get(method, method), ptr(values), len(values), int(n_sources), float(loading),
+                                  C.byref(first), C.byref(m), ptr(g), C.byref(flags)))
+    return first.value, g[:m.value].copy(), bool(flags.value & L.RTS_DOA_INVERSE)
+
+
+def source_count(values, K, criterion="mdl"):
+    """rts_source_count (pure host): the number of sources by Wax and Kailath's "aic" or "mdl" from the eigenvalues in descending
+    order (all > 0) and the number of snapshots K"""
+    values = np.ascontiguousarray(np.asarray(values, np.float64).ravel())
+    k = C.c_uint32(0)
+    check(L.lib().rts_source_count(ptr(values), len(values), int(K), {"aic": L.RTS_DOA_AIC, "mdl": L.RTS_DOA_MDL}.get(criterion, criterion), C.byref(k)))
+    return k.value
+
+
 def _st_cov_params(taps, source, first, count, first_bin, n_bins, skip, device_in, n_rows_in):
     """RtsStCovParams: _cov_params' fields (the rows are the span the snapshots lie in) and the taps"""
     c = _cov_params(source, first, count, first_bin, n_bins, skip, device_in, n_rows_in)
@@ -632,7 +689,7 @@ class Tracer:
         self.h = C.c_void_p()
         check(L.lib().rts_create(C.byref(p), C.byref(self.h)))
         self.width = width; self.max_refl = max_refl; self.depth = max_refl + (2 if max_refr else 0)
-        self.n_targets = 0; self.keep_all = keep_all
+        self.n_targets = 0; self.keep_all = keep_all; self.device = device
         self._keep = []
 
     def close(self):
@@ -1005,6 +1062,82 @@ class Tracer:
         self.cube_covariance(fetch=False, **(train or {}))
         w = self.cube_mvdr(steering, loading)
         return self.cube_beamform(w, **beamform_kwargs)
+
+    def cube_eig(self, n=None, device_cov=None, device_values=None, device_vectors=None, fetch=True):
+        """rts_cube_eig: the eigenpairs of the library-owned covariance of the last cube_covariance / cube_st_covariance, or of
+        device_cov = data_ptr() of a complex128 device tensor [n][n] (n is needed then).  Into caller device tensors float64 [n] and
+        complex128 [n][n] (device_values and device_vectors, both; nothing is fetched) or the library's outputs, returned when fetch:
+        (eigenvalues descending, eigenvectors, ROW k the eigenvector of value k); a failed solve raises there"""
+        if device_cov and not n:
+            raise ValueError("cube_eig(device_cov=...) needs n")
+        p = L.RtsEigParams()
+        p.n, p.device_cov = int(n or 0), device_cov if device_cov else None
+        check(L.lib().rts_cube_eig(self.h, C.byref(p), C.c_void_p(device_values) if device_values else None, C.c_void_p(device_vectors) if device_vectors else None))
+        if device_values or device_vectors:
+            return None
+        self._eig_n = int(n) if device_cov else (getattr(self, "_cov_n", 0) or int(n or 0))
+        return self.eigenpairs() if fetch else None
+
+    def eigenpairs(self):
+        """rts_cube_eig_get: the library-owned outputs of the last cube_eig: (eigenvalues float64 [n], eigenvectors complex [n][n])"""
+        n = getattr(self, "_eig_n", None) or 1
+        values = np.zeros(n, np.float64); vectors = np.zeros((n, n), np.complex128)
+        check(L.lib().rts_cube_eig_get(self.h, ptr(values), ptr(vectors.view(np.float64)), n, 2 * n * n))
+        return values, vectors
+
+    def cube_doa_scan(self, steering, g, first_vector=0, inverse=False, n_dirs=None, device_vectors=None, n=None, device_ptr=None, fetch=True):
+        """rts_cube_doa_scan: the angular spectrum q[dir] = sum_k g[k] |v_k^H a_dir|^2 (1 / q with inverse) through the rows first_vector ..
+        first_vector + len(g) - 1 of the library-owned eigenvectors of the last cube_eig, or of device_vectors = data_ptr() of a
+        complex128 device tensor [n][n] (n is needed then).  steering: a host table complex [n_dirs][n] (steering()'s rows), which is
+        transposed and uploaded through torch, or data_ptr() of a complex128 device tensor in the scan's own element-major layout
+        [n][n_dirs] (n_dirs is needed then).  Float64 [n_dirs] into a caller device tensor (device_ptr; nothing is fetched) or the
+        library's output, returned when fetch"""
+        g = np.ascontiguousarray(np.asarray(g, np.float64).ravel())
+        if isinstance(steering, int):
+            if not n_dirs:
+                raise ValueError("cube_doa_scan(steering=<device pointer>) needs n_dirs")
+            table = steering
+        else:
+            import torch
+            a = _steering_table(steering)
+            # the table lives on the handle until the next upload replaces it; torch's stream is not the handle's: the device-wide wait puts
+            # the table in place before the scan reads it and ends the previous scan before its table goes
+            self._doa_table = torch.from_numpy(a).to("cuda:%d" % self.device)
+            torch.cuda.synchronize(self.device)
+            table, n_dirs = self._doa_table.data_ptr(), a.shape[1]
+        if device_vectors and not n:
+            raise ValueError("cube_doa_scan(device_vectors=...) needs n")
+        p = L.RtsDoaScanParams()
+        p.n, p.first_vector, p.m, p.flags, p.n_dirs = int(n or 0), int(first_vector), len(g), L.RTS_DOA_INVERSE if inverse else 0, int(n_dirs)
+        p.g, p.device_steering, p.device_vectors = ptr(g), table, device_vectors if device_vectors else None
+        check(L.lib().rts_cube_doa_scan(self.h, C.byref(p), C.c_void_p(device_ptr) if device_ptr else None))
+        if device_ptr:
+            return None
+        self._doa_n = int(n_dirs)
+        return self.doa_spectrum() if fetch else None
+
+    def doa_spectrum(self):
+        """rts_cube_doa_get: the library-owned output of the last cube_doa_scan, float64 [n_dirs]"""
+        out = np.zeros(getattr(self, "_doa_n", None) or 1, np.float64)
+        check(L.lib().rts_cube_doa_get(self.h, ptr(out), out.size))
+        return out
+
+    def cube_doa(self, steering, method="music", n_sources=None, loading=0.0, train=None):
+        """cube_covariance(**train) -> cube_eig -> doa_weights(method, the eigenvalues, n_sources, loading) -> cube_doa_scan(steering):
+        the angular spectrum ("music", "capon" or "bartlett") of the training cells `train` names (cube_covariance's keywords;
+        default: every cell of the cube) over the host table steering [n_dirs][n_rx] (steering()'s rows).  n_sources None:
+        source_count's MDL estimate from the eigenvalues and the number of training cells.  The cube stays on the device; the
+        eigenvalues (at most 64) pass through the host.  Returns the spectrum float64 [n_dirs]."""
+        train = dict(train or {})
+        self.cube_covariance(fetch=False, **train)
+        values, _ = self.cube_eig()
+        if n_sources is None and method in ("music", L.RTS_DOA_MUSIC):
+            n_rx, n_p, nb = self._cube_shape
+            rows = {"cube": n_p, "map": getattr(self, "_doppler_n", 0)}.get(train.get("source", "cube"), train.get("n_rows_in", 0))
+            K = (train.get("count") or rows - train.get("first", 0)) * ((train.get("n_bins") or nb - train.get("first_bin", 0)) - (train["skip"][1] if train.get("skip") else 0))
+            n_sources = source_count(values, K, "mdl")
+        first, g, inverse = doa_weights(method, values, n_sources or 0, loading)
+        return self.cube_doa_scan(steering, g, first_vector=first, inverse=inverse)
 
     def cube_st_covariance(self, taps, source="cube", first=0, count=None, first_bin=0, n_bins=None, skip=None, device_in=None, n_rows_in=0,
                            device_ptr=None, fetch=True):

@@ -978,6 +978,177 @@ extern "C" int rts_cube_st_get(RtsHandle c, double* host_out, uint64_t capacity_
     return rts_cube_copy_out(c, "rts_cube_st_get", "no library-owned filter output (rts_cube_st_apply with device_out NULL; the output ends at rts_cube_attach) / null output", c->cube.st.valid, c->cube.st.p, c->cube.st.doubles, host_out, capacity_doubles);
 }
 
+// ------------------------------------------------------------------------------------- direction finding
+// (rts_amd.h: RtsEigParams, RtsDoaScanParams; the trees and the launch plans are rts_doa.h, shared by the host exports and the kernels, rts_doa.hip)
+static bool rts_bytes_overlap(const void* a, size_t na, const void* b, size_t nb)
+{
+    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + na, b0 = (uintptr_t)b, b1 = b0 + nb;
+    return a0 < b1 && b0 < a1;
+}
+
+extern "C" int rts_eig_eval(const double* cov, uint32_t n, double* values_out, double* vectors_out, uint32_t* sweeps_out)
+{
+    const RtsEigPlan plan = rts_eig_plan(n);
+    if (!plan.supported) { rts_set_error("rts_eig_eval: n = %u (1 .. %u)", n, RTS_BEAM_MAX_RX); return RTS_ERR_INVALID; }
+    if (!cov || !values_out || !vectors_out) { rts_set_error("rts_eig_eval: null covariance or output array"); return RTS_ERR_INVALID; }
+    std::vector<double> X(plan.vector_doubles), V(plan.vector_doubles), lambda(n), values(n), vectors(plan.vector_doubles);
+    uint32_t sweeps = 0;
+    const uint32_t status = rts_eig_eval_host(cov, n, X.data(), V.data(), lambda.data(), values.data(), vectors.data(), &sweeps);
+    if (status == 2u) { rts_set_error("rts_eig_eval: status 2: a non-finite entry in the covariance's lower triangle"); return RTS_ERR_INVALID; }
+    if (status) { rts_set_error("rts_eig_eval: status 1: no convergence in %u sweeps", RTS_EIG_MAX_SWEEPS); return RTS_ERR_INVALID; }
+    memcpy(values_out, values.data(), sizeof(double) * n);
+    memcpy(vectors_out, vectors.data(), sizeof(double) * plan.vector_doubles);
+    if (sweeps_out) *sweeps_out = sweeps;
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_eig(RtsHandle c, const RtsEigParams* p, void* device_values, void* device_vectors)
+{
+    const char* who = "rts_cube_eig";
+    CHECK_HANDLE(c);
+    NEED_CUBE(c, who, "no cube (call rts_cube_attach first)");
+    if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
+    if (p->reserved0 || p->reserved[0] || p->reserved[1]) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
+    const double* cov = (const double*)p->device_cov; uint32_t n = p->n;
+    if (cov) {
+        if ((uintptr_t)cov & 15u) { rts_set_error("%s: device_cov is not 16-byte aligned", who); return RTS_ERR_INVALID; }
+    } else {
+        if (!c->cube.cov.valid) { rts_set_error("%s: no covariance (rts_cube_covariance or rts_cube_st_covariance with device_out NULL first, or pass device_cov)", who); return RTS_ERR_INVALID; }
+        if (n != 0 && n != c->cube.cov_n) { rts_set_error("%s: n = %u, the library-owned covariance's %u (or 0)", who, n, c->cube.cov_n); return RTS_ERR_INVALID; }
+        cov = c->cube.cov.p; n = c->cube.cov_n;
+    }
+    const RtsEigPlan plan = rts_eig_plan(n);
+    if (!plan.supported) { rts_set_error("%s: n = %u (1 .. %u)", who, n, RTS_BEAM_MAX_RX); return RTS_ERR_INVALID; }
+    if (!device_values != !device_vectors) { rts_set_error("%s: device_values and device_vectors: both caller-owned or both NULL", who); return RTS_ERR_INVALID; }
+    if ((uintptr_t)device_values & 7u) { rts_set_error("%s: device_values is not 8-byte aligned", who); return RTS_ERR_INVALID; }
+    if ((uintptr_t)device_vectors & 15u) { rts_set_error("%s: device_vectors is not 16-byte aligned", who); return RTS_ERR_INVALID; }
+    if (device_values) {
+        const size_t nv = sizeof(double) * plan.value_doubles, nx = sizeof(double) * plan.vector_doubles;
+        if (rts_bytes_overlap(device_values, nv, device_vectors, nx)) { rts_set_error("%s: device_values overlaps device_vectors", who); return RTS_ERR_INVALID; }
+        if (rts_bytes_overlap(device_values, nv, cov, nx) || rts_bytes_overlap(device_vectors, nx, cov, nx)) { rts_set_error("%s: an output overlaps the covariance the call reads", who); return RTS_ERR_INVALID; }
+    }
+    CHECK_CLOSED(c);
+    double* values; double* vectors;
+    RTS_HIP(c->cube.eig_val.place(device_values, plan.value_doubles, &values));
+    RTS_HIP(c->cube.eig_vec.place(device_vectors, plan.vector_doubles, &vectors));
+    RTS_HIP(c->cube.d_eig_status.reserve(2));
+    if (!device_values) { c->cube.eig_val.record(values, plan.value_doubles); c->cube.eig_vec.record(vectors, plan.vector_doubles); c->cube.eig_n = n; }
+    return rts_cube_eig_device(c, plan, n, cov, c->cube.d_eig_status.p + (device_values ? 1 : 0), values, vectors);
+}
+
+extern "C" int rts_cube_eig_get(RtsHandle c, double* values_out, double* vectors_out, uint64_t capacity_values, uint64_t capacity_vector_doubles)
+{
+    CHECK_HANDLE(c);
+    const RtsCubeProduct& v = c->cube.eig_val; const RtsCubeProduct& x = c->cube.eig_vec;
+    if (!c->cube.set || !v.valid || !x.valid || (!values_out && !vectors_out)) { rts_set_error("rts_cube_eig_get: no library-owned eigenpairs (rts_cube_eig with both outputs NULL; the eigenpairs end at rts_cube_attach) / null outputs"); return RTS_ERR_INVALID; }
+    if ((values_out && capacity_values < v.doubles) || (vectors_out && capacity_vector_doubles < x.doubles)) { rts_set_error("rts_cube_eig_get: capacity too small"); return RTS_ERR_CAPACITY; }
+    RTS_HIP(hipStreamSynchronize(c->stream));
+    uint32_t status = 0;
+    RTS_HIP(hipMemcpy(&status, c->cube.d_eig_status.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (status == 2u) { rts_set_error("rts_cube_eig_get: status 2: a non-finite entry in the covariance's lower triangle; every output is NaN"); return RTS_ERR_INVALID; }
+    if (status) { rts_set_error("rts_cube_eig_get: status 1: no convergence in %u sweeps; every output is NaN", RTS_EIG_MAX_SWEEPS); return RTS_ERR_INVALID; }
+    if (values_out) RTS_HIP(hipMemcpy(values_out, v.p, sizeof(double) * v.doubles, hipMemcpyDeviceToHost));
+    if (vectors_out) RTS_HIP(hipMemcpy(vectors_out, x.p, sizeof(double) * x.doubles, hipMemcpyDeviceToHost));
+    return RTS_OK;
+}
+
+// the record of a scan over vectors of n elements: what needs no device memory
+static int rts_doa_scan_check(const char* who, uint32_t n, uint32_t first_vector, uint32_t m, uint32_t flags, uint64_t n_dirs, const double* g, RtsDoaScanPlan* plan)
+{
+    if (n == 0 || n > RTS_BEAM_MAX_RX) { rts_set_error("%s: n = %u (1 .. %u)", who, n, RTS_BEAM_MAX_RX); return RTS_ERR_INVALID; }
+    if (flags & ~RTS_DOA_INVERSE) { rts_set_error("%s: unknown flags 0x%x", who, flags); return RTS_ERR_INVALID; }
+    if (m == 0 || first_vector > n || m > n - first_vector) { rts_set_error("%s: first_vector = %u, m = %u: at least one vector, inside the table's %u rows", who, first_vector, m, n); return RTS_ERR_INVALID; }
+    if (n_dirs == 0) { rts_set_error("%s: n_dirs = 0", who); return RTS_ERR_INVALID; }
+    if (!g) { rts_set_error("%s: null g", who); return RTS_ERR_INVALID; }
+    for (uint32_t k = 0; k < m; k++) if (!std::isfinite(g[k])) { rts_set_error("%s: g[%u] is not finite", who, k); return RTS_ERR_INVALID; }
+    *plan = rts_doa_scan_plan(n, m, n_dirs);
+    if (!plan->supported) { rts_set_error("%s: n_dirs = %llu directions, %u per workgroup: more than %u workgroups (the launch grid)", who, (unsigned long long)n_dirs, RTS_DOA_THREADS, RTS_DOA_MAX_GRID_X); return RTS_ERR_INVALID; }
+    return RTS_OK;
+}
+
+extern "C" int rts_doa_scan_eval(const double* vectors, const double* g, uint32_t n, uint32_t m, const double* steering, uint64_t n_dirs, uint32_t flags, double* out)
+{
+    RtsDoaScanPlan plan;
+    int rc = rts_doa_scan_check("rts_doa_scan_eval", n, 0u, m, flags, n_dirs, g, &plan); if (rc != RTS_OK) return rc;
+    if (!vectors || !steering || !out) { rts_set_error("rts_doa_scan_eval: null vectors, steering or output array"); return RTS_ERR_INVALID; }
+    rts_doa_scan_eval_host(vectors, g, n, m, steering, n_dirs, flags, out);
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_doa_scan(RtsHandle c, const RtsDoaScanParams* p, void* device_out)
+{
+    const char* who = "rts_cube_doa_scan";
+    CHECK_HANDLE(c);
+    NEED_CUBE(c, who, "no cube (call rts_cube_attach first)");
+    if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
+    if (p->reserved[0] || p->reserved[1]) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
+    const double* vec = (const double*)p->device_vectors; uint32_t n = p->n;
+    if (vec) {
+        if ((uintptr_t)vec & 15u) { rts_set_error("%s: device_vectors is not 16-byte aligned", who); return RTS_ERR_INVALID; }
+    } else {
+        if (!c->cube.eig_vec.valid) { rts_set_error("%s: no eigenvectors (rts_cube_eig with both outputs NULL first, or pass device_vectors)", who); return RTS_ERR_INVALID; }
+        if (n != 0 && n != c->cube.eig_n) { rts_set_error("%s: n = %u, the library-owned eigenvectors' %u (or 0)", who, n, c->cube.eig_n); return RTS_ERR_INVALID; }
+        vec = c->cube.eig_vec.p; n = c->cube.eig_n;
+    }
+    RtsDoaScanPlan plan;
+    int rc = rts_doa_scan_check(who, n, p->first_vector, p->m, p->flags, p->n_dirs, p->g, &plan); if (rc != RTS_OK) return rc;
+    if (!p->device_steering) { rts_set_error("%s: null device_steering", who); return RTS_ERR_INVALID; }
+    if ((uintptr_t)p->device_steering & 15u) { rts_set_error("%s: device_steering is not 16-byte aligned", who); return RTS_ERR_INVALID; }
+    if ((uintptr_t)device_out & 7u) { rts_set_error("%s: device_out is not 8-byte aligned", who); return RTS_ERR_INVALID; }
+    const double* rows = vec + 2 * (size_t)p->first_vector * n;
+    if (device_out) {
+        const size_t no = sizeof(double) * plan.out_doubles;
+        if (rts_bytes_overlap(device_out, no, p->device_steering, 16u * (size_t)n * (size_t)p->n_dirs)) { rts_set_error("%s: device_out overlaps the steering table the call reads", who); return RTS_ERR_INVALID; }
+        if (rts_bytes_overlap(device_out, no, rows, 16u * (size_t)p->m * n)) { rts_set_error("%s: device_out overlaps the vectors the call reads", who); return RTS_ERR_INVALID; }
+    }
+    CHECK_CLOSED(c);
+    double* out; RTS_HIP(c->cube.doa.place(device_out, plan.out_doubles, &out));
+    // g -> pinned staging -> the device, on the stream (m <= RTS_BEAM_MAX_RX: one size for every call)
+    double* g = nullptr;
+    RTS_HIP(c->cube.doa_g.begin(RTS_BEAM_MAX_RX, RTS_BEAM_MAX_RX, RTS_BEAM_MAX_RX, &g));
+    memcpy(g, p->g, sizeof(double) * p->m);
+    RTS_HIP(c->cube.doa_g.send(p->m, c->stream));
+    if (!device_out) c->cube.doa.record(out, plan.out_doubles);
+    return rts_cube_doa_scan_device(c, plan, n, p->m, p->n_dirs, p->flags, (const double*)p->device_steering, rows, c->cube.doa_g.dev.p, out);
+}
+
+extern "C" int rts_cube_doa_get(RtsHandle c, double* host_out, uint64_t capacity_doubles)
+{
+    CHECK_HANDLE(c);
+    return rts_cube_copy_out(c, "rts_cube_doa_get", "no library-owned spectrum (rts_cube_doa_scan with device_out NULL; the spectrum ends at rts_cube_attach) / null output", c->cube.doa.valid, c->cube.doa.p, c->cube.doa.doubles, host_out, capacity_doubles);
+}
+
+extern "C" int rts_doa_weights(uint32_t method, const double* values, uint32_t n, uint32_t n_sources, double loading, uint32_t* first, uint32_t* m, double* g, uint32_t* flags)
+{
+    if (!values || !first || !m || !g || !flags) { rts_set_error("rts_doa_weights: null eigenvalues or output"); return RTS_ERR_INVALID; }
+    if (n == 0 || n > RTS_BEAM_MAX_RX) { rts_set_error("rts_doa_weights: n = %u (1 .. %u)", n, RTS_BEAM_MAX_RX); return RTS_ERR_INVALID; }
+    uint32_t bad = 0, f = 0, mm = 0, fl = 0; double gg[RTS_BEAM_MAX_RX];
+    switch (rts_doa_weights_host(method, values, n, n_sources, loading, &f, &mm, gg, &fl, &bad)) {
+        case 0: break;
+        case 1: rts_set_error("rts_doa_weights: unknown method %u (RTS_DOA_BARTLETT, _CAPON, _MUSIC)", method); return RTS_ERR_INVALID;
+        case 2: rts_set_error("rts_doa_weights: loading = %g (finite, >= 0)", loading); return RTS_ERR_INVALID;
+        case 3: rts_set_error("rts_doa_weights: values[%u] is not finite", bad); return RTS_ERR_INVALID;
+        case 4: rts_set_error("rts_doa_weights: RTS_DOA_MUSIC: n_sources = %u leaves no noise subspace of n = %u", n_sources, n); return RTS_ERR_INVALID;
+        default: rts_set_error("rts_doa_weights: RTS_DOA_CAPON: values[%u] + loading = %g is not > 0 (load more)", bad, values[bad] + loading); return RTS_ERR_INVALID;
+    }
+    *first = f; *m = mm; *flags = fl; memcpy(g, gg, sizeof(double) * mm);
+    return RTS_OK;
+}
+
+extern "C" int rts_source_count(const double* values, uint32_t n, uint64_t K, uint32_t criterion, uint32_t* n_sources)
+{
+    if (!values || !n_sources) { rts_set_error("rts_source_count: null eigenvalues or output"); return RTS_ERR_INVALID; }
+    if (n == 0 || n > RTS_BEAM_MAX_RX) { rts_set_error("rts_source_count: n = %u (1 .. %u)", n, RTS_BEAM_MAX_RX); return RTS_ERR_INVALID; }
+    if (K == 0) { rts_set_error("rts_source_count: K = 0 snapshots"); return RTS_ERR_INVALID; }
+    if (criterion != RTS_DOA_AIC && criterion != RTS_DOA_MDL) { rts_set_error("rts_source_count: unknown criterion %u (RTS_DOA_AIC, RTS_DOA_MDL)", criterion); return RTS_ERR_INVALID; }
+    for (uint32_t k = 0; k < n; k++) {
+        if (!std::isfinite(values[k]) || !(values[k] > 0.0)) { rts_set_error("rts_source_count: values[%u] = %g (finite, > 0: every eigenvalue enters a logarithm)", k, values[k]); return RTS_ERR_INVALID; }
+        if (k && values[k] > values[k - 1u]) { rts_set_error("rts_source_count: values[%u] > values[%u]: not in descending order", k, k - 1u); return RTS_ERR_INVALID; }
+    }
+    *n_sources = rts_source_count_host(values, n, K, criterion);
+    return RTS_OK;
+}
+
 // ------------------------------------------------------------------------------------- backprojection imaging
 // (rts_amd.h: RtsImageParams; the arithmetic and the launch plan are rts_image.h, shared by the host export and the kernel, rts_image.hip)
 static int rts_image_check(const RtsImageParams* p, const RtsCubeParams& q, const char* who)

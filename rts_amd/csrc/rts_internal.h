@@ -18,6 +18,7 @@
 #include "rts_beam.h"             // the beamformer's term, sum and streaming peak, its evaluator and the host-only plan of its launch
 #include "rts_adapt.h"            // adaptive beamforming: the covariance's term and partition, the weight solve, their evaluators and the host-only plans of their launches
 #include "rts_stap.h"             // space-time adaptive processing: the stacked snapshot, its covariance's and filter's evaluators, the host-only plan of the filter's launch
+#include "rts_doa.h"              // direction finding: the eigensolver's and the angular scan's trees, the spectra's weights, the source count, their evaluators and the host-only plans of their launches
 #include "rts_cfar_os.h"          // CFAR: what every detector shares (rts_cfar.h: window, training count, local maximum, refinement, record); OS: rank rule, alphas, the host evaluator
 #include "rts_owned.h"            // DevBuf, PinBuf, StagedUpload: device and pinned host memory that frees itself
 #include "rts_launch_plan.h"      // RTS_BLOCK, RTS_WTILE, RTS_COOP_GROUP, RTS_STACK_OVF and the host arithmetic of a launch
@@ -334,9 +335,16 @@ struct RtsCubeState {
     // filter's output, for rts_cube_st_get; the call's weight table goes through a staged upload
     RtsCubeProduct st;
     StagedUpload<double> st_w;
+    // direction finding (rts_cube_eig, rts_cube_doa_scan, rts_doa.hip): the eigenvalues and the eigenvectors and their order, for
+    // rts_cube_eig_get and rts_cube_doa_scan without device_vectors; the solves' status words (0: library-owned outputs, 1: caller-owned);
+    // the spectrum, for rts_cube_doa_get; the call's g goes through a staged upload of one size (RTS_BEAM_MAX_RX doubles)
+    RtsCubeProduct eig_val, eig_vec; uint32_t eig_n = 0; DevBuf<uint32_t> d_eig_status;
+    RtsCubeProduct doa;
+    StagedUpload<double> doa_g;
     // every product belongs to the cube it was made from: the Doppler map (which rts_cube_detect may take), the detection list, the image
-    // the spectrogram, the range transform, the beams, the covariance, the adaptive weights and the space-time filter's output end when another cube is attached
-    void end_products() { doppler.valid = false; det_valid = false; image.valid = false; stft.valid = false; range.valid = false; beam.valid = false; cov.valid = false; mvdr.valid = false; st.valid = false; }
+    // the spectrogram, the range transform, the beams, the covariance, the adaptive weights, the space-time filter's output, the eigenpairs and the angular spectrum end when another cube is attached
+    void end_products() { doppler.valid = false; det_valid = false; image.valid = false; stft.valid = false; range.valid = false; beam.valid = false; cov.valid = false; mvdr.valid = false; st.valid = false;
+                          eig_val.valid = false; eig_vec.valid = false; doa.valid = false; }
 };
 
 // What a pulse leaves for its accessors (rts_results_api.hip; the finalisers, the aggregation and the end-of-pulse chains of rts_api.hip; the
@@ -478,6 +486,9 @@ int rts_cube_beam_device(RtsContext* c, const RtsBeamParams& p, const RtsBeamPla
 int rts_cube_cov_device(RtsContext* c, const RtsCovSet& set, const RtsCovPlan& plan, uint32_t n_taps, const double* in, uint64_t rx_stride, double* part, double* out);      // rts_adapt.hip
 int rts_cube_mvdr_device(RtsContext* c, const RtsMvdrPlan& plan, uint32_t n_rx, uint32_t n_beams, double loading, const double* cov, const double* steering, uint32_t* status, double* out);
 int rts_cube_st_apply_device(RtsContext* c, const RtsStApplyParams& p, const RtsStApplyPlan& plan, const double* in, uint64_t rx_stride, const double* weights, void* out);      // rts_stap.hip
+int rts_cube_eig_device(RtsContext* c, const RtsEigPlan& plan, uint32_t n, const double* cov, uint32_t* status, double* values, double* vectors);      // rts_doa.hip
+int rts_cube_doa_scan_device(RtsContext* c, const RtsDoaScanPlan& plan, uint32_t n, uint32_t m, uint64_t n_dirs, uint32_t flags, const double* steering, const double* vectors,
+                             const double* g, double* out);
 int rts_cube_backproject_device(RtsContext* c, const RtsImageParams& p, const RtsImagePlan& plan, const double* geo, double* out);      // rts_image.hip
 int rts_post_finalise(RtsContext* c, const double* rcs_host, double wl, double gt, double gr, double carrier, double cspeed);
 int rts_pattern_pulse_upload(RtsContext* c, const RtsSpecParams& q, RtsPatArgs* out);      // the pulse's receiver rows -> the device, on c->stream
