@@ -587,6 +587,78 @@ int rts_cfar_os_alpha(uint32_t n_train, uint32_t rank, double pfa, double* alpha
 int rts_cfar_os_eval(const RtsCubeParams* q, const double* map, uint32_t n_doppler, const RtsCfarOsParams* p,
                      RtsDetection* out, uint32_t capacity, uint32_t* n_out);
 
+/* ---------------------------------------------------------------- plot extraction: detections clustered into target plots
+ * The detectors above report CELLS; an extended body (a skin return and its multi-bounce paths, a blade flash along Doppler) crosses
+ * the threshold in tens to thousands of them.  rts_cube_plots clusters a detection list into PLOTS -- the connected components of an
+ * adjacency on the map -- on the device, and writes one record per plot: power-weighted centroid, extent, peak and summed power.
+ * Detect WITHOUT RTS_CFAR_LOCAL_MAX, then extract plots.  The rules are rts_amd/csrc/rts_plot.h, shared by the kernels
+ * (rts_plot.hip) and the host evaluator rts_plots_eval, which agree bit for bit.
+ *   Input: a detection list in ascending flat order (rx, doppler_bin, range_bin) with no cell twice -- what both detectors write.
+ *     device_list NULL: the handle's list, the first min(total, stored) records, with the n_doppler of the map it was detected on
+ *     (the detect call records it).  Otherwise a caller-owned DEVICE array of n_list RtsDetection on a map of n_doppler rows and the
+ *     attached cube's n_bins; it is taken as given: a list that breaks the ordering rule makes the plots unspecified, but nothing is
+ *     read or written outside the list and the output buffers.  rts_plots_eval checks the ordering and the bin ranges and refuses a
+ *     list that breaks them.
+ *   Adjacency: two detections of the same rx are adjacent when |r - r'| <= link_range and an integer dk with |dk| <= link_doppler and
+ *     (k + dk) mod n_doppler == k' exists, and they are not the same cell.  Doppler wraps, range does not, receivers never join.  As
+ *     in the CFAR section the wrap is applied as it stands on short maps: with 2 link_doppler + 1 > n_doppler rows are simply named
+ *     more than once.  link = (0, 0) makes every detection its own plot.  A plot is a connected component of this relation.
+ *   Identity and order: a plot's first_index is the smallest list index among its cells (its ROOT); plots are written in ascending
+ *     first_index.  Plots of fewer than min_cells cells are removed after the components are formed, so the survivors keep their
+ *     relative order.  Output positions come from flags and a scan, never from atomics, and two runs on one list give the same bytes.
+ *   Record: with the root at cell (k0, r0), member i has dr_i = r_i - r0 and dk_i = k_i - k0 wrapped into [-n_doppler / 2, n_doppler / 2)
+ *     in integer arithmetic -- a component wider than half the Doppler circle is mis-unwrapped (its far members land on the wrong
+ *     side of the root); that is a documented limit, not repaired.  With P_i the detection's power: S = sum P_i, S_r = sum P_i dr_i,
+ *     S_k = sum P_i dk_i, S_rr = sum P_i dr_i^2, S_kk = sum P_i dk_i^2 (the square formed first), noise_sum = sum noise_i; each product
+ *     is rounded before it is added (no contraction).  The ORDER of every sum is a pure function of the member count: members in
+ *     ascending list index, added left to right from 0 inside blocks of 64 consecutive members, the block sums added left to right
+ *     from 0.  Then
+ *       range_centroid = (double)r0 + S_r / S;  doppler_centroid = w = (double)k0 + S_k / S wrapped into [-n_doppler / 2, n_doppler / 2)
+ *       exactly as RtsDetection's w;  delay = t0 + range_centroid dt;  doppler = w / (n_doppler pri) (0 when pri is 0);
+ *       range_spread, doppler_spread = sqrt(max(0, S_xx / S - (S_x / S)^2)), the power-weighted standard deviation in bins;
+ *       range_min, range_max over the members;  doppler_lo = (k0 + min dk) mod n_doppler, doppler_span = min(n_doppler, max dk - min dk + 1):
+ *       the Doppler extent is the circular interval doppler_lo .. doppler_lo + doppler_span - 1 mod n_doppler;
+ *       peak_index = the member of largest power, ties to the lowest index;  power_sum = S.
+ *     A plot of ONE cell takes that detection's own refinement: range_centroid = (double)r + range_offset, w from k + doppler_offset,
+ *     both spreads 0, delay and doppler by the very expressions of RtsDetection -- so a RTS_CFAR_LOCAL_MAX list with link = (0, 0)
+ *     passes through with delay and doppler equal to its detections' bit for bit.  S <= 0 (all powers zero): centroids at the root,
+ *     spreads 0.
+ *   Lifetime: rts_cube_plots never waits on the host: it sizes its launches by the list's capacity and reads the count on the device.
+ *     The plots index the detection list and live until the next rts_cube_plots, rts_cube_detect, rts_cube_detect_os,
+ *     rts_cube_attach or rts_destroy.  rts_cube_plots_get synchronises, sets *n_out to the total and copies min(total, stored,
+ *     capacity) records.  It returns RTS_ERR_CAPACITY when fewer records were copied than the total, when max_plots cut the device
+ *     list, and when the detection list the plots were made from was itself truncated (the plots then describe the stored prefix);
+ *     RTS_ERR_INVALID when no plots exist.
+ *   rts_plots_eval: pure host, the same plots of a host list on a map of q->n_rx x n_doppler x q->n_bins cells (q: n_rx, n_bins, t0,
+ *     dt; n_pulses is not used): up to `capacity` records to out, the total to *n_out, RTS_ERR_CAPACITY when capacity is too small.
+ *     Of p it uses link_range, link_doppler, min_cells and pri; the other fields are validated and otherwise ignored.
+ *   RTS_ERR_INVALID, the message naming the field: no cube; no detection list and no device_list; link_range or link_doppler above
+ *     RTS_PLOT_MAX_LINK; nonzero reserved fields; pri negative or not finite; device_list with n_doppler = 0 or not 8-byte aligned;
+ *     n_list or n_doppler nonzero without device_list.  rts_plots_eval additionally refuses NULL arguments (out may be NULL when
+ *     capacity is 0), n_doppler = 0, a list out of order and bins outside the map; a refused call leaves out untouched. */
+#define RTS_PLOT_MAX_LINK 4u
+typedef struct RtsPlotParams {
+    uint32_t link_range, link_doppler;   /* 0 .. RTS_PLOT_MAX_LINK: reach of the adjacency, cells, per axis            */
+    uint32_t min_cells;                  /* plots of fewer cells are dropped; 0 is taken as 1                          */
+    uint32_t max_plots;                  /* device list length; 0: as many as the detection list can hold              */
+    double pri;                          /* as RtsCfarParams.pri: for RtsPlot.doppler; 0: doppler = 0                   */
+    const void* device_list;             /* NULL: the handle's detection list; else caller-owned DEVICE RtsDetection[] */
+    uint32_t n_list, n_doppler;          /* with device_list: its length and the map's Doppler rows (>= 1); else 0      */
+    uint64_t reserved[2];                /* 0 */
+} RtsPlotParams;                                              /* 56 bytes */
+typedef struct RtsPlot {
+    uint32_t rx, n_cells, first_index, peak_index;            /* indices into the detection list                          */
+    uint32_t range_min, range_max, doppler_lo, doppler_span;  /* extent; Doppler circular: doppler_lo .. +span-1 mod n    */
+    double power_sum, peak_power, noise_sum;
+    double range_centroid, doppler_centroid;                  /* bins; Doppler wrapped into [-n/2, n/2)                   */
+    double range_spread, doppler_spread;                      /* power-weighted standard deviation, bins                  */
+    double delay, doppler;                                    /* t0 + range_centroid dt;  Hz                              */
+} RtsPlot;                                                    /* 104 bytes */
+int rts_cube_plots(RtsHandle h, const RtsPlotParams* p);
+int rts_cube_plots_get(RtsHandle h, RtsPlot* out, uint32_t capacity, uint32_t* n_out);
+int rts_plots_eval(const RtsCubeParams* q, const RtsDetection* list, uint32_t n_list, uint32_t n_doppler,
+                   const RtsPlotParams* p, RtsPlot* out, uint32_t capacity, uint32_t* n_out);   /* pure host */
+
 /* ---------------------------------------------------------------- tapered slow-time spectrogram (STFT) of the return cube
  * The short-time Fourier transform over the pulse axis, per range gate bin or summed over a gate: how Doppler changes INSIDE the
  * interval (rotor and blade flashes, tumbling bodies), where rts_cube_doppler's single rectangular DFT smears it into a band.  A

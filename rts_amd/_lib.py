@@ -127,6 +127,22 @@ class RtsCfarOsParams(C.Structure):
 
 assert C.sizeof(RtsCfarOsParams) == 72
 
+RTS_PLOT_MAX_LINK = 4
+
+
+class RtsPlotParams(C.Structure):
+    _fields_ = [("link_range", C.c_uint32), ("link_doppler", C.c_uint32), ("min_cells", C.c_uint32), ("max_plots", C.c_uint32),
+                ("pri", C.c_double), ("device_list", C.c_void_p), ("n_list", C.c_uint32), ("n_doppler", C.c_uint32),
+                ("reserved", C.c_uint64 * 2)]
+
+
+# RtsPlot (include/rts_amd.h), 104 bytes
+PLOT_DTYPE = np.dtype([("rx", "<u4"), ("n_cells", "<u4"), ("first_index", "<u4"), ("peak_index", "<u4"), ("range_min", "<u4"),
+                       ("range_max", "<u4"), ("doppler_lo", "<u4"), ("doppler_span", "<u4"), ("power_sum", "<f8"), ("peak_power", "<f8"),
+                       ("noise_sum", "<f8"), ("range_centroid", "<f8"), ("doppler_centroid", "<f8"), ("range_spread", "<f8"),
+                       ("doppler_spread", "<f8"), ("delay", "<f8"), ("doppler", "<f8")])
+assert PLOT_DTYPE.itemsize == 104 and C.sizeof(RtsPlotParams) == 56
+
 
 RTS_IMAGE_ACCUMULATE, RTS_IMAGE_PULSE_CHUNK, RTS_IMAGE_MAX_PIXELS = 1, 64, 16777216
 
@@ -332,6 +348,7 @@ EXPORTS = ["rts_create", "rts_destroy", "rts_last_error", "rts_device_count", "r
            "rts_cube_set_waveform", "rts_cube_render", "rts_cube_compress", "rts_waveform_eval",
            "rts_cube_add_noise", "rts_noise_eval", "rts_cube_detect", "rts_cube_detections_get",
            "rts_cube_detect_os", "rts_cfar_os_alpha", "rts_cfar_os_eval",
+           "rts_cube_plots", "rts_cube_plots_get", "rts_plots_eval",
            "rts_cube_backproject", "rts_cube_image_get", "rts_backproject_eval",
            "rts_cube_spectrogram", "rts_cube_spectrogram_get", "rts_stft_eval", "rts_window_make",
            "rts_cube_render_beat", "rts_beat_eval", "rts_cube_range_transform", "rts_cube_range_get", "rts_range_eval",
@@ -414,6 +431,9 @@ def lib():
         "rts_cube_detect_os": [vp, C.POINTER(RtsCfarOsParams), vp, u32],
         "rts_cfar_os_alpha": [u32, u32, C.c_double, C.POINTER(C.c_double)],
         "rts_cfar_os_eval": [C.POINTER(RtsCubeParams), vp, u32, C.POINTER(RtsCfarOsParams), vp, u32, C.POINTER(u32)],
+        "rts_cube_plots": [vp, C.POINTER(RtsPlotParams)],
+        "rts_cube_plots_get": [vp, vp, u32, C.POINTER(u32)],
+        "rts_plots_eval": [C.POINTER(RtsCubeParams), vp, u32, u32, C.POINTER(RtsPlotParams), vp, u32, C.POINTER(u32)],
         "rts_cube_backproject": [vp, C.POINTER(RtsImageParams), vp],
         "rts_cube_image_get": [vp, vp, u64],
         "rts_backproject_eval": [C.POINTER(RtsCubeParams), vp, C.POINTER(RtsImageParams), vp],

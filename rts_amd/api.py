@@ -252,6 +252,34 @@ def cfar_os_eval(map, guard=(2, 2), train=(8, 4), rank=None, pfa=None, alpha=Non
     return out[:n.value].copy()
 
 
+# ------------------------------------------------------------------------------- plot extraction (rts_plot.h)
+def _plot_params(link, min_cells, pri, max_plots=0, device_list=None, n_list=0, n_doppler=0):
+    """RtsPlotParams; link is the adjacency's reach (range, Doppler) in cells"""
+    p = L.RtsPlotParams()
+    p.link_range, p.link_doppler = (int(x) for x in link)
+    p.min_cells, p.max_plots, p.pri = int(min_cells), int(max_plots), float(pri)
+    p.device_list = C.c_void_p(device_list) if device_list else None
+    p.n_list, p.n_doppler = int(n_list), int(n_doppler)
+    return p
+
+
+def plots_eval(detections, n_doppler, link=(1, 1), min_cells=1, pri=0.0, t0=0.0, dt=1.0, n_rx=None, n_bins=None):
+    """rts_plots_eval (pure host): the plots of a DETECTION_DTYPE list in flat (rx, doppler_bin, range_bin) order on a map of
+    n_rx x n_doppler x n_bins cells (n_rx, n_bins None: the smallest map that holds the list); a PLOT_DTYPE array in ascending
+    first_index"""
+    d = np.ascontiguousarray(np.asarray(detections, L.DETECTION_DTYPE))
+    if n_rx is None:
+        n_rx = int(d["rx"].max()) + 1 if len(d) else 1
+    if n_bins is None:
+        n_bins = int(d["range_bin"].max()) + 1 if len(d) else 1
+    q = L.RtsCubeParams(int(n_rx), 1, int(n_bins), 0, float(t0), float(dt))
+    p = _plot_params(link, min_cells, pri)
+    n = C.c_uint32(0)
+    out = np.zeros(max(len(d), 1), L.PLOT_DTYPE)
+    check(L.lib().rts_plots_eval(C.byref(q), ptr(d) if len(d) else None, len(d), int(n_doppler), C.byref(p), ptr(out), len(out), C.byref(n)))
+    return out[:n.value].copy()
+
+
 # ------------------------------------------------------------------------------- backprojection imaging (rts_image.h)
 def _image_params(origin, step_x, step_y, n_x, n_y, tx_positions, rx_positions, cspeed, carrier, taps, first, count, weights, accumulate, n_rx):
     """RtsImageParams and the arrays it points to (keep them alive for the call).  tx_positions [P][3]; rx_positions [n_rx][P][3]
@@ -1228,6 +1256,26 @@ class Tracer:
             check(rc)
         out = np.zeros(max(n.value, 1), L.DETECTION_DTYPE)
         check(L.lib().rts_cube_detections_get(self.h, ptr(out), n.value, C.byref(n)))
+        return out[:n.value].copy()
+
+    def cube_plots(self, link=(1, 1), min_cells=1, pri=0.0, max_plots=0, device_list=None, n_list=0, n_doppler=0, fetch=True):
+        """rts_cube_plots + rts_cube_plots_get: the connected components of the handle's detection list (device_list None) or of a
+        caller-owned device array of n_list RtsDetection records on a map of n_doppler rows, one record per component; link is the
+        adjacency's reach (range, Doppler) in cells.  Detect without local_max first.  Returns a PLOT_DTYPE array in ascending
+        first_index."""
+        p = _plot_params(link, min_cells, pri, max_plots, device_list, n_list, n_doppler)
+        check(L.lib().rts_cube_plots(self.h, C.byref(p)))
+        return self.plots() if fetch else None
+
+    def plots(self):
+        """rts_cube_plots_get: the plots of the last cube_plots (every stored record; raises when max_plots cut them or the detection
+        list they were made from was truncated)"""
+        n = C.c_uint32(0)
+        rc = L.lib().rts_cube_plots_get(self.h, None, 0, C.byref(n))
+        if rc not in (L.RTS_OK, L.RTS_ERR_CAPACITY):
+            check(rc)
+        out = np.zeros(max(n.value, 1), L.PLOT_DTYPE)
+        check(L.lib().rts_cube_plots_get(self.h, ptr(out), n.value, C.byref(n)))
         return out[:n.value].copy()
 
     def cube_backproject(self, origin, step_x, step_y, n_x, n_y, tx_positions, rx_positions, cspeed, carrier, taps=8, first=0, count=None,

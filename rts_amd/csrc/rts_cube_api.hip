@@ -254,7 +254,7 @@ extern "C" int rts_cube_detect(RtsHandle c, const RtsCfarParams* p, const void* 
     if (p->mode != RTS_CFAR_CA && p->pfa != 0.0) { rts_set_error("rts_cube_detect: pfa is for mode RTS_CFAR_CA only (GO / SO take alpha)"); return RTS_ERR_INVALID; }
     if (p->mode != RTS_CFAR_CA && p->train_range == 0) { rts_set_error("rts_cube_detect: train_range = 0 with GO / SO (the halves are range halves)"); return RTS_ERR_INVALID; }
     { int rc = rts_cfar_pri_check("rts_cube_detect", p->pri); if (rc != RTS_OK) return rc; }
-    c->cube.det_valid = false;
+    c->cube.det_valid = false; c->cube.plot_valid = false;      // (plots index the list they were made from)
     return rts_cube_detect_device(c, *p, map, n_doppler, p->max_detections ? p->max_detections : RTS_CFAR_DEFAULT_MAX_DETECTIONS);
 }
 
@@ -322,7 +322,7 @@ extern "C" int rts_cube_detect_os(RtsHandle c, const RtsCfarOsParams* p, const v
     { int rc = rts_cfar_map(c, "rts_cube_detect_os", device_map, &map, &n_doppler); if (rc != RTS_OK) return rc; }
     const uint32_t nb = c->cube.params.n_bins;
     { int rc = rts_cfar_os_check(p, nb, n_doppler, "rts_cube_detect_os"); if (rc != RTS_OK) return rc; }
-    c->cube.det_valid = false;
+    c->cube.det_valid = false; c->cube.plot_valid = false;      // (plots index the list they were made from)
     // the alphas by training count -> pinned staging -> the device, on the stream (N0 + 1 <= RTS_CFAR_OS_MAX_TRAIN + 1: one size for every call);
     // a call that needs nothing the device table of the previous one lacks sends nothing
     const double* tab_dev = nullptr;
@@ -344,6 +344,88 @@ extern "C" int rts_cube_detect_os(RtsHandle c, const RtsCfarOsParams* p, const v
         tab_dev = s.os_alpha.dev.p;
     }
     return rts_cube_detect_os_device(c, *p, tab_dev, map, n_doppler, p->max_detections ? p->max_detections : RTS_CFAR_DEFAULT_MAX_DETECTIONS);
+}
+
+// ------------------------------------------------------------------------------------- plot extraction
+// (rts_amd.h: RtsPlotParams, RtsPlot; the rules and the host evaluator are rts_plot.h, shared with the kernels, rts_plot.hip)
+#define RTS_PLOT_MAX_LIST 0x40000000u      // the kernels index the list, the sort and the scan (one element more) with 32 bits
+static int rts_plot_check(const char* who, const RtsPlotParams* p)
+{
+    if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
+    switch (rts_plot_params_check(p)) {
+        case 0: return RTS_OK;
+        case 1: rts_set_error("%s: link_range = %u > %u (RTS_PLOT_MAX_LINK)", who, p->link_range, RTS_PLOT_MAX_LINK); break;
+        case 2: rts_set_error("%s: link_doppler = %u > %u (RTS_PLOT_MAX_LINK)", who, p->link_doppler, RTS_PLOT_MAX_LINK); break;
+        case 3: rts_set_error("%s: reserved fields must be 0", who); break;
+        case 4: rts_set_error("%s: pri = %g (finite, >= 0)", who, p->pri); break;
+        case 5: rts_set_error("%s: n_doppler = 0 with a device_list", who); break;
+        case 6: rts_set_error("%s: device_list is not 8-byte aligned", who); break;
+        default: rts_set_error("%s: n_list = %u, n_doppler = %u without a device_list (both 0: the handle's list brings its own)", who, p->n_list, p->n_doppler); break;
+    }
+    return RTS_ERR_INVALID;
+}
+
+extern "C" int rts_plots_eval(const RtsCubeParams* q, const RtsDetection* list, uint32_t n_list, uint32_t n_doppler, const RtsPlotParams* p, RtsPlot* out, uint32_t capacity, uint32_t* n_out)
+{
+    const char* who = "rts_plots_eval";
+    if (!q || q->n_rx == 0 || q->n_bins == 0 || !(q->dt > 0) || !std::isfinite(q->dt) || !std::isfinite(q->t0)) { rts_set_error("%s: bad cube parameters", who); return RTS_ERR_INVALID; }
+    { int rc = rts_plot_check(who, p); if (rc != RTS_OK) return rc; }
+    if (n_doppler == 0) { rts_set_error("%s: n_doppler = 0", who); return RTS_ERR_INVALID; }
+    if ((n_list && !list) || !n_out || (capacity && !out)) { rts_set_error("%s: null list or output", who); return RTS_ERR_INVALID; }
+    if (n_list > RTS_PLOT_MAX_LIST) { rts_set_error("%s: n_list = %u > %u", who, n_list, RTS_PLOT_MAX_LIST); return RTS_ERR_INVALID; }
+    uint32_t bad = 0;
+    switch (rts_plot_list_check(list, n_list, q->n_rx, n_doppler, q->n_bins, &bad)) {
+        case 0: break;
+        case 1: rts_set_error("%s: list[%u]: (rx, doppler_bin, range_bin) = (%u, %u, %u) outside the map of %u x %u x %u cells", who, bad, list[bad].rx, list[bad].doppler_bin, list[bad].range_bin,
+                              q->n_rx, n_doppler, q->n_bins); return RTS_ERR_INVALID;
+        default: rts_set_error("%s: list[%u] is not above list[%u] in flat (rx, doppler_bin, range_bin) order", who, bad, bad - 1u); return RTS_ERR_INVALID;
+    }
+    const uint32_t total = rts_plots_eval_host(q, list, n_list, n_doppler, p, out, capacity);
+    *n_out = total;
+    if (total > capacity) { rts_set_error("%s: %u of %u plots written (capacity %u)", who, capacity, total, capacity); return RTS_ERR_CAPACITY; }
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_plots(RtsHandle c, const RtsPlotParams* p)
+{
+    const char* who = "rts_cube_plots";
+    CHECK_HANDLE(c);
+    if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
+    CHECK_CLOSED(c);
+    NEED_CUBE(c, who, "no cube (call rts_cube_attach first)");
+    { int rc = rts_plot_check(who, p); if (rc != RTS_OK) return rc; }
+    RtsCubeState& s = c->cube;
+    const RtsDetection* list = (const RtsDetection*)p->device_list;
+    const uint32_t* n_dev = nullptr;
+    uint32_t n_cap = p->n_list, nd = p->n_doppler;
+    if (!list) {
+        if (!s.det_valid) { rts_set_error("%s: no detection list (rts_cube_detect, rts_cube_detect_os; a list ends at rts_cube_attach) and no device_list", who); return RTS_ERR_INVALID; }
+        list = s.d_det.p; n_dev = s.d_det_off.p + s.det_nseg; n_cap = s.det_max; nd = s.det_nd;
+    }
+    if (n_cap > RTS_PLOT_MAX_LIST) { rts_set_error("%s: a list of %u records > %u", who, n_cap, RTS_PLOT_MAX_LIST); return RTS_ERR_INVALID; }
+    s.plot_valid = false; s.plot_own_list = p->device_list == nullptr;
+    return rts_cube_plots_device(c, *p, list, n_dev, n_cap, nd, p->max_plots ? p->max_plots : n_cap);
+}
+
+extern "C" int rts_cube_plots_get(RtsHandle c, RtsPlot* out, uint32_t capacity, uint32_t* n_out)
+{
+    const char* who = "rts_cube_plots_get";
+    CHECK_HANDLE(c);
+    if (!n_out || (capacity && !out)) { rts_set_error("%s: null output", who); return RTS_ERR_INVALID; }
+    RtsCubeState& s = c->cube;
+    if (!s.plot_valid) { rts_set_error("%s: no plots (rts_cube_plots; plots end at rts_cube_detect, rts_cube_detect_os and rts_cube_attach)", who); return RTS_ERR_INVALID; }
+    RTS_HIP(hipStreamSynchronize(c->stream));
+    uint32_t total = 0, det_total = 0;
+    RTS_HIP(hipMemcpy(&total, s.d_plot_off.p + s.plot_cap, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (s.plot_own_list) RTS_HIP(hipMemcpy(&det_total, s.d_det_off.p + s.det_nseg, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    *n_out = total;
+    const uint32_t stored = total < s.plot_max ? total : s.plot_max;
+    const uint32_t n = stored < capacity ? stored : capacity;
+    if (n) RTS_HIP(hipMemcpy(out, s.d_plot.p, sizeof(RtsPlot) * n, hipMemcpyDeviceToHost));
+    if (n < total) { rts_set_error("%s: %u of %u plots copied (max_plots %u, capacity %u)", who, n, total, s.plot_max, capacity); return RTS_ERR_CAPACITY; }
+    if (s.plot_own_list && det_total > s.det_max) {
+        rts_set_error("%s: the detection list was truncated (%u of %u detections stored): the %u plots describe the stored prefix", who, s.det_max, det_total, total); return RTS_ERR_CAPACITY; }
+    return RTS_OK;
 }
 
 // ------------------------------------------------------------------------------------- tapered slow-time spectrogram

@@ -144,7 +144,7 @@ static int rts_cfar_launch(RtsContext* c, const char* who, const Params& p, cons
     RTS_HIP(rocprim::exclusive_scan(s.d_det_tmp.p, tmp, s.d_det_cnt.p, s.d_det_off.p, 0u, n_seg + 1, rocprim::plus<uint32_t>(), c->stream));
     k_write<<<grid, RTS_CFAR_THREADS, lds, c->stream>>>(a);
     RTS_HIP(hipGetLastError());
-    s.det_nseg = (uint32_t)n_seg; s.det_max = max_det; s.det_valid = true;
+    s.det_nseg = (uint32_t)n_seg; s.det_max = max_det; s.det_nd = n_doppler; s.det_valid = true;
     return RTS_OK;
 }
 

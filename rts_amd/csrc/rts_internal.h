@@ -20,6 +20,7 @@
 #include "rts_stap.h"             // space-time adaptive processing: the stacked snapshot, its covariance's and filter's evaluators, the host-only plan of the filter's launch
 #include "rts_doa.h"              // direction finding: the eigensolver's and the angular scan's trees, the spectra's weights, the source count, their evaluators and the host-only plans of their launches
 #include "rts_cfar_os.h"          // CFAR: what every detector shares (rts_cfar.h: window, training count, local maximum, refinement, record); OS: rank rule, alphas, the host evaluator
+#include "rts_plot.h"             // plot extraction: key, unwrap, adjacency, neighbour intervals, the blocked sums, the record, the validation, the host evaluator
 #include "rts_owned.h"            // DevBuf, PinBuf, StagedUpload: device and pinned host memory that frees itself
 #include "rts_launch_plan.h"      // RTS_BLOCK, RTS_WTILE, RTS_COOP_GROUP, RTS_STACK_OVF and the host arithmetic of a launch
 #include "rts_post_plan.h"        // RTS_SMALL_CAP32 / 64, RTS_AGG_TILE and the host arithmetic of the post-processing
@@ -83,6 +84,7 @@ struct __attribute__((aligned(16))) RtsEndRecord {
 };
 static_assert(sizeof(RtsEndRecord) == 112, "end record size");
 static_assert(sizeof(RtsDetection) == 72 && sizeof(RtsCfarParams) == 72 && sizeof(RtsCfarOsParams) == 72, "CFAR ABI sizes (rts_amd/_lib.py mirrors them)");
+static_assert(sizeof(RtsPlot) == 104 && sizeof(RtsPlotParams) == 56, "plot ABI sizes (rts_amd/_lib.py mirrors them)");
 // RtsEndRecord::pad : bits 0-1 chain (output row = chain * n + slot), 2-3 refrDepth, 8-15 (target + 1) of chain 0's
 // refraction (path prefill of rows >= 3), 16-17 children spawned
 
@@ -305,6 +307,14 @@ struct RtsCubeState {
     // CFAR detection (rts_cube_detect, rts_detect.hip): per-segment counts -> exclusive scan (offsets; element n_seg: the total),
     // the records of the last detection and how many it may hold; det_valid: a list exists for rts_cube_detections_get
     DevBuf<uint32_t> d_det_cnt, d_det_off; DevBuf<uint8_t> d_det_tmp; DevBuf<RtsDetection> d_det; uint32_t det_nseg = 0, det_max = 0; bool det_valid = false;
+    uint32_t det_nd = 0;                                  // the Doppler rows of the map the list was detected on (rts_cube_plots without a list of its own)
+    // plot extraction (rts_cube_plots, rts_plot.hip): flat keys, the parent array of the union (afterwards every element's component
+    // minimum), the identity, (label, index) sorted by label, per head its member count, keep flags -> exclusive scan (offsets;
+    // element plot_cap: the total), the sort's and the scan's scratch, the records.  plot_cap: the list capacity the launches were
+    // sized by, plot_max: the records d_plot may hold; plot_valid: plots exist for rts_cube_plots_get; plot_own_list: they were made
+    // from the handle's detection list (whose truncation rts_cube_plots_get reports)
+    DevBuf<uint64_t> d_plot_key; DevBuf<uint32_t> d_plot_parent, d_plot_idx, d_plot_lab_s, d_plot_idx_s, d_plot_len, d_plot_flag, d_plot_off; DevBuf<uint8_t> d_plot_tmp;
+    DevBuf<RtsPlot> d_plot; uint32_t plot_cap = 0, plot_max = 0; bool plot_valid = false, plot_own_list = false;
     // OS-CFAR (rts_cube_detect_os): the alphas by training count go through a staged upload; os_tab keeps them on the host for the next
     // call with the same window, rank and pfa (os_tab_key), so that only training counts not seen yet are solved for; os_tab_sent: the
     // device holds os_tab as it stands
@@ -343,7 +353,7 @@ struct RtsCubeState {
     StagedUpload<double> doa_g;
     // every product belongs to the cube it was made from: the Doppler map (which rts_cube_detect may take), the detection list, the image
     // the spectrogram, the range transform, the beams, the covariance, the adaptive weights, the space-time filter's output, the eigenpairs and the angular spectrum end when another cube is attached
-    void end_products() { doppler.valid = false; det_valid = false; image.valid = false; stft.valid = false; range.valid = false; beam.valid = false; cov.valid = false; mvdr.valid = false; st.valid = false;
+    void end_products() { doppler.valid = false; det_valid = false; plot_valid = false; image.valid = false; stft.valid = false; range.valid = false; beam.valid = false; cov.valid = false; mvdr.valid = false; st.valid = false;
                           eig_val.valid = false; eig_vec.valid = false; doa.valid = false; }
 };
 
@@ -478,6 +488,8 @@ int rts_cube_compress_device(RtsContext* c, uint32_t first_pulse, uint32_t n_pul
 int rts_cube_noise_device(RtsContext* c, uint32_t first_pulse, uint32_t n_pulses, double sigma, uint64_t seed);          // rts_detect.hip
 int rts_cube_detect_device(RtsContext* c, const RtsCfarParams& p, const double* map, uint32_t n_doppler, uint32_t max_det);
 int rts_cube_detect_os_device(RtsContext* c, const RtsCfarOsParams& p, const double* alpha_tab, const double* map, uint32_t n_doppler, uint32_t max_det);      // alpha_tab: device, by training count (pfa), or null (p.alpha)
+// rts_plot.hip.  list: n_cap records, of which the first min(n_cap, *n_dev) count (n_dev null: all n_cap)
+int rts_cube_plots_device(RtsContext* c, const RtsPlotParams& p, const RtsDetection* list, const uint32_t* n_dev, uint32_t n_cap, uint32_t n_doppler, uint32_t max_plots);
 int rts_cube_doppler_device(RtsContext* c, uint32_t n_fft, double* out);      // rts_stft.hip: the slow-time transforms
 int rts_cube_stft_device(RtsContext* c, const RtsStftParams& p, const RtsStftPlan& plan, const double* window, double* out);
 int rts_cube_beat_device(RtsContext* c, uint32_t pulse_index, const RtsBeatParams& p, const RtsBeatPlan& plan, double cspeed, double carrier, int64_t base);      // rts_beat.hip
