@@ -659,6 +659,113 @@ int rts_cube_plots_get(RtsHandle h, RtsPlot* out, uint32_t capacity, uint32_t* n
 int rts_plots_eval(const RtsCubeParams* q, const RtsDetection* list, uint32_t n_list, uint32_t n_doppler,
                    const RtsPlotParams* p, RtsPlot* out, uint32_t capacity, uint32_t* n_out);   /* pure host */
 
+/* ---------------------------------------------------------------- tracking: plots associated and filtered across coherent intervals
+ * A plot belongs to one interval.  rts_cube_track advances a per-handle TRACK TABLE by one frame of plots, on the device and without
+ * waiting on the host: per receiver a two-state Kalman filter in the plots' own coordinates (delay in seconds, Doppler in hertz),
+ * gated global-nearest-neighbour association with a deterministic matching, a confirm / coast / delete lifecycle, and new tracks
+ * from the plots nobody took.  The rules are rts_amd/csrc/rts_track.h, shared by the kernels (rts_track.hip) and the host evaluator
+ * rts_tracks_eval, which agree bit for bit on every field.  All arithmetic is IEEE double, every product and quotient rounded on its
+ * own (no contraction), in exactly the operand order written here; parentheses are evaluation order.
+ *   Input: a plot list whose rx is non-decreasing -- what rts_cube_plots writes.  device_plots NULL: the handle's plots, the first
+ *     min(total, stored) records, the count read on the device.  Otherwise a caller-owned DEVICE array of n_plots RtsPlot; it is taken
+ *     as given: a list that breaks the rule makes the tracks unspecified, but nothing outside the list and the track buffers is
+ *     touched.  Only rx, delay, doppler and power_sum are read.  A plot whose delay or doppler is not finite neither associates nor
+ *     starts a track.  rts_tracks_eval refuses a list whose rx decreases.
+ *   Time: T = time - the time of the previous frame (or of rts_cube_tracks_set).  The table HAS A TIME from the first rts_cube_track
+ *     or an rts_cube_tracks_set of n > 0 tracks until rts_cube_tracks_reset or an rts_cube_tracks_set of none; while it has one, T
+ *     must be positive and finite.  rts_tracks_eval takes T itself and asks the same when n_in > 0.
+ *   Model, per track with state (d, f) and covariance (p_dd, p_df, p_ff), k = delay_rate_per_hz, a = k T.  A closing range gives a
+ *     positive Doppler (the CFAR section), so the caller passes k = -1 / carrier; k = 0 decouples the axes.
+ *       d- = d + a f;   f- = f
+ *       u = p_df + a p_ff                                   (the off-diagonal after the first product F P)
+ *       pdd- = ((p_dd + a p_df) + a u) + q (((a a) T) / 3)
+ *       pdf- = u + q ((a T) / 2)
+ *       pff- = p_ff + q T
+ *       s_dd = pdd- + sigma_delay sigma_delay;   s_df = pdf-;   s_ff = pff- + sigma_doppler sigma_doppler
+ *       det = s_dd s_ff - s_df s_df
+ *   Innovation of plot (z_d, z_f):  v_d = z_d - d-;  v_f = wrap(z_f - f-).  wrap(x) with P = doppler_period > 0 and h = 0.5 P:
+ *       r = x - P floor((x + h) / P);  then r - P if r >= h, r + P if r < -h (the rounding cases), so r lies in [-h, h).
+ *     doppler_period = 0: wrap(x) = x.
+ *       d2 = ((((v_d v_d) s_ff) - ((2 (v_d v_f)) s_df)) + ((v_f v_f) s_dd)) / det
+ *   Gate: track i and plot j are an EDGE when they have the same rx, the plot is finite, and 0 <= d2 <= gate (a negative or NaN d2
+ *     needs a covariance that is not positive semi-definite, which rts_cube_tracks_set refuses at its diagonal).  No cheaper
+ *     pre-test stands in front of that expression.  Each track keeps its max_candidates (1 .. RTS_TRACK_MAX_CAND) edges of smallest
+ *     (d2, plot index); the others are dropped BEFORE the matching.
+ *   Matching: the greedy pass over the kept edges in ascending (d2, track index, plot index): an edge is taken when both its ends
+ *     are free.  The device reaches the same matching by rounds of locally dominant edges (rts_track.hip) and ends the rounds itself.
+ *   Update of a matched track, with K = P- S^-1:
+ *       k_dd = ((pdd- s_ff) - (pdf- s_df)) / det;   k_df = ((pdf- s_dd) - (pdd- s_df)) / det
+ *       k_fd = ((pdf- s_ff) - (pff- s_df)) / det;   k_ff = ((pff- s_dd) - (pdf- s_df)) / det
+ *       d = d- + ((k_dd v_d) + (k_df v_f));   f = wrap(f- + ((k_fd v_d) + (k_ff v_f)))
+ *       p_dd = pdd- - ((k_dd pdd-) + (k_df pdf-));  p_df = pdf- - ((k_dd pdf-) + (k_df pff-))  (once);  p_ff = pff- - ((k_fd pdf-) + (k_ff pff-))
+ *     hits + 1, misses = 0, plot_index = j, d2 as above, power_sum the plot's.  RTS_TRACK_CONFIRMED is set once hits >=
+ *     confirm_hits and stays set.
+ *   An unmatched track COASTS: state and covariance become the prediction (d-, f-, pdd-, pdf-, pff-), misses + 1, RTS_TRACK_COASTED,
+ *     plot_index = 0xffffffff, d2 = 0, power_sum = 0.  It is deleted when misses then exceeds max_misses (confirmed) or
+ *     tentative_misses (not).  age + 1 in both cases; RTS_TRACK_COASTED and RTS_TRACK_NEW describe this frame only.
+ *   Each finite plot no track took starts a track: state (delay, wrap(doppler)), covariance diag(sigma_delay sigma_delay,
+ *     sigma_doppler sigma_doppler), hits 1, misses 0, age 1, RTS_TRACK_NEW (and RTS_TRACK_CONFIRMED when confirm_hits is 1),
+ *     plot_index = j, d2 = 0, power_sum the plot's.
+ *   Order and ids: the surviving tracks in their previous order, then the new ones in ascending plot index, with ids next_id,
+ *     next_id + 1, .. in that order (uint64, per handle; rts_cube_tracks_reset does not rewind them).  Positions come from flags and
+ *     a scan, never from atomics: two runs give the same bytes.  The table holds max_tracks records (0: RTS_TRACK_DEFAULT_TRACKS, at
+ *     most RTS_TRACK_MAX_TRACKS): when it is full the survivors are kept, new tracks are stored in order until it is full, only
+ *     stored tracks consume ids, and rts_cube_tracks_get returns RTS_ERR_CAPACITY.
+ *   Lifetime: tracks span cubes.  They survive rts_cube_attach, the detect calls and rts_cube_plots, and end at
+ *     rts_cube_tracks_reset and rts_destroy.  The step copies what it needs of the plots when it runs: the table does not refer to
+ *     the plot buffers.  rts_cube_tracks_get synchronises, sets *n_out to the total (stored tracks plus the new ones a full table
+ *     turned away) and *next_id_out, and copies min(stored, capacity) records; RTS_ERR_CAPACITY when that is fewer than the total.
+ *     An empty table is 0 tracks, not an error.  rts_cube_tracks_set waits for the handle's stream and loads n tracks, next_id and
+ *     the time they stand at; the next rts_cube_track chooses max_tracks anew (at least n).
+ *   rts_tracks_eval: pure host, one step as a function: in[n_in], next_id and T to out (up to `capacity` records), *n_out (the
+ *     total) and *next_id_out; the table it models holds p->max_tracks records.  device_plots and n_plots are validated and
+ *     otherwise ignored.
+ *   RTS_ERR_INVALID, the message naming the field, outputs and table untouched: gate, sigma_delay, sigma_doppler not finite or not
+ *     positive; q negative or not finite; delay_rate_per_hz not finite; doppler_period negative or not finite; confirm_hits 0;
+ *     max_candidates 0 or above RTS_TRACK_MAX_CAND; max_tracks above RTS_TRACK_MAX_TRACKS, changed since the previous
+ *     rts_cube_track, or below the tracks loaded; no plots and no device_plots; n_plots without device_plots or above
+ *     RTS_TRACK_MAX_PLOTS; device_plots not 8-byte aligned; nonzero reserved fields; T not positive and finite.
+ *     rts_cube_tracks_set and rts_tracks_eval refuse a track whose state or covariance is not finite, whose p_dd or p_ff is
+ *     negative, or whose flags hold unknown bits, and more tracks than the table holds. */
+#define RTS_TRACK_MAX_CAND 16u
+#define RTS_TRACK_MAX_TRACKS 65536u
+#define RTS_TRACK_DEFAULT_TRACKS 16384u
+#define RTS_TRACK_MAX_PLOTS 16777216u
+#define RTS_TRACK_CONFIRMED 1u
+#define RTS_TRACK_COASTED 2u      /* no plot this frame */
+#define RTS_TRACK_NEW 4u          /* started this frame */
+typedef struct RtsTrackParams {
+    double gate;                         /* d2 <= gate associates (9.21: 99 % of a 2-degree-of-freedom chi-square)     */
+    double sigma_delay, sigma_doppler;   /* measurement standard deviations, s and Hz, > 0                             */
+    double q;                            /* Doppler random-walk intensity, Hz^2 / s, >= 0                              */
+    double delay_rate_per_hz;            /* k: d(delay)/dt per hertz of Doppler; -1 / carrier by the library's signs   */
+    double doppler_period;               /* Doppler is circular with this period (1 / pri); 0: not circular            */
+    uint32_t confirm_hits;               /* >= 1                                                                       */
+    uint32_t max_misses;                 /* a confirmed track is deleted when misses exceeds this                      */
+    uint32_t tentative_misses;           /* ... a tentative one when misses exceeds this                               */
+    uint32_t max_candidates;             /* 1 .. RTS_TRACK_MAX_CAND edges kept per track                               */
+    uint32_t max_tracks;                 /* table size; 0: RTS_TRACK_DEFAULT_TRACKS                                    */
+    uint32_t n_plots;                    /* with device_plots: its length; else 0                                      */
+    const void* device_plots;            /* NULL: the handle's plots; else caller-owned DEVICE RtsPlot[]               */
+    uint64_t reserved[2];                /* 0 */
+} RtsTrackParams;                                             /* 96 bytes */
+typedef struct RtsTrack {
+    uint64_t id;
+    uint32_t rx, flags;                                       /* RTS_TRACK_*                                              */
+    uint32_t hits, misses, age, plot_index;                   /* plot_index: matched or initiating plot, 0xffffffff none  */
+    double delay, doppler;                                    /* the state: s, Hz                                         */
+    double p_dd, p_df, p_ff;                                  /* its covariance                                           */
+    double d2, power_sum;                                     /* of this frame's match (0 when coasting)                  */
+} RtsTrack;                                                   /* 88 bytes */
+int rts_cube_track(RtsHandle h, const RtsTrackParams* p, double time);
+int rts_cube_tracks_get(RtsHandle h, RtsTrack* out, uint32_t capacity, uint32_t* n_out, uint64_t* next_id_out);
+int rts_cube_tracks_set(RtsHandle h, const RtsTrack* tracks, uint32_t n, uint64_t next_id, double time);
+int rts_cube_tracks_reset(RtsHandle h);
+int rts_cube_track_rounds(RtsHandle h, uint32_t* rounds);   /* diagnostic: rounds the last step's matching took; synchronises */
+int rts_tracks_eval(const RtsTrackParams* p, const RtsTrack* in, uint32_t n_in, uint64_t next_id, double T,
+                    const RtsPlot* plots, uint32_t n_plots, RtsTrack* out, uint32_t capacity, uint32_t* n_out,
+                    uint64_t* next_id_out);                                                      /* pure host */
+
 /* ---------------------------------------------------------------- tapered slow-time spectrogram (STFT) of the return cube
  * The short-time Fourier transform over the pulse axis, per range gate bin or summed over a gate: how Doppler changes INSIDE the
  * interval (rotor and blade flashes, tumbling bodies), where rts_cube_doppler's single rectangular DFT smears it into a band.  A

@@ -143,6 +143,22 @@ PLOT_DTYPE = np.dtype([("rx", "<u4"), ("n_cells", "<u4"), ("first_index", "<u4")
                        ("doppler_spread", "<f8"), ("delay", "<f8"), ("doppler", "<f8")])
 assert PLOT_DTYPE.itemsize == 104 and C.sizeof(RtsPlotParams) == 56
 
+RTS_TRACK_MAX_CAND, RTS_TRACK_MAX_TRACKS, RTS_TRACK_DEFAULT_TRACKS, RTS_TRACK_MAX_PLOTS = 16, 65536, 16384, 16777216
+RTS_TRACK_CONFIRMED, RTS_TRACK_COASTED, RTS_TRACK_NEW = 1, 2, 4
+
+
+class RtsTrackParams(C.Structure):
+    _fields_ = [("gate", C.c_double), ("sigma_delay", C.c_double), ("sigma_doppler", C.c_double), ("q", C.c_double),
+                ("delay_rate_per_hz", C.c_double), ("doppler_period", C.c_double), ("confirm_hits", C.c_uint32), ("max_misses", C.c_uint32),
+                ("tentative_misses", C.c_uint32), ("max_candidates", C.c_uint32), ("max_tracks", C.c_uint32), ("n_plots", C.c_uint32),
+                ("device_plots", C.c_void_p), ("reserved", C.c_uint64 * 2)]
+
+
+# RtsTrack (include/rts_amd.h), 88 bytes
+TRACK_DTYPE = np.dtype([("id", "<u8"), ("rx", "<u4"), ("flags", "<u4"), ("hits", "<u4"), ("misses", "<u4"), ("age", "<u4"), ("plot_index", "<u4"),
+                        ("delay", "<f8"), ("doppler", "<f8"), ("p_dd", "<f8"), ("p_df", "<f8"), ("p_ff", "<f8"), ("d2", "<f8"), ("power_sum", "<f8")])
+assert TRACK_DTYPE.itemsize == 88 and C.sizeof(RtsTrackParams) == 96
+
 
 RTS_IMAGE_ACCUMULATE, RTS_IMAGE_PULSE_CHUNK, RTS_IMAGE_MAX_PIXELS = 1, 64, 16777216
 
@@ -349,6 +365,7 @@ EXPORTS = ["rts_create", "rts_destroy", "rts_last_error", "rts_device_count", "r
            "rts_cube_add_noise", "rts_noise_eval", "rts_cube_detect", "rts_cube_detections_get",
            "rts_cube_detect_os", "rts_cfar_os_alpha", "rts_cfar_os_eval",
            "rts_cube_plots", "rts_cube_plots_get", "rts_plots_eval",
+           "rts_cube_track", "rts_cube_tracks_get", "rts_cube_tracks_set", "rts_cube_tracks_reset", "rts_cube_track_rounds", "rts_tracks_eval",
            "rts_cube_backproject", "rts_cube_image_get", "rts_backproject_eval",
            "rts_cube_spectrogram", "rts_cube_spectrogram_get", "rts_stft_eval", "rts_window_make",
            "rts_cube_render_beat", "rts_beat_eval", "rts_cube_range_transform", "rts_cube_range_get", "rts_range_eval",
@@ -434,6 +451,12 @@ def lib():
         "rts_cube_plots": [vp, C.POINTER(RtsPlotParams)],
         "rts_cube_plots_get": [vp, vp, u32, C.POINTER(u32)],
         "rts_plots_eval": [C.POINTER(RtsCubeParams), vp, u32, u32, C.POINTER(RtsPlotParams), vp, u32, C.POINTER(u32)],
+        "rts_cube_track": [vp, C.POINTER(RtsTrackParams), C.c_double],
+        "rts_cube_tracks_get": [vp, vp, u32, C.POINTER(u32), C.POINTER(u64)],
+        "rts_cube_tracks_set": [vp, vp, u32, u64, C.c_double],
+        "rts_cube_tracks_reset": [vp],
+        "rts_cube_track_rounds": [vp, C.POINTER(u32)],
+        "rts_tracks_eval": [C.POINTER(RtsTrackParams), vp, u32, u64, C.c_double, vp, u32, vp, u32, C.POINTER(u32), C.POINTER(u64)],
         "rts_cube_backproject": [vp, C.POINTER(RtsImageParams), vp],
         "rts_cube_image_get": [vp, vp, u64],
         "rts_backproject_eval": [C.POINTER(RtsCubeParams), vp, C.POINTER(RtsImageParams), vp],

@@ -280,6 +280,36 @@ def plots_eval(detections, n_doppler, link=(1, 1), min_cells=1, pri=0.0, t0=0.0,
     return out[:n.value].copy()
 
 
+# ------------------------------------------------------------------------------- tracking (rts_track.h)
+def _track_params(gate, sigma, q, delay_rate_per_hz, doppler_period, confirm_hits, max_misses, tentative_misses, max_candidates, max_tracks=0,
+                  device_plots=None, n_plots=0):
+    """RtsTrackParams; sigma is the measurement standard deviation (delay in s, Doppler in Hz)"""
+    p = L.RtsTrackParams()
+    p.gate, p.q, p.delay_rate_per_hz, p.doppler_period = float(gate), float(q), float(delay_rate_per_hz), float(doppler_period)
+    p.sigma_delay, p.sigma_doppler = (float(x) for x in sigma)
+    p.confirm_hits, p.max_misses, p.tentative_misses = int(confirm_hits), int(max_misses), int(tentative_misses)
+    p.max_candidates, p.max_tracks, p.n_plots = int(max_candidates), int(max_tracks), int(n_plots)
+    p.device_plots = C.c_void_p(device_plots) if device_plots else None
+    return p
+
+
+def tracks_eval(tracks, next_id, T, plots, sigma, gate=9.21, q=0.0, delay_rate_per_hz=0.0, doppler_period=0.0, confirm_hits=3, max_misses=3,
+                tentative_misses=0, max_candidates=L.RTS_TRACK_MAX_CAND, max_tracks=0):
+    """rts_tracks_eval (pure host): one tracker step as a function -- the TRACK_DTYPE table `tracks` carried over the interval T and
+    associated with the PLOT_DTYPE list `plots` (rx non-decreasing).  Returns (the stored tracks, next_id): survivors in their order,
+    then the new tracks in ascending plot index; a full table (max_tracks) keeps the prefix."""
+    t = np.ascontiguousarray(np.asarray(tracks, L.TRACK_DTYPE))
+    z = np.ascontiguousarray(np.asarray(plots, L.PLOT_DTYPE))
+    p = _track_params(gate, sigma, q, delay_rate_per_hz, doppler_period, confirm_hits, max_misses, tentative_misses, max_candidates, max_tracks)
+    out = np.zeros(max(len(t) + len(z), 1), L.TRACK_DTYPE)
+    n, nid = C.c_uint32(0), C.c_uint64(0)
+    rc = L.lib().rts_tracks_eval(C.byref(p), ptr(t) if len(t) else None, len(t), int(next_id), float(T), ptr(z) if len(z) else None, len(z),
+                                 ptr(out), len(out), C.byref(n), C.byref(nid))
+    if rc != L.RTS_ERR_CAPACITY:
+        check(rc)
+    return out[:min(n.value, max_tracks or L.RTS_TRACK_DEFAULT_TRACKS)].copy(), nid.value
+
+
 # ------------------------------------------------------------------------------- backprojection imaging (rts_image.h)
 def _image_params(origin, step_x, step_y, n_x, n_y, tx_positions, rx_positions, cspeed, carrier, taps, first, count, weights, accumulate, n_rx):
     """RtsImageParams and the arrays it points to (keep them alive for the call).  tx_positions [P][3]; rx_positions [n_rx][P][3]
@@ -1277,6 +1307,35 @@ class Tracer:
         out = np.zeros(max(n.value, 1), L.PLOT_DTYPE)
         check(L.lib().rts_cube_plots_get(self.h, ptr(out), n.value, C.byref(n)))
         return out[:n.value].copy()
+
+    def cube_track(self, time, sigma, gate=9.21, q=0.0, delay_rate_per_hz=0.0, doppler_period=0.0, confirm_hits=3, max_misses=3, tentative_misses=0,
+                   max_candidates=L.RTS_TRACK_MAX_CAND, max_tracks=0, device_plots=None, n_plots=0, fetch=True):
+        """rts_cube_track + rts_cube_tracks_get: the handle's track table advanced by the frame at `time` -- the handle's plots
+        (device_plots None) or a caller-owned device array of n_plots RtsPlot records; sigma is the measurement standard deviation
+        (delay in s, Doppler in Hz).  Never waits on the host unless fetch.  Returns (the TRACK_DTYPE table, next_id) when fetch."""
+        p = _track_params(gate, sigma, q, delay_rate_per_hz, doppler_period, confirm_hits, max_misses, tentative_misses, max_candidates, max_tracks,
+                          device_plots, n_plots)
+        check(L.lib().rts_cube_track(self.h, C.byref(p), float(time)))
+        return self.tracks() if fetch else None
+
+    def tracks(self):
+        """rts_cube_tracks_get: (the stored tracks, next_id); raises when a full table turned new tracks away"""
+        n, nid = C.c_uint32(0), C.c_uint64(0)
+        rc = L.lib().rts_cube_tracks_get(self.h, None, 0, C.byref(n), C.byref(nid))
+        if rc not in (L.RTS_OK, L.RTS_ERR_CAPACITY):
+            check(rc)
+        out = np.zeros(max(n.value, 1), L.TRACK_DTYPE)
+        check(L.lib().rts_cube_tracks_get(self.h, ptr(out), n.value, C.byref(n), C.byref(nid)))
+        return out[:n.value].copy(), nid.value
+
+    def cube_tracks_set(self, tracks, next_id, time):
+        """rts_cube_tracks_set: loads a TRACK_DTYPE table, the next id and the time the tracks stand at (waits for the handle's stream)"""
+        t = np.ascontiguousarray(np.asarray(tracks, L.TRACK_DTYPE))
+        check(L.lib().rts_cube_tracks_set(self.h, ptr(t) if len(t) else None, len(t), int(next_id), float(time)))
+
+    def cube_tracks_reset(self):
+        """rts_cube_tracks_reset: an empty table without a time; ids go on where they were"""
+        check(L.lib().rts_cube_tracks_reset(self.h))
 
     def cube_backproject(self, origin, step_x, step_y, n_x, n_y, tx_positions, rx_positions, cspeed, carrier, taps=8, first=0, count=None,
                          weights=None, accumulate=False, device_ptr=None, fetch=True):

@@ -428,6 +428,156 @@ extern "C" int rts_cube_plots_get(RtsHandle c, RtsPlot* out, uint32_t capacity, 
     return RTS_OK;
 }
 
+// ------------------------------------------------------------------------------------- tracking
+// (rts_amd.h: RtsTrackParams, RtsTrack; the rules and the host evaluator are rts_track.h, shared with the kernels, rts_track.hip)
+static int rts_track_check(const char* who, const RtsTrackParams* p)
+{
+    if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
+    switch (rts_track_params_check(p)) {
+        case 0: return RTS_OK;
+        case 1: rts_set_error("%s: gate = %g (finite, > 0)", who, p->gate); break;
+        case 2: rts_set_error("%s: sigma_delay = %g (finite, > 0)", who, p->sigma_delay); break;
+        case 3: rts_set_error("%s: sigma_doppler = %g (finite, > 0)", who, p->sigma_doppler); break;
+        case 4: rts_set_error("%s: q = %g (finite, >= 0)", who, p->q); break;
+        case 5: rts_set_error("%s: delay_rate_per_hz = %g (finite)", who, p->delay_rate_per_hz); break;
+        case 6: rts_set_error("%s: doppler_period = %g (finite, >= 0)", who, p->doppler_period); break;
+        case 7: rts_set_error("%s: confirm_hits = 0", who); break;
+        case 8: rts_set_error("%s: max_candidates = %u (1 .. %u, RTS_TRACK_MAX_CAND)", who, p->max_candidates, RTS_TRACK_MAX_CAND); break;
+        case 9: rts_set_error("%s: max_tracks = %u > %u (RTS_TRACK_MAX_TRACKS)", who, p->max_tracks, RTS_TRACK_MAX_TRACKS); break;
+        case 10: rts_set_error("%s: reserved fields must be 0", who); break;
+        case 11: rts_set_error("%s: n_plots = %u without device_plots", who, p->n_plots); break;
+        case 12: rts_set_error("%s: n_plots = %u > %u (RTS_TRACK_MAX_PLOTS)", who, p->n_plots, RTS_TRACK_MAX_PLOTS); break;
+        default: rts_set_error("%s: device_plots is not 8-byte aligned", who); break;
+    }
+    return RTS_ERR_INVALID;
+}
+static int rts_track_table_refuse(const char* who, const RtsTrack* t, uint32_t n)
+{
+    uint32_t bad = 0;
+    switch (rts_track_table_check(t, n, &bad)) {
+        case 0: return RTS_OK;
+        case 1: rts_set_error("%s: tracks[%u]: delay, doppler, p_dd, p_df, p_ff must be finite and p_dd, p_ff not negative", who, bad); break;
+        default: rts_set_error("%s: tracks[%u]: unknown flags 0x%x", who, bad, t[bad].flags); break;
+    }
+    return RTS_ERR_INVALID;
+}
+
+extern "C" int rts_tracks_eval(const RtsTrackParams* p, const RtsTrack* in, uint32_t n_in, uint64_t next_id, double T, const RtsPlot* plots, uint32_t n_plots,
+                               RtsTrack* out, uint32_t capacity, uint32_t* n_out, uint64_t* next_id_out)
+{
+    const char* who = "rts_tracks_eval";
+    { int rc = rts_track_check(who, p); if (rc != RTS_OK) return rc; }
+    if ((n_in && !in) || (n_plots && !plots) || !n_out || !next_id_out || (capacity && !out)) { rts_set_error("%s: null tracks, plots or output", who); return RTS_ERR_INVALID; }
+    if (n_in > rts_track_table_size(*p)) { rts_set_error("%s: n_in = %u tracks > max_tracks = %u", who, n_in, rts_track_table_size(*p)); return RTS_ERR_INVALID; }
+    if (n_plots > RTS_TRACK_MAX_PLOTS) { rts_set_error("%s: n_plots = %u > %u (RTS_TRACK_MAX_PLOTS)", who, n_plots, RTS_TRACK_MAX_PLOTS); return RTS_ERR_INVALID; }
+    if (n_in && !rts_track_interval_ok(T)) { rts_set_error("%s: T = %g with tracks (positive, finite)", who, T); return RTS_ERR_INVALID; }
+    { int rc = rts_track_table_refuse(who, in, n_in); if (rc != RTS_OK) return rc; }
+    uint32_t bad = 0;
+    if (rts_track_plots_check(plots, n_plots, &bad)) { rts_set_error("%s: plots[%u].rx = %u is below plots[%u].rx = %u (rx must not decrease)", who, bad, plots[bad].rx, bad - 1u, plots[bad - 1u].rx); return RTS_ERR_INVALID; }
+    const uint32_t total = rts_tracks_eval_host(p, in, n_in, next_id, T, plots, n_plots, out, capacity, next_id_out);
+    *n_out = total;
+    const uint32_t table = rts_track_table_size(*p), stored = total < table ? total : table, n = stored < capacity ? stored : capacity;
+    if (n < total) { rts_set_error("%s: %u of %u tracks written (max_tracks %u, capacity %u)", who, n, total, table, capacity); return RTS_ERR_CAPACITY; }
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_track(RtsHandle c, const RtsTrackParams* p, double time)
+{
+    const char* who = "rts_cube_track";
+    CHECK_HANDLE(c);
+    if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
+    CHECK_CLOSED(c);
+    { int rc = rts_track_check(who, p); if (rc != RTS_OK) return rc; }
+    RtsCubeState& s = c->cube;
+    const uint32_t table = rts_track_table_size(*p);
+    if (s.trk_max && table != s.trk_max) { rts_set_error("%s: max_tracks = %u, the table was made with %u (rts_cube_tracks_reset first)", who, table, s.trk_max); return RTS_ERR_INVALID; }
+    if (table < s.trk_loaded) { rts_set_error("%s: max_tracks = %u below the %u tracks loaded", who, table, s.trk_loaded); return RTS_ERR_INVALID; }
+    if (!rts_track_finite(time)) { rts_set_error("%s: time = %g (finite)", who, time); return RTS_ERR_INVALID; }
+    const double T = s.trk_live ? time - s.trk_time : 0.0;
+    if (s.trk_live && !rts_track_interval_ok(T)) { rts_set_error("%s: T = time - the previous frame's = %g (positive, finite)", who, T); return RTS_ERR_INVALID; }
+    const RtsPlot* list = (const RtsPlot*)p->device_plots;
+    const uint32_t* n_dev = nullptr;
+    uint32_t pcap = p->n_plots;
+    if (!list) {
+        if (!s.plot_valid) { rts_set_error("%s: no plots (rts_cube_plots; plots end at the detect calls and rts_cube_attach) and no device_plots", who); return RTS_ERR_INVALID; }
+        list = s.d_plot.p; n_dev = s.d_plot_off.p + s.plot_cap; pcap = s.plot_max;
+        if (pcap > RTS_TRACK_MAX_PLOTS) { rts_set_error("%s: a plot list of %u records > %u (RTS_TRACK_MAX_PLOTS)", who, pcap, RTS_TRACK_MAX_PLOTS); return RTS_ERR_INVALID; }
+    }
+    { int rc = rts_cube_track_device(c, *p, T, list, n_dev, pcap, table); if (rc != RTS_OK) return rc; }
+    s.trk_max = table; s.trk_loaded = 0; s.trk_live = true; s.trk_time = time;
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_tracks_get(RtsHandle c, RtsTrack* out, uint32_t capacity, uint32_t* n_out, uint64_t* next_id_out)
+{
+    const char* who = "rts_cube_tracks_get";
+    CHECK_HANDLE(c);
+    if (!n_out || (capacity && !out)) { rts_set_error("%s: null output", who); return RTS_ERR_INVALID; }
+    RtsCubeState& s = c->cube;
+    { int rc = rts_cube_track_tables(c); if (rc != RTS_OK) return rc; }
+    RTS_HIP(hipStreamSynchronize(c->stream));
+    RtsTrackMeta m;
+    RTS_HIP(hipMemcpy(&m, s.d_trk_meta.p + s.trk_cur, sizeof(m), hipMemcpyDeviceToHost));
+    *n_out = m.total;
+    if (next_id_out) *next_id_out = m.next_id;
+    const uint32_t n = m.n < capacity ? m.n : capacity;
+    if (n) RTS_HIP(hipMemcpy(out, s.d_trk[s.trk_cur].p, sizeof(RtsTrack) * n, hipMemcpyDeviceToHost));
+    if (n < m.total) { rts_set_error("%s: %u of %u tracks copied (max_tracks %u, capacity %u)", who, n, m.total, s.trk_max, capacity); return RTS_ERR_CAPACITY; }
+    return RTS_OK;
+}
+
+// the rounds the matching of the last rts_cube_track took (tools/track_bench.py); synchronises
+extern "C" int rts_cube_track_rounds(RtsHandle c, uint32_t* rounds)
+{
+    CHECK_HANDLE(c);
+    if (!rounds) { rts_set_error("rts_cube_track_rounds: null output"); return RTS_ERR_INVALID; }
+    RtsCubeState& s = c->cube;
+    { int rc = rts_cube_track_tables(c); if (rc != RTS_OK) return rc; }
+    RTS_HIP(hipStreamSynchronize(c->stream));
+    RtsTrackMeta m;
+    RTS_HIP(hipMemcpy(&m, s.d_trk_meta.p + s.trk_cur, sizeof(m), hipMemcpyDeviceToHost));
+    *rounds = m.rounds;
+    return RTS_OK;
+}
+
+static int rts_tracks_load(RtsContext* c, const RtsTrack* t, uint32_t n, const uint64_t* next_id)
+{
+    RtsCubeState& s = c->cube;
+    { int rc = rts_cube_track_tables(c); if (rc != RTS_OK) return rc; }
+    RTS_HIP(hipStreamSynchronize(c->stream));                 // (an enqueued step may still read and write both tables)
+    RtsTrackMeta m;
+    RTS_HIP(hipMemcpy(&m, s.d_trk_meta.p + s.trk_cur, sizeof(m), hipMemcpyDeviceToHost));
+    m.n = n; m.total = n; m.rounds = 0; m.reserved = 0;
+    if (next_id) m.next_id = *next_id;
+    if (n) RTS_HIP(hipMemcpy(s.d_trk[s.trk_cur].p, t, sizeof(RtsTrack) * n, hipMemcpyHostToDevice));
+    RTS_HIP(hipMemcpy(s.d_trk_meta.p + s.trk_cur, &m, sizeof(m), hipMemcpyHostToDevice));
+    s.trk_max = 0; s.trk_loaded = n;
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_tracks_set(RtsHandle c, const RtsTrack* tracks, uint32_t n, uint64_t next_id, double time)
+{
+    const char* who = "rts_cube_tracks_set";
+    CHECK_HANDLE(c);
+    CHECK_CLOSED(c);
+    if (n && !tracks) { rts_set_error("%s: null tracks", who); return RTS_ERR_INVALID; }
+    if (n > RTS_TRACK_MAX_TRACKS) { rts_set_error("%s: n = %u > %u (RTS_TRACK_MAX_TRACKS)", who, n, RTS_TRACK_MAX_TRACKS); return RTS_ERR_INVALID; }
+    if (n && !rts_track_finite(time)) { rts_set_error("%s: time = %g (finite)", who, time); return RTS_ERR_INVALID; }
+    { int rc = rts_track_table_refuse(who, tracks, n); if (rc != RTS_OK) return rc; }
+    { int rc = rts_tracks_load(c, tracks, n, &next_id); if (rc != RTS_OK) return rc; }
+    c->cube.trk_live = n != 0u; c->cube.trk_time = time;
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_tracks_reset(RtsHandle c)
+{
+    CHECK_HANDLE(c);
+    CHECK_CLOSED(c);
+    { int rc = rts_tracks_load(c, nullptr, 0, nullptr); if (rc != RTS_OK) return rc; }
+    c->cube.trk_live = false;
+    return RTS_OK;
+}
+
 // ------------------------------------------------------------------------------------- tapered slow-time spectrogram
 // (rts_amd.h: RtsStftParams; the tree and the launch plan are rts_stft.h, shared by the host export and the kernel, rts_stft.hip)
 static int rts_stft_check(const RtsStftParams* p, const RtsCubeParams& q, const char* who, RtsStftPlan* plan)

@@ -20,6 +20,7 @@
 #include "rts_stap.h"             // space-time adaptive processing: the stacked snapshot, its covariance's and filter's evaluators, the host-only plan of the filter's launch
 #include "rts_doa.h"              // direction finding: the eigensolver's and the angular scan's trees, the spectra's weights, the source count, their evaluators and the host-only plans of their launches
 #include "rts_cfar_os.h"          // CFAR: what every detector shares (rts_cfar.h: window, training count, local maximum, refinement, record); OS: rank rule, alphas, the host evaluator
+#include "rts_track.h"            // the tracker step: wrap, prediction, d2, the edge, the candidate order, update, coast, start, the validation, the host evaluator
 #include "rts_plot.h"             // plot extraction: key, unwrap, adjacency, neighbour intervals, the blocked sums, the record, the validation, the host evaluator
 #include "rts_owned.h"            // DevBuf, PinBuf, StagedUpload: device and pinned host memory that frees itself
 #include "rts_launch_plan.h"      // RTS_BLOCK, RTS_WTILE, RTS_COOP_GROUP, RTS_STACK_OVF and the host arithmetic of a launch
@@ -85,6 +86,10 @@ struct __attribute__((aligned(16))) RtsEndRecord {
 static_assert(sizeof(RtsEndRecord) == 112, "end record size");
 static_assert(sizeof(RtsDetection) == 72 && sizeof(RtsCfarParams) == 72 && sizeof(RtsCfarOsParams) == 72, "CFAR ABI sizes (rts_amd/_lib.py mirrors them)");
 static_assert(sizeof(RtsPlot) == 104 && sizeof(RtsPlotParams) == 56, "plot ABI sizes (rts_amd/_lib.py mirrors them)");
+static_assert(sizeof(RtsTrack) == 88 && sizeof(RtsTrackParams) == 96, "track ABI sizes (rts_amd/_lib.py mirrors them)");
+// what the device keeps beside each of the two track tables: the next id, the records stored, the total a table without end would
+// hold (stored + the new tracks turned away), the rounds the matching took
+struct RtsTrackMeta { uint64_t next_id; uint32_t n, total, rounds, reserved; };
 // RtsEndRecord::pad : bits 0-1 chain (output row = chain * n + slot), 2-3 refrDepth, 8-15 (target + 1) of chain 0's
 // refraction (path prefill of rows >= 3), 16-17 children spawned
 
@@ -315,6 +320,15 @@ struct RtsCubeState {
     // from the handle's detection list (whose truncation rts_cube_plots_get reports)
     DevBuf<uint64_t> d_plot_key; DevBuf<uint32_t> d_plot_parent, d_plot_idx, d_plot_lab_s, d_plot_idx_s, d_plot_len, d_plot_flag, d_plot_off; DevBuf<uint8_t> d_plot_tmp;
     DevBuf<RtsPlot> d_plot; uint32_t plot_cap = 0, plot_max = 0; bool plot_valid = false, plot_own_list = false;
+    // tracking (rts_cube_track, rts_track.hip): TWO tables of RTS_TRACK_MAX_TRACKS records and their RtsTrackMeta -- a step reads
+    // table trk_cur and writes the other -- the predictions, the plots' four fields, per track its candidates (entry k of track i at
+    // [k * table size + i]), their count, its plot and that edge's d2, per plot its track and the round's minimum (d2 bits, track), the
+    // rounds, the flags over [tracks | plots | 1] -> exclusive scan, the scan's scratch.  NOT a product of the cube: end_products()
+    // leaves them alone.  trk_max: the table size the previous step ran with (0: the next step chooses); trk_live: the table has a time
+    DevBuf<RtsTrack> d_trk[2]; DevBuf<RtsTrackMeta> d_trk_meta; DevBuf<RtsTrackPred> d_trk_pred;
+    DevBuf<double> d_trk_zd, d_trk_zf, d_trk_pw, d_trk_cd, d_trk_md2; DevBuf<uint64_t> d_trk_best_d;
+    DevBuf<uint32_t> d_trk_zrx, d_trk_cj, d_trk_cn, d_trk_of_track, d_trk_of_plot, d_trk_best_t, d_trk_rounds, d_trk_flag, d_trk_off; DevBuf<uint8_t> d_trk_tmp;
+    uint32_t trk_cur = 0, trk_max = 0, trk_loaded = 0; bool trk_live = false; double trk_time = 0.0;
     // OS-CFAR (rts_cube_detect_os): the alphas by training count go through a staged upload; os_tab keeps them on the host for the next
     // call with the same window, rank and pfa (os_tab_key), so that only training counts not seen yet are solved for; os_tab_sent: the
     // device holds os_tab as it stands
@@ -490,6 +504,9 @@ int rts_cube_detect_device(RtsContext* c, const RtsCfarParams& p, const double* 
 int rts_cube_detect_os_device(RtsContext* c, const RtsCfarOsParams& p, const double* alpha_tab, const double* map, uint32_t n_doppler, uint32_t max_det);      // alpha_tab: device, by training count (pfa), or null (p.alpha)
 // rts_plot.hip.  list: n_cap records, of which the first min(n_cap, *n_dev) count (n_dev null: all n_cap)
 int rts_cube_plots_device(RtsContext* c, const RtsPlotParams& p, const RtsDetection* list, const uint32_t* n_dev, uint32_t n_cap, uint32_t n_doppler, uint32_t max_plots);
+// rts_track.hip.  list: pcap records, of which the first min(pcap, *n_dev) count (n_dev null: all); tcap: the table's size; T: the interval
+int rts_cube_track_tables(RtsContext* c);      // the two tables and their meta records, zeroed on first use
+int rts_cube_track_device(RtsContext* c, const RtsTrackParams& p, double T, const RtsPlot* list, const uint32_t* n_dev, uint32_t pcap, uint32_t tcap);
 int rts_cube_doppler_device(RtsContext* c, uint32_t n_fft, double* out);      // rts_stft.hip: the slow-time transforms
 int rts_cube_stft_device(RtsContext* c, const RtsStftParams& p, const RtsStftPlan& plan, const double* window, double* out);
 int rts_cube_beat_device(RtsContext* c, uint32_t pulse_index, const RtsBeatParams& p, const RtsBeatPlan& plan, double cspeed, double carrier, int64_t base);      // rts_beat.hip
