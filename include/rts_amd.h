@@ -766,6 +766,117 @@ int rts_tracks_eval(const RtsTrackParams* p, const RtsTrack* in, uint32_t n_in, 
                     const RtsPlot* plots, uint32_t n_plots, RtsTrack* out, uint32_t capacity, uint32_t* n_out,
                     uint64_t* next_id_out);                                                      /* pure host */
 
+/* ---------------------------------------------------------------- track-before-detect: dynamic programming over range-Doppler maps
+ * Detect, plots and track are detect-BEFORE-track: a return reaches the tracker only when it crosses a CFAR threshold in one map.
+ * rts_cube_tbd_step integrates the maps of successive intervals along every kinematically admissible cell path instead (Barniv;
+ * Tonissen and Evans): a per-handle MERIT map takes each frame's score plus the best merit of a window of predecessor cells, a ring
+ * of POINTER maps remembers which predecessor that was, and rts_cube_tbd_extract thresholds the accumulated merit once and reads the
+ * paths back.  Both run on the device without waiting on the host.  The rules are rts_amd/csrc/rts_tbd.h, shared by the kernels
+ * (rts_tbd.hip) and the host evaluators rts_tbd_step_eval and rts_tbd_extract_eval, which agree bit for bit.  All arithmetic is IEEE
+ * double, every operation rounded on its own (no contraction); parentheses are evaluation order.
+ *   State, per handle, of shape (n_rx, n_doppler, n_bins): the merit map, f64 [n_rx][n_doppler][n_bins]; a ring of `depth` pointer
+ *     maps, uint8 in the same cell layout; per ring slot the shift table of its frame, int32 [n_doppler]; the frame count and the time
+ *     of the last frame.  It survives rts_cube_attach and the detect, plot and track calls, and ends at rts_cube_tbd_reset and
+ *     rts_destroy.  The shape and depth, half_doppler, half_range are fixed by the first step after a reset; a step that disagrees is
+ *     RTS_ERR_INVALID and leaves the state untouched.
+ *   Input of a step, as for rts_cube_detect: the handle's last rts_cube_doppler map (device_map NULL), or a caller's device pointer
+ *     (16-byte aligned) with n_doppler >= 1; complex128 [n_rx][n_doppler][n_bins] with n_rx and n_bins of the attached cube.  Cell
+ *     power P = re re + im im.
+ *   Score: RTS_TBD_POWER x = P scale; RTS_TBD_AMPLITUDE x = sqrt(P scale).  scale > 0 and finite (the caller passes 1 / noise power).
+ *     An x that is not finite counts as 0.
+ *   Shift table of the frame: T = time - the previous frame's time, positive and finite from the second frame on, ignored on the
+ *     first (whose table is all zeros).  w = kd wrapped into [-n_doppler / 2, n_doppler / 2) the way the CFAR section wraps it (kd -
+ *     n_doppler when kd >= 0.5 n_doppler); f = w / (n_doppler pri), 0 when pri is 0;
+ *       s[kd] = (int32) rint(((delay_rate_per_hz f) T) / dt)          (rint: to nearest, ties to even; dt of the attached cube)
+ *     A quotient that is not finite or lies beyond +-2^30 is RTS_ERR_INVALID.  The sign convention is the tracker's: the caller
+ *     passes delay_rate_per_hz = -1 / carrier.
+ *   Recursion.  First frame: merit = x, every pointer RTS_TBD_NONE.  Later frames, for cell (rx, kd, r): best = 0, code = NONE; the
+ *     offsets are visited in ascending (dd, dr), dd in [-Hd, Hd], dr in [-Hr, Hr]; the predecessor is cell (wrap(kd + dd),
+ *     r - s[kd] + dr) of the previous merit map -- the Doppler index wraps, a range index outside [0, n_bins) is skipped -- and it
+ *     replaces the best only when v > best: the FIRST maximum in that order wins, and a NaN or a merit that is not positive never
+ *     does.  code = (dd + Hd)(2 Hr + 1) + (dr + Hr);  merit = x + (decay best), decay in (0, 1].  The pointer map goes into ring slot
+ *     frame mod depth (frames count from 0); the merit map is replaced.
+ *   Limits: Hd <= RTS_TBD_MAX_HALF_DOPPLER, Hr <= RTS_TBD_MAX_HALF_RANGE (a code is at most 216), 2 Hd + 1 <= n_doppler,
+ *     Hr < n_bins, depth in 1 .. RTS_TBD_MAX_DEPTH, at most RTS_TBD_MAX_CELLS cells.
+ *   Extraction: the candidates are the cells of the current merit map with merit > threshold; with RTS_TBD_LOCAL_MAX also 3 x 3 local
+ *     maxima by the CFAR section's rule as it stands (strictly greater than the neighbours before the cell in flat order, >= those
+ *     after; Doppler wrapped, range truncated) -- including its consequence on a ONE-ROW map, where the neighbour (-1, 0) is the cell
+ *     itself and NO cell is a candidate: extract from a one-row state without RTS_TBD_LOCAL_MAX.  The list is in ascending flat order
+ *     (rx, doppler_bin, range_bin), from counts and a scan, never from atomics: two runs give the same bytes.  Up to max_tracks
+ *     records are stored (0: RTS_TBD_MAX_TRACKS, also the most); beyond that the total is kept and the get returns RTS_ERR_CAPACITY.
+ *   Walk.  Each candidate is walked back through the ring.  At a cell (kd, r) of frame k with code c:
+ *       dd = c / (2 Hr + 1) - Hd;  dr = c % (2 Hr + 1) - Hr;  the predecessor is (wrap(kd + dd), r - s_k[kd] + dr) in frame k - 1,
+ *     s_k the shift table stored with frame k.  The walk stops at NONE or after min(frames, depth) cells.  (A byte that is no code of
+ *     the window, or whose predecessor lies outside the range axis, ends the walk like NONE; a step never writes one.)
+ *   RtsTbdTrack: the end cell (rx, doppler_bin, range_bin), n_cells visited, the OLDEST cell reached (first_doppler_bin,
+ *     first_range_bin) -- paths merge going back, so cells around a target's end cell carry nearly the same merit and reach the same
+ *     oldest cell: records that share it describe one target, and the caller merges them -- merit, delay = t0 + range_bin dt (t0, dt
+ *     of the cube attached at the last step) and doppler = w / (n_doppler pri), 0 when pri is 0 (w of doppler_bin; pri of
+ *     RtsTbdExtractParams).  Paths: uint32 [n][depth][2], entry j the (doppler_bin, range_bin) of the cell j frames back, j = 0 the
+ *     end cell; entries beyond n_cells are 0xffffffff.
+ *   Getters: rts_cube_tbd_tracks_get and rts_cube_tbd_paths_get synchronise and follow the capacity rule of rts_cube_tracks_get
+ *     (*n_out the total; min(stored, capacity) records copied; RTS_ERR_CAPACITY when that is fewer than the total).
+ *     rts_cube_tbd_merit_get copies the merit map; rts_cube_tbd_ring_get the stored pointer maps and shift tables, OLDEST FIRST,
+ *     min(frames, depth) of them; rts_cube_tbd_info the state's shape (n_rx, n_doppler, n_bins, depth) and frame count (all 0 without
+ *     a state).  rts_cube_tbd_reset ends the state and the extraction.
+ *   Evaluators, pure host.  rts_tbd_step_eval: one step as a function -- map [n_rx][n_doppler][n_bins] (n_rx, n_bins, dt of q),
+ *     merit_in (NULL: the first frame; T is then ignored) to merit_out (not merit_in), ptr_out [cells] and shifts_out [n_doppler].
+ *     rts_tbd_extract_eval: merit, n_frames (1 .. depth) pointer maps [n_frames][cells] and shift tables [n_frames][n_doppler],
+ *     OLDEST FIRST, to records and paths (up to `capacity` and max_tracks of them) and *n_out, the total; the walk stops after
+ *     n_frames cells.
+ *   RTS_ERR_INVALID, the message naming the field, outputs and state untouched: half_doppler, half_range, depth beyond their
+ *     limits or changed since the first step; a window wider than the map; an unknown score; unknown flags; nonzero reserved fields;
+ *     scale not positive and finite; decay outside (0, 1]; delay_rate_per_hz not finite; pri negative or not finite; time not
+ *     finite; T not positive and finite; a shift quotient not finite or beyond +-2^30; a shape other than the state's; no map;
+ *     threshold NaN; max_tracks above RTS_TBD_MAX_TRACKS; an extraction or a getter without a state. */
+#define RTS_TBD_POWER 0u
+#define RTS_TBD_AMPLITUDE 1u
+#define RTS_TBD_LOCAL_MAX 1u             /* RtsTbdExtractParams.flags: only 3 x 3 local maxima of the merit map   */
+#define RTS_TBD_NONE 0xffu               /* a pointer without a predecessor                                        */
+#define RTS_TBD_MAX_HALF_DOPPLER 3u
+#define RTS_TBD_MAX_HALF_RANGE 15u
+#define RTS_TBD_MAX_DEPTH 64u
+#define RTS_TBD_MAX_TRACKS 65536u
+#define RTS_TBD_MAX_CELLS 0x40000000u
+typedef struct RtsTbdParams {
+    uint32_t half_doppler, half_range;   /* Hd, Hr: the transition window, cells on each side                      */
+    uint32_t depth;                      /* pointer maps kept, 1 .. RTS_TBD_MAX_DEPTH                              */
+    uint32_t score;                      /* RTS_TBD_POWER, RTS_TBD_AMPLITUDE                                       */
+    uint32_t flags, reserved0;           /* 0 */
+    double scale;                        /* > 0, finite: 1 / noise power                                           */
+    double decay;                        /* (0, 1]: the weight of the best predecessor                             */
+    double delay_rate_per_hz;            /* k: d(delay)/dt per hertz of Doppler; -1 / carrier by the library's signs */
+    double pri;                          /* pulse repetition interval, >= 0; 0: no shift                           */
+    uint64_t reserved[2];                /* 0 */
+} RtsTbdParams;                                               /* 72 bytes */
+typedef struct RtsTbdExtractParams {
+    double threshold;                    /* merit > threshold is a candidate                                       */
+    double pri;                          /* for RtsTbdTrack.doppler, >= 0; 0: doppler = 0                          */
+    uint32_t flags;                      /* RTS_TBD_LOCAL_MAX                                                      */
+    uint32_t max_tracks;                 /* records stored; 0: RTS_TBD_MAX_TRACKS                                  */
+    uint64_t reserved[2];                /* 0 */
+} RtsTbdExtractParams;                                        /* 40 bytes */
+typedef struct RtsTbdTrack {
+    uint32_t rx, doppler_bin, range_bin;                      /* the end cell, in the current merit map                   */
+    uint32_t n_cells;                                         /* cells of the path, 1 .. min(frames, depth)               */
+    uint32_t first_doppler_bin, first_range_bin;              /* the oldest cell reached                                  */
+    double merit;
+    double delay, doppler;                                    /* t0 + range_bin dt;  Hz                                   */
+} RtsTbdTrack;                                                /* 48 bytes */
+int rts_cube_tbd_step(RtsHandle h, const RtsTbdParams* p, double time, const void* device_map, uint32_t n_doppler);
+int rts_cube_tbd_extract(RtsHandle h, const RtsTbdExtractParams* e);
+int rts_cube_tbd_tracks_get(RtsHandle h, RtsTbdTrack* out, uint32_t capacity, uint32_t* n_out);
+int rts_cube_tbd_paths_get(RtsHandle h, uint32_t* out, uint32_t capacity_tracks);
+int rts_cube_tbd_merit_get(RtsHandle h, double* host_out, uint64_t capacity_doubles);
+int rts_cube_tbd_ring_get(RtsHandle h, uint8_t* ptr_out, int32_t* shifts_out, uint32_t capacity_frames, uint32_t* n_frames_out);
+int rts_cube_tbd_info(RtsHandle h, uint32_t shape_out[4], uint64_t* frames_out);
+int rts_cube_tbd_reset(RtsHandle h);
+int rts_tbd_step_eval(const RtsCubeParams* q, const double* map, uint32_t n_doppler, const double* merit_in, const RtsTbdParams* p,
+                      double T, double* merit_out, uint8_t* ptr_out, int32_t* shifts_out);        /* pure host */
+int rts_tbd_extract_eval(const RtsCubeParams* q, uint32_t n_doppler, const RtsTbdParams* p, const double* merit, const uint8_t* ptrs,
+                         const int32_t* shifts, uint32_t n_frames, const RtsTbdExtractParams* e, RtsTbdTrack* out, uint32_t* paths,
+                         uint32_t capacity, uint32_t* n_out);                                      /* pure host */
+
 /* ---------------------------------------------------------------- tapered slow-time spectrogram (STFT) of the return cube
  * The short-time Fourier transform over the pulse axis, per range gate bin or summed over a gate: how Doppler changes INSIDE the
  * interval (rotor and blade flashes, tumbling bodies), where rts_cube_doppler's single rectangular DFT smears it into a band.  A

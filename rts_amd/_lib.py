@@ -159,6 +159,26 @@ TRACK_DTYPE = np.dtype([("id", "<u8"), ("rx", "<u4"), ("flags", "<u4"), ("hits",
                         ("delay", "<f8"), ("doppler", "<f8"), ("p_dd", "<f8"), ("p_df", "<f8"), ("p_ff", "<f8"), ("d2", "<f8"), ("power_sum", "<f8")])
 assert TRACK_DTYPE.itemsize == 88 and C.sizeof(RtsTrackParams) == 96
 
+RTS_TBD_POWER, RTS_TBD_AMPLITUDE, RTS_TBD_LOCAL_MAX, RTS_TBD_NONE = 0, 1, 1, 0xff
+RTS_TBD_MAX_HALF_DOPPLER, RTS_TBD_MAX_HALF_RANGE, RTS_TBD_MAX_DEPTH, RTS_TBD_MAX_TRACKS, RTS_TBD_MAX_CELLS = 3, 15, 64, 65536, 0x40000000
+RTS_TBD_TILE = 1024      # rts_amd/csrc/rts_tbd.h: the range bins a workgroup of the step takes
+
+
+class RtsTbdParams(C.Structure):
+    _fields_ = [("half_doppler", C.c_uint32), ("half_range", C.c_uint32), ("depth", C.c_uint32), ("score", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved0", C.c_uint32), ("scale", C.c_double), ("decay", C.c_double), ("delay_rate_per_hz", C.c_double), ("pri", C.c_double),
+                ("reserved", C.c_uint64 * 2)]
+
+
+class RtsTbdExtractParams(C.Structure):
+    _fields_ = [("threshold", C.c_double), ("pri", C.c_double), ("flags", C.c_uint32), ("max_tracks", C.c_uint32), ("reserved", C.c_uint64 * 2)]
+
+
+# RtsTbdTrack (include/rts_amd.h), 48 bytes
+TBD_TRACK_DTYPE = np.dtype([("rx", "<u4"), ("doppler_bin", "<u4"), ("range_bin", "<u4"), ("n_cells", "<u4"), ("first_doppler_bin", "<u4"),
+                            ("first_range_bin", "<u4"), ("merit", "<f8"), ("delay", "<f8"), ("doppler", "<f8")])
+assert TBD_TRACK_DTYPE.itemsize == 48 and C.sizeof(RtsTbdParams) == 72 and C.sizeof(RtsTbdExtractParams) == 40
+
 
 RTS_IMAGE_ACCUMULATE, RTS_IMAGE_PULSE_CHUNK, RTS_IMAGE_MAX_PIXELS = 1, 64, 16777216
 
@@ -366,6 +386,8 @@ EXPORTS = ["rts_create", "rts_destroy", "rts_last_error", "rts_device_count", "r
            "rts_cube_detect_os", "rts_cfar_os_alpha", "rts_cfar_os_eval",
            "rts_cube_plots", "rts_cube_plots_get", "rts_plots_eval",
            "rts_cube_track", "rts_cube_tracks_get", "rts_cube_tracks_set", "rts_cube_tracks_reset", "rts_cube_track_rounds", "rts_tracks_eval",
+           "rts_cube_tbd_step", "rts_cube_tbd_extract", "rts_cube_tbd_tracks_get", "rts_cube_tbd_paths_get", "rts_cube_tbd_merit_get", "rts_cube_tbd_ring_get",
+           "rts_cube_tbd_info", "rts_cube_tbd_reset", "rts_tbd_step_eval", "rts_tbd_extract_eval",
            "rts_cube_backproject", "rts_cube_image_get", "rts_backproject_eval",
            "rts_cube_spectrogram", "rts_cube_spectrogram_get", "rts_stft_eval", "rts_window_make",
            "rts_cube_render_beat", "rts_beat_eval", "rts_cube_range_transform", "rts_cube_range_get", "rts_range_eval",
@@ -457,6 +479,16 @@ def lib():
         "rts_cube_tracks_reset": [vp],
         "rts_cube_track_rounds": [vp, C.POINTER(u32)],
         "rts_tracks_eval": [C.POINTER(RtsTrackParams), vp, u32, u64, C.c_double, vp, u32, vp, u32, C.POINTER(u32), C.POINTER(u64)],
+        "rts_cube_tbd_step": [vp, C.POINTER(RtsTbdParams), C.c_double, vp, u32],
+        "rts_cube_tbd_extract": [vp, C.POINTER(RtsTbdExtractParams)],
+        "rts_cube_tbd_tracks_get": [vp, vp, u32, C.POINTER(u32)],
+        "rts_cube_tbd_paths_get": [vp, vp, u32],
+        "rts_cube_tbd_merit_get": [vp, vp, u64],
+        "rts_cube_tbd_ring_get": [vp, vp, vp, u32, C.POINTER(u32)],
+        "rts_cube_tbd_info": [vp, C.POINTER(u32 * 4), C.POINTER(u64)],
+        "rts_cube_tbd_reset": [vp],
+        "rts_tbd_step_eval": [C.POINTER(RtsCubeParams), vp, u32, vp, C.POINTER(RtsTbdParams), C.c_double, vp, vp, vp],
+        "rts_tbd_extract_eval": [C.POINTER(RtsCubeParams), u32, C.POINTER(RtsTbdParams), vp, vp, vp, u32, C.POINTER(RtsTbdExtractParams), vp, vp, u32, C.POINTER(u32)],
         "rts_cube_backproject": [vp, C.POINTER(RtsImageParams), vp],
         "rts_cube_image_get": [vp, vp, u64],
         "rts_backproject_eval": [C.POINTER(RtsCubeParams), vp, C.POINTER(RtsImageParams), vp],

@@ -310,6 +310,59 @@ def tracks_eval(tracks, next_id, T, plots, sigma, gate=9.21, q=0.0, delay_rate_p
     return out[:min(n.value, max_tracks or L.RTS_TRACK_DEFAULT_TRACKS)].copy(), nid.value
 
 
+# ------------------------------------------------------------------------------- track-before-detect (rts_tbd.h)
+def _tbd_params(half, depth, score, scale, decay, delay_rate_per_hz, pri):
+    """RtsTbdParams; half is the transition window (Doppler, range) in cells on each side"""
+    p = L.RtsTbdParams()
+    p.half_doppler, p.half_range = (int(x) for x in half)
+    p.depth = int(depth)
+    p.score = {"power": L.RTS_TBD_POWER, "amplitude": L.RTS_TBD_AMPLITUDE}.get(score, score)
+    p.scale, p.decay, p.delay_rate_per_hz, p.pri = float(scale), float(decay), float(delay_rate_per_hz), float(pri)
+    return p
+
+
+def _tbd_extract_params(threshold, local_max, max_tracks, pri):
+    e = L.RtsTbdExtractParams()
+    e.threshold, e.pri, e.max_tracks = float(threshold), float(pri), int(max_tracks)
+    e.flags = L.RTS_TBD_LOCAL_MAX if local_max else 0
+    return e
+
+
+def tbd_step_eval(map, merit_in, T, half=(1, 2), depth=8, score="power", scale=1.0, decay=1.0, delay_rate_per_hz=0.0, pri=0.0, dt=1.0):
+    """rts_tbd_step_eval (pure host): one track-before-detect step on a host map [n_rx][n_doppler][n_bins] (complex) from the merit
+    map merit_in (None: the first frame).  Returns (merit f64, pointers uint8, both of the map's shape, shifts int32 [n_doppler])."""
+    m = np.ascontiguousarray(np.asarray(map, np.complex128))
+    n_rx, nd, nb = m.shape
+    q = L.RtsCubeParams(n_rx, 1, nb, 0, 0.0, float(dt))
+    p = _tbd_params(half, depth, score, scale, decay, delay_rate_per_hz, pri)
+    prev = None if merit_in is None else np.ascontiguousarray(np.asarray(merit_in, np.float64).reshape(m.shape))
+    merit, code, shifts = np.zeros(m.shape), np.zeros(m.shape, np.uint8), np.zeros(nd, np.int32)
+    check(L.lib().rts_tbd_step_eval(C.byref(q), ptr(m.view(np.float64)), nd, ptr(prev), C.byref(p), float(T), ptr(merit), ptr(code), ptr(shifts)))
+    return merit, code, shifts
+
+
+def tbd_extract_eval(merit, ptrs, shifts, threshold, half=(1, 2), depth=8, local_max=True, max_tracks=0, pri=0.0, t0=0.0, dt=1.0):
+    """rts_tbd_extract_eval (pure host): the candidates of the merit map [n_rx][n_doppler][n_bins] walked back through the pointer
+    maps ptrs [n_frames][n_rx][n_doppler][n_bins] and shift tables shifts [n_frames][n_doppler], oldest first.  Returns (the stored
+    TBD_TRACK_DTYPE records, their paths uint32 [n][depth][2])."""
+    m = np.ascontiguousarray(np.asarray(merit, np.float64))
+    n_rx, nd, nb = m.shape
+    c = np.ascontiguousarray(np.asarray(ptrs, np.uint8)); s = np.ascontiguousarray(np.asarray(shifts, np.int32))
+    n_frames = len(c)
+    assert c.shape == (n_frames,) + m.shape and s.shape == (n_frames, nd)
+    q = L.RtsCubeParams(n_rx, 1, nb, 0, float(t0), float(dt))
+    p = _tbd_params(half, depth, "power", 1.0, 1.0, 0.0, 0.0)
+    e = _tbd_extract_params(threshold, local_max, max_tracks, pri)
+    n = C.c_uint32(0)
+    cap = min(m.size, max_tracks or L.RTS_TBD_MAX_TRACKS)
+    out = np.zeros(max(cap, 1), L.TBD_TRACK_DTYPE); paths = np.zeros((max(cap, 1), int(depth), 2), np.uint32)
+    rc = L.lib().rts_tbd_extract_eval(C.byref(q), nd, C.byref(p), ptr(m), ptr(c), ptr(s), n_frames, C.byref(e), ptr(out), ptr(paths), cap, C.byref(n))
+    if rc != L.RTS_ERR_CAPACITY:
+        check(rc)
+    k = min(n.value, cap)
+    return out[:k].copy(), paths[:k].copy()
+
+
 # ------------------------------------------------------------------------------- backprojection imaging (rts_image.h)
 def _image_params(origin, step_x, step_y, n_x, n_y, tx_positions, rx_positions, cspeed, carrier, taps, first, count, weights, accumulate, n_rx):
     """RtsImageParams and the arrays it points to (keep them alive for the call).  tx_positions [P][3]; rx_positions [n_rx][P][3]
@@ -1336,6 +1389,61 @@ class Tracer:
     def cube_tracks_reset(self):
         """rts_cube_tracks_reset: an empty table without a time; ids go on where they were"""
         check(L.lib().rts_cube_tracks_reset(self.h))
+
+    def cube_tbd_step(self, time, half=(1, 2), depth=8, score="power", scale=1.0, decay=1.0, delay_rate_per_hz=0.0, pri=0.0, device_ptr=None, n_doppler=0):
+        """rts_cube_tbd_step: the handle's track-before-detect state advanced by the frame at `time` -- the handle's last cube_doppler
+        map (device_ptr None) or a caller complex128 device map [n_rx][n_doppler][n_bins]; half is the transition window (Doppler,
+        range) in cells on each side; scale is 1 / noise power.  Never waits on the host."""
+        p = _tbd_params(half, depth, score, scale, decay, delay_rate_per_hz, pri)
+        check(L.lib().rts_cube_tbd_step(self.h, C.byref(p), float(time), C.c_void_p(device_ptr) if device_ptr else None, int(n_doppler or 0)))
+        self._tbd_pri = float(pri)
+
+    def cube_tbd_extract(self, threshold, local_max=True, max_tracks=0, fetch=True, pri=None):
+        """rts_cube_tbd_extract + the getters: the cells of the merit map above `threshold` (local_max: only 3 x 3 local maxima), each
+        walked back through the pointer ring; pri (None: the last cube_tbd_step's) turns doppler_bin into hertz.  Never waits on the
+        host unless fetch.  Returns (the TBD_TRACK_DTYPE records, their paths uint32 [n][depth][2]) when fetch."""
+        e = _tbd_extract_params(threshold, local_max, max_tracks, getattr(self, "_tbd_pri", 0.0) if pri is None else pri)
+        check(L.lib().rts_cube_tbd_extract(self.h, C.byref(e)))
+        return self.tbd_tracks() if fetch else None
+
+    def tbd_info(self):
+        """rts_cube_tbd_info: ((n_rx, n_doppler, n_bins, depth), frames) of the track-before-detect state; zeros without one"""
+        shape, frames = (C.c_uint32 * 4)(), C.c_uint64(0)
+        check(L.lib().rts_cube_tbd_info(self.h, C.byref(shape), C.byref(frames)))
+        return tuple(shape), frames.value
+
+    def tbd_tracks(self):
+        """rts_cube_tbd_tracks_get + rts_cube_tbd_paths_get: (records, paths) of the last cube_tbd_extract (every stored record; raises
+        when max_tracks cut them)"""
+        n = C.c_uint32(0)
+        rc = L.lib().rts_cube_tbd_tracks_get(self.h, None, 0, C.byref(n))
+        if rc not in (L.RTS_OK, L.RTS_ERR_CAPACITY):
+            check(rc)
+        depth = self.tbd_info()[0][3]
+        out = np.zeros(max(n.value, 1), L.TBD_TRACK_DTYPE); paths = np.zeros((max(n.value, 1), max(depth, 1), 2), np.uint32)
+        check(L.lib().rts_cube_tbd_tracks_get(self.h, ptr(out), n.value, C.byref(n)))
+        check(L.lib().rts_cube_tbd_paths_get(self.h, ptr(paths), n.value))
+        return out[:n.value].copy(), paths[:n.value].copy()
+
+    def tbd_merit(self):
+        """rts_cube_tbd_merit_get: the merit map, f64 [n_rx][n_doppler][n_bins]"""
+        (n_rx, nd, nb, _), _ = self.tbd_info()
+        out = np.zeros((max(n_rx, 1), max(nd, 1), max(nb, 1)))
+        check(L.lib().rts_cube_tbd_merit_get(self.h, ptr(out), out.size))
+        return out
+
+    def tbd_ring(self):
+        """rts_cube_tbd_ring_get: (the stored pointer maps uint8 [n][n_rx][n_doppler][n_bins], their shift tables int32 [n][n_doppler]),
+        oldest first, n = min(frames, depth)"""
+        (n_rx, nd, nb, depth), frames = self.tbd_info()
+        n = C.c_uint32(0); k = max(min(frames, depth), 1)
+        codes = np.zeros((k, max(n_rx, 1), max(nd, 1), max(nb, 1)), np.uint8); shifts = np.zeros((k, max(nd, 1)), np.int32)
+        check(L.lib().rts_cube_tbd_ring_get(self.h, ptr(codes), ptr(shifts), k, C.byref(n)))
+        return codes[:n.value], shifts[:n.value]
+
+    def cube_tbd_reset(self):
+        """rts_cube_tbd_reset: ends the track-before-detect state and its extraction; the next cube_tbd_step fixes shape and window anew"""
+        check(L.lib().rts_cube_tbd_reset(self.h))
 
     def cube_backproject(self, origin, step_x, step_y, n_x, n_y, tx_positions, rx_positions, cspeed, carrier, taps=8, first=0, count=None,
                          weights=None, accumulate=False, device_ptr=None, fetch=True):

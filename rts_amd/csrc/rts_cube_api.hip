@@ -578,6 +578,228 @@ extern "C" int rts_cube_tracks_reset(RtsHandle c)
     return RTS_OK;
 }
 
+// ------------------------------------------------------------------------------------- track-before-detect
+// (rts_amd.h: RtsTbdParams, RtsTbdExtractParams, RtsTbdTrack; the rules and the host evaluators are rts_tbd.h, shared with the kernels, rts_tbd.hip)
+static int rts_tbd_check(const char* who, const RtsTbdParams* p, uint32_t nd, uint32_t nb)
+{
+    if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
+    switch (rts_tbd_params_check(p, nd, nb)) {
+        case 0: return RTS_OK;
+        case 1: rts_set_error("%s: half_doppler = %u > %u (RTS_TBD_MAX_HALF_DOPPLER)", who, p->half_doppler, RTS_TBD_MAX_HALF_DOPPLER); break;
+        case 2: rts_set_error("%s: half_range = %u > %u (RTS_TBD_MAX_HALF_RANGE)", who, p->half_range, RTS_TBD_MAX_HALF_RANGE); break;
+        case 3: rts_set_error("%s: depth = %u (1 .. %u, RTS_TBD_MAX_DEPTH)", who, p->depth, RTS_TBD_MAX_DEPTH); break;
+        case 4: rts_set_error("%s: unknown score %u (RTS_TBD_POWER, RTS_TBD_AMPLITUDE)", who, p->score); break;
+        case 5: rts_set_error("%s: unknown flags 0x%x", who, p->flags); break;
+        case 6: rts_set_error("%s: reserved fields must be 0", who); break;
+        case 7: rts_set_error("%s: scale = %g (finite, > 0)", who, p->scale); break;
+        case 8: rts_set_error("%s: decay = %g outside (0, 1]", who, p->decay); break;
+        case 9: rts_set_error("%s: delay_rate_per_hz = %g (finite)", who, p->delay_rate_per_hz); break;
+        case 10: rts_set_error("%s: pri = %g (finite, >= 0)", who, p->pri); break;
+        case 11: rts_set_error("%s: half_doppler = %u: the window (%u rows) exceeds n_doppler = %u", who, p->half_doppler, 2u * p->half_doppler + 1u, nd); break;
+        default: rts_set_error("%s: half_range = %u >= n_bins = %u", who, p->half_range, nb); break;
+    }
+    return RTS_ERR_INVALID;
+}
+static int rts_tbd_extract_refuse(const char* who, const RtsTbdExtractParams* e)
+{
+    if (!e) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
+    switch (rts_tbd_extract_check(e)) {
+        case 0: return RTS_OK;
+        case 1: rts_set_error("%s: threshold is NaN", who); break;
+        case 2: rts_set_error("%s: pri = %g (finite, >= 0)", who, e->pri); break;
+        case 3: rts_set_error("%s: unknown flags 0x%x", who, e->flags); break;
+        case 4: rts_set_error("%s: max_tracks = %u > %u (RTS_TBD_MAX_TRACKS)", who, e->max_tracks, RTS_TBD_MAX_TRACKS); break;
+        default: rts_set_error("%s: reserved fields must be 0", who); break;
+    }
+    return RTS_ERR_INVALID;
+}
+// the shape of a map: what an evaluator is given, or what a step finds
+static int rts_tbd_shape_check(const char* who, uint32_t n_rx, uint32_t nd, uint32_t nb, double dt, double t0)
+{
+    if (n_rx == 0 || nb == 0 || !(dt > 0) || !std::isfinite(dt) || !std::isfinite(t0)) { rts_set_error("%s: bad cube parameters", who); return RTS_ERR_INVALID; }
+    if (nd == 0) { rts_set_error("%s: n_doppler = 0", who); return RTS_ERR_INVALID; }
+    if ((uint64_t)n_rx * nd * nb > RTS_TBD_MAX_CELLS) { rts_set_error("%s: %u x %u x %u cells > %u (RTS_TBD_MAX_CELLS)", who, n_rx, nd, nb, RTS_TBD_MAX_CELLS); return RTS_ERR_INVALID; }
+    return RTS_OK;
+}
+static int rts_tbd_shifts_refuse(const char* who, const RtsTbdParams* p, uint32_t nd, double T, double dt)
+{
+    if (!rts_tbd_interval_ok(T)) { rts_set_error("%s: T = time - the previous frame's = %g (positive, finite)", who, T); return RTS_ERR_INVALID; }
+    uint32_t bad = 0;
+    if (rts_tbd_shifts_check(p, nd, T, dt, &bad)) {
+        rts_set_error("%s: the shift of Doppler row %u, ((delay_rate_per_hz f) T) / dt = %g, is not finite or beyond 2^30", who, bad, rts_tbd_shift_quotient(bad, nd, p->delay_rate_per_hz, p->pri, T, dt));
+        return RTS_ERR_INVALID;
+    }
+    return RTS_OK;
+}
+
+extern "C" int rts_tbd_step_eval(const RtsCubeParams* q, const double* map, uint32_t n_doppler, const double* merit_in, const RtsTbdParams* p, double T,
+                                 double* merit_out, uint8_t* ptr_out, int32_t* shifts_out)
+{
+    const char* who = "rts_tbd_step_eval";
+    if (!q) { rts_set_error("%s: bad cube parameters", who); return RTS_ERR_INVALID; }
+    { int rc = rts_tbd_shape_check(who, q->n_rx, n_doppler, q->n_bins, q->dt, q->t0); if (rc != RTS_OK) return rc; }
+    { int rc = rts_tbd_check(who, p, n_doppler, q->n_bins); if (rc != RTS_OK) return rc; }
+    if (!map || !merit_out || !ptr_out || !shifts_out || merit_out == merit_in) { rts_set_error("%s: null map or output (merit_out must not be merit_in)", who); return RTS_ERR_INVALID; }
+    if (merit_in) { int rc = rts_tbd_shifts_refuse(who, p, n_doppler, T, q->dt); if (rc != RTS_OK) return rc; }
+    rts_tbd_step_host(p, q->n_rx, n_doppler, q->n_bins, q->dt, map, merit_in, T, merit_out, ptr_out, shifts_out);
+    return RTS_OK;
+}
+
+extern "C" int rts_tbd_extract_eval(const RtsCubeParams* q, uint32_t n_doppler, const RtsTbdParams* p, const double* merit, const uint8_t* ptrs, const int32_t* shifts,
+                                    uint32_t n_frames, const RtsTbdExtractParams* e, RtsTbdTrack* out, uint32_t* paths, uint32_t capacity, uint32_t* n_out)
+{
+    const char* who = "rts_tbd_extract_eval";
+    if (!q) { rts_set_error("%s: bad cube parameters", who); return RTS_ERR_INVALID; }
+    { int rc = rts_tbd_shape_check(who, q->n_rx, n_doppler, q->n_bins, q->dt, q->t0); if (rc != RTS_OK) return rc; }
+    { int rc = rts_tbd_check(who, p, n_doppler, q->n_bins); if (rc != RTS_OK) return rc; }
+    { int rc = rts_tbd_extract_refuse(who, e); if (rc != RTS_OK) return rc; }
+    if (n_frames == 0 || n_frames > p->depth) { rts_set_error("%s: n_frames = %u (1 .. depth = %u)", who, n_frames, p->depth); return RTS_ERR_INVALID; }
+    if (!merit || !ptrs || !shifts || !n_out || (capacity && (!out || !paths))) { rts_set_error("%s: null merit, pointer maps, shift tables or output", who); return RTS_ERR_INVALID; }
+    const uint32_t total = rts_tbd_extract_host(p, e, q->n_rx, n_doppler, q->n_bins, q->t0, q->dt, merit, ptrs, shifts, n_frames, out, paths, capacity);
+    *n_out = total;
+    const uint32_t stored = total < rts_tbd_max_tracks(*e) ? total : rts_tbd_max_tracks(*e), n = stored < capacity ? stored : capacity;
+    if (n < total) { rts_set_error("%s: %u of %u tracks written (max_tracks %u, capacity %u)", who, n, total, rts_tbd_max_tracks(*e), capacity); return RTS_ERR_CAPACITY; }
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_tbd_step(RtsHandle c, const RtsTbdParams* p, double time, const void* device_map, uint32_t n_doppler)
+{
+    const char* who = "rts_cube_tbd_step";
+    CHECK_HANDLE(c);
+    if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
+    CHECK_CLOSED(c);
+    NEED_CUBE(c, who, "no cube (call rts_cube_attach first)");
+    const double* map;
+    { int rc = rts_cfar_map(c, who, device_map, &map, &n_doppler); if (rc != RTS_OK) return rc; }
+    RtsCubeState& s = c->cube;
+    const RtsCubeParams& q = s.params;
+    { int rc = rts_tbd_shape_check(who, q.n_rx, n_doppler, q.n_bins, q.dt, q.t0); if (rc != RTS_OK) return rc; }
+    { int rc = rts_tbd_check(who, p, n_doppler, q.n_bins); if (rc != RTS_OK) return rc; }
+    if (!rts_tbd_finite(time)) { rts_set_error("%s: time = %g (finite)", who, time); return RTS_ERR_INVALID; }
+    const bool first = s.tbd_frames == 0;
+    double T = 0.0;
+    if (!first) {
+        if (q.n_rx != s.tbd_rx || n_doppler != s.tbd_nd || q.n_bins != s.tbd_nb) {
+            rts_set_error("%s: a map of %u x %u x %u cells, the state has %u x %u x %u (rts_cube_tbd_reset first)", who, q.n_rx, n_doppler, q.n_bins, s.tbd_rx, s.tbd_nd, s.tbd_nb); return RTS_ERR_INVALID; }
+        if (p->depth != s.tbd_depth || p->half_doppler != s.tbd_hd || p->half_range != s.tbd_hr) {
+            rts_set_error("%s: depth, half_doppler, half_range = %u, %u, %u, the state was made with %u, %u, %u (rts_cube_tbd_reset first)", who, p->depth, p->half_doppler, p->half_range,
+                          s.tbd_depth, s.tbd_hd, s.tbd_hr); return RTS_ERR_INVALID; }
+        T = time - s.tbd_time;
+        { int rc = rts_tbd_shifts_refuse(who, p, n_doppler, T, q.dt); if (rc != RTS_OK) return rc; }
+    } else {
+        // the state's buffers, of their final sizes (a DevBuf that grows drops what it held: they are made once per state)
+        const size_t cells = (size_t)q.n_rx * n_doppler * q.n_bins;
+        RTS_HIP(s.d_tbd_merit[0].reserve(cells)); RTS_HIP(s.d_tbd_merit[1].reserve(cells));
+        RTS_HIP(s.d_tbd_ptr.reserve(cells * p->depth)); RTS_HIP(s.d_tbd_shift.reserve((size_t)n_doppler * p->depth));
+        s.tbd_rx = q.n_rx; s.tbd_nd = n_doppler; s.tbd_nb = q.n_bins; s.tbd_depth = p->depth; s.tbd_hd = p->half_doppler; s.tbd_hr = p->half_range; s.tbd_cur = 0;
+    }
+    { int rc = rts_cube_tbd_step_device(c, *p, map, first, T, q.dt, (uint32_t)(s.tbd_frames % s.tbd_depth)); if (rc != RTS_OK) return rc; }
+    s.tbd_frames++; s.tbd_time = time; s.tbd_t0 = q.t0; s.tbd_dt = q.dt;
+    return RTS_OK;
+}
+
+#define NEED_TBD(c, who) do { if ((c)->cube.tbd_frames == 0) { rts_set_error("%s: no track-before-detect state (rts_cube_tbd_step; a state ends at rts_cube_tbd_reset)", (who)); return RTS_ERR_INVALID; } } while (0)
+
+extern "C" int rts_cube_tbd_extract(RtsHandle c, const RtsTbdExtractParams* e)
+{
+    const char* who = "rts_cube_tbd_extract";
+    CHECK_HANDLE(c);
+    { int rc = rts_tbd_extract_refuse(who, e); if (rc != RTS_OK) return rc; }
+    CHECK_CLOSED(c);
+    NEED_TBD(c, who);
+    c->cube.tbd_ext_valid = false;
+    return rts_cube_tbd_extract_device(c, *e, rts_tbd_max_tracks(*e));
+}
+
+// total, and how many of the stored records fit `capacity`; synchronises
+static int rts_tbd_extracted(RtsContext* c, const char* who, uint32_t capacity, uint32_t* total, uint32_t* n)
+{
+    RtsCubeState& s = c->cube;
+    if (!s.tbd_ext_valid) { rts_set_error("%s: no extraction (rts_cube_tbd_extract; it ends at rts_cube_tbd_reset)", who); return RTS_ERR_INVALID; }
+    RTS_HIP(hipStreamSynchronize(c->stream));
+    RTS_HIP(hipMemcpy(total, s.d_tbd_off.p + s.tbd_ext_nseg, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    const uint32_t stored = *total < s.tbd_ext_max ? *total : s.tbd_ext_max;
+    *n = stored < capacity ? stored : capacity;
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_tbd_tracks_get(RtsHandle c, RtsTbdTrack* out, uint32_t capacity, uint32_t* n_out)
+{
+    const char* who = "rts_cube_tbd_tracks_get";
+    CHECK_HANDLE(c);
+    if (!n_out || (capacity && !out)) { rts_set_error("%s: null output", who); return RTS_ERR_INVALID; }
+    uint32_t total = 0, n = 0;
+    { int rc = rts_tbd_extracted(c, who, capacity, &total, &n); if (rc != RTS_OK) return rc; }
+    *n_out = total;
+    if (n) RTS_HIP(hipMemcpy(out, c->cube.d_tbd_out.p, sizeof(RtsTbdTrack) * n, hipMemcpyDeviceToHost));
+    if (n < total) { rts_set_error("%s: %u of %u tracks copied (max_tracks %u, capacity %u)", who, n, total, c->cube.tbd_ext_max, capacity); return RTS_ERR_CAPACITY; }
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_tbd_paths_get(RtsHandle c, uint32_t* out, uint32_t capacity_tracks)
+{
+    const char* who = "rts_cube_tbd_paths_get";
+    CHECK_HANDLE(c);
+    if (capacity_tracks && !out) { rts_set_error("%s: null output", who); return RTS_ERR_INVALID; }
+    uint32_t total = 0, n = 0;
+    { int rc = rts_tbd_extracted(c, who, capacity_tracks, &total, &n); if (rc != RTS_OK) return rc; }
+    if (n) RTS_HIP(hipMemcpy(out, c->cube.d_tbd_paths.p, sizeof(uint32_t) * 2u * c->cube.tbd_ext_depth * n, hipMemcpyDeviceToHost));
+    if (n < total) { rts_set_error("%s: the paths of %u of %u tracks copied (max_tracks %u, capacity %u)", who, n, total, c->cube.tbd_ext_max, capacity_tracks); return RTS_ERR_CAPACITY; }
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_tbd_merit_get(RtsHandle c, double* host_out, uint64_t capacity_doubles)
+{
+    const char* who = "rts_cube_tbd_merit_get";
+    CHECK_HANDLE(c);
+    NEED_TBD(c, who);
+    RtsCubeState& s = c->cube;
+    const size_t cells = (size_t)s.tbd_rx * s.tbd_nd * s.tbd_nb;
+    if (!host_out) { rts_set_error("%s: null output", who); return RTS_ERR_INVALID; }
+    if (capacity_doubles < cells) { rts_set_error("%s: capacity too small", who); return RTS_ERR_CAPACITY; }
+    RTS_HIP(hipStreamSynchronize(c->stream));
+    RTS_HIP(hipMemcpy(host_out, s.d_tbd_merit[s.tbd_cur].p, sizeof(double) * cells, hipMemcpyDeviceToHost));
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_tbd_ring_get(RtsHandle c, uint8_t* ptr_out, int32_t* shifts_out, uint32_t capacity_frames, uint32_t* n_frames_out)
+{
+    const char* who = "rts_cube_tbd_ring_get";
+    CHECK_HANDLE(c);
+    NEED_TBD(c, who);
+    RtsCubeState& s = c->cube;
+    if (!n_frames_out || (capacity_frames && (!ptr_out || !shifts_out))) { rts_set_error("%s: null output", who); return RTS_ERR_INVALID; }
+    const uint32_t have = s.tbd_frames < s.tbd_depth ? (uint32_t)s.tbd_frames : s.tbd_depth;
+    *n_frames_out = have;
+    if (capacity_frames < have) { rts_set_error("%s: %u frames stored, capacity %u", who, have, capacity_frames); return RTS_ERR_CAPACITY; }
+    const size_t cells = (size_t)s.tbd_rx * s.tbd_nd * s.tbd_nb;
+    RTS_HIP(hipStreamSynchronize(c->stream));
+    for (uint32_t i = 0; i < have; i++) {                               // oldest first: frame frames - have + i
+        const size_t slot = (size_t)((s.tbd_frames - have + i) % s.tbd_depth);
+        RTS_HIP(hipMemcpy(ptr_out + (size_t)i * cells, s.d_tbd_ptr.p + slot * cells, cells, hipMemcpyDeviceToHost));
+        RTS_HIP(hipMemcpy(shifts_out + (size_t)i * s.tbd_nd, s.d_tbd_shift.p + slot * s.tbd_nd, sizeof(int32_t) * s.tbd_nd, hipMemcpyDeviceToHost));
+    }
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_tbd_info(RtsHandle c, uint32_t shape_out[4], uint64_t* frames_out)
+{
+    CHECK_HANDLE(c);
+    if (!shape_out || !frames_out) { rts_set_error("rts_cube_tbd_info: null output"); return RTS_ERR_INVALID; }
+    const RtsCubeState& s = c->cube;
+    const bool have = s.tbd_frames != 0;
+    shape_out[0] = have ? s.tbd_rx : 0u; shape_out[1] = have ? s.tbd_nd : 0u; shape_out[2] = have ? s.tbd_nb : 0u; shape_out[3] = have ? s.tbd_depth : 0u;
+    *frames_out = s.tbd_frames;
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_tbd_reset(RtsHandle c)
+{
+    CHECK_HANDLE(c);
+    c->cube.tbd_frames = 0; c->cube.tbd_ext_valid = false;      // (the buffers stay: work enqueued on them runs before the next state's, on the same stream)
+    return RTS_OK;
+}
+
 // ------------------------------------------------------------------------------------- tapered slow-time spectrogram
 // (rts_amd.h: RtsStftParams; the tree and the launch plan are rts_stft.h, shared by the host export and the kernel, rts_stft.hip)
 static int rts_stft_check(const RtsStftParams* p, const RtsCubeParams& q, const char* who, RtsStftPlan* plan)

@@ -21,6 +21,7 @@
 #include "rts_doa.h"              // direction finding: the eigensolver's and the angular scan's trees, the spectra's weights, the source count, their evaluators and the host-only plans of their launches
 #include "rts_cfar_os.h"          // CFAR: what every detector shares (rts_cfar.h: window, training count, local maximum, refinement, record); OS: rank rule, alphas, the host evaluator
 #include "rts_track.h"            // the tracker step: wrap, prediction, d2, the edge, the candidate order, update, coast, start, the validation, the host evaluator
+#include "rts_tbd.h"              // track-before-detect: the shift table, the score, the window's first maximum, the candidate, the walk, the record, the validation, the host evaluators
 #include "rts_plot.h"             // plot extraction: key, unwrap, adjacency, neighbour intervals, the blocked sums, the record, the validation, the host evaluator
 #include "rts_owned.h"            // DevBuf, PinBuf, StagedUpload: device and pinned host memory that frees itself
 #include "rts_launch_plan.h"      // RTS_BLOCK, RTS_WTILE, RTS_COOP_GROUP, RTS_STACK_OVF and the host arithmetic of a launch
@@ -87,6 +88,7 @@ static_assert(sizeof(RtsEndRecord) == 112, "end record size");
 static_assert(sizeof(RtsDetection) == 72 && sizeof(RtsCfarParams) == 72 && sizeof(RtsCfarOsParams) == 72, "CFAR ABI sizes (rts_amd/_lib.py mirrors them)");
 static_assert(sizeof(RtsPlot) == 104 && sizeof(RtsPlotParams) == 56, "plot ABI sizes (rts_amd/_lib.py mirrors them)");
 static_assert(sizeof(RtsTrack) == 88 && sizeof(RtsTrackParams) == 96, "track ABI sizes (rts_amd/_lib.py mirrors them)");
+static_assert(sizeof(RtsTbdParams) == 72 && sizeof(RtsTbdExtractParams) == 40 && sizeof(RtsTbdTrack) == 48, "track-before-detect ABI sizes (rts_amd/_lib.py mirrors them)");
 // what the device keeps beside each of the two track tables: the next id, the records stored, the total a table without end would
 // hold (stored + the new tracks turned away), the rounds the matching took
 struct RtsTrackMeta { uint64_t next_id; uint32_t n, total, rounds, reserved; };
@@ -329,6 +331,16 @@ struct RtsCubeState {
     DevBuf<double> d_trk_zd, d_trk_zf, d_trk_pw, d_trk_cd, d_trk_md2; DevBuf<uint64_t> d_trk_best_d;
     DevBuf<uint32_t> d_trk_zrx, d_trk_cj, d_trk_cn, d_trk_of_track, d_trk_of_plot, d_trk_best_t, d_trk_rounds, d_trk_flag, d_trk_off; DevBuf<uint8_t> d_trk_tmp;
     uint32_t trk_cur = 0, trk_max = 0, trk_loaded = 0; bool trk_live = false; double trk_time = 0.0;
+    // track-before-detect (rts_cube_tbd_step, rts_cube_tbd_extract, rts_tbd.hip): TWO merit maps -- a step reads tbd_cur and writes the
+    // other -- the ring of tbd_depth pointer maps and of their shift tables (frame f in slot f mod depth), all of the shape and
+    // window the first step after a reset fixed (tbd_frames == 0: no state); the time, and t0 and dt, of the last frame.  The
+    // extraction: per segment of 64 cells its candidates' count -> exclusive scan (offsets; element tbd_ext_nseg: the total), the
+    // scan's scratch, the records and their paths.  NOT a product of the cube: end_products() leaves all of it alone.
+    DevBuf<double> d_tbd_merit[2]; DevBuf<uint8_t> d_tbd_ptr, d_tbd_tmp; DevBuf<int32_t> d_tbd_shift;
+    DevBuf<uint32_t> d_tbd_cnt, d_tbd_off, d_tbd_paths; DevBuf<RtsTbdTrack> d_tbd_out;
+    uint32_t tbd_rx = 0, tbd_nd = 0, tbd_nb = 0, tbd_depth = 0, tbd_hd = 0, tbd_hr = 0, tbd_cur = 0; uint64_t tbd_frames = 0;
+    double tbd_time = 0.0, tbd_t0 = 0.0, tbd_dt = 0.0;
+    uint32_t tbd_ext_nseg = 0, tbd_ext_max = 0, tbd_ext_depth = 0; bool tbd_ext_valid = false;
     // OS-CFAR (rts_cube_detect_os): the alphas by training count go through a staged upload; os_tab keeps them on the host for the next
     // call with the same window, rank and pfa (os_tab_key), so that only training counts not seen yet are solved for; os_tab_sent: the
     // device holds os_tab as it stands
@@ -507,6 +519,9 @@ int rts_cube_plots_device(RtsContext* c, const RtsPlotParams& p, const RtsDetect
 // rts_track.hip.  list: pcap records, of which the first min(pcap, *n_dev) count (n_dev null: all); tcap: the table's size; T: the interval
 int rts_cube_track_tables(RtsContext* c);      // the two tables and their meta records, zeroed on first use
 int rts_cube_track_device(RtsContext* c, const RtsTrackParams& p, double T, const RtsPlot* list, const uint32_t* n_dev, uint32_t pcap, uint32_t tcap);
+// rts_tbd.hip.  Both on a validated call and a state whose buffers exist; the step writes merit map tbd_cur ^ 1 and ring slot `slot`
+int rts_cube_tbd_step_device(RtsContext* c, const RtsTbdParams& p, const double* map, bool first, double T, double dt, uint32_t slot);
+int rts_cube_tbd_extract_device(RtsContext* c, const RtsTbdExtractParams& e, uint32_t max_tracks);
 int rts_cube_doppler_device(RtsContext* c, uint32_t n_fft, double* out);      // rts_stft.hip: the slow-time transforms
 int rts_cube_stft_device(RtsContext* c, const RtsStftParams& p, const RtsStftPlan& plan, const double* window, double* out);
 int rts_cube_beat_device(RtsContext* c, uint32_t pulse_index, const RtsBeatParams& p, const RtsBeatPlan& plan, double cspeed, double carrier, int64_t base);      // rts_beat.hip
