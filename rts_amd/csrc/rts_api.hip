@@ -366,6 +366,8 @@ static int fill_target_placement(const RtsContext* c, uint32_t t, RtsTargetDev& 
     td.rinv[6] = (R[3]*R[7] - R[4]*R[6]) * id; td.rinv[7] = (R[1]*R[6] - R[0]*R[7]) * id; td.rinv[8] = (R[0]*R[4] - R[1]*R[3]) * id;
     td.px = m.position[0]; td.py = m.position[1]; td.pz = m.position[2];
     td.root = b.root;
+    // the horizon's tolerances (rts_horizon.hip); a placement that mirrors the mesh would swap the sides of every plane: no ray skips its walk then
+    { const RtsHorizonMesh& hz = c->scene->hz[t]; td.hz_h0 = (float)hz.h0 * 1.000001f; td.hz_rho = det > 0.0 ? (float)hz.rho * 0.999999f : 0.0f; }      // (narrowed to the safe side each)
     // bounding sphere of the placed hierarchy: image of the local box centre, half diagonal stretched by the
     // rotation's deviation from orthonormality, padded by 1e-6 of the world scale
     double cl[3], half2 = 0, wc[3], wmax = 0;
@@ -396,7 +398,7 @@ static int rts_hist_ensure(RtsContext* c, uint32_t n_hist)
     return RTS_OK;
 }
 
-// The zero block and, behind it, room for the primary-ray mask; p_counters points at the block's 16 counters.
+// The zero block and, behind it, room for the primary-ray mask; p_counters points at the block's 24 counters.
 static int rts_zero_block_reserve(RtsContext* c)
 {
     RTS_HIP(c->d_tile_ctr.reserve(RTS_ZERO_WORDS + RTS_MASK_WORDS + 64));
@@ -582,6 +584,7 @@ static int pulse_args_and_buffers(RtsContext* c, RtsPulseLaunch& L)
     a.recv_records = c->d_recv.p; a.all_records = c->d_all.p; a.counters = c->p_counters; a.block_counters = c->d_block_counters.p; a.dir_hist = c->d_dir_hist.p;
     a.hit_prim = c->d_hit_prim.p; a.hit_t = c->d_hit_t.p; a.stack_ovf = c->d_stack_ovf.p; a.child = c->d_child.p;
     a.rx_window_screen = c->tune.rx_window_screen ? 1u : 0u;
+    a.horizon = (c->params.flags & RTS_FLAG_NO_HORIZON) ? 0u : 1u;
     a.coop_versions = c->tune.coop_versions ? 1u : 0u;
     a.tile_ctr = c->d_tile_ctr.p;
     return RTS_OK;

@@ -144,7 +144,8 @@ __global__ void __launch_bounds__(256) k_leaves(const uint32_t* __restrict__ ord
                                                 const uint32_t* __restrict__ prim_targ, RtsLeafTri* __restrict__ leaves, uint32_t n,
                                                 double ox, double oy, double oz, RtsMaskFrame f, uint32_t* __restrict__ mask,
                                                 const RtsTargetMotion* __restrict__ motion = nullptr, uint32_t prim_blocks = 0, const double* __restrict__ n_local = nullptr,
-                                                double* __restrict__ n_world = nullptr, const uint32_t* __restrict__ n_targ = nullptr, uint32_t n_normals = 0)
+                                                double* __restrict__ n_world = nullptr, const uint32_t* __restrict__ n_targ = nullptr, uint32_t n_normals = 0,
+                                                const float* __restrict__ horizon = nullptr)      // [n][2] the primitives' S+, S- (RtsScene::d_horizon; null: every side closed)
 {
     __shared__ __attribute__((aligned(16))) uint32_t s_raw[MASK ? sizeof(RtsMaskLds) / 4 : 1];
     if (PLACE && blockIdx.x >= prim_blocks) {                            // (uniform per block) the blocks behind the primitives': normals
@@ -172,7 +173,7 @@ __global__ void __launch_bounds__(256) k_leaves(const uint32_t* __restrict__ ord
             RtsLeafTri L;
             L.p0x = p[0]; L.p0y = p[1]; L.p0z = p[2]; L.e0x = e0.x; L.e0y = e0.y; L.e0z = e0.z; L.e1x = e1.x; L.e1y = e1.y; L.e1z = e1.z;
             L.nx = nn.x; L.ny = nn.y; L.nz = nn.z;
-            L.prim = g; L.targ = prim_targ[g]; L.pad[0] = 0u; L.pad[1] = 0u;
+            L.prim = g; L.targ = prim_targ[g]; L.hz[0] = horizon ? horizon[2*(size_t)g] : 1.0f; L.hz[1] = horizon ? horizon[2*(size_t)g+1] : 1.0f;
             leaves[g] = L;
         }
     }
@@ -196,9 +197,9 @@ int rts_scene_place(RtsContext* c, const RtsLaunchConsts& lc, bool place, uint32
     if (place && sc->n_prims) {
         const unsigned gp = blocks_for(sc->n_prims, 256), gn = blocks_for(sc->n_normals, 256);
         if (mask) k_leaves<true, true, true><<<gp + gn, 256, 0, st>>>(sc->d_prim_order.p, sc->d_tri_vidx.p, sc->d_verts_local.p, sc->d_prim_targ.p, c->d_leaves.p, sc->n_prims, lc.ox, lc.oy, lc.oz, f, pmask,
-                                                                     c->p_motion, gp, sc->d_normals_local.p, c->d_normals_world.p, sc->d_norm_targ.p, sc->n_normals);
+                                                                     c->p_motion, gp, sc->d_normals_local.p, c->d_normals_world.p, sc->d_norm_targ.p, sc->n_normals, sc->d_horizon.p);
         else k_leaves<true, false, true><<<gp + gn, 256, 0, st>>>(sc->d_prim_order.p, sc->d_tri_vidx.p, sc->d_verts_local.p, sc->d_prim_targ.p, c->d_leaves.p, sc->n_prims, lc.ox, lc.oy, lc.oz, f, nullptr,
-                                                                  c->p_motion, gp, sc->d_normals_local.p, c->d_normals_world.p, sc->d_norm_targ.p, sc->n_normals);
+                                                                  c->p_motion, gp, sc->d_normals_local.p, c->d_normals_world.p, sc->d_norm_targ.p, sc->n_normals, sc->d_horizon.p);
         c->verts_world_valid = false;
         RTS_HIP(hipGetLastError());
         return RTS_OK;

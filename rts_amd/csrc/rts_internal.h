@@ -47,11 +47,17 @@ struct __attribute__((aligned(16))) RtsLeafTri {
     double p0x, p0y, p0z, e0x, e0y, e0z, e1x, e1y, e1z, nx, ny, nz;
     uint32_t prim;                  // global primitive id (targets concatenated in order)
     uint32_t targ;                  // target index
-    uint32_t pad[2];
+    float hz[2];                    // the primitive's horizon S+, S- (rts_horizon.hip; 1: the side is closed), copied by k_leaves from RtsScene::d_horizon
 };
 static_assert(sizeof(RtsLeafTri) == 112, "leaf size");
+// The horizon's tolerances, relative to a mesh's extent E (the diagonal of its bounding box); the budget they belong to: DESIGN.md section 4
+#define RTS_HZ_H0 9.5367431640625e-07        // 2^-20: heights up to h0 = RTS_HZ_H0 E count as "not above the plane"
+#define RTS_HZ_RHO 0.00390625                 // 2^-8: the horizon holds for every origin within rho = RTS_HZ_RHO E of the triangle
+#define RTS_HZ_DEGEN 9.5367431640625e-07      // 2^-20: a triangle whose smallest altitude is below RTS_HZ_DEGEN E switches its mesh's horizon off
+#define RTS_HZ_MARGIN 0.00390625f             // m_S = 2^-8: what the sine of a bounce ray's elevation must exceed S by (a placement may be off a rotation by 1e-3, rts_api.hip)
+struct RtsHorizonMesh { double extent, h0, rho; };      // per mesh; rho = 0: its horizon is off
 // the walk step decodes the record from the fetch's seven dwordx4 registers (rts_walk_step, rts_trace.hip): q0 = (p0x, p0y), q1 = (p0z, e0x),
-// q2 = (e0y, e0z), q3 = (e1x, e1y), q4 = (e1z, nx), q5 = (ny, nz), q6 = (prim, targ, pad, pad)
+// q2 = (e0y, e0z), q3 = (e1x, e1y), q4 = (e1z, nx), q5 = (ny, nz), q6 = (prim, targ, S+, S-)
 static_assert(offsetof(RtsLeafTri, p0x) == 0 && offsetof(RtsLeafTri, p0z) == 16 && offsetof(RtsLeafTri, e0y) == 32 && offsetof(RtsLeafTri, e1x) == 48 &&
               offsetof(RtsLeafTri, e1z) == 64 && offsetof(RtsLeafTri, ny) == 80 && offsetof(RtsLeafTri, prim) == 96 && offsetof(RtsLeafTri, targ) == 100,
               "leaf record offsets of the walk step's decode");
@@ -66,6 +72,7 @@ struct RtsTargetDev {               // per target, per pulse
     double rinv[9];                 // inverse of the pulse's rotation (identity when the target does not rotate)
     double px, py, pz;
     double cx, cy, cz, r2;          // bounding sphere of the placed target (world space, radius^2, padded)
+    float hz_h0, hz_rho;            // the horizon's tolerances for this target [m] (RtsHorizonMesh; hz_rho = 0: no bounce ray skips this target's walk)
     float ew;                       // extra origin slack of the target-space slab test [m]: covers the rounding of the world
                                     // vertices, of the exact test and of the world -> target mapping (~1e-12 of the world scale)
     int32_t root;                   // root node of the target's hierarchy, < 0: no (finite) geometry
@@ -114,12 +121,12 @@ static_assert(sizeof(RtsChildState) == 128, "child state size");
 #define RTS_SEG_STRIPES 8
 #define RTS_TILE_CTRS_LAYOUT ((RTS_XCD + 1) * RTS_SEG_STRIPES + 8)       // counters reserved per kernel in the zero block (>= RTS_TILE_CTRS, >= RTS_XCD * RTS_SEG_STRIPES; 80: the layout's size since round 4, kept so that no offset behind it moves)
 // the zero block: ONE fill per launch clears [draw counters of the ordinary kernel | of the cooperative kernel | head words: cost
-// sum lo, hi, head count, pad | the launch's 16 u64 counters | the order's bins | the bins' reservation counters of the two-launch order build]
+// sum lo, hi, head count, pad | the launch's 24 u64 counters | the order's bins | the bins' reservation counters of the two-launch order build]
 #define RTS_OFF_CTR_COOP (RTS_TILE_CTRS_LAYOUT * RTS_TILE_CTR_STRIDE)
 #define RTS_OFF_HEAD (2 * RTS_TILE_CTRS_LAYOUT * RTS_TILE_CTR_STRIDE)
 #define RTS_OFF_LIVE (RTS_OFF_HEAD + 4)       // 1 + the number of tiles at the front of this launch's order that cost more than a dead tile (0: unknown) -- written by the order build (rts_post.hip)
 #define RTS_OFF_COUNTERS (RTS_OFF_HEAD + 8)
-#define RTS_OFF_BINS (RTS_OFF_COUNTERS + 32)
+#define RTS_OFF_BINS (RTS_OFF_COUNTERS + 48)
 #define RTS_OFF_TAKEN (RTS_OFF_BINS + RTS_TILE_BUCKETS)
 #define RTS_ZERO_WORDS (RTS_OFF_TAKEN + RTS_TILE_BUCKETS)
 #ifndef RTS_RX_LDS
@@ -215,6 +222,7 @@ struct RtsTraceArgs {
     uint32_t pre_filter;            // 1: primary rays go through the f32 pre-filter (needs the mask when there is geometry)
     const uint32_t* pmask;          // primary-ray mask: RTS_MASK_N^2 bits, then one word != 0 if the mask is void for this pulse (null: none)
     uint32_t stack_lds;             // LDS stack entries in use (RTS_STACK_LDS; smaller only to exercise the spill path in tests)
+    uint32_t horizon;               // 1: a bounce ray that leaves its triangle above the triangle's horizon skips the walk of the target it left (RTS_FLAG_NO_HORIZON: 0)
 };
 
 // ----------------------------------------------------------------------------- host context
@@ -228,7 +236,7 @@ struct RtsPinned {
     RtsLaunchConsts lc;
     RtsTargetMotion motion[256];
     RtsTargetDev td[256];
-    unsigned long long cnt[16];
+    unsigned long long cnt[24];
     uint32_t G, pad;
     double rcs[256];
     double gsum[5 * RTS_PIN_GROUPS]; uint64_t gkey[RTS_PIN_GROUPS]; uint64_t grow[RTS_PIN_GROUPS]; uint32_t gmin[RTS_PIN_GROUPS];
@@ -252,10 +260,12 @@ struct RtsScene {
     DevBuf<RtsNode4> d_nodes4; DevBuf<uint32_t> d_leaf_prim;
     DevBuf<uint32_t> d_prim_order;  // [n_prims] the primitives by first appearance in d_leaf_prim (rts_prim_order.h): thread i of k_leaves handles primitive d_prim_order[i]
     DevBuf<RtsNode4> d_nodes4v;     // [n_nodes][8] octant versions of d_nodes4 (empty: none -- RTS_NODE_VERSIONS=0, or the scene too large for them)
+    DevBuf<float> d_horizon;        // [n_prims][2] the primitives' horizon S+, S- by global primitive id (rts_horizon.hip); k_leaves copies it into the leaf records
+    std::vector<RtsHorizonMesh> hz; // per mesh: extent and the horizon's tolerances
     double build_ms = 0; uint32_t builder = 0;     // how long the hierarchy build took, and where it ran (0 host SAH, 1 device LBVH)
     size_t device_bytes() const {
         return d_tri_vidx.cap * 4 + d_tri_nidx.cap * 4 + d_vert_targ.cap * 4 + d_norm_targ.cap * 4 + d_prim_targ.cap * 4 + d_verts_local.cap * 8 +
-               d_normals_local.cap * 8 + (d_nodes4.cap + d_nodes4v.cap) * sizeof(RtsNode4) + d_leaf_prim.cap * 4 + d_prim_order.cap * 4;
+               d_normals_local.cap * 8 + (d_nodes4.cap + d_nodes4v.cap) * sizeof(RtsNode4) + d_leaf_prim.cap * 4 + d_prim_order.cap * 4 + d_horizon.cap * 4;
     }
 };
 
@@ -494,6 +504,7 @@ void rts_gate_unref(RtsGate* g);            // ... and destroys the group's trac
 // implemented in the .hip units
 int rts_sah_build(const double* verts, const uint32_t* tris, uint32_t n_tris, double split_budget, std::vector<RtsNode4>& nodes, std::vector<uint32_t>& leaf_prim, RtsBlasInfo& out);
 int rts_lbvh_build_device(RtsContext* c, RtsScene* ns, const RtsSceneFlat& flat, const RtsSceneTuning& tune);
+int rts_horizon_build(RtsContext* c, RtsScene* ns, const RtsSceneFlat& flat);      // rts_horizon.hip: ns->d_horizon, ns->hz (behind scene_finish)
 int rts_scene_place(RtsContext* c, const RtsLaunchConsts& lc, bool place, uint32_t* pmask);      // placement kernels (place) + the primary-ray mask (lc.mask.n != 0)
 int rts_tile_costs_flush(RtsContext* c);      // merge the cost records of the last launch into the history now (before its launch shape goes away)
 int rts_tile_records_masked(RtsContext* c, uint32_t* d_out, uint32_t n);      // the history's records of the tiles the last launch traced, 0 elsewhere

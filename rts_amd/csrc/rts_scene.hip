@@ -207,6 +207,11 @@ extern "C" int rts_set_scene(RtsHandle c, const RtsMesh* meshes, uint32_t n_targ
     rts_tuning_read(&st, rts_env);
     { int rc = scene_build(c, ns.get(), meshes, flat, st); if (rc != RTS_OK) return rc; }
     { int rc = scene_finish(c, ns.get(), st); if (rc != RTS_OK) return rc; }
+    {   // the primitives' horizon (rts_horizon.hip): once per scene, like the order it is built along
+        const auto t_hz0 = std::chrono::steady_clock::now();
+        int rc = rts_horizon_build(c, ns.get(), flat); if (rc != RTS_OK) return rc;
+        if (st.debug_build) fprintf(stderr, "[rts] horizon: %.2f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_hz0).count());
+    }
     ns->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_build0).count();
     return scene_swap(c, ns.release());
 }
@@ -243,6 +248,7 @@ extern "C" int rts_scene_info(RtsHandle c, RtsSceneInfo* out)
     out->n_targets = (uint32_t)sc->meshes.size(); out->n_prims = sc->n_prims; out->n_nodes = sc->n_nodes; out->n_leaves = sc->n_leaves;
     out->handles_sharing = (uint32_t)sc->refs.load(); out->builder = sc->builder; out->build_ms = sc->build_ms;
     out->shared_device_bytes = sc->device_bytes(); out->version_bytes = sc->d_nodes4v.cap * sizeof(RtsNode4);
+    out->horizon_bytes = sc->d_horizon.cap * sizeof(float);
     out->handle_device_bytes = c->d_leaves.cap * sizeof(RtsLeafTri) + c->d_verts_world.cap * 8 + c->d_normals_world.cap * 8 + c->d_params.cap;
     return RTS_OK;
 }

@@ -409,6 +409,11 @@ __device__ __forceinline__ void rts_walk_coop(const RtsTraceArgs& a, int32_t* s_
 #define RTS_RXP_RW 15          // sqrt(widened radius^2) (1 + 1e-6)
 #define RTS_RXP_N 16
 struct RtsUnitLds { int32_t* stack; int32_t* exch; double* first; unsigned long long* path; uint32_t* n; const RtsRxDev* rx; const float (*rxp)[RTS_RXP_N]; uint32_t* lane_scratch; uint32_t* walk; };      // walk: per wave [walk iterations of the tile, walks]
+// THE SKIP FIELD: bits 23-31 of a lane's shaded-hit counter (n[RTS_BLOCK + tid]; the count itself stays below 2^22, like the segment count) hold (target + 1) whose walk the
+// lane's NEXT segment skips -- the bounce ray left that target's triangle above the triangle's horizon (rts_shade) --, 0: none.  The decision crosses from the shading of one
+// segment to the target loop of the next without a register, and without an LDS word of its own (the block's LDS is full at four waves per SIMD).
+#define RTS_SKIP_SHIFT 23
+#define RTS_SHADED_MASK 0x007fffffu
 // The payload of one ray chain between its segments (PerRayData fields that the walk does not touch but the shading does;
 // the first hit point, the path words and the counters live in LDS, RtsUnitLds).
 struct RtsRay { dvec3 dir, prev; double rayLength, power, doppler, refx, refy; uint32_t reflDepth, refrDepth; int received; bool end, chain_start; };
@@ -607,6 +612,29 @@ __device__ __forceinline__ bool rts_shade(const RtsTraceArgs& a, const RtsUnitLd
             doppler += dot3(mk3(T.vx, T.vy, T.vz), sub3(k1, k0));          // :314
         }
         dir = widen3(nd);                                                  // :303
+        if (!REFR) {
+            // THE HORIZON (rts_horizon.hip).  The record carries S+ / S-: an upper bound, per side of the triangle's plane, of h(x) / |x - q| over
+            // every point x of the SAME mesh more than h0 above the plane and every q within rho of the triangle.  The next segment starts at o = the hit point and
+            // runs along d = dir; c = |d . n| / (|d| |n|) is the sine of its elevation over the plane, the side the sign of d . n.  It skips this target's walk when
+            //   (1) c - delta / (tmin |d|) > S_side + m_S,   (2) c |d| tmin >= 2 (h0 + delta),   (3) 4 delta <= rho
+            // with tmin = SCENE_EPS_R (what the reference's bounce rays accept from: t > tmin) and delta >= the distance of o from the plane and from the triangle:
+            // o = prev + (double)hit_t * dir with hit_t NARROWED TO F32 -- off the f64 test's own t by <= 2^-24 |hit_t|, along an incoming direction of length ~1: 2^-22 |hit_t|
+            // with a factor 4 to spare -- plus 2^-45 (256 ulp) of the largest coordinate for the f64 roundings of the placed vertices, of the test and of this sum.
+            // Why nothing is lost: a point x = o + t d of the mesh with t > tmin has height h(x) >= t |d| c - delta >= 2 (h0 + delta) - delta > h0 by (2), so S bounds it:
+            // S >= h(x) / |x - o| (o is within rho of the triangle by (3)) >= (t |d| c - delta) / (t |d|) >= c - delta / (tmin |d|) -- against (1).  So the reference's
+            // closest hit over this target is "none", which is what skipping the walk produces.  m_S covers a placement that is a rotation only to 1e-3
+            // (fill_target_placement) and the rounding of c; a mesh whose horizon is off has S = 1 throughout, a mirrored placement rho = 0.  NaN anywhere: no skip.
+            uint32_t skip = 0u;
+            if (a.horizon) {
+                const double dn = dir.x*L.nx + dir.y*L.ny + dir.z*L.nz, dl = sqrt(dir.x*dir.x + dir.y*dir.y + dir.z*dir.z), nl = sqrt(L.nx*L.nx + L.ny*L.ny + L.nz*L.nz);
+                const double c = fabs(dn) / (dl * nl), S = (double)(dn > 0.0 ? L.hz[0] : L.hz[1]);
+                const double ht = fabs((double)hit_t);
+                const double delta = ht * 0x1p-22 + (fmax(fmax(fabs(prev.x), fabs(prev.y)), fabs(prev.z)) + ht) * 0x1p-45;
+                const double reach = dl * (double)SCENE_EPS_R;
+                if ((c - delta / reach > S + (double)RTS_HZ_MARGIN) && (c * reach >= 2.0 * ((double)T.hz_h0 + delta)) && (4.0 * delta <= (double)T.hz_rho)) skip = L.targ + 1u;
+            }
+            atomicAnd(&s_n[RTS_BLOCK + tid], RTS_SHADED_MASK); if (skip) atomicOr(&s_n[RTS_BLOCK + tid], skip << RTS_SKIP_SHIFT);      // (ds_and_b32 / ds_or_b32, no return)
+        }
         {   // direction history: the RCS angles of received rays are rebuilt from it (:320-326)
             const size_t plane = REFR ? (size_t)chain * (a.max_refl + 1) + reflDepth : (size_t)(reflDepth - 1);
             float* dh = a.dir_hist + plane * 3 * a.n_rays;
@@ -818,14 +846,14 @@ __device__ __forceinline__ void rts_primary_setup(const RtsTraceArgs& a, const R
     dir = (may_target || may_rx) ? rts_primary_dir(lc, slot) : mk3(0.0, 0.0, 0.0);
     prev = origin;
     s_first[tid] = 0.0; s_first[RTS_BLOCK + tid] = 0.0; s_first[2 * RTS_BLOCK + tid] = 0.0;
-    s_path[tid] = 0ULL; s_path[RTS_BLOCK + tid] = 0ULL;
+    s_path[tid] = 0ULL; s_path[RTS_BLOCK + tid] = 0ULL; atomicAnd(&L_.n[RTS_BLOCK + tid], RTS_SHADED_MASK);      // (no skip pending)
     rayLength = 0; power = 0; doppler = 0;
 }
 
 template <bool COUNT, bool KEEP_ALL, bool REFR, bool COOP, bool VERS = false>
 __device__ __forceinline__ void rts_trace_unit(const RtsTraceArgs& a, const RtsLaunchConsts& lc, const RtsUnitLds& L_, const uint32_t tid, const uint32_t gtid, const uint32_t lane,
                                                const uint32_t slot, const bool pre_on, const bool mask_on, const uint32_t D, const uint32_t max_refr, const dvec3& origin,
-                                               uint32_t& n_nodes, uint32_t& n_tris, bool& hard_overflow, unsigned long long (&lane_stats)[5],
+                                               uint32_t& n_nodes, uint32_t& n_tris, bool& hard_overflow, unsigned long long (&lane_stats)[11],
                                                const uint32_t pre = 0u)      // pre: bit 0 = k_trace ran the pre-filter already, bits 1 / 2 = its may_target / may_rx
 {
       int32_t* const s_stack = L_.stack; int32_t* const s_exch = L_.exch; double* const s_first = L_.first; unsigned long long* const s_path = L_.path; uint32_t* const s_n = L_.n;
@@ -870,11 +898,13 @@ __device__ __forceinline__ void rts_trace_unit(const RtsTraceArgs& a, const RtsL
             const bool primary = chain == 0 && chain_start;
             const bool may_hit = primary ? may_target : a.n_prims > 0;
             uint32_t steps = 0;                                                // walk steps of this lane in this segment (all targets)
+            bool escaped = false;                                              // (counting build) the segment skipped a target's walk above its triangle's horizon
             if (may_hit) {
                 float t_prune = RTS_DEFAULT_TMAX;
                 for (uint32_t targ = 0; targ < a.n_targets; targ++) {
                     const RtsTargetDev& TG = a.targets[targ];                            // uniform index: scalar loads
                     if (TG.root < 0) continue;
+                    if (!REFR && (s_n[RTS_BLOCK + tid] >> RTS_SKIP_SHIFT) == targ + 1u) { if (COUNT) escaped = true; continue; }      // the ray left this target above its triangle's horizon: it cannot meet it again (rts_shade)
                     {   // bounding sphere of the placed target (f64 on the live payload: no registers survive into the walk
                         // below, an f32 box test here cost a wave of occupancy); radius is padded on the host
                         const dvec3 q = mk3(TG.cx - prev.x, TG.cy - prev.y, TG.cz - prev.z);
@@ -936,6 +966,17 @@ __device__ __forceinline__ void rts_trace_unit(const RtsTraceArgs& a, const RtsL
                 lane_stats[3] += (unsigned long long)__popcll(__ballot(steps > 0u));      // segments that walked at all (the others: cleared by the pre-filter or by every target's bounding sphere)
                 lane_stats[4] += (unsigned long long)__popcll(__ballot(steps == 0u)) * smax;      // lane-steps issued to lanes that are in the round but NEVER STARTED a walk in it -- what packing the live launch indices of several tiles into dense waves could recover
             }
+            if (COUNT && escaped && (!COOP || (lane & (CG - 1u)) == 0u)) lane_stats[5] += 1ull;      // segments that skipped a target's walk (the horizon); per lane: every lane brings its own sum home
+            if (COUNT && !COOP) {
+                // the split by bounce round, by the first lane that is in the round at all (lane 0 may have left its chain): the wave's walk iterations and
+                // rounds, round 0 apart from rounds >= 1, and the rounds >= 1 in which the wave ran no walk at all
+                const unsigned long long act_ = __ballot(true);
+                if (lane == (uint32_t)(__ffsll((long long)act_) - 1)) {
+                    const uint32_t smax_ = L_.lane_scratch[2u * (tid >> 6)];
+                    if (primary) { lane_stats[9] += smax_; lane_stats[10] += 1ull; }
+                    else { lane_stats[8] += 1ull; lane_stats[6] += smax_; if (smax_ == 0u) lane_stats[7] += 1ull; }
+                }
+            }
             if (COUNT && COOP && steps) lane_stats[3] += 1ull;
             {   // (a cooperative unit of several rays: a ray whose chain has ended waits for the unit's other rays -- the walk's ballots are the wave's)
                 const bool go_on_ = rts_shade<KEEP_ALL, REFR, COOP, CG>(a, L_, tid, gtid, lane, slot, chain, D, max_refr, origin, primary, may_rx, best_t, best_leaf, best_prim, tmin, S, pending, refr_code0);
@@ -984,7 +1025,7 @@ __global__ void __launch_bounds__(RTS_BLOCK, (REFR && COOP) ? 2 : ((REFR || COOP
     // four waves per SIMD) by spilling to scratch.  They are touched per SHADED hit and at write-back only.
     __shared__ __attribute__((aligned(16))) double s_first[3 * RTS_BLOCK];
     __shared__ __attribute__((aligned(16))) unsigned long long s_path[2 * RTS_BLOCK];
-    __shared__ uint32_t s_n[3 * RTS_BLOCK];                      // segments, shaded hits, stack entries spilled (per lane)
+    __shared__ uint32_t s_n[3 * RTS_BLOCK];                      // segments, shaded hits (+ the skip field, RTS_SKIP_SHIFT), stack entries spilled (per lane)
     s_n[threadIdx.x] = 0; s_n[RTS_BLOCK + threadIdx.x] = 0; s_n[2 * RTS_BLOCK + threadIdx.x] = 0;
     {
         const uint32_t* src = reinterpret_cast<const uint32_t*>(a.lc); uint32_t* dst = reinterpret_cast<uint32_t*>(&s_lc);
@@ -1064,7 +1105,7 @@ __global__ void __launch_bounds__(RTS_BLOCK, (REFR && COOP) ? 2 : ((REFR || COOP
     __shared__ uint32_t s_lane_scratch[COUNT ? 2 * (RTS_BLOCK / 64) : 1];      // (counting build: per-wave max / sum of a round's walk steps)
     __shared__ uint32_t s_walk[2 * (RTS_BLOCK / 64)];           // per wave: walk iterations of the current tile (each walk's slowest lane), walks
     const RtsUnitLds ul = {s_stack, s_exch, s_first, s_path, s_n, s_rx, s_rxp, s_lane_scratch, s_walk};
-    unsigned long long lane_stats[5] = {0ull, 0ull, 0ull, 0ull, 0ull};
+    unsigned long long lane_stats[11] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
     // (LDS addresses formed from the scalar wave number AT EACH USE: hoisted out of the tile loop as vector registers they were
     // parked in scratch and reloaded eight times per draw)
 #define RTS_OPAQUE_S(x) ({ uint32_t o_ = (x); asm volatile("" : "+s"(o_)); o_; })
@@ -1271,11 +1312,14 @@ __global__ void __launch_bounds__(RTS_BLOCK, (REFR && COOP) ? 2 : ((REFR || COOP
     if (COUNT && !COOP && lane == 0 && lane_stats[0]) { atomicAdd(&a.counters[8], lane_stats[0]); atomicAdd(&a.counters[9], lane_stats[1]); atomicAdd(&a.counters[10], lane_stats[2]); }
     if (COUNT && (lane & (CG - 1u)) == 0u && lane_stats[3]) atomicAdd(&a.counters[11], lane_stats[3]);
     if (COUNT && !COOP && lane == 0 && lane_stats[4]) atomicAdd(&a.counters[15], lane_stats[4]);
+    if (COUNT && lane_stats[5]) atomicAdd(&a.counters[16], lane_stats[5]);      // (every lane its own: the skipped walks, and below what it saw as its rounds' first lane)
+    if (COUNT && !COOP && lane_stats[8]) { atomicAdd(&a.counters[17], lane_stats[6]); atomicAdd(&a.counters[18], lane_stats[7]); atomicAdd(&a.counters[19], lane_stats[8]); }
+    if (COUNT && !COOP && lane_stats[10]) { atomicAdd(&a.counters[20], lane_stats[9]); atomicAdd(&a.counters[21], lane_stats[10]); }
     // (the thread index is re-formed here from the wave's number -- scalar, kept since the start -- and the lane number instead of
     // being carried through the kernel: the allocator, at its 128-register limit, otherwise parks threadIdx.x in scratch in the
     // prologue and reloads it here)
     const uint32_t tid_e = (wave_u << 6) | __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-    unsigned long long n_seg = s_n[tid_e] & 0x003fffffu, n_shaded = s_n[RTS_BLOCK + tid_e], n_spill = s_n[2 * RTS_BLOCK + tid_e], n_nodes_w = n_nodes, n_tris_w = n_tris;
+    unsigned long long n_seg = s_n[tid_e] & 0x003fffffu, n_shaded = s_n[RTS_BLOCK + tid_e] & RTS_SHADED_MASK, n_spill = s_n[2 * RTS_BLOCK + tid_e], n_nodes_w = n_nodes, n_tris_w = n_tris;
     for (int off = 32; off > 0; off >>= 1) {
         n_seg += __shfl_down(n_seg, off); n_shaded += __shfl_down(n_shaded, off);
         if (COUNT) { n_nodes_w += __shfl_down(n_nodes_w, off); n_tris_w += __shfl_down(n_tris_w, off); }
@@ -1309,7 +1353,7 @@ __global__ void k_sum_counters(const unsigned long long* __restrict__ block_coun
 #define RTS_LD64(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
     if (t == 7) { const unsigned long long h = head_count ? (unsigned long long)__hip_atomic_load(head_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ULL; counters[7] = h; host_cnt[7] = h; }     // the order's head count travels home with the counters (sizes the next cooperative grid)
     if (t == 0) host_cnt[0] = RTS_LD64(&counters[0]);                          // received rays (appended by the trace kernels)
-    if ((t >= 8 && t <= 12) || t == 14 || t == 15) host_cnt[t] = RTS_LD64(&counters[t]);      // lane statistics and walked segments of the counting build; [12] cost records dropped, [14] tiles (| XCC mask << 56) on which the shader clock ran backwards, [15] never-started lane-steps
+    if ((t >= 8 && t <= 12) || (t >= 14 && t <= 21)) host_cnt[t] = RTS_LD64(&counters[t]);      // lane statistics and walked segments of the counting build; [12] cost records dropped, [14] tiles (| XCC mask << 56) on which the shader clock ran backwards, [15] never-started lane-steps, [16] segments that skipped a target's walk (the horizon), [17] walk iterations of the waves in bounce rounds >= 1, [18] such rounds without any walk, [19] such rounds, [20] [21] walk iterations and rounds of round 0
     const unsigned int k = t & 7u, lane = t >> 3;                              // 32 partial sums per counter
     unsigned long long v = 0;
     // (counting builds poison the rows before the launch -- rts_trace_launch -- : a row no block wrote is COUNTED, counters[13], instead

@@ -4,12 +4,13 @@ per-launch-index buffers (KEEP_ALL: payload, paths, RCS angles, per-segment hit 
 its order, and the segment / shaded / received counts are compared between
     host SAH tree + primary-ray pre-filter (the default)   |   host SAH tree, no pre-filter
     device LBVH with slab references + pre-filter          |   device LBVH, one reference per triangle, no pre-filter
-(the hierarchy and the filter may only change how much work is done).  Scenes: triangle soups (ordinary triangles, slivers,
+(the hierarchy and the filter may only change how much work is done), and between the default and RTS_FLAG_NO_HORIZON (bounce rays
+that leave their triangle above its horizon skip the walk of the target they left; the counting build says how many did).  Scenes: triangle soups (ordinary triangles, slivers,
 fans, duplicates, degenerate triangles) as one to three targets, placed near the origin, far from it or at Earth-centred
 coordinates, some behind or around the transmitter; beams from 1e-4 to 3 rad wide, pointed at / beside / away from the
 targets; 0-6 capture spheres, some containing the transmitter; W = 6..40; reflection depth 0..6; smooth / flat normals;
 optionally the refraction branch.
-   python tools/fuzz_equal.py [n_scenes] [seed0] [--oracle]  (about 0.1 s per scene on an MI355X; --oracle adds the comparison of
+   python tools/fuzz_equal.py [n_scenes] [seed0] [--oracle] [--solids]  (--solids: closed meshes of ellipsoids, on which the horizon engages; about 0.1 s per scene on an MI355X; --oracle adds the comparison of
                                                               the default launch with the CPU restatement's brute force)
 The counting builds of the same two host-tree launches say in how many scenes the pre-filter actually removed work."""
 import math
@@ -48,7 +49,17 @@ def soup(rng, n_reg, n_sliver, n_fan, scale):
     return dict(tris=t, verts=v, normals=nrm, refl_coeff=float(rng.choice([0.8, -0.6, 1.0, 0.3])), refr_index=float(rng.choice([1.0, 1.3, 2.0])))
 
 
-def random_scene(seed, version=4, big=False):
+def solid(rng, scale):
+    """--solids: a closed mesh without degenerate triangles -- one to three ellipsoids from the library's icosphere, overlapping (concave creases where they
+    cross) -- with analytic normals: what the horizon is built for (the soups above hold slivers and zero-area triangles, which switch a mesh's horizon off)"""
+    parts = []
+    for _ in range(int(rng.integers(1, 4))):
+        parts.append(scenes._ico_ellipsoid(int(rng.integers(1, 4)), tuple(scale * 10 ** rng.uniform(-0.3, 0.8, 3)), centre=tuple(rng.normal(0, 2.0 * scale, 3))))
+    v, t, n = scenes._merge(parts)
+    return dict(tris=t, verts=v, normals=n, refl_coeff=float(rng.uniform(0.2, 1.0)), refr_index=1.0)
+
+
+def random_scene(seed, version=4, big=False, solids=False):
     """versions 1, 2: the generator as it was when the regression seeds of tests/test_gpu_parity.py were found (1: as first
     written; 2: + the scenes biased towards an active pre-filter; 3: + many targets / receivers, NaN vertices, W = 1, deep chains;
     4 (round 5): + receivers the pre-filter's WINDOW screen has to judge -- capture spheres the beam crosses, the transmitter on or near their
@@ -63,7 +74,9 @@ def random_scene(seed, version=4, big=False):
         n_t = int(rng.integers(8, 40))                                # the linear loop over the targets' hierarchies
     meshes, motion = [], []
     for k in range(n_t):
-        if many_targets:
+        if solids:
+            meshes.append(solid(rng, scale))
+        elif many_targets:
             meshes.append(soup(rng, int(rng.integers(1, 12)), int(rng.integers(0, 4)), int(rng.integers(0, 5)), scale))
         else:
             k_big = 12 if big else 1                                   # --big: soups of a few thousand triangles
@@ -141,6 +154,8 @@ def random_scene(seed, version=4, big=False):
 def run(spec, **kw):
     tr = H.gpu_tracer(api, spec, keep_all=True, **kw)
     _, st = H.gpu_trace(api, spec, tr=tr)
+    if kw.get("count_traversal"):
+        st["skipped_walks"] = tr.walk_stats()[5]                     # bounce segments that skipped a target's walk above their triangle's horizon
     out = (tr.all_rays(spec["W"] ** 3), tr.received(), st, tr.scene_info())
     tr.close()
     return out
@@ -250,13 +265,14 @@ def against_oracle(spec, a):
 def main():
     args = [x for x in sys.argv[1:] if not x.startswith("--")]
     big = "--big" in sys.argv                                        # thousands of triangles per target, W up to 64
+    solids = "--solids" in sys.argv                                  # closed meshes of ellipsoids instead of triangle soups: scenes on which the horizon engages
     with_oracle = "--oracle" in sys.argv                             # also: the default launch against the oracle's brute force (CPU, slower)
     n = int(args[0]) if len(args) > 0 else 200
     seed0 = int(args[1]) if len(args) > 1 else 1
     tot = dict(filter_engaged=0, scenes=0, rays=0, segments=0, shaded=0, received=0, refs_host=0, refs_dev=0, prims=0)
     kinds = {}
     for seed in range(seed0, seed0 + n):
-        spec, place, aim = random_scene(seed, big=big)
+        spec, place, aim = random_scene(seed, big=big, solids=solids)
         try:
             os.environ.pop("RTS_SPLIT_BUDGET", None)
             a = run(spec)
@@ -278,6 +294,10 @@ def main():
             same(a, e, "seed %d: counting build" % seed); same(a, f, "seed %d: counting build, no pre-filter" % seed)
             assert e[2]["tri_tests"] <= f[2]["tri_tests"] and e[2]["node_visits"] <= f[2]["node_visits"], (seed, e[2], f[2])       # (the filter only ever REMOVES visits)
             tot["filter_engaged"] += 1 if e[2]["node_visits"] < f[2]["node_visits"] else 0
+            hz = run(spec, horizon=False); hzc = run(spec, horizon=False, count_traversal=True)      # the horizon: bounce rays that provably leave their target skip its walk; here every one walks
+            same(a, hz, "seed %d: horizon on / off" % seed); same(a, hzc, "seed %d: horizon on / off (counting build)" % seed)
+            assert hzc[2]["skipped_walks"] == 0 and e[2]["tri_tests"] <= hzc[2]["tri_tests"] and e[2]["node_visits"] <= hzc[2]["node_visits"], (seed, e[2], hzc[2])
+            tot["horizon_engaged"] = tot.get("horizon_engaged", 0) + (1 if e[2]["skipped_walks"] else 0); tot["skipped_walks"] = tot.get("skipped_walks", 0) + e[2]["skipped_walks"]
             same(a, c, "seed %d: host / device tree" % seed)
             same(a, d, "seed %d: host / device tree without references" % seed)
             if with_oracle:
