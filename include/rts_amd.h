@@ -488,6 +488,65 @@ int rts_waveform_eval(const RtsWaveform* w, const double* x, uint32_t n, double*
 int rts_cube_add_noise(RtsHandle h, uint32_t first_pulse, uint32_t n_pulses, double noise_power, uint64_t seed);
 int rts_noise_eval(uint64_t seed, const uint64_t* index, uint32_t n, double noise_power, double* out);
 
+/* ---------------------------------------------------------------- clutter and jammer sources: correlated Gaussian patches
+ * One call adds K = n_patches statistically independent patches to EVERY row of the attached cube.  One first-order complex
+ * autoregression per patch and range bin covers ground clutter, clutter with internal motion and barrage jammers.  Patch k has
+ *   spatial[k][rx]  its response on the receivers (complex128).  For a far-field patch this is its rts_steering_make row: a plane
+ *                   wave's snapshot equals its steering row;
+ *   power[k] >= 0   its mean power;
+ *   doppler[k]      its Doppler in cycles per pulse;
+ *   rho[k]          its pulse-to-pulse correlation in [0, 1] (NULL: all 1).  rho = 1 with the ridge's Doppler is ground clutter;
+ *                   rho slightly below 1 is clutter with internal motion (a Lorentzian line of that width); rho = 0 is a noise
+ *                   jammer, white in slow and fast time and of rank one across the receivers;
+ * and range_profile[bin] >= 0 (NULL: all 1) scales the power per bin: range law, swath gate, jammer blanking.
+ *     pole_k = rho_k (cos 2 pi f, sin 2 pi f),  f = doppler_k - floor(doppler_k)       on the host: the exact reflections about 1 and
+ *                                                                                      1/2, then libm (rts_steering_make's rule)
+ *     g_k    = sqrt(1 - rho_k rho_k)                                                   on the host
+ *     s_kr   = sqrt(power_k * profile_r)                                               IEEE sqrt, the same bits on both sides
+ *     w(k,r,p) = the generator of rts_cube_add_noise above with sqrt(noise_power / 2) = sqrt(0.5) (unit power), key
+ *                (lo32(seed), hi32(seed)) and Philox counter (r, p, k, 1): the fourth word keeps these draws apart from
+ *                rts_cube_add_noise's (counter (lo, hi, 0, 0)) under the same seed
+ *     c_kr0  = s_kr w(k,r,0)                                                           (s wr, s wi)
+ *     c_krp  = pole_k (x) c_kr,p-1 + (g_k * s_kr) w(k,r,p)                             a (x) b = (ar br - ai bi, ar bi + ai br);
+ *              when g_k == 0 the second term is not formed and no draw is made
+ *     cube[rx][p][r] += sum_k spatial[k][rx] (x) c_krp
+ * Fixed trees of IEEE basic operations without contraction, apart from the draw's log, cos and sin (OCML on the device, libm on
+ * the host: a few ulp).  The sum runs in ONE order, whatever the launch shape:
+ *   * partial j (0 <= j < 64) adds the terms of the patches k = j, j + 64, j + 128, .. in ascending k; its first term is the start value;
+ *   * the 64 partials then combine as j with j + 32 (j < 32), then + 16, + 8, + 4, + 2, + 1: partial j = partial j + partial (j + s);
+ *   * a partial without a patch is left out of the tree, it is not added as zero: where only partial j + s exists it becomes partial j;
+ *   * the total is added to the cube sample by one plain read-add-write.  No atomics -- the rule of rts_cube_add_noise.
+ * The recursion always starts at pulse 0 of the cube and covers all n_pulses rows: there is no row range.  A bin with
+ * profile_r == 0 is neither read nor written.  A patch with power_k == 0 is skipped: it brings no term to its partial (a partial
+ * whose patches are all skipped is a partial without a patch) and makes no draw; with every patch skipped nothing is written.
+ * By construction E|c_krp|^2 = power_k profile_r for every p, and E[c_krp conj(c_kr,p-1)] = pole_k power_k profile_r.
+ *   * The bins are independent.  Added after rts_cube_compress a patch set is clutter at the range resolution; added before, the
+ *     waveform's autocorrelation spreads it -- the right place for a jammer.
+ *   * With several GPUs add it ONCE, on one handle, after rts_cube_reduce -- the rule of the noise.
+ *   * Geometry that changes with range is several calls with different range_profile gates; calls with disjoint gates equal one
+ *     call with their union, byte for byte.
+ * Out of scope: range-correlated clutter, non-Gaussian (K-distributed) amplitude, deriving patch tables from a terrain mesh.
+ * rts_cube_add_sources is enqueued on the handle's stream; the tables go through one staged upload and the caller's arrays are
+ * free on return.  RTS_ERR_INVALID, naming the field, and the cube and the handle untouched: no cube attached; a NULL p, spatial,
+ * power or doppler; flags or reserved fields not 0; n_patches 0 or above RTS_SRC_MAX_PATCHES; n_rx above RTS_BEAM_MAX_RX;
+ * n_patches * n_rx above RTS_SRC_MAX_TABLE; an entry that is not finite; a negative power or profile; a rho outside [0, 1]; cube
+ * memory that is not 16-byte aligned.
+ * rts_sources_eval: pure host, the same rules (rts_source.h) on a host array [n_rx][n_pulses][n_bins] (interleaved re / im) that
+ * it adds to in place, *q standing in for the attached cube; the same validation, and the array untouched when it refuses. */
+#define RTS_SRC_MAX_PATCHES 1024u
+#define RTS_SRC_MAX_TABLE   4096u   /* bounds n_patches * n_rx: the spatial table, 64 KiB of complex128, sits in LDS */
+typedef struct RtsSourceParams {
+    uint32_t n_patches, flags;        /* 1 .. RTS_SRC_MAX_PATCHES; flags 0 */
+    const double* spatial;            /* host [n_patches][n_rx] interleaved re / im, finite */
+    const double* power;              /* host [n_patches], finite, >= 0 */
+    const double* doppler;            /* host [n_patches], finite, cycles per pulse */
+    const double* rho;                /* host [n_patches] in [0, 1], or NULL: all 1 */
+    const double* range_profile;      /* host [n_bins], finite, >= 0, or NULL: all 1 */
+    uint64_t seed, reserved[2];
+} RtsSourceParams;                    /* 72 bytes */
+int rts_cube_add_sources(RtsHandle h, const RtsSourceParams* p);
+int rts_sources_eval(const RtsCubeParams* q, const RtsSourceParams* p, double* cube_inout);
+
 /* CFAR detection.  Input z[rx][k][r], complex128 [n_rx][n_doppler][n_bins] (n_rx, n_bins of the attached cube): the handle's last
  * rts_cube_doppler output (device_map NULL; n_doppler is then its n_fft and the argument is ignored) or a caller device pointer
  * (n_doppler >= 1 required, any value).  Cell power P = re re + im im.

@@ -245,6 +245,17 @@ class RtsBeamParams(C.Structure):
 assert C.sizeof(RtsBeamParams) == 56
 
 
+RTS_SRC_MAX_PATCHES, RTS_SRC_MAX_TABLE, RTS_SRC_TILE = 1024, 4096, 8      # (RTS_SRC_TILE: rts_source.h's workgroup tile, bins)
+
+
+class RtsSourceParams(C.Structure):
+    _fields_ = [("n_patches", C.c_uint32), ("flags", C.c_uint32), ("spatial", C.c_void_p), ("power", C.c_void_p), ("doppler", C.c_void_p),
+                ("rho", C.c_void_p), ("range_profile", C.c_void_p), ("seed", C.c_uint64), ("reserved", C.c_uint64 * 2)]
+
+
+assert C.sizeof(RtsSourceParams) == 72
+
+
 RTS_ADAPT_TILE, RTS_ADAPT_MAX_PARTS = 64, 512
 
 
@@ -384,7 +395,7 @@ EXPORTS = ["rts_create", "rts_destroy", "rts_last_error", "rts_device_count", "r
            "rts_tile_records_get", "rts_tile_records_set", "rts_deal_tiles", "rts_set_tile_list",
            "rts_set_patterns", "rts_finalise_patterns", "rts_trace_pulse_end_patterns", "rts_pattern_eval",
            "rts_cube_set_waveform", "rts_cube_render", "rts_cube_compress", "rts_waveform_eval",
-           "rts_cube_add_noise", "rts_noise_eval", "rts_cube_detect", "rts_cube_detections_get",
+           "rts_cube_add_noise", "rts_noise_eval", "rts_cube_add_sources", "rts_sources_eval", "rts_cube_detect", "rts_cube_detections_get",
            "rts_cube_detect_os", "rts_cfar_os_alpha", "rts_cfar_os_eval",
            "rts_cube_plots", "rts_cube_plots_get", "rts_plots_eval",
            "rts_cube_track", "rts_cube_tracks_get", "rts_cube_tracks_set", "rts_cube_tracks_reset", "rts_cube_track_rounds", "rts_tracks_eval",
@@ -467,6 +478,8 @@ def lib():
         "rts_waveform_eval": [C.POINTER(RtsWaveform), vp, u32, vp],
         "rts_cube_add_noise": [vp, u32, u32, C.c_double, u64],
         "rts_noise_eval": [u64, vp, u32, C.c_double, vp],
+        "rts_cube_add_sources": [vp, C.POINTER(RtsSourceParams)],
+        "rts_sources_eval": [C.POINTER(RtsCubeParams), C.POINTER(RtsSourceParams), vp],
         "rts_cube_detect": [vp, C.POINTER(RtsCfarParams), vp, u32],
         "rts_cube_detections_get": [vp, vp, u32, C.POINTER(u32)],
         "rts_cube_detect_os": [vp, C.POINTER(RtsCfarOsParams), vp, u32],

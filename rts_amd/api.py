@@ -203,6 +203,44 @@ def noise_eval(seed, index, noise_power):
     return (out[:, 0] + 1j * out[:, 1]).reshape(shape)
 
 
+# ------------------------------------------------------------------------------- clutter and jammer sources (rts_source.h)
+def _source_params(spatial, power, doppler, rho, range_profile, seed, n_rx, n_bins):
+    """RtsSourceParams and the arrays it points to (keep them alive for the call)"""
+    sp = np.ascontiguousarray(np.asarray(spatial, np.complex128))
+    if sp.ndim != 2 or sp.shape[1] != n_rx:
+        raise ValueError("sources: spatial of shape %s for %d receivers ([n_patches][n_rx])" % (sp.shape, n_rx))
+    K = sp.shape[0]
+    keep = [sp]
+    p = L.RtsSourceParams()
+    p.n_patches, p.seed = K, int(seed)
+    p.spatial = ptr(sp.view(np.float64))
+    for name, value, n in (("power", power, K), ("doppler", doppler, K), ("rho", rho, K), ("range_profile", range_profile, n_bins)):
+        if value is None:
+            if name in ("power", "doppler"):
+                raise ValueError("sources: %s is required" % name)
+            continue
+        v = np.ascontiguousarray(np.asarray(value, np.float64).ravel())
+        if len(v) != n:
+            raise ValueError("sources: %s of %d values (%d expected)" % (name, len(v), n))
+        keep.append(v)
+        setattr(p, name, ptr(v))
+    return p, keep
+
+
+def sources_eval(cube, spatial, power, doppler, rho=None, range_profile=None, seed=0):
+    """rts_sources_eval (pure host): K independent first-order Gaussian patches added to a copy of the host array cube
+    [n_rx][n_pulses][n_bins] (complex), which is returned.  spatial [K][n_rx] is each patch's response on the receivers (a far-field
+    patch: its steering() row), power [K] its mean power, doppler [K] in cycles per pulse, rho [K] in [0, 1] its pulse-to-pulse
+    correlation (None: 1; 1 is ground clutter, a little below 1 clutter with internal motion, 0 a noise jammer), range_profile
+    [n_bins] >= 0 scales the power per bin (None: 1)"""
+    out = np.array(cube, np.complex128, order="C", copy=True)
+    n_rx, n_pulses, nb = out.shape
+    q = L.RtsCubeParams(n_rx, n_pulses, nb, 0, 0.0, 1.0)
+    p, keep = _source_params(spatial, power, doppler, rho, range_profile, seed, n_rx, nb)
+    check(L.lib().rts_sources_eval(C.byref(q), C.byref(p), ptr(out.view(np.float64))))
+    return out
+
+
 # ------------------------------------------------------------------------------- ordered-statistic CFAR (rts_cfar_os.h)
 def cfar_os_n0(guard, train):
     """training cells of a full window: guard and train are (range, Doppler) cells on each side"""
@@ -1317,6 +1355,16 @@ class Tracer:
         if count is None:
             count = self._cube_shape[1] - first
         check(L.lib().rts_cube_add_noise(self.h, first, count, float(noise_power), int(seed)))
+
+    def cube_add_sources(self, spatial, power, doppler, rho=None, range_profile=None, seed=0):
+        """rts_cube_add_sources: K independent first-order Gaussian patches (clutter, jammers) added to every row of the attached cube
+        on the device; the arguments are sources_eval's.  Each draw is a function of (seed, bin, pulse, patch) alone and the sum over
+        the patches runs in one fixed order, so the result does not depend on the launch"""
+        shape = getattr(self, "_cube_shape", None)
+        if shape is None:
+            check(L.lib().rts_cube_add_sources(self.h, None))          # (the library's own refusal: no cube)
+        p, keep = _source_params(spatial, power, doppler, rho, range_profile, seed, shape[0], shape[2])
+        check(L.lib().rts_cube_add_sources(self.h, C.byref(p)))
 
     def cube_detect(self, guard=(2, 2), train=(8, 4), mode="ca", pfa=None, alpha=None, local_max=True, pri=0.0, device_ptr=None,
                     n_doppler=None, max_detections=0, fetch=True):

@@ -194,6 +194,64 @@ extern "C" int rts_cube_add_noise(RtsHandle c, uint32_t first_pulse, uint32_t n_
     return rts_cube_noise_device(c, first_pulse, n_pulses, sqrt(noise_power / 2.0), seed);
 }
 
+// ------------------------------------------------------------------------------------- clutter and jammer sources
+// (rts_amd.h: RtsSourceParams; the rules, the validation, the evaluator and the launch plan are rts_source.h, shared with the kernel, rts_source.hip)
+static int rts_sources_check(const char* who, const RtsSourceParams* p, uint32_t n_rx, uint32_t n_bins)
+{
+    if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
+    uint32_t bad = 0;
+    switch (rts_src_check(p, n_rx, n_bins, &bad)) {
+        case 0: return RTS_OK;
+        case 1: rts_set_error("%s: n_patches = %u (1 .. %u, RTS_SRC_MAX_PATCHES)", who, p->n_patches, RTS_SRC_MAX_PATCHES); break;
+        case 2: rts_set_error("%s: unknown flags 0x%x", who, p->flags); break;
+        case 3: rts_set_error("%s: reserved fields must be 0", who); break;
+        case 4: rts_set_error("%s: null spatial", who); break;
+        case 5: rts_set_error("%s: null power", who); break;
+        case 6: rts_set_error("%s: null doppler", who); break;
+        case 7: rts_set_error("%s: n_rx = %u receivers: more than %u (RTS_BEAM_MAX_RX)", who, n_rx, RTS_BEAM_MAX_RX); break;
+        case 8: rts_set_error("%s: n_patches * n_rx = %u * %u: more than %u (RTS_SRC_MAX_TABLE: the spatial table sits in a workgroup's LDS)", who, p->n_patches, n_rx, RTS_SRC_MAX_TABLE); break;
+        case 10: rts_set_error("%s: spatial[%u][%u] is not finite", who, bad / n_rx, bad % n_rx); break;
+        case 11: rts_set_error("%s: power[%u] = %g (finite, >= 0)", who, bad, p->power[bad]); break;
+        case 12: rts_set_error("%s: doppler[%u] is not finite", who, bad); break;
+        case 13: rts_set_error("%s: rho[%u] = %g outside [0, 1]", who, bad, p->rho[bad]); break;
+        default: rts_set_error("%s: range_profile[%u] = %g (finite, >= 0)", who, bad, p->range_profile[bad]); break;
+    }
+    return RTS_ERR_INVALID;
+}
+
+extern "C" int rts_sources_eval(const RtsCubeParams* q, const RtsSourceParams* p, double* cube_inout)
+{
+    const char* who = "rts_sources_eval";
+    if (!q || q->n_rx == 0 || q->n_pulses == 0 || q->n_bins == 0) { rts_set_error("%s: bad cube parameters", who); return RTS_ERR_INVALID; }
+    { int rc = rts_sources_check(who, p, q->n_rx, q->n_bins); if (rc != RTS_OK) return rc; }
+    if (!cube_inout) { rts_set_error("%s: null array", who); return RTS_ERR_INVALID; }
+    std::vector<double> work(rts_src_work_doubles(p->n_patches));
+    rts_sources_eval_host(q, p, cube_inout, work.data());
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_add_sources(RtsHandle c, const RtsSourceParams* p)
+{
+    const char* who = "rts_cube_add_sources";
+    CHECK_HANDLE(c);
+    NEED_CUBE(c, who, "no cube (call rts_cube_attach first)");
+    const RtsCubeParams& q = c->cube.params;
+    { int rc = rts_sources_check(who, p, q.n_rx, q.n_bins); if (rc != RTS_OK) return rc; }
+    if ((uintptr_t)c->cube.p & 15u) { rts_set_error("%s: the cube's device memory is not 16-byte aligned", who); return RTS_ERR_INVALID; }
+    const RtsSrcPlan plan = rts_src_plan(q.n_rx, q.n_bins, p->n_patches, p->range_profile != nullptr);
+    if (!plan.supported) { rts_set_error("%s: a cube of %u receivers x %u bins with %u patches has no launch plan", who, q.n_rx, q.n_bins, p->n_patches); return RTS_ERR_INVALID; }
+    CHECK_CLOSED(c);
+    const uint64_t live = rts_src_live_mask(p->n_patches, p->power);
+    if (!live) return RTS_OK;                                   // every patch has power 0: nothing is written
+    // the table -> pinned staging -> the device, on the stream; the staging grows to the largest table this cube's bins allow
+    const size_t most = 2u * ((size_t)RTS_SRC_MAX_TABLE + 2u * RTS_SRC_MAX_PATCHES) + q.n_bins;
+    double* tab = nullptr;
+    RTS_HIP(c->cube.src_tab.begin(plan.table_doubles, most, most, &tab));
+    rts_src_table(p, q.n_rx, q.n_bins, tab);
+    RTS_HIP(c->cube.src_tab.send(plan.table_doubles, c->stream));
+    return rts_cube_sources_device(c, plan, p->n_patches, p->range_profile != nullptr, p->seed, live, c->cube.src_tab.dev.p);
+}
+
 // The checks rts_cube_detect, rts_cube_detect_os and rts_cfar_os_eval share, in the order each of them applies them.
 // The map of a device detector: the caller's (n_doppler rows, 16-byte aligned) or the handle's last Doppler map.
 static int rts_cfar_map(RtsContext* c, const char* who, const void* device_map, const double** map, uint32_t* n_doppler)

@@ -22,6 +22,7 @@
 #include "rts_cfar_os.h"          // CFAR: what every detector shares (rts_cfar.h: window, training count, local maximum, refinement, record); OS: rank rule, alphas, the host evaluator
 #include "rts_track.h"            // the tracker step: wrap, prediction, d2, the edge, the candidate order, update, coast, start, the validation, the host evaluator
 #include "rts_tbd.h"              // track-before-detect: the shift table, the score, the window's first maximum, the candidate, the walk, the record, the validation, the host evaluators
+#include "rts_source.h"           // clutter and jammer sources: pole, scale, draw, recursion, partials and tree, the validation, the host evaluator and the host-only plan of the launch
 #include "rts_plot.h"             // plot extraction: key, unwrap, adjacency, neighbour intervals, the blocked sums, the record, the validation, the host evaluator
 #include "rts_owned.h"            // DevBuf, PinBuf, StagedUpload: device and pinned host memory that frees itself
 #include "rts_launch_plan.h"      // RTS_BLOCK, RTS_WTILE, RTS_COOP_GROUP, RTS_STACK_OVF and the host arithmetic of a launch
@@ -96,6 +97,7 @@ static_assert(sizeof(RtsDetection) == 72 && sizeof(RtsCfarParams) == 72 && sizeo
 static_assert(sizeof(RtsPlot) == 104 && sizeof(RtsPlotParams) == 56, "plot ABI sizes (rts_amd/_lib.py mirrors them)");
 static_assert(sizeof(RtsTrack) == 88 && sizeof(RtsTrackParams) == 96, "track ABI sizes (rts_amd/_lib.py mirrors them)");
 static_assert(sizeof(RtsTbdParams) == 72 && sizeof(RtsTbdExtractParams) == 40 && sizeof(RtsTbdTrack) == 48, "track-before-detect ABI sizes (rts_amd/_lib.py mirrors them)");
+static_assert(sizeof(RtsSourceParams) == 72, "source ABI size (rts_amd/_lib.py mirrors it)");
 // what the device keeps beside each of the two track tables: the next id, the records stored, the total a table without end would
 // hold (stored + the new tracks turned away), the rounds the matching took
 struct RtsTrackMeta { uint64_t next_id; uint32_t n, total, rounds, reserved; };
@@ -371,6 +373,9 @@ struct RtsCubeState {
     // beamforming (rts_cube_beamform, rts_beam.hip): the output, for rts_cube_beam_get; the call's weight table goes through a staged upload
     RtsCubeProduct beam;
     StagedUpload<double> beam_w;
+    // clutter and jammer sources (rts_cube_add_sources, rts_source.hip): the call's table (rts_src_table) goes through a staged upload;
+    // the call changes the cube in place, so there is no product
+    StagedUpload<double> src_tab;
     // adaptive beamforming (rts_cube_covariance, rts_cube_mvdr, rts_adapt.hip): the covariance and its n_rx, for rts_cube_covariance_get
     // and rts_cube_mvdr without device_cov, and the parts' partial sums; the weights, for rts_cube_mvdr_get; the call's steering rows go
     // through a staged upload; the solves' status words (0: library-owned output, 1: caller-owned)
@@ -537,6 +542,7 @@ int rts_cube_doppler_device(RtsContext* c, uint32_t n_fft, double* out);      //
 int rts_cube_stft_device(RtsContext* c, const RtsStftParams& p, const RtsStftPlan& plan, const double* window, double* out);
 int rts_cube_beat_device(RtsContext* c, uint32_t pulse_index, const RtsBeatParams& p, const RtsBeatPlan& plan, double cspeed, double carrier, int64_t base);      // rts_beat.hip
 int rts_cube_range_device(RtsContext* c, const RtsRangeParams& p, const RtsRangePlan& plan, const double* window, double* out);
+int rts_cube_sources_device(RtsContext* c, const RtsSrcPlan& plan, uint32_t K, bool has_profile, uint64_t seed, uint64_t live, const double* table);      // rts_source.hip
 int rts_cube_beam_device(RtsContext* c, const RtsBeamParams& p, const RtsBeamPlan& plan, const double* in, uint64_t rx_stride, const double* weights, void* out);      // rts_beam.hip
 int rts_cube_cov_device(RtsContext* c, const RtsCovSet& set, const RtsCovPlan& plan, uint32_t n_taps, const double* in, uint64_t rx_stride, double* part, double* out);      // rts_adapt.hip
 int rts_cube_mvdr_device(RtsContext* c, const RtsMvdrPlan& plan, uint32_t n_rx, uint32_t n_beams, double loading, const double* cov, const double* steering, uint32_t* status, double* out);

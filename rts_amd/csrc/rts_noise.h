@@ -8,8 +8,18 @@
 //   * with several GPUs it is added ONCE, on one handle, after rts_cube_reduce or the caller's all-reduce (else it is summed N times).
 // Fixed trees of IEEE basic operations, compiled with -ffp-contract=off; log, sin and cos are the platform's (OCML on the device,
 // libm on the host), so the two agree to a few ulp, not bit for bit.
+// rts_noise_sample4 takes the four counter words as they are: the correlated sources (rts_source.h) draw under counter
+// (bin, pulse, patch, 1), which no flat index of the cube reaches (its words 2 and 3 are 0).
+// Includes nothing of HIP: the library's units bring rts_device_math.h's RTS_HD first, a host compiler gets the plain form.
 #pragma once
-#include "rts_device_math.h"
+#include <math.h>
+#include <stdint.h>
+#ifndef RTS_HD
+#define RTS_HD static inline          // (a host compiler; the library's units have rts_device_math.h's __host__ __device__ form)
+#endif
+#ifndef RTS_PI
+#define RTS_PI 3.14159265358979323846
+#endif
 
 #define RTS_PHILOX_M0 0xD2511F53u
 #define RTS_PHILOX_M1 0xCD9E8D57u
@@ -27,14 +37,20 @@ RTS_HD void rts_philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1)
     }
 }
 
-// the complex noise sample of flat index i under seed, scaled by sigma = sqrt(noise_power / 2): E|n|^2 = 2 sigma^2
-RTS_HD void rts_noise_sample(uint64_t seed, uint64_t i, double sigma, double* re, double* im)
+// the complex sample of counter (c0, c1, c2, c3) under seed, scaled by sigma: E|n|^2 = 2 sigma^2
+RTS_HD void rts_noise_sample4(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, double sigma, double* re, double* im)
 {
-    uint32_t c[4] = {(uint32_t)i, (uint32_t)(i >> 32), 0u, 0u};
+    uint32_t c[4] = {c0, c1, c2, c3};
     rts_philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
     const uint64_t a = (((uint64_t)c[0] << 32) | c[1]) >> 11, b = (((uint64_t)c[2] << 32) | c[3]) >> 11;
     const double u1 = (double)(a + 1) * 0x1p-53, u2 = (double)b * 0x1p-53;
     const double sr = sigma * sqrt(-2.0 * log(u1));
     const double ang = 2.0 * RTS_PI * u2;
     *re = sr * cos(ang); *im = sr * sin(ang);
+}
+
+// the complex noise sample of flat index i under seed, scaled by sigma = sqrt(noise_power / 2)
+RTS_HD void rts_noise_sample(uint64_t seed, uint64_t i, double sigma, double* re, double* im)
+{
+    rts_noise_sample4(seed, (uint32_t)i, (uint32_t)(i >> 32), 0u, 0u, sigma, re, im);
 }
