@@ -68,6 +68,10 @@ typedef struct RtsParams {
                                      triangle's horizon -- how high the rest of the same mesh rises over the triangle's plane, found once per
                                      scene (rts_get_horizon) -- provably misses that mesh and skips its walk.  Results are identical either
                                      way (tested); refracting launches never skip. */
+#define RTS_FLAG_NO_HORIZON_SECTORS 64u /* the horizon by its isotropic rule only.  By default a bounce ray that the isotropic rule keeps walking is
+                                     tested again against the horizon of the azimuth quadrant it leaves into (four values per side of a
+                                     primitive, rts_get_horizon_sectors): a wing rises over a fuselage triangle's plane in one direction only.
+                                     Results are identical either way (tested); for A/B runs, the tests and the fuzzer. */
 #define RTS_FLAG_COUNT_TRAVERSAL 2u /* run the counting build of the trace kernel (node visits and
                                      triangle tests per segment, for the roofline accounting)        */
 
@@ -199,14 +203,19 @@ typedef struct RtsSceneInfo {
                                     vertices and normals); per-launch buffers (rts_reserve) not included       */
     uint64_t version_bytes;      /* of shared_device_bytes: the eight octant versions of the node records (0: the
                                     scene has none -- RTS_NODE_VERSIONS=0, or too large for them)               */
-    uint64_t horizon_bytes;      /* of shared_device_bytes: the primitives' horizon, two floats each (rts_get_horizon)      */
+    uint64_t horizon_bytes;      /* of shared_device_bytes: the primitives' horizon, 2 x 4 bytes each (rts_get_horizon)    */
 } RtsSceneInfo;
 int rts_scene_info(RtsHandle h, RtsSceneInfo* out);
-/* The horizon of the scene's primitives as the leaf records carry it: out[n_prims][2] = (S+, S-) by global primitive id, S+ on the side
+/* The isotropic horizon of the scene's primitives (per side the largest of its four azimuth sectors, below): out[n_prims][2] = (S+, S-) by global primitive id, S+ on the side
  * the normal (p0 - p2) x (p1 - p0) points to.  S = an upper bound of the sine of the elevation, over the triangle's plane, at which any
  * other point of the same mesh is seen from the triangle (0: nothing rises above the plane on that side; 1: the side is closed, or the
  * mesh's horizon is off -- a degenerate triangle, too large a mesh). */
 int rts_get_horizon(RtsHandle h, float* out, uint32_t capacity_prims);
+/* The horizon by azimuth sector, as the leaf records carry it: out[n_prims][2][4] bytes by global primitive id -- side (+, -), then the quadrant
+ * of the departing ray's in-plane azimuth in the primitive's own frame u = e0 = p1 - p0, w = n x e0: sector = (a.u < 0 ? 1 : 0) | (a.w < 0 ? 2 : 0).
+ * A byte b stands for b / 255, rounded up by the build; 0 is exactly 0, 255 closed.  rts_get_horizon returns, per side, the largest of the four
+ * decoded: the isotropic S. */
+int rts_get_horizon_sectors(RtsHandle h, uint8_t* out, uint32_t capacity_prims);
 
 /* ---------------------------------------------------------------- launch
  * Replaces rtContextValidate/Compile/Launch3D (ray_tracer.cpp:1126-1165): places the targets,
@@ -244,7 +253,7 @@ int rts_get_block_timeline(RtsHandle h, double* out, uint32_t n);
 /* Lane statistics of the last launch's traversal (counting build, RTS_FLAG_COUNT_TRAVERSAL): out3[0] walk iterations issued x 64
  * lanes, out3[1] the part issued to lanes that took part in their tile's bounce round, out3[2] walk steps actually taken. */
 int rts_get_lane_stats(RtsHandle h, uint64_t* out3);
-int rts_get_walk_stats(RtsHandle h, uint64_t* out, uint32_t n);   /* out[0..2] as rts_get_lane_stats; [3] segments that walked; [4] lane-steps issued to lanes that are in a bounce round but never started a walk in it; [5] bounce segments that skipped a target's walk above their triangle's horizon; [6] walk iterations of the waves in bounce rounds >= 1, [7] bounce rounds >= 1 in which the wave ran no walk at all, [8] bounce rounds >= 1, [9] walk iterations of the waves in round 0 (the primaries), [10] rounds 0 (counting builds; n <= 11) */
+int rts_get_walk_stats(RtsHandle h, uint64_t* out, uint32_t n);   /* out[0..2] as rts_get_lane_stats; [3] segments that walked; [4] lane-steps issued to lanes that are in a bounce round but never started a walk in it; [5] bounce segments that skipped a target's walk above their triangle's horizon by the isotropic rule ([11]: by an azimuth sector only); [6] walk iterations of the waves in bounce rounds >= 1, [7] bounce rounds >= 1 in which the wave ran no walk at all, [8] bounce rounds >= 1, [9] walk iterations of the waves in round 0 (the primaries), [10] rounds 0 (counting builds; n <= 12) */
 int rts_received_count(RtsHandle h, uint64_t* count);
 int rts_get_received(RtsHandle h, struct PerRayData* rays, int32_t* paths, double* rcs_angles, uint64_t* slots,
                      uint64_t capacity);

@@ -830,11 +830,11 @@ _PY_LAP = {} if _os.environ.get("RTS_PY_LAP") == "1" else None
 class Tracer:
     """One RtsHandle: scene + receivers + per-pulse launch on one GPU."""
 
-    def __init__(self, width, max_refl, max_refr=0, smooth=True, device=0, keep_all=False, count_traversal=False, device_build=None, pre_filter=True, horizon=True):
+    def __init__(self, width, max_refl, max_refr=0, smooth=True, device=0, keep_all=False, count_traversal=False, device_build=None, pre_filter=True, horizon=True, horizon_sectors=True):
         p = L.RtsParams(width, max_refl, max_refr, 1 if smooth else 0, device,
                         (L.RTS_FLAG_KEEP_ALL_RAYS if keep_all else 0) | (L.RTS_FLAG_COUNT_TRAVERSAL if count_traversal else 0) |
                         (0 if device_build is None else (L.RTS_FLAG_DEVICE_BUILD if device_build else L.RTS_FLAG_HOST_BUILD)) |      # None: the library's default (device)
-                         (0 if pre_filter else L.RTS_FLAG_NO_PREFILTER) | (0 if horizon else L.RTS_FLAG_NO_HORIZON))
+                         (0 if pre_filter else L.RTS_FLAG_NO_PREFILTER) | (0 if horizon else L.RTS_FLAG_NO_HORIZON) | (0 if horizon_sectors else L.RTS_FLAG_NO_HORIZON_SECTORS))
         self.h = C.c_void_p()
         check(L.lib().rts_create(C.byref(p), C.byref(self.h)))
         self.width = width; self.max_refl = max_refl; self.depth = max_refl + (2 if max_refr else 0)
@@ -865,15 +865,23 @@ class Tracer:
         self.n_targets = len(meshes)
 
     def horizon(self, n_prims):
-        """the scene's per-primitive horizon, [n_prims][2] = (S+, S-) by global primitive id (rts_get_horizon)"""
+        """the scene's per-primitive isotropic horizon, [n_prims][2] = (S+, S-) by global primitive id: per side the largest of its
+        four sectors (rts_get_horizon)"""
         out = np.zeros((int(n_prims), 2), np.float32)
         check(L.lib().rts_get_horizon(self.h, ptr(out), int(n_prims)))
         return out
 
+    def horizon_sectors(self, n_prims):
+        """the horizon by azimuth sector as the leaf records carry it, uint8 [n_prims][2][4] = side (+, -), quadrant of the in-plane
+        azimuth in the primitive's frame (e0, n x e0); a byte b stands for b / 255 (rts_get_horizon_sectors)"""
+        out = np.zeros((int(n_prims), 2, 4), np.uint8)
+        check(L.lib().rts_get_horizon_sectors(self.h, ptr(out), int(n_prims)))
+        return out
+
     def walk_stats(self):
-        """the counting build's walk statistics of the last launch (rts_get_walk_stats), eleven values"""
-        ls = (C.c_uint64 * 11)()
-        check(L.lib().rts_get_walk_stats(self.h, ls, 11))
+        """the counting build's walk statistics of the last launch (rts_get_walk_stats), twelve values"""
+        ls = (C.c_uint64 * 12)()
+        check(L.lib().rts_get_walk_stats(self.h, ls, 12))
         return [int(v) for v in ls]
 
     def share_scene(self, other):

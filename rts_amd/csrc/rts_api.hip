@@ -584,7 +584,7 @@ static int pulse_args_and_buffers(RtsContext* c, RtsPulseLaunch& L)
     a.recv_records = c->d_recv.p; a.all_records = c->d_all.p; a.counters = c->p_counters; a.block_counters = c->d_block_counters.p; a.dir_hist = c->d_dir_hist.p;
     a.hit_prim = c->d_hit_prim.p; a.hit_t = c->d_hit_t.p; a.stack_ovf = c->d_stack_ovf.p; a.child = c->d_child.p;
     a.rx_window_screen = c->tune.rx_window_screen ? 1u : 0u;
-    a.horizon = (c->params.flags & RTS_FLAG_NO_HORIZON) ? 0u : 1u;
+    a.horizon = (c->params.flags & RTS_FLAG_NO_HORIZON) ? 0u : (c->params.flags & RTS_FLAG_NO_HORIZON_SECTORS) ? 1u : 2u;
     a.coop_versions = c->tune.coop_versions ? 1u : 0u;
     a.tile_ctr = c->d_tile_ctr.p;
     return RTS_OK;

@@ -145,7 +145,7 @@ __global__ void __launch_bounds__(256) k_leaves(const uint32_t* __restrict__ ord
                                                 double ox, double oy, double oz, RtsMaskFrame f, uint32_t* __restrict__ mask,
                                                 const RtsTargetMotion* __restrict__ motion = nullptr, uint32_t prim_blocks = 0, const double* __restrict__ n_local = nullptr,
                                                 double* __restrict__ n_world = nullptr, const uint32_t* __restrict__ n_targ = nullptr, uint32_t n_normals = 0,
-                                                const float* __restrict__ horizon = nullptr)      // [n][2] the primitives' S+, S- (RtsScene::d_horizon; null: every side closed)
+                                                const uint32_t* __restrict__ horizon = nullptr)      // [n][2] the primitives' sector bytes (RtsScene::d_horizon; null: every side closed)
 {
     __shared__ __attribute__((aligned(16))) uint32_t s_raw[MASK ? sizeof(RtsMaskLds) / 4 : 1];
     if (PLACE && blockIdx.x >= prim_blocks) {                            // (uniform per block) the blocks behind the primitives': normals
@@ -173,7 +173,7 @@ __global__ void __launch_bounds__(256) k_leaves(const uint32_t* __restrict__ ord
             RtsLeafTri L;
             L.p0x = p[0]; L.p0y = p[1]; L.p0z = p[2]; L.e0x = e0.x; L.e0y = e0.y; L.e0z = e0.z; L.e1x = e1.x; L.e1y = e1.y; L.e1z = e1.z;
             L.nx = nn.x; L.ny = nn.y; L.nz = nn.z;
-            L.prim = g; L.targ = prim_targ[g]; L.hz[0] = horizon ? horizon[2*(size_t)g] : 1.0f; L.hz[1] = horizon ? horizon[2*(size_t)g+1] : 1.0f;
+            L.prim = g; L.targ = prim_targ[g]; L.hz[0] = horizon ? horizon[2*(size_t)g] : 0xffffffffu; L.hz[1] = horizon ? horizon[2*(size_t)g+1] : 0xffffffffu;
             leaves[g] = L;
         }
     }

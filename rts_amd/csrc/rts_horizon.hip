@@ -17,7 +17,22 @@
 // Switched off for a mesh (every S = 1) when it holds a triangle that is degenerate or not finite -- smallest altitude
 // 2 area / longest edge below RTS_HZ_DEGEN E: the f64 triangle test's own error is no longer small against tmin / 2 there --
 // or when its share of the work, primitives x blocks of the scene, exceeds RTS_HZ_WORK_CAP.
+//
+// BY AZIMUTH SECTOR.  A wing rises over a fuselage triangle's plane in one direction only, so each side carries FOUR values S_k, one per quadrant of the in-plane azimuth
+// in T's own frame u = e0 / |e0|, w = n x u (n = e1 x e0, the record's normal): sector k = (a . u < 0 ? 1 : 0) | (a . w < 0 ? 2 : 0).  The contract, per sector, is the old one:
+//     S_k >= h(x) / |x - q|   for every such x and q whenever the azimuth of (x - q), projected into T's plane, lies in quadrant k WIDENED by eps_az = RTS_HZ_EPS_AZ on both edges.
+// eps_az = 2^-6 rad: a placement may be off a rotation by 1e-3 (fill_target_placement), which turns the placed frame against this one by no more than that; the rule's two sign
+// tests are f64 dot products of vectors it reads from the placed record, wrong only within ~1e-15 rad of a boundary.  2^-6 is more than 15 x the sum.
+// Which sectors another primitive or block U (sphere c_U, r_U) can reach from any q within rho of T (q in the sphere c_T, r_T + rho): x - q = P + v with P = c_U - c_T and
+// |v| <= R = r_U + r_T + rho, so the in-plane coordinates of x - q lie in [P.u - R, P.u + R] x [P.w - R, P.w + R] (a box around the disc: no tighter than the contract) and
+// the in-plane length is at most |P| + R.  A direction a is inside the widened quadrant (su, sw) exactly when su a.u >= -|a| sin eps_az and sw a.w >= -|a| sin eps_az, so U is
+// attributed to every quadrant with su P.u + m >= 0 and sw P.w + m >= 0, m = R + (|P| + R) (eps_az + 1e-9) (sin x <= x; 1e-9 for the roundings of P.u, P.w) -- all four when
+// |P| <= R.  A block is skipped only when it can raise none of the eight values.
+// Storage: the eight values as BYTES, b = S rounded UP to a multiple of 1/255 (RTS_HZ_DECODE(b) >= S, checked with the decoder's own expression; 0 is exactly 0, 255 closed),
+// in the two words per primitive that held S+ and S- as floats: word = side, byte k = sector k.  The slices' results meet in an atomic maximum on a scratch array of bytes-as-words.
+#include <algorithm>
 #include <cmath>
+#include <vector>
 #include "rts_internal.h"
 #include "rts_ray_ops.h"
 
@@ -25,7 +40,7 @@
 #define RTS_HZ_WORK_CAP (1ull << 31)
 #define RTS_HZ_SLICES 8u            // the blocks are dealt to this many threads per primitive (a primitive's 1 500 block tests are one dependent chain; the scene's primitives alone do not fill the device)
 
-struct RtsHzPrim { double cx, cy, cz, r, nx, ny, nz, d; };      // bounding sphere; unit normal and plane offset (height of x = n . x - d)
+struct RtsHzPrim { double cx, cy, cz, r, nx, ny, nz, d, ux, uy, uz, wx, wy, wz; };      // bounding sphere; unit normal and plane offset (height of x = n . x - d); the in-plane frame u = e0 / |e0|, w = n x u
 struct RtsHzBlk { double cx, cy, cz, r; uint32_t tlo, thi; };  // bounding sphere of the block's primitives; the targets it holds
 
 // per position i of the order: the primitive's sphere and plane, its vertices side by side; a degenerate one raises its mesh's flag
@@ -53,6 +68,9 @@ __global__ void k_hz_prims(const uint32_t* __restrict__ order, const uint32_t* _
     q.r = sqrt(r2) * (1.0 + 1e-12);
     const double inv = good ? 1.0 / nl : 0.0;
     q.nx = nn.x * inv; q.ny = nn.y * inv; q.nz = nn.z * inv; q.d = q.nx * p[0] + q.ny * p[1] + q.nz * p[2];
+    const double iu = (good && l0 > 0.0) ? 1.0 / l0 : 0.0;      // (a mesh that is off never looks at its frames)
+    q.ux = e0.x * iu; q.uy = e0.y * iu; q.uz = e0.z * iu;
+    q.wx = q.ny * q.uz - q.nz * q.uy; q.wy = q.nz * q.ux - q.nx * q.uz; q.wz = q.nx * q.uy - q.ny * q.ux;
     hp[i] = q;
 }
 
@@ -78,27 +96,52 @@ __device__ __forceinline__ double hz_raise(double s, double hmax, double gap, do
     return s;
 }
 
+// the quadrants (bit k = sector k) that a sphere of radius R around the offset P (in-plane coordinates pu, pw; dist >= the in-plane length of P) can reach, each widened by
+// RTS_HZ_EPS_AZ (the head of this file); written so that a NaN reaches all four
+__device__ __forceinline__ uint32_t hz_reach(double pu, double pw, double dist, double R)
+{
+    const double m = R + (dist + R) * (RTS_HZ_EPS_AZ + 1e-9);
+    const bool up = !(pu + m < 0.0), un = !(m - pu < 0.0), wp = !(pw + m < 0.0), wn = !(m - pw < 0.0);
+    return (up && wp ? 1u : 0u) | (un && wp ? 2u : 0u) | (up && wn ? 4u : 0u) | (un && wn ? 8u : 0u);
+}
+
+// the byte a value s in [0, 1] is stored as: rounded UP against the decoder's own expression; 1, beyond and NaN: 255 (closed)
+__device__ __forceinline__ uint32_t hz_encode(double s)
+{
+    if (!(s < 1.0)) return 255u;
+    uint32_t b = s > 0.0 ? (uint32_t)ceil(s * 255.0) : 0u;
+    if (b > 255u) b = 255u;
+    while (b < 255u && RTS_HZ_DECODE(b) < s) b++;
+    return b;
+}
+
 // thread (i, slice): primitive T = order[i] against the blocks b = slice, slice + RTS_HZ_SLICES, ..., then every primitive of the blocks that may raise one of
-// its sides; the slices' results meet in an atomic maximum on the f32 bits (S >= 0: the bits order like the values; the array starts at zero)
+// its eight values (side x sector); the slices' results meet in an atomic maximum on the bytes, one word each (acc [n][8] by global primitive id: side * 4 + sector; starts at zero)
 __global__ void __launch_bounds__(256) k_hz_main(const uint32_t* __restrict__ order, const uint32_t* __restrict__ prim_targ, uint32_t n, uint32_t n_blocks, const RtsHorizonMesh* __restrict__ mesh,
                                                  const uint32_t* __restrict__ mesh_off, const RtsHzPrim* __restrict__ hp, const RtsHzBlk* __restrict__ hb, const double* __restrict__ pv,
-                                                 uint32_t* __restrict__ horizon)
+                                                 uint32_t* __restrict__ acc)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, slice = blockIdx.y;
     if (i >= n) return;
     const uint32_t g = order[i], t = prim_targ[g];
-    double sp = 0.0, sm = 0.0;
-    if (mesh_off[t]) { sp = 1.0; sm = 1.0; }
+    double s[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (mesh_off[t]) { for (int k = 0; k < 8; k++) s[k] = 1.0; }
     else {
         const RtsHzPrim T = hp[i];
         const double h0 = RTS_HZ_H0 * mesh[t].extent, rho = RTS_HZ_RHO * mesh[t].extent;
-        for (uint32_t b = slice; b < n_blocks && !(sp >= 1.0 && sm >= 1.0); b += RTS_HZ_SLICES) {
+        for (uint32_t b = slice; b < n_blocks; b += RTS_HZ_SLICES) {
+            bool closed = true;
+            for (int k = 0; k < 8; k++) closed = closed && s[k] >= 1.0;
+            if (closed) break;
             const RtsHzBlk B = hb[b];
             if (t < B.tlo || t > B.thi) continue;
             const double hc = T.nx * B.cx + T.ny * B.cy + T.nz * B.cz - T.d;
             const double dx = B.cx - T.cx, dy = B.cy - T.cy, dz = B.cz - T.cz;
-            const double gap = sqrt(dx * dx + dy * dy + dz * dz) - B.r - T.r - rho;
-            if (hz_raise(sp, hc + B.r, gap, h0) <= sp && hz_raise(sm, -hc + B.r, gap, h0) <= sm) continue;      // the block can raise neither side
+            const double dist = sqrt(dx * dx + dy * dy + dz * dz), gap = dist - B.r - T.r - rho;
+            const uint32_t reach = hz_reach(dx * T.ux + dy * T.uy + dz * T.uz, dx * T.wx + dy * T.wy + dz * T.wz, dist, B.r + T.r + rho);
+            bool raises = false;                                     // the block can raise none of the eight values: skipped
+            for (int k = 0; k < 4; k++) if (reach >> k & 1u) raises = raises || hz_raise(s[k], hc + B.r, gap, h0) > s[k] || hz_raise(s[4 + k], -hc + B.r, gap, h0) > s[4 + k];
+            if (!raises) continue;
             const uint32_t j0 = b * RTS_HZ_BLOCK, j1 = min(n, j0 + RTS_HZ_BLOCK);
             for (uint32_t j = j0; j < j1; j++) {
                 if (j == i || prim_targ[order[j]] != t) continue;
@@ -106,20 +149,28 @@ __global__ void __launch_bounds__(256) k_hz_main(const uint32_t* __restrict__ or
                 const double* u = pv + (size_t)j * 9;
                 const double a0 = T.nx * u[0] + T.ny * u[1] + T.nz * u[2] - T.d, a1 = T.nx * u[3] + T.ny * u[4] + T.nz * u[5] - T.d, a2 = T.nx * u[6] + T.ny * u[7] + T.nz * u[8] - T.d;
                 const double ex = U.cx - T.cx, ey = U.cy - T.cy, ez = U.cz - T.cz;
-                const double pg = sqrt(ex * ex + ey * ey + ez * ez) - U.r - T.r - rho;
-                sp = hz_raise(sp, fmax(a0, fmax(a1, a2)), pg, h0);
-                sm = hz_raise(sm, fmax(-a0, fmax(-a1, -a2)), pg, h0);
+                const double pd = sqrt(ex * ex + ey * ey + ez * ez), pg = pd - U.r - T.r - rho;
+                const uint32_t pr = hz_reach(ex * T.ux + ey * T.uy + ez * T.uz, ex * T.wx + ey * T.wy + ez * T.wz, pd, U.r + T.r + rho);
+                const double hp_ = fmax(a0, fmax(a1, a2)), hm_ = fmax(-a0, fmax(-a1, -a2));
+                for (int k = 0; k < 4; k++) if (pr >> k & 1u) { s[k] = hz_raise(s[k], hp_, pg, h0); s[4 + k] = hz_raise(s[4 + k], hm_, pg, h0); }
             }
         }
     }
-    // narrowed upwards: the f32 the leaf record carries is never below the f64 bound
-    float fp = (float)sp, fm = (float)sm;
-    if ((double)fp < sp) fp = __uint_as_float(__float_as_uint(fp) + 1u);
-    if ((double)fm < sm) fm = __uint_as_float(__float_as_uint(fm) + 1u);
-    atomicMax(&horizon[2 * (size_t)g], __float_as_uint(fminf(fp, 1.0f))); atomicMax(&horizon[2 * (size_t)g + 1], __float_as_uint(fminf(fm, 1.0f)));
+    for (int k = 0; k < 8; k++) { const uint32_t b = hz_encode(s[k]); if (b) atomicMax(&acc[8 * (size_t)g + k], b); }
 }
 
-// The scene's horizon: ns->d_horizon [n_prims][2] (S+, S-) and ns->hz[t] (extent, h0, rho of mesh t; rho = 0: the mesh is off).
+// the eight bytes of a primitive into the two words the leaf record carries: word = side, byte k = sector k
+__global__ void k_hz_pack(const uint32_t* __restrict__ acc, uint32_t n, uint32_t* __restrict__ horizon)
+{
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n) return;
+    for (int side = 0; side < 2; side++) {
+        const uint32_t* a = acc + 8 * (size_t)g + 4 * side;
+        horizon[2 * (size_t)g + side] = (a[0] & 0xffu) | (a[1] & 0xffu) << 8 | (a[2] & 0xffu) << 16 | (a[3] & 0xffu) << 24;
+    }
+}
+
+// The scene's horizon: ns->d_horizon [n_prims][2] (side +, side -: four sector bytes each) and ns->hz[t] (extent, h0, rho of mesh t; rho = 0: the mesh is off).
 // Called by rts_set_scene behind scene_finish (d_prim_order exists); the scratch arrays are freed on return.
 int rts_horizon_build(RtsContext* c, RtsScene* ns, const RtsSceneFlat& flat)
 {
@@ -135,16 +186,17 @@ int rts_horizon_build(RtsContext* c, RtsScene* ns, const RtsSceneFlat& flat)
         ns->hz[t].extent = E; ns->hz[t].h0 = RTS_HZ_H0 * E; ns->hz[t].rho = RTS_HZ_RHO * E;
         if (!(E > 0.0) || !std::isfinite(E) || (unsigned long long)ns->meshes[t].n_tris * n_blocks > RTS_HZ_WORK_CAP) off[t] = 1u;
     }
-    DevBuf<RtsHorizonMesh> d_mesh; DevBuf<uint32_t> d_off; DevBuf<RtsHzPrim> d_hp; DevBuf<RtsHzBlk> d_hb; DevBuf<double> d_pv;
-    RTS_HIP(d_mesh.reserve(n_targets)); RTS_HIP(d_off.reserve(n_targets)); RTS_HIP(d_hp.reserve(n)); RTS_HIP(d_hb.reserve(n_blocks)); RTS_HIP(d_pv.reserve((size_t)n * 9));
+    DevBuf<RtsHorizonMesh> d_mesh; DevBuf<uint32_t> d_off; DevBuf<RtsHzPrim> d_hp; DevBuf<RtsHzBlk> d_hb; DevBuf<double> d_pv; DevBuf<uint32_t> d_acc;
+    RTS_HIP(d_mesh.reserve(n_targets)); RTS_HIP(d_off.reserve(n_targets)); RTS_HIP(d_hp.reserve(n)); RTS_HIP(d_hb.reserve(n_blocks)); RTS_HIP(d_pv.reserve((size_t)n * 9)); RTS_HIP(d_acc.reserve((size_t)n * 8));
     RTS_HIP(ns->d_horizon.reserve((size_t)n * 2));
     RTS_HIP(hipStreamSynchronize(c->stream));
     RTS_HIP(hipMemcpy(d_mesh.p, ns->hz.data(), sizeof(RtsHorizonMesh) * n_targets, hipMemcpyHostToDevice));
     RTS_HIP(hipMemcpy(d_off.p, off.data(), sizeof(uint32_t) * n_targets, hipMemcpyHostToDevice));
     k_hz_prims<<<(n + 255u) / 256u, 256, 0, c->stream>>>(ns->d_prim_order.p, ns->d_tri_vidx.p, ns->d_verts_local.p, ns->d_prim_targ.p, n, d_mesh.p, d_off.p, d_hp.p, d_pv.p);
     k_hz_blocks<<<(n_blocks + 255u) / 256u, 256, 0, c->stream>>>(ns->d_prim_order.p, ns->d_prim_targ.p, n, n_blocks, d_hp.p, d_hb.p);
-    RTS_HIP(hipMemsetAsync(ns->d_horizon.p, 0, sizeof(float) * 2 * (size_t)n, c->stream));
-    k_hz_main<<<dim3((n + 255u) / 256u, RTS_HZ_SLICES), 256, 0, c->stream>>>(ns->d_prim_order.p, ns->d_prim_targ.p, n, n_blocks, d_mesh.p, d_off.p, d_hp.p, d_hb.p, d_pv.p, reinterpret_cast<uint32_t*>(ns->d_horizon.p));
+    RTS_HIP(hipMemsetAsync(d_acc.p, 0, sizeof(uint32_t) * 8 * (size_t)n, c->stream));
+    k_hz_main<<<dim3((n + 255u) / 256u, RTS_HZ_SLICES), 256, 0, c->stream>>>(ns->d_prim_order.p, ns->d_prim_targ.p, n, n_blocks, d_mesh.p, d_off.p, d_hp.p, d_hb.p, d_pv.p, d_acc.p);
+    k_hz_pack<<<(n + 255u) / 256u, 256, 0, c->stream>>>(d_acc.p, n, ns->d_horizon.p);
     RTS_HIP(hipGetLastError());
     RTS_HIP(hipMemcpyAsync(off.data(), d_off.p, sizeof(uint32_t) * n_targets, hipMemcpyDeviceToHost, c->stream));
     RTS_HIP(hipStreamSynchronize(c->stream));
@@ -152,14 +204,41 @@ int rts_horizon_build(RtsContext* c, RtsScene* ns, const RtsSceneFlat& flat)
     return RTS_OK;
 }
 
-// the scene's horizon as the leaf records carry it: out[n_prims][2] = (S+, S-) by global primitive id
+// the sector bytes of the scene's primitives, off the device: out[n_prims][2] words
+static int hz_fetch(RtsContext* c, const char* who, const void* out, uint32_t capacity_prims, std::vector<uint32_t>& w)
+{
+    if (!out) { rts_set_error("%s: null argument", who); return RTS_ERR_INVALID; }
+    const RtsScene* sc = c->scene;
+    if (capacity_prims < sc->n_prims) { rts_set_error("%s: capacity too small (%u primitives)", who, sc->n_prims); return RTS_ERR_CAPACITY; }
+    RTS_HIP(hipStreamSynchronize(c->stream));
+    w.resize(2 * (size_t)sc->n_prims);
+    if (sc->n_prims) RTS_HIP(hipMemcpy(w.data(), sc->d_horizon.p, sizeof(uint32_t) * 2 * (size_t)sc->n_prims, hipMemcpyDeviceToHost));
+    return RTS_OK;
+}
+
+// the scene's ISOTROPIC horizon: out[n_prims][2] = (S+, S-) by global primitive id, per side the largest of its four decoded sectors -- the S the rule tests first
+// (never below the decoded f64: narrowed upwards; 0 and 1 exact)
 extern "C" int rts_get_horizon(RtsHandle c, float* out, uint32_t capacity_prims)
 {
     CHECK_HANDLE(c);
-    if (!out) { rts_set_error("rts_get_horizon: null argument"); return RTS_ERR_INVALID; }
-    const RtsScene* sc = c->scene;
-    if (capacity_prims < sc->n_prims) { rts_set_error("rts_get_horizon: capacity too small (%u primitives)", sc->n_prims); return RTS_ERR_CAPACITY; }
-    RTS_HIP(hipStreamSynchronize(c->stream));
-    if (sc->n_prims) RTS_HIP(hipMemcpy(out, sc->d_horizon.p, sizeof(float) * 2 * (size_t)sc->n_prims, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> w;
+    const int rc = hz_fetch(c, "rts_get_horizon", out, capacity_prims, w); if (rc != RTS_OK) return rc;
+    for (size_t k = 0; k < w.size(); k++) {
+        const uint32_t b = std::max(std::max(w[k] & 0xffu, w[k] >> 8 & 0xffu), std::max(w[k] >> 16 & 0xffu, w[k] >> 24));
+        const double s = RTS_HZ_DECODE(b);
+        float f = b == 255u ? 1.0f : (float)s;
+        if ((double)f < s) f = std::nextafterf(f, 2.0f);
+        out[k] = f;
+    }
+    return RTS_OK;
+}
+
+// the horizon as the leaf records carry it: out[n_prims][2][4] bytes by global primitive id, side (+, -) and sector; a byte b stands for b / 255 (RTS_HZ_DECODE)
+extern "C" int rts_get_horizon_sectors(RtsHandle c, uint8_t* out, uint32_t capacity_prims)
+{
+    CHECK_HANDLE(c);
+    std::vector<uint32_t> w;
+    const int rc = hz_fetch(c, "rts_get_horizon_sectors", out, capacity_prims, w); if (rc != RTS_OK) return rc;
+    for (size_t k = 0; k < w.size(); k++) for (int j = 0; j < 4; j++) out[4 * k + j] = (uint8_t)(w[k] >> (8 * j) & 0xffu);
     return RTS_OK;
 }

@@ -48,17 +48,19 @@ struct __attribute__((aligned(16))) RtsLeafTri {
     double p0x, p0y, p0z, e0x, e0y, e0z, e1x, e1y, e1z, nx, ny, nz;
     uint32_t prim;                  // global primitive id (targets concatenated in order)
     uint32_t targ;                  // target index
-    float hz[2];                    // the primitive's horizon S+, S- (rts_horizon.hip; 1: the side is closed), copied by k_leaves from RtsScene::d_horizon
+    uint32_t hz[2];                 // the primitive's horizon, side + and side -: four sector bytes each, byte k = S_k as k / 255 rounded up (rts_horizon.hip; 255: closed), copied by k_leaves from RtsScene::d_horizon
 };
 static_assert(sizeof(RtsLeafTri) == 112, "leaf size");
 // The horizon's tolerances, relative to a mesh's extent E (the diagonal of its bounding box); the budget they belong to: DESIGN.md section 4
 #define RTS_HZ_H0 9.5367431640625e-07        // 2^-20: heights up to h0 = RTS_HZ_H0 E count as "not above the plane"
 #define RTS_HZ_RHO 0.00390625                 // 2^-8: the horizon holds for every origin within rho = RTS_HZ_RHO E of the triangle
 #define RTS_HZ_DEGEN 9.5367431640625e-07      // 2^-20: a triangle whose smallest altitude is below RTS_HZ_DEGEN E switches its mesh's horizon off
+#define RTS_HZ_EPS_AZ 0.015625                  // eps_az = 2^-6 rad: every azimuth sector's bound holds this far beyond the quadrant's two edges (rts_horizon.hip)
+#define RTS_HZ_DECODE(b) ((double)(b) * (1.0 / 255.0))      // a sector byte's value; the build rounds up against this very expression
 #define RTS_HZ_MARGIN 0.00390625f             // m_S = 2^-8: what the sine of a bounce ray's elevation must exceed S by (a placement may be off a rotation by 1e-3, rts_api.hip)
 struct RtsHorizonMesh { double extent, h0, rho; };      // per mesh; rho = 0: its horizon is off
 // the walk step decodes the record from the fetch's seven dwordx4 registers (rts_walk_step, rts_trace.hip): q0 = (p0x, p0y), q1 = (p0z, e0x),
-// q2 = (e0y, e0z), q3 = (e1x, e1y), q4 = (e1z, nx), q5 = (ny, nz), q6 = (prim, targ, S+, S-)
+// q2 = (e0y, e0z), q3 = (e1x, e1y), q4 = (e1z, nx), q5 = (ny, nz), q6 = (prim, targ, sectors of side +, of side -)
 static_assert(offsetof(RtsLeafTri, p0x) == 0 && offsetof(RtsLeafTri, p0z) == 16 && offsetof(RtsLeafTri, e0y) == 32 && offsetof(RtsLeafTri, e1x) == 48 &&
               offsetof(RtsLeafTri, e1z) == 64 && offsetof(RtsLeafTri, ny) == 80 && offsetof(RtsLeafTri, prim) == 96 && offsetof(RtsLeafTri, targ) == 100,
               "leaf record offsets of the walk step's decode");
@@ -224,7 +226,7 @@ struct RtsTraceArgs {
     uint32_t pre_filter;            // 1: primary rays go through the f32 pre-filter (needs the mask when there is geometry)
     const uint32_t* pmask;          // primary-ray mask: RTS_MASK_N^2 bits, then one word != 0 if the mask is void for this pulse (null: none)
     uint32_t stack_lds;             // LDS stack entries in use (RTS_STACK_LDS; smaller only to exercise the spill path in tests)
-    uint32_t horizon;               // 1: a bounce ray that leaves its triangle above the triangle's horizon skips the walk of the target it left (RTS_FLAG_NO_HORIZON: 0)
+    uint32_t horizon;               // 2: a bounce ray that leaves its triangle above the triangle's horizon skips the walk of the target it left; 1: by the isotropic rule only (RTS_FLAG_NO_HORIZON_SECTORS); 0: never (RTS_FLAG_NO_HORIZON)
 };
 
 // ----------------------------------------------------------------------------- host context
@@ -262,7 +264,7 @@ struct RtsScene {
     DevBuf<RtsNode4> d_nodes4; DevBuf<uint32_t> d_leaf_prim;
     DevBuf<uint32_t> d_prim_order;  // [n_prims] the primitives by first appearance in d_leaf_prim (rts_prim_order.h): thread i of k_leaves handles primitive d_prim_order[i]
     DevBuf<RtsNode4> d_nodes4v;     // [n_nodes][8] octant versions of d_nodes4 (empty: none -- RTS_NODE_VERSIONS=0, or the scene too large for them)
-    DevBuf<float> d_horizon;        // [n_prims][2] the primitives' horizon S+, S- by global primitive id (rts_horizon.hip); k_leaves copies it into the leaf records
+    DevBuf<uint32_t> d_horizon;     // [n_prims][2] the primitives' horizon, side + and side - (four sector bytes each), by global primitive id (rts_horizon.hip); k_leaves copies it into the leaf records
     std::vector<RtsHorizonMesh> hz; // per mesh: extent and the horizon's tolerances
     double build_ms = 0; uint32_t builder = 0;     // how long the hierarchy build took, and where it ran (0 host SAH, 1 device LBVH)
     size_t device_bytes() const {

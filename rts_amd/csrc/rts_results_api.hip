@@ -55,13 +55,13 @@ extern "C" int rts_get_block_timeline(RtsHandle c, double* out, uint32_t n)
 // ... and the split VERDICT r4 #3 asked for: out[0..2] as rts_get_lane_stats, out[3] segments that walked at all, out[4] lane-steps issued to
 // lanes that are in their tile's bounce round but never started a walk in it (a primary the pre-filter or every bounding sphere cleared, in a
 // tile other lanes of which walk): out[4] / out[0] is what packing live launch indices of several tiles into dense waves could recover at most;
-// (out[1] - out[2] - out[4]) / out[0] what waiting for the round's slowest WALKING lane costs.  n: capacity of out (<= 11 values are written).
+// (out[1] - out[2] - out[4]) / out[0] what waiting for the round's slowest WALKING lane costs.  n: capacity of out (<= 12 values are written).
 static int rts_walk_counters(RtsContext* c, const char* who, uint64_t* out, uint32_t n)
 {
     if (!c || !out) { rts_set_error("%s: null argument", who); return RTS_ERR_INVALID; }
     CHECK_CLOSED(c);
-    const int src[11] = {8, 9, 10, 11, 15, 16, 17, 18, 19, 20, 21};      // (out[5]: segments that skipped a target's walk above their triangle's horizon; out[6], out[7]: the waves' walk iterations in bounce rounds >= 1, such rounds without any walk; out[8]: such rounds; out[9], out[10]: the walk iterations and the rounds of round 0 -- these five by each round's first lane, the three above by lane 0 of the wave)
-    for (uint32_t k = 0; k < n && k < 11u; k++) out[k] = c->pin.p->cnt[src[k]];
+    const int src[12] = {8, 9, 10, 11, 15, 16, 17, 18, 19, 20, 21, 22};      // (out[5]: segments that skipped a target's walk above their triangle's horizon by the isotropic rule, out[11]: by an azimuth sector only; out[6], out[7]: the waves' walk iterations in bounce rounds >= 1, such rounds without any walk; out[8]: such rounds; out[9], out[10]: the walk iterations and the rounds of round 0 -- these five by each round's first lane, the three above by lane 0 of the wave)
+    for (uint32_t k = 0; k < n && k < 12u; k++) out[k] = c->pin.p->cnt[src[k]];
     return RTS_OK;
 }
 extern "C" int rts_get_lane_stats(RtsHandle c, uint64_t* out3) { return rts_walk_counters(c, "rts_get_lane_stats", out3, 3); }

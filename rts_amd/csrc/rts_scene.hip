@@ -248,7 +248,7 @@ extern "C" int rts_scene_info(RtsHandle c, RtsSceneInfo* out)
     out->n_targets = (uint32_t)sc->meshes.size(); out->n_prims = sc->n_prims; out->n_nodes = sc->n_nodes; out->n_leaves = sc->n_leaves;
     out->handles_sharing = (uint32_t)sc->refs.load(); out->builder = sc->builder; out->build_ms = sc->build_ms;
     out->shared_device_bytes = sc->device_bytes(); out->version_bytes = sc->d_nodes4v.cap * sizeof(RtsNode4);
-    out->horizon_bytes = sc->d_horizon.cap * sizeof(float);
+    out->horizon_bytes = sc->d_horizon.cap * sizeof(uint32_t);
     out->handle_device_bytes = c->d_leaves.cap * sizeof(RtsLeafTri) + c->d_verts_world.cap * 8 + c->d_normals_world.cap * 8 + c->d_params.cap;
     return RTS_OK;
 }

@@ -412,8 +412,10 @@ struct RtsUnitLds { int32_t* stack; int32_t* exch; double* first; unsigned long 
 // THE SKIP FIELD: bits 23-31 of a lane's shaded-hit counter (n[RTS_BLOCK + tid]; the count itself stays below 2^22, like the segment count) hold (target + 1) whose walk the
 // lane's NEXT segment skips -- the bounce ray left that target's triangle above the triangle's horizon (rts_shade) --, 0: none.  The decision crosses from the shading of one
 // segment to the target loop of the next without a register, and without an LDS word of its own (the block's LDS is full at four waves per SIMD).
+// Bit 22 beside it: the skip was decided by an azimuth sector only (the isotropic rule would have walked) -- read by the counting build alone.
 #define RTS_SKIP_SHIFT 23
-#define RTS_SHADED_MASK 0x007fffffu
+#define RTS_SECTOR_BIT 22
+#define RTS_SHADED_MASK 0x003fffffu
 // The payload of one ray chain between its segments (PerRayData fields that the walk does not touch but the shading does;
 // the first hit point, the path words and the counters live in LDS, RtsUnitLds).
 struct RtsRay { dvec3 dir, prev; double rayLength, power, doppler, refx, refy; uint32_t reflDepth, refrDepth; int received; bool end, chain_start; };
@@ -624,16 +626,32 @@ __device__ __forceinline__ bool rts_shade(const RtsTraceArgs& a, const RtsUnitLd
             // S >= h(x) / |x - o| (o is within rho of the triangle by (3)) >= (t |d| c - delta) / (t |d|) >= c - delta / (tmin |d|) -- against (1).  So the reference's
             // closest hit over this target is "none", which is what skipping the walk produces.  m_S covers a placement that is a rotation only to 1e-3
             // (fill_target_placement) and the rounding of c; a mesh whose horizon is off has S = 1 throughout, a mirrored placement rho = 0.  NaN anywhere: no skip.
+            // BY AZIMUTH SECTOR.  The side's word holds four bytes S_k = b_k / 255 (rounded up by the build), one per quadrant of the in-plane azimuth in the triangle's frame
+            // u = e0, w = n x e0; each bounds h(x) / |x - q| over the x whose direction from q, projected into the plane, lies in its quadrant widened by eps_az = 2^-6 rad.  First
+            // the isotropic test, S = the largest of the four.  Where (2) and (3) hold and (1) fails on it: k = the signs of d . e0 and d . (n x e0) of the PLACED record, and (1)
+            // again with S_k.  The sector step of the proof: a point x = o + t d has exactly d's in-plane azimuth as seen from o; o is within rho of the triangle by (3), so it is
+            // one of the q the bound is built for; eps_az covers the placed frame's error against the build's (a rotation to 1e-3) and a sign test that rounds the other way (the
+            // neighbouring quadrant's S_k holds 2^-6 rad beyond the edge).  So S_k bounds h(x) / |x - o| for every x the segment can meet, and the argument above goes through.
             uint32_t skip = 0u;
             if (a.horizon) {
                 const double dn = dir.x*L.nx + dir.y*L.ny + dir.z*L.nz, dl = sqrt(dir.x*dir.x + dir.y*dir.y + dir.z*dir.z), nl = sqrt(L.nx*L.nx + L.ny*L.ny + L.nz*L.nz);
-                const double c = fabs(dn) / (dl * nl), S = (double)(dn > 0.0 ? L.hz[0] : L.hz[1]);
+                const uint32_t hw = dn > 0.0 ? L.hz[0] : L.hz[1];
+                const double c = fabs(dn) / (dl * nl), S = RTS_HZ_DECODE(max(max(hw & 0xffu, (hw >> 8) & 0xffu), max((hw >> 16) & 0xffu, hw >> 24)));
                 const double ht = fabs((double)hit_t);
                 const double delta = ht * 0x1p-22 + (fmax(fmax(fabs(prev.x), fabs(prev.y)), fabs(prev.z)) + ht) * 0x1p-45;
                 const double reach = dl * (double)SCENE_EPS_R;
-                if ((c - delta / reach > S + (double)RTS_HZ_MARGIN) && (c * reach >= 2.0 * ((double)T.hz_h0 + delta)) && (4.0 * delta <= (double)T.hz_rho)) skip = L.targ + 1u;
+                const double lhs = c - delta / reach;
+                if ((c * reach >= 2.0 * ((double)T.hz_h0 + delta)) && (4.0 * delta <= (double)T.hz_rho)) {
+                    if (lhs > S + (double)RTS_HZ_MARGIN) skip = (L.targ + 1u) << 1;
+                    else if (a.horizon > 1u) {
+                        const double du = dir.x*L.e0x + dir.y*L.e0y + dir.z*L.e0z;
+                        const double dw = dir.x*(L.ny*L.e0z - L.nz*L.e0y) + dir.y*(L.nz*L.e0x - L.nx*L.e0z) + dir.z*(L.nx*L.e0y - L.ny*L.e0x);
+                        const uint32_t k = (du < 0.0 ? 1u : 0u) | (dw < 0.0 ? 2u : 0u);
+                        if (du == du && dw == dw && lhs > RTS_HZ_DECODE((hw >> (8u * k)) & 0xffu) + (double)RTS_HZ_MARGIN) skip = ((L.targ + 1u) << 1) | 1u;      // (bit 0: by a sector only -- the counting build tells the two rules apart)
+                    }
+                }
             }
-            atomicAnd(&s_n[RTS_BLOCK + tid], RTS_SHADED_MASK); if (skip) atomicOr(&s_n[RTS_BLOCK + tid], skip << RTS_SKIP_SHIFT);      // (ds_and_b32 / ds_or_b32, no return)
+            atomicAnd(&s_n[RTS_BLOCK + tid], RTS_SHADED_MASK); if (skip) atomicOr(&s_n[RTS_BLOCK + tid], skip << RTS_SECTOR_BIT);      // (ds_and_b32 / ds_or_b32, no return)
         }
         {   // direction history: the RCS angles of received rays are rebuilt from it (:320-326)
             const size_t plane = REFR ? (size_t)chain * (a.max_refl + 1) + reflDepth : (size_t)(reflDepth - 1);
@@ -853,7 +871,7 @@ __device__ __forceinline__ void rts_primary_setup(const RtsTraceArgs& a, const R
 template <bool COUNT, bool KEEP_ALL, bool REFR, bool COOP, bool VERS = false>
 __device__ __forceinline__ void rts_trace_unit(const RtsTraceArgs& a, const RtsLaunchConsts& lc, const RtsUnitLds& L_, const uint32_t tid, const uint32_t gtid, const uint32_t lane,
                                                const uint32_t slot, const bool pre_on, const bool mask_on, const uint32_t D, const uint32_t max_refr, const dvec3& origin,
-                                               uint32_t& n_nodes, uint32_t& n_tris, bool& hard_overflow, unsigned long long (&lane_stats)[11],
+                                               uint32_t& n_nodes, uint32_t& n_tris, bool& hard_overflow, unsigned long long (&lane_stats)[12],
                                                const uint32_t pre = 0u)      // pre: bit 0 = k_trace ran the pre-filter already, bits 1 / 2 = its may_target / may_rx
 {
       int32_t* const s_stack = L_.stack; int32_t* const s_exch = L_.exch; double* const s_first = L_.first; unsigned long long* const s_path = L_.path; uint32_t* const s_n = L_.n;
@@ -898,13 +916,13 @@ __device__ __forceinline__ void rts_trace_unit(const RtsTraceArgs& a, const RtsL
             const bool primary = chain == 0 && chain_start;
             const bool may_hit = primary ? may_target : a.n_prims > 0;
             uint32_t steps = 0;                                                // walk steps of this lane in this segment (all targets)
-            bool escaped = false;                                              // (counting build) the segment skipped a target's walk above its triangle's horizon
+            uint32_t escaped = 0u;                                             // (counting build) the segment skipped a target's walk above its triangle's horizon: 1 by the isotropic rule, 2 by a sector only
             if (may_hit) {
                 float t_prune = RTS_DEFAULT_TMAX;
                 for (uint32_t targ = 0; targ < a.n_targets; targ++) {
                     const RtsTargetDev& TG = a.targets[targ];                            // uniform index: scalar loads
                     if (TG.root < 0) continue;
-                    if (!REFR && (s_n[RTS_BLOCK + tid] >> RTS_SKIP_SHIFT) == targ + 1u) { if (COUNT) escaped = true; continue; }      // the ray left this target above its triangle's horizon: it cannot meet it again (rts_shade)
+                    if (!REFR && (s_n[RTS_BLOCK + tid] >> RTS_SKIP_SHIFT) == targ + 1u) { if (COUNT) escaped = 1u + ((s_n[RTS_BLOCK + tid] >> RTS_SECTOR_BIT) & 1u); continue; }      // the ray left this target above its triangle's horizon: it cannot meet it again (rts_shade)
                     {   // bounding sphere of the placed target (f64 on the live payload: no registers survive into the walk
                         // below, an f32 box test here cost a wave of occupancy); radius is padded on the host
                         const dvec3 q = mk3(TG.cx - prev.x, TG.cy - prev.y, TG.cz - prev.z);
@@ -966,7 +984,7 @@ __device__ __forceinline__ void rts_trace_unit(const RtsTraceArgs& a, const RtsL
                 lane_stats[3] += (unsigned long long)__popcll(__ballot(steps > 0u));      // segments that walked at all (the others: cleared by the pre-filter or by every target's bounding sphere)
                 lane_stats[4] += (unsigned long long)__popcll(__ballot(steps == 0u)) * smax;      // lane-steps issued to lanes that are in the round but NEVER STARTED a walk in it -- what packing the live launch indices of several tiles into dense waves could recover
             }
-            if (COUNT && escaped && (!COOP || (lane & (CG - 1u)) == 0u)) lane_stats[5] += 1ull;      // segments that skipped a target's walk (the horizon); per lane: every lane brings its own sum home
+            if (COUNT && escaped && (!COOP || (lane & (CG - 1u)) == 0u)) lane_stats[escaped == 1u ? 5 : 11] += 1ull;      // segments that skipped a target's walk (the horizon); per lane: every lane brings its own sum home
             if (COUNT && !COOP) {
                 // the split by bounce round, by the first lane that is in the round at all (lane 0 may have left its chain): the wave's walk iterations and
                 // rounds, round 0 apart from rounds >= 1, and the rounds >= 1 in which the wave ran no walk at all
@@ -1105,7 +1123,7 @@ __global__ void __launch_bounds__(RTS_BLOCK, (REFR && COOP) ? 2 : ((REFR || COOP
     __shared__ uint32_t s_lane_scratch[COUNT ? 2 * (RTS_BLOCK / 64) : 1];      // (counting build: per-wave max / sum of a round's walk steps)
     __shared__ uint32_t s_walk[2 * (RTS_BLOCK / 64)];           // per wave: walk iterations of the current tile (each walk's slowest lane), walks
     const RtsUnitLds ul = {s_stack, s_exch, s_first, s_path, s_n, s_rx, s_rxp, s_lane_scratch, s_walk};
-    unsigned long long lane_stats[11] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
+    unsigned long long lane_stats[12] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
     // (LDS addresses formed from the scalar wave number AT EACH USE: hoisted out of the tile loop as vector registers they were
     // parked in scratch and reloaded eight times per draw)
 #define RTS_OPAQUE_S(x) ({ uint32_t o_ = (x); asm volatile("" : "+s"(o_)); o_; })
@@ -1312,6 +1330,7 @@ __global__ void __launch_bounds__(RTS_BLOCK, (REFR && COOP) ? 2 : ((REFR || COOP
     if (COUNT && !COOP && lane == 0 && lane_stats[0]) { atomicAdd(&a.counters[8], lane_stats[0]); atomicAdd(&a.counters[9], lane_stats[1]); atomicAdd(&a.counters[10], lane_stats[2]); }
     if (COUNT && (lane & (CG - 1u)) == 0u && lane_stats[3]) atomicAdd(&a.counters[11], lane_stats[3]);
     if (COUNT && !COOP && lane == 0 && lane_stats[4]) atomicAdd(&a.counters[15], lane_stats[4]);
+    if (COUNT && lane_stats[11]) atomicAdd(&a.counters[22], lane_stats[11]);      // (... by an azimuth sector only)
     if (COUNT && lane_stats[5]) atomicAdd(&a.counters[16], lane_stats[5]);      // (every lane its own: the skipped walks, and below what it saw as its rounds' first lane)
     if (COUNT && !COOP && lane_stats[8]) { atomicAdd(&a.counters[17], lane_stats[6]); atomicAdd(&a.counters[18], lane_stats[7]); atomicAdd(&a.counters[19], lane_stats[8]); }
     if (COUNT && !COOP && lane_stats[10]) { atomicAdd(&a.counters[20], lane_stats[9]); atomicAdd(&a.counters[21], lane_stats[10]); }
@@ -1353,7 +1372,7 @@ __global__ void k_sum_counters(const unsigned long long* __restrict__ block_coun
 #define RTS_LD64(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
     if (t == 7) { const unsigned long long h = head_count ? (unsigned long long)__hip_atomic_load(head_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ULL; counters[7] = h; host_cnt[7] = h; }     // the order's head count travels home with the counters (sizes the next cooperative grid)
     if (t == 0) host_cnt[0] = RTS_LD64(&counters[0]);                          // received rays (appended by the trace kernels)
-    if ((t >= 8 && t <= 12) || (t >= 14 && t <= 21)) host_cnt[t] = RTS_LD64(&counters[t]);      // lane statistics and walked segments of the counting build; [12] cost records dropped, [14] tiles (| XCC mask << 56) on which the shader clock ran backwards, [15] never-started lane-steps, [16] segments that skipped a target's walk (the horizon), [17] walk iterations of the waves in bounce rounds >= 1, [18] such rounds without any walk, [19] such rounds, [20] [21] walk iterations and rounds of round 0
+    if ((t >= 8 && t <= 12) || (t >= 14 && t <= 22)) host_cnt[t] = RTS_LD64(&counters[t]);      // lane statistics and walked segments of the counting build; [12] cost records dropped, [14] tiles (| XCC mask << 56) on which the shader clock ran backwards, [15] never-started lane-steps, [16] segments that skipped a target's walk (the horizon), [17] walk iterations of the waves in bounce rounds >= 1, [18] such rounds without any walk, [19] such rounds, [20] [21] walk iterations and rounds of round 0, [22] segments that skipped by an azimuth sector only
     const unsigned int k = t & 7u, lane = t >> 3;                              // 32 partial sums per counter
     unsigned long long v = 0;
     // (counting builds poison the rows before the launch -- rts_trace_launch -- : a row no block wrote is COUNTED, counters[13], instead

@@ -155,7 +155,9 @@ def run(spec, **kw):
     tr = H.gpu_tracer(api, spec, keep_all=True, **kw)
     _, st = H.gpu_trace(api, spec, tr=tr)
     if kw.get("count_traversal"):
-        st["skipped_walks"] = tr.walk_stats()[5]                     # bounce segments that skipped a target's walk above their triangle's horizon
+        ws = tr.walk_stats()
+        st["skipped_walks"] = ws[5] + ws[11]                         # bounce segments that skipped a target's walk above their triangle's horizon ...
+        st["skipped_by_sector"] = ws[11]                             # ... of them by an azimuth sector only (the isotropic rule would have walked)
     out = (tr.all_rays(spec["W"] ** 3), tr.received(), st, tr.scene_info())
     tr.close()
     return out
@@ -298,6 +300,11 @@ def main():
             same(a, hz, "seed %d: horizon on / off" % seed); same(a, hzc, "seed %d: horizon on / off (counting build)" % seed)
             assert hzc[2]["skipped_walks"] == 0 and e[2]["tri_tests"] <= hzc[2]["tri_tests"] and e[2]["node_visits"] <= hzc[2]["node_visits"], (seed, e[2], hzc[2])
             tot["horizon_engaged"] = tot.get("horizon_engaged", 0) + (1 if e[2]["skipped_walks"] else 0); tot["skipped_walks"] = tot.get("skipped_walks", 0) + e[2]["skipped_walks"]
+            hs = run(spec, horizon_sectors=False); hsc = run(spec, horizon_sectors=False, count_traversal=True)      # the sectors: here the isotropic rule alone decides
+            same(a, hs, "seed %d: horizon sectors on / off" % seed); same(a, hsc, "seed %d: horizon sectors on / off (counting build)" % seed)
+            assert hsc[2]["skipped_by_sector"] == 0 and hsc[2]["skipped_walks"] == e[2]["skipped_walks"] - e[2]["skipped_by_sector"], (seed, e[2], hsc[2])
+            assert e[2]["tri_tests"] <= hsc[2]["tri_tests"] <= hzc[2]["tri_tests"] and e[2]["node_visits"] <= hsc[2]["node_visits"] <= hzc[2]["node_visits"], (seed, e[2], hsc[2], hzc[2])
+            tot["skipped_by_sector"] = tot.get("skipped_by_sector", 0) + e[2]["skipped_by_sector"]
             same(a, c, "seed %d: host / device tree" % seed)
             same(a, d, "seed %d: host / device tree without references" % seed)
             if with_oracle:
