@@ -1564,7 +1564,7 @@ class Tracer:
 
     def bvh(self):
         """static target-space hierarchy: (nodes [n][32] float32 view of the 128-byte records, leaf_prim, roots)"""
-        s = self.stats()
+        s = self.scene_info()                                                         # (the scene's records: stats() holds those of the last finished launch's scene)
         nl = C.c_uint32(0)
         check(L.lib().rts_get_bvh(self.h, None, None, None, 0, 0, C.byref(nl)))        # leaf slots (>= primitives: split references)
         nodes = np.zeros((max(s["n_nodes"], 1), 32), np.float32); leaf = np.zeros(max(nl.value, 1), np.uint32)

@@ -392,7 +392,7 @@ inline unsigned blocks_for(size_t n, unsigned bs) { return (unsigned)((n + bs - 
 //   k_sah_bins   : the 3 x 16 bins of every open node                          per position; a block whose positions all belong to
 //                                                                              one node bins into LDS and flushes once
 //   k_sah_split  : best split, child boxes, child links, the next level's open nodes       per open node
-//   k_sah_scatter: partition of the node's positions (children are contiguous ranges)       per position
+//   k_sah_side, a scan, k_sah_scatter: the STABLE partition of the node's positions (children are contiguous ranges)       per position
 // A node's references occupy a contiguous range of the position array; a leaf is ~position, so the final position order IS
 // the leaf order.  Output: the Node2 array the collapse to 4-wide records reads (root = node 0), child boxes exact (unions
 // of bins hold every reference box).  A node whose references all have the same centroid is cut in the middle and both
@@ -533,44 +533,45 @@ __global__ void k_sah_split(const SahWork* __restrict__ work, uint32_t n_work, c
     nodes[wk.node] = nd;
 }
 
-__global__ void __launch_bounds__(256) k_sah_scatter(const float* __restrict__ ref_box, const uint32_t* __restrict__ idx, const int32_t* __restrict__ work_of, const SahWork* __restrict__ work,
-                              const SahSplit* __restrict__ split, uint32_t* __restrict__ fill /* [n_work][2] */, uint32_t* __restrict__ idx_out, int32_t* __restrict__ work_out, uint32_t n)
+// The partition of every open node's positions, in two kernels around one scan.  It is STABLE -- a node's references keep their
+// order on either side -- so the position order, and with it the leaf order, is a function of the input alone: a node whose
+// centroids all coincide is cut by POSITION, and destinations drawn from atomic counters would leave which of its references go
+// left to the order in which the waves of the level above happened to arrive -- the same scene built twice, two leaf orders, and
+// two trees where the coincident references' boxes differ (tests/test_gpu_builders.py builds every scene twice).
+//   k_sah_side    : 1 where the reference at a position goes to its node's left child       per position
+//   (exclusive scan of the sides over all positions: lefts in front of a position)
+//   k_sah_scatter : left: begin + lefts before it in its node; right: begin + n_left + rights before it in its node
+__global__ void __launch_bounds__(256) k_sah_side(const float* __restrict__ ref_box, const uint32_t* __restrict__ idx, const int32_t* __restrict__ work_of, const SahWork* __restrict__ work,
+                                                  const SahSplit* __restrict__ split, uint32_t* __restrict__ side, uint32_t n)
 {
-    // Destinations are handed out by two counters per node (left, right).  At the top levels a node owns whole blocks of
-    // positions: such a block counts its lefts and rights in LDS and draws ONE range per side (per position the 3 x 10^5
-    // references of a C3 mesh queued behind two addresses: 0.64 ms per level, 37 ms of a 52 ms build).
-    __shared__ uint32_t s_cnt[2], s_base[2];
-    __shared__ int s_first, s_last;
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    const int w = p < n ? work_of[p] : -1;
-    if (threadIdx.x == 0) { s_first = work_of[blockIdx.x * blockDim.x]; const uint32_t lastp = min((blockIdx.x + 1) * blockDim.x, n) - 1; s_last = work_of[lastp]; s_cnt[0] = 0; s_cnt[1] = 0; }
-    __syncthreads();
-    const bool one_node = s_first >= 0 && s_first == s_last;
-    uint32_t r = 0; bool left = false, sorted = false; uint32_t local = 0;
-    SahWork wk; SahSplit sp;
+    if (p >= n) return;
+    const int w = work_of[p];
+    uint32_t left = 0u;
     if (w >= 0) {
-        wk = work[w]; sp = split[w]; r = idx[p];
+        const SahSplit sp = split[w];
         if (sp.axis >= 0) {
-            const float* b = ref_box + 6 * (size_t)r;
+            const float* b = ref_box + 6 * (size_t)idx[p];
             const float c = (b[sp.axis] + b[3 + sp.axis]) * 0.5f;
             int bi = (int)((c - sp.lo) * sp.scale); bi = bi < 0 ? 0 : (bi >= SAH_BINS ? SAH_BINS - 1 : bi);
-            left = bi <= sp.bin; sorted = true;
-            if (one_node) local = atomicAdd(&s_cnt[left ? 0 : 1], 1u);
-        } else left = (int)p < wk.begin + sp.n_left;
+            left = bi <= sp.bin ? 1u : 0u;
+        } else left = (int)p < work[w].begin + sp.n_left ? 1u : 0u;              // cut in the middle
     }
-    if (one_node) {
-        __syncthreads();
-        if (threadIdx.x < 2 && s_cnt[threadIdx.x]) s_base[threadIdx.x] = atomicAdd(&fill[2 * (size_t)s_first + threadIdx.x], s_cnt[threadIdx.x]);
-        __syncthreads();
-    }
+    side[p] = left;
+}
+
+__global__ void __launch_bounds__(256) k_sah_scatter(const uint32_t* __restrict__ idx, const int32_t* __restrict__ work_of, const SahWork* __restrict__ work, const SahSplit* __restrict__ split,
+                                                     const uint32_t* __restrict__ side, const uint32_t* __restrict__ lefts_before, uint32_t* __restrict__ idx_out, int32_t* __restrict__ work_out, uint32_t n)
+{
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
+    const int w = work_of[p];
     if (w < 0) { idx_out[p] = idx[p]; work_out[p] = -1; return; }                 // already a leaf: stays where it is
-    uint32_t dest = p;
-    if (sorted) {
-        const uint32_t off = one_node ? s_base[left ? 0 : 1] + local : atomicAdd(&fill[2 * (size_t)w + (left ? 0 : 1)], 1u);
-        dest = left ? (uint32_t)wk.begin + off : (uint32_t)(wk.begin + sp.n_left) + off;
-    }
-    idx_out[dest] = r; work_out[dest] = left ? sp.wl : sp.wr;
+    const SahWork wk = work[w]; const SahSplit sp = split[w];
+    const uint32_t rank_l = lefts_before[p] - lefts_before[wk.begin];             // lefts of this node in front of p (k_sah_split's count of the bins and this sum of the sides agree: same expression per reference)
+    const bool left = side[p] != 0u;
+    const uint32_t dest = left ? (uint32_t)wk.begin + rank_l : (uint32_t)(wk.begin + sp.n_left) + ((p - (uint32_t)wk.begin) - rank_l);
+    idx_out[dest] = idx[p]; work_out[dest] = left ? sp.wl : sp.wr;
 }
 
 // Crowded spots of a provisional tree (the second and third rounds of the host builder's reference splitting, rts_sah.cpp):
@@ -679,7 +680,7 @@ int rts_lbvh_build_device(RtsContext* c, RtsScene* ns, const RtsSceneFlat& flat,
     // (crowding rounds -- a provisional tree, twice the slabs for triangles in crowded spots, the host builder's second stage: built,
     // measured on C3 at 0 / 1 / 2 rounds: 0.812 / 0.810 / 0.830 ms, and they double the build time: off unless RTS_CROWD_ROUNDS asks)
     const int crowd_rounds = tune.crowd_rounds;
-    DevBuf<uint32_t> d_sah_bins, d_sah_cb, d_sah_fill, d_boost; DevBuf<SahSplit> d_sah_split; DevBuf<SahWork> d_sah_work_a, d_sah_work_b;
+    DevBuf<uint32_t> d_sah_bins, d_sah_cb, d_sah_cnt, d_sah_lefts, d_boost; DevBuf<char> d_sah_scan_tmp; DevBuf<SahSplit> d_sah_split; DevBuf<SahWork> d_sah_work_a, d_sah_work_b;
     DevBuf<RtsNode4> d_nodes4_tmp; DevBuf<uint32_t> d_reach, d_newid, d_rflag;
     RTS_HIP(d_boost.reserve((size_t)ns->n_prims + 2)); RTS_HIP(hipMemsetAsync(d_boost.p, 0, sizeof(uint32_t) * ((size_t)ns->n_prims + 2), st));       // per triangle: 1 = twice the slabs (k_crowd); last word: a counter
 
@@ -692,12 +693,16 @@ int rts_lbvh_build_device(RtsContext* c, RtsScene* ns, const RtsSceneFlat& flat,
         uint32_t* idx_a = d_vals_sorted.p; uint32_t* idx_b = d_vals.p;
         int32_t* wo_a = d_parent.p; int32_t* wo_b = d_leaf_parent.p;                     // work-node index per position (the LBVH's link arrays are free in this mode)
         const uint32_t max_work = nv / 2 + 2;
-        RTS_HIP(d_sah_bins.reserve((size_t)max_work * SAH_BIN_WORDS)); RTS_HIP(d_sah_cb.reserve((size_t)max_work * 12)); RTS_HIP(d_sah_fill.reserve((size_t)max_work * 2 + 2));
+        RTS_HIP(d_sah_bins.reserve((size_t)max_work * SAH_BIN_WORDS)); RTS_HIP(d_sah_cb.reserve((size_t)max_work * 12)); RTS_HIP(d_sah_cnt.reserve(2)); RTS_HIP(d_sah_lefts.reserve(nv));
         RTS_HIP(d_sah_split.reserve(max_work)); RTS_HIP(d_sah_work_a.reserve(max_work)); RTS_HIP(d_sah_work_b.reserve(max_work));
         k_iota<<<blocks_for(nv, 256), 256, 0, st>>>(d_flags.p, wo_a, nv);            // (d_flags only as a dummy target for the iota; work_of := 0)
         SahWork w0; w0.begin = 0; w0.end = (int32_t)nv; w0.node = 0; w0.pad = 0;
         RTS_HIP(hipMemcpyAsync(d_sah_work_a.p, &w0, sizeof(w0), hipMemcpyHostToDevice, st));
-        uint32_t* cnt = d_sah_fill.p + (size_t)max_work * 2;                           // [0] next node id, [1] open nodes of the next level
+        uint32_t* cnt = d_sah_cnt.p;                                                   // [0] next node id, [1] open nodes of the next level
+        uint32_t* side = d_flags.p;                                                    // (free in this mode, like the link arrays: the refit's counters)
+        size_t scan_need = 0;
+        RTS_HIP(rocprim::exclusive_scan(nullptr, scan_need, side, d_sah_lefts.p, 0u, nv, rocprim::plus<uint32_t>(), st));
+        RTS_HIP(d_sah_scan_tmp.reserve(scan_need + 16));
         uint32_t h_cnt[2] = {1u, 0u};
         RTS_HIP(hipMemcpyAsync(cnt, h_cnt, sizeof(h_cnt), hipMemcpyHostToDevice, st));
         SahWork* wk_a = d_sah_work_a.p; SahWork* wk_b = d_sah_work_b.p;
@@ -705,12 +710,13 @@ int rts_lbvh_build_device(RtsContext* c, RtsScene* ns, const RtsSceneFlat& flat,
         for (int level = 0; n_work > 0 && level < 256; level++) {
             const size_t init_n = std::max((size_t)n_work * SAH_BIN_WORDS, (size_t)n_work * 12);
             k_sah_init_bins<<<blocks_for(init_n, 256), 256, 0, st>>>(d_sah_bins.p, d_sah_cb.p, n_work);
-            RTS_HIP(hipMemsetAsync(d_sah_fill.p, 0, sizeof(uint32_t) * 2 * (size_t)n_work, st));
             RTS_HIP(hipMemsetAsync(cnt + 1, 0, sizeof(uint32_t), st));
             k_sah_bounds<<<blocks_for(nv, 256), 256, 0, st>>>(d_prim_box.p, idx_a, wo_a, d_sah_cb.p, nv);
             k_sah_bins<<<blocks_for(nv, 256), 256, 0, st>>>(d_prim_box.p, idx_a, wo_a, d_sah_cb.p, d_sah_bins.p, nv);
             k_sah_split<<<blocks_for(n_work, 64), 64, 0, st>>>(wk_a, n_work, d_sah_cb.p, d_sah_bins.p, d_sah_split.p, d_nodes2.p, wk_b, cnt);
-            k_sah_scatter<<<blocks_for(nv, 256), 256, 0, st>>>(d_prim_box.p, idx_a, wo_a, wk_a, d_sah_split.p, d_sah_fill.p, idx_b, wo_b, nv);
+            k_sah_side<<<blocks_for(nv, 256), 256, 0, st>>>(d_prim_box.p, idx_a, wo_a, wk_a, d_sah_split.p, side, nv);
+            { size_t need = scan_need; RTS_HIP(rocprim::exclusive_scan(d_sah_scan_tmp.p, need, side, d_sah_lefts.p, 0u, nv, rocprim::plus<uint32_t>(), st)); }
+            k_sah_scatter<<<blocks_for(nv, 256), 256, 0, st>>>(idx_a, wo_a, wk_a, d_sah_split.p, side, d_sah_lefts.p, idx_b, wo_b, nv);
             RTS_HIP(hipMemcpyAsync(h_cnt, cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st)); RTS_HIP(hipStreamSynchronize(st));
             n_work = h_cnt[1];
             if (n_work > max_work) { rts_set_error("rts_set_scene: device SAH builder: %u open nodes at level %d exceed the bound %u", n_work, level, max_work); return RTS_ERR_HIP; }

@@ -10,7 +10,8 @@
 //
 // Boxes are f32, rounded outward and padded by 2^-22 of their largest coordinate magnitude, so that the f32 slab test
 // stays conservative with respect to the f64 triangle test (same budget as the reference's `bound` program plus pad,
-// triangle_mesh.cu:204-233).  Triangles with a non-finite vertex get no leaf: they can never be hit.
+// triangle_mesh.cu:204-233).  Triangles with a coordinate that is not finite, or too large for a finite padded f32 box
+// (rts_coord_valid), get no leaf: they can never be hit.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -162,7 +163,7 @@ int rts_sah_build(const double* verts, const uint32_t* tris, uint32_t n_tris, do
         Ref r; r.poly.n = 3; r.prim = i; bool finite = true;
         for (int k = 0; k < 3; k++) {
             const double* p = verts + 3*(size_t)tris[3*(size_t)i + k];
-            finite = finite && std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]);
+            finite = finite && rts_coord_valid(p[0]) && rts_coord_valid(p[1]) && rts_coord_valid(p[2]);      // (3.5e38 is finite in f64, not in a padded f32 box)
             r.poly.v[k][0] = p[0]; r.poly.v[k][1] = p[1]; r.poly.v[k][2] = p[2];
         }
         if (!finite) continue;

@@ -99,7 +99,12 @@ static inline void rts_scene_append_tree(const std::vector<RtsNode4>& mesh_nodes
     if (blas->root >= 0) blas->root += node_base;
 }
 
-// The f64 bounds of mesh t over its finite triangles (for the per-pulse placement constants): lo / hi, zeros when it has none,
+// A coordinate a hierarchy can hold: finite AND far enough inside the f32 range for its padded, outward-rounded box to stay finite
+// (load_tri of rts_lbvh.hip applies the same bound).  A triangle with any other coordinate gets no leaf from either builder: kept, the
+// f32 boxes of its leaf and of every ancestor up to the root overflow to the "unused" sentinel and hide the valid triangles beside it.
+static inline bool rts_coord_valid(double x) { return std::fabs(x) < 3.0e38; }
+
+// The f64 bounds of mesh t over its valid triangles (for the per-pulse placement constants): lo / hi, zeros when it has none,
 // and the largest magnitude among them.
 static inline void rts_mesh_bounds(const RtsSceneFlat& f, uint32_t t, RtsBlasInfo* b)
 {
@@ -108,7 +113,7 @@ static inline void rts_mesh_bounds(const RtsSceneFlat& f, uint32_t t, RtsBlasInf
     uint32_t nv = 0;
     for (uint32_t i = 0; i < m.n_tris; i++) {
         bool finite = true;
-        for (int k = 0; k < 3; k++) { const double* p = &f.verts[3 * (size_t)f.vidx[3 * ((size_t)m.tri_base + i) + k]]; finite = finite && std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]); }
+        for (int k = 0; k < 3; k++) { const double* p = &f.verts[3 * (size_t)f.vidx[3 * ((size_t)m.tri_base + i) + k]]; finite = finite && rts_coord_valid(p[0]) && rts_coord_valid(p[1]) && rts_coord_valid(p[2]); }
         if (!finite) continue;
         nv++;
         for (int k = 0; k < 3; k++) { const double* p = &f.verts[3 * (size_t)f.vidx[3 * ((size_t)m.tri_base + i) + k]]; for (int a = 0; a < 3; a++) { lo[a] = std::min(lo[a], p[a]); hi[a] = std::max(hi[a], p[a]); } }

@@ -274,6 +274,9 @@ def test_bvh_invariants(rts, scenes):
             assert used >= 1
     assert seen_leaves.all() and covered.all()
     assert seen_nodes.all() or not host_sah
+    # ... and the vectorised checker of tests/bvh_check.py on the same arrays (15 lattice points per primitive, closed inequalities)
+    import bvh_check
+    bvh_check.check_hierarchy(nodes, leaf_prim, roots, spec["meshes"], max_refs=None if host_sah else 8, all_reachable=bool(seen_nodes.all()))
     tr.close()
 
 

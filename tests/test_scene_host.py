@@ -188,7 +188,8 @@ def test_concatenation(driver, k):
 
 def restated_bounds(m):
     tv = m["v"][m["t"]] if len(m["t"]) else np.zeros((0, 3, 3))
-    tv = tv[np.isfinite(tv).all(axis=(1, 2))]
+    with np.errstate(invalid="ignore"):
+        tv = tv[(np.abs(tv) < 3.0e38).all(axis=(1, 2))]                            # finite, and inside the range of a padded f32 box (rts_coord_valid)
     if len(tv) == 0:
         return [0.0] * 7
     lo = tv.min(axis=(0, 1)); hi = tv.max(axis=(0, 1))
@@ -201,8 +202,9 @@ def test_bounds(driver):
     one_bad = v.copy(); one_bad[4, 1] = math.nan                               # the last triangle is left out, and with it vertex 4's 100 / 300
     all_bad = v.copy(); all_bad[2, 0] = math.inf                               # vertex 2 is in every triangle
     neg = -np.abs(RNG.normal(size=(6, 3))) - 1.0
+    too_big = v.copy(); too_big[4, 2] = -3.5e38                                # finite in f64, beyond a padded f32 box: left out like the NaN
     meshes = [mesh(quad, one_bad, []), mesh(quad, all_bad, []), mesh([], [], []), mesh(RNG.integers(0, 6, size=(8, 3)), neg, []),
-              mesh(quad, v, [])]
+              mesh(quad, v, []), mesh(quad, too_big, [])]
     a = driver([case("bounds", meshes)])[0]
     check_flat(a, meshes)
     got = [floats(a, "bounds", i) for i in range(len(meshes))]
@@ -211,4 +213,4 @@ def test_bounds(driver):
     assert got[0] == [-4.0, -8.0, -10.0, 7.0, 5.0, 9.0, 10.0]
     assert got[1] == [0.0] * 7 and got[2] == [0.0] * 7
     assert got[3][6] == -min(got[3][:3]) and max(got[3][3:6]) < 0                 # negative-only coordinates: max_abs comes from lo
-    assert got[4] == [-4.0, -8.0, -10.0, 100.0, 200.0, 300.0, 300.0]
+    assert got[4] == [-4.0, -8.0, -10.0, 100.0, 200.0, 300.0, 300.0] and got[5] == got[0]
