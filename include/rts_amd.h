@@ -1514,6 +1514,118 @@ int rts_cube_backproject(RtsHandle h, const RtsImageParams* p, void* device_out)
 int rts_cube_image_get(RtsHandle h, double* host_out, uint64_t capacity_doubles);
 int rts_backproject_eval(const RtsCubeParams* q, const double* cube, const RtsImageParams* p, double* out);  /* pure host, no device */
 
+/* ---------------------------------------------------------------- autofocus: range alignment, phase-gradient autofocus, correction
+ * Motion compensation of a target whose motion is NOT known (rts_cube_doppler needs a scatterer that stays in its bin with a pure
+ * tone for a phase history, rts_cube_backproject needs every pulse's positions): first the rows' range walk is estimated from their
+ * envelopes and taken out, then the pulse-to-pulse phase error is estimated from the data and taken out.  Three operations, all
+ * ordered on the handle's stream, none waits on the host.  "Rows" are cube rows first_pulse + j, j in [0, P), P = n_pulses; every
+ * receiver is treated on its own.  The arithmetic is rts_amd/csrc/rts_focus.h, shared by the kernels and the host evaluators (the
+ * library builds with -ffp-contract=off: the trees below are the contract).
+ *
+ * rts_cube_align: range shifts S, f64 [n_rx][P], in bins, against a GLOBAL reference (adjacent-pulse lags accumulate their errors
+ *   into a drift; these do not).  The lag is absolute: max_lag L must cover the whole walk.
+ *   Envelope e[j][n] = sqrt(re*re + im*im) over the whole row; a read outside [0, n_bins) gives 0.  The gate is bins first_bin ..
+ *   first_bin + n_gate - 1 (n_gate 0: to the row's last bin).  S = 0, then n_iters times:
+ *     R_j    = (int64) floor(S_j + 0.5)
+ *     ref[n] = sum_j e[j][n + R_j] for every gate bin n: ascending j from 0 inside chunks of RTS_ALIGN_PULSE_CHUNK pulses, the chunk
+ *              sums added in ascending order, the first chunk's sum the start value (the image's rule)
+ *     C_j(l) = sum_{n in gate} ref[n] * e[j][n + l], l in [-L, L]: each product rounded before it is added; ascending n from 0.0
+ *              inside blocks of RTS_ALIGN_BIN_BLOCK consecutive gate bins counted from the gate's first bin, the block sums added
+ *              left to right from 0.0 (the plots' rule)
+ *     l*     : scan l = 0, -1, +1, -2, +2, ..., -L, +L and replace only on a strict >: a NaN never wins, an all-zero row gives 0,
+ *              ties go to the smaller |l| and then to the negative lag
+ *     delta  : 0 with RTS_ALIGN_INTEGER or |l*| == L; else den = C(l*-1) - 2 C(l*) + C(l*+1) and, when den < 0,
+ *              delta = 0.5 * (C(l*-1) - C(l*+1)) / den clamped to [-0.5, 0.5] (0 when den >= 0 or not a number)
+ *     S_j    = (double)l* + delta
+ *   IEEE basic operations in a fixed order: the device and rts_align_eval agree BIT FOR BIT.
+ *   device_out: caller-owned device memory of n_rx P doubles (8-byte aligned), or NULL: library-owned, recorded as the handle's
+ *   shift table (rts_cube_align_get synchronises and copies it; RTS_CORRECT_USE_ALIGN takes it on the device), alive until the next
+ *   alignment of another size, rts_cube_attach or rts_destroy.  A caller-owned output is not recorded.
+ *   Memory: the envelopes of the rows, 8 n_rx P n_bins bytes of handle-owned scratch.
+ *   Regime: point-like scatterers well above the noise in the gate.  On an ungated row at 0 dB per-sample SNR the reference is
+ *   mostly noise and the estimate is lost; gate the target.
+ *
+ * rts_cube_pga: the phase error phi, f64 [n_rx][P] in cycles, by phase-gradient autofocus; it does not change the cube.  N = P must be
+ *   a power of two in [4, RTS_PGA_MAX_PULSES] (the transform is rts_stft.h's radix-2 tree; zero padding would put a step into the
+ *   phase history).  phi = 0, W = window0 (0: N / 2); per iteration and gate column n:
+ *     x[p] = y[p][n] * exp(-j 2 pi phi[p]): f = phi - floor(phi), (sn, cs) = sincospi(2 f) (the image's rotation), re = vr cs + vi sn,
+ *            im = vi cs - vr sn -- always from the UNCHANGED cube: nothing accumulates in the data
+ *     X    = the forward transform of rts_stft.h (bit-reversed load, rts_stft_pair / rts_stft_butterfly, the twiddle table)
+ *     k*   = the first maximum of re*re + im*im in ascending k
+ *     Y[k] = X[(k + k*) mod N] where min(k, N - k) <= W / 2 (integer division), else 0
+ *     g    = conj(T(conj(Y))), T the same tree; no 1 / N
+ *     a[p] = g[p] conj(g[p-1]), re = gr hr + gi hi, im = gi hr - gr hi, p >= 1; a[0] = 0
+ *   A[p] = sum_n a_n[p]: ascending gate bins from 0.0 inside tiles of RTS_PGA_BIN_TILE consecutive gate bins, the tile sums added in
+ *   ascending tile order, the first tile's sum the start value (RTS_STFT_SUM_BINS' scheme; no atomics).  Then per receiver:
+ *     D[0] = 0, D[p] = atan2(Im A[p], Re A[p]) / (2 pi) (0 when both are 0);  psi = the running sum of D, left to right
+ *     x_p = (double)p - (N - 1) / 2.0;  mean = sum psi / N;  slope = sum x_p psi_p / sum x_p x_p (sums left to right from 0.0)
+ *     psi'_p = psi_p - mean - slope * x_p  -- the image neither rotates nor shifts in Doppler
+ *     phi += psi';  rms[i] = sqrt(sum psi'^2 / N) in cycles;  W = max(window_min, W / 2)   (window_min 0: 8)
+ *   Output: phi f64 [n_rx][P], then the convergence record rms f64 [n_rx][n_iters], n_rx (P + n_iters) doubles in all.  device_out:
+ *   caller-owned (8-byte aligned), or NULL: library-owned, recorded as the handle's phase table (rts_cube_pga_get copies whichever of
+ *   phase_out and rms_out is not NULL; RTS_CORRECT_USE_PGA takes it on the device).
+ *   The twiddles, sincospi and atan2 are the device library's on the device and libm's on the host: the device and rts_pga_eval
+ *   agree to a tolerance (tests/test_gpu_focus.py), not to the bit; a column whose two largest |X[k]|^2 tie may pick another k*.
+ *   Run it on an ALIGNED cube, on a gate that holds the target: it needs a dominant scatterer per column that stays in its bin.
+ *
+ * rts_cube_correct: shifts and / or phases applied to the cube IN PLACE.  For each row and bin n:
+ *     d = (double)n + S;  v = the old row interpolated at d (RtsImageParams above: taps, the same interpolator; S == 0 gives the row
+ *     bit for bit);  then the rotation of rts_cube_pga's load by phi.
+ *   Without shifts nothing is resampled (no copy is made: a thread reads only the element it writes), without phases nothing is
+ *   rotated; with shifts the rows are copied to a handle-owned scratch first and the kernel reads the copy.  Rows outside the range
+ *   are not touched.  shifts, phase: host arrays [n_rx][P] or NULL; they go through a staged upload and are free on return.
+ *   RTS_CORRECT_USE_ALIGN / RTS_CORRECT_USE_PGA take the handle's library-owned tables on the device instead, without a host wait;
+ *   the table must have been made for the same first_pulse and n_pulses.
+ *   The Doppler map, the image and the other recorded products of the cube are NOT invalidated (nor are they by rts_cube_compress or
+ *   rts_cube_add_sources): a product made before the correction is a product of the cube as it was.
+ *
+ * RTS_ERR_INVALID, the message naming the field, outputs untouched: no cube attached; NULL p; nonzero reserved fields; unknown flags;
+ * n_pulses 0 or rows beyond the cube; a gate beyond the row; max_lag above RTS_ALIGN_MAX_LAG; n_iters outside [1, RTS_ALIGN_MAX_ITERS] /
+ * [1, RTS_PGA_MAX_ITERS]; n_pulses of rts_cube_pga not a power of two in [4, RTS_PGA_MAX_PULSES]; taps not 1 and not even in [2,
+ * RTS_WAVEFORM_MAX_TAPS]; a host shift or phase that is not finite; a flag together with the matching host pointer; neither shifts nor
+ * phases; a flag without a valid table of the same rows; a device_out that is not 8-byte aligned; more than 65 535 receivers, or
+ * rows x ceil(n_bins / 256) above 2^31 - 1 (the launch grids).  A cube that is not finite gives unspecified values, but nothing is
+ * read or written outside the cube and the outputs.
+ * rts_align_eval, rts_pga_eval, rts_correct_eval: pure host, no device; the same validation (q in place of the attached cube; the
+ * USE flags are refused) and the same rts_focus.h functions on a host cube [n_rx][q->n_pulses][n_bins] (interleaved re / im), which
+ * rts_correct_eval changes in place. */
+#define RTS_ALIGN_INTEGER 1u             /* no sub-bin refinement */
+#define RTS_ALIGN_MAX_LAG 64u
+#define RTS_ALIGN_MAX_ITERS 8u
+#define RTS_ALIGN_PULSE_CHUNK 64u        /* the summation order of ref, see above */
+#define RTS_ALIGN_BIN_BLOCK 64u          /* the summation order of C, see above   */
+typedef struct RtsAlignParams {
+    uint32_t first_pulse, n_pulses;      /* cube rows first_pulse .. first_pulse + n_pulses - 1 */
+    uint32_t first_bin, n_gate;          /* the gate; n_gate 0: to the row's last bin           */
+    uint32_t max_lag, n_iters, flags, reserved0;
+    uint64_t reserved[2];                /* 0 */
+} RtsAlignParams;
+#define RTS_PGA_MAX_PULSES 4096u
+#define RTS_PGA_MAX_ITERS 16u
+#define RTS_PGA_BIN_TILE 8u              /* the summation order of A, see above */
+typedef struct RtsPgaParams {
+    uint32_t first_pulse, n_pulses;      /* n_pulses: a power of two in [4, RTS_PGA_MAX_PULSES] */
+    uint32_t first_bin, n_gate;          /* the gate; n_gate 0: to the row's last bin           */
+    uint32_t n_iters, window0, window_min, reserved0;      /* window0 0: n_pulses / 2; window_min 0: 8 */
+    uint64_t reserved[2];                /* 0 */
+} RtsPgaParams;
+#define RTS_CORRECT_USE_ALIGN 1u         /* shifts: the handle's library-owned table of rts_cube_align */
+#define RTS_CORRECT_USE_PGA 2u           /* phases: the handle's library-owned table of rts_cube_pga   */
+typedef struct RtsCorrectParams {
+    uint32_t first_pulse, n_pulses, taps, flags;
+    const double* shifts;                /* [n_rx][n_pulses] bins, or NULL    host */
+    const double* phase;                 /* [n_rx][n_pulses] cycles, or NULL  host */
+    uint64_t reserved[2];                /* 0 */
+} RtsCorrectParams;
+int rts_cube_align(RtsHandle h, const RtsAlignParams* p, void* device_out);          /* f64 [n_rx][n_pulses]; NULL: library-owned */
+int rts_cube_align_get(RtsHandle h, double* host_out, uint64_t capacity_doubles);
+int rts_cube_pga(RtsHandle h, const RtsPgaParams* p, void* device_out);              /* f64 [n_rx][n_pulses] phase, then [n_rx][n_iters] rms */
+int rts_cube_pga_get(RtsHandle h, double* phase_out, double* rms_out, uint64_t capacity_phase, uint64_t capacity_rms);
+int rts_cube_correct(RtsHandle h, const RtsCorrectParams* p);
+int rts_align_eval(const RtsCubeParams* q, const double* cube, const RtsAlignParams* p, double* out);                          /* pure host */
+int rts_pga_eval(const RtsCubeParams* q, const double* cube, const RtsPgaParams* p, double* phase_out, double* rms_out);      /* pure host */
+int rts_correct_eval(const RtsCubeParams* q, double* cube, const RtsCorrectParams* p);                                        /* pure host */
+
 /* ---------------------------------------------------------------- several GPUs (not in the reference: it is single-GPU)
  * Rays are independent (each launch index writes only its own rows, ray_tracer.cu:227-253) and so are pulses
  * (ray_tracer.cpp:843).  rts_plan_cpi deals the n_pulses x total_rays (pulse, launch index) pairs of one coherent

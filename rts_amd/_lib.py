@@ -211,6 +211,31 @@ class RtsStftParams(C.Structure):
 assert C.sizeof(RtsStftParams) == 56
 
 
+RTS_ALIGN_INTEGER, RTS_ALIGN_MAX_LAG, RTS_ALIGN_MAX_ITERS, RTS_ALIGN_PULSE_CHUNK, RTS_ALIGN_BIN_BLOCK = 1, 64, 8, 64, 64
+RTS_PGA_MAX_PULSES, RTS_PGA_MAX_ITERS, RTS_PGA_BIN_TILE = 4096, 16, 8
+RTS_CORRECT_USE_ALIGN, RTS_CORRECT_USE_PGA = 1, 2
+
+
+class RtsAlignParams(C.Structure):
+    _fields_ = [("first_pulse", C.c_uint32), ("n_pulses", C.c_uint32), ("first_bin", C.c_uint32), ("n_gate", C.c_uint32),
+                ("max_lag", C.c_uint32), ("n_iters", C.c_uint32), ("flags", C.c_uint32), ("reserved0", C.c_uint32),
+                ("reserved", C.c_uint64 * 2)]
+
+
+class RtsPgaParams(C.Structure):
+    _fields_ = [("first_pulse", C.c_uint32), ("n_pulses", C.c_uint32), ("first_bin", C.c_uint32), ("n_gate", C.c_uint32),
+                ("n_iters", C.c_uint32), ("window0", C.c_uint32), ("window_min", C.c_uint32), ("reserved0", C.c_uint32),
+                ("reserved", C.c_uint64 * 2)]
+
+
+class RtsCorrectParams(C.Structure):
+    _fields_ = [("first_pulse", C.c_uint32), ("n_pulses", C.c_uint32), ("taps", C.c_uint32), ("flags", C.c_uint32),
+                ("shifts", C.c_void_p), ("phase", C.c_void_p), ("reserved", C.c_uint64 * 2)]
+
+
+assert C.sizeof(RtsAlignParams) == 48 and C.sizeof(RtsPgaParams) == 48 and C.sizeof(RtsCorrectParams) == 48
+
+
 RTS_BEAT_STRIP, RTS_BEAT_MAX_PARTS = 16, 64
 RTS_RANGE_REVERSE, RTS_RANGE_MAX_FFT = 1, 4096
 
@@ -404,6 +429,7 @@ EXPORTS = ["rts_create", "rts_destroy", "rts_last_error", "rts_device_count", "r
            "rts_cube_tbd_info", "rts_cube_tbd_reset", "rts_tbd_step_eval", "rts_tbd_extract_eval",
            "rts_cube_backproject", "rts_cube_image_get", "rts_backproject_eval",
            "rts_cube_spectrogram", "rts_cube_spectrogram_get", "rts_stft_eval", "rts_window_make",
+           "rts_cube_align", "rts_cube_align_get", "rts_cube_pga", "rts_cube_pga_get", "rts_cube_correct", "rts_align_eval", "rts_pga_eval", "rts_correct_eval",
            "rts_cube_render_beat", "rts_beat_eval", "rts_cube_range_transform", "rts_cube_range_get", "rts_range_eval",
            "rts_cube_beamform", "rts_cube_beam_get", "rts_beamform_eval", "rts_steering_make",
            "rts_cube_covariance", "rts_cube_covariance_get", "rts_covariance_eval", "rts_cube_mvdr", "rts_cube_mvdr_get", "rts_mvdr_eval",
@@ -512,6 +538,14 @@ def lib():
         "rts_cube_spectrogram_get": [vp, vp, u64],
         "rts_stft_eval": [C.POINTER(RtsCubeParams), vp, C.POINTER(RtsStftParams), vp, C.POINTER(u32)],
         "rts_window_make": [u32, u32, vp],
+        "rts_cube_align": [vp, C.POINTER(RtsAlignParams), vp],
+        "rts_cube_align_get": [vp, vp, u64],
+        "rts_cube_pga": [vp, C.POINTER(RtsPgaParams), vp],
+        "rts_cube_pga_get": [vp, vp, vp, u64, u64],
+        "rts_cube_correct": [vp, C.POINTER(RtsCorrectParams)],
+        "rts_align_eval": [C.POINTER(RtsCubeParams), vp, C.POINTER(RtsAlignParams), vp],
+        "rts_pga_eval": [C.POINTER(RtsCubeParams), vp, C.POINTER(RtsPgaParams), vp, vp],
+        "rts_correct_eval": [C.POINTER(RtsCubeParams), vp, C.POINTER(RtsCorrectParams)],
         "rts_cube_render_beat": [vp, u32, C.POINTER(RtsBeatParams), C.c_double, C.c_double],
         "rts_beat_eval": [C.POINTER(RtsCubeParams), C.POINTER(RtsBeatParams), vp, u32, u32, vp],
         "rts_cube_range_transform": [vp, C.POINTER(RtsRangeParams), vp],

@@ -520,6 +520,77 @@ def spectrogram_axes(window_len, hop, n_fft, n_pulses, pri, first=0):
     return centres, k / (n_fft * float(pri))
 
 
+# ------------------------------------------------------------------------------- autofocus: alignment, PGA, correction (rts_focus.h)
+def _gate(gate):
+    """(first_bin, n_gate) of a gate given as None (the whole row) or (first_bin, n_gate); n_gate 0: to the row's last bin"""
+    return (0, 0) if gate is None else (int(gate[0]), int(gate[1]))
+
+
+def _align_params(first, count, gate, max_lag, n_iters, integer, n_pulses_cube):
+    p = L.RtsAlignParams()
+    p.first_pulse, p.n_pulses = int(first), int(n_pulses_cube - first if count is None else count)
+    p.first_bin, p.n_gate = _gate(gate)
+    p.max_lag, p.n_iters, p.flags = int(max_lag), int(n_iters), L.RTS_ALIGN_INTEGER if integer else 0
+    return p
+
+
+def _pga_params(first, count, gate, n_iters, window0, window_min, n_pulses_cube):
+    p = L.RtsPgaParams()
+    p.first_pulse, p.n_pulses = int(first), int(n_pulses_cube - first if count is None else count)
+    p.first_bin, p.n_gate = _gate(gate)
+    p.n_iters, p.window0, p.window_min = int(n_iters), int(window0), int(window_min)
+    return p
+
+
+def _correct_params(first, count, taps, shifts, phase, use_align, use_pga, n_rx, n_pulses_cube):
+    """RtsCorrectParams and the arrays it points to (keep them alive for the call)"""
+    p = L.RtsCorrectParams()
+    p.first_pulse, p.n_pulses, p.taps = int(first), int(n_pulses_cube - first if count is None else count), int(taps)
+    p.flags = (L.RTS_CORRECT_USE_ALIGN if use_align else 0) | (L.RTS_CORRECT_USE_PGA if use_pga else 0)
+    keep = []
+    for name, a in (("shifts", shifts), ("phase", phase)):
+        if a is None:
+            continue
+        a = np.ascontiguousarray(np.asarray(a, np.float64))
+        if a.size != n_rx * p.n_pulses:
+            raise ValueError("correct: %s of %d values for %d receivers x %d rows" % (name, a.size, n_rx, p.n_pulses))
+        setattr(p, name, ptr(a)); keep.append(a)
+    return p, keep
+
+
+def align_eval(cube, first=0, count=None, gate=None, max_lag=8, n_iters=4, integer=False):
+    """rts_align_eval (pure host): the range shifts, float64 [n_rx][count] in bins, of a host cube [n_rx][n_pulses][n_bins] (complex)"""
+    cube = np.ascontiguousarray(np.asarray(cube, np.complex128))
+    n_rx, n_p, nb = cube.shape
+    q = L.RtsCubeParams(n_rx, n_p, nb, 0, 0.0, 1.0)
+    p = _align_params(first, count, gate, max_lag, n_iters, integer, n_p)
+    out = np.zeros((n_rx, max(min(p.n_pulses, n_p), 1)))
+    check(L.lib().rts_align_eval(C.byref(q), ptr(cube.view(np.float64)), C.byref(p), ptr(out)))
+    return out
+
+
+def pga_eval(cube, first=0, count=None, gate=None, n_iters=6, window0=0, window_min=0):
+    """rts_pga_eval (pure host): (the phase error float64 [n_rx][count] in cycles, the iterations' rms float64 [n_rx][n_iters])"""
+    cube = np.ascontiguousarray(np.asarray(cube, np.complex128))
+    n_rx, n_p, nb = cube.shape
+    q = L.RtsCubeParams(n_rx, n_p, nb, 0, 0.0, 1.0)
+    p = _pga_params(first, count, gate, n_iters, window0, window_min, n_p)
+    phase = np.zeros((n_rx, max(min(p.n_pulses, n_p), 1))); rms = np.zeros((n_rx, max(min(p.n_iters, L.RTS_PGA_MAX_ITERS), 1)))
+    check(L.lib().rts_pga_eval(C.byref(q), ptr(cube.view(np.float64)), C.byref(p), ptr(phase), ptr(rms)))
+    return phase, rms
+
+
+def correct_eval(cube, shifts=None, phase=None, first=0, count=None, taps=8):
+    """rts_correct_eval (pure host): a copy of the host cube with rows first .. first + count - 1 resampled at n + shifts (bins) and
+    rotated by -phase (cycles); shifts, phase: [n_rx][count] or None"""
+    out = np.array(cube, np.complex128, order="C", copy=True)
+    n_rx, n_p, nb = out.shape
+    q = L.RtsCubeParams(n_rx, n_p, nb, 0, 0.0, 1.0)
+    p, keep = _correct_params(first, count, taps, shifts, phase, False, False, n_rx, n_p)
+    check(L.lib().rts_correct_eval(C.byref(q), ptr(out.view(np.float64)), C.byref(p)))
+    return out
+
+
 # ------------------------------------------------------------------------------- FMCW: beat render, range transform (rts_beat.h)
 _RENDER_SOURCES = {"rays": L.RTS_RENDER_RAYS, "paths": L.RTS_RENDER_PATHS}
 
@@ -1556,6 +1627,62 @@ class Tracer:
         out = np.zeros(shape, dtype)
         check(L.lib().rts_cube_spectrogram_get(self.h, ptr(out), out.size * (2 if dtype is np.complex128 else 1)))
         return out
+
+    def cube_align(self, first=0, count=None, gate=None, max_lag=8, n_iters=4, integer=False, device_ptr=None, fetch=True):
+        """rts_cube_align: the range shifts of the attached cube's rows first .. first + count - 1 (default: to the last) against their
+        global reference, over the gate (None: the whole row, or (first_bin, n_gate)), lags up to max_lag (it must cover the whole
+        walk).  Into a caller float64 device tensor [n_rx][count] (device_ptr; nothing is fetched) or the handle's shift table,
+        returned float64 [n_rx][count] when fetch"""
+        n_rx, n_p, nb = self._cube_shape
+        p = _align_params(first, count, gate, max_lag, n_iters, integer, n_p)
+        check(L.lib().rts_cube_align(self.h, C.byref(p), C.c_void_p(device_ptr) if device_ptr else None))
+        if device_ptr:
+            return None
+        self._align_shape = (n_rx, p.n_pulses)
+        return self.align_shifts() if fetch else None
+
+    def align_shifts(self):
+        """rts_cube_align_get: the handle's shift table"""
+        out = np.zeros(getattr(self, "_align_shape", None) or (1, 1))
+        check(L.lib().rts_cube_align_get(self.h, ptr(out), out.size))
+        return out
+
+    def cube_pga(self, first=0, count=None, gate=None, n_iters=6, window0=0, window_min=0, device_ptr=None, fetch=True):
+        """rts_cube_pga: the phase error of rows first .. first + count - 1 (count a power of two in [4, 4096]) by phase-gradient
+        autofocus over the gate; the cube is not changed.  Into a caller float64 device tensor of n_rx (count + n_iters) values
+        (device_ptr: the phase [n_rx][count], then the rms [n_rx][n_iters]; nothing is fetched) or the handle's phase table, returned
+        (phase in cycles [n_rx][count], rms [n_rx][n_iters]) when fetch"""
+        n_rx, n_p, nb = self._cube_shape
+        p = _pga_params(first, count, gate, n_iters, window0, window_min, n_p)
+        check(L.lib().rts_cube_pga(self.h, C.byref(p), C.c_void_p(device_ptr) if device_ptr else None))
+        if device_ptr:
+            return None
+        self._pga_shape = (n_rx, p.n_pulses, p.n_iters)
+        return self.pga_phase() if fetch else None
+
+    def pga_phase(self):
+        """rts_cube_pga_get: (the handle's phase table, its convergence record)"""
+        n_rx, n, it = getattr(self, "_pga_shape", None) or (1, 1, 1)
+        phase = np.zeros((n_rx, n)); rms = np.zeros((n_rx, it))
+        check(L.lib().rts_cube_pga_get(self.h, ptr(phase), ptr(rms), phase.size, rms.size))
+        return phase, rms
+
+    def cube_correct(self, shifts=None, phase=None, first=0, count=None, taps=8, use_align=False, use_pga=False):
+        """rts_cube_correct: rows first .. first + count - 1 of the attached cube resampled at n + shifts (bins) and rotated by -phase
+        (cycles), in place; shifts, phase: host arrays [n_rx][count], or use_align / use_pga: the handle's tables, on the device"""
+        n_rx, n_p, nb = self._cube_shape
+        p, keep = _correct_params(first, count, taps, shifts, phase, use_align, use_pga, n_rx, n_p)
+        check(L.lib().rts_cube_correct(self.h, C.byref(p)))
+
+    def cube_autofocus(self, first=0, count=None, gate=None, max_lag=8, taps=8, align_iters=4, **pga_kwargs):
+        """align -> correct(shifts) -> pga -> correct(phase) on the attached cube, nothing fetched in between; pga_kwargs: n_iters,
+        window0, window_min.  Returns (shifts [n_rx][count], phase [n_rx][count], rms [n_rx][n_iters])"""
+        self.cube_align(first, count, gate, max_lag, align_iters, fetch=False)
+        self.cube_correct(first=first, count=count, taps=taps, use_align=True)
+        self.cube_pga(first, count, gate, fetch=False, **pga_kwargs)
+        self.cube_correct(first=first, count=count, taps=taps, use_pga=True)
+        phase, rms = self.pga_phase()
+        return self.align_shifts(), phase, rms
 
     def cube(self):
         out = np.zeros(self._cube_shape + (2,), np.float64)

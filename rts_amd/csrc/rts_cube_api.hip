@@ -933,6 +933,195 @@ extern "C" int rts_cube_spectrogram_get(RtsHandle c, double* host_out, uint64_t 
     return rts_cube_copy_out(c, "rts_cube_spectrogram_get", "no library-owned spectrogram (rts_cube_spectrogram with device_out NULL; a spectrogram ends at rts_cube_attach) / null output", c->cube.stft.valid, c->cube.stft.p, c->cube.stft.doubles, host_out, capacity_doubles);
 }
 
+// ------------------------------------------------------------------------------------- autofocus: range alignment, phase-gradient autofocus, correction
+// (rts_amd.h: RtsAlignParams, RtsPgaParams, RtsCorrectParams; the arithmetic and the launch plans are rts_focus.h, shared by the host exports and the kernels, rts_focus.hip)
+static int rts_focus_gate_check(const char* who, uint32_t first_bin, uint32_t n_gate, uint32_t n_bins, uint32_t* gate)
+{
+    if (first_bin >= n_bins || n_gate > n_bins - first_bin) { rts_set_error("%s: first_bin = %u, n_gate = %u: inside the cube's %u bins", who, first_bin, n_gate, n_bins); return RTS_ERR_INVALID; }
+    *gate = n_gate ? n_gate : n_bins - first_bin;
+    return RTS_OK;
+}
+static int rts_focus_rx_check(const char* who, uint32_t n_rx)
+{
+    if (n_rx > RTS_FOCUS_MAX_RX) { rts_set_error("%s: n_rx = %u receivers: more than %u (the launch grid)", who, n_rx, RTS_FOCUS_MAX_RX); return RTS_ERR_INVALID; }
+    return RTS_OK;
+}
+
+static int rts_align_check(const RtsAlignParams* p, const RtsCubeParams& q, const char* who, RtsAlignPlan* plan)
+{
+    if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
+    if (p->reserved0 || p->reserved[0] || p->reserved[1]) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
+    if (p->flags & ~RTS_ALIGN_INTEGER) { rts_set_error("%s: unknown flags 0x%x", who, p->flags); return RTS_ERR_INVALID; }
+    { int rc = rts_pulses_check(who, p->first_pulse, p->n_pulses, q.n_pulses, true); if (rc != RTS_OK) return rc; }
+    uint32_t gate = 0;
+    { int rc = rts_focus_gate_check(who, p->first_bin, p->n_gate, q.n_bins, &gate); if (rc != RTS_OK) return rc; }
+    if (p->max_lag > RTS_ALIGN_MAX_LAG) { rts_set_error("%s: max_lag = %u (0 .. %u)", who, p->max_lag, RTS_ALIGN_MAX_LAG); return RTS_ERR_INVALID; }
+    if (p->n_iters == 0 || p->n_iters > RTS_ALIGN_MAX_ITERS) { rts_set_error("%s: n_iters = %u (1 .. %u)", who, p->n_iters, RTS_ALIGN_MAX_ITERS); return RTS_ERR_INVALID; }
+    { int rc = rts_focus_rx_check(who, q.n_rx); if (rc != RTS_OK) return rc; }
+    *plan = rts_align_plan(q.n_rx, p->n_pulses, q.n_bins, gate, p->max_lag);
+    if (!plan->supported) { rts_set_error("%s: n_pulses = %u rows: more than %u (the launch grid)", who, p->n_pulses, RTS_FOCUS_MAX_GRID_X); return RTS_ERR_INVALID; }
+    return RTS_OK;
+}
+
+static int rts_pga_check(const RtsPgaParams* p, const RtsCubeParams& q, const char* who, RtsPgaPlan* plan)
+{
+    if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
+    if (p->reserved0 || p->reserved[0] || p->reserved[1]) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
+    if (p->n_pulses < 4u || p->n_pulses > RTS_PGA_MAX_PULSES || (p->n_pulses & (p->n_pulses - 1u)) != 0u) {
+        rts_set_error("%s: n_pulses = %u must be a power of two in [4, %u] (the radix-2 transform; no zero padding of a phase history)", who, p->n_pulses, RTS_PGA_MAX_PULSES); return RTS_ERR_INVALID; }
+    { int rc = rts_pulses_check(who, p->first_pulse, p->n_pulses, q.n_pulses, true); if (rc != RTS_OK) return rc; }
+    uint32_t gate = 0;
+    { int rc = rts_focus_gate_check(who, p->first_bin, p->n_gate, q.n_bins, &gate); if (rc != RTS_OK) return rc; }
+    if (p->n_iters == 0 || p->n_iters > RTS_PGA_MAX_ITERS) { rts_set_error("%s: n_iters = %u (1 .. %u)", who, p->n_iters, RTS_PGA_MAX_ITERS); return RTS_ERR_INVALID; }
+    { int rc = rts_focus_rx_check(who, q.n_rx); if (rc != RTS_OK) return rc; }
+    *plan = rts_pga_plan(q.n_rx, p->n_pulses, gate, p->n_iters, p->window0, p->window_min);
+    if (!plan->supported) { rts_set_error("%s: n_pulses = %u: the columns do not fit the workgroup's memory", who, p->n_pulses); return RTS_ERR_INVALID; }
+    return RTS_OK;
+}
+
+// handle: the USE flags are allowed (the evaluators have no tables)
+static int rts_correct_check(const RtsCorrectParams* p, const RtsCubeParams& q, const char* who, bool handle, RtsCorrectPlan* plan)
+{
+    if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
+    if (p->reserved[0] || p->reserved[1]) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
+    if (p->flags & ~(RTS_CORRECT_USE_ALIGN | RTS_CORRECT_USE_PGA)) { rts_set_error("%s: unknown flags 0x%x", who, p->flags); return RTS_ERR_INVALID; }
+    if (p->flags && !handle) { rts_set_error("%s: flags = 0x%x: the evaluator has no tables (pass shifts / phase)", who, p->flags); return RTS_ERR_INVALID; }
+    { int rc = rts_pulses_check(who, p->first_pulse, p->n_pulses, q.n_pulses, true); if (rc != RTS_OK) return rc; }
+    { int rc = rts_taps_check(who, p->taps); if (rc != RTS_OK) return rc; }
+    const bool use_s = (p->flags & RTS_CORRECT_USE_ALIGN) != 0, use_p = (p->flags & RTS_CORRECT_USE_PGA) != 0;
+    if (use_s && p->shifts) { rts_set_error("%s: shifts together with RTS_CORRECT_USE_ALIGN", who); return RTS_ERR_INVALID; }
+    if (use_p && p->phase) { rts_set_error("%s: phase together with RTS_CORRECT_USE_PGA", who); return RTS_ERR_INVALID; }
+    if (!use_s && !use_p && !p->shifts && !p->phase) { rts_set_error("%s: neither shifts nor phase (arrays or flags)", who); return RTS_ERR_INVALID; }
+    { int rc = rts_focus_rx_check(who, q.n_rx); if (rc != RTS_OK) return rc; }
+    const size_t n = (size_t)q.n_rx * p->n_pulses;
+    if (p->shifts) for (size_t i = 0; i < n; i++) if (!std::isfinite(p->shifts[i])) { rts_set_error("%s: shifts[%zu] is not finite", who, i); return RTS_ERR_INVALID; }
+    if (p->phase) for (size_t i = 0; i < n; i++) if (!std::isfinite(p->phase[i])) { rts_set_error("%s: phase[%zu] is not finite", who, i); return RTS_ERR_INVALID; }
+    *plan = rts_correct_plan(q.n_rx, p->n_pulses, q.n_bins, p->shifts != nullptr, p->phase != nullptr, use_s || p->shifts);
+    if (!plan->supported) { rts_set_error("%s: n_pulses = %u rows x %u workgroups per row (n_bins): more than %u (the launch grid)", who, p->n_pulses, plan->tiles, RTS_FOCUS_MAX_GRID_X); return RTS_ERR_INVALID; }
+    return RTS_OK;
+}
+
+static int rts_eval_cube_check(const char* who, const RtsCubeParams* q)
+{
+    if (!q || q->n_rx == 0 || q->n_pulses == 0 || q->n_bins == 0) { rts_set_error("%s: bad cube parameters", who); return RTS_ERR_INVALID; }
+    return RTS_OK;
+}
+
+extern "C" int rts_align_eval(const RtsCubeParams* q, const double* cube, const RtsAlignParams* p, double* out)
+{
+    { int rc = rts_eval_cube_check("rts_align_eval", q); if (rc != RTS_OK) return rc; }
+    RtsAlignPlan plan;
+    int rc = rts_align_check(p, *q, "rts_align_eval", &plan); if (rc != RTS_OK) return rc;
+    if (!cube || !out) { rts_set_error("rts_align_eval: null cube or output array"); return RTS_ERR_INVALID; }
+    std::vector<double> work((size_t)p->n_pulses * q->n_bins + plan.n_gate + plan.n_lags);
+    rts_align_eval_host(q, cube, p, plan, out, work.data());
+    return RTS_OK;
+}
+
+extern "C" int rts_pga_eval(const RtsCubeParams* q, const double* cube, const RtsPgaParams* p, double* phase_out, double* rms_out)
+{
+    { int rc = rts_eval_cube_check("rts_pga_eval", q); if (rc != RTS_OK) return rc; }
+    RtsPgaPlan plan;
+    int rc = rts_pga_check(p, *q, "rts_pga_eval", &plan); if (rc != RTS_OK) return rc;
+    if (!cube || !phase_out || !rms_out) { rts_set_error("rts_pga_eval: null cube or output array"); return RTS_ERR_INVALID; }
+    std::vector<double> work(14 * (size_t)p->n_pulses);
+    rts_pga_eval_host(q, cube, p, plan, phase_out, rms_out, work.data());
+    return RTS_OK;
+}
+
+extern "C" int rts_correct_eval(const RtsCubeParams* q, double* cube, const RtsCorrectParams* p)
+{
+    { int rc = rts_eval_cube_check("rts_correct_eval", q); if (rc != RTS_OK) return rc; }
+    RtsCorrectPlan plan;
+    int rc = rts_correct_check(p, *q, "rts_correct_eval", false, &plan); if (rc != RTS_OK) return rc;
+    if (!cube) { rts_set_error("rts_correct_eval: null cube"); return RTS_ERR_INVALID; }
+    std::vector<double> work(2 * (size_t)q->n_bins);
+    rts_correct_eval_host(q, cube, p, p->shifts, p->phase, work.data());
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_align(RtsHandle c, const RtsAlignParams* p, void* device_out)
+{
+    const char* who = "rts_cube_align";
+    CHECK_HANDLE(c);
+    NEED_CUBE(c, who, "no cube (call rts_cube_attach first)");
+    RtsAlignPlan plan;
+    int rc = rts_align_check(p, c->cube.params, who, &plan); if (rc != RTS_OK) return rc;
+    if ((uintptr_t)device_out & 7u) { rts_set_error("%s: device_out is not 8-byte aligned", who); return RTS_ERR_INVALID; }
+    CHECK_CLOSED(c);
+    double* out; RTS_HIP(c->cube.align.place(device_out, plan.out_doubles, &out));
+    if (!device_out) { c->cube.align.record(out, plan.out_doubles); c->cube.align_first = p->first_pulse; c->cube.align_P = p->n_pulses; }
+    return rts_cube_align_device(c, *p, plan, out);
+}
+
+extern "C" int rts_cube_align_get(RtsHandle c, double* host_out, uint64_t capacity_doubles)
+{
+    CHECK_HANDLE(c);
+    return rts_cube_copy_out(c, "rts_cube_align_get", "no library-owned shift table (rts_cube_align with device_out NULL; a table ends at rts_cube_attach) / null output", c->cube.align.valid, c->cube.align.p, c->cube.align.doubles, host_out, capacity_doubles);
+}
+
+extern "C" int rts_cube_pga(RtsHandle c, const RtsPgaParams* p, void* device_out)
+{
+    const char* who = "rts_cube_pga";
+    CHECK_HANDLE(c);
+    NEED_CUBE(c, who, "no cube (call rts_cube_attach first)");
+    RtsPgaPlan plan;
+    int rc = rts_pga_check(p, c->cube.params, who, &plan); if (rc != RTS_OK) return rc;
+    if ((uintptr_t)device_out & 7u) { rts_set_error("%s: device_out is not 8-byte aligned", who); return RTS_ERR_INVALID; }
+    CHECK_CLOSED(c);
+    double* out; RTS_HIP(c->cube.pga.place(device_out, plan.out_doubles, &out));
+    if (!device_out) { c->cube.pga.record(out, plan.out_doubles); c->cube.pga_first = p->first_pulse; c->cube.pga_P = p->n_pulses; c->cube.pga_iters = p->n_iters; }
+    return rts_cube_pga_device(c, *p, plan, out);
+}
+
+extern "C" int rts_cube_pga_get(RtsHandle c, double* phase_out, double* rms_out, uint64_t capacity_phase, uint64_t capacity_rms)
+{
+    const char* who = "rts_cube_pga_get";
+    CHECK_HANDLE(c);
+    const RtsCubeState& s = c->cube;
+    if (!s.set || !s.pga.valid) { rts_set_error("%s: no library-owned phase table (rts_cube_pga with device_out NULL; a table ends at rts_cube_attach)", who); return RTS_ERR_INVALID; }
+    if (!phase_out && !rms_out) { rts_set_error("%s: null outputs", who); return RTS_ERR_INVALID; }
+    const size_t n_phase = (size_t)s.params.n_rx * s.pga_P, n_rms = (size_t)s.params.n_rx * s.pga_iters;
+    if ((phase_out && capacity_phase < n_phase) || (rms_out && capacity_rms < n_rms)) { rts_set_error("%s: capacity too small", who); return RTS_ERR_CAPACITY; }
+    RTS_HIP(hipStreamSynchronize(c->stream));
+    if (phase_out) RTS_HIP(hipMemcpy(phase_out, s.pga.p, sizeof(double) * n_phase, hipMemcpyDeviceToHost));
+    if (rms_out) RTS_HIP(hipMemcpy(rms_out, s.pga.p + n_phase, sizeof(double) * n_rms, hipMemcpyDeviceToHost));
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_correct(RtsHandle c, const RtsCorrectParams* p)
+{
+    const char* who = "rts_cube_correct";
+    CHECK_HANDLE(c);
+    NEED_CUBE(c, who, "no cube (call rts_cube_attach first)");
+    RtsCubeState& s = c->cube;
+    RtsCorrectPlan plan;
+    int rc = rts_correct_check(p, s.params, who, true, &plan); if (rc != RTS_OK) return rc;
+    const double* shifts = nullptr; const double* phase = nullptr;
+    if (p->flags & RTS_CORRECT_USE_ALIGN) {
+        if (!s.align.valid || s.align_first != p->first_pulse || s.align_P != p->n_pulses) { rts_set_error("%s: RTS_CORRECT_USE_ALIGN: no library-owned shift table of rows %u .. %u + %u (rts_cube_align with device_out NULL)", who, p->first_pulse, p->first_pulse, p->n_pulses); return RTS_ERR_INVALID; }
+        shifts = s.align.p;
+    }
+    if (p->flags & RTS_CORRECT_USE_PGA) {
+        if (!s.pga.valid || s.pga_first != p->first_pulse || s.pga_P != p->n_pulses) { rts_set_error("%s: RTS_CORRECT_USE_PGA: no library-owned phase table of rows %u .. %u + %u (rts_cube_pga with device_out NULL)", who, p->first_pulse, p->first_pulse, p->n_pulses); return RTS_ERR_INVALID; }
+        phase = s.pga.p;
+    }
+    CHECK_CLOSED(c);
+    // the host tables -> pinned staging -> the device, on the stream
+    if (plan.table_doubles) {
+        double* h = nullptr;
+        RTS_HIP(s.focus_tab.begin(plan.table_doubles, plan.table_doubles, plan.table_doubles, &h));
+        const size_t n = (size_t)s.params.n_rx * p->n_pulses;
+        size_t at = 0;
+        if (p->shifts) { memcpy(h, p->shifts, sizeof(double) * n); at = n; }
+        if (p->phase) memcpy(h + at, p->phase, sizeof(double) * n);
+        RTS_HIP(s.focus_tab.send(plan.table_doubles, c->stream));
+        if (p->shifts) shifts = s.focus_tab.dev.p;
+        if (p->phase) phase = s.focus_tab.dev.p + at;
+    }
+    return rts_cube_correct_device(c, *p, plan, shifts, phase);
+}
+
 // ------------------------------------------------------------------------------------- FMCW: dechirped beat render, fast-time range transform
 // (rts_amd.h: RtsBeatParams, RtsRangeParams; the trees and the launch plans are rts_beat.h / rts_stft.h, shared by the host exports and the kernels, rts_beat.hip)
 static int rts_beat_check(const RtsBeatParams* p, const RtsCubeParams& q, uint32_t pulse_index, const char* who)

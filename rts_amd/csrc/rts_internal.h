@@ -14,6 +14,7 @@
 #include "rts_image.h"            // the arithmetic of a backprojected pixel and the host-only plan of its launch
 #include "rts_cube_source.h"      // what a received record brings to the cube: which counts, its delay, phase and amplitude, the cell and the add
 #include "rts_stft.h"             // the radix-2 tree of the slow-time and fast-time transforms and the host-only plans of the Doppler map's and the spectrogram's launches
+#include "rts_focus.h"            // autofocus: range alignment's reference, correlation and pick, the PGA's rotation, mask, products and update, the correction, their evaluators and the host-only plans of their launches
 #include "rts_beat.h"             // the tree of the dechirped beat render, the range transform's evaluator and the host-only plans of their launches
 #include "rts_beam.h"             // the beamformer's term, sum and streaming peak, its evaluator and the host-only plan of its launch
 #include "rts_adapt.h"            // adaptive beamforming: the covariance's term and partition, the weight solve, their evaluators and the host-only plans of their launches
@@ -394,10 +395,18 @@ struct RtsCubeState {
     RtsCubeProduct eig_val, eig_vec; uint32_t eig_n = 0; DevBuf<uint32_t> d_eig_status;
     RtsCubeProduct doa;
     StagedUpload<double> doa_g;
+    // autofocus (rts_cube_align, rts_cube_pga, rts_cube_correct, rts_focus.hip): the shift table and the phase table (phase, then the
+    // iterations' rms) with the row ranges they were made for, for their getters and RTS_CORRECT_USE_ALIGN / RTS_CORRECT_USE_PGA; the
+    // rows' envelopes and the reference; the PGA's tile sums, their sums and the rotations; the correction's copy of the rows; a
+    // correction's host tables [shifts | phase] go through a staged upload
+    RtsCubeProduct align; uint32_t align_first = 0, align_P = 0;
+    RtsCubeProduct pga; uint32_t pga_first = 0, pga_P = 0, pga_iters = 0;
+    DevBuf<double> d_focus_env, d_focus_ref, d_pga_part, d_pga_sum, d_pga_rot, d_focus_rows;
+    StagedUpload<double> focus_tab;
     // every product belongs to the cube it was made from: the Doppler map (which rts_cube_detect may take), the detection list, the image
     // the spectrogram, the range transform, the beams, the covariance, the adaptive weights, the space-time filter's output, the eigenpairs and the angular spectrum end when another cube is attached
     void end_products() { doppler.valid = false; det_valid = false; plot_valid = false; image.valid = false; stft.valid = false; range.valid = false; beam.valid = false; cov.valid = false; mvdr.valid = false; st.valid = false;
-                          eig_val.valid = false; eig_vec.valid = false; doa.valid = false; }
+                          eig_val.valid = false; eig_vec.valid = false; doa.valid = false; align.valid = false; pga.valid = false; }
 };
 
 // What a pulse leaves for its accessors (rts_results_api.hip; the finalisers, the aggregation and the end-of-pulse chains of rts_api.hip; the
@@ -542,6 +551,9 @@ int rts_cube_tbd_step_device(RtsContext* c, const RtsTbdParams& p, const double*
 int rts_cube_tbd_extract_device(RtsContext* c, const RtsTbdExtractParams& e, uint32_t max_tracks);
 int rts_cube_doppler_device(RtsContext* c, uint32_t n_fft, double* out);      // rts_stft.hip: the slow-time transforms
 int rts_cube_stft_device(RtsContext* c, const RtsStftParams& p, const RtsStftPlan& plan, const double* window, double* out);
+int rts_cube_align_device(RtsContext* c, const RtsAlignParams& p, const RtsAlignPlan& plan, double* out);      // rts_focus.hip: autofocus
+int rts_cube_pga_device(RtsContext* c, const RtsPgaParams& p, const RtsPgaPlan& plan, double* out);      // out: phase [n_rx][N], then rms [n_rx][n_iters]
+int rts_cube_correct_device(RtsContext* c, const RtsCorrectParams& p, const RtsCorrectPlan& plan, const double* shifts, const double* phase);      // the tables on the device, or null
 int rts_cube_beat_device(RtsContext* c, uint32_t pulse_index, const RtsBeatParams& p, const RtsBeatPlan& plan, double cspeed, double carrier, int64_t base);      // rts_beat.hip
 int rts_cube_range_device(RtsContext* c, const RtsRangeParams& p, const RtsRangePlan& plan, const double* window, double* out);
 int rts_cube_sources_device(RtsContext* c, const RtsSrcPlan& plan, uint32_t K, bool has_profile, uint64_t seed, uint64_t live, const double* table);      // rts_source.hip
