@@ -244,7 +244,7 @@ extern "C" int rts_set_receivers(RtsHandle c, const RtsReceiverSphere* rx, uint3
     CHECK_CLOSED(c);
     if (n_rx && !rx) { rts_set_error("rts_set_receivers: null array"); return RTS_ERR_INVALID; }
     if (n_rx > 65535) { rts_set_error("rts_set_receivers: more than 65535 receivers"); return RTS_ERR_UNSUPPORTED; }
-    { int rc = check_key_width(c->depth, (uint32_t)c->scene->meshes.size(), n_rx, "rts_set_receivers"); if (rc != RTS_OK) return rc; }
+    RTS_TRY(check_key_width(c->depth, (uint32_t)c->scene->meshes.size(), n_rx, "rts_set_receivers"));
     std::vector<RtsRxDev> h(n_rx);
     for (uint32_t i = 0; i < n_rx; i++) {
         const RtsReceiverSphere& r = rx[i];
@@ -429,11 +429,11 @@ extern "C" int rts_reserve(RtsHandle c, uint64_t n_rays)
     // upper bounds of any launch's grid: threads of the child slab, threads of the overflow stack, blocks of both kernels
     const RtsLaunchSizes sz = rts_launch_sizes(n, (uint64_t)c->n_cu * 64 * RTS_BLOCK, (uint64_t)c->n_cu * 1024, rts_coop_threads(c), (uint64_t)c->n_cu * 64 + c->tune.coop_grid_max,
                                                c->params.max_refl, c->params.max_refr, (c->params.flags & RTS_FLAG_KEEP_ALL_RAYS) != 0);
-    { int rc = rts_launch_buffers_reserve(c, sz); if (rc != RTS_OK) return rc; }
-    { int rc = rts_zero_block_reserve(c); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_launch_buffers_reserve(c, sz));
+    RTS_TRY(rts_zero_block_reserve(c));
     const size_t n_tiles = (size_t)rts_wave_tiles(n);
     RTS_HIP(c->d_tile_cost.reserve(n_tiles)); RTS_HIP(c->d_tile_key.reserve(n_tiles)); RTS_HIP(c->d_tile_order.reserve(n_tiles));
-    { int rc = rts_hist_ensure(c, (uint32_t)rts_wave_tiles(W3)); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_hist_ensure(c, (uint32_t)rts_wave_tiles(W3)));
     // touch the two slabs the trace kernel writes sparsely, so that their pages exist before the first launch
     RTS_HIP(hipMemsetAsync(c->d_recv.p, 0, sizeof(RtsEndRecord) * sz.recv, c->stream));
     RTS_HIP(hipMemsetAsync(c->d_dir_hist.p, 0, sizeof(float) * c->d_dir_hist.cap, c->stream));
@@ -542,7 +542,7 @@ static int pulse_upload_and_fill(RtsContext* c, bool moved)
     const uint32_t n_targets = (uint32_t)c->scene->meshes.size(); const RtsMaskFrame& mask = c->last_lc.mask;
     c->pin.p->lc = c->last_lc;
     RTS_HIP(hipMemcpyAsync(c->d_params.p, &c->pin.p->lc, moved && n_targets ? offsetof(RtsPinned, td) + sizeof(RtsTargetDev) * n_targets : sizeof(RtsLaunchConsts), hipMemcpyHostToDevice, c->stream));
-    { int rc = rts_zero_block_reserve(c); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_zero_block_reserve(c));
     RTS_HIP(hipMemsetAsync(c->d_tile_ctr.p, 0, sizeof(uint32_t) * (((RTS_ZERO_WORDS + (mask.n ? (size_t)mask.n * mask.n / 32u + 1u : 0u)) + 63u) & ~(size_t)63u), c->stream));      // (a whole number of 256-byte pieces: the runtime splits an odd-sized fill into two kernels)
     return RTS_OK;
 }
@@ -550,7 +550,7 @@ static int pulse_upload_and_fill(RtsContext* c, bool moved)
 // Leaves the placement (a target moved) and the primary-ray mask enqueued -- one pass over the leaves for both -- and bvh_valid true.
 static int pulse_scene_place(RtsContext* c, bool moved)
 {
-    { int rc = rts_scene_place(c, c->last_lc, moved, pulse_mask_words(c)); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_scene_place(c, c->last_lc, moved, pulse_mask_words(c)));
     if (moved) { RTS_STAGE(c, "scene_place"); c->bvh_valid = true; c->stats.bvh_rebuilt = 1; }
     RTS_HIP(hipEventRecord(c->ev[1], c->stream));
     return RTS_OK;
@@ -573,7 +573,7 @@ static int pulse_args_and_buffers(RtsContext* c, RtsPulseLaunch& L)
     a.coop_walk_steps = c->tune.coop_walk_steps; a.coop_min_cost = c->tune.coop_walk_steps ? std::min<uint32_t>(c->tune.coop_floor, 1875u) : 0u;      // (nothing shorter than 50 us is looked at; RTS_COOP_STEPS=0: every tile is flagged)
     a.slab_threads = a.total_threads + rts_coop_threads(c);
     const RtsLaunchSizes sz = rts_launch_sizes(n, a.total_threads, a.total_threads, rts_coop_threads(c), (uint64_t)L.grid + c->tune.coop_grid_max, a.max_refl, a.max_refr, L.keep_all);
-    { int rc = rts_launch_buffers_reserve(c, sz); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_launch_buffers_reserve(c, sz));
     if (L.keep_all) {      // (the buffers' last element is spare)
         rts_fill_i32(st, c->d_hit_prim.p, -2, sz.hit_prim - 1);
         RTS_HIP(hipMemsetAsync(c->d_hit_t.p, 0, sizeof(float) * (sz.hit_t - 1), st));
@@ -599,10 +599,10 @@ static int pulse_tile_order(RtsContext* c, RtsPulseLaunch& L)
     const uint32_t n_tiles = s.n_tiles, resident_waves = L.grid * (RTS_BLOCK / RTS_WTILE);
     a.batch_dead = s.aligned ? (uint32_t)c->tune.batch_dead : 0u;      // (a wave tile must be 64 CONSECUTIVE launch indices for the tile-level screen: rts_tile_maybe)
     if (!(c->tune.tile_lpt && s.aligned && n_tiles > resident_waves)) { c->tile_cost_pending = false; c->tile_last_valid = false; return RTS_OK; }
-    { int rc = rts_hist_ensure(c, s.n_hist); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_hist_ensure(c, s.n_hist));
     if (c->tile_cost_pending || c->hist->any) {
         c->coop_big_now = (L.r.il_parts > 1 && !L.shared_gpu && c->tune.coop_big_part > c->tune.coop_big) ? c->tune.coop_big_part : c->tune.coop_big;
-        int rc = rts_tile_order_build(c, c->tile_cost_sig, c->tile_cost_pending, s.sig, n_tiles, resident_waves); if (rc != RTS_OK) return rc;
+        RTS_TRY(rts_tile_order_build(c, c->tile_cost_sig, c->tile_cost_pending, s.sig, n_tiles, resident_waves));
         a.tile_order = c->d_tile_order.p; a.tile_head = c->tune.coop_frac > 0.0 ? c->d_tile_ctr.p + RTS_OFF_HEAD + 2 : nullptr; a.tile_head_all = a.tile_head; c->hist->any = true;
         a.tile_live = c->d_tile_ctr.p + RTS_OFF_LIVE;      // (written by the order build)
     }
@@ -698,7 +698,7 @@ extern "C" int rts_trace_pulse_begin(RtsHandle c, const RtsPulse* p)
     if (L.r.err != RTS_RANGE_OK && L.r.err != RTS_RANGE_LIST_BEYOND) return pulse_range_error(c, p, L.r);
     pulse_reset_results(c, p);
     RTS_HIP(hipEventRecord(c->ev[0], c->stream));
-    { int rc = pulse_stage_motion(c, p, &L.moved); if (rc != RTS_OK) return rc; }
+    RTS_TRY(pulse_stage_motion(c, p, &L.moved));
     if (L.r.err != RTS_RANGE_OK) return pulse_range_error(c, p, L.r);
     L.n = (uint32_t)L.r.count;
     c->ray_first = L.r.first; c->n_rays = L.n;
@@ -712,16 +712,16 @@ extern "C" int rts_trace_pulse_begin(RtsHandle c, const RtsPulse* p)
     L.pre_filter = c->tune.use_pmask && !c->pre_dense;           // (a launch where most rays hit pays for the filter and skips nothing)
     pulse_fill_constants(c, *p, L.r, L.pre_filter);
     lt.lap(0);
-    { int rc = pulse_upload_and_fill(c, L.moved); if (rc != RTS_OK) return rc; }
+    RTS_TRY(pulse_upload_and_fill(c, L.moved));
     lt.lap(1);
-    { int rc = pulse_scene_place(c, L.moved); if (rc != RTS_OK) return rc; }
+    RTS_TRY(pulse_scene_place(c, L.moved));
     lt.lap(2);
-    { int rc = pulse_args_and_buffers(c, L); if (rc != RTS_OK) return rc; }
-    { int rc = pulse_tile_order(c, L); if (rc != RTS_OK) return rc; }
-    { int rc = pulse_timelines(c, L); if (rc != RTS_OK) return rc; }
+    RTS_TRY(pulse_args_and_buffers(c, L));
+    RTS_TRY(pulse_tile_order(c, L));
+    RTS_TRY(pulse_timelines(c, L));
     c->last_args = L.a;
     lt.lap(3);
-    { int rc = pulse_launch(c, L); if (rc != RTS_OK) return rc; }
+    RTS_TRY(pulse_launch(c, L));
     lt.lap(4);
     // (the eight counters were written into the pinned block by k_sum_counters itself: no copy)
     c->pulse.begin(open_here);
@@ -792,7 +792,7 @@ static void pulse_debug_dump(RtsContext* c, const unsigned long long* cnt)
 static int rts_pulse_home(RtsContext* c)
 {
     const unsigned long long* cnt = c->pin.p->cnt;
-    { int rc = rts_counters_home(c, cnt); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_counters_home(c, cnt));
     if (c->tl_blocks) pulse_timeline_summary(c);
     rts_pulse_account(c, cnt);
     return RTS_OK;
@@ -802,9 +802,9 @@ static int rts_pulse_home(RtsContext* c)
 static int rts_post_received(RtsContext* c)
 {
     RTS_HIP(hipEventRecord(c->ev[4], c->stream));
-    int rc = rts_post_order_and_expand(c); if (rc != RTS_OK) return rc;
-    if (c->params.flags & RTS_FLAG_KEEP_ALL_RAYS) { rc = rts_post_expand_all(c); if (rc != RTS_OK) return rc; }
-    if (c->res.mirror.want) { rc = rts_post_mirror_received(c); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_post_order_and_expand(c));
+    if (c->params.flags & RTS_FLAG_KEEP_ALL_RAYS) { RTS_TRY(rts_post_expand_all(c)); }
+    if (c->res.mirror.want) { RTS_TRY(rts_post_mirror_received(c)); }
     RTS_HIP(hipEventRecord(c->ev[5], c->stream));
     return RTS_OK;
 }
@@ -815,7 +815,7 @@ extern "C" int rts_trace_pulse_end(RtsHandle c)
     CHECK_HANDLE(c);
     if (!c->pulse.end()) { rts_set_error("rts_trace_pulse_end: no pulse in flight on this handle"); return RTS_ERR_INVALID; }
     RTS_HIP(rts_stream_wait(c, c->stream));         // the one host sync of the launch: the received count sizes what follows
-    { int rc = rts_pulse_home(c); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_pulse_home(c));
     if (c->tune.debug_coop && c->d_order_sum.p && c->d_tile_ctr.p) pulse_debug_dump(c, c->pin.p->cnt);
     c->res.agg_timed = false; c->res.fin_timed = false;
     return rts_post_received(c);
@@ -904,7 +904,7 @@ static int rts_spec_resolve(RtsContext* c)      // the outcome of a chain that w
     if (!c->pulse.resolve()) return RTS_OK;
     RTS_HIP(hipSetDevice(c->device));
     RTS_HIP(rts_stream_wait(c, c->stream));
-    { int rc = rts_pulse_home(c); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_pulse_home(c));
     if (c->res.n_recv > c->spec_cap) {                                      // more rays than the speculative chain was sized for: it did nothing; the ordinary chain now
         c->res.agg_pending.valid = false;
         return rts_post_chain(c);
@@ -960,7 +960,7 @@ static int rts_trace_pulse_end_chain(RtsContext* c)
     // only the one-block path reads it on the device): such a handle never speculates
     const uint32_t cap = rts_spec_cap(c->last_args.max_refr, rts_handle_key_plan(c));
     if (rts_speculates(c, cap)) return rts_chain_on_device_count(c, cap);
-    int rc = rts_trace_pulse_end(c); if (rc != RTS_OK) return rc;
+    RTS_TRY(rts_trace_pulse_end(c));
     return rts_post_chain(c, true);
 }
 
@@ -1008,7 +1008,7 @@ static RtsPatView pat_view(const RtsPattern& p)
 
 extern "C" int rts_pattern_eval(const RtsPattern* p, const double* u, const double* v, uint32_t n, double* out)
 {
-    int rc = rts_pattern_check(p, "rts_pattern_eval:", 0); if (rc != RTS_OK) return rc;
+    RTS_TRY(rts_pattern_check(p, "rts_pattern_eval:", 0));
     if (n && (!u || !v || !out)) { rts_set_error("rts_pattern_eval: null point or output array"); return RTS_ERR_INVALID; }
     const RtsPatView w = pat_view(*p);
     for (uint32_t i = 0; i < n; i++) out[i] = rts_pat_eval(w, u[i], v[i]);
@@ -1022,9 +1022,9 @@ extern "C" int rts_set_patterns(RtsHandle c, const RtsPattern* tx, const RtsPatt
     if (n_rx > (1u << 20) || n_targets > (1u << 20)) { rts_set_error("rts_set_patterns: %u receivers / %u targets", n_rx, n_targets); return RTS_ERR_INVALID; }
     std::vector<const RtsPattern*> all; all.reserve(1 + (size_t)n_rx + n_targets);
     all.push_back(tx); for (uint32_t k = 0; k < n_rx; k++) all.push_back(&rx[k]); for (uint32_t t = 0; t < n_targets; t++) all.push_back(&rcs[t]);
-    { int rc = rts_pattern_check(tx, "rts_set_patterns: transmitter", 0); if (rc != RTS_OK) return rc; }
-    for (uint32_t k = 0; k < n_rx; k++) { int rc = rts_pattern_check(&rx[k], "rts_set_patterns: receiver", k); if (rc != RTS_OK) return rc; }
-    for (uint32_t t = 0; t < n_targets; t++) { int rc = rts_pattern_check(&rcs[t], "rts_set_patterns: target", t); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_pattern_check(tx, "rts_set_patterns: transmitter", 0));
+    for (uint32_t k = 0; k < n_rx; k++) RTS_TRY(rts_pattern_check(&rx[k], "rts_set_patterns: receiver", k));
+    for (uint32_t t = 0; t < n_targets; t++) RTS_TRY(rts_pattern_check(&rcs[t], "rts_set_patterns: target", t));
     // ---- pack: [views | the tables' arrays], offsets first, device pointers once the buffer exists
     const size_t n_pat = all.size(), head = (n_pat * sizeof(RtsPatView) + 15) & ~(size_t)15;
     size_t n_dbl = 0;
@@ -1085,7 +1085,7 @@ extern "C" int rts_finalise_patterns(RtsHandle c, const RtsPatternPulse* pulse)
     CHECK_HANDLE(c);
     CHECK_CLOSED(c);
     RtsSpecParams q;
-    int rc = rts_pattern_pulse_params(c, pulse, q, "rts_finalise_patterns"); if (rc != RTS_OK) return rc;
+    RTS_TRY(rts_pattern_pulse_params(c, pulse, q, "rts_finalise_patterns"));
     return rts_finalise_bracket(c, [&] { return rts_post_finalise_patterns(c, q); });
 }
 
@@ -1095,7 +1095,7 @@ extern "C" int rts_trace_pulse_end_patterns(RtsHandle c, const RtsPatternPulse* 
     if (!c->pulse.open()) { rts_set_error("rts_trace_pulse_end_patterns: no pulse in flight on this handle"); return RTS_ERR_INVALID; }
     if (cube_pulse >= 0 && (!c->cube.set || (uint32_t)cube_pulse >= c->cube.params.n_pulses)) { rts_set_error("rts_trace_pulse_end_patterns: no cube attached, or pulse %d outside it", cube_pulse); return RTS_ERR_INVALID; }
     RtsSpecParams& q = c->spec;
-    int rc = rts_pattern_pulse_params(c, pulse, q, "rts_trace_pulse_end_patterns"); if (rc != RTS_OK) return rc;
+    RTS_TRY(rts_pattern_pulse_params(c, pulse, q, "rts_trace_pulse_end_patterns"));
     q.rcs.assign(c->scene->meshes.size() + 1, 1.0); q.gt = q.gr = 1.0;
     q.cube_pulse = cube_pulse; q.base = recv_index_base; q.mode = 0;
     return rts_trace_pulse_end_chain(c);
@@ -1113,7 +1113,7 @@ extern "C" int rts_received_prefetch(RtsHandle c)
     CHECK_HANDLE(c);
     if (!c->pulse.open()) { rts_set_error("rts_received_prefetch: no pulse in flight on this handle"); return RTS_ERR_INVALID; }
     const uint32_t cap = rts_small_cap(rts_recv_key64(c->last_args.max_refr));      // (the chain's only sort: the received rows')
-    { int rc = rts_mirror_reserve(c, cap); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_mirror_reserve(c, cap));
     c->res.mirror.want = true;
     if (!rts_speculates(c, cap)) return RTS_OK;
     c->spec.mode = 1;
@@ -1129,7 +1129,7 @@ extern "C" int rts_set_tile_list(RtsHandle c, uint32_t tile, const uint32_t* til
     if (c->pulse.open()) { rts_set_error("rts_set_tile_list: a pulse of this handle is in flight"); return RTS_ERR_INVALID; }
     CHECK_CLOSED(c);
     // the cost records of the last launch are indexed through the list in force: into the history before it goes
-    { int rc = rts_tile_costs_flush(c); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_tile_costs_flush(c));
     if (tile == 0) { c->il_list_n = 0; c->il_list_tile = 0; c->il_list_gen++; c->tile_last_valid = false; return RTS_OK; }      // no list any more
     if ((n_ids && !tile_ids) || tile % RTS_WTILE != 0) { rts_set_error("rts_set_tile_list: tile must be a positive multiple of %d launch indices (got %u)", RTS_WTILE, tile); return RTS_ERR_INVALID; }
     if (n_ids == 0) { c->il_list_n = 0; c->il_list_tile = tile; c->il_list_last = 0; c->il_list_gen++; c->tile_last_valid = false; return RTS_OK; }      // an EMPTY list: this worker was dealt nothing, its launches trace no launch index
@@ -1151,9 +1151,9 @@ extern "C" int rts_tile_records_get(RtsHandle c, uint32_t* records, uint32_t n)
     if (c->pulse.open()) { rts_set_error("rts_tile_records_get: a pulse of this handle is in flight"); return RTS_ERR_INVALID; }
     const uint64_t total = rts_lattice_size(c->params.width);
     if (!records || n != (uint32_t)rts_wave_tiles(total)) { rts_set_error("rts_tile_records_get: n must be ceil(W^3 / %d) = %llu", RTS_WTILE, (unsigned long long)rts_wave_tiles(total)); return RTS_ERR_INVALID; }
-    { int rc = rts_tile_costs_flush(c); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_tile_costs_flush(c));
     RTS_HIP(c->d_rec_tmp.reserve(n));
-    { int rc = rts_tile_records_masked(c, c->d_rec_tmp.p, n); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_tile_records_masked(c, c->d_rec_tmp.p, n));
     RTS_HIP(hipMemcpyAsync(records, c->d_rec_tmp.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, c->stream));
     RTS_HIP(hipStreamSynchronize(c->stream));
     return RTS_OK;
@@ -1470,7 +1470,7 @@ static int wrapper_context(RtsContext** out)
     if (it == g_wrapper_ctx.end()) {
         RtsParams p; memset(&p, 0, sizeof(p)); p.width = 1; p.max_refl = 1; p.device = cur;
         RtsContext* c = nullptr;
-        int rc = rts_create(&p, &c); if (rc != RTS_OK) return rc;
+        RTS_TRY(rts_create(&p, &c));
         it = g_wrapper_ctx.emplace(cur, c).first;
     }
     *out = it->second;
@@ -1486,7 +1486,7 @@ extern "C" int rts_kernel_wrapper_on(RtsHandle h, PerRayData* h_rx_results_arr, 
     if (receivedRays == 0) return RTS_OK;
     if (!h_rx_results_arr || (depthTotal && !h_rx_intersects_arr) || !h_delay_arr || !h_phase_arr || !h_pathMatch) { rts_set_error("rts_kernel_wrapper: null array"); return RTS_ERR_INVALID; }
     RtsContext* c = h;
-    if (!c) { int rc = wrapper_context(&c); if (rc != RTS_OK) return rc; }
+    if (!c) RTS_TRY(wrapper_context(&c));
     else { CHECK_CLOSED(c); c->res.forget(); c->pulse_traced = false; }      // the handle's own received set is overwritten
     RTS_HIP(hipSetDevice(c->device));
     const size_t R = receivedRays, D = depthTotal;

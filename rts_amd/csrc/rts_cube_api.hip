@@ -3,30 +3,7 @@
 #include <cmath>
 #include <cstring>
 #include <algorithm>
-#include "rts_internal.h"
-
-// ------------------------------------------------------------------------------------- shared argument checks (each forms the message of the entry point `who`), the copy-out
-#define NEED_CUBE(c, who, wording) do { if (!(c)->cube.set) { rts_set_error("%s: %s", (who), (wording)); return RTS_ERR_INVALID; } } while (0)
-
-static int rts_pulses_check(const char* who, uint32_t first, uint32_t n, uint32_t rows, bool at_least_one)      // pulses first .. first + n inside the cube's rows; a product needs at least one
-{
-    if ((!at_least_one || n != 0) && first < rows && n <= rows - first) return RTS_OK;
-    if (at_least_one) rts_set_error("%s: first_pulse = %u, n_pulses = %u: at least one pulse, inside the cube's %u rows", who, first, n, rows);
-    else rts_set_error("%s: pulses %u .. %u + %u outside the cube's %u", who, first, first, n, rows);
-    return RTS_ERR_INVALID;
-}
-
-static int rts_taps_check(const char* who, uint32_t taps)      // the interpolator's support (rts_waveform.h): the nearest sample, or an even number of taps
-{
-    if (taps != 1u && (taps < 2u || taps > RTS_WAVEFORM_MAX_TAPS || (taps & 1u))) { rts_set_error("%s: taps = %u (1, or even in [2, %u])", who, taps, RTS_WAVEFORM_MAX_TAPS); return RTS_ERR_INVALID; }
-    return RTS_OK;
-}
-
-static int rts_pulse_index_check(const char* who, uint32_t pulse_index, uint32_t rows)      // the row an impulse writer or the waveform render adds to
-{
-    if (pulse_index >= rows) { rts_set_error("%s: pulse %u >= %u", who, pulse_index, rows); return RTS_ERR_INVALID; }
-    return RTS_OK;
-}
+#include "rts_cube_api.h"
 
 // what a render reads and how (rts_cube_render's arguments, RtsBeatParams' fields); RTS_RENDER_PATHS reads the aggregation's results
 static int rts_render_source_check(const char* who, uint32_t source, uint32_t flags)
@@ -38,16 +15,6 @@ static int rts_render_source_check(const char* who, uint32_t source, uint32_t fl
 static int rts_render_paths_check(const RtsContext* c, const char* who)
 {
     if (!c->res.agg_valid) { rts_set_error("%s: RTS_RENDER_PATHS needs rts_aggregate of this pulse first (the groups' power, delay and phase are its results)", who); return RTS_ERR_INVALID; }
-    return RTS_OK;
-}
-
-// `doubles` doubles at src -> the host, once the stream has produced them; have: they exist (the cube, or a valid product: its RECORDED place and size); none: the message when not
-static int rts_cube_copy_out(RtsContext* c, const char* who, const char* none, bool have, const double* src, size_t doubles, double* host_out, uint64_t capacity_doubles)
-{
-    if (!c->cube.set || !have || !host_out) { rts_set_error("%s: %s", who, none); return RTS_ERR_INVALID; }
-    if (capacity_doubles < doubles) { rts_set_error("%s: capacity too small", who); return RTS_ERR_CAPACITY; }
-    RTS_HIP(hipStreamSynchronize(c->stream));
-    RTS_HIP(hipMemcpy(host_out, src, sizeof(double) * doubles, hipMemcpyDeviceToHost));
     return RTS_OK;
 }
 
@@ -71,7 +38,7 @@ extern "C" int rts_cube_accumulate(RtsHandle c, uint32_t pulse_index, double csp
     CHECK_HANDLE(c);
     CHECK_CLOSED(c);
     NEED_CUBE(c, "rts_cube_accumulate", "call rts_cube_attach first");
-    { int rc = rts_pulse_index_check("rts_cube_accumulate", pulse_index, c->cube.params.n_pulses); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_pulse_index_check("rts_cube_accumulate", pulse_index, c->cube.params.n_pulses));
     return rts_cube_accumulate_device(c, pulse_index, cspeed, carrier);
 }
 
@@ -81,7 +48,7 @@ extern "C" int rts_cube_accumulate_paths(RtsHandle c, uint32_t pulse_index)
     CHECK_CLOSED(c);
     NEED_CUBE(c, "rts_cube_accumulate_paths", "call rts_cube_attach first");
     if (!c->res.agg_valid) { rts_set_error("rts_cube_accumulate_paths: call rts_aggregate for this pulse first (the groups' power, delay and phase are its results)"); return RTS_ERR_INVALID; }
-    { int rc = rts_pulse_index_check("rts_cube_accumulate_paths", pulse_index, c->cube.params.n_pulses); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_pulse_index_check("rts_cube_accumulate_paths", pulse_index, c->cube.params.n_pulses));
     return rts_cube_accumulate_paths_device(c, pulse_index, c->res.agg_base_local);
 }
 
@@ -90,7 +57,7 @@ extern "C" int rts_cube_doppler(RtsHandle c, uint32_t n_fft, void* device_out)
     CHECK_HANDLE(c);
     CHECK_CLOSED(c);
     NEED_CUBE(c, "rts_cube_doppler", "call rts_cube_attach first");
-    if (n_fft < 2 || n_fft > 4096 || (n_fft & (n_fft - 1)) != 0 || n_fft < c->cube.params.n_pulses) {
+    if (!rts_pow2_in(n_fft, 2u, 4096u) || n_fft < c->cube.params.n_pulses) {
         rts_set_error("rts_cube_doppler: n_fft = %u must be a power of two in [max(2, n_pulses = %u), 4096]", n_fft, c->cube.params.n_pulses); return RTS_ERR_INVALID; }
     const size_t doubles = 2 * (size_t)c->cube.params.n_rx * n_fft * c->cube.params.n_bins;
     double* out; RTS_HIP(c->cube.doppler.place(device_out, doubles, &out));
@@ -102,7 +69,7 @@ extern "C" int rts_cube_doppler_get(RtsHandle c, double* host_out, uint64_t capa
 {
     CHECK_HANDLE(c);
     CHECK_CLOSED(c);
-    return rts_cube_copy_out(c, "rts_cube_doppler_get", "no transform (rts_cube_doppler) / null output", c->cube.doppler.valid, c->cube.doppler.p, c->cube.doppler.doubles, host_out, capacity_doubles);
+    return rts_cube_copy_out(c, "rts_cube_doppler_get", "no transform (rts_cube_doppler) / null output", c->cube.doppler, host_out, capacity_doubles);
 }
 
 extern "C" int rts_cube_get(RtsHandle c, double* host_out, uint64_t capacity_doubles)
@@ -119,7 +86,7 @@ static int rts_waveform_check(const RtsWaveform* w, const char* who)
     if (!w) { rts_set_error("%s: null waveform", who); return RTS_ERR_INVALID; }
     if (w->reserved[0] || w->reserved[1]) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
     if (w->n_samples == 0 || w->n_samples > RTS_WAVEFORM_MAX_SAMPLES) { rts_set_error("%s: %u samples (1 .. %u)", who, w->n_samples, RTS_WAVEFORM_MAX_SAMPLES); return RTS_ERR_INVALID; }
-    { int rc = rts_taps_check(who, w->taps); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_taps_check(who, w->taps));
     if (!w->samples) { rts_set_error("%s: null sample array", who); return RTS_ERR_INVALID; }
     for (uint32_t i = 0; i < 2 * w->n_samples; i++) if (!std::isfinite(w->samples[i])) { rts_set_error("%s: sample %u is not finite", who, i / 2); return RTS_ERR_INVALID; }
     return RTS_OK;
@@ -127,7 +94,7 @@ static int rts_waveform_check(const RtsWaveform* w, const char* who)
 
 extern "C" int rts_waveform_eval(const RtsWaveform* w, const double* x, uint32_t n, double* out)
 {
-    int rc = rts_waveform_check(w, "rts_waveform_eval"); if (rc != RTS_OK) return rc;
+    RTS_TRY(rts_waveform_check(w, "rts_waveform_eval"));
     if (n && (!x || !out)) { rts_set_error("rts_waveform_eval: null point or output array"); return RTS_ERR_INVALID; }
     for (uint32_t i = 0; i < n; i++) rts_wave_eval(w->samples, w->n_samples, w->taps, x[i], &out[2 * (size_t)i], &out[2 * (size_t)i + 1]);
     return RTS_OK;
@@ -136,7 +103,7 @@ extern "C" int rts_waveform_eval(const RtsWaveform* w, const double* x, uint32_t
 extern "C" int rts_cube_set_waveform(RtsHandle c, const RtsWaveform* w)
 {
     CHECK_HANDLE(c);
-    int rc = rts_waveform_check(w, "rts_cube_set_waveform"); if (rc != RTS_OK) return rc;
+    RTS_TRY(rts_waveform_check(w, "rts_cube_set_waveform"));
     // the handle's enqueued work may still read the previous waveform: a speculative chain is resolved, then the stream drained
     if (c->pulse.chained()) CHECK_CLOSED(c);      // (an OPEN pulse stays in flight: its render comes after the stream is drained below)
     RTS_HIP(hipStreamSynchronize(c->stream));
@@ -149,13 +116,13 @@ extern "C" int rts_cube_set_waveform(RtsHandle c, const RtsWaveform* w)
 extern "C" int rts_cube_render(RtsHandle c, uint32_t pulse_index, uint32_t source, uint32_t flags, double cspeed, double carrier)
 {
     CHECK_HANDLE(c);
-    { int rc = rts_render_source_check("rts_cube_render", source, flags); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_render_source_check("rts_cube_render", source, flags));
     CHECK_CLOSED(c);
     NEED_CUBE(c, "rts_cube_render", "call rts_cube_attach first");
     if (!c->cube.wave_set) { rts_set_error("rts_cube_render: no waveform (rts_cube_set_waveform)"); return RTS_ERR_INVALID; }
-    { int rc = rts_pulse_index_check("rts_cube_render", pulse_index, c->cube.params.n_pulses); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_pulse_index_check("rts_cube_render", pulse_index, c->cube.params.n_pulses));
     const bool paths = source == RTS_RENDER_PATHS;
-    if (paths) { int rc = rts_render_paths_check(c, "rts_cube_render"); if (rc != RTS_OK) return rc; }
+    if (paths) RTS_TRY(rts_render_paths_check(c, "rts_cube_render"));
     return rts_cube_render_device(c, pulse_index, paths, (flags & RTS_RENDER_DOPPLER) != 0, cspeed, carrier, c->res.agg_base_local);
 }
 
@@ -166,7 +133,7 @@ extern "C" int rts_cube_compress(RtsHandle c, uint32_t first_pulse, uint32_t n_p
     NEED_CUBE(c, "rts_cube_compress", "call rts_cube_attach first");
     if (!c->cube.wave_set) { rts_set_error("rts_cube_compress: no waveform (rts_cube_set_waveform)"); return RTS_ERR_INVALID; }
     const RtsCubeParams& q = c->cube.params;
-    { int rc = rts_pulses_check("rts_cube_compress", first_pulse, n_pulses, q.n_pulses, false); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_pulses_check("rts_cube_compress", first_pulse, n_pulses, q.n_pulses, false));
     if (q.n_bins > RTS_COMPRESS_MAX_BINS) { rts_set_error("rts_cube_compress: %u range bins > %u (RTS_COMPRESS_MAX_BINS: one row of complex128 in a workgroup's LDS)", q.n_bins, RTS_COMPRESS_MAX_BINS); return RTS_ERR_INVALID; }
     return rts_cube_compress_device(c, first_pulse, n_pulses);
 }
@@ -189,7 +156,7 @@ extern "C" int rts_cube_add_noise(RtsHandle c, uint32_t first_pulse, uint32_t n_
     CHECK_CLOSED(c);
     NEED_CUBE(c, "rts_cube_add_noise", "call rts_cube_attach first");
     const RtsCubeParams& q = c->cube.params;
-    { int rc = rts_pulses_check("rts_cube_add_noise", first_pulse, n_pulses, q.n_pulses, false); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_pulses_check("rts_cube_add_noise", first_pulse, n_pulses, q.n_pulses, false));
     if ((uintptr_t)c->cube.p & 15u) { rts_set_error("rts_cube_add_noise: the cube's device memory is not 16-byte aligned"); return RTS_ERR_INVALID; }
     return rts_cube_noise_device(c, first_pulse, n_pulses, sqrt(noise_power / 2.0), seed);
 }
@@ -222,8 +189,8 @@ static int rts_sources_check(const char* who, const RtsSourceParams* p, uint32_t
 extern "C" int rts_sources_eval(const RtsCubeParams* q, const RtsSourceParams* p, double* cube_inout)
 {
     const char* who = "rts_sources_eval";
-    if (!q || q->n_rx == 0 || q->n_pulses == 0 || q->n_bins == 0) { rts_set_error("%s: bad cube parameters", who); return RTS_ERR_INVALID; }
-    { int rc = rts_sources_check(who, p, q->n_rx, q->n_bins); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_eval_cube_check(who, q, true, false));
+    RTS_TRY(rts_sources_check(who, p, q->n_rx, q->n_bins));
     if (!cube_inout) { rts_set_error("%s: null array", who); return RTS_ERR_INVALID; }
     std::vector<double> work(rts_src_work_doubles(p->n_patches));
     rts_sources_eval_host(q, p, cube_inout, work.data());
@@ -236,7 +203,7 @@ extern "C" int rts_cube_add_sources(RtsHandle c, const RtsSourceParams* p)
     CHECK_HANDLE(c);
     NEED_CUBE(c, who, "no cube (call rts_cube_attach first)");
     const RtsCubeParams& q = c->cube.params;
-    { int rc = rts_sources_check(who, p, q.n_rx, q.n_bins); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_sources_check(who, p, q.n_rx, q.n_bins));
     if ((uintptr_t)c->cube.p & 15u) { rts_set_error("%s: the cube's device memory is not 16-byte aligned", who); return RTS_ERR_INVALID; }
     const RtsSrcPlan plan = rts_src_plan(q.n_rx, q.n_bins, p->n_patches, p->range_profile != nullptr);
     if (!plan.supported) { rts_set_error("%s: a cube of %u receivers x %u bins with %u patches has no launch plan", who, q.n_rx, q.n_bins, p->n_patches); return RTS_ERR_INVALID; }
@@ -253,20 +220,6 @@ extern "C" int rts_cube_add_sources(RtsHandle c, const RtsSourceParams* p)
 }
 
 // The checks rts_cube_detect, rts_cube_detect_os and rts_cfar_os_eval share, in the order each of them applies them.
-// The map of a device detector: the caller's (n_doppler rows, 16-byte aligned) or the handle's last Doppler map.
-static int rts_cfar_map(RtsContext* c, const char* who, const void* device_map, const double** map, uint32_t* n_doppler)
-{
-    *map = (const double*)device_map;
-    if (*map) {
-        if (*n_doppler == 0) { rts_set_error("%s: n_doppler = 0 with a caller map", who); return RTS_ERR_INVALID; }
-        if ((uintptr_t)*map & 15u) { rts_set_error("%s: device_map is not 16-byte aligned", who); return RTS_ERR_INVALID; }
-    } else {
-        if (!c->cube.doppler.valid) { rts_set_error("%s: no map (call rts_cube_doppler first, or pass device_map)", who); return RTS_ERR_INVALID; }
-        *map = c->cube.doppler.p; *n_doppler = c->cube.doppler_n;
-    }
-    return RTS_OK;
-}
-
 // flags, reserved fields and the window of either parameter record on a map of n_doppler x nb cells
 template <class Params> static int rts_cfar_window_check(const char* who, const Params* p, uint32_t nb, uint32_t n_doppler)
 {
@@ -305,13 +258,13 @@ extern "C" int rts_cube_detect(RtsHandle c, const RtsCfarParams* p, const void* 
     CHECK_CLOSED(c);
     NEED_CUBE(c, "rts_cube_detect", "no cube (call rts_cube_attach first)");
     const double* map;
-    { int rc = rts_cfar_map(c, "rts_cube_detect", device_map, &map, &n_doppler); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_cfar_map(c, "rts_cube_detect", device_map, &map, &n_doppler));
     if (p->mode > RTS_CFAR_SO) { rts_set_error("rts_cube_detect: unknown mode %u (RTS_CFAR_CA, _GO, _SO)", p->mode); return RTS_ERR_INVALID; }
-    { int rc = rts_cfar_window_check("rts_cube_detect", p, c->cube.params.n_bins, n_doppler); if (rc != RTS_OK) return rc; }
-    { int rc = rts_cfar_level_check("rts_cube_detect", p->pfa, p->alpha); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_cfar_window_check("rts_cube_detect", p, c->cube.params.n_bins, n_doppler));
+    RTS_TRY(rts_cfar_level_check("rts_cube_detect", p->pfa, p->alpha));
     if (p->mode != RTS_CFAR_CA && p->pfa != 0.0) { rts_set_error("rts_cube_detect: pfa is for mode RTS_CFAR_CA only (GO / SO take alpha)"); return RTS_ERR_INVALID; }
     if (p->mode != RTS_CFAR_CA && p->train_range == 0) { rts_set_error("rts_cube_detect: train_range = 0 with GO / SO (the halves are range halves)"); return RTS_ERR_INVALID; }
-    { int rc = rts_cfar_pri_check("rts_cube_detect", p->pri); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_cfar_pri_check("rts_cube_detect", p->pri));
     c->cube.det_valid = false; c->cube.plot_valid = false;      // (plots index the list they were made from)
     return rts_cube_detect_device(c, *p, map, n_doppler, p->max_detections ? p->max_detections : RTS_CFAR_DEFAULT_MAX_DETECTIONS);
 }
@@ -321,15 +274,9 @@ extern "C" int rts_cube_detections_get(RtsHandle c, RtsDetection* out, uint32_t 
     CHECK_HANDLE(c);
     if (!n_out || (capacity && !out)) { rts_set_error("rts_cube_detections_get: null output"); return RTS_ERR_INVALID; }
     if (!c->cube.det_valid) { rts_set_error("rts_cube_detections_get: no detection list (rts_cube_detect, rts_cube_detect_os; a list ends at rts_cube_attach)"); return RTS_ERR_INVALID; }
-    RTS_HIP(hipStreamSynchronize(c->stream));
-    uint32_t total = 0;
-    RTS_HIP(hipMemcpy(&total, c->cube.d_det_off.p + c->cube.det_nseg, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    *n_out = total;
-    uint32_t n = total < c->cube.det_max ? total : c->cube.det_max;
-    if (n > capacity) n = capacity;
-    if (n) RTS_HIP(hipMemcpy(out, c->cube.d_det.p, sizeof(RtsDetection) * n, hipMemcpyDeviceToHost));
-    if (n < total) { rts_set_error("rts_cube_detections_get: %u of %u detections copied (max_detections %u, capacity %u)", n, total, c->cube.det_max, capacity); return RTS_ERR_CAPACITY; }
-    return RTS_OK;
+    uint32_t n = 0;
+    RTS_TRY(rts_list_copy_out(c, c->cube.d_det_off.p + c->cube.det_nseg, c->cube.det_max, c->cube.d_det.p, sizeof(RtsDetection), out, capacity, n_out, &n));
+    return rts_list_fits_check("rts_cube_detections_get", "%s: %u of %u detections copied (max_detections %u, capacity %u)", n, *n_out, c->cube.det_max, capacity);
 }
 
 // ------------------------------------------------------------------------------------- ordered-statistic CFAR
@@ -337,10 +284,10 @@ extern "C" int rts_cube_detections_get(RtsHandle c, RtsDetection* out, uint32_t 
 // fields it shares with RtsCfarParams are rts_cube_detect's, above)
 static int rts_cfar_os_check(const RtsCfarOsParams* p, uint32_t nb, uint32_t n_doppler, const char* who)
 {
-    { int rc = rts_cfar_window_check(who, p, nb, n_doppler); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_cfar_window_check(who, p, nb, n_doppler));
     const uint32_t N0 = rts_cfar_n0(p->guard_range, p->guard_doppler, p->train_range, p->train_doppler);
     if (p->rank == 0 || p->rank > N0) { rts_set_error("%s: rank = %u outside [1, N0 = %u] (the training cells of a full window)", who, p->rank, N0); return RTS_ERR_INVALID; }
-    { int rc = rts_cfar_level_check(who, p->pfa, p->alpha); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_cfar_level_check(who, p->pfa, p->alpha));
     return rts_cfar_pri_check(who, p->pri);
 }
 
@@ -356,18 +303,17 @@ extern "C" int rts_cfar_os_alpha(uint32_t n_train, uint32_t rank, double pfa, do
 
 extern "C" int rts_cfar_os_eval(const RtsCubeParams* q, const double* map, uint32_t n_doppler, const RtsCfarOsParams* p, RtsDetection* out, uint32_t capacity, uint32_t* n_out)
 {
-    if (!q || q->n_rx == 0 || q->n_bins == 0 || !(q->dt > 0) || !std::isfinite(q->dt) || !std::isfinite(q->t0)) { rts_set_error("rts_cfar_os_eval: bad cube parameters"); return RTS_ERR_INVALID; }
+    RTS_TRY(rts_eval_cube_check("rts_cfar_os_eval", q, false, true));
     if (!p) { rts_set_error("rts_cfar_os_eval: null parameters"); return RTS_ERR_INVALID; }
     if (n_doppler == 0) { rts_set_error("rts_cfar_os_eval: n_doppler = 0"); return RTS_ERR_INVALID; }
-    int rc = rts_cfar_os_check(p, q->n_bins, n_doppler, "rts_cfar_os_eval"); if (rc != RTS_OK) return rc;
+    RTS_TRY(rts_cfar_os_check(p, q->n_bins, n_doppler, "rts_cfar_os_eval"));
     if (!map || !n_out || (capacity && !out)) { rts_set_error("rts_cfar_os_eval: null map or output"); return RTS_ERR_INVALID; }
     const uint32_t N0 = rts_cfar_n0(p->guard_range, p->guard_doppler, p->train_range, p->train_doppler);
     std::vector<double> tab; std::vector<uint64_t> keys(N0);
     if (p->pfa != 0.0) { tab.assign((size_t)N0 + 1, 0.0); rts_cfar_os_alpha_table(p->guard_range, p->guard_doppler, p->train_range, p->train_doppler, p->rank, p->pfa, q->n_bins, tab.data()); }
     const uint32_t total = rts_cfar_os_eval_host(q, map, n_doppler, p, tab.empty() ? nullptr : tab.data(), keys.data(), out, capacity);
     *n_out = total;
-    if (total > capacity) { rts_set_error("rts_cfar_os_eval: %u of %u detections written (capacity %u)", capacity, total, capacity); return RTS_ERR_CAPACITY; }
-    return RTS_OK;
+    return rts_list_fits_check("rts_cfar_os_eval", "%s: %u of %u detections written (capacity %u)", rts_list_copied(total, total, capacity), total, capacity);
 }
 
 extern "C" int rts_cube_detect_os(RtsHandle c, const RtsCfarOsParams* p, const void* device_map, uint32_t n_doppler)
@@ -377,9 +323,9 @@ extern "C" int rts_cube_detect_os(RtsHandle c, const RtsCfarOsParams* p, const v
     CHECK_CLOSED(c);
     NEED_CUBE(c, "rts_cube_detect_os", "no cube (call rts_cube_attach first)");
     const double* map;
-    { int rc = rts_cfar_map(c, "rts_cube_detect_os", device_map, &map, &n_doppler); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_cfar_map(c, "rts_cube_detect_os", device_map, &map, &n_doppler));
     const uint32_t nb = c->cube.params.n_bins;
-    { int rc = rts_cfar_os_check(p, nb, n_doppler, "rts_cube_detect_os"); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_cfar_os_check(p, nb, n_doppler, "rts_cube_detect_os"));
     c->cube.det_valid = false; c->cube.plot_valid = false;      // (plots index the list they were made from)
     // the alphas by training count -> pinned staging -> the device, on the stream (N0 + 1 <= RTS_CFAR_OS_MAX_TRAIN + 1: one size for every call);
     // a call that needs nothing the device table of the previous one lacks sends nothing
@@ -426,8 +372,8 @@ static int rts_plot_check(const char* who, const RtsPlotParams* p)
 extern "C" int rts_plots_eval(const RtsCubeParams* q, const RtsDetection* list, uint32_t n_list, uint32_t n_doppler, const RtsPlotParams* p, RtsPlot* out, uint32_t capacity, uint32_t* n_out)
 {
     const char* who = "rts_plots_eval";
-    if (!q || q->n_rx == 0 || q->n_bins == 0 || !(q->dt > 0) || !std::isfinite(q->dt) || !std::isfinite(q->t0)) { rts_set_error("%s: bad cube parameters", who); return RTS_ERR_INVALID; }
-    { int rc = rts_plot_check(who, p); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_eval_cube_check(who, q, false, true));
+    RTS_TRY(rts_plot_check(who, p));
     if (n_doppler == 0) { rts_set_error("%s: n_doppler = 0", who); return RTS_ERR_INVALID; }
     if ((n_list && !list) || !n_out || (capacity && !out)) { rts_set_error("%s: null list or output", who); return RTS_ERR_INVALID; }
     if (n_list > RTS_PLOT_MAX_LIST) { rts_set_error("%s: n_list = %u > %u", who, n_list, RTS_PLOT_MAX_LIST); return RTS_ERR_INVALID; }
@@ -440,8 +386,7 @@ extern "C" int rts_plots_eval(const RtsCubeParams* q, const RtsDetection* list, 
     }
     const uint32_t total = rts_plots_eval_host(q, list, n_list, n_doppler, p, out, capacity);
     *n_out = total;
-    if (total > capacity) { rts_set_error("%s: %u of %u plots written (capacity %u)", who, capacity, total, capacity); return RTS_ERR_CAPACITY; }
-    return RTS_OK;
+    return rts_list_fits_check(who, "%s: %u of %u plots written (capacity %u)", rts_list_copied(total, total, capacity), total, capacity);
 }
 
 extern "C" int rts_cube_plots(RtsHandle c, const RtsPlotParams* p)
@@ -451,7 +396,7 @@ extern "C" int rts_cube_plots(RtsHandle c, const RtsPlotParams* p)
     if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
     CHECK_CLOSED(c);
     NEED_CUBE(c, who, "no cube (call rts_cube_attach first)");
-    { int rc = rts_plot_check(who, p); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_plot_check(who, p));
     RtsCubeState& s = c->cube;
     const RtsDetection* list = (const RtsDetection*)p->device_list;
     const uint32_t* n_dev = nullptr;
@@ -472,15 +417,11 @@ extern "C" int rts_cube_plots_get(RtsHandle c, RtsPlot* out, uint32_t capacity, 
     if (!n_out || (capacity && !out)) { rts_set_error("%s: null output", who); return RTS_ERR_INVALID; }
     RtsCubeState& s = c->cube;
     if (!s.plot_valid) { rts_set_error("%s: no plots (rts_cube_plots; plots end at rts_cube_detect, rts_cube_detect_os and rts_cube_attach)", who); return RTS_ERR_INVALID; }
-    RTS_HIP(hipStreamSynchronize(c->stream));
-    uint32_t total = 0, det_total = 0;
-    RTS_HIP(hipMemcpy(&total, s.d_plot_off.p + s.plot_cap, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    uint32_t total = 0, det_total = 0, n = 0;
+    RTS_TRY(rts_list_copy_out(c, s.d_plot_off.p + s.plot_cap, s.plot_max, s.d_plot.p, sizeof(RtsPlot), out, capacity, &total, &n));
     if (s.plot_own_list) RTS_HIP(hipMemcpy(&det_total, s.d_det_off.p + s.det_nseg, sizeof(uint32_t), hipMemcpyDeviceToHost));
     *n_out = total;
-    const uint32_t stored = total < s.plot_max ? total : s.plot_max;
-    const uint32_t n = stored < capacity ? stored : capacity;
-    if (n) RTS_HIP(hipMemcpy(out, s.d_plot.p, sizeof(RtsPlot) * n, hipMemcpyDeviceToHost));
-    if (n < total) { rts_set_error("%s: %u of %u plots copied (max_plots %u, capacity %u)", who, n, total, s.plot_max, capacity); return RTS_ERR_CAPACITY; }
+    RTS_TRY(rts_list_fits_check(who, "%s: %u of %u plots copied (max_plots %u, capacity %u)", n, total, s.plot_max, capacity));
     if (s.plot_own_list && det_total > s.det_max) {
         rts_set_error("%s: the detection list was truncated (%u of %u detections stored): the %u plots describe the stored prefix", who, s.det_max, det_total, total); return RTS_ERR_CAPACITY; }
     return RTS_OK;
@@ -524,19 +465,18 @@ extern "C" int rts_tracks_eval(const RtsTrackParams* p, const RtsTrack* in, uint
                                RtsTrack* out, uint32_t capacity, uint32_t* n_out, uint64_t* next_id_out)
 {
     const char* who = "rts_tracks_eval";
-    { int rc = rts_track_check(who, p); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_track_check(who, p));
     if ((n_in && !in) || (n_plots && !plots) || !n_out || !next_id_out || (capacity && !out)) { rts_set_error("%s: null tracks, plots or output", who); return RTS_ERR_INVALID; }
     if (n_in > rts_track_table_size(*p)) { rts_set_error("%s: n_in = %u tracks > max_tracks = %u", who, n_in, rts_track_table_size(*p)); return RTS_ERR_INVALID; }
     if (n_plots > RTS_TRACK_MAX_PLOTS) { rts_set_error("%s: n_plots = %u > %u (RTS_TRACK_MAX_PLOTS)", who, n_plots, RTS_TRACK_MAX_PLOTS); return RTS_ERR_INVALID; }
     if (n_in && !rts_track_interval_ok(T)) { rts_set_error("%s: T = %g with tracks (positive, finite)", who, T); return RTS_ERR_INVALID; }
-    { int rc = rts_track_table_refuse(who, in, n_in); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_track_table_refuse(who, in, n_in));
     uint32_t bad = 0;
     if (rts_track_plots_check(plots, n_plots, &bad)) { rts_set_error("%s: plots[%u].rx = %u is below plots[%u].rx = %u (rx must not decrease)", who, bad, plots[bad].rx, bad - 1u, plots[bad - 1u].rx); return RTS_ERR_INVALID; }
     const uint32_t total = rts_tracks_eval_host(p, in, n_in, next_id, T, plots, n_plots, out, capacity, next_id_out);
     *n_out = total;
-    const uint32_t table = rts_track_table_size(*p), stored = total < table ? total : table, n = stored < capacity ? stored : capacity;
-    if (n < total) { rts_set_error("%s: %u of %u tracks written (max_tracks %u, capacity %u)", who, n, total, table, capacity); return RTS_ERR_CAPACITY; }
-    return RTS_OK;
+    const uint32_t table = rts_track_table_size(*p);
+    return rts_list_fits_check(who, "%s: %u of %u tracks written (max_tracks %u, capacity %u)", rts_list_copied(total, table, capacity), total, table, capacity);
 }
 
 extern "C" int rts_cube_track(RtsHandle c, const RtsTrackParams* p, double time)
@@ -545,7 +485,7 @@ extern "C" int rts_cube_track(RtsHandle c, const RtsTrackParams* p, double time)
     CHECK_HANDLE(c);
     if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
     CHECK_CLOSED(c);
-    { int rc = rts_track_check(who, p); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_track_check(who, p));
     RtsCubeState& s = c->cube;
     const uint32_t table = rts_track_table_size(*p);
     if (s.trk_max && table != s.trk_max) { rts_set_error("%s: max_tracks = %u, the table was made with %u (rts_cube_tracks_reset first)", who, table, s.trk_max); return RTS_ERR_INVALID; }
@@ -561,7 +501,7 @@ extern "C" int rts_cube_track(RtsHandle c, const RtsTrackParams* p, double time)
         list = s.d_plot.p; n_dev = s.d_plot_off.p + s.plot_cap; pcap = s.plot_max;
         if (pcap > RTS_TRACK_MAX_PLOTS) { rts_set_error("%s: a plot list of %u records > %u (RTS_TRACK_MAX_PLOTS)", who, pcap, RTS_TRACK_MAX_PLOTS); return RTS_ERR_INVALID; }
     }
-    { int rc = rts_cube_track_device(c, *p, T, list, n_dev, pcap, table); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_cube_track_device(c, *p, T, list, n_dev, pcap, table));
     s.trk_max = table; s.trk_loaded = 0; s.trk_live = true; s.trk_time = time;
     return RTS_OK;
 }
@@ -572,7 +512,7 @@ extern "C" int rts_cube_tracks_get(RtsHandle c, RtsTrack* out, uint32_t capacity
     CHECK_HANDLE(c);
     if (!n_out || (capacity && !out)) { rts_set_error("%s: null output", who); return RTS_ERR_INVALID; }
     RtsCubeState& s = c->cube;
-    { int rc = rts_cube_track_tables(c); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_cube_track_tables(c));
     RTS_HIP(hipStreamSynchronize(c->stream));
     RtsTrackMeta m;
     RTS_HIP(hipMemcpy(&m, s.d_trk_meta.p + s.trk_cur, sizeof(m), hipMemcpyDeviceToHost));
@@ -580,8 +520,7 @@ extern "C" int rts_cube_tracks_get(RtsHandle c, RtsTrack* out, uint32_t capacity
     if (next_id_out) *next_id_out = m.next_id;
     const uint32_t n = m.n < capacity ? m.n : capacity;
     if (n) RTS_HIP(hipMemcpy(out, s.d_trk[s.trk_cur].p, sizeof(RtsTrack) * n, hipMemcpyDeviceToHost));
-    if (n < m.total) { rts_set_error("%s: %u of %u tracks copied (max_tracks %u, capacity %u)", who, n, m.total, s.trk_max, capacity); return RTS_ERR_CAPACITY; }
-    return RTS_OK;
+    return rts_list_fits_check(who, "%s: %u of %u tracks copied (max_tracks %u, capacity %u)", n, m.total, s.trk_max, capacity);
 }
 
 // the rounds the matching of the last rts_cube_track took (tools/track_bench.py); synchronises
@@ -590,7 +529,7 @@ extern "C" int rts_cube_track_rounds(RtsHandle c, uint32_t* rounds)
     CHECK_HANDLE(c);
     if (!rounds) { rts_set_error("rts_cube_track_rounds: null output"); return RTS_ERR_INVALID; }
     RtsCubeState& s = c->cube;
-    { int rc = rts_cube_track_tables(c); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_cube_track_tables(c));
     RTS_HIP(hipStreamSynchronize(c->stream));
     RtsTrackMeta m;
     RTS_HIP(hipMemcpy(&m, s.d_trk_meta.p + s.trk_cur, sizeof(m), hipMemcpyDeviceToHost));
@@ -601,7 +540,7 @@ extern "C" int rts_cube_track_rounds(RtsHandle c, uint32_t* rounds)
 static int rts_tracks_load(RtsContext* c, const RtsTrack* t, uint32_t n, const uint64_t* next_id)
 {
     RtsCubeState& s = c->cube;
-    { int rc = rts_cube_track_tables(c); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_cube_track_tables(c));
     RTS_HIP(hipStreamSynchronize(c->stream));                 // (an enqueued step may still read and write both tables)
     RtsTrackMeta m;
     RTS_HIP(hipMemcpy(&m, s.d_trk_meta.p + s.trk_cur, sizeof(m), hipMemcpyDeviceToHost));
@@ -621,8 +560,8 @@ extern "C" int rts_cube_tracks_set(RtsHandle c, const RtsTrack* tracks, uint32_t
     if (n && !tracks) { rts_set_error("%s: null tracks", who); return RTS_ERR_INVALID; }
     if (n > RTS_TRACK_MAX_TRACKS) { rts_set_error("%s: n = %u > %u (RTS_TRACK_MAX_TRACKS)", who, n, RTS_TRACK_MAX_TRACKS); return RTS_ERR_INVALID; }
     if (n && !rts_track_finite(time)) { rts_set_error("%s: time = %g (finite)", who, time); return RTS_ERR_INVALID; }
-    { int rc = rts_track_table_refuse(who, tracks, n); if (rc != RTS_OK) return rc; }
-    { int rc = rts_tracks_load(c, tracks, n, &next_id); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_track_table_refuse(who, tracks, n));
+    RTS_TRY(rts_tracks_load(c, tracks, n, &next_id));
     c->cube.trk_live = n != 0u; c->cube.trk_time = time;
     return RTS_OK;
 }
@@ -631,7 +570,7 @@ extern "C" int rts_cube_tracks_reset(RtsHandle c)
 {
     CHECK_HANDLE(c);
     CHECK_CLOSED(c);
-    { int rc = rts_tracks_load(c, nullptr, 0, nullptr); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_tracks_load(c, nullptr, 0, nullptr));
     c->cube.trk_live = false;
     return RTS_OK;
 }
@@ -672,9 +611,10 @@ static int rts_tbd_extract_refuse(const char* who, const RtsTbdExtractParams* e)
     return RTS_ERR_INVALID;
 }
 // the shape of a map: what an evaluator is given, or what a step finds
-static int rts_tbd_shape_check(const char* who, uint32_t n_rx, uint32_t nd, uint32_t nb, double dt, double t0)
+static int rts_tbd_shape_check(const char* who, const RtsCubeParams* q, uint32_t nd)
 {
-    if (n_rx == 0 || nb == 0 || !(dt > 0) || !std::isfinite(dt) || !std::isfinite(t0)) { rts_set_error("%s: bad cube parameters", who); return RTS_ERR_INVALID; }
+    RTS_TRY(rts_eval_cube_check(who, q, false, true));
+    const uint32_t n_rx = q->n_rx, nb = q->n_bins;
     if (nd == 0) { rts_set_error("%s: n_doppler = 0", who); return RTS_ERR_INVALID; }
     if ((uint64_t)n_rx * nd * nb > RTS_TBD_MAX_CELLS) { rts_set_error("%s: %u x %u x %u cells > %u (RTS_TBD_MAX_CELLS)", who, n_rx, nd, nb, RTS_TBD_MAX_CELLS); return RTS_ERR_INVALID; }
     return RTS_OK;
@@ -694,11 +634,10 @@ extern "C" int rts_tbd_step_eval(const RtsCubeParams* q, const double* map, uint
                                  double* merit_out, uint8_t* ptr_out, int32_t* shifts_out)
 {
     const char* who = "rts_tbd_step_eval";
-    if (!q) { rts_set_error("%s: bad cube parameters", who); return RTS_ERR_INVALID; }
-    { int rc = rts_tbd_shape_check(who, q->n_rx, n_doppler, q->n_bins, q->dt, q->t0); if (rc != RTS_OK) return rc; }
-    { int rc = rts_tbd_check(who, p, n_doppler, q->n_bins); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_tbd_shape_check(who, q, n_doppler));
+    RTS_TRY(rts_tbd_check(who, p, n_doppler, q->n_bins));
     if (!map || !merit_out || !ptr_out || !shifts_out || merit_out == merit_in) { rts_set_error("%s: null map or output (merit_out must not be merit_in)", who); return RTS_ERR_INVALID; }
-    if (merit_in) { int rc = rts_tbd_shifts_refuse(who, p, n_doppler, T, q->dt); if (rc != RTS_OK) return rc; }
+    if (merit_in) RTS_TRY(rts_tbd_shifts_refuse(who, p, n_doppler, T, q->dt));
     rts_tbd_step_host(p, q->n_rx, n_doppler, q->n_bins, q->dt, map, merit_in, T, merit_out, ptr_out, shifts_out);
     return RTS_OK;
 }
@@ -707,17 +646,14 @@ extern "C" int rts_tbd_extract_eval(const RtsCubeParams* q, uint32_t n_doppler, 
                                     uint32_t n_frames, const RtsTbdExtractParams* e, RtsTbdTrack* out, uint32_t* paths, uint32_t capacity, uint32_t* n_out)
 {
     const char* who = "rts_tbd_extract_eval";
-    if (!q) { rts_set_error("%s: bad cube parameters", who); return RTS_ERR_INVALID; }
-    { int rc = rts_tbd_shape_check(who, q->n_rx, n_doppler, q->n_bins, q->dt, q->t0); if (rc != RTS_OK) return rc; }
-    { int rc = rts_tbd_check(who, p, n_doppler, q->n_bins); if (rc != RTS_OK) return rc; }
-    { int rc = rts_tbd_extract_refuse(who, e); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_tbd_shape_check(who, q, n_doppler));
+    RTS_TRY(rts_tbd_check(who, p, n_doppler, q->n_bins));
+    RTS_TRY(rts_tbd_extract_refuse(who, e));
     if (n_frames == 0 || n_frames > p->depth) { rts_set_error("%s: n_frames = %u (1 .. depth = %u)", who, n_frames, p->depth); return RTS_ERR_INVALID; }
     if (!merit || !ptrs || !shifts || !n_out || (capacity && (!out || !paths))) { rts_set_error("%s: null merit, pointer maps, shift tables or output", who); return RTS_ERR_INVALID; }
     const uint32_t total = rts_tbd_extract_host(p, e, q->n_rx, n_doppler, q->n_bins, q->t0, q->dt, merit, ptrs, shifts, n_frames, out, paths, capacity);
     *n_out = total;
-    const uint32_t stored = total < rts_tbd_max_tracks(*e) ? total : rts_tbd_max_tracks(*e), n = stored < capacity ? stored : capacity;
-    if (n < total) { rts_set_error("%s: %u of %u tracks written (max_tracks %u, capacity %u)", who, n, total, rts_tbd_max_tracks(*e), capacity); return RTS_ERR_CAPACITY; }
-    return RTS_OK;
+    return rts_list_fits_check(who, "%s: %u of %u tracks written (max_tracks %u, capacity %u)", rts_list_copied(total, rts_tbd_max_tracks(*e), capacity), total, rts_tbd_max_tracks(*e), capacity);
 }
 
 extern "C" int rts_cube_tbd_step(RtsHandle c, const RtsTbdParams* p, double time, const void* device_map, uint32_t n_doppler)
@@ -728,11 +664,11 @@ extern "C" int rts_cube_tbd_step(RtsHandle c, const RtsTbdParams* p, double time
     CHECK_CLOSED(c);
     NEED_CUBE(c, who, "no cube (call rts_cube_attach first)");
     const double* map;
-    { int rc = rts_cfar_map(c, who, device_map, &map, &n_doppler); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_cfar_map(c, who, device_map, &map, &n_doppler));
     RtsCubeState& s = c->cube;
     const RtsCubeParams& q = s.params;
-    { int rc = rts_tbd_shape_check(who, q.n_rx, n_doppler, q.n_bins, q.dt, q.t0); if (rc != RTS_OK) return rc; }
-    { int rc = rts_tbd_check(who, p, n_doppler, q.n_bins); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_tbd_shape_check(who, &q, n_doppler));
+    RTS_TRY(rts_tbd_check(who, p, n_doppler, q.n_bins));
     if (!rts_tbd_finite(time)) { rts_set_error("%s: time = %g (finite)", who, time); return RTS_ERR_INVALID; }
     const bool first = s.tbd_frames == 0;
     double T = 0.0;
@@ -743,7 +679,7 @@ extern "C" int rts_cube_tbd_step(RtsHandle c, const RtsTbdParams* p, double time
             rts_set_error("%s: depth, half_doppler, half_range = %u, %u, %u, the state was made with %u, %u, %u (rts_cube_tbd_reset first)", who, p->depth, p->half_doppler, p->half_range,
                           s.tbd_depth, s.tbd_hd, s.tbd_hr); return RTS_ERR_INVALID; }
         T = time - s.tbd_time;
-        { int rc = rts_tbd_shifts_refuse(who, p, n_doppler, T, q.dt); if (rc != RTS_OK) return rc; }
+        RTS_TRY(rts_tbd_shifts_refuse(who, p, n_doppler, T, q.dt));
     } else {
         // the state's buffers, of their final sizes (a DevBuf that grows drops what it held: they are made once per state)
         const size_t cells = (size_t)q.n_rx * n_doppler * q.n_bins;
@@ -751,7 +687,7 @@ extern "C" int rts_cube_tbd_step(RtsHandle c, const RtsTbdParams* p, double time
         RTS_HIP(s.d_tbd_ptr.reserve(cells * p->depth)); RTS_HIP(s.d_tbd_shift.reserve((size_t)n_doppler * p->depth));
         s.tbd_rx = q.n_rx; s.tbd_nd = n_doppler; s.tbd_nb = q.n_bins; s.tbd_depth = p->depth; s.tbd_hd = p->half_doppler; s.tbd_hr = p->half_range; s.tbd_cur = 0;
     }
-    { int rc = rts_cube_tbd_step_device(c, *p, map, first, T, q.dt, (uint32_t)(s.tbd_frames % s.tbd_depth)); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_cube_tbd_step_device(c, *p, map, first, T, q.dt, (uint32_t)(s.tbd_frames % s.tbd_depth)));
     s.tbd_frames++; s.tbd_time = time; s.tbd_t0 = q.t0; s.tbd_dt = q.dt;
     return RTS_OK;
 }
@@ -762,23 +698,19 @@ extern "C" int rts_cube_tbd_extract(RtsHandle c, const RtsTbdExtractParams* e)
 {
     const char* who = "rts_cube_tbd_extract";
     CHECK_HANDLE(c);
-    { int rc = rts_tbd_extract_refuse(who, e); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_tbd_extract_refuse(who, e));
     CHECK_CLOSED(c);
     NEED_TBD(c, who);
     c->cube.tbd_ext_valid = false;
     return rts_cube_tbd_extract_device(c, *e, rts_tbd_max_tracks(*e));
 }
 
-// total, and how many of the stored records fit `capacity`; synchronises
-static int rts_tbd_extracted(RtsContext* c, const char* who, uint32_t capacity, uint32_t* total, uint32_t* n)
+// the extraction's records or their paths (record_bytes each) -> the host: the total, and how many of the stored ones fit `capacity`
+static int rts_tbd_extracted(RtsContext* c, const char* who, const void* d_list, size_t record_bytes, void* out, uint32_t capacity, uint32_t* total, uint32_t* n)
 {
     RtsCubeState& s = c->cube;
     if (!s.tbd_ext_valid) { rts_set_error("%s: no extraction (rts_cube_tbd_extract; it ends at rts_cube_tbd_reset)", who); return RTS_ERR_INVALID; }
-    RTS_HIP(hipStreamSynchronize(c->stream));
-    RTS_HIP(hipMemcpy(total, s.d_tbd_off.p + s.tbd_ext_nseg, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    const uint32_t stored = *total < s.tbd_ext_max ? *total : s.tbd_ext_max;
-    *n = stored < capacity ? stored : capacity;
-    return RTS_OK;
+    return rts_list_copy_out(c, s.d_tbd_off.p + s.tbd_ext_nseg, s.tbd_ext_max, d_list, record_bytes, out, capacity, total, n);
 }
 
 extern "C" int rts_cube_tbd_tracks_get(RtsHandle c, RtsTbdTrack* out, uint32_t capacity, uint32_t* n_out)
@@ -787,11 +719,9 @@ extern "C" int rts_cube_tbd_tracks_get(RtsHandle c, RtsTbdTrack* out, uint32_t c
     CHECK_HANDLE(c);
     if (!n_out || (capacity && !out)) { rts_set_error("%s: null output", who); return RTS_ERR_INVALID; }
     uint32_t total = 0, n = 0;
-    { int rc = rts_tbd_extracted(c, who, capacity, &total, &n); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_tbd_extracted(c, who, c->cube.d_tbd_out.p, sizeof(RtsTbdTrack), out, capacity, &total, &n));
     *n_out = total;
-    if (n) RTS_HIP(hipMemcpy(out, c->cube.d_tbd_out.p, sizeof(RtsTbdTrack) * n, hipMemcpyDeviceToHost));
-    if (n < total) { rts_set_error("%s: %u of %u tracks copied (max_tracks %u, capacity %u)", who, n, total, c->cube.tbd_ext_max, capacity); return RTS_ERR_CAPACITY; }
-    return RTS_OK;
+    return rts_list_fits_check(who, "%s: %u of %u tracks copied (max_tracks %u, capacity %u)", n, total, c->cube.tbd_ext_max, capacity);
 }
 
 extern "C" int rts_cube_tbd_paths_get(RtsHandle c, uint32_t* out, uint32_t capacity_tracks)
@@ -800,10 +730,8 @@ extern "C" int rts_cube_tbd_paths_get(RtsHandle c, uint32_t* out, uint32_t capac
     CHECK_HANDLE(c);
     if (capacity_tracks && !out) { rts_set_error("%s: null output", who); return RTS_ERR_INVALID; }
     uint32_t total = 0, n = 0;
-    { int rc = rts_tbd_extracted(c, who, capacity_tracks, &total, &n); if (rc != RTS_OK) return rc; }
-    if (n) RTS_HIP(hipMemcpy(out, c->cube.d_tbd_paths.p, sizeof(uint32_t) * 2u * c->cube.tbd_ext_depth * n, hipMemcpyDeviceToHost));
-    if (n < total) { rts_set_error("%s: the paths of %u of %u tracks copied (max_tracks %u, capacity %u)", who, n, total, c->cube.tbd_ext_max, capacity_tracks); return RTS_ERR_CAPACITY; }
-    return RTS_OK;
+    RTS_TRY(rts_tbd_extracted(c, who, c->cube.d_tbd_paths.p, sizeof(uint32_t) * 2u * c->cube.tbd_ext_depth, out, capacity_tracks, &total, &n));
+    return rts_list_fits_check(who, "%s: the paths of %u of %u tracks copied (max_tracks %u, capacity %u)", n, total, c->cube.tbd_ext_max, capacity_tracks);
 }
 
 extern "C" int rts_cube_tbd_merit_get(RtsHandle c, double* host_out, uint64_t capacity_doubles)
@@ -866,13 +794,13 @@ static int rts_stft_check(const RtsStftParams* p, const RtsCubeParams& q, const 
     if (p->reserved[0] || p->reserved[1]) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
     if (p->flags & ~(RTS_STFT_POWER | RTS_STFT_SUM_BINS)) { rts_set_error("%s: unknown flags 0x%x", who, p->flags); return RTS_ERR_INVALID; }
     if ((p->flags & RTS_STFT_SUM_BINS) && !(p->flags & RTS_STFT_POWER)) { rts_set_error("%s: flags: RTS_STFT_SUM_BINS needs RTS_STFT_POWER", who); return RTS_ERR_INVALID; }
-    if (p->n_fft < 2u || p->n_fft > RTS_STFT_MAX_FFT || (p->n_fft & (p->n_fft - 1u)) != 0u) { rts_set_error("%s: n_fft = %u must be a power of two in [2, %u]", who, p->n_fft, RTS_STFT_MAX_FFT); return RTS_ERR_INVALID; }
-    { int rc = rts_pulses_check(who, p->first_pulse, p->n_pulses, q.n_pulses, true); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_fft_size_check(who, p->n_fft, RTS_STFT_MAX_FFT));
+    RTS_TRY(rts_pulses_check(who, p->first_pulse, p->n_pulses, q.n_pulses, true));
     if (p->window_len == 0 || p->window_len > p->n_fft || p->window_len > p->n_pulses) { rts_set_error("%s: window_len = %u (1 .. n_fft = %u, <= n_pulses = %u)", who, p->window_len, p->n_fft, p->n_pulses); return RTS_ERR_INVALID; }
     if (p->hop == 0) { rts_set_error("%s: hop = 0 (>= 1)", who); return RTS_ERR_INVALID; }
-    if (p->first_bin >= q.n_bins || p->n_bins > q.n_bins - p->first_bin) { rts_set_error("%s: first_bin = %u, n_bins = %u: inside the cube's %u bins", who, p->first_bin, p->n_bins, q.n_bins); return RTS_ERR_INVALID; }
-    if (p->window) for (uint32_t i = 0; i < p->window_len; i++) if (!std::isfinite(p->window[i])) { rts_set_error("%s: window[%u] is not finite", who, i); return RTS_ERR_INVALID; }
-    const uint32_t n_gate = p->n_bins ? p->n_bins : q.n_bins - p->first_bin;
+    uint32_t n_gate = 0;
+    RTS_TRY(rts_gate_check(who, "%s: first_bin = %u, n_bins = %u: inside the cube's %u bins", p->first_bin, p->n_bins, q.n_bins, &n_gate));
+    RTS_TRY(rts_window_finite_check(who, p->window, p->window_len));
     *plan = rts_stft_plan(q.n_rx, p->n_pulses, p->window_len, p->hop, p->n_fft, n_gate, p->flags);
     if (!plan->supported) {
         if (q.n_rx > RTS_STFT_MAX_RX) rts_set_error("%s: n_rx = %u receivers: more than %u (the launch grid)", who, q.n_rx, RTS_STFT_MAX_RX);
@@ -893,9 +821,9 @@ extern "C" int rts_window_make(uint32_t kind, uint32_t n, double* out)
 
 extern "C" int rts_stft_eval(const RtsCubeParams* q, const double* cube, const RtsStftParams* p, double* out, uint32_t* n_frames_out)
 {
-    if (!q || q->n_rx == 0 || q->n_pulses == 0 || q->n_bins == 0) { rts_set_error("rts_stft_eval: bad cube parameters"); return RTS_ERR_INVALID; }
+    RTS_TRY(rts_eval_cube_check("rts_stft_eval", q, true, false));
     RtsStftPlan plan;
-    int rc = rts_stft_check(p, *q, "rts_stft_eval", &plan); if (rc != RTS_OK) return rc;
+    RTS_TRY(rts_stft_check(p, *q, "rts_stft_eval", &plan));
     if (!cube || !out) { rts_set_error("rts_stft_eval: null cube or output array"); return RTS_ERR_INVALID; }
     std::vector<double> work(4 * (size_t)p->n_fft);
     rts_stft_eval_host(q, cube, p, plan, out, work.data());
@@ -909,17 +837,14 @@ extern "C" int rts_cube_spectrogram(RtsHandle c, const RtsStftParams* p, void* d
     NEED_CUBE(c, "rts_cube_spectrogram", "no cube (call rts_cube_attach first)");
     const RtsCubeParams& q = c->cube.params;
     RtsStftPlan plan;
-    int rc = rts_stft_check(p, q, "rts_cube_spectrogram", &plan); if (rc != RTS_OK) return rc;
+    RTS_TRY(rts_stft_check(p, q, "rts_cube_spectrogram", &plan));
     if ((uintptr_t)device_out & 15u) { rts_set_error("rts_cube_spectrogram: device_out is not 16-byte aligned"); return RTS_ERR_INVALID; }
     CHECK_CLOSED(c);
     double* out; RTS_HIP(c->cube.stft.place(device_out, plan.out_doubles, &out));
     // the window -> pinned staging -> the device, on the stream (window_len <= RTS_STFT_MAX_FFT: one size for every call)
     const double* win = nullptr;
     if (p->window) {
-        double* w = nullptr;
-        RTS_HIP(c->cube.stft_win.begin(RTS_STFT_MAX_FFT, RTS_STFT_MAX_FFT, RTS_STFT_MAX_FFT, &w));
-        memcpy(w, p->window, sizeof(double) * p->window_len);
-        RTS_HIP(c->cube.stft_win.send(p->window_len, c->stream));
+        RTS_HIP(c->cube.stft_win.upload(p->window, p->window_len, RTS_STFT_MAX_FFT, c->stream));
         win = c->cube.stft_win.dev.p;
     }
     if (!device_out) c->cube.stft.record(out, plan.out_doubles);
@@ -930,16 +855,14 @@ extern "C" int rts_cube_spectrogram(RtsHandle c, const RtsStftParams* p, void* d
 extern "C" int rts_cube_spectrogram_get(RtsHandle c, double* host_out, uint64_t capacity_doubles)
 {
     CHECK_HANDLE(c);
-    return rts_cube_copy_out(c, "rts_cube_spectrogram_get", "no library-owned spectrogram (rts_cube_spectrogram with device_out NULL; a spectrogram ends at rts_cube_attach) / null output", c->cube.stft.valid, c->cube.stft.p, c->cube.stft.doubles, host_out, capacity_doubles);
+    return rts_cube_copy_out(c, "rts_cube_spectrogram_get", "no library-owned spectrogram (rts_cube_spectrogram with device_out NULL; a spectrogram ends at rts_cube_attach) / null output", c->cube.stft, host_out, capacity_doubles);
 }
 
 // ------------------------------------------------------------------------------------- autofocus: range alignment, phase-gradient autofocus, correction
 // (rts_amd.h: RtsAlignParams, RtsPgaParams, RtsCorrectParams; the arithmetic and the launch plans are rts_focus.h, shared by the host exports and the kernels, rts_focus.hip)
 static int rts_focus_gate_check(const char* who, uint32_t first_bin, uint32_t n_gate, uint32_t n_bins, uint32_t* gate)
 {
-    if (first_bin >= n_bins || n_gate > n_bins - first_bin) { rts_set_error("%s: first_bin = %u, n_gate = %u: inside the cube's %u bins", who, first_bin, n_gate, n_bins); return RTS_ERR_INVALID; }
-    *gate = n_gate ? n_gate : n_bins - first_bin;
-    return RTS_OK;
+    return rts_gate_check(who, "%s: first_bin = %u, n_gate = %u: inside the cube's %u bins", first_bin, n_gate, n_bins, gate);
 }
 static int rts_focus_rx_check(const char* who, uint32_t n_rx)
 {
@@ -952,12 +875,12 @@ static int rts_align_check(const RtsAlignParams* p, const RtsCubeParams& q, cons
     if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
     if (p->reserved0 || p->reserved[0] || p->reserved[1]) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
     if (p->flags & ~RTS_ALIGN_INTEGER) { rts_set_error("%s: unknown flags 0x%x", who, p->flags); return RTS_ERR_INVALID; }
-    { int rc = rts_pulses_check(who, p->first_pulse, p->n_pulses, q.n_pulses, true); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_pulses_check(who, p->first_pulse, p->n_pulses, q.n_pulses, true));
     uint32_t gate = 0;
-    { int rc = rts_focus_gate_check(who, p->first_bin, p->n_gate, q.n_bins, &gate); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_focus_gate_check(who, p->first_bin, p->n_gate, q.n_bins, &gate));
     if (p->max_lag > RTS_ALIGN_MAX_LAG) { rts_set_error("%s: max_lag = %u (0 .. %u)", who, p->max_lag, RTS_ALIGN_MAX_LAG); return RTS_ERR_INVALID; }
     if (p->n_iters == 0 || p->n_iters > RTS_ALIGN_MAX_ITERS) { rts_set_error("%s: n_iters = %u (1 .. %u)", who, p->n_iters, RTS_ALIGN_MAX_ITERS); return RTS_ERR_INVALID; }
-    { int rc = rts_focus_rx_check(who, q.n_rx); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_focus_rx_check(who, q.n_rx));
     *plan = rts_align_plan(q.n_rx, p->n_pulses, q.n_bins, gate, p->max_lag);
     if (!plan->supported) { rts_set_error("%s: n_pulses = %u rows: more than %u (the launch grid)", who, p->n_pulses, RTS_FOCUS_MAX_GRID_X); return RTS_ERR_INVALID; }
     return RTS_OK;
@@ -967,13 +890,13 @@ static int rts_pga_check(const RtsPgaParams* p, const RtsCubeParams& q, const ch
 {
     if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
     if (p->reserved0 || p->reserved[0] || p->reserved[1]) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
-    if (p->n_pulses < 4u || p->n_pulses > RTS_PGA_MAX_PULSES || (p->n_pulses & (p->n_pulses - 1u)) != 0u) {
+    if (!rts_pow2_in(p->n_pulses, 4u, RTS_PGA_MAX_PULSES)) {
         rts_set_error("%s: n_pulses = %u must be a power of two in [4, %u] (the radix-2 transform; no zero padding of a phase history)", who, p->n_pulses, RTS_PGA_MAX_PULSES); return RTS_ERR_INVALID; }
-    { int rc = rts_pulses_check(who, p->first_pulse, p->n_pulses, q.n_pulses, true); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_pulses_check(who, p->first_pulse, p->n_pulses, q.n_pulses, true));
     uint32_t gate = 0;
-    { int rc = rts_focus_gate_check(who, p->first_bin, p->n_gate, q.n_bins, &gate); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_focus_gate_check(who, p->first_bin, p->n_gate, q.n_bins, &gate));
     if (p->n_iters == 0 || p->n_iters > RTS_PGA_MAX_ITERS) { rts_set_error("%s: n_iters = %u (1 .. %u)", who, p->n_iters, RTS_PGA_MAX_ITERS); return RTS_ERR_INVALID; }
-    { int rc = rts_focus_rx_check(who, q.n_rx); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_focus_rx_check(who, q.n_rx));
     *plan = rts_pga_plan(q.n_rx, p->n_pulses, gate, p->n_iters, p->window0, p->window_min);
     if (!plan->supported) { rts_set_error("%s: n_pulses = %u: the columns do not fit the workgroup's memory", who, p->n_pulses); return RTS_ERR_INVALID; }
     return RTS_OK;
@@ -986,13 +909,13 @@ static int rts_correct_check(const RtsCorrectParams* p, const RtsCubeParams& q, 
     if (p->reserved[0] || p->reserved[1]) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
     if (p->flags & ~(RTS_CORRECT_USE_ALIGN | RTS_CORRECT_USE_PGA)) { rts_set_error("%s: unknown flags 0x%x", who, p->flags); return RTS_ERR_INVALID; }
     if (p->flags && !handle) { rts_set_error("%s: flags = 0x%x: the evaluator has no tables (pass shifts / phase)", who, p->flags); return RTS_ERR_INVALID; }
-    { int rc = rts_pulses_check(who, p->first_pulse, p->n_pulses, q.n_pulses, true); if (rc != RTS_OK) return rc; }
-    { int rc = rts_taps_check(who, p->taps); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_pulses_check(who, p->first_pulse, p->n_pulses, q.n_pulses, true));
+    RTS_TRY(rts_taps_check(who, p->taps));
     const bool use_s = (p->flags & RTS_CORRECT_USE_ALIGN) != 0, use_p = (p->flags & RTS_CORRECT_USE_PGA) != 0;
     if (use_s && p->shifts) { rts_set_error("%s: shifts together with RTS_CORRECT_USE_ALIGN", who); return RTS_ERR_INVALID; }
     if (use_p && p->phase) { rts_set_error("%s: phase together with RTS_CORRECT_USE_PGA", who); return RTS_ERR_INVALID; }
     if (!use_s && !use_p && !p->shifts && !p->phase) { rts_set_error("%s: neither shifts nor phase (arrays or flags)", who); return RTS_ERR_INVALID; }
-    { int rc = rts_focus_rx_check(who, q.n_rx); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_focus_rx_check(who, q.n_rx));
     const size_t n = (size_t)q.n_rx * p->n_pulses;
     if (p->shifts) for (size_t i = 0; i < n; i++) if (!std::isfinite(p->shifts[i])) { rts_set_error("%s: shifts[%zu] is not finite", who, i); return RTS_ERR_INVALID; }
     if (p->phase) for (size_t i = 0; i < n; i++) if (!std::isfinite(p->phase[i])) { rts_set_error("%s: phase[%zu] is not finite", who, i); return RTS_ERR_INVALID; }
@@ -1001,17 +924,11 @@ static int rts_correct_check(const RtsCorrectParams* p, const RtsCubeParams& q, 
     return RTS_OK;
 }
 
-static int rts_eval_cube_check(const char* who, const RtsCubeParams* q)
-{
-    if (!q || q->n_rx == 0 || q->n_pulses == 0 || q->n_bins == 0) { rts_set_error("%s: bad cube parameters", who); return RTS_ERR_INVALID; }
-    return RTS_OK;
-}
-
 extern "C" int rts_align_eval(const RtsCubeParams* q, const double* cube, const RtsAlignParams* p, double* out)
 {
-    { int rc = rts_eval_cube_check("rts_align_eval", q); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_eval_cube_check("rts_align_eval", q, true, false));
     RtsAlignPlan plan;
-    int rc = rts_align_check(p, *q, "rts_align_eval", &plan); if (rc != RTS_OK) return rc;
+    RTS_TRY(rts_align_check(p, *q, "rts_align_eval", &plan));
     if (!cube || !out) { rts_set_error("rts_align_eval: null cube or output array"); return RTS_ERR_INVALID; }
     std::vector<double> work((size_t)p->n_pulses * q->n_bins + plan.n_gate + plan.n_lags);
     rts_align_eval_host(q, cube, p, plan, out, work.data());
@@ -1020,9 +937,9 @@ extern "C" int rts_align_eval(const RtsCubeParams* q, const double* cube, const 
 
 extern "C" int rts_pga_eval(const RtsCubeParams* q, const double* cube, const RtsPgaParams* p, double* phase_out, double* rms_out)
 {
-    { int rc = rts_eval_cube_check("rts_pga_eval", q); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_eval_cube_check("rts_pga_eval", q, true, false));
     RtsPgaPlan plan;
-    int rc = rts_pga_check(p, *q, "rts_pga_eval", &plan); if (rc != RTS_OK) return rc;
+    RTS_TRY(rts_pga_check(p, *q, "rts_pga_eval", &plan));
     if (!cube || !phase_out || !rms_out) { rts_set_error("rts_pga_eval: null cube or output array"); return RTS_ERR_INVALID; }
     std::vector<double> work(14 * (size_t)p->n_pulses);
     rts_pga_eval_host(q, cube, p, plan, phase_out, rms_out, work.data());
@@ -1031,9 +948,9 @@ extern "C" int rts_pga_eval(const RtsCubeParams* q, const double* cube, const Rt
 
 extern "C" int rts_correct_eval(const RtsCubeParams* q, double* cube, const RtsCorrectParams* p)
 {
-    { int rc = rts_eval_cube_check("rts_correct_eval", q); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_eval_cube_check("rts_correct_eval", q, true, false));
     RtsCorrectPlan plan;
-    int rc = rts_correct_check(p, *q, "rts_correct_eval", false, &plan); if (rc != RTS_OK) return rc;
+    RTS_TRY(rts_correct_check(p, *q, "rts_correct_eval", false, &plan));
     if (!cube) { rts_set_error("rts_correct_eval: null cube"); return RTS_ERR_INVALID; }
     std::vector<double> work(2 * (size_t)q->n_bins);
     rts_correct_eval_host(q, cube, p, p->shifts, p->phase, work.data());
@@ -1046,7 +963,7 @@ extern "C" int rts_cube_align(RtsHandle c, const RtsAlignParams* p, void* device
     CHECK_HANDLE(c);
     NEED_CUBE(c, who, "no cube (call rts_cube_attach first)");
     RtsAlignPlan plan;
-    int rc = rts_align_check(p, c->cube.params, who, &plan); if (rc != RTS_OK) return rc;
+    RTS_TRY(rts_align_check(p, c->cube.params, who, &plan));
     if ((uintptr_t)device_out & 7u) { rts_set_error("%s: device_out is not 8-byte aligned", who); return RTS_ERR_INVALID; }
     CHECK_CLOSED(c);
     double* out; RTS_HIP(c->cube.align.place(device_out, plan.out_doubles, &out));
@@ -1057,7 +974,7 @@ extern "C" int rts_cube_align(RtsHandle c, const RtsAlignParams* p, void* device
 extern "C" int rts_cube_align_get(RtsHandle c, double* host_out, uint64_t capacity_doubles)
 {
     CHECK_HANDLE(c);
-    return rts_cube_copy_out(c, "rts_cube_align_get", "no library-owned shift table (rts_cube_align with device_out NULL; a table ends at rts_cube_attach) / null output", c->cube.align.valid, c->cube.align.p, c->cube.align.doubles, host_out, capacity_doubles);
+    return rts_cube_copy_out(c, "rts_cube_align_get", "no library-owned shift table (rts_cube_align with device_out NULL; a table ends at rts_cube_attach) / null output", c->cube.align, host_out, capacity_doubles);
 }
 
 extern "C" int rts_cube_pga(RtsHandle c, const RtsPgaParams* p, void* device_out)
@@ -1066,7 +983,7 @@ extern "C" int rts_cube_pga(RtsHandle c, const RtsPgaParams* p, void* device_out
     CHECK_HANDLE(c);
     NEED_CUBE(c, who, "no cube (call rts_cube_attach first)");
     RtsPgaPlan plan;
-    int rc = rts_pga_check(p, c->cube.params, who, &plan); if (rc != RTS_OK) return rc;
+    RTS_TRY(rts_pga_check(p, c->cube.params, who, &plan));
     if ((uintptr_t)device_out & 7u) { rts_set_error("%s: device_out is not 8-byte aligned", who); return RTS_ERR_INVALID; }
     CHECK_CLOSED(c);
     double* out; RTS_HIP(c->cube.pga.place(device_out, plan.out_doubles, &out));
@@ -1096,7 +1013,7 @@ extern "C" int rts_cube_correct(RtsHandle c, const RtsCorrectParams* p)
     NEED_CUBE(c, who, "no cube (call rts_cube_attach first)");
     RtsCubeState& s = c->cube;
     RtsCorrectPlan plan;
-    int rc = rts_correct_check(p, s.params, who, true, &plan); if (rc != RTS_OK) return rc;
+    RTS_TRY(rts_correct_check(p, s.params, who, true, &plan));
     const double* shifts = nullptr; const double* phase = nullptr;
     if (p->flags & RTS_CORRECT_USE_ALIGN) {
         if (!s.align.valid || s.align_first != p->first_pulse || s.align_P != p->n_pulses) { rts_set_error("%s: RTS_CORRECT_USE_ALIGN: no library-owned shift table of rows %u .. %u + %u (rts_cube_align with device_out NULL)", who, p->first_pulse, p->first_pulse, p->n_pulses); return RTS_ERR_INVALID; }
@@ -1129,7 +1046,7 @@ static int rts_beat_check(const RtsBeatParams* p, const RtsCubeParams& q, uint32
     if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
     if (!std::isfinite(p->slope) || p->slope == 0.0) { rts_set_error("%s: slope = %g (finite, != 0)", who, p->slope); return RTS_ERR_INVALID; }
     if (!std::isfinite(p->duration) || !(p->duration > 0.0)) { rts_set_error("%s: duration = %g (finite, > 0)", who, p->duration); return RTS_ERR_INVALID; }
-    { int rc = rts_render_source_check(who, p->source, p->flags); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_render_source_check(who, p->source, p->flags));
     if (p->reserved[0] || p->reserved[1]) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
     if (pulse_index >= q.n_pulses) { rts_set_error("%s: pulse_index = %u >= the cube's %u rows", who, pulse_index, q.n_pulses); return RTS_ERR_INVALID; }
     if (q.n_rx > RTS_BEAT_MAX_RX) { rts_set_error("%s: n_rx = %u receivers: more than %u (the launch grid)", who, q.n_rx, RTS_BEAT_MAX_RX); return RTS_ERR_INVALID; }
@@ -1138,8 +1055,8 @@ static int rts_beat_check(const RtsBeatParams* p, const RtsCubeParams& q, uint32
 
 extern "C" int rts_beat_eval(const RtsCubeParams* q, const RtsBeatParams* p, const RtsBeatContribution* c, uint32_t n, uint32_t pulse_index, double* cube)
 {
-    if (!q || q->n_rx == 0 || q->n_pulses == 0 || q->n_bins == 0 || !(q->dt > 0) || !std::isfinite(q->dt) || !std::isfinite(q->t0)) { rts_set_error("rts_beat_eval: bad cube parameters"); return RTS_ERR_INVALID; }
-    int rc = rts_beat_check(p, *q, pulse_index, "rts_beat_eval"); if (rc != RTS_OK) return rc;
+    RTS_TRY(rts_eval_cube_check("rts_beat_eval", q, true, true));
+    RTS_TRY(rts_beat_check(p, *q, pulse_index, "rts_beat_eval"));
     if ((n && !c) || !cube) { rts_set_error("rts_beat_eval: null contribution array or cube"); return RTS_ERR_INVALID; }
     std::vector<double> work(2 * (size_t)q->n_rx * q->n_bins);
     rts_beat_eval_host(q, p, c, n, pulse_index, cube, work.data());
@@ -1150,12 +1067,12 @@ extern "C" int rts_cube_render_beat(RtsHandle c, uint32_t pulse_index, const Rts
 {
     CHECK_HANDLE(c);
     NEED_CUBE(c, "rts_cube_render_beat", "call rts_cube_attach first");
-    { int rc = rts_beat_check(p, c->cube.params, pulse_index, "rts_cube_render_beat"); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_beat_check(p, c->cube.params, pulse_index, "rts_cube_render_beat"));
     const bool paths = p->source == RTS_RENDER_PATHS;
     if (!paths && (!std::isfinite(cspeed) || !(cspeed > 0.0))) { rts_set_error("rts_cube_render_beat: cspeed = %g (finite, > 0, with RTS_RENDER_RAYS)", cspeed); return RTS_ERR_INVALID; }
     if (!paths && (!std::isfinite(carrier) || carrier < 0.0)) { rts_set_error("rts_cube_render_beat: carrier = %g (finite, >= 0, with RTS_RENDER_RAYS)", carrier); return RTS_ERR_INVALID; }
     CHECK_CLOSED(c);
-    if (paths) { int rc = rts_render_paths_check(c, "rts_cube_render_beat"); if (rc != RTS_OK) return rc; }
+    if (paths) RTS_TRY(rts_render_paths_check(c, "rts_cube_render_beat"));
     const RtsBeatPlan plan = rts_beat_plan(c->res.n_recv, c->cube.params.n_rx, c->cube.params.n_bins, c->tune.beat_force_parts);
     if (!plan.supported) { rts_set_error("rts_cube_render_beat: %llu received rays: more than the launch takes", (unsigned long long)c->res.n_recv); return RTS_ERR_INVALID; }
     return rts_cube_beat_device(c, pulse_index, *p, plan, cspeed, carrier, c->res.agg_base_local);
@@ -1166,13 +1083,13 @@ static int rts_range_check(const RtsRangeParams* p, const RtsCubeParams& q, cons
     if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
     if (p->reserved0 || p->reserved[0] || p->reserved[1]) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
     if (p->flags & ~RTS_RANGE_REVERSE) { rts_set_error("%s: unknown flags 0x%x", who, p->flags); return RTS_ERR_INVALID; }
-    if (p->n_fft < 2u || p->n_fft > RTS_RANGE_MAX_FFT || (p->n_fft & (p->n_fft - 1u)) != 0u) { rts_set_error("%s: n_fft = %u must be a power of two in [2, %u]", who, p->n_fft, RTS_RANGE_MAX_FFT); return RTS_ERR_INVALID; }
-    { int rc = rts_pulses_check(who, p->first_pulse, p->n_pulses, q.n_pulses, true); if (rc != RTS_OK) return rc; }
-    if (p->first_bin >= q.n_bins || p->n_samples > q.n_bins - p->first_bin) { rts_set_error("%s: first_bin = %u, n_samples = %u: inside the row's %u bins", who, p->first_bin, p->n_samples, q.n_bins); return RTS_ERR_INVALID; }
-    const uint32_t n_samples = p->n_samples ? p->n_samples : q.n_bins - p->first_bin;
+    RTS_TRY(rts_fft_size_check(who, p->n_fft, RTS_RANGE_MAX_FFT));
+    RTS_TRY(rts_pulses_check(who, p->first_pulse, p->n_pulses, q.n_pulses, true));
+    uint32_t n_samples = 0;
+    RTS_TRY(rts_gate_check(who, "%s: first_bin = %u, n_samples = %u: inside the row's %u bins", p->first_bin, p->n_samples, q.n_bins, &n_samples));
     if (n_samples > p->n_fft) { rts_set_error("%s: n_samples = %u > n_fft = %u", who, n_samples, p->n_fft); return RTS_ERR_INVALID; }
     if (p->n_out > p->n_fft) { rts_set_error("%s: n_out = %u > n_fft = %u", who, p->n_out, p->n_fft); return RTS_ERR_INVALID; }
-    if (p->window) for (uint32_t i = 0; i < n_samples; i++) if (!std::isfinite(p->window[i])) { rts_set_error("%s: window[%u] is not finite", who, i); return RTS_ERR_INVALID; }
+    RTS_TRY(rts_window_finite_check(who, p->window, n_samples));
     *plan = rts_range_plan(q.n_rx, p->n_pulses, n_samples, p->n_fft, p->n_out);
     if (!plan->supported) { rts_set_error("%s: n_rx = %u receivers x n_pulses = %u rows, %u per workgroup: more than %u workgroups (the launch grid)", who, q.n_rx, p->n_pulses, plan->RT, RTS_RANGE_MAX_GRID_X); return RTS_ERR_INVALID; }
     return RTS_OK;
@@ -1180,9 +1097,9 @@ static int rts_range_check(const RtsRangeParams* p, const RtsCubeParams& q, cons
 
 extern "C" int rts_range_eval(const RtsCubeParams* q, const double* cube, const RtsRangeParams* p, double* out)
 {
-    if (!q || q->n_rx == 0 || q->n_pulses == 0 || q->n_bins == 0) { rts_set_error("rts_range_eval: bad cube parameters"); return RTS_ERR_INVALID; }
+    RTS_TRY(rts_eval_cube_check("rts_range_eval", q, true, false));
     RtsRangePlan plan;
-    int rc = rts_range_check(p, *q, "rts_range_eval", &plan); if (rc != RTS_OK) return rc;
+    RTS_TRY(rts_range_check(p, *q, "rts_range_eval", &plan));
     if (!cube || !out) { rts_set_error("rts_range_eval: null cube or output array"); return RTS_ERR_INVALID; }
     std::vector<double> work(3 * (size_t)p->n_fft);
     rts_range_eval_host(q, cube, p, plan, out, work.data());
@@ -1195,7 +1112,7 @@ extern "C" int rts_cube_range_transform(RtsHandle c, const RtsRangeParams* p, vo
     NEED_CUBE(c, "rts_cube_range_transform", "no cube (call rts_cube_attach first)");
     const RtsCubeParams& q = c->cube.params;
     RtsRangePlan plan;
-    int rc = rts_range_check(p, q, "rts_cube_range_transform", &plan); if (rc != RTS_OK) return rc;
+    RTS_TRY(rts_range_check(p, q, "rts_cube_range_transform", &plan));
     if ((uintptr_t)device_out & 15u) { rts_set_error("rts_cube_range_transform: device_out is not 16-byte aligned"); return RTS_ERR_INVALID; }
     if ((uintptr_t)c->cube.p & 15u) { rts_set_error("rts_cube_range_transform: the cube's device memory is not 16-byte aligned"); return RTS_ERR_INVALID; }
     CHECK_CLOSED(c);
@@ -1203,10 +1120,7 @@ extern "C" int rts_cube_range_transform(RtsHandle c, const RtsRangeParams* p, vo
     // the window -> pinned staging -> the device, on the stream (n_samples <= RTS_RANGE_MAX_FFT: one size for every call)
     const double* win = nullptr;
     if (p->window) {
-        double* w = nullptr;
-        RTS_HIP(c->cube.range_win.begin(RTS_RANGE_MAX_FFT, RTS_RANGE_MAX_FFT, RTS_RANGE_MAX_FFT, &w));
-        memcpy(w, p->window, sizeof(double) * plan.n_samples);
-        RTS_HIP(c->cube.range_win.send(plan.n_samples, c->stream));
+        RTS_HIP(c->cube.range_win.upload(p->window, plan.n_samples, RTS_RANGE_MAX_FFT, c->stream));
         win = c->cube.range_win.dev.p;
     }
     if (!device_out) c->cube.range.record(out, plan.out_doubles);
@@ -1216,7 +1130,7 @@ extern "C" int rts_cube_range_transform(RtsHandle c, const RtsRangeParams* p, vo
 extern "C" int rts_cube_range_get(RtsHandle c, double* host_out, uint64_t capacity_doubles)
 {
     CHECK_HANDLE(c);
-    return rts_cube_copy_out(c, "rts_cube_range_get", "no library-owned range map (rts_cube_range_transform with device_out NULL; a range map ends at rts_cube_attach) / null output", c->cube.range.valid, c->cube.range.p, c->cube.range.doubles, host_out, capacity_doubles);
+    return rts_cube_copy_out(c, "rts_cube_range_get", "no library-owned range map (rts_cube_range_transform with device_out NULL; a range map ends at rts_cube_attach) / null output", c->cube.range, host_out, capacity_doubles);
 }
 
 // ------------------------------------------------------------------------------------- receive-array beamforming
@@ -1226,7 +1140,7 @@ static int rts_beam_check(const RtsBeamParams* p, uint32_t n_rx, const char* who
 {
     if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
     if (p->reserved[0] || p->reserved[1]) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
-    if (p->source > RTS_BEAM_FROM_POINTER) { rts_set_error("%s: unknown source %u (RTS_BEAM_FROM_CUBE, _MAP, _POINTER)", who, p->source); return RTS_ERR_INVALID; }
+    RTS_TRY(rts_source_known_check(who, p->source));
     if (p->flags & ~(RTS_BEAM_POWER | RTS_BEAM_PEAK)) { rts_set_error("%s: unknown flags 0x%x", who, p->flags); return RTS_ERR_INVALID; }
     if ((p->flags & RTS_BEAM_PEAK) && (p->flags & RTS_BEAM_POWER)) { rts_set_error("%s: flags: RTS_BEAM_PEAK excludes RTS_BEAM_POWER", who); return RTS_ERR_INVALID; }
     if (p->n_beams == 0 || p->n_beams > RTS_BEAM_MAX_BEAMS) { rts_set_error("%s: n_beams = %u (1 .. %u)", who, p->n_beams, RTS_BEAM_MAX_BEAMS); return RTS_ERR_INVALID; }
@@ -1234,28 +1148,26 @@ static int rts_beam_check(const RtsBeamParams* p, uint32_t n_rx, const char* who
     if ((uint64_t)p->n_beams * n_rx > RTS_BEAM_MAX_WEIGHTS) { rts_set_error("%s: n_beams * n_rx = %u * %u weights: more than %u (the table sits in a workgroup's LDS)", who, p->n_beams, n_rx, RTS_BEAM_MAX_WEIGHTS); return RTS_ERR_INVALID; }
     if (!p->weights) { rts_set_error("%s: null weights", who); return RTS_ERR_INVALID; }
     for (uint32_t i = 0; i < 2 * p->n_beams * n_rx; i++) if (!std::isfinite(p->weights[i])) { rts_set_error("%s: weights[%u][%u] is not finite", who, i / 2 / n_rx, i / 2 % n_rx); return RTS_ERR_INVALID; }
-    if (p->source != RTS_BEAM_FROM_POINTER && p->n_rows_in != 0) { rts_set_error("%s: n_rows_in = %u without RTS_BEAM_FROM_POINTER", who, p->n_rows_in); return RTS_ERR_INVALID; }
-    if (p->source != RTS_BEAM_FROM_POINTER && p->device_in) { rts_set_error("%s: device_in without RTS_BEAM_FROM_POINTER", who); return RTS_ERR_INVALID; }
-    if (p->source == RTS_BEAM_FROM_POINTER && p->n_rows_in == 0) { rts_set_error("%s: n_rows_in = 0 with RTS_BEAM_FROM_POINTER", who); return RTS_ERR_INVALID; }
-    return RTS_OK;
+    return rts_source_fields_check(who, p->source, p->n_rows_in, p->device_in);
 }
 // the span inside the source's rows, and the plan of its launch
 static int rts_beam_rows_check(const RtsBeamParams* p, uint32_t rows, uint32_t n_rx, uint32_t n_bins, const char* who, RtsBeamPlan* plan)
 {
-    if (p->first_row >= rows || p->n_rows > rows - p->first_row) { rts_set_error("%s: first_row = %u, n_rows = %u: inside the source's %u rows", who, p->first_row, p->n_rows, rows); return RTS_ERR_INVALID; }
-    *plan = rts_beam_plan(n_rx, p->n_beams, p->n_rows ? p->n_rows : rows - p->first_row, n_bins, p->flags);
+    uint32_t n_rows = 0;
+    RTS_TRY(rts_rows_check(who, p->first_row, p->n_rows, rows, &n_rows));
+    *plan = rts_beam_plan(n_rx, p->n_beams, n_rows, n_bins, p->flags);
     if (!plan->supported) { rts_set_error("%s: %llu cells (n_rows * n_bins), %u per workgroup: more than %u workgroups (the launch grid)", who, (unsigned long long)plan->cells, RTS_BEAM_THREADS, RTS_BEAM_MAX_GRID_X); return RTS_ERR_INVALID; }
     return RTS_OK;
 }
 
 extern "C" int rts_beamform_eval(const RtsCubeParams* q, const double* in, uint32_t n_rows_in, const RtsBeamParams* p, double* out)
 {
-    if (!q || q->n_rx == 0 || q->n_bins == 0) { rts_set_error("rts_beamform_eval: bad cube parameters"); return RTS_ERR_INVALID; }
+    RTS_TRY(rts_eval_cube_check("rts_beamform_eval", q, false, false));
     if (n_rows_in == 0) { rts_set_error("rts_beamform_eval: n_rows_in = 0"); return RTS_ERR_INVALID; }
-    int rc = rts_beam_check(p, q->n_rx, "rts_beamform_eval"); if (rc != RTS_OK) return rc;
-    if (p->source == RTS_BEAM_FROM_POINTER && p->n_rows_in != n_rows_in) { rts_set_error("rts_beamform_eval: the parameters' n_rows_in = %u, the array's %u", p->n_rows_in, n_rows_in); return RTS_ERR_INVALID; }
+    RTS_TRY(rts_beam_check(p, q->n_rx, "rts_beamform_eval"));
+    RTS_TRY(rts_source_rows_match_check("rts_beamform_eval", p->source, p->n_rows_in, n_rows_in));
     RtsBeamPlan plan;
-    rc = rts_beam_rows_check(p, n_rows_in, q->n_rx, q->n_bins, "rts_beamform_eval", &plan); if (rc != RTS_OK) return rc;
+    RTS_TRY(rts_beam_rows_check(p, n_rows_in, q->n_rx, q->n_bins, "rts_beamform_eval", &plan));
     if (!in || !out) { rts_set_error("rts_beamform_eval: null input or output array"); return RTS_ERR_INVALID; }
     rts_beam_eval_host(q->n_rx, q->n_bins, in, n_rows_in, p->first_row, (uint32_t)(plan.cells / q->n_bins), p->n_beams, p->weights, p->flags, out);
     return RTS_OK;
@@ -1288,37 +1200,19 @@ extern "C" int rts_cube_beamform(RtsHandle c, const RtsBeamParams* p, void* devi
     CHECK_HANDLE(c);
     NEED_CUBE(c, "rts_cube_beamform", "no cube (call rts_cube_attach first)");
     const RtsCubeParams& q = c->cube.params;
-    int rc = rts_beam_check(p, q.n_rx, "rts_cube_beamform"); if (rc != RTS_OK) return rc;
-    const double* src = c->cube.p; uint32_t rows = q.n_pulses;
-    if (p->source == RTS_BEAM_FROM_MAP) {
-        const RtsCubeProduct& m = c->cube.doppler;
-        if (!m.valid || !m.own.p || m.p != m.own.p) { rts_set_error("rts_cube_beamform: RTS_BEAM_FROM_MAP: no library-owned map (rts_cube_doppler with device_out NULL)"); return RTS_ERR_INVALID; }
-        src = m.p; rows = c->cube.doppler_n;
-    } else if (p->source == RTS_BEAM_FROM_POINTER) {
-        if (!p->device_in) { rts_set_error("rts_cube_beamform: null device_in with RTS_BEAM_FROM_POINTER"); return RTS_ERR_INVALID; }
-        src = (const double*)p->device_in; rows = p->n_rows_in;
-    }
-    if ((uintptr_t)src & 15u) { rts_set_error("rts_cube_beamform: %s is not 16-byte aligned", p->source == RTS_BEAM_FROM_POINTER ? "device_in" : "the source's device memory"); return RTS_ERR_INVALID; }
+    RTS_TRY(rts_beam_check(p, q.n_rx, "rts_cube_beamform"));
+    const double* src; uint32_t rows;
+    RTS_TRY(rts_device_source(c, "rts_cube_beamform", p->source, p->device_in, p->n_rows_in, &src, &rows));
     RtsBeamPlan plan;
-    rc = rts_beam_rows_check(p, rows, q.n_rx, q.n_bins, "rts_cube_beamform", &plan); if (rc != RTS_OK) return rc;
+    RTS_TRY(rts_beam_rows_check(p, rows, q.n_rx, q.n_bins, "rts_cube_beamform", &plan));
     if ((uintptr_t)device_out & 15u) { rts_set_error("rts_cube_beamform: device_out is not 16-byte aligned"); return RTS_ERR_INVALID; }
     const uint64_t rx_stride = (uint64_t)rows * q.n_bins;
     const double* in = src + 2 * (size_t)p->first_row * q.n_bins;
-    if (device_out) {       // the transform is not in place: the output's bytes against each receiver's span of the input
-        const uintptr_t o0 = (uintptr_t)device_out, o1 = o0 + sizeof(double) * plan.out_doubles;
-        for (uint32_t r = 0; r < q.n_rx; r++) {
-            const uintptr_t i0 = (uintptr_t)(in + 2 * (size_t)r * rx_stride), i1 = i0 + 16u * (uintptr_t)plan.cells;
-            if (o0 < i1 && i0 < o1) { rts_set_error("rts_cube_beamform: device_out overlaps the input the call reads (receiver %u): the transform is not in place", r); return RTS_ERR_INVALID; }
-        }
-    }
+    RTS_TRY(rts_output_apart_check("rts_cube_beamform", "%s: device_out overlaps the input the call reads (receiver %u): the transform is not in place", device_out, plan.out_doubles, in, rx_stride, 0u, plan.cells, q.n_rx));
     CHECK_CLOSED(c);
     double* out; RTS_HIP(c->cube.beam.place(device_out, plan.out_doubles, &out));
     // the weights -> pinned staging -> the device, on the stream (n_beams n_rx <= RTS_BEAM_MAX_WEIGHTS: one size for every call)
-    const size_t nw = 2 * (size_t)p->n_beams * q.n_rx;
-    double* w = nullptr;
-    RTS_HIP(c->cube.beam_w.begin(2u * RTS_BEAM_MAX_WEIGHTS, 2u * RTS_BEAM_MAX_WEIGHTS, 2u * RTS_BEAM_MAX_WEIGHTS, &w));
-    memcpy(w, p->weights, sizeof(double) * nw);
-    RTS_HIP(c->cube.beam_w.send(nw, c->stream));
+    RTS_HIP(c->cube.beam_w.upload(p->weights, 2 * (size_t)p->n_beams * q.n_rx, 2u * RTS_BEAM_MAX_WEIGHTS, c->stream));
     if (!device_out) c->cube.beam.record(out, plan.out_doubles);
     return rts_cube_beam_device(c, *p, plan, in, rx_stride, c->cube.beam_w.dev.p, out);
 }
@@ -1326,7 +1220,7 @@ extern "C" int rts_cube_beamform(RtsHandle c, const RtsBeamParams* p, void* devi
 extern "C" int rts_cube_beam_get(RtsHandle c, double* host_out, uint64_t capacity_doubles)
 {
     CHECK_HANDLE(c);
-    return rts_cube_copy_out(c, "rts_cube_beam_get", "no library-owned beams (rts_cube_beamform with device_out NULL; the beams end at rts_cube_attach) / null output", c->cube.beam.valid, c->cube.beam.p, c->cube.beam.doubles, host_out, capacity_doubles);
+    return rts_cube_copy_out(c, "rts_cube_beam_get", "no library-owned beams (rts_cube_beamform with device_out NULL; the beams end at rts_cube_attach) / null output", c->cube.beam, host_out, capacity_doubles);
 }
 
 // ------------------------------------------------------------------------------------- adaptive (MVDR) beamforming
@@ -1336,25 +1230,22 @@ static int rts_cov_check(const RtsCovParams* p, uint32_t n_rx, const char* who)
 {
     if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
     if (p->reserved[0] || p->reserved[1]) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
-    if (p->source > RTS_BEAM_FROM_POINTER) { rts_set_error("%s: unknown source %u (RTS_BEAM_FROM_CUBE, _MAP, _POINTER)", who, p->source); return RTS_ERR_INVALID; }
+    RTS_TRY(rts_source_known_check(who, p->source));
     if (n_rx > RTS_BEAM_MAX_RX) { rts_set_error("%s: n_rx = %u receivers: more than %u", who, n_rx, RTS_BEAM_MAX_RX); return RTS_ERR_INVALID; }
-    if (p->source != RTS_BEAM_FROM_POINTER && p->n_rows_in != 0) { rts_set_error("%s: n_rows_in = %u without RTS_BEAM_FROM_POINTER", who, p->n_rows_in); return RTS_ERR_INVALID; }
-    if (p->source != RTS_BEAM_FROM_POINTER && p->device_in) { rts_set_error("%s: device_in without RTS_BEAM_FROM_POINTER", who); return RTS_ERR_INVALID; }
-    if (p->source == RTS_BEAM_FROM_POINTER && p->n_rows_in == 0) { rts_set_error("%s: n_rows_in = 0 with RTS_BEAM_FROM_POINTER", who); return RTS_ERR_INVALID; }
-    return RTS_OK;
+    return rts_source_fields_check(who, p->source, p->n_rows_in, p->device_in);
 }
 // the training set inside the source's rows and bins, and the plan of its launches.  n_taps 1: the receivers' covariance; more: the
 // stacked one (rts_stap.h) -- the span holds n_taps - 1 fewer start rows than rows, the matrix is of order n_taps n_rx
 static int rts_cov_set_check(const RtsCovParams* p, uint32_t rows, uint32_t n_rx, uint32_t nb, const char* who, RtsCovSet* set, RtsCovPlan* plan, uint32_t n_taps = 1u)
 {
-    if (p->first_row >= rows || p->n_rows > rows - p->first_row) { rts_set_error("%s: first_row = %u, n_rows = %u: inside the source's %u rows", who, p->first_row, p->n_rows, rows); return RTS_ERR_INVALID; }
-    if (p->first_bin >= nb || p->n_bins > nb - p->first_bin) { rts_set_error("%s: first_bin = %u, n_bins = %u: inside the source's %u bins", who, p->first_bin, p->n_bins, nb); return RTS_ERR_INVALID; }
-    const uint32_t span = p->n_bins ? p->n_bins : nb - p->first_bin;
+    uint32_t span = 0;
+    RTS_TRY(rts_rows_check(who, p->first_row, p->n_rows, rows, &set->n_rows));
+    RTS_TRY(rts_gate_check(who, "%s: first_bin = %u, n_bins = %u: inside the source's %u bins", p->first_bin, p->n_bins, nb, &span));
     if (p->skip_n_bins == 0 && p->skip_first_bin != 0) { rts_set_error("%s: skip_first_bin = %u with skip_n_bins = 0", who, p->skip_first_bin); return RTS_ERR_INVALID; }
     if (p->skip_n_bins != 0 && (p->skip_first_bin < p->first_bin || p->skip_first_bin - p->first_bin >= span || p->skip_n_bins > span - (p->skip_first_bin - p->first_bin))) {
         rts_set_error("%s: skip_first_bin = %u, skip_n_bins = %u: inside the bins %u .. %u + %u", who, p->skip_first_bin, p->skip_n_bins, p->first_bin, p->first_bin, span); return RTS_ERR_INVALID; }
     if (p->skip_n_bins == span) { rts_set_error("%s: skip_n_bins = %u leaves no bin of the span's %u", who, p->skip_n_bins, span); return RTS_ERR_INVALID; }
-    set->first_row = p->first_row; set->n_rows = p->n_rows ? p->n_rows : rows - p->first_row; set->first_bin = p->first_bin;
+    set->first_row = p->first_row; set->first_bin = p->first_bin;
     set->kept = span - p->skip_n_bins; set->skip_n = p->skip_n_bins; set->skip_at = p->skip_n_bins ? p->skip_first_bin - p->first_bin : set->kept;
     if (set->n_rows < n_taps) { rts_set_error("%s: n_rows = %u rows hold no snapshot of n_taps = %u", who, set->n_rows, n_taps); return RTS_ERR_INVALID; }
     set->n_rows -= n_taps - 1u;
@@ -1365,12 +1256,12 @@ static int rts_cov_set_check(const RtsCovParams* p, uint32_t rows, uint32_t n_rx
 
 extern "C" int rts_covariance_eval(const RtsCubeParams* q, const double* in, uint32_t n_rows_in, const RtsCovParams* p, double* out)
 {
-    if (!q || q->n_rx == 0 || q->n_bins == 0) { rts_set_error("rts_covariance_eval: bad cube parameters"); return RTS_ERR_INVALID; }
+    RTS_TRY(rts_eval_cube_check("rts_covariance_eval", q, false, false));
     if (n_rows_in == 0) { rts_set_error("rts_covariance_eval: n_rows_in = 0"); return RTS_ERR_INVALID; }
-    int rc = rts_cov_check(p, q->n_rx, "rts_covariance_eval"); if (rc != RTS_OK) return rc;
-    if (p->source == RTS_BEAM_FROM_POINTER && p->n_rows_in != n_rows_in) { rts_set_error("rts_covariance_eval: the parameters' n_rows_in = %u, the array's %u", p->n_rows_in, n_rows_in); return RTS_ERR_INVALID; }
+    RTS_TRY(rts_cov_check(p, q->n_rx, "rts_covariance_eval"));
+    RTS_TRY(rts_source_rows_match_check("rts_covariance_eval", p->source, p->n_rows_in, n_rows_in));
     RtsCovSet set; RtsCovPlan plan;
-    rc = rts_cov_set_check(p, n_rows_in, q->n_rx, q->n_bins, "rts_covariance_eval", &set, &plan); if (rc != RTS_OK) return rc;
+    RTS_TRY(rts_cov_set_check(p, n_rows_in, q->n_rx, q->n_bins, "rts_covariance_eval", &set, &plan));
     if (!in || !out) { rts_set_error("rts_covariance_eval: null input or output array"); return RTS_ERR_INVALID; }
     rts_cov_eval_host(q->n_rx, q->n_bins, in, n_rows_in, set, plan, out);
     return RTS_OK;
@@ -1381,29 +1272,16 @@ extern "C" int rts_cube_covariance(RtsHandle c, const RtsCovParams* p, void* dev
     CHECK_HANDLE(c);
     NEED_CUBE(c, "rts_cube_covariance", "no cube (call rts_cube_attach first)");
     const RtsCubeParams& q = c->cube.params;
-    int rc = rts_cov_check(p, q.n_rx, "rts_cube_covariance"); if (rc != RTS_OK) return rc;
-    const double* src = c->cube.p; uint32_t rows = q.n_pulses;
-    if (p->source == RTS_BEAM_FROM_MAP) {
-        const RtsCubeProduct& m = c->cube.doppler;
-        if (!m.valid || !m.own.p || m.p != m.own.p) { rts_set_error("rts_cube_covariance: RTS_BEAM_FROM_MAP: no library-owned map (rts_cube_doppler with device_out NULL)"); return RTS_ERR_INVALID; }
-        src = m.p; rows = c->cube.doppler_n;
-    } else if (p->source == RTS_BEAM_FROM_POINTER) {
-        if (!p->device_in) { rts_set_error("rts_cube_covariance: null device_in with RTS_BEAM_FROM_POINTER"); return RTS_ERR_INVALID; }
-        src = (const double*)p->device_in; rows = p->n_rows_in;
-    }
-    if ((uintptr_t)src & 15u) { rts_set_error("rts_cube_covariance: %s is not 16-byte aligned", p->source == RTS_BEAM_FROM_POINTER ? "device_in" : "the source's device memory"); return RTS_ERR_INVALID; }
+    RTS_TRY(rts_cov_check(p, q.n_rx, "rts_cube_covariance"));
+    const double* src; uint32_t rows;
+    RTS_TRY(rts_device_source(c, "rts_cube_covariance", p->source, p->device_in, p->n_rows_in, &src, &rows));
     RtsCovSet set; RtsCovPlan plan;
-    rc = rts_cov_set_check(p, rows, q.n_rx, q.n_bins, "rts_cube_covariance", &set, &plan); if (rc != RTS_OK) return rc;
+    RTS_TRY(rts_cov_set_check(p, rows, q.n_rx, q.n_bins, "rts_cube_covariance", &set, &plan));
     if ((uintptr_t)device_out & 15u) { rts_set_error("rts_cube_covariance: device_out is not 16-byte aligned"); return RTS_ERR_INVALID; }
     const uint64_t rx_stride = (uint64_t)rows * q.n_bins;
-    if (device_out) {       // the output's bytes against each receiver's span of the input: its first training cell .. its last
-        const uintptr_t o0 = (uintptr_t)device_out, o1 = o0 + sizeof(double) * plan.out_doubles;
-        const uint64_t e0 = rts_cov_cell_index(set, q.n_bins, 0), e1 = rts_cov_cell_index(set, q.n_bins, plan.K - 1u) + 1u;
-        for (uint32_t r = 0; r < q.n_rx; r++) {
-            const uintptr_t i0 = (uintptr_t)(src + 2 * ((size_t)r * rx_stride + e0)), i1 = (uintptr_t)(src + 2 * ((size_t)r * rx_stride + e1));
-            if (o0 < i1 && i0 < o1) { rts_set_error("rts_cube_covariance: device_out overlaps the input the call reads (receiver %u)", r); return RTS_ERR_INVALID; }
-        }
-    }
+    // the output's bytes against each receiver's span of the input: its first training cell .. its last
+    RTS_TRY(rts_output_apart_check("rts_cube_covariance", "%s: device_out overlaps the input the call reads (receiver %u)", device_out, plan.out_doubles, src, rx_stride, rts_cov_cell_index(set, q.n_bins, 0),
+                                   rts_cov_cell_index(set, q.n_bins, plan.K - 1u) + 1u, q.n_rx));
     CHECK_CLOSED(c);
     double* out; RTS_HIP(c->cube.cov.place(device_out, plan.out_doubles, &out));
     RTS_HIP(c->cube.d_cov_part.reserve(plan.scratch_bytes / sizeof(double)));
@@ -1414,7 +1292,7 @@ extern "C" int rts_cube_covariance(RtsHandle c, const RtsCovParams* p, void* dev
 extern "C" int rts_cube_covariance_get(RtsHandle c, double* host_out, uint64_t capacity_doubles)
 {
     CHECK_HANDLE(c);
-    return rts_cube_copy_out(c, "rts_cube_covariance_get", "no library-owned covariance (rts_cube_covariance with device_out NULL; a covariance ends at rts_cube_attach) / null output", c->cube.cov.valid, c->cube.cov.p, c->cube.cov.doubles, host_out, capacity_doubles);
+    return rts_cube_copy_out(c, "rts_cube_covariance_get", "no library-owned covariance (rts_cube_covariance with device_out NULL; a covariance ends at rts_cube_attach) / null output", c->cube.cov, host_out, capacity_doubles);
 }
 
 // the record, the limits and the steering rows of a solve over n_rx receivers
@@ -1437,7 +1315,7 @@ extern "C" int rts_mvdr_eval(const double* cov, uint32_t n_rx, const RtsMvdrPara
     if (!p) { rts_set_error("rts_mvdr_eval: null parameters"); return RTS_ERR_INVALID; }
     if (p->n_rx != n_rx) { rts_set_error("rts_mvdr_eval: the parameters' n_rx = %u, the array's %u", p->n_rx, n_rx); return RTS_ERR_INVALID; }
     RtsMvdrPlan plan;
-    int rc = rts_mvdr_check(p, n_rx, "rts_mvdr_eval", &plan); if (rc != RTS_OK) return rc;
+    RTS_TRY(rts_mvdr_check(p, n_rx, "rts_mvdr_eval", &plan));
     if (!cov || !out) { rts_set_error("rts_mvdr_eval: null covariance or output array"); return RTS_ERR_INVALID; }
     std::vector<double> L(2 * (size_t)n_rx * n_rx), x(2 * (size_t)n_rx), w(plan.out_doubles);
     const int pivot = rts_mvdr_eval_host(cov, n_rx, p->n_beams, p->steering, p->loading, L.data(), x.data(), w.data());
@@ -1451,29 +1329,18 @@ extern "C" int rts_cube_mvdr(RtsHandle c, const RtsMvdrParams* p, void* device_o
     CHECK_HANDLE(c);
     NEED_CUBE(c, "rts_cube_mvdr", "no cube (call rts_cube_attach first)");
     if (!p) { rts_set_error("rts_cube_mvdr: null parameters"); return RTS_ERR_INVALID; }
-    const double* cov = (const double*)p->device_cov; uint32_t n_rx = p->n_rx;
-    if (cov) {
-        if ((uintptr_t)cov & 15u) { rts_set_error("rts_cube_mvdr: device_cov is not 16-byte aligned"); return RTS_ERR_INVALID; }
-    } else {
-        if (!c->cube.cov.valid) { rts_set_error("rts_cube_mvdr: no covariance (rts_cube_covariance with device_out NULL first, or pass device_cov)"); return RTS_ERR_INVALID; }
-        if (n_rx != 0 && n_rx != c->cube.cov_n) { rts_set_error("rts_cube_mvdr: n_rx = %u, the library-owned covariance's %u (or 0)", n_rx, c->cube.cov_n); return RTS_ERR_INVALID; }
-        cov = c->cube.cov.p; n_rx = c->cube.cov_n;
-    }
+    const double* cov; uint32_t n_rx = p->n_rx;
+    RTS_TRY(rts_pointer_or_owned("rts_cube_mvdr", p->device_cov, c->cube.cov, c->cube.cov_n, "%s: device_cov is not 16-byte aligned",
+                                 "%s: no covariance (rts_cube_covariance with device_out NULL first, or pass device_cov)", "%s: n_rx = %u, the library-owned covariance's %u (or 0)", &cov, &n_rx));
     RtsMvdrPlan plan;
-    int rc = rts_mvdr_check(p, n_rx, "rts_cube_mvdr", &plan); if (rc != RTS_OK) return rc;
+    RTS_TRY(rts_mvdr_check(p, n_rx, "rts_cube_mvdr", &plan));
     if ((uintptr_t)device_out & 15u) { rts_set_error("rts_cube_mvdr: device_out is not 16-byte aligned"); return RTS_ERR_INVALID; }
-    if (device_out) {
-        const uintptr_t o0 = (uintptr_t)device_out, o1 = o0 + sizeof(double) * plan.out_doubles, i0 = (uintptr_t)cov, i1 = i0 + 16u * (uintptr_t)n_rx * n_rx;
-        if (o0 < i1 && i0 < o1) { rts_set_error("rts_cube_mvdr: device_out overlaps the covariance the call reads"); return RTS_ERR_INVALID; }
-    }
+    if (device_out && rts_bytes_overlap(device_out, sizeof(double) * plan.out_doubles, cov, 16u * (size_t)n_rx * n_rx)) { rts_set_error("rts_cube_mvdr: device_out overlaps the covariance the call reads"); return RTS_ERR_INVALID; }
     CHECK_CLOSED(c);
     double* out; RTS_HIP(c->cube.mvdr.place(device_out, plan.out_doubles, &out));
     RTS_HIP(c->cube.d_mvdr_status.reserve(2));
     // the steering rows -> pinned staging -> the device, on the stream (n_beams n_rx <= RTS_BEAM_MAX_WEIGHTS: one size for every call)
-    double* s = nullptr;
-    RTS_HIP(c->cube.mvdr_s.begin(2u * RTS_BEAM_MAX_WEIGHTS, 2u * RTS_BEAM_MAX_WEIGHTS, 2u * RTS_BEAM_MAX_WEIGHTS, &s));
-    memcpy(s, p->steering, sizeof(double) * plan.out_doubles);
-    RTS_HIP(c->cube.mvdr_s.send(plan.out_doubles, c->stream));
+    RTS_HIP(c->cube.mvdr_s.upload(p->steering, plan.out_doubles, 2u * RTS_BEAM_MAX_WEIGHTS, c->stream));
     if (!device_out) c->cube.mvdr.record(out, plan.out_doubles);
     return rts_cube_mvdr_device(c, plan, n_rx, p->n_beams, p->loading, cov, c->cube.mvdr_s.dev.p, c->cube.d_mvdr_status.p + (device_out ? 1 : 0), out);
 }
@@ -1484,9 +1351,8 @@ extern "C" int rts_cube_mvdr_get(RtsHandle c, double* host_out, uint64_t capacit
     const RtsCubeProduct& m = c->cube.mvdr;
     if (!c->cube.set || !m.valid || !host_out) { rts_set_error("rts_cube_mvdr_get: no library-owned weights (rts_cube_mvdr with device_out NULL; the weights end at rts_cube_attach) / null output"); return RTS_ERR_INVALID; }
     if (capacity_doubles < m.doubles) { rts_set_error("rts_cube_mvdr_get: capacity too small"); return RTS_ERR_CAPACITY; }
-    RTS_HIP(hipStreamSynchronize(c->stream));
     uint32_t status = 0;
-    RTS_HIP(hipMemcpy(&status, c->cube.d_mvdr_status.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    RTS_TRY(rts_status_word(c, c->cube.d_mvdr_status.p, &status));
     if (status) { rts_set_error("rts_cube_mvdr_get: the solve failed at pivot %u (not finite or not > 0: the covariance plus loading is not positive definite); every weight is NaN", status - 1u); return RTS_ERR_INVALID; }
     RTS_HIP(hipMemcpy(host_out, m.p, sizeof(double) * m.doubles, hipMemcpyDeviceToHost));
     return RTS_OK;
@@ -1510,34 +1376,19 @@ static RtsCovParams rts_st_cov_fields(const RtsStCovParams* p)
     s.skip_first_bin = p->skip_first_bin; s.skip_n_bins = p->skip_n_bins; s.device_in = p->device_in; s.reserved[0] = p->reserved[0]; s.reserved[1] = p->reserved[1];
     return s;
 }
-// the device source of a call (the beamformer's three) and its rows
-static int rts_st_source(RtsContext* c, const char* who, uint32_t source, const void* device_in, uint32_t n_rows_in, const double** src, uint32_t* rows)
-{
-    *src = c->cube.p; *rows = c->cube.params.n_pulses;
-    if (source == RTS_BEAM_FROM_MAP) {
-        const RtsCubeProduct& m = c->cube.doppler;
-        if (!m.valid || !m.own.p || m.p != m.own.p) { rts_set_error("%s: RTS_BEAM_FROM_MAP: no library-owned map (rts_cube_doppler with device_out NULL)", who); return RTS_ERR_INVALID; }
-        *src = m.p; *rows = c->cube.doppler_n;
-    } else if (source == RTS_BEAM_FROM_POINTER) {
-        if (!device_in) { rts_set_error("%s: null device_in with RTS_BEAM_FROM_POINTER", who); return RTS_ERR_INVALID; }
-        *src = (const double*)device_in; *rows = n_rows_in;
-    }
-    if ((uintptr_t)*src & 15u) { rts_set_error("%s: %s is not 16-byte aligned", who, source == RTS_BEAM_FROM_POINTER ? "device_in" : "the source's device memory"); return RTS_ERR_INVALID; }
-    return RTS_OK;
-}
 
 extern "C" int rts_st_covariance_eval(const RtsCubeParams* q, const double* in, uint32_t n_rows_in, const RtsStCovParams* p, double* out)
 {
     const char* who = "rts_st_covariance_eval";
-    if (!q || q->n_rx == 0 || q->n_bins == 0) { rts_set_error("%s: bad cube parameters", who); return RTS_ERR_INVALID; }
+    RTS_TRY(rts_eval_cube_check(who, q, false, false));
     if (n_rows_in == 0) { rts_set_error("%s: n_rows_in = 0", who); return RTS_ERR_INVALID; }
     if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
     const RtsCovParams s = rts_st_cov_fields(p);
-    int rc = rts_cov_check(&s, q->n_rx, who); if (rc != RTS_OK) return rc;
-    rc = rts_st_taps_check(who, p->n_taps, p->reserved0, q->n_rx); if (rc != RTS_OK) return rc;
-    if (p->source == RTS_BEAM_FROM_POINTER && p->n_rows_in != n_rows_in) { rts_set_error("%s: the parameters' n_rows_in = %u, the array's %u", who, p->n_rows_in, n_rows_in); return RTS_ERR_INVALID; }
+    RTS_TRY(rts_cov_check(&s, q->n_rx, who));
+    RTS_TRY(rts_st_taps_check(who, p->n_taps, p->reserved0, q->n_rx));
+    RTS_TRY(rts_source_rows_match_check(who, p->source, p->n_rows_in, n_rows_in));
     RtsCovSet set; RtsCovPlan plan;
-    rc = rts_cov_set_check(&s, n_rows_in, q->n_rx, q->n_bins, who, &set, &plan, p->n_taps); if (rc != RTS_OK) return rc;
+    RTS_TRY(rts_cov_set_check(&s, n_rows_in, q->n_rx, q->n_bins, who, &set, &plan, p->n_taps));
     if (!in || !out) { rts_set_error("%s: null input or output array", who); return RTS_ERR_INVALID; }
     rts_st_cov_eval_host(q->n_rx, p->n_taps, q->n_bins, in, n_rows_in, set, plan, out);
     return RTS_OK;
@@ -1551,22 +1402,17 @@ extern "C" int rts_cube_st_covariance(RtsHandle c, const RtsStCovParams* p, void
     if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
     const RtsCubeParams& q = c->cube.params;
     const RtsCovParams s = rts_st_cov_fields(p);
-    int rc = rts_cov_check(&s, q.n_rx, who); if (rc != RTS_OK) return rc;
-    rc = rts_st_taps_check(who, p->n_taps, p->reserved0, q.n_rx); if (rc != RTS_OK) return rc;
+    RTS_TRY(rts_cov_check(&s, q.n_rx, who));
+    RTS_TRY(rts_st_taps_check(who, p->n_taps, p->reserved0, q.n_rx));
     const double* src; uint32_t rows;
-    rc = rts_st_source(c, who, p->source, p->device_in, p->n_rows_in, &src, &rows); if (rc != RTS_OK) return rc;
+    RTS_TRY(rts_device_source(c, who, p->source, p->device_in, p->n_rows_in, &src, &rows));
     RtsCovSet set; RtsCovPlan plan;
-    rc = rts_cov_set_check(&s, rows, q.n_rx, q.n_bins, who, &set, &plan, p->n_taps); if (rc != RTS_OK) return rc;
+    RTS_TRY(rts_cov_set_check(&s, rows, q.n_rx, q.n_bins, who, &set, &plan, p->n_taps));
     if ((uintptr_t)device_out & 15u) { rts_set_error("%s: device_out is not 16-byte aligned", who); return RTS_ERR_INVALID; }
     const uint64_t rx_stride = (uint64_t)rows * q.n_bins;
-    if (device_out) {       // the output's bytes against each receiver's span of the input: the first snapshot's first cell .. the last one's last tap
-        const uintptr_t o0 = (uintptr_t)device_out, o1 = o0 + sizeof(double) * plan.out_doubles;
-        const uint64_t e0 = rts_cov_cell_index(set, q.n_bins, 0), e1 = rts_cov_cell_index(set, q.n_bins, plan.K - 1u) + (uint64_t)(p->n_taps - 1u) * q.n_bins + 1u;
-        for (uint32_t r = 0; r < q.n_rx; r++) {
-            const uintptr_t i0 = (uintptr_t)(src + 2 * ((size_t)r * rx_stride + e0)), i1 = (uintptr_t)(src + 2 * ((size_t)r * rx_stride + e1));
-            if (o0 < i1 && i0 < o1) { rts_set_error("%s: device_out overlaps the input the call reads (receiver %u)", who, r); return RTS_ERR_INVALID; }
-        }
-    }
+    // the output's bytes against each receiver's span of the input: the first snapshot's first cell .. the last one's last tap
+    RTS_TRY(rts_output_apart_check(who, "%s: device_out overlaps the input the call reads (receiver %u)", device_out, plan.out_doubles, src, rx_stride, rts_cov_cell_index(set, q.n_bins, 0),
+                                   rts_cov_cell_index(set, q.n_bins, plan.K - 1u) + (uint64_t)(p->n_taps - 1u) * q.n_bins + 1u, q.n_rx));
     CHECK_CLOSED(c);
     double* out; RTS_HIP(c->cube.cov.place(device_out, plan.out_doubles, &out));
     RTS_HIP(c->cube.d_cov_part.reserve(plan.scratch_bytes / sizeof(double)));
@@ -1579,24 +1425,21 @@ static int rts_st_apply_check(const RtsStApplyParams* p, uint32_t n_rx, const ch
 {
     if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
     if (p->reserved[0] || p->reserved[1]) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
-    if (p->source > RTS_BEAM_FROM_POINTER) { rts_set_error("%s: unknown source %u (RTS_BEAM_FROM_CUBE, _MAP, _POINTER)", who, p->source); return RTS_ERR_INVALID; }
+    RTS_TRY(rts_source_known_check(who, p->source));
     if (p->flags & ~RTS_BEAM_POWER) { rts_set_error("%s: unknown flags 0x%x (RTS_BEAM_POWER)", who, p->flags); return RTS_ERR_INVALID; }
-    { int rc = rts_st_taps_check(who, p->n_taps, p->reserved0, n_rx); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_st_taps_check(who, p->n_taps, p->reserved0, n_rx));
     const uint32_t D = p->n_taps * n_rx;
     if (p->n_filters == 0 || p->n_filters > RTS_BEAM_MAX_BEAMS) { rts_set_error("%s: n_filters = %u (1 .. %u)", who, p->n_filters, RTS_BEAM_MAX_BEAMS); return RTS_ERR_INVALID; }
     if ((uint64_t)p->n_filters * D > RTS_BEAM_MAX_WEIGHTS) { rts_set_error("%s: n_filters * n_taps * n_rx = %u * %u weights: more than %u (a weight table of rts_cube_beamform)", who, p->n_filters, D, RTS_BEAM_MAX_WEIGHTS); return RTS_ERR_INVALID; }
     if (!p->weights) { rts_set_error("%s: null weights", who); return RTS_ERR_INVALID; }
     for (uint32_t i = 0; i < 2 * p->n_filters * D; i++) if (!std::isfinite(p->weights[i])) { rts_set_error("%s: weights[%u][%u] is not finite", who, i / 2 / D, i / 2 % D); return RTS_ERR_INVALID; }
-    if (p->source != RTS_BEAM_FROM_POINTER && p->n_rows_in != 0) { rts_set_error("%s: n_rows_in = %u without RTS_BEAM_FROM_POINTER", who, p->n_rows_in); return RTS_ERR_INVALID; }
-    if (p->source != RTS_BEAM_FROM_POINTER && p->device_in) { rts_set_error("%s: device_in without RTS_BEAM_FROM_POINTER", who); return RTS_ERR_INVALID; }
-    if (p->source == RTS_BEAM_FROM_POINTER && p->n_rows_in == 0) { rts_set_error("%s: n_rows_in = 0 with RTS_BEAM_FROM_POINTER", who); return RTS_ERR_INVALID; }
-    return RTS_OK;
+    return rts_source_fields_check(who, p->source, p->n_rows_in, p->device_in);
 }
 // the span inside the source's rows, and the plan of its launch
 static int rts_st_apply_rows_check(const RtsStApplyParams* p, uint32_t rows, uint32_t n_rx, uint32_t n_bins, const char* who, RtsStApplyPlan* plan)
 {
-    if (p->first_row >= rows || p->n_rows > rows - p->first_row) { rts_set_error("%s: first_row = %u, n_rows = %u: inside the source's %u rows", who, p->first_row, p->n_rows, rows); return RTS_ERR_INVALID; }
-    const uint32_t n_rows = p->n_rows ? p->n_rows : rows - p->first_row;
+    uint32_t n_rows = 0;
+    RTS_TRY(rts_rows_check(who, p->first_row, p->n_rows, rows, &n_rows));
     if (n_rows < p->n_taps) { rts_set_error("%s: n_rows = %u rows hold no snapshot of n_taps = %u", who, n_rows, p->n_taps); return RTS_ERR_INVALID; }
     *plan = rts_st_apply_plan(n_rx, p->n_taps, p->n_filters, n_rows, n_bins, p->flags);
     if (!plan->supported) { rts_set_error("%s: n_rows = %u, n_bins = %u, n_filters = %u: more than %u workgroups (the launch grid)", who, n_rows, n_bins, p->n_filters, RTS_ST_MAX_GRID_X); return RTS_ERR_INVALID; }
@@ -1606,12 +1449,12 @@ static int rts_st_apply_rows_check(const RtsStApplyParams* p, uint32_t rows, uin
 extern "C" int rts_st_apply_eval(const RtsCubeParams* q, const double* in, uint32_t n_rows_in, const RtsStApplyParams* p, double* out)
 {
     const char* who = "rts_st_apply_eval";
-    if (!q || q->n_rx == 0 || q->n_bins == 0) { rts_set_error("%s: bad cube parameters", who); return RTS_ERR_INVALID; }
+    RTS_TRY(rts_eval_cube_check(who, q, false, false));
     if (n_rows_in == 0) { rts_set_error("%s: n_rows_in = 0", who); return RTS_ERR_INVALID; }
-    int rc = rts_st_apply_check(p, q->n_rx, who); if (rc != RTS_OK) return rc;
-    if (p->source == RTS_BEAM_FROM_POINTER && p->n_rows_in != n_rows_in) { rts_set_error("%s: the parameters' n_rows_in = %u, the array's %u", who, p->n_rows_in, n_rows_in); return RTS_ERR_INVALID; }
+    RTS_TRY(rts_st_apply_check(p, q->n_rx, who));
+    RTS_TRY(rts_source_rows_match_check(who, p->source, p->n_rows_in, n_rows_in));
     RtsStApplyPlan plan;
-    rc = rts_st_apply_rows_check(p, n_rows_in, q->n_rx, q->n_bins, who, &plan); if (rc != RTS_OK) return rc;
+    RTS_TRY(rts_st_apply_rows_check(p, n_rows_in, q->n_rx, q->n_bins, who, &plan));
     if (!in || !out) { rts_set_error("%s: null input or output array", who); return RTS_ERR_INVALID; }
     rts_st_apply_eval_host(q->n_rx, p->n_taps, q->n_bins, in, n_rows_in, p->first_row, plan.out_rows + p->n_taps - 1u, p->n_filters, p->weights, p->flags, out);
     return RTS_OK;
@@ -1622,7 +1465,7 @@ extern "C" int rts_st_steering_make(const double* spatial, uint32_t n_rx, uint32
     const char* who = "rts_st_steering_make";
     if (!spatial || !doppler || !out) { rts_set_error("%s: null spatial, doppler or output array", who); return RTS_ERR_INVALID; }
     if (n_rx == 0 || n_beams == 0 || n_doppler == 0) { rts_set_error("%s: n_rx = %u, n_beams = %u, n_doppler = %u (each >= 1)", who, n_rx, n_beams, n_doppler); return RTS_ERR_INVALID; }
-    { int rc = rts_st_taps_check(who, n_taps, 0u, n_rx); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_st_taps_check(who, n_taps, 0u, n_rx));
     for (size_t i = 0; i < 2 * (size_t)n_beams * n_rx; i++) if (!std::isfinite(spatial[i])) { rts_set_error("%s: spatial[%zu][%zu] is not finite", who, i / 2 / n_rx, i / 2 % n_rx); return RTS_ERR_INVALID; }
     for (uint32_t k = 0; k < n_doppler; k++) if (!std::isfinite(doppler[k])) { rts_set_error("%s: doppler[%u] is not finite", who, k); return RTS_ERR_INVALID; }
     if (tap_taper) for (uint32_t m = 0; m < n_taps; m++) if (!std::isfinite(tap_taper[m])) { rts_set_error("%s: tap_taper[%u] is not finite", who, m); return RTS_ERR_INVALID; }
@@ -1645,30 +1488,20 @@ extern "C" int rts_cube_st_apply(RtsHandle c, const RtsStApplyParams* p, void* d
     CHECK_HANDLE(c);
     NEED_CUBE(c, who, "no cube (call rts_cube_attach first)");
     const RtsCubeParams& q = c->cube.params;
-    int rc = rts_st_apply_check(p, q.n_rx, who); if (rc != RTS_OK) return rc;
+    RTS_TRY(rts_st_apply_check(p, q.n_rx, who));
     const double* src; uint32_t rows;
-    rc = rts_st_source(c, who, p->source, p->device_in, p->n_rows_in, &src, &rows); if (rc != RTS_OK) return rc;
+    RTS_TRY(rts_device_source(c, who, p->source, p->device_in, p->n_rows_in, &src, &rows));
     RtsStApplyPlan plan;
-    rc = rts_st_apply_rows_check(p, rows, q.n_rx, q.n_bins, who, &plan); if (rc != RTS_OK) return rc;
+    RTS_TRY(rts_st_apply_rows_check(p, rows, q.n_rx, q.n_bins, who, &plan));
     if ((uintptr_t)device_out & 15u) { rts_set_error("%s: device_out is not 16-byte aligned", who); return RTS_ERR_INVALID; }
     const uint64_t rx_stride = (uint64_t)rows * q.n_bins;
     const double* in = src + 2 * (size_t)p->first_row * q.n_bins;
-    if (device_out) {       // the filter is not in place: the output's bytes against each receiver's span of the input
-        const uintptr_t o0 = (uintptr_t)device_out, o1 = o0 + sizeof(double) * plan.out_doubles;
-        const uint64_t span = (uint64_t)(plan.out_rows + p->n_taps - 1u) * q.n_bins;
-        for (uint32_t r = 0; r < q.n_rx; r++) {
-            const uintptr_t i0 = (uintptr_t)(in + 2 * (size_t)r * rx_stride), i1 = i0 + 16u * (uintptr_t)span;
-            if (o0 < i1 && i0 < o1) { rts_set_error("%s: device_out overlaps the input the call reads (receiver %u): the filter is not in place", who, r); return RTS_ERR_INVALID; }
-        }
-    }
+    RTS_TRY(rts_output_apart_check(who, "%s: device_out overlaps the input the call reads (receiver %u): the filter is not in place", device_out, plan.out_doubles, in, rx_stride, 0u,
+                                   (uint64_t)(plan.out_rows + p->n_taps - 1u) * q.n_bins, q.n_rx));
     CHECK_CLOSED(c);
     double* out; RTS_HIP(c->cube.st.place(device_out, plan.out_doubles, &out));
     // the weights -> pinned staging -> the device, on the stream (n_filters D <= RTS_BEAM_MAX_WEIGHTS: one size for every call)
-    const size_t nw = 2 * (size_t)p->n_filters * plan.D;
-    double* w = nullptr;
-    RTS_HIP(c->cube.st_w.begin(2u * RTS_BEAM_MAX_WEIGHTS, 2u * RTS_BEAM_MAX_WEIGHTS, 2u * RTS_BEAM_MAX_WEIGHTS, &w));
-    memcpy(w, p->weights, sizeof(double) * nw);
-    RTS_HIP(c->cube.st_w.send(nw, c->stream));
+    RTS_HIP(c->cube.st_w.upload(p->weights, 2 * (size_t)p->n_filters * plan.D, 2u * RTS_BEAM_MAX_WEIGHTS, c->stream));
     if (!device_out) c->cube.st.record(out, plan.out_doubles);
     return rts_cube_st_apply_device(c, *p, plan, in, rx_stride, c->cube.st_w.dev.p, out);
 }
@@ -1676,17 +1509,11 @@ extern "C" int rts_cube_st_apply(RtsHandle c, const RtsStApplyParams* p, void* d
 extern "C" int rts_cube_st_get(RtsHandle c, double* host_out, uint64_t capacity_doubles)
 {
     CHECK_HANDLE(c);
-    return rts_cube_copy_out(c, "rts_cube_st_get", "no library-owned filter output (rts_cube_st_apply with device_out NULL; the output ends at rts_cube_attach) / null output", c->cube.st.valid, c->cube.st.p, c->cube.st.doubles, host_out, capacity_doubles);
+    return rts_cube_copy_out(c, "rts_cube_st_get", "no library-owned filter output (rts_cube_st_apply with device_out NULL; the output ends at rts_cube_attach) / null output", c->cube.st, host_out, capacity_doubles);
 }
 
 // ------------------------------------------------------------------------------------- direction finding
 // (rts_amd.h: RtsEigParams, RtsDoaScanParams; the trees and the launch plans are rts_doa.h, shared by the host exports and the kernels, rts_doa.hip)
-static bool rts_bytes_overlap(const void* a, size_t na, const void* b, size_t nb)
-{
-    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + na, b0 = (uintptr_t)b, b1 = b0 + nb;
-    return a0 < b1 && b0 < a1;
-}
-
 extern "C" int rts_eig_eval(const double* cov, uint32_t n, double* values_out, double* vectors_out, uint32_t* sweeps_out)
 {
     const RtsEigPlan plan = rts_eig_plan(n);
@@ -1710,14 +1537,9 @@ extern "C" int rts_cube_eig(RtsHandle c, const RtsEigParams* p, void* device_val
     NEED_CUBE(c, who, "no cube (call rts_cube_attach first)");
     if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
     if (p->reserved0 || p->reserved[0] || p->reserved[1]) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
-    const double* cov = (const double*)p->device_cov; uint32_t n = p->n;
-    if (cov) {
-        if ((uintptr_t)cov & 15u) { rts_set_error("%s: device_cov is not 16-byte aligned", who); return RTS_ERR_INVALID; }
-    } else {
-        if (!c->cube.cov.valid) { rts_set_error("%s: no covariance (rts_cube_covariance or rts_cube_st_covariance with device_out NULL first, or pass device_cov)", who); return RTS_ERR_INVALID; }
-        if (n != 0 && n != c->cube.cov_n) { rts_set_error("%s: n = %u, the library-owned covariance's %u (or 0)", who, n, c->cube.cov_n); return RTS_ERR_INVALID; }
-        cov = c->cube.cov.p; n = c->cube.cov_n;
-    }
+    const double* cov; uint32_t n = p->n;
+    RTS_TRY(rts_pointer_or_owned(who, p->device_cov, c->cube.cov, c->cube.cov_n, "%s: device_cov is not 16-byte aligned",
+                                 "%s: no covariance (rts_cube_covariance or rts_cube_st_covariance with device_out NULL first, or pass device_cov)", "%s: n = %u, the library-owned covariance's %u (or 0)", &cov, &n));
     const RtsEigPlan plan = rts_eig_plan(n);
     if (!plan.supported) { rts_set_error("%s: n = %u (1 .. %u)", who, n, RTS_BEAM_MAX_RX); return RTS_ERR_INVALID; }
     if (!device_values != !device_vectors) { rts_set_error("%s: device_values and device_vectors: both caller-owned or both NULL", who); return RTS_ERR_INVALID; }
@@ -1743,9 +1565,8 @@ extern "C" int rts_cube_eig_get(RtsHandle c, double* values_out, double* vectors
     const RtsCubeProduct& v = c->cube.eig_val; const RtsCubeProduct& x = c->cube.eig_vec;
     if (!c->cube.set || !v.valid || !x.valid || (!values_out && !vectors_out)) { rts_set_error("rts_cube_eig_get: no library-owned eigenpairs (rts_cube_eig with both outputs NULL; the eigenpairs end at rts_cube_attach) / null outputs"); return RTS_ERR_INVALID; }
     if ((values_out && capacity_values < v.doubles) || (vectors_out && capacity_vector_doubles < x.doubles)) { rts_set_error("rts_cube_eig_get: capacity too small"); return RTS_ERR_CAPACITY; }
-    RTS_HIP(hipStreamSynchronize(c->stream));
     uint32_t status = 0;
-    RTS_HIP(hipMemcpy(&status, c->cube.d_eig_status.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    RTS_TRY(rts_status_word(c, c->cube.d_eig_status.p, &status));
     if (status == 2u) { rts_set_error("rts_cube_eig_get: status 2: a non-finite entry in the covariance's lower triangle; every output is NaN"); return RTS_ERR_INVALID; }
     if (status) { rts_set_error("rts_cube_eig_get: status 1: no convergence in %u sweeps; every output is NaN", RTS_EIG_MAX_SWEEPS); return RTS_ERR_INVALID; }
     if (values_out) RTS_HIP(hipMemcpy(values_out, v.p, sizeof(double) * v.doubles, hipMemcpyDeviceToHost));
@@ -1770,7 +1591,7 @@ static int rts_doa_scan_check(const char* who, uint32_t n, uint32_t first_vector
 extern "C" int rts_doa_scan_eval(const double* vectors, const double* g, uint32_t n, uint32_t m, const double* steering, uint64_t n_dirs, uint32_t flags, double* out)
 {
     RtsDoaScanPlan plan;
-    int rc = rts_doa_scan_check("rts_doa_scan_eval", n, 0u, m, flags, n_dirs, g, &plan); if (rc != RTS_OK) return rc;
+    RTS_TRY(rts_doa_scan_check("rts_doa_scan_eval", n, 0u, m, flags, n_dirs, g, &plan));
     if (!vectors || !steering || !out) { rts_set_error("rts_doa_scan_eval: null vectors, steering or output array"); return RTS_ERR_INVALID; }
     rts_doa_scan_eval_host(vectors, g, n, m, steering, n_dirs, flags, out);
     return RTS_OK;
@@ -1783,16 +1604,11 @@ extern "C" int rts_cube_doa_scan(RtsHandle c, const RtsDoaScanParams* p, void* d
     NEED_CUBE(c, who, "no cube (call rts_cube_attach first)");
     if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
     if (p->reserved[0] || p->reserved[1]) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
-    const double* vec = (const double*)p->device_vectors; uint32_t n = p->n;
-    if (vec) {
-        if ((uintptr_t)vec & 15u) { rts_set_error("%s: device_vectors is not 16-byte aligned", who); return RTS_ERR_INVALID; }
-    } else {
-        if (!c->cube.eig_vec.valid) { rts_set_error("%s: no eigenvectors (rts_cube_eig with both outputs NULL first, or pass device_vectors)", who); return RTS_ERR_INVALID; }
-        if (n != 0 && n != c->cube.eig_n) { rts_set_error("%s: n = %u, the library-owned eigenvectors' %u (or 0)", who, n, c->cube.eig_n); return RTS_ERR_INVALID; }
-        vec = c->cube.eig_vec.p; n = c->cube.eig_n;
-    }
+    const double* vec; uint32_t n = p->n;
+    RTS_TRY(rts_pointer_or_owned(who, p->device_vectors, c->cube.eig_vec, c->cube.eig_n, "%s: device_vectors is not 16-byte aligned",
+                                 "%s: no eigenvectors (rts_cube_eig with both outputs NULL first, or pass device_vectors)", "%s: n = %u, the library-owned eigenvectors' %u (or 0)", &vec, &n));
     RtsDoaScanPlan plan;
-    int rc = rts_doa_scan_check(who, n, p->first_vector, p->m, p->flags, p->n_dirs, p->g, &plan); if (rc != RTS_OK) return rc;
+    RTS_TRY(rts_doa_scan_check(who, n, p->first_vector, p->m, p->flags, p->n_dirs, p->g, &plan));
     if (!p->device_steering) { rts_set_error("%s: null device_steering", who); return RTS_ERR_INVALID; }
     if ((uintptr_t)p->device_steering & 15u) { rts_set_error("%s: device_steering is not 16-byte aligned", who); return RTS_ERR_INVALID; }
     if ((uintptr_t)device_out & 7u) { rts_set_error("%s: device_out is not 8-byte aligned", who); return RTS_ERR_INVALID; }
@@ -1805,10 +1621,7 @@ extern "C" int rts_cube_doa_scan(RtsHandle c, const RtsDoaScanParams* p, void* d
     CHECK_CLOSED(c);
     double* out; RTS_HIP(c->cube.doa.place(device_out, plan.out_doubles, &out));
     // g -> pinned staging -> the device, on the stream (m <= RTS_BEAM_MAX_RX: one size for every call)
-    double* g = nullptr;
-    RTS_HIP(c->cube.doa_g.begin(RTS_BEAM_MAX_RX, RTS_BEAM_MAX_RX, RTS_BEAM_MAX_RX, &g));
-    memcpy(g, p->g, sizeof(double) * p->m);
-    RTS_HIP(c->cube.doa_g.send(p->m, c->stream));
+    RTS_HIP(c->cube.doa_g.upload(p->g, p->m, RTS_BEAM_MAX_RX, c->stream));
     if (!device_out) c->cube.doa.record(out, plan.out_doubles);
     return rts_cube_doa_scan_device(c, plan, n, p->m, p->n_dirs, p->flags, (const double*)p->device_steering, rows, c->cube.doa_g.dev.p, out);
 }
@@ -1816,7 +1629,7 @@ extern "C" int rts_cube_doa_scan(RtsHandle c, const RtsDoaScanParams* p, void* d
 extern "C" int rts_cube_doa_get(RtsHandle c, double* host_out, uint64_t capacity_doubles)
 {
     CHECK_HANDLE(c);
-    return rts_cube_copy_out(c, "rts_cube_doa_get", "no library-owned spectrum (rts_cube_doa_scan with device_out NULL; the spectrum ends at rts_cube_attach) / null output", c->cube.doa.valid, c->cube.doa.p, c->cube.doa.doubles, host_out, capacity_doubles);
+    return rts_cube_copy_out(c, "rts_cube_doa_get", "no library-owned spectrum (rts_cube_doa_scan with device_out NULL; the spectrum ends at rts_cube_attach) / null output", c->cube.doa, host_out, capacity_doubles);
 }
 
 extern "C" int rts_doa_weights(uint32_t method, const double* values, uint32_t n, uint32_t n_sources, double loading, uint32_t* first, uint32_t* m, double* g, uint32_t* flags)
@@ -1856,10 +1669,10 @@ static int rts_image_check(const RtsImageParams* p, const RtsCubeParams& q, cons
 {
     if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
     if (p->n_x == 0 || p->n_y == 0 || (uint64_t)p->n_x * p->n_y > RTS_IMAGE_MAX_PIXELS) { rts_set_error("%s: n_x = %u, n_y = %u (each >= 1, n_x * n_y <= %u)", who, p->n_x, p->n_y, RTS_IMAGE_MAX_PIXELS); return RTS_ERR_INVALID; }
-    { int rc = rts_taps_check(who, p->taps); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_taps_check(who, p->taps));
     if (p->flags & ~RTS_IMAGE_ACCUMULATE) { rts_set_error("%s: unknown flags 0x%x", who, p->flags); return RTS_ERR_INVALID; }
     if (p->reserved[0] || p->reserved[1]) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
-    { int rc = rts_pulses_check(who, p->first_pulse, p->n_pulses, q.n_pulses, true); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_pulses_check(who, p->first_pulse, p->n_pulses, q.n_pulses, true));
     if (!std::isfinite(p->cspeed) || !(p->cspeed > 0.0)) { rts_set_error("%s: cspeed = %g (finite, > 0)", who, p->cspeed); return RTS_ERR_INVALID; }
     if (!std::isfinite(p->carrier) || p->carrier < 0.0) { rts_set_error("%s: carrier = %g (finite, >= 0)", who, p->carrier); return RTS_ERR_INVALID; }
     for (int k = 0; k < 3; k++) {
@@ -1878,8 +1691,8 @@ static int rts_image_check(const RtsImageParams* p, const RtsCubeParams& q, cons
 
 extern "C" int rts_backproject_eval(const RtsCubeParams* q, const double* cube, const RtsImageParams* p, double* out)
 {
-    if (!q || q->n_rx == 0 || q->n_pulses == 0 || q->n_bins == 0 || !(q->dt > 0) || !std::isfinite(q->dt) || !std::isfinite(q->t0)) { rts_set_error("rts_backproject_eval: bad cube parameters"); return RTS_ERR_INVALID; }
-    int rc = rts_image_check(p, *q, "rts_backproject_eval"); if (rc != RTS_OK) return rc;
+    RTS_TRY(rts_eval_cube_check("rts_backproject_eval", q, true, true));
+    RTS_TRY(rts_image_check(p, *q, "rts_backproject_eval"));
     if (!cube || !out) { rts_set_error("rts_backproject_eval: null cube or output array"); return RTS_ERR_INVALID; }
     rts_image_eval_host(q, cube, p, out);
     return RTS_OK;
@@ -1890,7 +1703,7 @@ extern "C" int rts_cube_backproject(RtsHandle c, const RtsImageParams* p, void* 
     CHECK_HANDLE(c);
     NEED_CUBE(c, "rts_cube_backproject", "no cube (call rts_cube_attach first)");
     const RtsCubeParams& q = c->cube.params;
-    int rc = rts_image_check(p, q, "rts_cube_backproject"); if (rc != RTS_OK) return rc;
+    RTS_TRY(rts_image_check(p, q, "rts_cube_backproject"));
     if ((uintptr_t)device_out & 15u) { rts_set_error("rts_cube_backproject: device_out is not 16-byte aligned"); return RTS_ERR_INVALID; }
     if ((p->flags & RTS_IMAGE_ACCUMULATE) && !device_out && !(c->cube.image.valid && c->cube.img_nx == p->n_x && c->cube.img_ny == p->n_y)) {
         rts_set_error("rts_cube_backproject: RTS_IMAGE_ACCUMULATE without device_out needs a library-owned image of the same n_x, n_y"); return RTS_ERR_INVALID; }
@@ -1913,5 +1726,5 @@ extern "C" int rts_cube_backproject(RtsHandle c, const RtsImageParams* p, void* 
 extern "C" int rts_cube_image_get(RtsHandle c, double* host_out, uint64_t capacity_doubles)
 {
     CHECK_HANDLE(c);
-    return rts_cube_copy_out(c, "rts_cube_image_get", "no library-owned image (rts_cube_backproject with device_out NULL; an image ends at rts_cube_attach) / null output", c->cube.image.valid, c->cube.image.p, c->cube.image.doubles, host_out, capacity_doubles);
+    return rts_cube_copy_out(c, "rts_cube_image_get", "no library-owned image (rts_cube_backproject with device_out NULL; an image ends at rts_cube_attach) / null output", c->cube.image, host_out, capacity_doubles);
 }

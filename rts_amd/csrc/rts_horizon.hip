@@ -222,7 +222,7 @@ extern "C" int rts_get_horizon(RtsHandle c, float* out, uint32_t capacity_prims)
 {
     CHECK_HANDLE(c);
     std::vector<uint32_t> w;
-    const int rc = hz_fetch(c, "rts_get_horizon", out, capacity_prims, w); if (rc != RTS_OK) return rc;
+    RTS_TRY(hz_fetch(c, "rts_get_horizon", out, capacity_prims, w));
     for (size_t k = 0; k < w.size(); k++) {
         const uint32_t b = std::max(std::max(w[k] & 0xffu, w[k] >> 8 & 0xffu), std::max(w[k] >> 16 & 0xffu, w[k] >> 24));
         const double s = RTS_HZ_DECODE(b);
@@ -238,7 +238,7 @@ extern "C" int rts_get_horizon_sectors(RtsHandle c, uint8_t* out, uint32_t capac
 {
     CHECK_HANDLE(c);
     std::vector<uint32_t> w;
-    const int rc = hz_fetch(c, "rts_get_horizon_sectors", out, capacity_prims, w); if (rc != RTS_OK) return rc;
+    RTS_TRY(hz_fetch(c, "rts_get_horizon_sectors", out, capacity_prims, w));
     for (size_t k = 0; k < w.size(); k++) for (int j = 0; j < 4; j++) out[4 * k + j] = (uint8_t)(w[k] >> (8 * j) & 0xffu);
     return RTS_OK;
 }

@@ -584,6 +584,8 @@ int rts_debug_stage(RtsContext* c, const char* name);
 
 #define RTS_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
     rts_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return RTS_ERR_HIP; } } while (0)
+// ... and the library's own status: what is not RTS_OK is the caller's return value (the callee has set the message)
+#define RTS_TRY(expr) do { const int rc_ = (expr); if (rc_ != RTS_OK) return rc_; } while (0)
 
 // every entry point that takes a handle (rts_api.hip, rts_cube_api.hip) makes its device current ...
 #define CHECK_HANDLE(c) do { if (!(c)) { rts_set_error("null handle"); return RTS_ERR_INVALID; } RTS_HIP(hipSetDevice((c)->device)); } while (0)
@@ -597,7 +599,7 @@ int rts_pulse_settle(RtsContext* c);
 template <class Work> static inline int rts_finalise_bracket(RtsContext* c, Work work)
 {
     RTS_HIP(hipEventRecord(c->ev[6], c->stream));
-    { const int rc = work(); if (rc != RTS_OK) return rc; }
+    RTS_TRY(work());
     RTS_HIP(hipEventRecord(c->ev[7], c->stream));
     c->res.fin_timed = true; c->stats_pending = true; c->res.agg_valid = false;
     return RTS_OK;

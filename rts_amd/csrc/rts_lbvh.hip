@@ -764,23 +764,23 @@ int rts_lbvh_build_device(RtsContext* c, RtsScene* ns, const RtsSceneFlat& flat,
         double acc[2] = {0, 0};
         RTS_HIP(hipMemcpyAsync(acc, d_acc.p, sizeof(acc), hipMemcpyDeviceToHost, st)); RTS_HIP(hipStreamSynchronize(st));
         a_thr[t] = (split_budget > 0 && acc[1] > 0 && acc[0] > 0 && std::isfinite(acc[0])) ? (acc[0] / acc[1]) / ((1.0 + split_budget) * (1.0 + split_budget)) : 0.0;
-        { int rc = count_refs(t); if (rc != RTS_OK) return rc; }
-        { int rc = read_counts(t); if (rc != RTS_OK) return rc; }
+        RTS_TRY(count_refs(t));
+        RTS_TRY(read_counts(t));
         // crowded spots: a provisional tree over these references, the triangles behind crowded references get twice the
         // slabs, count again
         for (int round = 0; sah_tree && split_budget > 0 && round < crowd_rounds && n_valid[t] > 1; round++) {
-            { int rc = ensure_tmp(n_refs[t]); if (rc != RTS_OK) return rc; }
+            RTS_TRY(ensure_tmp(n_refs[t]));
             RTS_HIP(hipMemcpyAsync(d_bounds.p, init_bounds, sizeof(init_bounds), hipMemcpyHostToDevice, st));
             k_ref_boxes<<<blocks_for(n, 256), 256, 0, st>>>(tv, ns->d_verts_local.p, d_cnt.p, d_off.p, d_prim_box.p, d_ref_tri.p, d_bounds.p, n);
-            { int rc = sah_levels(n_refs[t], n_valid[t]); if (rc != RTS_OK) return rc; }
+            RTS_TRY(sah_levels(n_refs[t], n_valid[t]));
             uint32_t* n_boosted = d_boost.p + ns->n_prims; uint32_t before = 0, after = 0;
             RTS_HIP(hipMemcpyAsync(&before, n_boosted, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
             k_crowd<<<blocks_for(n_valid[t], 256), 256, 0, st>>>(d_nodes2.p, d_prim_box.p, d_vals_sorted.p, d_ref_tri.p, tv, ns->d_verts_local.p, n_valid[t], d_boost.p + mh[t].tri_base, n_boosted);
             RTS_HIP(hipMemcpyAsync(&after, n_boosted, sizeof(uint32_t), hipMemcpyDeviceToHost, st)); RTS_HIP(hipStreamSynchronize(st));
             if (tune.debug_build) fprintf(stderr, "[rts build] mesh %u round %d: %u triangles, %u references (%u valid), %u triangles boosted\n", t, round, n, n_refs[t], n_valid[t], after - before);
             if (after == before) break;
-            { int rc = count_refs(t); if (rc != RTS_OK) return rc; }
-            { int rc = read_counts(t); if (rc != RTS_OK) return rc; }
+            RTS_TRY(count_refs(t));
+            RTS_TRY(read_counts(t));
         }
         RtsBlasInfo& b = ns->blas[t];
         b.n_leaves = n_valid[t]; b.n_nodes = n_valid[t] == 0 ? 0 : std::max<uint32_t>(n_valid[t] - 1, 1);
@@ -792,7 +792,7 @@ int rts_lbvh_build_device(RtsContext* c, RtsScene* ns, const RtsSceneFlat& flat,
     if (r_max == 0) return RTS_OK;
 
     // ---- pass B: boxes, tree, 4-wide records -- per mesh, over its references
-    { int rc = ensure_tmp(r_max); if (rc != RTS_OK) return rc; }
+    RTS_TRY(ensure_tmp(r_max));
     int32_t node_base = 0, leaf_base = 0;
     for (uint32_t t = 0; t < n_targets; t++) {
         const uint32_t n = mh[t].n_tris, nr = n_refs[t], nv = n_valid[t];
@@ -800,12 +800,12 @@ int rts_lbvh_build_device(RtsContext* c, RtsScene* ns, const RtsSceneFlat& flat,
         if (nv == 0) continue;
         RTS_HIP(hipMemcpyAsync(d_bounds.p, init_bounds, sizeof(init_bounds), hipMemcpyHostToDevice, st));
         const uint32_t* tv = ns->d_tri_vidx.p + 3 * (size_t)mh[t].tri_base;
-        { int rc = count_refs(t); if (rc != RTS_OK) return rc; }
+        RTS_TRY(count_refs(t));
         k_ref_boxes<<<blocks_for(n, 256), 256, 0, st>>>(tv, ns->d_verts_local.p, d_cnt.p, d_off.p, d_prim_box.p, d_ref_tri.p, d_bounds.p, n);
         size_t tmp_n = tmp;
         if (sah_tree && nv > 1) {
             // ---- top-down binned SAH over the references (the quality tree)
-            { int rc = sah_levels(nr, nv); if (rc != RTS_OK) return rc; }
+            RTS_TRY(sah_levels(nr, nv));
             k_leaf_order<<<blocks_for(nv, 256), 256, 0, st>>>(d_vals_sorted.p, d_ref_tri.p, mh[t].tri_base, ns->d_leaf_prim.p + leaf_base, nv);
             const uint32_t n2 = nv - 1;
             RTS_HIP(d_nodes4_tmp.reserve(n2)); RTS_HIP(d_reach.reserve((size_t)n2 + 1)); RTS_HIP(d_newid.reserve(n2)); RTS_HIP(d_rflag.reserve(n2));

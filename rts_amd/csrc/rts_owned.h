@@ -13,6 +13,7 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stddef.h>
+#include <string.h>
 #include <utility>
 
 template <typename T> struct DevBuf {
@@ -102,6 +103,14 @@ template <typename T> struct StagedUpload {
         e = hipEventRecord(ev, s); if (e != hipSuccess) return e;
         armed = true;
         return hipSuccess;
+    }
+    // one array of n <= capacity elements, for the sites whose staging and device buffer have one size for every call
+    hipError_t upload(const T* src, size_t n, size_t capacity, hipStream_t s)
+    {
+        T* h = nullptr;
+        const hipError_t e = begin(capacity, capacity, capacity, &h); if (e != hipSuccess) return e;
+        memcpy(h, src, n * sizeof(T));
+        return send(n, s);
     }
     void drop_event() { if (ev) (void)hipEventDestroy(ev); ev = nullptr; armed = false; }
 };

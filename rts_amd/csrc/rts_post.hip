@@ -454,7 +454,7 @@ int rts_post_order_and_expand(RtsContext* c)
     const uint32_t R = (uint32_t)c->res.n_recv, D = c->depth;
     if (R == 0) return RTS_OK;
     hipStream_t st = c->stream;
-    { int rc = rts_recv_reserve(c, R); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_recv_reserve(c, R));
     size_t tmp = 0;
     if (c->tune.post_small && R <= rts_small_cap_recv(c)) {
         // items per thread by the size of the set (a speculative chain -- count on the device -- is sized for the capacity)
@@ -631,7 +631,7 @@ int rts_post_finalise(RtsContext* c, const double* rcs_host, double wl, double g
     const uint32_t R = (uint32_t)c->res.n_recv;
     if (R == 0) return RTS_OK;
     const uint32_t nt = (uint32_t)c->scene->meshes.size();
-    { int rc = rts_rcs_upload(c, rcs_host); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_rcs_upload(c, rcs_host));
     k_finalise<<<blocks_for(R, 256), 256, 0, c->stream>>>(c->d_rx_rays.p, c->d_rx_paths.p, R, c->depth, c->d_rcsval.p, nt, wl, gt, gr, carrier, cspeed, c->res.recv_dev);
     RTS_HIP(hipGetLastError());
     return RTS_OK;
@@ -707,7 +707,7 @@ int rts_post_finalise_patterns(RtsContext* c, const RtsSpecParams& q)
     const uint32_t R = (uint32_t)c->res.n_recv;
     if (R == 0) return RTS_OK;
     RtsPatArgs a;
-    int rc = rts_pattern_pulse_upload(c, q, &a); if (rc != RTS_OK) return rc;
+    RTS_TRY(rts_pattern_pulse_upload(c, q, &a));
     k_finalise_patterns<<<blocks_for(R, 256), 256, 0, c->stream>>>(c->d_rx_rays.p, c->d_rx_paths.p, c->d_rx_angles.p, R, c->depth, a, c->res.recv_dev);
     RTS_HIP(hipGetLastError());
     return RTS_OK;
@@ -1232,13 +1232,13 @@ int rts_post_all_small(RtsContext* c, uint32_t cap, const RtsSpecParams& sp, boo
     const uint32_t D = c->depth; hipStream_t st = c->stream;
     const uint32_t nt = (uint32_t)c->scene->meshes.size();
     // ---- what rts_post_order_and_expand, rts_post_finalise and rts_aggregate_device reserve, for cap rays
-    int rc = rts_recv_reserve(c, cap); if (rc != RTS_OK) return rc;
-    rc = rts_rcs_upload(c, sp.fin == 0 ? sp.rcs.data() : nullptr); if (rc != RTS_OK) return rc;      // (the pattern finaliser reads no per-target constants)
+    RTS_TRY(rts_recv_reserve(c, cap));
+    RTS_TRY(rts_rcs_upload(c, sp.fin == 0 ? sp.rcs.data() : nullptr));      // (the pattern finaliser reads no per-target constants)
     const RtsKeyPlan k = rts_handle_key_plan(c);
     RTS_HIP(c->d_delay.reserve(cap)); RTS_HIP(c->d_phase.reserve(cap)); RTS_HIP(c->d_pathmatch.reserve(cap));
     const bool use_rows = sp.base == RTS_BASE_USE_ROWS;
     RtsAggScratch s;
-    rc = rts_agg_scratch(c, k, cap, use_rows, &s); if (rc != RTS_OK) return rc;
+    RTS_TRY(rts_agg_scratch(c, k, cap, use_rows, &s));
     const uint64_t base = use_rows ? 0 : sp.base;
     RtsPostAll q; memset(&q, 0, sizeof(q));
     q.ta = c->last_args; q.rec = c->d_recv.p; q.cap = cap; q.n_rays = c->n_rays; q.with_chain = c->last_args.max_refr != 0 ? 1 : 0;
@@ -1254,7 +1254,7 @@ int rts_post_all_small(RtsContext* c, uint32_t cap, const RtsSpecParams& sp, boo
     if (sp.fin == 0) rts_post_all_launch(st, q, kr64, ka64, RtsFinUniform{});
     else {
         RtsFinPatterns f;
-        rc = rts_pattern_pulse_upload(c, sp, &f.a); if (rc != RTS_OK) return rc;
+        RTS_TRY(rts_pattern_pulse_upload(c, sp, &f.a));
         rts_post_all_launch(st, q, kr64, ka64, f);
     }
     RTS_HIP(hipGetLastError());
@@ -1284,7 +1284,7 @@ int rts_aggregate_device(RtsContext* c, int32_t max_path, int32_t max_rx, const 
         return RTS_ERR_UNSUPPORTED;
     }
     RtsAggScratch s;
-    { int rc = rts_agg_scratch(c, k, R, d_rows != nullptr, &s); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_agg_scratch(c, k, R, d_rows != nullptr, &s));
     size_t tmp = 0;
     const uint32_t small_cap = rts_small_cap(rts_agg_key64(k));
     const bool small = c->tune.post_small && !k.wide && R <= small_cap;       // one block orders, one block finishes (see k_agg_order_small)

@@ -137,7 +137,7 @@ extern "C" int rts_finalise_values(RtsHandle c, const double* power, const doubl
     if (!power || !doppler) { rts_set_error("rts_finalise_values: null array"); return RTS_ERR_INVALID; }
     return rts_finalise_bracket(c, [&]() -> int {
         RtsHostMirror& m = c->res.mirror;
-        if (!m.buf.p) { int rc = rts_mirror_reserve(c, RTS_SMALL_CAP32); if (rc != RTS_OK) return rc; }
+        if (!m.buf.p) RTS_TRY(rts_mirror_reserve(c, RTS_SMALL_CAP32));
         if (count <= m.cap) {
             // (the staging is free: what read it last -- this handle's previous pulse -- was waited for before this pulse was begun)
             memcpy(m.buf.p + m.o_vpower, power, sizeof(double) * count); memcpy(m.buf.p + m.o_vdoppler, doppler, sizeof(double) * count);
@@ -147,7 +147,7 @@ extern "C" int rts_finalise_values(RtsHandle c, const double* power, const doubl
         RTS_HIP(c->d_delay.reserve(count)); RTS_HIP(c->d_phase.reserve(count));
         RTS_HIP(hipMemcpyAsync(c->d_delay.p, power, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
         RTS_HIP(hipMemcpyAsync(c->d_phase.p, doppler, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
-        int rc = rts_post_set_values(c, c->d_delay.p, c->d_phase.p); if (rc != RTS_OK) return rc;
+        RTS_TRY(rts_post_set_values(c, c->d_delay.p, c->d_phase.p));
         RTS_HIP(hipStreamSynchronize(c->stream));
         return RTS_OK;
     });
@@ -192,14 +192,14 @@ static int rts_groups_home(RtsContext* c, const char* who) { CHECK_CLOSED(c); NE
 extern "C" int rts_group_count(RtsHandle c, uint32_t* count)
 {
     if (!c || !count) { rts_set_error("rts_group_count: null argument"); return RTS_ERR_INVALID; }
-    { int rc = rts_groups_home(c, "rts_group_count"); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_groups_home(c, "rts_group_count"));
     *count = (uint32_t)c->res.groups.size(); return RTS_OK;
 }
 
 extern "C" int rts_get_groups(RtsHandle c, RtsGroup* groups, uint32_t capacity)
 {
     if (!c || (!groups && capacity)) { rts_set_error("rts_get_groups: null argument"); return RTS_ERR_INVALID; }
-    { int rc = rts_groups_home(c, "rts_get_groups"); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_groups_home(c, "rts_get_groups"));
     if (capacity < c->res.groups.size()) { rts_set_error("rts_get_groups: capacity too small"); return RTS_ERR_CAPACITY; }
     if (!c->res.groups.empty()) memcpy(groups, c->res.groups.data(), sizeof(RtsGroup)*c->res.groups.size());
     return RTS_OK;

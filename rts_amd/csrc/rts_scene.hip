@@ -197,19 +197,19 @@ extern "C" int rts_set_scene(RtsHandle c, const RtsMesh* meshes, uint32_t n_targ
 {
     CHECK_HANDLE(c);
     CHECK_CLOSED(c);
-    { int rc = check_key_width(c->depth, n_targets, c->n_rx, "rts_set_scene"); if (rc != RTS_OK) return rc; }
+    RTS_TRY(check_key_width(c->depth, n_targets, c->n_rx, "rts_set_scene"));
     RtsSceneFlat flat;
-    { int rc = rts_scene_flatten(meshes, n_targets, c->params.interpolate_smooth, &flat); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_scene_flatten(meshes, n_targets, c->params.interpolate_smooth, &flat));
     std::unique_ptr<RtsScene> ns(new RtsScene()); ns->device = c->device;      // swapped in at the end: every failure path below leaves the handle's old scene alone
-    { int rc = scene_upload(c, ns.get(), flat); if (rc != RTS_OK) return rc; }
+    RTS_TRY(scene_upload(c, ns.get(), flat));
     const auto t_build0 = std::chrono::steady_clock::now();
     RtsSceneTuning st; st.device_build = (c->params.flags & RTS_FLAG_HOST_BUILD) == 0;
     rts_tuning_read(&st, rts_env);
-    { int rc = scene_build(c, ns.get(), meshes, flat, st); if (rc != RTS_OK) return rc; }
-    { int rc = scene_finish(c, ns.get(), st); if (rc != RTS_OK) return rc; }
+    RTS_TRY(scene_build(c, ns.get(), meshes, flat, st));
+    RTS_TRY(scene_finish(c, ns.get(), st));
     {   // the primitives' horizon (rts_horizon.hip): once per scene, like the order it is built along
         const auto t_hz0 = std::chrono::steady_clock::now();
-        int rc = rts_horizon_build(c, ns.get(), flat); if (rc != RTS_OK) return rc;
+        RTS_TRY(rts_horizon_build(c, ns.get(), flat));
         if (st.debug_build) fprintf(stderr, "[rts] horizon: %.2f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_hz0).count());
     }
     ns->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_build0).count();
@@ -232,7 +232,7 @@ extern "C" int rts_share_scene(RtsHandle dst, RtsHandle src)
     if (dst->scene == src->scene) return RTS_OK;
     rts_scene_unref(dst->scene);
     dst->scene = src->scene; dst->scene->refs++;
-    { int rc = rts_attach_scene(dst); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_attach_scene(dst));
     if (dst->tune.share_history && src->tune.share_history && dst->params.width == src->params.width) {      // ... and the tile-cost history of the scene's handles (RtsTileHist)
         rts_hist_unref(dst->hist);
         dst->hist = src->hist; dst->hist->refs++;

@@ -255,7 +255,7 @@ int rts_cube_track_tables(RtsContext* c)
 int rts_cube_track_device(RtsContext* c, const RtsTrackParams& p, double T, const RtsPlot* list, const uint32_t* n_dev, uint32_t pcap, uint32_t tcap)
 {
     RtsCubeState& s = c->cube;
-    { int rc = rts_cube_track_tables(c); if (rc != RTS_OK) return rc; }
+    RTS_TRY(rts_cube_track_tables(c));
     const uint32_t pcap1 = pcap ? pcap : 1u;
     const size_t n_scan = (size_t)tcap + pcap + 1;
     RTS_HIP(s.d_trk_pred.reserve(tcap)); RTS_HIP(s.d_trk_cd.reserve((size_t)tcap * RTS_TRACK_MAX_CAND)); RTS_HIP(s.d_trk_cj.reserve((size_t)tcap * RTS_TRACK_MAX_CAND));

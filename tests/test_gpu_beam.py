@@ -345,3 +345,29 @@ def test_errors_and_lifetime(rts):
     for call in (lambda: tr.cube_beamform(wts), lambda: tr.beam_map()):
         with pytest.raises(L.RtsError):
             call()
+
+
+def test_output_right_behind_the_last_cell_read(rts):
+    """the accepted neighbour of the two overlap refusals of test_errors_and_lifetime: the caller's output starts at the first byte behind
+    the last receiver's last cell read, inside the cube's own allocation: RTS_OK, the library-owned call's bytes, the sentinel behind it
+    and the cube untouched"""
+    from rts_amd import _lib as L
+    import torch
+    lib = L.lib()
+    rng = np.random.default_rng(41)
+    n_rx, n_p, nb, n_beams = 3, 4, 7, 2
+    inp = B.random_complex(rng, (n_rx, n_p, nb))
+    wts = np.ascontiguousarray(B.random_complex(rng, (n_beams, n_rx)))
+    block = torch.empty(inp.size + n_beams * n_p * nb + 1, dtype=torch.complex128, device="cuda")      # ONE allocation: [the cube | the caller's output | a sentinel]
+    block[:inp.size] = torch.from_numpy(inp.ravel()); block[inp.size:] = complex(7.25, -7.25)
+    torch.cuda.synchronize()
+    tr = rts.Tracer(8, 1)
+    tr.cube_attach(n_rx, n_p, nb, 0.0, 1.0, device_ptr=block.data_ptr())
+    owned = tr.cube_beamform(wts)
+    p = L.RtsBeamParams(); p.n_beams, p.source, p.weights = n_beams, L.RTS_BEAM_FROM_CUBE, wts.ctypes.data
+    assert lib.rts_cube_beamform(tr.h, C.byref(p), C.c_void_p(block.data_ptr() + 16 * inp.size)) == L.RTS_OK, lib.rts_last_error()
+    tr.cube()                                                                    # (drains the handle's stream)
+    after = host(block)
+    assert np.array_equal(bits(after[inp.size:-1]), bits(np.asarray(owned).ravel()))
+    assert after[-1] == complex(7.25, -7.25) and np.array_equal(bits(after[:inp.size]), bits(inp.ravel()))
+    tr.close()

@@ -296,6 +296,55 @@ def test_errors_and_lifetime(rts):
             call()
 
 
+def test_covariance_output_right_behind_the_last_cell_read(rts):
+    """the accepted neighbour of the stacked covariance's two overlap refusals of test_errors_and_lifetime: the caller's output starts at the
+    first byte behind the last receiver's last tap's last cell, inside the cube's own allocation: RTS_OK, the library-owned call's
+    bytes, the sentinel behind it and the cube untouched"""
+    from rts_amd import _lib as L
+    import torch
+    lib = L.lib()
+    rng = np.random.default_rng(41)
+    n_rx, n_p, nb, M = 3, 4, 7, 2
+    inp = B.random_complex(rng, (n_rx, n_p, nb))
+    block = torch.empty(inp.size + (n_rx * M) * (n_rx * M) + 1, dtype=torch.complex128, device="cuda")      # ONE allocation: [the cube | the caller's output | a sentinel]
+    block[:inp.size] = torch.from_numpy(inp.ravel()); block[inp.size:] = complex(7.25, -7.25)
+    torch.cuda.synchronize()
+    tr = rts.Tracer(8, 1)
+    tr.cube_attach(n_rx, n_p, nb, 0.0, 1.0, device_ptr=block.data_ptr())
+    owned = tr.cube_st_covariance(M)
+    p = L.RtsStCovParams(); p.n_taps = M
+    assert lib.rts_cube_st_covariance(tr.h, C.byref(p), C.c_void_p(block.data_ptr() + 16 * inp.size)) == L.RTS_OK, lib.rts_last_error()
+    tr.cube()                                                                    # (drains the handle's stream)
+    after = host(block)
+    assert np.array_equal(bits(after[inp.size:-1]), bits(np.asarray(owned).ravel()))
+    assert after[-1] == complex(7.25, -7.25) and np.array_equal(bits(after[:inp.size]), bits(inp.ravel()))
+    tr.close()
+
+
+def test_apply_output_right_behind_the_last_cell_read(rts):
+    """... and of the filter's: the last output row's last tap reads the last receiver's last row"""
+    from rts_amd import _lib as L
+    import torch
+    lib = L.lib()
+    rng = np.random.default_rng(43)
+    n_rx, n_p, nb, M, F = 3, 4, 7, 2, 2
+    inp = B.random_complex(rng, (n_rx, n_p, nb))
+    w = np.ascontiguousarray(B.random_complex(rng, (F, n_rx * M)))
+    block = torch.empty(inp.size + F * (n_p - M + 1) * nb + 1, dtype=torch.complex128, device="cuda")      # ONE allocation: [the cube | the caller's output | a sentinel]
+    block[:inp.size] = torch.from_numpy(inp.ravel()); block[inp.size:] = complex(7.25, -7.25)
+    torch.cuda.synchronize()
+    tr = rts.Tracer(8, 1)
+    tr.cube_attach(n_rx, n_p, nb, 0.0, 1.0, device_ptr=block.data_ptr())
+    owned = tr.cube_st_apply(w, M)
+    p = L.RtsStApplyParams(); p.n_taps, p.n_filters, p.weights = M, F, w.ctypes.data
+    assert lib.rts_cube_st_apply(tr.h, C.byref(p), C.c_void_p(block.data_ptr() + 16 * inp.size)) == L.RTS_OK, lib.rts_last_error()
+    tr.cube()                                                                    # (drains the handle's stream)
+    after = host(block)
+    assert np.array_equal(bits(after[inp.size:-1]), bits(np.asarray(owned).ravel()))
+    assert after[-1] == complex(7.25, -7.25) and np.array_equal(bits(after[:inp.size]), bits(inp.ravel()))
+    tr.close()
+
+
 # ----------------------------------------------------------------------------- 4. the whole chain
 def test_whole_chain(rts):
     """tests/stap_ref.py's scene on the device: noise, the stacked covariance without the target's bins, the weights, the filter --
