@@ -192,8 +192,8 @@ __global__ void __launch_bounds__(RTS_MVDR_THREADS) k_mvdr(const RtsMvdrArgs a)
     }
 }
 
-// cov: [n_rx][n_rx] on the device; steering: the call's rows on the device (rts_cube_api.hip uploads them on the stream before this:
-// RtsCubeState::mvdr_s); status: the word this call reports to
+// cov: [n_rx][n_rx] on the device; steering: the call's rows on the device (rts_cube_array_api.hip uploads them on the stream before this:
+// RtsCubeState::adapt.mvdr_s); status: the word this call reports to
 int rts_cube_mvdr_device(RtsContext* c, const RtsMvdrPlan& plan, uint32_t n_rx, uint32_t n_beams, double loading, const double* cov, const double* steering, uint32_t* status, double* out)
 {
     RtsMvdrArgs a;

@@ -1,4 +1,4 @@
-// rts_api.hip -- host side of librts_amd.so: the C-ABI of include/rts_amd.h but for the scene (rts_scene.hip), the cube (rts_cube_api.hip; rts_cube_reduce is here) and the accessors of a pulse's results (rts_results_api.hip).
+// rts_api.hip -- host side of librts_amd.so: the C-ABI of include/rts_amd.h but for the scene (rts_scene.hip), the cube (rts_cube_api.hip, rts_cube_detect_api.hip, rts_cube_array_api.hip; rts_cube_reduce is here) and the accessors of a pulse's results (rts_results_api.hip).
 //
 // Mirrors the host driver rs::RTS of the reference (ray_tracer.cpp:507-1364) from the point
 // where it owns device state: context set-up, per-pulse scene placement, launch, read-back,
@@ -115,8 +115,8 @@ void rts_hist_unref(RtsTileHist* h) { if (h && --h->refs == 0) delete h; }
 void rts_gate_unref(RtsGate* g) { if (g && --g->refs == 0) { if (g->tstream) (void)hipStreamDestroy(g->tstream); delete g; } }
 
 // The teardown of a handle, once.  After this body the members destroy themselves in reverse order of declaration: every DevBuf
-// (hipFree), the pinned blocks pin, pin_rx and the mirror's (hipHostFree) and the staged uploads (pat_rx and the cube's: cube.os_alpha, img_geo,
-// stft_win, range_win, beam_w: their event, then their blocks).  That is safe because no work can read
+// (hipFree), the pinned blocks pin, pin_rx and the mirror's (hipHostFree) and the staged uploads (pat_rx and the cube's, one per family that has a
+// table to send: cube.detect.os_alpha, cube.image.geo, cube.stft.win ...: their event, then their blocks), in the order rts_cube_state.h's grouping gives.  That is safe because no work can read
 // them any more: `stream` and `cstream` have been drained, the trace stream has been drained (it may live on with the other
 // handles of the link group, but carries no work of this handle), and nothing is enqueued on a handle's behalf anywhere else.
 RtsContext::~RtsContext()

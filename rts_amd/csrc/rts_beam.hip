@@ -80,7 +80,7 @@ template <int MODE> __global__ void __launch_bounds__(RTS_BEAM_THREADS) k_cube_b
 }
 
 // in: the source's receiver 0, row first_row (device); rx_stride: its n_rows_in n_bins; weights: the call's table on the device
-// (rts_cube_api.hip uploads it on the stream before this: RtsCubeState::beam_w)
+// (rts_cube_array_api.hip uploads it on the stream before this: RtsCubeState::beam.w)
 int rts_cube_beam_device(RtsContext* c, const RtsBeamParams& p, const RtsBeamPlan& plan, const double* in, uint64_t rx_stride, const double* weights, void* out)
 {
     RtsBeamArgs a;

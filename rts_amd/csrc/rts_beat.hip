@@ -103,7 +103,7 @@ int rts_cube_beat_device(RtsContext* c, uint32_t pulse_index, const RtsBeatParam
     a.part_len = plan.part_len; a.doppler = (p.flags & RTS_RENDER_DOPPLER) ? 1 : 0;
     a.cube = c->cube.p; a.n_pulses = q.n_pulses; a.n_bins = q.n_bins; a.pulse = pulse_index; a.t0 = q.t0; a.dt = q.dt;
     a.S = p.slope; a.T = p.duration; a.scratch = nullptr;
-    if (plan.scratch_doubles) { RTS_HIP(c->cube.d_beat_part.reserve(plan.scratch_doubles)); a.scratch = (double2*)c->cube.d_beat_part.p; }
+    if (plan.scratch_doubles) { RTS_HIP(c->cube.fmcw.d_beat_part.reserve(plan.scratch_doubles)); a.scratch = (double2*)c->cube.fmcw.d_beat_part.p; }
     dim3 grid(plan.tiles, q.n_rx, plan.P);
     k_cube_beat<<<grid, RTS_BEAT_THREADS, 0, c->stream>>>(a, c->res.recv_dev);
     RTS_HIP(hipGetLastError());
@@ -168,7 +168,7 @@ __global__ void __launch_bounds__(RTS_RANGE_THREADS) k_cube_range(const RtsRange
     }
 }
 
-// window: the call's taper on the device (rts_cube_api.hip uploads it on the stream before this: RtsCubeState::range_win) or NULL
+// window: the call's taper on the device (rts_cube_api.hip uploads it on the stream before this: RtsCubeState::fmcw.range_win) or NULL
 int rts_cube_range_device(RtsContext* c, const RtsRangeParams& p, const RtsRangePlan& plan, const double* window, double* out)
 {
     const RtsCubeParams& q = c->cube.params;

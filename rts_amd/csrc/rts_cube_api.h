@@ -1,4 +1,4 @@
-// rts_cube_api.h -- what the entry points of the cube part of the C-ABI share (rts_cube_api.hip): the argument checks that more
+// rts_cube_api.h -- what the entry points of the cube part of the C-ABI share (rts_cube_api.hip, rts_cube_detect_api.hip, rts_cube_array_api.hip): the argument checks that more
 // than one of them applies, each forming the message of the entry point `who` from the rules of rts_cube_args.h; where a call reads
 // from; how a product or a counted list comes home.  Internal: no kernels, nothing of this is exported.
 #pragma once
@@ -95,9 +95,9 @@ static inline int rts_device_source(RtsContext* c, const char* who, uint32_t sou
 {
     *src = c->cube.p; *rows = c->cube.params.n_pulses;
     if (source == RTS_BEAM_FROM_MAP) {
-        const RtsCubeProduct& m = c->cube.doppler;
+        const RtsCubeProduct& m = c->cube.doppler.map;
         if (!m.valid || !m.own.p || m.p != m.own.p) { rts_set_error("%s: RTS_BEAM_FROM_MAP: no library-owned map (rts_cube_doppler with device_out NULL)", who); return RTS_ERR_INVALID; }
-        *src = m.p; *rows = c->cube.doppler_n;
+        *src = m.p; *rows = c->cube.doppler.n_fft;
     } else if (source == RTS_BEAM_FROM_POINTER) {
         if (!device_in) { rts_set_error("%s: null device_in with RTS_BEAM_FROM_POINTER", who); return RTS_ERR_INVALID; }
         *src = (const double*)device_in; *rows = n_rows_in;
@@ -138,8 +138,8 @@ static inline int rts_cfar_map(RtsContext* c, const char* who, const void* devic
         if (*n_doppler == 0) { rts_set_error("%s: n_doppler = 0 with a caller map", who); return RTS_ERR_INVALID; }
         if ((uintptr_t)*map & 15u) { rts_set_error("%s: device_map is not 16-byte aligned", who); return RTS_ERR_INVALID; }
     } else {
-        if (!c->cube.doppler.valid) { rts_set_error("%s: no map (call rts_cube_doppler first, or pass device_map)", who); return RTS_ERR_INVALID; }
-        *map = c->cube.doppler.p; *n_doppler = c->cube.doppler_n;
+        if (!c->cube.doppler.map.valid) { rts_set_error("%s: no map (call rts_cube_doppler first, or pass device_map)", who); return RTS_ERR_INVALID; }
+        *map = c->cube.doppler.map.p; *n_doppler = c->cube.doppler.n_fft;
     }
     return RTS_OK;
 }

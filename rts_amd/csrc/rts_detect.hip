@@ -124,7 +124,7 @@ static int rts_cfar_launch(RtsContext* c, const char* who, const Params& p, cons
                            void (*k_count)(Args), void (*k_write)(Args), uint32_t rule_rows)
 {
     const RtsCubeParams& q = c->cube.params;
-    RtsCubeState& s = c->cube;
+    RtsDetectState& s = c->cube.detect;
     RtsCfarFrame& f = a.f;
     f.map = (const double2*)map; f.nd = n_doppler; f.nb = q.n_bins; f.n_rt = (q.n_bins + RTS_CFAR_TR - 1) / RTS_CFAR_TR;
     f.w = rts_cfar_window(p.guard_range, p.guard_doppler, p.train_range, p.train_doppler);
@@ -132,19 +132,19 @@ static int rts_cfar_launch(RtsContext* c, const char* who, const Params& p, cons
     const size_t n_seg = (size_t)q.n_rx * n_doppler * f.n_rt;
     if (n_seg + 1 > 0xffffffffull) { rts_set_error("%s: %zu segments: the map is too large", who, n_seg); return RTS_ERR_INVALID; }
     f.n_seg = (uint32_t)n_seg; f.max_det = max_det;
-    RTS_HIP(s.d_det_cnt.reserve(n_seg + 1)); RTS_HIP(s.d_det_off.reserve(n_seg + 1)); RTS_HIP(s.d_det.reserve(max_det));
+    RTS_HIP(s.d_cnt.reserve(n_seg + 1)); RTS_HIP(s.d_off.reserve(n_seg + 1)); RTS_HIP(s.d_list.reserve(max_det));
     size_t tmp = 0;
-    RTS_HIP(rocprim::exclusive_scan(nullptr, tmp, s.d_det_cnt.p, s.d_det_off.p, 0u, n_seg + 1, rocprim::plus<uint32_t>(), c->stream));
-    RTS_HIP(s.d_det_tmp.reserve(tmp + 1));
-    f.cnt = s.d_det_cnt.p; f.off = s.d_det_off.p; f.out = s.d_det.p;
+    RTS_HIP(rocprim::exclusive_scan(nullptr, tmp, s.d_cnt.p, s.d_off.p, 0u, n_seg + 1, rocprim::plus<uint32_t>(), c->stream));
+    RTS_HIP(s.d_tmp.reserve(tmp + 1));
+    f.cnt = s.d_cnt.p; f.off = s.d_off.p; f.out = s.d_list.p;
     const size_t lds = sizeof(double) * (size_t)(RTS_CFAR_TD + 2 * f.w.hd + rule_rows) * (RTS_CFAR_TR + 2 * f.w.hr);      // P and the rule's rows: <= 60 KiB
     dim3 grid(f.n_rt, (n_doppler + RTS_CFAR_TD - 1) / RTS_CFAR_TD, q.n_rx);
     k_count<<<grid, RTS_CFAR_THREADS, lds, c->stream>>>(a);
     RTS_HIP(hipGetLastError());
-    RTS_HIP(rocprim::exclusive_scan(s.d_det_tmp.p, tmp, s.d_det_cnt.p, s.d_det_off.p, 0u, n_seg + 1, rocprim::plus<uint32_t>(), c->stream));
+    RTS_HIP(rocprim::exclusive_scan(s.d_tmp.p, tmp, s.d_cnt.p, s.d_off.p, 0u, n_seg + 1, rocprim::plus<uint32_t>(), c->stream));
     k_write<<<grid, RTS_CFAR_THREADS, lds, c->stream>>>(a);
     RTS_HIP(hipGetLastError());
-    s.det_nseg = (uint32_t)n_seg; s.det_max = max_det; s.det_nd = n_doppler; s.det_valid = true;
+    s.nseg = (uint32_t)n_seg; s.max = max_det; s.nd = n_doppler; s.valid = true;
     return RTS_OK;
 }
 

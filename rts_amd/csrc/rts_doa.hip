@@ -160,7 +160,7 @@ __global__ void __launch_bounds__(RTS_DOA_THREADS) k_doa_scan(const RtsDoaArgs a
 }
 
 // steering: [n][n_dirs] on the device; vectors: the first of the m rows of a table [.][n] on the device; g: [m] on the device
-// (rts_cube_api.hip uploads it on the stream before this: RtsCubeState::doa_g)
+// (rts_cube_array_api.hip uploads it on the stream before this: RtsCubeState::doa.g)
 int rts_cube_doa_scan_device(RtsContext* c, const RtsDoaScanPlan& plan, uint32_t n, uint32_t m, uint64_t n_dirs, uint32_t flags, const double* steering, const double* vectors,
                              const double* g, double* out)
 {

@@ -71,9 +71,9 @@ static unsigned rts_focus_stride_grid(size_t total) { const size_t b = (total + 
 int rts_cube_align_device(RtsContext* c, const RtsAlignParams& p, const RtsAlignPlan& plan, double* out)
 {
     const RtsCubeParams& q = c->cube.params;
-    RTS_HIP(c->cube.d_focus_env.reserve(plan.env_doubles));
-    RTS_HIP(c->cube.d_focus_ref.reserve(plan.ref_doubles));
-    double* env = c->cube.d_focus_env.p; double* ref = c->cube.d_focus_ref.p;
+    RTS_HIP(c->cube.focus.d_env.reserve(plan.env_doubles));
+    RTS_HIP(c->cube.focus.d_ref.reserve(plan.ref_doubles));
+    double* env = c->cube.focus.d_env.p; double* ref = c->cube.focus.d_ref.p;
     RTS_HIP(hipMemsetAsync(out, 0, sizeof(double) * plan.out_doubles, c->stream));
     k_focus_envelope<<<rts_focus_stride_grid(plan.env_doubles), RTS_FOCUS_THREADS, 0, c->stream>>>((const double2*)c->cube.p, env, q.n_rx, q.n_pulses, q.n_bins, p.first_pulse, p.n_pulses);
     RTS_HIP(hipGetLastError());
@@ -223,17 +223,17 @@ int rts_cube_pga_device(RtsContext* c, const RtsPgaParams& p, const RtsPgaPlan& 
     const RtsCubeParams& q = c->cube.params;
     const uint32_t N = p.n_pulses;
     const size_t n_rows = (size_t)q.n_rx * N;
-    RTS_HIP(c->cube.d_pga_part.reserve(plan.partial_doubles));
-    RTS_HIP(c->cube.d_pga_sum.reserve(2 * n_rows));
-    RTS_HIP(c->cube.d_pga_rot.reserve(2 * n_rows));
+    RTS_HIP(c->cube.focus.d_pga_part.reserve(plan.partial_doubles));
+    RTS_HIP(c->cube.focus.d_pga_sum.reserve(2 * n_rows));
+    RTS_HIP(c->cube.focus.d_pga_rot.reserve(2 * n_rows));
     double* phi = out; double* rms = out + n_rows;
-    double2* rot = (double2*)c->cube.d_pga_rot.p;
+    double2* rot = (double2*)c->cube.focus.d_pga_rot.p;
     RtsPgaArgs a;
     a.cube = (const double2*)c->cube.p; a.n_pulses_cube = q.n_pulses; a.n_bins_cube = q.n_bins;
     a.first_pulse = p.first_pulse; a.first_bin = p.first_bin; a.n_gate = plan.n_gate; a.N = N; a.logN = plan.logN;
     a.BT = plan.BT; a.passes = plan.passes; a.tiles = plan.tiles; a.W = plan.window0;
-    a.rot = rot; a.partial = (double2*)c->cube.d_pga_part.p;
-    const double2* A = plan.tiles > 1u ? (const double2*)c->cube.d_pga_sum.p : a.partial;
+    a.rot = rot; a.partial = (double2*)c->cube.focus.d_pga_part.p;
+    const double2* A = plan.tiles > 1u ? (const double2*)c->cube.focus.d_pga_sum.p : a.partial;
     RTS_HIP(hipFuncSetAttribute((const void*)k_pga_tile, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
     k_pga_init<<<(unsigned)((n_rows + 255) / 256), 256, 0, c->stream>>>(phi, rot, n_rows);
     RTS_HIP(hipGetLastError());
@@ -242,7 +242,7 @@ int rts_cube_pga_device(RtsContext* c, const RtsPgaParams& p, const RtsPgaPlan& 
         k_pga_tile<<<grid, RTS_FOCUS_THREADS, plan.lds, c->stream>>>(a);
         RTS_HIP(hipGetLastError());
         if (plan.tiles > 1u) {
-            k_pga_sum_tiles<<<(unsigned)((n_rows + 255) / 256), 256, 0, c->stream>>>(a.partial, (double2*)c->cube.d_pga_sum.p, n_rows, N, plan.tiles);
+            k_pga_sum_tiles<<<(unsigned)((n_rows + 255) / 256), 256, 0, c->stream>>>(a.partial, (double2*)c->cube.focus.d_pga_sum.p, n_rows, N, plan.tiles);
             RTS_HIP(hipGetLastError());
         }
         k_pga_update<<<q.n_rx, RTS_FOCUS_THREADS, 0, c->stream>>>(A, phi, rot, rms, N, p.n_iters, it);
@@ -295,9 +295,9 @@ int rts_cube_correct_device(RtsContext* c, const RtsCorrectParams& p, const RtsC
     a.n_pulses_cube = q.n_pulses; a.n_bins = q.n_bins; a.first_pulse = p.first_pulse; a.P = p.n_pulses; a.taps = p.taps; a.tiles = plan.tiles;
     a.shifts = shifts; a.phase = phase;
     if (shifts) {
-        RTS_HIP(c->cube.d_focus_rows.reserve(plan.scratch_doubles));
-        a.rows = c->cube.d_focus_rows.p;
-        k_focus_copy_rows<<<rts_focus_stride_grid(plan.scratch_doubles / 2), RTS_FOCUS_THREADS, 0, c->stream>>>((const double2*)c->cube.p, (double2*)c->cube.d_focus_rows.p, q.n_rx, q.n_pulses, q.n_bins,
+        RTS_HIP(c->cube.focus.d_rows.reserve(plan.scratch_doubles));
+        a.rows = c->cube.focus.d_rows.p;
+        k_focus_copy_rows<<<rts_focus_stride_grid(plan.scratch_doubles / 2), RTS_FOCUS_THREADS, 0, c->stream>>>((const double2*)c->cube.p, (double2*)c->cube.focus.d_rows.p, q.n_rx, q.n_pulses, q.n_bins,
                                                                                                                  p.first_pulse, p.n_pulses);
         RTS_HIP(hipGetLastError());
     }

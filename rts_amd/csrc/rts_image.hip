@@ -67,7 +67,7 @@ __global__ void __launch_bounds__(256) k_backproject_sum(const double2* __restri
     out[i] = s;
 }
 
-// geo: the call's [tx | rx | w] block on the device (rts_cube_api.hip uploads it on the stream before this: RtsCubeState::img_geo)
+// geo: the call's [tx | rx | w] block on the device (rts_cube_api.hip uploads it on the stream before this: RtsCubeState::image.geo)
 int rts_cube_backproject_device(RtsContext* c, const RtsImageParams& p, const RtsImagePlan& plan, const double* geo, double* out)
 {
     const RtsCubeParams& q = c->cube.params;
@@ -80,7 +80,7 @@ int rts_cube_backproject_device(RtsContext* c, const RtsImageParams& p, const Rt
     a.cspeed = p.cspeed; a.carrier = p.carrier;
     a.tx = geo; a.rx = geo + 3 * (size_t)p.n_pulses; a.w = a.rx + 3 * (size_t)q.n_rx * p.n_pulses;
     a.out = (double2*)out; a.scratch = nullptr;
-    if (plan.split) { RTS_HIP(c->cube.d_img_scratch.reserve(2 * plan.scratch)); a.scratch = (double2*)c->cube.d_img_scratch.p; }
+    if (plan.split) { RTS_HIP(c->cube.image.d_scratch.reserve(2 * plan.scratch)); a.scratch = (double2*)c->cube.image.d_scratch.p; }
     dim3 grid(plan.tiles_x * plan.tiles_y, plan.split ? plan.n_chunks : 1u, q.n_rx);
     k_backproject<<<grid, RTS_IMAGE_TILE, 0, c->stream>>>(a);
     RTS_HIP(hipGetLastError());

@@ -26,6 +26,7 @@
 #include "rts_source.h"           // clutter and jammer sources: pole, scale, draw, recursion, partials and tree, the validation, the host evaluator and the host-only plan of the launch
 #include "rts_plot.h"             // plot extraction: key, unwrap, adjacency, neighbour intervals, the blocked sums, the record, the validation, the host evaluator
 #include "rts_owned.h"            // DevBuf, PinBuf, StagedUpload: device and pinned host memory that frees itself
+#include "rts_cube_state.h"       // RtsCubeProduct, RtsCubeState: the cube part of a handle, one record per family of entry points
 #include "rts_launch_plan.h"      // RTS_BLOCK, RTS_WTILE, RTS_COOP_GROUP, RTS_STACK_OVF and the host arithmetic of a launch
 #include "rts_post_plan.h"        // RTS_SMALL_CAP32 / 64, RTS_AGG_TILE and the host arithmetic of the post-processing
 #include "rts_pulse_state.h"      // RtsPulseState: IDLE / OPEN / CHAINED, and the only code that moves the per-device count of open pulses
@@ -101,9 +102,6 @@ static_assert(sizeof(RtsPlot) == 104 && sizeof(RtsPlotParams) == 56, "plot ABI s
 static_assert(sizeof(RtsTrack) == 88 && sizeof(RtsTrackParams) == 96, "track ABI sizes (rts_amd/_lib.py mirrors them)");
 static_assert(sizeof(RtsTbdParams) == 72 && sizeof(RtsTbdExtractParams) == 40 && sizeof(RtsTbdTrack) == 48, "track-before-detect ABI sizes (rts_amd/_lib.py mirrors them)");
 static_assert(sizeof(RtsSourceParams) == 72, "source ABI size (rts_amd/_lib.py mirrors it)");
-// what the device keeps beside each of the two track tables: the next id, the records stored, the total a table without end would
-// hold (stored + the new tracks turned away), the rounds the matching took
-struct RtsTrackMeta { uint64_t next_id; uint32_t n, total, rounds, reserved; };
 // RtsEndRecord::pad : bits 0-1 chain (output row = chain * n + slot), 2-3 refrDepth, 8-15 (target + 1) of chain 0's
 // refraction (path prefill of rows >= 3), 16-17 children spawned
 
@@ -303,112 +301,6 @@ struct RtsHostMirror {
 // rts_aggregate enqueues; the table is read (stream wait + pinned block -> RtsGroup records) by the first call that needs it
 struct RtsAggPending { bool valid = false, rows = false; uint32_t R = 0, D = 0, spec = 0; RtsKeyPlan key = {}; uint64_t base = 0; double* gsum = nullptr; };
 
-// A derived output of the attached cube (Doppler map, image, spectrogram): `own` when the library allocates it, p / doubles: where the
-// last one went and its size; valid: it is a product of the ATTACHED cube, for its rts_cube_*_get -- every product ends at rts_cube_attach
-// (RtsCubeState::end_products).  The image and the spectrogram are recorded only when library-owned (a caller-owned
-// output leaves the record alone), the Doppler map also when caller-owned (rts_cube_detect without a map takes it).
-struct RtsCubeProduct {
-    DevBuf<double> own; double* p = nullptr; size_t doubles = 0; bool valid = false;
-    // where a call's n doubles go: the caller's memory, or `own` made large enough.  A regrow frees the block a record may name: the record
-    // ends BEFORE it, so a call that fails after this (the reserve itself, a staged upload) leaves no getter a freed address
-    hipError_t place(void* device_out, size_t n, double** out)
-    {
-        *out = (double*)device_out; if (*out) return hipSuccess;
-        if (n > own.cap) { p = nullptr; doubles = 0; valid = false; }
-        const hipError_t e = own.reserve(n); *out = own.p; return e;
-    }
-    void record(double* out, size_t n) { p = out; doubles = n; valid = true; }
-};
-
-// The cube part of a handle: it shares nothing with the pulse path but the handle (rts_cube_api.hip; the launchers of rts_render.hip,
-// rts_stft.hip, rts_beat.hip, rts_detect.hip, rts_image.hip).
-struct RtsCubeState {
-    RtsCubeParams params = {}; double* p = nullptr; DevBuf<double> own; bool set = false;      // p: the attached cube, own when the library allocated it
-    DevBuf<double> d_wave; uint32_t wave_M = 0, wave_L = 0; bool wave_set = false;         // the transmit waveform (rts_cube_set_waveform): M interleaved samples, L taps
-    RtsCubeProduct doppler; uint32_t doppler_n = 0;       // slow-time transform of the cube (rts_cube_doppler) and its n_fft
-    // CFAR detection (rts_cube_detect, rts_detect.hip): per-segment counts -> exclusive scan (offsets; element n_seg: the total),
-    // the records of the last detection and how many it may hold; det_valid: a list exists for rts_cube_detections_get
-    DevBuf<uint32_t> d_det_cnt, d_det_off; DevBuf<uint8_t> d_det_tmp; DevBuf<RtsDetection> d_det; uint32_t det_nseg = 0, det_max = 0; bool det_valid = false;
-    uint32_t det_nd = 0;                                  // the Doppler rows of the map the list was detected on (rts_cube_plots without a list of its own)
-    // plot extraction (rts_cube_plots, rts_plot.hip): flat keys, the parent array of the union (afterwards every element's component
-    // minimum), the identity, (label, index) sorted by label, per head its member count, keep flags -> exclusive scan (offsets;
-    // element plot_cap: the total), the sort's and the scan's scratch, the records.  plot_cap: the list capacity the launches were
-    // sized by, plot_max: the records d_plot may hold; plot_valid: plots exist for rts_cube_plots_get; plot_own_list: they were made
-    // from the handle's detection list (whose truncation rts_cube_plots_get reports)
-    DevBuf<uint64_t> d_plot_key; DevBuf<uint32_t> d_plot_parent, d_plot_idx, d_plot_lab_s, d_plot_idx_s, d_plot_len, d_plot_flag, d_plot_off; DevBuf<uint8_t> d_plot_tmp;
-    DevBuf<RtsPlot> d_plot; uint32_t plot_cap = 0, plot_max = 0; bool plot_valid = false, plot_own_list = false;
-    // tracking (rts_cube_track, rts_track.hip): TWO tables of RTS_TRACK_MAX_TRACKS records and their RtsTrackMeta -- a step reads
-    // table trk_cur and writes the other -- the predictions, the plots' four fields, per track its candidates (entry k of track i at
-    // [k * table size + i]), their count, its plot and that edge's d2, per plot its track and the round's minimum (d2 bits, track), the
-    // rounds, the flags over [tracks | plots | 1] -> exclusive scan, the scan's scratch.  NOT a product of the cube: end_products()
-    // leaves them alone.  trk_max: the table size the previous step ran with (0: the next step chooses); trk_live: the table has a time
-    DevBuf<RtsTrack> d_trk[2]; DevBuf<RtsTrackMeta> d_trk_meta; DevBuf<RtsTrackPred> d_trk_pred;
-    DevBuf<double> d_trk_zd, d_trk_zf, d_trk_pw, d_trk_cd, d_trk_md2; DevBuf<uint64_t> d_trk_best_d;
-    DevBuf<uint32_t> d_trk_zrx, d_trk_cj, d_trk_cn, d_trk_of_track, d_trk_of_plot, d_trk_best_t, d_trk_rounds, d_trk_flag, d_trk_off; DevBuf<uint8_t> d_trk_tmp;
-    uint32_t trk_cur = 0, trk_max = 0, trk_loaded = 0; bool trk_live = false; double trk_time = 0.0;
-    // track-before-detect (rts_cube_tbd_step, rts_cube_tbd_extract, rts_tbd.hip): TWO merit maps -- a step reads tbd_cur and writes the
-    // other -- the ring of tbd_depth pointer maps and of their shift tables (frame f in slot f mod depth), all of the shape and
-    // window the first step after a reset fixed (tbd_frames == 0: no state); the time, and t0 and dt, of the last frame.  The
-    // extraction: per segment of 64 cells its candidates' count -> exclusive scan (offsets; element tbd_ext_nseg: the total), the
-    // scan's scratch, the records and their paths.  NOT a product of the cube: end_products() leaves all of it alone.
-    DevBuf<double> d_tbd_merit[2]; DevBuf<uint8_t> d_tbd_ptr, d_tbd_tmp; DevBuf<int32_t> d_tbd_shift;
-    DevBuf<uint32_t> d_tbd_cnt, d_tbd_off, d_tbd_paths; DevBuf<RtsTbdTrack> d_tbd_out;
-    uint32_t tbd_rx = 0, tbd_nd = 0, tbd_nb = 0, tbd_depth = 0, tbd_hd = 0, tbd_hr = 0, tbd_cur = 0; uint64_t tbd_frames = 0;
-    double tbd_time = 0.0, tbd_t0 = 0.0, tbd_dt = 0.0;
-    uint32_t tbd_ext_nseg = 0, tbd_ext_max = 0, tbd_ext_depth = 0; bool tbd_ext_valid = false;
-    // OS-CFAR (rts_cube_detect_os): the alphas by training count go through a staged upload; os_tab keeps them on the host for the next
-    // call with the same window, rank and pfa (os_tab_key), so that only training counts not seen yet are solved for; os_tab_sent: the
-    // device holds os_tab as it stands
-    StagedUpload<double> os_alpha; std::vector<double> os_tab; uint32_t os_tab_key[5] = {0, 0, 0, 0, 0}; double os_tab_pfa = 0.0; bool os_tab_sent = false;
-    // backprojection (rts_cube_backproject, rts_image.hip): the image and its shape, for rts_cube_image_get / RTS_IMAGE_ACCUMULATE; the
-    // call's geometry [tx | rx | w] goes through a staged upload; the chunk sums of a split launch
-    RtsCubeProduct image; uint32_t img_nx = 0, img_ny = 0;
-    StagedUpload<double> img_geo; DevBuf<double> d_img_scratch;
-    // spectrogram (rts_cube_spectrogram, rts_stft.hip): the output, for rts_cube_spectrogram_get; the call's window goes through a
-    // staged upload; the tile sums of RTS_STFT_SUM_BINS
-    RtsCubeProduct stft;
-    StagedUpload<double> stft_win; DevBuf<double> d_stft_part;
-    // FMCW (rts_beat.hip): the part sums of a beat render (rts_cube_render_beat); the range transform's output
-    // (rts_cube_range_transform), for rts_cube_range_get, and its staged window
-    DevBuf<double> d_beat_part;
-    RtsCubeProduct range;
-    StagedUpload<double> range_win;
-    // beamforming (rts_cube_beamform, rts_beam.hip): the output, for rts_cube_beam_get; the call's weight table goes through a staged upload
-    RtsCubeProduct beam;
-    StagedUpload<double> beam_w;
-    // clutter and jammer sources (rts_cube_add_sources, rts_source.hip): the call's table (rts_src_table) goes through a staged upload;
-    // the call changes the cube in place, so there is no product
-    StagedUpload<double> src_tab;
-    // adaptive beamforming (rts_cube_covariance, rts_cube_mvdr, rts_adapt.hip): the covariance and its n_rx, for rts_cube_covariance_get
-    // and rts_cube_mvdr without device_cov, and the parts' partial sums; the weights, for rts_cube_mvdr_get; the call's steering rows go
-    // through a staged upload; the solves' status words (0: library-owned output, 1: caller-owned)
-    RtsCubeProduct cov; uint32_t cov_n = 0; DevBuf<double> d_cov_part;
-    RtsCubeProduct mvdr;
-    StagedUpload<double> mvdr_s; DevBuf<uint32_t> d_mvdr_status;
-    // space-time adaptive processing (rts_cube_st_covariance: `cov` above, of order n_taps n_rx; rts_cube_st_apply, rts_stap.hip): the
-    // filter's output, for rts_cube_st_get; the call's weight table goes through a staged upload
-    RtsCubeProduct st;
-    StagedUpload<double> st_w;
-    // direction finding (rts_cube_eig, rts_cube_doa_scan, rts_doa.hip): the eigenvalues and the eigenvectors and their order, for
-    // rts_cube_eig_get and rts_cube_doa_scan without device_vectors; the solves' status words (0: library-owned outputs, 1: caller-owned);
-    // the spectrum, for rts_cube_doa_get; the call's g goes through a staged upload of one size (RTS_BEAM_MAX_RX doubles)
-    RtsCubeProduct eig_val, eig_vec; uint32_t eig_n = 0; DevBuf<uint32_t> d_eig_status;
-    RtsCubeProduct doa;
-    StagedUpload<double> doa_g;
-    // autofocus (rts_cube_align, rts_cube_pga, rts_cube_correct, rts_focus.hip): the shift table and the phase table (phase, then the
-    // iterations' rms) with the row ranges they were made for, for their getters and RTS_CORRECT_USE_ALIGN / RTS_CORRECT_USE_PGA; the
-    // rows' envelopes and the reference; the PGA's tile sums, their sums and the rotations; the correction's copy of the rows; a
-    // correction's host tables [shifts | phase] go through a staged upload
-    RtsCubeProduct align; uint32_t align_first = 0, align_P = 0;
-    RtsCubeProduct pga; uint32_t pga_first = 0, pga_P = 0, pga_iters = 0;
-    DevBuf<double> d_focus_env, d_focus_ref, d_pga_part, d_pga_sum, d_pga_rot, d_focus_rows;
-    StagedUpload<double> focus_tab;
-    // every product belongs to the cube it was made from: the Doppler map (which rts_cube_detect may take), the detection list, the image
-    // the spectrogram, the range transform, the beams, the covariance, the adaptive weights, the space-time filter's output, the eigenpairs and the angular spectrum end when another cube is attached
-    void end_products() { doppler.valid = false; det_valid = false; plot_valid = false; image.valid = false; stft.valid = false; range.valid = false; beam.valid = false; cov.valid = false; mvdr.valid = false; st.valid = false;
-                          eig_val.valid = false; eig_vec.valid = false; doa.valid = false; align.valid = false; pga.valid = false; }
-};
-
 // What a pulse leaves for its accessors (rts_results_api.hip; the finalisers, the aggregation and the end-of-pulse chains of rts_api.hip; the
 // launchers of rts_post.hip / rts_render.hip read n_recv / recv_dev).  The device buffers the results live in stay on the handle.
 struct RtsPulseResults {
@@ -486,7 +378,7 @@ struct RtsContext {
     uint64_t recv_hint = 0; bool recv_hint_valid = false;                    // received rays of the handle's previous pulse
     RtsPulseResults res;                // what the last pulse left for its accessors (rts_results_api.hip)
     PinBuf<RtsRxDev> pin_rx; std::vector<RtsRxDev> rx_host;      // receivers: last values set (an unchanged set is not uploaded again) and the pinned staging of the asynchronous upload
-    RtsCubeState cube;                  // the complex return cube and what is derived from it (rts_cube_api.hip)
+    RtsCubeState cube;                  // the complex return cube and what is derived from it, by family (rts_cube_state.h; the three rts_cube*_api.hip units)
     PinBuf<RtsPinned> pin;      // pinned host staging (one RtsPinned) and its address on the device (pin.dev): kernels write the small per-pulse read-backs (counters, group table) straight into it
     bool rcs_uploaded = false; DevBuf<double> d_rcsval; int n_cu = 0; bool stats_pending = false;
     RtsStats stats;
@@ -587,7 +479,7 @@ int rts_debug_stage(RtsContext* c, const char* name);
 // ... and the library's own status: what is not RTS_OK is the caller's return value (the callee has set the message)
 #define RTS_TRY(expr) do { const int rc_ = (expr); if (rc_ != RTS_OK) return rc_; } while (0)
 
-// every entry point that takes a handle (rts_api.hip, rts_cube_api.hip) makes its device current ...
+// every entry point that takes a handle (rts_api.hip, the three rts_cube*_api.hip units) makes its device current ...
 #define CHECK_HANDLE(c) do { if (!(c)) { rts_set_error("null handle"); return RTS_ERR_INVALID; } RTS_HIP(hipSetDevice((c)->device)); } while (0)
 // ... and those that consume a pulse's results, or replace what its enqueued work reads, settle the handle's pulse first: an OPEN one is
 // ended (rts_trace_pulse_end), a CHAINED one resolved (rts_api.hip)

@@ -153,7 +153,7 @@ RTS_HD RtsPlot rts_plot_record(const RtsDetection& root, uint32_t first_index, u
     return p;
 }
 
-// ---- validation.  The parameter record: 0, or the number of the rule it breaks (rts_cube_api.hip words the message)
+// ---- validation.  The parameter record: 0, or the number of the rule it breaks (rts_cube_detect_api.hip words the message)
 //   1 link_range  2 link_doppler  3 reserved  4 pri  5 device_list with n_doppler = 0  6 device_list not 8-byte aligned
 //   7 n_list or n_doppler without device_list
 RTS_HD int rts_plot_params_check(const RtsPlotParams* p)

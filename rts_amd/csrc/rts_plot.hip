@@ -164,23 +164,23 @@ __global__ void __launch_bounds__(RTS_PLOT_THREADS) k_plot_reduce(const RtsPlotA
 
 int rts_cube_plots_device(RtsContext* c, const RtsPlotParams& p, const RtsDetection* list, const uint32_t* n_dev, uint32_t n_cap, uint32_t n_doppler, uint32_t max_plots)
 {
-    RtsCubeState& s = c->cube;
-    const RtsCubeParams& q = s.params;
+    RtsPlotState& s = c->cube.plot;
+    const RtsCubeParams& q = c->cube.params;
     const uint32_t cap = n_cap ? n_cap : 1u;
-    RTS_HIP(s.d_plot_key.reserve(cap)); RTS_HIP(s.d_plot_parent.reserve(cap)); RTS_HIP(s.d_plot_idx.reserve(cap)); RTS_HIP(s.d_plot_lab_s.reserve(cap));
-    RTS_HIP(s.d_plot_idx_s.reserve(cap)); RTS_HIP(s.d_plot_len.reserve(cap)); RTS_HIP(s.d_plot_flag.reserve((size_t)cap + 1)); RTS_HIP(s.d_plot_off.reserve((size_t)cap + 1));
-    RTS_HIP(s.d_plot.reserve(max_plots ? max_plots : 1u));
+    RTS_HIP(s.d_key.reserve(cap)); RTS_HIP(s.d_parent.reserve(cap)); RTS_HIP(s.d_idx.reserve(cap)); RTS_HIP(s.d_lab_s.reserve(cap));
+    RTS_HIP(s.d_idx_s.reserve(cap)); RTS_HIP(s.d_len.reserve(cap)); RTS_HIP(s.d_flag.reserve((size_t)cap + 1)); RTS_HIP(s.d_off.reserve((size_t)cap + 1));
+    RTS_HIP(s.d_list.reserve(max_plots ? max_plots : 1u));
     unsigned bits = 1; while (bits < 32u && (cap >> bits) != 0u) bits++;      // labels and the padding value are at most cap
     size_t tmp_sort = 0, tmp_scan = 0;
-    RTS_HIP(rocprim::radix_sort_pairs(nullptr, tmp_sort, s.d_plot_parent.p, s.d_plot_lab_s.p, s.d_plot_idx.p, s.d_plot_idx_s.p, (size_t)cap, 0u, bits, c->stream));
-    RTS_HIP(rocprim::exclusive_scan(nullptr, tmp_scan, s.d_plot_flag.p, s.d_plot_off.p, 0u, (size_t)cap + 1, rocprim::plus<uint32_t>(), c->stream));
-    RTS_HIP(s.d_plot_tmp.reserve((tmp_sort > tmp_scan ? tmp_sort : tmp_scan) + 1));
+    RTS_HIP(rocprim::radix_sort_pairs(nullptr, tmp_sort, s.d_parent.p, s.d_lab_s.p, s.d_idx.p, s.d_idx_s.p, (size_t)cap, 0u, bits, c->stream));
+    RTS_HIP(rocprim::exclusive_scan(nullptr, tmp_scan, s.d_flag.p, s.d_off.p, 0u, (size_t)cap + 1, rocprim::plus<uint32_t>(), c->stream));
+    RTS_HIP(s.d_tmp.reserve((tmp_sort > tmp_scan ? tmp_sort : tmp_scan) + 1));
     RtsPlotArgs a;
     a.list = list; a.n_dev = n_dev; a.n_cap = n_cap; a.cap = cap;
     a.nd = n_doppler; a.nb = q.n_bins; a.lr = p.link_range; a.ld = p.link_doppler; a.min_cells = p.min_cells ? p.min_cells : 1u; a.max_plots = max_plots;
     a.t0 = q.t0; a.dt = q.dt; a.pri = p.pri;
-    a.key = s.d_plot_key.p; a.parent = s.d_plot_parent.p; a.idx = s.d_plot_idx.p; a.lab_s = s.d_plot_lab_s.p; a.idx_s = s.d_plot_idx_s.p; a.len = s.d_plot_len.p;
-    a.flag = s.d_plot_flag.p; a.off = s.d_plot_off.p; a.out = s.d_plot.p;
+    a.key = s.d_key.p; a.parent = s.d_parent.p; a.idx = s.d_idx.p; a.lab_s = s.d_lab_s.p; a.idx_s = s.d_idx_s.p; a.len = s.d_len.p;
+    a.flag = s.d_flag.p; a.off = s.d_off.p; a.out = s.d_list.p;
     const unsigned grid = (cap + RTS_PLOT_THREADS - 1) / RTS_PLOT_THREADS;
     k_plot_init<<<grid, RTS_PLOT_THREADS, 0, c->stream>>>(a);
     RTS_HIP(hipGetLastError());
@@ -188,12 +188,12 @@ int rts_cube_plots_device(RtsContext* c, const RtsPlotParams& p, const RtsDetect
     RTS_HIP(hipGetLastError());
     k_plot_flatten<<<grid, RTS_PLOT_THREADS, 0, c->stream>>>(a);
     RTS_HIP(hipGetLastError());
-    RTS_HIP(rocprim::radix_sort_pairs(s.d_plot_tmp.p, tmp_sort, s.d_plot_parent.p, s.d_plot_lab_s.p, s.d_plot_idx.p, s.d_plot_idx_s.p, (size_t)cap, 0u, bits, c->stream));
+    RTS_HIP(rocprim::radix_sort_pairs(s.d_tmp.p, tmp_sort, s.d_parent.p, s.d_lab_s.p, s.d_idx.p, s.d_idx_s.p, (size_t)cap, 0u, bits, c->stream));
     k_plot_flag<<<grid, RTS_PLOT_THREADS, 0, c->stream>>>(a);
     RTS_HIP(hipGetLastError());
-    RTS_HIP(rocprim::exclusive_scan(s.d_plot_tmp.p, tmp_scan, s.d_plot_flag.p, s.d_plot_off.p, 0u, (size_t)cap + 1, rocprim::plus<uint32_t>(), c->stream));
+    RTS_HIP(rocprim::exclusive_scan(s.d_tmp.p, tmp_scan, s.d_flag.p, s.d_off.p, 0u, (size_t)cap + 1, rocprim::plus<uint32_t>(), c->stream));
     k_plot_reduce<<<grid, RTS_PLOT_THREADS, 0, c->stream>>>(a);
     RTS_HIP(hipGetLastError());
-    s.plot_cap = cap; s.plot_max = max_plots; s.plot_valid = true;
+    s.cap = cap; s.max = max_plots; s.valid = true;
     return RTS_OK;
 }

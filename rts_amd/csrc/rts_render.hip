@@ -127,7 +127,7 @@ int rts_cube_render_device(RtsContext* c, uint32_t pulse_index, bool paths, bool
     if (a.src.R == 0) return RTS_OK;
     const RtsCubeParams& q = c->cube.params;
     a.cube = c->cube.p; a.n_rx = q.n_rx; a.n_pulses = q.n_pulses; a.n_bins = q.n_bins; a.pulse = pulse_index; a.t0 = q.t0; a.dt = q.dt;
-    a.wave = c->cube.d_wave.p; a.M = c->cube.wave_M; a.L = c->cube.wave_L;
+    a.wave = c->cube.wave.d.p; a.M = c->cube.wave.M; a.L = c->cube.wave.L;
     const size_t lds = sizeof(double) * (2 * (size_t)a.M + (size_t)RTS_RENDER_SUB * a.L);      // <= 64 KiB + 16 KiB
     RTS_HIP(hipFuncSetAttribute((const void*)k_cube_render, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     dim3 grid((q.n_bins + RTS_RENDER_TILE - 1) / RTS_RENDER_TILE, q.n_rx);
@@ -176,7 +176,7 @@ int rts_cube_compress_device(RtsContext* c, uint32_t first_pulse, uint32_t n_pul
     const size_t lds = 16 * (size_t)q.n_bins;                                   // <= 128 KiB (RTS_COMPRESS_MAX_BINS)
     RTS_HIP(hipFuncSetAttribute((const void*)k_cube_compress, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     dim3 grid(n_pulses, q.n_rx);
-    k_cube_compress<<<grid, RTS_COMPRESS_THREADS, lds, c->stream>>>(c->cube.p, c->cube.d_wave.p, c->cube.wave_M, q.n_pulses, first_pulse, q.n_bins);
+    k_cube_compress<<<grid, RTS_COMPRESS_THREADS, lds, c->stream>>>(c->cube.p, c->cube.wave.d.p, c->cube.wave.M, q.n_pulses, first_pulse, q.n_bins);
     RTS_HIP(hipGetLastError());
     return RTS_OK;
 }

@@ -145,7 +145,7 @@ template <int NS> __global__ void __launch_bounds__(RTS_SRC_THREADS) k_cube_sour
     }
 }
 
-// table: the call's table on the device (rts_cube_api.hip uploads it on the stream before this: RtsCubeState::src_tab); live: the
+// table: the call's table on the device (rts_cube_api.hip uploads it on the stream before this: RtsCubeState::source.tab); live: the
 // partials that exist (rts_src_live_mask, not 0)
 int rts_cube_sources_device(RtsContext* c, const RtsSrcPlan& plan, uint32_t K, bool has_profile, uint64_t seed, uint64_t live, const double* table)
 {

@@ -93,7 +93,7 @@ template <int M> static void rts_st_launch(const RtsStArgs& a, const RtsStApplyP
 }
 
 // in: the source's receiver 0, row first_row (device); rx_stride: its n_rows_in n_bins; weights: the call's table on the device
-// (rts_cube_api.hip uploads it on the stream before this: RtsCubeState::st_w)
+// (rts_cube_array_api.hip uploads it on the stream before this: RtsCubeState::stap.w)
 int rts_cube_st_apply_device(RtsContext* c, const RtsStApplyParams& p, const RtsStApplyPlan& plan, const double* in, uint64_t rx_stride, const double* weights, void* out)
 {
     RtsStArgs a;

@@ -154,7 +154,7 @@ __global__ void __launch_bounds__(256) k_stft_sum_tiles(const double* __restrict
     out[i] = s;
 }
 
-// window: the call's taper on the device (rts_cube_api.hip uploads it on the stream before this: RtsCubeState::stft_win) or NULL
+// window: the call's taper on the device (rts_cube_api.hip uploads it on the stream before this: RtsCubeState::stft.win) or NULL
 int rts_cube_stft_device(RtsContext* c, const RtsStftParams& p, const RtsStftPlan& plan, const double* window, double* out)
 {
     const RtsCubeParams& q = c->cube.params;
@@ -164,7 +164,7 @@ int rts_cube_stft_device(RtsContext* c, const RtsStftParams& p, const RtsStftPla
     a.first_bin = p.first_bin; a.n_gate = plan.n_gate; a.BT = plan.BT; a.passes = plan.passes; a.tiles = plan.tiles; a.n_frames = plan.n_frames;
     a.power = (p.flags & RTS_STFT_POWER) ? 1u : 0u; a.sum = (p.flags & RTS_STFT_SUM_BINS) ? 1u : 0u;
     a.w = window; a.out = out; a.partial = nullptr;
-    if (plan.partial_doubles) { RTS_HIP(c->cube.d_stft_part.reserve(plan.partial_doubles)); a.partial = c->cube.d_stft_part.p; }
+    if (plan.partial_doubles) { RTS_HIP(c->cube.stft.d_part.reserve(plan.partial_doubles)); a.partial = c->cube.stft.d_part.p; }
     dim3 grid(plan.n_frames * plan.tiles, q.n_rx);
     if (a.sum) {
         RTS_HIP(hipFuncSetAttribute((const void*)k_cube_stft<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));

@@ -1,5 +1,5 @@
 // rts_tbd.h -- the rules of track-before-detect by dynamic programming (include/rts_amd.h: RtsTbdParams, RtsTbdExtractParams,
-// RtsTbdTrack), each written once and called by the kernels (rts_tbd.hip), the entry points (rts_cube_api.hip) and the host
+// RtsTbdTrack), each written once and called by the kernels (rts_tbd.hip), the entry points (rts_cube_detect_api.hip) and the host
 // evaluators (rts_tbd_step_eval, rts_tbd_extract_eval): the Doppler wrap and the shift table, the score, the window's first maximum
 // and its code, the candidate rule, the walk back through the pointer maps, the record, the validation, and the evaluators
 // themselves.  Every expression is written in the operand order of the header text and the units are built without contraction, so
@@ -99,7 +99,7 @@ RTS_HD RtsTbdTrack rts_tbd_record(uint32_t rx, uint32_t kd, uint32_t r, uint32_t
     return o;
 }
 
-// ---- validation.  The step's record on a map of nd x nb cells: 0, or the number of the rule it breaks (rts_cube_api.hip words the message)
+// ---- validation.  The step's record on a map of nd x nb cells: 0, or the number of the rule it breaks (rts_cube_detect_api.hip words the message)
 //   1 half_doppler  2 half_range  3 depth  4 score  5 flags  6 reserved  7 scale  8 decay  9 delay_rate_per_hz  10 pri
 //   11 2 half_doppler + 1 > n_doppler  12 half_range >= n_bins
 RTS_HD int rts_tbd_params_check(const RtsTbdParams* p, uint32_t nd, uint32_t nb)

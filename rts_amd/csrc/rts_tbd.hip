@@ -109,44 +109,44 @@ template <bool WRITE> __global__ void __launch_bounds__(RTS_TBD_THREADS) k_tbd_c
 // One step of a validated call on a state whose buffers exist: map -> merit[cur ^ 1], the pointers and the shifts into ring slot `slot`
 int rts_cube_tbd_step_device(RtsContext* c, const RtsTbdParams& p, const double* map, bool first, double T, double dt, uint32_t slot)
 {
-    RtsCubeState& s = c->cube;
-    const size_t cells = (size_t)s.tbd_rx * s.tbd_nd * s.tbd_nb;
+    RtsTbdState& s = c->cube.tbd;
+    const size_t cells = (size_t)s.rx * s.nd * s.nb;
     RtsTbdStepArgs a;
-    a.map = map; a.prev = first ? nullptr : s.d_tbd_merit[s.tbd_cur].p; a.next = s.d_tbd_merit[s.tbd_cur ^ 1u].p;
-    a.ptr = s.d_tbd_ptr.p + (size_t)slot * cells; a.shift = s.d_tbd_shift.p + (size_t)slot * s.tbd_nd;
-    a.n_rx = s.tbd_rx; a.nd = s.tbd_nd; a.nb = s.tbd_nb; a.tiles = (s.tbd_nb + RTS_TBD_TILE - 1u) / RTS_TBD_TILE;
+    a.map = map; a.prev = first ? nullptr : s.d_merit[s.cur].p; a.next = s.d_merit[s.cur ^ 1u].p;
+    a.ptr = s.d_ptr.p + (size_t)slot * cells; a.shift = s.d_shift.p + (size_t)slot * s.nd;
+    a.n_rx = s.rx; a.nd = s.nd; a.nb = s.nb; a.tiles = (s.nb + RTS_TBD_TILE - 1u) / RTS_TBD_TILE;
     a.Hd = (int)p.half_doppler; a.Hr = (int)p.half_range; a.score = p.score;
     a.scale = p.scale; a.decay = p.decay; a.k = p.delay_rate_per_hz; a.pri = p.pri; a.T = T; a.dt = dt;
     const size_t lds = sizeof(double) * (2u * p.half_doppler + 1u) * (RTS_TBD_TILE + 2u * p.half_range);
     const uint64_t grid = (uint64_t)a.tiles * a.nd * a.n_rx;             // (cells <= RTS_TBD_MAX_CELLS: below 2^31)
     k_tbd_step<<<(unsigned)grid, RTS_TBD_THREADS, lds, c->stream>>>(a);
     RTS_HIP(hipGetLastError());
-    s.tbd_cur ^= 1u;
+    s.cur ^= 1u;
     return RTS_OK;
 }
 
 int rts_cube_tbd_extract_device(RtsContext* c, const RtsTbdExtractParams& e, uint32_t max_tracks)
 {
-    RtsCubeState& s = c->cube;
-    const uint32_t cells = s.tbd_rx * s.tbd_nd * s.tbd_nb, n_seg = (cells + 63u) / 64u;
+    RtsTbdState& s = c->cube.tbd;
+    const uint32_t cells = s.rx * s.nd * s.nb, n_seg = (cells + 63u) / 64u;
     const size_t n_scan = (size_t)n_seg + 1;
-    RTS_HIP(s.d_tbd_cnt.reserve(n_scan)); RTS_HIP(s.d_tbd_off.reserve(n_scan));
-    RTS_HIP(s.d_tbd_out.reserve(max_tracks)); RTS_HIP(s.d_tbd_paths.reserve((size_t)max_tracks * s.tbd_depth * 2u));
+    RTS_HIP(s.d_cnt.reserve(n_scan)); RTS_HIP(s.d_off.reserve(n_scan));
+    RTS_HIP(s.d_out.reserve(max_tracks)); RTS_HIP(s.d_paths.reserve((size_t)max_tracks * s.depth * 2u));
     size_t tmp_scan = 0;
-    RTS_HIP(rocprim::exclusive_scan(nullptr, tmp_scan, s.d_tbd_cnt.p, s.d_tbd_off.p, 0u, n_scan, rocprim::plus<uint32_t>(), c->stream));
-    RTS_HIP(s.d_tbd_tmp.reserve(tmp_scan + 1));
+    RTS_HIP(rocprim::exclusive_scan(nullptr, tmp_scan, s.d_cnt.p, s.d_off.p, 0u, n_scan, rocprim::plus<uint32_t>(), c->stream));
+    RTS_HIP(s.d_tmp.reserve(tmp_scan + 1));
     RtsTbdExtArgs a;
-    a.merit = s.d_tbd_merit[s.tbd_cur].p; a.ring = s.d_tbd_ptr.p; a.shifts = s.d_tbd_shift.p;
-    a.n_rx = s.tbd_rx; a.nd = s.tbd_nd; a.nb = s.tbd_nb; a.cells = cells; a.n_seg = n_seg; a.depth = s.tbd_depth; a.Hd = s.tbd_hd; a.Hr = s.tbd_hr;
-    a.last = (uint32_t)((s.tbd_frames - 1u) % s.tbd_depth); a.max_cells = s.tbd_frames < s.tbd_depth ? (uint32_t)s.tbd_frames : s.tbd_depth;
-    a.threshold = e.threshold; a.t0 = s.tbd_t0; a.dt = s.tbd_dt; a.pri = e.pri; a.local_max = e.flags & RTS_TBD_LOCAL_MAX; a.max_tracks = max_tracks;
-    a.cnt = s.d_tbd_cnt.p; a.off = s.d_tbd_off.p; a.out = s.d_tbd_out.p; a.paths = s.d_tbd_paths.p;
+    a.merit = s.d_merit[s.cur].p; a.ring = s.d_ptr.p; a.shifts = s.d_shift.p;
+    a.n_rx = s.rx; a.nd = s.nd; a.nb = s.nb; a.cells = cells; a.n_seg = n_seg; a.depth = s.depth; a.Hd = s.hd; a.Hr = s.hr;
+    a.last = (uint32_t)((s.frames - 1u) % s.depth); a.max_cells = s.frames < s.depth ? (uint32_t)s.frames : s.depth;
+    a.threshold = e.threshold; a.t0 = s.t0; a.dt = s.dt; a.pri = e.pri; a.local_max = e.flags & RTS_TBD_LOCAL_MAX; a.max_tracks = max_tracks;
+    a.cnt = s.d_cnt.p; a.off = s.d_off.p; a.out = s.d_out.p; a.paths = s.d_paths.p;
     const unsigned grid = (unsigned)((n_scan * 64u + RTS_TBD_THREADS - 1) / RTS_TBD_THREADS);
     k_tbd_cand<false><<<grid, RTS_TBD_THREADS, 0, c->stream>>>(a);
     RTS_HIP(hipGetLastError());
-    RTS_HIP(rocprim::exclusive_scan(s.d_tbd_tmp.p, tmp_scan, s.d_tbd_cnt.p, s.d_tbd_off.p, 0u, n_scan, rocprim::plus<uint32_t>(), c->stream));
+    RTS_HIP(rocprim::exclusive_scan(s.d_tmp.p, tmp_scan, s.d_cnt.p, s.d_off.p, 0u, n_scan, rocprim::plus<uint32_t>(), c->stream));
     k_tbd_cand<true><<<grid, RTS_TBD_THREADS, 0, c->stream>>>(a);
     RTS_HIP(hipGetLastError());
-    s.tbd_ext_nseg = n_seg; s.tbd_ext_max = max_tracks; s.tbd_ext_depth = s.tbd_depth; s.tbd_ext_valid = true;
+    s.ext_nseg = n_seg; s.ext_max = max_tracks; s.ext_depth = s.depth; s.ext_valid = true;
     return RTS_OK;
 }

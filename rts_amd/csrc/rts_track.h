@@ -1,5 +1,5 @@
 // rts_track.h -- the rules of the tracker step (include/rts_amd.h: RtsTrackParams, RtsTrack), each written once and called by the
-// kernels (rts_track.hip), the entry points (rts_cube_api.hip) and the host evaluator (rts_tracks_eval): the Doppler wrap, the
+// kernels (rts_track.hip), the entry points (rts_cube_detect_api.hip) and the host evaluator (rts_tracks_eval): the Doppler wrap, the
 // prediction with S and its determinant, the innovation and d2, the edge rule, the candidate list and its order, the update, the
 // coast, the initiation, the lifecycle, the validation, and the evaluator itself -- the serial greedy pass over the sorted kept
 // edges (the kernels reach the same matching by rounds).  Every expression is written in the operand order of the header text and
@@ -124,7 +124,7 @@ RTS_HD RtsTrack rts_track_start(const RtsTrackParams& p, uint64_t id, uint32_t j
 }
 RTS_HD uint32_t rts_track_table_size(const RtsTrackParams& p) { return p.max_tracks ? p.max_tracks : RTS_TRACK_DEFAULT_TRACKS; }
 
-// ---- validation.  The parameter record: 0, or the number of the rule it breaks (rts_cube_api.hip words the message)
+// ---- validation.  The parameter record: 0, or the number of the rule it breaks (rts_cube_detect_api.hip words the message)
 //   1 gate  2 sigma_delay  3 sigma_doppler  4 q  5 delay_rate_per_hz  6 doppler_period  7 confirm_hits  8 max_candidates  9 max_tracks
 //   10 reserved  11 n_plots without device_plots  12 n_plots above RTS_TRACK_MAX_PLOTS  13 device_plots not 8-byte aligned
 RTS_HD int rts_track_params_check(const RtsTrackParams* p)

@@ -243,35 +243,35 @@ __global__ void __launch_bounds__(RTS_TRACK_THREADS) k_track_write(const RtsTrac
 // the table's buffers: both tables hold RTS_TRACK_MAX_TRACKS records from the start (a DevBuf that grows drops what it held)
 int rts_cube_track_tables(RtsContext* c)
 {
-    RtsCubeState& s = c->cube;
-    if (s.d_trk_meta.p) return RTS_OK;
-    RTS_HIP(s.d_trk[0].reserve(RTS_TRACK_MAX_TRACKS)); RTS_HIP(s.d_trk[1].reserve(RTS_TRACK_MAX_TRACKS));
-    RTS_HIP(s.d_trk_meta.reserve(2));
-    RTS_HIP(hipMemsetAsync(s.d_trk_meta.p, 0, 2 * sizeof(RtsTrackMeta), c->stream));
-    s.trk_cur = 0;
+    RtsTrackState& s = c->cube.track;
+    if (s.d_meta.p) return RTS_OK;
+    RTS_HIP(s.d_tab[0].reserve(RTS_TRACK_MAX_TRACKS)); RTS_HIP(s.d_tab[1].reserve(RTS_TRACK_MAX_TRACKS));
+    RTS_HIP(s.d_meta.reserve(2));
+    RTS_HIP(hipMemsetAsync(s.d_meta.p, 0, 2 * sizeof(RtsTrackMeta), c->stream));
+    s.cur = 0;
     return RTS_OK;
 }
 
 int rts_cube_track_device(RtsContext* c, const RtsTrackParams& p, double T, const RtsPlot* list, const uint32_t* n_dev, uint32_t pcap, uint32_t tcap)
 {
-    RtsCubeState& s = c->cube;
+    RtsTrackState& s = c->cube.track;
     RTS_TRY(rts_cube_track_tables(c));
     const uint32_t pcap1 = pcap ? pcap : 1u;
     const size_t n_scan = (size_t)tcap + pcap + 1;
-    RTS_HIP(s.d_trk_pred.reserve(tcap)); RTS_HIP(s.d_trk_cd.reserve((size_t)tcap * RTS_TRACK_MAX_CAND)); RTS_HIP(s.d_trk_cj.reserve((size_t)tcap * RTS_TRACK_MAX_CAND));
-    RTS_HIP(s.d_trk_cn.reserve(tcap)); RTS_HIP(s.d_trk_of_track.reserve(tcap)); RTS_HIP(s.d_trk_md2.reserve(tcap));
-    RTS_HIP(s.d_trk_zd.reserve(pcap1)); RTS_HIP(s.d_trk_zf.reserve(pcap1)); RTS_HIP(s.d_trk_pw.reserve(pcap1)); RTS_HIP(s.d_trk_zrx.reserve(pcap1));
-    RTS_HIP(s.d_trk_of_plot.reserve(pcap1)); RTS_HIP(s.d_trk_best_d.reserve(pcap1)); RTS_HIP(s.d_trk_best_t.reserve(pcap1));
-    RTS_HIP(s.d_trk_flag.reserve(n_scan)); RTS_HIP(s.d_trk_off.reserve(n_scan)); RTS_HIP(s.d_trk_rounds.reserve(1));
+    RTS_HIP(s.d_pred.reserve(tcap)); RTS_HIP(s.d_cd.reserve((size_t)tcap * RTS_TRACK_MAX_CAND)); RTS_HIP(s.d_cj.reserve((size_t)tcap * RTS_TRACK_MAX_CAND));
+    RTS_HIP(s.d_cn.reserve(tcap)); RTS_HIP(s.d_of_track.reserve(tcap)); RTS_HIP(s.d_md2.reserve(tcap));
+    RTS_HIP(s.d_zd.reserve(pcap1)); RTS_HIP(s.d_zf.reserve(pcap1)); RTS_HIP(s.d_pw.reserve(pcap1)); RTS_HIP(s.d_zrx.reserve(pcap1));
+    RTS_HIP(s.d_of_plot.reserve(pcap1)); RTS_HIP(s.d_best_d.reserve(pcap1)); RTS_HIP(s.d_best_t.reserve(pcap1));
+    RTS_HIP(s.d_flag.reserve(n_scan)); RTS_HIP(s.d_off.reserve(n_scan)); RTS_HIP(s.d_rounds.reserve(1));
     size_t tmp_scan = 0;
-    RTS_HIP(rocprim::exclusive_scan(nullptr, tmp_scan, s.d_trk_flag.p, s.d_trk_off.p, 0u, n_scan, rocprim::plus<uint32_t>(), c->stream));
-    RTS_HIP(s.d_trk_tmp.reserve(tmp_scan + 1));
+    RTS_HIP(rocprim::exclusive_scan(nullptr, tmp_scan, s.d_flag.p, s.d_off.p, 0u, n_scan, rocprim::plus<uint32_t>(), c->stream));
+    RTS_HIP(s.d_tmp.reserve(tmp_scan + 1));
     RtsTrackArgs a;
     a.p = p; a.T = T; a.list = list; a.n_dev = n_dev; a.pcap = pcap; a.tcap = tcap;
-    a.in = s.d_trk[s.trk_cur].p; a.out = s.d_trk[s.trk_cur ^ 1u].p; a.meta_in = s.d_trk_meta.p + s.trk_cur; a.meta_out = s.d_trk_meta.p + (s.trk_cur ^ 1u);
-    a.pred = s.d_trk_pred.p; a.zd = s.d_trk_zd.p; a.zf = s.d_trk_zf.p; a.pw = s.d_trk_pw.p; a.zrx = s.d_trk_zrx.p;
-    a.cd = s.d_trk_cd.p; a.cj = s.d_trk_cj.p; a.cn = s.d_trk_cn.p; a.of_track = s.d_trk_of_track.p; a.of_plot = s.d_trk_of_plot.p; a.md2 = s.d_trk_md2.p;
-    a.best_d = (unsigned long long*)s.d_trk_best_d.p; a.best_t = s.d_trk_best_t.p; a.rounds = s.d_trk_rounds.p; a.flag = s.d_trk_flag.p; a.off = s.d_trk_off.p;
+    a.in = s.d_tab[s.cur].p; a.out = s.d_tab[s.cur ^ 1u].p; a.meta_in = s.d_meta.p + s.cur; a.meta_out = s.d_meta.p + (s.cur ^ 1u);
+    a.pred = s.d_pred.p; a.zd = s.d_zd.p; a.zf = s.d_zf.p; a.pw = s.d_pw.p; a.zrx = s.d_zrx.p;
+    a.cd = s.d_cd.p; a.cj = s.d_cj.p; a.cn = s.d_cn.p; a.of_track = s.d_of_track.p; a.of_plot = s.d_of_plot.p; a.md2 = s.d_md2.p;
+    a.best_d = (unsigned long long*)s.d_best_d.p; a.best_t = s.d_best_t.p; a.rounds = s.d_rounds.p; a.flag = s.d_flag.p; a.off = s.d_off.p;
     const uint32_t widest = tcap > pcap1 ? tcap : pcap1;
     k_track_prep<<<(widest + RTS_TRACK_THREADS - 1) / RTS_TRACK_THREADS, RTS_TRACK_THREADS, 0, c->stream>>>(a);
     RTS_HIP(hipGetLastError());
@@ -282,9 +282,9 @@ int rts_cube_track_device(RtsContext* c, const RtsTrackParams& p, double T, cons
     const unsigned grid = (unsigned)((n_scan + RTS_TRACK_THREADS - 1) / RTS_TRACK_THREADS);
     k_track_flag<<<grid, RTS_TRACK_THREADS, 0, c->stream>>>(a);
     RTS_HIP(hipGetLastError());
-    RTS_HIP(rocprim::exclusive_scan(s.d_trk_tmp.p, tmp_scan, s.d_trk_flag.p, s.d_trk_off.p, 0u, n_scan, rocprim::plus<uint32_t>(), c->stream));
+    RTS_HIP(rocprim::exclusive_scan(s.d_tmp.p, tmp_scan, s.d_flag.p, s.d_off.p, 0u, n_scan, rocprim::plus<uint32_t>(), c->stream));
     k_track_write<<<grid, RTS_TRACK_THREADS, 0, c->stream>>>(a);
     RTS_HIP(hipGetLastError());
-    s.trk_cur ^= 1u;
+    s.cur ^= 1u;
     return RTS_OK;
 }

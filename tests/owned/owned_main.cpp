@@ -1,5 +1,5 @@
 // Driver of tests/test_owned_host.py: rts_amd/csrc/rts_owned.h alone, built with a plain host compiler and linked WITHOUT the HIP
-// runtime -- the ten calls the header makes are the stand-ins below, which log every call, keep the sets of live blocks and live
+// runtime -- the ten calls the header makes are the stand-ins of fake_hip.h, which log every call, keep the sets of live blocks and live
 // events and can be told to fail their n-th call; the copy stand-in copies the bytes.  One case per line on stdin (a name, then unsigned integers), one line of tokens on stdout:
 //   M:<id>:<bytes> F:<id>        hipMalloc / hipFree of block <id> (ids count allocations from 1 within the case)
 //   HM:<id>:<bytes> HF:<id>      hipHostMalloc / hipHostFree
@@ -14,85 +14,9 @@
 //   EQ:<0|1>                     after a send: the bytes at the device block equal the bytes the driver wrote to staging
 // The expectations live in the test.
 #include "rts_owned.h"
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <string>
+#include "fake_hip.h"
 #include <type_traits>
 #include <utility>
-
-static std::map<void*, int> g_live;      // address -> id
-static std::map<void*, size_t> g_bytes;  // address -> size of the block
-static std::map<void*, int> g_events;    // live events -> id
-static int g_next_id = 1, g_next_event = 1;
-static int g_fail_alloc = 0, g_fail_getptr = 0, g_fail_event = 0;      // fail the n-th allocation / device-address query / event creation from now (0: never)
-static const hipStream_t g_stream = (hipStream_t)(void*)&g_next_id;    // the case's stream: never dereferenced
-static std::string g_log;
-static void logf(const char* tag, long long a, long long b = -1)
-{
-    char s[64]; if (b >= 0) snprintf(s, sizeof(s), "%s:%lld:%lld ", tag, a, b); else snprintf(s, sizeof(s), "%s:%lld ", tag, a);
-    g_log += s;
-}
-static hipError_t fake_alloc(const char* tag, void** p, size_t bytes)
-{
-    if (g_fail_alloc && --g_fail_alloc == 0) { g_log += std::string("X:") + tag + " "; return hipErrorOutOfMemory; }      // (*p untouched)
-    *p = malloc(bytes ? bytes : 1);
-    g_live[*p] = g_next_id; g_bytes[*p] = bytes; logf(tag, g_next_id++, (long long)bytes);
-    return hipSuccess;
-}
-static hipError_t fake_free(const char* tag, void* p)
-{
-    auto it = g_live.find(p);
-    if (it == g_live.end()) { g_log += std::string("BAD:") + tag + " "; return hipErrorInvalidValue; }      // a second free of one address lands here
-    logf(tag, it->second); g_live.erase(it); g_bytes.erase(p); free(p);
-    return hipSuccess;
-}
-static void* dev_address(void* host) { return (char*)host + 1; }      // never dereferenced
-extern "C" {
-hipError_t hipMalloc(void** p, size_t bytes) { return fake_alloc("M", p, bytes); }
-hipError_t hipFree(void* p) { return fake_free("F", p); }
-hipError_t hipHostMalloc(void** p, size_t bytes, unsigned int flags) { if (flags != hipHostMallocDefault) g_log += "BAD:flags "; return fake_alloc("HM", p, bytes); }
-hipError_t hipHostFree(void* p) { return fake_free("HF", p); }
-hipError_t hipHostGetDevicePointer(void** dev, void* host, unsigned int flags)
-{
-    auto it = g_live.find(host);
-    if (it == g_live.end() || flags != 0) { g_log += "BAD:GP "; return hipErrorInvalidValue; }
-    if (g_fail_getptr && --g_fail_getptr == 0) { g_log += "X:GP "; return hipErrorInvalidValue; }
-    logf("GP", it->second); *dev = dev_address(host);
-    return hipSuccess;
-}
-hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned flags)
-{
-    if (flags != hipEventDisableTiming) g_log += "BAD:flags ";
-    if (g_fail_event && --g_fail_event == 0) { g_log += "X:EC "; return hipErrorOutOfMemory; }      // (*e untouched)
-    *e = (hipEvent_t)malloc(1); g_events[(void*)*e] = g_next_event; logf("EC", g_next_event++);
-    return hipSuccess;
-}
-static hipError_t event_call(const char* tag, hipEvent_t e)
-{
-    auto it = g_events.find((void*)e);
-    if (it == g_events.end()) { g_log += std::string("BAD:") + tag + " "; return hipErrorInvalidHandle; }      // a null, dead or twice destroyed event
-    logf(tag, it->second);
-    return hipSuccess;
-}
-hipError_t hipEventSynchronize(hipEvent_t e) { return event_call("ES", e); }
-hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) { if (s != g_stream) g_log += "BAD:stream "; return event_call("ER", e); }
-hipError_t hipEventDestroy(hipEvent_t e)
-{
-    const hipError_t r = event_call("ED", e);
-    if (r == hipSuccess) { g_events.erase((void*)e); free((void*)e); }
-    return r;
-}
-hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s)
-{
-    auto d = g_live.find(dst), f = g_live.find(const_cast<void*>(src));
-    if (d == g_live.end() || f == g_live.end() || kind != hipMemcpyHostToDevice || s != g_stream || bytes > g_bytes[d->first] || bytes > g_bytes[f->first]) { g_log += "BAD:CP "; return hipErrorInvalidValue; }
-    char t[96]; snprintf(t, sizeof(t), "CP:%d:%d:%zu ", d->second, f->second, bytes); g_log += t;
-    memcpy(dst, src, bytes);
-    return hipSuccess;
-}
-}
 
 // a struct that holds owners as members and in an array can be moved and never copied
 struct Holder { DevBuf<int> a[3]; DevBuf<double> b; PinBuf<char> c; };
@@ -179,7 +103,7 @@ int main()
         unsigned long long v[14] = {0}; int used = 0;
         if (sscanf(line, "%31s %31s%n", name, kind, &used) != 2) continue;
         int n = 0; for (const char* s = line + used; n < 14; n++) { int k = 0; if (sscanf(s, "%llu%n", &v[n], &k) != 1) break; s += k; }
-        g_log.clear(); g_live.clear(); g_bytes.clear(); g_events.clear(); g_next_id = g_next_event = 1; g_fail_alloc = g_fail_getptr = g_fail_event = 0; g_want_dev = !strcmp(kind, "pindev");
+        fake_reset(); g_want_dev = !strcmp(kind, "pindev");
         const bool pin = !strncmp(kind, "pin", 3);
         if (n < 1) { fprintf(stderr, "bad case: %s", line); return 2; }
         if (!strcmp(kind, "staged")) run_staged(name, v, n);
@@ -190,9 +114,8 @@ int main()
         case 145: if (pin) run<PinBuf<Elem<145>>>(name, v + 1, n - 1); else run<DevBuf<Elem<145>>>(name, v + 1, n - 1); break;
         default: fprintf(stderr, "bad element size: %s", line); return 2;
         }
-        printf("%sLIVE:%zu\n", g_log.c_str(), g_live.size() + g_events.size());
-        for (auto& kv : g_live) free(kv.first);
-        for (auto& kv : g_events) free(kv.first);
+        printf("%sLIVE:%zu\n", g_log.c_str(), fake_live());
+        fake_sweep();
     }
     return 0;
 }

@@ -1,11 +1,11 @@
-"""One handle through many calls: the host-side state the cube kernels are launched from (RtsCubeState, rts_amd/csrc/rts_internal.h)
+"""One handle through many calls: the host-side state the cube kernels are launched from (RtsCubeState, rts_amd/csrc/rts_cube_state.h)
 across regrows of its buffers, a short table after a long one, the OS-CFAR alpha cache, the records of every product across the other
 products' calls and across rts_cube_attach, and two handles whose calls alternate.  No kernel is new here and no tolerance is: at
 every step of every sequence a result is held to
 
   (a) its host evaluator (the numpy transform of tests/cube_ref.py for the Doppler map), compared as the product's own GPU test
-      compares it -- bit for bit for the beams, the covariances, the MVDR weights, the space-time filter, the eigenpairs and the scan
-      (tests/test_gpu_beam.py, _adapt.py, _stap.py, _doa.py), field by field for a detection list (tests/test_gpu_cfar_os.py: BYTE_EQUAL,
+      compares it -- bit for bit for the beams, the covariances, the MVDR weights, the space-time filter, the eigenpairs, the scan and
+      the shift table (tests/test_gpu_beam.py, _adapt.py, _stap.py, _doa.py, _focus.py; the phase table within _focus.py's bound), field by field for a detection list (tests/test_gpu_cfar_os.py: BYTE_EQUAL,
       then assert_same_list), byte for byte for plots and tracks (tests/test_gpu_plot.py, _track.py), rtol 1e-10 and atol 1e-12
       max|ref| for the spectrogram, the range transform and the image (tests/test_gpu_stft.py, _beat.py, _image.py), atol 1e-10
       max|cube| sqrt(n_fft) for the Doppler map (tests/test_gpu_cube_edges.py);
@@ -15,34 +15,34 @@ every step of every sequence a result is held to
    max(n + n / 8 + 16, 2 cap, 65 536) elements.  So on one handle a first small call leaves cap = 65 536, a call with 65 536 < n <=
    131 072 leaves max(n + n / 8 + 16, 131 072), a small call keeps that, and a call above it regrows again.  Each family's four sizes
    and the capacities they leave are written next to its sequence; the buffers each regrows twice:
-     Doppler               doppler.own            (doubles: 2 n_rx n_fft n_bins)
-     spectrogram, summed   stft.own, d_stft_part  (n_rx n_frames n_fft; that times the tiles of 8 gate bins, rts_stft_plan)
-     range transform       range.own              (2 n_rx n_pulses n_out)
-     beamform              beam.own               (2 n_beams n_rows n_bins)
-     covariance / stacked  d_cov_part             (2 parts D^2, parts = min(ceil(K / 64), 512): rts_cov_plan; cov.own holds 2 D^2 <= 8 192
+     Doppler               doppler.map.own        (doubles: 2 n_rx n_fft n_bins)
+     spectrogram, summed   stft.out.own, stft.d_part (n_rx n_frames n_fft; that times the tiles of 8 gate bins, rts_stft_plan)
+     range transform       fmcw.range.own         (2 n_rx n_pulses n_out)
+     beamform              beam.out.own           (2 n_beams n_rows n_bins)
+     covariance / stacked  adapt.d_cov_part       (2 parts D^2, parts = min(ceil(K / 64), 512): rts_cov_plan; adapt.cov.own holds 2 D^2 <= 8 192
                                                    doubles and never leaves its first 65 536)
-     space-time apply      st.own                 (2 n_filters out_rows n_bins)
-     DOA scan              doa.own                (n_dirs)
-     backprojection, split image.own, d_img_scratch (2 n_rx n_y n_x; 2 n_chunks n_rx n_y n_x with n_chunks = ceil(P / 64) > 1 and fewer than
+     space-time apply      stap.out.own           (2 n_filters out_rows n_bins)
+     DOA scan              doa.spectrum.own       (n_dirs)
+     backprojection, split image.out.own, image.d_scratch (2 n_rx n_y n_x; 2 n_chunks n_rx n_y n_x with n_chunks = ceil(P / 64) > 1 and fewer than
                                                    1 024 workgroups: rts_image_plan)
-     OS-CFAR, then plots   d_det (max_detections records), d_plot_key .. d_plot_off, d_plot (the list capacity, which is max_detections)
-     track                 d_trk_zd, _zf, _pw, _zrx, _of_plot, _best_d, _best_t (n_plots), d_trk_flag, _off (table + n_plots + 1);
-                           d_trk_cd, _cj (16 candidates per track of the table: 16 max_tracks)
+     OS-CFAR, then plots   detect.d_list (max_detections records), plot.d_key .. d_off, plot.d_list (the list capacity, which is max_detections)
+     track                 track.d_zd, d_zf, d_pw, d_zrx, d_of_plot, d_best_d, d_best_t (n_plots), d_flag, d_off (table + n_plots + 1);
+                           d_cd, d_cj (16 candidates per track of the table: 16 max_tracks)
    After each large step an older product of the handle is read again through its getter and must hold the bytes it was made with.
    A getter is asked right after the call that regrew its buffer: it returns the new product (both oracles), and a capacity one
    double short of the new size is refused, so the record names the new block and size.  The window between RtsCubeProduct::place
    and ::record is not reachable through the C ABI short of a failing allocation, so "refuses" is checked where it is reachable:
    after rts_cube_attach (part 4).
-   NOT exercised: d_beat_part.  rts_cube_render_beat reads the received set of a traced pulse and returns before it reserves anything
-   when there is none (rts_cube_beat_device: R == 0), and this file traces nothing; the pulse path has its own tests.  Nor d_det_cnt,
-   d_det_off and d_det_tmp, which the map's segments size (n_rx n_doppler ceil(n_bins / tile) + 1: past 65 536 only with a map of
-   millions of cells, whose evaluator run takes far longer than a test may), nor d_trk_pred, _cn, _of_track and _md2, which hold one
+   NOT exercised: fmcw.d_beat_part.  rts_cube_render_beat reads the received set of a traced pulse and returns before it reserves anything
+   when there is none (rts_cube_beat_device: R == 0), and this file traces nothing; the pulse path has its own tests.  Nor detect.d_cnt,
+   d_off and d_tmp, which the map's segments size (n_rx n_doppler ceil(n_bins / tile) + 1: past 65 536 only with a map of
+   millions of cells, whose evaluator run takes far longer than a test may), nor track.d_pred, d_cn, d_of_track and d_md2, which hold one
    element per track of a table of at most 65 536: their first 65 536 are all they ever need.
 
-2. A short table after a long one.  beam_w, st_w, mvdr_s, doa_g, stft_win, range_win, img_geo and os_alpha keep one device block; the
+2. A short table after a long one.  beam.w, stap.w, adapt.mvdr_s, doa.g, stft.win, fmcw.range_win, image.geo and detect.os_alpha keep one device block; the
    long call fills it with values near 1e6, the short call that follows must not read past its own.
 
-3. The OS-CFAR alpha cache (rts_cube_detect_os: os_tab, os_tab_key, os_tab_pfa, os_tab_sent) through eight calls: a hit, new training
+3. The OS-CFAR alpha cache (rts_cube_detect_os: detect.os_tab, os_key, os_pfa, os_sent) through eight calls: a hit, new training
    counts under the same key, pfa, rank and window changed one at a time (the last to a window of the same N0), a fixed alpha, and the
    first key again.  The maps are unit power with cells planted 1e-3 above and below the thresholds of every key in the sequence, so
    a wrong table changes the list itself.
@@ -65,6 +65,7 @@ import test_image_host as TH
 import track_ref as TR
 from test_gpu_beam import assert_peak           # the peak form's comparison: power and beam bit for bit, the offset as a range_offset
 from test_gpu_cfar_os import BYTE_EQUAL         # the fields a device list shares with the evaluator's byte for byte
+from test_gpu_focus import PGA_DEVICE_BOUND     # the PGA against its evaluator: 10 times the evaluator's measured distance from numpy
 
 pytestmark = pytest.mark.gpu
 
@@ -121,6 +122,13 @@ def bound(got, ref, what=""):
     """the project's bound for a kernel against its evaluator (tests/test_gpu_stft.py, test_gpu_beat.py, test_gpu_image.py)"""
     assert got.shape == ref.shape and got.dtype == ref.dtype, (what, got.shape, ref.shape)
     np.testing.assert_allclose(got, ref, rtol=1e-10, atol=1e-12 * np.abs(ref).max(), err_msg=str(what))
+
+
+def pga_bound(got, want, what=""):
+    """tests/test_gpu_focus.py: the phase table and the iterations' rms within PGA_DEVICE_BOUND of the evaluator's"""
+    assert len(got) == len(want) == 2
+    for g, w in zip(got, want):
+        assert g.shape == w.shape and np.all(np.isfinite(g)) and np.abs(g - w).max() <= PGA_DEVICE_BOUND, what
 
 
 def doppler_bound(got, cube, n_fft, what=""):
@@ -717,6 +725,8 @@ class Table:
             ("eig", lambda t: t.cube_eig(), lambda t: t.eigenpairs(), (vals, vecs), exact),
             ("doa", lambda t: t.cube_doa_scan(self.dtable.data_ptr(), gd, first_vector=1, n_dirs=33), lambda t: t.doa_spectrum(), rts.doa_scan_eval(vecs[1:3], gd, table), exact),
             ("image", image, lambda t: t.image(), rts.backproject_eval(c, self.t0, self.dt, g["origin"], g["step_x"], g["step_y"], 6, 4, g["tx"], g["rx"], g["c"], g["fc"], taps=2, first=2), bound),
+            ("align", lambda t: t.cube_align(1, 6, (2, 30), 4, 2), lambda t: t.align_shifts(), rts.align_eval(c, 1, 6, (2, 30), 4, 2), exact),
+            ("pga", lambda t: t.cube_pga(0, 8, (2, 30), 3), lambda t: t.pga_phase(), rts.pga_eval(c, 0, 8, (2, 30), 3), pga_bound),
             ("detections", lambda t: t.cube_detect_os(**os_par), lambda t: t.detections(), None, self.compare_detections),
             ("plots", lambda t: t.cube_plots((1, 1), pri=1e-3), lambda t: t.plots(), None, self.compare_plots),
         ]
