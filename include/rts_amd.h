@@ -1173,8 +1173,17 @@ int rts_range_eval(const RtsCubeParams* q, const double* cube, const RtsRangePar
  *   RTS_ERR_INVALID for a NULL pointer (taper apart), n_rx or n_beams 0, a wavelength not finite and > 0, a non-finite position,
  *   direction or taper.
  * NOTE on geometry: the tracer ends a ray's length on the receiver's capture SPHERE, not at its centre.  Receivers of equal radius in
- *   the far field share that offset, so their relative phases are those of their centres.  Unequal radii or near-field geometry are
- *   the caller's to model; the beamformer itself is plain linear algebra on whatever cube it is given. */
+ *   the far field whose spheres are DISJOINT share that offset, so their relative phases are those of their centres.  Unequal radii
+ *   or near-field geometry are the caller's to model; the beamformer itself is plain linear algebra on whatever cube it is given.
+ * NOTE on dense arrays: a ray is delivered to ONE receiver only.  Where capture spheres overlap, the last capturing receiver of the
+ *   list takes the ray and the ray's length accumulates the earlier spheres' entry distances (the reference's behaviour, quirk 4:
+ *   tests/test_capture_branches.py).  So array elements closer than two radii cannot share a launch: of eight elements half a
+ *   wavelength apart in one rts_set_receivers call the first seven receive nothing and the eighth every ray, with lengths that are
+ *   not its own.  The recipe for a dense array is one launch per element -- rts_set_receivers with that element alone, then
+ *   rts_cube_attach of a one-receiver cube at the element's slab (n_pulses * n_bins samples) of a shared [n_rx][n_pulses][n_bins]
+ *   device buffer, then the pulses -- and a handle that attaches the whole buffer with n_rx elements for the array families.
+ *   tests/test_array_chain_host.py shows both on the oracle, tests/test_gpu_array_chain.py the recipe on the device: the beams,
+ *   the MVDR null, the angular spectra and the space-time filters of such a cube point where the sign rule above says. */
 #define RTS_BEAM_FROM_CUBE    0u   /* rows of the attached cube                                                     */
 #define RTS_BEAM_FROM_MAP     1u   /* the handle's last library-owned rts_cube_doppler map; rows = its n_fft       */
 #define RTS_BEAM_FROM_POINTER 2u   /* device_in: complex128 [n_rx][n_rows_in][n_bins], 16-byte aligned              */
