@@ -844,6 +844,130 @@ int rts_tracks_eval(const RtsTrackParams* p, const RtsTrack* in, uint32_t n_in, 
                     const RtsPlot* plots, uint32_t n_plots, RtsTrack* out, uint32_t capacity, uint32_t* n_out,
                     uint64_t* next_id_out);                                                      /* pure host */
 
+/* ---------------------------------------------------------------- multistatic localisation: the plots of several receivers to targets
+ * Plots and tracks live in ONE receiver's coordinates.  A scene has one transmitter at tx and n_rx receivers at known positions
+ * s_0 .. s_(n_rx-1); a target at x moving with v shows in receiver m at the bistatic delay (|x - tx| + |x - s_m|) / cspeed with the
+ * Doppler -(1 / lambda) (u_t + u_m) . v, where u_t, u_m are the unit vectors from tx and s_m to x (a closing range gives a positive
+ * Doppler, the sign of the CFAR section).  rts_cube_locate turns one frame of per-receiver records into TARGETS -- position,
+ * velocity, the records they are made of -- on the device and without waiting on the host.  The rules are rts_amd/csrc/rts_locate.h,
+ * shared by the kernels (rts_locate.hip) and the host evaluator rts_locate_eval, which agree bit for bit on every field.  All
+ * arithmetic is IEEE double, every product, quotient and square root rounded on its own (no contraction), sums of three terms added
+ * left to right, |a| = sqrt((a_x a_x + a_y a_y) + a_z a_z).
+ *   Notation: R = cspeed delay (a record's range sum);  d_a = s_a - tx for the three ANCHOR receivers a = anchors[0 .. 2];
+ *     sigma_R = cspeed sigma_delay;  lambda = cspeed / carrier (carrier = 0: no Doppler is used and every velocity is 0).
+ *   Sources.  RTS_LOCATE_FROM_PLOTS: the handle's plots (device_list NULL: the first min(total, stored) records, the count read on
+ *     the device) or a caller-owned DEVICE array of n_list RtsPlot whose rx does not decrease -- taken as given, as in rts_cube_track;
+ *     rts_locate_eval refuses a list whose rx decreases.  Only rx, delay, doppler and power_sum are read.  RTS_LOCATE_FROM_TRACKS:
+ *     the handle's track table (device_list must be NULL); only tracks that are RTS_TRACK_CONFIRMED and not RTS_TRACK_COASTED take
+ *     part, through their delay, doppler and power_sum; the table is in no receiver order, so the step orders a copy by (rx, table
+ *     index), and plot[] holds TABLE indices; rts_locate_eval takes a host RtsTrack[].  RTS_LOCATE_FROM_CANDIDATES: device_list is
+ *     a DEVICE array of n_list RtsTarget, accepted candidates in ascending `candidate`; only the resolution (7) runs, on their
+ *     n_receivers, cost and plot[] (every index below RTS_LOCATE_MAX_INDEX or 0xffffffff; an index names ONE record whatever receiver
+ *     it stands at), and the other fields are copied.  It exists to hold the resolution to its definition on conflict graphs that no
+ *     geometry produces on demand.  Records of a receiver >= n_rx are ignored.  A record whose delay, doppler or power_sum is not
+ *     finite keeps its place in its segment but takes no part: it forms no triple and completes no candidate.
+ *   1. Segments.  seg[m] is the records of receiver m in list order (tracks: in table order).  Of an anchor's segment the first
+ *     P = min(size, RTS_LOCATE_MAX_PER_RX) records are used; a longer one makes rts_cube_targets_get return RTS_ERR_CAPACITY.
+ *   2. Triples.  Every (i, j, k) in seg[a0] x seg[a1] x seg[a2] (positions inside the segments, below P_0, P_1, P_2):
+ *     Screen: skipped when |R_a - R_b| > |s_a - s_b| for an anchor pair or R_a < |d_a| for an anchor: no point has those range sums.
+ *     Equations in w = (u, r), u = x - tx, r = |u|:  d_a . u - R_a r = c_a = (|d_a|^2 - R_a R_a) / 2, a 3 x 4 system M w = c with
+ *       M = [D | -R] (row a of D is d_a).
+ *     Solve: M M^T = D D^T + R R^T is factored by Cholesky (lower, row by row: pivot p, l = sqrt(p), the entries below divided by l);
+ *       a pivot that is not positive and finite gives no candidate.  y = (M M^T)^-1 c by the two triangular solves, w0 = M^T y:
+ *       u0 = (y_0 d_0 + y_1 d_1) + y_2 d_2,  r0 = -((R_0 y_0 + R_1 y_1) + R_2 y_2).  The null vector n of M from its four 3 x 3
+ *       cofactors, with X_pq the cross product of columns p and q of D:  n_x = -(R . X_12), n_y = R . X_02, n_z = -(R . X_01),
+ *       n_r = -det D (det D = column 2 . X_01).  This never inverts D, so a transmitter and anchors in ONE PLANE -- the usual
+ *       ground network, det D = 0 -- are solved too.  The roots of |u0 + l n_u|^2 = (r0 + l n_r)^2:  a = |n_u|^2 - n_r n_r,
+ *       b = u0 . n_u - r0 n_r, q = |u0|^2 - r0 r0, disc = b b - a q; disc < 0 (or NaN) gives no candidate; t = -(b + sqrt(disc)) when
+ *       b >= 0, else -(b - sqrt(disc)); l_A = t / a, l_B = q / t (the cancellation-free pair).  Each root has r = r0 + l n_r,
+ *       u = u0 + l n_u, x = tx + u.  ROOT 0 is the one of smaller (r, l), root 1 the other (in a ground network both have the same
+ *       r: mirror images in the plane).
+ *     A root is kept when r > 0, R_a - r > 0 for the three anchors, x and r are finite, and box_lo <= x <= box_hi on every axis.
+ *     The candidate index is ((i P_1 + j) P_2 + k) 2 + root, a uint64.
+ *   3. Completion.  Every non-anchor receiver m in ascending order takes the participating record of seg[m] with the smallest
+ *     |R - Rhat_m|, Rhat_m = |x0 - tx| + |x0 - s_m| at the root's x0, ties to the lowest position, and only when that distance is at
+ *     most cspeed assoc_delay; otherwise m has no record.  K = 3 + the receivers that took one; K < min_receivers drops the candidate.
+ *   4. Refinement.  n_iters Gauss-Newton steps on the K range sums, the receivers in ascending order: rows J_m = u_t + u_m (each
+ *     component ((x - tx)_c / |x - tx|) + ((x - s_m)_c / |x - s_m|)), residuals rho_m = R_m - (|x - tx| + |x - s_m|), A = J^T J and
+ *     g = J^T rho accumulated from 0 (each product rounded, then added), A factored as above, x + A^-1 g.  A pivot that is not positive
+ *     and finite ends the refinement where x stands and sets RTS_TARGET_UNREFINED.  The final x must be finite and in the box.
+ *   5. Velocity and cost at the final x (J, rho, A taken there anew).  carrier > 0: v = -lambda A^-1 J^T f with f_m the records'
+ *     Dopplers, e_m = f_m + (J_m . v) / lambda; a pivot that fails here leaves v = 0 and e_m = f_m and sets RTS_TARGET_UNREFINED.
+ *     Dopplers are taken as unambiguous: a stated limit.  cost = sum (rho_m rho_m) / (sigma_R sigma_R) + sum (e_m e_m) /
+ *     (sigma_doppler sigma_doppler), the first sum from 0 over the receivers, then the second on top of it; dof = 2 K - 6.  carrier
+ *     = 0: the second sum is absent and dof = K - 3.  The candidate is ACCEPTED when cost <= gate max(dof, 1).  power_sum: its
+ *     records' power_sum added from 0 in receiver order.
+ *   6. Capacity.  The accepted candidates are stored in ascending candidate index, at most max_candidates (0:
+ *     RTS_LOCATE_DEFAULT_CANDIDATES, at most RTS_LOCATE_MAX_CANDIDATES); beyond that the stored prefix is resolved and
+ *     rts_cube_targets_get returns RTS_ERR_CAPACITY.  Positions come from counts and a scan, never from atomics.
+ *   7. Resolution.  The greedy pass over the accepted candidates in ascending (-K, cost, candidate index): a candidate becomes a
+ *     TARGET when none of its records is taken, and then takes them.  The device reaches the same set by rounds of locally dominant
+ *     candidates (rts_locate.hip) and ends the rounds itself.  Targets are written in ascending candidate index, at most max_targets
+ *     (0: RTS_LOCATE_DEFAULT_TARGETS, at most RTS_LOCATE_MAX_TARGETS).  With exactly THREE receivers every feasible triple is a
+ *     zero-cost candidate, so n targets give up to n^3 - n GHOSTS before the resolution and some survive it: inherent, not repaired
+ *     -- use four receivers or more.
+ *   Lifetime: the targets are NOT a product of the cube: the step copies what it needs of the records, and the targets survive
+ *     rts_cube_attach, the detect calls, rts_cube_plots and rts_cube_track; they end at the next rts_cube_locate and at rts_destroy.
+ *     rts_cube_targets_get synchronises, sets *n_out to the total and copies min(total, stored, capacity) records; RTS_ERR_CAPACITY
+ *     when fewer were copied than the total, when max_candidates cut the candidates and when an anchor's segment was cut;
+ *     RTS_ERR_INVALID before the first rts_cube_locate.  rx_positions is read during the call only (it goes through a staged upload).
+ *   rts_locate_eval: pure host, the same targets of a host list of the source's record type (RtsPlot, RtsTrack or RtsTarget):
+ *     up to `capacity` records to out, the total to *n_out, RTS_ERR_CAPACITY as above.  device_list and p->n_list are validated and
+ *     otherwise ignored.
+ *   RTS_ERR_INVALID, the message naming the field, outputs untouched: n_rx outside 3 .. RTS_LOCATE_MAX_RX; NULL rx_positions;
+ *     anchors equal or >= n_rx; anchor baselines collinear, |(d_1 - d_0) x (d_2 - d_0)| <= 1e-9 |d_1 - d_0| |d_2 - d_0|; a position
+ *     that is not finite; cspeed, sigma_delay, sigma_doppler, gate or assoc_delay not finite or not positive; carrier negative or not
+ *     finite; a box bound that is not finite or box_lo > box_hi; min_receivers outside 3 .. n_rx; n_iters above RTS_LOCATE_MAX_ITERS;
+ *     max_candidates or max_targets above their limits; an unknown source; no list for the source (no plots and no device_list;
+ *     RTS_LOCATE_FROM_CANDIDATES without device_list; RTS_LOCATE_FROM_TRACKS with one); n_list without device_list or above
+ *     RTS_LOCATE_MAX_LIST (candidates: RTS_LOCATE_MAX_CANDIDATES); device_list not 8-byte aligned; nonzero reserved fields.
+ *     rts_locate_eval additionally refuses NULL arguments, a plot list whose rx decreases and a candidate list that is not in
+ *     ascending `candidate`, names an index >= RTS_LOCATE_MAX_INDEX, has n_receivers outside 1 .. RTS_LOCATE_MAX_RX or a cost that
+ *     is negative or NaN. */
+#define RTS_LOCATE_MAX_RX 16u
+#define RTS_LOCATE_MAX_PER_RX 1024u
+#define RTS_LOCATE_MAX_ITERS 8u
+#define RTS_LOCATE_DEFAULT_CANDIDATES 65536u
+#define RTS_LOCATE_MAX_CANDIDATES 1048576u
+#define RTS_LOCATE_DEFAULT_TARGETS 4096u
+#define RTS_LOCATE_MAX_TARGETS 65536u
+#define RTS_LOCATE_MAX_LIST 16777216u
+#define RTS_LOCATE_MAX_INDEX 1048576u
+#define RTS_LOCATE_FROM_PLOTS 0u
+#define RTS_LOCATE_FROM_TRACKS 1u
+#define RTS_LOCATE_FROM_CANDIDATES 2u
+#define RTS_TARGET_UNREFINED 1u   /* a Gauss-Newton pivot failed: x is where the refinement stood */
+typedef struct RtsLocateParams {
+    double tx[3];                        /* the transmitter                                                             */
+    const double* rx_positions;          /* HOST [n_rx][3], read during the call                                        */
+    double cspeed, carrier;              /* carrier 0: no Doppler, velocity 0                                           */
+    double sigma_delay, sigma_doppler;   /* measurement standard deviations, s and Hz, > 0                              */
+    double gate;                         /* accepted when cost <= gate max(dof, 1)                                      */
+    double assoc_delay;                  /* completion window, seconds, > 0                                             */
+    double box_lo[3], box_hi[3];         /* the closed search volume                                                    */
+    uint32_t n_rx;                       /* 3 .. RTS_LOCATE_MAX_RX                                                      */
+    uint32_t anchors[3];                 /* three distinct receivers, not collinear                                     */
+    uint32_t min_receivers;              /* 3 .. n_rx                                                                   */
+    uint32_t n_iters;                    /* 0 .. RTS_LOCATE_MAX_ITERS Gauss-Newton steps                                */
+    uint32_t max_candidates, max_targets;/* 0: the defaults                                                             */
+    uint32_t source;                     /* RTS_LOCATE_FROM_*                                                           */
+    uint32_t n_list;                     /* with device_list: its length; else 0                                        */
+    const void* device_list;             /* NULL: the handle's plots / tracks; else caller-owned DEVICE records         */
+    uint64_t reserved[2];                /* 0 */
+} RtsLocateParams;                                            /* 192 bytes */
+typedef struct RtsTarget {
+    double pos[3], vel[3];                                    /* m, m / s                                                 */
+    double cost, power_sum;
+    uint64_t candidate;                                       /* the candidate index                                      */
+    uint32_t n_receivers, flags;                              /* K; RTS_TARGET_*                                          */
+    uint32_t plot[RTS_LOCATE_MAX_RX];                         /* per receiver the list index of its record, 0xffffffff none */
+} RtsTarget;                                                  /* 144 bytes */
+int rts_cube_locate(RtsHandle h, const RtsLocateParams* p);
+int rts_cube_targets_get(RtsHandle h, RtsTarget* out, uint32_t capacity, uint32_t* n_out);
+int rts_cube_locate_rounds(RtsHandle h, uint32_t* rounds);   /* diagnostic: rounds the last resolution took; synchronises */
+int rts_locate_eval(const RtsLocateParams* p, const void* list, uint32_t n_list, RtsTarget* out, uint32_t capacity,
+                    uint32_t* n_out);                                                            /* pure host */
+
 /* ---------------------------------------------------------------- track-before-detect: dynamic programming over range-Doppler maps
  * Detect, plots and track are detect-BEFORE-track: a return reaches the tracker only when it crosses a CFAR threshold in one map.
  * rts_cube_tbd_step integrates the maps of successive intervals along every kinematically admissible cell path instead (Barniv;

@@ -161,6 +161,23 @@ TRACK_DTYPE = np.dtype([("id", "<u8"), ("rx", "<u4"), ("flags", "<u4"), ("hits",
                         ("delay", "<f8"), ("doppler", "<f8"), ("p_dd", "<f8"), ("p_df", "<f8"), ("p_ff", "<f8"), ("d2", "<f8"), ("power_sum", "<f8")])
 assert TRACK_DTYPE.itemsize == 88 and C.sizeof(RtsTrackParams) == 96
 
+RTS_LOCATE_MAX_RX, RTS_LOCATE_MAX_PER_RX, RTS_LOCATE_MAX_ITERS, RTS_LOCATE_MAX_LIST, RTS_LOCATE_MAX_INDEX = 16, 1024, 8, 16777216, 1048576
+RTS_LOCATE_DEFAULT_CANDIDATES, RTS_LOCATE_MAX_CANDIDATES, RTS_LOCATE_DEFAULT_TARGETS, RTS_LOCATE_MAX_TARGETS = 65536, 1048576, 4096, 65536
+RTS_LOCATE_FROM_PLOTS, RTS_LOCATE_FROM_TRACKS, RTS_LOCATE_FROM_CANDIDATES, RTS_TARGET_UNREFINED = 0, 1, 2, 1
+
+
+class RtsLocateParams(C.Structure):
+    _fields_ = [("tx", C.c_double * 3), ("rx_positions", C.c_void_p), ("cspeed", C.c_double), ("carrier", C.c_double), ("sigma_delay", C.c_double),
+                ("sigma_doppler", C.c_double), ("gate", C.c_double), ("assoc_delay", C.c_double), ("box_lo", C.c_double * 3), ("box_hi", C.c_double * 3),
+                ("n_rx", C.c_uint32), ("anchors", C.c_uint32 * 3), ("min_receivers", C.c_uint32), ("n_iters", C.c_uint32), ("max_candidates", C.c_uint32),
+                ("max_targets", C.c_uint32), ("source", C.c_uint32), ("n_list", C.c_uint32), ("device_list", C.c_void_p), ("reserved", C.c_uint64 * 2)]
+
+
+# RtsTarget (include/rts_amd.h), 144 bytes
+TARGET_DTYPE = np.dtype([("pos", "<f8", (3,)), ("vel", "<f8", (3,)), ("cost", "<f8"), ("power_sum", "<f8"), ("candidate", "<u8"), ("n_receivers", "<u4"),
+                         ("flags", "<u4"), ("plot", "<u4", (16,))])
+assert TARGET_DTYPE.itemsize == 144 and C.sizeof(RtsLocateParams) == 192
+
 RTS_TBD_POWER, RTS_TBD_AMPLITUDE, RTS_TBD_LOCAL_MAX, RTS_TBD_NONE = 0, 1, 1, 0xff
 RTS_TBD_MAX_HALF_DOPPLER, RTS_TBD_MAX_HALF_RANGE, RTS_TBD_MAX_DEPTH, RTS_TBD_MAX_TRACKS, RTS_TBD_MAX_CELLS = 3, 15, 64, 65536, 0x40000000
 RTS_TBD_TILE = 1024      # rts_amd/csrc/rts_tbd.h: the range bins a workgroup of the step takes
@@ -425,6 +442,7 @@ EXPORTS = ["rts_create", "rts_destroy", "rts_last_error", "rts_device_count", "r
            "rts_cube_detect_os", "rts_cfar_os_alpha", "rts_cfar_os_eval",
            "rts_cube_plots", "rts_cube_plots_get", "rts_plots_eval",
            "rts_cube_track", "rts_cube_tracks_get", "rts_cube_tracks_set", "rts_cube_tracks_reset", "rts_cube_track_rounds", "rts_tracks_eval",
+           "rts_cube_locate", "rts_cube_targets_get", "rts_cube_locate_rounds", "rts_locate_eval",
            "rts_cube_tbd_step", "rts_cube_tbd_extract", "rts_cube_tbd_tracks_get", "rts_cube_tbd_paths_get", "rts_cube_tbd_merit_get", "rts_cube_tbd_ring_get",
            "rts_cube_tbd_info", "rts_cube_tbd_reset", "rts_tbd_step_eval", "rts_tbd_extract_eval",
            "rts_cube_backproject", "rts_cube_image_get", "rts_backproject_eval",
@@ -521,6 +539,10 @@ def lib():
         "rts_cube_tracks_reset": [vp],
         "rts_cube_track_rounds": [vp, C.POINTER(u32)],
         "rts_tracks_eval": [C.POINTER(RtsTrackParams), vp, u32, u64, C.c_double, vp, u32, vp, u32, C.POINTER(u32), C.POINTER(u64)],
+        "rts_cube_locate": [vp, C.POINTER(RtsLocateParams)],
+        "rts_cube_targets_get": [vp, vp, u32, C.POINTER(u32)],
+        "rts_cube_locate_rounds": [vp, C.POINTER(u32)],
+        "rts_locate_eval": [C.POINTER(RtsLocateParams), vp, u32, vp, u32, C.POINTER(u32)],
         "rts_cube_tbd_step": [vp, C.POINTER(RtsTbdParams), C.c_double, vp, u32],
         "rts_cube_tbd_extract": [vp, C.POINTER(RtsTbdExtractParams)],
         "rts_cube_tbd_tracks_get": [vp, vp, u32, C.POINTER(u32)],

@@ -348,6 +348,52 @@ def tracks_eval(tracks, next_id, T, plots, sigma, gate=9.21, q=0.0, delay_rate_p
     return out[:min(n.value, max_tracks or L.RTS_TRACK_DEFAULT_TRACKS)].copy(), nid.value
 
 
+# ------------------------------------------------------------------------------- multistatic localisation (rts_locate.h)
+_LOCATE_SOURCES = {"plots": (L.RTS_LOCATE_FROM_PLOTS, L.PLOT_DTYPE), "tracks": (L.RTS_LOCATE_FROM_TRACKS, L.TRACK_DTYPE),
+                   "candidates": (L.RTS_LOCATE_FROM_CANDIDATES, L.TARGET_DTYPE)}
+
+
+def _locate_params(tx, rx_positions, cspeed, carrier, sigma, gate, assoc_delay, box, anchors, min_receivers, n_iters, max_candidates=0, max_targets=0,
+                   source="plots", device_list=None, n_list=0):
+    """(RtsLocateParams, the receiver array it points to -- keep it alive for the call); sigma is the measurement standard deviation
+    (delay in s, Doppler in Hz), box = (lo, hi), min_receivers None: every receiver"""
+    rx = np.ascontiguousarray(np.asarray(rx_positions, np.float64).reshape(-1, 3))
+    p = L.RtsLocateParams()
+    p.tx[:] = [float(x) for x in tx]
+    p.rx_positions = rx.ctypes.data
+    p.n_rx = len(rx)
+    p.anchors[:] = [int(a) for a in anchors]
+    p.cspeed, p.carrier, p.gate, p.assoc_delay = float(cspeed), float(carrier), float(gate), float(assoc_delay)
+    p.sigma_delay, p.sigma_doppler = (float(x) for x in sigma)
+    p.box_lo[:] = [float(x) for x in box[0]]
+    p.box_hi[:] = [float(x) for x in box[1]]
+    p.min_receivers = len(rx) if min_receivers is None else int(min_receivers)
+    p.n_iters, p.max_candidates, p.max_targets = int(n_iters), int(max_candidates), int(max_targets)
+    p.source = _LOCATE_SOURCES[source][0]
+    p.device_list = C.c_void_p(device_list) if device_list else None
+    p.n_list = int(n_list)
+    return p, rx
+
+
+def locate_eval(list, tx, rx_positions, cspeed, carrier, sigma, gate=9.21, assoc_delay=1e-7, box=((-1e6,) * 3, (1e6,) * 3), anchors=(0, 1, 2), min_receivers=None,
+                n_iters=4, max_candidates=0, max_targets=0, source="plots"):
+    """rts_locate_eval (pure host): the targets of one frame of per-receiver records -- a PLOT_DTYPE list (rx non-decreasing), a
+    TRACK_DTYPE table or, for the resolution alone, a TARGET_DTYPE list of accepted candidates -- seen from a transmitter at tx by
+    the receivers at rx_positions [n_rx][3].  Returns the stored TARGET_DTYPE records in ascending candidate index (a truncated list
+    gives its stored prefix)."""
+    z = np.ascontiguousarray(np.asarray(list, _LOCATE_SOURCES[source][1]))
+    p, keep = _locate_params(tx, rx_positions, cspeed, carrier, sigma, gate, assoc_delay, box, anchors, min_receivers, n_iters, max_candidates, max_targets, source)
+    n = C.c_uint32(0)
+    rc = L.lib().rts_locate_eval(C.byref(p), ptr(z) if len(z) else None, len(z), None, 0, C.byref(n))
+    if rc not in (L.RTS_OK, L.RTS_ERR_CAPACITY):
+        check(rc)
+    out = np.zeros(max(n.value, 1), L.TARGET_DTYPE)
+    rc = L.lib().rts_locate_eval(C.byref(p), ptr(z) if len(z) else None, len(z), ptr(out), len(out), C.byref(n))
+    if rc != L.RTS_ERR_CAPACITY:
+        check(rc)
+    return out[:min(n.value, max_targets or L.RTS_LOCATE_DEFAULT_TARGETS)].copy()
+
+
 # ------------------------------------------------------------------------------- track-before-detect (rts_tbd.h)
 def _tbd_params(half, depth, score, scale, decay, delay_rate_per_hz, pri):
     """RtsTbdParams; half is the transition window (Doppler, range) in cells on each side"""
@@ -1528,6 +1574,28 @@ class Tracer:
     def cube_tracks_reset(self):
         """rts_cube_tracks_reset: an empty table without a time; ids go on where they were"""
         check(L.lib().rts_cube_tracks_reset(self.h))
+
+    def cube_locate(self, tx, rx_positions, cspeed, carrier, sigma, gate=9.21, assoc_delay=1e-7, box=((-1e6,) * 3, (1e6,) * 3), anchors=(0, 1, 2),
+                    min_receivers=None, n_iters=4, max_candidates=0, max_targets=0, source="plots", device_list=None, n_list=0, fetch=True):
+        """rts_cube_locate + rts_cube_targets_get: one frame of per-receiver records -- the handle's plots or its track table (source
+        "plots" / "tracks", device_list None), a caller-owned device array of n_list RtsPlot records, or for the resolution alone n_list
+        RtsTarget candidates (source "candidates") -- to targets: position, velocity and the records they are made of, seen from a
+        transmitter at tx by the receivers at rx_positions [n_rx][3]; sigma is the measurement standard deviation (delay in s, Doppler
+        in Hz).  Never waits on the host unless fetch.  Returns a TARGET_DTYPE array in ascending candidate index when fetch."""
+        p, keep = _locate_params(tx, rx_positions, cspeed, carrier, sigma, gate, assoc_delay, box, anchors, min_receivers, n_iters, max_candidates, max_targets,
+                                 source, device_list, n_list)
+        check(L.lib().rts_cube_locate(self.h, C.byref(p)))
+        return self.cube_targets() if fetch else None
+
+    def cube_targets(self):
+        """rts_cube_targets_get: the targets of the last cube_locate (every stored record; raises when a capacity cut them)"""
+        n = C.c_uint32(0)
+        rc = L.lib().rts_cube_targets_get(self.h, None, 0, C.byref(n))
+        if rc not in (L.RTS_OK, L.RTS_ERR_CAPACITY):
+            check(rc)
+        out = np.zeros(max(n.value, 1), L.TARGET_DTYPE)
+        check(L.lib().rts_cube_targets_get(self.h, ptr(out), n.value, C.byref(n)))
+        return out[:n.value].copy()
 
     def cube_tbd_step(self, time, half=(1, 2), depth=8, score="power", scale=1.0, decay=1.0, delay_rate_per_hz=0.0, pri=0.0, device_ptr=None, n_doppler=0):
         """rts_cube_tbd_step: the handle's track-before-detect state advanced by the frame at `time` -- the handle's last cube_doppler

@@ -1,6 +1,6 @@
 // rts_cube_args.h -- the pure rules the cube entry points apply to their arguments (rts_cube_api.h words the messages): a span
 // inside a total, a power of two in a range, two byte ranges against each other, an output against every receiver's span of
-// the input, the source fields of a beamformer-style record.  Each returns the fact, or the number of the rule that broke.
+// the input, the source fields of a beamformer-style record, a caller's device list and its length.  Each returns the fact, or the number of the rule that broke.
 // Host only, no HIP, no handle: tests/test_cube_args_host.py builds it alone (tests/cube_args/cube_args_main.cpp).
 #pragma once
 #include <cstddef>
@@ -55,4 +55,14 @@ static inline uint32_t rts_list_copied(uint32_t total, uint32_t max, uint32_t ca
 {
     const uint32_t stored = total < max ? total : max;
     return stored < capacity ? stored : capacity;
+}
+
+// a caller-owned device list of n_list records of 8-byte alignment (null: the handle's own).  0: consistent; 1: n_list without a
+// list; 2: n_list above `most`; 3: the list is not 8-byte aligned
+static inline int rts_device_list_rule(const void* device_list, uint32_t n_list, uint32_t most)
+{
+    if (!device_list && n_list != 0) return 1;
+    if (n_list > most) return 2;
+    if ((uintptr_t)device_list & 7u) return 3;
+    return 0;
 }

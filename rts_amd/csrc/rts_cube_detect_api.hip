@@ -1,6 +1,6 @@
-// rts_cube_detect_api.hip -- the cube part of the C-ABI of include/rts_amd.h, the detection chain: both CFAR detectors and rts_cfar_os_alpha, plots, tracks,
+// rts_cube_detect_api.hip -- the cube part of the C-ABI of include/rts_amd.h, the detection chain: both CFAR detectors and rts_cfar_os_alpha, plots, tracks, multistatic localisation,
 // track-before-detect, and the pure-host evaluators that go with them.  Host code only, no kernels: argument checks, the handle's cube state (RtsCubeState:
-// detect, plot, track, tbd; rts_cube_state.h), the calls of the launchers in the kernels' units.
+// detect, plot, track, locate, tbd; rts_cube_state.h), the calls of the launchers in the kernels' units.
 #include <cmath>
 #include <cstring>
 #include <algorithm>
@@ -360,6 +360,139 @@ extern "C" int rts_cube_tracks_reset(RtsHandle c)
     CHECK_CLOSED(c);
     RTS_TRY(rts_tracks_load(c, nullptr, 0, nullptr));
     c->cube.track.live = false;
+    return RTS_OK;
+}
+
+// ------------------------------------------------------------------------------------- multistatic localisation
+// (rts_amd.h: RtsLocateParams, RtsTarget; the rules and the host evaluator are rts_locate.h, shared with the kernels, rts_locate.hip)
+static int rts_locate_check(const char* who, const RtsLocateParams* p)
+{
+    if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
+    switch (rts_locate_params_check(p)) {
+        case 0: return RTS_OK;
+        case 1: rts_set_error("%s: n_rx = %u (3 .. %u, RTS_LOCATE_MAX_RX)", who, p->n_rx, RTS_LOCATE_MAX_RX); break;
+        case 2: rts_set_error("%s: null rx_positions", who); break;
+        case 3: rts_set_error("%s: tx and rx_positions must be finite", who); break;
+        case 4: rts_set_error("%s: anchors = (%u, %u, %u): three distinct receivers below n_rx = %u", who, p->anchors[0], p->anchors[1], p->anchors[2], p->n_rx); break;
+        case 5: rts_set_error("%s: anchors = (%u, %u, %u): their baselines are collinear", who, p->anchors[0], p->anchors[1], p->anchors[2]); break;
+        case 6: rts_set_error("%s: cspeed = %g (finite, > 0)", who, p->cspeed); break;
+        case 7: rts_set_error("%s: carrier = %g (finite, >= 0)", who, p->carrier); break;
+        case 8: rts_set_error("%s: sigma_delay = %g (finite, > 0)", who, p->sigma_delay); break;
+        case 9: rts_set_error("%s: sigma_doppler = %g (finite, > 0)", who, p->sigma_doppler); break;
+        case 10: rts_set_error("%s: gate = %g (finite, > 0)", who, p->gate); break;
+        case 11: rts_set_error("%s: assoc_delay = %g (finite, > 0)", who, p->assoc_delay); break;
+        case 12: rts_set_error("%s: box_lo, box_hi must be finite with box_lo <= box_hi on every axis", who); break;
+        case 13: rts_set_error("%s: min_receivers = %u (3 .. n_rx = %u)", who, p->min_receivers, p->n_rx); break;
+        case 14: rts_set_error("%s: n_iters = %u > %u (RTS_LOCATE_MAX_ITERS)", who, p->n_iters, RTS_LOCATE_MAX_ITERS); break;
+        case 15: rts_set_error("%s: max_candidates = %u > %u (RTS_LOCATE_MAX_CANDIDATES)", who, p->max_candidates, RTS_LOCATE_MAX_CANDIDATES); break;
+        case 16: rts_set_error("%s: max_targets = %u > %u (RTS_LOCATE_MAX_TARGETS)", who, p->max_targets, RTS_LOCATE_MAX_TARGETS); break;
+        case 17: rts_set_error("%s: unknown source %u (RTS_LOCATE_FROM_PLOTS, _TRACKS, _CANDIDATES)", who, p->source); break;
+        case 18: rts_set_error("%s: n_list = %u without device_list", who, p->n_list); break;
+        case 19: rts_set_error("%s: n_list = %u > %u, the source's limit", who, p->n_list, rts_locate_list_most(p->source)); break;
+        case 20: rts_set_error("%s: device_list is not 8-byte aligned", who); break;
+        case 21: rts_set_error("%s: reserved fields must be 0", who); break;
+        default: rts_set_error("%s: device_list with RTS_LOCATE_FROM_TRACKS (the source is the handle's table)", who); break;
+    }
+    return RTS_ERR_INVALID;
+}
+// what every getter of a locate list says beyond the copy: the candidates or an anchor's segment were cut
+static int rts_locate_cut_check(const char* who, bool cand_cut, bool seg_cut, uint32_t total)
+{
+    if (cand_cut) { rts_set_error("%s: max_candidates cut the accepted candidates: the %u targets resolve the stored prefix", who, total); return RTS_ERR_CAPACITY; }
+    if (seg_cut) { rts_set_error("%s: an anchor's segment holds more than %u records (RTS_LOCATE_MAX_PER_RX): the %u targets use its first ones", who, RTS_LOCATE_MAX_PER_RX, total); return RTS_ERR_CAPACITY; }
+    return RTS_OK;
+}
+
+extern "C" int rts_locate_eval(const RtsLocateParams* p, const void* list, uint32_t n_list, RtsTarget* out, uint32_t capacity, uint32_t* n_out)
+{
+    const char* who = "rts_locate_eval";
+    RTS_TRY(rts_locate_check(who, p));
+    if (!n_out || (capacity && !out)) { rts_set_error("%s: null output", who); return RTS_ERR_INVALID; }
+    switch (rts_device_list_rule(list, n_list, rts_locate_list_most(p->source))) {      // (the rule of p->device_list, on the host list)
+        case 0: break;
+        case 1: rts_set_error("%s: null list with n_list = %u", who, n_list); return RTS_ERR_INVALID;
+        case 2: rts_set_error("%s: n_list = %u > %u", who, n_list, rts_locate_list_most(p->source)); return RTS_ERR_INVALID;
+        default: rts_set_error("%s: list is not 8-byte aligned", who); return RTS_ERR_INVALID;
+    }
+    uint32_t bad = 0;
+    if (p->source == RTS_LOCATE_FROM_PLOTS && rts_locate_plots_check((const RtsPlot*)list, n_list, &bad)) {
+        rts_set_error("%s: list[%u].rx is below list[%u].rx (rx must not decrease)", who, bad, bad - 1u); return RTS_ERR_INVALID; }
+    if (p->source == RTS_LOCATE_FROM_CANDIDATES) switch (rts_locate_candidates_check((const RtsTarget*)list, n_list, &bad)) {
+        case 0: break;
+        case 1: rts_set_error("%s: list[%u].candidate is not above list[%u].candidate", who, bad, bad - 1u); return RTS_ERR_INVALID;
+        case 2: rts_set_error("%s: list[%u] names an index >= %u (RTS_LOCATE_MAX_INDEX)", who, bad, RTS_LOCATE_MAX_INDEX); return RTS_ERR_INVALID;
+        case 3: rts_set_error("%s: list[%u].n_receivers outside 1 .. %u", who, bad, RTS_LOCATE_MAX_RX); return RTS_ERR_INVALID;
+        default: rts_set_error("%s: list[%u].cost is negative or NaN", who, bad); return RTS_ERR_INVALID;
+    }
+    uint32_t cut = 0;
+    const uint32_t total = rts_locate_eval_host(p, list, n_list, out, capacity, &cut), max_t = rts_locate_max_targets(*p);
+    *n_out = total;
+    RTS_TRY(rts_list_fits_check(who, "%s: %u of %u targets written (max_targets %u, capacity %u)", rts_list_copied(total, max_t, capacity), total, max_t, capacity));
+    return rts_locate_cut_check(who, (cut & 1u) != 0u, (cut & 2u) != 0u, total);
+}
+
+extern "C" int rts_cube_locate(RtsHandle c, const RtsLocateParams* p)
+{
+    const char* who = "rts_cube_locate";
+    CHECK_HANDLE(c);
+    RTS_TRY(rts_locate_check(who, p));
+    CHECK_CLOSED(c);
+    RtsCubeState& s = c->cube;
+    const void* list = p->device_list; const void* n_dev = nullptr;
+    uint32_t rcap = p->n_list;
+    if (p->source == RTS_LOCATE_FROM_PLOTS && !list) {
+        if (!s.plot.valid) { rts_set_error("%s: no plots (rts_cube_plots; plots end at the detect calls and rts_cube_attach) and no device_list", who); return RTS_ERR_INVALID; }
+        list = s.plot.d_list.p; n_dev = s.plot.d_off.p + s.plot.cap; rcap = s.plot.max;
+        if (rcap > RTS_LOCATE_MAX_LIST) { rts_set_error("%s: a plot list of %u records > %u (RTS_LOCATE_MAX_LIST)", who, rcap, RTS_LOCATE_MAX_LIST); return RTS_ERR_INVALID; }
+    } else if (p->source == RTS_LOCATE_FROM_TRACKS) {
+        RTS_TRY(rts_cube_track_tables(c));
+        list = s.track.d_tab[s.track.cur].p; n_dev = s.track.d_meta.p + s.track.cur; rcap = s.track.max ? s.track.max : RTS_TRACK_MAX_TRACKS;
+    } else if (p->source == RTS_LOCATE_FROM_CANDIDATES && !list) { rts_set_error("%s: RTS_LOCATE_FROM_CANDIDATES without device_list", who); return RTS_ERR_INVALID; }
+    s.locate.valid = false;
+    const RtsLocateGeo* geo = nullptr;
+    if (p->source != RTS_LOCATE_FROM_CANDIDATES) {                      // the call's constants -> pinned staging -> the device, on the stream
+        const RtsLocateGeo g = rts_locate_geo(*p);
+        RTS_HIP(s.locate.geo.upload(&g, 1, 1, c->stream));
+        geo = s.locate.geo.dev.p;
+    }
+    const uint32_t max_c = rts_locate_max_candidates(*p), max_t = rts_locate_max_targets(*p);
+    RTS_TRY(rts_cube_locate_device(c, *p, geo, list, n_dev, rcap, max_c, max_t));
+    s.locate.max_c = max_c; s.locate.max_t = max_t; s.locate.valid = true;
+    return RTS_OK;
+}
+
+static int rts_locate_meta(RtsContext* c, const char* who, RtsLocateMeta* m)
+{
+    if (!c->cube.locate.valid) { rts_set_error("%s: no targets (rts_cube_locate)", who); return RTS_ERR_INVALID; }
+    RTS_HIP(hipStreamSynchronize(c->stream));
+    RTS_HIP(hipMemcpy(m, c->cube.locate.d_meta.p, sizeof(*m), hipMemcpyDeviceToHost));
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_targets_get(RtsHandle c, RtsTarget* out, uint32_t capacity, uint32_t* n_out)
+{
+    const char* who = "rts_cube_targets_get";
+    CHECK_HANDLE(c);
+    if (!n_out || (capacity && !out)) { rts_set_error("%s: null output", who); return RTS_ERR_INVALID; }
+    RtsLocateState& s = c->cube.locate;
+    RtsLocateMeta m;
+    RTS_TRY(rts_locate_meta(c, who, &m));
+    const uint32_t n = rts_list_copied(m.targets_total, s.max_t, capacity);
+    if (n) RTS_HIP(hipMemcpy(out, s.d_out.p, sizeof(RtsTarget) * n, hipMemcpyDeviceToHost));
+    *n_out = m.targets_total;
+    RTS_TRY(rts_list_fits_check(who, "%s: %u of %u targets copied (max_targets %u, capacity %u)", n, m.targets_total, s.max_t, capacity));
+    return rts_locate_cut_check(who, m.cand_total > s.max_c, m.seg_cut != 0u, m.targets_total);
+}
+
+// the rounds the resolution of the last rts_cube_locate took (tools/locate_bench.py); synchronises
+extern "C" int rts_cube_locate_rounds(RtsHandle c, uint32_t* rounds)
+{
+    const char* who = "rts_cube_locate_rounds";
+    CHECK_HANDLE(c);
+    if (!rounds) { rts_set_error("%s: null output", who); return RTS_ERR_INVALID; }
+    RtsLocateMeta m;
+    RTS_TRY(rts_locate_meta(c, who, &m));
+    *rounds = m.rounds;
     return RTS_OK;
 }
 

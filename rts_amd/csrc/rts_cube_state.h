@@ -10,6 +10,7 @@
 #include "../../include/rts_amd.h"
 #include "rts_owned.h"
 #include "rts_track.h"            // RtsTrackPred
+#include "rts_locate.h"           // RtsLocateGeo
 
 // A derived output of the attached cube (Doppler map, image, spectrogram): `own` when the library allocates it, p / doubles: where the
 // last one went and its size; valid: it is a product of the ATTACHED cube, for its rts_cube_*_get -- every product ends at rts_cube_attach
@@ -67,6 +68,21 @@ struct RtsTrackState {
     DevBuf<uint32_t> d_zrx, d_cj, d_cn, d_of_track, d_of_plot, d_best_t, d_rounds, d_flag, d_off;
     uint32_t cur = 0, max = 0, loaded = 0; bool live = false; double time = 0.0;
 };
+// what the device keeps beside the targets: the candidates accepted and stored, the targets a list without end would hold, the rounds
+// the resolution took, whether an anchor's segment was cut
+struct RtsLocateMeta { uint32_t cand_total, cand_stored, targets_total, rounds, seg_cut, reserved[3]; };
+// multistatic localisation (rts_cube_locate, rts_locate.hip): the copy of the records' four fields in segment order with their list
+// indices and receivers, the segments' bounds and the count; for a track table the flags over [16][table] -> exclusive scan; per
+// (i, j) pair of the anchors' segments its candidates' count -> exclusive scan (offsets; the last element: the total); the candidates;
+// per candidate its state, per record whether it is taken and the round's minimum (16 - K, cost bits, position); the winners' flags
+// -> exclusive scan; the scans' scratch; the targets and their RtsLocateMeta; the call's constants go through a staged upload.  NOT a
+// product of the cube: end_products() leaves them alone.  max_c, max_t: the capacities of the last call; valid: targets exist
+struct RtsLocateState {
+    DevBuf<double> d_zr, d_zf, d_zp; DevBuf<uint64_t> d_best_c; DevBuf<uint8_t> d_tmp;
+    DevBuf<uint32_t> d_zi, d_zrx, d_seg, d_n, d_tflag, d_toff, d_pcnt, d_poff, d_state, d_taken, d_best_k, d_best_i, d_win, d_woff;
+    DevBuf<RtsTarget> d_cand, d_out; DevBuf<RtsLocateMeta> d_meta; StagedUpload<RtsLocateGeo> geo;
+    uint32_t max_c = 0, max_t = 0; bool valid = false;
+};
 // track-before-detect (rts_cube_tbd_step, rts_cube_tbd_extract, rts_tbd.hip): TWO merit maps -- a step reads cur and writes the
 // other -- the ring of depth pointer maps and of their shift tables (frame f in slot f mod depth), all of the shape and
 // window the first step after a reset fixed (frames == 0: no state); the time, and t0 and dt, of the last frame.  The
@@ -123,7 +139,7 @@ struct RtsFocusState {
 // the kernels' units, each on its own family).
 struct RtsCubeState {
     RtsCubeParams params = {}; double* p = nullptr; DevBuf<double> own; bool set = false;      // p: the attached cube, own when the library allocated it
-    RtsWaveState wave; RtsDopplerState doppler; RtsDetectState detect; RtsPlotState plot; RtsTrackState track; RtsTbdState tbd; RtsImageState image; RtsStftState stft;
+    RtsWaveState wave; RtsDopplerState doppler; RtsDetectState detect; RtsPlotState plot; RtsTrackState track; RtsLocateState locate; RtsTbdState tbd; RtsImageState image; RtsStftState stft;
     RtsFmcwState fmcw; RtsBeamState beam; RtsSourceState source; RtsAdaptState adapt; RtsStapState stap; RtsDoaState doa; RtsFocusState focus;
     // every product belongs to the cube it was made from: the Doppler map (which rts_cube_detect may take), the detection list, the plots, the image, the spectrogram, the
     // range transform, the beams, the covariance, the adaptive weights, the space-time filter's output, the eigenpairs, the angular spectrum and the autofocus tables end when another cube is attached

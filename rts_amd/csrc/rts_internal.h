@@ -21,6 +21,7 @@
 #include "rts_stap.h"             // space-time adaptive processing: the stacked snapshot, its covariance's and filter's evaluators, the host-only plan of the filter's launch
 #include "rts_doa.h"              // direction finding: the eigensolver's and the angular scan's trees, the spectra's weights, the source count, their evaluators and the host-only plans of their launches
 #include "rts_cfar_os.h"          // CFAR: what every detector shares (rts_cfar.h: window, training count, local maximum, refinement, record); OS: rank rule, alphas, the host evaluator
+#include "rts_locate.h"           // multistatic localisation: the closed form of a triple, completion, refinement, cost, the resolution's order, the validation, the host evaluator
 #include "rts_track.h"            // the tracker step: wrap, prediction, d2, the edge, the candidate order, update, coast, start, the validation, the host evaluator
 #include "rts_tbd.h"              // track-before-detect: the shift table, the score, the window's first maximum, the candidate, the walk, the record, the validation, the host evaluators
 #include "rts_source.h"           // clutter and jammer sources: pole, scale, draw, recursion, partials and tree, the validation, the host evaluator and the host-only plan of the launch
@@ -100,6 +101,7 @@ static_assert(sizeof(RtsEndRecord) == 112, "end record size");
 static_assert(sizeof(RtsDetection) == 72 && sizeof(RtsCfarParams) == 72 && sizeof(RtsCfarOsParams) == 72, "CFAR ABI sizes (rts_amd/_lib.py mirrors them)");
 static_assert(sizeof(RtsPlot) == 104 && sizeof(RtsPlotParams) == 56, "plot ABI sizes (rts_amd/_lib.py mirrors them)");
 static_assert(sizeof(RtsTrack) == 88 && sizeof(RtsTrackParams) == 96, "track ABI sizes (rts_amd/_lib.py mirrors them)");
+static_assert(sizeof(RtsTarget) == 144 && sizeof(RtsLocateParams) == 192, "locate ABI sizes (rts_amd/_lib.py mirrors them)");
 static_assert(sizeof(RtsTbdParams) == 72 && sizeof(RtsTbdExtractParams) == 40 && sizeof(RtsTbdTrack) == 48, "track-before-detect ABI sizes (rts_amd/_lib.py mirrors them)");
 static_assert(sizeof(RtsSourceParams) == 72, "source ABI size (rts_amd/_lib.py mirrors it)");
 // RtsEndRecord::pad : bits 0-1 chain (output row = chain * n + slot), 2-3 refrDepth, 8-15 (target + 1) of chain 0's
@@ -438,6 +440,8 @@ int rts_cube_plots_device(RtsContext* c, const RtsPlotParams& p, const RtsDetect
 // rts_track.hip.  list: pcap records, of which the first min(pcap, *n_dev) count (n_dev null: all); tcap: the table's size; T: the interval
 int rts_cube_track_tables(RtsContext* c);      // the two tables and their meta records, zeroed on first use
 int rts_cube_track_device(RtsContext* c, const RtsTrackParams& p, double T, const RtsPlot* list, const uint32_t* n_dev, uint32_t pcap, uint32_t tcap);
+// rts_locate.hip.  geo: the call's constants on the device (null: candidates); list, n_dev, rcap: the source's records, their count on the device, their capacity
+int rts_cube_locate_device(RtsContext* c, const RtsLocateParams& p, const RtsLocateGeo* geo, const void* list, const void* n_dev, uint32_t rcap, uint32_t max_c, uint32_t max_t);
 // rts_tbd.hip.  Both on a validated call and a state whose buffers exist; the step writes merit map tbd_cur ^ 1 and ring slot `slot`
 int rts_cube_tbd_step_device(RtsContext* c, const RtsTbdParams& p, const double* map, bool first, double T, double dt, uint32_t slot);
 int rts_cube_tbd_extract_device(RtsContext* c, const RtsTbdExtractParams& e, uint32_t max_tracks);
