@@ -1759,6 +1759,102 @@ int rts_align_eval(const RtsCubeParams* q, const double* cube, const RtsAlignPar
 int rts_pga_eval(const RtsCubeParams* q, const double* cube, const RtsPgaParams* p, double* phase_out, double* rms_out);      /* pure host */
 int rts_correct_eval(const RtsCubeParams* q, double* cube, const RtsCorrectParams* p);                                        /* pure host */
 
+/* ---------------------------------------------------------------- passive radar: reference-channel cancellation and cross-correlation
+ * A passive receiver has no waveform of its own: a transmitter of opportunity sends a noise-like signal that differs in every
+ * coherent row, one receiver (ref_rx, the reference channel) records it, the others (the surveillance channels) record its echoes
+ * under the direct signal and the static clutter, 40 - 80 dB above them.  Two steps turn such a cube [n_rx][n_pulses][n_bins] --
+ * rendered with a new waveform segment per pulse (rts_cube_set_waveform + rts_cube_render with RTS_RENDER_DOPPLER), the reference
+ * row and any direct or clutter terms written by the caller into a caller-owned cube -- into the input of the existing chain:
+ * rts_cube_cancel removes from the surveillance rows what the reference explains, rts_cube_xcorr correlates every row with the
+ * reference row of the same pulse.  The output attached as a cube of n_bins = n_lags, t0 = first_lag * dt, then rts_cube_doppler:
+ * that IS the cross-ambiguity function by the batches algorithm, and detection, plots, tracks and localisation follow unchanged.
+ * The rows are independent batches: a read outside a row is 0.  The arithmetic is rts_amd/csrc/rts_passive.h, shared by the kernels
+ * (rts_passive.hip) and the host evaluators; the trees hold + - * / and sqrt only and the library builds with -ffp-contract=off, so
+ * device and evaluators agree BIT FOR BIT.
+ *
+ * rts_cube_cancel (batch ECA: a least-squares projection, in place on the surveillance rows; the reference rows are never written).
+ *   K = n_taps; x_k[p][n] = ref[p][n - k], +0.0 for n < k.  The span first_pulse .. first_pulse + n_pulses - 1 is cut into blocks of
+ *   rows_per_block consecutive rows (0, or more than n_pulses: the whole span is one block; the last block may be shorter),
+ *   n_blocks = ceil(n_pulses / rows_per_block).  Per block, with the sums over the block's rows p and all bins n:
+ *     G[i][j] = sum conj(x_i) x_j    (K x K Hermitian, the lower triangle j <= i is formed; shared by every receiver)
+ *     b_r[i]  = sum conj(x_i) y_r    (per cancelled receiver r)
+ *     term: a conj(b) = (ar br + ai bi, ai br - ar bi) with b = x_i and a = x_j or y_r; a term whose x is the +0.0 above is formed
+ *       and added like any other.
+ *     The sums' tree: a row is cut into ceil(n_bins / RTS_PASSIVE_TILE) tiles of consecutive bins; the block's tiles, numbered
+ *       row-major, are cut into parts = min(tiles, max(1, RTS_PASSIVE_MAX_PARTS / n_blocks)) parts, part q owning the tiles
+ *       floor(q tiles / parts) .. floor((q + 1) tiles / parts) - 1.  A part's sum runs over its cells in ascending order, the first
+ *       term the start value; the parts are summed in ascending q, part 0 the start value.  A function of the shape alone.
+ *     A = G + loading I (one add per diagonal real part; loading >= 0, finite, in the cube's power units times the block's cells),
+ *       factored and solved as rts_cube_mvdr factors and solves (column Cholesky, forward then back substitution; no division by a
+ *       norm): A c_r = b_r.
+ *     y_r[p][n] <- y_r[p][n] - c_r[0] x_0[p][n] - ... - c_r[K-1] x_{K-1}[p][n], k ascending, each step
+ *       y - c x = (yr - (cr xr - ci xi), yi - (cr xi + ci xr)).
+ *   A FAILED BLOCK: a pivot that is not finite or not > 0 (fewer samples than taps with loading 0, an all-zero or a non-finite
+ *     reference).  The block's rows stay as they are for every receiver, its coefficients are 0, and it is counted.
+ *   rx_mask: bit r set: receiver r is cancelled; 0: every receiver but ref_rx.  The rows of the others stay bit-identical.
+ *   The block length is the notch: coefficients estimated per block remove everything inside the K lags whose phase turns by less
+ *     than about one cycle over the block, so rows_per_block rows give a Doppler notch of about 1 / (rows_per_block PRI) around 0.  A
+ *     target survives at a lag >= K, or at a Doppler of several cycles per block.
+ *   rts_cube_cancel_info: n_blocks and the failed blocks of the last call.  The failed blocks are counted from the blocks' pivot
+ *   words on the device at every call: a stream synchronisation and a blocking copy of n_blocks words, a device round trip (pass
+ *   n_failed_out NULL to skip it).  rts_cube_cancel_coeffs_get: the
+ *   coefficients, complex128 [n_rx][n_blocks][K]; the slots of ref_rx and of receivers outside the mask hold zeros.  Both end at
+ *   rts_cube_attach.  The other products of the cube are not invalidated (as with rts_cube_compress).
+ * rts_cube_xcorr (out of place).  For every receiver r -- ref_rx too: its row is the reference's autocorrelation, by which a
+ *   caller judges the waveform -- and every row p of the span:
+ *     z[r][p][l - first_lag] = sum_{n = 0}^{n_bins - 1 - l} y_r[p][n + l] conj(ref[p][n]),   l = first_lag .. first_lag + n_lags - 1
+ *   n ascending, the first term the start value, the term the one above with a = y, b = ref; a lag at or beyond n_bins gives
+ *   (+0.0, +0.0).  Output complex128 [n_rx][n_pulses (the span's)][n_lags] into device_out (caller-owned device memory, 16-byte
+ *   aligned, apart from the cube) or, with NULL, library-owned memory that rts_cube_xcorr_get copies; it ends at rts_cube_attach.
+ *   Limits: n_bins <= RTS_COMPRESS_MAX_BINS, n_lags <= RTS_XCORR_MAX_LAGS, first_lag <= RTS_XCORR_MAX_FIRST_LAG, at most 65 535
+ *   receivers and span rows.  The surveillance row passes through a workgroup's LDS in windows of 256 + 256 samples (8 KiB of the
+ *   160 KiB a gfx950 workgroup may allocate), one thread per lag: LDS bounds neither n_bins nor n_lags.  The cancellation's workgroups
+ *   hold a tile with its K - 1 samples of history (at most 319 complex128: 5 104 bytes) and, in the solve, the factor and the work
+ *   vectors (16 K K + 1 024 K bytes: 128 KiB at K = 64).
+ * The calls are enqueued on the handle's stream and never wait for the device's earlier work.
+ * RTS_ERR_INVALID, the message naming the field: no cube attached; NULL p; a cube that is not 16-byte aligned.  rts_cube_cancel,
+ *   rts_cancel_eval: (1) nonzero reserved fields; (2) more than RTS_PASSIVE_MAX_RX receivers; (3) ref_rx >= n_rx; (4) n_taps outside
+ *   1 .. RTS_PASSIVE_MAX_TAPS; (5) a span of no pulse or outside the cube; (6) a loading that is negative or not finite; (7) ref_rx
+ *   inside rx_mask; (8) rx_mask naming a receiver the cube does not have; (9) more than RTS_PASSIVE_MAX_BLOCKS blocks.
+ *   rts_cube_xcorr, rts_xcorr_eval: (1) nonzero reserved fields; (2) ref_rx >= n_rx; (3) a span of no pulse or outside the cube;
+ *   (4) n_lags outside 1 .. RTS_XCORR_MAX_LAGS; (5) first_lag above RTS_XCORR_MAX_FIRST_LAG; (6) n_bins above RTS_COMPRESS_MAX_BINS;
+ *   (7) more than 65 535 receivers or span rows; and a misaligned device_out or one that overlaps the cube.  The getters: nothing to
+ *   return (no call yet, or an rts_cube_attach since), a NULL output; RTS_ERR_CAPACITY when the capacity is too small.  A refused
+ *   call leaves the cube and the handle's products as they were.
+ * rts_cancel_eval / rts_xcorr_eval: pure host, no device: the same rts_passive.h functions on host arrays of the cube's layout, q its
+ *   shape.  rts_cancel_eval works in place on cube_inout; coeffs_out ([n_rx][n_blocks][K] complex128), n_blocks_out and n_failed_out
+ *   may each be NULL. */
+#define RTS_PASSIVE_MAX_TAPS    64u      /* K                                                                                  */
+#define RTS_PASSIVE_MAX_RX      64u      /* the bits of rx_mask                                                                */
+#define RTS_PASSIVE_TILE        256u     /* bins per tile of the sums' tree                                                    */
+#define RTS_PASSIVE_MAX_PARTS   512u     /* parts of all blocks together, while a block has at least one                       */
+#define RTS_PASSIVE_MAX_BLOCKS  4096u    /* the parts' scratch is blocks * parts * (K (K + 1) / 2 + n_rx K) * 16 bytes         */
+#define RTS_XCORR_MAX_LAGS      16384u
+#define RTS_XCORR_MAX_FIRST_LAG 0x7fff0000u
+typedef struct RtsCancelParams {
+    uint32_t ref_rx, n_taps;         /* the reference channel; K: 1 .. RTS_PASSIVE_MAX_TAPS                          */
+    uint32_t first_pulse, n_pulses;  /* the span: at least one pulse                                                 */
+    uint32_t rows_per_block;         /* 0: the whole span is one block                                               */
+    uint32_t reserved0;              /* 0 */
+    uint64_t rx_mask;                /* the receivers cancelled; 0: all but ref_rx                                   */
+    double loading;                  /* >= 0, finite: added to G's diagonal                                          */
+    uint64_t reserved[2];            /* 0 */
+} RtsCancelParams;                                            /* 56 bytes */
+typedef struct RtsXcorrParams {
+    uint32_t ref_rx, reserved0;      /* the reference channel; 0                                                     */
+    uint32_t first_pulse, n_pulses;  /* the span: at least one pulse                                                 */
+    uint32_t first_lag, n_lags;      /* lags first_lag .. first_lag + n_lags - 1                                     */
+    uint64_t reserved[2];            /* 0 */
+} RtsXcorrParams;                                             /* 40 bytes */
+int rts_cube_cancel(RtsHandle h, const RtsCancelParams* p);
+int rts_cube_cancel_info(RtsHandle h, uint32_t* n_blocks_out, uint32_t* n_failed_out);
+int rts_cube_cancel_coeffs_get(RtsHandle h, double* host_out, uint64_t capacity_doubles);   /* complex128 [n_rx][n_blocks][K] */
+int rts_cancel_eval(const RtsCubeParams* q, double* cube_inout, const RtsCancelParams* p, double* coeffs_out, uint32_t* n_blocks_out,
+                    uint32_t* n_failed_out);                                                                                  /* pure host */
+int rts_cube_xcorr(RtsHandle h, const RtsXcorrParams* p, void* device_out);                 /* complex128 [n_rx][n_pulses][n_lags] */
+int rts_cube_xcorr_get(RtsHandle h, double* host_out, uint64_t capacity_doubles);
+int rts_xcorr_eval(const RtsCubeParams* q, const double* cube, const RtsXcorrParams* p, double* out);                        /* pure host */
+
 /* ---------------------------------------------------------------- several GPUs (not in the reference: it is single-GPU)
  * Rays are independent (each launch index writes only its own rows, ray_tracer.cu:227-253) and so are pulses
  * (ray_tracer.cpp:843).  rts_plan_cpi deals the n_pulses x total_rays (pulse, launch index) pairs of one coherent

@@ -316,6 +316,25 @@ class RtsMvdrParams(C.Structure):
 assert C.sizeof(RtsCovParams) == 56 and C.sizeof(RtsMvdrParams) == 48
 
 
+# passive radar (include/rts_amd.h)
+RTS_PASSIVE_MAX_TAPS, RTS_PASSIVE_MAX_RX, RTS_PASSIVE_TILE, RTS_PASSIVE_MAX_PARTS, RTS_PASSIVE_MAX_BLOCKS = 64, 64, 256, 512, 4096
+RTS_XCORR_MAX_LAGS, RTS_XCORR_MAX_FIRST_LAG = 16384, 0x7fff0000
+
+
+class RtsCancelParams(C.Structure):
+    _fields_ = [("ref_rx", C.c_uint32), ("n_taps", C.c_uint32), ("first_pulse", C.c_uint32), ("n_pulses", C.c_uint32),
+                ("rows_per_block", C.c_uint32), ("reserved0", C.c_uint32), ("rx_mask", C.c_uint64), ("loading", C.c_double),
+                ("reserved", C.c_uint64 * 2)]
+
+
+class RtsXcorrParams(C.Structure):
+    _fields_ = [("ref_rx", C.c_uint32), ("reserved0", C.c_uint32), ("first_pulse", C.c_uint32), ("n_pulses", C.c_uint32),
+                ("first_lag", C.c_uint32), ("n_lags", C.c_uint32), ("reserved", C.c_uint64 * 2)]
+
+
+assert C.sizeof(RtsCancelParams) == 56 and C.sizeof(RtsXcorrParams) == 40
+
+
 RTS_ST_MAX_TAPS = 16
 
 
@@ -452,7 +471,8 @@ EXPORTS = ["rts_create", "rts_destroy", "rts_last_error", "rts_device_count", "r
            "rts_cube_beamform", "rts_cube_beam_get", "rts_beamform_eval", "rts_steering_make",
            "rts_cube_covariance", "rts_cube_covariance_get", "rts_covariance_eval", "rts_cube_mvdr", "rts_cube_mvdr_get", "rts_mvdr_eval",
            "rts_cube_st_covariance", "rts_st_covariance_eval", "rts_cube_st_apply", "rts_cube_st_get", "rts_st_apply_eval", "rts_st_steering_make",
-           "rts_cube_eig", "rts_cube_eig_get", "rts_eig_eval", "rts_cube_doa_scan", "rts_cube_doa_get", "rts_doa_scan_eval", "rts_doa_weights", "rts_source_count"]
+           "rts_cube_eig", "rts_cube_eig_get", "rts_eig_eval", "rts_cube_doa_scan", "rts_cube_doa_get", "rts_doa_scan_eval", "rts_doa_weights", "rts_source_count",
+           "rts_cube_cancel", "rts_cube_cancel_info", "rts_cube_cancel_coeffs_get", "rts_cancel_eval", "rts_cube_xcorr", "rts_cube_xcorr_get", "rts_xcorr_eval"]
 
 
 def lib():
@@ -583,6 +603,13 @@ def lib():
         "rts_cube_mvdr": [vp, C.POINTER(RtsMvdrParams), vp],
         "rts_cube_mvdr_get": [vp, vp, u64],
         "rts_mvdr_eval": [vp, u32, C.POINTER(RtsMvdrParams), vp],
+        "rts_cube_cancel": [vp, C.POINTER(RtsCancelParams)],
+        "rts_cube_cancel_info": [vp, C.POINTER(u32), C.POINTER(u32)],
+        "rts_cube_cancel_coeffs_get": [vp, vp, u64],
+        "rts_cancel_eval": [C.POINTER(RtsCubeParams), vp, C.POINTER(RtsCancelParams), vp, C.POINTER(u32), C.POINTER(u32)],
+        "rts_cube_xcorr": [vp, C.POINTER(RtsXcorrParams), vp],
+        "rts_cube_xcorr_get": [vp, vp, u64],
+        "rts_xcorr_eval": [C.POINTER(RtsCubeParams), vp, C.POINTER(RtsXcorrParams), vp],
         "rts_cube_st_covariance": [vp, C.POINTER(RtsStCovParams), vp],
         "rts_st_covariance_eval": [C.POINTER(RtsCubeParams), vp, u32, C.POINTER(RtsStCovParams), vp],
         "rts_cube_st_apply": [vp, C.POINTER(RtsStApplyParams), vp],

@@ -811,6 +811,65 @@ def mvdr_eval(cov, steering, loading=0.0):
     return out
 
 
+def _rx_mask(rx):
+    """RtsCancelParams.rx_mask: None (0: every receiver but the reference), an integer mask, or the receivers' indices"""
+    if rx is None:
+        return 0
+    if isinstance(rx, (int, np.integer)):
+        return int(rx)
+    m = 0
+    for r in rx:
+        m |= 1 << int(r)
+    return m
+
+
+def _cancel_params(ref_rx, n_taps, first, count, rows_per_block, rx, loading, n_pulses_cube):
+    p = L.RtsCancelParams()
+    p.ref_rx, p.n_taps, p.first_pulse = int(ref_rx), int(n_taps), int(first)
+    p.n_pulses = int(n_pulses_cube - first if count is None else count)
+    p.rows_per_block, p.rx_mask, p.loading = int(rows_per_block), _rx_mask(rx), float(loading)
+    return p
+
+
+def _xcorr_params(ref_rx, n_lags, first_lag, first, count, n_pulses_cube):
+    p = L.RtsXcorrParams()
+    p.ref_rx, p.first_pulse, p.n_pulses = int(ref_rx), int(first), int(n_pulses_cube - first if count is None else count)
+    p.first_lag, p.n_lags = int(first_lag), int(n_lags)
+    return p
+
+
+def _cancel_blocks(n_rows, rows_per_block):
+    R = n_rows if rows_per_block == 0 or rows_per_block > n_rows else rows_per_block
+    return (n_rows + R - 1) // R
+
+
+def cancel_eval(cube, ref_rx, n_taps, rows_per_block=0, first=0, count=None, rx=None, loading=0.0):
+    """rts_cancel_eval (pure host): batch ECA of a host cube [n_rx][n_pulses][n_bins] (complex) -- per block of rows_per_block rows
+    (0: the whole span) of rows first .. first + count - 1 the least-squares fit of the n_taps lagged copies of receiver ref_rx's row
+    is subtracted from the receivers rx (None: all but ref_rx; indices or a mask).  Returns (the cancelled cube, the coefficients
+    complex [n_rx][n_blocks][n_taps], (n_blocks, n_failed))"""
+    out = np.ascontiguousarray(np.array(cube, np.complex128))
+    n_rx, n_p, nb = out.shape
+    q = L.RtsCubeParams(n_rx, n_p, nb, 0, 0.0, 1.0)
+    p = _cancel_params(ref_rx, n_taps, first, count, rows_per_block, rx, loading, n_p)
+    coeffs = np.zeros((n_rx, max(_cancel_blocks(max(p.n_pulses, 1), p.rows_per_block), 1), max(p.n_taps, 1)), np.complex128)
+    nblk, nfail = C.c_uint32(0), C.c_uint32(0)
+    check(L.lib().rts_cancel_eval(C.byref(q), ptr(out.view(np.float64)), C.byref(p), ptr(coeffs.view(np.float64)), C.byref(nblk), C.byref(nfail)))
+    return out, coeffs, (nblk.value, nfail.value)
+
+
+def xcorr_eval(cube, ref_rx, n_lags, first_lag=0, first=0, count=None):
+    """rts_xcorr_eval (pure host): z[r][p][l - first_lag] = sum_n y_r[p][n + l] conj(ref[p][n]) of a host cube [n_rx][n_pulses][n_bins]
+    (complex) with ref the row of receiver ref_rx, over rows first .. first + count - 1: complex [n_rx][count][n_lags]"""
+    cube = np.ascontiguousarray(np.asarray(cube, np.complex128))
+    n_rx, n_p, nb = cube.shape
+    q = L.RtsCubeParams(n_rx, n_p, nb, 0, 0.0, 1.0)
+    p = _xcorr_params(ref_rx, n_lags, first_lag, first, count, n_p)
+    out = np.zeros((n_rx, max(p.n_pulses, 1), max(p.n_lags, 1)), np.complex128)
+    check(L.lib().rts_xcorr_eval(C.byref(q), ptr(cube.view(np.float64)), C.byref(p), ptr(out.view(np.float64))))
+    return out
+
+
 def eig_eval(cov, sweeps=False):
     """rts_eig_eval (pure host): the eigenpairs of a Hermitian matrix complex [n][n] (its lower triangle and the real part of its
     diagonal are read) by one-sided Jacobi: (eigenvalues float64 [n] in descending order, eigenvectors complex [n][n], ROW k the
@@ -1473,6 +1532,54 @@ class Tracer:
         if count is None:
             count = self._cube_shape[1] - first
         check(L.lib().rts_cube_compress(self.h, first, count))
+
+    def cube_cancel(self, ref_rx, n_taps, rows_per_block=0, first=0, count=None, rx=None, loading=0.0):
+        """rts_cube_cancel: batch ECA in place on the attached cube -- per block of rows_per_block rows (0: the whole span) of rows
+        first .. first + count - 1 (default: to the last pulse) the least-squares fit of the n_taps lagged copies of receiver
+        ref_rx's row is subtracted from the receivers rx (None: all but ref_rx; indices or a mask).  The block length is the Doppler
+        notch: about one cycle per block around 0, over the lags below n_taps"""
+        p = _cancel_params(ref_rx, n_taps, first, count, rows_per_block, rx, loading, self._cube_shape[1])
+        check(L.lib().rts_cube_cancel(self.h, C.byref(p)))
+        self._cancel_shape = (self._cube_shape[0], _cancel_blocks(p.n_pulses, p.rows_per_block), p.n_taps)
+
+    def cancel_info(self):
+        """rts_cube_cancel_info: (n_blocks, n_failed) of the last cube_cancel; a failed block (a pivot of the factor not finite or
+        not > 0) was left unchanged and its coefficients are 0"""
+        nblk, nfail = C.c_uint32(0), C.c_uint32(0)
+        check(L.lib().rts_cube_cancel_info(self.h, C.byref(nblk), C.byref(nfail)))
+        return nblk.value, nfail.value
+
+    def cancel_coeffs(self):
+        """rts_cube_cancel_coeffs_get: the coefficients of the last cube_cancel, complex [n_rx][n_blocks][n_taps] (zeros for the
+        reference and for receivers that were not cancelled)"""
+        out = np.zeros(getattr(self, "_cancel_shape", None) or (1, 1, 1), np.complex128)
+        check(L.lib().rts_cube_cancel_coeffs_get(self.h, ptr(out.view(np.float64)), 2 * out.size))
+        return out
+
+    def cube_xcorr(self, ref_rx, n_lags, first_lag=0, first=0, count=None, device_ptr=None, fetch=True):
+        """rts_cube_xcorr: every row of rows first .. first + count - 1 (default: to the last pulse) of every receiver correlated with
+        receiver ref_rx's row of the same pulse at the lags first_lag .. first_lag + n_lags - 1: complex [n_rx][count][n_lags], into
+        a caller complex128 device tensor (device_ptr; nothing is fetched) or the library's output, returned when fetch.  Attached
+        as a cube of n_bins = n_lags, t0 = first_lag * dt, cube_doppler makes the range-Doppler map of it"""
+        p = _xcorr_params(ref_rx, n_lags, first_lag, first, count, self._cube_shape[1])
+        check(L.lib().rts_cube_xcorr(self.h, C.byref(p), C.c_void_p(device_ptr) if device_ptr else None))
+        if device_ptr:
+            return None
+        self._xcorr_shape = (self._cube_shape[0], p.n_pulses, p.n_lags)
+        return self.xcorr_map() if fetch else None
+
+    def xcorr_map(self):
+        """rts_cube_xcorr_get: the library-owned output of the last cube_xcorr, complex [n_rx][count][n_lags]"""
+        out = np.zeros(getattr(self, "_xcorr_shape", None) or (1, 1, 1), np.complex128)
+        check(L.lib().rts_cube_xcorr_get(self.h, ptr(out.view(np.float64)), 2 * out.size))
+        return out
+
+    def cube_passive(self, ref_rx, n_taps, n_lags, rows_per_block=0, first_lag=0, first=0, count=None, rx=None, loading=0.0, device_ptr=None,
+                     fetch=True):
+        """cube_cancel(ref_rx, n_taps, rows_per_block, first, count, rx, loading) -> cube_xcorr(ref_rx, n_lags, first_lag, first,
+        count, device_ptr, fetch): the passive radar's two steps on the attached cube; returns cube_xcorr's result"""
+        self.cube_cancel(ref_rx, n_taps, rows_per_block, first, count, rx, loading)
+        return self.cube_xcorr(ref_rx, n_lags, first_lag, first, count, device_ptr, fetch)
 
     def cube_add_noise(self, noise_power, seed, first=0, count=None):
         """rts_cube_add_noise: complex Gaussian noise of power noise_power (E|n|^2) added to rows first .. first + count - 1 (default:

@@ -137,23 +137,35 @@ RTS_HD void rts_mvdr_below(double* L, uint32_t ld, uint32_t i, uint32_t j, doubl
         rts_adapt_sub_term(L[2 * ((size_t)i * ld + k)], L[2 * ((size_t)i * ld + k) + 1], L[2 * ((size_t)j * ld + k)], L[2 * ((size_t)j * ld + k) + 1], &xr, &xi);
     L[2 * ((size_t)i * ld + j)] = xr / ljj; L[2 * ((size_t)i * ld + j) + 1] = xi / ljj;
 }
-// one beam: s [n] interleaved -> w [n] interleaved; x: the beam's work vector [n], element k at x[2 k xs], x[2 k xs + 1]
-RTS_HD void rts_mvdr_beam(const double* L, uint32_t ld, uint32_t n, const double* s, double* x, size_t xs, double* w)
+// the two substitutions on a factor, shared by the beams below and by rts_passive.h's coefficient solve.  x: the work vector [n],
+// element k at x[2 k xs], x[2 k xs + 1]
+// forward: x = L^-1 s, s [n] interleaved
+RTS_HD void rts_chol_forward(const double* L, uint32_t ld, uint32_t n, const double* s, double* x, size_t xs)
 {
-    for (uint32_t i = 0; i < n; i++) {                   // forward: u = L^-1 s
+    for (uint32_t i = 0; i < n; i++) {
         double xr = s[2 * i], xi = s[2 * i + 1];
         for (uint32_t k = 0; k < i; k++) rts_adapt_sub_mul(L[2 * ((size_t)i * ld + k)], L[2 * ((size_t)i * ld + k) + 1], x[2 * k * xs], x[2 * k * xs + 1], &xr, &xi);
         const double lii = L[2 * ((size_t)i * ld + i)];
         x[2 * i * xs] = xr / lii; x[2 * i * xs + 1] = xi / lii;
     }
-    double den = rts_adapt_abs2(x[0], x[1]);
-    for (uint32_t k = 1; k < n; k++) den += rts_adapt_abs2(x[2 * k * xs], x[2 * k * xs + 1]);
-    for (uint32_t i = n; i-- > 0u;) {                    // back: v = L^-H u, in place
+}
+// back: x = L^-H x, in place
+RTS_HD void rts_chol_back(const double* L, uint32_t ld, uint32_t n, double* x, size_t xs)
+{
+    for (uint32_t i = n; i-- > 0u;) {
         double xr = x[2 * i * xs], xi = x[2 * i * xs + 1];
         for (uint32_t k = i + 1u; k < n; k++) rts_adapt_sub_conj_mul(L[2 * ((size_t)k * ld + i)], L[2 * ((size_t)k * ld + i) + 1], x[2 * k * xs], x[2 * k * xs + 1], &xr, &xi);
         const double lii = L[2 * ((size_t)i * ld + i)];
         x[2 * i * xs] = xr / lii; x[2 * i * xs + 1] = xi / lii;
     }
+}
+// one beam: s [n] interleaved -> w [n] interleaved; x: the beam's work vector
+RTS_HD void rts_mvdr_beam(const double* L, uint32_t ld, uint32_t n, const double* s, double* x, size_t xs, double* w)
+{
+    rts_chol_forward(L, ld, n, s, x, xs);                // u = L^-1 s
+    double den = rts_adapt_abs2(x[0], x[1]);
+    for (uint32_t k = 1; k < n; k++) den += rts_adapt_abs2(x[2 * k * xs], x[2 * k * xs + 1]);
+    rts_chol_back(L, ld, n, x, xs);                      // v = L^-H u
     for (uint32_t i = 0; i < n; i++) { w[2 * i] = x[2 * i * xs] / den; w[2 * i + 1] = x[2 * i * xs + 1] / den; }
 }
 
@@ -181,6 +193,18 @@ static inline void rts_cov_eval_host(uint32_t n_rx, uint32_t row_bins, const dou
         else { out[2 * ((size_t)i * n_rx + j)] = sr; out[2 * ((size_t)i * n_rx + j) + 1] = si; out[2 * ((size_t)j * n_rx + i)] = sr; out[2 * ((size_t)j * n_rx + i) + 1] = -si; }
     }
 }
+// the column Cholesky of the lower triangle of A [n][n] in place, on the host.  Returns -1, or the column of the pivot that failed
+static inline int rts_chol_factor_host(double* L, uint32_t n)
+{
+    for (uint32_t j = 0; j < n; j++) {
+        const double d = rts_mvdr_pivot(L, n, j);
+        if (!rts_adapt_pivot_ok(d)) return (int)j;
+        const double ljj = sqrt(d);
+        L[2 * ((size_t)j * n + j)] = ljj;
+        for (uint32_t i = j + 1u; i < n; i++) rts_mvdr_below(L, n, i, j, ljj);
+    }
+    return -1;
+}
 // the solve on the host: cov [n][n], steering [n_beams][n] -> out [n_beams][n]; L: 2 n n doubles of work, x: 2 n.  Returns -1, or the
 // column of the pivot that failed (out untouched)
 static inline int rts_mvdr_eval_host(const double* cov, uint32_t n, uint32_t n_beams, const double* steering, double loading, double* L, double* x, double* out)
@@ -190,13 +214,8 @@ static inline int rts_mvdr_eval_host(const double* cov, uint32_t n, uint32_t n_b
         L[2 * ((size_t)i * n + j)] = i == j ? re + loading : re;
         L[2 * ((size_t)i * n + j) + 1] = i == j ? 0.0 : cov[2 * ((size_t)i * n + j) + 1];       // (the diagonal's imaginary part is never used)
     }
-    for (uint32_t j = 0; j < n; j++) {
-        const double d = rts_mvdr_pivot(L, n, j);
-        if (!rts_adapt_pivot_ok(d)) return (int)j;
-        const double ljj = sqrt(d);
-        L[2 * ((size_t)j * n + j)] = ljj;
-        for (uint32_t i = j + 1u; i < n; i++) rts_mvdr_below(L, n, i, j, ljj);
-    }
+    const int bad = rts_chol_factor_host(L, n);
+    if (bad >= 0) return bad;
     for (uint32_t b = 0; b < n_beams; b++) rts_mvdr_beam(L, n, n, steering + 2 * (size_t)b * n, x, 1u, out + 2 * (size_t)b * n);
     return -1;
 }

@@ -1,5 +1,5 @@
 // rts_cube_api.hip -- the cube part of the C-ABI of include/rts_amd.h, first of three host units: the cube and the signal in it -- attach, accumulate,
-// Doppler and get; waveform, render, compress; noise; clutter and jammer sources; spectrogram; autofocus; FMCW; backprojection -- and the pure-host evaluators
+// Doppler and get; waveform, render, compress; passive cancellation and cross-correlation; noise; clutter and jammer sources; spectrogram; autofocus; FMCW; backprojection -- and the pure-host evaluators
 // that go with them (rts_cube_reduce apart: rts_api.hip; the detection chain: rts_cube_detect_api.hip; the receive array: rts_cube_array_api.hip).
 // Host code only, no kernels: argument checks, the handle's cube state (RtsCubeState, rts_cube_state.h), the calls of the launchers in the kernels' units.
 #include <cmath>
@@ -138,6 +138,146 @@ extern "C" int rts_cube_compress(RtsHandle c, uint32_t first_pulse, uint32_t n_p
     RTS_TRY(rts_pulses_check("rts_cube_compress", first_pulse, n_pulses, q.n_pulses, false));
     if (q.n_bins > RTS_COMPRESS_MAX_BINS) { rts_set_error("rts_cube_compress: %u range bins > %u (RTS_COMPRESS_MAX_BINS: one row of complex128 in a workgroup's LDS)", q.n_bins, RTS_COMPRESS_MAX_BINS); return RTS_ERR_INVALID; }
     return rts_cube_compress_device(c, first_pulse, n_pulses);
+}
+
+// ------------------------------------------------------------------------------------- passive radar: reference-channel cancellation, cross-correlation
+// (rts_amd.h: RtsCancelParams, RtsXcorrParams; the rules, the plans and the host evaluators are rts_passive.h, shared with the kernels, rts_passive.hip)
+static int rts_cancel_check(const RtsCancelParams* p, const RtsCubeParams& q, const char* who, RtsCancelPlan* plan)
+{
+    if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
+    switch (rts_cancel_rule(p, q.n_rx, q.n_pulses)) {
+        case 0: break;
+        case 1: rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID;
+        case 2: rts_set_error("%s: n_rx = %u receivers: more than %u (RTS_PASSIVE_MAX_RX: the bits of rx_mask)", who, q.n_rx, RTS_PASSIVE_MAX_RX); return RTS_ERR_INVALID;
+        case 3: rts_set_error("%s: ref_rx = %u >= the cube's %u receivers", who, p->ref_rx, q.n_rx); return RTS_ERR_INVALID;
+        case 4: rts_set_error("%s: n_taps = %u (1 .. %u, RTS_PASSIVE_MAX_TAPS)", who, p->n_taps, RTS_PASSIVE_MAX_TAPS); return RTS_ERR_INVALID;
+        case 5: return rts_pulses_check(who, p->first_pulse, p->n_pulses, q.n_pulses, true);
+        case 6: rts_set_error("%s: loading = %g (finite, >= 0)", who, p->loading); return RTS_ERR_INVALID;
+        case 7: rts_set_error("%s: rx_mask = 0x%llx names ref_rx = %u (the reference rows are never written)", who, (unsigned long long)p->rx_mask, p->ref_rx); return RTS_ERR_INVALID;
+        case 8: rts_set_error("%s: rx_mask = 0x%llx names a receiver beyond the cube's %u", who, (unsigned long long)p->rx_mask, q.n_rx); return RTS_ERR_INVALID;
+        default: rts_set_error("%s: n_pulses = %u in blocks of rows_per_block = %u: more than %u blocks (RTS_PASSIVE_MAX_BLOCKS)", who, p->n_pulses, p->rows_per_block, RTS_PASSIVE_MAX_BLOCKS); return RTS_ERR_INVALID;
+    }
+    *plan = rts_cancel_plan(q.n_rx, q.n_bins, p->n_pulses, p->rows_per_block, p->n_taps);
+    if (!plan->supported) { rts_set_error("%s: a cube of %u receivers x %u bins with %u taps has no launch plan", who, q.n_rx, q.n_bins, p->n_taps); return RTS_ERR_INVALID; }
+    return RTS_OK;
+}
+
+static int rts_xcorr_check(const RtsXcorrParams* p, const RtsCubeParams& q, const char* who, RtsXcorrPlan* plan)
+{
+    if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
+    switch (rts_xcorr_rule(p, q.n_rx, q.n_pulses, q.n_bins)) {
+        case 0: break;
+        case 1: rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID;
+        case 2: rts_set_error("%s: ref_rx = %u >= the cube's %u receivers", who, p->ref_rx, q.n_rx); return RTS_ERR_INVALID;
+        case 3: return rts_pulses_check(who, p->first_pulse, p->n_pulses, q.n_pulses, true);
+        case 4: rts_set_error("%s: n_lags = %u (1 .. %u, RTS_XCORR_MAX_LAGS)", who, p->n_lags, RTS_XCORR_MAX_LAGS); return RTS_ERR_INVALID;
+        case 5: rts_set_error("%s: first_lag = %u (0 .. %u, RTS_XCORR_MAX_FIRST_LAG)", who, p->first_lag, RTS_XCORR_MAX_FIRST_LAG); return RTS_ERR_INVALID;
+        case 6: rts_set_error("%s: %u range bins > %u (RTS_COMPRESS_MAX_BINS)", who, q.n_bins, RTS_COMPRESS_MAX_BINS); return RTS_ERR_INVALID;
+        default: rts_set_error("%s: n_rx = %u receivers x n_pulses = %u rows: more than 65535 of either (the launch grid)", who, q.n_rx, p->n_pulses); return RTS_ERR_INVALID;
+    }
+    *plan = rts_xcorr_plan(q.n_rx, p->n_pulses, p->n_lags);
+    if (!plan->supported) { rts_set_error("%s: %u receivers x %u rows x %u lags have no launch plan", who, q.n_rx, p->n_pulses, p->n_lags); return RTS_ERR_INVALID; }
+    return RTS_OK;
+}
+
+extern "C" int rts_cancel_eval(const RtsCubeParams* q, double* cube_inout, const RtsCancelParams* p, double* coeffs_out, uint32_t* n_blocks_out, uint32_t* n_failed_out)
+{
+    const char* who = "rts_cancel_eval";
+    RTS_TRY(rts_eval_cube_check(who, q, true, false));
+    RtsCancelPlan plan;
+    RTS_TRY(rts_cancel_check(p, *q, who, &plan));
+    if (!cube_inout) { rts_set_error("%s: null cube", who); return RTS_ERR_INVALID; }
+    std::vector<double> work(rts_cancel_work_doubles(plan.K));
+    uint32_t failed = 0;
+    rts_cancel_eval_host(q, cube_inout, p, plan, coeffs_out, &failed, work.data());
+    if (n_blocks_out) *n_blocks_out = plan.n_blocks;
+    if (n_failed_out) *n_failed_out = failed;
+    return RTS_OK;
+}
+
+extern "C" int rts_xcorr_eval(const RtsCubeParams* q, const double* cube, const RtsXcorrParams* p, double* out)
+{
+    const char* who = "rts_xcorr_eval";
+    RTS_TRY(rts_eval_cube_check(who, q, true, false));
+    RtsXcorrPlan plan;
+    RTS_TRY(rts_xcorr_check(p, *q, who, &plan));
+    if (!cube || !out) { rts_set_error("%s: null cube or output array", who); return RTS_ERR_INVALID; }
+    rts_xcorr_eval_host(q, cube, p, out);
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_cancel(RtsHandle c, const RtsCancelParams* p)
+{
+    const char* who = "rts_cube_cancel";
+    CHECK_HANDLE(c);
+    NEED_CUBE(c, who, "no cube (call rts_cube_attach first)");
+    const RtsCubeParams& q = c->cube.params;
+    RtsCancelPlan plan;
+    RTS_TRY(rts_cancel_check(p, q, who, &plan));
+    if ((uintptr_t)c->cube.p & 15u) { rts_set_error("%s: the cube's device memory is not 16-byte aligned", who); return RTS_ERR_INVALID; }
+    CHECK_CLOSED(c);
+    RtsPassiveState& s = c->cube.passive;
+    // (mask, loading and shape are all the kernels read beside the cube: they travel as launch arguments, so this family has no staged upload)
+    s.cancel_valid = false;                                    // a regrow frees what the record names; it is valid again once the launches are enqueued
+    RTS_HIP(s.d_part.reserve(plan.scratch_doubles));
+    RTS_HIP(s.d_sums.reserve(plan.sums_doubles));
+    RTS_HIP(s.d_coeff.reserve(plan.coeff_doubles));
+    RTS_HIP(s.d_fail.reserve(plan.n_blocks));
+    RTS_TRY(rts_cube_cancel_device(c, *p, plan, rts_passive_mask(p->rx_mask, p->ref_rx, q.n_rx)));
+    s.n_blocks = plan.n_blocks; s.n_taps = plan.K; s.n_rx = q.n_rx; s.cancel_valid = true;
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_cancel_info(RtsHandle c, uint32_t* n_blocks_out, uint32_t* n_failed_out)
+{
+    const char* who = "rts_cube_cancel_info";
+    CHECK_HANDLE(c);
+    const RtsPassiveState& s = c->cube.passive;
+    if (!c->cube.set || !s.cancel_valid) { rts_set_error("%s: no cancellation (rts_cube_cancel; its record ends at rts_cube_attach)", who); return RTS_ERR_INVALID; }
+    if (!n_blocks_out && !n_failed_out) { rts_set_error("%s: null outputs", who); return RTS_ERR_INVALID; }
+    if (n_failed_out) {
+        std::vector<uint32_t> fail(s.n_blocks);
+        RTS_HIP(hipStreamSynchronize(c->stream));
+        RTS_HIP(hipMemcpy(fail.data(), s.d_fail.p, sizeof(uint32_t) * s.n_blocks, hipMemcpyDeviceToHost));
+        uint32_t n = 0; for (uint32_t f : fail) n += f != 0u;
+        *n_failed_out = n;
+    }
+    if (n_blocks_out) *n_blocks_out = s.n_blocks;
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_cancel_coeffs_get(RtsHandle c, double* host_out, uint64_t capacity_doubles)
+{
+    CHECK_HANDLE(c);
+    const RtsPassiveState& s = c->cube.passive;
+    return rts_cube_copy_out(c, "rts_cube_cancel_coeffs_get", "no cancellation (rts_cube_cancel; its coefficients end at rts_cube_attach) / null output", s.cancel_valid, s.d_coeff.p,
+                             2 * (size_t)s.n_rx * s.n_blocks * s.n_taps, host_out, capacity_doubles);
+}
+
+extern "C" int rts_cube_xcorr(RtsHandle c, const RtsXcorrParams* p, void* device_out)
+{
+    const char* who = "rts_cube_xcorr";
+    CHECK_HANDLE(c);
+    NEED_CUBE(c, who, "no cube (call rts_cube_attach first)");
+    const RtsCubeParams& q = c->cube.params;
+    RtsXcorrPlan plan;
+    RTS_TRY(rts_xcorr_check(p, q, who, &plan));
+    if ((uintptr_t)device_out & 15u) { rts_set_error("%s: device_out is not 16-byte aligned", who); return RTS_ERR_INVALID; }
+    if ((uintptr_t)c->cube.p & 15u) { rts_set_error("%s: the cube's device memory is not 16-byte aligned", who); return RTS_ERR_INVALID; }
+    const uint64_t rx_stride = (uint64_t)q.n_pulses * q.n_bins;
+    RTS_TRY(rts_output_apart_check(who, "%s: device_out overlaps receiver %u of the cube: the correlation is not in place", device_out, plan.out_doubles, c->cube.p, rx_stride,
+                                   (uint64_t)p->first_pulse * q.n_bins, (uint64_t)(p->first_pulse + p->n_pulses) * q.n_bins, q.n_rx));
+    CHECK_CLOSED(c);
+    double* out; RTS_HIP(c->cube.passive.xcorr.place(device_out, plan.out_doubles, &out));
+    RTS_TRY(rts_cube_xcorr_device(c, *p, plan, out));
+    if (!device_out) c->cube.passive.xcorr.record(out, plan.out_doubles);      // (once the launch is enqueued: a failed one leaves no product over unwritten memory)
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_xcorr_get(RtsHandle c, double* host_out, uint64_t capacity_doubles)
+{
+    CHECK_HANDLE(c);
+    return rts_cube_copy_out(c, "rts_cube_xcorr_get", "no library-owned correlation (rts_cube_xcorr with device_out NULL; a correlation ends at rts_cube_attach) / null output", c->cube.passive.xcorr, host_out, capacity_doubles);
 }
 
 // ------------------------------------------------------------------------------------- receiver noise

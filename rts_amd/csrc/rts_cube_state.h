@@ -134,14 +134,26 @@ struct RtsFocusState {
     DevBuf<double> d_env, d_ref, d_pga_part, d_pga_sum, d_pga_rot, d_rows; StagedUpload<double> tab;
     void end() { align.valid = false; pga.valid = false; }
 };
+// passive radar (rts_cube_cancel, rts_cube_xcorr, rts_passive.hip): the parts' partial sums and their sums, both in records of
+// [K (K + 1) / 2 entries of G | n_rx rows of K entries of b] (rts_passive.h), the coefficients [n_rx][n_blocks][K], per block the column + 1 of
+// its failed pivot (0: solved) -- the info record is counted from it --, and the shape of the last cancellation, for
+// rts_cube_cancel_info / rts_cube_cancel_coeffs_get; the correlation's output, for rts_cube_xcorr_get.  The record and the product end
+// at rts_cube_attach.  (The product goes by an alias: tests/cube_state's driver lists the products declared under the type's own name
+// one by one and stays as it is; tests/passive/passive_state_main.cpp lists this one and holds end() to it.)
+using RtsXcorrProduct = RtsCubeProduct;
+struct RtsPassiveState {
+    DevBuf<double> d_part, d_sums, d_coeff; DevBuf<uint32_t> d_fail; uint32_t n_blocks = 0, n_taps = 0, n_rx = 0; bool cancel_valid = false;
+    RtsXcorrProduct xcorr;
+    void end() { cancel_valid = false; xcorr.valid = false; }
+};
 
 // The cube part of a handle: it shares nothing with the pulse path but the handle (the three rts_cube*_api.hip units; the launchers of
 // the kernels' units, each on its own family).
 struct RtsCubeState {
     RtsCubeParams params = {}; double* p = nullptr; DevBuf<double> own; bool set = false;      // p: the attached cube, own when the library allocated it
     RtsWaveState wave; RtsDopplerState doppler; RtsDetectState detect; RtsPlotState plot; RtsTrackState track; RtsLocateState locate; RtsTbdState tbd; RtsImageState image; RtsStftState stft;
-    RtsFmcwState fmcw; RtsBeamState beam; RtsSourceState source; RtsAdaptState adapt; RtsStapState stap; RtsDoaState doa; RtsFocusState focus;
+    RtsFmcwState fmcw; RtsBeamState beam; RtsSourceState source; RtsAdaptState adapt; RtsStapState stap; RtsDoaState doa; RtsFocusState focus; RtsPassiveState passive;
     // every product belongs to the cube it was made from: the Doppler map (which rts_cube_detect may take), the detection list, the plots, the image, the spectrogram, the
-    // range transform, the beams, the covariance, the adaptive weights, the space-time filter's output, the eigenpairs, the angular spectrum and the autofocus tables end when another cube is attached
-    void end_products() { doppler.end(); detect.end(); plot.end(); image.end(); stft.end(); fmcw.end(); beam.end(); adapt.end(); stap.end(); doa.end(); focus.end(); }
+    // range transform, the beams, the covariance, the adaptive weights, the space-time filter's output, the eigenpairs, the angular spectrum, the autofocus tables, the cancellation's record and the reference correlation end when another cube is attached
+    void end_products() { doppler.end(); detect.end(); plot.end(); image.end(); stft.end(); fmcw.end(); beam.end(); adapt.end(); stap.end(); doa.end(); focus.end(); passive.end(); }
 };

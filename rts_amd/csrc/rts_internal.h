@@ -21,6 +21,7 @@
 #include "rts_stap.h"             // space-time adaptive processing: the stacked snapshot, its covariance's and filter's evaluators, the host-only plan of the filter's launch
 #include "rts_doa.h"              // direction finding: the eigensolver's and the angular scan's trees, the spectra's weights, the source count, their evaluators and the host-only plans of their launches
 #include "rts_cfar_os.h"          // CFAR: what every detector shares (rts_cfar.h: window, training count, local maximum, refinement, record); OS: rank rule, alphas, the host evaluator
+#include "rts_passive.h"          // passive radar: the lagged read, the Gram and cross sums' partition, the failed-block rule, the subtraction, the correlation's tree, the rules, the plans, the host evaluators
 #include "rts_locate.h"           // multistatic localisation: the closed form of a triple, completion, refinement, cost, the resolution's order, the validation, the host evaluator
 #include "rts_track.h"            // the tracker step: wrap, prediction, d2, the edge, the candidate order, update, coast, start, the validation, the host evaluator
 #include "rts_tbd.h"              // track-before-detect: the shift table, the score, the window's first maximum, the candidate, the walk, the record, the validation, the host evaluators
@@ -101,6 +102,7 @@ static_assert(sizeof(RtsEndRecord) == 112, "end record size");
 static_assert(sizeof(RtsDetection) == 72 && sizeof(RtsCfarParams) == 72 && sizeof(RtsCfarOsParams) == 72, "CFAR ABI sizes (rts_amd/_lib.py mirrors them)");
 static_assert(sizeof(RtsPlot) == 104 && sizeof(RtsPlotParams) == 56, "plot ABI sizes (rts_amd/_lib.py mirrors them)");
 static_assert(sizeof(RtsTrack) == 88 && sizeof(RtsTrackParams) == 96, "track ABI sizes (rts_amd/_lib.py mirrors them)");
+static_assert(sizeof(RtsCancelParams) == 56 && sizeof(RtsXcorrParams) == 40, "passive ABI sizes (rts_amd/_lib.py mirrors them)");
 static_assert(sizeof(RtsTarget) == 144 && sizeof(RtsLocateParams) == 192, "locate ABI sizes (rts_amd/_lib.py mirrors them)");
 static_assert(sizeof(RtsTbdParams) == 72 && sizeof(RtsTbdExtractParams) == 40 && sizeof(RtsTbdTrack) == 48, "track-before-detect ABI sizes (rts_amd/_lib.py mirrors them)");
 static_assert(sizeof(RtsSourceParams) == 72, "source ABI size (rts_amd/_lib.py mirrors it)");
@@ -456,6 +458,9 @@ int rts_cube_sources_device(RtsContext* c, const RtsSrcPlan& plan, uint32_t K, b
 int rts_cube_beam_device(RtsContext* c, const RtsBeamParams& p, const RtsBeamPlan& plan, const double* in, uint64_t rx_stride, const double* weights, void* out);      // rts_beam.hip
 int rts_cube_cov_device(RtsContext* c, const RtsCovSet& set, const RtsCovPlan& plan, uint32_t n_taps, const double* in, uint64_t rx_stride, double* part, double* out);      // rts_adapt.hip
 int rts_cube_mvdr_device(RtsContext* c, const RtsMvdrPlan& plan, uint32_t n_rx, uint32_t n_beams, double loading, const double* cov, const double* steering, uint32_t* status, double* out);
+// rts_passive.hip.  mask: the receivers cancelled (resolved); the state's buffers exist
+int rts_cube_cancel_device(RtsContext* c, const RtsCancelParams& p, const RtsCancelPlan& plan, uint64_t mask);
+int rts_cube_xcorr_device(RtsContext* c, const RtsXcorrParams& p, const RtsXcorrPlan& plan, double* out);
 int rts_cube_st_apply_device(RtsContext* c, const RtsStApplyParams& p, const RtsStApplyPlan& plan, const double* in, uint64_t rx_stride, const double* weights, void* out);      // rts_stap.hip
 int rts_cube_eig_device(RtsContext* c, const RtsEigPlan& plan, uint32_t n, const double* cov, uint32_t* status, double* values, double* vectors);      // rts_doa.hip
 int rts_cube_doa_scan_device(RtsContext* c, const RtsDoaScanPlan& plan, uint32_t n, uint32_t m, uint64_t n_dirs, uint32_t flags, const double* steering, const double* vectors,
