@@ -1855,6 +1855,55 @@ int rts_cube_xcorr(RtsHandle h, const RtsXcorrParams* p, void* device_out);     
 int rts_cube_xcorr_get(RtsHandle h, double* host_out, uint64_t capacity_doubles);
 int rts_xcorr_eval(const RtsCubeParams* q, const double* cube, const RtsXcorrParams* p, double* out);                        /* pure host */
 
+/* ---------------------------------------------------------------- MIMO radar: the matched-filter bank, to a virtual-array cube
+ * Several transmitters, each with its own waveform, render into ONE cube (rts_cube_render adds; handles may share a cube).  The bank
+ * takes them apart again: one matched filter per transmit waveform on every receive row.  Its output is a cube of n_waves * n_rx
+ * VIRTUAL elements -- element t * n_rx + r is what receiver r heard of transmitter t, and for a far target it is the sample of a
+ * physical element at rx_position[r] + tx_offset[t] -- which the array families (beamformer, covariance, MVDR, STAP, eigensolver,
+ * angular scan) take as it stands once it is attached as a cube of n_waves * n_rx receivers.
+ * For waveform t (samples s_t[0 .. M_t - 1]), receiver r, pulse p of the call's row range and bin n:
+ *     z[n]                            = sum over m = 0 .. M_t - 1, ascending, of  y[r][p][n + m] (x) conj(s_t[m])
+ *     out[t * n_rx + r][p - first][n] = conj(code[t][p - first]) (x) z[n]          (code NULL: z[n] itself, no multiply formed)
+ *   The tree is rts_cube_compress's: the sums start at +0.0; a term with n + m >= n_bins is not formed; per term
+ *   zr += yr sr + yi si and zi += yi sr - yr si, every operation rounded on its own (the library builds with -ffp-contract=off; no
+ *   MFMA); the code multiply is (cr zr + ci zi, cr zi - ci zr).  The arithmetic is rts_amd/csrc/rts_mimo.h, shared by the kernel
+ *   (rts_mimo.hip) and rts_bank_eval: device and evaluator agree BIT FOR BIT, whatever the kernel's tiling.
+ *   Output: out of place, complex128 [n_waves * n_rx][n_pulses of the call][n_bins], into device_out (caller-owned device memory,
+ *   16-byte aligned, apart from the rows the call reads) or, with NULL, library-owned memory that rts_cube_bank_get copies; that
+ *   product ends at rts_cube_attach.  The cube is not changed.  Attaching the output ends the handle's products, so an output that is
+ *   to be attached must be caller-owned.
+ *   code: an optional HOST table [n_waves][n_pulses of the call] of complex128, the slow-time code of each transmitter (TDM: zeros and
+ *   ones; DDMA: a phase ramp per transmitter), finite.  A zero entry gives a row of zeros by the same multiply, not by a skip.  The
+ *   render side has no slow-time code: the caller renders transmitter t at pulse p with the waveform code[t][p] * s_t.
+ *   waves: n_waves records (1 .. RTS_BANK_MAX_WAVES) that each pass rts_cube_set_waveform's rule; `taps` is validated and not
+ *   used; the waveforms of one set may differ in length.  The samples and the code table are copied before the call returns.
+ *   Limits: the output holds at most RTS_BANK_MAX_CELLS cells (its size is formed without a product that could wrap); the launch
+ *   has at most 2^31 - 1 workgroups.  n_bins is NOT bounded by a workgroup's LDS (a workgroup stages RTS_BANK_TILE + max M - 1
+ *   samples of a row, at most 73 984 bytes), nor is n_waves.  The bank does not bound n_waves * n_rx either; RTS_BEAM_MAX_RX
+ *   bounds what the array families accept afterwards.
+ *   Not here: FFT-based fast convolution (a different tree), the design of waveform sets, Doppler-tolerant banks.
+ * The call is enqueued on the handle's stream and never waits for the device's earlier work.
+ * RTS_ERR_INVALID, the message naming the field: no cube attached; NULL p; (1) nonzero reserved fields; (2) n_waves outside
+ *   1 .. RTS_BANK_MAX_WAVES; (3) NULL waves; a waveform that rts_cube_set_waveform would refuse; (4) a span of no pulse or outside
+ *   the cube; (5) a code entry that is not finite; (6) an output beyond RTS_BANK_MAX_CELLS cells or a launch beyond 2^31 - 1
+ *   workgroups; a cube or a device_out that is not 16-byte aligned; a device_out that overlaps the rows the call reads.  The getter:
+ *   nothing to return (no call with device_out NULL yet, or an rts_cube_attach since), a NULL output; RTS_ERR_CAPACITY when the
+ *   capacity is too small.  A refused call leaves the output and the handle's products as they were.
+ * rts_bank_eval: pure host, no device: the same rts_mimo.h functions on a host array of the cube's layout, q its shape. */
+#define RTS_BANK_MAX_WAVES 16u
+#define RTS_BANK_TILE      512u             /* output bins per workgroup                                                    */
+#define RTS_BANK_MAX_CELLS 549755813888ull  /* 2^39 complex128 of output: what a flat launch of the beamformer may write    */
+typedef struct RtsBankParams {
+    const RtsWaveform* waves;        /* [n_waves]                                                                    */
+    uint32_t n_waves;                /* 1 .. RTS_BANK_MAX_WAVES                                                      */
+    const double* code;              /* NULL, or host [n_waves][n_pulses] interleaved re / im, finite                */
+    uint32_t first_pulse, n_pulses;  /* the span: at least one pulse                                                 */
+    uint64_t reserved[2];            /* 0 */
+} RtsBankParams;                                              /* 48 bytes */
+int rts_cube_bank(RtsHandle h, const RtsBankParams* p, void* device_out);                   /* complex128 [n_waves * n_rx][n_pulses][n_bins] */
+int rts_cube_bank_get(RtsHandle h, double* host_out, uint64_t capacity_doubles);
+int rts_bank_eval(const RtsCubeParams* q, const double* cube, const RtsBankParams* p, double* out);                          /* pure host */
+
 /* ---------------------------------------------------------------- several GPUs (not in the reference: it is single-GPU)
  * Rays are independent (each launch index writes only its own rows, ray_tracer.cu:227-253) and so are pulses
  * (ray_tracer.cpp:843).  rts_plan_cpi deals the n_pulses x total_rays (pulse, launch index) pairs of one coherent

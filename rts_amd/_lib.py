@@ -335,6 +335,18 @@ class RtsXcorrParams(C.Structure):
 assert C.sizeof(RtsCancelParams) == 56 and C.sizeof(RtsXcorrParams) == 40
 
 
+# MIMO radar: the matched-filter bank (include/rts_amd.h)
+RTS_BANK_MAX_WAVES, RTS_BANK_TILE, RTS_BANK_MAX_CELLS = 16, 512, 1 << 39
+
+
+class RtsBankParams(C.Structure):
+    _fields_ = [("waves", C.POINTER(RtsWaveform)), ("n_waves", C.c_uint32), ("code", C.c_void_p), ("first_pulse", C.c_uint32), ("n_pulses", C.c_uint32),
+                ("reserved", C.c_uint64 * 2)]
+
+
+assert C.sizeof(RtsBankParams) == 48
+
+
 RTS_ST_MAX_TAPS = 16
 
 
@@ -472,7 +484,8 @@ EXPORTS = ["rts_create", "rts_destroy", "rts_last_error", "rts_device_count", "r
            "rts_cube_covariance", "rts_cube_covariance_get", "rts_covariance_eval", "rts_cube_mvdr", "rts_cube_mvdr_get", "rts_mvdr_eval",
            "rts_cube_st_covariance", "rts_st_covariance_eval", "rts_cube_st_apply", "rts_cube_st_get", "rts_st_apply_eval", "rts_st_steering_make",
            "rts_cube_eig", "rts_cube_eig_get", "rts_eig_eval", "rts_cube_doa_scan", "rts_cube_doa_get", "rts_doa_scan_eval", "rts_doa_weights", "rts_source_count",
-           "rts_cube_cancel", "rts_cube_cancel_info", "rts_cube_cancel_coeffs_get", "rts_cancel_eval", "rts_cube_xcorr", "rts_cube_xcorr_get", "rts_xcorr_eval"]
+           "rts_cube_cancel", "rts_cube_cancel_info", "rts_cube_cancel_coeffs_get", "rts_cancel_eval", "rts_cube_xcorr", "rts_cube_xcorr_get", "rts_xcorr_eval",
+           "rts_cube_bank", "rts_cube_bank_get", "rts_bank_eval"]
 
 
 def lib():
@@ -610,6 +623,9 @@ def lib():
         "rts_cube_xcorr": [vp, C.POINTER(RtsXcorrParams), vp],
         "rts_cube_xcorr_get": [vp, vp, u64],
         "rts_xcorr_eval": [C.POINTER(RtsCubeParams), vp, C.POINTER(RtsXcorrParams), vp],
+        "rts_cube_bank": [vp, C.POINTER(RtsBankParams), vp],
+        "rts_cube_bank_get": [vp, vp, u64],
+        "rts_bank_eval": [C.POINTER(RtsCubeParams), vp, C.POINTER(RtsBankParams), vp],
         "rts_cube_st_covariance": [vp, C.POINTER(RtsStCovParams), vp],
         "rts_st_covariance_eval": [C.POINTER(RtsCubeParams), vp, u32, C.POINTER(RtsStCovParams), vp],
         "rts_cube_st_apply": [vp, C.POINTER(RtsStApplyParams), vp],

@@ -172,6 +172,15 @@ class Waveform:
         m = np.arange(n, dtype=np.float64) - (n - 1) / 2.0
         return cls(np.exp(1j * np.pi * float(bandwidth_times_dt) * m * m / n), taps)
 
+    @classmethod
+    def coded(cls, chips, samples_per_chip=1, taps=16):
+        """phase-coded waveform: every chip (a complex value: +1 / -1 of a binary code, a polyphase code's phasors) held for
+        samples_per_chip samples -- the waveforms of a coded MIMO set (cube_bank) are the rows of one code family"""
+        c = np.asarray(chips, np.complex128).ravel()
+        if int(samples_per_chip) < 1:
+            raise ValueError("Waveform.coded: samples_per_chip = %d" % samples_per_chip)
+        return cls(np.repeat(c, int(samples_per_chip)), taps)
+
     def desc(self):
         d = L.RtsWaveform()
         d.samples, d.n_samples, d.taps = ptr(self._iq), len(self.samples), self.taps
@@ -870,6 +879,50 @@ def xcorr_eval(cube, ref_rx, n_lags, first_lag=0, first=0, count=None):
     return out
 
 
+def _bank_params(waves, code, first, count, n_pulses_cube):
+    """RtsBankParams and what it points to (keep it alive for the call)"""
+    ws = [w for w in waves]
+    descs = (L.RtsWaveform * max(len(ws), 1))()
+    for i, w in enumerate(ws):
+        d = _waveform_desc(w)
+        descs[i].samples, descs[i].n_samples, descs[i].taps = d.samples, d.n_samples, d.taps
+        descs[i].reserved[0], descs[i].reserved[1] = d.reserved[0], d.reserved[1]
+    p = L.RtsBankParams()
+    p.waves, p.n_waves, p.first_pulse = descs, len(ws), int(first)
+    p.n_pulses = int(n_pulses_cube - first if count is None else count)
+    keep = [ws, descs]
+    if code is not None:
+        c = np.ascontiguousarray(np.asarray(code, np.complex128))
+        if c.shape != (len(ws), p.n_pulses):
+            raise ValueError("bank: code of shape %s for %d waveforms x %d pulses" % (c.shape, len(ws), p.n_pulses))
+        keep.append(c)
+        p.code = ptr(c.view(np.float64))
+    return p, keep
+
+
+def bank_eval(cube, waves, code=None, first=0, count=None):
+    """rts_bank_eval (pure host): the matched-filter bank of a host cube [n_rx][n_pulses][n_bins] (complex) -- every row of rows
+    first .. first + count - 1 of every receiver correlated with each of the waveforms (Waveform or RtsWaveform), then multiplied by
+    conj(code[t][p]) (code complex [n_waves][count], None: no multiply): complex [n_waves * n_rx][count][n_bins], virtual element
+    t * n_rx + r"""
+    cube = np.ascontiguousarray(np.asarray(cube, np.complex128))
+    n_rx, n_p, nb = cube.shape
+    q = L.RtsCubeParams(n_rx, n_p, nb, 0, 0.0, 1.0)
+    p, keep = _bank_params(waves, code, first, count, n_p)
+    out = np.zeros((max(p.n_waves, 1) * n_rx, max(p.n_pulses, 1), nb), np.complex128)
+    check(L.lib().rts_bank_eval(C.byref(q), ptr(cube.view(np.float64)), C.byref(p), ptr(out.view(np.float64))))
+    return out
+
+
+def virtual_positions(tx_offsets, rx_positions):
+    """the positions [n_tx * n_rx][3] of the virtual elements of a MIMO array in the bank's element order (t * n_rx + r):
+    rx_positions[r] + tx_offsets[t] -- for a far target the echo of transmitter t on receiver r has the phase of one element there.
+    The steering table of the virtual cube is steering(virtual_positions(...), ...)"""
+    tx = np.asarray(tx_offsets, np.float64).reshape(-1, 3)
+    rx = np.asarray(rx_positions, np.float64).reshape(-1, 3)
+    return (tx[:, None, :] + rx[None, :, :]).reshape(-1, 3)
+
+
 def eig_eval(cov, sweeps=False):
     """rts_eig_eval (pure host): the eigenpairs of a Hermitian matrix complex [n][n] (its lower triangle and the real part of its
     diagonal are read) by one-sided Jacobi: (eigenvalues float64 [n] in descending order, eigenvectors complex [n][n], ROW k the
@@ -1532,6 +1585,26 @@ class Tracer:
         if count is None:
             count = self._cube_shape[1] - first
         check(L.lib().rts_cube_compress(self.h, first, count))
+
+    def cube_bank(self, waves, code=None, first=0, count=None, device_ptr=None, fetch=True):
+        """rts_cube_bank: the matched-filter bank -- every row of rows first .. first + count - 1 (default: to the last pulse) of every
+        receiver of the attached cube correlated with each of the waveforms (one per transmitter that was rendered into the cube),
+        then multiplied by conj(code[t][p]) (code complex [n_waves][count], None: no multiply): complex [n_waves * n_rx][count][n_bins],
+        virtual element t * n_rx + r, into a caller complex128 device tensor (device_ptr; nothing is fetched) or the library's output,
+        returned when fetch.  The cube is not changed.  Attached as a cube of n_waves * n_rx receivers (a caller-owned output: the
+        attach ends the library's), the array methods run on the virtual array (virtual_positions)"""
+        p, keep = _bank_params(waves, code, first, count, self._cube_shape[1])
+        check(L.lib().rts_cube_bank(self.h, C.byref(p), C.c_void_p(device_ptr) if device_ptr else None))
+        if device_ptr:
+            return None
+        self._bank_shape = (p.n_waves * self._cube_shape[0], p.n_pulses, self._cube_shape[2])
+        return self.bank_map() if fetch else None
+
+    def bank_map(self):
+        """rts_cube_bank_get: the library-owned output of the last cube_bank, complex [n_waves * n_rx][count][n_bins]"""
+        out = np.zeros(getattr(self, "_bank_shape", None) or (1, 1, 1), np.complex128)
+        check(L.lib().rts_cube_bank_get(self.h, ptr(out.view(np.float64)), 2 * out.size))
+        return out
 
     def cube_cancel(self, ref_rx, n_taps, rows_per_block=0, first=0, count=None, rx=None, loading=0.0):
         """rts_cube_cancel: batch ECA in place on the attached cube -- per block of rows_per_block rows (0: the whole span) of rows

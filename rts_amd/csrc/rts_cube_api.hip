@@ -1,5 +1,5 @@
 // rts_cube_api.hip -- the cube part of the C-ABI of include/rts_amd.h, first of three host units: the cube and the signal in it -- attach, accumulate,
-// Doppler and get; waveform, render, compress; passive cancellation and cross-correlation; noise; clutter and jammer sources; spectrogram; autofocus; FMCW; backprojection -- and the pure-host evaluators
+// Doppler and get; waveform, render, compress; the MIMO matched-filter bank; passive cancellation and cross-correlation; noise; clutter and jammer sources; spectrogram; autofocus; FMCW; backprojection -- and the pure-host evaluators
 // that go with them (rts_cube_reduce apart: rts_api.hip; the detection chain: rts_cube_detect_api.hip; the receive array: rts_cube_array_api.hip).
 // Host code only, no kernels: argument checks, the handle's cube state (RtsCubeState, rts_cube_state.h), the calls of the launchers in the kernels' units.
 #include <cmath>
@@ -138,6 +138,76 @@ extern "C" int rts_cube_compress(RtsHandle c, uint32_t first_pulse, uint32_t n_p
     RTS_TRY(rts_pulses_check("rts_cube_compress", first_pulse, n_pulses, q.n_pulses, false));
     if (q.n_bins > RTS_COMPRESS_MAX_BINS) { rts_set_error("rts_cube_compress: %u range bins > %u (RTS_COMPRESS_MAX_BINS: one row of complex128 in a workgroup's LDS)", q.n_bins, RTS_COMPRESS_MAX_BINS); return RTS_ERR_INVALID; }
     return rts_cube_compress_device(c, first_pulse, n_pulses);
+}
+
+// ------------------------------------------------------------------------------------- MIMO radar: the matched-filter bank
+// (rts_amd.h: RtsBankParams; the rule, the plan and the host evaluator are rts_mimo.h, shared with the kernel, rts_mimo.hip; each
+// waveform passes rts_waveform_check, the one statement of the RtsWaveform rule)
+static int rts_bank_check(const RtsBankParams* p, const RtsCubeParams& q, const char* who, uint32_t* M, RtsBankPlan* plan)
+{
+    if (!p) { rts_set_error("%s: null parameters", who); return RTS_ERR_INVALID; }
+    const int rule = rts_bank_rule(p, q.n_pulses);
+    if (rule == 1) { rts_set_error("%s: reserved fields must be 0", who); return RTS_ERR_INVALID; }
+    if (rule == 2) { rts_set_error("%s: n_waves = %u (1 .. %u, RTS_BANK_MAX_WAVES)", who, p->n_waves, RTS_BANK_MAX_WAVES); return RTS_ERR_INVALID; }
+    if (rule == 3) { rts_set_error("%s: null waves", who); return RTS_ERR_INVALID; }
+    for (uint32_t t = 0; t < p->n_waves; t++) {
+        char name[64]; snprintf(name, sizeof(name), "%s: waves[%u]", who, t);
+        RTS_TRY(rts_waveform_check(&p->waves[t], name));
+        M[t] = p->waves[t].n_samples;
+    }
+    if (rule == 4) return rts_pulses_check(who, p->first_pulse, p->n_pulses, q.n_pulses, true);
+    const int64_t bad = rts_bank_code_bad(p->code, p->n_waves, p->n_pulses);
+    if (bad >= 0) { rts_set_error("%s: code[%u][%u] is not finite", who, (uint32_t)(bad / 2 / p->n_pulses), (uint32_t)(bad / 2 % p->n_pulses)); return RTS_ERR_INVALID; }
+    *plan = rts_bank_plan(q.n_rx, p->n_pulses, q.n_bins, p->n_waves, M, p->code != nullptr);
+    if (!plan->supported) {
+        rts_set_error("%s: an output of %u waveforms x %u receivers x %u rows x %u bins: more than %llu cells (RTS_BANK_MAX_CELLS) or than %u workgroups", who, p->n_waves, q.n_rx, p->n_pulses,
+                      q.n_bins, (unsigned long long)RTS_BANK_MAX_CELLS, RTS_MIMO_MAX_GRID);
+        return RTS_ERR_INVALID;
+    }
+    return RTS_OK;
+}
+
+extern "C" int rts_bank_eval(const RtsCubeParams* q, const double* cube, const RtsBankParams* p, double* out)
+{
+    const char* who = "rts_bank_eval";
+    RTS_TRY(rts_eval_cube_check(who, q, true, false));
+    uint32_t M[RTS_BANK_MAX_WAVES]; RtsBankPlan plan;
+    RTS_TRY(rts_bank_check(p, *q, who, M, &plan));
+    if (!cube || !out) { rts_set_error("%s: null cube or output array", who); return RTS_ERR_INVALID; }
+    rts_bank_eval_host(q, cube, p, out);
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_bank(RtsHandle c, const RtsBankParams* p, void* device_out)
+{
+    const char* who = "rts_cube_bank";
+    CHECK_HANDLE(c);
+    NEED_CUBE(c, who, "no cube (call rts_cube_attach first)");
+    const RtsCubeParams& q = c->cube.params;
+    uint32_t M[RTS_BANK_MAX_WAVES]; RtsBankPlan plan;
+    RTS_TRY(rts_bank_check(p, q, who, M, &plan));
+    if ((uintptr_t)device_out & 15u) { rts_set_error("%s: device_out is not 16-byte aligned", who); return RTS_ERR_INVALID; }
+    if ((uintptr_t)c->cube.p & 15u) { rts_set_error("%s: the cube's device memory is not 16-byte aligned", who); return RTS_ERR_INVALID; }
+    RTS_TRY(rts_output_apart_check(who, "%s: device_out overlaps receiver %u of the cube: the bank is not in place", device_out, plan.out_doubles, c->cube.p, (uint64_t)q.n_pulses * q.n_bins,
+                                   (uint64_t)p->first_pulse * q.n_bins, (uint64_t)(p->first_pulse + p->n_pulses) * q.n_bins, q.n_rx));
+    CHECK_CLOSED(c);
+    RtsMimoState& s = c->cube.mimo;
+    double* out; RTS_HIP(s.out.place(device_out, plan.out_doubles, &out));
+    // the waveforms' samples and the code table -> pinned staging -> the device, on the stream; a smaller set reuses both blocks
+    double* h = nullptr;
+    RTS_HIP(s.tab.begin(plan.tab_doubles, plan.tab_doubles, plan.tab_doubles, &h));
+    for (uint32_t t = 0; t < p->n_waves; t++) memcpy(h + plan.off[t], p->waves[t].samples, sizeof(double) * 2 * M[t]);
+    if (p->code) memcpy(h + plan.code_off, p->code, sizeof(double) * 2 * (size_t)p->n_waves * p->n_pulses);
+    RTS_HIP(s.tab.send(plan.tab_doubles, c->stream));
+    RTS_TRY(rts_cube_bank_device(c, *p, plan, M, s.tab.dev.p, p->code != nullptr, out));
+    if (!device_out) s.out.record(out, plan.out_doubles);      // (once the launch is enqueued: a failed one leaves no product over unwritten memory)
+    return RTS_OK;
+}
+
+extern "C" int rts_cube_bank_get(RtsHandle c, double* host_out, uint64_t capacity_doubles)
+{
+    CHECK_HANDLE(c);
+    return rts_cube_copy_out(c, "rts_cube_bank_get", "no library-owned bank output (rts_cube_bank with device_out NULL; it ends at rts_cube_attach) / null output", c->cube.mimo.out, host_out, capacity_doubles);
 }
 
 // ------------------------------------------------------------------------------------- passive radar: reference-channel cancellation, cross-correlation

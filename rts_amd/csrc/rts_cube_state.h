@@ -146,14 +146,19 @@ struct RtsPassiveState {
     RtsXcorrProduct xcorr;
     void end() { cancel_valid = false; xcorr.valid = false; }
 };
+// MIMO radar (rts_cube_bank, rts_mimo.hip): the call's table [the waveforms' samples, one after another | the code table] goes through a
+// staged upload; the bank's output, for rts_cube_bank_get.  The product ends at rts_cube_attach.  (Declared through an alias, as the
+// correlation's: tests/mimo/mimo_state_main.cpp lists this one and holds end() to it.)
+using RtsBankProduct = RtsCubeProduct;
+struct RtsMimoState { StagedUpload<double> tab; RtsBankProduct out; void end() { out.valid = false; } };
 
 // The cube part of a handle: it shares nothing with the pulse path but the handle (the three rts_cube*_api.hip units; the launchers of
 // the kernels' units, each on its own family).
 struct RtsCubeState {
     RtsCubeParams params = {}; double* p = nullptr; DevBuf<double> own; bool set = false;      // p: the attached cube, own when the library allocated it
     RtsWaveState wave; RtsDopplerState doppler; RtsDetectState detect; RtsPlotState plot; RtsTrackState track; RtsLocateState locate; RtsTbdState tbd; RtsImageState image; RtsStftState stft;
-    RtsFmcwState fmcw; RtsBeamState beam; RtsSourceState source; RtsAdaptState adapt; RtsStapState stap; RtsDoaState doa; RtsFocusState focus; RtsPassiveState passive;
+    RtsFmcwState fmcw; RtsBeamState beam; RtsSourceState source; RtsAdaptState adapt; RtsStapState stap; RtsDoaState doa; RtsFocusState focus; RtsPassiveState passive; RtsMimoState mimo;
     // every product belongs to the cube it was made from: the Doppler map (which rts_cube_detect may take), the detection list, the plots, the image, the spectrogram, the
-    // range transform, the beams, the covariance, the adaptive weights, the space-time filter's output, the eigenpairs, the angular spectrum, the autofocus tables, the cancellation's record and the reference correlation end when another cube is attached
-    void end_products() { doppler.end(); detect.end(); plot.end(); image.end(); stft.end(); fmcw.end(); beam.end(); adapt.end(); stap.end(); doa.end(); focus.end(); passive.end(); }
+    // range transform, the beams, the covariance, the adaptive weights, the space-time filter's output, the eigenpairs, the angular spectrum, the autofocus tables, the cancellation's record, the reference correlation and the bank's output end when another cube is attached
+    void end_products() { doppler.end(); detect.end(); plot.end(); image.end(); stft.end(); fmcw.end(); beam.end(); adapt.end(); stap.end(); doa.end(); focus.end(); passive.end(); mimo.end(); }
 };

@@ -22,6 +22,7 @@
 #include "rts_doa.h"              // direction finding: the eigensolver's and the angular scan's trees, the spectra's weights, the source count, their evaluators and the host-only plans of their launches
 #include "rts_cfar_os.h"          // CFAR: what every detector shares (rts_cfar.h: window, training count, local maximum, refinement, record); OS: rank rule, alphas, the host evaluator
 #include "rts_passive.h"          // passive radar: the lagged read, the Gram and cross sums' partition, the failed-block rule, the subtraction, the correlation's tree, the rules, the plans, the host evaluators
+#include "rts_mimo.h"             // MIMO radar: the bank's term, its sum's order, the code multiply, the rule, the plan of the launch, the host evaluator
 #include "rts_locate.h"           // multistatic localisation: the closed form of a triple, completion, refinement, cost, the resolution's order, the validation, the host evaluator
 #include "rts_track.h"            // the tracker step: wrap, prediction, d2, the edge, the candidate order, update, coast, start, the validation, the host evaluator
 #include "rts_tbd.h"              // track-before-detect: the shift table, the score, the window's first maximum, the candidate, the walk, the record, the validation, the host evaluators
@@ -103,6 +104,7 @@ static_assert(sizeof(RtsDetection) == 72 && sizeof(RtsCfarParams) == 72 && sizeo
 static_assert(sizeof(RtsPlot) == 104 && sizeof(RtsPlotParams) == 56, "plot ABI sizes (rts_amd/_lib.py mirrors them)");
 static_assert(sizeof(RtsTrack) == 88 && sizeof(RtsTrackParams) == 96, "track ABI sizes (rts_amd/_lib.py mirrors them)");
 static_assert(sizeof(RtsCancelParams) == 56 && sizeof(RtsXcorrParams) == 40, "passive ABI sizes (rts_amd/_lib.py mirrors them)");
+static_assert(sizeof(RtsBankParams) == 48, "bank ABI size (rts_amd/_lib.py mirrors it)");
 static_assert(sizeof(RtsTarget) == 144 && sizeof(RtsLocateParams) == 192, "locate ABI sizes (rts_amd/_lib.py mirrors them)");
 static_assert(sizeof(RtsTbdParams) == 72 && sizeof(RtsTbdExtractParams) == 40 && sizeof(RtsTbdTrack) == 48, "track-before-detect ABI sizes (rts_amd/_lib.py mirrors them)");
 static_assert(sizeof(RtsSourceParams) == 72, "source ABI size (rts_amd/_lib.py mirrors it)");
@@ -461,6 +463,8 @@ int rts_cube_mvdr_device(RtsContext* c, const RtsMvdrPlan& plan, uint32_t n_rx, 
 // rts_passive.hip.  mask: the receivers cancelled (resolved); the state's buffers exist
 int rts_cube_cancel_device(RtsContext* c, const RtsCancelParams& p, const RtsCancelPlan& plan, uint64_t mask);
 int rts_cube_xcorr_device(RtsContext* c, const RtsXcorrParams& p, const RtsXcorrPlan& plan, double* out);
+// rts_mimo.hip.  M: the waveforms' lengths; tab: the staged table on the device (plan.off, plan.code_off); code: it holds a code table
+int rts_cube_bank_device(RtsContext* c, const RtsBankParams& p, const RtsBankPlan& plan, const uint32_t* M, const double* tab, bool code, double* out);
 int rts_cube_st_apply_device(RtsContext* c, const RtsStApplyParams& p, const RtsStApplyPlan& plan, const double* in, uint64_t rx_stride, const double* weights, void* out);      // rts_stap.hip
 int rts_cube_eig_device(RtsContext* c, const RtsEigPlan& plan, uint32_t n, const double* cov, uint32_t* status, double* values, double* vectors);      // rts_doa.hip
 int rts_cube_doa_scan_device(RtsContext* c, const RtsDoaScanPlan& plan, uint32_t n, uint32_t m, uint64_t n_dirs, uint32_t flags, const double* steering, const double* vectors,
